@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the distance hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A "step" is one pass of kernel 1 over the whole synthetic database: all
 self-vs-self core/accessory distances, sketches already resident in HBM,
@@ -105,7 +105,43 @@ def parse():
     ap.add_argument("--even-bands", action="store_true",
                     help="N > 1: keep equal bands (default: re-cut them from measured rates during "
                          "the untimed set-up, so that the root, whose band needs no transfer, takes more)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR as .npy files: a fixed "
+                         "stratified sample of the distance matrix's rows (distances.npy, float32 [m, 2]) and their "
+                         "row numbers in PopPUNK order (distances_rows.npy, float64 [m]); the same arguments give "
+                         "the same inputs, so two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_ROWS = 1 << 21      # 16 MB of float32 distances + 16 MB of float64 row numbers: under the 64 MB a dump may hold
+DUMP_SEED = 20240613
+
+
+def dump_rows(total_rows, m=DUMP_ROWS, seed=DUMP_SEED):
+    """The rows --dump-outputs writes: all of them when there are at most m, else one seeded random row from each of
+    m equal strata (distinct, sorted, spread over the whole matrix, the same for the same total on every run)."""
+    if total_rows <= m:
+        return np.arange(total_rows, dtype=np.int64)
+    edges = np.arange(m + 1, dtype=np.int64) * total_rows // m
+    rng = np.random.Generator(np.random.PCG64(seed))
+    return edges[:-1] + (rng.random(m) * (edges[1:] - edges[:-1])).astype(np.int64)
+
+
+def dump_outputs(out_dir, dist_t, torch):
+    """Rank 0's PopPUNK-ordered [n_pairs, 2] float32 matrix of the last timed step -> out_dir (see --dump-outputs)."""
+    rows = dump_rows(int(dist_t.shape[0]))
+    idx = torch.from_numpy(rows).to(dist_t.device)
+    sample = dist_t.index_select(0, idx).cpu().numpy().astype(np.float32, copy=False)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "distances.npy"), sample)
+    np.save(os.path.join(out_dir, "distances_rows.npy"), rows.astype(np.float64))
+    return {"dir": out_dir, "files": ["distances.npy", "distances_rows.npy"], "rows": int(len(rows)),
+            "of_rows": int(dist_t.shape[0]), "seed": DUMP_SEED}
 
 
 def relaunch_under_torchrun(args):
@@ -1308,6 +1344,8 @@ def build_line(rep):
                            "note": "the band-split leg did not run; host_call: one process, all GPUs (solo_legs)"}
     if value_note:
         line["value_note"] = value_note
+    if f.get("dump_outputs"):
+        line["dump_outputs"] = f["dump_outputs"]
     if world > 1:
         compute_ms = f.get("compute_ms_max")
         mg = {
@@ -1405,6 +1443,7 @@ def main():
         rep.error(rep.phase, e)
     rep.finish()
     rep.emit()
+    dump_failed = bool(args.dump_outputs) and rank == 0 and "dump_outputs" not in rep.fields
     if world > 1:
         try:
             if dist.is_initialized():
@@ -1419,7 +1458,9 @@ def main():
                 t_end = time.time() + max(args.watchdog_s, args.collective_timeout) + 30.0
                 while not os.path.exists(os.path.join(rep.per_rank_dir, "emitted")) and time.time() < t_end:
                     time.sleep(0.05)
-            os._exit(0 if rank == 0 else 1)      # do not hang in atexit handlers of a broken process group
+            os._exit(0 if rank == 0 and not dump_failed else 1)      # do not hang in atexit handlers of a broken process group
+    if dump_failed:
+        sys.exit("bench.py: --dump-outputs %s: nothing written (the line's error says why)" % args.dump_outputs)
 
 
 def run(args, rep, rank, local_rank, world, fake, torch, dist, engine, synth, datetime):
@@ -1706,6 +1747,9 @@ def run(args, rep, rank, local_rank, world, fake, torch, dist, engine, synth, da
     f["elapsed"], f["compute_ms_max"] = elapsed, compute_ms
     f["band_shares"] = [round(b / max(job.total_rows, 1), 4) for b in job.band_rows]
     f["gathered_bytes"] = int(sum(job.band_rows[1:])) * 8
+    if args.dump_outputs and rank == 0:          # job.out: the matrix the last timed step left on rank 0
+        rep.enter("dump_outputs")
+        f["dump_outputs"] = dump_outputs(args.dump_outputs, job.out, torch)
 
     if fake:
         return

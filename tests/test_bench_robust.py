@@ -178,3 +178,41 @@ def test_the_line_takes_the_faster_of_the_two_transports_only_when_the_matrices_
     assert d["value_transport"] == "peer_store" and d["ms_per_step"] == 7.0
     d = line({"available": False, "why": "x"})
     assert d["value_transport"] == "gather" and "not available" in d["value_note"]
+
+
+def test_dump_outputs_writes_the_matrix_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: after the timed steps rank 0 writes what the last one left in its PopPUNK-ordered matrix
+    (FAKE: every rank fills its band with its rank number, so rank 0's rows come first as 0 and rank 1's follow as 1):
+    float32 distances beside their float64 row numbers; 1 124 250 rows are few enough to be written whole."""
+    import numpy as np
+    d = _run(None, ["--dump-outputs", str(tmp_path / "out")])
+    _check_common(d)
+    dist = np.load(str(tmp_path / "out" / "distances.npy"))
+    rows = np.load(str(tmp_path / "out" / "distances_rows.npy"))
+    assert dist.dtype == np.float32 and rows.dtype == np.float64 and dist.shape == (len(rows), 2)
+    assert d["dump_outputs"]["rows"] == d["dump_outputs"]["of_rows"] == d["config"]["pairs"] == len(rows)
+    assert np.array_equal(rows, np.arange(len(rows)))
+    assert np.array_equal(dist[:, 0], dist[:, 1]) and set(np.unique(dist).tolist()) == {0.0, 1.0}
+    assert np.all(np.diff(dist[:, 0]) >= 0)
+    assert abs(float((dist[:, 0] == 0).mean()) - d["multi_gpu"]["band_shares"][0]) < 1e-3
+
+
+def test_dump_rows_are_a_fixed_stratified_sample_within_64_mb(monkeypatch):
+    """The headline matrix (49 995 000 rows, 400 MB) is dumped as one seeded row from each of DUMP_ROWS equal strata:
+    the same rows on every run, distinct and sorted, float32 pairs + float64 row numbers within 64 MB.  --steps sets
+    the timed steps, so it must be at least 1 (ms_per_step divides by it)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 10000 * 9999 // 2
+    r = bench.dump_rows(n)
+    m = bench.DUMP_ROWS
+    assert np.array_equal(r, bench.dump_rows(n)) and r.dtype == np.int64 and len(r) == m
+    edges = np.arange(m + 1, dtype=np.int64) * n // m
+    assert np.all(r >= edges[:-1]) and np.all(r < edges[1:])
+    assert m * (2 * 4 + 8) <= 64 << 20
+    assert np.array_equal(bench.dump_rows(m), np.arange(m)) and len(bench.dump_rows(m + 1)) == m
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse()
