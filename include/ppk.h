@@ -275,6 +275,86 @@ int ppk_qc_edges_dev(const float *d_dist, size_t n_rows, size_t n_ref, int mode,
                      unsigned long long *d_n_edges, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Assignment with a fitted BGMM model (PopPUNK's default --fit-model bgmm; --use-model and poppunk_assign against
+ * such a fit).  Replaces BGMMFit.assign -> assign_samples -> log_likelihood / log_multivariate_normal_density
+ * (PopPUNK/models.py:411-465, :138-192; PopPUNK/bgmm.py:100-176) and, for the edge lists, the
+ * construct_network_from_assignments -> generateTuples that follows it (PopPUNK/__main__.py:643-652,
+ * PopPUNK/network.py:1170-1184; poppunk_assign: PopPUNK/assign.py:600, PopPUNK/network.py:1384,:1425-1433).
+ * Fitting the mixture (sklearn, PopPUNK/bgmm.py:20-70) stays with the caller.
+ * For a row x = (core, accessory):
+ *   xs = x / scale                   in the dtype numpy promotes to (models.py:246-254: PopPUNK's scale is float32,
+ *                                    so float32 / float32; a float64 scale gives a float64 quotient)
+ *   lpr_c = log w_c - 0.5 (|L_c^-1 (xs - mu_c)|^2 + 2 log 2pi + 2 sum log diag L_c)     in float64
+ *   label = argmax_c lpr_c (the first on ties; = argmax of the responsibilities, models.py:181-187)
+ *   resp_c = exp(lpr_c - logsumexp(lpr)) as float32 (values=True, models.py:434-437)
+ * L_c = chol(cov_c), lower; when cov_c is not positive-definite chol(cov_c + 1e-7 I), and when that fails too the
+ * fit is refused (bgmm.py:131-172).
+ * A model has 1 <= K <= PPK_BGMM_MAX_K components.  ppk_bgmm is plain data owned by the caller: the device entry
+ * points take its values at the call (by kernel argument, or one small copy the library makes on the call's stream),
+ * so it may be changed or freed as soon as the call returns. */
+#define PPK_BGMM_MAX_K 16
+typedef struct ppk_bgmm {
+  int K;                          /* components */
+  int within_label;               /* the label whose rows are edges (BGMMFit.within_label, models.py:359-375) */
+  int scale_is_f64;               /* 0: xs = float32(x / scale_f32), 1: xs = double(x) / scale_f64 */
+  int n_jitter;                   /* components that took the 1e-7 fallback (information) */
+  float scale_f32[2];
+  double scale_f64[2];
+  double mean[PPK_BGMM_MAX_K][2];
+  double chol[PPK_BGMM_MAX_K][3];      /* L00, L10, L11 of the (possibly jittered) covariance */
+  double inv_diag[PPK_BGMM_MAX_K][2];  /* 1 / L00, 1 / L11 */
+  double log_const[PPK_BGMM_MAX_K];    /* log w_c - 0.5 (2 log 2pi + 2 sum log diag L_c) */
+  /* what the kernels evaluate: z = L_c^-1 (xs - mu_c) as z0 = xs a0 + b0, z1 = ys p + (z0 q + r), i.e.
+   * {a0, b0, p, q, r} = {1/L00, -mu0/L00, 1/L11, -L10/L11, -mu1/L11}, and lpr_c = log_const - 0.5 (z0^2 + z1^2),
+   * each step one fused multiply-add in double */
+  double lin[PPK_BGMM_MAX_K][5];
+  int jitter[PPK_BGMM_MAX_K];          /* 1 where the 1e-7 fallback was taken */
+} ppk_bgmm;
+
+/* The model as the kernels need it, from the arrays of <prefix>_fit.npz (BGMMFit.load, models.py:359-375): weights
+ * double [K], means double [K][2], covariances double [K][2][2], scale double [2] (the stored values; scale_is_f64
+ * != 0 when the npz holds them as float64).  Host only, no device is touched.  PPK_ERR_ARG for K outside
+ * [1, PPK_BGMM_MAX_K], within_label outside [0, K), a non-positive scale, or a covariance that is not positive-definite
+ * even with 1e-7 on its diagonal (the reference's ValueError). */
+int ppk_bgmm_prepare(int K, const double *weights, const double *means, const double *covariances,
+                     const double *scale, int scale_is_f64, int within_label, ppk_bgmm *out);
+
+/* On a resident [n_rows][2] float32 distance buffer: d_labels int32 [n_rows] (nullable), d_resp float [n_rows][K]
+ * (nullable: labels only, no transcendental is evaluated); at least one of the two. */
+int ppk_bgmm_assign_dev(const float *d_dist, size_t n_rows, const ppk_bgmm *model, int32_t *d_labels,
+                        float *d_resp, void *stream);
+
+/* The rows whose label is model->within_label as an edge list, element for element what ppk_bgmm_assign_dev followed by
+ * ppk_generate_tuples_dev(labels, within_label, n_ref == 0, n_ref, int_offset, ...) gives: n_ref == 0 self
+ * (condensed rows -> (i, j) + int_offset), else row = q*n_ref + r -> (r + int_offset, n_ref + q + int_offset)
+ * (src/boundary.cpp:97-123).  Stable; *d_n_edges the total, only the first cap stored; size rules as
+ * ppk_edge_threshold_dev. */
+int ppk_bgmm_edges_dev(const float *d_dist, size_t n_rows, size_t n_ref, const ppk_bgmm *model,
+                       long long int_offset, long long *d_edges, size_t cap,
+                       unsigned long long *d_n_edges, void *stream);
+
+/* Fused kernel 1 + BGMM assignment: ppk_dist_edges_dev with the label test in the place of the boundary
+ * (queryDatabase -> BGMMFit.assign -> generateTuples without the [n_pairs, 2] matrix).  Arguments and output as
+ * ppk_dist_edges_dev; the list equals ppk_dist_dev -> ppk_bgmm_edges_dev on the same band (int_offset 0). */
+int ppk_dist_bgmm_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers,
+                            const float *random_tbl, size_t n_clu, int flags, size_t q_begin, size_t q_end,
+                            const ppk_bgmm *model, long long *d_edges, size_t cap,
+                            unsigned long long *d_n_edges, unsigned long long *d_n_failed, void *stream);
+
+/* Host form, several devices: ppk_query_edges_dbs with the BGMM label test -- the same band split, pieces (option
+ * "chunk_rows"), concatenation in row order and PPK_ERR_CAPACITY -> ppk_parked_fetch hand-over; the list does not
+ * depend on the number of devices or pieces. */
+int ppk_query_bgmm_edges_dbs(const ppk_db *const *refs, const ppk_db *const *qrys, int n_dev,
+                             const int32_t *kmers, const float *random_tbl, size_t n_clu, int flags,
+                             const ppk_bgmm *model, long long *ij_out, size_t cap, size_t *n_edges,
+                             unsigned long long *n_failed);
+
+/* Host arrays: dist float [n_rows][2] -> labels int32 [n_rows] (nullable) and resp float [n_rows][K] (nullable), on
+ * device_id (BGMMFit.assign(X) of the Python mirror; blocking). */
+int ppk_bgmm_assign(const float *dist, size_t n_rows, const ppk_bgmm *model, int device_id, int32_t *labels,
+                    float *resp);
+
+/* ------------------------------------------------------------------------
  * Boundary sweeps of --fit-model refine (SURVEY.md 8f "next" rows), on a
  * resident self/condensed [n_rows][2] float32 distance buffer.  Outputs are
  * three int64 arrays (i, j, offset index), element for element the vectors

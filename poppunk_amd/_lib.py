@@ -20,7 +20,30 @@ _llp, _ullp, _szp, _intp = (C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong),
                             C.POINTER(C.c_size_t), C.POINTER(C.c_int))
 _vp, _sz = C.c_void_p, C.c_size_t
 
+BGMM_MAX_K = 16
+
+
+class Bgmm(C.Structure):
+    """struct ppk_bgmm (include/ppk.h): a fitted BGMM model as the kernels read it (ppk_bgmm_prepare fills it)."""
+    _fields_ = [("K", C.c_int), ("within_label", C.c_int), ("scale_is_f64", C.c_int), ("n_jitter", C.c_int),
+                ("scale_f32", C.c_float * 2), ("scale_f64", C.c_double * 2),
+                ("mean", (C.c_double * 2) * BGMM_MAX_K), ("chol", (C.c_double * 3) * BGMM_MAX_K),
+                ("inv_diag", (C.c_double * 2) * BGMM_MAX_K), ("log_const", C.c_double * BGMM_MAX_K),
+                ("lin", (C.c_double * 5) * BGMM_MAX_K),
+                ("jitter", C.c_int * BGMM_MAX_K)]
+
+
+_bgmmp, _f64p = C.POINTER(Bgmm), C.POINTER(C.c_double)
+
 SIGNATURES = {
+    "ppk_bgmm_prepare": (C.c_int, [C.c_int, _f64p, _f64p, _f64p, _f64p, C.c_int, C.c_int, _bgmmp]),
+    "ppk_bgmm_assign_dev": (C.c_int, [_vp, _sz, _bgmmp, _vp, _vp, _vp]),
+    "ppk_bgmm_edges_dev": (C.c_int, [_vp, _sz, _sz, _bgmmp, C.c_longlong, _vp, _sz, _vp, _vp]),
+    "ppk_dist_bgmm_edges_dev": (C.c_int, [_vp, _vp, _i32p, _f32p, _sz, C.c_int, _sz, _sz, _bgmmp, _vp, _sz, _vp, _vp,
+                                          _vp]),
+    "ppk_query_bgmm_edges_dbs": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.c_int, _i32p, _f32p, _sz, C.c_int,
+                                           _bgmmp, _llp, _sz, _szp, _ullp]),
+    "ppk_bgmm_assign": (C.c_int, [_f32p, _sz, _bgmmp, C.c_int, _i32p, _f32p]),
     "ppk_last_error": (C.c_char_p, []),
     "ppk_version": (C.c_char_p, []),
     "ppk_release_scratch": (C.c_int, []),
@@ -192,7 +215,7 @@ def sources_hash_now():
     import hashlib
     here = os.path.join(_HERE, "csrc")
     names = ["ppk_api.hip", "ppk_host.hip", "ppk_dist.hip", "ppk_boundary.hip", "ppk_iterate.hip", "ppk_square.hip",
-             "ppk_sparse.hip", "ppk_h5.cpp", "ppk_internal.h", "ppk_block_asm.inc", "../../include/ppk.h"]
+             "ppk_sparse.hip", "ppk_bgmm.hip", "ppk_h5.cpp", "ppk_internal.h", "ppk_block_asm.inc", "../../include/ppk.h"]
     h = hashlib.sha256()
     try:
         for n in names:

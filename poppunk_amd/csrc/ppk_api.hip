@@ -24,7 +24,8 @@ int ppk_launch_dist(const ppk_db *ref, const ppk_db *qry_or_null, const int32_t 
                     const float *d_rtab, size_t n_clu, int flags, size_t q_begin, size_t q_end,
                     void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, int slope,
                     float x_max, float y_max, float scale_x, float scale_y, int inclusive,
-                    double *d_lut, hipStream_t s, const int *knn_args = nullptr, bool lut_ready = false);
+                    double *d_lut, hipStream_t s, const int *knn_args = nullptr, bool lut_ready = false,
+                    const ppk_bgmm *d_bgmm = nullptr);
 
 // ---- errors ---------------------------------------------------------------
 static thread_local std::string g_err;
@@ -716,12 +717,11 @@ extern "C" int ppk_dist_dev(const ppk_db *ref, const ppk_db *qry, const int32_t 
                          d_n_failed, nullptr, 2, 0.f, 0.f, 1.f, 1.f, 1, d_lut, s, nullptr, lut_ready);
 }
 
-extern "C" int ppk_dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers,
-                                  const float *random_tbl, size_t n_clu, int flags, size_t q_begin,
-                                  size_t q_end, int slope, float x_max, float y_max, float scale_x,
-                                  float scale_y, int inclusive, long long *d_edges, size_t cap,
-                                  unsigned long long *d_n_edges, unsigned long long *d_n_failed,
-                                  void *stream) {
+// The fused edge list of a band: the line boundary (model == NULL) or the label test of a BGMM model
+static int dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, const float *random_tbl,
+                          size_t n_clu, int flags, size_t q_begin, size_t q_end, int slope, float x_max, float y_max,
+                          float scale_x, float scale_y, int inclusive, const ppk_bgmm *model, long long *d_edges,
+                          size_t cap, unsigned long long *d_n_edges, unsigned long long *d_n_failed, void *stream) {
   int rc = ppk_check_pair(ref, qry, kmers, q_begin, q_end);
   if (rc != PPK_OK) return rc;
   if (!d_n_edges) return ppk_fail(PPK_ERR_ARG, "d_n_edges is NULL");
@@ -755,6 +755,9 @@ extern "C" int ppk_dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const in
       rc = ppk_launch_dist(ref, qry, kmers, d_rtab, d_rtab ? n_clu : 1, flags, 0, nq, d_dist, d_n_failed,
                            nullptr, slope, x_max, y_max, scale_x, scale_y, inclusive, d_lut, s);
       if (rc != PPK_OK) return rc;
+      if (model)
+        return ppk_bgmm_edges_dev(static_cast<float *>(d_dist), rows, qry ? ref->n : 0, model, 0, d_edges, cap,
+                                  d_n_edges, stream);
       return ppk_edge_threshold_dev(static_cast<float *>(d_dist), rows, qry ? ref->n : 0, slope, x_max,
                                     y_max, inclusive, d_edges, cap, d_n_edges, stream);
     }
@@ -766,10 +769,12 @@ extern "C" int ppk_dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const in
   if (rc != PPK_OK) return rc;
   rc = scratch_get(ref->device, SLOT_WS, ppk_compact_ws_bytes(n_words), &d_ws);
   if (rc != PPK_OK) return rc;
+  const ppk_bgmm *d_model = nullptr;
+  if (model && (rc = ppk_bgmm_to_device(ref->device, *model, &d_model, s)) != PPK_OK) return rc;
   PPK_HIP(hipMemsetAsync(d_mask, 0, n_words * sizeof(uint64_t), s));
   rc = ppk_launch_dist(ref, qry, kmers, d_rtab, d_rtab ? n_clu : 1, flags, q_begin, q_end, nullptr,
                        d_n_failed, static_cast<uint64_t *>(d_mask), slope, x_max, y_max, scale_x,
-                       scale_y, inclusive, d_lut, s, nullptr, lut_ready);
+                       scale_y, inclusive, d_lut, s, nullptr, lut_ready, d_model);
   if (rc != PPK_OK) return rc;
   EdgeGeom g = {};
   g.layout = qry ? EDGE_TILED_NONSELF : EDGE_TILED_SELF;
@@ -779,6 +784,33 @@ extern "C" int ppk_dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const in
   g.int_offset = 0;
   return ppk_launch_compact(static_cast<const uint64_t *>(d_mask), n_words, g, d_ws, d_edges, cap,
                             d_n_edges, s);
+}
+
+extern "C" int ppk_dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers,
+                                  const float *random_tbl, size_t n_clu, int flags, size_t q_begin,
+                                  size_t q_end, int slope, float x_max, float y_max, float scale_x,
+                                  float scale_y, int inclusive, long long *d_edges, size_t cap,
+                                  unsigned long long *d_n_edges, unsigned long long *d_n_failed,
+                                  void *stream) {
+  return dist_edges_dev(ref, qry, kmers, random_tbl, n_clu, flags, q_begin, q_end, slope, x_max, y_max, scale_x,
+                        scale_y, inclusive, nullptr, d_edges, cap, d_n_edges, d_n_failed, stream);
+}
+
+static int check_bgmm(const ppk_bgmm *model) {
+  if (!model) return ppk_fail(PPK_ERR_ARG, "model is NULL");
+  if (model->K < 1 || model->K > PPK_BGMM_MAX_K || model->within_label < 0 || model->within_label >= model->K)
+    return ppk_fail(PPK_ERR_ARG, "the BGMM model is not prepared (ppk_bgmm_prepare)");
+  return PPK_OK;
+}
+
+extern "C" int ppk_dist_bgmm_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers,
+                                       const float *random_tbl, size_t n_clu, int flags, size_t q_begin,
+                                       size_t q_end, const ppk_bgmm *model, long long *d_edges, size_t cap,
+                                       unsigned long long *d_n_edges, unsigned long long *d_n_failed,
+                                       void *stream) {
+  if (int rc = check_bgmm(model)) return rc;
+  return dist_edges_dev(ref, qry, kmers, random_tbl, n_clu, flags, q_begin, q_end, 2, 0.f, 0.f, 1.f, 1.f, 0, model,
+                        d_edges, cap, d_n_edges, d_n_failed, stream);
 }
 
 // k nearest neighbours of every sample straight from the resident sketches: kernel 1's tiles emit
@@ -1166,6 +1198,55 @@ extern "C" int ppk_edge_threshold_dev(const float *d_dist, size_t n_rows, size_t
                                  static_cast<uint64_t *>(d_mask), s);
   if (rc != PPK_OK) return rc;
   return edges_from_mask(dev, n_rows, g, static_cast<uint64_t *>(d_mask), d_edges, cap, d_n_edges, s);
+}
+
+extern "C" int ppk_bgmm_assign_dev(const float *d_dist, size_t n_rows, const ppk_bgmm *model, int32_t *d_labels,
+                                   float *d_resp, void *stream) {
+  if (int rc = check_bgmm(model)) return rc;
+  if (n_rows == 0) return PPK_OK;
+  if (!d_labels && !d_resp) return ppk_fail(PPK_ERR_ARG, "neither labels nor responsibilities asked for");
+  if (!d_dist) return ppk_fail(PPK_ERR_ARG, "NULL distance buffer");
+  return ppk_launch_bgmm_assign(d_dist, n_rows, *model, d_labels, d_resp, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int ppk_bgmm_edges_dev(const float *d_dist, size_t n_rows, size_t n_ref, const ppk_bgmm *model,
+                                  long long int_offset, long long *d_edges, size_t cap,
+                                  unsigned long long *d_n_edges, void *stream) {
+  if (int rc = check_bgmm(model)) return rc;
+  if (!d_n_edges) return ppk_fail(PPK_ERR_ARG, "d_n_edges is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int dev = 0;
+  PPK_HIP(hipGetDevice(&dev));
+  PpkCall call(dev, s);
+  EdgeGeom g = {};
+  g.n_rows = n_rows;
+  g.int_offset = int_offset;
+  if (n_ref == 0) {
+    g.layout = EDGE_LINEAR_SELF;
+    g.n_samples = samples_of_rows(n_rows);
+    if (g.n_samples * (g.n_samples - 1) / 2 != n_rows)
+      return ppk_fail(PPK_ERR_ARG, "row count is not n(n-1)/2 for any n (self/condensed matrix expected)");
+  } else {
+    g.layout = EDGE_LINEAR_NONSELF;
+    g.n_ref = n_ref;
+    if (n_rows % n_ref) return ppk_fail(PPK_ERR_ARG, "row count is not a multiple of n_ref");
+  }
+  const size_t n_words = ppk_mask_words_linear(n_rows);
+  void *d_mask = nullptr, *d_ws = nullptr;
+  int rc = scratch_get(dev, SLOT_MASK, n_words * sizeof(uint64_t) + 16, &d_mask);
+  if (rc != PPK_OK) return rc;
+  rc = scratch_get(dev, SLOT_WS, ppk_compact_ws_bytes(n_words), &d_ws);
+  if (rc != PPK_OK) return rc;
+  if ((reinterpret_cast<uintptr_t>(d_dist) & 15) != 0) {
+    // a distance buffer that is not 16-byte aligned: a row-order mask, compacted uncounted
+    rc = ppk_launch_mask_from_bgmm(d_dist, n_rows, *model, static_cast<uint64_t *>(d_mask), s);
+    if (rc != PPK_OK) return rc;
+    return ppk_launch_compact(static_cast<uint64_t *>(d_mask), n_words, g, d_ws, d_edges, cap, d_n_edges, s);
+  }
+  rc = ppk_launch_mask_from_bgmm_counted(d_dist, n_rows, *model, static_cast<uint64_t *>(d_mask), d_ws, s);
+  if (rc != PPK_OK) return rc;
+  g.pair_interleaved = 1;
+  return ppk_launch_compact(static_cast<uint64_t *>(d_mask), n_words, g, d_ws, d_edges, cap, d_n_edges, s, true);
 }
 
 extern "C" int ppk_qc_edges_dev(const float *d_dist, size_t n_rows, size_t n_ref, int mode,

@@ -49,10 +49,30 @@ assign_kernel_x2(const f32x4 *__restrict__ dist, size_t n_pairs, int slope, floa
   }
 }
 
+// Row predicates of the edge-list passes: the refine/threshold line (src/boundary.cpp:82-95) and the label test of a
+// fitted BGMM (ppk_bgmm_label; KT > 0: K as a compile-time constant).
+struct LinePred {
+  int slope;
+  float x_max, y_max;
+  int inclusive;
+  __device__ __forceinline__ bool operator()(float x, float y) const {
+    const float s = ppk_line_dist(x, y, x_max, y_max, slope);
+    return inclusive ? (s <= 0.0f) : (s < 0.0f);
+  }
+};
+template <int KT>
+struct BgmmPred {
+  ppk_bgmm m;
+  __device__ __forceinline__ bool operator()(float x, float y) const {
+    return ppk_bgmm_label<KT>(x, y, m) == m.within_label;
+  }
+};
+
 // One wavefront covers 64 consecutive rows; its ballot IS the mask word.
+template <class Pred>
 __global__ void __launch_bounds__(kBlock)
-mask_from_dist_kernel(const float2 *__restrict__ dist, size_t n_rows, int slope, float x_max,
-                      float y_max, int inclusive, uint64_t *__restrict__ mask, size_t n_words) {
+mask_from_dist_kernel(const float2 *__restrict__ dist, size_t n_rows, const Pred pred_of,
+                      uint64_t *__restrict__ mask, size_t n_words) {
   const size_t wstride = (size_t)gridDim.x * (kBlock / 64);
   const int lane = threadIdx.x & 63;
   for (size_t w = (size_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); w < n_words;
@@ -61,8 +81,7 @@ mask_from_dist_kernel(const float2 *__restrict__ dist, size_t n_rows, int slope,
     bool pred = false;
     if (row < n_rows) {
       const float2 d = dist[row];
-      const float s = ppk_line_dist(d.x, d.y, x_max, y_max, slope);
-      pred = inclusive ? (s <= 0.0f) : (s < 0.0f);
+      pred = pred_of(d.x, d.y);
     }
     const uint64_t m = __ballot(pred);
     if (lane == 0) mask[w] = m;
@@ -131,9 +150,10 @@ mask_from_dist_kernel_x2(const f32x4 *__restrict__ dist, size_t n_rows, int slop
 // odd rows of the 128 -- instead of being shuffled into row order here (two ds_bpermute and two more compares per
 // kilobyte read: the pass ran at 5.3 TB/s against the assign pass's 6.7).  mask_expand_kernel, which touches a mask
 // word only to list its few set bits, puts the pair back in row order (EdgeGeom::pair_interleaved).
+template <class Pred>
 __global__ void __launch_bounds__(kBlock)
-mask_from_dist_counted_kernel(const f32x4 *__restrict__ dist, size_t n_rows, int slope, float x_max, float y_max,
-                              int inclusive, uint64_t *__restrict__ mask, size_t n_words,
+mask_from_dist_counted_kernel(const f32x4 *__restrict__ dist, size_t n_rows, const Pred pred,
+                              uint64_t *__restrict__ mask, size_t n_words,
                               unsigned long long *__restrict__ block_sums, size_t n_cblocks, unsigned per) {
   __shared__ unsigned sh[kBlock / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -164,10 +184,9 @@ mask_from_dist_counted_kernel(const f32x4 *__restrict__ dist, size_t n_rows, int
         const size_t w2 = w2_0 + (size_t)(it0 + j) * (kBlock / 64) + wave;
         if (2 * w2 >= n_words) break;      // wave-uniform
         const size_t row = w2 * 128 + 2 * (size_t)lane;
-        const float s0 = ppk_line_dist(d[j].x, d[j].y, x_max, y_max, slope);
-        const float s1 = ppk_line_dist(d[j].z, d[j].w, x_max, y_max, slope);
-        const uint64_t wa = __ballot(row < n_rows && (inclusive ? (s0 <= 0.0f) : (s0 < 0.0f)));
-        const uint64_t wb = __ballot(row + 1 < n_rows && (inclusive ? (s1 <= 0.0f) : (s1 < 0.0f)));
+        const bool p0 = pred(d[j].x, d[j].y), p1 = pred(d[j].z, d[j].w);
+        const uint64_t wa = __ballot(row < n_rows && p0);
+        const uint64_t wb = __ballot(row + 1 < n_rows && p1);
         if (lane == 0) {
           typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
           u64x2 v;
@@ -554,26 +573,58 @@ int ppk_launch_mask_from_dist(const float *d_dist, size_t n_rows, int slope, flo
                        inclusive, d_mask, n_words);
   } else {
     const unsigned grid = grid_for(n_words, kBlock / 64, 4096);
-    hipLaunchKernelGGL(mask_from_dist_kernel, dim3(grid), dim3(kBlock), 0, s,
-                       reinterpret_cast<const float2 *>(d_dist), n_rows, slope, x_max, y_max,
-                       inclusive, d_mask, n_words);
+    hipLaunchKernelGGL(mask_from_dist_kernel<LinePred>, dim3(grid), dim3(kBlock), 0, s,
+                       reinterpret_cast<const float2 *>(d_dist), n_rows, LinePred{slope, x_max, y_max, inclusive},
+                       d_mask, n_words);
   }
   PPK_HIP(hipGetLastError());
   return PPK_OK;
 }
 
 // mask + per-block bit counts in one pass (d_ws as for ppk_launch_compact, which is then told the counts exist)
-int ppk_launch_mask_from_dist_counted(const float *d_dist, size_t n_rows, int slope, float x_max, float y_max,
-                                      int inclusive, uint64_t *d_mask, void *d_ws, hipStream_t s) {
+namespace {
+template <class Pred>
+int launch_mask_counted(const float *d_dist, size_t n_rows, const Pred &pred, uint64_t *d_mask, void *d_ws,
+                        hipStream_t s) {
   const size_t n_words = ppk_mask_words_linear(n_rows);
   if (n_words == 0) return PPK_OK;
+  if ((reinterpret_cast<uintptr_t>(d_dist) & 15) != 0)
+    return ppk_fail(PPK_ERR_STATE, "internal: the counted mask pass needs a 16-byte aligned distance buffer");
   const size_t nb = (n_words + kWordsPerBlock - 1) / kWordsPerBlock;
   if (nb > 0x7fffffffull) return ppk_fail(PPK_ERR_ARG, "edge mask too large for one launch");
   const size_t slots = 256 * 8;      // workgroups of 256 threads the device holds at once
   const unsigned per = (unsigned)((nb + slots - 1) / slots);
-  hipLaunchKernelGGL(mask_from_dist_counted_kernel, dim3((unsigned)((nb + per - 1) / per)), dim3(kBlock), 0, s,
-                     reinterpret_cast<const f32x4 *>(d_dist), n_rows, slope, x_max, y_max, inclusive, d_mask, n_words,
+  hipLaunchKernelGGL(mask_from_dist_counted_kernel<Pred>, dim3((unsigned)((nb + per - 1) / per)), dim3(kBlock), 0, s,
+                     reinterpret_cast<const f32x4 *>(d_dist), n_rows, pred, d_mask, n_words,
                      static_cast<unsigned long long *>(d_ws), nb, per);
+  PPK_HIP(hipGetLastError());
+  return PPK_OK;
+}
+}  // namespace
+
+int ppk_launch_mask_from_dist_counted(const float *d_dist, size_t n_rows, int slope, float x_max, float y_max,
+                                      int inclusive, uint64_t *d_mask, void *d_ws, hipStream_t s) {
+  return launch_mask_counted(d_dist, n_rows, LinePred{slope, x_max, y_max, inclusive}, d_mask, d_ws, s);
+}
+
+// K = 2, 3, 4 (every PopPUNK default fit: --K 2) with the component loop unrolled; other K at run time
+int ppk_launch_mask_from_bgmm_counted(const float *d_dist, size_t n_rows, const ppk_bgmm &m, uint64_t *d_mask,
+                                      void *d_ws, hipStream_t s) {
+  switch (m.K) {
+    case 2: return launch_mask_counted(d_dist, n_rows, BgmmPred<2>{m}, d_mask, d_ws, s);
+    case 3: return launch_mask_counted(d_dist, n_rows, BgmmPred<3>{m}, d_mask, d_ws, s);
+    case 4: return launch_mask_counted(d_dist, n_rows, BgmmPred<4>{m}, d_mask, d_ws, s);
+    default: return launch_mask_counted(d_dist, n_rows, BgmmPred<0>{m}, d_mask, d_ws, s);
+  }
+}
+
+// row-order mask (any alignment: 8-byte loads), compacted without counts
+int ppk_launch_mask_from_bgmm(const float *d_dist, size_t n_rows, const ppk_bgmm &m, uint64_t *d_mask, hipStream_t s) {
+  const size_t n_words = ppk_mask_words_linear(n_rows);
+  if (n_words == 0) return PPK_OK;
+  const unsigned grid = grid_for(n_words, kBlock / 64, 4096);
+  hipLaunchKernelGGL(mask_from_dist_kernel<BgmmPred<0>>, dim3(grid), dim3(kBlock), 0, s,
+                     reinterpret_cast<const float2 *>(d_dist), n_rows, BgmmPred<0>{m}, d_mask, n_words);
   PPK_HIP(hipGetLastError());
   return PPK_OK;
 }

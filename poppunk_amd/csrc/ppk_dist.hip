@@ -98,7 +98,12 @@ __device__ __forceinline__ uint32_t pack_get(const PackW<2> &pk, int k, int bits
   return (uint32_t)(v >> ((nk - 1 - k) * bits)) & mask;
 }
 
-enum { MODE_DIST = 0, MODE_JACCARD = 1, MODE_COUNTS = 2, MODE_MASK = 3, MODE_KNN = 4 };
+enum { MODE_DIST = 0, MODE_JACCARD = 1, MODE_COUNTS = 2, MODE_MASK = 3, MODE_KNN = 4, MODE_BGMM = 5 };
+// The two edge-bitmask modes: MODE_MASK applies the refine/threshold line (ppk_line_dist), MODE_BGMM the label of a
+// fitted BGMM (ppk_bgmm_label; the model is read through the kernel's otherwise unused `out` pointer).  Everything
+// but the per-pair predicate is shared; the predicate is a compile-time choice, so MODE_BGMM adds instantiations
+// and leaves those of MODE_MASK as they were.
+constexpr bool ppk_is_mask(int mode) { return mode == MODE_MASK || mode == MODE_BGMM; }
 
 // MODE_KNN (k nearest neighbours of every sample, straight from the tiles; self job: among the other samples,
 // ref x query job: of every query among the refs AND of every ref among the queries, queries numbered
@@ -766,7 +771,7 @@ dist_kernel(const uint64_t *__restrict__ refT, const uint32_t *__restrict__ qryT
     if (wave_active) {
 #pragma unroll
       for (int j = 0; j < TQ; ++j) {
-        if constexpr (MODE == MODE_DIST || MODE == MODE_MASK) {
+        if constexpr (MODE == MODE_DIST || ppk_is_mask(MODE)) {
           pack_put(packed[j], cnt[j], k, p.cnt_bits);
         } else {
           const size_t q = qw0 + j;
@@ -794,7 +799,7 @@ dist_kernel(const uint64_t *__restrict__ refT, const uint32_t *__restrict__ qryT
   }
 
   // ---- epilogue: regression (+ boundary) per pair ---------------------------
-  if constexpr (MODE == MODE_DIST || MODE == MODE_MASK) {
+  if constexpr (MODE == MODE_DIST || ppk_is_mask(MODE)) {
     if (!wave_active) return;
     const int cr = (ref_clu && r < p.n_ref) ? ref_clu[r] : 0;
 #pragma unroll
@@ -823,10 +828,15 @@ dist_kernel(const uint64_t *__restrict__ refT, const uint32_t *__restrict__ qryT
       } else {
         bool pred = false;
         if (valid) {
-          // RefineFit.assign pre-scales X/scale in float32 (PopPUNK/models.py:1085-1089)
-          const float xs = __fdiv_rn(core, p.scale_x), ys = __fdiv_rn(acc, p.scale_y);
-          const float s = ppk_line_dist(xs, ys, p.x_max, p.y_max, p.slope);
-          pred = p.inclusive ? (s <= 0.0f) : (s < 0.0f);
+          if constexpr (MODE == MODE_BGMM) {
+            const ppk_bgmm &bg = *static_cast<const ppk_bgmm *>(out);
+            pred = ppk_bgmm_label(core, acc, bg) == bg.within_label;
+          } else {
+            // RefineFit.assign pre-scales X/scale in float32 (PopPUNK/models.py:1085-1089)
+            const float xs = __fdiv_rn(core, p.scale_x), ys = __fdiv_rn(acc, p.scale_y);
+            const float s = ppk_line_dist(xs, ys, p.x_max, p.y_max, p.slope);
+            pred = p.inclusive ? (s <= 0.0f) : (s < 0.0f);
+          }
         }
         const uint64_t m = __ballot(pred);
         if (lane == 0) mask_out[(q - p.q_begin) * p.n_rtiles + rt] = m;
@@ -896,8 +906,8 @@ dist_kernel_v2(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ q
   // WIDE without KSPLIT: the tile kernel whose count register windows the k list (PackWide).  WIDE with KSPLIT: a
   // k-split unit (it counts ONE k, or a piece of one: W = 2 holds it) whose tile is fitted by its last unit straight
   // from the units' partial counts (PackParts) -- no count register is ever rebuilt, so any k list fits.
-  static_assert(!WIDE || (KSPLIT ? (W == 2 && (MODE == MODE_DIST || MODE == MODE_MASK))
-                                 : (W == 4 && (MODE == MODE_DIST || MODE == MODE_MASK || MODE == MODE_KNN))),
+  static_assert(!WIDE || (KSPLIT ? (W == 2 && (MODE == MODE_DIST || ppk_is_mask(MODE)))
+                                 : (W == 4 && (MODE == MODE_DIST || ppk_is_mask(MODE) || MODE == MODE_KNN))),
                 "the wide instantiations");
   constexpr bool WIDE_TILE = WIDE && !KSPLIT;
   const int ablate = EXP ? p.ablate : 0;
@@ -914,11 +924,11 @@ dist_kernel_v2(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ q
   // double buffer: 63 KB.  The modes with a per-pair fit take 80 KB -- two workgroups then own all
   // 160 KB of a CU -- so that the epilogue of an interior tile can hold the whole (E, F) table
   // (5 k x 1024 counts x 16 B) in LDS, see below.
-  constexpr bool LDS_TABLE = NW == 8 && W == 2 && !WIDE && (MODE == MODE_DIST || MODE == MODE_MASK || MODE == MODE_KNN);
+  constexpr bool LDS_TABLE = NW == 8 && W == 2 && !WIDE && (MODE == MODE_DIST || ppk_is_mask(MODE) || MODE == MODE_KNN);
   constexpr int TAB_U4 = 5 * 1024;
   // KS_FUSED: a k-split job whose tiles are fitted by their last workgroup (below); one more entry behind the
   // compare buffers holds the workgroup's grid position across the loop, in LDS instead of two SGPRs
-  constexpr bool KS_FUSED = KSPLIT && (MODE == MODE_DIST || MODE == MODE_MASK);
+  constexpr bool KS_FUSED = KSPLIT && (MODE == MODE_DIST || ppk_is_mask(MODE));
   constexpr bool KS_MEM = KS_FUSED && WIDE;
   constexpr int KS_SLOT = 2 * CHUNK_U4;      // (WIDE: the workgroup's spill slot index lives there)
   __shared__ u32x4 lds[LDS_TABLE && TAB_U4 > 2 * CHUNK_U4 + 1 ? TAB_U4 : 2 * CHUNK_U4 + (KS_FUSED || WIDE ? 1 : 0)];
@@ -1188,7 +1198,7 @@ dist_kernel_v2(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ q
         // one unit = part of one k: nothing happens between blocks, the counts leave after the loop
       } else if (blk == ublocks - 1) {
         // ---- end of one k --------------------------------------------------------
-        if constexpr (MODE == MODE_DIST || MODE == MODE_MASK || MODE == MODE_KNN) {
+        if constexpr (MODE == MODE_DIST || ppk_is_mask(MODE) || MODE == MODE_KNN) {
           // another k follows: the count register moves up by one field
           bool parked = false;
           if constexpr (WIDE_TILE) {
@@ -1273,7 +1283,7 @@ dist_kernel_v2(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ q
     compare_loop(std::false_type{});
 
   // ---- epilogue: regression (+ boundary) per pair ---------------------------
-  if constexpr (MODE == MODE_DIST || MODE == MODE_MASK || MODE == MODE_KNN) {
+  if constexpr (MODE == MODE_DIST || ppk_is_mask(MODE) || MODE == MODE_KNN) {
     if (ablate & 1) return;
     if (!KS_FUSED && !WIDE_TILE && MODE != MODE_KNN && !wave_active) return;      // (KNN, k-split, wide: every wave takes part in an exchange)
     // the compare stream leaves the wave at priority 0 (it falls through each block, see
@@ -1659,16 +1669,22 @@ dist_kernel_v2(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ q
             } else if (!(ablate_l & 128))      // (measurement only)
               *reinterpret_cast<f32x4_a8 *>(orow + (2u * (uint32_t)lane_late + 128u * h)) = v;
           }
-        } else if constexpr (MODE == MODE_MASK) {
+        } else if constexpr (ppk_is_mask(MODE)) {
           uint64_t ball[R];
           // (a k-split tile takes this statement wherever it lies: pairs that do not exist -- r <= q, padding,
           // outside the band, the uncompared half of a half tile -- have no bit, like in the general statement)
           const bool q_in_band_m = !KS_FUSED || (qq >= qb && qq < qe);      // wave-uniform
 #pragma unroll
           for (int rr = 0; rr < R; ++rr) {
-            const float xs = __fdiv_rn(core[rr], p.scale_x), ys = __fdiv_rn(acc[rr], p.scale_y);
-            const float sd = ppk_line_dist(xs, ys, p.x_max, p.y_max, p.slope);
-            bool pred = p.inclusive ? (sd <= 0.0f) : (sd < 0.0f);
+            bool pred;
+            if constexpr (MODE == MODE_BGMM) {
+              const ppk_bgmm &bg = *static_cast<const ppk_bgmm *>(out);
+              pred = ppk_bgmm_label(core[rr], acc[rr], bg) == bg.within_label;
+            } else {
+              const float xs = __fdiv_rn(core[rr], p.scale_x), ys = __fdiv_rn(acc[rr], p.scale_y);
+              const float sd = ppk_line_dist(xs, ys, p.x_max, p.y_max, p.slope);
+              pred = p.inclusive ? (sd <= 0.0f) : (sd < 0.0f);
+            }
             if constexpr (KS_FUSED) {
               const uint32_t rf = (uint32_t)ref_of(rr), q32 = (uint32_t)qq;
               pred = pred && !(half && rr < 2) && rf < (uint32_t)p.r_limit && (!p.self || rf > q32);
@@ -1842,14 +1858,19 @@ dist_kernel_v2(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ q
               o[rf * p.n_ref - (rf * (rf + 1)) / 2 + (qq - rf - 1) - p.row_base] = make_float2(core[r], acc[r]);
           }
         }
-      } else if constexpr (MODE == MODE_MASK) {
+      } else if constexpr (ppk_is_mask(MODE)) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           bool pred = false;
           if (valid[r]) {
-            const float xs = __fdiv_rn(core[r], p.scale_x), ys = __fdiv_rn(acc[r], p.scale_y);
-            const float sd = ppk_line_dist(xs, ys, p.x_max, p.y_max, p.slope);
-            pred = p.inclusive ? (sd <= 0.0f) : (sd < 0.0f);
+            if constexpr (MODE == MODE_BGMM) {
+              const ppk_bgmm &bg = *static_cast<const ppk_bgmm *>(out);
+              pred = ppk_bgmm_label(core[r], acc[r], bg) == bg.within_label;
+            } else {
+              const float xs = __fdiv_rn(core[r], p.scale_x), ys = __fdiv_rn(acc[r], p.scale_y);
+              const float sd = ppk_line_dist(xs, ys, p.x_max, p.y_max, p.slope);
+              pred = p.inclusive ? (sd <= 0.0f) : (sd < 0.0f);
+            }
           }
           ball[r] = __ballot(pred);
           // strip tile: the lane sample is the row of the mask, the wave-uniform strip sample its
@@ -1866,7 +1887,7 @@ dist_kernel_v2(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ q
         for (int r = 0; r < R; ++r)
           if (valid[r]) knn_bits[q][r] = __float_as_uint((p.knn_col ? acc[r] : core[r]) + 0.0f);
       }
-      if constexpr (MODE == MODE_MASK) {
+      if constexpr (ppk_is_mask(MODE)) {
         // ball[0]/ball[1]: even/odd refs of r0..r0+127; ball[2]/ball[3]: of r0+128..r0+255.
         // Interleave them into the [q][ref/64] bitmask words the compaction pass reads.
         if (lane_late == 0 && !strip) {
@@ -2266,7 +2287,7 @@ int launch_v2(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const f
   // sit on the query axis against all smaller samples on the lane axis, writing the same
   // condensed rows; the strip tiles lead the same grid.
   const size_t rem = p.n_ref % V2_RT;
-  if constexpr (MODE == MODE_DIST || MODE == MODE_MASK) {
+  if constexpr (MODE == MODE_DIST || ppk_is_mask(MODE)) {
     bool split = p.self && rem != 0 && rem <= 224 && p.n_ref > V2_RT;
 #ifdef PPK_EXPERIMENTS
     if (ppk_config().strip.load() == 0) split = false;
@@ -2308,10 +2329,10 @@ int launch_v2(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const f
   const size_t n_blocks = n_tri + p.n_strip_pad;
   if (n_blocks * (size_t)(NW * 64) >= ((size_t)1 << 32))
     return ppk_fail(PPK_ERR_ARG, "internal: tile grid too large for one launch (ppk_launch_dist splits bands before this)");
-  if ((MODE == MODE_DIST || MODE == MODE_MASK) && NW == 8 && p.k_split) {
+  if ((MODE == MODE_DIST || ppk_is_mask(MODE)) && NW == 8 && p.k_split) {
     // k-split job in one launch: ks_units workgroups per tile, the last one to finish fits it (KS_FUSED in the
     // kernel).  Scratch: one zero-initialised counter per tile; 32 bytes per (tile, unit, thread) of partial counts.
-    if constexpr (NW == 8 && W == 2 && (MODE == MODE_DIST || MODE == MODE_MASK)) {
+    if constexpr (NW == 8 && W == 2 && (MODE == MODE_DIST || ppk_is_mask(MODE))) {
       void *d_tickets = nullptr, *d_part = nullptr;
       const size_t ticket_bytes = (n_blocks * 4 + 255) / 256 * 256;
       int rc = ppk_scratch_get(ref->device, SLOT_TICKETS, ticket_bytes, &d_tickets);
@@ -2428,7 +2449,7 @@ template <int MODE>
 int launch_tiles_packed(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const float *d_rtab,
                         void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, DistParams &p,
                         hipStream_t s) {
-  static_assert(MODE == MODE_DIST || MODE == MODE_MASK || MODE == MODE_KNN, "packed modes");
+  static_assert(MODE == MODE_DIST || ppk_is_mask(MODE) || MODE == MODE_KNN, "packed modes");
   const int total_bits = p.nk * p.cnt_bits;
   if constexpr (MODE == MODE_KNN) {
     if (p.bbits != 14) return ppk_fail(PPK_ERR_ARG, "neighbours from tiles need bbits = 14 (use the square-matrix path)");
@@ -2445,7 +2466,7 @@ int launch_tiles_packed(const ppk_db *ref, const ppk_db *qry, const double *d_lu
   }
   // (option "wide_kpg": a narrower window, i.e. the wide path on a k list the register would hold -- tests)
   const long long force_kpg = ppk_config().wide_kpg.load();
-  if constexpr (MODE == MODE_DIST || MODE == MODE_MASK) {
+  if constexpr (MODE == MODE_DIST || ppk_is_mask(MODE)) {
     // a k-split job whose tiles are fitted from the units' partial counts as they lie (any k list)
     // (every k list of more than 64 count bits: rebuilding three- and four-dword registers in the last unit measured
     // the same -- profiles/r05/ksplit_fit_from_parts.txt -- and cost two more instantiations, both with spills; the
@@ -2629,7 +2650,8 @@ static int launch_dist_band(const ppk_db *ref, const ppk_db *qry_or_null, const 
                             const float *d_rtab, size_t n_clu, int flags, size_t q_begin, size_t q_end,
                             void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, int slope,
                             float x_max, float y_max, float scale_x, float scale_y, int inclusive,
-                            double *d_lut, hipStream_t s, const int *knn_args, bool lut_ready);
+                            double *d_lut, hipStream_t s, const int *knn_args, bool lut_ready,
+                            const ppk_bgmm *d_bgmm);
 
 size_t ppk_rows_per_dispatch(const ppk_db *ref) {
   const size_t r_tiles = (ref->n + V2_RT - 1) / V2_RT;
@@ -2648,11 +2670,12 @@ int ppk_launch_dist(const ppk_db *ref, const ppk_db *qry_or_null, const int32_t 
                     const float *d_rtab, size_t n_clu, int flags, size_t q_begin, size_t q_end,
                     void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, int slope,
                     float x_max, float y_max, float scale_x, float scale_y, int inclusive,
-                    double *d_lut, hipStream_t s, const int *knn_args, bool lut_ready) {
+                    double *d_lut, hipStream_t s, const int *knn_args, bool lut_ready,
+                    const ppk_bgmm *d_bgmm) {
   const size_t q_sub = ppk_rows_per_dispatch(ref);
   if (q_end - q_begin <= q_sub)
     return launch_dist_band(ref, qry_or_null, kmers, d_rtab, n_clu, flags, q_begin, q_end, d_out, d_n_failed, d_mask,
-                            slope, x_max, y_max, scale_x, scale_y, inclusive, d_lut, s, knn_args, lut_ready);
+                            slope, x_max, y_max, scale_x, scale_y, inclusive, d_lut, s, knn_args, lut_ready, d_bgmm);
   const size_t n_qry = qry_or_null ? qry_or_null->n : 0;
   const size_t row_bytes = (flags & (PPK_FLAG_COUNTS | PPK_FLAG_JACCARD)) ? ref->nk * 4 : 8;
   const size_t n_rtiles = (ref->n + 63) / 64;
@@ -2666,7 +2689,8 @@ int ppk_launch_dist(const ppk_db *ref, const ppk_db *qry_or_null, const int32_t 
       if (d_mask) mask = d_mask + (lo - q_begin) * n_rtiles;
     }
     int rc = launch_dist_band(ref, qry_or_null, kmers, d_rtab, n_clu, flags, lo, hi, out, d_n_failed, mask, slope,
-                              x_max, y_max, scale_x, scale_y, inclusive, d_lut, s, knn_args, lut_ready || lo > q_begin);
+                              x_max, y_max, scale_x, scale_y, inclusive, d_lut, s, knn_args, lut_ready || lo > q_begin,
+                              d_bgmm);
     if (rc != PPK_OK) return rc;
   }
   return PPK_OK;
@@ -2676,7 +2700,8 @@ static int launch_dist_band(const ppk_db *ref, const ppk_db *qry_or_null, const 
                             const float *d_rtab, size_t n_clu, int flags, size_t q_begin, size_t q_end,
                             void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, int slope,
                             float x_max, float y_max, float scale_x, float scale_y, int inclusive,
-                            double *d_lut, hipStream_t s, const int *knn_args, bool lut_ready) {
+                            double *d_lut, hipStream_t s, const int *knn_args, bool lut_ready,
+                            const ppk_bgmm *d_bgmm) {
   const ppk_db *qry = qry_or_null ? qry_or_null : ref;
   DistParams p = {};
   p.self = qry_or_null ? 0 : 1;
@@ -2730,6 +2755,9 @@ static int launch_dist_band(const ppk_db *ref, const ppk_db *qry_or_null, const 
   p.ext_adjust = ppk_config().ext_collision_adjust.load() ? 1 : 0;
   p.ext_skip = ppk_config().ext_fit_skip.load() ? 1 : 0;
 
+  // MODE_BGMM reads the model through the kernel's `out` pointer (MODE_MASK leaves it unused)
+  if (d_bgmm && !d_mask) return ppk_fail(PPK_ERR_STATE, "internal: a BGMM launch needs an edge bitmask");
+  void *bgmm_out = const_cast<ppk_bgmm *>(d_bgmm);
   const bool want_counts = flags & PPK_FLAG_COUNTS;
   const bool want_jac = flags & PPK_FLAG_JACCARD;
   if (want_counts)
@@ -2792,7 +2820,8 @@ static int launch_dist_band(const ppk_db *ref, const ppk_db *qry_or_null, const 
     // ONE launch: every tile's last unit fits it (a unit's counts travel as 16-bit numbers)
     // (a unit's counts travel as 16-bit numbers; fitted from the parts as they lie, a k's pieces are added in place)
     if (choice.route == PPK_ROUTE_KSPLIT_ONE_LAUNCH) {
-      const int rc1 = d_mask ? launch_tiles_packed<MODE_MASK>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s)
+      const int rc1 = d_bgmm ? launch_tiles_packed<MODE_BGMM>(ref, qry, d_lut, d_rtab, bgmm_out, d_n_failed, d_mask, p, s)
+                      : d_mask ? launch_tiles_packed<MODE_MASK>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s)
                              : launch_tiles_packed<MODE_DIST>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, nullptr, p, s);
       if (rc1 != kNoKsplitScratch) return rc1;
       // the device could not give the partial counts their scratch: the band runs through the tile kernel, which
@@ -2805,6 +2834,7 @@ static int launch_dist_band(const ppk_db *ref, const ppk_db *qry_or_null, const 
   if (small) {
     if (d_mask) {      // (cannot happen: edge_ks admits one-launch shapes only; stay on the tile kernel)
       p.k_split = 0;
+      if (d_bgmm) return launch_tiles_packed<MODE_BGMM>(ref, qry, d_lut, d_rtab, bgmm_out, d_n_failed, d_mask, p, s);
       return launch_tiles_packed<MODE_MASK>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
     }
     void *p_cnt = nullptr;
@@ -2831,6 +2861,7 @@ static int launch_dist_band(const ppk_db *ref, const ppk_db *qry_or_null, const 
     // d_out: candidate arrays, d_mask: KnnState + bounds over n_ref (+ n_qry: a ref x query job) samples (MODE_KNN)
     return launch_tiles_packed<MODE_KNN>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
   }
+  if (d_bgmm) return launch_tiles_packed<MODE_BGMM>(ref, qry, d_lut, d_rtab, bgmm_out, d_n_failed, d_mask, p, s);
   if (d_mask) return launch_tiles_packed<MODE_MASK>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
   return launch_tiles_packed<MODE_DIST>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
 }

@@ -1517,8 +1517,9 @@ struct EdgePart {
   size_t count() const { return spill.size() / 2 + n_dev; }
 };
 
+// model == NULL: the line boundary (slope ... inclusive); else the BGMM label test (ppk_dist_bgmm_edges_dev)
 void run_edge_part(EdgePart &p, const int32_t *kmers, const float *random_tbl, size_t n_clu, int flags, int slope,
-                   float x_max, float y_max, float scale_x, float scale_y, int inclusive) {
+                   float x_max, float y_max, float scale_x, float scale_y, int inclusive, const ppk_bgmm *model) {
   auto fail = [&](int code) {
     p.rc = code;
     p.err = ppk_error();
@@ -1587,8 +1588,10 @@ void run_edge_part(EdgePart &p, const int32_t *kmers, const float *random_tbl, s
       }
       const size_t room = cap - acc;
       if (hipMemsetAsync(d_cnt, 0, 16, s) != hipSuccess) return fail(ppk_fail(PPK_ERR_HIP, "hipMemset failed"));
-      rc = ppk_dist_edges_dev(p.ref, p.qry, kmers, random_tbl, n_clu, flags, lo, hi, slope, x_max, y_max, scale_x,
-                              scale_y, inclusive, d_edges + 2 * acc, room, d_cnt, d_cnt + 1, s);
+      rc = model ? ppk_dist_bgmm_edges_dev(p.ref, p.qry, kmers, random_tbl, n_clu, flags, lo, hi, model,
+                                           d_edges + 2 * acc, room, d_cnt, d_cnt + 1, s)
+                 : ppk_dist_edges_dev(p.ref, p.qry, kmers, random_tbl, n_clu, flags, lo, hi, slope, x_max, y_max,
+                                      scale_x, scale_y, inclusive, d_edges + 2 * acc, room, d_cnt, d_cnt + 1, s);
       if (rc != PPK_OK) return fail(rc);
       g_trace.mark(p.dup, "e_launched", (long long)lo);
       unsigned long long h[2] = {0, 0};
@@ -1628,7 +1631,7 @@ namespace {
 int query_edges_dbs_locked(const ppk_db *const *refs, const ppk_db *const *qrys, int n_dev,
                            const int32_t *kmers, const float *random_tbl, size_t n_clu, int flags,
                            int slope, float x_max, float y_max, float scale_x, float scale_y,
-                           int inclusive, long long *ij_out, size_t cap, size_t *n_edges,
+                           int inclusive, const ppk_bgmm *model, long long *ij_out, size_t cap, size_t *n_edges,
                            unsigned long long *n_failed) {
   if (n_edges) *n_edges = 0;
   if (n_failed) *n_failed = 0;
@@ -1662,8 +1665,8 @@ int query_edges_dbs_locked(const ppk_db *const *refs, const ppk_db *const *qrys,
     EdgePart &p = parts[(size_t)d];
     p.q_begin = bounds[(size_t)d];
     p.q_end = bounds[(size_t)d + 1];
-    auto work = [&p, kmers, random_tbl, n_clu, flags, slope, x_max, y_max, scale_x, scale_y, inclusive]() {
-      run_edge_part(p, kmers, random_tbl, n_clu, flags, slope, x_max, y_max, scale_x, scale_y, inclusive);
+    auto work = [&p, kmers, random_tbl, n_clu, flags, slope, x_max, y_max, scale_x, scale_y, inclusive, model]() {
+      run_edge_part(p, kmers, random_tbl, n_clu, flags, slope, x_max, y_max, scale_x, scale_y, inclusive, model);
     };
     if (n_dev == 1) work();
     else th.push_back(ppk_pool_run(work));
@@ -1729,7 +1732,24 @@ extern "C" int ppk_query_edges_dbs(const ppk_db *const *refs, const ppk_db *cons
   g_trace.t0 = now_ms();
   g_trace.mark(-1, "e_enter");
   const int rc = query_edges_dbs_locked(refs, qrys, n_dev, kmers, random_tbl, n_clu, flags, slope, x_max, y_max, scale_x,
-                                        scale_y, inclusive, ij_out, cap, n_edges, n_failed);
+                                        scale_y, inclusive, nullptr, ij_out, cap, n_edges, n_failed);
+  g_trace.mark(-1, "e_return", n_edges ? (long long)*n_edges : -1);
+  return rc;
+}
+
+// the same with the label test of a fitted BGMM (queryDatabase -> BGMMFit.assign -> generateTuples)
+extern "C" int ppk_query_bgmm_edges_dbs(const ppk_db *const *refs, const ppk_db *const *qrys, int n_dev,
+                                        const int32_t *kmers, const float *random_tbl, size_t n_clu, int flags,
+                                        const ppk_bgmm *model, long long *ij_out, size_t cap, size_t *n_edges,
+                                        unsigned long long *n_failed) {
+  if (n_edges) *n_edges = 0;
+  if (n_failed) *n_failed = 0;
+  if (!model) return ppk_fail(PPK_ERR_ARG, "model is NULL");
+  std::lock_guard<std::mutex> lk(g_query_mu);
+  g_trace.t0 = now_ms();
+  g_trace.mark(-1, "e_enter");
+  const int rc = query_edges_dbs_locked(refs, qrys, n_dev, kmers, random_tbl, n_clu, flags, 2, 0.f, 0.f, 1.f, 1.f, 0,
+                                        model, ij_out, cap, n_edges, n_failed);
   g_trace.mark(-1, "e_return", n_edges ? (long long)*n_edges : -1);
   return rc;
 }
@@ -1789,7 +1809,7 @@ extern "C" int ppk_query_edges(const uint64_t *ref_sk, size_t n_ref, const uint6
   }
   if (rc == PPK_OK)
     rc = query_edges_dbs_locked(refs.data(), n_qry ? qrys.data() : nullptr, n_dev, kmers, random_tbl, n_clu, flags, slope,
-                                x_max, y_max, scale_x, scale_y, inclusive, ij_out, cap, n_edges, n_failed);
+                                x_max, y_max, scale_x, scale_y, inclusive, nullptr, ij_out, cap, n_edges, n_failed);
   const std::string keep = ppk_error();
   for (ppk_db *db : owned) ppk_db_destroy(db);
   if (rc != PPK_OK) ppk_set_error(keep);

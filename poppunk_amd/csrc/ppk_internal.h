@@ -197,13 +197,23 @@ int ppk_launch_mask_from_dist_counted(const float *d_dist, size_t n_rows, int sl
                                       int inclusive, uint64_t *d_mask, void *d_ws, hipStream_t s);
 int ppk_launch_assign(const float *d_dist, size_t n_rows, int slope, float x_max, float y_max,
                       float *d_out, hipStream_t s);
+// BGMM assignment: labels and / or responsibilities (ppk_bgmm.hip); the edge list's predicate pass (ppk_boundary.hip),
+// counted and pair-interleaved like ppk_launch_mask_from_dist_counted's, or row-order for unaligned buffers
+int ppk_launch_bgmm_assign(const float *d_dist, size_t n_rows, const ppk_bgmm &m, int32_t *d_labels, float *d_resp,
+                           hipStream_t s);
+int ppk_launch_mask_from_bgmm_counted(const float *d_dist, size_t n_rows, const ppk_bgmm &m, uint64_t *d_mask,
+                                      void *d_ws, hipStream_t s);      // (d_dist 16-byte aligned)
+int ppk_launch_mask_from_bgmm(const float *d_dist, size_t n_rows, const ppk_bgmm &m, uint64_t *d_mask, hipStream_t s);
+// the model into scratch slot SLOT_BGMM of `dev`, enqueued on `s` (the caller holds a PpkCall)
+int ppk_bgmm_to_device(int dev, const ppk_bgmm &m, const ppk_bgmm **d_model, hipStream_t s);
 
 // grow-only per-device scratch (ppk_api.hip)
 enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 4, SLOT_ITER_C = 5,
        SLOT_BOUNDS = 6, SLOT_HOST_IN = 7,      // HOST_IN: the uploaded input of a host-array call
        SLOT_TICKETS = 8,                       // one counter per tile of a k-split job: zero when allocated, left zero by every launch
        SLOT_WIDE = 9,                          // spill-slot pool of the wide-k tile kernel: its first page (the slot bitmap) zero when allocated, left zero by every launch
-       SLOT_COUNT = 10 };
+       SLOT_BGMM = 10,                         // the device copy of a ppk_bgmm that the fused BGMM edge call's tile kernels read
+       SLOT_COUNT = 11 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and
@@ -272,6 +282,63 @@ __device__ __forceinline__ float ppk_line_dist(float x0, float y0, float x_max, 
     side = __fsub_rn(y0, y_max);
   }
   return side;
+}
+
+// BGMMFit assignment of one row (PopPUNK/bgmm.py:100-176, PopPUNK/models.py:181-187), the ONE statement every
+// BGMM path uses (kernel 2 and the fused tile epilogues), so that the fused edge list equals the two-step one bit for
+// bit.  xs = x / scale in the dtype numpy promotes to (float32 / float32, or float64).  The triangular solve and the
+// quadratic form are six fused multiply-adds per component on the constants ppk_bgmm_prepare computed in double
+// (ppk_bgmm::lin): the pass is VALU-issue bound (profiles/bgmm/), and the explicit fma() is the operation count that
+// matters -- its rounding differs from the reference's separate multiply and add by a few units in the last place of
+// lpr, far below the 1e-9 the label comparison allows.
+__device__ __forceinline__ void ppk_bgmm_scaled(float core, float acc, const ppk_bgmm &m, double &xs, double &ys) {
+  if (m.scale_is_f64) {
+    xs = (double)core / m.scale_f64[0];
+    ys = (double)acc / m.scale_f64[1];
+  } else {
+    xs = (double)__fdiv_rn(core, m.scale_f32[0]);
+    ys = (double)__fdiv_rn(acc, m.scale_f32[1]);
+  }
+}
+__device__ __forceinline__ double ppk_bgmm_lpr(double xs, double ys, const ppk_bgmm &m, int c) {
+  const double *l = m.lin[c];
+  const double z0 = __builtin_fma(xs, l[0], l[1]);
+  const double z1 = __builtin_fma(ys, l[2], __builtin_fma(z0, l[3], l[4]));
+  return __builtin_fma(-0.5, __builtin_fma(z0, z0, z1 * z1), m.log_const[c]);
+}
+// argmax_c lpr_c, the first index on ties (np.argmax of the responsibilities, which keep the order of lpr): no
+// transcendental.  KT > 0: the component count as a compile-time constant (kernel 2's instantiations for K <= 4: the
+// loop unrolls and the model's constants stay in scalar registers across rows); 0: m.K at run time.  The arithmetic
+// is the same statement in the same order either way.
+template <int KT = 0>
+__device__ __forceinline__ int ppk_bgmm_label_k(double xs, double ys, const ppk_bgmm &m) {
+  double best = ppk_bgmm_lpr(xs, ys, m, 0);
+  int label = 0;
+  if constexpr (KT > 0) {
+#pragma unroll
+    for (int c = 1; c < KT; ++c) {
+      const double v = ppk_bgmm_lpr(xs, ys, m, c);
+      if (v > best) {
+        best = v;
+        label = c;
+      }
+    }
+  } else {
+    for (int c = 1; c < m.K; ++c) {
+      const double v = ppk_bgmm_lpr(xs, ys, m, c);
+      if (v > best) {
+        best = v;
+        label = c;
+      }
+    }
+  }
+  return label;
+}
+template <int KT = 0>
+__device__ __forceinline__ int ppk_bgmm_label(float core, float acc, const ppk_bgmm &m) {
+  double xs, ys;
+  ppk_bgmm_scaled(core, acc, m, xs, ys);
+  return ppk_bgmm_label_k<KT>(xs, ys, m);
 }
 
 // ---- helper threads ----------------------------------------------------------------

@@ -187,6 +187,29 @@ def dist(ref, qry=None, kmers=None, random_tbl=None, random_correct=True, jaccar
     return out, n_failed
 
 
+def _fused_edges(ref, qry, kmers, random_tbl, random_correct, q_begin, q_end, cap, what, launch):
+    """The fused kernel-1 edge calls (line boundary / BGMM): capacity guess, exact re-run when it was short.
+    `launch(ref_h, qry_h, kmers_p, tbl_p, n_clu, flags, q_begin, q_end, d_edges, cap, d_n_edges, d_n_failed, stream)`."""
+    torch = _torch()
+    _check_pair(ref, qry)
+    nq = qry.n if qry is not None else ref.n
+    q_end = nq if q_end is None else int(q_end)
+    kmers, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
+    rows = rows_in_band(ref.n, qry.n if qry is not None else 0, q_begin, q_end)
+    flags = FLAG_RANDOM_CORRECT if random_correct else 0
+    dev = torch.device("cuda:%d" % ref.device)
+    if cap is None:
+        cap = min(rows, max(1 << 20, rows // 8))
+    n_failed = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def call(edges, c, n_edges):
+        n_failed.zero_()
+        return launch(ref._h, qry._h if qry is not None else None, kmers.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr,
+                      n_clu, flags, q_begin, q_end, C.c_void_p(edges.data_ptr()), c, C.c_void_p(n_edges.data_ptr()),
+                      C.c_void_p(n_failed.data_ptr()), _stream_ptr(ref.device))
+    return _edges_dev(call, what, dev, cap), n_failed
+
+
 def dist_edges(ref, qry=None, kmers=None, random_tbl=None, random_correct=True, slope=2,
                x_max=0.0, y_max=0.0, scale=(1.0, 1.0), inclusive=True, q_begin=0, q_end=None,
                cap=None):
@@ -194,43 +217,17 @@ def dist_edges(ref, qry=None, kmers=None, random_tbl=None, random_correct=True, 
 
     The edge count is data dependent: the call runs with a capacity guess and is
     re-run with the exact size only if the guess was too small."""
-    torch = _torch()
     lib = _lib.lib()
-    _check_pair(ref, qry)
-    nq = qry.n if qry is not None else ref.n
-    q_end = nq if q_end is None else int(q_end)
-    kmers, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
-    rows = rows_in_band(ref.n, qry.n if qry is not None else 0, q_begin, q_end)
-    flags = FLAG_RANDOM_CORRECT if random_correct else 0
-    dev = "cuda:%d" % ref.device
-    if cap is None:
-        cap = min(rows, max(1 << 20, rows // 8))
-    with torch.cuda.device(ref.device):
-        while True:
-            edges = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dev)
-            n_edges = torch.zeros(1, dtype=torch.int64, device=dev)
-            n_failed = torch.zeros(1, dtype=torch.int64, device=dev)
-            rc = lib.ppk_dist_edges_dev(ref._h, qry._h if qry is not None else None,
-                                        kmers.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr, n_clu,
-                                        flags, q_begin, q_end, int(slope), float(x_max),
-                                        float(y_max), float(scale[0]), float(scale[1]),
-                                        1 if inclusive else 0, C.c_void_p(edges.data_ptr()), cap,
-                                        C.c_void_p(n_edges.data_ptr()),
-                                        C.c_void_p(n_failed.data_ptr()), _stream_ptr(ref.device))
-            _lib.check(rc, "ppk_dist_edges_dev")
-            n = int(n_edges.item())
-            if n <= cap:
-                return edges[:n], n_failed
-            cap = n
+    return _fused_edges(ref, qry, kmers, random_tbl, random_correct, q_begin, q_end, cap, "ppk_dist_edges_dev",
+                        lambda r, q, k, t, nc, fl, qb, qe, e, c, ne, nf, st: lib.ppk_dist_edges_dev(
+                            r, q, k, t, nc, fl, qb, qe, int(slope), float(x_max), float(y_max), float(scale[0]),
+                            float(scale[1]), 1 if inclusive else 0, e, c, ne, nf, st))
 
 
-def edges_host(refs, qrys=None, kmers=None, random_tbl=None, random_correct=True, slope=2, x_max=0.0,
-               y_max=0.0, scale=(1.0, 1.0), inclusive=True, cap=None):
-    """ppk_query_edges_dbs: the edge list of the whole matrix as a host int64 [m, 2] array, computed by
-    every device that holds a copy of the database (`refs` / `qrys`: one SketchDB per device, or a single
-    SketchDB), each on its band of rows, one worker thread per device inside the library.
-    Returns (edges, n_failed)."""
-    import numpy as np
+def _host_edges(refs, qrys, kmers, random_tbl, random_correct, cap, what, launch):
+    """The multi-device host edge calls (line boundary / BGMM): one SketchDB per device (or a single one), a host int64
+    [m, 2] array, the parked list fetched when `cap` was too small.
+    `launch(refs_h, qrys_h, n_dev, kmers_p, tbl_p, n_clu, flags, out_p, cap, byref(n_edges), byref(n_failed))`."""
     lib = _lib.lib()
     refs = [refs] if isinstance(refs, SketchDB) else list(refs)
     if qrys is not None:
@@ -251,15 +248,114 @@ def edges_host(refs, qrys=None, kmers=None, random_tbl=None, random_correct=True
     out = np.empty((max(int(cap), 1), 2), dtype=np.int64)
     n_edges = C.c_size_t(0)
     n_failed = C.c_ulonglong(0)
-    rc = lib.ppk_query_edges_dbs(rh, qh, len(refs), kmers.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr, n_clu,
-                                 FLAG_RANDOM_CORRECT if random_correct else 0, int(slope), float(x_max),
-                                 float(y_max), float(scale[0]), float(scale[1]), 1 if inclusive else 0,
-                                 out.ctypes.data_as(llp), int(cap), C.byref(n_edges), C.byref(n_failed))
+    rc = launch(rh, qh, len(refs), kmers.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr, n_clu,
+                FLAG_RANDOM_CORRECT if random_correct else 0, out.ctypes.data_as(llp), int(cap), C.byref(n_edges),
+                C.byref(n_failed))
     if rc == _lib.ERR_CAPACITY:
         out = np.empty((n_edges.value, 2), dtype=np.int64)
         rc = lib.ppk_parked_fetch(out.ctypes.data_as(llp), None, None, n_edges.value, None)
-    _lib.check(rc, "ppk_query_edges_dbs")
+    _lib.check(rc, what)
     return out[:n_edges.value], int(n_failed.value)
+
+
+def edges_host(refs, qrys=None, kmers=None, random_tbl=None, random_correct=True, slope=2, x_max=0.0,
+               y_max=0.0, scale=(1.0, 1.0), inclusive=True, cap=None):
+    """ppk_query_edges_dbs: the edge list of the whole matrix as a host int64 [m, 2] array, computed by
+    every device that holds a copy of the database (`refs` / `qrys`: one SketchDB per device, or a single
+    SketchDB), each on its band of rows, one worker thread per device inside the library.
+    Returns (edges, n_failed)."""
+    lib = _lib.lib()
+    return _host_edges(refs, qrys, kmers, random_tbl, random_correct, cap, "ppk_query_edges_dbs",
+                       lambda rh, qh, nd, k, t, nc, fl, o, c, ne, nf: lib.ppk_query_edges_dbs(
+                           rh, qh, nd, k, t, nc, fl, int(slope), float(x_max), float(y_max), float(scale[0]),
+                           float(scale[1]), 1 if inclusive else 0, o, c, ne, nf))
+
+
+def _check_dist_tensor(dist_t):
+    torch = _torch()
+    if not (dist_t.is_cuda and dist_t.dtype == torch.float32 and dist_t.is_contiguous()
+            and dist_t.dim() == 2 and dist_t.shape[1] == 2):
+        raise TypeError("distMat must be a C-contiguous float32 [n,2] CUDA tensor")
+
+
+def bgmm_assign_dev(dist_t, model, labels=True, values=False):
+    """BGMMFit.assign on a resident float32 [n,2] CUDA tensor with a prepared model (`_lib.Bgmm`).
+    Returns (labels int32 [n] or None, responsibilities float32 [n, K] or None)."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    if not (labels or values):
+        raise ValueError("ask for labels, responsibilities or both")
+    n = dist_t.shape[0]
+    with torch.cuda.device(dist_t.device):
+        lab = torch.empty(n, dtype=torch.int32, device=dist_t.device) if labels else None
+        resp = torch.empty((n, model.K), dtype=torch.float32, device=dist_t.device) if values else None
+        rc = _lib.lib().ppk_bgmm_assign_dev(C.c_void_p(dist_t.data_ptr()), n, C.byref(model),
+                                            C.c_void_p(lab.data_ptr()) if lab is not None else None,
+                                            C.c_void_p(resp.data_ptr()) if resp is not None else None,
+                                            _stream_ptr(dist_t.device.index))
+        _lib.check(rc, "ppk_bgmm_assign_dev")
+    return lab, resp
+
+
+def _edges_dev(call, what, device, cap):
+    """Run an edge-list call with a capacity guess, once more with the exact size if the guess was short."""
+    torch = _torch()
+    with torch.cuda.device(device):
+        while True:
+            edges = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=device)
+            n_edges = torch.zeros(1, dtype=torch.int64, device=device)
+            _lib.check(call(edges, cap, n_edges), what)
+            m = int(n_edges.item())
+            if m <= cap:
+                return edges[:m]
+            cap = m
+
+
+def bgmm_edges_dev(dist_t, model, n_ref=0, int_offset=0, cap=None):
+    """Rows labelled model.within_label -> int64 [m,2] edges in generateTuples order (n_ref 0: self)."""
+    _check_dist_tensor(dist_t)
+    n = dist_t.shape[0]
+    if cap is None:
+        cap = min(n, max(1 << 20, n // 8))
+    return _edges_dev(lambda e, c, ne: _lib.lib().ppk_bgmm_edges_dev(
+        C.c_void_p(dist_t.data_ptr()), n, int(n_ref), C.byref(model), int(int_offset), C.c_void_p(e.data_ptr()), c,
+        C.c_void_p(ne.data_ptr()), _stream_ptr(dist_t.device.index)), "ppk_bgmm_edges_dev", dist_t.device, cap)
+
+
+def generate_tuples_dev(assign_t, within_label, self_comparison=True, num_ref=0, int_offset=0, cap=None):
+    """poppunk_refine.generateTuples on a resident int32 [n] CUDA tensor -> int64 [m,2]."""
+    torch = _torch()
+    if not (assign_t.is_cuda and assign_t.dtype == torch.int32 and assign_t.is_contiguous()):
+        raise TypeError("assignments must be a contiguous int32 CUDA tensor")
+    n = assign_t.shape[0]
+    if cap is None:
+        cap = min(n, max(1 << 20, n // 8))
+    return _edges_dev(lambda e, c, ne: _lib.lib().ppk_generate_tuples_dev(
+        C.c_void_p(assign_t.data_ptr()), n, int(within_label), 1 if self_comparison else 0, int(num_ref),
+        int(int_offset), C.c_void_p(e.data_ptr()), c, C.c_void_p(ne.data_ptr()), _stream_ptr(assign_t.device.index)),
+        "ppk_generate_tuples_dev", assign_t.device, cap)
+
+
+def dist_bgmm_edges(ref, qry=None, kmers=None, random_tbl=None, model=None, random_correct=True, q_begin=0,
+                    q_end=None, cap=None):
+    """Fused kernel 1 + BGMM assignment + compaction (ppk_dist_bgmm_edges_dev).  Returns (edges int64 [n_edges,2]
+    CUDA, n_failed); capacity guess, exact re-run when it was short (as dist_edges)."""
+    if model is None:
+        raise ValueError("a prepared BGMM model is needed")
+    lib = _lib.lib()
+    return _fused_edges(ref, qry, kmers, random_tbl, random_correct, q_begin, q_end, cap, "ppk_dist_bgmm_edges_dev",
+                        lambda r, q, k, t, nc, fl, qb, qe, e, c, ne, nf, st: lib.ppk_dist_bgmm_edges_dev(
+                            r, q, k, t, nc, fl, qb, qe, C.byref(model), e, c, ne, nf, st))
+
+
+def bgmm_edges_host(refs, qrys=None, kmers=None, random_tbl=None, model=None, random_correct=True, cap=None):
+    """ppk_query_bgmm_edges_dbs: edges_host with the BGMM label test.  Returns (edges int64 [m,2] host, n_failed)."""
+    if model is None:
+        raise ValueError("a prepared BGMM model is needed")
+    lib = _lib.lib()
+    return _host_edges(refs, qrys, kmers, random_tbl, random_correct, cap, "ppk_query_bgmm_edges_dbs",
+                       lambda rh, qh, nd, k, t, nc, fl, o, c, ne, nf: lib.ppk_query_bgmm_edges_dbs(
+                           rh, qh, nd, k, t, nc, fl, C.byref(model), o, c, ne, nf))
 
 
 def assign_threshold_dev(dist_t, slope, x_max, y_max, out=None):

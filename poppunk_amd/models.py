@@ -13,7 +13,13 @@ boundary, models.py:846-954) is outside the hot path; a fitted boundary is the i
   * `edges(X)`           : assign -> generateTuples(y, within_label = -1)
   * `edges_from_sketches(db, ...)` : distances, X/scale, boundary and edge compaction fused in
                            one pass (`engine.dist_edges`): the distance matrix never exists
+
+`BGMMModel` is the same for PopPUNK's default model, a fitted Bayesian Gaussian mixture: the assignment half of
+`BGMMFit` (PopPUNK/models.py:359-375 load, :411-465 assign; PopPUNK/bgmm.py:100-176 log_likelihood) and the
+edge list `construct_network_from_assignments` builds from it.
 """
+import ctypes as C
+
 import numpy as np
 
 from . import engine, poppunk_refine
@@ -90,6 +96,115 @@ class RefineBoundary:
         return engine.dist_edges(db, qry_db, kmers, random_tbl, slope=slope, x_max=float(x_max),
                                  y_max=float(y_max), scale=tuple(float(v) for v in self.scale),
                                  inclusive=False, **kw)
+
+
+# ---- BGMM assignment (PopPUNK's default --fit-model bgmm) -----------------------------------------------
+class BGMMModel:
+    """A fitted BGMM model (the state `BGMMFit.assign` reads), assignment only: fitting stays with sklearn.
+
+      * `from_npz(path_or_mapping)` : the arrays `BGMMFit.load` reads from `<prefix>_fit.npz` (models.py:359-375);
+                                      the `_fit.pkl` is never opened (unpickling needs sklearn and runs code)
+      * `assign(X, values=False)`   : `BGMMFit.assign` (models.py:411-465) through ppk_bgmm_assign: int64 labels, or
+                                      the float32 [n, K] responsibilities with values=True
+      * `assign_dev(dist_t, values=False)` : the same on a resident CUDA matrix (int32 labels / float32 resp)
+      * `edges(X, ...)`             : assign -> generateTuples(y, within_label, ...) (network.py:1170-1184)
+      * `edges_from_sketches(db, qry_db, kmers, random_tbl)` : distances, assignment and edge compaction fused
+                                      in one pass (engine.dist_bgmm_edges): the distance matrix never exists
+      * `edges_host(refs, qrys, kmers, random_tbl)` : the same on one or several devices into a host array
+    """
+
+    def __init__(self, weights, means, covariances, scale, within_label, between_label=None):
+        from . import _lib
+        self.weights = np.asarray(weights, dtype=np.float64).reshape(-1)
+        K = self.weights.shape[0]
+        self.means = np.asarray(means, dtype=np.float64).reshape(K, 2)
+        self.covariances = np.asarray(covariances, dtype=np.float64).reshape(K, 2, 2)
+        self.scale = np.asarray(scale)
+        if self.scale.dtype not in (np.float32, np.float64):
+            self.scale = self.scale.astype(np.float64)
+        self.within_label = int(within_label)
+        self.between_label = None if between_label is None else int(between_label)
+        self.n_components = K
+        # PopPUNK's scale is np.amax of the float32 matrix: X / scale is then a float32 quotient; a float64 scale
+        # gives a float64 one (numpy's promotion, models.py:246-254)
+        self._model = _lib.Bgmm()
+        arrays = [np.ascontiguousarray(a, dtype=np.float64)
+                  for a in (self.weights, self.means, self.covariances, self.scale.reshape(2))]
+        ptrs = [a.ctypes.data_as(C.POINTER(C.c_double)) for a in arrays]
+        rc = _lib.lib().ppk_bgmm_prepare(K, *ptrs, 1 if self.scale.dtype == np.float64 else 0, self.within_label,
+                                         self._model)
+        if rc == _lib.ERR_ARG:      # the reference's ValueError (bgmm.py:170-172) and bad shapes
+            raise ValueError(_lib.last_error())
+        _lib.check(rc, "ppk_bgmm_prepare")
+        self.fitted = True
+
+    @classmethod
+    def from_npz(cls, source):
+        """`source`: a path to `<prefix>_fit.npz` or a mapping of its arrays."""
+        if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__"):
+            with np.load(source, allow_pickle=False) as z:
+                d = {k: z[k] for k in z.files}
+        else:
+            d = dict(source)
+        keys = set(d)
+        if {"intercept", "core_acc_intercepts"} & keys:
+            raise ValueError("this is a refine/threshold fit (RefineFit, models.py:1001-1026): use RefineBoundary")
+        if {"n_clusters", "maxs", "mins"} & keys:
+            raise ValueError("this is a DBSCAN fit (DBSCANFit, models.py:618-657): its assignment "
+                             "(hdbscan.approximate_predict) needs the fitted condensed tree and has no per-row closed "
+                             "form, so it is not supported here")
+        missing = [k for k in ("weights", "means", "covariances", "scale", "within", "between") if k not in keys]
+        if missing:
+            raise ValueError("not a BGMM fit: missing %s" % ", ".join(missing))
+        return cls(d["weights"], d["means"], d["covariances"], d["scale"], np.asarray(d["within"]).item(),
+                   np.asarray(d["between"]).item())
+
+    @property
+    def model(self):
+        """The prepared `_lib.Bgmm` the entry points take."""
+        return self._model
+
+    def _check(self):
+        if not self.fitted:
+            raise RuntimeError("Trying to assign using an unfitted model")
+
+    def assign(self, X, values=False, device_id=0):
+        """models.py:411-465: int64 labels [n] (np.zeros(n, dtype=int)), or float32 responsibilities [n, K] with
+        values=True (the array has X's dtype in the reference; distances are float32)."""
+        from . import _lib
+        self._check()
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != 2:
+            raise ValueError("X must be [n, 2] (core, accessory)")
+        n = X.shape[0]
+        lab = None if values else np.empty(n, dtype=np.int32)
+        resp = np.empty((n, self.n_components), dtype=np.float32) if values else None
+        rc = _lib.lib().ppk_bgmm_assign(X.ctypes.data_as(C.POINTER(C.c_float)), n, self._model, int(device_id),
+                                        lab.ctypes.data_as(C.POINTER(C.c_int32)) if lab is not None else None,
+                                        resp.ctypes.data_as(C.POINTER(C.c_float)) if resp is not None else None)
+        _lib.check(rc, "ppk_bgmm_assign")
+        return resp if values else lab.astype(np.int64)
+
+    def assign_dev(self, dist_t, values=False):
+        self._check()
+        lab, resp = engine.bgmm_assign_dev(dist_t, self._model, labels=not values, values=values)
+        return resp if values else lab
+
+    def edges(self, X, self_comparison=True, num_ref=0, int_offset=0):
+        """assign -> generateTuples(assignments, within_label, self, num_ref, int_offset) (network.py:1180-1184)."""
+        y = self.assign(X)
+        return poppunk_refine.generateTuples(y, self.within_label, self=self_comparison, num_ref=num_ref,
+                                             int_offset=int_offset)
+
+    def edges_from_sketches(self, db, qry_db, kmers, random_tbl, **kw):
+        """CUDA int64 [n_edges, 2]: the pairs assigned within_label, in generateTuples order; and n_failed."""
+        self._check()
+        return engine.dist_bgmm_edges(db, qry_db, kmers, random_tbl, model=self._model, **kw)
+
+    def edges_host(self, refs, qrys, kmers, random_tbl, **kw):
+        """The same as a host int64 [m, 2] array over every device holding a copy of the database; and n_failed."""
+        self._check()
+        return engine.bgmm_edges_host(refs, qrys, kmers, random_tbl, model=self._model, **kw)
 
 
 # ---- the lineage models' neighbour matrices (PopPUNK/models.py:1095-1385) -----------------------------
