@@ -755,11 +755,11 @@ static int dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *k
       rc = ppk_launch_dist(ref, qry, kmers, d_rtab, d_rtab ? n_clu : 1, flags, 0, nq, d_dist, d_n_failed,
                            nullptr, slope, x_max, y_max, scale_x, scale_y, inclusive, d_lut, s);
       if (rc != PPK_OK) return rc;
-      if (model)
-        return ppk_bgmm_edges_dev(static_cast<float *>(d_dist), rows, qry ? ref->n : 0, model, 0, d_edges, cap,
-                                  d_n_edges, stream);
-      return ppk_edge_threshold_dev(static_cast<float *>(d_dist), rows, qry ? ref->n : 0, slope, x_max,
-                                    y_max, inclusive, d_edges, cap, d_n_edges, stream);
+      RowTest t = {};
+      t.kind = model ? RowTest::BGMM : RowTest::LINE;
+      if (model) t.bgmm = *model;
+      t.slope = slope, t.inclusive = inclusive, t.x_max = x_max, t.y_max = y_max;
+      return ppk_row_edges(d_dist, rows, qry ? ref->n : 0, 0, t, d_edges, cap, d_n_edges, s);
     }
   }
   const size_t n_rtiles = (ref->n + 63) / 64;
@@ -1141,63 +1141,15 @@ extern "C" int ppk_assign_threshold_dev(const float *d_dist, size_t n_rows, int 
   return ppk_launch_assign(d_dist, n_rows, slope, x_max, y_max, d_out, static_cast<hipStream_t>(stream));
 }
 
-static size_t samples_of_rows(size_t n_rows) {
-  size_t n = (size_t)(0.5 * (1.0 + std::sqrt(1.0 + 8.0 * (double)n_rows)));
-  while (n > 1 && n * (n - 1) / 2 > n_rows) --n;
-  while ((n + 1) * n / 2 <= n_rows) ++n;
-  return n;
-}
-
-static int edges_from_mask(int dev, size_t n_rows, const EdgeGeom &g, uint64_t *d_mask,
-                           long long *d_edges, size_t cap, unsigned long long *d_n_edges,
-                           hipStream_t s) {
-  void *d_ws = nullptr;
-  const size_t n_words = ppk_mask_words_linear(n_rows);
-  int rc = scratch_get(dev, SLOT_WS, ppk_compact_ws_bytes(n_words), &d_ws);
-  if (rc != PPK_OK) return rc;
-  return ppk_launch_compact(d_mask, n_words, g, d_ws, d_edges, cap, d_n_edges, s);
-}
-
 extern "C" int ppk_edge_threshold_dev(const float *d_dist, size_t n_rows, size_t n_ref, int slope,
                                       float x_max, float y_max, int inclusive, long long *d_edges,
                                       size_t cap, unsigned long long *d_n_edges, void *stream) {
   if (slope < 0 || slope > 2) return ppk_fail(PPK_ERR_ARG, "slope must be 0, 1 or 2");
   if (!d_n_edges) return ppk_fail(PPK_ERR_ARG, "d_n_edges is NULL");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int dev = 0;
-  PPK_HIP(hipGetDevice(&dev));
-  PpkCall call(dev, s);
-  EdgeGeom g = {};
-  g.n_rows = n_rows;
-  if (n_ref == 0) {
-    g.layout = EDGE_LINEAR_SELF;
-    g.n_samples = samples_of_rows(n_rows);
-    if (g.n_samples * (g.n_samples - 1) / 2 != n_rows)
-      return ppk_fail(PPK_ERR_ARG, "row count is not n(n-1)/2 for any n (self/condensed matrix expected)");
-  } else {
-    g.layout = EDGE_LINEAR_NONSELF;
-    g.n_ref = n_ref;
-    if (n_rows % n_ref) return ppk_fail(PPK_ERR_ARG, "row count is not a multiple of n_ref");
-  }
-  void *d_mask = nullptr;
-  int rc = scratch_get(dev, SLOT_MASK, ppk_mask_words_linear(n_rows) * sizeof(uint64_t) + 16, &d_mask);
-  if (rc != PPK_OK) return rc;
-  if ((reinterpret_cast<uintptr_t>(d_dist) & 15) == 0) {
-    // 16-byte loads, and the compaction's counting pass folded into the predicate pass (three launches, not four)
-    void *d_ws = nullptr;
-    const size_t n_words = ppk_mask_words_linear(n_rows);
-    rc = scratch_get(dev, SLOT_WS, ppk_compact_ws_bytes(n_words), &d_ws);
-    if (rc != PPK_OK) return rc;
-    rc = ppk_launch_mask_from_dist_counted(d_dist, n_rows, slope, x_max, y_max, inclusive,
-                                           static_cast<uint64_t *>(d_mask), d_ws, s);
-    if (rc != PPK_OK) return rc;
-    g.pair_interleaved = 1;
-    return ppk_launch_compact(static_cast<uint64_t *>(d_mask), n_words, g, d_ws, d_edges, cap, d_n_edges, s, true);
-  }
-  rc = ppk_launch_mask_from_dist(d_dist, n_rows, slope, x_max, y_max, inclusive,
-                                 static_cast<uint64_t *>(d_mask), s);
-  if (rc != PPK_OK) return rc;
-  return edges_from_mask(dev, n_rows, g, static_cast<uint64_t *>(d_mask), d_edges, cap, d_n_edges, s);
+  RowTest t = {};
+  t.kind = RowTest::LINE;
+  t.slope = slope, t.inclusive = inclusive, t.x_max = x_max, t.y_max = y_max;
+  return ppk_row_edges(d_dist, n_rows, n_ref, 0, t, d_edges, cap, d_n_edges, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ppk_bgmm_assign_dev(const float *d_dist, size_t n_rows, const ppk_bgmm *model, int32_t *d_labels,
@@ -1214,39 +1166,10 @@ extern "C" int ppk_bgmm_edges_dev(const float *d_dist, size_t n_rows, size_t n_r
                                   unsigned long long *d_n_edges, void *stream) {
   if (int rc = check_bgmm(model)) return rc;
   if (!d_n_edges) return ppk_fail(PPK_ERR_ARG, "d_n_edges is NULL");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int dev = 0;
-  PPK_HIP(hipGetDevice(&dev));
-  PpkCall call(dev, s);
-  EdgeGeom g = {};
-  g.n_rows = n_rows;
-  g.int_offset = int_offset;
-  if (n_ref == 0) {
-    g.layout = EDGE_LINEAR_SELF;
-    g.n_samples = samples_of_rows(n_rows);
-    if (g.n_samples * (g.n_samples - 1) / 2 != n_rows)
-      return ppk_fail(PPK_ERR_ARG, "row count is not n(n-1)/2 for any n (self/condensed matrix expected)");
-  } else {
-    g.layout = EDGE_LINEAR_NONSELF;
-    g.n_ref = n_ref;
-    if (n_rows % n_ref) return ppk_fail(PPK_ERR_ARG, "row count is not a multiple of n_ref");
-  }
-  const size_t n_words = ppk_mask_words_linear(n_rows);
-  void *d_mask = nullptr, *d_ws = nullptr;
-  int rc = scratch_get(dev, SLOT_MASK, n_words * sizeof(uint64_t) + 16, &d_mask);
-  if (rc != PPK_OK) return rc;
-  rc = scratch_get(dev, SLOT_WS, ppk_compact_ws_bytes(n_words), &d_ws);
-  if (rc != PPK_OK) return rc;
-  if ((reinterpret_cast<uintptr_t>(d_dist) & 15) != 0) {
-    // a distance buffer that is not 16-byte aligned: a row-order mask, compacted uncounted
-    rc = ppk_launch_mask_from_bgmm(d_dist, n_rows, *model, static_cast<uint64_t *>(d_mask), s);
-    if (rc != PPK_OK) return rc;
-    return ppk_launch_compact(static_cast<uint64_t *>(d_mask), n_words, g, d_ws, d_edges, cap, d_n_edges, s);
-  }
-  rc = ppk_launch_mask_from_bgmm_counted(d_dist, n_rows, *model, static_cast<uint64_t *>(d_mask), d_ws, s);
-  if (rc != PPK_OK) return rc;
-  g.pair_interleaved = 1;
-  return ppk_launch_compact(static_cast<uint64_t *>(d_mask), n_words, g, d_ws, d_edges, cap, d_n_edges, s, true);
+  RowTest t = {};
+  t.kind = RowTest::BGMM;
+  t.bgmm = *model;
+  return ppk_row_edges(d_dist, n_rows, n_ref, int_offset, t, d_edges, cap, d_n_edges, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ppk_qc_edges_dev(const float *d_dist, size_t n_rows, size_t n_ref, int mode,
@@ -1254,28 +1177,10 @@ extern "C" int ppk_qc_edges_dev(const float *d_dist, size_t n_rows, size_t n_ref
                                 unsigned long long *d_n_edges, void *stream) {
   if (!d_n_edges) return ppk_fail(PPK_ERR_ARG, "d_n_edges is NULL");
   if (mode != 0 && mode != 1) return ppk_fail(PPK_ERR_ARG, "mode must be 0 (long) or 1 (zero)");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int dev = 0;
-  PPK_HIP(hipGetDevice(&dev));
-  PpkCall call(dev, s);
-  EdgeGeom g = {};
-  g.n_rows = n_rows;
-  if (n_ref == 0) {
-    g.layout = EDGE_LINEAR_SELF;
-    g.n_samples = samples_of_rows(n_rows);
-    if (g.n_samples * (g.n_samples - 1) / 2 != n_rows)
-      return ppk_fail(PPK_ERR_ARG, "row count is not n(n-1)/2 for any n (self/condensed matrix expected)");
-  } else {
-    g.layout = EDGE_LINEAR_NONSELF;
-    g.n_ref = n_ref;
-    if (n_rows % n_ref) return ppk_fail(PPK_ERR_ARG, "row count is not a multiple of n_ref");
-  }
-  void *d_mask = nullptr;
-  int rc = scratch_get(dev, SLOT_MASK, ppk_mask_words_linear(n_rows) * sizeof(uint64_t) + 8, &d_mask);
-  if (rc != PPK_OK) return rc;
-  rc = ppk_launch_mask_from_qc(d_dist, n_rows, mode, max_pi, max_a, static_cast<uint64_t *>(d_mask), s);
-  if (rc != PPK_OK) return rc;
-  return edges_from_mask(dev, n_rows, g, static_cast<uint64_t *>(d_mask), d_edges, cap, d_n_edges, s);
+  RowTest t = {};
+  t.kind = RowTest::QC;
+  t.mode = mode, t.max_pi = max_pi, t.max_a = max_a;
+  return ppk_row_edges(d_dist, n_rows, n_ref, 0, t, d_edges, cap, d_n_edges, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ppk_generate_tuples_dev(const int32_t *d_assign, size_t n_rows, int within_label,
@@ -1283,28 +1188,12 @@ extern "C" int ppk_generate_tuples_dev(const int32_t *d_assign, size_t n_rows, i
                                        long long *d_edges, size_t cap,
                                        unsigned long long *d_n_edges, void *stream) {
   if (!d_n_edges) return ppk_fail(PPK_ERR_ARG, "d_n_edges is NULL");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int dev = 0;
-  PPK_HIP(hipGetDevice(&dev));
-  PpkCall call(dev, s);
-  EdgeGeom g = {};
-  g.n_rows = n_rows;
-  g.int_offset = int_offset;
-  if (self) {
-    g.layout = EDGE_LINEAR_SELF;
-    // src/boundary.cpp:104 derives n from the row count the same way
-    g.n_samples = samples_of_rows(n_rows);
-  } else {
-    if (num_ref == 0) return ppk_fail(PPK_ERR_ARG, "num_ref must be > 0 when self is false");
-    g.layout = EDGE_LINEAR_NONSELF;
-    g.n_ref = num_ref;
-  }
-  void *d_mask = nullptr;
-  int rc = scratch_get(dev, SLOT_MASK, ppk_mask_words_linear(n_rows) * sizeof(uint64_t) + 8, &d_mask);
-  if (rc != PPK_OK) return rc;
-  rc = ppk_launch_mask_from_assign(d_assign, n_rows, within_label, static_cast<uint64_t *>(d_mask), s);
-  if (rc != PPK_OK) return rc;
-  return edges_from_mask(dev, n_rows, g, static_cast<uint64_t *>(d_mask), d_edges, cap, d_n_edges, s);
+  if (!self && num_ref == 0) return ppk_fail(PPK_ERR_ARG, "num_ref must be > 0 when self is false");
+  RowTest t = {};
+  t.kind = RowTest::LABEL;
+  t.within_label = within_label;
+  return ppk_row_edges(d_assign, n_rows, self ? 0 : num_ref, int_offset, t, d_edges, cap, d_n_edges,
+                       static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ppk_generate_all_tuples_dev(size_t num_ref, size_t num_queries, int self, long long int_offset,

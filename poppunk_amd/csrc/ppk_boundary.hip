@@ -1,8 +1,9 @@
 // Kernel 2: boundary assignment and edge-list compaction on gfx950.
 //
 //  - assign_kernel            : src/boundary.cpp:60-80  (assign_threshold)
-//  - mask_from_dist_kernel    : the predicate of src/boundary.cpp:82-95 (edge_iterate),
-//                               one wavefront __ballot -> one uint64 of 64 rows
+//  - mask_from_dist_kernel    : a row predicate (the line of src/boundary.cpp:82-95, a BGMM label, a
+//                               qcDistMat test), one wavefront __ballot -> one uint64 of 64 rows;
+//                               mask_from_dist_counted_kernel the same from 16-byte loads, with counts
 //  - mask_from_assign_kernel  : the predicate of src/boundary.cpp:97-123 (generate_tuples)
 //  - compaction (count / scan / expand): replaces the serial push_back loops;
 //    stable, so the edge list equals the reference's element for element.
@@ -49,8 +50,8 @@ assign_kernel_x2(const f32x4 *__restrict__ dist, size_t n_pairs, int slope, floa
   }
 }
 
-// Row predicates of the edge-list passes: the refine/threshold line (src/boundary.cpp:82-95) and the label test of a
-// fitted BGMM (ppk_bgmm_label; KT > 0: K as a compile-time constant).
+// Row predicates of the edge-list passes: the refine/threshold line (src/boundary.cpp:82-95), the label test of a
+// fitted BGMM (ppk_bgmm_label; KT > 0: K as a compile-time constant) and qcDistMat's tests (PopPUNK/qc.py:332,:349).
 struct LinePred {
   int slope;
   float x_max, y_max;
@@ -65,6 +66,14 @@ struct BgmmPred {
   ppk_bgmm m;
   __device__ __forceinline__ bool operator()(float x, float y) const {
     return ppk_bgmm_label<KT>(x, y, m) == m.within_label;
+  }
+};
+// mode 0 = distance too long (core > max_pi | acc > max_a), mode 1 = zero distance (core == 0 | acc == 0)
+struct QcPred {
+  int mode;
+  float max_pi, max_a;
+  __device__ __forceinline__ bool operator()(float x, float y) const {
+    return mode == 0 ? (x > max_pi || y > max_a) : (x == 0.0f || y == 0.0f);
   }
 };
 
@@ -85,60 +94,6 @@ mask_from_dist_kernel(const float2 *__restrict__ dist, size_t n_rows, const Pred
     }
     const uint64_t m = __ballot(pred);
     if (lane == 0) mask[w] = m;
-  }
-}
-
-// qcDistMat's row predicates (PopPUNK/qc.py:332,:349): mode 0 = distance too long
-// (core > max_pi | acc > max_a), mode 1 = zero distance (core == 0 | acc == 0)
-__global__ void __launch_bounds__(kBlock)
-mask_from_qc_kernel(const float2 *__restrict__ dist, size_t n_rows, int mode, float max_pi,
-                    float max_a, uint64_t *__restrict__ mask, size_t n_words) {
-  const size_t wstride = (size_t)gridDim.x * (kBlock / 64);
-  const int lane = threadIdx.x & 63;
-  for (size_t w = (size_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); w < n_words;
-       w += wstride) {
-    const size_t row = w * 64 + lane;
-    bool pred = false;
-    if (row < n_rows) {
-      const float2 d = dist[row];
-      pred = mode == 0 ? (d.x > max_pi || d.y > max_a) : (d.x == 0.0f || d.y == 0.0f);
-    }
-    const uint64_t m = __ballot(pred);
-    if (lane == 0) mask[w] = m;
-  }
-}
-
-// The same with 16-byte loads: a wavefront covers 128 consecutive rows, lane l holding rows 2l and
-// 2l+1.  Mask word A wants row v of the first 64 in bit v, i.e. the predicate of lane v/2, row
-// v%2: one ds_bpermute (the LDS crossbar, no memory traffic) per mask word moves each lane's two
-// predicate bits to the lane whose ballot position they belong to.
-__global__ void __launch_bounds__(kBlock)
-mask_from_dist_kernel_x2(const f32x4 *__restrict__ dist, size_t n_rows, int slope, float x_max,
-                         float y_max, int inclusive, uint64_t *__restrict__ mask, size_t n_words) {
-  const size_t n_w2 = (n_words + 1) / 2;        // pairs of mask words
-  const size_t wstride = (size_t)gridDim.x * (kBlock / 64);
-  const int lane = threadIdx.x & 63;
-  const int src_a = (lane >> 1) * 4, src_b = (32 + (lane >> 1)) * 4;   // byte lane ids for bpermute
-  for (size_t w2 = (size_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); w2 < n_w2; w2 += wstride) {
-    const size_t row = w2 * 128 + 2 * (size_t)lane;
-    int p = 0;
-    if (row + 1 < n_rows) {
-      const f32x4 d = __builtin_nontemporal_load(dist + (row >> 1));
-      const float s0 = ppk_line_dist(d.x, d.y, x_max, y_max, slope);
-      const float s1 = ppk_line_dist(d.z, d.w, x_max, y_max, slope);
-      p = (inclusive ? (s0 <= 0.0f) : (s0 < 0.0f)) ? 1 : 0;
-      p |= (inclusive ? (s1 <= 0.0f) : (s1 < 0.0f)) ? 2 : 0;
-    } else if (row < n_rows) {
-      const float2 d = reinterpret_cast<const float2 *>(dist)[row];
-      const float s0 = ppk_line_dist(d.x, d.y, x_max, y_max, slope);
-      p = (inclusive ? (s0 <= 0.0f) : (s0 < 0.0f)) ? 1 : 0;
-    }
-    const int pa = __builtin_amdgcn_ds_bpermute(src_a, p), pb = __builtin_amdgcn_ds_bpermute(src_b, p);
-    const uint64_t wa = __ballot((pa >> (lane & 1)) & 1), wb = __ballot((pb >> (lane & 1)) & 1);
-    if (lane == 0) {
-      mask[2 * w2] = wa;
-      if (2 * w2 + 1 < n_words) mask[2 * w2 + 1] = wb;
-    }
   }
 }
 
@@ -562,94 +517,90 @@ int ppk_launch_assign(const float *d_dist, size_t n_rows, int slope, float x_max
   return PPK_OK;
 }
 
-int ppk_launch_mask_from_dist(const float *d_dist, size_t n_rows, int slope, float x_max,
-                              float y_max, int inclusive, uint64_t *d_mask, hipStream_t s) {
-  const size_t n_words = ppk_mask_words_linear(n_rows);
-  if (n_words == 0) return PPK_OK;
-  if ((reinterpret_cast<uintptr_t>(d_dist) & 15) == 0) {
-    const unsigned grid = grid_for((n_words + 1) / 2, kBlock / 64, 4096);
-    hipLaunchKernelGGL(mask_from_dist_kernel_x2, dim3(grid), dim3(kBlock), 0, s,
-                       reinterpret_cast<const f32x4 *>(d_dist), n_rows, slope, x_max, y_max,
-                       inclusive, d_mask, n_words);
-  } else {
-    const unsigned grid = grid_for(n_words, kBlock / 64, 4096);
-    hipLaunchKernelGGL(mask_from_dist_kernel<LinePred>, dim3(grid), dim3(kBlock), 0, s,
-                       reinterpret_cast<const float2 *>(d_dist), n_rows, LinePred{slope, x_max, y_max, inclusive},
-                       d_mask, n_words);
-  }
-  PPK_HIP(hipGetLastError());
-  return PPK_OK;
-}
-
-// mask + per-block bit counts in one pass (d_ws as for ppk_launch_compact, which is then told the counts exist)
 namespace {
+// The mask pass of a distance-row test from a 16-byte aligned matrix: 16-byte loads, pair-interleaved words, and the
+// compaction's counting pass folded in (its block counts left in d_ws: three launches for the list, not four).
 template <class Pred>
-int launch_mask_counted(const float *d_dist, size_t n_rows, const Pred &pred, uint64_t *d_mask, void *d_ws,
-                        hipStream_t s) {
-  const size_t n_words = ppk_mask_words_linear(n_rows);
-  if (n_words == 0) return PPK_OK;
-  if ((reinterpret_cast<uintptr_t>(d_dist) & 15) != 0)
-    return ppk_fail(PPK_ERR_STATE, "internal: the counted mask pass needs a 16-byte aligned distance buffer");
+void launch_mask_counted(const float *d_dist, size_t n_rows, size_t n_words, const Pred &pred, uint64_t *d_mask,
+                         void *d_ws, hipStream_t s) {
   const size_t nb = (n_words + kWordsPerBlock - 1) / kWordsPerBlock;
-  if (nb > 0x7fffffffull) return ppk_fail(PPK_ERR_ARG, "edge mask too large for one launch");
   const size_t slots = 256 * 8;      // workgroups of 256 threads the device holds at once
   const unsigned per = (unsigned)((nb + slots - 1) / slots);
   hipLaunchKernelGGL(mask_from_dist_counted_kernel<Pred>, dim3((unsigned)((nb + per - 1) / per)), dim3(kBlock), 0, s,
                      reinterpret_cast<const f32x4 *>(d_dist), n_rows, pred, d_mask, n_words,
                      static_cast<unsigned long long *>(d_ws), nb, per);
-  PPK_HIP(hipGetLastError());
-  return PPK_OK;
+}
+
+// ... or, for any alignment, 8-byte loads and row-order words
+template <class Pred>
+void launch_mask(const float *d_dist, size_t n_rows, size_t n_words, const Pred &pred, bool counted, uint64_t *d_mask,
+                 void *d_ws, hipStream_t s) {
+  if (counted) return launch_mask_counted(d_dist, n_rows, n_words, pred, d_mask, d_ws, s);
+  hipLaunchKernelGGL(mask_from_dist_kernel<Pred>, dim3(grid_for(n_words, kBlock / 64, 4096)), dim3(kBlock), 0, s,
+                     reinterpret_cast<const float2 *>(d_dist), n_rows, pred, d_mask, n_words);
+}
+
+size_t samples_of_rows(size_t n_rows) {
+  size_t n = (size_t)(0.5 * (1.0 + std::sqrt(1.0 + 8.0 * (double)n_rows)));
+  while (n > 1 && n * (n - 1) / 2 > n_rows) --n;
+  while ((n + 1) * n / 2 <= n_rows) ++n;
+  return n;
 }
 }  // namespace
 
-int ppk_launch_mask_from_dist_counted(const float *d_dist, size_t n_rows, int slope, float x_max, float y_max,
-                                      int inclusive, uint64_t *d_mask, void *d_ws, hipStream_t s) {
-  return launch_mask_counted(d_dist, n_rows, LinePred{slope, x_max, y_max, inclusive}, d_mask, d_ws, s);
-}
-
-// K = 2, 3, 4 (every PopPUNK default fit: --K 2) with the component loop unrolled; other K at run time
-int ppk_launch_mask_from_bgmm_counted(const float *d_dist, size_t n_rows, const ppk_bgmm &m, uint64_t *d_mask,
-                                      void *d_ws, hipStream_t s) {
-  switch (m.K) {
-    case 2: return launch_mask_counted(d_dist, n_rows, BgmmPred<2>{m}, d_mask, d_ws, s);
-    case 3: return launch_mask_counted(d_dist, n_rows, BgmmPred<3>{m}, d_mask, d_ws, s);
-    case 4: return launch_mask_counted(d_dist, n_rows, BgmmPred<4>{m}, d_mask, d_ws, s);
-    default: return launch_mask_counted(d_dist, n_rows, BgmmPred<0>{m}, d_mask, d_ws, s);
+int ppk_row_edges(const void *d_rows, size_t n_rows, size_t n_ref, long long int_offset, const RowTest &t,
+                  long long *d_edges, size_t cap, unsigned long long *d_n_edges, hipStream_t s) {
+  int dev = 0;
+  PPK_HIP(hipGetDevice(&dev));
+  PpkCall call(dev, s);
+  const bool check_rows = t.kind != RowTest::LABEL;
+  EdgeGeom g = {};
+  g.n_rows = n_rows;
+  g.int_offset = int_offset;
+  if (n_ref == 0) {
+    g.layout = EDGE_LINEAR_SELF;
+    g.n_samples = samples_of_rows(n_rows);
+    if (check_rows && g.n_samples * (g.n_samples - 1) / 2 != n_rows)
+      return ppk_fail(PPK_ERR_ARG, "row count is not n(n-1)/2 for any n (self/condensed matrix expected)");
+  } else {
+    g.layout = EDGE_LINEAR_NONSELF;
+    g.n_ref = n_ref;
+    if (check_rows && n_rows % n_ref) return ppk_fail(PPK_ERR_ARG, "row count is not a multiple of n_ref");
   }
-}
-
-// row-order mask (any alignment: 8-byte loads), compacted without counts
-int ppk_launch_mask_from_bgmm(const float *d_dist, size_t n_rows, const ppk_bgmm &m, uint64_t *d_mask, hipStream_t s) {
   const size_t n_words = ppk_mask_words_linear(n_rows);
-  if (n_words == 0) return PPK_OK;
-  const unsigned grid = grid_for(n_words, kBlock / 64, 4096);
-  hipLaunchKernelGGL(mask_from_dist_kernel<BgmmPred<0>>, dim3(grid), dim3(kBlock), 0, s,
-                     reinterpret_cast<const float2 *>(d_dist), n_rows, BgmmPred<0>{m}, d_mask, n_words);
-  PPK_HIP(hipGetLastError());
-  return PPK_OK;
-}
-
-int ppk_launch_mask_from_qc(const float *d_dist, size_t n_rows, int mode, float max_pi, float max_a,
-                            uint64_t *d_mask, hipStream_t s) {
-  const size_t n_words = ppk_mask_words_linear(n_rows);
-  if (n_words == 0) return PPK_OK;
-  const unsigned grid = grid_for(n_words, kBlock / 64, 4096);
-  hipLaunchKernelGGL(mask_from_qc_kernel, dim3(grid), dim3(kBlock), 0, s,
-                     reinterpret_cast<const float2 *>(d_dist), n_rows, mode, max_pi, max_a, d_mask,
-                     n_words);
-  PPK_HIP(hipGetLastError());
-  return PPK_OK;
-}
-
-int ppk_launch_mask_from_assign(const int32_t *d_assign, size_t n_rows, int within_label,
-                                uint64_t *d_mask, hipStream_t s) {
-  const size_t n_words = ppk_mask_words_linear(n_rows);
-  if (n_words == 0) return PPK_OK;
-  const unsigned grid = grid_for(n_words, kBlock / 64, 4096);
-  hipLaunchKernelGGL(mask_from_assign_kernel, dim3(grid), dim3(kBlock), 0, s, d_assign, n_rows,
-                     within_label, d_mask, n_words);
-  PPK_HIP(hipGetLastError());
-  return PPK_OK;
+  void *p_mask = nullptr, *d_ws = nullptr;
+  int rc = ppk_scratch_get(dev, SLOT_MASK, n_words * sizeof(uint64_t) + 16, &p_mask);   // (+16: word pairs)
+  if (rc == PPK_OK) rc = ppk_scratch_get(dev, SLOT_WS, ppk_compact_ws_bytes(n_words), &d_ws);
+  if (rc != PPK_OK) return rc;
+  uint64_t *d_mask = static_cast<uint64_t *>(p_mask);
+  const float *d_dist = static_cast<const float *>(d_rows);
+  const bool counted = check_rows && (reinterpret_cast<uintptr_t>(d_rows) & 15) == 0;
+  if (n_words) {
+    switch (t.kind) {
+      case RowTest::LINE:
+        launch_mask(d_dist, n_rows, n_words, LinePred{t.slope, t.x_max, t.y_max, t.inclusive}, counted, d_mask, d_ws, s);
+        break;
+      case RowTest::QC:
+        launch_mask(d_dist, n_rows, n_words, QcPred{t.mode, t.max_pi, t.max_a}, counted, d_mask, d_ws, s);
+        break;
+      case RowTest::BGMM:
+        // K = 2, 3, 4 (every PopPUNK default fit: --K 2) with the component loop unrolled; other K at run time
+        switch (counted ? t.bgmm.K : 0) {
+          case 2: launch_mask_counted(d_dist, n_rows, n_words, BgmmPred<2>{t.bgmm}, d_mask, d_ws, s); break;
+          case 3: launch_mask_counted(d_dist, n_rows, n_words, BgmmPred<3>{t.bgmm}, d_mask, d_ws, s); break;
+          case 4: launch_mask_counted(d_dist, n_rows, n_words, BgmmPred<4>{t.bgmm}, d_mask, d_ws, s); break;
+          default: launch_mask(d_dist, n_rows, n_words, BgmmPred<0>{t.bgmm}, counted, d_mask, d_ws, s);
+        }
+        break;
+      case RowTest::LABEL:
+        hipLaunchKernelGGL(mask_from_assign_kernel, dim3(grid_for(n_words, kBlock / 64, 4096)), dim3(kBlock), 0, s,
+                           static_cast<const int32_t *>(d_rows), n_rows, t.within_label, d_mask, n_words);
+        break;
+    }
+    PPK_HIP(hipGetLastError());
+  }
+  g.pair_interleaved = counted;
+  return ppk_launch_compact(d_mask, n_words, g, d_ws, d_edges, cap, d_n_edges, s, counted);
 }
 
 int ppk_launch_compact(const uint64_t *d_mask, size_t n_words, const EdgeGeom &g, void *d_ws,

@@ -1332,6 +1332,46 @@ extern "C" int ppk_parked_fetch(long long *out0, long long *out1, long long *out
   return PPK_OK;
 }
 
+// The edge list of a device entry on a host array (ppk_host_result: a capacity guess, once more with the exact size).
+// Each pass uploads `in` to SLOT_HOST_IN, allocates the count word and a c-entry result, and
+// run(d_in, d_res, c, d_n, want) enqueues the entry on the null stream and leaves the entries it wanted in *want.
+static int host_edge_list(int device_id, const void *in, size_t in_bytes, size_t guess, long long *ij_out, size_t cap,
+                          size_t *n_edges,
+                          const std::function<int(const void *, long long *, size_t, unsigned long long *,
+                                                  unsigned long long *)> &run) {
+  auto copy_out = [&](const void *d, size_t n, size_t) {
+    if (!ij_out) return ppk_fail(PPK_ERR_ARG, "ij_out is NULL");
+    if (hipMemcpy(ij_out, d, n * 16, hipMemcpyDeviceToHost) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipMemcpy D2H failed");
+    return (int)PPK_OK;
+  };
+  return ppk_host_result(1, device_id, guess, cap, n_edges,
+                         [&](size_t c, void **d_res, unsigned long long *want) {
+                           // the uploaded input sits in a persistent scratch block (hipMalloc + hipFree of
+                           // 400 MB per call cost 20+ ms)
+                           PpkCall call(device_id, nullptr);
+                           void *d_in = nullptr;
+                           unsigned long long *d_n = nullptr;
+                           int rc = ppk_scratch_get(device_id, SLOT_HOST_IN, in_bytes + 8, &d_in);
+                           if (rc == PPK_OK && (hipMalloc(reinterpret_cast<void **>(&d_n), 8) != hipSuccess ||
+                                                hipMalloc(d_res, (c ? c : 1) * 16) != hipSuccess))
+                             rc = ppk_fail(PPK_ERR_HIP, "hipMalloc failed");
+                           // Every pass uploads: the device mutex (PpkCall) is released between the two passes
+                           // of a too-small guess, and another host thread's call on this device may have
+                           // rewritten, moved or freed SLOT_HOST_IN meanwhile (round-3 advisor finding).
+                           if (rc == PPK_OK) rc = ppk_upload(device_id, d_in, in, in_bytes, nullptr);
+                           if (rc == PPK_OK) rc = run(d_in, static_cast<long long *>(*d_res), c, d_n, want);
+                           if (d_n) (void)hipFree(d_n);
+                           return rc;
+                         },
+                         copy_out);
+}
+
+// the count word of a finished entry, to the host
+static int fetch_count(const unsigned long long *d_n, unsigned long long *n) {
+  if (hipMemcpy(n, d_n, 8, hipMemcpyDeviceToHost) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipMemcpy D2H failed");
+  return PPK_OK;
+}
+
 extern "C" int ppk_edge_threshold(const float *dist, size_t n_rows, size_t n_ref, int slope,
                                   float x_max, float y_max, int inclusive, int device_id,
                                   long long *ij_out, size_t cap, size_t *n_edges) {
@@ -1343,33 +1383,13 @@ extern "C" int ppk_edge_threshold(const float *dist, size_t n_rows, size_t n_ref
   if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
   size_t guess = n_rows / 8 > ((size_t)1 << 20) ? n_rows / 8 : ((size_t)1 << 20);
   if (guess > n_rows) guess = n_rows;
-  auto copy_out = [&](const void *d, size_t n, size_t) {
-    if (!ij_out) return ppk_fail(PPK_ERR_ARG, "ij_out is NULL");
-    if (hipMemcpy(ij_out, d, n * 16, hipMemcpyDeviceToHost) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipMemcpy D2H failed");
-    return (int)PPK_OK;
-  };
-  return ppk_host_result(1, device_id, guess, cap, n_edges,
-                         [&](size_t c, void **d_res, unsigned long long *want) {
-                           // the uploaded matrix sits in a persistent scratch block (hipMalloc + hipFree of
-                           // 400 MB per call cost 20+ ms)
-                           PpkCall call(device_id, nullptr);
-                           void *p_in = nullptr;
-                           unsigned long long *d_n = nullptr;
-                           int rc = ppk_scratch_get(device_id, SLOT_HOST_IN, n_rows * 8 + 8, &p_in);
-                           float *d_dist = static_cast<float *>(p_in);
-                           if (rc == PPK_OK && (hipMalloc(reinterpret_cast<void **>(&d_n), 8) != hipSuccess ||
-                                                hipMalloc(d_res, (c ? c : 1) * 16) != hipSuccess))
-                             rc = ppk_fail(PPK_ERR_HIP, "hipMalloc failed");
-                           if (rc == PPK_OK) rc = ppk_upload(device_id, d_dist, dist, n_rows * 8, nullptr);
-                           if (rc == PPK_OK)
-                             rc = ppk_edge_threshold_dev(d_dist, n_rows, n_ref, slope, x_max, y_max, inclusive,
-                                                         static_cast<long long *>(*d_res), c, d_n, nullptr);
-                           if (rc == PPK_OK && hipMemcpy(want, d_n, 8, hipMemcpyDeviceToHost) != hipSuccess)
-                             rc = ppk_fail(PPK_ERR_HIP, "hipMemcpy D2H failed");
-                           if (d_n) (void)hipFree(d_n);
-                           return rc;
-                         },
-                         copy_out);
+  return host_edge_list(device_id, dist, n_rows * 8, guess, ij_out, cap, n_edges,
+                        [&](const void *d_in, long long *d_res, size_t c, unsigned long long *d_n,
+                            unsigned long long *want) {
+                          int rc = ppk_edge_threshold_dev(static_cast<const float *>(d_in), n_rows, n_ref, slope,
+                                                          x_max, y_max, inclusive, d_res, c, d_n, nullptr);
+                          return rc == PPK_OK ? fetch_count(d_n, want) : rc;
+                        });
 }
 
 // poppunk_refine.generateAllTuples on a host array: the count is known beforehand (no parking); the list is
@@ -1412,44 +1432,26 @@ extern "C" int ppk_qc_edges(const float *dist, size_t n_rows, size_t n_ref, int 
   if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
   size_t guess = n_rows / 16 > ((size_t)1 << 20) ? n_rows / 16 : ((size_t)1 << 20);   // QC failures are the exception
   if (guess > 2 * n_rows) guess = 2 * n_rows;
-  auto copy_out = [&](const void *d, size_t n, size_t) {
-    if (!ij_out) return ppk_fail(PPK_ERR_ARG, "ij_out is NULL");
-    if (hipMemcpy(ij_out, d, n * 16, hipMemcpyDeviceToHost) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipMemcpy D2H failed");
-    return (int)PPK_OK;
-  };
-  return ppk_host_result(1, device_id, guess, cap, n_edges,
-                         [&](size_t c, void **d_res, unsigned long long *want) {
-                           PpkCall call(device_id, nullptr);
-                           void *p_in = nullptr;
-                           unsigned long long *d_n = nullptr;
-                           int rc = ppk_scratch_get(device_id, SLOT_HOST_IN, n_rows * 8 + 8, &p_in);
-                           float *d_dist = static_cast<float *>(p_in);
-                           if (rc == PPK_OK && (hipMalloc(reinterpret_cast<void **>(&d_n), 8) != hipSuccess ||
-                                                hipMalloc(d_res, (c ? c : 1) * 16) != hipSuccess))
-                             rc = ppk_fail(PPK_ERR_HIP, "hipMalloc failed");
-                           // Every pass uploads: the device mutex (PpkCall) is released between the two passes
-                           // of a too-small guess, and another host thread's call on this device may have
-                           // rewritten, moved or freed SLOT_HOST_IN meanwhile (round-3 advisor finding).
-                           if (rc == PPK_OK) rc = ppk_upload(device_id, d_dist, dist, n_rows * 8, nullptr);
-                           unsigned long long total = 0;
-                           bool first = true;
-                           for (int mode = 0; mode < 2 && rc == PPK_OK; ++mode) {
-                             if (!(modes & (1 << mode))) continue;
-                             const size_t used = total < c ? (size_t)total : c;
-                             unsigned long long got = 0;
-                             rc = ppk_qc_edges_dev(d_dist, n_rows, n_ref, mode, max_pi, max_a,
-                                                   static_cast<long long *>(*d_res) + 2 * used, c - used, d_n, nullptr);
-                             if (rc == PPK_OK && hipMemcpy(&got, d_n, 8, hipMemcpyDeviceToHost) != hipSuccess)
-                               rc = ppk_fail(PPK_ERR_HIP, "hipMemcpy D2H failed");
-                             total += got;
-                             if (first) *n_first = (size_t)got;
-                             first = false;
-                           }
-                           *want = total;
-                           if (d_n) (void)hipFree(d_n);
-                           return rc;
-                         },
-                         copy_out);
+  return host_edge_list(device_id, dist, n_rows * 8, guess, ij_out, cap, n_edges,
+                        [&](const void *d_in, long long *d_res, size_t c, unsigned long long *d_n,
+                            unsigned long long *want) {
+                          unsigned long long total = 0;
+                          bool first = true;
+                          int rc = PPK_OK;
+                          for (int mode = 0; mode < 2 && rc == PPK_OK; ++mode) {
+                            if (!(modes & (1 << mode))) continue;
+                            const size_t used = total < c ? (size_t)total : c;
+                            unsigned long long got = 0;
+                            rc = ppk_qc_edges_dev(static_cast<const float *>(d_in), n_rows, n_ref, mode, max_pi,
+                                                  max_a, d_res + 2 * used, c - used, d_n, nullptr);
+                            if (rc == PPK_OK) rc = fetch_count(d_n, &got);
+                            total += got;
+                            if (first) *n_first = (size_t)got;
+                            first = false;
+                          }
+                          *want = total;
+                          return rc;
+                        });
 }
 
 extern "C" int ppk_generate_tuples(const int32_t *assignments, size_t n_rows, int within_label,
@@ -1463,31 +1465,13 @@ extern "C" int ppk_generate_tuples(const int32_t *assignments, size_t n_rows, in
   if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
   size_t guess = n_rows / 8 > ((size_t)1 << 20) ? n_rows / 8 : ((size_t)1 << 20);
   if (guess > n_rows) guess = n_rows;
-  auto copy_out = [&](const void *d, size_t n, size_t) {
-    if (!ij_out) return ppk_fail(PPK_ERR_ARG, "ij_out is NULL");
-    if (hipMemcpy(ij_out, d, n * 16, hipMemcpyDeviceToHost) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipMemcpy D2H failed");
-    return (int)PPK_OK;
-  };
-  return ppk_host_result(1, device_id, guess, cap, n_edges,
-                         [&](size_t c, void **d_res, unsigned long long *want) {
-                           PpkCall call(device_id, nullptr);
-                           void *p_in = nullptr;
-                           unsigned long long *d_n = nullptr;
-                           int rc = ppk_scratch_get(device_id, SLOT_HOST_IN, n_rows * 4 + 8, &p_in);
-                           int32_t *d_a = static_cast<int32_t *>(p_in);
-                           if (rc == PPK_OK && (hipMalloc(reinterpret_cast<void **>(&d_n), 8) != hipSuccess ||
-                                                hipMalloc(d_res, (c ? c : 1) * 16) != hipSuccess))
-                             rc = ppk_fail(PPK_ERR_HIP, "hipMalloc failed");
-                           if (rc == PPK_OK) rc = ppk_upload(device_id, d_a, assignments, n_rows * 4, nullptr);
-                           if (rc == PPK_OK)
-                             rc = ppk_generate_tuples_dev(d_a, n_rows, within_label, self, num_ref, int_offset,
-                                                          static_cast<long long *>(*d_res), c, d_n, nullptr);
-                           if (rc == PPK_OK && hipMemcpy(want, d_n, 8, hipMemcpyDeviceToHost) != hipSuccess)
-                             rc = ppk_fail(PPK_ERR_HIP, "hipMemcpy D2H failed");
-                           if (d_n) (void)hipFree(d_n);
-                           return rc;
-                         },
-                         copy_out);
+  return host_edge_list(device_id, assignments, n_rows * 4, guess, ij_out, cap, n_edges,
+                        [&](const void *d_in, long long *d_res, size_t c, unsigned long long *d_n,
+                            unsigned long long *want) {
+                          int rc = ppk_generate_tuples_dev(static_cast<const int32_t *>(d_in), n_rows, within_label,
+                                                           self, num_ref, int_offset, d_res, c, d_n, nullptr);
+                          return rc == PPK_OK ? fetch_count(d_n, want) : rc;
+                        });
 }
 
 // ---- fused host entry: sketches -> distances -> boundary -> edge list, on one or several devices --------

@@ -176,34 +176,39 @@ struct EdgeGeom {
   long long *coo_seg;
   size_t seg_blocks;        // EDGE_COO_SEGMENTS with counts from the producer: compaction blocks per segment (seg_words / 256)
   unsigned long long *seg_totals;      // ... and room for one total per segment (device)
-  int pair_interleaved;     // linear layouts: the mask came from ppk_launch_mask_from_dist_counted (even / odd rows of 128 in word pairs)
+  int pair_interleaved;     // linear layouts: the mask came from mask_from_dist_counted_kernel (even / odd rows of 128 in word pairs)
 };
 
 // Workspace sizes / launchers; all enqueue on `s` and never synchronise.
 size_t ppk_mask_words_linear(size_t n_rows);
 size_t ppk_compact_ws_bytes(size_t n_words);
-int ppk_launch_mask_from_dist(const float *d_dist, size_t n_rows, int slope, float x_max,
-                              float y_max, int inclusive, uint64_t *d_mask, hipStream_t s);
-int ppk_launch_mask_from_qc(const float *d_dist, size_t n_rows, int mode, float max_pi, float max_a,
-                            uint64_t *d_mask, hipStream_t s);
-int ppk_launch_mask_from_assign(const int32_t *d_assign, size_t n_rows, int within_label,
-                                uint64_t *d_mask, hipStream_t s);
 int ppk_launch_all_tuples(size_t n_entries, size_t num_ref, size_t num_queries, int self, long long int_offset,
                           long long *d_edges, hipStream_t s);
 int ppk_launch_compact(const uint64_t *d_mask, size_t n_words, const EdgeGeom &g, void *d_ws,
                        long long *d_edges, size_t cap, unsigned long long *d_n_edges,
                        hipStream_t s, bool counted = false);
-int ppk_launch_mask_from_dist_counted(const float *d_dist, size_t n_rows, int slope, float x_max, float y_max,
-                                      int inclusive, uint64_t *d_mask, void *d_ws, hipStream_t s);
 int ppk_launch_assign(const float *d_dist, size_t n_rows, int slope, float x_max, float y_max,
                       float *d_out, hipStream_t s);
-// BGMM assignment: labels and / or responsibilities (ppk_bgmm.hip); the edge list's predicate pass (ppk_boundary.hip),
-// counted and pair-interleaved like ppk_launch_mask_from_dist_counted's, or row-order for unaligned buffers
+// BGMM assignment: labels and / or responsibilities (ppk_bgmm.hip)
 int ppk_launch_bgmm_assign(const float *d_dist, size_t n_rows, const ppk_bgmm &m, int32_t *d_labels, float *d_resp,
                            hipStream_t s);
-int ppk_launch_mask_from_bgmm_counted(const float *d_dist, size_t n_rows, const ppk_bgmm &m, uint64_t *d_mask,
-                                      void *d_ws, hipStream_t s);      // (d_dist 16-byte aligned)
-int ppk_launch_mask_from_bgmm(const float *d_dist, size_t n_rows, const ppk_bgmm &m, uint64_t *d_mask, hipStream_t s);
+
+// The row test of a row-linear edge list: a float32 [n, 2] distance matrix (LINE, BGMM, QC) or an int32 label array
+// (LABEL: generate_tuples).  Only the kind's own fields are read.
+struct RowTest {
+  enum Kind { LINE, BGMM, QC, LABEL } kind;
+  int slope, inclusive;    // LINE: the refine line (src/boundary.cpp:82-95)
+  float x_max, y_max;
+  ppk_bgmm bgmm;           // BGMM: the row's label == bgmm.within_label
+  int mode;                // QC: 0 distance too long (x > max_pi | y > max_a), 1 zero distance (x == 0 | y == 0)
+  float max_pi, max_a;
+  int within_label;        // LABEL: assign[row] == within_label
+};
+// The edge list of the rows that pass `t`, on the current device: n_ref == 0 a self (condensed) matrix, otherwise
+// n_ref refs per query row.  The row count must fit the layout, except for LABEL, which takes it as it comes (as
+// src/boundary.cpp:104 does).  A 16-byte aligned matrix takes the counted, pair-interleaved mask pass.
+int ppk_row_edges(const void *d_rows, size_t n_rows, size_t n_ref, long long int_offset, const RowTest &t,
+                  long long *d_edges, size_t cap, unsigned long long *d_n_edges, hipStream_t s);
 // the model into scratch slot SLOT_BGMM of `dev`, enqueued on `s` (the caller holds a PpkCall)
 int ppk_bgmm_to_device(int dev, const ppk_bgmm &m, const ppk_bgmm **d_model, hipStream_t s);
 

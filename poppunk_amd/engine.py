@@ -361,9 +361,7 @@ def bgmm_edges_host(refs, qrys=None, kmers=None, random_tbl=None, model=None, ra
 def assign_threshold_dev(dist_t, slope, x_max, y_max, out=None):
     """poppunk_refine.assignThreshold on a resident float32 [n,2] CUDA tensor."""
     torch = _torch()
-    if not (dist_t.is_cuda and dist_t.dtype == torch.float32 and dist_t.is_contiguous()
-            and dist_t.dim() == 2 and dist_t.shape[1] == 2):
-        raise TypeError("distMat must be a C-contiguous float32 [n,2] CUDA tensor")
+    _check_dist_tensor(dist_t)
     n = dist_t.shape[0]
     with torch.cuda.device(dist_t.device):
         if out is None:
@@ -378,51 +376,27 @@ def assign_threshold_dev(dist_t, slope, x_max, y_max, out=None):
 
 def edge_threshold_dev(dist_t, slope, x_max, y_max, n_ref=0, inclusive=True, cap=None):
     """poppunk_refine.edgeThreshold on a resident float32 [n,2] CUDA tensor -> int64 [m,2]."""
-    torch = _torch()
-    if not (dist_t.is_cuda and dist_t.dtype == torch.float32 and dist_t.is_contiguous()
-            and dist_t.dim() == 2 and dist_t.shape[1] == 2):
-        raise TypeError("distMat must be a C-contiguous float32 [n,2] CUDA tensor")
+    _check_dist_tensor(dist_t)
     n = dist_t.shape[0]
     if cap is None:
         cap = min(n, max(1 << 20, n // 8))
-    with torch.cuda.device(dist_t.device):
-        while True:
-            edges = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dist_t.device)
-            n_edges = torch.zeros(1, dtype=torch.int64, device=dist_t.device)
-            rc = _lib.lib().ppk_edge_threshold_dev(C.c_void_p(dist_t.data_ptr()), n, int(n_ref),
-                                                   int(slope), float(x_max), float(y_max),
-                                                   1 if inclusive else 0,
-                                                   C.c_void_p(edges.data_ptr()), cap,
-                                                   C.c_void_p(n_edges.data_ptr()),
-                                                   _stream_ptr(dist_t.device.index))
-            _lib.check(rc, "ppk_edge_threshold_dev")
-            m = int(n_edges.item())
-            if m <= cap:
-                return edges[:m]
-            cap = m
+    return _edges_dev(lambda e, c, ne: _lib.lib().ppk_edge_threshold_dev(
+        C.c_void_p(dist_t.data_ptr()), n, int(n_ref), int(slope), float(x_max), float(y_max), 1 if inclusive else 0,
+        C.c_void_p(e.data_ptr()), c, C.c_void_p(ne.data_ptr()), _stream_ptr(dist_t.device.index)),
+        "ppk_edge_threshold_dev", dist_t.device, cap)
 
 
 def qc_edges_dev(dist_t, max_pi_dist, max_a_dist, n_ref=0, zero=False, cap=None):
     """qcDistMat's outlier edge lists on a resident float32 [n,2] CUDA tensor
     (PopPUNK/qc.py:332-337 long distances; :349-354 zero distances) -> int64 [m,2]."""
-    torch = _torch()
+    _check_dist_tensor(dist_t)
     n = dist_t.shape[0]
     if cap is None:
         cap = min(n, max(1 << 20, n // 8))
-    with torch.cuda.device(dist_t.device):
-        while True:
-            edges = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dist_t.device)
-            n_edges = torch.zeros(1, dtype=torch.int64, device=dist_t.device)
-            rc = _lib.lib().ppk_qc_edges_dev(C.c_void_p(dist_t.data_ptr()), n, int(n_ref),
-                                             1 if zero else 0, float(max_pi_dist), float(max_a_dist),
-                                             C.c_void_p(edges.data_ptr()), cap,
-                                             C.c_void_p(n_edges.data_ptr()),
-                                             _stream_ptr(dist_t.device.index))
-            _lib.check(rc, "ppk_qc_edges_dev")
-            m = int(n_edges.item())
-            if m <= cap:
-                return edges[:m]
-            cap = m
+    return _edges_dev(lambda e, c, ne: _lib.lib().ppk_qc_edges_dev(
+        C.c_void_p(dist_t.data_ptr()), n, int(n_ref), 1 if zero else 0, float(max_pi_dist), float(max_a_dist),
+        C.c_void_p(e.data_ptr()), c, C.c_void_p(ne.data_ptr()), _stream_ptr(dist_t.device.index)),
+        "ppk_qc_edges_dev", dist_t.device, cap)
 
 
 def threshold_iterate_1d_dev(dist_t, offsets, slope, x0, y0, x1, y1, cap=None):

@@ -22,6 +22,14 @@ def grid10():
     return np.ascontiguousarray(np.hstack((xv.reshape(-1, 1), yv.reshape(-1, 1))), dtype=np.float32)
 
 
+def unaligned_view(a):
+    """`a` on the device as an 8-byte but not 16-byte aligned view: the row-order mask path of the edge lists."""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(np.vstack([a[:1], a]))).cuda()[1:]
+    assert t.is_contiguous() and t.data_ptr() % 16 == 8
+    return t
+
+
 class _HipRefine:
     assign = staticmethod(lambda d, slope, x, y: poppunk_refine.assignThreshold(d, slope, x, y, 2))
     edges = staticmethod(lambda d, slope, x, y: poppunk_refine.edgeThreshold_array(d, slope, x, y))
@@ -128,6 +136,11 @@ def test_noconvert_type_errors():
         poppunk_refine.edgeThreshold(np.zeros((2, 10), dtype=np.float32).T, 2, 0.5, 0.5)
     with pytest.raises(RuntimeError):
         poppunk_refine.edgeThreshold(np.zeros((4, 2), dtype=np.float32), 2, 0.5, 0.5)  # 4 != n(n-1)/2
+    import torch
+    with pytest.raises(TypeError):
+        engine.qc_edges_dev(torch.zeros((10, 2), dtype=torch.float64, device="cuda"), 0.5, 0.5)
+    with pytest.raises(TypeError):
+        engine.qc_edges_dev(torch.zeros((2, 10), dtype=torch.float32, device="cuda").T, 0.5, 0.5, zero=True)
 
 
 def test_large_stream_and_edge_order():
@@ -158,6 +171,8 @@ def test_fused_edges_equal_two_step(slope, inclusive):
     assert scaled.dtype == np.float32
     xs, ys = x_max / float(scale[0]), y_max / float(scale[1])
     want = oracle.edge_threshold(scaled, slope, xs, ys, inclusive=inclusive)
+    got = engine.edge_threshold_dev(unaligned_view(scaled), slope, xs, ys, inclusive=inclusive)
+    assert np.array_equal(got.cpu().numpy(), want)
     db = engine.SketchDB(sk, 16, 14, device=0)
     got, _ = engine.dist_edges(db, None, KMERS, tbl, slope=slope, x_max=xs, y_max=ys, scale=scale,
                                inclusive=inclusive)
@@ -366,10 +381,12 @@ def test_qc_edges_on_device():
     want = oracle.generate_tuples(long_rows.astype(np.int32), 0)
     got = engine.qc_edges_dev(dt, max_pi, max_a).cpu().numpy()
     assert len(want) > 100 and np.array_equal(got, want)
+    assert np.array_equal(engine.qc_edges_dev(unaligned_view(d), max_pi, max_a).cpu().numpy(), want)
     zero_rows = np.where((d[:, 0] == 0) | (d[:, 1] == 0), 0, 1)
     want = oracle.generate_tuples(zero_rows.astype(np.int32), 0)
     got = engine.qc_edges_dev(dt, max_pi, max_a, zero=True).cpu().numpy()
     assert len(want) > 500 and np.array_equal(got, want)
+    assert np.array_equal(engine.qc_edges_dev(unaligned_view(d), max_pi, max_a, zero=True).cpu().numpy(), want)
     # ref x query layout (poppunk_assign QC, qc.py:406-407)
     nr = 37
     dq = d[:nr * 50]
