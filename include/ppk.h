@@ -385,6 +385,33 @@ int ppk_threshold_iterate_2d_dev(const float *d_dist, size_t n_rows, const float
                                  void *stream);
 
 /* ------------------------------------------------------------------------
+ * Network scores of the sweeps.  For vertices 0 .. n_vertices-1 and G_t = the graph of every edge
+ * whose offset index is <= t, d_stats[t] = {|E(G_t)|, connected components of G_t (isolated vertices included),
+ * triangles T, connected triples W = sum_v d_v (d_v - 1) / 2}: the integers networkSummary derives its score from
+ * (PopPUNK/network.py:1204-1307 without betweenness: density = E / (0.5 n (n - 1)), transitivity = 3T / W) at every
+ * step of refine.growNetwork (PopPUNK/refine.py:375-474), which grows the graph offset by offset.
+ *  - edges: d_i[k * stride], d_j[k * stride] (stride 1: separate arrays; 2: an int64 [m][2] edge list, d_j = d_i + 1),
+ *    in any order, i > j allowed; d_off[k] their offset indices (NULL: every edge at offset 0, n_off must be 1
+ *    unless there are no edges).
+ *  - PPK_ERR_ARG, ppk_last_error() naming one offending edge: an id outside [0, n_vertices), a self-loop, an offset
+ *    index outside [0, n_off).  Also PPK_ERR_ARG: n_off 0 or > 1023, n_vertices or n_edges >= 2^31.
+ *  - an unordered pair given twice is a precondition violation: the counts are then unspecified (nothing is read or
+ *    written out of bounds).  No edges: {0, n, 0, 0} for every t.
+ *  - labels_at >= 0: d_labels int32 [n_vertices] = the components of G_{labels_at}, numbered in the order of their
+ *    smallest vertex (scipy.sparse.csgraph.connected_components; replaces distfile.clusters_from_edges on the device).
+ * Synchronises the stream once (the per-offset edge counts size the batches).
+ * (Replaces the networkSummary calls of growNetwork: graph-tool's label_components / global_clustering,
+ * network.py:1258-1264, or cugraph's, network.py:1236-1249.) */
+int ppk_network_sweep_dev(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off,
+                          size_t n_edges, size_t n_vertices, size_t n_off, long long labels_at, long long *d_stats,
+                          int32_t *d_labels, void *stream);
+/* Host arrays: i, j, off int64 [n_edges] (off nullable as above) -> stats int64 [n_off][4], labels int32 [n_vertices]
+ * (when labels_at >= 0), on device_id; blocking.  (The same replacement, for callers holding numpy arrays.) */
+int ppk_network_sweep(const long long *i, const long long *j, const long long *off, size_t n_edges,
+                      size_t n_vertices, size_t n_off, int device_id, long long labels_at, long long *stats,
+                      int32_t *labels);
+
+/* ------------------------------------------------------------------------
  * Host-buffer convenience wrappers (what a pybind11/ctypes drop-in binds):
  * upload, run on `devices[0..n_dev)` (the pair space is band-split across
  * them), copy back.  Blocking.

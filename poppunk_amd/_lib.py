@@ -44,6 +44,8 @@ SIGNATURES = {
     "ppk_query_bgmm_edges_dbs": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.c_int, _i32p, _f32p, _sz, C.c_int,
                                            _bgmmp, _llp, _sz, _szp, _ullp]),
     "ppk_bgmm_assign": (C.c_int, [_f32p, _sz, _bgmmp, C.c_int, _i32p, _f32p]),
+    "ppk_network_sweep_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, C.c_longlong, _vp, _vp, _vp]),
+    "ppk_network_sweep": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, C.c_longlong, _llp, _i32p]),
     "ppk_last_error": (C.c_char_p, []),
     "ppk_version": (C.c_char_p, []),
     "ppk_release_scratch": (C.c_int, []),
@@ -215,7 +217,7 @@ def sources_hash_now():
     import hashlib
     here = os.path.join(_HERE, "csrc")
     names = ["ppk_api.hip", "ppk_host.hip", "ppk_dist.hip", "ppk_boundary.hip", "ppk_iterate.hip", "ppk_square.hip",
-             "ppk_sparse.hip", "ppk_bgmm.hip", "ppk_h5.cpp", "ppk_internal.h", "ppk_block_asm.inc", "../../include/ppk.h"]
+             "ppk_sparse.hip", "ppk_bgmm.hip", "ppk_network.hip", "ppk_h5.cpp", "ppk_internal.h", "ppk_block_asm.inc", "../../include/ppk.h"]
     h = hashlib.sha256()
     try:
         for n in names:

@@ -73,6 +73,7 @@ struct PpkConfig {
   std::atomic<long long> ks_grid_pad{0};        // PPK_KS_GRID_PAD: 1 = the one-launch k-split grid is one column wider, which puts the units of a tile on different XCDs (tests of the hand-over)
   std::atomic<long long> knn_lane_lists{0};     // PPK_KNN_LANE_LISTS: 1 = the per-lane selection lists of ppk_knn_rect_dev (the form before the one list per wavefront; measurement)
   std::atomic<long long> sweep_window{1};       // PPK_SWEEP_WINDOW: the boundary sweeps' classify pass finds a row's count by bisection over nested boundaries (0: every boundary evaluated for every row it keeps; same results)
+  std::atomic<long long> net_window{0};         // PPK_NET_WINDOW: vertex ids per LDS table window of the network sweep's triangle stage (0 = as many as LDS holds; small values force the windowed path: tests; same results)
   std::atomic<long long> knn_list{0};           // PPK_KNN_LIST: entries of the neighbour-candidate list (0 = sized from n and knn)
   std::atomic<long long> host_parts_rows{16 << 20};   // PPK_HOST_PARTS_ROWS: ... from this many rows up
   std::atomic<long long> host_parts{2};         // PPK_HOST_PARTS: worker threads of a one-device host query (>= 16 Mi rows)
@@ -218,7 +219,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_TICKETS = 8,                       // one counter per tile of a k-split job: zero when allocated, left zero by every launch
        SLOT_WIDE = 9,                          // spill-slot pool of the wide-k tile kernel: its first page (the slot bitmap) zero when allocated, left zero by every launch
        SLOT_BGMM = 10,                         // the device copy of a ppk_bgmm that the fused BGMM edge call's tile kernels read
-       SLOT_COUNT = 11 };
+       SLOT_NET = 11,                          // the network sweep's counters, buckets, sorted adjacency and temp storage
+       SLOT_COUNT = 12 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

@@ -451,6 +451,80 @@ def threshold_iterate_2d_dev(dist_t, x_max, y_max, cap=None):
             cap = m
 
 
+def network_sweep_dev(i_t, j_t, off_t, n, n_off, labels_at=None):
+    """The counts behind networkSummary for every step of refine.growNetwork (ppk_network_sweep_dev):
+    G_t = the edges (i_t[k], j_t[k]) with off_t[k] <= t over vertices 0 .. n-1.  int64 CUDA tensors of one length (a
+    strided view such as edges[:, 0] is read in place); off_t None puts every edge at offset 0 (n_off must be 1).
+    Returns (stats int64 [n_off, 4] = edges, components, triangles, connected triples; labels int32 [n] of
+    G_{labels_at} numbered as scipy's connected_components, or None)."""
+    torch = _torch()
+    m = int(i_t.shape[0])
+    for t in (i_t, j_t) + ((off_t,) if off_t is not None else ()):
+        if not (t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.shape[0] == m):
+            raise TypeError("edge arrays must be int64 CUDA tensors of one length")
+    stride = i_t.stride(0) if m > 1 else 1
+    if (m > 1 and j_t.stride(0) != stride) or stride not in (1, 2):
+        raise TypeError("edge arrays must be contiguous, or the two columns of a contiguous [m, 2] tensor")
+    if off_t is not None and off_t.stride(0) != 1 and m > 1:
+        raise TypeError("the offset array must be contiguous")
+    la = -1 if labels_at is None else int(labels_at)
+    dev = i_t.device
+    with torch.cuda.device(dev):
+        stats = torch.empty((max(int(n_off), 1), 4), dtype=torch.int64, device=dev)
+        labels = torch.empty(max(int(n), 1), dtype=torch.int32, device=dev) if la >= 0 else None
+        rc = _lib.lib().ppk_network_sweep_dev(
+            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride,
+            C.c_void_p(off_t.data_ptr()) if off_t is not None else None, m, int(n), int(n_off), la,
+            C.c_void_p(stats.data_ptr()), C.c_void_p(labels.data_ptr()) if labels is not None else None,
+            _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_network_sweep_dev")
+    return stats, (labels[:int(n)] if labels is not None else None)
+
+
+def network_stats_dev(edges_t, n, labels=False):
+    """network_sweep_dev of one int64 [m, 2] CUDA edge list (edge_threshold_dev, dist_edges, ...), read in place.
+    Returns (stats int64 [4], labels int32 [n] or None)."""
+    torch = _torch()
+    if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
+            and edges_t.is_contiguous()):
+        raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
+    stats, lab = network_sweep_dev(edges_t[:, 0], edges_t[:, 1], None, n, 1, 0 if labels else None)
+    return stats[0], lab
+
+
+def _samples_of(n_rows):
+    n = int((1 + (1 + 8 * n_rows) ** 0.5) // 2)
+    while n * (n - 1) // 2 > n_rows:
+        n -= 1
+    while (n + 1) * n // 2 <= n_rows:
+        n += 1
+    if n * (n - 1) // 2 != n_rows:
+        raise ValueError("row count is not n(n-1)/2 for any n (self/condensed matrix expected)")
+    return n
+
+
+def _sweep_scores(dist_t, sweep, n_off):
+    from . import refine
+    n = _samples_of(dist_t.shape[0])
+    i, j, o = sweep
+    stats, _ = network_sweep_dev(i, j, o, n, n_off)
+    st = stats.cpu().numpy()
+    return stats, refine.grow_scores(st, n)
+
+
+def refine_sweep_scores_dev(dist_t, offsets, slope, x0, y0, x1, y1):
+    """thresholdIterate1D + growNetwork on a resident float32 [n,2] CUDA matrix, without the edge list leaving the
+    device (PopPUNK/refine.py:190-202).  Returns (stats int64 [len(offsets), 4] CUDA, growNetwork's score list)."""
+    off = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
+    return _sweep_scores(dist_t, threshold_iterate_1d_dev(dist_t, off, slope, x0, y0, x1, y1), off.size)
+
+
+def refine_sweep_scores_2d_dev(dist_t, x_max, y_max):
+    """thresholdIterate2D + growNetwork for one y (PopPUNK/refine.py:587-595), as refine_sweep_scores_dev."""
+    xm = np.ascontiguousarray(x_max, dtype=np.float32).ravel()
+    return _sweep_scores(dist_t, threshold_iterate_2d_dev(dist_t, xm, y_max), xm.size)
+
+
 def long_to_square_dev(dist_t, col, n):
     """pp_sketchlib.longToSquare of one column of the resident [n_pairs,2] matrix -> [n,n] CUDA."""
     torch = _torch()
