@@ -412,6 +412,32 @@ int ppk_network_sweep(const long long *i, const long long *j, const long long *o
                       int32_t *labels);
 
 /* ------------------------------------------------------------------------
+ * Network summary with betweenness: ppk_network_sweep_dev's edge stream, arguments, validation and
+ * error messages, and its d_stats [n_off][4] bit for bit (the same stages), plus for every G_t:
+ *  - d_bt double [n_off][2] = {mean, size-weighted mean} over the components of G_t with more than 3 vertices of each
+ *    component's maximum normalised vertex betweenness; 0 when there is no such component.
+ *  - d_scored int64 [n_off] (nullable) = the number of those components.
+ *  - values_at >= 0: d_values double [n_vertices] = every vertex's normalised betweenness in G_{values_at}, within
+ *    its own component (0 in components of 3 or fewer vertices).
+ * BC(v) = sum over sources s of v's component of delta_s(v) / ((n_c - 1)(n_c - 2)), exact Brandes: networkx's
+ * betweenness_centrality(normalized=True) (a star's centre 1, the inner vertices of a 4-vertex path 2/3).  That
+ * graph-tool's betweenness(norm=True) gives the same values is UNVERIFIED.  Deterministic: the same input, in any edge
+ * order, gives the same bits on every call.  Offsets without edges of their own repeat the row before them.
+ * Synchronises the stream once for the counts and once per offset that adds edges (its components size the launch).
+ * (Replaces networkSummary(G, calc_betweenness=True), PopPUNK/network.py:1204-1307, graph-tool branch: the
+ * label_components / global_clustering calls, :1258-1264, and the per-component vertex_betweenness, :1288-1307,
+ * network.py:1309-1312 -- for every step of growNetwork with score_idx > 0, PopPUNK/refine.py:452-457.) */
+int ppk_network_summary_dev(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off,
+                            size_t n_edges, size_t n_vertices, size_t n_off, long long values_at, long long *d_stats,
+                            double *d_bt, long long *d_scored, double *d_values, void *stream);
+/* Host arrays: i, j, off int64 [n_edges] (off nullable) -> stats int64 [n_off][4], bt double [n_off][2], scored int64
+ * [n_off] (nullable), values double [n_vertices] (when values_at >= 0), on device_id; blocking.  (The same
+ * replacement, for callers holding numpy arrays: print_network_summary, network.py:616-643.) */
+int ppk_network_summary(const long long *i, const long long *j, const long long *off, size_t n_edges,
+                        size_t n_vertices, size_t n_off, int device_id, long long values_at, long long *stats,
+                        double *bt, long long *scored, double *values);
+
+/* ------------------------------------------------------------------------
  * Host-buffer convenience wrappers (what a pybind11/ctypes drop-in binds):
  * upload, run on `devices[0..n_dev)` (the pair space is band-split across
  * them), copy back.  Blocking.

@@ -46,6 +46,8 @@ SIGNATURES = {
     "ppk_bgmm_assign": (C.c_int, [_f32p, _sz, _bgmmp, C.c_int, _i32p, _f32p]),
     "ppk_network_sweep_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, C.c_longlong, _vp, _vp, _vp]),
     "ppk_network_sweep": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, C.c_longlong, _llp, _i32p]),
+    "ppk_network_summary_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, C.c_longlong, _vp, _vp, _vp, _vp, _vp]),
+    "ppk_network_summary": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, C.c_longlong, _llp, _f64p, _llp, _f64p]),
     "ppk_last_error": (C.c_char_p, []),
     "ppk_version": (C.c_char_p, []),
     "ppk_release_scratch": (C.c_int, []),

@@ -74,6 +74,8 @@ struct PpkConfig {
   std::atomic<long long> knn_lane_lists{0};     // PPK_KNN_LANE_LISTS: 1 = the per-lane selection lists of ppk_knn_rect_dev (the form before the one list per wavefront; measurement)
   std::atomic<long long> sweep_window{1};       // PPK_SWEEP_WINDOW: the boundary sweeps' classify pass finds a row's count by bisection over nested boundaries (0: every boundary evaluated for every row it keeps; same results)
   std::atomic<long long> net_window{0};         // PPK_NET_WINDOW: vertex ids per LDS table window of the network sweep's triangle stage (0 = as many as LDS holds; small values force the windowed path: tests; same results)
+  std::atomic<long long> bt_lds_max{0};        // PPK_BT_LDS_MAX: largest component whose Brandes state lives in LDS (0 = as many vertices as LDS holds; small values force the global-state path: tests; results within rounding)
+  std::atomic<long long> bt_small_max{64};      // PPK_BT_SMALL_MAX: largest component Brandes gives one wave for all its sources (0 = none; at most 256; results within rounding)
   std::atomic<long long> knn_list{0};           // PPK_KNN_LIST: entries of the neighbour-candidate list (0 = sized from n and knn)
   std::atomic<long long> host_parts_rows{16 << 20};   // PPK_HOST_PARTS_ROWS: ... from this many rows up
   std::atomic<long long> host_parts{2};         // PPK_HOST_PARTS: worker threads of a one-device host query (>= 16 Mi rows)
@@ -220,7 +222,9 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_WIDE = 9,                          // spill-slot pool of the wide-k tile kernel: its first page (the slot bitmap) zero when allocated, left zero by every launch
        SLOT_BGMM = 10,                         // the device copy of a ppk_bgmm that the fused BGMM edge call's tile kernels read
        SLOT_NET = 11,                          // the network sweep's counters, buckets, sorted adjacency and temp storage
-       SLOT_COUNT = 12 };
+       SLOT_NET_BT = 12,                       // its betweenness stage: relabelling, the local adjacency, the plan
+       SLOT_NET_WORK = 13,                     // ... and one graph's partial sums and global-state slab (sized after its plan)
+       SLOT_COUNT = 14 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

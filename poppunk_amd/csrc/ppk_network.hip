@@ -19,6 +19,8 @@
 //                  table indexed by w and probes it for every w in N+(v), v in N+(u): each triangle is found once,
 //                  at u = its smallest vertex, and counted at the largest offset of its three edges
 //    then one small kernel prefix-sums the per-offset increments into the [n_off][4] result.
+//  - ppk_network_summary_dev : the same counts plus networkSummary's betweenness (network.py:1286-1307) for every
+//    G_t: the stages above, then the betweenness stage below.
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -376,11 +378,613 @@ int bad_edge_message(const long long *d_i, const long long *d_j, size_t stride, 
                                    ", j=" + std::to_string(j) + ", offset " + std::to_string(o) + "): " + why);
 }
 
-}  // namespace
+// ---- betweenness ------------------------------------------------------------------------------
+// After the counts, every distinct graph G_t (each offset that adds edges) is rebuilt from the same sorted adjacency
+// and union-find, and its components of more than 3 vertices are scored with exact Brandes:
+//   bt_relabel  roots and sizes from the union-find at t; those components ordered by (size desc, root), their
+//               vertices given local ids ordered by (component, id); a local CSR of G_t with rows sorted by neighbour
+//   bt_plan     one workgroup splits every component into work items of a fixed number of sources, sized from the
+//               component's work (sources x adjacency); the graph's ONE synchronisation reads the plan's header
+//   bt_brandes  level-synchronous Brandes per source; a work item writes its partial sums, never adds into a shared one
+//   bt_reduce   per vertex the partials in item order, normalised; per component the maximum; the two means
+constexpr int kBtItems = 1024;         // work items per graph the plan aims at (fixed: results do not depend on the GPU)
+constexpr int kBtSmallCap = 256;       // the small-component path's LDS holds components up to this size
+constexpr size_t kBtLdsBytes = 160 * 1024 - 64;   // dynamic LDS of the LDS-state path (static: a few scalars)
+constexpr unsigned long long kNone = ~0ull;
+enum { H_K, H_KBIG, H_KGLOB, H_ITEMS, H_ITEMS_GLOB, H_PARTIAL, H_SCORED, H_NC_GLOB, H_NC_LDS, H_WORK, H_ADJ,
+       H_LEN = 16 };
 
-extern "C" int ppk_network_sweep_dev(const long long *d_i, const long long *d_j, size_t stride,
-                                     const long long *d_off, size_t n_edges, size_t n_vertices, size_t n_off,
-                                     long long labels_at, long long *d_stats, int32_t *d_labels, void *stream) {
+size_t bt_state_bytes(size_t nc) { return 36 * nc + 8; }
+
+__device__ __forceinline__ int bt_find(const int *parent, int x) {
+  for (int p = parent[x]; p != x; p = parent[x]) x = p;
+  return x;
+}
+
+__global__ void __launch_bounds__(kThreads) bt_sizes_kernel(const int *parent, size_t n, int *root, int *size) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) {
+    const int r = bt_find(parent, (int)v);
+    root[v] = r;
+    atomicAdd(&size[r], 1);
+  }
+}
+
+// one key per root of a component of more than 3 vertices: (n - size, root); every other vertex kNone
+__global__ void __launch_bounds__(kThreads) bt_root_keys_kernel(const int *root, const int *size, size_t n,
+                                                                unsigned long long *keys) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x)
+    keys[v] = (root[v] == (int)v && size[v] > 3) ? ((unsigned long long)(n - size[v]) << 32 | v) : kNone;
+}
+
+// component c (sorted position): its rank at its root, its size (0 past the last component)
+__global__ void __launch_bounds__(kThreads) bt_comps_kernel(const unsigned long long *sorted, const int *size,
+                                                            size_t n, int *crank, int *csize) {
+  for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c <= n; c += (size_t)gridDim.x * blockDim.x) {
+    const unsigned long long key = c < n ? sorted[c] : kNone;
+    if (key == kNone) {
+      csize[c] = 0;
+    } else {
+      const int r = (int)(key & 0xffffffffu);
+      crank[r] = (int)c;
+      csize[c] = size[r];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) bt_vertex_keys_kernel(const int *root, const int *size, const int *crank,
+                                                                  size_t n, unsigned long long *keys, int *local) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) {
+    const int r = root[v];
+    keys[v] = size[r] > 3 ? ((unsigned long long)crank[r] << 32 | v) : kNone;
+    local[v] = -1;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) bt_local_kernel(const unsigned long long *sorted, size_t n, int *local,
+                                                            int *order) {
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
+    const unsigned long long key = sorted[p];
+    if (key == kNone) continue;
+    const int v = (int)(key & 0xffffffffu);
+    local[v] = (int)p;
+    order[p] = v;
+  }
+}
+
+// the entries of G_t (offset <= t) whose row is a scored vertex, as (local row, local neighbour) keys, appended in
+// any order (they are sorted next); the rest of the 2|E(G_t)| slots keep kNone
+__global__ void __launch_bounds__(kThreads) bt_edges_kernel(const unsigned long long *keys, const int *nbr, size_t e,
+                                                            unsigned t, const int *local, unsigned *fill,
+                                                            unsigned long long *out) {
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < e; p += (size_t)gridDim.x * blockDim.x) {
+    const unsigned long long key = keys[p];
+    const int lr = (key & ((1u << kOffBits) - 1)) <= t ? local[key >> (kOffBits + 1)] : -1;
+    if (lr >= 0) out[atomicAdd(fill, 1u)] = (unsigned long long)lr << 32 | (unsigned)local[nbr[p]];
+  }
+}
+
+// row starts of the local CSR (rstart has n_scored + 1 entries) and the neighbours as int
+__global__ void __launch_bounds__(kThreads) bt_rows_kernel(const unsigned long long *sorted, size_t len,
+                                                           const long long *hdr, unsigned *rstart, int *lnbr) {
+  const size_t ns = (size_t)hdr[H_SCORED];
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < len; p += (size_t)gridDim.x * blockDim.x) {
+    const unsigned long long key = sorted[p];
+    if (key == kNone) continue;
+    const size_t row = key >> 32;
+    lnbr[p] = (int)(key & 0xffffffffu);
+    const size_t first = p ? (sorted[p - 1] >> 32) + 1 : 0;
+    for (size_t x = first; x <= row; ++x) rstart[x] = (unsigned)p;
+    if (p + 1 == len || sorted[p + 1] == kNone)
+      for (size_t x = row + 1; x <= ns; ++x) rstart[x] = (unsigned)(p + 1);
+  }
+}
+
+// component starts (exclusive scan of csize) and the scored-vertex count: a one-workgroup scan
+__global__ void __launch_bounds__(kThreads) bt_starts_kernel(const int *csize, size_t n, int *cstart, long long *hdr) {
+  __shared__ long long part[kThreads];
+  const size_t per = (n + 1 + kThreads - 1) / kThreads, c0 = threadIdx.x * per;
+  const size_t c1 = c0 + per < n + 1 ? c0 + per : n + 1;
+  long long acc = 0;
+  for (size_t c = c0; c < c1; ++c) acc += csize[c];
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long long run = 0;
+    for (int k = 0; k < kThreads; ++k) {
+      const long long x = part[k];
+      part[k] = run;
+      run += x;
+    }
+    hdr[H_SCORED] = run;
+  }
+  __syncthreads();
+  acc = part[threadIdx.x];
+  for (size_t c = c0; c < c1; ++c) {
+    cstart[c] = (int)acc;
+    acc += csize[c];
+  }
+  if (threadIdx.x == kThreads - 1) cstart[n + 1] = (int)acc;
+}
+
+// the plan: components [0, K) sorted by size; [0, K_glob) global-state, [K_glob, K_big) LDS-state (both 256-thread
+// items of spi[c] sources), [K_big, K) one wave each.  ibase / pbase: each component's first item and first partial.
+__global__ void __launch_bounds__(kThreads) bt_plan_kernel(const int *csize, const int *cstart, const unsigned *rstart,
+                                                           size_t n, int small_max, int lds_max, int *spi, int *ibase,
+                                                           long long *pbase, long long *hdr) {
+  __shared__ long long s_part[kThreads], s_items[kThreads];
+  __shared__ double s_work[kThreads];
+  __shared__ int s_k[kThreads], s_big[kThreads], s_glob[kThreads];
+  __shared__ long long s_adj[kThreads];
+  const int tid = threadIdx.x;
+  int k = 0, kb = 0, kg = 0;
+  long long adj_sum = 0;
+  double work = 0;
+  for (size_t c = tid; c < n; c += kThreads) {
+    const int nc = csize[c];
+    if (nc == 0) continue;
+    ++k;
+    const long long adj = (long long)rstart[cstart[c + 1]] - rstart[cstart[c]];
+    adj_sum += adj;
+    if (nc > small_max) {
+      ++kb;
+      work += (double)nc * (double)(adj + nc);
+      if (nc > lds_max) ++kg;
+    }
+  }
+  s_k[tid] = k;
+  s_big[tid] = kb;
+  s_glob[tid] = kg;
+  s_work[tid] = work;
+  s_adj[tid] = adj_sum;
+  __syncthreads();
+  if (tid == 0) {
+    int K = 0, KB = 0, KG = 0;
+    double W = 0;
+    long long A = 0;
+    for (int q = 0; q < kThreads; ++q) {
+      K += s_k[q];
+      KB += s_big[q];
+      KG += s_glob[q];
+      W += s_work[q];
+      A += s_adj[q];
+    }
+    s_k[0] = K;
+    s_big[0] = KB;
+    s_glob[0] = KG;
+    s_work[0] = W;
+    hdr[H_K] = K;
+    hdr[H_KBIG] = KB;
+    hdr[H_KGLOB] = KG;
+    hdr[H_WORK] = (long long)W;    // sum of nc (adjacency + nc) over the 256-thread components (measurement)
+    hdr[H_ADJ] = A;
+  }
+  __syncthreads();
+  const int K = s_k[0], KB = s_big[0], KG = s_glob[0];
+  const double target = s_work[0] / kBtItems > 1.0 ? s_work[0] / kBtItems : 1.0;
+  // per-thread contiguous ranges of components, then one scan of the 256 sums
+  const int per = (K + kThreads - 1) / kThreads, c0 = tid * per, c1 = c0 + per < K ? c0 + per : K;
+  long long items = 0, part = 0;
+  for (int c = c0; c < c1; ++c) {
+    const int nc = csize[c];
+    int s = nc;
+    if (c < KB) {
+      const double cost = (double)((long long)rstart[cstart[c + 1]] - rstart[cstart[c]] + nc);
+      const double want = ceil(target / cost);
+      s = want < (double)nc ? (int)want : nc;
+      if (s < 1) s = 1;
+    }
+    spi[c] = s;
+    const int it = (nc + s - 1) / s;
+    items += it;
+    part += (long long)it * nc;
+  }
+  s_items[tid] = items;
+  s_part[tid] = part;
+  __syncthreads();
+  if (tid == 0) {
+    long long ri = 0, rp = 0;
+    for (int q = 0; q < kThreads; ++q) {
+      const long long a = s_items[q], b = s_part[q];
+      s_items[q] = ri;
+      s_part[q] = rp;
+      ri += a;
+      rp += b;
+    }
+    ibase[K] = (int)ri;
+    pbase[K] = rp;
+    hdr[H_PARTIAL] = rp;
+  }
+  __syncthreads();
+  items = s_items[tid];
+  part = s_part[tid];
+  for (int c = c0; c < c1; ++c) {
+    const int nc = csize[c], it = (nc + spi[c] - 1) / spi[c];
+    ibase[c] = (int)items;
+    pbase[c] = part;
+    items += it;
+    part += (long long)it * nc;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    hdr[H_ITEMS] = ibase[KB];
+    hdr[H_ITEMS_GLOB] = ibase[KG];
+    hdr[H_NC_GLOB] = KG > 0 ? csize[0] : 0;
+    hdr[H_NC_LDS] = KG < KB ? csize[KG] : 0;
+  }
+}
+
+// Brandes for sources [s0, s1) of one component of nc vertices (comp-relative ids; the local CSR row of v is
+// rstart[base + v] ..., its neighbours nb[] - base).  SUB lanes share a vertex (64: a wave walks the row; 1: a lane).
+// State: lev / q (BFS order) / ls (level starts, nc + 2) int, sig (path counts), cof = (1 + delta) / sig and bc (this
+// item's sum over its sources) double.  Levels are pushed (discover), sigma and delta pulled in CSR order, so every
+// value is a fixed-order sum whatever order the queue was filled in.
+template <int SUB>
+__device__ __forceinline__ double bt_sum(double x) {
+  if (SUB > 1)
+#pragma unroll
+    for (int o = SUB / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, SUB);
+  return x;
+}
+
+template <int SUB>
+__device__ __forceinline__ void bt_brandes(const unsigned *__restrict__ rstart, const int *__restrict__ nb, int base,
+                                           int nc, int s0, int s1, int *lev, int *q, int *ls, double *sig, double *cof,
+                                           double *bc, int *tail) {
+  const int tid = threadIdx.x, nthr = blockDim.x, g = tid / SUB, l = tid % SUB, ng = nthr / SUB;
+  const unsigned *rs = rstart + base;
+  for (int v = tid; v < nc; v += nthr) bc[v] = 0.0;
+  for (int s = s0; s < s1; ++s) {
+    for (int v = tid; v < nc; v += nthr) lev[v] = -1;
+    __syncthreads();
+    if (tid == 0) {
+      lev[s] = 0;
+      sig[s] = 1.0;
+      q[0] = s;
+      ls[0] = 0;
+      ls[1] = 1;
+      *tail = 1;
+    }
+    __syncthreads();
+    int d = 0;
+    while (true) {                       // level d: its sigma (pulled from d - 1), and level d + 1 discovered
+      const int a = ls[d], b = ls[d + 1];
+      if (a == b) break;
+      for (int k = a + g; k < b; k += ng) {
+        const int w = q[k];
+        double acc = 0.0;
+        for (unsigned e = rs[w] + l; e < rs[w + 1]; e += SUB) {
+          const int x = nb[e] - base;
+          const int lx = lev[x];
+          if (lx < 0) {                  // (before the sigma test: at d = 0, d - 1 is the undiscovered mark)
+            if (atomicCAS(&lev[x], -1, d + 1) == -1) q[atomicAdd(tail, 1)] = x;
+          } else if (lx == d - 1) {
+            acc += sig[x];
+          }
+        }
+        acc = bt_sum<SUB>(acc);
+        if (d > 0 && l == 0) sig[w] = acc;
+      }
+      __syncthreads();
+      if (tid == 0) ls[d + 2] = *tail;
+      __syncthreads();
+      ++d;
+    }
+    for (int dd = d - 1; dd >= 1; --dd) {    // levels d - 1 .. 1: delta pulled from the level below
+      const int a = ls[dd], b = ls[dd + 1];
+      for (int k = a + g; k < b; k += ng) {
+        const int v = q[k];
+        double acc = 0.0;
+        for (unsigned e = rs[v] + l; e < rs[v + 1]; e += SUB) {
+          const int x = nb[e] - base;
+          if (lev[x] == dd + 1) acc += cof[x];
+        }
+        acc = bt_sum<SUB>(acc);
+        if (l == 0) {
+          const double sv = sig[v], delta = sv * acc;
+          bc[v] += delta;
+          cof[v] = (1.0 + delta) / sv;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__device__ __forceinline__ int bt_comp_of(const int *first, int count, int x) {   // last c < count with first[c] <= x
+  int lo = 0, hi = count;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (first[mid] <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// 256-thread items [i0, i1) (dynamic fetch: which workgroup runs an item changes nothing it writes); state in LDS
+// (slab == nullptr) or in this workgroup's part of a global slab of slab_stride bytes
+template <bool IN_LDS>
+__global__ void __launch_bounds__(kThreads) bt_items_kernel(const unsigned *rstart, const int *nb, const int *csize,
+                                                            const int *cstart, const int *spi, const int *ibase,
+                                                            const long long *pbase, int kbig, int i0, int i1,
+                                                            unsigned *next, char *slab, size_t slab_stride,
+                                                            double *partial) {
+  extern __shared__ double lds_state[];
+  __shared__ int item, tail;
+  char *mine = IN_LDS ? reinterpret_cast<char *>(lds_state) : slab + (size_t)blockIdx.x * slab_stride;
+  while (true) {
+    __syncthreads();
+    if (threadIdx.x == 0) item = i0 + (int)atomicAdd(next, 1u);
+    __syncthreads();
+    const int k = item;
+    if (k >= i1) break;
+    const int c = bt_comp_of(ibase, kbig, k), nc = csize[c], base = cstart[c];
+    const int s0 = (k - ibase[c]) * spi[c], s1 = s0 + spi[c] < nc ? s0 + spi[c] : nc;
+    double *sig = reinterpret_cast<double *>(mine), *cof = sig + nc, *bc = cof + nc;
+    int *lev = reinterpret_cast<int *>(bc + nc), *q = lev + nc, *ls = q + nc;
+    bt_brandes<64>(rstart, nb, base, nc, s0, s1, lev, q, ls, sig, cof, bc, &tail);
+    __syncthreads();
+    double *out = partial + pbase[c] + (long long)(k - ibase[c]) * nc;
+    for (int v = threadIdx.x; v < nc; v += blockDim.x) out[v] = bc[v];
+  }
+}
+
+// one wave per component of at most kBtSmallCap vertices, every source
+__global__ void __launch_bounds__(64) bt_small_kernel(const unsigned *rstart, const int *nb, const int *csize,
+                                                      const int *cstart, const long long *pbase, int k0,
+                                                      double *partial) {
+  __shared__ double sig[kBtSmallCap], cof[kBtSmallCap], bc[kBtSmallCap];
+  __shared__ int lev[kBtSmallCap], q[kBtSmallCap], ls[kBtSmallCap + 2], tail;
+  const int c = k0 + blockIdx.x, nc = csize[c];
+  if (nc > kBtSmallCap) return;        // (the plan never sends one)
+  bt_brandes<1>(rstart, nb, cstart[c], nc, 0, nc, lev, q, ls, sig, cof, bc, &tail);
+  __syncthreads();
+  double *out = partial + pbase[c];
+  for (int v = threadIdx.x; v < nc; v += blockDim.x) out[v] = bc[v];
+}
+
+// per scored vertex: the sum of its component's partials in item order, times 1 / ((nc - 1)(nc - 2))
+__global__ void __launch_bounds__(kThreads) bt_reduce_kernel(const double *partial, const int *csize,
+                                                             const int *cstart, const int *ibase,
+                                                             const long long *pbase, const long long *hdr, double *val) {
+  const int K = (int)hdr[H_K], ns = (int)hdr[H_SCORED];
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < ns; p += gridDim.x * blockDim.x) {
+    const int c = bt_comp_of(cstart, K, p), nc = csize[c], items = ibase[c + 1] - ibase[c];
+    const double *x = partial + pbase[c] + (p - cstart[c]);
+    double acc = 0.0;
+    for (int k = 0; k < items; ++k) acc += x[(long long)k * nc];
+    val[p] = acc * (1.0 / ((double)(nc - 1) * (double)(nc - 2)));
+  }
+}
+
+// per component its maximum; then (one thread, component order) the mean and the size-weighted mean
+__global__ void __launch_bounds__(kThreads) bt_summary_kernel(const double *val, const int *csize, const int *cstart,
+                                                              const long long *hdr, double *cmax, int t, double *bt,
+                                                              long long *scored) {
+  const int K = (int)hdr[H_K];
+  for (int c = threadIdx.x; c < K; c += blockDim.x) {
+    double m = 0.0;
+    for (int p = cstart[c]; p < cstart[c + 1]; ++p) m = val[p] > m ? val[p] : m;
+    cmax[c] = m;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double mean = 0.0, wmean = 0.0;
+  if (K == 1) {
+    mean = wmean = cmax[0];
+  } else if (K > 1) {
+    double s = 0.0, sw = 0.0, w = 0.0;
+    for (int c = 0; c < K; ++c) {
+      s += cmax[c];
+      sw += cmax[c] * (double)csize[c];
+      w += (double)csize[c];
+    }
+    mean = s / K;
+    wmean = sw / w;
+  }
+  bt[2 * t] = mean;
+  bt[2 * t + 1] = wmean;
+  if (scored) scored[t] = K;
+}
+
+__global__ void __launch_bounds__(kThreads) bt_values_kernel(const double *val, const int *order, const long long *hdr,
+                                                             double *values) {
+  const int ns = (int)hdr[H_SCORED];
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < ns; p += gridDim.x * blockDim.x) values[order[p]] = val[p];
+}
+
+// offsets without edges of their own repeat the row before them (zeros before the first edge)
+__global__ void bt_fill_kernel(const unsigned *cnt, int n_off, double *bt, long long *scored) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  for (int t = 0; t < n_off; ++t) {
+    if (cnt[t]) continue;
+    bt[2 * t] = t ? bt[2 * t - 2] : 0.0;
+    bt[2 * t + 1] = t ? bt[2 * t - 1] : 0.0;
+    if (scored) scored[t] = t ? scored[t - 1] : 0;
+  }
+}
+
+long long *pinned_plan(int dev) {
+  static long long *blocks[64] = {};
+  if (dev < 0 || dev >= 64) return nullptr;
+  if (!blocks[dev] && hipHostMalloc(reinterpret_cast<void **>(&blocks[dev]), H_LEN * 8, hipHostMallocDefault) != hipSuccess)
+    blocks[dev] = nullptr;
+  return blocks[dev];
+}
+
+// what the betweenness stage reads from the counts' stages, and writes
+struct BtJob {
+  double *bt;                  // [n_off][2]
+  long long *scored;           // [n_off] or nullptr
+  double *values;              // [n] or nullptr
+  long long values_at;         // -1: no values
+};
+
+int bt_run(const BtJob &job, hipStream_t s, int dev, size_t n, size_t m, size_t no, const std::vector<unsigned> &counts,
+           const std::vector<unsigned> &starts, const unsigned *cnt, const int *bu, const int *bv, int *parent,
+           const unsigned long long *keys, const int *nbr) {
+  const size_t e = 2 * m;
+  unsigned bits = 1;
+  while (bits < 32 && ((size_t)1 << bits) < n) ++bits;
+  const unsigned end_bit = 32 + bits;
+  size_t sort_tmp = 0, sort_tmp2 = 0;
+  if (n) PPK_HIP(rocprim::radix_sort_keys(nullptr, sort_tmp, (unsigned long long *)nullptr, (unsigned long long *)nullptr, n, 0u, end_bit, s));
+  if (e) PPK_HIP(rocprim::radix_sort_keys(nullptr, sort_tmp2, (unsigned long long *)nullptr, (unsigned long long *)nullptr, e, 0u, end_bit, s));
+  const size_t tmp = sort_tmp > sort_tmp2 ? sort_tmp : sort_tmp2;
+  size_t at = 0;
+  const size_t o_hdr = at; at += 256;
+  const size_t o_fill = at; at += 256;
+  const size_t o_root = at; at += align256(n * 4);
+  const size_t o_size = at; at += align256(n * 4);
+  const size_t o_crank = at; at += align256(n * 4);
+  const size_t o_csize = at; at += align256((n + 2) * 4);
+  const size_t o_cstart = at; at += align256((n + 2) * 4);
+  const size_t o_spi = at; at += align256((n + 2) * 4);
+  const size_t o_ibase = at; at += align256((n + 2) * 4);
+  const size_t o_pbase = at; at += align256((n + 2) * 8);
+  const size_t o_local = at; at += align256(n * 4);
+  const size_t o_order = at; at += align256(n * 4);
+  const size_t o_ka = at; at += align256(n * 8);
+  const size_t o_kb = at; at += align256(n * 8);
+  const size_t o_rstart = at; at += align256((n + 1) * 4);
+  const size_t o_val = at; at += align256(n * 8);
+  const size_t o_cmax = at; at += align256(n * 8);
+  const size_t o_ea = at; at += align256(e * 8);
+  const size_t o_eb = at; at += align256(e * 8);
+  const size_t o_lnbr = at; at += align256(e * 4);
+  const size_t o_tmp = at; at += align256(tmp + 16);
+  void *base = nullptr;
+  int rc = ppk_scratch_get(dev, SLOT_NET_BT, at, &base);
+  if (rc != PPK_OK) return rc;
+  char *B = static_cast<char *>(base);
+  long long *hdr = reinterpret_cast<long long *>(B + o_hdr);
+  unsigned *fill = reinterpret_cast<unsigned *>(B + o_fill);
+  int *root = reinterpret_cast<int *>(B + o_root), *size = reinterpret_cast<int *>(B + o_size);
+  int *crank = reinterpret_cast<int *>(B + o_crank), *csize = reinterpret_cast<int *>(B + o_csize);
+  int *cstart = reinterpret_cast<int *>(B + o_cstart), *spi = reinterpret_cast<int *>(B + o_spi);
+  int *ibase = reinterpret_cast<int *>(B + o_ibase);
+  long long *pbase = reinterpret_cast<long long *>(B + o_pbase);
+  int *local = reinterpret_cast<int *>(B + o_local), *order = reinterpret_cast<int *>(B + o_order);
+  unsigned long long *ka = reinterpret_cast<unsigned long long *>(B + o_ka), *kb = reinterpret_cast<unsigned long long *>(B + o_kb);
+  unsigned *rstart = reinterpret_cast<unsigned *>(B + o_rstart);
+  double *val = reinterpret_cast<double *>(B + o_val), *cmax = reinterpret_cast<double *>(B + o_cmax);
+  unsigned long long *ea = reinterpret_cast<unsigned long long *>(B + o_ea), *eb = reinterpret_cast<unsigned long long *>(B + o_eb);
+  int *lnbr = reinterpret_cast<int *>(B + o_lnbr);
+  void *d_tmp = B + o_tmp;
+  long long *h = pinned_plan(dev);
+  if (!h) return ppk_fail(PPK_ERR_HIP, "hipHostMalloc failed");
+
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  static bool big_lds[64] = {}, asked[64] = {};
+  if (!asked[dev & 63]) {
+    asked[dev & 63] = true;
+    big_lds[dev & 63] = hipFuncSetAttribute(reinterpret_cast<const void *>(bt_items_kernel<true>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBtLdsBytes) == hipSuccess;
+    (void)hipGetLastError();
+  }
+  long long lds_max = (long long)(((big_lds[dev & 63] ? kBtLdsBytes : 65536 - 64) - 8) / 36);
+  const long long forced_lds = ppk_config().bt_lds_max.load();
+  if (forced_lds > 0 && forced_lds < lds_max) lds_max = forced_lds;
+  long long small_max = ppk_config().bt_small_max.load();
+  if (small_max < 0) small_max = 0;
+  if (small_max > kBtSmallCap) small_max = kBtSmallCap;
+
+  // the graph values are read from: the last one at or before values_at that adds edges
+  long long values_graph = -1;
+  if (job.values) {
+    PPK_HIP(hipMemsetAsync(job.values, 0, n * 8, s));
+    for (long long o = 0; o <= job.values_at && o < (long long)no; ++o)
+      if (counts[o]) values_graph = o;
+  }
+
+  hipLaunchKernelGGL(net_parent_init_kernel, dim3(grid_for(n, kThreads, 4096)), dim3(kThreads), 0, s, parent, n);
+  PPK_HIP(hipGetLastError());
+  size_t edges_t = 0;
+  for (size_t o = 0; o < no; ++o) {
+    if (!counts[o]) continue;
+    edges_t += counts[o];
+    // -- relabel
+    ppk_prof_stage("bt_relabel", s);
+    hipLaunchKernelGGL(net_union_kernel, dim3(grid_for(counts[o], kThreads * 4, 2048)), dim3(kThreads), 0, s,
+                       bu + starts[o], bv + starts[o], counts[o], parent, fill + 1);
+    PPK_HIP(hipMemsetAsync(size, 0, n * 4, s));
+    PPK_HIP(hipMemsetAsync(fill, 0, 4, s));
+    const dim3 gn(grid_for(n, kThreads, 4096));
+    hipLaunchKernelGGL(bt_sizes_kernel, gn, dim3(kThreads), 0, s, parent, n, root, size);
+    hipLaunchKernelGGL(bt_root_keys_kernel, gn, dim3(kThreads), 0, s, root, size, n, ka);
+    size_t tb = tmp;
+    PPK_HIP(rocprim::radix_sort_keys(d_tmp, tb, ka, kb, n, 0u, end_bit, s));
+    hipLaunchKernelGGL(bt_comps_kernel, dim3(grid_for(n + 1, kThreads, 4096)), dim3(kThreads), 0, s, kb, size, n,
+                       crank, csize);
+    hipLaunchKernelGGL(bt_starts_kernel, dim3(1), dim3(kThreads), 0, s, csize, n, cstart, hdr);
+    hipLaunchKernelGGL(bt_vertex_keys_kernel, gn, dim3(kThreads), 0, s, root, size, crank, n, ka, local);
+    tb = tmp;
+    PPK_HIP(rocprim::radix_sort_keys(d_tmp, tb, ka, kb, n, 0u, end_bit, s));
+    hipLaunchKernelGGL(bt_local_kernel, gn, dim3(kThreads), 0, s, kb, n, local, order);
+    const size_t len = 2 * edges_t;
+    PPK_HIP(hipMemsetAsync(ea, 0xff, len * 8, s));
+    hipLaunchKernelGGL(bt_edges_kernel, dim3(grid_for(e, kThreads * 8, 4096)), dim3(kThreads), 0, s, keys, nbr, e,
+                       (unsigned)o, local, fill, ea);
+    tb = tmp;
+    PPK_HIP(rocprim::radix_sort_keys(d_tmp, tb, ea, eb, len, 0u, end_bit, s));
+    hipLaunchKernelGGL(bt_rows_kernel, dim3(grid_for(len, kThreads, 8192)), dim3(kThreads), 0, s, eb, len, hdr,
+                       rstart, lnbr);
+    PPK_HIP(hipGetLastError());
+    // -- plan: the graph's one synchronisation
+    ppk_prof_stage("bt_plan", s);
+    hipLaunchKernelGGL(bt_plan_kernel, dim3(1), dim3(kThreads), 0, s, csize, cstart, rstart, n, (int)small_max,
+                       (int)lds_max, spi, ibase, pbase, hdr);
+    PPK_HIP(hipGetLastError());
+    PPK_HIP(hipMemcpyAsync(h, hdr, H_LEN * 8, hipMemcpyDeviceToHost, s));
+    PPK_HIP(hipStreamSynchronize(s));
+    const int K = (int)h[H_K], kbig = (int)h[H_KBIG], n_items = (int)h[H_ITEMS], items_glob = (int)h[H_ITEMS_GLOB];
+    const size_t n_partial = (size_t)h[H_PARTIAL], nc_glob = (size_t)h[H_NC_GLOB], nc_lds = (size_t)h[H_NC_LDS];
+    // -- Brandes
+    ppk_prof_stage("bt_brandes", s);
+    if (K > 0) {
+      const unsigned g_glob = items_glob > 0 ? (unsigned)(items_glob < 2 * cus ? items_glob : 2 * cus) : 0;
+      const size_t slab_stride = align256(bt_state_bytes(nc_glob));
+      void *wbase = nullptr;
+      rc = ppk_scratch_get(dev, SLOT_NET_WORK, 256 + align256(n_partial * 8) + g_glob * slab_stride, &wbase);
+      if (rc != PPK_OK) return rc;
+      char *W = static_cast<char *>(wbase);
+      unsigned *next = reinterpret_cast<unsigned *>(W);
+      double *partial = reinterpret_cast<double *>(W + 256);
+      char *slab = W + 256 + align256(n_partial * 8);
+      PPK_HIP(hipMemsetAsync(next, 0, 8, s));
+      if (items_glob > 0)
+        hipLaunchKernelGGL(bt_items_kernel<false>, dim3(g_glob), dim3(kThreads), 0, s, rstart, lnbr, csize, cstart,
+                           spi, ibase, pbase, kbig, 0, items_glob, next, slab, slab_stride, partial);
+      if (n_items > items_glob) {
+        const int li = n_items - items_glob;
+        hipLaunchKernelGGL(bt_items_kernel<true>, dim3((unsigned)(li < 8 * cus ? li : 8 * cus)), dim3(kThreads),
+                           bt_state_bytes(nc_lds), s, rstart, lnbr, csize, cstart, spi, ibase, pbase, kbig, items_glob,
+                           n_items, next + 1, (char *)nullptr, (size_t)0, partial);
+      }
+      if (K > kbig)
+        hipLaunchKernelGGL(bt_small_kernel, dim3((unsigned)(K - kbig)), dim3(64), 0, s, rstart, lnbr, csize, cstart,
+                           pbase, kbig, partial);
+      PPK_HIP(hipGetLastError());
+      ppk_prof_stage("bt_reduce", s);
+      hipLaunchKernelGGL(bt_reduce_kernel, dim3(grid_for((size_t)h[H_SCORED], kThreads, 4096)), dim3(kThreads), 0, s,
+                         partial, csize, cstart, ibase, pbase, hdr, val);
+    }
+    if (K == 0) ppk_prof_stage("bt_reduce", s);
+    hipLaunchKernelGGL(bt_summary_kernel, dim3(1), dim3(kThreads), 0, s, val, csize, cstart, hdr, cmax, (int)o, job.bt,
+                       job.scored);
+    if ((long long)o == values_graph && K > 0)
+      hipLaunchKernelGGL(bt_values_kernel, dim3(grid_for((size_t)h[H_SCORED], kThreads, 4096)), dim3(kThreads), 0, s,
+                         val, order, hdr, job.values);
+    PPK_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(bt_fill_kernel, dim3(1), dim3(64), 0, s, cnt, (int)no, job.bt, job.scored);
+  PPK_HIP(hipGetLastError());
+  return PPK_OK;
+}
+
+int net_sweep(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off, size_t n_edges,
+              size_t n_vertices, size_t n_off, long long labels_at, long long *d_stats, int32_t *d_labels, void *stream,
+              const BtJob *bt) {
   if (n_off == 0 || n_off > (size_t)kMaxOff) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_off must be 1 .. 1023");
   if (!d_off && n_off != 1 && n_edges)
     return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: no offset array needs n_off == 1");
@@ -527,9 +1131,25 @@ extern "C" int ppk_network_sweep_dev(const long long *d_i, const long long *d_j,
     PPK_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(net_stats_kernel, dim3(1), dim3(64), 0, s, cnt, links, tri, wed, (long long)n, (int)no, d_stats);
+  if (bt) {
+    PPK_HIP(hipGetLastError());
+    rc = bt_run(*bt, s, dev, n, m, no, counts, starts, cnt, bu, bv, parent, kb, nbr);
+    if (rc != PPK_OK) {
+      ppk_prof_stage(nullptr, s);
+      return rc;
+    }
+  }
   ppk_prof_stage(nullptr, s);
   PPK_HIP(hipGetLastError());
   return PPK_OK;
+}
+
+}  // namespace
+
+extern "C" int ppk_network_sweep_dev(const long long *d_i, const long long *d_j, size_t stride,
+                                     const long long *d_off, size_t n_edges, size_t n_vertices, size_t n_off,
+                                     long long labels_at, long long *d_stats, int32_t *d_labels, void *stream) {
+  return net_sweep(d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, labels_at, d_stats, d_labels, stream, nullptr);
 }
 
 extern "C" int ppk_network_sweep(const long long *i, const long long *j, const long long *off, size_t n_edges,
@@ -562,5 +1182,54 @@ extern "C" int ppk_network_sweep(const long long *i, const long long *j, const l
   if (rc != PPK_OK) return rc;
   PPK_HIP(hipMemcpy(stats, d_stats, n_off * 32, hipMemcpyDeviceToHost));
   if (labels_at >= 0 && n_vertices) PPK_HIP(hipMemcpy(labels, d_labels, n_vertices * 4, hipMemcpyDeviceToHost));
+  return PPK_OK;
+}
+
+extern "C" int ppk_network_summary_dev(const long long *d_i, const long long *d_j, size_t stride,
+                                       const long long *d_off, size_t n_edges, size_t n_vertices, size_t n_off,
+                                       long long values_at, long long *d_stats, double *d_bt, long long *d_scored,
+                                       double *d_values, void *stream) {
+  if (n_off >= 1 && n_off <= (size_t)kMaxOff && (values_at < -1 || values_at >= (long long)n_off))
+    return ppk_fail(PPK_ERR_ARG, "ppk_network_summary: values_at must be -1 or an offset index");
+  if (!d_bt || (values_at >= 0 && !d_values && n_vertices)) return ppk_fail(PPK_ERR_ARG, "ppk_network_summary: NULL array");
+  const BtJob job{d_bt, d_scored, values_at >= 0 && n_vertices ? d_values : nullptr, values_at};
+  return net_sweep(d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, -1, d_stats, nullptr, stream, &job);
+}
+
+extern "C" int ppk_network_summary(const long long *i, const long long *j, const long long *off, size_t n_edges,
+                                   size_t n_vertices, size_t n_off, int device_id, long long values_at, long long *stats,
+                                   double *bt, long long *scored, double *values) {
+  if (!stats || !bt || (n_edges && (!i || !j)) || (values_at >= 0 && !values && n_vertices))
+    return ppk_fail(PPK_ERR_ARG, "ppk_network_summary: NULL array");
+  if (n_off == 0 || n_off > (size_t)kMaxOff) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_off must be 1 .. 1023");
+  if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_edges must be < 2^31");
+  if (n_vertices >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_vertices must be < 2^31");
+  DeviceGuard guard(device_id);
+  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
+  PpkCall call(device_id, nullptr);
+  const size_t eb = align256(n_edges * 8), sb = align256(n_off * 32), bb = align256(n_off * 16), cb = align256(n_off * 8);
+  const size_t vb = align256(n_vertices * 8);
+  void *p = nullptr;
+  int rc = ppk_scratch_get(device_id, SLOT_HOST_IN, 3 * eb + sb + bb + cb + vb + 256, &p);
+  if (rc != PPK_OK) return rc;
+  char *B = static_cast<char *>(p);
+  long long *d_i = reinterpret_cast<long long *>(B), *d_j = reinterpret_cast<long long *>(B + eb);
+  long long *d_o = off ? reinterpret_cast<long long *>(B + 2 * eb) : nullptr;
+  long long *d_stats = reinterpret_cast<long long *>(B + 3 * eb);
+  double *d_bt = reinterpret_cast<double *>(B + 3 * eb + sb);
+  long long *d_scored = reinterpret_cast<long long *>(B + 3 * eb + sb + bb);
+  double *d_values = reinterpret_cast<double *>(B + 3 * eb + sb + bb + cb);
+  if (n_edges) {
+    PPK_HIP(hipMemcpy(d_i, i, n_edges * 8, hipMemcpyHostToDevice));
+    PPK_HIP(hipMemcpy(d_j, j, n_edges * 8, hipMemcpyHostToDevice));
+    if (off) PPK_HIP(hipMemcpy(d_o, off, n_edges * 8, hipMemcpyHostToDevice));
+  }
+  rc = ppk_network_summary_dev(d_i, d_j, 1, d_o, n_edges, n_vertices, n_off, values_at, d_stats, d_bt, d_scored,
+                               values_at >= 0 ? d_values : nullptr, nullptr);
+  if (rc != PPK_OK) return rc;
+  PPK_HIP(hipMemcpy(stats, d_stats, n_off * 32, hipMemcpyDeviceToHost));
+  PPK_HIP(hipMemcpy(bt, d_bt, n_off * 16, hipMemcpyDeviceToHost));
+  if (scored) PPK_HIP(hipMemcpy(scored, d_scored, n_off * 8, hipMemcpyDeviceToHost));
+  if (values_at >= 0 && n_vertices) PPK_HIP(hipMemcpy(values, d_values, n_vertices * 8, hipMemcpyDeviceToHost));
   return PPK_OK;
 }

@@ -451,12 +451,8 @@ def threshold_iterate_2d_dev(dist_t, x_max, y_max, cap=None):
             cap = m
 
 
-def network_sweep_dev(i_t, j_t, off_t, n, n_off, labels_at=None):
-    """The counts behind networkSummary for every step of refine.growNetwork (ppk_network_sweep_dev, DESIGN.md 3.7):
-    G_t = the edges (i_t[k], j_t[k]) with off_t[k] <= t over vertices 0 .. n-1.  int64 CUDA tensors of one length (a
-    strided view such as edges[:, 0] is read in place); off_t None puts every edge at offset 0 (n_off must be 1).
-    Returns (stats int64 [n_off, 4] = edges, components, triangles, connected triples; labels int32 [n] of
-    G_{labels_at} numbered as scipy's connected_components, or None)."""
+def _edge_stream(i_t, j_t, off_t):
+    """(m, stride) of the edge stream of network_sweep_dev / network_summary_dev, after checking its tensors."""
     torch = _torch()
     m = int(i_t.shape[0])
     for t in (i_t, j_t) + ((off_t,) if off_t is not None else ()):
@@ -467,6 +463,17 @@ def network_sweep_dev(i_t, j_t, off_t, n, n_off, labels_at=None):
         raise TypeError("edge arrays must be contiguous, or the two columns of a contiguous [m, 2] tensor")
     if off_t is not None and off_t.stride(0) != 1 and m > 1:
         raise TypeError("the offset array must be contiguous")
+    return m, stride
+
+
+def network_sweep_dev(i_t, j_t, off_t, n, n_off, labels_at=None):
+    """The counts behind networkSummary for every step of refine.growNetwork (ppk_network_sweep_dev, DESIGN.md 3.7):
+    G_t = the edges (i_t[k], j_t[k]) with off_t[k] <= t over vertices 0 .. n-1.  int64 CUDA tensors of one length (a
+    strided view such as edges[:, 0] is read in place); off_t None puts every edge at offset 0 (n_off must be 1).
+    Returns (stats int64 [n_off, 4] = edges, components, triangles, connected triples; labels int32 [n] of
+    G_{labels_at} numbered as scipy's connected_components, or None)."""
+    torch = _torch()
+    m, stride = _edge_stream(i_t, j_t, off_t)
     la = -1 if labels_at is None else int(labels_at)
     dev = i_t.device
     with torch.cuda.device(dev):
@@ -492,6 +499,42 @@ def network_stats_dev(edges_t, n, labels=False):
     return stats[0], lab
 
 
+def network_summary_dev(i_t, j_t, off_t, n, n_off, values_at=None):
+    """network_sweep_dev plus networkSummary's betweenness for every G_t (ppk_network_summary_dev).
+    The same edge stream and checks.  Returns (stats int64 [n_off, 4], bit for bit network_sweep_dev's; bt float64
+    [n_off, 2] = mean and size-weighted mean over the components of more than 3 vertices of their maximum normalised
+    vertex betweenness; scored int64 [n_off] = how many such components; values float64 [n] = every vertex's
+    normalised betweenness in G_{values_at} within its component, or None), CUDA tensors."""
+    torch = _torch()
+    m, stride = _edge_stream(i_t, j_t, off_t)
+    va = -1 if values_at is None else int(values_at)
+    dev = i_t.device
+    no = max(int(n_off), 1)
+    with torch.cuda.device(dev):
+        stats = torch.empty((no, 4), dtype=torch.int64, device=dev)
+        bt = torch.empty((no, 2), dtype=torch.float64, device=dev)
+        scored = torch.empty(no, dtype=torch.int64, device=dev)
+        values = torch.empty(max(int(n), 1), dtype=torch.float64, device=dev) if va >= 0 else None
+        rc = _lib.lib().ppk_network_summary_dev(
+            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride,
+            C.c_void_p(off_t.data_ptr()) if off_t is not None else None, m, int(n), int(n_off), va,
+            C.c_void_p(stats.data_ptr()), C.c_void_p(bt.data_ptr()), C.c_void_p(scored.data_ptr()),
+            C.c_void_p(values.data_ptr()) if values is not None else None, _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_network_summary_dev")
+    return stats, bt, scored, (values[:int(n)] if values is not None else None)
+
+
+def network_summary_graph_dev(edges_t, n, values=False):
+    """network_summary_dev of one int64 [m, 2] CUDA edge list, read in place.  Returns (stats int64 [4], bt float64
+    [2], scored int64 [] and values float64 [n] or None)."""
+    torch = _torch()
+    if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
+            and edges_t.is_contiguous()):
+        raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
+    stats, bt, scored, val = network_summary_dev(edges_t[:, 0], edges_t[:, 1], None, n, 1, 0 if values else None)
+    return stats[0], bt[0], scored[0], val
+
+
 def _samples_of(n_rows):
     n = int((1 + (1 + 8 * n_rows) ** 0.5) // 2)
     while n * (n - 1) // 2 > n_rows:
@@ -503,26 +546,39 @@ def _samples_of(n_rows):
     return n
 
 
-def _sweep_scores(dist_t, sweep, n_off):
+def _sweep_scores(dist_t, sweep, n_off, score_idx=0):
     from . import refine
     n = _samples_of(dist_t.shape[0])
     i, j, o = sweep
-    stats, _ = network_sweep_dev(i, j, o, n, n_off)
-    st = stats.cpu().numpy()
-    return stats, refine.grow_scores(st, n)
+    if score_idx == 0:
+        stats, _ = network_sweep_dev(i, j, o, n, n_off)
+        st = stats.cpu().numpy()
+        return stats, refine.grow_scores(st, n)
+    stats, bt, _, _ = network_summary_dev(i, j, o, n, n_off)
+    return stats, refine.grow_scores(stats.cpu().numpy(), n, score_idx, bt=bt.cpu().numpy())
 
 
-def refine_sweep_scores_dev(dist_t, offsets, slope, x0, y0, x1, y1):
+def _check_score_idx(score_idx):
+    if score_idx not in (0, 1, 2):
+        raise ValueError("score_idx must be 0, 1 or 2")
+    return int(score_idx)
+
+
+def refine_sweep_scores_dev(dist_t, offsets, slope, x0, y0, x1, y1, score_idx=0):
     """thresholdIterate1D + growNetwork on a resident float32 [n,2] CUDA matrix, without the edge list leaving the
-    device (PopPUNK/refine.py:190-202).  Returns (stats int64 [len(offsets), 4] CUDA, growNetwork's score list)."""
+    device (PopPUNK/refine.py:190-202).  Returns (stats int64 [len(offsets), 4] CUDA, growNetwork's score list).
+    score_idx 1 / 2 (refine's --score-idx) scores with the mean / size-weighted mean betweenness (network_summary_dev);
+    0 leaves betweenness out, as growNetwork does."""
+    score_idx = _check_score_idx(score_idx)
     off = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
-    return _sweep_scores(dist_t, threshold_iterate_1d_dev(dist_t, off, slope, x0, y0, x1, y1), off.size)
+    return _sweep_scores(dist_t, threshold_iterate_1d_dev(dist_t, off, slope, x0, y0, x1, y1), off.size, score_idx)
 
 
-def refine_sweep_scores_2d_dev(dist_t, x_max, y_max):
+def refine_sweep_scores_2d_dev(dist_t, x_max, y_max, score_idx=0):
     """thresholdIterate2D + growNetwork for one y (PopPUNK/refine.py:587-595), as refine_sweep_scores_dev."""
+    score_idx = _check_score_idx(score_idx)
     xm = np.ascontiguousarray(x_max, dtype=np.float32).ravel()
-    return _sweep_scores(dist_t, threshold_iterate_2d_dev(dist_t, xm, y_max), xm.size)
+    return _sweep_scores(dist_t, threshold_iterate_2d_dev(dist_t, xm, y_max), xm.size, score_idx)
 
 
 def long_to_square_dev(dist_t, col, n):
