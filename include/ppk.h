@@ -438,6 +438,39 @@ int ppk_network_summary(const long long *i, const long long *j, const long long 
                         double *bt, long long *scored, double *values);
 
 /* ------------------------------------------------------------------------
+ * Minimum spanning forests.  Edges d_i[k * stride], d_j[k * stride] (stride 1: separate arrays; 2:
+ * an int64 [m][2] edge list, d_j = d_i + 1), weights d_w[k], over vertices 0 .. n_vertices-1; i > j, parallel edges and
+ * both orientations of a pair allowed.  Edges are totally ordered by (w, min(i, j), max(i, j), k), -0.0 read as +0.0;
+ * under that order the minimum spanning forest is unique (Kruskal with a stable sort on the key), and it is what this
+ * returns:
+ *  - d_tree int64 [min(n_edges, n_vertices - 1)]: the input indices k of the forest's edges, ascending;
+ *    *d_n_tree = how many (n_vertices - components).
+ *  - d_labels int32 [n_vertices] (nullable): components numbered in the order of their smallest vertex
+ *    (scipy.sparse.csgraph.connected_components; ppk_network_sweep_dev's labels_at).
+ * Deterministic: the same input gives the same bits on every call; a permuted input gives the same (min, max, w) set.
+ * PPK_ERR_ARG, ppk_last_error() naming one offending edge: an id outside [0, n_vertices), a self-loop, a NaN or
+ * infinite weight.  Also PPK_ERR_ARG: n_vertices or n_edges >= 2^31.  No edges: *d_n_tree = 0 and every vertex its own
+ * component.  Synchronises the stream once (the validation's read-back); none between the Boruvka rounds.
+ * (Replaces gt.min_spanning_tree in generate_minimum_spanning_tree, PopPUNK/network.py:1747-1750, or cugraph's
+ * minimum_spanning_tree, network.py:2146 and PopPUNK/sparse_mst.py:111.) */
+int ppk_mst_dev(const long long *d_i, const long long *d_j, size_t stride, const float *d_w, size_t n_edges,
+                size_t n_vertices, long long *d_tree, unsigned long long *d_n_tree, int32_t *d_labels, void *stream);
+/* Host arrays: i, j int64 [n_edges], w float32 [n_edges] -> tree int64 [min(n_edges, n_vertices - 1)], *n_tree, labels
+ * int32 [n_vertices] (nullable), on device_id; blocking. */
+int ppk_mst(const long long *i, const long long *j, const float *w, size_t n_edges, size_t n_vertices, int device_id,
+            long long *tree, unsigned long long *n_tree, int32_t *labels);
+/* process_weights (PopPUNK/network.py:646-674) of a model edge list: d_w[k] = column 0 (weights_type 0, core), column 1
+ * (1, accessory) or the float32 sqrtf(x0*x0 + x1*x1), un-fused (2, euclidean: np.linalg.norm(x, axis=1)) of the row of
+ * d_dist float32 [n_rows][2] that edge k = (i, j) came from.  With a = min(i, j) - int_offset, b = max(i, j) - int_offset:
+ * n_ref == 0 (self): the condensed row of (a, b); otherwise row = (b - n_ref) * n_ref + a, the inverse of
+ * generate_tuples' non-self mapping.  PPK_ERR_ARG naming the edge: an edge with no row in the matrix; also a row count
+ * that is not n(n-1)/2 (self) or a multiple of n_ref.  Synchronises the stream once (the check's read-back).
+ * (Replaces process_weights(distMat[assignments == within_label], weights_type) of generate_network_from_distances,
+ * network.py:2108-2117.) */
+int ppk_edge_weights_dev(const float *d_dist, size_t n_rows, const long long *d_i, const long long *d_j, size_t stride,
+                         size_t n_edges, size_t n_ref, long long int_offset, int weights_type, float *d_w, void *stream);
+
+/* ------------------------------------------------------------------------
  * Host-buffer convenience wrappers (what a pybind11/ctypes drop-in binds):
  * upload, run on `devices[0..n_dev)` (the pair space is band-split across
  * them), copy back.  Blocking.

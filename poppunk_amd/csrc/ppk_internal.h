@@ -224,7 +224,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_NET = 11,                          // the network sweep's counters, buckets, sorted adjacency and temp storage
        SLOT_NET_BT = 12,                       // its betweenness stage: relabelling, the local adjacency, the plan
        SLOT_NET_WORK = 13,                     // ... and one graph's partial sums and global-state slab (sized after its plan)
-       SLOT_COUNT = 14 };
+       SLOT_MST = 14,                          // the minimum spanning forest's ranks, labels and temp storage
+       SLOT_COUNT = 15 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

@@ -1,0 +1,515 @@
+// Minimum spanning forests and model edge weights on the device.
+//
+//  - ppk_mst_dev : the minimum spanning forest of a weighted multigraph, for generate_minimum_spanning_tree
+//    (PopPUNK/network.py:1721-1831: graph-tool's min_spanning_tree, or cugraph's minimum_spanning_tree).  Edges are
+//    totally ordered by (w, min(i, j), max(i, j), input index), so the forest is unique: Kruskal with a stable sort on
+//    that key.  Stages (ppk_prof_stages names):
+//      validate    one pass checks every id, self-loop and weight; the call's ONE synchronisation reads the first bad
+//                  edge
+//      rank        two stable rocPRIM radix sorts (min << b | max, then the order-preserving 32-bit key of w): an
+//                  edge's position is its rank in the total order; both ends are gathered in rank order
+//      boruvka     ceil(log2 n) rounds, each a fixed sequence of launches and no host round trip: every edge between
+//                  two roots atomicMin's its rank into both roots' best slot (ranks are unique, so the minimum does
+//                  not depend on arrival order); every root hooks along its best edge (a mutual pair: the larger root
+//                  hooks under the smaller) and marks that rank; read-only pointer-jumping passes compress the hook
+//                  forest, src -> dst, 16 hops a pass.  A word per round (and per pass) written by the launch before
+//                  lets every later launch of a finished forest return at once
+//      labels      optional: components numbered by their smallest vertex (scipy's connected_components)
+//      compact     the marked ranks back to input indices, in ascending input order (rocPRIM select)
+//    Kernel boundaries are the only hand-offs between workgroups; the only atomics are integer minima of unique keys.
+//  - ppk_edge_weights_dev : process_weights (PopPUNK/network.py:646-674) of a model edge list: core, accessory or the
+//    float32 Euclidean norm of every edge's row of the distance matrix.
+#include <cmath>
+#include <cstring>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+
+#include <string>
+
+#include "ppk_internal.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr unsigned kNone = 0xffffffffu;   // an empty best slot (ranks are < 2^31)
+constexpr int kHops = 16;                 // pointer hops per compression pass
+constexpr int kMaxRounds = 32;
+
+unsigned grid_for(size_t items, size_t per_block, unsigned cap) {
+  size_t g = (items + per_block - 1) / per_block;
+  if (g < 1) g = 1;
+  return (unsigned)(g < cap ? g : cap);
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// order-preserving unsigned key of a finite float, -0.0 read as +0.0
+__device__ __forceinline__ unsigned float_key(float w) {
+  unsigned u = __float_as_uint(w);
+  if (u == 0x80000000u) u = 0;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// ---- validate ----------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) mst_validate_kernel(const long long *ei, const long long *ej, size_t stride,
+                                                                const float *w, size_t m, long long n,
+                                                                unsigned long long *bad) {
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += (size_t)gridDim.x * blockDim.x) {
+    const long long i = ei[k * stride], j = ej[k * stride];
+    const bool ok = i >= 0 && i < n && j >= 0 && j < n && i != j && isfinite(w[k]);
+    if (!ok) atomicMin(bad, (unsigned long long)k);
+  }
+}
+
+// ---- rank --------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) mst_pair_key_kernel(const long long *ei, const long long *ej, size_t stride,
+                                                                size_t m, unsigned bits, unsigned long long *keys,
+                                                                int *vals) {
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += (size_t)gridDim.x * blockDim.x) {
+    const unsigned long long i = (unsigned long long)ei[k * stride], j = (unsigned long long)ej[k * stride];
+    keys[k] = i < j ? (i << bits) | j : (j << bits) | i;
+    vals[k] = (int)k;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) mst_weight_key_kernel(const float *w, const int *idx, size_t m,
+                                                                  unsigned *keys) {
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += (size_t)gridDim.x * blockDim.x)
+    keys[p] = float_key(w[idx[p]]);
+}
+
+__global__ void __launch_bounds__(kThreads) mst_ends_kernel(const long long *ei, const long long *ej, size_t stride,
+                                                            const int *order, size_t m, int *eu, int *ev) {
+  for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < m; r += (size_t)gridDim.x * blockDim.x) {
+    const size_t k = (size_t)order[r];
+    eu[r] = (int)ei[k * stride];
+    ev[r] = (int)ej[k * stride];
+  }
+}
+
+// ---- boruvka -----------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) mst_init_kernel(int *comp, unsigned *best, size_t n) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) {
+    comp[v] = (int)v;
+    best[v] = kNone;
+  }
+}
+
+// round > 0 runs only when the round before hooked something.  Ranks ascend along the grid-stride loop, so a plain
+// (possibly stale) read of the slot skips most atomics that could not lower it.
+__global__ void __launch_bounds__(kThreads) mst_min_kernel(const int *eu, const int *ev, size_t m, const int *comp,
+                                                           unsigned *best, const unsigned *hooked, int round) {
+  if (round > 0 && hooked[round - 1] == 0) return;
+  for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < m; r += (size_t)gridDim.x * blockDim.x) {
+    const int cu = comp[eu[r]], cv = comp[ev[r]];
+    if (cu == cv) continue;
+    const unsigned rr = (unsigned)r;
+    if (best[cu] > rr) atomicMin(&best[cu], rr);
+    if (best[cv] > rr) atomicMin(&best[cv], rr);
+  }
+}
+
+// Every root hooks along its best edge into dst; every other vertex copies its root.  Of a mutual pair (both roots'
+// best edge is the same rank) the larger root hooks under the smaller, so the hook graph is a forest.
+__global__ void __launch_bounds__(kThreads) mst_hook_kernel(const int *eu, const int *ev, size_t n, const int *comp,
+                                                            const unsigned *best, int *dst, unsigned char *chosen,
+                                                            unsigned *hooked, int round) {
+  if (round > 0 && hooked[round - 1] == 0) return;
+  bool any = false;
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) {
+    const int c = comp[v];
+    int to = c;
+    if (c == (int)v) {
+      const unsigned b = best[v];
+      if (b != kNone) {
+        const int a = comp[eu[b]], z = comp[ev[b]];
+        const int other = a == (int)v ? z : a;
+        if (!(best[other] == b && (int)v < other)) {
+          to = other;
+          chosen[b] = 1;
+          any = true;
+        }
+      }
+    }
+    dst[v] = to;
+  }
+  if (any) hooked[round] = 1;
+}
+
+// One read-only compression pass src -> dst: up to kHops pointer hops per vertex.  A pass that changes nothing
+// leaves dst equal to src, so the passes after it may return without touching either.  Pass 0 also empties every
+// best slot for the next round.
+__global__ void __launch_bounds__(kThreads) mst_jump_kernel(const int *src, int *dst, size_t n, unsigned *best,
+                                                            const unsigned *hooked, unsigned *changed, int round,
+                                                            int pass) {
+  if (hooked[round] == 0) return;
+  if (pass > 0 && changed[pass - 1] == 0) return;
+  bool any = false;
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) {
+    if (pass == 0) best[v] = kNone;
+    const int x0 = src[v];
+    int x = x0;
+    for (int h = 0; h < kHops; ++h) {
+      const int y = src[x];
+      if (y == x) break;
+      x = y;
+    }
+    dst[v] = x;
+    any = any || x != x0;
+  }
+  if (any) changed[pass] = 1;
+}
+
+// ---- labels ------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) mst_fill_kernel(int *a, size_t n, int value) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) a[v] = value;
+}
+
+__global__ void __launch_bounds__(kThreads) mst_min_vertex_kernel(const int *comp, size_t n, int *minv) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) {
+    const int c = comp[v];
+    if (minv[c] > (int)v) atomicMin(&minv[c], (int)v);
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) mst_first_kernel(const int *comp, const int *minv, size_t n, int *first) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x)
+    first[v] = minv[comp[v]] == (int)v ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(kThreads) mst_label_kernel(const int *comp, const int *minv, const int *rank, size_t n,
+                                                             int32_t *labels) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x)
+    labels[v] = rank[minv[comp[v]]];
+}
+
+// ---- compact -----------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) mst_unrank_kernel(const unsigned char *chosen, const int *order, size_t m,
+                                                              unsigned char *flag) {
+  for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < m; r += (size_t)gridDim.x * blockDim.x)
+    flag[order[r]] = chosen[r];
+}
+
+// ---- edge weights ------------------------------------------------------------------------------------------------
+// The correctly rounded float32 square root of s >= 0, as numpy's: the device sqrt (measured 1 ulp off) corrected
+// against the midpoints to its neighbours, whose squares (25-bit by 25-bit) are exact in double.
+__device__ __forceinline__ float sqrt_rn(float s) {
+  float r = __fsqrt_rn(s);
+  if (!(s > 0.0f) || isinf(s)) return r;
+  const double ds = (double)s;
+  for (int it = 0; it < 2; ++it) {
+    const float up = nextafterf(r, INFINITY), dn = nextafterf(r, 0.0f);
+    const double hi = ((double)r + (double)up) * 0.5, lo = ((double)r + (double)dn) * 0.5;
+    if (hi * hi < ds) r = up;
+    else if (lo * lo > ds) r = dn;
+    else break;
+  }
+  return r;
+}
+
+__device__ __forceinline__ size_t cond_index(size_t a, size_t b, size_t n) {   // a < b < n
+  return a * n - (a * (a + 1)) / 2 + (b - a - 1);
+}
+
+__global__ void __launch_bounds__(kThreads) mst_weights_kernel(const float2 *dist, long long n_samples, long long n_ref,
+                                                               long long n_qry, long long off, const long long *ei,
+                                                               const long long *ej, size_t stride, size_t m, int type,
+                                                               float *w, unsigned long long *bad) {
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += (size_t)gridDim.x * blockDim.x) {
+    const long long i = ei[k * stride], j = ej[k * stride];
+    // offsets subtracted before the comparisons: no overflow for ids near the int64 limits
+    const long long a = (i < j ? i : j) - off, b = (i < j ? j : i) - off;
+    size_t row = 0;
+    bool ok;
+    if (n_ref == 0) {
+      ok = a >= 0 && b < n_samples && a != b;
+      if (ok) row = cond_index((size_t)a, (size_t)b, (size_t)n_samples);
+    } else {
+      ok = a >= 0 && a < n_ref && b >= n_ref && b - n_ref < n_qry;
+      if (ok) row = (size_t)(b - n_ref) * (size_t)n_ref + (size_t)a;
+    }
+    if (!ok) {
+      atomicMin(bad, (unsigned long long)k);
+      continue;
+    }
+    const float2 d = dist[row];
+    w[k] = type == 0 ? d.x : type == 1 ? d.y : sqrt_rn(__fadd_rn(__fmul_rn(d.x, d.x), __fmul_rn(d.y, d.y)));
+  }
+}
+
+// one pinned word per device for the one read-back of each call
+unsigned long long *pinned_word(int dev) {
+  static unsigned long long *words[64] = {};
+  if (dev < 0 || dev >= 64) return nullptr;
+  if (!words[dev] && hipHostMalloc(reinterpret_cast<void **>(&words[dev]), 256, hipHostMallocDefault) != hipSuccess)
+    words[dev] = nullptr;
+  return words[dev];
+}
+
+int read_edge(const long long *d_i, const long long *d_j, size_t stride, size_t k, long long *i, long long *j) {
+  if (hipMemcpy(i, d_i + k * stride, 8, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(j, d_j + k * stride, 8, hipMemcpyDeviceToHost) != hipSuccess)
+    return ppk_fail(PPK_ERR_HIP, "cannot read back the bad edge");
+  return PPK_OK;
+}
+
+int mst_bad_edge(const long long *d_i, const long long *d_j, size_t stride, const float *d_w, size_t k, size_t n) {
+  long long i = 0, j = 0;
+  float w = 0.0f;
+  int rc = read_edge(d_i, d_j, stride, k, &i, &j);
+  if (rc != PPK_OK) return rc;
+  PPK_HIP(hipMemcpy(&w, d_w + k, 4, hipMemcpyDeviceToHost));
+  std::string why;
+  if (i < 0 || (size_t)i >= n || j < 0 || (size_t)j >= n) why = "vertex id out of range [0, " + std::to_string(n) + ")";
+  else if (i == j) why = "self-loop";
+  else why = std::isnan(w) ? "NaN weight" : "infinite weight";
+  return ppk_fail(PPK_ERR_ARG, "ppk_mst: edge " + std::to_string(k) + " (i=" + std::to_string(i) + ", j=" +
+                                   std::to_string(j) + "): " + why);
+}
+
+int ceil_log2(size_t n) {
+  int r = 0;
+  while (r < 62 && ((size_t)1 << r) < n) ++r;
+  return r;
+}
+
+}  // namespace
+
+extern "C" int ppk_mst_dev(const long long *d_i, const long long *d_j, size_t stride, const float *d_w, size_t n_edges,
+                           size_t n_vertices, long long *d_tree, unsigned long long *d_n_tree, int32_t *d_labels,
+                           void *stream) {
+  if (n_vertices >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_mst: n_vertices must be < 2^31");
+  if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_mst: n_edges must be < 2^31");
+  if (stride != 1 && stride != 2) return ppk_fail(PPK_ERR_ARG, "ppk_mst: stride must be 1 or 2");
+  if (!d_n_tree || (n_edges && (!d_i || !d_j || !d_w || !d_tree)))
+    return ppk_fail(PPK_ERR_ARG, "ppk_mst: NULL array");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int dev = 0;
+  PPK_HIP(hipGetDevice(&dev));
+  PpkCall call(dev, s);
+  const size_t m = n_edges, n = n_vertices;
+  const unsigned bits = (unsigned)(ceil_log2(n) > 0 ? ceil_log2(n) : 1);
+  const int rounds = ceil_log2(n) > 0 ? ceil_log2(n) : 1;
+  // compression passes per round: 16^passes >= n (the hook forest is no deeper than n), odd so that every round ends
+  // with its labels back in comp_a
+  int passes = 1;
+  while (passes < 8 && ((size_t)1 << (4 * passes)) < n) ++passes;
+  if (!(passes & 1)) ++passes;
+
+  size_t sort64 = 0, sort32 = 0, scan_tmp = 0, sel_tmp = 0;
+  if (m) {
+    PPK_HIP(rocprim::radix_sort_pairs(nullptr, sort64, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                      (int *)nullptr, (int *)nullptr, m, 0u, 2 * bits, s));
+    PPK_HIP(rocprim::radix_sort_pairs(nullptr, sort32, (unsigned *)nullptr, (unsigned *)nullptr, (int *)nullptr,
+                                      (int *)nullptr, m, 0u, 32u, s));
+    PPK_HIP(rocprim::select(nullptr, sel_tmp, rocprim::counting_iterator<long long>(0), (unsigned char *)nullptr,
+                            (long long *)nullptr, (unsigned long long *)nullptr, m, s));
+  }
+  if (n && d_labels)
+    PPK_HIP(rocprim::exclusive_scan(nullptr, scan_tmp, (int *)nullptr, (int *)nullptr, 0, n, rocprim::plus<int>(), s));
+  size_t tmp = sort64;
+  if (sort32 > tmp) tmp = sort32;
+  if (scan_tmp > tmp) tmp = scan_tmp;
+  if (sel_tmp > tmp) tmp = sel_tmp;
+
+  // scratch: bad | round words | pass words | keys a, b (the 32-bit keys and then the ends reuse them) | values a, b |
+  // chosen (by rank) | flags (by index) | comp a, b | best | min vertex | first | rank | temp
+  size_t at = 0;
+  const size_t o_bad = at; at += 256;
+  const size_t o_hook = at; at += align256(kMaxRounds * 4);
+  const size_t o_pass = at; at += align256((size_t)kMaxRounds * 16 * 4);
+  const size_t zero_end = at;
+  const size_t o_ka = at; at += align256(m * 8);
+  const size_t o_kb = at; at += align256(m * 8);
+  const size_t o_va = at; at += align256(m * 4);
+  const size_t o_vb = at; at += align256(m * 4);
+  const size_t o_cho = at; at += align256(m);
+  const size_t o_flag = at; at += align256(m);
+  const size_t o_ca = at; at += align256(n * 4);
+  const size_t o_cb = at; at += align256(n * 4);
+  const size_t o_best = at; at += align256(n * 4);
+  const size_t o_minv = at; at += align256(n * 4);
+  const size_t o_first = at; at += align256(n * 4);
+  const size_t o_rank = at; at += align256(n * 4);
+  const size_t o_tmp = at; at += align256(tmp + 16);
+  void *base = nullptr;
+  int rc = ppk_scratch_get(dev, SLOT_MST, at, &base);
+  if (rc != PPK_OK) return rc;
+  char *B = static_cast<char *>(base);
+  unsigned long long *bad = reinterpret_cast<unsigned long long *>(B + o_bad);
+  unsigned *hooked = reinterpret_cast<unsigned *>(B + o_hook), *changed = reinterpret_cast<unsigned *>(B + o_pass);
+  unsigned long long *ka = reinterpret_cast<unsigned long long *>(B + o_ka), *kb = reinterpret_cast<unsigned long long *>(B + o_kb);
+  unsigned *wa = reinterpret_cast<unsigned *>(B + o_ka), *wb = wa + m;
+  int *eu = reinterpret_cast<int *>(B + o_kb), *ev = eu + m;
+  int *va = reinterpret_cast<int *>(B + o_va), *vb = reinterpret_cast<int *>(B + o_vb);
+  unsigned char *chosen = reinterpret_cast<unsigned char *>(B + o_cho), *flag = reinterpret_cast<unsigned char *>(B + o_flag);
+  int *ca = reinterpret_cast<int *>(B + o_ca), *cb = reinterpret_cast<int *>(B + o_cb);
+  unsigned *best = reinterpret_cast<unsigned *>(B + o_best);
+  int *minv = reinterpret_cast<int *>(B + o_minv), *first = reinterpret_cast<int *>(B + o_first);
+  int *rank = reinterpret_cast<int *>(B + o_rank);
+  void *d_tmp = B + o_tmp;
+  unsigned long long *h = pinned_word(dev);
+  if (!h) return ppk_fail(PPK_ERR_HIP, "hipHostMalloc failed");
+  const unsigned cap_grid = 4096;
+
+  // -- validate: the one synchronisation
+  ppk_prof_stage("validate", s);
+  PPK_HIP(hipMemsetAsync(B, 0, zero_end, s));
+  PPK_HIP(hipMemsetAsync(bad, 0xff, 8, s));
+  if (m)
+    hipLaunchKernelGGL(mst_validate_kernel, dim3(grid_for(m, kThreads * 8, 2048)), dim3(kThreads), 0, s, d_i, d_j,
+                       stride, d_w, m, (long long)n, bad);
+  PPK_HIP(hipGetLastError());
+  PPK_HIP(hipMemcpyAsync(h, bad, 8, hipMemcpyDeviceToHost, s));
+  PPK_HIP(hipStreamSynchronize(s));
+  if (h[0] != ~0ull) {
+    ppk_prof_stage(nullptr, s);
+    return mst_bad_edge(d_i, d_j, stride, d_w, (size_t)h[0], n);
+  }
+
+  // -- rank: (min, max, index) by a stable sort on the pair, then a stable sort on w
+  ppk_prof_stage("rank", s);
+  if (m) {
+    const unsigned g = grid_for(m, kThreads, cap_grid * 4);
+    hipLaunchKernelGGL(mst_pair_key_kernel, dim3(g), dim3(kThreads), 0, s, d_i, d_j, stride, m, bits, ka, va);
+    PPK_HIP(hipGetLastError());
+    size_t tb = tmp;
+    PPK_HIP(rocprim::radix_sort_pairs(d_tmp, tb, ka, kb, va, vb, m, 0u, 2 * bits, s));
+    hipLaunchKernelGGL(mst_weight_key_kernel, dim3(g), dim3(kThreads), 0, s, d_w, vb, m, wa);
+    PPK_HIP(hipGetLastError());
+    tb = tmp;
+    PPK_HIP(rocprim::radix_sort_pairs(d_tmp, tb, wa, wb, vb, va, m, 0u, 32u, s));
+    hipLaunchKernelGGL(mst_ends_kernel, dim3(g), dim3(kThreads), 0, s, d_i, d_j, stride, va, m, eu, ev);
+    PPK_HIP(hipGetLastError());
+    PPK_HIP(hipMemsetAsync(chosen, 0, m, s));
+  }
+  const int *order = va;
+
+  // -- boruvka: labels in ca at the start and end of every round
+  ppk_prof_stage("boruvka", s);
+  if (n) {
+    const unsigned gn = grid_for(n, kThreads, cap_grid);
+    hipLaunchKernelGGL(mst_init_kernel, dim3(gn), dim3(kThreads), 0, s, ca, best, n);
+    PPK_HIP(hipGetLastError());
+    if (m) {
+      const unsigned gm = grid_for(m, kThreads * 4, cap_grid);
+      for (int r = 0; r < rounds; ++r) {
+        hipLaunchKernelGGL(mst_min_kernel, dim3(gm), dim3(kThreads), 0, s, eu, ev, m, ca, best, hooked, r);
+        hipLaunchKernelGGL(mst_hook_kernel, dim3(gn), dim3(kThreads), 0, s, eu, ev, n, ca, best, cb, chosen, hooked, r);
+        for (int p = 0; p < passes; ++p)
+          hipLaunchKernelGGL(mst_jump_kernel, dim3(gn), dim3(kThreads), 0, s, (p & 1) ? ca : cb, (p & 1) ? cb : ca,
+                             n, best, hooked, changed + 16 * r, r, p);
+        PPK_HIP(hipGetLastError());
+      }
+    }
+  }
+
+  // -- labels
+  if (d_labels && n) {
+    ppk_prof_stage("labels", s);
+    const unsigned gn = grid_for(n, kThreads, cap_grid);
+    hipLaunchKernelGGL(mst_fill_kernel, dim3(gn), dim3(kThreads), 0, s, minv, n, 0x7fffffff);
+    hipLaunchKernelGGL(mst_min_vertex_kernel, dim3(gn), dim3(kThreads), 0, s, ca, n, minv);
+    hipLaunchKernelGGL(mst_first_kernel, dim3(gn), dim3(kThreads), 0, s, ca, minv, n, first);
+    PPK_HIP(hipGetLastError());
+    size_t tb = tmp;
+    PPK_HIP(rocprim::exclusive_scan(d_tmp, tb, first, rank, 0, n, rocprim::plus<int>(), s));
+    hipLaunchKernelGGL(mst_label_kernel, dim3(gn), dim3(kThreads), 0, s, ca, minv, rank, n, d_labels);
+    PPK_HIP(hipGetLastError());
+  }
+
+  // -- compact: chosen ranks -> input indices, ascending
+  ppk_prof_stage("compact", s);
+  if (m) {
+    hipLaunchKernelGGL(mst_unrank_kernel, dim3(grid_for(m, kThreads, cap_grid * 4)), dim3(kThreads), 0, s, chosen,
+                       order, m, flag);
+    PPK_HIP(hipGetLastError());
+    size_t tb = tmp;
+    PPK_HIP(rocprim::select(d_tmp, tb, rocprim::counting_iterator<long long>(0), flag, d_tree, d_n_tree, m, s));
+  } else {
+    PPK_HIP(hipMemsetAsync(d_n_tree, 0, 8, s));
+  }
+  ppk_prof_stage(nullptr, s);
+  PPK_HIP(hipGetLastError());
+  return PPK_OK;
+}
+
+extern "C" int ppk_mst(const long long *i, const long long *j, const float *w, size_t n_edges, size_t n_vertices,
+                       int device_id, long long *tree, unsigned long long *n_tree, int32_t *labels) {
+  if (!n_tree || (n_edges && (!i || !j || !w || !tree))) return ppk_fail(PPK_ERR_ARG, "ppk_mst: NULL array");
+  if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_mst: n_edges must be < 2^31");
+  if (n_vertices >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_mst: n_vertices must be < 2^31");
+  DeviceGuard guard(device_id);
+  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
+  PpkCall call(device_id, nullptr);
+  const size_t eb = align256(n_edges * 8), wb = align256(n_edges * 4), lb = align256(n_vertices * 4);
+  void *p = nullptr;
+  int rc = ppk_scratch_get(device_id, SLOT_HOST_IN, 3 * eb + wb + lb + 256, &p);
+  if (rc != PPK_OK) return rc;
+  char *B = static_cast<char *>(p);
+  long long *d_i = reinterpret_cast<long long *>(B), *d_j = reinterpret_cast<long long *>(B + eb);
+  long long *d_tree = reinterpret_cast<long long *>(B + 2 * eb);
+  float *d_w = reinterpret_cast<float *>(B + 3 * eb);
+  int32_t *d_labels = reinterpret_cast<int32_t *>(B + 3 * eb + wb);
+  unsigned long long *d_n = reinterpret_cast<unsigned long long *>(B + 3 * eb + wb + lb);
+  if (n_edges) {
+    PPK_HIP(hipMemcpy(d_i, i, n_edges * 8, hipMemcpyHostToDevice));
+    PPK_HIP(hipMemcpy(d_j, j, n_edges * 8, hipMemcpyHostToDevice));
+    PPK_HIP(hipMemcpy(d_w, w, n_edges * 4, hipMemcpyHostToDevice));
+  }
+  rc = ppk_mst_dev(d_i, d_j, 1, d_w, n_edges, n_vertices, d_tree, d_n, labels ? d_labels : nullptr, nullptr);
+  if (rc != PPK_OK) return rc;
+  PPK_HIP(hipMemcpy(n_tree, d_n, 8, hipMemcpyDeviceToHost));
+  if (*n_tree) PPK_HIP(hipMemcpy(tree, d_tree, *n_tree * 8, hipMemcpyDeviceToHost));
+  if (labels && n_vertices) PPK_HIP(hipMemcpy(labels, d_labels, n_vertices * 4, hipMemcpyDeviceToHost));
+  return PPK_OK;
+}
+
+extern "C" int ppk_edge_weights_dev(const float *d_dist, size_t n_rows, const long long *d_i, const long long *d_j,
+                                    size_t stride, size_t n_edges, size_t n_ref, long long int_offset, int weights_type,
+                                    float *d_w, void *stream) {
+  if (weights_type < 0 || weights_type > 2)
+    return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: weights_type must be 0 (core), 1 (accessory) or 2 (euclidean)");
+  if (stride != 1 && stride != 2) return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: stride must be 1 or 2");
+  if (n_edges && (!d_dist || !d_i || !d_j || !d_w)) return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: NULL array");
+  if (n_rows >= ((size_t)1 << 62)) return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: n_rows too large");
+  size_t n_samples = 0, n_qry = 0;
+  if (n_ref == 0) {
+    n_samples = (size_t)((1.0 + std::sqrt(1.0 + 8.0 * (double)n_rows)) / 2.0);
+    while (n_samples > 1 && n_samples * (n_samples - 1) / 2 > n_rows) --n_samples;
+    while ((n_samples + 1) * n_samples / 2 <= n_rows) ++n_samples;
+    if (n_samples * (n_samples - 1) / 2 != n_rows)
+      return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: row count is not n(n-1)/2 for any n (self matrix expected)");
+  } else {
+    if (n_rows % n_ref) return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: row count is not a multiple of n_ref");
+    n_qry = n_rows / n_ref;
+  }
+  if (!n_edges) return PPK_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int dev = 0;
+  PPK_HIP(hipGetDevice(&dev));
+  PpkCall call(dev, s);
+  void *base = nullptr;
+  int rc = ppk_scratch_get(dev, SLOT_MST, 256, &base);
+  if (rc != PPK_OK) return rc;
+  unsigned long long *bad = static_cast<unsigned long long *>(base);
+  unsigned long long *h = pinned_word(dev);
+  if (!h) return ppk_fail(PPK_ERR_HIP, "hipHostMalloc failed");
+  PPK_HIP(hipMemsetAsync(bad, 0xff, 8, s));
+  hipLaunchKernelGGL(mst_weights_kernel, dim3(grid_for(n_edges, kThreads * 4, 4096)), dim3(kThreads), 0, s,
+                     reinterpret_cast<const float2 *>(d_dist), (long long)n_samples, (long long)n_ref, (long long)n_qry,
+                     int_offset, d_i, d_j, stride, n_edges, weights_type, d_w, bad);
+  PPK_HIP(hipGetLastError());
+  PPK_HIP(hipMemcpyAsync(h, bad, 8, hipMemcpyDeviceToHost, s));
+  PPK_HIP(hipStreamSynchronize(s));
+  if (h[0] != ~0ull) {
+    long long i = 0, j = 0;
+    rc = read_edge(d_i, d_j, stride, (size_t)h[0], &i, &j);
+    if (rc != PPK_OK) return rc;
+    return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: edge " + std::to_string(h[0]) + " (i=" + std::to_string(i) +
+                                     ", j=" + std::to_string(j) + ") has no row in the distance matrix");
+  }
+  return PPK_OK;
+}

@@ -535,6 +535,69 @@ def network_summary_graph_dev(edges_t, n, values=False):
     return stats[0], bt[0], scored[0], val
 
 
+def _mst_stream(edges_t):
+    """(i_t, j_t) of an int64 [m, 2] CUDA edge list, or the pair itself."""
+    torch = _torch()
+    if isinstance(edges_t, (tuple, list)):
+        return edges_t[0], edges_t[1]
+    if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
+            and edges_t.is_contiguous()):
+        raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor, or an (i, j) pair of int64 tensors")
+    return edges_t[:, 0], edges_t[:, 1]
+
+
+def mst_dev(edges_t, w_t, n, labels=False):
+    """The minimum spanning forest of a weighted multigraph (ppk_mst_dev).  edges_t: an int64 [m, 2]
+    CUDA tensor or (i_t, j_t) as network_sweep_dev takes them; w_t: float32 [m] CUDA weights.  Edges are totally
+    ordered by (w, min, max, index), so the forest is unique.  Returns (tree_idx int64 [n - components]: the input
+    indices of the forest's edges, ascending; the number of components; labels int32 [n] numbered as scipy's
+    connected_components numbers them, or None), CUDA tensors and an int."""
+    torch = _torch()
+    i_t, j_t = _mst_stream(edges_t)
+    m, stride = _edge_stream(i_t, j_t, None)
+    if not (w_t.is_cuda and w_t.dtype == torch.float32 and w_t.dim() == 1 and w_t.shape[0] == m
+            and w_t.is_contiguous()):
+        raise TypeError("weights must be a contiguous float32 CUDA tensor, one per edge")
+    n = int(n)
+    dev = i_t.device
+    with torch.cuda.device(dev):
+        tree = torch.empty(max(min(m, n - 1), 1), dtype=torch.int64, device=dev)
+        n_tree = torch.zeros(1, dtype=torch.int64, device=dev)
+        lab = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if labels else None
+        rc = _lib.lib().ppk_mst_dev(C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride,
+                                    C.c_void_p(w_t.data_ptr()), m, n, C.c_void_p(tree.data_ptr()),
+                                    C.c_void_p(n_tree.data_ptr()), C.c_void_p(lab.data_ptr()) if labels else None,
+                                    _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_mst_dev")
+        k = int(n_tree.item())
+    return tree[:k], n - k, (lab[:n] if labels else None)
+
+
+WEIGHTS_TYPES = {"core": 0, "accessory": 1, "euclidean": 2}
+
+
+def edge_weights_dev(dist_t, edges_t, weights_type="core", n_ref=0, int_offset=0):
+    """process_weights (PopPUNK/network.py:646-674) of a model edge list on the device (ppk_edge_weights_dev):
+    dist_t the resident float32 [n_rows, 2] matrix, edges_t the int64 [m, 2] list generate_tuples_dev /
+    edge_threshold_dev / bgmm_edges_dev made from it (or an (i, j) pair).  n_ref 0: a self (condensed) matrix.
+    Returns float32 [m]: core, accessory or the Euclidean norm of every edge's row, bit for bit numpy's."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    if weights_type not in WEIGHTS_TYPES:
+        raise ValueError("weights_type must be one of %s" % sorted(WEIGHTS_TYPES))
+    i_t, j_t = _mst_stream(edges_t)
+    m, stride = _edge_stream(i_t, j_t, None)
+    dev = dist_t.device
+    with torch.cuda.device(dev):
+        w = torch.empty(max(m, 1), dtype=torch.float32, device=dev)
+        rc = _lib.lib().ppk_edge_weights_dev(C.c_void_p(dist_t.data_ptr()), dist_t.shape[0],
+                                             C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride, m,
+                                             int(n_ref), int(int_offset), WEIGHTS_TYPES[weights_type],
+                                             C.c_void_p(w.data_ptr()), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_edge_weights_dev")
+    return w[:m]
+
+
 def _samples_of(n_rows):
     n = int((1 + (1 + 8 * n_rows) ** 0.5) // 2)
     while n * (n - 1) // 2 > n_rows:
