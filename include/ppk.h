@@ -471,6 +471,31 @@ int ppk_edge_weights_dev(const float *d_dist, size_t n_rows, const long long *d_
                          size_t n_edges, size_t n_ref, long long int_offset, int weights_type, float *d_w, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Neighbour-joining trees.  Exact neighbour joining of n samples' core distances, with the join and
+ * tie rule of Biopython's DistanceTreeConstructor.nj.  Only the strictly lower triangle D[a][b], a > b, is read, the
+ * diagonal taken as 0: src_kind PPK_NJ_SQUARE, d_src float32 [n][n] row-major (stride, col ignored); PPK_NJ_LONG, the
+ * condensed upper triangle read at d_src[e * stride + col] as ppk_long_to_square_dev reads it.  Working values are
+ * float64, un-fused.  r active nodes sit in slots in sample order; while r > 2, with nd[x] = S[x] / (r - 2):
+ *  - join the active pair a > b of least Q = (D[a,b] - nd[a]) - nd[b]; of equal Q (-0.0 == +0.0) the least a, then b;
+ *  - len_a = ((D[a,b] + nd[a]) - nd[b]) / 2, len_b = D[a,b] - len_a;
+ *  - slot b becomes the new node, D'[b,k] = ((D[a,k] + D[b,k]) - D[a,b]) / 2; slot a is removed;
+ *  - row sums (this library's rule, not Biopython's recomputation): S'[k] = ((S[k] - D[a,k]) - D[b,k]) + D'[b,k],
+ *    S'[b] = ((S[a] + S[b]) - r * D[a,b]) / 2; initially S[k] = sum of D[k][j], j = 0 .. n-1 ascending, from +0.0.
+ * Output, n >= 2: d_join int64 [n-1][2], d_len float64 [n-1][2].  Row t < n-2: join t's node ids (a, b) -- sample ids
+ * 0 .. n-1, or n + t' for the node join t' made -- and (len_a, len_b).  Row n-2: the final edge, the ids of the two
+ * nodes left (slot 1, slot 0) and its length D[1,0] in both length columns.  n = 1 writes nothing.
+ * Deterministic: the same input gives the same bits on every call.  PPK_ERR_ARG, ppk_last_error() naming the entry: a
+ * NaN or infinite lower-triangle entry; also n = 0 or n >= 2^31.  Synchronises the stream once (the check's read-back);
+ * none between joins.  PPK_ERR_INTERRUPTED when the interrupt check asks (polled every 256 joins).
+ * (Replaces DistanceTreeConstructor().nj(pdm) in generate_nj_tree, PopPUNK/trees.py:186-189, and its rapidnj branch.) */
+#define PPK_NJ_SQUARE 0
+#define PPK_NJ_LONG 1
+int ppk_nj_dev(const float *d_src, int src_kind, size_t stride, size_t col, size_t n, long long *d_join, double *d_len,
+               void *stream);
+/* Host arrays: square float32 [n][n] -> join int64 [n-1][2], len float64 [n-1][2], on device_id; blocking. */
+int ppk_nj(const float *square, size_t n, int device_id, long long *join, double *len);
+
+/* ------------------------------------------------------------------------
  * Host-buffer convenience wrappers (what a pybind11/ctypes drop-in binds):
  * upload, run on `devices[0..n_dev)` (the pair space is band-split across
  * them), copy back.  Blocking.

@@ -168,6 +168,7 @@ static bool interrupted() {
   int (*f)(void) = g_interrupt_check.load();
   return f && f() != 0;
 }
+bool ppk_interrupted() { return interrupted(); }
 static void progress_line(double frac, bool last) {
   char buf[64];
   const int n = snprintf(buf, sizeof(buf), "\rProgress (GPU): %.1f%%%s", 100.0 * frac, last ? "\n" : "");

@@ -97,6 +97,7 @@ int ppk_check_arch(int device_id);       // gfx950 / wave64 or an error, cached 
 int ppk_check_pair(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, size_t q_begin, size_t q_end);
 void ppk_upload_rings_release();
 void ppk_assign_bufs_release_all();
+bool ppk_interrupted();                  // the ppk_set_interrupt_check check asks to stop (ppk_host.hip)
 
 #define PPK_HIP(call)                                                              \
   do {                                                                             \
@@ -225,7 +226,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_NET_BT = 12,                       // its betweenness stage: relabelling, the local adjacency, the plan
        SLOT_NET_WORK = 13,                     // ... and one graph's partial sums and global-state slab (sized after its plan)
        SLOT_MST = 14,                          // the minimum spanning forest's ranks, labels and temp storage
-       SLOT_COUNT = 15 };
+       SLOT_NJ = 15,                           // neighbour joining's float64 triangles, row sums and best slots
+       SLOT_COUNT = 16 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

@@ -598,6 +598,54 @@ def edge_weights_dev(dist_t, edges_t, weights_type="core", n_ref=0, int_offset=0
     return w[:m]
 
 
+NJ_SQUARE, NJ_LONG = 0, 1
+
+
+def nj_dev(src, n=None, col=0):
+    """Neighbour joining of a core-distance matrix on the device (ppk_nj_dev), read in place: a
+    float32 [n, n] CUDA square, or the resident long form, [n_pairs] or column col of [n_pairs, k].  Only the strictly
+    lower triangle is read.  Returns (join int64 [n-1, 2], len float64 [n-1, 2]) CUDA tensors: row t < n-2 is join
+    t's node ids (a, b) -- samples 0 .. n-1, node n + t' made by join t' -- and (len_a, len_b); row n-2 is the final
+    edge (the two nodes left, its length twice).  n = 1 gives empty tensors."""
+    torch = _torch()
+    if not (src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and src.dim() in (1, 2)):
+        raise TypeError("the matrix must be a contiguous float32 CUDA tensor: [n, n] square or [n_pairs(, k)] long")
+    if src.dim() == 2 and src.shape[0] == src.shape[1]:
+        kind, stride, col, nn = NJ_SQUARE, 1, 0, int(src.shape[0])
+    else:
+        kind, stride, col, nn = NJ_LONG, (1 if src.dim() == 1 else int(src.shape[1])), int(col), \
+            _samples_of(int(src.shape[0]))
+        if nn * (nn - 1) // 2 != int(src.shape[0]):
+            raise ValueError("a long-form matrix must have n(n-1)/2 rows")
+        if not 0 <= col < stride:
+            raise ValueError("col must index a column of the long form")
+    if n is not None and int(n) != nn:
+        raise ValueError("n = %d does not match the matrix (%d samples)" % (int(n), nn))
+    dev = src.device
+    with torch.cuda.device(dev):
+        join = torch.empty((max(nn - 1, 0), 2), dtype=torch.int64, device=dev)
+        ln = torch.empty((max(nn - 1, 0), 2), dtype=torch.float64, device=dev)
+        rc = _lib.lib().ppk_nj_dev(C.c_void_p(src.data_ptr()), kind, stride, col, nn,
+                                   C.c_void_p(join.data_ptr()), C.c_void_p(ln.data_ptr()), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_nj_dev")
+    return join, ln
+
+
+def nj(square, device_id=0):
+    """ppk_nj: neighbour joining of a host float32 [n, n] matrix (lower triangle read).  Returns numpy
+    (join int64 [n-1, 2], len float64 [n-1, 2]) as nj_dev."""
+    sq = np.ascontiguousarray(square, dtype=np.float32)
+    if sq.ndim != 2 or sq.shape[0] != sq.shape[1]:
+        raise ValueError("the matrix must be square")
+    nn = int(sq.shape[0])
+    join = np.empty((max(nn - 1, 0), 2), dtype=np.int64)
+    ln = np.empty((max(nn - 1, 0), 2), dtype=np.float64)
+    _lib.check(_lib.lib().ppk_nj(sq.ctypes.data_as(C.POINTER(C.c_float)), nn, int(device_id),
+                                 join.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                 ln.ctypes.data_as(C.POINTER(C.c_double))), "ppk_nj")
+    return join, ln
+
+
 def _samples_of(n_rows):
     n = int((1 + (1 + 8 * n_rows) ** 0.5) // 2)
     while n * (n - 1) // 2 > n_rows:
