@@ -477,6 +477,10 @@ struct DevState {
   // block they sit in -- a call with the same k list, random table and options skips the rebuild
   uint64_t lut_key = 0;
   const void *lut_ptr = nullptr;
+  // the pinned block of ppk_read_back (grow-only, never freed) and the kernels' dynamic-LDS opt-ins (ppk_lds_opt_in)
+  unsigned long long *pinned = nullptr;
+  size_t pinned_bytes = 0;
+  std::map<const void *, bool> lds_opt_in;
 };
 DevState g_dev[64];
 
@@ -561,6 +565,51 @@ int stage_tables(const ppk_db *ref, const int32_t *kmers, const float *random_tb
 }  // namespace
 
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out) { return scratch_get(dev, slot, bytes, out); }
+
+int ppk_read_back(int dev, hipStream_t s, std::initializer_list<PpkCopy> copies, const unsigned long long **words) {
+  if (dev < 0 || dev >= 64) return ppk_fail(PPK_ERR_ARG, "device id " + std::to_string(dev) + " out of range [0, 64)");
+  if (tl_call.dev != dev) return ppk_fail(PPK_ERR_STATE, "internal: read-back requested outside a PpkCall scope");
+  size_t bytes = 0;
+  for (const PpkCopy &c : copies) bytes += (c.bytes + 7) & ~(size_t)7;
+  DevState &ds = g_dev[dev];
+  if (ds.pinned_bytes < align256(bytes)) {
+    if (ds.pinned) (void)hipHostFree(ds.pinned);
+    const size_t want = align256(bytes) + align256(bytes) / 4 + 4096;   // as the scratch slots grow
+    hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&ds.pinned), want, hipHostMallocDefault);
+    ds.pinned_bytes = e == hipSuccess ? want : 0;
+    if (e != hipSuccess) {
+      ds.pinned = nullptr;
+      return ppk_fail(PPK_ERR_HIP, std::string("hipHostMalloc(read-back): ") + hipGetErrorString(e));
+    }
+  }
+  char *at = reinterpret_cast<char *>(ds.pinned);
+  for (const PpkCopy &c : copies) {
+    PPK_HIP(hipMemcpyAsync(at, c.src, c.bytes, hipMemcpyDeviceToHost, s));
+    at += (c.bytes + 7) & ~(size_t)7;
+  }
+  PPK_HIP(hipStreamSynchronize(s));
+  *words = ds.pinned;
+  return PPK_OK;
+}
+
+bool ppk_read_edge(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off, size_t k,
+                   long long *i, long long *j, long long *o) {
+  if (o) *o = 0;
+  return hipMemcpy(i, d_i + k * stride, 8, hipMemcpyDeviceToHost) == hipSuccess &&
+         hipMemcpy(j, d_j + k * stride, 8, hipMemcpyDeviceToHost) == hipSuccess &&
+         (!d_off || hipMemcpy(o, d_off + k, 8, hipMemcpyDeviceToHost) == hipSuccess);
+}
+
+bool ppk_lds_opt_in(const void *kernel, int dev, int bytes) {
+  if (dev < 0 || dev >= 64) return false;
+  std::lock_guard<std::recursive_mutex> lk(g_dev[dev].mu);
+  auto it = g_dev[dev].lds_opt_in.find(kernel);
+  if (it != g_dev[dev].lds_opt_in.end()) return it->second;
+  const bool ok = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+  (void)hipGetLastError();
+  g_dev[dev].lds_opt_in[kernel] = ok;
+  return ok;
+}
 
 // lut_kernel has been enqueued for the tables stage_tables announced: they may be re-used
 void ppk_lut_commit(int dev, const void *d_lut) {

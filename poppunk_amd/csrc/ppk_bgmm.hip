@@ -21,11 +21,6 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kBlock = 256;
 
-unsigned grid_for(size_t items, int block, unsigned cap) {
-  const size_t g = (items + (size_t)block - 1) / (size_t)block;
-  return (unsigned)(g < cap ? (g ? g : 1) : cap);
-}
-
 // logsumexp over the components (scipy.special.logsumexp as bgmm.py:124 calls it: max + log sum exp(lpr - max)),
 // then resp_c = exp(lpr_c - logprob) (models.py:179); lpr is re-evaluated per pass instead of being held in an
 // array the compiler would have to index at run time

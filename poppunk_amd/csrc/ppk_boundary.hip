@@ -433,13 +433,6 @@ seg_totals_kernel(const unsigned long long *__restrict__ block_sums, size_t seg_
   }
 }
 
-inline unsigned grid_for(size_t items, size_t per_block, unsigned cap_blocks) {
-  size_t b = (items + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > cap_blocks) b = cap_blocks;
-  return (unsigned)b;
-}
-
 // Every pair of the dense network (src/boundary.cpp:125-150), no input: a thread takes kAllPerThread
 // consecutive entries, so the self form pays its sqrt once and walks the condensed rows from there.
 constexpr int kAllPerThread = 8;

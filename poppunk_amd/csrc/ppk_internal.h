@@ -7,6 +7,7 @@
 #include <atomic>
 #include <functional>
 #include <cstdlib>
+#include <initializer_list>
 #include <memory>
 #include <thread>
 #include <vector>
@@ -245,6 +246,66 @@ class PpkCall {
   hipStream_t prev_s_;
   unsigned prev_touched_;
 };
+
+// ---- host-side frame of the graph modules (ppk_network.hip, ppk_mst.hip, ppk_nj.hip) ------------------------------
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// blocks of `per_block` items each: at least 1, at most `cap`
+inline unsigned grid_for(size_t items, size_t per_block, unsigned cap) {
+  size_t g = (items + per_block - 1) / per_block;
+  if (g < 1) g = 1;
+  return (unsigned)(g < cap ? g : cap);
+}
+
+// A scratch layout, written once as a function of a Carve and run twice: on a null base to measure (`at` is the
+// total), then on the block to bind.  Each take(p, count) points p at the next buffer, `count` elements rounded up to
+// 256 bytes; `at` is the offset of the one after it.
+struct Carve {
+  char *base = nullptr;
+  size_t at = 0;
+  template <typename T>
+  Carve &take(T *&p, size_t count) {
+    p = base ? reinterpret_cast<T *>(base + at) : nullptr;
+    at += align256(count * sizeof(T));
+    return *this;
+  }
+};
+template <typename Layout>
+int ppk_scratch_carve(int dev, int slot, Layout &&layout) {
+  Carve c;
+  layout(c);
+  void *base = nullptr;
+  const int rc = ppk_scratch_get(dev, slot, c.at, &base);
+  if (rc != PPK_OK) return rc;
+  c = Carve{static_cast<char *>(base)};
+  layout(c);
+  return PPK_OK;
+}
+
+// The call's one synchronisation: the copies, in order, into the device's grow-only pinned read-back block (back to
+// back at 8-byte offsets), then one hipStreamSynchronize of `s`.  *words: the block, valid until the next read-back
+// on the device.  Inside a PpkCall scope of `dev` only.
+struct PpkCopy {
+  const void *src;
+  size_t bytes;
+};
+int ppk_read_back(int dev, hipStream_t s, std::initializer_list<PpkCopy> copies, const unsigned long long **words);
+// ends and offset index (o: 0 without d_off, may be null then) of edge k of a device edge stream, for an error message
+bool ppk_read_edge(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off, size_t k,
+                   long long *i, long long *j, long long *o);
+// hipFuncSetAttribute(kernel, MaxDynamicSharedMemorySize, bytes) once per (kernel, device): whether it took
+bool ppk_lds_opt_in(const void *kernel, int dev, int bytes);
+
+// The host-array twin of a device entry point: `device` selected and its PpkCall scope held (null stream) around
+// SLOT_HOST_IN carved by `layout` and `body` (the uploads, the device call and the downloads).
+template <typename Layout, typename Body>
+int ppk_host_frame(int device, Layout &&layout, Body &&body) {
+  DeviceGuard guard(device);
+  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device));
+  PpkCall call(device, nullptr);
+  const int rc = ppk_scratch_carve(device, SLOT_HOST_IN, layout);
+  return rc != PPK_OK ? rc : body();
+}
+
 void ppk_query_cache_clear();
 // host entry points with a data-dependent result size (ppk_host.hip): one pass; a result that did not
 // fit the caller's buffer stays parked on the device for the calling thread's ppk_parked_fetch

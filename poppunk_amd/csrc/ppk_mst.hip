@@ -37,14 +37,6 @@ constexpr unsigned kNone = 0xffffffffu;   // an empty best slot (ranks are < 2^3
 constexpr int kHops = 16;                 // pointer hops per compression pass
 constexpr int kMaxRounds = 32;
 
-unsigned grid_for(size_t items, size_t per_block, unsigned cap) {
-  size_t g = (items + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  return (unsigned)(g < cap ? g : cap);
-}
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // order-preserving unsigned key of a finite float, -0.0 read as +0.0
 __device__ __forceinline__ unsigned float_key(float w) {
   unsigned u = __float_as_uint(w);
@@ -239,27 +231,11 @@ __global__ void __launch_bounds__(kThreads) mst_weights_kernel(const float2 *dis
   }
 }
 
-// one pinned word per device for the one read-back of each call
-unsigned long long *pinned_word(int dev) {
-  static unsigned long long *words[64] = {};
-  if (dev < 0 || dev >= 64) return nullptr;
-  if (!words[dev] && hipHostMalloc(reinterpret_cast<void **>(&words[dev]), 256, hipHostMallocDefault) != hipSuccess)
-    words[dev] = nullptr;
-  return words[dev];
-}
-
-int read_edge(const long long *d_i, const long long *d_j, size_t stride, size_t k, long long *i, long long *j) {
-  if (hipMemcpy(i, d_i + k * stride, 8, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(j, d_j + k * stride, 8, hipMemcpyDeviceToHost) != hipSuccess)
-    return ppk_fail(PPK_ERR_HIP, "cannot read back the bad edge");
-  return PPK_OK;
-}
-
 int mst_bad_edge(const long long *d_i, const long long *d_j, size_t stride, const float *d_w, size_t k, size_t n) {
   long long i = 0, j = 0;
   float w = 0.0f;
-  int rc = read_edge(d_i, d_j, stride, k, &i, &j);
-  if (rc != PPK_OK) return rc;
+  if (!ppk_read_edge(d_i, d_j, stride, nullptr, k, &i, &j, nullptr))
+    return ppk_fail(PPK_ERR_HIP, "cannot read back the bad edge");
   PPK_HIP(hipMemcpy(&w, d_w + k, 4, hipMemcpyDeviceToHost));
   std::string why;
   if (i < 0 || (size_t)i >= n || j < 0 || (size_t)j >= n) why = "vertex id out of range [0, " + std::to_string(n) + ")";
@@ -314,56 +290,35 @@ extern "C" int ppk_mst_dev(const long long *d_i, const long long *d_j, size_t st
   if (scan_tmp > tmp) tmp = scan_tmp;
   if (sel_tmp > tmp) tmp = sel_tmp;
 
-  // scratch: bad | round words | pass words | keys a, b (the 32-bit keys and then the ends reuse them) | values a, b |
-  // chosen (by rank) | flags (by index) | comp a, b | best | min vertex | first | rank | temp
-  size_t at = 0;
-  const size_t o_bad = at; at += 256;
-  const size_t o_hook = at; at += align256(kMaxRounds * 4);
-  const size_t o_pass = at; at += align256((size_t)kMaxRounds * 16 * 4);
-  const size_t zero_end = at;
-  const size_t o_ka = at; at += align256(m * 8);
-  const size_t o_kb = at; at += align256(m * 8);
-  const size_t o_va = at; at += align256(m * 4);
-  const size_t o_vb = at; at += align256(m * 4);
-  const size_t o_cho = at; at += align256(m);
-  const size_t o_flag = at; at += align256(m);
-  const size_t o_ca = at; at += align256(n * 4);
-  const size_t o_cb = at; at += align256(n * 4);
-  const size_t o_best = at; at += align256(n * 4);
-  const size_t o_minv = at; at += align256(n * 4);
-  const size_t o_first = at; at += align256(n * 4);
-  const size_t o_rank = at; at += align256(n * 4);
-  const size_t o_tmp = at; at += align256(tmp + 16);
-  void *base = nullptr;
-  int rc = ppk_scratch_get(dev, SLOT_MST, at, &base);
+  // scratch: bad | round words | pass words (zeroed up to here) | keys a, b (the 32-bit keys and then the ends reuse
+  // them) | values a, b | chosen (by rank) | flags (by index) | comp a, b | best | min vertex | first | rank | temp
+  unsigned long long *bad, *ka, *kb;
+  unsigned *hooked, *changed, *best;
+  int *va, *vb, *ca, *cb, *minv, *first, *rank;
+  unsigned char *chosen, *flag;
+  char *d_tmp;
+  size_t zero_end = 0;
+  int rc = ppk_scratch_carve(dev, SLOT_MST, [&](Carve &c) {
+    c.take(bad, 1).take(hooked, kMaxRounds).take(changed, (size_t)kMaxRounds * 16);
+    zero_end = c.at;
+    c.take(ka, m).take(kb, m).take(va, m).take(vb, m).take(chosen, m).take(flag, m);
+    c.take(ca, n).take(cb, n).take(best, n).take(minv, n).take(first, n).take(rank, n).take(d_tmp, tmp + 16);
+  });
   if (rc != PPK_OK) return rc;
-  char *B = static_cast<char *>(base);
-  unsigned long long *bad = reinterpret_cast<unsigned long long *>(B + o_bad);
-  unsigned *hooked = reinterpret_cast<unsigned *>(B + o_hook), *changed = reinterpret_cast<unsigned *>(B + o_pass);
-  unsigned long long *ka = reinterpret_cast<unsigned long long *>(B + o_ka), *kb = reinterpret_cast<unsigned long long *>(B + o_kb);
-  unsigned *wa = reinterpret_cast<unsigned *>(B + o_ka), *wb = wa + m;
-  int *eu = reinterpret_cast<int *>(B + o_kb), *ev = eu + m;
-  int *va = reinterpret_cast<int *>(B + o_va), *vb = reinterpret_cast<int *>(B + o_vb);
-  unsigned char *chosen = reinterpret_cast<unsigned char *>(B + o_cho), *flag = reinterpret_cast<unsigned char *>(B + o_flag);
-  int *ca = reinterpret_cast<int *>(B + o_ca), *cb = reinterpret_cast<int *>(B + o_cb);
-  unsigned *best = reinterpret_cast<unsigned *>(B + o_best);
-  int *minv = reinterpret_cast<int *>(B + o_minv), *first = reinterpret_cast<int *>(B + o_first);
-  int *rank = reinterpret_cast<int *>(B + o_rank);
-  void *d_tmp = B + o_tmp;
-  unsigned long long *h = pinned_word(dev);
-  if (!h) return ppk_fail(PPK_ERR_HIP, "hipHostMalloc failed");
+  unsigned *wa = reinterpret_cast<unsigned *>(ka), *wb = wa + m;
+  int *eu = reinterpret_cast<int *>(kb), *ev = eu + m;
   const unsigned cap_grid = 4096;
 
   // -- validate: the one synchronisation
   ppk_prof_stage("validate", s);
-  PPK_HIP(hipMemsetAsync(B, 0, zero_end, s));
+  PPK_HIP(hipMemsetAsync(bad, 0, zero_end, s));
   PPK_HIP(hipMemsetAsync(bad, 0xff, 8, s));
   if (m)
     hipLaunchKernelGGL(mst_validate_kernel, dim3(grid_for(m, kThreads * 8, 2048)), dim3(kThreads), 0, s, d_i, d_j,
                        stride, d_w, m, (long long)n, bad);
   PPK_HIP(hipGetLastError());
-  PPK_HIP(hipMemcpyAsync(h, bad, 8, hipMemcpyDeviceToHost, s));
-  PPK_HIP(hipStreamSynchronize(s));
+  const unsigned long long *h = nullptr;
+  if ((rc = ppk_read_back(dev, s, {{bad, 8}}, &h)) != PPK_OK) return rc;
   if (h[0] != ~0ull) {
     ppk_prof_stage(nullptr, s);
     return mst_bad_edge(d_i, d_j, stride, d_w, (size_t)h[0], n);
@@ -441,30 +396,27 @@ extern "C" int ppk_mst(const long long *i, const long long *j, const float *w, s
   if (!n_tree || (n_edges && (!i || !j || !w || !tree))) return ppk_fail(PPK_ERR_ARG, "ppk_mst: NULL array");
   if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_mst: n_edges must be < 2^31");
   if (n_vertices >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_mst: n_vertices must be < 2^31");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
-  PpkCall call(device_id, nullptr);
-  const size_t eb = align256(n_edges * 8), wb = align256(n_edges * 4), lb = align256(n_vertices * 4);
-  void *p = nullptr;
-  int rc = ppk_scratch_get(device_id, SLOT_HOST_IN, 3 * eb + wb + lb + 256, &p);
-  if (rc != PPK_OK) return rc;
-  char *B = static_cast<char *>(p);
-  long long *d_i = reinterpret_cast<long long *>(B), *d_j = reinterpret_cast<long long *>(B + eb);
-  long long *d_tree = reinterpret_cast<long long *>(B + 2 * eb);
-  float *d_w = reinterpret_cast<float *>(B + 3 * eb);
-  int32_t *d_labels = reinterpret_cast<int32_t *>(B + 3 * eb + wb);
-  unsigned long long *d_n = reinterpret_cast<unsigned long long *>(B + 3 * eb + wb + lb);
-  if (n_edges) {
-    PPK_HIP(hipMemcpy(d_i, i, n_edges * 8, hipMemcpyHostToDevice));
-    PPK_HIP(hipMemcpy(d_j, j, n_edges * 8, hipMemcpyHostToDevice));
-    PPK_HIP(hipMemcpy(d_w, w, n_edges * 4, hipMemcpyHostToDevice));
-  }
-  rc = ppk_mst_dev(d_i, d_j, 1, d_w, n_edges, n_vertices, d_tree, d_n, labels ? d_labels : nullptr, nullptr);
-  if (rc != PPK_OK) return rc;
-  PPK_HIP(hipMemcpy(n_tree, d_n, 8, hipMemcpyDeviceToHost));
-  if (*n_tree) PPK_HIP(hipMemcpy(tree, d_tree, *n_tree * 8, hipMemcpyDeviceToHost));
-  if (labels && n_vertices) PPK_HIP(hipMemcpy(labels, d_labels, n_vertices * 4, hipMemcpyDeviceToHost));
-  return PPK_OK;
+  long long *d_i, *d_j, *d_tree;
+  float *d_w;
+  int32_t *d_labels;
+  unsigned long long *d_n;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_i, n_edges).take(d_j, n_edges).take(d_tree, n_edges).take(d_w, n_edges).take(d_labels, n_vertices);
+    c.take(d_n, 1);
+  }, [&]() -> int {
+    if (n_edges) {
+      PPK_HIP(hipMemcpy(d_i, i, n_edges * 8, hipMemcpyHostToDevice));
+      PPK_HIP(hipMemcpy(d_j, j, n_edges * 8, hipMemcpyHostToDevice));
+      PPK_HIP(hipMemcpy(d_w, w, n_edges * 4, hipMemcpyHostToDevice));
+    }
+    const int rc =
+        ppk_mst_dev(d_i, d_j, 1, d_w, n_edges, n_vertices, d_tree, d_n, labels ? d_labels : nullptr, nullptr);
+    if (rc != PPK_OK) return rc;
+    PPK_HIP(hipMemcpy(n_tree, d_n, 8, hipMemcpyDeviceToHost));
+    if (*n_tree) PPK_HIP(hipMemcpy(tree, d_tree, *n_tree * 8, hipMemcpyDeviceToHost));
+    if (labels && n_vertices) PPK_HIP(hipMemcpy(labels, d_labels, n_vertices * 4, hipMemcpyDeviceToHost));
+    return PPK_OK;
+  });
 }
 
 extern "C" int ppk_edge_weights_dev(const float *d_dist, size_t n_rows, const long long *d_i, const long long *d_j,
@@ -491,23 +443,20 @@ extern "C" int ppk_edge_weights_dev(const float *d_dist, size_t n_rows, const lo
   int dev = 0;
   PPK_HIP(hipGetDevice(&dev));
   PpkCall call(dev, s);
-  void *base = nullptr;
-  int rc = ppk_scratch_get(dev, SLOT_MST, 256, &base);
+  unsigned long long *bad;
+  int rc = ppk_scratch_carve(dev, SLOT_MST, [&](Carve &c) { c.take(bad, 1); });
   if (rc != PPK_OK) return rc;
-  unsigned long long *bad = static_cast<unsigned long long *>(base);
-  unsigned long long *h = pinned_word(dev);
-  if (!h) return ppk_fail(PPK_ERR_HIP, "hipHostMalloc failed");
   PPK_HIP(hipMemsetAsync(bad, 0xff, 8, s));
   hipLaunchKernelGGL(mst_weights_kernel, dim3(grid_for(n_edges, kThreads * 4, 4096)), dim3(kThreads), 0, s,
                      reinterpret_cast<const float2 *>(d_dist), (long long)n_samples, (long long)n_ref, (long long)n_qry,
                      int_offset, d_i, d_j, stride, n_edges, weights_type, d_w, bad);
   PPK_HIP(hipGetLastError());
-  PPK_HIP(hipMemcpyAsync(h, bad, 8, hipMemcpyDeviceToHost, s));
-  PPK_HIP(hipStreamSynchronize(s));
+  const unsigned long long *h = nullptr;
+  if ((rc = ppk_read_back(dev, s, {{bad, 8}}, &h)) != PPK_OK) return rc;
   if (h[0] != ~0ull) {
     long long i = 0, j = 0;
-    rc = read_edge(d_i, d_j, stride, (size_t)h[0], &i, &j);
-    if (rc != PPK_OK) return rc;
+    if (!ppk_read_edge(d_i, d_j, stride, nullptr, (size_t)h[0], &i, &j, nullptr))
+      return ppk_fail(PPK_ERR_HIP, "cannot read back the bad edge");
     return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: edge " + std::to_string(h[0]) + " (i=" + std::to_string(i) +
                                      ", j=" + std::to_string(j) + ") has no row in the distance matrix");
   }

@@ -334,24 +334,6 @@ __global__ void net_stats_kernel(const unsigned *cnt, const unsigned *links, con
   }
 }
 
-unsigned grid_for(size_t items, size_t per_block, unsigned cap) {
-  size_t g = (items + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  return (unsigned)(g < cap ? g : cap);
-}
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// one pinned block per device for the call's one read-back: the first bad edge and the per-offset counts
-unsigned long long *pinned_counts(int dev) {
-  static unsigned long long *blocks[64] = {};
-  if (dev < 0 || dev >= 64) return nullptr;
-  if (!blocks[dev] && hipHostMalloc(reinterpret_cast<void **>(&blocks[dev]), 8 + (kMaxOff + 1) * 4 + 256,
-                                    hipHostMallocDefault) != hipSuccess)
-    blocks[dev] = nullptr;
-  return blocks[dev];
-}
-
 // the LDS table of the triangle stage: the whole id range where it fits, else windows (option "net_window" forces a
 // smaller one: tests of the windowed path)
 unsigned table_entries(size_t n, bool big_lds) {
@@ -363,18 +345,17 @@ unsigned table_entries(size_t n, bool big_lds) {
   return (unsigned)((w + 1) & ~(size_t)1);
 }
 
-int bad_edge_message(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off, size_t k,
-                     size_t n, size_t n_off) {
+// who: the entry point's name, which starts every message
+int bad_edge_message(const std::string &who, const long long *d_i, const long long *d_j, size_t stride,
+                     const long long *d_off, size_t k, size_t n, size_t n_off) {
   long long i = 0, j = 0, o = 0;
-  if (hipMemcpy(&i, d_i + k * stride, 8, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(&j, d_j + k * stride, 8, hipMemcpyDeviceToHost) != hipSuccess ||
-      (d_off && hipMemcpy(&o, d_off + k, 8, hipMemcpyDeviceToHost) != hipSuccess))
-    return ppk_fail(PPK_ERR_HIP, "ppk_network_sweep: cannot read back the bad edge");
+  if (!ppk_read_edge(d_i, d_j, stride, d_off, k, &i, &j, &o))
+    return ppk_fail(PPK_ERR_HIP, who + ": cannot read back the bad edge");
   std::string why;
   if (i < 0 || (size_t)i >= n || j < 0 || (size_t)j >= n) why = "vertex id out of range [0, " + std::to_string(n) + ")";
   else if (i == j) why = "self-loop";
   else why = "offset index out of range [0, " + std::to_string(n_off) + ")";
-  return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: edge " + std::to_string(k) + " (i=" + std::to_string(i) +
+  return ppk_fail(PPK_ERR_ARG, who + ": edge " + std::to_string(k) + " (i=" + std::to_string(i) +
                                    ", j=" + std::to_string(j) + ", offset " + std::to_string(o) + "): " + why);
 }
 
@@ -803,14 +784,6 @@ __global__ void bt_fill_kernel(const unsigned *cnt, int n_off, double *bt, long 
   }
 }
 
-long long *pinned_plan(int dev) {
-  static long long *blocks[64] = {};
-  if (dev < 0 || dev >= 64) return nullptr;
-  if (!blocks[dev] && hipHostMalloc(reinterpret_cast<void **>(&blocks[dev]), H_LEN * 8, hipHostMallocDefault) != hipSuccess)
-    blocks[dev] = nullptr;
-  return blocks[dev];
-}
-
 // what the betweenness stage reads from the counts' stages, and writes
 struct BtJob {
   double *bt;                  // [n_off][2]
@@ -830,59 +803,24 @@ int bt_run(const BtJob &job, hipStream_t s, int dev, size_t n, size_t m, size_t 
   if (n) PPK_HIP(rocprim::radix_sort_keys(nullptr, sort_tmp, (unsigned long long *)nullptr, (unsigned long long *)nullptr, n, 0u, end_bit, s));
   if (e) PPK_HIP(rocprim::radix_sort_keys(nullptr, sort_tmp2, (unsigned long long *)nullptr, (unsigned long long *)nullptr, e, 0u, end_bit, s));
   const size_t tmp = sort_tmp > sort_tmp2 ? sort_tmp : sort_tmp2;
-  size_t at = 0;
-  const size_t o_hdr = at; at += 256;
-  const size_t o_fill = at; at += 256;
-  const size_t o_root = at; at += align256(n * 4);
-  const size_t o_size = at; at += align256(n * 4);
-  const size_t o_crank = at; at += align256(n * 4);
-  const size_t o_csize = at; at += align256((n + 2) * 4);
-  const size_t o_cstart = at; at += align256((n + 2) * 4);
-  const size_t o_spi = at; at += align256((n + 2) * 4);
-  const size_t o_ibase = at; at += align256((n + 2) * 4);
-  const size_t o_pbase = at; at += align256((n + 2) * 8);
-  const size_t o_local = at; at += align256(n * 4);
-  const size_t o_order = at; at += align256(n * 4);
-  const size_t o_ka = at; at += align256(n * 8);
-  const size_t o_kb = at; at += align256(n * 8);
-  const size_t o_rstart = at; at += align256((n + 1) * 4);
-  const size_t o_val = at; at += align256(n * 8);
-  const size_t o_cmax = at; at += align256(n * 8);
-  const size_t o_ea = at; at += align256(e * 8);
-  const size_t o_eb = at; at += align256(e * 8);
-  const size_t o_lnbr = at; at += align256(e * 4);
-  const size_t o_tmp = at; at += align256(tmp + 16);
-  void *base = nullptr;
-  int rc = ppk_scratch_get(dev, SLOT_NET_BT, at, &base);
+  long long *hdr, *pbase;
+  unsigned *fill, *rstart;
+  int *root, *size, *crank, *csize, *cstart, *spi, *ibase, *local, *order, *lnbr;
+  unsigned long long *ka, *kb, *ea, *eb;
+  double *val, *cmax;
+  char *d_tmp;
+  int rc = ppk_scratch_carve(dev, SLOT_NET_BT, [&](Carve &c) {
+    c.take(hdr, H_LEN).take(fill, 1).take(root, n).take(size, n).take(crank, n);
+    c.take(csize, n + 2).take(cstart, n + 2).take(spi, n + 2).take(ibase, n + 2).take(pbase, n + 2);
+    c.take(local, n).take(order, n).take(ka, n).take(kb, n).take(rstart, n + 1).take(val, n).take(cmax, n);
+    c.take(ea, e).take(eb, e).take(lnbr, e).take(d_tmp, tmp + 16);
+  });
   if (rc != PPK_OK) return rc;
-  char *B = static_cast<char *>(base);
-  long long *hdr = reinterpret_cast<long long *>(B + o_hdr);
-  unsigned *fill = reinterpret_cast<unsigned *>(B + o_fill);
-  int *root = reinterpret_cast<int *>(B + o_root), *size = reinterpret_cast<int *>(B + o_size);
-  int *crank = reinterpret_cast<int *>(B + o_crank), *csize = reinterpret_cast<int *>(B + o_csize);
-  int *cstart = reinterpret_cast<int *>(B + o_cstart), *spi = reinterpret_cast<int *>(B + o_spi);
-  int *ibase = reinterpret_cast<int *>(B + o_ibase);
-  long long *pbase = reinterpret_cast<long long *>(B + o_pbase);
-  int *local = reinterpret_cast<int *>(B + o_local), *order = reinterpret_cast<int *>(B + o_order);
-  unsigned long long *ka = reinterpret_cast<unsigned long long *>(B + o_ka), *kb = reinterpret_cast<unsigned long long *>(B + o_kb);
-  unsigned *rstart = reinterpret_cast<unsigned *>(B + o_rstart);
-  double *val = reinterpret_cast<double *>(B + o_val), *cmax = reinterpret_cast<double *>(B + o_cmax);
-  unsigned long long *ea = reinterpret_cast<unsigned long long *>(B + o_ea), *eb = reinterpret_cast<unsigned long long *>(B + o_eb);
-  int *lnbr = reinterpret_cast<int *>(B + o_lnbr);
-  void *d_tmp = B + o_tmp;
-  long long *h = pinned_plan(dev);
-  if (!h) return ppk_fail(PPK_ERR_HIP, "hipHostMalloc failed");
 
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-  static bool big_lds[64] = {}, asked[64] = {};
-  if (!asked[dev & 63]) {
-    asked[dev & 63] = true;
-    big_lds[dev & 63] = hipFuncSetAttribute(reinterpret_cast<const void *>(bt_items_kernel<true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBtLdsBytes) == hipSuccess;
-    (void)hipGetLastError();
-  }
-  long long lds_max = (long long)(((big_lds[dev & 63] ? kBtLdsBytes : 65536 - 64) - 8) / 36);
+  const bool big_lds = ppk_lds_opt_in(reinterpret_cast<const void *>(bt_items_kernel<true>), dev, (int)kBtLdsBytes);
+  long long lds_max = (long long)(((big_lds ? kBtLdsBytes : 65536 - 64) - 8) / 36);
   const long long forced_lds = ppk_config().bt_lds_max.load();
   if (forced_lds > 0 && forced_lds < lds_max) lds_max = forced_lds;
   long long small_max = ppk_config().bt_small_max.load();
@@ -935,8 +873,8 @@ int bt_run(const BtJob &job, hipStream_t s, int dev, size_t n, size_t m, size_t 
     hipLaunchKernelGGL(bt_plan_kernel, dim3(1), dim3(kThreads), 0, s, csize, cstart, rstart, n, (int)small_max,
                        (int)lds_max, spi, ibase, pbase, hdr);
     PPK_HIP(hipGetLastError());
-    PPK_HIP(hipMemcpyAsync(h, hdr, H_LEN * 8, hipMemcpyDeviceToHost, s));
-    PPK_HIP(hipStreamSynchronize(s));
+    const unsigned long long *h = nullptr;
+    if ((rc = ppk_read_back(dev, s, {{hdr, H_LEN * 8}}, &h)) != PPK_OK) return rc;
     const int K = (int)h[H_K], kbig = (int)h[H_KBIG], n_items = (int)h[H_ITEMS], items_glob = (int)h[H_ITEMS_GLOB];
     const size_t n_partial = (size_t)h[H_PARTIAL], nc_glob = (size_t)h[H_NC_GLOB], nc_lds = (size_t)h[H_NC_LDS];
     // -- Brandes
@@ -944,13 +882,13 @@ int bt_run(const BtJob &job, hipStream_t s, int dev, size_t n, size_t m, size_t 
     if (K > 0) {
       const unsigned g_glob = items_glob > 0 ? (unsigned)(items_glob < 2 * cus ? items_glob : 2 * cus) : 0;
       const size_t slab_stride = align256(bt_state_bytes(nc_glob));
-      void *wbase = nullptr;
-      rc = ppk_scratch_get(dev, SLOT_NET_WORK, 256 + align256(n_partial * 8) + g_glob * slab_stride, &wbase);
+      unsigned *next;
+      double *partial;
+      char *slab;
+      rc = ppk_scratch_carve(dev, SLOT_NET_WORK, [&](Carve &c) {
+        c.take(next, 2).take(partial, n_partial).take(slab, g_glob * slab_stride);
+      });
       if (rc != PPK_OK) return rc;
-      char *W = static_cast<char *>(wbase);
-      unsigned *next = reinterpret_cast<unsigned *>(W);
-      double *partial = reinterpret_cast<double *>(W + 256);
-      char *slab = W + 256 + align256(n_partial * 8);
       PPK_HIP(hipMemsetAsync(next, 0, 8, s));
       if (items_glob > 0)
         hipLaunchKernelGGL(bt_items_kernel<false>, dim3(g_glob), dim3(kThreads), 0, s, rstart, lnbr, csize, cstart,
@@ -982,19 +920,26 @@ int bt_run(const BtJob &job, hipStream_t s, int dev, size_t n, size_t m, size_t 
   return PPK_OK;
 }
 
-int net_sweep(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off, size_t n_edges,
-              size_t n_vertices, size_t n_off, long long labels_at, long long *d_stats, int32_t *d_labels, void *stream,
-              const BtJob *bt) {
-  if (n_off == 0 || n_off > (size_t)kMaxOff) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_off must be 1 .. 1023");
-  if (!d_off && n_off != 1 && n_edges)
-    return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: no offset array needs n_off == 1");
-  if (n_vertices >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_vertices must be < 2^31");
-  if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_edges must be < 2^31");
-  if (stride != 1 && stride != 2) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: stride must be 1 or 2");
+// the sizes of a host-array network call, checked (who: the entry point's name)
+int net_check(const std::string &who, size_t n_edges, size_t n_vertices, size_t n_off) {
+  if (n_off == 0 || n_off > (size_t)kMaxOff) return ppk_fail(PPK_ERR_ARG, who + ": n_off must be 1 .. 1023");
+  if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, who + ": n_edges must be < 2^31");
+  if (n_vertices >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, who + ": n_vertices must be < 2^31");
+  return PPK_OK;
+}
+
+int net_sweep(const std::string &who, const long long *d_i, const long long *d_j, size_t stride, const long long *d_off,
+              size_t n_edges, size_t n_vertices, size_t n_off, long long labels_at, long long *d_stats,
+              int32_t *d_labels, void *stream, const BtJob *bt) {
+  if (n_off == 0 || n_off > (size_t)kMaxOff) return ppk_fail(PPK_ERR_ARG, who + ": n_off must be 1 .. 1023");
+  if (!d_off && n_off != 1 && n_edges) return ppk_fail(PPK_ERR_ARG, who + ": no offset array needs n_off == 1");
+  if (n_vertices >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, who + ": n_vertices must be < 2^31");
+  if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, who + ": n_edges must be < 2^31");
+  if (stride != 1 && stride != 2) return ppk_fail(PPK_ERR_ARG, who + ": stride must be 1 or 2");
   if (labels_at < -1 || labels_at >= (long long)n_off)
-    return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: labels_at must be -1 or an offset index");
+    return ppk_fail(PPK_ERR_ARG, who + ": labels_at must be -1 or an offset index");
   if (!d_stats || (labels_at >= 0 && !d_labels && n_vertices) || (n_edges && (!d_i || !d_j)))
-    return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: NULL array");
+    return ppk_fail(PPK_ERR_ARG, who + ": NULL array");
   hipStream_t s = static_cast<hipStream_t>(stream);
   int dev = 0;
   PPK_HIP(hipGetDevice(&dev));
@@ -1012,65 +957,39 @@ int net_sweep(const long long *d_i, const long long *d_j, size_t stride, const l
                                   rocprim::plus<unsigned>(), s));
   if (n) PPK_HIP(rocprim::exclusive_scan(nullptr, scan_tmp2, (int *)nullptr, (int *)nullptr, 0, n, rocprim::plus<int>(), s));
   const size_t tmp = sort_tmp > scan_tmp ? (sort_tmp > scan_tmp2 ? sort_tmp : scan_tmp2) : (scan_tmp > scan_tmp2 ? scan_tmp : scan_tmp2);
-  const size_t cnt_b = align256(1024 * 4), big_b = align256(1024 * 8);
-  size_t at = 0;
-  const size_t o_bad = at; at += 256;
-  const size_t o_cnt = at; at += cnt_b;
-  const size_t o_cur = at; at += cnt_b;
-  const size_t o_links = at; at += cnt_b;
-  const size_t o_tri = at; at += big_b;
-  const size_t o_wed = at; at += big_b;
-  const size_t zero_end = at;
-  const size_t o_parent = at; at += align256(n * 4);
-  const size_t o_root = at; at += align256(n * 4);
-  const size_t o_rank = at; at += align256(n * 4);
-  const size_t o_start = at; at += align256((2 * n + 1) * 4);
-  const size_t o_bu = at; at += align256(m * 4);
-  const size_t o_bv = at; at += align256(m * 4);
-  const size_t o_ka = at; at += align256(e * 8);
-  const size_t o_kb = at; at += align256(e * 8);
-  const size_t o_va = at; at += align256(e * 4);
-  const size_t o_vb = at; at += align256(e * 4);
-  const size_t o_off = at; at += align256(e * 2);
-  const size_t o_tmp = at; at += align256(tmp + 16);
-  void *base = nullptr;
-  int rc = ppk_scratch_get(dev, SLOT_NET, at, &base);
+  unsigned long long *bad, *tri, *wed, *ka, *kb;
+  unsigned *cnt, *cursor, *links, *start2;
+  int *parent, *is_root, *rank, *bu, *bv, *va, *vb;
+  uint16_t *off16;
+  char *d_tmp;
+  size_t zero_begin = 0, zero_end = 0;
+  int rc = ppk_scratch_carve(dev, SLOT_NET, [&](Carve &c) {
+    c.take(bad, 1);
+    zero_begin = c.at;
+    c.take(cnt, 1024).take(cursor, 1024).take(links, 1024).take(tri, 1024).take(wed, 1024);
+    zero_end = c.at;
+    c.take(parent, n).take(is_root, n).take(rank, n).take(start2, 2 * n + 1).take(bu, m).take(bv, m);
+    c.take(ka, e).take(kb, e).take(va, e).take(vb, e).take(off16, e).take(d_tmp, tmp + 16);
+  });
   if (rc != PPK_OK) return rc;
-  char *B = static_cast<char *>(base);
-  unsigned long long *bad = reinterpret_cast<unsigned long long *>(B + o_bad);
-  unsigned *cnt = reinterpret_cast<unsigned *>(B + o_cnt), *cursor = reinterpret_cast<unsigned *>(B + o_cur);
-  unsigned *links = reinterpret_cast<unsigned *>(B + o_links);
-  unsigned long long *tri = reinterpret_cast<unsigned long long *>(B + o_tri);
-  unsigned long long *wed = reinterpret_cast<unsigned long long *>(B + o_wed);
-  int *parent = reinterpret_cast<int *>(B + o_parent), *is_root = reinterpret_cast<int *>(B + o_root);
-  int *rank = reinterpret_cast<int *>(B + o_rank);
-  unsigned *start2 = reinterpret_cast<unsigned *>(B + o_start);
-  int *bu = reinterpret_cast<int *>(B + o_bu), *bv = reinterpret_cast<int *>(B + o_bv);
-  unsigned long long *ka = reinterpret_cast<unsigned long long *>(B + o_ka), *kb = reinterpret_cast<unsigned long long *>(B + o_kb);
-  int *va = reinterpret_cast<int *>(B + o_va), *vb = reinterpret_cast<int *>(B + o_vb);
-  uint16_t *off16 = reinterpret_cast<uint16_t *>(B + o_off);
-  void *d_tmp = B + o_tmp;
-  unsigned long long *h = pinned_counts(dev);
-  if (!h) return ppk_fail(PPK_ERR_HIP, "hipHostMalloc failed");
 
   // -- validate: the one synchronisation
   ppk_prof_stage("validate", s);
-  PPK_HIP(hipMemsetAsync(B + o_cnt, 0, zero_end - o_cnt, s));
+  PPK_HIP(hipMemsetAsync(cnt, 0, zero_end - zero_begin, s));
   PPK_HIP(hipMemsetAsync(bad, 0xff, 8, s));
   const unsigned cap_grid = 2048;
   if (m)
     hipLaunchKernelGGL(net_validate_kernel, dim3(grid_for(m, kThreads * 8, cap_grid)), dim3(kThreads), 0, s, d_i, d_j,
                        stride, d_off, m, (long long)n, (int)no, cnt, bad);
   PPK_HIP(hipGetLastError());
-  PPK_HIP(hipMemcpyAsync(h, bad, 8, hipMemcpyDeviceToHost, s));
-  PPK_HIP(hipMemcpyAsync(h + 1, cnt, no * 4, hipMemcpyDeviceToHost, s));
-  PPK_HIP(hipStreamSynchronize(s));
+  const unsigned long long *h = nullptr;
+  if ((rc = ppk_read_back(dev, s, {{bad, 8}, {cnt, no * 4}}, &h)) != PPK_OK) return rc;
   if (h[0] != ~0ull) {
     ppk_prof_stage(nullptr, s);
-    return bad_edge_message(d_i, d_j, stride, d_off, (size_t)h[0], n, no);
+    return bad_edge_message(who, d_i, d_j, stride, d_off, (size_t)h[0], n, no);
   }
   std::vector<unsigned> counts(no), starts(no);
-  memcpy(counts.data(), h + 1, no * 4);
+  memcpy(counts.data(), h + 1, no * 4);     // before bt_run's read-back reuses the block
   for (size_t o = 0, acc = 0; o < no; ++o) {
     starts[o] = (unsigned)acc;
     acc += counts[o];
@@ -1117,15 +1036,8 @@ int net_sweep(const long long *d_i, const long long *d_j, size_t stride, const l
     PPK_HIP(hipGetLastError());
     // -- triangles
     ppk_prof_stage("triangles", s);
-    static bool big_lds[64] = {}, asked[64] = {};
-    if (!asked[dev & 63]) {
-      asked[dev & 63] = true;
-      big_lds[dev & 63] = hipFuncSetAttribute(reinterpret_cast<const void *>(net_triangles_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              (int)(kTableMax * sizeof(uint16_t))) == hipSuccess;
-      (void)hipGetLastError();
-    }
-    const unsigned tl = table_entries(n, big_lds[dev & 63]);
+    const unsigned tl = table_entries(n, ppk_lds_opt_in(reinterpret_cast<const void *>(net_triangles_kernel), dev,
+                                                        (int)(kTableMax * sizeof(uint16_t))));
     hipLaunchKernelGGL(net_triangles_kernel, dim3((unsigned)(n < (1u << 20) ? n : (1u << 20))), dim3(kThreads),
                        tl * sizeof(uint16_t), s, nbr, off16, start2, n, (int)no, tl, tri);
     PPK_HIP(hipGetLastError());
@@ -1149,7 +1061,8 @@ int net_sweep(const long long *d_i, const long long *d_j, size_t stride, const l
 extern "C" int ppk_network_sweep_dev(const long long *d_i, const long long *d_j, size_t stride,
                                      const long long *d_off, size_t n_edges, size_t n_vertices, size_t n_off,
                                      long long labels_at, long long *d_stats, int32_t *d_labels, void *stream) {
-  return net_sweep(d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, labels_at, d_stats, d_labels, stream, nullptr);
+  return net_sweep("ppk_network_sweep", d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, labels_at, d_stats,
+                   d_labels, stream, nullptr);
 }
 
 extern "C" int ppk_network_sweep(const long long *i, const long long *j, const long long *off, size_t n_edges,
@@ -1157,32 +1070,26 @@ extern "C" int ppk_network_sweep(const long long *i, const long long *j, const l
                                  int32_t *labels) {
   if (!stats || (n_edges && (!i || !j)) || (labels_at >= 0 && !labels && n_vertices))
     return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: NULL array");
-  if (n_off == 0 || n_off > (size_t)kMaxOff) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_off must be 1 .. 1023");
-  if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_edges must be < 2^31");
-  if (n_vertices >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_vertices must be < 2^31");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
-  PpkCall call(device_id, nullptr);
-  const size_t eb = align256(n_edges * 8), sb = align256(n_off * 32), lb = align256(n_vertices * 4);
-  void *p = nullptr;
-  int rc = ppk_scratch_get(device_id, SLOT_HOST_IN, 3 * eb + sb + lb + 256, &p);
+  const int rc = net_check("ppk_network_sweep", n_edges, n_vertices, n_off);
   if (rc != PPK_OK) return rc;
-  char *B = static_cast<char *>(p);
-  long long *d_i = reinterpret_cast<long long *>(B), *d_j = reinterpret_cast<long long *>(B + eb);
-  long long *d_o = off ? reinterpret_cast<long long *>(B + 2 * eb) : nullptr;
-  long long *d_stats = reinterpret_cast<long long *>(B + 3 * eb);
-  int32_t *d_labels = reinterpret_cast<int32_t *>(B + 3 * eb + sb);
-  if (n_edges) {
-    PPK_HIP(hipMemcpy(d_i, i, n_edges * 8, hipMemcpyHostToDevice));
-    PPK_HIP(hipMemcpy(d_j, j, n_edges * 8, hipMemcpyHostToDevice));
-    if (off) PPK_HIP(hipMemcpy(d_o, off, n_edges * 8, hipMemcpyHostToDevice));
-  }
-  rc = ppk_network_sweep_dev(d_i, d_j, 1, d_o, n_edges, n_vertices, n_off, labels_at, d_stats,
-                             labels_at >= 0 ? d_labels : nullptr, nullptr);
-  if (rc != PPK_OK) return rc;
-  PPK_HIP(hipMemcpy(stats, d_stats, n_off * 32, hipMemcpyDeviceToHost));
-  if (labels_at >= 0 && n_vertices) PPK_HIP(hipMemcpy(labels, d_labels, n_vertices * 4, hipMemcpyDeviceToHost));
-  return PPK_OK;
+  long long *d_i, *d_j, *d_o, *d_stats;
+  int32_t *d_labels;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_i, n_edges).take(d_j, n_edges).take(d_o, n_edges).take(d_stats, 4 * n_off).take(d_labels, n_vertices);
+    c.at += 256;     // (spare)
+  }, [&]() -> int {
+    if (n_edges) {
+      PPK_HIP(hipMemcpy(d_i, i, n_edges * 8, hipMemcpyHostToDevice));
+      PPK_HIP(hipMemcpy(d_j, j, n_edges * 8, hipMemcpyHostToDevice));
+      if (off) PPK_HIP(hipMemcpy(d_o, off, n_edges * 8, hipMemcpyHostToDevice));
+    }
+    const int rc = ppk_network_sweep_dev(d_i, d_j, 1, off ? d_o : nullptr, n_edges, n_vertices, n_off, labels_at,
+                                         d_stats, labels_at >= 0 ? d_labels : nullptr, nullptr);
+    if (rc != PPK_OK) return rc;
+    PPK_HIP(hipMemcpy(stats, d_stats, n_off * 32, hipMemcpyDeviceToHost));
+    if (labels_at >= 0 && n_vertices) PPK_HIP(hipMemcpy(labels, d_labels, n_vertices * 4, hipMemcpyDeviceToHost));
+    return PPK_OK;
+  });
 }
 
 extern "C" int ppk_network_summary_dev(const long long *d_i, const long long *d_j, size_t stride,
@@ -1193,7 +1100,8 @@ extern "C" int ppk_network_summary_dev(const long long *d_i, const long long *d_
     return ppk_fail(PPK_ERR_ARG, "ppk_network_summary: values_at must be -1 or an offset index");
   if (!d_bt || (values_at >= 0 && !d_values && n_vertices)) return ppk_fail(PPK_ERR_ARG, "ppk_network_summary: NULL array");
   const BtJob job{d_bt, d_scored, values_at >= 0 && n_vertices ? d_values : nullptr, values_at};
-  return net_sweep(d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, -1, d_stats, nullptr, stream, &job);
+  return net_sweep("ppk_network_summary", d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, -1, d_stats, nullptr,
+                   stream, &job);
 }
 
 extern "C" int ppk_network_summary(const long long *i, const long long *j, const long long *off, size_t n_edges,
@@ -1201,35 +1109,27 @@ extern "C" int ppk_network_summary(const long long *i, const long long *j, const
                                    double *bt, long long *scored, double *values) {
   if (!stats || !bt || (n_edges && (!i || !j)) || (values_at >= 0 && !values && n_vertices))
     return ppk_fail(PPK_ERR_ARG, "ppk_network_summary: NULL array");
-  if (n_off == 0 || n_off > (size_t)kMaxOff) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_off must be 1 .. 1023");
-  if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_edges must be < 2^31");
-  if (n_vertices >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_network_sweep: n_vertices must be < 2^31");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
-  PpkCall call(device_id, nullptr);
-  const size_t eb = align256(n_edges * 8), sb = align256(n_off * 32), bb = align256(n_off * 16), cb = align256(n_off * 8);
-  const size_t vb = align256(n_vertices * 8);
-  void *p = nullptr;
-  int rc = ppk_scratch_get(device_id, SLOT_HOST_IN, 3 * eb + sb + bb + cb + vb + 256, &p);
+  const int rc = net_check("ppk_network_summary", n_edges, n_vertices, n_off);
   if (rc != PPK_OK) return rc;
-  char *B = static_cast<char *>(p);
-  long long *d_i = reinterpret_cast<long long *>(B), *d_j = reinterpret_cast<long long *>(B + eb);
-  long long *d_o = off ? reinterpret_cast<long long *>(B + 2 * eb) : nullptr;
-  long long *d_stats = reinterpret_cast<long long *>(B + 3 * eb);
-  double *d_bt = reinterpret_cast<double *>(B + 3 * eb + sb);
-  long long *d_scored = reinterpret_cast<long long *>(B + 3 * eb + sb + bb);
-  double *d_values = reinterpret_cast<double *>(B + 3 * eb + sb + bb + cb);
-  if (n_edges) {
-    PPK_HIP(hipMemcpy(d_i, i, n_edges * 8, hipMemcpyHostToDevice));
-    PPK_HIP(hipMemcpy(d_j, j, n_edges * 8, hipMemcpyHostToDevice));
-    if (off) PPK_HIP(hipMemcpy(d_o, off, n_edges * 8, hipMemcpyHostToDevice));
-  }
-  rc = ppk_network_summary_dev(d_i, d_j, 1, d_o, n_edges, n_vertices, n_off, values_at, d_stats, d_bt, d_scored,
-                               values_at >= 0 ? d_values : nullptr, nullptr);
-  if (rc != PPK_OK) return rc;
-  PPK_HIP(hipMemcpy(stats, d_stats, n_off * 32, hipMemcpyDeviceToHost));
-  PPK_HIP(hipMemcpy(bt, d_bt, n_off * 16, hipMemcpyDeviceToHost));
-  if (scored) PPK_HIP(hipMemcpy(scored, d_scored, n_off * 8, hipMemcpyDeviceToHost));
-  if (values_at >= 0 && n_vertices) PPK_HIP(hipMemcpy(values, d_values, n_vertices * 8, hipMemcpyDeviceToHost));
-  return PPK_OK;
+  long long *d_i, *d_j, *d_o, *d_stats, *d_scored;
+  double *d_bt, *d_values;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_i, n_edges).take(d_j, n_edges).take(d_o, n_edges);
+    c.take(d_stats, 4 * n_off).take(d_bt, 2 * n_off).take(d_scored, n_off).take(d_values, n_vertices);
+    c.at += 256;     // (spare)
+  }, [&]() -> int {
+    if (n_edges) {
+      PPK_HIP(hipMemcpy(d_i, i, n_edges * 8, hipMemcpyHostToDevice));
+      PPK_HIP(hipMemcpy(d_j, j, n_edges * 8, hipMemcpyHostToDevice));
+      if (off) PPK_HIP(hipMemcpy(d_o, off, n_edges * 8, hipMemcpyHostToDevice));
+    }
+    const int rc = ppk_network_summary_dev(d_i, d_j, 1, off ? d_o : nullptr, n_edges, n_vertices, n_off, values_at,
+                                           d_stats, d_bt, d_scored, values_at >= 0 ? d_values : nullptr, nullptr);
+    if (rc != PPK_OK) return rc;
+    PPK_HIP(hipMemcpy(stats, d_stats, n_off * 32, hipMemcpyDeviceToHost));
+    PPK_HIP(hipMemcpy(bt, d_bt, n_off * 16, hipMemcpyDeviceToHost));
+    if (scored) PPK_HIP(hipMemcpy(scored, d_scored, n_off * 8, hipMemcpyDeviceToHost));
+    if (values_at >= 0 && n_vertices) PPK_HIP(hipMemcpy(values, d_values, n_vertices * 8, hipMemcpyDeviceToHost));
+    return PPK_OK;
+  });
 }

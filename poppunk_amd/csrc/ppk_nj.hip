@@ -35,8 +35,6 @@ struct Best {
   unsigned long long e;
 };
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 __host__ __device__ __forceinline__ size_t tri(size_t a) { return a * (a - 1) / 2; }   // entries before row a
 
 // the row a of triangle entry e (tri(a) <= e < tri(a + 1))
@@ -294,14 +292,6 @@ int nj_bad_entry(const float *src, int kind, size_t stride, size_t col, size_t n
                                    (std::isnan(v) ? "NaN" : "infinite"));
 }
 
-unsigned long long *pinned_word(int dev) {
-  static unsigned long long *words[64] = {};
-  if (dev < 0 || dev >= 64) return nullptr;
-  if (!words[dev] && hipHostMalloc(reinterpret_cast<void **>(&words[dev]), 256, hipHostMallocDefault) != hipSuccess)
-    words[dev] = nullptr;
-  return words[dev];
-}
-
 }  // namespace
 
 extern "C" int ppk_nj_dev(const float *d_src, int src_kind, size_t stride, size_t col, size_t n, long long *d_join,
@@ -321,38 +311,18 @@ extern "C" int ppk_nj_dev(const float *d_src, int src_kind, size_t stride, size_
 
   // scratch: bad | best slots | old_of | per-slot S, nd, ids, alive (x2) | triangle 0 | triangle 1
   const size_t c1 = first_compaction((long long)n);
-  size_t at = 0;
-  const size_t o_bad = at; at += 256;
-  const size_t o_part = at; at += align256(kMaxParts * sizeof(Best));
-  const size_t o_old = at; at += align256(n * 4);
-  size_t o_S[2], o_nd[2], o_ids[2], o_alive[2], o_W[2];
-  for (int i = 0; i < 2; ++i) {
-    o_S[i] = at; at += align256(n * 8);
-    o_nd[i] = at; at += align256(n * 8);
-    o_ids[i] = at; at += align256(n * 8);
-    o_alive[i] = at; at += align256(n);
-  }
-  o_W[0] = at; at += align256(tri(n) * 8);
-  o_W[1] = at; at += align256(tri(c1) * 8);
-  void *base = nullptr;
-  int rc = ppk_scratch_get(dev, SLOT_NJ, at, &base);
-  if (rc != PPK_OK) return rc;
-  char *B = static_cast<char *>(base);
-  unsigned long long *bad = reinterpret_cast<unsigned long long *>(B + o_bad);
-  Best *part = reinterpret_cast<Best *>(B + o_part);
-  unsigned *old_of = reinterpret_cast<unsigned *>(B + o_old);
+  unsigned long long *bad;
+  Best *part;
+  unsigned *old_of;
   double *S[2], *nd[2], *W[2];
   long long *ids[2];
   unsigned char *alive[2];
-  for (int i = 0; i < 2; ++i) {
-    S[i] = reinterpret_cast<double *>(B + o_S[i]);
-    nd[i] = reinterpret_cast<double *>(B + o_nd[i]);
-    ids[i] = reinterpret_cast<long long *>(B + o_ids[i]);
-    alive[i] = reinterpret_cast<unsigned char *>(B + o_alive[i]);
-    W[i] = reinterpret_cast<double *>(B + o_W[i]);
-  }
-  unsigned long long *h = pinned_word(dev);
-  if (!h) return ppk_fail(PPK_ERR_HIP, "hipHostMalloc failed");
+  int rc = ppk_scratch_carve(dev, SLOT_NJ, [&](Carve &c) {
+    c.take(bad, 1).take(part, kMaxParts).take(old_of, n);
+    for (int i = 0; i < 2; ++i) c.take(S[i], n).take(nd[i], n).take(ids[i], n).take(alive[i], n);
+    c.take(W[0], tri(n)).take(W[1], tri(c1));
+  });
+  if (rc != PPK_OK) return rc;
 
   // -- load: the one synchronisation
   ppk_prof_stage("load", s);
@@ -360,8 +330,8 @@ extern "C" int ppk_nj_dev(const float *d_src, int src_kind, size_t stride, size_
   hipLaunchKernelGGL(nj_load_kernel, dim3((unsigned)(n - 1 < 8192 ? n - 1 : 8192)), dim3(kThreads), 0, s, d_src,
                      src_kind, stride, col, n, W[0], bad);
   PPK_HIP(hipGetLastError());
-  PPK_HIP(hipMemcpyAsync(h, bad, 8, hipMemcpyDeviceToHost, s));
-  PPK_HIP(hipStreamSynchronize(s));
+  const unsigned long long *h = nullptr;
+  if ((rc = ppk_read_back(dev, s, {{bad, 8}}, &h)) != PPK_OK) return rc;
   if (h[0] != ~0ull) {
     ppk_prof_stage(nullptr, s);
     return nj_bad_entry(d_src, src_kind, stride, col, n, (size_t)h[0]);
@@ -417,21 +387,17 @@ extern "C" int ppk_nj(const float *square, size_t n, int device_id, long long *j
   if (n >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_nj: n must be < 2^31");
   if (n > 1 && (!square || !join || !len)) return ppk_fail(PPK_ERR_ARG, "ppk_nj: NULL array");
   if (n == 1) return PPK_OK;
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
-  PpkCall call(device_id, nullptr);
-  const size_t sb = align256(n * n * 4), jb = align256((n - 1) * 16);
-  void *p = nullptr;
-  int rc = ppk_scratch_get(device_id, SLOT_HOST_IN, sb + 2 * jb, &p);
-  if (rc != PPK_OK) return rc;
-  char *B = static_cast<char *>(p);
-  float *d_sq = reinterpret_cast<float *>(B);
-  long long *d_join = reinterpret_cast<long long *>(B + sb);
-  double *d_len = reinterpret_cast<double *>(B + sb + jb);
-  PPK_HIP(hipMemcpy(d_sq, square, n * n * 4, hipMemcpyHostToDevice));
-  rc = ppk_nj_dev(d_sq, PPK_NJ_SQUARE, 1, 0, n, d_join, d_len, nullptr);
-  if (rc != PPK_OK) return rc;
-  PPK_HIP(hipMemcpy(join, d_join, (n - 1) * 16, hipMemcpyDeviceToHost));
-  PPK_HIP(hipMemcpy(len, d_len, (n - 1) * 16, hipMemcpyDeviceToHost));
-  return PPK_OK;
+  float *d_sq;
+  long long *d_join;
+  double *d_len;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_sq, n * n).take(d_join, 2 * (n - 1)).take(d_len, 2 * (n - 1));
+  }, [&]() -> int {
+    PPK_HIP(hipMemcpy(d_sq, square, n * n * 4, hipMemcpyHostToDevice));
+    const int rc = ppk_nj_dev(d_sq, PPK_NJ_SQUARE, 1, 0, n, d_join, d_len, nullptr);
+    if (rc != PPK_OK) return rc;
+    PPK_HIP(hipMemcpy(join, d_join, (n - 1) * 16, hipMemcpyDeviceToHost));
+    PPK_HIP(hipMemcpy(len, d_len, (n - 1) * 16, hipMemcpyDeviceToHost));
+    return PPK_OK;
+  });
 }

@@ -312,6 +312,7 @@ def test_errors_name_an_edge_and_the_next_call_succeeds():
     for args, msg in cases:
         assert call(*args) == _lib.ERR_ARG, msg
         assert msg in lib.ppk_last_error(), (msg, lib.ppk_last_error())
+        assert b"ppk_network_summary" in lib.ppk_last_error(), lib.ppk_last_error()
         assert call(i, j, o, 5, 3, 2) == _lib.OK
         torch.cuda.synchronize()
         assert st[:3].tolist() == [[1, 4, 0, 0], [3, 2, 0, 2], [4, 2, 0, 4]]
