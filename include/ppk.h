@@ -496,6 +496,51 @@ int ppk_nj_dev(const float *d_src, int src_kind, size_t stride, size_t col, size
 int ppk_nj(const float *square, size_t n, int device_id, long long *join, double *len);
 
 /* ------------------------------------------------------------------------
+ * Stochastic cluster embeddings: 2-D coordinates of n samples from their k nearest neighbours, the
+ * loop of mandrake's SCE as this library defines it.  Input: neighbour lists in get_kNN_distances form, d_i, d_j int64
+ * [n*k], d_dist float32 [n*k]: entry e of row i = e / k, 2 <= n < 2^31, 1 <= k <= n - 1 (callers clamp k to n - 1).
+ * Node weights are all ones.  PPK_ERR_ARG, ppk_last_error() naming the first bad entry e, its i and j: i[e] != e / k
+ * (rows not grouped), j outside [0, n), j == i, a NaN, infinite or negative distance (ppk_embed_dev: a P outside
+ * [0, 1]).  Both device calls synchronise the stream once (the check's read-back).
+ *
+ * ppk_embed_weights_dev -> d_P float64 [n*k] and d_c uint64 [n*k] (nullable):
+ *  - the distances are divided by their root mean square (left as they are when every one is 0) [EXT];
+ *  - per row, x_j = d_j^2 - min_j d_j^2 and beta by float64 bisection from beta = 1 (doubling while no upper bound is
+ *    known) on H(beta) = ln Z + beta sum_j p_j x_j / Z, p_j = exp(-beta x_j), Z = sum_j p_j, toward H = ln(perplexity):
+ *    H > target raises beta.  It stops once hi - lo <= hi * 2^-48, or after 256 steps: a row that cannot reach the
+ *    target (K < perplexity, equal distances, zero distances of duplicates) ends at beta = 2^-256 or 2^256, finite;
+ *  - P[e] = (p_j / Z) / n (sum P = 1), c[e] = rint(P[e] * 2^52), the integer sampling weight of edge e.
+ *
+ * ppk_embed_dev: P (as above, or any P in [0, 1]) + lists + seed -> d_Y float64 [n][2].  With W = min(workers, n)
+ * workers per iteration (the cap that keeps small n stable) and T = max(1, rint(max_iter / W))
+ * iterations (ties to even), every draw from the counter-based generator of ppk_embed.hip
+ * (splitmix64 finaliser over seed, iteration, worker and draw):
+ *  - Y starts uniform in +-1e-4; Eq = 1;
+ *  - iteration t, learning rate eta = eta0 * max(1 - t / (T - 1), 1e-4) (T = 1: eta0): each worker draws one edge,
+ *    upper_bound(prefix(c), mulhi64(r, sum c)), as its attractive pair (i, j), and n_repu (<= 127) pairs
+ *    (mulhi64(r, n), mulhi64(r', n)) as repulsive pairs, skipping k == l.  For every pair (k, l), from the
+ *    iteration's snapshot of Y: dY = y_k - y_l, q = 1 / (1 + |dY|^2), g = -4q (attractive) or 4q^2 / Eq
+ *    (repulsive) [EXT]; gain = (eta g) dY, each coordinate clipped to +-0.1, is added to y_k and subtracted from
+ *    y_l as int64 Q32.32 rint(gain * 2^32);
+ *  - after the iteration, Y += deltas * 2^-32 and Eq = (Eq nsq + qsum) / (nsq + qcount), nsq = n(n - 1), qsum the
+ *    Q32.32 sum of the repulsive pairs' q (2^-32 units), qcount how many repulsive pairs were not skipped [EXT].
+ * Float64 throughout, un-fused, IEEE division.  Deterministic: integer accumulation only, so the same input gives the
+ * same bits on every call, and the host restatement of these rules gives them too.  PPK_ERR_INTERRUPTED when the
+ * interrupt check asks (polled every 256 iterations).  No synchronisation between iterations.
+ * (Replaces poppunk_refine.get_kNN_distances + SCE.wtsne / wtsne_gpu_fp32 in generate_embedding,
+ * PopPUNK/mandrake.py:66-111.) */
+int ppk_embed_weights_dev(const long long *d_i, const long long *d_j, const float *d_dist, size_t n, size_t k,
+                          double perplexity, double *d_P, unsigned long long *d_c, void *stream);
+int ppk_embed_dev(const long long *d_i, const long long *d_j, const double *d_P, size_t n, size_t k,
+                  unsigned long long seed, long long max_iter, int n_repu, double eta0, long long workers,
+                  double *d_Y, void *stream);
+/* Host arrays: i, j int64 [n*k], dist float32 [n*k] -> P float64 [n*k] (nullable), Y float64 [n][2], on device_id;
+ * ppk_embed_weights_dev then ppk_embed_dev; blocking.  max_iter >= 1, 1 <= workers <= 2^24. */
+int ppk_embed(const long long *i, const long long *j, const float *dist, size_t n, size_t k, double perplexity,
+              unsigned long long seed, long long max_iter, int n_repu, double eta0, long long workers, int device_id,
+              double *P, double *Y);
+
+/* ------------------------------------------------------------------------
  * Host-buffer convenience wrappers (what a pybind11/ctypes drop-in binds):
  * upload, run on `devices[0..n_dev)` (the pair space is band-split across
  * them), copy back.  Blocking.

@@ -53,6 +53,11 @@ SIGNATURES = {
     "ppk_edge_weights_dev": (C.c_int, [_vp, _sz, _vp, _vp, _sz, _sz, _sz, C.c_longlong, C.c_int, _vp, _vp]),
     "ppk_nj_dev": (C.c_int, [_vp, C.c_int, _sz, _sz, _sz, _vp, _vp, _vp]),
     "ppk_nj": (C.c_int, [_f32p, _sz, C.c_int, _llp, _f64p]),
+    "ppk_embed_weights_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz, C.c_double, _vp, _vp, _vp]),
+    "ppk_embed_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz, C.c_ulonglong, C.c_longlong, C.c_int, C.c_double,
+                                C.c_longlong, _vp, _vp]),
+    "ppk_embed": (C.c_int, [_llp, _llp, _f32p, _sz, _sz, C.c_double, C.c_ulonglong, C.c_longlong, C.c_int,
+                            C.c_double, C.c_longlong, C.c_int, _f64p, _f64p]),
     "ppk_last_error": (C.c_char_p, []),
     "ppk_version": (C.c_char_p, []),
     "ppk_release_scratch": (C.c_int, []),
@@ -224,7 +229,8 @@ def sources_hash_now():
     import hashlib
     here = os.path.join(_HERE, "csrc")
     names = ["ppk_api.hip", "ppk_host.hip", "ppk_dist.hip", "ppk_boundary.hip", "ppk_iterate.hip", "ppk_square.hip",
-             "ppk_sparse.hip", "ppk_bgmm.hip", "ppk_network.hip", "ppk_mst.hip", "ppk_nj.hip", "ppk_h5.cpp", "ppk_internal.h",
+             "ppk_sparse.hip", "ppk_bgmm.hip", "ppk_network.hip", "ppk_mst.hip", "ppk_nj.hip", "ppk_embed.hip", "ppk_h5.cpp",
+             "ppk_internal.h",
              "ppk_block_asm.inc", "../../include/ppk.h"]
     h = hashlib.sha256()
     try:

@@ -228,7 +228,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_NET_WORK = 13,                     // ... and one graph's partial sums and global-state slab (sized after its plan)
        SLOT_MST = 14,                          // the minimum spanning forest's ranks, labels and temp storage
        SLOT_NJ = 15,                           // neighbour joining's float64 triangles, row sums and best slots
-       SLOT_COUNT = 16 };
+       SLOT_EMBED = 16,                        // the embedding's sampling weights and prefix, Q32.32 deltas, Eq
+       SLOT_COUNT = 17 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

@@ -646,6 +646,84 @@ def nj(square, device_id=0):
     return join, ln
 
 
+EMBED_WORKERS = 65536     # workers per iteration as mandrake's GPU call sets them (PopPUNK/mandrake.py:77)
+
+
+def _embed_lists(i_t, j_t, n, what):
+    torch = _torch()
+    n = int(n)
+    for t in (i_t, j_t):
+        if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 1):
+            raise TypeError("%s: i and j must be contiguous int64 CUDA vectors" % what)
+    m = int(i_t.numel())
+    if int(j_t.numel()) != m or n < 2 or m % n or not 1 <= m // n <= n - 1:
+        raise ValueError("%s: lists of n*k entries with n >= 2 and 1 <= k <= n - 1 expected (n = %d, %d entries)"
+                         % (what, n, m))
+    return m // n
+
+
+def embed_weights_dev(i_t, j_t, dist_t, n, perplexity=20.0, weights=False):
+    """The embedding's calibration on the device (ppk_embed_weights_dev) from neighbour lists in
+    get_kNN_distances form (CUDA i, j int64 and dist float32 [n*k], row i = e // k).  Returns P, float64 [n*k] with
+    sum 1, and with weights=True also the integer sampling weights rint(P * 2^52) as int64 (uint64 bits)."""
+    torch = _torch()
+    k = _embed_lists(i_t, j_t, n, "embed_weights_dev")
+    if not (dist_t.is_cuda and dist_t.dtype == torch.float32 and dist_t.is_contiguous()
+            and int(dist_t.numel()) == int(i_t.numel())):
+        raise TypeError("embed_weights_dev: dist must be a contiguous float32 CUDA vector as long as i")
+    dev = i_t.device
+    with torch.cuda.device(dev):
+        P = torch.empty(int(i_t.numel()), dtype=torch.float64, device=dev)
+        c = torch.empty(int(i_t.numel()), dtype=torch.int64, device=dev) if weights else None
+        rc = _lib.lib().ppk_embed_weights_dev(C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()),
+                                              C.c_void_p(dist_t.data_ptr()), int(n), k, float(perplexity),
+                                              C.c_void_p(P.data_ptr()), C.c_void_p(c.data_ptr() if weights else None),
+                                              _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_embed_weights_dev")
+    return (P, c) if weights else P
+
+
+def embed_dev(i_t, j_t, P_t, n, seed, max_iter=10000000, n_repu=5, eta0=1.0, workers=EMBED_WORKERS):
+    """The embedding's loop on the device (ppk_embed_dev): lists and P (embed_weights_dev) -> Y,
+    a float64 [n, 2] CUDA tensor.  min(workers, n) workers per iteration, round(max_iter / that) iterations."""
+    torch = _torch()
+    k = _embed_lists(i_t, j_t, n, "embed_dev")
+    if not (P_t.is_cuda and P_t.dtype == torch.float64 and P_t.is_contiguous()
+            and int(P_t.numel()) == int(i_t.numel())):
+        raise TypeError("embed_dev: P must be a contiguous float64 CUDA vector as long as i")
+    dev = i_t.device
+    with torch.cuda.device(dev):
+        Y = torch.empty((int(n), 2), dtype=torch.float64, device=dev)
+        rc = _lib.lib().ppk_embed_dev(C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()),
+                                      C.c_void_p(P_t.data_ptr()), int(n), k, int(seed) & ((1 << 64) - 1),
+                                      int(max_iter), int(n_repu), float(eta0), int(workers), C.c_void_p(Y.data_ptr()),
+                                      _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_embed_dev")
+    return Y
+
+
+def embed(i, j, dist, n, seed, perplexity=20.0, max_iter=10000000, n_repu=5, eta0=1.0, workers=EMBED_WORKERS,
+          device_id=0):
+    """ppk_embed: embed_weights_dev then embed_dev on host arrays (numpy or sequences, get_kNN_distances form).
+    Returns numpy (P float64 [n*k], Y float64 [n, 2])."""
+    ii = np.ascontiguousarray(i, dtype=np.int64).ravel()
+    jj = np.ascontiguousarray(j, dtype=np.int64).ravel()
+    dd = np.ascontiguousarray(dist, dtype=np.float32).ravel()
+    n, m = int(n), int(ii.size)
+    if jj.size != m or dd.size != m or n < 2 or m % n or not 1 <= m // n <= n - 1:
+        raise ValueError("embed: lists of n*k entries with n >= 2 and 1 <= k <= n - 1 expected (n = %d, %d entries)"
+                         % (n, m))
+    P = np.empty(m, dtype=np.float64)
+    Y = np.empty((n, 2), dtype=np.float64)
+    ll, f64 = C.POINTER(C.c_longlong), C.POINTER(C.c_double)
+    _lib.check(_lib.lib().ppk_embed(ii.ctypes.data_as(ll), jj.ctypes.data_as(ll),
+                                    dd.ctypes.data_as(C.POINTER(C.c_float)), n, m // n, float(perplexity),
+                                    int(seed) & ((1 << 64) - 1), int(max_iter), int(n_repu), float(eta0),
+                                    int(workers), int(device_id), P.ctypes.data_as(f64), Y.ctypes.data_as(f64)),
+               "ppk_embed")
+    return P, Y
+
+
 def _samples_of(n_rows):
     n = int((1 + (1 + 8 * n_rows) ** 0.5) // 2)
     while n * (n - 1) // 2 > n_rows:
