@@ -355,6 +355,76 @@ int ppk_bgmm_assign(const float *dist, size_t n_rows, const ppk_bgmm *model, int
                     float *resp);
 
 /* ------------------------------------------------------------------------
+ * DBSCAN: fitting and assigning PopPUNK's --fit-model dbscan (HDBSCAN; DBSCANFit, PopPUNK/models.py:468-783,
+ * PopPUNK/dbscan.py:20-66).  The device computes the core distances and the minimum spanning tree of the mutual
+ * reachability graph, and assigns rows with a fitted model; the hierarchy between the two (single linkage, condensed
+ * tree, excess-of-mass selection) is sequential and lives on the host (poppunk_amd/dbscan.py).
+ * Training points P: float32 [n][2], already divided by the model's scale.  m = min_samples and c = min_cluster_size
+ * in PopPUNK's (the hdbscan package's) meaning; sklearn's HDBSCAN counts the point itself, so this m is its m + 1.
+ *   d2(a, b)    = (double)(ax - bx)^2 + (double)(ay - by)^2: float32 widened, then IEEE double operations, none
+ *                 fused.  Everything is ordered on d2; d = sqrt(d2) only where a lambda is formed.
+ *   core2[a]    = the m-th smallest d2(a, b) over b != a (duplicates count; m <= n - 1 or PPK_ERR_ARG)
+ *   mr2(a, b)   = max(core2[a], core2[b], d2(a, b))
+ *   edges are ordered by (mr2, min(a, b), max(a, b)), a total order.  Ties in mr2 are the rule (every neighbour
+ *   inside a point's core distance ties exactly) and decide labels, so the order is part of the definition; the
+ *   minimum spanning tree is the unique one under it and is emitted sorted by it.
+ * Host: union-find over the sorted edges -> single-linkage tree -> condensed tree for c -> stabilities -> excess of
+ * mass with allow_single_cluster = False, cluster_selection_epsilon = 0, no max_cluster_size (the rules of
+ * sklearn/cluster/_hdbscan/_tree.pyx), lambda = 1 / d and +inf at d = 0.  Labels: -1 noise, clusters numbered in
+ * increasing order of their smallest member.  A fit keeps core2, every point's condensed-tree parent and the lambda at
+ * which it leaves it, and per condensed cluster (0 is the root) its parent, its birth lambda and its label: the label
+ * of the selected cluster at or above it, -1 when there is none.
+ * Assignment of a row x = (core, accessory), q = x / scale (float32 / float32; with a float64 scale the float64
+ * quotient rounded to float32, the training points' type):
+ *   [EXT] the five steps below restate hdbscan/prediction.py (approximate_predict -> _find_neighbor_and_lambda ->
+ *   [EXT] _find_cluster_and_probability) from memory; that package is not available to check against.
+ *   1. [EXT] order the training points by (d2(q, t), t); N = the first 2m of them (all, if n < 2m)
+ *   2. [EXT] r2 = d2 of the (m + 1)-th (0-based position m; the last, if n <= m)
+ *   3. [EXT] t* = the first t of N in that order that minimises w2 = max(core2[t], r2, d2(q, t));
+ *      [EXT] lambda_q = 1 / sqrt(w2), or DBL_MAX when w2 = 0
+ *   4. [EXT] start at t*'s condensed-tree parent; if lambda(t*) > lambda_q, climb while the cluster is not the root
+ *      [EXT] and its birth lambda >= lambda_q
+ *   5. [EXT] label = that cluster's label (see above: a cluster below a selected one carries the selected one's)
+ *   The tie rule of step 1 (by training index) is this library's; a k-d tree's is unspecified.
+ * The per-row search goes through a uniform grid over the training points kept in the model; it
+ * certifies per row that no point outside the cells it read can precede or tie the 2m nearest, and scans everything
+ * otherwise, so the labels are those of the definition whatever the structure (option dbscan_search: 1 = always the
+ * plain scan, 2 = the grid at any size). */
+/* d_pts float32 [n][2] -> d_core2 double [n]; bit for bit np.partition of the full float64 row. */
+int ppk_dbscan_core_dev(const float *d_pts, size_t n, int min_samples, double *d_core2, void *stream);
+/* The n - 1 edges (d_a < d_b, d_mr2) of the minimum spanning tree, sorted under the total order.  No
+ * synchronisation. */
+int ppk_dbscan_mst_dev(const float *d_pts, const double *d_core2, size_t n, int32_t *d_a, int32_t *d_b,
+                       double *d_mr2, void *stream);
+/* Both from and to host arrays (core2 [n]; a, b, mr2 [n - 1]); blocking. */
+int ppk_dbscan_fit(const float *pts, size_t n, int min_samples, int device_id, double *core2, int32_t *a,
+                   int32_t *b, double *mr2);
+
+/* A fitted model on device_id: copies of the host arrays above (pts float32 [n][2], core2, pt_cluster, pt_lambda
+ * [n]; cl_parent, cl_birth, cl_label [n_cl], cluster 0 the root with parent -1 and every parent before its child),
+ * the scale (double [2]; scale_is_f64 as ppk_bgmm_prepare) and the label whose rows are edges.  PPK_ERR_ARG for
+ * n outside [1, 2^31), min_samples < 1, a non-positive scale or tree arrays that do not form a rooted tree. */
+typedef struct ppk_dbscan ppk_dbscan;
+int ppk_dbscan_create(const float *pts, const double *core2, size_t n, int min_samples, const int32_t *pt_cluster,
+                      const double *pt_lambda, const int32_t *cl_parent, const double *cl_birth,
+                      const int32_t *cl_label, size_t n_cl, const double *scale, int scale_is_f64, int within_label,
+                      int device_id, ppk_dbscan **out);
+void ppk_dbscan_destroy(ppk_dbscan *model);
+/* d_dist float32 [n_rows][2] -> d_labels int32 [n_rows], on the model's device. */
+int ppk_dbscan_assign_dev(const float *d_dist, size_t n_rows, const ppk_dbscan *model, int32_t *d_labels,
+                          void *stream);
+/* ppk_dbscan_assign_dev + ppk_generate_tuples_dev(labels, within_label, n_ref == 0, n_ref, int_offset, ...), element
+ * for element, stable, the same cap / PPK_ERR_CAPACITY rules (the shared row-test edge-list path). */
+int ppk_dbscan_edges_dev(const float *d_dist, size_t n_rows, size_t n_ref, const ppk_dbscan *model,
+                         long long int_offset, long long *d_edges, size_t cap, unsigned long long *d_n_edges,
+                         void *stream);
+/* Rows, since the model was created, whose search ended as a scan of every training point (rows far outside the
+ * training cloud; every row with option dbscan_search = 1 is NOT counted: that kernel has no search).  Blocking. */
+int ppk_dbscan_stats(const ppk_dbscan *model, unsigned long long *rows_scanned);
+/* Host arrays, in chunks of 4 Mi rows; blocking. */
+int ppk_dbscan_assign(const float *dist, size_t n_rows, const ppk_dbscan *model, int32_t *labels);
+
+/* ------------------------------------------------------------------------
  * Boundary sweeps of --fit-model refine (SURVEY.md 8f "next" rows), on a
  * resident self/condensed [n_rows][2] float32 distance buffer.  Outputs are
  * three int64 arrays (i, j, offset index), element for element the vectors

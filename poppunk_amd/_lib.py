@@ -58,6 +58,16 @@ SIGNATURES = {
                                 C.c_longlong, _vp, _vp]),
     "ppk_embed": (C.c_int, [_llp, _llp, _f32p, _sz, _sz, C.c_double, C.c_ulonglong, C.c_longlong, C.c_int,
                             C.c_double, C.c_longlong, C.c_int, _f64p, _f64p]),
+    "ppk_dbscan_core_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _vp]),
+    "ppk_dbscan_mst_dev": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "ppk_dbscan_fit": (C.c_int, [_f32p, _sz, C.c_int, C.c_int, _f64p, _i32p, _i32p, _f64p]),
+    "ppk_dbscan_create": (C.c_int, [_f32p, _f64p, _sz, C.c_int, _i32p, _f64p, _i32p, _f64p, _i32p, _sz, _f64p,
+                                    C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "ppk_dbscan_destroy": (None, [_vp]),
+    "ppk_dbscan_assign_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp]),
+    "ppk_dbscan_edges_dev": (C.c_int, [_vp, _sz, _sz, _vp, C.c_longlong, _vp, _sz, _vp, _vp]),
+    "ppk_dbscan_assign": (C.c_int, [_f32p, _sz, _vp, _i32p]),
+    "ppk_dbscan_stats": (C.c_int, [_vp, _ullp]),
     "ppk_last_error": (C.c_char_p, []),
     "ppk_version": (C.c_char_p, []),
     "ppk_release_scratch": (C.c_int, []),
@@ -229,7 +239,8 @@ def sources_hash_now():
     import hashlib
     here = os.path.join(_HERE, "csrc")
     names = ["ppk_api.hip", "ppk_host.hip", "ppk_dist.hip", "ppk_boundary.hip", "ppk_iterate.hip", "ppk_square.hip",
-             "ppk_sparse.hip", "ppk_bgmm.hip", "ppk_network.hip", "ppk_mst.hip", "ppk_nj.hip", "ppk_embed.hip", "ppk_h5.cpp",
+             "ppk_sparse.hip", "ppk_bgmm.hip", "ppk_network.hip", "ppk_mst.hip", "ppk_nj.hip", "ppk_embed.hip",
+             "ppk_dbscan.hip", "ppk_h5.cpp",
              "ppk_internal.h",
              "ppk_block_asm.inc", "../../include/ppk.h"]
     h = hashlib.sha256()

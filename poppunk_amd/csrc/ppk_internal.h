@@ -77,6 +77,7 @@ struct PpkConfig {
   std::atomic<long long> net_window{0};         // PPK_NET_WINDOW: vertex ids per LDS table window of the network sweep's triangle stage (0 = as many as LDS holds; small values force the windowed path: tests; same results)
   std::atomic<long long> bt_lds_max{0};        // PPK_BT_LDS_MAX: largest component whose Brandes state lives in LDS (0 = as many vertices as LDS holds; small values force the global-state path: tests; results within rounding)
   std::atomic<long long> bt_small_max{64};      // PPK_BT_SMALL_MAX: largest component Brandes gives one wave for all its sources (0 = none; at most 256; results within rounding)
+  std::atomic<long long> dbscan_search{0};      // PPK_DBSCAN_SEARCH: the DBSCAN assignment's search: 0 = the grid from 1 024 training points up, 1 = the scan of every training point, 2 = the grid at any size (same labels)
   std::atomic<long long> knn_list{0};           // PPK_KNN_LIST: entries of the neighbour-candidate list (0 = sized from n and knn)
   std::atomic<long long> host_parts_rows{16 << 20};   // PPK_HOST_PARTS_ROWS: ... from this many rows up
   std::atomic<long long> host_parts{2};         // PPK_HOST_PARTS: worker threads of a one-device host query (>= 16 Mi rows)
@@ -229,7 +230,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_MST = 14,                          // the minimum spanning forest's ranks, labels and temp storage
        SLOT_NJ = 15,                           // neighbour joining's float64 triangles, row sums and best slots
        SLOT_EMBED = 16,                        // the embedding's sampling weights and prefix, Q32.32 deltas, Eq
-       SLOT_COUNT = 17 };
+       SLOT_DBSCAN = 17,                       // the DBSCAN fit's Boruvka state and sort storage; the labels behind its edge list
+       SLOT_COUNT = 18 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

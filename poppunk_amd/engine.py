@@ -336,6 +336,74 @@ def generate_tuples_dev(assign_t, within_label, self_comparison=True, num_ref=0,
         "ppk_generate_tuples_dev", assign_t.device, cap)
 
 
+def _check_points_tensor(pts_t):
+    torch = _torch()
+    if not (pts_t.is_cuda and pts_t.dtype == torch.float32 and pts_t.is_contiguous() and pts_t.dim() == 2
+            and pts_t.shape[1] == 2):
+        raise TypeError("points must be a C-contiguous float32 [n,2] CUDA tensor")
+
+
+def dbscan_core_dev(pts_t, min_samples):
+    """Squared core distances of scaled training points (ppk_dbscan_core_dev): float64 [n], the
+    min_samples-th smallest squared distance to another point, bit for bit np.partition's of the float64 row."""
+    torch = _torch()
+    _check_points_tensor(pts_t)
+    n = pts_t.shape[0]
+    with torch.cuda.device(pts_t.device):
+        core2 = torch.empty(n, dtype=torch.float64, device=pts_t.device)
+        rc = _lib.lib().ppk_dbscan_core_dev(C.c_void_p(pts_t.data_ptr()), n, int(min_samples),
+                                            C.c_void_p(core2.data_ptr()), _stream_ptr(pts_t.device.index))
+        if rc == _lib.ERR_ARG:
+            raise ValueError(_lib.last_error())
+        _lib.check(rc, "ppk_dbscan_core_dev")
+    return core2
+
+
+def dbscan_mst_dev(pts_t, core2_t):
+    """The minimum spanning tree of the mutual-reachability graph under the total order (mr2, lo, hi)
+    (ppk_dbscan_mst_dev).  Returns (a int32 [n-1], b int32 [n-1], mr2 float64 [n-1]), sorted by that order."""
+    torch = _torch()
+    _check_points_tensor(pts_t)
+    n = pts_t.shape[0]
+    if not (core2_t.is_cuda and core2_t.dtype == torch.float64 and core2_t.is_contiguous() and core2_t.dim() == 1
+            and core2_t.shape[0] == n):
+        raise TypeError("core2 must be a contiguous float64 [n] CUDA tensor")
+    dev = pts_t.device
+    with torch.cuda.device(dev):
+        a = torch.empty(max(n - 1, 1), dtype=torch.int32, device=dev)
+        b = torch.empty(max(n - 1, 1), dtype=torch.int32, device=dev)
+        w = torch.empty(max(n - 1, 1), dtype=torch.float64, device=dev)
+        rc = _lib.lib().ppk_dbscan_mst_dev(C.c_void_p(pts_t.data_ptr()), C.c_void_p(core2_t.data_ptr()), n,
+                                           C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
+                                           C.c_void_p(w.data_ptr()), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_dbscan_mst_dev")
+    return a[:n - 1], b[:n - 1], w[:n - 1]
+
+
+def dbscan_assign_dev(dist_t, handle):
+    """DBSCANFit.assign on a resident float32 [n,2] CUDA tensor with a model handle (ppk_dbscan_create): int32 [n]."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    n = dist_t.shape[0]
+    with torch.cuda.device(dist_t.device):
+        lab = torch.empty(n, dtype=torch.int32, device=dist_t.device)
+        rc = _lib.lib().ppk_dbscan_assign_dev(C.c_void_p(dist_t.data_ptr()), n, handle, C.c_void_p(lab.data_ptr()),
+                                              _stream_ptr(dist_t.device.index))
+        _lib.check(rc, "ppk_dbscan_assign_dev")
+    return lab
+
+
+def dbscan_edges_dev(dist_t, handle, n_ref=0, int_offset=0, cap=None):
+    """Rows assigned the model's within-strain label -> int64 [m,2] edges in generateTuples order (n_ref 0: self)."""
+    _check_dist_tensor(dist_t)
+    n = dist_t.shape[0]
+    if cap is None:
+        cap = min(n, max(1 << 20, n // 8))
+    return _edges_dev(lambda e, c, ne: _lib.lib().ppk_dbscan_edges_dev(
+        C.c_void_p(dist_t.data_ptr()), n, int(n_ref), handle, int(int_offset), C.c_void_p(e.data_ptr()), c,
+        C.c_void_p(ne.data_ptr()), _stream_ptr(dist_t.device.index)), "ppk_dbscan_edges_dev", dist_t.device, cap)
+
+
 def dist_bgmm_edges(ref, qry=None, kmers=None, random_tbl=None, model=None, random_correct=True, q_begin=0,
                     q_end=None, cap=None):
     """Fused kernel 1 + BGMM assignment + compaction (ppk_dist_bgmm_edges_dev).  Returns (edges int64 [n_edges,2]

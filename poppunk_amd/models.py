@@ -17,6 +17,10 @@ boundary, models.py:846-954) is outside the hot path; a fitted boundary is the i
 `BGMMModel` is the same for PopPUNK's default model, a fitted Bayesian Gaussian mixture: the assignment half of
 `BGMMFit` (PopPUNK/models.py:359-375 load, :411-465 assign; PopPUNK/bgmm.py:100-176 log_likelihood) and the
 edge list `construct_network_from_assignments` builds from it.
+
+`DBSCANModel` is PopPUNK's `--fit-model dbscan` (DBSCANFit, PopPUNK/models.py:468-783), fit and assignment: core
+distances, the mutual-reachability spanning tree and the per-row assignment on the device, the hierarchy between
+them on the host (poppunk_amd/dbscan.py).
 """
 import ctypes as C
 
@@ -205,6 +209,275 @@ class BGMMModel:
         """The same as a host int64 [m, 2] array over every device holding a copy of the database; and n_failed."""
         self._check()
         return engine.bgmm_edges_host(refs, qrys, kmers, random_tbl, model=self._model, **kw)
+
+
+# ---- DBSCAN (PopPUNK's --fit-model dbscan) ----------------------------------------------------------------------
+class DBSCANModel:
+    """PopPUNK's HDBSCAN model: `DBSCANFit.fit` / `.assign` / `.save` / `.load` (PopPUNK/models.py:468-783).
+
+      * `fit(X, max_num_clusters, min_cluster_prop, ...)` : subsample, scale, and the reference's loop over
+                                      (min_samples, min_cluster_size) until the within- and between-strain clusters are
+                                      distinct; RuntimeError where the reference exits.  Returns the labels of X.
+      * `fit_dev(dist_t, ...)`      : the same from a resident CUDA matrix (the subsample is gathered on the device)
+      * `assign(X)` / `assign_dev(dist_t)` : int64 labels [n] / int32 CUDA labels [n]
+      * `edges(X, ...)` / `edges_dev(dist_t, ...)` : assign -> generateTuples(y, within_label, ...)
+      * `save(prefix)` / `from_npz(path_or_mapping)` : `<prefix>_fit.npz` with the reference's keys plus this model's
+                                      own state under `ppk_*` keys (allow_pickle=False both ways)
+    The subsample is a seeded `numpy.random.Generator` permutation (the reference's `random.randint` seed cannot be
+    reproduced).  What "a DBSCAN fit" means here is written down in include/ppk.h, section DBSCAN."""
+
+    FORMAT_VERSION = 1
+    _STATE = ("points", "core2", "pt_cluster", "pt_lambda", "cl_parent", "cl_birth", "cl_label", "labels")
+
+    def __init__(self):
+        self.fitted = False
+        self._handles = {}
+        self.assign_points = True
+
+    # -- state ---------------------------------------------------------------------------------------------------
+    def _set_state(self, points, core2, tree, min_samples, min_cluster_size):
+        self.points = np.ascontiguousarray(points, dtype=np.float32)
+        self.core2 = np.ascontiguousarray(core2, dtype=np.float64)
+        self.pt_cluster = np.ascontiguousarray(tree.pt_cluster, dtype=np.int32)
+        self.pt_lambda = np.ascontiguousarray(tree.pt_lambda, dtype=np.float64)
+        self.cl_parent = np.ascontiguousarray(tree.cl_parent, dtype=np.int32)
+        self.cl_birth = np.ascontiguousarray(tree.cl_birth, dtype=np.float64)
+        self.cl_label = np.ascontiguousarray(tree.cl_label, dtype=np.int32)
+        self.labels = np.ascontiguousarray(tree.labels, dtype=np.int32)
+        self.min_samples, self.min_cluster_size = int(min_samples), int(min_cluster_size)
+        self._drop_handles()
+
+    def _drop_handles(self):
+        from . import _lib
+        for h in self._handles.values():
+            _lib.lib().ppk_dbscan_destroy(h)
+        self._handles = {}
+
+    def __del__(self):
+        try:
+            self._drop_handles()
+        except Exception:
+            pass
+
+    def _create(self, scale, within_label, device_id):
+        from . import _lib
+        scale = np.asarray(scale)
+        s64 = np.ascontiguousarray(scale.reshape(2), dtype=np.float64)
+        h = C.c_void_p()
+        f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        rc = _lib.lib().ppk_dbscan_create(
+            self.points.ctypes.data_as(C.POINTER(C.c_float)), self.core2.ctypes.data_as(f64p), self.points.shape[0],
+            self.min_samples, self.pt_cluster.ctypes.data_as(i32p), self.pt_lambda.ctypes.data_as(f64p),
+            self.cl_parent.ctypes.data_as(i32p), self.cl_birth.ctypes.data_as(f64p), self.cl_label.ctypes.data_as(i32p),
+            self.cl_parent.shape[0], s64.ctypes.data_as(f64p), 1 if scale.dtype == np.float64 else 0,
+            int(within_label), int(device_id), C.byref(h))
+        if rc == _lib.ERR_ARG:
+            raise ValueError(_lib.last_error())
+        _lib.check(rc, "ppk_dbscan_create")
+        return h
+
+    def handle(self, device_id=0):
+        """The model on `device_id` as the `ppk_dbscan_*` entry points take it (made on first use)."""
+        self._check()
+        device_id = int(device_id)
+        if device_id not in self._handles:
+            self._handles[device_id] = self._create(self.scale, self.within_label, device_id)
+        return self._handles[device_id]
+
+    def _check(self):
+        if not self.fitted:
+            raise RuntimeError("Trying to assign using an unfitted model")
+
+    # -- fitting -------------------------------------------------------------------------------------------------
+    @staticmethod
+    def subsample_index(n_rows, max_samples, seed):
+        """Rows of the subsample, in the order they are fitted in; None when every row is used."""
+        if n_rows <= max_samples:
+            return None
+        return np.random.default_rng(seed).permutation(n_rows)[:max_samples]
+
+    def _fit_loop(self, sub, tree_of, max_num_clusters, min_cluster_prop, device_id):
+        """models.py:515-600 on the scaled subsample `sub`; tree_of(min_samples) -> (core2, a, b, mr2)."""
+        from . import _lib, dbscan
+        n = sub.shape[0]
+        min_samples = dbscan.min_samples_for(n, min_cluster_prop)
+        min_cluster_size = dbscan.min_cluster_size_for(n)
+        indistinct = True
+        self.fitted = False
+        while dbscan.loop_continues(indistinct, min_samples, min_cluster_size):
+            core2, a, b, mr2 = tree_of(min_samples)
+            tree = dbscan.fit_tree(a, b, mr2, n, min_cluster_size)
+            n_clusters = tree.n_clusters
+            if dbscan.acceptable(n_clusters, max_num_clusters):
+                self._set_state(sub, core2, tree, min_samples, min_cluster_size)
+                self.n_clusters = n_clusters
+                sub64 = sub.astype(np.float64)
+                self.cluster_means = np.stack([sub64[tree.labels == k].mean(axis=0) for k in range(n_clusters)])
+                self.cluster_mins = np.stack([sub64[tree.labels == k].min(axis=0) for k in range(n_clusters)])
+                self.cluster_maxs = np.stack([sub64[tree.labels == k].max(axis=0) for k in range(n_clusters)])
+                # the reference assigns the (already scaled) subsample back through the model, scale (1, 1)
+                h = self._create(np.ones(2, dtype=np.float32), 0, device_id)
+                try:
+                    y = np.empty(n, dtype=np.int32)
+                    _lib.check(_lib.lib().ppk_dbscan_assign(sub.ctypes.data_as(C.POINTER(C.c_float)), n, h,
+                                                            y.ctypes.data_as(C.POINTER(C.c_int32))), "ppk_dbscan_assign")
+                finally:
+                    _lib.lib().ppk_dbscan_destroy(h)
+                self.subsample_labels = y.astype(np.int64)
+                self.within_label = dbscan.findWithinLabel(self.cluster_means, y)
+                try:
+                    self.between_label = dbscan.findBetweenLabel(y, self.within_label)
+                except ValueError:
+                    self.between_label = None
+                indistinct = (self.between_label is None or
+                              dbscan.evaluate_dbscan_clusters(self.cluster_mins, self.cluster_maxs, self.within_label,
+                                                              self.between_label))
+            min_samples, min_cluster_size = dbscan.next_parameters(min_samples, min_cluster_size)
+        if indistinct:
+            raise RuntimeError("Failed to find distinct clusters in this dataset")
+        self.fitted = True
+
+    def fit(self, X, max_num_clusters, min_cluster_prop, max_samples=100000, seed=42, assign_points=True, device_id=0):
+        from . import _lib
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != 2:
+            raise ValueError("X must be [n, 2] (core, accessory)")
+        idx = self.subsample_index(X.shape[0], max_samples, seed)
+        sub = np.array(X if idx is None else X[idx], dtype=np.float32, order="C")
+        self.scale = np.amax(sub, axis=0)
+        if not np.all(np.isfinite(sub)) or not np.all(self.scale > 0):
+            raise ValueError("distances must be finite, with a positive maximum in both columns")
+        sub /= self.scale
+        self.assign_points = bool(assign_points)
+        n = sub.shape[0]
+
+        def tree_of(min_samples):
+            core2 = np.empty(n, dtype=np.float64)
+            a, b = np.empty(n - 1, dtype=np.int32), np.empty(n - 1, dtype=np.int32)
+            mr2 = np.empty(n - 1, dtype=np.float64)
+            f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+            rc = _lib.lib().ppk_dbscan_fit(sub.ctypes.data_as(C.POINTER(C.c_float)), n, int(min_samples),
+                                           int(device_id), core2.ctypes.data_as(f64p), a.ctypes.data_as(i32p),
+                                           b.ctypes.data_as(i32p), mr2.ctypes.data_as(f64p))
+            if rc == _lib.ERR_ARG:
+                raise ValueError(_lib.last_error())
+            _lib.check(rc, "ppk_dbscan_fit")
+            return core2, a, b, mr2
+
+        self._fit_loop(sub, tree_of, max_num_clusters, min_cluster_prop, device_id)
+        return self.assign(X, device_id=device_id) if self.assign_points else self.subsample_labels
+
+    def fit_dev(self, dist_t, max_num_clusters, min_cluster_prop, max_samples=100000, seed=42, assign_points=True):
+        import torch
+        engine._check_dist_tensor(dist_t)
+        idx = self.subsample_index(dist_t.shape[0], max_samples, seed)
+        sub_t = dist_t.clone() if idx is None else dist_t[torch.as_tensor(idx, device=dist_t.device)]
+        scale_t = sub_t.amax(dim=0)
+        self.scale = scale_t.cpu().numpy()
+        if not bool(torch.isfinite(sub_t).all()) or not np.all(self.scale > 0):
+            raise ValueError("distances must be finite, with a positive maximum in both columns")
+        sub_t = (sub_t / scale_t).contiguous()          # IEEE float32 division, as numpy's
+        self.assign_points = bool(assign_points)
+
+        def tree_of(min_samples):
+            core2_t = engine.dbscan_core_dev(sub_t, min_samples)
+            a_t, b_t, w_t = engine.dbscan_mst_dev(sub_t, core2_t)
+            return core2_t.cpu().numpy(), a_t.cpu().numpy(), b_t.cpu().numpy(), w_t.cpu().numpy()
+
+        self._fit_loop(sub_t.cpu().numpy(), tree_of, max_num_clusters, min_cluster_prop, dist_t.device.index)
+        if self.assign_points:
+            return self.assign_dev(dist_t)
+        return torch.as_tensor(self.subsample_labels.astype(np.int32), device=dist_t.device)
+
+    # -- assignment ----------------------------------------------------------------------------------------------
+    def assign(self, X, device_id=0):
+        """models.py:707-783: int64 labels [n] (np.zeros(n, dtype=int))."""
+        from . import _lib
+        self._check()
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != 2:
+            raise ValueError("X must be [n, 2] (core, accessory)")
+        lab = np.empty(X.shape[0], dtype=np.int32)
+        _lib.check(_lib.lib().ppk_dbscan_assign(X.ctypes.data_as(C.POINTER(C.c_float)), X.shape[0],
+                                                self.handle(device_id), lab.ctypes.data_as(C.POINTER(C.c_int32))),
+                   "ppk_dbscan_assign")
+        return lab.astype(np.int64)
+
+    def assign_dev(self, dist_t):
+        self._check()
+        return engine.dbscan_assign_dev(dist_t, self.handle(dist_t.device.index))
+
+    def edges(self, X, self_comparison=True, num_ref=0, int_offset=0, device_id=0):
+        """assign -> generateTuples(assignments, within_label, self, num_ref, int_offset) (network.py:1180-1184)."""
+        y = self.assign(X, device_id=device_id)
+        return poppunk_refine.generateTuples(y, self.within_label, self=self_comparison, num_ref=num_ref,
+                                             int_offset=int_offset)
+
+    def edges_dev(self, dist_t, n_ref=0, int_offset=0, cap=None):
+        """CUDA int64 [m, 2]: the rows assigned within_label, in generateTuples order (n_ref 0: self)."""
+        self._check()
+        return engine.dbscan_edges_dev(dist_t, self.handle(dist_t.device.index), n_ref=n_ref, int_offset=int_offset,
+                                       cap=cap)
+
+    # -- persistence ---------------------------------------------------------------------------------------------
+    def save(self, prefix):
+        """`<prefix>_fit.npz`: DBSCANFit.save's keys (models.py:618-627) and the `ppk_*` arrays.  Returns the path."""
+        if not self.fitted:
+            raise RuntimeError("Trying to save unfitted model")
+        path = str(prefix) + "_fit.npz"
+        np.savez(path, n_clusters=self.n_clusters, within=self.within_label, between=self.between_label,
+                 means=self.cluster_means, maxs=self.cluster_maxs, mins=self.cluster_mins, scale=self.scale,
+                 assign_points=self.assign_points, use_gpu=True,
+                 ppk_format=self.FORMAT_VERSION, ppk_min_samples=self.min_samples,
+                 ppk_min_cluster_size=self.min_cluster_size,
+                 **{"ppk_" + k: getattr(self, k) for k in self._STATE})
+        return path
+
+    @classmethod
+    def from_npz(cls, source):
+        """`source`: a path to `<prefix>_fit.npz` or a mapping of its arrays."""
+        if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__"):
+            with np.load(source, allow_pickle=False) as z:
+                d = {k: z[k] for k in z.files}
+        else:
+            d = dict(source)
+        keys = set(d)
+        if {"intercept", "core_acc_intercepts"} & keys:
+            raise ValueError("this is a refine/threshold fit (RefineFit, models.py:1001-1026): use RefineBoundary")
+        if {"weights", "covariances"} & keys:
+            raise ValueError("this is a BGMM fit (BGMMFit, models.py:359-375): use BGMMModel")
+        missing = [k for k in ("n_clusters", "within", "between", "means", "maxs", "mins", "scale") if k not in keys]
+        if missing:
+            raise ValueError("not a DBSCAN fit: missing %s" % ", ".join(missing))
+        need = ["ppk_format", "ppk_min_samples", "ppk_min_cluster_size"] + ["ppk_" + k for k in cls._STATE]
+        if any(k not in keys for k in need):
+            raise ValueError("this DBSCAN fit was written by PopPUNK: its state is a pickled hdbscan.HDBSCAN object "
+                             "(<prefix>_fit.pkl), which cannot be read without that package and is never unpickled "
+                             "here; fit the database again with DBSCANModel.fit, which saves its own arrays")
+        if int(np.asarray(d["ppk_format"]).item()) != cls.FORMAT_VERSION:
+            raise ValueError("unknown DBSCANModel format version %s" % np.asarray(d["ppk_format"]).item())
+        m = cls()
+
+        class _T:
+            pass
+        t = _T()
+        for k in ("pt_cluster", "pt_lambda", "cl_parent", "cl_birth", "cl_label", "labels"):
+            setattr(t, k, d["ppk_" + k])
+        m._set_state(d["ppk_points"], d["ppk_core2"], t, np.asarray(d["ppk_min_samples"]).item(),
+                     np.asarray(d["ppk_min_cluster_size"]).item())
+        if m.points.ndim != 2 or m.points.shape[1] != 2 or any(
+                getattr(m, k).shape[0] != m.points.shape[0] for k in ("core2", "pt_cluster", "pt_lambda")):
+            raise ValueError("inconsistent ppk_* arrays in the DBSCAN fit")
+        m.n_clusters = int(np.asarray(d["n_clusters"]).item())
+        m.within_label = int(np.asarray(d["within"]).item())
+        m.between_label = int(np.asarray(d["between"]).item())
+        m.cluster_means, m.cluster_maxs, m.cluster_mins = d["means"], d["maxs"], d["mins"]
+        m.scale = np.asarray(d["scale"])
+        if m.scale.dtype not in (np.float32, np.float64):
+            m.scale = m.scale.astype(np.float64)
+        m.assign_points = bool(np.asarray(d["assign_points"]).item()) if "assign_points" in keys else True
+        m.fitted = True
+        return m
 
 
 # ---- the lineage models' neighbour matrices (PopPUNK/models.py:1095-1385) -----------------------------
