@@ -280,7 +280,7 @@ int ppk_qc_edges_dev(const float *d_dist, size_t n_rows, size_t n_ref, int mode,
  * (PopPUNK/models.py:411-465, :138-192; PopPUNK/bgmm.py:100-176) and, for the edge lists, the
  * construct_network_from_assignments -> generateTuples that follows it (PopPUNK/__main__.py:643-652,
  * PopPUNK/network.py:1170-1184; poppunk_assign: PopPUNK/assign.py:600, PopPUNK/network.py:1384,:1425-1433).
- * Fitting the mixture (sklearn, PopPUNK/bgmm.py:20-70) stays with the caller.
+ * Fitting the mixture (PopPUNK/bgmm.py:20-70) is the section "BGMM fit" below.
  * For a row x = (core, accessory):
  *   xs = x / scale                   in the dtype numpy promotes to (models.py:246-254: PopPUNK's scale is float32,
  *                                    so float32 / float32; a float64 scale gives a float64 quotient)
@@ -353,6 +353,143 @@ int ppk_query_bgmm_edges_dbs(const ppk_db *const *refs, const ppk_db *const *qry
  * device_id (BGMMFit.assign(X) of the Python mirror; blocking). */
 int ppk_bgmm_assign(const float *dist, size_t n_rows, const ppk_bgmm *model, int device_id, int32_t *labels,
                     float *resp);
+
+/* ------------------------------------------------------------------------
+ * BGMM fit: PopPUNK's default --fit-model bgmm, BGMMFit.fit -> fit2dMultiGaussian (PopPUNK/models.py:305-338,
+ * PopPUNK/bgmm.py:20-45): sklearn's BayesianGaussianMixture(n_components = K, n_init = 5, covariance_type = 'full',
+ * weight_concentration_prior = 0.1, mean_precision_prior = 0.1, mean_prior = [0, 0]) with its defaults for the rest
+ * (weight_concentration_prior_type = 'dirichlet_process', degrees_of_freedom_prior = 2, reg_covar = 1e-6, tol = 1e-3,
+ * max_iter = 100).  What that computes (variational EM, sklearn/mixture/_bayesian_mixture.py and _base.py, 1.7),
+ * restated; this restatement is the definition here:
+ *   Training rows: xs = float32(x / scale_f32) (the in-place float32 division of ClusterFit.fit, models.py:246-254;
+ *   ppk_bgmm's rule for scale_is_f64 == 0), widened to float64.  Everything below is float64 (sklearn itself would run
+ *   in float32 on float32 input).  n rows, K components, d = 2, eps = 2^-52.
+ *   W0 = np.cov of the training rows (divisor n - 1); m0, beta0, nu0, gamma0 = mean_prior, mean_precision_prior,
+ *   degrees_of_freedom_prior, weight_concentration_prior.
+ *   Statistics of responsibilities r[i][k]:  nk = sum_i r + 10 eps;  xk = sum_i r x / nk;
+ *     sk = sum_i r (x - xk)(x - xk)^T / nk + reg_covar I.
+ *   M-step:
+ *     M1  a_k = 1 + nk,  b_k = gamma0 + (nk_{K-1} + ... + nk_{k+1}), added from the last component down
+ *     M2  beta_k = beta0 + nk,  mean_k = (beta0 m0 + nk xk) / beta_k
+ *     M3  nu_k = nu0 + nk,  cov_k = (W0 + nk (sk + beta0 / beta_k (xk - m0)(xk - m0)^T)) / nu_k
+ *     M4  L_k = chol(cov_k), lower; not positive-definite: the fit is refused (sklearn's ValueError)
+ *     M5  weights_k = a_k / (a_k + b_k) prod_{j<k} b_j / (a_j + b_j), then divided by their sum (stick-breaking)
+ *   E-step, per row:  z = L_k^-1 (xs - mean_k),  with psi = digamma
+ *     E[log w_k] = psi(a_k) - psi(a_k + b_k) + sum_{j<k} (psi(b_j) - psi(a_j + b_j))
+ *     w_k = E[log w_k] - 0.5 (d log 2pi + |z|^2) - sum log diag L_k - 0.5 d log nu_k
+ *           + 0.5 (d log 2 + psi(nu_k / 2) + psi((nu_k - 1) / 2) - d / beta_k)
+ *     log r_k = w_k - logsumexp_k w_k (max + log sum exp(w - max)),  r_k = exp(log r_k)
+ *   Lower bound (sklearn's, without the constant terms), from the NEW parameters and the E-step's log r:
+ *     B   c_k = -sum log diag L_k - 0.5 d log nu_k
+ *         bound = - sum_ik r log r + sum_k (nu_k c_k + nu_k d/2 log 2 + lgamma(nu_k / 2) + lgamma((nu_k - 1) / 2))
+ *                 + sum_k betaln(a_k, b_k) - 0.5 d sum_k log beta_k
+ *   Initialisation: the M-step of one-hot responsibilities (labels).  Then per iteration E-step -> M-step -> bound;
+ *   stop when |bound - previous bound| < tol (the previous bound of the first iteration is -inf) or after max_iter
+ *   iterations; of n_init runs the one with the greatest bound, the first on ties, converged or not.
+ *   covariances are cov_k: already divided by the degrees of freedom, as sklearn's covariances_.
+ * The labels of a run are given (init_labels: one run), or come from
+ *   [EXT] this library's own initialisation, which stands where sklearn draws k-means from numpy's global random
+ *   [EXT] state (not reproducible): Lloyd's iterations on the device from K given centres per run -- pass t labels
+ *   [EXT] every training row with its nearest centre under (d2, index of centre), d2 = dx dx + dy dy in IEEE double
+ *   [EXT] with nothing fused, and moves every centre to the mean of its rows (an emptied centre keeps its place); the
+ *   [EXT] iterations stop after the first pass in which no label changed, or after PPK_BGMM_KMEANS_MAX_ITER passes;
+ *   [EXT] the labels of the last pass initialise the run.  The centres of run r are drawn by the caller (the Python
+ *   [EXT] package: k-means++ with numpy.random.default_rng(seed + r) on a bounded sample, poppunk_amd/bgmm.py).
+ * On the device one pass (ppk_bgmm_stats_dev) evaluates the E-step and returns, per component, the seven sums
+ *   S r, S r dx, S r dy, S r dx dx, S r dx dy, S r dy dy, S r log r     with (dx, dy) = xs - pivot_k,
+ * the pivot being the component's current mean; the host finishes nk = S r + 10 eps, m = S r d / nk, xk = pivot + m,
+ * sk = S r d d^T / nk - m m^T (2 - S r / nk) + reg_covar I, which is the centred form above exactly in exact
+ * arithmetic (raw moments about 0 would cancel), then M1-M5 and B.  The sums are added in a fixed order (no
+ * floating-point atomics, a grid that depends on the row count only): the same rows give the same bits on every call,
+ * whether they are a whole matrix or named by an index list inside a larger one. */
+#define PPK_BGMM_FIT_STATS 7
+#define PPK_BGMM_FIT_MAX_ITER 1024
+#define PPK_BGMM_FIT_MAX_INIT 32
+#define PPK_BGMM_KMEANS_MAX_ITER 50
+typedef struct ppk_bgmm_fit_params {
+  int K;                                /* components, 1 .. PPK_BGMM_MAX_K */
+  int max_iter;                         /* 0 .. PPK_BGMM_FIT_MAX_ITER; 0 returns the state after initialisation */
+  int n_init;                           /* runs when centres are given, 1 .. PPK_BGMM_FIT_MAX_INIT */
+  int reserved;
+  double weight_concentration_prior;    /* gamma0 */
+  double mean_precision_prior;          /* beta0 */
+  double mean_prior[2];                 /* m0 */
+  double degrees_of_freedom_prior;      /* nu0 > 1 */
+  double reg_covar;
+  double tol;
+} ppk_bgmm_fit_params;
+/* fit2dMultiGaussian's values: {K, 100, 5, 0.1, 0.1, (0, 0), 2, 1e-6, 1e-3}. */
+int ppk_bgmm_fit_params_default(int K, ppk_bgmm_fit_params *out);
+
+/* The variational state after an M-step, and what the next E-step evaluates from it. */
+typedef struct ppk_bgmm_state {
+  int K;
+  int reserved;
+  double weight_conc_a[PPK_BGMM_MAX_K], weight_conc_b[PPK_BGMM_MAX_K];   /* sklearn's weight_concentration_ */
+  double mean_precision[PPK_BGMM_MAX_K];
+  double means[PPK_BGMM_MAX_K][2];
+  double dof[PPK_BGMM_MAX_K];                 /* degrees_of_freedom_ */
+  double covariances[PPK_BGMM_MAX_K][4];      /* covariances_, row-major 2 x 2 */
+  double chol[PPK_BGMM_MAX_K][3];             /* L00, L10, L11 */
+  double weights[PPK_BGMM_MAX_K];
+  double lin[PPK_BGMM_MAX_K][5];              /* z = L^-1 (xs - mean) as fused multiply-adds: ppk_bgmm::lin */
+  double log_const[PPK_BGMM_MAX_K];           /* w_k + 0.5 |z|^2 */
+} ppk_bgmm_state;
+
+typedef struct ppk_bgmm_fit_result {
+  ppk_bgmm_state state;                 /* of the best run */
+  int n_iter, converged;                /* of the best run */
+  int best_init, n_init_run;            /* which run won; how many were made */
+  unsigned long long n_train;
+  double lower_bound;                   /* -inf when max_iter = 0 */
+  double cov_prior[4];                  /* W0 */
+  double train_mean[2];
+  double init_lower_bound[PPK_BGMM_FIT_MAX_INIT];
+  int init_n_iter[PPK_BGMM_FIT_MAX_INIT];
+  int kmeans_iter[PPK_BGMM_FIT_MAX_INIT];     /* passes of the own initialisation (0 with given labels) */
+  double lower_bounds[PPK_BGMM_FIT_MAX_ITER]; /* the best run's bound after each of its n_iter iterations */
+} ppk_bgmm_fit_result;
+
+/* out = {sizeof(ppk_bgmm_fit_params), sizeof(ppk_bgmm_state), sizeof(ppk_bgmm_fit_result)} as this library was built:
+ * a binding checks its own layouts against them. */
+int ppk_bgmm_fit_struct_sizes(size_t out[3]);
+
+/* digamma(x) for x > 0 (NaN otherwise): the recurrence up to x >= 10, then the asymptotic series.  Host only. */
+double ppk_bgmm_digamma(double x);
+
+/* The M-step and the bound from one pass's sums: stats double [K][PPK_BGMM_FIT_STATS] about pivot double [K][2],
+ * cov_prior double [4].  lower_bound_out nullable.  Host only, no device is touched.  PPK_ERR_ARG for params outside
+ * their ranges, a non-finite sum, or a covariance that lost positive-definiteness (M4). */
+int ppk_bgmm_mstep(const ppk_bgmm_fit_params *params, const double *stats, const double *pivot,
+                   const double *cov_prior, ppk_bgmm_state *state_out, double *lower_bound_out);
+
+/* One E-step + statistics pass over the training rows of a resident [n_rows][2] float32 matrix: all of them
+ * (d_index NULL), or the n_index rows an int64 device list names, in its order (an entry outside [0, n_rows) is a
+ * precondition violation: it contributes nothing and nothing is read out of bounds).  scale float [2] (host).
+ * d_stats double [K][PPK_BGMM_FIT_STATS] about pivot = state->means.  No synchronisation. */
+int ppk_bgmm_stats_dev(const float *d_rows, size_t n_rows, const long long *d_index, size_t n_index,
+                       const float *scale, const ppk_bgmm_state *state, double *d_stats, void *stream);
+
+/* One pass of the own initialisation: d_labels int32 [n] is read and rewritten with the nearest of centres double
+ * [K][2] (host); *d_changed (device) = how many labels changed; d_stats as above with r = the one-hot labels and
+ * pivot = centres (new centre = centre + S r d / S r).  No synchronisation. */
+int ppk_bgmm_kmeans_dev(const float *d_rows, size_t n_rows, const long long *d_index, size_t n_index,
+                        const float *scale, int K, const double *centres, int32_t *d_labels, double *d_stats,
+                        unsigned *d_changed, void *stream);
+
+/* The fit.  Exactly one of d_init_labels (device int32 per training row: one run) and init_centres (host double
+ * [params->n_init][K][2]: the own initialisation, one run per set) is given.  Synchronises the stream once per pass
+ * (the sums are needed on the host for the stop test).  PPK_ERR_ARG, the message naming the cause: K outside
+ * [1, PPK_BGMM_MAX_K], fewer than 2 training rows or fewer than K, a label outside [0, K), a non-finite row (the first
+ * is named), an index outside the matrix, a non-positive scale, a covariance that lost positive-definiteness. */
+int ppk_bgmm_fit_dev(const float *d_rows, size_t n_rows, const long long *d_index, size_t n_index, const float *scale,
+                     const int32_t *d_init_labels, const double *init_centres, const ppk_bgmm_fit_params *params,
+                     ppk_bgmm_fit_result *result, void *stream);
+/* Host arrays, on device_id; blocking.  The training rows are uploaded in the order of the index list, so the result
+ * equals ppk_bgmm_fit_dev's through the same list bit for bit. */
+int ppk_bgmm_fit(const float *rows, size_t n_rows, const long long *index, size_t n_index, const float *scale,
+                 const int32_t *init_labels, const double *init_centres, const ppk_bgmm_fit_params *params,
+                 int device_id, ppk_bgmm_fit_result *result);
 
 /* ------------------------------------------------------------------------
  * DBSCAN: fitting and assigning PopPUNK's --fit-model dbscan (HDBSCAN; DBSCANFit, PopPUNK/models.py:468-783,

@@ -33,7 +33,38 @@ class Bgmm(C.Structure):
                 ("jitter", C.c_int * BGMM_MAX_K)]
 
 
+BGMM_FIT_STATS, BGMM_FIT_MAX_ITER, BGMM_FIT_MAX_INIT, BGMM_KMEANS_MAX_ITER = 7, 1024, 32, 50
+
+
+class BgmmFitParams(C.Structure):
+    """struct ppk_bgmm_fit_params (include/ppk.h, "BGMM fit"); ppk_bgmm_fit_params_default fills it."""
+    _fields_ = [("K", C.c_int), ("max_iter", C.c_int), ("n_init", C.c_int), ("reserved", C.c_int),
+                ("weight_concentration_prior", C.c_double), ("mean_precision_prior", C.c_double),
+                ("mean_prior", C.c_double * 2), ("degrees_of_freedom_prior", C.c_double), ("reg_covar", C.c_double),
+                ("tol", C.c_double)]
+
+
+class BgmmState(C.Structure):
+    """struct ppk_bgmm_state: the variational state after an M-step (ppk_bgmm_mstep fills it)."""
+    _fields_ = [("K", C.c_int), ("reserved", C.c_int),
+                ("weight_conc_a", C.c_double * BGMM_MAX_K), ("weight_conc_b", C.c_double * BGMM_MAX_K),
+                ("mean_precision", C.c_double * BGMM_MAX_K), ("means", (C.c_double * 2) * BGMM_MAX_K),
+                ("dof", C.c_double * BGMM_MAX_K), ("covariances", (C.c_double * 4) * BGMM_MAX_K),
+                ("chol", (C.c_double * 3) * BGMM_MAX_K), ("weights", C.c_double * BGMM_MAX_K),
+                ("lin", (C.c_double * 5) * BGMM_MAX_K), ("log_const", C.c_double * BGMM_MAX_K)]
+
+
+class BgmmFitResult(C.Structure):
+    """struct ppk_bgmm_fit_result."""
+    _fields_ = [("state", BgmmState), ("n_iter", C.c_int), ("converged", C.c_int), ("best_init", C.c_int),
+                ("n_init_run", C.c_int), ("n_train", C.c_ulonglong), ("lower_bound", C.c_double),
+                ("cov_prior", C.c_double * 4), ("train_mean", C.c_double * 2),
+                ("init_lower_bound", C.c_double * BGMM_FIT_MAX_INIT), ("init_n_iter", C.c_int * BGMM_FIT_MAX_INIT),
+                ("kmeans_iter", C.c_int * BGMM_FIT_MAX_INIT), ("lower_bounds", C.c_double * BGMM_FIT_MAX_ITER)]
+
+
 _bgmmp, _f64p = C.POINTER(Bgmm), C.POINTER(C.c_double)
+_fitpp, _statep, _fitrp = C.POINTER(BgmmFitParams), C.POINTER(BgmmState), C.POINTER(BgmmFitResult)
 
 SIGNATURES = {
     "ppk_bgmm_prepare": (C.c_int, [C.c_int, _f64p, _f64p, _f64p, _f64p, C.c_int, C.c_int, _bgmmp]),
@@ -44,6 +75,14 @@ SIGNATURES = {
     "ppk_query_bgmm_edges_dbs": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.c_int, _i32p, _f32p, _sz, C.c_int,
                                            _bgmmp, _llp, _sz, _szp, _ullp]),
     "ppk_bgmm_assign": (C.c_int, [_f32p, _sz, _bgmmp, C.c_int, _i32p, _f32p]),
+    "ppk_bgmm_fit_params_default": (C.c_int, [C.c_int, _fitpp]),
+    "ppk_bgmm_fit_struct_sizes": (C.c_int, [_szp]),
+    "ppk_bgmm_digamma": (C.c_double, [C.c_double]),
+    "ppk_bgmm_mstep": (C.c_int, [_fitpp, _f64p, _f64p, _f64p, _statep, _f64p]),
+    "ppk_bgmm_stats_dev": (C.c_int, [_vp, _sz, _vp, _sz, _f32p, _statep, _vp, _vp]),
+    "ppk_bgmm_kmeans_dev": (C.c_int, [_vp, _sz, _vp, _sz, _f32p, C.c_int, _f64p, _vp, _vp, _vp, _vp]),
+    "ppk_bgmm_fit_dev": (C.c_int, [_vp, _sz, _vp, _sz, _f32p, _vp, _f64p, _fitpp, _fitrp, _vp]),
+    "ppk_bgmm_fit": (C.c_int, [_f32p, _sz, _llp, _sz, _f32p, _i32p, _f64p, _fitpp, C.c_int, _fitrp]),
     "ppk_network_sweep_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, C.c_longlong, _vp, _vp, _vp]),
     "ppk_network_sweep": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, C.c_longlong, _llp, _i32p]),
     "ppk_network_summary_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, C.c_longlong, _vp, _vp, _vp, _vp, _vp]),
@@ -240,7 +279,7 @@ def sources_hash_now():
     here = os.path.join(_HERE, "csrc")
     names = ["ppk_api.hip", "ppk_host.hip", "ppk_dist.hip", "ppk_boundary.hip", "ppk_iterate.hip", "ppk_square.hip",
              "ppk_sparse.hip", "ppk_bgmm.hip", "ppk_network.hip", "ppk_mst.hip", "ppk_nj.hip", "ppk_embed.hip",
-             "ppk_dbscan.hip", "ppk_h5.cpp",
+             "ppk_dbscan.hip", "ppk_bgmm_fit.hip", "ppk_h5.cpp",
              "ppk_internal.h",
              "ppk_block_asm.inc", "../../include/ppk.h"]
     h = hashlib.sha256()

@@ -231,7 +231,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_NJ = 15,                           // neighbour joining's float64 triangles, row sums and best slots
        SLOT_EMBED = 16,                        // the embedding's sampling weights and prefix, Q32.32 deltas, Eq
        SLOT_DBSCAN = 17,                       // the DBSCAN fit's Boruvka state and sort storage; the labels behind its edge list
-       SLOT_COUNT = 18 };
+       SLOT_BGMM_FIT = 18,                     // the BGMM fit's per-workgroup partial sums, its sums, counters and k-means labels
+       SLOT_COUNT = 19 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

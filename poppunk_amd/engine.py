@@ -322,6 +322,142 @@ def bgmm_edges_dev(dist_t, model, n_ref=0, int_offset=0, cap=None):
         C.c_void_p(ne.data_ptr()), _stream_ptr(dist_t.device.index)), "ppk_bgmm_edges_dev", dist_t.device, cap)
 
 
+# ---- BGMM fit (include/ppk.h "BGMM fit") --------------------------------------------------------
+def bgmm_fit_params(K, **overrides):
+    """`_lib.BgmmFitParams` with fit2dMultiGaussian's values (PopPUNK/bgmm.py:38-43); keyword arguments replace
+    fields (`mean_prior` a pair).  ValueError for values outside their ranges (K outside [1, 16], ...)."""
+    p = _lib.BgmmFitParams()
+    rc = _lib.lib().ppk_bgmm_fit_params_default(int(K), C.byref(p))
+    if rc == _lib.ERR_ARG:
+        raise ValueError(_lib.last_error())
+    _lib.check(rc, "ppk_bgmm_fit_params_default")
+    for k, v in overrides.items():
+        if k == "mean_prior":
+            p.mean_prior[0], p.mean_prior[1] = float(v[0]), float(v[1])
+        elif k in ("max_iter", "n_init"):
+            setattr(p, k, int(v))
+        elif k in ("weight_concentration_prior", "mean_precision_prior", "degrees_of_freedom_prior", "reg_covar", "tol"):
+            setattr(p, k, float(v))
+        else:
+            raise TypeError("unknown BGMM fit parameter %r" % k)
+    return p
+
+
+def _fit_scale(scale):
+    s = np.ascontiguousarray(np.asarray(scale, dtype=np.float32).reshape(2))
+    return s, s.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _check_index_tensor(index_t, dist_t):
+    torch = _torch()
+    if index_t is None:
+        return None, 0
+    if not (index_t.is_cuda and index_t.dtype == torch.int64 and index_t.is_contiguous() and index_t.dim() == 1
+            and index_t.device == dist_t.device):
+        raise TypeError("index must be a contiguous int64 [m] CUDA tensor on the matrix's device")
+    return C.c_void_p(index_t.data_ptr()), index_t.shape[0]
+
+
+def _fit_check(rc, what):
+    if rc == _lib.ERR_ARG:
+        raise ValueError(_lib.last_error())
+    _lib.check(rc, what)
+
+
+def bgmm_stats_dev(dist_t, state, scale, index_t=None):
+    """One E-step + statistics pass (ppk_bgmm_stats_dev) from a `_lib.BgmmState`: float64 CUDA [K, 7], per component
+    S r, S r dx, S r dy, S r dx dx, S r dx dy, S r dy dy, S r log r about the state's means."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    ip, ni = _check_index_tensor(index_t, dist_t)
+    s, sp = _fit_scale(scale)
+    with torch.cuda.device(dist_t.device):
+        out = torch.empty((state.K, _lib.BGMM_FIT_STATS), dtype=torch.float64, device=dist_t.device)
+        _fit_check(_lib.lib().ppk_bgmm_stats_dev(C.c_void_p(dist_t.data_ptr()), dist_t.shape[0], ip, ni, sp,
+                                                 C.byref(state), C.c_void_p(out.data_ptr()),
+                                                 _stream_ptr(dist_t.device.index)), "ppk_bgmm_stats_dev")
+    return out
+
+
+def bgmm_kmeans_dev(dist_t, centres, scale, labels_t, index_t=None):
+    """One pass of the own initialisation (ppk_bgmm_kmeans_dev): `labels_t` (int32 CUDA, one per training row) is
+    rewritten with the nearest of `centres` [K, 2]; returns (sums float64 CUDA [K, 7] about the centres, number of
+    labels that changed as an int32 CUDA tensor [1])."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    ip, ni = _check_index_tensor(index_t, dist_t)
+    n = ni if index_t is not None else dist_t.shape[0]
+    if not (labels_t.is_cuda and labels_t.dtype == torch.int32 and labels_t.is_contiguous() and labels_t.shape == (n,)):
+        raise TypeError("labels must be a contiguous int32 CUDA tensor with one entry per training row")
+    c = np.ascontiguousarray(centres, dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != 2:
+        raise ValueError("centres must be [K, 2]")
+    s, sp = _fit_scale(scale)
+    with torch.cuda.device(dist_t.device):
+        out = torch.empty((c.shape[0], _lib.BGMM_FIT_STATS), dtype=torch.float64, device=dist_t.device)
+        changed = torch.zeros(1, dtype=torch.int32, device=dist_t.device)
+        _fit_check(_lib.lib().ppk_bgmm_kmeans_dev(C.c_void_p(dist_t.data_ptr()), dist_t.shape[0], ip, ni, sp, c.shape[0],
+                                                  c.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  C.c_void_p(labels_t.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(changed.data_ptr()), _stream_ptr(dist_t.device.index)),
+                   "ppk_bgmm_kmeans_dev")
+    return out, changed
+
+
+def _fit_centres(init_centres, params):
+    if init_centres is None:
+        return None, None
+    c = np.ascontiguousarray(init_centres, dtype=np.float64)
+    if c.shape != (params.n_init, params.K, 2):
+        raise ValueError("init_centres must be [n_init, K, 2]")
+    return c, c.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def bgmm_fit_dev(dist_t, scale, params, index_t=None, init_labels_t=None, init_centres=None):
+    """The fit on a resident float32 [n, 2] CUDA matrix (ppk_bgmm_fit_dev): every row, or the rows `index_t` names.
+    Exactly one of `init_labels_t` (int32 CUDA, one per training row) and `init_centres` ([n_init, K, 2]).  Returns a
+    `bgmm.FitResult`; ValueError for what the header lists as PPK_ERR_ARG."""
+    from . import bgmm
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    ip, ni = _check_index_tensor(index_t, dist_t)
+    n = ni if index_t is not None else dist_t.shape[0]
+    if init_labels_t is not None and not (init_labels_t.is_cuda and init_labels_t.dtype == torch.int32
+                                          and init_labels_t.is_contiguous() and init_labels_t.shape == (n,)):
+        raise TypeError("init_labels must be a contiguous int32 CUDA tensor with one entry per training row")
+    c, cp = _fit_centres(init_centres, params)
+    s, sp = _fit_scale(scale)
+    res = _lib.BgmmFitResult()
+    with torch.cuda.device(dist_t.device):
+        _fit_check(_lib.lib().ppk_bgmm_fit_dev(C.c_void_p(dist_t.data_ptr()), dist_t.shape[0], ip, ni, sp,
+                                               C.c_void_p(init_labels_t.data_ptr()) if init_labels_t is not None else None,
+                                               cp, C.byref(params), C.byref(res), _stream_ptr(dist_t.device.index)),
+                   "ppk_bgmm_fit_dev")
+    return bgmm.FitResult(res)
+
+
+def bgmm_fit(X, scale, params, index=None, init_labels=None, init_centres=None, device_id=0):
+    """The same from host arrays (ppk_bgmm_fit; blocking): X float32 [n, 2], `index` int64 positions or None."""
+    from . import bgmm
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    if X.ndim != 2 or X.shape[1] != 2:
+        raise ValueError("X must be [n, 2] (core, accessory)")
+    idx = None if index is None else np.ascontiguousarray(index, dtype=np.int64)
+    lab = None if init_labels is None else np.ascontiguousarray(init_labels, dtype=np.int32)
+    n = X.shape[0] if idx is None else idx.shape[0]
+    if lab is not None and lab.shape != (n,):
+        raise ValueError("init_labels must have one entry per training row")
+    c, cp = _fit_centres(init_centres, params)
+    s, sp = _fit_scale(scale)
+    res = _lib.BgmmFitResult()
+    _fit_check(_lib.lib().ppk_bgmm_fit(X.ctypes.data_as(C.POINTER(C.c_float)), X.shape[0],
+                                       idx.ctypes.data_as(C.POINTER(C.c_longlong)) if idx is not None else None,
+                                       0 if idx is None else idx.shape[0], sp,
+                                       lab.ctypes.data_as(C.POINTER(C.c_int32)) if lab is not None else None, cp,
+                                       C.byref(params), int(device_id), C.byref(res)), "ppk_bgmm_fit")
+    return bgmm.FitResult(res)
+
+
 def generate_tuples_dev(assign_t, within_label, self_comparison=True, num_ref=0, int_offset=0, cap=None):
     """poppunk_refine.generateTuples on a resident int32 [n] CUDA tensor -> int64 [m,2]."""
     torch = _torch()

@@ -104,8 +104,14 @@ class RefineBoundary:
 
 # ---- BGMM assignment (PopPUNK's default --fit-model bgmm) -----------------------------------------------
 class BGMMModel:
-    """A fitted BGMM model (the state `BGMMFit.assign` reads), assignment only: fitting stays with sklearn.
+    """PopPUNK's default model, a Bayesian Gaussian mixture: `BGMMFit.fit` / `.assign` / `.save` / `.load`
+    (PopPUNK/models.py:296-465).  The constructor takes fitted arrays (the state `BGMMFit.assign` reads).
 
+      * `fit(X, max_components, ...)` / `fit_dev(dist_t, max_components, ...)` : class methods returning a fitted
+                                      model: subsample, scale, the variational fit on the device (include/ppk.h
+                                      "BGMM fit"), assignment, within / between labels.  `max_samples=None` fits on
+                                      every row.  `fit_info` and `labels` describe the fit.
+      * `save(prefix)`              : `<prefix>/<basename>_fit.npz` with `BGMMFit.save`'s keys (models.py:341-352)
       * `from_npz(path_or_mapping)` : the arrays `BGMMFit.load` reads from `<prefix>_fit.npz` (models.py:359-375);
                                       the `_fit.pkl` is never opened (unpickling needs sklearn and runs code)
       * `assign(X, values=False)`   : `BGMMFit.assign` (models.py:411-465) through ppk_bgmm_assign: int64 labels, or
@@ -141,6 +147,121 @@ class BGMMModel:
             raise ValueError(_lib.last_error())
         _lib.check(rc, "ppk_bgmm_prepare")
         self.fitted = True
+        self.fit_info = None        # set by fit / fit_dev
+        self.fit_result = None
+        self.labels = None
+        self.assign_points = True
+
+    # -- fitting -------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _fit_inputs(n_rows, max_components, max_samples, seed, n_init, init_labels):
+        params = engine.bgmm_fit_params(max_components, n_init=1 if init_labels is not None else n_init)
+        idx = None if max_samples is None else DBSCANModel.subsample_index(n_rows, max_samples, seed)
+        return params, idx
+
+    @classmethod
+    def _fitted(cls, res, scale, seed, init, assign_points, labels_of):
+        """The model of a `bgmm.FitResult`: BGMMFit.fit after fit2dMultiGaussian (models.py:326-338).
+        labels_of(model) -> (the labels, the number of rows per label)."""
+        from . import bgmm
+        model = cls(res.weights, res.means, res.covariances, scale, 0)
+        y, counts = labels_of(model)
+        model = cls(res.weights, res.means, res.covariances, scale, bgmm.within_from_counts(res.means, counts),
+                    bgmm.between_from_counts(counts))
+        model.labels = y
+        model.fit_result, model.assign_points, model.seed = res, bool(assign_points), int(seed)
+        model.fit_info = {"n_iter": res.n_iter, "converged": res.converged, "lower_bound": res.lower_bound,
+                          "lower_bounds": res.lower_bounds, "n_train": res.n_train, "init": init,
+                          "best_init": res.best_init, "init_lower_bounds": res.init_lower_bounds,
+                          "kmeans_iter": res.kmeans_iter}
+        return model
+
+    @classmethod
+    def fit(cls, X, max_components, max_samples=100000, seed=42, assign_points=True, device_id=0, init_labels=None,
+            n_init=5):
+        """`BGMMFit.fit` (models.py:305-338) from a host matrix; returns the fitted model, whose `labels` are the
+        int64 assignments of X (`assign_points`) or of the subsample.  More rows than `max_samples`: a seeded
+        subsample (`DBSCANModel.subsample_index`); `max_samples=None`: every row.  scale = np.amax of the training
+        rows.  `init_labels` (one per training row) replaces the own initialisation (one run); otherwise `n_init`
+        runs from k-means++ centres drawn with seeds seed, seed + 1, ... (poppunk_amd/bgmm.py)."""
+        from . import bgmm
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != 2:
+            raise ValueError("X must be [n, 2] (core, accessory)")
+        params, idx = cls._fit_inputs(X.shape[0], max_components, max_samples, seed, n_init, init_labels)
+        sub = X if idx is None else X[idx]
+        if sub.shape[0] < 1:
+            raise ValueError("no rows to fit")
+        scale = np.amax(sub, axis=0)
+        centres = None
+        if init_labels is None:
+            centres = bgmm.initial_centres(lambda pos: sub if pos is None else sub[pos], sub.shape[0], scale,
+                                           params.K, seed, params.n_init)
+        res = engine.bgmm_fit(X, scale, params, index=idx, init_labels=init_labels, init_centres=centres,
+                              device_id=device_id)
+
+        def labels_of(model):
+            y = model.assign(X if assign_points else sub, device_id=device_id)
+            return y, np.bincount(y, minlength=params.K)
+        return cls._fitted(res, scale, seed, "labels" if init_labels is not None else "kmeans++", assign_points,
+                           labels_of)
+
+    @classmethod
+    def fit_dev(cls, dist_t, max_components, max_samples=100000, seed=42, assign_points=True, init_labels=None,
+                n_init=5):
+        """The same from a resident CUDA matrix: the training rows are read where they are (through the subsample's
+        index list, or all of them); besides the sums of each pass, only the scale and the k-means++ draw's rows (at
+        most 4 096 per run) come to the host.  `labels` is an int32 CUDA tensor."""
+        from . import bgmm
+        import torch
+        engine._check_dist_tensor(dist_t)
+        params, idx = cls._fit_inputs(dist_t.shape[0], max_components, max_samples, seed, n_init, init_labels)
+        dev = dist_t.device
+        idx_t = None if idx is None else torch.as_tensor(idx, device=dev)
+        n_train = dist_t.shape[0] if idx is None else idx.shape[0]
+        if n_train < 1:
+            raise ValueError("no rows to fit")
+        scale = (dist_t if idx_t is None else dist_t[idx_t]).amax(dim=0).cpu().numpy()
+
+        def fetch(pos):
+            if pos is None:
+                return (dist_t if idx_t is None else dist_t[idx_t]).cpu().numpy()
+            at = torch.as_tensor(pos if idx is None else idx[pos], device=dev)
+            return dist_t[at].cpu().numpy()
+        centres, lab_t = None, None
+        if init_labels is None:
+            centres = bgmm.initial_centres(fetch, n_train, scale, params.K, seed, params.n_init)
+        else:
+            lab_t = torch.as_tensor(np.ascontiguousarray(init_labels, dtype=np.int32), device=dev)
+        res = engine.bgmm_fit_dev(dist_t, scale, params, index_t=idx_t, init_labels_t=lab_t, init_centres=centres)
+        rows_t = dist_t if (assign_points or idx_t is None) else dist_t[idx_t].contiguous()
+
+        def labels_of(model):
+            y = model.assign_dev(rows_t)
+            return y, torch.bincount(y, minlength=params.K).cpu().numpy()
+        return cls._fitted(res, scale, seed, "labels" if init_labels is not None else "kmeans++", assign_points,
+                           labels_of)
+
+    def save(self, prefix):
+        """`<prefix>/<basename>_fit.npz` with exactly `BGMMFit.save`'s keys (models.py:341-352: weights, means,
+        covariances, within, between, scale), which `from_npz` and PopPUNK's `BGMMFit.load` read, plus -- for a model
+        fitted here -- the variational state, `n_iter`, `lower_bound` and `seed` under `ppk_*` keys.  No `_fit.pkl`
+        is written: the reference's holds a pickled sklearn object.  Returns the path."""
+        import os
+        self._check()
+        prefix = str(prefix)
+        os.makedirs(prefix, exist_ok=True)
+        path = os.path.join(prefix, os.path.basename(os.path.normpath(prefix)) + "_fit.npz")
+        extra = {}
+        if self.fit_result is not None:
+            r = self.fit_result
+            extra = {"ppk_weight_concentration": r.weight_concentration, "ppk_mean_precision": r.mean_precision,
+                     "ppk_degrees_of_freedom": r.degrees_of_freedom, "ppk_n_iter": r.n_iter,
+                     "ppk_converged": r.converged, "ppk_lower_bound": r.lower_bound,
+                     "ppk_lower_bounds": r.lower_bounds, "ppk_n_train": r.n_train, "ppk_seed": self.seed}
+        np.savez(path, weights=self.weights, means=self.means, covariances=self.covariances, within=self.within_label,
+                 between=self.between_label if self.between_label is not None else -1, scale=self.scale, **extra)
+        return path
 
     @classmethod
     def from_npz(cls, source):
