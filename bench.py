@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the distance hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it sets up, warms up, times the K steps, writes
+--dump-outputs if asked and prints the line.  Every other measurement below (the CPU baseline, the host and file
+calls, the other configurations, kernel 2, the (f) rows, config 5, rank 0's solo legs at N > 1) runs only with
+`--full`, after the same timed steps; without it those keys are on the line as null.
 
 A "step" is one pass of kernel 1 over the whole synthetic database: all
 self-vs-self core/accessory distances, sketches already resident in HBM,
@@ -22,6 +27,7 @@ output [n_pairs, 2] float32 in PopPUNK row order on rank 0.
 Rank 0 prints ONE JSON line (see the driver contract) carrying
   `roofline`     the dominant kernel, HIP-event timed inside libppk_hip.so on its own stream,
                  against the integer-VALU roof that binds it (and, for reference, the HBM figures);
+and, with `--full`,
   `cpu_baseline` the oracle, timed on this host on a bounded sample (N = 1 only);
   `host_call`    the PCIe-inclusive call PopPUNK itself makes (never `value`); N > 1: as
                  `multi_gpu.host_call`, ONE process driving all N GPUs (a worker thread per device);
@@ -36,7 +42,7 @@ Rank 0 prints ONE JSON line (see the driver contract) carrying
   `f_rows`       (N = 1) SURVEY 8(f) on the resident 10 000-genome matrix: thresholdIterate1D / 2D with the
                  library's stage split, neighbours from the tiles and from the square matrix, long <-> square,
                  qcDistMat's two edge lists -- each with a byte (or lane-op) model and the fraction it implies.
-N > 1: the two legs that need NO process group -- `multi_gpu.host_call` and `config5.host_call`, one process
+N > 1 with `--full`: the two legs that need NO process group -- `multi_gpu.host_call` and `config5.host_call`, one process
 driving all N GPUs -- run on rank 0 BEFORE torch.distributed is initialised (the other ranks wait on a file),
 so a process group that never forms cannot lose them.
 """
@@ -75,15 +81,22 @@ def parse():
                     help="N > 1: grow the database to genomes*sqrt(N) (constant pairs per GPU) instead "
                          "of the default strong scaling on the same genomes")
     ap.add_argument("--strong", action="store_true", help="(default; kept for compatibility)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (N > 1: rank 0's solo legs before them), also run every other leg of the "
+                         "line: cpu_baseline, host_call, file_call, config2 / config4 / default_sketch / wide_k / "
+                         "latency / kernel2 / f_rows and config5.  Off by default: a plain run sets up, warms up, times "
+                         "the steps and prints the line, those keys null.  The --no-* options below take single legs "
+                         "out of a --full run")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-host-call", action="store_true", help="skip the host_call leg")
-    ap.add_argument("--no-file-call", action="store_true", help="skip the file_call leg (database file -> distances)")
-    ap.add_argument("--no-config5", action="store_true", help="skip the config-5 (fused edge list) leg")
+    ap.add_argument("--no-host-call", action="store_true", help="--full: skip the host_call leg")
+    ap.add_argument("--no-file-call", action="store_true",
+                    help="--full: skip the file_call leg (database file -> distances)")
+    ap.add_argument("--no-config5", action="store_true", help="--full: skip the config-5 (fused edge list) leg")
     ap.add_argument("--no-peer-store", action="store_true",
                     help="N > 1: skip the leg in which every rank stores its band straight into rank 0's matrix")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the config2 / config4 / default_sketch / kernel2 legs (N = 1)")
+                    help="--full: skip the config2 / config4 / default_sketch / kernel2 legs (N = 1)")
     ap.add_argument("--config5-genomes", type=int, default=100000)
     ap.add_argument("--config5-steps", type=int, default=3)
     ap.add_argument("--spinup-ms", type=float, default=200.0,
@@ -115,6 +128,8 @@ def parse():
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    if not args.full:       # a plain run: the headline steps alone
+        args.no_cpu = args.no_host_call = args.no_file_call = args.no_config5 = args.no_other_configs = True
     return args
 
 
@@ -1322,7 +1337,7 @@ def build_line(rep):
         "value": value, "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
         "scaling": "weak" if (args.weak and world > 1) else "strong", "vs_baseline": None, "dtype": "u64",
-        "data": f.get("data", "synthetic"),
+        "data": f.get("data", "synthetic"), "full": bool(getattr(args, "full", False)),
         "config": {"workload": "%d synthetic genomes self-vs-self, s=1024 (sketchsize64=16, "
                                "bbits=14), k=13,17,21,25,29, %d pairs, output [n_pairs,2] f32 "
                                "on rank 0" % (n, total_pairs),
@@ -1481,7 +1496,7 @@ def run(args, rep, rank, local_rank, world, fake, torch, dist, engine, synth, da
         f["data"] = "FAKE (bench.py self-test on CPU: no kernels ran, the numbers mean nothing)"
     else:
         sk, _ = synth.make_sketches(n, kmers, sketchsize64=16, bbits=14)
-    if world > 1:
+    if world > 1 and args.full:
         # what needs no process group comes first (rank 0 alone, every GPU; the others wait on a file)
         rep.enter("solo_legs")
         try:

@@ -58,6 +58,8 @@ def test_clean_run_prints_the_gathered_value():
     assert mg["gathered"]["value"] == d["value"] and mg["gathered"]["ms_per_step"] == d["ms_per_step"]
     assert isinstance(mg["peer_store"], dict) and mg["peer_store"].get("available") is False
     assert d["value_transport"] == "gather" and mg["transport_requested"] == "best"
+    # a plain run: the headline steps alone, none of the legs that --full adds
+    assert d["full"] is False and mg["host_call"] is None and d["config5"] is None
 
 
 @pytest.mark.parametrize("inject", ["isend:0", "isend:7", "isend:30", "isend:60"])
@@ -90,8 +92,9 @@ def test_even_bands_flag_skips_the_rebalance():
 def test_no_collective_legs_survive_a_process_group_that_never_forms():
     """Round-3 verdict: `multi_gpu.host_call` and `config5.host_call` -- one process driving all N GPUs, no
     collective -- are measured by rank 0 BEFORE torch.distributed is initialised, so a failing init_process_group
-    still leaves both on the line (FAKE mode: stand-ins, the control flow is what is tested)."""
-    d = _run("init")
+    still leaves both on the line (FAKE mode: stand-ins, the control flow is what is tested).  They are legs of a
+    --full run."""
+    d = _run("init", ["--full"])
     mg = _check_common(d)
     assert "injected failure of init_process_group" in mg["error"]
     assert mg["host_call"] == {"fake": True, "devices": [0, 1]}
@@ -100,8 +103,36 @@ def test_no_collective_legs_survive_a_process_group_that_never_forms():
 
 
 def test_clean_run_carries_the_solo_legs_too():
-    d = _run(None)
-    assert d["multi_gpu"]["host_call"] == {"fake": True, "devices": [0, 1]}
+    d = _run(None, ["--full"])
+    assert d["full"] is True and d["multi_gpu"]["host_call"] == {"fake": True, "devices": [0, 1]}
+
+
+def test_full_is_off_by_default_and_gates_every_leg_beside_the_headline(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures the headline alone: every other leg (cpu_baseline,
+    host_call, file_call, the other configurations, config5) is off unless --full is given; under --full the --no-*
+    options still take single legs out."""
+    sys.path.insert(0, ROOT)
+    import bench
+    legs = ("no_cpu", "no_host_call", "no_file_call", "no_config5", "no_other_configs")
+    plain = ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"]
+    monkeypatch.setattr(sys, "argv", plain)
+    args = bench.parse()
+    assert args.full is False and all(getattr(args, leg) for leg in legs)
+    assert (args.steps, args.warmup, args.dump_outputs) == (5, 2, None)
+    monkeypatch.setattr(sys, "argv", plain + ["--full"])
+    args = bench.parse()
+    assert args.full is True and not any(getattr(args, leg) for leg in legs)
+    monkeypatch.setattr(sys, "argv", plain + ["--full", "--no-cpu", "--no-config5"])
+    args = bench.parse()
+    assert [leg for leg in legs if getattr(args, leg)] == ["no_cpu", "no_config5"]
+    # the line says which kind of run it came from, the headline keys unchanged
+    rep = bench.Report(0, 1, args)
+    rep.fields.update({"n": 2000, "elapsed": 0.05})
+    d = bench.build_line(rep)
+    assert d["full"] is True and d["ms_per_step"] == pytest.approx(10.0)
+    assert d["value"] == pytest.approx(2000 * 1999 // 2 * 5 / 0.05)
+    assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"]) == \
+        ("genome-pair distances/sec (10k self, s=1024, k=13-29)", "pairs/s", True, "u64")
 
 
 def test_recorded_traffic_is_refused_when_the_library_was_built_from_other_sources(tmp_path):
@@ -129,7 +160,7 @@ def test_a_rank_that_dies_still_leaves_rank_0s_line():
     """torch.distributed.run answers a rank's non-zero exit with SIGTERM to the others; rank 0 may be inside a
     collective at that moment.  The signal reaches a thread of its own through a wake-up pipe and the line goes
     out with the error and rank 0's own compute-only figure."""
-    d = _run("die")
+    d = _run("die", ["--full"])
     assert d["n_gpus"] == 2 and "FAKE" in d["data"]
     mg = d["multi_gpu"]
     assert mg["error"]          # "SIGTERM in phase ..." and / or the broken collective rank 0 was in

@@ -7,10 +7,10 @@ ROUND=${ROUND:-r05}
 OUT=gpurun_out/$ROUND
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
-# the whole default line (what the driver runs)
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
-# the same command under the kernel trace: one summary row per kernel name + per-dispatch rows (split by grid below)
-B="python bench.py --steps 100 --warmup 20 --no-cpu --no-config5 --no-host-call --no-file-call"
+# the whole line, every leg (--full; a plain run times the headline steps alone)
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+# the device-side legs of the same command under the kernel trace: one summary row per kernel name + per-dispatch rows (split by grid below)
+B="python bench.py --full --steps 100 --warmup 20 --no-cpu --no-config5 --no-host-call --no-file-call"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- $B > $OUT/bench_under_rocprof.log 2>&1
 python tools/kernel_rows.py $(ls $OUT/kt/*/kt_kernel_trace.csv $OUT/kt/kt_kernel_trace.csv 2>/dev/null | head -1) > $OUT/bench_kernel_rows.csv 2>> $OUT/bench_under_rocprof.log
 # PMC passes (their own runs, no tracing of anything else), headline kernel only
@@ -25,7 +25,7 @@ python tools/ab_pinning.py 2>&1 | grep -v amdgpu > $OUT/ab_pinning.txt
 python tools/latency_table.py 2>&1 | grep -v amdgpu > $OUT/latency_table.txt
 python tools/time_wide.py 2>&1 | grep -v amdgpu > $OUT/time_wide.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/k2 -o k2 -- python tools/k2_trace.py 200 > $OUT/k2_trace.txt 2>&1
-PPK_BENCH_ONE_GPU=1 PPK_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 5 --warmup 2 --config5-genomes 20000 --no-cpu > $OUT/two_ranks_one_gpu.json 2> $OUT/two_ranks_one_gpu.err
+PPK_BENCH_ONE_GPU=1 PPK_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 2 --full --steps 5 --warmup 2 --config5-genomes 20000 --no-cpu > $OUT/two_ranks_one_gpu.json 2> $OUT/two_ranks_one_gpu.err
 if [ "${FULL:-0}" = "1" ]; then
   timeout 1500 python tools/measure_configs.py $OUT/configs.json > $OUT/configs.log 2>&1
   ./tools/watch_clocks.sh > $OUT/power_clocks.txt 2>&1
