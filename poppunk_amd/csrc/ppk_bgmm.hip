@@ -199,8 +199,8 @@ extern "C" int ppk_bgmm_prepare(int K, const double *weights, const double *mean
 }
 
 // ---- host arrays --------------------------------------------------------------------------------------------------
-// BGMMFit.assign(X) of the Python mirror: the rows go through in chunks of 8 Mi (64 MB in), each uploaded, assigned
-// and fetched in turn on the device's default stream.
+// BGMMFit.assign(X) of the Python mirror: the rows go through one chunk's buffers in SLOT_HOST_IN, 8 Mi rows (64 MB
+// in) at a time, each chunk uploaded, assigned and fetched in turn on the device's default stream.
 extern "C" int ppk_bgmm_assign(const float *dist, size_t n_rows, const ppk_bgmm *model, int device_id, int32_t *labels,
                                float *resp) {
   if (!model) return ppk_fail(PPK_ERR_ARG, "ppk_bgmm_assign: model is NULL");
@@ -210,30 +210,30 @@ extern "C" int ppk_bgmm_assign(const float *dist, size_t n_rows, const ppk_bgmm 
   if (!dist || (!labels && !resp)) return ppk_fail(PPK_ERR_ARG, "ppk_bgmm_assign: NULL input / no output");
   if (device_id < 0 || device_id >= 64) return ppk_fail(PPK_ERR_ARG, "device id out of range");
   if (int rc = ppk_check_arch(device_id)) return rc;
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
   const size_t chunk = (size_t)8 << 20;
   const size_t buf_rows = n_rows < chunk ? n_rows : chunk;
   const size_t K = (size_t)model->K;
-  char *d_buf = nullptr;
-  const size_t in_bytes = (buf_rows * 8 + 255) / 256 * 256, lab_bytes = (buf_rows * 4 + 255) / 256 * 256;
-  PPK_HIP(hipMalloc(reinterpret_cast<void **>(&d_buf), in_bytes + lab_bytes + buf_rows * K * 4));
-  float *d_in = reinterpret_cast<float *>(d_buf);
-  int32_t *d_lab = labels ? reinterpret_cast<int32_t *>(d_buf + in_bytes) : nullptr;
-  float *d_resp = resp ? reinterpret_cast<float *>(d_buf + in_bytes + lab_bytes) : nullptr;
-  int rc = PPK_OK;
-  for (size_t r0 = 0; r0 < n_rows && rc == PPK_OK; r0 += chunk) {
-    const size_t rows = n_rows - r0 < chunk ? n_rows - r0 : chunk;
-    if (hipMemcpy(d_in, dist + 2 * r0, rows * 8, hipMemcpyHostToDevice) != hipSuccess) {
-      rc = ppk_fail(PPK_ERR_HIP, "hipMemcpy H2D failed");
-      break;
+  float *d_in, *d_resp;
+  int32_t *d_lab;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_in, buf_rows * 2).take(d_lab, labels ? buf_rows : 0).take(d_resp, resp ? buf_rows * K : 0);
+  }, [&]() -> int {
+    // an output not asked for has no room in the layout: the kernel is told so by a null pointer
+    if (!labels) d_lab = nullptr;
+    if (!resp) d_resp = nullptr;
+    int rc = PPK_OK;
+    for (size_t r0 = 0; r0 < n_rows && rc == PPK_OK; r0 += chunk) {
+      const size_t rows = n_rows - r0 < chunk ? n_rows - r0 : chunk;
+      if (hipMemcpy(d_in, dist + 2 * r0, rows * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        rc = ppk_fail(PPK_ERR_HIP, "hipMemcpy H2D failed");
+        break;
+      }
+      rc = ppk_launch_bgmm_assign(d_in, rows, *model, d_lab, d_resp, nullptr);
+      if (rc != PPK_OK) break;
+      if ((d_lab && hipMemcpy(labels + r0, d_lab, rows * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
+          (d_resp && hipMemcpy(resp + r0 * K, d_resp, rows * K * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        rc = ppk_fail(PPK_ERR_HIP, "BGMM assignment failed on the device");
     }
-    rc = ppk_launch_bgmm_assign(d_in, rows, *model, d_lab, d_resp, nullptr);
-    if (rc != PPK_OK) break;
-    if ((d_lab && hipMemcpy(labels + r0, d_lab, rows * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (d_resp && hipMemcpy(resp + r0 * K, d_resp, rows * K * 4, hipMemcpyDeviceToHost) != hipSuccess))
-      rc = ppk_fail(PPK_ERR_HIP, "BGMM assignment failed on the device");
-  }
-  (void)hipFree(d_buf);
-  return rc;
+    return rc;
+  });
 }

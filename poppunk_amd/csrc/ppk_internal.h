@@ -232,7 +232,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_EMBED = 16,                        // the embedding's sampling weights and prefix, Q32.32 deltas, Eq
        SLOT_DBSCAN = 17,                       // the DBSCAN fit's Boruvka state and sort storage; the labels behind its edge list
        SLOT_BGMM_FIT = 18,                     // the BGMM fit's per-workgroup partial sums, its sums, counters and k-means labels
-       SLOT_COUNT = 19 };
+       SLOT_SPARSE = 19,                       // extend's and lowerRank's row starts, sort pairs, counts, offsets and temp storage
+       SLOT_COUNT = 20 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and
@@ -251,7 +252,8 @@ class PpkCall {
   unsigned prev_touched_;
 };
 
-// ---- host-side frame of the graph modules (ppk_network.hip, ppk_mst.hip, ppk_nj.hip) ------------------------------
+// ---- host-side frame of every module but the distance queries and sweeps (ppk_host.hip, ppk_iterate.hip: their
+// results may not fit the caller's buffer, see ppk_host_result): network, MST, NJ, embed, DBSCAN, BGMM, square, sparse
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // blocks of `per_block` items each: at least 1, at most `cap`
 inline unsigned grid_for(size_t items, size_t per_block, unsigned cap) {

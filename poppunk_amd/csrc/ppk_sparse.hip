@@ -7,6 +7,10 @@
 // the rows are sorted side by side by one segmented radix sort (hipCUB), and one thread per row does the
 // reference's walk over the head of its sorted row.  Row counts -> exclusive scan -> the (i, j, dist)
 // triplets in row order, as the reference concatenates its per-row vectors.
+//
+// Nothing is allocated per call: the work buffers are one layout of scratch slot SLOT_SPARSE (sparse_work), the
+// uploaded inputs and the result triplets -- at a bound known before anything runs -- one layout of SLOT_HOST_IN
+// (ppk_host_frame).  A call synchronises twice: for the bad-rows flag and for the number of triplets.
 #include <hipcub/hipcub.hpp>
 
 #include "ppk_internal.h"
@@ -21,21 +25,6 @@ __device__ __forceinline__ float dist_of(uint64_t key) {
   const unsigned o = (unsigned)(key >> 32);
   return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
-
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipMalloc failed");
-    return PPK_OK;
-  }
-  template <typename T>
-  T *as() const {
-    return static_cast<T *>(p);
-  }
-};
 
 // rows of a row-sorted COO: entries of row r are [start[r], start[r+1]) (src/extend.cpp:15-38); flag[0] is
 // raised when the row indices are not ascending or leave [0, n_rows)
@@ -210,41 +199,153 @@ ext_pick_kernel(const uint64_t *__restrict__ skeys, const int *__restrict__ sval
   if (!WRITE) count[i] = kept;
 }
 
-unsigned blocks_for(size_t items) { return (unsigned)((items + 255) / 256 ? (items + 255) / 256 : 1); }
 
-int h2d(void *d, const void *h, size_t bytes) {
+// hipCUB's two entry points as both calls use them; tmp == nullptr only sizes `bytes`
+hipError_t sort_rows(void *tmp, size_t &bytes, const uint64_t *kin, uint64_t *kout, const int *vin, int *vout,
+                     size_t items, size_t n_rows, const int *seg, const int *seg_end, hipStream_t s) {
+  return hipcub::DeviceSegmentedRadixSort::SortPairs(tmp, bytes, kin, kout, vin, vout, (int)items, (int)n_rows, seg,
+                                                     seg_end, 0, 64, s);
+}
+hipError_t scan_counts(void *tmp, size_t &bytes, const unsigned long long *count, unsigned long long *sums, size_t n,
+                       hipStream_t s) {
+  return hipcub::DeviceScan::InclusiveSum(tmp, bytes, count, sums, (int)n, s);
+}
+
+// The work buffers of one call, all of SLOT_SPARSE and carved ONCE (a second carve that grew the slot would free the
+// block under the first one's pointers): row starts, sort segments, the bad-rows flag, both key / value pairs, row
+// counts and offsets, what `more` appends, and hipCUB's temporary storage for the sort and the scan.
+struct SparseWork {
+  int *start, *seg, *flag;
+  uint64_t *kin, *kout;
+  int *vin, *vout;
+  unsigned long long *cnt, *offs;
+  char *tmp;
+  size_t tmp_bytes;
+};
+template <typename More>
+int sparse_work(int dev, SparseWork &w, size_t starts, size_t segs, size_t items, size_t rows, hipStream_t s,
+                More &&more) {
+  size_t sort_tmp = 0, scan_tmp = 0;
+  PPK_HIP(sort_rows(nullptr, sort_tmp, nullptr, nullptr, nullptr, nullptr, items, rows, nullptr, nullptr, s));
+  PPK_HIP(scan_counts(nullptr, scan_tmp, nullptr, nullptr, rows, s));
+  w.tmp_bytes = sort_tmp > scan_tmp ? sort_tmp : scan_tmp;
+  return ppk_scratch_carve(dev, SLOT_SPARSE, [&](Carve &c) {
+    c.take(w.start, starts).take(w.seg, segs).take(w.flag, 1).take(w.kin, items).take(w.kout, items);
+    c.take(w.vin, items).take(w.vout, items).take(w.cnt, rows).take(w.offs, rows + 1);
+    more(c);
+    c.take(w.tmp, w.tmp_bytes + 256);
+  });
+}
+
+// w.start of a row-sorted COO.  The one read-back in front of the totals: a matrix whose rows do not ascend gives
+// garbage starts, so it is refused here, before any kernel indexes by them.
+int row_starts(int dev, const SparseWork &w, const long long *d_ri, size_t nnz, size_t n_rows, const char *limit,
+               hipStream_t s) {
+  PPK_HIP(hipMemsetAsync(w.flag, 0, 4, s));
+  const size_t most = nnz > n_rows + 1 ? nnz : n_rows + 1;
+  hipLaunchKernelGGL(row_start_kernel, dim3(grid_for(most, 256, ~0u)), dim3(256), 0, s, d_ri, nnz, n_rows, w.start,
+                     w.flag);
+  PPK_HIP(hipGetLastError());
+  const unsigned long long *h = nullptr;
+  if (int rc = ppk_read_back(dev, s, {{w.flag, 4}}, &h)) return rc;
+  if ((int)h[0])
+    return ppk_fail(PPK_ERR_ARG, std::string("sparse matrix: row indices must be ascending and below ") + limit);
+  return PPK_OK;
+}
+
+// counts[n] -> offsets[n + 1] (exclusive)
+int offsets_of(const SparseWork &w, const unsigned long long *count, unsigned long long *offs, size_t n,
+               hipStream_t s) {
+  PPK_HIP(hipMemsetAsync(offs, 0, (n + 1) * 8, s));
+  size_t bytes = w.tmp_bytes;
+  PPK_HIP(scan_counts(w.tmp, bytes, count, offs + 1, n, s));
+  return PPK_OK;
+}
+
+// lowerRank of device arrays: the triplets into d_oi / d_oj / d_od (room for nnz each: a row keeps no more than it
+// has), their number into *total (host) -- the call's second and last synchronisation
+int lower_rank_dev(const long long *d_ri, const long long *d_rj, const float *d_rd, size_t nnz, size_t n,
+                   unsigned long long knn, int reciprocal_only, int count_unique, float epsilon, long long *d_oi,
+                   long long *d_oj, float *d_od, unsigned long long *total, hipStream_t s) {
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipGetDevice failed");
-  return ppk_upload(dev, d, h, bytes, nullptr);      // staged through the pinned ring; ordered on the null stream
-}
-int d2h(void *h, const void *d, size_t bytes) {
-  if (bytes && hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipMemcpy D2H failed");
+  PPK_HIP(hipGetDevice(&dev));
+  PpkCall call(dev, s);
+  SparseWork w;
+  // what the walk keeps: the result itself, or (as many at most) the reciprocal pass's input
+  long long *ki = d_oi, *kj = d_oj;
+  float *kd = d_od;
+  unsigned long long *offs2 = nullptr;
+  int rc = sparse_work(dev, w, n + 1, 0, nnz, n, s, [&](Carve &c) {
+    if (reciprocal_only) c.take(ki, nnz).take(kj, nnz).take(kd, nnz).take(offs2, n + 1);
+  });
+  if (rc == PPK_OK) rc = row_starts(dev, w, d_ri, nnz, n, "n_samples", s);
+  if (rc != PPK_OK) return rc;
+  hipLaunchKernelGGL(lr_keys_kernel, dim3(grid_for(nnz, 256, ~0u)), dim3(256), 0, s, d_ri, d_rd, nnz, w.start, w.kin,
+                     w.vin);
+  PPK_HIP(hipGetLastError());
+  size_t bytes = w.tmp_bytes;
+  PPK_HIP(sort_rows(w.tmp, bytes, w.kin, w.kout, w.vin, w.vout, nnz, n, w.start, w.start + 1, s));
+  const dim3 grid(grid_for(n, 256, ~0u));
+  hipLaunchKernelGGL(lr_walk_kernel<false>, grid, dim3(256), 0, s, w.kout, w.vout, d_rj, w.start, n, knn, count_unique,
+                     epsilon, w.cnt, nullptr, nullptr, nullptr, nullptr);
+  if ((rc = offsets_of(w, w.cnt, w.offs, n, s)) != PPK_OK) return rc;
+  hipLaunchKernelGGL(lr_walk_kernel<true>, grid, dim3(256), 0, s, w.kout, w.vout, d_rj, w.start, n, knn, count_unique,
+                     epsilon, nullptr, w.offs, ki, kj, kd);
+  PPK_HIP(hipGetLastError());
+  const unsigned long long *d_total = w.offs + n;
+  if (reciprocal_only) {
+    // (the walk's counts have been scanned: w.cnt is free again)
+    hipLaunchKernelGGL(lr_recip_kernel<false>, grid, dim3(256), 0, s, kj, kd, w.offs, n, w.cnt, nullptr, nullptr,
+                       nullptr, nullptr);
+    if ((rc = offsets_of(w, w.cnt, offs2, n, s)) != PPK_OK) return rc;
+    hipLaunchKernelGGL(lr_recip_kernel<true>, grid, dim3(256), 0, s, kj, kd, w.offs, n, nullptr, offs2, d_oi, d_oj,
+                       d_od);
+    PPK_HIP(hipGetLastError());
+    d_total = offs2 + n;
+  }
+  const unsigned long long *h = nullptr;
+  if ((rc = ppk_read_back(dev, s, {{d_total, 8}}, &h)) != PPK_OK) return rc;
+  *total = h[0];
   return PPK_OK;
 }
 
-// segmented sort of (keys, vals) by key; segments [seg[r], seg[r+1])
-int sort_rows(uint64_t *kin, uint64_t *kout, int *vin, int *vout, size_t items, size_t n_rows, const int *seg) {
-  if (items == 0) return PPK_OK;
-  size_t tmp = 0;
-  PPK_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, tmp, kin, kout, vin, vout, (int)items, (int)n_rows, seg,
-                                                      seg + 1, 0, 64, nullptr));
-  DevBuf ws;
-  if (int rc = ws.alloc(tmp + 256)) return rc;
-  PPK_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(ws.p, tmp, kin, kout, vin, vout, (int)items, (int)n_rows, seg,
-                                                      seg + 1, 0, 64, nullptr));
-  PPK_HIP(hipStreamSynchronize(nullptr));          // ws is freed on return
-  return PPK_OK;
-}
-
-// counts[n] -> offsets[n + 1] (exclusive), total read back
-int scan_counts(const unsigned long long *d_count, unsigned long long *d_offs, size_t n, unsigned long long *total) {
-  size_t tmp = 0;
-  PPK_HIP(hipMemsetAsync(d_offs, 0, (n + 1) * 8, nullptr));
-  PPK_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tmp, d_count, d_offs + 1, (int)n, nullptr));
-  DevBuf ws;
-  if (int rc = ws.alloc(tmp + 256)) return rc;
-  PPK_HIP(hipcub::DeviceScan::InclusiveSum(ws.p, tmp, d_count, d_offs + 1, (int)n, nullptr));
-  PPK_HIP(hipMemcpy(total, d_offs + n, 8, hipMemcpyDeviceToHost));
+// extend of device arrays: the triplets into d_oi / d_oj / d_od (room for min(items, n_rows * knn) each), their
+// number into *total (host) -- the call's second and last synchronisation
+int extend_dev(const long long *d_ri, const long long *d_rj, const float *d_rd, size_t nnz, const float *d_qq,
+               const float *d_qr, size_t n_ref, size_t n_qry, unsigned long long knn, long long *d_oi, long long *d_oj,
+               float *d_od, unsigned long long *total, hipStream_t s) {
+  int dev = 0;
+  PPK_HIP(hipGetDevice(&dev));
+  PpkCall call(dev, s);
+  const size_t n_rows = n_ref + n_qry, items = n_ref * n_qry + nnz + n_qry * n_rows;
+  SparseWork w;
+  int rc = sparse_work(dev, w, n_ref + 1, n_rows + 1, items, n_rows, s, [](Carve &) {});
+  if (rc == PPK_OK) rc = row_starts(dev, w, d_ri, nnz, n_ref, "the number of references", s);
+  if (rc != PPK_OK) return rc;
+  hipLaunchKernelGGL(ext_seg_kernel, dim3(grid_for(n_rows + 1, 256, ~0u)), dim3(256), 0, s, w.start, n_ref, n_qry, nnz,
+                     w.seg);
+  if (n_ref * n_qry)
+    hipLaunchKernelGGL(ext_ref_dense_kernel, dim3(grid_for(n_ref * n_qry, 256, ~0u)), dim3(256), 0, s, d_qr, n_ref,
+                       n_qry, w.seg, w.kin, w.vin);
+  if (nnz)
+    hipLaunchKernelGGL(ext_ref_sparse_kernel, dim3(grid_for(nnz, 256, ~0u)), dim3(256), 0, s, d_ri, d_rj, d_rd, nnz,
+                       n_qry, w.start, w.seg, w.kin, w.vin);
+  if (n_qry)
+    hipLaunchKernelGGL(ext_qry_kernel, dim3(grid_for(n_qry * n_rows, 256, ~0u)), dim3(256), 0, s, d_qq, d_qr, n_ref,
+                       n_qry, w.seg, w.kin, w.vin);
+  PPK_HIP(hipGetLastError());
+  size_t bytes = w.tmp_bytes;
+  PPK_HIP(sort_rows(w.tmp, bytes, w.kin, w.kout, w.vin, w.vout, items, n_rows, w.seg, w.seg + 1, s));
+  const dim3 grid(grid_for(n_rows, 256, ~0u));
+  hipLaunchKernelGGL(ext_pick_kernel<false>, grid, dim3(256), 0, s, w.kout, w.vout, w.seg, n_rows, knn, w.cnt, nullptr,
+                     nullptr, nullptr, nullptr);
+  if ((rc = offsets_of(w, w.cnt, w.offs, n_rows, s)) != PPK_OK) return rc;
+  hipLaunchKernelGGL(ext_pick_kernel<true>, grid, dim3(256), 0, s, w.kout, w.vout, w.seg, n_rows, knn, nullptr, w.offs,
+                     d_oi, d_oj, d_od);
+  PPK_HIP(hipGetLastError());
+  const unsigned long long *h = nullptr;
+  if ((rc = ppk_read_back(dev, s, {{w.offs + n_rows, 8}}, &h)) != PPK_OK) return rc;
+  *total = h[0];
   return PPK_OK;
 }
 
@@ -254,15 +355,16 @@ int check_coo(const long long *rr_i, const long long *rr_j, const float *rr_d, s
   return PPK_OK;
 }
 
-int copy_out(const DevBuf &oi, const DevBuf &oj, const DevBuf &od, unsigned long long total, long long *i_out,
-             long long *j_out, float *d_out, size_t cap, size_t *n_out) {
+int copy_out(const long long *d_oi, const long long *d_oj, const float *d_od, unsigned long long total,
+             long long *i_out, long long *j_out, float *d_out, size_t cap, size_t *n_out) {
   *n_out = (size_t)total;
   if (total > cap) return ppk_fail(PPK_ERR_CAPACITY, "output too small: need " + std::to_string(total));
-  if (total && (!i_out || !j_out || !d_out)) return ppk_fail(PPK_ERR_ARG, "NULL output");
-  int rc = d2h(i_out, oi.p, total * 8);
-  if (rc == PPK_OK) rc = d2h(j_out, oj.p, total * 8);
-  if (rc == PPK_OK) rc = d2h(d_out, od.p, total * 4);
-  return rc;
+  if (!total) return PPK_OK;
+  if (!i_out || !j_out || !d_out) return ppk_fail(PPK_ERR_ARG, "NULL output");
+  PPK_HIP(hipMemcpy(i_out, d_oi, total * 8, hipMemcpyDeviceToHost));
+  PPK_HIP(hipMemcpy(j_out, d_oj, total * 8, hipMemcpyDeviceToHost));
+  PPK_HIP(hipMemcpy(d_out, d_od, total * 4, hipMemcpyDeviceToHost));
+  return PPK_OK;
 }
 
 }  // namespace
@@ -276,73 +378,21 @@ extern "C" int ppk_lower_rank(const long long *rr_i, const long long *rr_j, cons
   if (int rc = check_coo(rr_i, rr_j, rr_d, nnz)) return rc;
   if (n_samples == 0 || nnz == 0) return PPK_OK;
   if (n_samples >= (size_t)0x7fffffff) return ppk_fail(PPK_ERR_ARG, "too many samples");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
-  if (int rc = ppk_check_arch(device_id)) return rc;
-  DevBuf ri, rj, rd, start, flag, kin, kout, vin, vout, cnt, offs, oi, oj, od;
-  int rc = ri.alloc(nnz * 8);
-  if (rc == PPK_OK) rc = rj.alloc(nnz * 8);
-  if (rc == PPK_OK) rc = rd.alloc(nnz * 4);
-  if (rc == PPK_OK) rc = start.alloc((n_samples + 1) * 4);
-  if (rc == PPK_OK) rc = flag.alloc(4);
-  if (rc == PPK_OK) rc = kin.alloc(nnz * 8);
-  if (rc == PPK_OK) rc = kout.alloc(nnz * 8);
-  if (rc == PPK_OK) rc = vin.alloc(nnz * 4);
-  if (rc == PPK_OK) rc = vout.alloc(nnz * 4);
-  if (rc == PPK_OK) rc = cnt.alloc(n_samples * 8);
-  if (rc == PPK_OK) rc = offs.alloc((n_samples + 1) * 8);
-  if (rc == PPK_OK) rc = h2d(ri.p, rr_i, nnz * 8);
-  if (rc == PPK_OK) rc = h2d(rj.p, rr_j, nnz * 8);
-  if (rc == PPK_OK) rc = h2d(rd.p, rr_d, nnz * 4);
-  if (rc != PPK_OK) return rc;
-  PPK_HIP(hipMemsetAsync(flag.p, 0, 4, nullptr));
-  const size_t most = nnz > n_samples + 1 ? nnz : n_samples + 1;
-  hipLaunchKernelGGL(row_start_kernel, dim3(blocks_for(most)), dim3(256), 0, nullptr, ri.as<long long>(), nnz, n_samples,
-                     start.as<int>(), flag.as<int>());
-  int bad = 0;
-  PPK_HIP(hipMemcpy(&bad, flag.p, 4, hipMemcpyDeviceToHost));
-  if (bad) return ppk_fail(PPK_ERR_ARG, "sparse matrix: row indices must be ascending and below n_samples");
-  hipLaunchKernelGGL(lr_keys_kernel, dim3(blocks_for(nnz)), dim3(256), 0, nullptr, ri.as<long long>(), rd.as<float>(), nnz,
-                     start.as<int>(), kin.as<uint64_t>(), vin.as<int>());
-  PPK_HIP(hipGetLastError());
-  rc = sort_rows(kin.as<uint64_t>(), kout.as<uint64_t>(), vin.as<int>(), vout.as<int>(), nnz, n_samples, start.as<int>());
-  if (rc != PPK_OK) return rc;
-  const dim3 grid(blocks_for(n_samples));
-  hipLaunchKernelGGL(lr_walk_kernel<false>, grid, dim3(256), 0, nullptr, kout.as<uint64_t>(), vout.as<int>(),
-                     rj.as<long long>(), start.as<int>(), n_samples, (unsigned long long)knn, count_unique_distances, epsilon,
-                     cnt.as<unsigned long long>(), nullptr, nullptr, nullptr, nullptr);
-  unsigned long long total = 0;
-  rc = scan_counts(cnt.as<unsigned long long>(), offs.as<unsigned long long>(), n_samples, &total);
-  if (rc == PPK_OK) rc = oi.alloc(total * 8);
-  if (rc == PPK_OK) rc = oj.alloc(total * 8);
-  if (rc == PPK_OK) rc = od.alloc(total * 4);
-  if (rc != PPK_OK) return rc;
-  hipLaunchKernelGGL(lr_walk_kernel<true>, grid, dim3(256), 0, nullptr, kout.as<uint64_t>(), vout.as<int>(),
-                     rj.as<long long>(), start.as<int>(), n_samples, (unsigned long long)knn, count_unique_distances, epsilon,
-                     nullptr, offs.as<unsigned long long>(), oi.as<long long>(), oj.as<long long>(), od.as<float>());
-  PPK_HIP(hipGetLastError());
-  if (!reciprocal_only) {
-    PPK_HIP(hipDeviceSynchronize());
-    return copy_out(oi, oj, od, total, i_out, j_out, d_out, cap, n_out);
-  }
-  DevBuf cnt2, offs2, fi, fj, fd;
-  rc = cnt2.alloc(n_samples * 8);
-  if (rc == PPK_OK) rc = offs2.alloc((n_samples + 1) * 8);
-  if (rc != PPK_OK) return rc;
-  hipLaunchKernelGGL(lr_recip_kernel<false>, grid, dim3(256), 0, nullptr, oj.as<long long>(), od.as<float>(),
-                     offs.as<unsigned long long>(), n_samples, cnt2.as<unsigned long long>(), nullptr, nullptr, nullptr, nullptr);
-  unsigned long long total2 = 0;
-  rc = scan_counts(cnt2.as<unsigned long long>(), offs2.as<unsigned long long>(), n_samples, &total2);
-  if (rc == PPK_OK) rc = fi.alloc(total2 * 8);
-  if (rc == PPK_OK) rc = fj.alloc(total2 * 8);
-  if (rc == PPK_OK) rc = fd.alloc(total2 * 4);
-  if (rc != PPK_OK) return rc;
-  hipLaunchKernelGGL(lr_recip_kernel<true>, grid, dim3(256), 0, nullptr, oj.as<long long>(), od.as<float>(),
-                     offs.as<unsigned long long>(), n_samples, nullptr, offs2.as<unsigned long long>(), fi.as<long long>(),
-                     fj.as<long long>(), fd.as<float>());
-  PPK_HIP(hipGetLastError());
-  PPK_HIP(hipDeviceSynchronize());
-  return copy_out(fi, fj, fd, total2, i_out, j_out, d_out, cap, n_out);
+  long long *d_ri, *d_rj, *d_oi, *d_oj;
+  float *d_rd, *d_od;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_ri, nnz).take(d_rj, nnz).take(d_rd, nnz).take(d_oi, nnz).take(d_oj, nnz).take(d_od, nnz);
+  }, [&]() -> int {
+    int rc = ppk_check_arch(device_id);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_ri, rr_i, nnz * 8, nullptr);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_rj, rr_j, nnz * 8, nullptr);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_rd, rr_d, nnz * 4, nullptr);
+    unsigned long long total = 0;
+    if (rc == PPK_OK)
+      rc = lower_rank_dev(d_ri, d_rj, d_rd, nnz, n_samples, knn, reciprocal_only, count_unique_distances, epsilon,
+                          d_oi, d_oj, d_od, &total, nullptr);
+    return rc != PPK_OK ? rc : copy_out(d_oi, d_oj, d_od, total, i_out, j_out, d_out, cap, n_out);
+  });
 }
 
 extern "C" int ppk_extend(const long long *rr_i, const long long *rr_j, const float *rr_d, size_t nnz,
@@ -358,65 +408,24 @@ extern "C" int ppk_extend(const long long *rr_i, const long long *rr_j, const fl
   const size_t items = n_ref * n_qry + nnz + n_qry * (n_ref + n_qry);
   if (items >= (size_t)0x7fffffff || n_rows >= (size_t)0x7fffffff)
     return ppk_fail(PPK_ERR_ARG, "ppk_extend: fewer than 2^31 candidate distances supported (n_ref*n_qry + nnz + n_qry*(n_ref+n_qry))");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
-  if (int rc = ppk_check_arch(device_id)) return rc;
-  DevBuf ri, rj, rd, qq, qr, start, seg, flag, kin, kout, vin, vout, cnt, offs, oi, oj, od;
-  int rc = ri.alloc(nnz * 8);
-  if (rc == PPK_OK) rc = rj.alloc(nnz * 8);
-  if (rc == PPK_OK) rc = rd.alloc(nnz * 4);
-  if (rc == PPK_OK) rc = qq.alloc(n_qry * n_qry * 4);
-  if (rc == PPK_OK) rc = qr.alloc(n_ref * n_qry * 4);
-  if (rc == PPK_OK) rc = start.alloc((n_ref + 1) * 4);
-  if (rc == PPK_OK) rc = seg.alloc((n_rows + 1) * 4);
-  if (rc == PPK_OK) rc = flag.alloc(4);
-  if (rc == PPK_OK) rc = kin.alloc(items * 8);
-  if (rc == PPK_OK) rc = kout.alloc(items * 8);
-  if (rc == PPK_OK) rc = vin.alloc(items * 4);
-  if (rc == PPK_OK) rc = vout.alloc(items * 4);
-  if (rc == PPK_OK) rc = cnt.alloc(n_rows * 8);
-  if (rc == PPK_OK) rc = offs.alloc((n_rows + 1) * 8);
-  if (rc == PPK_OK) rc = h2d(ri.p, rr_i, nnz * 8);
-  if (rc == PPK_OK) rc = h2d(rj.p, rr_j, nnz * 8);
-  if (rc == PPK_OK) rc = h2d(rd.p, rr_d, nnz * 4);
-  if (rc == PPK_OK) rc = h2d(qq.p, qq_square, n_qry * n_qry * 4);
-  if (rc == PPK_OK) rc = h2d(qr.p, qr_rect, n_ref * n_qry * 4);
-  if (rc != PPK_OK) return rc;
-  PPK_HIP(hipMemsetAsync(flag.p, 0, 4, nullptr));
-  const size_t most = nnz > n_ref + 1 ? nnz : n_ref + 1;
-  hipLaunchKernelGGL(row_start_kernel, dim3(blocks_for(most)), dim3(256), 0, nullptr, ri.as<long long>(), nnz, n_ref,
-                     start.as<int>(), flag.as<int>());
-  int bad = 0;
-  PPK_HIP(hipMemcpy(&bad, flag.p, 4, hipMemcpyDeviceToHost));
-  if (bad) return ppk_fail(PPK_ERR_ARG, "sparse matrix: row indices must be ascending and below the number of references");
-  hipLaunchKernelGGL(ext_seg_kernel, dim3(blocks_for(n_rows + 1)), dim3(256), 0, nullptr, start.as<int>(), n_ref, n_qry, nnz,
-                     seg.as<int>());
-  if (n_ref * n_qry)
-    hipLaunchKernelGGL(ext_ref_dense_kernel, dim3(blocks_for(n_ref * n_qry)), dim3(256), 0, nullptr, qr.as<float>(), n_ref,
-                       n_qry, seg.as<int>(), kin.as<uint64_t>(), vin.as<int>());
-  if (nnz)
-    hipLaunchKernelGGL(ext_ref_sparse_kernel, dim3(blocks_for(nnz)), dim3(256), 0, nullptr, ri.as<long long>(),
-                       rj.as<long long>(), rd.as<float>(), nnz, n_qry, start.as<int>(), seg.as<int>(), kin.as<uint64_t>(),
-                       vin.as<int>());
-  if (n_qry)
-    hipLaunchKernelGGL(ext_qry_kernel, dim3(blocks_for(n_qry * n_rows)), dim3(256), 0, nullptr, qq.as<float>(), qr.as<float>(),
-                       n_ref, n_qry, seg.as<int>(), kin.as<uint64_t>(), vin.as<int>());
-  PPK_HIP(hipGetLastError());
-  rc = sort_rows(kin.as<uint64_t>(), kout.as<uint64_t>(), vin.as<int>(), vout.as<int>(), items, n_rows, seg.as<int>());
-  if (rc != PPK_OK) return rc;
-  const dim3 grid(blocks_for(n_rows));
-  hipLaunchKernelGGL(ext_pick_kernel<false>, grid, dim3(256), 0, nullptr, kout.as<uint64_t>(), vout.as<int>(), seg.as<int>(),
-                     n_rows, (unsigned long long)knn, cnt.as<unsigned long long>(), nullptr, nullptr, nullptr, nullptr);
-  unsigned long long total = 0;
-  rc = scan_counts(cnt.as<unsigned long long>(), offs.as<unsigned long long>(), n_rows, &total);
-  if (rc == PPK_OK) rc = oi.alloc(total * 8);
-  if (rc == PPK_OK) rc = oj.alloc(total * 8);
-  if (rc == PPK_OK) rc = od.alloc(total * 4);
-  if (rc != PPK_OK) return rc;
-  hipLaunchKernelGGL(ext_pick_kernel<true>, grid, dim3(256), 0, nullptr, kout.as<uint64_t>(), vout.as<int>(), seg.as<int>(),
-                     n_rows, (unsigned long long)knn, nullptr, offs.as<unsigned long long>(), oi.as<long long>(),
-                     oj.as<long long>(), od.as<float>());
-  PPK_HIP(hipGetLastError());
-  PPK_HIP(hipDeviceSynchronize());
-  return copy_out(oi, oj, od, total, i_out, j_out, d_out, cap, n_out);
+  if (items == 0) return PPK_OK;      // references alone and an empty sparse matrix: no candidate, no entry
+  // a row keeps at most knn of its candidates
+  const size_t most = knn < items && n_rows * knn < items ? n_rows * knn : items;
+  long long *d_ri, *d_rj, *d_oi, *d_oj;
+  float *d_rd, *d_qq, *d_qr, *d_od;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_ri, nnz).take(d_rj, nnz).take(d_rd, nnz).take(d_qq, n_qry * n_qry).take(d_qr, n_ref * n_qry);
+    c.take(d_oi, most).take(d_oj, most).take(d_od, most);
+  }, [&]() -> int {
+    int rc = ppk_check_arch(device_id);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_ri, rr_i, nnz * 8, nullptr);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_rj, rr_j, nnz * 8, nullptr);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_rd, rr_d, nnz * 4, nullptr);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_qq, qq_square, n_qry * n_qry * 4, nullptr);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_qr, qr_rect, n_ref * n_qry * 4, nullptr);
+    unsigned long long total = 0;
+    if (rc == PPK_OK)
+      rc = extend_dev(d_ri, d_rj, d_rd, nnz, d_qq, d_qr, n_ref, n_qry, knn, d_oi, d_oj, d_od, &total, nullptr);
+    return rc != PPK_OK ? rc : copy_out(d_oi, d_oj, d_od, total, i_out, j_out, d_out, cap, n_out);
+  });
 }

@@ -371,23 +371,20 @@ extern "C" int ppk_knn_rect_dev(const float *d_block, size_t stride, size_t col,
   PPK_HIP(hipGetDevice(&dev));
   PpkCall call(dev, s);
   const size_t nn = n_rows * n_cols;
-  void *p_a = nullptr, *p_c = nullptr;
-  const size_t o_kin = 0, o_kout = o_kin + nn * 4, o_vin = o_kout + nn * 4, o_vout = o_vin + nn * 4;
-  const size_t o_seg = o_vout + nn * 4, o_end = o_seg + (n_rows + 1) * 4 + 256;
-  int rc = ppk_scratch_get(dev, SLOT_ITER_B, o_end, &p_a);
-  if (rc != PPK_OK) return rc;
-  char *A = static_cast<char *>(p_a);
-  float *kin = reinterpret_cast<float *>(A + o_kin), *kout = reinterpret_cast<float *>(A + o_kout);
-  int *vin = reinterpret_cast<int *>(A + o_vin), *vout = reinterpret_cast<int *>(A + o_vout);
-  int *seg = reinterpret_cast<int *>(A + o_seg);
-  hipLaunchKernelGGL(knn_init_kernel, dim3((unsigned)((nn + n_rows + 256) / 256)), dim3(256), 0, s, kin,
-                     vin, seg, n_rows, n_cols, d_block, stride, col);
+  float *kin = nullptr, *kout = nullptr;
+  int *vin = nullptr, *vout = nullptr, *seg = nullptr;
+  char *d_tmp;
   size_t tmp = 0;
   PPK_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, tmp, kin, kout, vin, vout, (int)nn,
-                                                      (int)n_rows, seg, seg + 1, 0, 32, s));
-  rc = ppk_scratch_get(dev, SLOT_ITER_C, tmp + 256, &p_c);
+                                                      (int)n_rows, seg, seg, 0, 32, s));
+  int rc = ppk_scratch_carve(dev, SLOT_ITER_B, [&](Carve &c) {
+    c.take(kin, nn).take(kout, nn).take(vin, nn).take(vout, nn).take(seg, n_rows + 1);
+  });
+  if (rc == PPK_OK) rc = ppk_scratch_carve(dev, SLOT_ITER_C, [&](Carve &c) { c.take(d_tmp, tmp + 256); });
   if (rc != PPK_OK) return rc;
-  PPK_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(p_c, tmp, kin, kout, vin, vout, (int)nn,
+  hipLaunchKernelGGL(knn_init_kernel, dim3((unsigned)((nn + n_rows + 256) / 256)), dim3(256), 0, s, kin,
+                     vin, seg, n_rows, n_cols, d_block, stride, col);
+  PPK_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(d_tmp, tmp, kin, kout, vin, vout, (int)nn,
                                                       (int)n_rows, seg, seg + 1, 0, 32, s));
   hipLaunchKernelGGL(knn_pick_kernel, dim3((unsigned)n_rows), dim3(64), 0, s, kout, vout, n_cols,
                      self_offset, knn, d_i, d_j, d_dist);
@@ -519,22 +516,19 @@ int ppk_knn_from_candidates(int dev, const uint32_t *d_keys, const uint64_t *d_v
                             long long missing_j) {
   if (knn > 32) return ppk_fail(PPK_ERR_ARG, "neighbours from tiles: at most 32 neighbours per sample");
   if (count >= (size_t)0x7fffffff) return ppk_fail(PPK_ERR_ARG, "too many neighbour candidates for one sort");
-  const size_t o_keys = 0, o_vals = (count * 4 + 255) & ~(size_t)255, o_tmp = o_vals + ((count * 8 + 255) & ~(size_t)255);
   int end_bit = 1;
   while (((size_t)1 << end_bit) <= n && end_bit < 32) ++end_bit;      // sample ids 0 .. n (n = an empty slot, see requeue)
   size_t tmp = 0;
-  uint32_t *nk = nullptr;
-  uint64_t *nv = nullptr;
-  PPK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, d_keys, nk, d_vals, nv, (int)count, 0, end_bit, s));
-  void *p_c = nullptr;
-  int rc = ppk_scratch_get(dev, SLOT_ITER_C, o_tmp + tmp + 256, &p_c);
+  uint32_t *skeys = nullptr;
+  uint64_t *svals = nullptr;
+  char *d_tmp;
+  PPK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, d_keys, skeys, d_vals, svals, (int)count, 0, end_bit, s));
+  int rc = ppk_scratch_carve(dev, SLOT_ITER_C, [&](Carve &c) {
+    c.take(skeys, count).take(svals, count).take(d_tmp, tmp + 256);
+  });
   if (rc != PPK_OK) return rc;
-  char *C = static_cast<char *>(p_c);
-  uint32_t *skeys = reinterpret_cast<uint32_t *>(C + o_keys);
-  uint64_t *svals = reinterpret_cast<uint64_t *>(C + o_vals);
   if (count)
-    PPK_HIP(hipcub::DeviceRadixSort::SortPairs(C + o_tmp, tmp, d_keys, skeys, d_vals, svals, (int)count, 0,
-                                               end_bit, s));
+    PPK_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp, d_keys, skeys, d_vals, svals, (int)count, 0, end_bit, s));
   const dim3 grid((unsigned)((n + 3) / 4));
   if (knn <= 8)
     hipLaunchKernelGGL(knn_select_sorted_kernel<8>, grid, dim3(256), 0, s, skeys, svals, count, n, knn, missing_j, d_i, d_j,
@@ -566,69 +560,44 @@ extern "C" int ppk_knn_dev(const float *d_square, size_t n, int knn, long long *
 }
 
 // ---- host-buffer forms (what the pybind functions would bind) --------------------------------
-namespace {
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipMalloc failed");
-    return PPK_OK;
-  }
-};
-int h2d(void *d, const void *h, size_t bytes) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipGetDevice failed");
-  return ppk_upload(dev, d, h, bytes, nullptr);      // staged through the pinned ring; ordered on the null stream
-}
-int d2h(void *h, const void *d, size_t bytes) {
-  if (bytes && hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-    return ppk_fail(PPK_ERR_HIP, "hipMemcpy D2H failed");
+// Each is ppk_host_frame: inputs and outputs one layout of SLOT_HOST_IN, the uploads through the pinned ring
+// (ppk_upload), the result's pages touched under them.
+static int download(void *h, const void *d, size_t bytes) {
+  if (bytes) PPK_HIP(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost));
   return PPK_OK;
 }
-}  // namespace
 
 extern "C" int ppk_long_to_square(const float *vec, size_t n, int device_id, float *square) {
   if (n == 0) return PPK_OK;
   if (!vec || !square) return ppk_fail(PPK_ERR_ARG, "NULL buffer");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
   const size_t rows = n * (n - 1) / 2;
   HostToucher toucher(square, n * n * 4);      // the result array's pages, under the upload
-  DevBuf a, b;
-  int rc = a.alloc(rows * 4);
-  if (rc == PPK_OK) rc = b.alloc(n * n * 4);
-  if (rc == PPK_OK) rc = h2d(a.p, vec, rows * 4);
-  if (rc == PPK_OK) rc = ppk_long_to_square_dev(static_cast<float *>(a.p), 1, 0, n, static_cast<float *>(b.p), nullptr);
-  toucher.join();
-  if (rc == PPK_OK) rc = d2h(square, b.p, n * n * 4);
-  return rc;
+  float *d_long, *d_square;
+  return ppk_host_frame(device_id, [&](Carve &c) { c.take(d_long, rows).take(d_square, n * n); }, [&]() -> int {
+    int rc = ppk_upload(device_id, d_long, vec, rows * 4, nullptr);
+    if (rc == PPK_OK) rc = ppk_long_to_square_dev(d_long, 1, 0, n, d_square, nullptr);
+    toucher.join();
+    return rc != PPK_OK ? rc : download(square, d_square, n * n * 4);
+  });
 }
 
 extern "C" int ppk_long_to_square_multi(const float *rr, const float *qr, const float *qq, size_t n_ref,
                                         size_t n_qry, int device_id, float *square) {
   if (!rr || !qr || !qq || !square || n_ref == 0 || n_qry == 0) return ppk_fail(PPK_ERR_ARG, "NULL buffer / empty input");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
   const size_t n_rr = n_ref * (n_ref - 1) / 2, n_qr = n_ref * n_qry, n_qq = n_qry * (n_qry - 1) / 2;
   const size_t n = n_ref + n_qry;
   HostToucher toucher(square, n * n * 4);
-  DevBuf a, b, c, d;
-  int rc = a.alloc(n_rr * 4);
-  if (rc == PPK_OK) rc = b.alloc(n_qr * 4);
-  if (rc == PPK_OK) rc = c.alloc(n_qq * 4);
-  if (rc == PPK_OK) rc = d.alloc(n * n * 4);
-  if (rc == PPK_OK) rc = h2d(a.p, rr, n_rr * 4);
-  if (rc == PPK_OK) rc = h2d(b.p, qr, n_qr * 4);
-  if (rc == PPK_OK) rc = h2d(c.p, qq, n_qq * 4);
-  if (rc == PPK_OK)
-    rc = ppk_long_to_square_multi_dev(static_cast<float *>(a.p), static_cast<float *>(b.p),
-                                      static_cast<float *>(c.p), 1, 0, n_ref, n_qry,
-                                      static_cast<float *>(d.p), nullptr);
-  toucher.join();
-  if (rc == PPK_OK) rc = d2h(square, d.p, n * n * 4);
-  return rc;
+  float *d_rr, *d_qr, *d_qq, *d_square;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_rr, n_rr).take(d_qr, n_qr).take(d_qq, n_qq).take(d_square, n * n);
+  }, [&]() -> int {
+    int rc = ppk_upload(device_id, d_rr, rr, n_rr * 4, nullptr);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_qr, qr, n_qr * 4, nullptr);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_qq, qq, n_qq * 4, nullptr);
+    if (rc == PPK_OK) rc = ppk_long_to_square_multi_dev(d_rr, d_qr, d_qq, 1, 0, n_ref, n_qry, d_square, nullptr);
+    toucher.join();
+    return rc != PPK_OK ? rc : download(square, d_square, n * n * 4);
+  });
 }
 
 // Both square matrices of update_distance_matrices (PopPUNK/utils.py:357-408) from the two-column long
@@ -640,53 +609,41 @@ extern "C" int ppk_long_to_square2(const float *rr, const float *qr, const float
   if (!rr || !core_square || !acc_square || n_ref == 0) return ppk_fail(PPK_ERR_ARG, "ppk_long_to_square2: NULL buffer / empty input");
   if ((n_qry != 0) != (qr != nullptr) || (n_qry != 0 && !qq && n_qry > 1))
     return ppk_fail(PPK_ERR_ARG, "ppk_long_to_square2: query matrices and n_qry do not match");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
   const size_t n_rr = n_ref * (n_ref - 1) / 2, n_qr = n_ref * n_qry, n_qq = n_qry ? n_qry * (n_qry - 1) / 2 : 0;
   const size_t n = n_ref + n_qry;
   HostToucher touch_core(core_square, n * n * 4);
   HostToucher touch_acc(acc_square, n * n * 4);
-  DevBuf a, b, c, d, e;
-  int rc = a.alloc(n_rr * 8);
-  if (rc == PPK_OK && n_qry) rc = b.alloc(n_qr * 8);
-  if (rc == PPK_OK && n_qq) rc = c.alloc(n_qq * 8);
-  if (rc == PPK_OK) rc = d.alloc(n * n * 4);
-  if (rc == PPK_OK) rc = e.alloc(n * n * 4);
-  if (rc == PPK_OK && n_rr) rc = h2d(a.p, rr, n_rr * 8);
-  if (rc == PPK_OK && n_qry) rc = h2d(b.p, qr, n_qr * 8);
-  if (rc == PPK_OK && n_qq) rc = h2d(c.p, qq, n_qq * 8);
-  float *sq[2] = {static_cast<float *>(d.p), static_cast<float *>(e.p)};
-  for (size_t col = 0; col < 2 && rc == PPK_OK; ++col) {
-    if (n_qry == 0) {
-      rc = ppk_long_to_square_dev(static_cast<float *>(a.p), 2, col, n_ref, sq[col], nullptr);
-    } else {
+  float *d_rr, *d_qr, *d_qq, *sq[2];
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_rr, n_rr * 2).take(d_qr, n_qr * 2).take(d_qq, n_qq * 2).take(sq[0], n * n).take(sq[1], n * n);
+  }, [&]() -> int {
+    int rc = ppk_upload(device_id, d_rr, rr, n_rr * 8, nullptr);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_qr, qr, n_qr * 8, nullptr);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_qq, qq, n_qq * 8, nullptr);
+    for (size_t col = 0; col < 2 && rc == PPK_OK; ++col) {
       // (one query: its query-query matrix has no rows; the kernel reads nothing of it)
-      rc = ppk_long_to_square_multi_dev(static_cast<float *>(a.p), static_cast<float *>(b.p),
-                                        static_cast<float *>(n_qq ? c.p : b.p), 2, col, n_ref, n_qry, sq[col], nullptr);
+      rc = n_qry == 0 ? ppk_long_to_square_dev(d_rr, 2, col, n_ref, sq[col], nullptr)
+                      : ppk_long_to_square_multi_dev(d_rr, d_qr, d_qq, 2, col, n_ref, n_qry, sq[col], nullptr);
     }
-  }
-  touch_core.join();
-  if (rc == PPK_OK) rc = d2h(core_square, d.p, n * n * 4);
-  touch_acc.join();
-  if (rc == PPK_OK) rc = d2h(acc_square, e.p, n * n * 4);
-  return rc;
+    touch_core.join();
+    if (rc == PPK_OK) rc = download(core_square, sq[0], n * n * 4);
+    touch_acc.join();
+    return rc != PPK_OK ? rc : download(acc_square, sq[1], n * n * 4);
+  });
 }
 
 extern "C" int ppk_square_to_long(const float *square, size_t n, int device_id, float *vec) {
   if (n < 2) return PPK_OK;
   if (!vec || !square) return ppk_fail(PPK_ERR_ARG, "NULL buffer");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
   const size_t rows = n * (n - 1) / 2;
   HostToucher toucher(vec, rows * 4);
-  DevBuf a, b;
-  int rc = a.alloc(n * n * 4);
-  if (rc == PPK_OK) rc = b.alloc(rows * 4);
-  if (rc == PPK_OK) rc = h2d(a.p, square, n * n * 4);
-  if (rc == PPK_OK) rc = ppk_square_to_long_dev(static_cast<float *>(a.p), n, static_cast<float *>(b.p), nullptr);
-  toucher.join();
-  if (rc == PPK_OK) rc = d2h(vec, b.p, rows * 4);
-  return rc;
+  float *d_square, *d_long;
+  return ppk_host_frame(device_id, [&](Carve &c) { c.take(d_square, n * n).take(d_long, rows); }, [&]() -> int {
+    int rc = ppk_upload(device_id, d_square, square, n * n * 4, nullptr);
+    if (rc == PPK_OK) rc = ppk_square_to_long_dev(d_square, n, d_long, nullptr);
+    toucher.join();
+    return rc != PPK_OK ? rc : download(vec, d_long, rows * 4);
+  });
 }
 
 extern "C" int ppk_prune_long_dev(const float *d_long, size_t n, size_t cols, const long long *d_keep,
@@ -731,42 +688,35 @@ extern "C" int ppk_prune_long(const float *dist, size_t n, size_t cols, const lo
   if (!dist || !keep || !out || cols == 0) return ppk_fail(PPK_ERR_ARG, "NULL buffer");
   int rc = check_keep(keep, n_keep, n);
   if (rc != PPK_OK) return rc;
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
   const size_t rows_in = n * (n - 1) / 2, rows_out = n_keep * (n_keep - 1) / 2;
   HostToucher toucher(out, rows_out * cols * 4);
-  DevBuf a, k, b;
-  rc = a.alloc(rows_in * cols * 4);
-  if (rc == PPK_OK) rc = k.alloc(n_keep * 8);
-  if (rc == PPK_OK) rc = b.alloc(rows_out * cols * 4);
-  if (rc == PPK_OK) rc = h2d(a.p, dist, rows_in * cols * 4);
-  if (rc == PPK_OK) rc = h2d(k.p, keep, n_keep * 8);
-  if (rc == PPK_OK)
-    rc = ppk_prune_long_dev(static_cast<float *>(a.p), n, cols, static_cast<long long *>(k.p), n_keep,
-                            static_cast<float *>(b.p), nullptr);
-  toucher.join();
-  if (rc == PPK_OK) rc = d2h(out, b.p, rows_out * cols * 4);
-  return rc;
+  float *d_in, *d_out;
+  long long *d_keep;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_in, rows_in * cols).take(d_keep, n_keep).take(d_out, rows_out * cols);
+  }, [&]() -> int {
+    int rc = ppk_upload(device_id, d_in, dist, rows_in * cols * 4, nullptr);
+    if (rc == PPK_OK) rc = ppk_upload(device_id, d_keep, keep, n_keep * 8, nullptr);
+    if (rc == PPK_OK) rc = ppk_prune_long_dev(d_in, n, cols, d_keep, n_keep, d_out, nullptr);
+    toucher.join();
+    return rc != PPK_OK ? rc : download(out, d_out, rows_out * cols * 4);
+  });
 }
 
 extern "C" int ppk_knn(const float *square, size_t n, int knn, int device_id, long long *i_out,
                        long long *j_out, float *dist_out) {
   if (n == 0 || knn <= 0) return PPK_OK;
   if (!square || !i_out || !j_out || !dist_out) return ppk_fail(PPK_ERR_ARG, "NULL buffer");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
   const size_t m = n * (size_t)knn;
-  DevBuf a, bi, bj, bd;
-  int rc = a.alloc(n * n * 4);
-  if (rc == PPK_OK) rc = bi.alloc(m * 8);
-  if (rc == PPK_OK) rc = bj.alloc(m * 8);
-  if (rc == PPK_OK) rc = bd.alloc(m * 4);
-  if (rc == PPK_OK) rc = h2d(a.p, square, n * n * 4);
-  if (rc == PPK_OK)
-    rc = ppk_knn_dev(static_cast<float *>(a.p), n, knn, static_cast<long long *>(bi.p),
-                     static_cast<long long *>(bj.p), static_cast<float *>(bd.p), nullptr);
-  if (rc == PPK_OK) rc = d2h(i_out, bi.p, m * 8);
-  if (rc == PPK_OK) rc = d2h(j_out, bj.p, m * 8);
-  if (rc == PPK_OK) rc = d2h(dist_out, bd.p, m * 4);
-  return rc;
+  float *d_square, *d_dist;
+  long long *d_i, *d_j;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_square, n * n).take(d_i, m).take(d_j, m).take(d_dist, m);
+  }, [&]() -> int {
+    int rc = ppk_upload(device_id, d_square, square, n * n * 4, nullptr);
+    if (rc == PPK_OK) rc = ppk_knn_dev(d_square, n, knn, d_i, d_j, d_dist, nullptr);
+    if (rc == PPK_OK) rc = download(i_out, d_i, m * 8);
+    if (rc == PPK_OK) rc = download(j_out, d_j, m * 8);
+    return rc != PPK_OK ? rc : download(dist_out, d_dist, m * 4);
+  });
 }

@@ -65,6 +65,26 @@ def test_labels_and_responsibilities_match_golden():
         assert np.array_equal(lab.cpu().numpy()[:n], g[case + "_labels"][:n]), case
 
 
+def test_host_assign_across_a_chunk_boundary_equals_the_device_path():
+    """ppk_bgmm_assign works through its rows in chunks of 8 Mi from one buffer: three rows more than a chunk take the
+    loop's second pass, and labels and responsibilities asked for together equal the device-array path's."""
+    import ctypes as C
+    import torch
+    from poppunk_amd import _lib, engine
+    m = case_model(golden(), "k2")
+    assert m.n_components == 2
+    n = (8 << 20) + 3
+    X = np.random.Generator(np.random.PCG64(8)).random((n, 2), dtype=np.float32)
+    lab = np.empty(n, dtype=np.int32)
+    resp = np.empty((n, 2), dtype=np.float32)
+    rc = _lib.lib().ppk_bgmm_assign(X.ctypes.data_as(C.POINTER(C.c_float)), n, m.model, 0,
+                                    lab.ctypes.data_as(C.POINTER(C.c_int32)), resp.ctypes.data_as(C.POINTER(C.c_float)))
+    _lib.check(rc, "ppk_bgmm_assign")
+    want_lab, want_resp = engine.bgmm_assign_dev(torch.from_numpy(X).cuda(), m.model, True, True)
+    assert np.array_equal(lab, want_lab.cpu().numpy())
+    assert np.array_equal(resp, want_resp.cpu().numpy())
+
+
 def test_empty_input():
     import torch
     from poppunk_amd import engine

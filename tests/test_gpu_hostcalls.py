@@ -497,6 +497,59 @@ def test_repeated_host_calls_do_not_leak_device_memory():
     assert base - after < (64 << 20), "device memory shrank by %d MB over 25 passes" % ((base - after) >> 20)
 
 
+def _two_component_model(dist):
+    """A BGMM model with one component over the near pairs and one over the far ones."""
+    from poppunk_amd.models import BGMMModel
+    scale = dist.max(axis=0).astype(np.float32)
+    return BGMMModel([0.3, 0.7], [[0.2, 0.2], [0.7, 0.7]], [[[0.02, 0.0], [0.0, 0.02]], [[0.04, 0.01], [0.01, 0.04]]],
+                     scale, 0, 1)
+
+
+def test_host_array_calls_hold_their_memory_steady():
+    """The host-array forms of the matrix transforms, the neighbour lists, extend / lowerRank and the BGMM assignment
+    keep their device buffers in scratch: once a call has run, the same call again leaves the free device memory
+    where it was, and ppk_release_scratch gives back what they hold."""
+    import torch
+    from poppunk_amd import qc
+    rng = np.random.Generator(np.random.PCG64(1000))
+    n = 1000
+    dist = rng.random((n * (n - 1) // 2, 2)).astype(np.float32)
+    col0 = np.ascontiguousarray(dist[:, 0])
+    sq = pp_sketchlib.longToSquare(col0)
+    names = ["s%d" % i for i in range(n)]
+    nn = poppunk_refine.get_kNN_distances(sq, 6)
+    sub = poppunk_refine.get_kNN_distances(np.ascontiguousarray(sq[:900, :900]), 6)
+    qq, qr = np.ascontiguousarray(sq[900:, 900:]), np.ascontiguousarray(sq[:900, 900:])
+    bgmm = _two_component_model(dist)
+    calls = [
+        lambda: pp_sketchlib.longToSquare(col0),
+        lambda: pp_sketchlib.squareToLong(sq),
+        lambda: qc.prune_distance_matrix(names, names[3:600:7], dist, None),
+        lambda: poppunk_refine.get_kNN_distances(sq, 6),
+        lambda: poppunk_refine.get_kNN_distances(sq, 40),
+        lambda: poppunk_refine.lowerRank_arrays(nn, n, 2, True, True, 1e-4),
+        lambda: poppunk_refine.extend_arrays(sub, qq, qr, 6),
+        lambda: bgmm.assign(dist),
+        lambda: bgmm.assign(dist, values=True),
+    ]
+
+    def free_bytes():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info(0)[0]
+
+    pp_sketchlib.clear_cache()
+    _lib.lib().ppk_release_scratch()
+    start = free_bytes()
+    for k, call in enumerate(calls):
+        call()
+        warm = free_bytes()
+        call()
+        again = free_bytes()
+        assert abs(warm - again) < (64 << 20), "call %d moved free device memory by %d MB" % (k, (warm - again) >> 20)
+    _lib.lib().ppk_release_scratch()
+    assert abs(start - free_bytes()) < (64 << 20)
+
+
 def test_fused_host_edge_call_is_steady_at_100k_genomes():
     """BENCH_r03 recorded [271, 801, 271] ms for three calls of ppk_query_edges_dbs at 100 000 genomes.  Until round 4
     every call allocated its device edge list (rows / 8 entries: 10 GB here) and freed it again; the list is now kept
@@ -549,6 +602,10 @@ def test_host_entry_points_from_four_threads_at_once():
     dist, _ = pp_sketchlib.query_arrays(sk, None, KMERS, 16, 14, tbl)
     x_max, y_max = synth.boundary_for_quantile(dist, 0.1)
     sq = pp_sketchlib.longToSquare(np.ascontiguousarray(dist[:, 1]))
+    col0 = np.ascontiguousarray(dist[:, 0])
+    sub = poppunk_refine.get_kNN_distances(np.ascontiguousarray(sq[:400, :400]), 5)
+    qq, qr = np.ascontiguousarray(sq[400:, 400:]), np.ascontiguousarray(sq[:400, 400:])
+    bgmm = _two_component_model(dist)
 
     jobs = [
         lambda: pp_sketchlib.query_arrays(sk, None, KMERS, 16, 14, tbl)[0],
@@ -559,6 +616,9 @@ def test_host_entry_points_from_four_threads_at_once():
         lambda: qc.qc_edge_lists(dist, 0, 0.02, 0.3)[0],
         lambda: poppunk_refine.assignThreshold(dist, 1, x_max, y_max),
         lambda: np.stack(poppunk_refine.thresholdIterate2D_arrays(dist, np.linspace(0.01, x_max, 6), y_max)),
+        lambda: np.stack(poppunk_refine.extend_arrays(sub, qq, qr, 4)[:2]),
+        lambda: pp_sketchlib.longToSquare(col0),
+        lambda: bgmm.assign(dist),
     ]
     want = [j() for j in jobs]
     errors = []
@@ -566,7 +626,7 @@ def test_host_entry_points_from_four_threads_at_once():
     def worker(t):
         try:
             for rep in range(6):
-                for idx in range(t, len(jobs), 4):          # thread t: jobs t and t + 4
+                for idx in range(t, len(jobs), 4):          # thread t: jobs t, t + 4, t + 8
                     if not np.array_equal(jobs[idx](), want[idx]):
                         errors.append("thread %d job %d rep %d differs" % (t, idx, rep))
         except Exception as e:  # noqa: BLE001

@@ -255,3 +255,63 @@ def test_lineage_ranks_extended_from_databases(tmp_path, monkeypatch):
     for m, w in ((b.nn_dists, a.nn_dists), (b.lower_rank_dists[2], a.lower_rank_dists[2])):
         assert np.array_equal(m.row, w.row) and np.array_equal(m.col, w.col) and np.array_equal(m.data, w.data)
     pp_sketchlib.clear_cache()
+
+
+# ---- the calls share grow-only scratch: what one call leaves behind must never reach the next ---------------------
+
+def _check_lower_rank(n, depth, levels, unique=False, recip=False):
+    """One case of test_lower_rank, compared the same way."""
+    rng = np.random.Generator(np.random.PCG64(n * 7 + depth))
+    coo = _knn_coo(_square(rng, n, levels), min(depth, n - 1))
+    for knn in (1, 2, 3, depth + 2):
+        for eps in ((0.0, 1e-3, 0.06) if unique else (0.0,)):
+            want = oracle.lower_rank(*coo, n, knn, reciprocal_only=recip, count_unique_distances=unique, epsilon=eps)
+            _same(poppunk_refine.lowerRank_arrays(coo, n, knn, recip, unique, eps), want)
+
+
+def _check_extend(n_ref, n_qry, depth, levels):
+    """One case of test_extend, compared the same way."""
+    rng = np.random.Generator(np.random.PCG64(n_ref * 3 + n_qry))
+    rr = _square(rng, n_ref, levels)
+    coo = _knn_coo(rr, min(depth, n_ref - 1))
+    qq = _square(rng, n_qry, levels)
+    qr = (rng.integers(1, levels + 1, size=(n_ref, n_qry)).astype(np.float32) / np.float32(levels * 4))
+    for knn in (1, depth, depth + 3):
+        _same(poppunk_refine.extend_arrays(coo, qq, qr, knn), oracle.extend(*coo, qq, qr, knn))
+
+
+def test_calls_that_shrink_grow_and_share_the_scratch():
+    """Large, small and large again through the same blocks, another host call in between: a flag word or offsets
+    left over from the call before, buffers that overlap at small counts, pointers that outlive a block's growth and
+    host calls overwriting each other's uploads would each change a result here."""
+    from poppunk_amd import pp_sketchlib
+    _check_lower_rank(257, 10, 50, unique=True, recip=True)
+    _check_extend(64, 200, 5, 40)
+    _check_lower_rank(3, 2, 2)
+    _check_extend(5, 1, 3, 2)
+    rng = np.random.Generator(np.random.PCG64(65))
+    vec = rng.random(65 * 64 // 2).astype(np.float32)
+    assert np.array_equal(pp_sketchlib.longToSquare(vec), oracle.long_to_square(vec))
+    _check_lower_rank(1000, 12, 7)
+    _check_extend(500, 61, 9, 6)
+    # an empty sparse matrix: beside one query and five references, beside several queries, beside references
+    # alone (nothing to keep) and beside queries alone
+    none = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32))
+    for n_ref, n_qry in ((5, 1), (4, 3), (6, 0), (0, 4)):
+        qq = _square(rng, n_qry, 3) if n_qry else np.zeros((0, 0), np.float32)
+        qr = (rng.integers(1, 4, size=(n_ref, n_qry)) / np.float32(8)).astype(np.float32)
+        for knn in (1, 3):
+            _same(poppunk_refine.extend_arrays(none, qq, qr, knn), oracle.extend(*none, qq, qr, knn))
+
+
+def test_lower_rank_refuses_descending_rows_then_answers_a_good_call_of_the_same_shape():
+    """The input of test_lower_rank_rows_with_self_entries_gaps_and_bad_input with its rows reversed is refused --
+    before anything indexes by the row starts computed from it -- and the flag is armed again for the next call."""
+    ri = np.asarray([0, 0, 0, 2, 2, 2, 3, 3, 3, 3, 5], dtype=np.int64)
+    rj = np.asarray([3, 1, 2, 2, 0, 5, 0, 1, 2, 5, 3], dtype=np.int64)
+    rd = np.asarray([.3, .1, .2, 0., .2, .1, .5, .5, .5, .5, .5], dtype=np.float32)
+    for recip in (False, True):
+        with pytest.raises(RuntimeError, match="ascending"):
+            poppunk_refine.lowerRank_arrays((ri[::-1].copy(), rj, rd), 6, 2, recip, True, 1e-5)
+        _same(poppunk_refine.lowerRank_arrays((ri, rj, rd), 6, 2, recip, True, 1e-5),
+              oracle.lower_rank(ri, rj, rd, 6, 2, recip, True, 1e-5))
