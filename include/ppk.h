@@ -157,6 +157,16 @@ int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t nk,
                   int src_on_device, void *stream, ppk_db **out);
 void ppk_db_destroy(ppk_db *db);
 size_t ppk_db_size(const ppk_db *db);
+/* A bbits = 14 database whose self job runs whole pair tiles (option "ksplit" and the job's size decide) also keeps
+ * a rank-coded copy: every bin value replaced by its rank among the distinct values of its (k, bin) position over the
+ * database's samples, in 8, 10 or 12 bit-planes instead of 14 (the smallest that hold the ranks; none beyond 4 096
+ * distinct values).  Equal values keep equal codes and different values different ones, so a self job on such a
+ * database counts the same matches, and returns the same bits, from fewer planes.  Costs up to 12/14 of the
+ * database's memory again and one pass at creation; option "rank_planes" 0 (PPK_RANK_PLANES) builds and reads none.
+ * ppk_db_rank_planes: the planes of the copy, 0 without one.  ppk_db_rank_read (tests): the copy as it lies,
+ * [k][block * planes + plane][padded samples (a multiple of 256)] uint64, `words` = its exact length. */
+int ppk_db_rank_planes(const ppk_db *db);
+int ppk_db_rank_read(const ppk_db *db, uint64_t *out, size_t words);
 
 /* Number of distance rows for rows q in [q_begin, q_end) (self: n_qry == 0). */
 size_t ppk_rows_in_band(size_t n_ref, size_t n_qry, size_t q_begin, size_t q_end);

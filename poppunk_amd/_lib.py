@@ -115,6 +115,8 @@ SIGNATURES = {
                                 C.POINTER(_vp)]),
     "ppk_db_destroy": (None, [_vp]),
     "ppk_db_size": (_sz, [_vp]),
+    "ppk_db_rank_planes": (C.c_int, [_vp]),
+    "ppk_db_rank_read": (C.c_int, [_vp, _vp, _sz]),
     "ppk_rows_in_band": (_sz, [_sz, _sz, _sz, _sz]),
     "ppk_band_split": (C.c_int, [_sz, _sz, C.c_int, _szp]),
     "ppk_dist_dev": (C.c_int, [_vp, _vp, _i32p, _f32p, _sz, C.c_int, _sz, _sz, _vp, _vp, _vp]),
@@ -281,7 +283,7 @@ def sources_hash_now():
              "ppk_sparse.hip", "ppk_bgmm.hip", "ppk_network.hip", "ppk_mst.hip", "ppk_nj.hip", "ppk_embed.hip",
              "ppk_dbscan.hip", "ppk_bgmm_fit.hip", "ppk_h5.cpp",
              "ppk_internal.h",
-             "ppk_block_asm.inc", "../../include/ppk.h"]
+             "ppk_block_asm.inc", "ppk_dist_tile.inc", "../../include/ppk.h"]
     h = hashlib.sha256()
     try:
         for n in names:

@@ -56,6 +56,7 @@ const OptionEntry kOptions[] = {
     {"strip", "PPK_STRIP", &PpkConfig::strip},
     {"edge_list_keep", "PPK_EDGE_LIST_KEEP", &PpkConfig::edge_list_keep},
 #endif
+    {"rank_planes", "PPK_RANK_PLANES", &PpkConfig::rank_planes},
     {"lds_table", "PPK_LDS_TABLE", &PpkConfig::lds_table},
     {"ksplit", "PPK_KSPLIT", &PpkConfig::ksplit},
     {"ksplit_slices", "PPK_KSPLIT_SLICES", &PpkConfig::ksplit_slices},
@@ -386,12 +387,15 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   db->words = sketchsize64 * bbits;
   db->d_skT = nullptr;
   db->d_clu = nullptr;
+  db->d_skR = nullptr;
+  db->rank_planes = 0;
   const size_t cols = nk * db->words;
   const size_t in_bytes = n * cols * sizeof(uint64_t);
   const size_t out_bytes = db->npad * cols * sizeof(uint64_t);
 
   auto bail = [&](int code, const std::string &msg) {
     if (db->d_skT) (void)hipFree(db->d_skT);
+    if (db->d_skR) (void)hipFree(db->d_skR);
     if (db->d_clu) (void)hipFree(db->d_clu);
     delete db;
     return ppk_fail(code, msg);
@@ -421,6 +425,38 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
       e = hipErrorUnknown;
     if (e != hipSuccess) rc = PPK_ERR_HIP;
   }
+  // Rank-coded copy (ppk_db::d_skR), once per database: D = the most distinct values any (k, bin) position holds over
+  // the samples decides the planes (8, 10 or 12; more than 4 096 values: no copy).  Only a database whose self job runs
+  // whole tiles reads one (launch_v2), so only such a database pays for one.  The count is read back: one
+  // synchronisation of `s` per database.
+  if (rc == PPK_OK && ppk_config().rank_planes.load() != 0 && ppk_self_job_takes_tiles(db)) {
+    unsigned *d_max = nullptr;
+    unsigned distinct = 0;
+    e = hipMalloc(reinterpret_cast<void **>(&d_max), sizeof(unsigned));
+    if (e == hipSuccess) {
+      rc = ppk_launch_rank_count(db->d_skT, n, db->npad, nk, sketchsize64, d_max, s);
+      if (rc == PPK_OK) {
+        e = hipMemcpyAsync(&distinct, d_max, sizeof(unsigned), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = ppk_fail(PPK_ERR_HIP, std::string("rank codes: ") + hipGetErrorString(e));
+      }
+      (void)hipFree(d_max);
+      const int planes = distinct <= 256 ? 8 : distinct <= 1024 ? 10 : distinct <= 4096 ? 12 : 0;
+      if (rc == PPK_OK && planes) {
+        // (a device too full for the copy keeps the raw planes alone: the copy only buys speed)
+        e = hipMalloc(reinterpret_cast<void **>(&db->d_skR), db->npad * nk * sketchsize64 * (size_t)planes * sizeof(uint64_t));
+        if (e != hipSuccess) {
+          (void)hipGetLastError();
+          db->d_skR = nullptr;
+        } else {
+          rc = ppk_launch_rank_codes(db->d_skT, db->d_skR, n, db->npad, nk, sketchsize64, planes, s);
+          db->rank_planes = planes;
+        }
+      }
+    } else {
+      (void)hipGetLastError();
+    }
+  }
   // the staging copy must outlive the transpose; the host-source path blocks here
   if (d_stage) {
     (void)hipStreamSynchronize(s);
@@ -435,11 +471,24 @@ extern "C" void ppk_db_destroy(ppk_db *db) {
   if (!db) return;
   DeviceGuard guard(db->device);
   if (db->d_skT) (void)hipFree(db->d_skT);
+  if (db->d_skR) (void)hipFree(db->d_skR);
   if (db->d_clu) (void)hipFree(db->d_clu);
   delete db;
 }
 
 extern "C" size_t ppk_db_size(const ppk_db *db) { return db ? db->n : 0; }
+extern "C" int ppk_db_rank_planes(const ppk_db *db) { return db ? db->rank_planes : 0; }
+extern "C" int ppk_db_rank_read(const ppk_db *db, uint64_t *out, size_t words) {
+  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_rank_read: NULL argument");
+  if (!db->rank_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_rank_read: the database has no rank-coded copy");
+  if (words != db->nk * db->s64 * (size_t)db->rank_planes * db->npad)
+    return ppk_fail(PPK_ERR_ARG, "ppk_db_rank_read: `words` is not nk * sketchsize64 * planes * padded samples");
+  DeviceGuard guard(db->device);
+  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(db->device));
+  PPK_HIP(hipDeviceSynchronize());
+  PPK_HIP(hipMemcpy(out, db->d_skR, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return PPK_OK;
+}
 
 // ---- kernel 1, device entry points -------------------------------------------------
 int ppk_check_pair(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, size_t q_begin,

@@ -28,6 +28,12 @@ struct ppk_db {
   size_t n, npad, nk, s64, bbits, words;   // words = s64*bbits per (sample,k)
   uint64_t *d_skT;                         // [(k*words + w)*npad + sample]
   uint16_t *d_clu;                         // [npad] or nullptr
+  // bbits = 14 only: the same sketches with every bin value replaced by its rank among the distinct values of its
+  // (k, bin) position, bit-sliced in rank_planes (8, 10 or 12; 0 = no such copy) planes: [(k*s64 + blk)*rank_planes +
+  // plane][npad].  Equal values have equal codes and different values different ones, so a self job counts the same
+  // matches from fewer planes (launch_v2 in ppk_dist.hip).
+  uint64_t *d_skR;
+  int rank_planes;
 };
 
 // A database whose per-pair counts the tile kernels cannot hold: more k-mer lengths than the fit tables are laid
@@ -55,6 +61,7 @@ struct PpkConfig {
   std::atomic<long long> edge_list_keep{1};     // PPK_EDGE_LIST_KEEP: the fused host edge call keeps its device list buffer between calls (0: allocate + free per call, measurement)
 #endif
   // -- product options
+  std::atomic<long long> rank_planes{1};        // PPK_RANK_PLANES: a bbits = 14 database whose self job runs whole tiles keeps a rank-coded copy (ppk_db::d_skR) and self jobs compare it (0: no copy is built, none is read; same bits)
   std::atomic<long long> lds_table{1};          // PPK_LDS_TABLE: interior tiles of the default sketch shape fit from the (E, F) table in LDS (0: the general statement everywhere; same bits)
   std::atomic<long long> ksplit{1200};           // PPK_KSPLIT: tile-count threshold (at 5 k) of the small-job path
   std::atomic<long long> ksplit_wide{215};      // PPK_KSPLIT_WIDE: the same threshold for sketches whose tiles are not fitted from the LDS table (never above ksplit)
@@ -152,6 +159,11 @@ struct PpkRouteChoice {
   size_t tiles, limit, scratch_bytes;
 };
 PpkRouteChoice ppk_choose_route_impl(const PpkRouteShape &sh, const PpkGeometry &g, const PpkRouteKnobs &k);
+// rank-coded copy of a bbits = 14 database (ppk_dist.hip)
+bool ppk_self_job_takes_tiles(const ppk_db *db);
+int ppk_launch_rank_count(const uint64_t *d_skT, size_t n, size_t npad, size_t nk, size_t s64, unsigned *d_max, hipStream_t s);
+int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, size_t n, size_t npad, size_t nk, size_t s64, int planes,
+                          hipStream_t s);
 
 // Profiling hooks (ppk_prof_*) -------------------------------------------------
 void ppk_prof_begin(hipStream_t s);

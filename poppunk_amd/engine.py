@@ -127,6 +127,23 @@ class SketchDB:
     def __len__(self):
         return self.n
 
+    @property
+    def rank_planes(self):
+        """Bit-planes of the database's rank-coded copy (8, 10 or 12), 0 without one (ppk_db_rank_planes)."""
+        return int(_lib.lib().ppk_db_rank_planes(self._h))
+
+    def rank_codes(self):
+        """The rank-coded copy un-bitsliced (tests): uint16 [n, nk, 64 * sketchsize64] codes."""
+        planes, npad = self.rank_planes, (self.n + 255) // 256 * 256
+        raw = np.empty((self.nk, self.sketchsize64, planes, npad), dtype=np.uint64)
+        _lib.check(_lib.lib().ppk_db_rank_read(self._h, C.c_void_p(raw.ctypes.data), raw.size), "ppk_db_rank_read")
+        bits = np.unpackbits(raw[..., :self.n].view(np.uint8).reshape(self.nk, self.sketchsize64, planes, self.n, 8),
+                             axis=-1, bitorder="little")      # [k, blk, plane, sample, 64 bins]
+        codes = np.zeros((self.nk, self.sketchsize64, self.n, 64), dtype=np.uint16)
+        for b in range(planes):
+            codes |= bits[:, :, b].astype(np.uint16) << b
+        return np.ascontiguousarray(codes.transpose(2, 0, 1, 3)).reshape(self.n, self.nk, 64 * self.sketchsize64)
+
 
 def _prep_tables(kmers, random_tbl, nk):
     kmers = np.ascontiguousarray(kmers, dtype=np.int32)

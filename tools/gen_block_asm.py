@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Generates poppunk_amd/csrc/ppk_block_asm.inc: the hand-scheduled gfx950 instruction
-stream for ONE 64-bin block (14 bit-planes) of the 4-ref x 4-query register tile.
+stream for ONE 64-bin block (14 bit-planes) of the 4-ref x 4-query register tile, and the same
+stream for the 12, 10 and 8 planes of a rank-coded database (RANK_PLANES below).
 
 Why assembly: on MI355X a v_bitop3_b32 whose src0 and src1 sit in the same VGPR bank
 (register number mod 4) issues ~1.5x slower (tools/ubench_bank.hip: 4.7 vs 3.1 clk).  hipcc
@@ -24,6 +25,18 @@ import os
 import sys
 
 BB = 14
+# Plane counts of a rank-coded database (ppk_db::rank_planes): every bin value replaced by its rank among the
+# distinct values of its position, so that fewer planes decide equality.  Per count: (DMA pieces per wavefront,
+# planes that carry them).  The 14-plane block spends its 4 pieces at planes 1 / 4 / 7 / 10 and lets the priority
+# fall at planes 0 / 4 / 8 / 12; the shorter blocks keep the same spacing relative to their length.  The LAST piece
+# of a wavefront is the one that may be a query piece or nothing at all (its exec mask is then 0): with P planes
+# there are 2 P ref pieces and ceil(P / 4) query pieces for 8 wavefronts.
+RANK_PLANES = {12: (4, (1, 3, 6, 9)), 10: (3, (1, 4, 7)), 8: (3, (1, 3, 5))}
+
+
+def prio_levels(bb, v):
+    """the four falling priorities of the 14-plane block, rescaled to a block of bb planes"""
+    return [v[min(3, (b * BB // bb) // 4)] for b in range(bb)]
 
 
 class Map:
@@ -60,7 +73,7 @@ REF_PLANE_BYTES = 2048      # 256 samples x 8 B
 REF_HALF_BYTES = 1024
 
 
-def gen(QRY_PLANE_BYTES, TQ=4, dma_planes=None, half=False, a2=False):
+def gen(QRY_PLANE_BYTES, TQ=4, dma_planes=None, half=False, a2=False, bb=BB):
     """TQ = 4: counters %[c0]..%[c15], one per pair (p = 4r + q).
     TQ = 8: counters %[c0]..%[c15], two pairs per counter (pair p = 8r + q -> counter p >> 1,
     16-bit half p & 1; a block adds at most 64 and a k at most 16 * 64 per pair ... callers
@@ -78,20 +91,23 @@ def gen(QRY_PLANE_BYTES, TQ=4, dma_planes=None, half=False, a2=False):
         opening burst of ds_reads).  Operands: %[m00] / %[m03] LDS byte address of piece 0 / 3
         (pieces 1, 2 are 8 KB apart), %[sb0..3] 64-bit global base of each piece, %[voa] / %[vob]
         per-lane byte offset of pieces 0-2 / 3, %[xblo],%[xbhi] exec mask of piece 3 (the last query
-        piece has fewer rows).  After the last block the caller lets the pieces re-load that block."""
+        piece has fewer rows; all zero for a wavefront whose last slot is empty: the instruction then
+        issues nothing).  "3" names the wavefront's LAST piece, which is piece 2 where a block has fewer
+        than 25 pieces.  After the last block the caller lets the pieces re-load that block."""
+        last = len(dma_planes) - 1      # (3 in the 14- and 12-plane blocks, 2 in the shorter ones)
         if t == 0:
             emit("s_mov_b32 m0, %[m00]")
-        elif t < 3:
+        elif t < last:
             emit("s_add_u32 m0, %%[m00], %d" % (8192 * t))
         else:
             emit("s_mov_b32 m0, %[m03]")
-        if t == 3:      # (a 64-bit "s" operand is not reliably kept in SGPRs by the compiler: halves)
+        if t == last:      # (a 64-bit "s" operand is not reliably kept in SGPRs by the compiler: halves)
             emit("s_mov_b32 exec_lo, %[xblo]")
             emit("s_mov_b32 exec_hi, %[xbhi]")
         else:
             emit("s_nop 0")     # m0 write -> LDS-DMA needs one wait state
-        emit("global_load_lds_dwordx4 %%[%s], %%[sb%d]" % ("voa" if t < 3 else "vob", t))
-        if t == 3:
+        emit("global_load_lds_dwordx4 %%[%s], %%[sb%d]" % ("voa" if t < last else "vob", t))
+        if t == last:
             emit("s_mov_b64 exec, -1")
 
     def load_s(plane):
@@ -132,15 +148,15 @@ def gen(QRY_PLANE_BYTES, TQ=4, dma_planes=None, half=False, a2=False):
     prio = None
     if dma_planes:       # (the full block of the packed modes; on the half block it measured 1 % worse)
         v = [int(x) for x in os.environ.get("GEN_PRIO", "3,2,1,0").split(",")]
-        prio_cnt = v.pop() if len(v) == BB + 1 else None      # (a 15th value: the popcount tail)
-        prio = v if len(v) == BB else [v[b // 4] for b in range(BB)]
+        prio_cnt = v.pop() if len(v) == bb + 1 else None      # (a 15th value: the popcount tail)
+        prio = v if len(v) == bb else prio_levels(bb, v)
     if half:
         # Diagonal tiles whose queries all lie beyond the tile's first 128 refs: refs 0/1 of every
         # lane pair with nothing, so only refs 2/3 (the a1 operands) are compared: half the stream.
         load_s(0)
         load_a1(0)
-        for b in range(BB):
-            last = b == BB - 1
+        for b in range(bb):
+            last = b == bb - 1
             if prio and (b == 0 or prio[b] != prio[b - 1]):
                 emit("s_setprio %d" % prio[b])
             if not last:
@@ -167,8 +183,8 @@ def gen(QRY_PLANE_BYTES, TQ=4, dma_planes=None, half=False, a2=False):
         load_s(0)
         load_a0(0)
         load_a1(0)
-        for b in range(BB):
-            last = b == BB - 1
+        for b in range(bb):
+            last = b == bb - 1
             if prio and (b == 0 or prio[b] != prio[b - 1]):
                 emit("s_setprio %d" % prio[b])
             if not last:
@@ -189,8 +205,8 @@ def gen(QRY_PLANE_BYTES, TQ=4, dma_planes=None, half=False, a2=False):
     load_s(0)
     load_a0(0)
     load_a1(0)
-    for b in range(BB):
-        last = b == BB - 1
+    for b in range(bb):
+        last = b == bb - 1
         if prio and (b == 0 or prio[b] != prio[b - 1]):
             emit("s_setprio %d" % prio[b])
         if not last:
@@ -259,6 +275,12 @@ def main():
         write_macro(f, "PPK_BLOCK_HALF_ASM_Q32", gen(256, 4, half=True))
         f.write("#define PPK_BLOCK_ASM PPK_BLOCK_ASM_Q32\n")
         f.write("#define PPK_BLOCK_CLOBBERS %s\n" % clob)
+        # the packed two-dword kernel on a rank-coded database: the in-stream-DMA and the half block per plane count
+        # (GEN_DMA_PLANES applies to the 14-plane block only)
+        for pl, (_, dplanes) in sorted(RANK_PLANES.items(), reverse=True):
+            f.write("// %d planes (rank-coded database)\n" % pl)
+            write_macro(f, "PPK_BLOCK_DMA_ASM_Q32_P%d" % pl, gen(256, 4, dma_planes=list(dplanes), bb=pl))
+            write_macro(f, "PPK_BLOCK_HALF_ASM_Q32_P%d" % pl, gen(256, 4, half=True, bb=pl))
     if "--experiments" not in sys.argv[1:]:
         return
     # measured-and-rejected shapes: generated on demand, not tracked (tools/ubench_pipe.hip needs them)
