@@ -47,6 +47,7 @@ extern "C" {
 #define PPK_ERR_CAPACITY 3 /* caller-provided output too small               */
 #define PPK_ERR_STATE 4    /* call sequence error                            */
 #define PPK_ERR_INTERRUPTED 5 /* the interrupt check asked to stop (Ctrl-C)   */
+#define PPK_REFINE_NOT_NESTED 6 /* ppk_refine_local_create_dev: the two lines form no bracket (use ppk_refine_score_dev) */
 
 /* flags of ppk_query / ppk_dist_dev: the random_correct and jaccard booleans of
  * pp_sketchlib.queryDatabase (PopPUNK/sketchlib.py:528-537,:547-566) */
@@ -104,6 +105,9 @@ int ppk_device_count(int *n);
  *     "sweep_window" (1)   the classify pass of ppk_threshold_iterate_1d/2d_dev finds how many boundaries hold a row by
  *                          bisection when the boundaries are nested outwards (refine's sweeps are); 0 = every boundary
  *                          is evaluated for every row the filter keeps (same results; the GPU suite runs both)
+ *   refine fit
+ *     "refine_local" (1)   refineFit's local search scores its evaluations through the bracket handle
+ *                          (ppk_refine_local_*); 0 = every evaluation through ppk_refine_score_dev (same fit)
  *   host calls
  *     "chunk_rows" (8 Mi)  rows per sub-band of a host query (about an eighth of the job, at least 1 Mi, below 16 Mi
  *                          rows); also scales the pieces of the fused host edge call
@@ -600,6 +604,38 @@ int ppk_threshold_iterate_2d_dev(const float *d_dist, size_t n_rows, const float
                                  size_t n_off, float y_max, long long *d_i, long long *d_j,
                                  long long *d_off, size_t cap, unsigned long long *d_n_out,
                                  void *stream);
+
+/* ------------------------------------------------------------------------
+ * Fitting the refine boundary: the network counts of ONE boundary, what refine's local search
+ * (scipy's bounded minimiser around newNetwork, PopPUNK/refine.py:221-232,:476-548) asks for per evaluation.
+ * d_dist: a resident self/condensed float32 [n_rows][2] matrix, n_rows = n(n-1)/2 >= 1, 8-byte aligned.
+ * d_stats: device int64 [4] = {edges, connected components, triangles, connected triples} of the graph over n vertices
+ * of every row with line_dist <= 0 (edgeThreshold's rows, inclusive): bit for bit ppk_edge_threshold_dev followed by
+ * ppk_network_sweep_dev at one offset.  No edge list is formed.  Integer atomics only: the same input gives the same
+ * counts on every call.  Synchronises the stream once (the read-back of the counts: they are written on return). */
+int ppk_refine_score_dev(const float *d_dist, size_t n_rows, int slope, float x_max, float y_max, long long *d_stats,
+                         void *stream);
+/* host arrays: dist float32 [n_rows][2], stats int64 [4]; blocking */
+int ppk_refine_score(const float *dist, size_t n_rows, int slope, float x_max, float y_max, int device_id,
+                     long long *stats);
+/* The same counts for every line between two nested lines, from a handle that does the common work once.
+ * create: (x_lo, y_lo) the inner and (x_hi, y_hi) the outer line; x_lo <= x_hi and y_lo <= y_hi (slope 0: only the x
+ * pair is read, slope 1: only the y pair; slope 2 also needs x_lo, y_lo >= 2^-40 and finite intercepts).  Otherwise
+ * PPK_REFINE_NOT_NESTED (a status of its own, *out = NULL): the caller scores with ppk_refine_score_dev.  One pass
+ * sorts the rows into base (edges of every line of the bracket), never (of none) and candidates (kept with their
+ * coordinates, in row order); the base graph stays resident in the handle (n^2 / 8 bytes).  The matrix is not read
+ * after create returns.  Synchronises the stream (the candidate count sizes the handle).
+ * eval: d_stats as ppk_refine_score_dev gives for the same line, all four counts, for every line with
+ * x_lo <= x_max <= x_hi and y_lo <= y_max <= y_hi (slope 0: x only, slope 1: y only); PPK_ERR_ARG outside.  Changes
+ * nothing in the handle; synchronises the stream once.
+ * stats: split[3] = rows that are {base, candidates, never}; host only. */
+typedef struct ppk_refine_local ppk_refine_local;
+int ppk_refine_local_create_dev(const float *d_dist, size_t n_rows, int slope, float x_lo, float y_lo, float x_hi,
+                                float y_hi, void *stream, ppk_refine_local **out);
+void ppk_refine_local_destroy(ppk_refine_local *handle);
+int ppk_refine_local_stats(const ppk_refine_local *handle, unsigned long long *split);
+int ppk_refine_local_eval_dev(const ppk_refine_local *handle, float x_max, float y_max, long long *d_stats,
+                              void *stream);
 
 /* ------------------------------------------------------------------------
  * Network scores of the sweeps.  For vertices 0 .. n_vertices-1 and G_t = the graph of every edge

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("PPK_LIBRARY") or os.path.join(_HERE, "csrc", "libppk_hip.so")
 
 OK, ERR_ARG, ERR_HIP, ERR_CAPACITY, ERR_STATE, ERR_INTERRUPTED = 0, 1, 2, 3, 4, 5
+REFINE_NOT_NESTED = 6      # ppk_refine_local_create_dev: the two lines do not form a bracket
 FLAG_RANDOM_CORRECT, FLAG_JACCARD, FLAG_COUNTS = 1, 2, 4
 
 # every symbol include/ppk.h declares: name -> (restype, argtypes)
@@ -107,6 +108,13 @@ SIGNATURES = {
     "ppk_dbscan_edges_dev": (C.c_int, [_vp, _sz, _sz, _vp, C.c_longlong, _vp, _sz, _vp, _vp]),
     "ppk_dbscan_assign": (C.c_int, [_f32p, _sz, _vp, _i32p]),
     "ppk_dbscan_stats": (C.c_int, [_vp, _ullp]),
+    "ppk_refine_score_dev": (C.c_int, [_vp, _sz, C.c_int, C.c_float, C.c_float, _vp, _vp]),
+    "ppk_refine_score": (C.c_int, [_f32p, _sz, C.c_int, C.c_float, C.c_float, C.c_int, _llp]),
+    "ppk_refine_local_create_dev": (C.c_int, [_vp, _sz, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _vp,
+                                              C.POINTER(_vp)]),
+    "ppk_refine_local_destroy": (None, [_vp]),
+    "ppk_refine_local_stats": (C.c_int, [_vp, _ullp]),
+    "ppk_refine_local_eval_dev": (C.c_int, [_vp, C.c_float, C.c_float, _vp, _vp]),
     "ppk_last_error": (C.c_char_p, []),
     "ppk_version": (C.c_char_p, []),
     "ppk_release_scratch": (C.c_int, []),
@@ -281,7 +289,7 @@ def sources_hash_now():
     here = os.path.join(_HERE, "csrc")
     names = ["ppk_api.hip", "ppk_host.hip", "ppk_dist.hip", "ppk_boundary.hip", "ppk_iterate.hip", "ppk_square.hip",
              "ppk_sparse.hip", "ppk_bgmm.hip", "ppk_network.hip", "ppk_mst.hip", "ppk_nj.hip", "ppk_embed.hip",
-             "ppk_dbscan.hip", "ppk_bgmm_fit.hip", "ppk_h5.cpp",
+             "ppk_dbscan.hip", "ppk_bgmm_fit.hip", "ppk_refine.hip", "ppk_h5.cpp",
              "ppk_internal.h",
              "ppk_block_asm.inc", "ppk_dist_tile.inc", "../../include/ppk.h"]
     h = hashlib.sha256()

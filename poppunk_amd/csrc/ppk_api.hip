@@ -80,6 +80,7 @@ const OptionEntry kOptions[] = {
     {"bt_lds_max", "PPK_BT_LDS_MAX", &PpkConfig::bt_lds_max},
     {"bt_small_max", "PPK_BT_SMALL_MAX", &PpkConfig::bt_small_max},
     {"dbscan_search", "PPK_DBSCAN_SEARCH", &PpkConfig::dbscan_search},
+    {"refine_local", "PPK_REFINE_LOCAL", &PpkConfig::refine_local},
     {"host_parts", "PPK_HOST_PARTS", &PpkConfig::host_parts},
     {"host_parts_rows", "PPK_HOST_PARTS_ROWS", &PpkConfig::host_parts_rows},
     {"host_trace", "PPK_HOST_TRACE", &PpkConfig::host_trace},

@@ -85,6 +85,7 @@ struct PpkConfig {
   std::atomic<long long> bt_lds_max{0};        // PPK_BT_LDS_MAX: largest component whose Brandes state lives in LDS (0 = as many vertices as LDS holds; small values force the global-state path: tests; results within rounding)
   std::atomic<long long> bt_small_max{64};      // PPK_BT_SMALL_MAX: largest component Brandes gives one wave for all its sources (0 = none; at most 256; results within rounding)
   std::atomic<long long> dbscan_search{0};      // PPK_DBSCAN_SEARCH: the DBSCAN assignment's search: 0 = the grid from 1 024 training points up, 1 = the scan of every training point, 2 = the grid at any size (same labels)
+  std::atomic<long long> refine_local{1};       // PPK_REFINE_LOCAL: refineFit's local search scores through the bracket handle (ppk_refine_local_*); 0 = every evaluation through ppk_refine_score_dev (same fit)
   std::atomic<long long> knn_list{0};           // PPK_KNN_LIST: entries of the neighbour-candidate list (0 = sized from n and knn)
   std::atomic<long long> host_parts_rows{16 << 20};   // PPK_HOST_PARTS_ROWS: ... from this many rows up
   std::atomic<long long> host_parts{2};         // PPK_HOST_PARTS: worker threads of a one-device host query (>= 16 Mi rows)
@@ -245,7 +246,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_DBSCAN = 17,                       // the DBSCAN fit's Boruvka state and sort storage; the labels behind its edge list
        SLOT_BGMM_FIT = 18,                     // the BGMM fit's per-workgroup partial sums, its sums, counters and k-means labels
        SLOT_SPARSE = 19,                       // extend's and lowerRank's row starts, sort pairs, counts, offsets and temp storage
-       SLOT_COUNT = 20 };
+       SLOT_REFINE = 20,                       // the refine fit's bit matrix, union-find parents and counters (one boundary at a time)
+       SLOT_COUNT = 21 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

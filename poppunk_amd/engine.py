@@ -991,6 +991,89 @@ def refine_sweep_scores_2d_dev(dist_t, x_max, y_max, score_idx=0):
     return _sweep_scores(dist_t, threshold_iterate_2d_dev(dist_t, xm, y_max), xm.size, score_idx)
 
 
+def refine_score_dev(dist_t, slope, x_max, y_max):
+    """The counts of ONE refine boundary on a resident float32 [n(n-1)/2, 2] CUDA matrix (ppk_refine_score_dev,
+    DESIGN.md 3.14): int64 numpy [4] = edges, components, triangles, connected triples of the graph of every row with
+    line_dist <= 0 -- edge_threshold_dev + network_stats_dev in one call, without the edge list."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    with torch.cuda.device(dist_t.device):
+        stats = torch.empty(4, dtype=torch.int64, device=dist_t.device)
+        rc = _lib.lib().ppk_refine_score_dev(C.c_void_p(dist_t.data_ptr()), dist_t.shape[0], int(slope), float(x_max),
+                                             float(y_max), C.c_void_p(stats.data_ptr()),
+                                             _stream_ptr(dist_t.device.index))
+        _lib.check(rc, "ppk_refine_score_dev")
+    return stats.cpu().numpy()
+
+
+def refine_score(X, slope, x_max, y_max, device_id=0):
+    """refine_score_dev on a host float32 [n(n-1)/2, 2] array (ppk_refine_score)."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    if X.ndim != 2 or X.shape[1] != 2:
+        raise ValueError("distances must be a float32 [n, 2] array")
+    stats = np.zeros(4, dtype=np.int64)
+    rc = _lib.lib().ppk_refine_score(X.ctypes.data_as(C.POINTER(C.c_float)), X.shape[0], int(slope), float(x_max),
+                                     float(y_max), int(device_id), stats.ctypes.data_as(C.POINTER(C.c_longlong)))
+    _lib.check(rc, "ppk_refine_score")
+    return stats
+
+
+class RefineLocal:
+    """The bracket handle of refine's local search (ppk_refine_local_*): the rows of a resident
+    condensed matrix sorted once into base / candidates / never against two nested lines; `eval(x_max, y_max)` then
+    gives refine_score_dev's counts for any line between them.  `create` returns None when the two lines are not
+    nested (the caller scores with refine_score_dev).  `split` = (base, candidates, never) rows."""
+
+    def __init__(self, handle, device):
+        self._h, self.device = handle, device
+        split = (C.c_ulonglong * 3)()
+        _lib.check(_lib.lib().ppk_refine_local_stats(self._h, split), "ppk_refine_local_stats")
+        self.split = tuple(int(v) for v in split)
+
+    @classmethod
+    def create(cls, dist_t, slope, x_lo, y_lo, x_hi, y_hi):
+        torch = _torch()
+        _check_dist_tensor(dist_t)
+        h = C.c_void_p()
+        with torch.cuda.device(dist_t.device):
+            rc = _lib.lib().ppk_refine_local_create_dev(
+                C.c_void_p(dist_t.data_ptr()), dist_t.shape[0], int(slope), float(x_lo), float(y_lo), float(x_hi),
+                float(y_hi), _stream_ptr(dist_t.device.index), C.byref(h))
+        if rc == _lib.REFINE_NOT_NESTED:
+            return None
+        _lib.check(rc, "ppk_refine_local_create_dev")
+        return cls(h, dist_t.device)
+
+    def eval(self, x_max, y_max):
+        torch = _torch()
+        if self._h is None:
+            raise RuntimeError("the bracket handle is closed")
+        with torch.cuda.device(self.device):
+            stats = torch.empty(4, dtype=torch.int64, device=self.device)
+            rc = _lib.lib().ppk_refine_local_eval_dev(self._h, float(x_max), float(y_max), C.c_void_p(stats.data_ptr()),
+                                                      _stream_ptr(self.device.index))
+            _lib.check(rc, "ppk_refine_local_eval_dev")
+        return stats.cpu().numpy()
+
+    def close(self):
+        if self._h is not None:
+            _lib.lib().ppk_refine_local_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def long_to_square_dev(dist_t, col, n):
     """pp_sketchlib.longToSquare of one column of the resident [n_pairs,2] matrix -> [n,n] CUDA."""
     torch = _torch()

@@ -2,8 +2,13 @@
 
 Mirrors what `RefineFit.assign` / `RefineFit.apply_threshold` (PopPUNK/models.py:956-994,
 :1065-1091) do around kernel 2, and the hand-off `construct_network_from_assignments` makes to
-`generateTuples` (PopPUNK/network.py:1170-1184).  Fitting itself (the optimiser walking the
-boundary, models.py:846-954) is outside the hot path; a fitted boundary is the input here.
+`generateTuples` (PopPUNK/network.py:1170-1184), and the fit itself (`RefineFit.fit`, models.py:807-954;
+DESIGN.md 3.14).
+
+  * `fit(X, sample_names, model, max_move, min_move, ...)` / `fit_dev(dist_t, ...)` : the boundary refined from the
+                           means of a fitted BGMMModel / DBSCANModel or a manual start file (refine.refineFit on the
+                           device), then the core-only and accessory-only boundaries for `indiv_refine`
+  * `save(prefix)` / `from_npz(source)` : `<prefix>_fit.npz` with `RefineFit.save`'s keys
 
   * `assign(X)`          : `poppunk_refine.assignThreshold(X/self.scale, slope, x_max, y_max)` with
                            the slope -> (x_max, y_max) mapping of the reference
@@ -44,6 +49,9 @@ class RefineBoundary:
         self.within_label = WITHIN_LABEL
         self.fitted = optimal_x is not None or core_boundary is not None or accessory_boundary is not None
         self.threshold = False
+        self.indiv_fitted = False
+        self.unconstrained = False
+        self.mean0 = self.mean1 = self.min_move = self.max_move = None
 
     @classmethod
     def from_threshold(cls, threshold, dtype=np.float32):
@@ -81,6 +89,130 @@ class RefineBoundary:
         x_max, y_max = self._line(slope)
         scaled = dist_t / torch.as_tensor(self.scale, device=dist_t.device)
         return engine.assign_threshold_dev(scaled, slope, x_max, y_max)
+
+    # ---- fitting (RefineFit.fit, models.py:807-954) ----------------------------------------------
+    def _start_points(self, model, startFile):
+        """mean0, mean1 in the scaled space: a manual start file, a DBSCAN fit's cluster means or a BGMM fit's
+        component means (models.py:866-882).  Copies: the unconstrained search moves them in place."""
+        import sys
+        from . import refine
+        if startFile:
+            mean0, mean1, scaled = refine.readManualStart(startFile)
+            if not scaled:
+                mean0 /= self.scale
+                mean1 /= self.scale
+            return mean0, mean1
+        if isinstance(model, DBSCANModel):
+            sys.stderr.write("Initial model-based network construction based on DBSCAN fit\n")
+            means = model.cluster_means
+        elif isinstance(model, BGMMModel):
+            sys.stderr.write("Initial model-based network construction based on Gaussian fit\n")
+            means = model.means
+        else:
+            raise RuntimeError("Unrecognised model type")
+        return (np.array(means[model.within_label, :], dtype=np.float64),
+                np.array(means[model.between_label, :], dtype=np.float64))
+
+    def fit_dev(self, dist_t, sample_names, model, max_move, min_move, startFile=None, indiv_refine=None,
+                unconstrained=False, score_idx=0, no_local=False, betweenness_sample=100, sample_size=None,
+                use_gpu=False):
+        """RefineFit.fit on a resident float32 [n(n-1)/2, 2] CUDA matrix: the 2-D refinement from the start points of
+        `model` (a BGMMModel, a DBSCANModel, or `startFile`), then, for indiv_refine 'core' / 'accessory' / 'both',
+        the slope-0 and slope-1 refinements, with the reference's fall-back when one of them fails.  Returns the
+        assignment (assign_dev).  multi_boundary is not mirrored (it needs printClusters)."""
+        import sys
+        import torch
+        from . import refine
+        if sample_size is not None:
+            raise NotImplementedError("RefineBoundary.fit: random vertex subsampling (sample_size) is not mirrored")
+        self.scale = np.asarray(np.copy(model.scale), dtype=np.float32).reshape(2)
+        self.max_move, self.min_move = max_move, min_move
+        self.unconstrained = unconstrained
+        self.mean0, self.mean1 = self._start_points(model, startFile)
+
+        scaled = dist_t / torch.as_tensor(self.scale, device=dist_t.device)      # (the rule of assign_dev)
+        scorer = refine.DeviceScorer(scaled)
+        common = dict(score_idx=score_idx, no_local=no_local, num_processes=self.threads,
+                      betweenness_sample=betweenness_sample, sample_size=sample_size, use_gpu=use_gpu)
+        self.optimal_x, self.optimal_y, self.optimal_s = refine.refineFit(
+            scorer, sample_names, self.mean0, self.mean1, self.scale, max_move, min_move, slope=2,
+            unconstrained=unconstrained, **common)
+        self.slope = 2
+        self.fitted = True
+        self.threshold = False
+        self.indiv_fitted = False
+
+        self.core_boundary = self.optimal_x
+        self.accessory_boundary = self.optimal_y
+        if indiv_refine is not None:
+            try:
+                for dist_type, slope in zip(['core', 'accessory'], [0, 1]):
+                    if indiv_refine == 'both' or indiv_refine == dist_type:
+                        sys.stderr.write("Refining " + dist_type + " distances separately\n")
+                        core_boundary, accessory_boundary, _ = refine.refineFit(
+                            scorer, sample_names, self.mean0, self.mean1, self.scale, max_move, min_move, slope=slope,
+                            **common)
+                        if dist_type == "core":
+                            self.core_boundary = core_boundary
+                        if dist_type == "accessory":
+                            self.accessory_boundary = accessory_boundary
+                self.indiv_fitted = True
+            except RuntimeError as e:
+                print(e)
+                sys.stderr.write("Could not separately refine core and accessory boundaries. "
+                                 "Using joint 2D refinement only.\n")
+        return self.assign_dev(dist_t)
+
+    def fit(self, X, sample_names, model, max_move, min_move, startFile=None, indiv_refine=None, unconstrained=False,
+            score_idx=0, no_local=False, betweenness_sample=100, sample_size=None, use_gpu=False, device_id=0):
+        """fit_dev on a host float32 [n(n-1)/2, 2] array, uploaded once: the same model to the bit.  Returns the
+        assignment as a numpy array."""
+        import torch
+        if sample_size is not None:
+            raise NotImplementedError("RefineBoundary.fit: random vertex subsampling (sample_size) is not mirrored")
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        y = self.fit_dev(torch.from_numpy(X).to("cuda:%d" % device_id), sample_names, model, max_move, min_move,
+                         startFile=startFile, indiv_refine=indiv_refine, unconstrained=unconstrained,
+                         score_idx=score_idx, no_local=no_local, betweenness_sample=betweenness_sample,
+                         sample_size=sample_size, use_gpu=use_gpu)
+        return y.cpu().numpy()
+
+    def save(self, prefix):
+        """`<prefix>/<basename>_fit.npz` with RefineFit.save's keys (models.py:996-1005: intercept,
+        core_acc_intercepts, scale, indiv_fitted), which `from_npz` and PopPUNK's RefineFit.load read.  No `_fit.pkl`
+        is written.  Returns the path."""
+        import os
+        if not self.fitted:
+            raise RuntimeError("Trying to save unfitted model")
+        prefix = str(prefix)
+        os.makedirs(prefix, exist_ok=True)
+        path = os.path.join(prefix, os.path.basename(os.path.normpath(prefix)) + "_fit.npz")
+        np.savez(path, intercept=np.array([self.optimal_x, self.optimal_y]),
+                 core_acc_intercepts=np.array([self.core_boundary, self.accessory_boundary]), scale=self.scale,
+                 indiv_fitted=self.indiv_fitted)
+        return path
+
+    @classmethod
+    def from_npz(cls, source):
+        """RefineFit.load (models.py:1010-1036) from a path to `<prefix>_fit.npz` or a mapping of its arrays, a file
+        PopPUNK wrote included: a file without `indiv_fitted` predates it (False), and NaN in both `intercept[1]` and
+        `core_acc_intercepts[1]` marks a threshold model."""
+        if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__"):
+            with np.load(source, allow_pickle=False) as z:
+                d = {k: z[k] for k in z.files}
+        else:
+            d = dict(source)
+        missing = [k for k in ("intercept", "core_acc_intercepts", "scale") if k not in d]
+        if missing:
+            raise ValueError("not a refine fit: missing %s" % ", ".join(missing))
+        b = cls(scale=d["scale"], slope=2, optimal_x=np.asarray(d["intercept"]).item(0),
+                optimal_y=np.asarray(d["intercept"]).item(1),
+                core_boundary=np.asarray(d["core_acc_intercepts"]).item(0),
+                accessory_boundary=np.asarray(d["core_acc_intercepts"]).item(1))
+        b.indiv_fitted = bool(np.asarray(d["indiv_fitted"]).item()) if "indiv_fitted" in d else False
+        if np.isnan(b.optimal_y) and np.isnan(b.accessory_boundary):
+            b.threshold = True
+        return b
 
     def edges(self, X, self_comparison=True, num_ref=0, int_offset=0, slope=None):
         """assign -> generateTuples(assignments, within_label, self, num_ref, int_offset):

@@ -14,16 +14,35 @@ density = E / (0.5 n (n - 1)) (cugraph: E / (0.5 n^2 - 1)), and transitivity = 3
 graph-tool's `global_clustering` itself cannot be run here: that it returns NaN for a graph without connected
 triples is UNVERIFIED.
 
+Fitting the boundary mirrors PopPUNK/refine.py:51-247 and :476-664:
+
+    refineFit(distMat, sample_names, mean0, mean1, scale, max_move, min_move, slope=2, score_idx=0,
+              unconstrained=False, no_local=False, num_processes=1, betweenness_sample=100, sample_size=None,
+              use_gpu=False) -> (optimal_x, optimal_y, optimised_s)
+    newNetwork(s, ...), newNetwork2D(y_idx, ...), check_search_range(...), readManualStart(startFile)
+
+`distMat` is a float32 [n(n-1)/2, 2] numpy array (uploaded once per call) or a resident CUDA tensor; the sweeps, every
+evaluation of the local search and the 2-D grid run on that one tensor and no edge list leaves the device.  The local
+search is scipy's bounded minimiser, as upstream; its objective takes the four integer counts of one boundary from
+ppk_refine_score_dev, or, between the two lines of the search's bounds, from the bracket handle ppk_refine_local_*
+(option refine_local, 1 by default; both give the same counts, hence the same fit).  score_idx 1 and 2 evaluate through
+edge_threshold_dev + network_summary_graph_dev.  `num_processes` and `use_gpu` are accepted and ignored; `sample_size`
+raises NotImplementedError before the device is touched.  `last_fit` describes the latest refineFit call: the global
+scores, the bounds, every evaluation of the local search (s, counts, score) and which path scored it.
+
 Not mirrored by growNetwork (NotImplementedError, raised before the device is touched): betweenness scores
 (score_idx > 0; the device path for those is engine.refine_sweep_scores_dev(..., score_idx=...)),
 random vertex subsampling (sample_size), and writing each step's clusters (write_clusters: printClusters).
 `use_gpu` selects cugraph upstream; it is accepted and ignored (this is the device path either way).
 """
 import ctypes as C
+import sys
+from itertools import chain
 
 import numpy as np
 
 from . import _lib
+from .utils import decisionBoundary, transformLine
 
 betweenness_sample_default = 100       # PopPUNK/__init__.py
 
@@ -134,3 +153,285 @@ def growNetwork(sample_names, i_vec, j_vec, idx_vec, s_range, score_idx=0, threa
     n = len(sample_names)
     stats, _ = network_sweep(i_vec, j_vec, idx, n, int(idx.max()) + 1)
     return grow_scores(stats, n, score_idx)
+
+
+# ---- fitting the boundary (PopPUNK/refine.py:51-247, :476-664) -----------------------------------
+last_fit = {}          # the latest refineFit call: see the module docstring
+
+
+def check_search_range(scale, mean0, mean1, lower_s, upper_s):
+    """The axis intercepts at both ends of a search range along mean0 -> mean1, with the reference's report on stderr
+    (PopPUNK/refine.py:314-352) -> ((min_x, max_x), (min_y, max_y))."""
+    gradient = (mean1[1] - mean0[1]) / (mean1[0] - mean0[0])
+    bottom_end = transformLine(lower_s, mean0, mean1)
+    top_end = transformLine(upper_s, mean0, mean1)
+    min_x, min_y = decisionBoundary(bottom_end, gradient)
+    max_x, max_y = decisionBoundary(top_end, gradient)
+    sys.stderr.write("Search range (" + ",".join(["{:.3f}".format(x) for x in bottom_end * scale]) + ") to (" +
+                     ",".join(["{:.3f}".format(x) for x in top_end * scale]) + ")\n")
+    sys.stderr.write("Searching core intercept from " + "{:.3f}".format(min_x * scale[0]) + " to " +
+                     "{:.3f}".format(max_x * scale[0]) + "\n")
+    sys.stderr.write("Searching accessory intercept from " + "{:.3f}".format(min_y * scale[1]) + " to " +
+                     "{:.3f}".format(max_y * scale[1]) + "\n")
+    return ((min_x, max_x), (min_y, max_y))
+
+
+def boundary_of_s(s, mean0, mean1, gradient, slope=2):
+    """(x_max, y_max) of the boundary at distance s along mean0 -> mean1, as newNetwork sets it up
+    (refine.py:523-532), in double; the device calls narrow it to float32 as pybind11 does for edgeThreshold."""
+    new_intercept = transformLine(s, mean0, mean1)
+    if slope == 2:
+        x_max, y_max = decisionBoundary(new_intercept, gradient)
+    elif slope == 0:
+        x_max = new_intercept[0]
+        y_max = 0
+    elif slope == 1:
+        x_max = 0
+        y_max = new_intercept[1]
+    else:
+        raise RuntimeError("slope must be 0, 1 or 2")
+    return x_max, y_max
+
+
+class DeviceScorer:
+    """What refineFit asks of the device, on one resident matrix: the two sweeps' score lists, the counts of one
+    boundary, and the bracket handle.  (The CPU tests drive refineFit with a stand-in of the same four methods.)"""
+
+    def __init__(self, distMat, device_id=0):
+        import torch
+        from . import engine
+        self.engine = engine
+        if isinstance(distMat, torch.Tensor):
+            self.dist_t = distMat
+        else:
+            X = np.ascontiguousarray(distMat, dtype=np.float32)
+            if X.ndim != 2 or X.shape[1] != 2:
+                raise ValueError("distMat must be a float32 [n, 2] array")
+            self.dist_t = torch.from_numpy(X).to("cuda:%d" % device_id)
+        self.n_rows = int(self.dist_t.shape[0])
+
+    def sweep_1d(self, s_range, slope, mean0, mean1, score_idx):
+        """-> (rows the sweep lists, growNetwork's list)"""
+        stats, scores = self.engine.refine_sweep_scores_dev(self.dist_t, s_range, slope, mean0[0], mean0[1], mean1[0],
+                                                            mean1[1], score_idx)
+        return int(stats[-1, 0].item()), scores
+
+    def sweep_2d(self, x_range, y_max, score_idx):
+        stats, scores = self.engine.refine_sweep_scores_2d_dev(self.dist_t, x_range, y_max, score_idx)
+        return int(stats[-1, 0].item()), scores
+
+    def score(self, slope, x_max, y_max, score_idx):
+        """-> (counts int64 [4], betweenness means or None) of one boundary"""
+        if score_idx == 0:
+            return self.engine.refine_score_dev(self.dist_t, slope, x_max, y_max), None
+        edges = self.engine.edge_threshold_dev(self.dist_t, slope, x_max, y_max)
+        stats, bt, _, _ = self.engine.network_summary_graph_dev(edges, self.engine._samples_of(self.n_rows))
+        return stats.cpu().numpy(), bt.cpu().numpy()
+
+    def bracket(self, slope, lo, hi):
+        """-> an object with eval(x_max, y_max) -> counts and split, or None (the lines are not nested)"""
+        return self.engine.RefineLocal.create(self.dist_t, slope, lo[0], lo[1], hi[0], hi[1])
+
+
+def _scorer_of(distMat):
+    return distMat if hasattr(distMat, "sweep_1d") else DeviceScorer(distMat)
+
+
+def _check_fit_args(score_idx, sample_size, who):
+    if sample_size is not None:
+        raise NotImplementedError(who + ": random vertex subsampling (sample_size) is not mirrored")
+    if score_idx not in (0, 1, 2):
+        raise ValueError("score_idx must be 0, 1 or 2")
+
+
+def newNetwork(s, sample_names, distMat, mean0, mean1, gradient, slope=2, score_idx=0, cpus=1,
+               betweenness_sample=betweenness_sample_default, sample_size=None, use_gpu=False):
+    """PopPUNK/refine.py:476-548: -score of the network of the boundary at s, in one device call
+    (ppk_refine_score_dev; score_idx 1 / 2: edge_threshold_dev + network_summary_graph_dev)."""
+    _check_fit_args(score_idx, sample_size, "newNetwork")
+    scorer = _scorer_of(distMat)
+    x_max, y_max = boundary_of_s(s, mean0, mean1, gradient, slope)
+    stats, bt = scorer.score(slope, x_max, y_max, score_idx)
+    return -summary_from_stats(stats, len(sample_names), bt)[1][score_idx]
+
+
+def newNetwork2D(y_idx, sample_names, distMat, x_range, y_range, score_idx=0,
+                 betweenness_sample=betweenness_sample_default, sample_size=None, use_gpu=False):
+    """PopPUNK/refine.py:550-610: growNetwork's list over x_range at y_range[y_idx]; [0] * len(x_range) when the
+    sweep lists every row."""
+    _check_fit_args(score_idx, sample_size, "newNetwork2D")
+    scorer = _scorer_of(distMat)
+    y_max = y_range[y_idx]
+    listed, scores = scorer.sweep_2d(x_range, y_max, score_idx)
+    if listed == scorer.n_rows:
+        scores = [0] * len(x_range)
+    return scores
+
+
+def _local_objective(scorer, n, mean0, mean1, gradient, slope, score_idx, bounds, evals, info):
+    """newNetwork as the local search calls it, scoring through the bracket handle where one can be made: the two
+    lines of the bounds, computed as newNetwork computes them and narrowed to float32, must be nested."""
+    handle = None
+    info["local_path"] = "summary" if score_idx > 0 else "score"
+    if score_idx == 0 and _lib.get_option("refine_local") != 0 and hasattr(scorer, "bracket"):
+        lo = [np.float32(v) for v in boundary_of_s(bounds[0], mean0, mean1, gradient, slope)]
+        hi = [np.float32(v) for v in boundary_of_s(bounds[1], mean0, mean1, gradient, slope)]
+        handle = scorer.bracket(slope, lo, hi)
+        if handle is not None:
+            info["local_path"] = "bracket"
+            info["split"] = getattr(handle, "split", None)
+
+    def inside(v, k):
+        return lo[k] <= np.float32(v) <= hi[k]
+
+    def objective(s):
+        x_max, y_max = boundary_of_s(s, mean0, mean1, gradient, slope)
+        if handle is not None and (slope == 1 or inside(x_max, 0)) and (slope == 0 or inside(y_max, 1)):
+            stats, bt = handle.eval(x_max, y_max), None
+        else:
+            stats, bt = scorer.score(slope, x_max, y_max, score_idx)
+        score = -summary_from_stats(stats, n, bt)[1][score_idx]
+        evals.append((float(s), [int(v) for v in stats], float(score)))
+        return score
+
+    return objective, handle
+
+
+def refineFit(distMat, sample_names, mean0, mean1, scale, max_move, min_move, slope=2, score_idx=0,
+              unconstrained=False, no_local=False, num_processes=1, betweenness_sample=betweenness_sample_default,
+              sample_size=None, use_gpu=False):
+    """PopPUNK/refine.py:51-247: the global sweep (40 offsets along mean0 -> mean1, or the 20 x 20 grid of the
+    unconstrained search), then scipy's bounded minimiser between the global minimum's neighbours
+    -> (optimal_x, optimal_y, optimised_s)."""
+    global last_fit
+    _check_fit_args(score_idx, sample_size, "refineFit")
+    import scipy.optimize
+    info = {"global_s": None, "bounds": None, "evals": [], "local_path": None, "split": None}
+    last_fit = info
+    n = len(sample_names)
+    sys.stderr.write("Trying to optimise score globally\n")
+
+    gradient = (mean1[1] - mean0[1]) / (mean1[0] - mean0[0])
+
+    if unconstrained:
+        if slope != 2:
+            raise RuntimeError("Unconstrained optimization and indiv-refine incompatible")
+
+        global_grid_resolution = 20
+        x_max_start, y_max_start = decisionBoundary(mean0, gradient, adj=-1 * min_move)
+        x_max_end, y_max_end = decisionBoundary(mean1, gradient, adj=max_move)
+
+        if x_max_start < 0 or y_max_start < 0:
+            raise RuntimeError("Boundary range below zero")
+
+        x_max = np.linspace(x_max_start, x_max_end, global_grid_resolution, dtype=np.float32)
+        y_max = np.linspace(y_max_start, y_max_end, global_grid_resolution, dtype=np.float32)
+        sys.stderr.write("Searching core intercept from " + "{:.3f}".format(x_max_start * scale[0]) + " to " +
+                         "{:.3f}".format(x_max_end * scale[0]) + "\n")
+        sys.stderr.write("Searching accessory intercept from " + "{:.3f}".format(y_max_start * scale[1]) + " to " +
+                         "{:.3f}".format(y_max_end * scale[1]) + "\n")
+
+        scorer = _scorer_of(distMat)
+        global_s = [newNetwork2D(y_idx, sample_names, scorer, x_max, y_max, score_idx, betweenness_sample,
+                                 sample_size, use_gpu) for y_idx in range(global_grid_resolution)]
+        global_s = np.array(list(chain.from_iterable(global_s)))
+        global_s[np.isnan(global_s)] = 1
+        info["global_s"] = global_s
+        min_idx = np.argmin(global_s)
+        optimal_x = x_max[min_idx % global_grid_resolution]
+        optimal_y = y_max[min_idx // global_grid_resolution]
+        optimised_s = global_s[min_idx]
+
+        if not (optimal_x > x_max_start and optimal_x < x_max_end and
+                optimal_y > y_max_start and optimal_y < y_max_end):
+            no_local = True
+        elif not no_local:
+            # the reference's parameterisation of the 1-D search along the found slope, kept as it stands
+            gradient = optimal_x / optimal_y
+            delta = x_max[1] - x_max[0]
+            bounds = [-delta, delta]
+            mean1 = (optimal_x + delta, delta * gradient)
+    else:
+        search_length = max_move + ((mean1[0] - mean0[0])**2 + (mean1[1] - mean0[1])**2)**0.5
+        global_grid_resolution = 40
+        s_range = np.linspace(-min_move, search_length, num=global_grid_resolution)
+        (min_x, max_x), (min_y, max_y) = check_search_range(scale, mean0, mean1, s_range[0], s_range[-1])
+        if min_x < 0 or min_y < 0:
+            raise RuntimeError("Boundary range below zero")
+
+        scorer = _scorer_of(distMat)
+        listed, scores = scorer.sweep_1d(s_range, slope, mean0, mean1, score_idx)
+        if listed == scorer.n_rows:
+            raise RuntimeError("Boundary range includes all points")
+        global_s = np.array(scores)
+        global_s[np.isnan(global_s)] = 1
+        info["global_s"] = global_s
+        min_idx = np.argmin(np.array(global_s))
+        if min_idx > 0 and min_idx < len(s_range) - 1:
+            bounds = [s_range[min_idx - 1], s_range[min_idx + 1]]
+        else:
+            no_local = True
+        if no_local:
+            optimised_s = s_range[min_idx]
+
+    if not no_local:
+        sys.stderr.write("Trying to optimise score locally\n")
+        info["bounds"] = [float(bounds[0]), float(bounds[1])]
+        objective, handle = _local_objective(scorer, n, mean0, mean1, gradient, slope, score_idx, bounds,
+                                             info["evals"], info)
+        try:
+            local_s = scipy.optimize.minimize_scalar(objective, bounds=bounds, method='Bounded',
+                                                     options={'disp': True})
+        finally:
+            if handle is not None and hasattr(handle, "close"):
+                handle.close()
+        optimised_s = local_s.x
+
+    if not unconstrained or not no_local:
+        optimised_coor = transformLine(optimised_s, mean0, mean1)
+        if slope == 2:
+            optimal_x, optimal_y = decisionBoundary(optimised_coor, gradient)
+            if optimal_x < 0 or optimal_y < 0:
+                raise RuntimeError("Optimisation failed: produced a boundary outside of allowed range\n")
+        else:
+            optimal_x = optimised_coor[0]
+            optimal_y = optimised_coor[1]
+            if (slope == 0 and optimal_x < 0) or (slope == 1 and optimal_y < 0):
+                raise RuntimeError("Optimisation failed: produced a boundary outside of allowed range\n")
+
+    return optimal_x, optimal_y, optimised_s
+
+
+def readManualStart(startFile):
+    """PopPUNK/refine.py:612-664: `start x,y`, `end x,y` and an optional `scaled False` line -> (mean0, mean1, scaled);
+    a badly formed file is reported on stderr and ends the process, as upstream."""
+    mean0 = None
+    mean1 = None
+    scaled = True
+
+    with open(startFile, 'r') as start:
+        for line in start:
+            (param, value) = line.rstrip().split()
+            if param == 'start':
+                mean0 = np.array([float(v) for v in value.split(',')])
+            elif param == 'end':
+                mean1 = np.array([float(v) for v in value.split(',')])
+            elif param == 'scaled':
+                if value == "False" or value == "false":
+                    scaled = False
+            else:
+                raise RuntimeError("Incorrectly formatted manual start file")
+    try:
+        if not isinstance(mean0, np.ndarray) or not isinstance(mean1, np.ndarray):
+            raise RuntimeError('Must set both start and end')
+        if mean0.shape != (2,) or mean1.shape != (2,):
+            raise RuntimeError('Wrong size for values')
+        for val in np.nditer(np.hstack([mean0, mean1])):
+            if val > 1 or val < 0:
+                raise RuntimeError('Value out of range (between 0 and 1)')
+    except RuntimeError as e:
+        sys.stderr.write("Could not read manual start file " + startFile + "\n")
+        sys.stderr.write(str(e) + "\n")
+        sys.exit(1)
+
+    return mean0, mean1, scaled

@@ -14,6 +14,8 @@ import os
 import sys
 from contextlib import contextmanager
 
+import numpy as np
+
 from . import pp_sketchlib
 from .distfile import readPickle, storePickle  # noqa: F401
 
@@ -76,3 +78,29 @@ def update_distance_matrices(refList, distMat, queryList=None, query_ref_distMat
         return refList, core, acc
     core, acc = pp_sketchlib.squareMatrices(distMat, query_ref_distMat, query_query_distMat)
     return refList + queryList, core, acc
+
+
+def transformLine(s, mean0, mean1):
+    """The point at distance s from mean0 along the line mean0 -> mean1 (PopPUNK/utils.py:509-532), as
+    np.array([x, y]).  The statement order is the reference's: every caller compares doubles derived from it."""
+    dx = mean1[0] - mean0[0]
+    dy = mean1[1] - mean0[1]
+    ds = np.sqrt(dx**2 + dy**2)
+    x = mean0[0] + s * (dx / ds)
+    y = mean0[1] + s * (dy / ds)
+    return np.array([x, y])
+
+
+def decisionBoundary(intercept, gradient, adj=0.0):
+    """The axis intercepts (x, y) of the boundary through `intercept`, normal to a line of slope `gradient`
+    (PopPUNK/utils.py:535-560).  With adj != 0 the point is first moved along its own direction from the origin by
+    adj, IN PLACE as the reference does it: refineFit's unconstrained branch passes mean0 and mean1 themselves and goes
+    on with the moved points."""
+    if adj != 0.0:
+        original_hypotenuse = (intercept[0]**2 + intercept[1]**2)**0.5
+        length_ratio = (original_hypotenuse + adj) / original_hypotenuse
+        intercept[0] = intercept[0] * length_ratio
+        intercept[1] = intercept[1] * length_ratio
+    x = intercept[0] + intercept[1] * gradient
+    y = intercept[1] + intercept[0] / gradient
+    return (x, y)
