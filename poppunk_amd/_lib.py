@@ -286,12 +286,15 @@ def sources_hash_now():
     """The same hash computed from the sources as they are on disk now (csrc/Makefile HASHED): differs from
     `source_hash()` when the library has not been rebuilt since an edit.  None when a source is missing."""
     import hashlib
+    import re
     here = os.path.join(_HERE, "csrc")
-    names = ["ppk_api.hip", "ppk_host.hip", "ppk_dist.hip", "ppk_boundary.hip", "ppk_iterate.hip", "ppk_square.hip",
-             "ppk_sparse.hip", "ppk_bgmm.hip", "ppk_network.hip", "ppk_mst.hip", "ppk_nj.hip", "ppk_embed.hip",
-             "ppk_dbscan.hip", "ppk_bgmm_fit.hip", "ppk_refine.hip", "ppk_h5.cpp",
-             "ppk_internal.h",
-             "ppk_block_asm.inc", "ppk_dist_tile.inc", "../../include/ppk.h"]
+    try:
+        with open(os.path.join(here, "Makefile")) as f:
+            mk = f.read()
+        srcs, hdrs = (re.search(r"^%s\s*:=\s*(.*)$" % v, mk, re.M).group(1).split() for v in ("SRCS", "HDRS"))
+    except (OSError, AttributeError):
+        return None
+    names = srcs + ["ppk_h5.cpp"] + hdrs       # the order HASHED concatenates them in
     h = hashlib.sha256()
     try:
         for n in names:

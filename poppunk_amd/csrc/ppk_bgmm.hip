@@ -7,7 +7,7 @@
 //  - bgmm_assign_kernel        : labels (no transcendental) and / or the float32 responsibilities (fp64 exp / log)
 //  - the edge predicate: ppk_boundary.hip's mask passes with BgmmPred (label == within_label) as their row predicate
 //
-// The per-row statement is ppk_bgmm_label / ppk_bgmm_lpr (ppk_internal.h), which kernel 1's fused MODE_BGMM epilogue
+// The per-row statement is ppk_bgmm_label / ppk_bgmm_lpr (ppk_device.h), which kernel 1's fused MODE_BGMM epilogue
 // calls too.  8 B in and 4 B out per row for labels, but the pass is VALU-issue bound, not HBM bound: two IEEE float32
 // divisions per row and six fp64 fused multiply-adds plus a compare-select per component (profiles/bgmm/README.md).
 #include <cmath>
@@ -135,18 +135,7 @@ int ppk_bgmm_to_device(int dev, const ppk_bgmm &m, const ppk_bgmm **d_model, hip
 
 // ---- host preparation (no device) ------------------------------------------------------------------------------
 // log_multivariate_normal_density (bgmm.py:131-176): scipy.linalg.cholesky(cv, lower=True); on LinAlgError the same
-// of cv + 1e-7 I; on a second failure ValueError.  LAPACK's dpotrf fails when a pivot is <= 0 or NaN.
-static bool chol2(double a, double b, double d, double L[3]) {
-  if (!(a > 0.0)) return false;
-  const double l00 = std::sqrt(a);
-  const double l10 = b / l00;
-  const double r = d - l10 * l10;
-  if (!(r > 0.0)) return false;
-  L[0] = l00;
-  L[1] = l10;
-  L[2] = std::sqrt(r);
-  return true;
-}
+// of cv + 1e-7 I; on a second failure ValueError (chol2).
 
 extern "C" int ppk_bgmm_prepare(int K, const double *weights, const double *means, const double *covariances,
                                 const double *scale, int scale_is_f64, int within_label, ppk_bgmm *out) {
@@ -186,11 +175,7 @@ extern "C" int ppk_bgmm_prepare(int K, const double *weights, const double *mean
     m.chol[c][2] = L[2];
     m.inv_diag[c][0] = 1.0 / L[0];
     m.inv_diag[c][1] = 1.0 / L[2];
-    m.lin[c][0] = m.inv_diag[c][0];
-    m.lin[c][1] = -m.mean[c][0] * m.inv_diag[c][0];
-    m.lin[c][2] = m.inv_diag[c][1];
-    m.lin[c][3] = -L[1] * m.inv_diag[c][1];
-    m.lin[c][4] = -m.mean[c][1] * m.inv_diag[c][1];
+    ppk_lin_of(m.mean[c], L, m.inv_diag[c][0], m.inv_diag[c][1], m.lin[c]);
     const double log_det = 2.0 * (std::log(L[0]) + std::log(L[2]));
     m.log_const[c] = std::log(weights[c]) - 0.5 * (2.0 * log2pi + log_det);
   }

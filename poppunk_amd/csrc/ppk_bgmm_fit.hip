@@ -42,18 +42,6 @@ struct FitArgs {
   double pivot[PPK_BGMM_MAX_K][2];     // the moments are taken about it; MODE_NEAREST: the centres
 };
 
-__device__ __forceinline__ double fit_lpr(double xs, double ys, const FitArgs &a, int c) {
-  const double *l = a.lin[c];
-  const double z0 = __builtin_fma(xs, l[0], l[1]);
-  const double z1 = __builtin_fma(ys, l[2], __builtin_fma(z0, l[3], l[4]));
-  return __builtin_fma(-0.5, __builtin_fma(z0, z0, z1 * z1), a.log_const[c]);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = PPK_LANES / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
-  return v;
-}
 
 // rows float2 [n_rows]; index int64 [n] or null (then n == n_rows and row i is training row i).  An index outside
 // [0, n_rows) contributes nothing and is never dereferenced (bgmm_check_kernel reports it to the fit).
@@ -81,20 +69,20 @@ bgmm_stats_kernel(const float2 *__restrict__ rows, size_t n_rows, const long lon
         row = (size_t)r;
       }
       const float2 v = rows[row];
-      const double xs = (double)__fdiv_rn(v.x, a.scale[0]), ys = (double)__fdiv_rn(v.y, a.scale[1]);
+      const double xs = ppk_scaled_f32(v.x, a.scale[0]), ys = ppk_scaled_f32(v.y, a.scale[1]);
       double r[kChunk], rl[kChunk];
       if (MODE == MODE_EM) {
         // scipy's logsumexp: max + log sum exp(w - max); log_resp = w - that; resp = exp(log_resp)
-        double mx = fit_lpr(xs, ys, a, 0);
-        for (int c = 1; c < a.K; ++c) mx = fmax(mx, fit_lpr(xs, ys, a, c));
+        double mx = ppk_bgmm_lpr(xs, ys, a, 0);
+        for (int c = 1; c < a.K; ++c) mx = fmax(mx, ppk_bgmm_lpr(xs, ys, a, c));
         double sum = 0.0;
-        for (int c = 0; c < a.K; ++c) sum += exp(fit_lpr(xs, ys, a, c) - mx);
+        for (int c = 0; c < a.K; ++c) sum += exp(ppk_bgmm_lpr(xs, ys, a, c) - mx);
         const double lse = mx + log(sum);
 #pragma unroll
         for (int j = 0; j < kChunk; ++j) {
           r[j] = rl[j] = 0.0;
           if (c0 + j < a.K) {
-            const double lr = fit_lpr(xs, ys, a, c0 + j) - lse;
+            const double lr = ppk_bgmm_lpr(xs, ys, a, c0 + j) - lse;
             r[j] = exp(lr);
             rl[j] = r[j] * lr;
           }
@@ -142,7 +130,7 @@ bgmm_stats_kernel(const float2 *__restrict__ rows, size_t n_rows, const long lon
     for (int j = 0; j < kChunk; ++j)
 #pragma unroll
       for (int s = 0; s < kStats; ++s) {
-        const double w = wave_sum(acc[j][s]);
+        const double w = wave_sum(acc[j][s], warpSize);
         if (lane == 0) red[wave][j * kStats + s] = w;
       }
     if (MODE == MODE_NEAREST && c0 == 0) {
@@ -242,18 +230,6 @@ double digamma_pos(double x) {
   return shift + (std::log(x) - 0.5 / x - series);
 }
 
-bool chol2(double a, double b, double d, double L[3]) {
-  if (!(a > 0.0)) return false;
-  const double l00 = std::sqrt(a);
-  const double l10 = b / l00;
-  const double r = d - l10 * l10;
-  if (!(r > 0.0)) return false;
-  L[0] = l00;
-  L[1] = l10;
-  L[2] = std::sqrt(r);
-  return true;
-}
-
 int check_params(const ppk_bgmm_fit_params *p, const char *who) {
   if (!p) return ppk_fail(PPK_ERR_ARG, std::string(who) + ": params is NULL");
   if (p->K < 1 || p->K > PPK_BGMM_MAX_K)
@@ -329,11 +305,7 @@ int mstep(const ppk_bgmm_fit_params &p, const double *st, const double *pivot, c
     cum += digamma_pos(b) - dsum;
     const double *L = S->chol[k];
     const double i0 = 1.0 / L[0], i1 = 1.0 / L[2];
-    S->lin[k][0] = i0;
-    S->lin[k][1] = -S->means[k][0] * i0;
-    S->lin[k][2] = i1;
-    S->lin[k][3] = -L[1] * i1;
-    S->lin[k][4] = -S->means[k][1] * i1;
+    ppk_lin_of(S->means[k], L, i0, i1, S->lin[k]);
     const double dof = S->dof[k];
     const double log_det = std::log(i0) + std::log(i1);                 // of the precision's Cholesky factor
     const double log_lambda = 2.0 * log2 + digamma_pos(0.5 * dof) + digamma_pos(0.5 * (dof - 1.0));

@@ -236,22 +236,6 @@ scan_block_sums_kernel(unsigned long long *__restrict__ block_sums, size_t n_blo
   }
 }
 
-__device__ __forceinline__ size_t cond_row_start(size_t i, size_t n) {
-  return i * n - (i * (i + 1)) / 2;
-}
-
-// (i, j) of condensed row k (src/boundary.cpp:22-31): double sqrt estimate,
-// then an integer fix-up so the result is exact for every n.
-__device__ __forceinline__ size_t cond_row_idx(size_t k, size_t n) {
-  const double d = sqrt((double)(4 * n * (n - 1)) - 8.0 * (double)k - 7.0);
-  long long i = (long long)n - 2 - (long long)floor(d / 2.0 - 0.5);
-  if (i < 0) i = 0;
-  if (i > (long long)n - 2) i = (long long)n - 2;
-  while (i > 0 && cond_row_start((size_t)i, n) > k) --i;
-  while ((size_t)i + 2 < n && cond_row_start((size_t)i + 1, n) <= k) ++i;
-  return (size_t)i;
-}
-
 // Pass 3: every thread re-counts its 8 words, a block-level exclusive scan gives
 // its output offset, and it writes one (i,j) per set bit -- in row order.
 // SELF_SCAN (masks of up to kSelfScanBlocks compaction blocks -- 8 192 blocks = 134 M rows; the 10 000-genome matrix has
@@ -327,7 +311,7 @@ mask_expand_kernel(const uint64_t *__restrict__ mask, size_t n_words,
     if (g.layout == EDGE_LINEAR_SELF) {
       const size_t n = g.n_samples;
       const size_t row0 = w * 64;
-      size_t ii = cond_row_idx(row0, n);
+      size_t ii = cond_row_i(row0, n);
       size_t rs = cond_row_start(ii, n);
       while (bits) {
         const int t = __builtin_ctzll(bits);
@@ -358,7 +342,7 @@ mask_expand_kernel(const uint64_t *__restrict__ mask, size_t n_words,
       const size_t n = g.n_samples;
       const size_t seg = w / g.seg_words;
       const size_t row0 = (w % g.seg_words) * 64;
-      size_t ii = cond_row_idx(row0 < g.n_rows ? row0 : g.n_rows - 1, n);
+      size_t ii = cond_row_i(row0 < g.n_rows ? row0 : g.n_rows - 1, n);
       size_t rs = cond_row_start(ii, n);
       while (bits) {
         const int t = __builtin_ctzll(bits);
@@ -443,7 +427,7 @@ all_tuples_kernel(size_t n_entries, size_t num_ref, size_t num_queries, int self
        e0 += (size_t)gridDim.x * kBlock * kAllPerThread) {
     const size_t e1 = e0 + kAllPerThread < n_entries ? e0 + kAllPerThread : n_entries;
     if (self) {
-      size_t ii = cond_row_idx(e0, num_ref);
+      size_t ii = cond_row_i(e0, num_ref);
       size_t rs = cond_row_start(ii, num_ref);
       for (size_t row = e0; row < e1; ++row) {
         while (row >= rs + (num_ref - 1 - ii)) {
@@ -532,13 +516,6 @@ void launch_mask(const float *d_dist, size_t n_rows, size_t n_words, const Pred 
   hipLaunchKernelGGL(mask_from_dist_kernel<Pred>, dim3(grid_for(n_words, kBlock / 64, 4096)), dim3(kBlock), 0, s,
                      reinterpret_cast<const float2 *>(d_dist), n_rows, pred, d_mask, n_words);
 }
-
-size_t samples_of_rows(size_t n_rows) {
-  size_t n = (size_t)(0.5 * (1.0 + std::sqrt(1.0 + 8.0 * (double)n_rows)));
-  while (n > 1 && n * (n - 1) / 2 > n_rows) --n;
-  while ((n + 1) * n / 2 <= n_rows) ++n;
-  return n;
-}
 }  // namespace
 
 int ppk_row_edges(const void *d_rows, size_t n_rows, size_t n_ref, long long int_offset, const RowTest &t,
@@ -552,9 +529,8 @@ int ppk_row_edges(const void *d_rows, size_t n_rows, size_t n_ref, long long int
   g.int_offset = int_offset;
   if (n_ref == 0) {
     g.layout = EDGE_LINEAR_SELF;
-    g.n_samples = samples_of_rows(n_rows);
-    if (check_rows && g.n_samples * (g.n_samples - 1) / 2 != n_rows)
-      return ppk_fail(PPK_ERR_ARG, "row count is not n(n-1)/2 for any n (self/condensed matrix expected)");
+    if (!check_rows) g.n_samples = ppk_samples_of_rows(n_rows);
+    else if (int rc = ppk_condensed_samples(n_rows, &g.n_samples)) return rc;
   } else {
     g.layout = EDGE_LINEAR_NONSELF;
     g.n_ref = n_ref;

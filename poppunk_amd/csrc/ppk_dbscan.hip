@@ -302,17 +302,10 @@ __global__ void __launch_bounds__(kBlock) dbscan_assign_kernel(const float2 *__r
   __shared__ double tc[kTile];
   const size_t row = (size_t)blockIdx.x * kBlock + threadIdx.x;
   const bool live = row < n_rows;
-  // q = x / scale in the dtype numpy promotes to, as ppk_bgmm_scaled: float32 / float32, or the float64 quotient
   double2 q = make_double2(0.0, 0.0);
   if (live) {
     const float2 d = dist[row];
-    if (m.scale_is_f64) {
-      q.x = (double)d.x / m.scale_f64[0];
-      q.y = (double)d.y / m.scale_f64[1];
-    } else {
-      q.x = (double)__fdiv_rn(d.x, m.scale_f32[0]);
-      q.y = (double)__fdiv_rn(d.y, m.scale_f32[1]);
-    }
+    ppk_bgmm_scaled(d.x, d.y, m, q.x, q.y);      // x / scale in the dtype numpy promotes to
   }
   const unsigned n = m.n;
   // d2 of position rank_r (r2) and of position rank_k (the last of N), two bits a pass, one d2 per pair for both
@@ -402,23 +395,6 @@ struct GridModel {
   double x0, y0, wx, wy, eps;
 };
 
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__device__ __forceinline__ double2 scaled_row(float2 d, const AssignModel &m) {
-  double2 q;
-  if (m.scale_is_f64) {
-    q.x = (double)d.x / m.scale_f64[0];
-    q.y = (double)d.y / m.scale_f64[1];
-  } else {
-    q.x = (double)__fdiv_rn(d.x, m.scale_f32[0]);
-    q.y = (double)__fdiv_rn(d.y, m.scale_f32[1]);
-  }
-  return q;
-}
-
 // every point of the square [cx0, cx1] x [cy0, cy1], the lanes striding each grid row's run
 #define PPK_SQUARE_FOR(i)                                                        \
   for (int cy_ = cy0; cy_ <= cy1; ++cy_)                                         \
@@ -430,7 +406,9 @@ __global__ void __launch_bounds__(kBlock) dbscan_assign_grid_kernel(const float2
   const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n_rows) return;                       // whole waves leave; nothing below synchronises the workgroup
   const AssignModel &m = gm.am;
-  const double2 q = scaled_row(dist[row], m);
+  const float2 d = dist[row];
+  double2 q;
+  ppk_bgmm_scaled(d.x, d.y, m, q.x, q.y);
   const int g = gm.g;
   const double fx = (q.x - gm.x0) / gm.wx, fy = (q.y - gm.y0) / gm.wy;
   const int cxq = fx >= 0.0 ? (fx < (double)g ? (int)fx : g - 1) : 0;     // a NaN row lands in cell 0 and never certifies
@@ -450,7 +428,7 @@ __global__ void __launch_bounds__(kBlock) dbscan_assign_grid_kernel(const float2
       all = cx0 == 0 && cy0 == 0 && cx1 == g - 1 && cy1 == g - 1;
       unsigned c = 0;
       for (int cy = cy0 + lane; cy <= cy1; cy += 64) c += (unsigned)(gm.cell[cy * g + cx1 + 1] - gm.cell[cy * g + cx0]);
-      if (all || wave_sum(c) >= target) break;
+      if (all || wave_sum_all(c) >= target) break;
       r += 1 + r / 4;
     }
     pr = 0;
@@ -468,12 +446,12 @@ __global__ void __launch_bounds__(kBlock) dbscan_assign_grid_kernel(const float2
         b2 += k < k2t;
         b3 += k < k3;
       }
-      a1 = wave_sum(a1);
-      a2 = wave_sum(a2);
-      a3 = wave_sum(a3);
-      b1 = wave_sum(b1);
-      b2 = wave_sum(b2);
-      b3 = wave_sum(b3);
+      a1 = wave_sum_all(a1);
+      a2 = wave_sum_all(a2);
+      a3 = wave_sum_all(a3);
+      b1 = wave_sum_all(b1);
+      b2 = wave_sum_all(b2);
+      b3 = wave_sum_all(b3);
       pr |= (unsigned long long)((a1 <= m.rank_r) + (a2 <= m.rank_r) + (a3 <= m.rank_r)) << shift;
       pk |= (unsigned long long)((b1 <= m.rank_k) + (b2 <= m.rank_k) + (b3 <= m.rank_k)) << shift;
     }
@@ -505,8 +483,8 @@ __global__ void __launch_bounds__(kBlock) dbscan_assign_grid_kernel(const float2
     below += k < pk;
     ties += k == pk;
   }
-  below = wave_sum(below);
-  ties = wave_sum(ties);
+  below = wave_sum_all(below);
+  ties = wave_sum_all(ties);
   const unsigned quota = m.rank_k + 1 - below;
   unsigned last_idx = 0xffffffffu;
   if (ties > quota) {
@@ -521,9 +499,9 @@ __global__ void __launch_bounds__(kBlock) dbscan_assign_grid_kernel(const float2
         c2 += t < t2;
         c3 += t < t3;
       }
-      c1 = wave_sum(c1);
-      c2 = wave_sum(c2);
-      c3 = wave_sum(c3);
+      c1 = wave_sum_all(c1);
+      c2 = wave_sum_all(c2);
+      c3 = wave_sum_all(c3);
       pi |= (unsigned)((c1 <= quota - 1) + (c2 <= quota - 1) + (c3 <= quota - 1)) << shift;
     }
     last_idx = pi;
@@ -565,12 +543,6 @@ __global__ void __launch_bounds__(kBlock) dbscan_assign_grid_kernel(const float2
   labels[row] = m.cl_label[cl];
 }
 #undef PPK_SQUARE_FOR
-
-int ceil_log2(size_t n) {
-  int r = 0;
-  while (r < 62 && ((size_t)1 << r) < n) ++r;
-  return r;
-}
 
 int check_model(const ppk_dbscan *m, const char *what) {
   if (!m || !m->d_block || m->n < 1 || m->n_cl < 1)

@@ -1,0 +1,261 @@
+// Arithmetic that two or more translation units of libppk_hip.so need, written here once: `__device__
+// __forceinline__`, or `__host__ __device__` where the host states it too (and tests/device_helpers_host.hip runs it).
+// No kernel lives here.  ppk_internal.h includes this file; it also stands alone.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <cmath>
+#include <string>
+
+#include "../../include/ppk.h"
+
+#ifndef PPK_LANES
+#define PPK_LANES 64           // wavefront width on CDNA
+#endif
+
+int ppk_fail(int code, const std::string &msg);      // ppk_api.hip
+
+// ---- condensed upper triangle: PopPUNK's row order, row k <-> (i, j), 0 <= i < j < n (src/boundary.cpp:22-31) ----
+// Exact while 4 n (n - 1) is exact in a double, n <= 2^25 or so (beyond that the root's argument rounds, and from
+// n ~ 2^31 it goes negative for the last rows); a matrix of 2^25 samples is 4 PB.  The tile kernels' epilogues keep
+// their own row index expressions (ppk_dist_tile.inc).
+__host__ __device__ __forceinline__ size_t cond_row_start(size_t i, size_t n) { return i * n - (i * (i + 1)) / 2; }
+// i of row k: a double sqrt estimate, then an integer fix-up
+__host__ __device__ __forceinline__ size_t cond_row_i(size_t k, size_t n) {
+  const double d = sqrt((double)(4 * n * (n - 1)) - 8.0 * (double)k - 7.0);
+  long long i = (long long)n - 2 - (long long)floor(d / 2.0 - 0.5);
+  if (i < 0) i = 0;
+  if (i > (long long)n - 2) i = (long long)n - 2;
+  while (i > 0 && cond_row_start((size_t)i, n) > k) --i;
+  while ((size_t)i + 2 < n && cond_row_start((size_t)i + 1, n) <= k) ++i;
+  return (size_t)i;
+}
+__host__ __device__ __forceinline__ void cond_pair(size_t k, size_t n, int &i, int &j) {
+  const size_t ii = cond_row_i(k, n);
+  i = (int)ii;
+  j = (int)(ii + 1 + (k - cond_row_start(ii, n)));
+}
+__host__ __device__ __forceinline__ size_t cond_index(size_t a, size_t b, size_t n) {   // a < b < n
+  return a * n - (a * (a + 1)) / 2 + (b - a - 1);
+}
+// the n with n (n - 1) / 2 <= n_rows < (n + 1) n / 2
+inline size_t ppk_samples_of_rows(size_t n_rows) {
+  size_t n = (size_t)(0.5 * (1.0 + std::sqrt(1.0 + 8.0 * (double)n_rows)));
+  while (n > 1 && n * (n - 1) / 2 > n_rows) --n;
+  while ((n + 1) * n / 2 <= n_rows) ++n;
+  return n;
+}
+// *n = the samples of a condensed matrix of n_rows rows, or PPK_ERR_ARG "<who>row count is not n(n-1)/2 ..."
+inline int ppk_condensed_samples(size_t n_rows, size_t *n, const std::string &who = "",
+                                 const char *expected = "self/condensed matrix") {
+  *n = ppk_samples_of_rows(n_rows);
+  if (*n * (*n - 1) / 2 == n_rows) return PPK_OK;
+  return ppk_fail(PPK_ERR_ARG, who + "row count is not n(n-1)/2 for any n (" + expected + " expected)");
+}
+
+// ---- lower triangle: neighbour joining's order, entry e = tri(a) + b, b < a (ppk_nj.hip) ----
+__host__ __device__ __forceinline__ size_t tri(size_t a) { return a * (a - 1) / 2; }   // entries before row a
+// the row a of triangle entry e (tri(a) <= e < tri(a + 1))
+__host__ __device__ __forceinline__ size_t row_of(size_t e) {
+  size_t a = (size_t)((1.0 + sqrt(1.0 + 8.0 * (double)e)) * 0.5);
+  while (a > 1 && tri(a) > e) --a;
+  while (tri(a + 1) <= e) ++a;
+  return a;
+}
+__host__ __device__ __forceinline__ size_t tidx(size_t x, size_t y) { return x > y ? tri(x) + y : tri(y) + x; }
+
+// ---- lock-free union-find on an int parent array (ppk_network.hip, ppk_refine.hip) ----
+__device__ __forceinline__ int ld_relaxed(const int *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_relaxed(int *p, int v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// root of x with path halving.  parent[x] <= x always (a root only ever links under a smaller one), so every write
+// here stores an ancestor, and a racing write at worst stores a less compressed one.
+__device__ __forceinline__ int uf_find(int *parent, int x) {
+  while (true) {
+    const int p = ld_relaxed(parent + x);
+    if (p == x) return x;
+    const int gp = ld_relaxed(parent + p);
+    if (gp != p) st_relaxed(parent + x, gp);
+    x = gp;
+  }
+}
+// links the roots of a and b (the larger under the smaller): 1 when this call removed a component
+__device__ __forceinline__ unsigned uf_union(int *parent, int a, int b) {
+  while (true) {
+    a = uf_find(parent, a);
+    b = uf_find(parent, b);
+    if (a == b) return 0;
+    const int hi = a > b ? a : b, lo = a > b ? b : a;
+    if (atomicCAS(parent + hi, hi, lo) == hi) return 1;
+  }
+}
+// root of x in a finished forest: plain loads, no write
+__device__ __forceinline__ int uf_find_ro(const int *parent, int x) {
+  for (int p = parent[x]; p != x; p = parent[x]) x = p;
+  return x;
+}
+
+// ---- order-preserving float -> uint32 keys (unsigned compare == operator< on non-NaN floats) ----
+// The raw transform of the bit pattern: -0.0 sorts strictly BEFORE +0.0 (ppk_iterate.hip's sort key).
+__host__ __device__ __forceinline__ unsigned ord_raw(float f) {
+  const unsigned u = __builtin_bit_cast(unsigned, f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// The folded form: -0.0 -> +0.0 first (f + 0.0f), so the two zeros share a key and radix order equals operator<
+// (ppk_square.hip, ppk_sparse.hip, ppk_mst.hip).  ord_inv gives the float back, -0.0 as +0.0.
+__host__ __device__ __forceinline__ unsigned ord_of(float f) { return ord_raw(f + 0.0f); }
+__host__ __device__ __forceinline__ float ord_inv(unsigned o) {
+  return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+// ---- wave reductions ----
+// The loops still written out at their call sites (ppk_boundary.hip, ppk_embed.hip, the fit's changed-label count)
+// compile to other instructions through a call (profiles/shared_device/README.md); new code calls these.
+// shuffle-down: the sum on lane 0, added in this fixed order (the BGMM fit's fp64 sums depend on it).  `width` is the
+// shuffle's: the fit passes warpSize, the shuffle's own default -- the same lanes, but other index arithmetic than 64.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v, int width = PPK_LANES) {
+#pragma unroll
+  for (int o = PPK_LANES / 2; o > 0; o >>= 1) v += __shfl_down(v, o, width);
+  return v;
+}
+// shuffle-xor: the sum on every lane
+template <typename T>
+__device__ __forceinline__ T wave_sum_all(T v) {
+  for (int o = PPK_LANES / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+// adds every thread's v into *out: one atomic per wave
+__device__ __forceinline__ void wave_add(unsigned long long *out, unsigned long long v) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);
+}
+
+// spread the 32 bits of x to the even bit positions of a 64-bit word (wave-uniform: SALU)
+__device__ __forceinline__ uint64_t spread_even(uint32_t v) {
+  uint64_t x = v;
+  x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
+  x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
+  x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+  x = (x | (x << 2)) & 0x3333333333333333ull;
+  x = (x | (x << 1)) & 0x5555555555555555ull;
+  return x;
+}
+
+// line_dist of src/boundary.cpp:42-58: float32, un-fused, evaluated as
+// ((y0*x_max) + (x0*y_max)) - (x_max*y_max)  (SURVEY.md Appendix B).
+__device__ __forceinline__ float ppk_line_dist(float x0, float y0, float x_max, float y_max,
+                                               int slope) {
+  float side = 0.0f;
+  if (slope == 2) {
+    if (x_max == 0.0f || y_max == 0.0f) {
+      side = __fsqrt_rn(__fadd_rn(__fmul_rn(x0, x0), __fmul_rn(y0, y0)));
+    } else {
+      side = __fsub_rn(__fadd_rn(__fmul_rn(y0, x_max), __fmul_rn(x0, y_max)),
+                       __fmul_rn(x_max, y_max));
+    }
+  } else if (slope == 0) {
+    side = __fsub_rn(x0, x_max);
+  } else if (slope == 1) {
+    side = __fsub_rn(y0, y_max);
+  }
+  return side;
+}
+
+// ---- the x / scale rule and the 2-D Gaussian form ----
+// BGMMFit assignment of one row (PopPUNK/bgmm.py:100-176, PopPUNK/models.py:181-187), the ONE statement every
+// path uses (kernel 2, the fused tile epilogues, the DBSCAN assignment's scaling and the BGMM fit's E-step), so that
+// the fused edge list equals the two-step one bit for bit.  xs = x / scale in the dtype numpy promotes to (float32 /
+// float32, or float64).  The triangular solve and the quadratic form are six fused multiply-adds per component on
+// the constants the host computed in double (ppk_lin_of): the pass is VALU-issue bound (profiles/bgmm/), and the
+// explicit fma() is the operation count that matters -- its rounding differs from the reference's separate multiply
+// and add by a few units in the last place of lpr, far below the 1e-9 the label comparison allows.
+__device__ __forceinline__ double ppk_scaled_f32(float x, float scale) { return (double)__fdiv_rn(x, scale); }
+// M: a model with scale_is_f64, scale_f32[2] and scale_f64[2] (ppk_bgmm; the DBSCAN assignment's AssignModel)
+template <class M>
+__device__ __forceinline__ void ppk_bgmm_scaled(float core, float acc, const M &m, double &xs, double &ys) {
+  if (m.scale_is_f64) {
+    xs = (double)core / m.scale_f64[0];
+    ys = (double)acc / m.scale_f64[1];
+  } else {
+    xs = ppk_scaled_f32(core, m.scale_f32[0]);
+    ys = ppk_scaled_f32(acc, m.scale_f32[1]);
+  }
+}
+// the weighted log-probability of component c.  M: a model with lin[][5] and log_const[] (ppk_bgmm; the fit's FitArgs)
+template <class M>
+__device__ __forceinline__ double ppk_bgmm_lpr(double xs, double ys, const M &m, int c) {
+  const double *l = m.lin[c];
+  const double z0 = __builtin_fma(xs, l[0], l[1]);
+  const double z1 = __builtin_fma(ys, l[2], __builtin_fma(z0, l[3], l[4]));
+  return __builtin_fma(-0.5, __builtin_fma(z0, z0, z1 * z1), m.log_const[c]);
+}
+// argmax_c lpr_c, the first index on ties (np.argmax of the responsibilities, which keep the order of lpr): no
+// transcendental.  KT > 0: the component count as a compile-time constant (kernel 2's instantiations for K <= 4: the
+// loop unrolls and the model's constants stay in scalar registers across rows); 0: m.K at run time.  The arithmetic
+// is the same statement in the same order either way.
+template <int KT = 0>
+__device__ __forceinline__ int ppk_bgmm_label_k(double xs, double ys, const ppk_bgmm &m) {
+  double best = ppk_bgmm_lpr(xs, ys, m, 0);
+  int label = 0;
+  if constexpr (KT > 0) {
+#pragma unroll
+    for (int c = 1; c < KT; ++c) {
+      const double v = ppk_bgmm_lpr(xs, ys, m, c);
+      if (v > best) {
+        best = v;
+        label = c;
+      }
+    }
+  } else {
+    for (int c = 1; c < m.K; ++c) {
+      const double v = ppk_bgmm_lpr(xs, ys, m, c);
+      if (v > best) {
+        best = v;
+        label = c;
+      }
+    }
+  }
+  return label;
+}
+template <int KT = 0>
+__device__ __forceinline__ int ppk_bgmm_label(float core, float acc, const ppk_bgmm &m) {
+  double xs, ys;
+  ppk_bgmm_scaled(core, acc, m, xs, ys);
+  return ppk_bgmm_label_k<KT>(xs, ys, m);
+}
+
+// ---- host only ----
+// Lower Cholesky factor {L00, L10, L11} of [[a, b], [b, d]], as LAPACK's dpotrf (scipy.linalg.cholesky, bgmm.py:131-
+// 176): false when a pivot is <= 0 or NaN
+inline bool chol2(double a, double b, double d, double L[3]) {
+  if (!(a > 0.0)) return false;
+  const double l00 = std::sqrt(a);
+  const double l10 = b / l00;
+  const double r = d - l10 * l10;
+  if (!(r > 0.0)) return false;
+  L[0] = l00;
+  L[1] = l10;
+  L[2] = std::sqrt(r);
+  return true;
+}
+// ppk_bgmm_lpr's coefficients lin[c] = {1/L00, -mu0/L00, 1/L11, -L10/L11, -mu1/L11} from the mean, L and i0 = 1/L00, i1 = 1/L11
+inline void ppk_lin_of(const double mean[2], const double L[3], double i0, double i1, double lin[5]) {
+  lin[0] = i0;
+  lin[1] = -mean[0] * i0;
+  lin[2] = i1;
+  lin[3] = -L[1] * i1;
+  lin[4] = -mean[1] * i1;
+}
+// the least r with 2^r >= n (at most 62)
+inline int ceil_log2(size_t n) {
+  int r = 0;
+  while (r < 62 && ((size_t)1 << r) < n) ++r;
+  return r;
+}

@@ -1,4 +1,5 @@
-// Internal declarations shared by the translation units of libppk_hip.so.
+// Internal host declarations shared by the translation units of libppk_hip.so; the device and host-device
+// arithmetic they share is ppk_device.h, included below.
 // gfx950 / CDNA4 only (wave64); no other target is supported.
 #pragma once
 
@@ -22,6 +23,8 @@
 #define PPK_MAX_NK 128         // k-mer lengths per query (the reference accepts k = 3 .. 101: PopPUNK/__main__.py)
 #define PPK_LANES 64           // wavefront width on CDNA
 #define PPK_NPAD 256           // sample axis padded to a multiple of this
+
+#include "ppk_device.h"
 
 struct ppk_db {
   int device;
@@ -347,94 +350,6 @@ int ppk_knn_band_dev(const ppk_db *db, const ppk_db *qry, const int32_t *kmers, 
                      int flags, int knn, int dist_col, size_t q_begin, size_t q_end, long long missing_j, long long *d_i,
                      long long *d_j, float *d_dist, unsigned long long *n_candidates, void *stream);
 size_t ppk_rows_per_dispatch(const ppk_db *ref);     // query rows one kernel launch may cover (ppk_launch_dist)
-
-// spread the 32 bits of x to the even bit positions of a 64-bit word (wave-uniform: SALU)
-__device__ __forceinline__ uint64_t spread_even(uint32_t v) {
-  uint64_t x = v;
-  x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
-  x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
-  x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
-  x = (x | (x << 2)) & 0x3333333333333333ull;
-  x = (x | (x << 1)) & 0x5555555555555555ull;
-  return x;
-}
-
-// line_dist of src/boundary.cpp:42-58: float32, un-fused, evaluated as
-// ((y0*x_max) + (x0*y_max)) - (x_max*y_max)  (SURVEY.md Appendix B).
-__device__ __forceinline__ float ppk_line_dist(float x0, float y0, float x_max, float y_max,
-                                               int slope) {
-  float side = 0.0f;
-  if (slope == 2) {
-    if (x_max == 0.0f || y_max == 0.0f) {
-      side = __fsqrt_rn(__fadd_rn(__fmul_rn(x0, x0), __fmul_rn(y0, y0)));
-    } else {
-      side = __fsub_rn(__fadd_rn(__fmul_rn(y0, x_max), __fmul_rn(x0, y_max)),
-                       __fmul_rn(x_max, y_max));
-    }
-  } else if (slope == 0) {
-    side = __fsub_rn(x0, x_max);
-  } else if (slope == 1) {
-    side = __fsub_rn(y0, y_max);
-  }
-  return side;
-}
-
-// BGMMFit assignment of one row (PopPUNK/bgmm.py:100-176, PopPUNK/models.py:181-187), the ONE statement every
-// BGMM path uses (kernel 2 and the fused tile epilogues), so that the fused edge list equals the two-step one bit for
-// bit.  xs = x / scale in the dtype numpy promotes to (float32 / float32, or float64).  The triangular solve and the
-// quadratic form are six fused multiply-adds per component on the constants ppk_bgmm_prepare computed in double
-// (ppk_bgmm::lin): the pass is VALU-issue bound (profiles/bgmm/), and the explicit fma() is the operation count that
-// matters -- its rounding differs from the reference's separate multiply and add by a few units in the last place of
-// lpr, far below the 1e-9 the label comparison allows.
-__device__ __forceinline__ void ppk_bgmm_scaled(float core, float acc, const ppk_bgmm &m, double &xs, double &ys) {
-  if (m.scale_is_f64) {
-    xs = (double)core / m.scale_f64[0];
-    ys = (double)acc / m.scale_f64[1];
-  } else {
-    xs = (double)__fdiv_rn(core, m.scale_f32[0]);
-    ys = (double)__fdiv_rn(acc, m.scale_f32[1]);
-  }
-}
-__device__ __forceinline__ double ppk_bgmm_lpr(double xs, double ys, const ppk_bgmm &m, int c) {
-  const double *l = m.lin[c];
-  const double z0 = __builtin_fma(xs, l[0], l[1]);
-  const double z1 = __builtin_fma(ys, l[2], __builtin_fma(z0, l[3], l[4]));
-  return __builtin_fma(-0.5, __builtin_fma(z0, z0, z1 * z1), m.log_const[c]);
-}
-// argmax_c lpr_c, the first index on ties (np.argmax of the responsibilities, which keep the order of lpr): no
-// transcendental.  KT > 0: the component count as a compile-time constant (kernel 2's instantiations for K <= 4: the
-// loop unrolls and the model's constants stay in scalar registers across rows); 0: m.K at run time.  The arithmetic
-// is the same statement in the same order either way.
-template <int KT = 0>
-__device__ __forceinline__ int ppk_bgmm_label_k(double xs, double ys, const ppk_bgmm &m) {
-  double best = ppk_bgmm_lpr(xs, ys, m, 0);
-  int label = 0;
-  if constexpr (KT > 0) {
-#pragma unroll
-    for (int c = 1; c < KT; ++c) {
-      const double v = ppk_bgmm_lpr(xs, ys, m, c);
-      if (v > best) {
-        best = v;
-        label = c;
-      }
-    }
-  } else {
-    for (int c = 1; c < m.K; ++c) {
-      const double v = ppk_bgmm_lpr(xs, ys, m, c);
-      if (v > best) {
-        best = v;
-        label = c;
-      }
-    }
-  }
-  return label;
-}
-template <int KT = 0>
-__device__ __forceinline__ int ppk_bgmm_label(float core, float acc, const ppk_bgmm &m) {
-  double xs, ys;
-  ppk_bgmm_scaled(core, acc, m, xs, ys);
-  return ppk_bgmm_label_k<KT>(xs, ys, m);
-}
 
 // ---- helper threads ----------------------------------------------------------------
 // A host call uses a dozen short-lived helpers (page touchers, per-device workers, hash lanes); starting

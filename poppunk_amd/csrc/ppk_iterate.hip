@@ -44,12 +44,6 @@ namespace {
 // offsets per call
 constexpr int kMaxOff = 1023;
 
-// order-preserving float -> uint32 (the sort key; unsigned compare == operator< on non-NaN floats)
-__device__ __forceinline__ unsigned f2ord(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // a boundary as the classify pass reads it (one s_load_dwordx4): x_max, y_max, fl(x_max * y_max)
 struct Bnd {
   float xm, ym, c, pad;
@@ -391,7 +385,7 @@ ti1_classify_kernel(const float2 *__restrict__ dist, size_t n_rows, const Bnd *_
         if constexpr (MODE == 2) d0 = __fsub_rn(__fadd_rn(__fmul_rn(y[r], b0.xm), __fmul_rn(x[r], b0.ym)), b0.c);
         else d0 = ppk_line_dist(x[r], y[r], b0.xm, b0.ym, slope);
         d0 = d0 + 0.0f;      // -0.0 -> +0.0 so that the radix order equals operator<
-        const unsigned c = f2ord(d0);
+        const unsigned c = ord_raw(d0);      // the sort key
         if (is_cand) cand_key[slot] = c;
         // rows grow within a lane: strict < keeps the earliest
         if (in && cnt[r] == 0 && d0 == d0 && c < best_ord) {
@@ -839,21 +833,13 @@ ti2_mask_kernel(const float2 *__restrict__ dist, size_t n_rows, const Bnd *__res
       // (words past the rows' end are zero: no lane of theirs is valid)
       if (lane < kTi2Words) mask[(size_t)(o0 + j) * seg_words + w0 + lane] = (uint64_t)rlo[j] | ((uint64_t)rhi[j] << 32);
       unsigned c = (unsigned)__popc(rlo[j]) + (unsigned)__popc(rhi[j]);
-#pragma unroll
-      for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
+      c = wave_sum(c);
       if (lane == 0 && c) atomicAdd(&sh[j], c);
     }
     __syncthreads();
     if (threadIdx.x < (unsigned)oc) block_sums[(size_t)(o0 + threadIdx.x) * seg_blocks + cb] = sh[threadIdx.x];
     __syncthreads();
   }
-}
-
-size_t samples_of(size_t n_rows) {
-  size_t n = (size_t)(0.5 * (1.0 + std::sqrt(1.0 + 8.0 * (double)n_rows)));
-  while (n > 1 && n * (n - 1) / 2 > n_rows) --n;
-  while ((n + 1) * n / 2 <= n_rows) ++n;
-  return n;
 }
 
 inline unsigned nblk(size_t n, size_t per = 256) { return (unsigned)((n + per - 1) / per); }
@@ -1238,9 +1224,8 @@ extern "C" int ppk_threshold_iterate_1d_dev(const float *d_dist, size_t n_rows,
   for (size_t o = 1; o < n_off; ++o)
     if (offsets[o] < offsets[o - 1])
       return ppk_fail(PPK_ERR_ARG, "Offsets to thresholdIterate1D must be sorted");
-  const size_t n_samples = samples_of(n_rows);
-  if (n_samples * (n_samples - 1) / 2 != n_rows)
-    return ppk_fail(PPK_ERR_ARG, "row count is not n(n-1)/2 for any n (self/condensed matrix expected)");
+  size_t n_samples = 0;
+  if (int rc = ppk_condensed_samples(n_rows, &n_samples)) return rc;
   if (n_rows >= (size_t)0x7fffffff * 64) return ppk_fail(PPK_ERR_ARG, "too many rows");
 
   // boundaries, with the arithmetic of boundary.cpp:161-186 (float/double mix kept as is)
@@ -1292,9 +1277,8 @@ extern "C" int ppk_threshold_iterate_2d_dev(const float *d_dist, size_t n_rows, 
   for (size_t o = 1; o < n_off; ++o)
     if (x_max[o] < x_max[o - 1])
       return ppk_fail(PPK_ERR_ARG, "x_max range to thresholdIterate2D must be sorted");
-  const size_t n_samples = samples_of(n_rows);
-  if (n_samples * (n_samples - 1) / 2 != n_rows)
-    return ppk_fail(PPK_ERR_ARG, "row count is not n(n-1)/2 for any n (self/condensed matrix expected)");
+  size_t n_samples = 0;
+  if (int rc = ppk_condensed_samples(n_rows, &n_samples)) return rc;
   std::vector<Bnd> bnd(n_off);
   bool fast = y_max != 0.0f;
   for (size_t o = 0; o < n_off; ++o) {

@@ -37,13 +37,6 @@ constexpr unsigned kNone = 0xffffffffu;   // an empty best slot (ranks are < 2^3
 constexpr int kHops = 16;                 // pointer hops per compression pass
 constexpr int kMaxRounds = 32;
 
-// order-preserving unsigned key of a finite float, -0.0 read as +0.0
-__device__ __forceinline__ unsigned float_key(float w) {
-  unsigned u = __float_as_uint(w);
-  if (u == 0x80000000u) u = 0;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // ---- validate ----------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kThreads) mst_validate_kernel(const long long *ei, const long long *ej, size_t stride,
                                                                 const float *w, size_t m, long long n,
@@ -69,7 +62,7 @@ __global__ void __launch_bounds__(kThreads) mst_pair_key_kernel(const long long 
 __global__ void __launch_bounds__(kThreads) mst_weight_key_kernel(const float *w, const int *idx, size_t m,
                                                                   unsigned *keys) {
   for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += (size_t)gridDim.x * blockDim.x)
-    keys[p] = float_key(w[idx[p]]);
+    keys[p] = ord_of(w[idx[p]]);      // finite (mst_validate_kernel), -0.0 read as +0.0
 }
 
 __global__ void __launch_bounds__(kThreads) mst_ends_kernel(const long long *ei, const long long *ej, size_t stride,
@@ -201,10 +194,6 @@ __device__ __forceinline__ float sqrt_rn(float s) {
   return r;
 }
 
-__device__ __forceinline__ size_t cond_index(size_t a, size_t b, size_t n) {   // a < b < n
-  return a * n - (a * (a + 1)) / 2 + (b - a - 1);
-}
-
 __global__ void __launch_bounds__(kThreads) mst_weights_kernel(const float2 *dist, long long n_samples, long long n_ref,
                                                                long long n_qry, long long off, const long long *ei,
                                                                const long long *ej, size_t stride, size_t m, int type,
@@ -243,12 +232,6 @@ int mst_bad_edge(const long long *d_i, const long long *d_j, size_t stride, cons
   else why = std::isnan(w) ? "NaN weight" : "infinite weight";
   return ppk_fail(PPK_ERR_ARG, "ppk_mst: edge " + std::to_string(k) + " (i=" + std::to_string(i) + ", j=" +
                                    std::to_string(j) + "): " + why);
-}
-
-int ceil_log2(size_t n) {
-  int r = 0;
-  while (r < 62 && ((size_t)1 << r) < n) ++r;
-  return r;
 }
 
 }  // namespace
@@ -429,11 +412,7 @@ extern "C" int ppk_edge_weights_dev(const float *d_dist, size_t n_rows, const lo
   if (n_rows >= ((size_t)1 << 62)) return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: n_rows too large");
   size_t n_samples = 0, n_qry = 0;
   if (n_ref == 0) {
-    n_samples = (size_t)((1.0 + std::sqrt(1.0 + 8.0 * (double)n_rows)) / 2.0);
-    while (n_samples > 1 && n_samples * (n_samples - 1) / 2 > n_rows) --n_samples;
-    while ((n_samples + 1) * n_samples / 2 <= n_rows) ++n_samples;
-    if (n_samples * (n_samples - 1) / 2 != n_rows)
-      return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: row count is not n(n-1)/2 for any n (self matrix expected)");
+    if (int rc = ppk_condensed_samples(n_rows, &n_samples, "ppk_edge_weights: ", "self matrix")) return rc;
   } else {
     if (n_rows % n_ref) return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: row count is not a multiple of n_ref");
     n_qry = n_rows / n_ref;

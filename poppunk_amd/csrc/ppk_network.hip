@@ -41,13 +41,6 @@ constexpr int kScatterItems = 16;      // edges per thread of one scatter chunk
 constexpr size_t kTableMax = 73728;
 constexpr size_t kTableSmall = 24576;  // ... when the launch cannot be given more than 64 KiB of dynamic LDS
 
-__device__ __forceinline__ int ld_relaxed(const int *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_relaxed(int *p, int v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Per-lane run of one histogram bin: consecutive adds to the same bin (the common case: rows are in offset order)
 // cost one LDS atomic per run instead of one per add.
 struct BinRun {
@@ -162,34 +155,12 @@ __global__ void __launch_bounds__(kThreads) net_parent_init_kernel(int *parent, 
     parent[v] = (int)v;
 }
 
-// root of x with path halving.  parent[x] <= x always (a root only ever links under a smaller one), so every write
-// here stores an ancestor, and a racing write at worst stores a less compressed one.
-__device__ __forceinline__ int uf_find(int *parent, int x) {
-  while (true) {
-    const int p = ld_relaxed(parent + x);
-    if (p == x) return x;
-    const int gp = ld_relaxed(parent + p);
-    if (gp != p) st_relaxed(parent + x, gp);
-    x = gp;
-  }
-}
-
 // one offset batch: link the two roots of every edge; links[t] += the successful links
 __global__ void __launch_bounds__(kThreads) net_union_kernel(const int *bu, const int *bv, unsigned len, int *parent,
                                                              unsigned *links_t) {
   unsigned mine = 0;
   for (unsigned k = blockIdx.x * blockDim.x + threadIdx.x; k < len; k += gridDim.x * blockDim.x) {
-    int a = bu[k], b = bv[k];
-    while (true) {
-      a = uf_find(parent, a);
-      b = uf_find(parent, b);
-      if (a == b) break;
-      const int hi = a > b ? a : b, lo = a > b ? b : a;
-      if (atomicCAS(parent + hi, hi, lo) == hi) {
-        ++mine;
-        break;
-      }
-    }
+    mine += uf_union(parent, bu[k], bv[k]);
   }
   __shared__ unsigned acc;
   if (threadIdx.x == 0) acc = 0;
@@ -377,14 +348,9 @@ enum { H_K, H_KBIG, H_KGLOB, H_ITEMS, H_ITEMS_GLOB, H_PARTIAL, H_SCORED, H_NC_GL
 
 size_t bt_state_bytes(size_t nc) { return 36 * nc + 8; }
 
-__device__ __forceinline__ int bt_find(const int *parent, int x) {
-  for (int p = parent[x]; p != x; p = parent[x]) x = p;
-  return x;
-}
-
 __global__ void __launch_bounds__(kThreads) bt_sizes_kernel(const int *parent, size_t n, int *root, int *size) {
   for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) {
-    const int r = bt_find(parent, (int)v);
+    const int r = uf_find_ro(parent, (int)v);
     root[v] = r;
     atomicAdd(&size[r], 1);
   }

@@ -35,18 +35,6 @@ struct Best {
   unsigned long long e;
 };
 
-__host__ __device__ __forceinline__ size_t tri(size_t a) { return a * (a - 1) / 2; }   // entries before row a
-
-// the row a of triangle entry e (tri(a) <= e < tri(a + 1))
-__device__ __forceinline__ size_t row_of(size_t e) {
-  size_t a = (size_t)((1.0 + sqrt(1.0 + 8.0 * (double)e)) * 0.5);
-  while (a > 1 && tri(a) > e) --a;
-  while (tri(a + 1) <= e) ++a;
-  return a;
-}
-
-__device__ __forceinline__ size_t tidx(size_t x, size_t y) { return x > y ? tri(x) + y : tri(y) + x; }
-
 // (q, e) lexicographic: the smaller Q, then the smaller triangle index (the smaller a, then the smaller b).  -0.0 and
 // +0.0 compare equal.
 __device__ __forceinline__ bool better(double q, unsigned long long e, double bq, unsigned long long be) {
@@ -281,10 +269,7 @@ size_t first_compaction(long long n) {
 }
 
 int nj_bad_entry(const float *src, int kind, size_t stride, size_t col, size_t n, size_t e) {
-  size_t a = (size_t)((1.0 + std::sqrt(1.0 + 8.0 * (double)e)) * 0.5);
-  while (a > 1 && tri(a) > e) --a;
-  while (tri(a + 1) <= e) ++a;
-  const size_t b = e - tri(a);
+  const size_t a = row_of(e), b = e - tri(a);
   const size_t off = kind == PPK_NJ_SQUARE ? a * n + b : (b * n - b * (b + 1) / 2 + (a - b - 1)) * stride + col;
   float v = 0.0f;
   PPK_HIP(hipMemcpy(&v, src + off, 4, hipMemcpyDeviceToHost));

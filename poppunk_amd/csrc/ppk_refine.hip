@@ -56,64 +56,9 @@ constexpr size_t kChunk = (size_t)kChunkSteps * kThreads;
 enum { C_LINKS = 0, C_DEG2, C_TRIPLES, C_TRI, C_P, C_S1, C_S2, C_S3, C_BASE, C_CAND, C_NEVER, C_LEN = 16 };
 enum { CLASS_BASE = 0, CLASS_CAND = 1, CLASS_NEVER = 2 };
 
-__device__ __forceinline__ size_t cond_row_start(size_t i, size_t n) { return i * n - (i * (i + 1)) / 2; }
-// i of condensed row k (src/boundary.cpp:22-31): a double sqrt estimate, then an integer fix-up, exact for every n
-__device__ __forceinline__ size_t cond_row_i(size_t k, size_t n) {
-  const double d = sqrt((double)(4 * n * (n - 1)) - 8.0 * (double)k - 7.0);
-  long long i = (long long)n - 2 - (long long)floor(d / 2.0 - 0.5);
-  if (i < 0) i = 0;
-  if (i > (long long)n - 2) i = (long long)n - 2;
-  while (i > 0 && cond_row_start((size_t)i, n) > k) --i;
-  while ((size_t)i + 2 < n && cond_row_start((size_t)i + 1, n) <= k) ++i;
-  return (size_t)i;
-}
-// (i, j) of row k < n(n-1)/2: 0 <= i < j < n
-__device__ __forceinline__ void cond_pair(size_t k, size_t n, int &i, int &j) {
-  const size_t ii = cond_row_i(k, n);
-  i = (int)ii;
-  j = (int)(ii + 1 + (k - cond_row_start(ii, n)));
-}
-
-__device__ __forceinline__ int ld_relaxed(const int *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_relaxed(int *p, int v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// root of x with path halving; parent[x] <= x always, so every write stores an ancestor
-__device__ __forceinline__ int uf_find(int *parent, int x) {
-  while (true) {
-    const int p = ld_relaxed(parent + x);
-    if (p == x) return x;
-    const int gp = ld_relaxed(parent + p);
-    if (gp != p) st_relaxed(parent + x, gp);
-    x = gp;
-  }
-}
-// links the roots of a and b (the larger under the smaller): 1 when this call removed a component
-__device__ __forceinline__ unsigned uf_union(int *parent, int a, int b) {
-  while (true) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) return 0;
-    const int hi = a > b ? a : b, lo = a > b ? b : a;
-    if (atomicCAS(parent + hi, hi, lo) == hi) return 1;
-  }
-}
 __device__ __forceinline__ void set_edge(unsigned long long *bits, size_t words, int i, int j) {
   atomicOr(bits + (size_t)i * words + ((unsigned)j >> 6), 1ull << (j & 63));
   atomicOr(bits + (size_t)j * words + ((unsigned)i >> 6), 1ull << (i & 63));
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;      // valid on lane 0
-}
-// adds every thread's v into *out: one atomic per wave
-__device__ __forceinline__ void wave_add(unsigned long long *out, unsigned long long v) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);
 }
 
 __global__ void __launch_bounds__(kThreads) rf_parent_init_kernel(int *parent, size_t n) {
@@ -373,22 +318,13 @@ __global__ void rl_stats_kernel(const unsigned long long *base, const unsigned l
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-size_t samples_of_rows(size_t n_rows) {
-  size_t n = (size_t)(0.5 * (1.0 + std::sqrt(1.0 + 8.0 * (double)n_rows)));
-  while (n > 1 && n * (n - 1) / 2 > n_rows) --n;
-  while ((n + 1) * n / 2 <= n_rows) ++n;
-  return n;
-}
-
 // the matrix of a refine call, checked: *n = its sample count
 int check_matrix(const std::string &who, const float *d_dist, size_t n_rows, int slope, size_t *n) {
   if (!d_dist) return ppk_fail(PPK_ERR_ARG, who + ": NULL distance matrix");
   if (reinterpret_cast<uintptr_t>(d_dist) & 7) return ppk_fail(PPK_ERR_ARG, who + ": the matrix must be 8-byte aligned");
   if (slope < 0 || slope > 2) return ppk_fail(PPK_ERR_ARG, who + ": slope must be 0, 1 or 2");
   if (n_rows == 0) return ppk_fail(PPK_ERR_ARG, who + ": no rows");
-  *n = samples_of_rows(n_rows);
-  if (*n * (*n - 1) / 2 != n_rows)
-    return ppk_fail(PPK_ERR_ARG, who + ": row count is not n(n-1)/2 for any n (self/condensed matrix expected)");
+  if (int rc = ppk_condensed_samples(n_rows, n, who + ": ")) return rc;
   if (*n >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, who + ": n_vertices must be < 2^31");
   return PPK_OK;
 }

@@ -17,14 +17,7 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned ord_of(float f) {
-  const unsigned u = __float_as_uint(f + 0.0f);          // -0.0 -> +0.0: radix order equals operator<
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dist_of(uint64_t key) {
-  const unsigned o = (unsigned)(key >> 32);
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
+__device__ __forceinline__ float dist_of(uint64_t key) { return ord_inv((unsigned)(key >> 32)); }
 
 // rows of a row-sorted COO: entries of row r are [start[r], start[r+1]) (src/extend.cpp:15-38); flag[0] is
 // raised when the row indices are not ascending or leave [0, n_rows)

@@ -21,10 +21,6 @@ namespace {
 
 constexpr int T = 64;
 
-__device__ __forceinline__ size_t cond_index(size_t i, size_t j, size_t n) {  // i < j
-  return i * n - (i * (i + 1)) / 2 + (j - i - 1);
-}
-
 // grid: (n/T) x (n/T) tiles, only bj >= bi do work.  vec element e lives at vec[e*stride + col].
 __global__ void __launch_bounds__(256)
 long_to_square_kernel(const float *__restrict__ vec, size_t stride, size_t col, size_t n,
@@ -157,13 +153,6 @@ prune_query_rows_kernel(const float *__restrict__ in, size_t row_elems, const lo
 // reference's stable sort (src/extend.cpp:266-279).  A lane keeps the K smallest keys of its strided
 // share of the row sorted in registers (an element is inserted only if it beats the lane's K-th
 // best, which becomes rare quickly), then the K wave-wide minima are extracted one by one.
-__device__ __forceinline__ unsigned knn_ord(float f) {
-  const unsigned u = __float_as_uint(f + 0.0f);          // -0.0 -> +0.0
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float knn_unord(unsigned o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
 
 template <int K>
 __global__ void __launch_bounds__(256)
@@ -181,7 +170,7 @@ knn_select_kernel(const float *__restrict__ src, size_t stride, size_t col, size
   const float *row = src + (i * n_cols) * stride + col;
   for (size_t c = lane; c < n_cols; c += 64) {
     if (c == self) continue;
-    uint64_t x = ((uint64_t)knn_ord(row[c * stride]) << 32) | (uint64_t)c;
+    uint64_t x = ((uint64_t)ord_of(row[c * stride]) << 32) | (uint64_t)c;
     if (x < best[K - 1]) {
 #pragma unroll
       for (int j = 0; j < K; ++j) {      // bubble x through the sorted list
@@ -211,7 +200,7 @@ knn_select_kernel(const float *__restrict__ src, size_t stride, size_t col, size
     if (best[0] == m) {                   // keys are unique: exactly one lane
       oi[i * knn + r] = (long long)self;
       oj[i * knn + r] = (long long)(m & 0xffffffffull);
-      od[i * knn + r] = knn_unord((unsigned)(m >> 32));
+      od[i * knn + r] = ord_inv((unsigned)(m >> 32));
 #pragma unroll
       for (int j = 0; j + 1 < K; ++j) best[j] = best[j + 1];
       best[K - 1] = NONE;
@@ -265,7 +254,7 @@ knn_select_wave_kernel(const float *__restrict__ src, size_t stride, size_t col,
 #pragma unroll
     for (int b = 0; b < kBatch; ++b) {
       const size_t c = c0 + (size_t)b * 64 + lane;
-      x[b] = (c < n_cols && c != self) ? (((uint64_t)knn_ord(nxt[b]) << 32) | (uint64_t)c) : NONE;
+      x[b] = (c < n_cols && c != self) ? (((uint64_t)ord_of(nxt[b]) << 32) | (uint64_t)c) : NONE;
     }
     if (c0 + 64 * kBatch < n_cols) load(c0 + 64 * kBatch);
 #pragma unroll
@@ -293,7 +282,7 @@ knn_select_wave_kernel(const float *__restrict__ src, size_t stride, size_t col,
       od[o] = 0.0f;
     } else {
       oj[o] = (long long)(best & 0xffffffffull);
-      od[o] = knn_unord((unsigned)(best >> 32));
+      od[o] = ord_inv((unsigned)(best >> 32));
     }
   }
 }
