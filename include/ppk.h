@@ -168,9 +168,15 @@ size_t ppk_db_size(const ppk_db *db);
  * database counts the same matches, and returns the same bits, from fewer planes.  Costs up to 12/14 of the
  * database's memory again and one pass at creation; option "rank_planes" 0 (PPK_RANK_PLANES) builds and reads none.
  * ppk_db_rank_planes: the planes of the copy, 0 without one.  ppk_db_rank_read (tests): the copy as it lies,
- * [k][block * planes + plane][padded samples (a multiple of 256)] uint64, `words` = its exact length. */
+ * [k][block * planes + plane][padded samples (a multiple of 256)] uint64, `words` = its exact length.
+ * A 64-bin block none of whose positions holds more than 2^(planes - 1) distinct values is "short": the top plane of
+ * its codes is zero in every sample, and a self job compares planes - 1 planes there (the copy keeps all of them).
+ * Option "rank_short" 0 (PPK_RANK_SHORT), read at launch, compares every plane of every block: same bits.
+ * ppk_db_rank_block_planes: the planes compared per block under "rank_short" 1, out[k * sketchsize64 + block] = planes
+ * or planes - 1; `cap` >= nk * sketchsize64 bytes.  An error without a coded copy. */
 int ppk_db_rank_planes(const ppk_db *db);
 int ppk_db_rank_read(const ppk_db *db, uint64_t *out, size_t words);
+int ppk_db_rank_block_planes(const ppk_db *db, uint8_t *out, size_t cap);
 
 /* Number of distance rows for rows q in [q_begin, q_end) (self: n_qry == 0). */
 size_t ppk_rows_in_band(size_t n_ref, size_t n_qry, size_t q_begin, size_t q_end);

@@ -57,6 +57,7 @@ const OptionEntry kOptions[] = {
     {"edge_list_keep", "PPK_EDGE_LIST_KEEP", &PpkConfig::edge_list_keep},
 #endif
     {"rank_planes", "PPK_RANK_PLANES", &PpkConfig::rank_planes},
+    {"rank_short", "PPK_RANK_SHORT", &PpkConfig::rank_short},
     {"lds_table", "PPK_LDS_TABLE", &PpkConfig::lds_table},
     {"ksplit", "PPK_KSPLIT", &PpkConfig::ksplit},
     {"ksplit_slices", "PPK_KSPLIT_SLICES", &PpkConfig::ksplit_slices},
@@ -390,6 +391,7 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   db->d_clu = nullptr;
   db->d_skR = nullptr;
   db->rank_planes = 0;
+  for (unsigned &w : db->rank_short) w = 0;
   const size_t cols = nk * db->words;
   const size_t in_bytes = n * cols * sizeof(uint64_t);
   const size_t out_bytes = db->npad * cols * sizeof(uint64_t);
@@ -429,16 +431,21 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   // Rank-coded copy (ppk_db::d_skR), once per database: D = the most distinct values any (k, bin) position holds over
   // the samples decides the planes (8, 10 or 12; more than 4 096 values: no copy).  Only a database whose self job runs
   // whole tiles reads one (launch_v2), so only such a database pays for one.  The count is read back: one
-  // synchronisation of `s` per database.
+  // synchronisation of `s` per database.  The same pass leaves the maximum of each (k, 64-bin block), read back with
+  // it: a block that holds at most 2^(planes - 1) values per position has a zero top plane, and the tile kernel leaves
+  // that plane out there (ppk_db::rank_short).
   if (rc == PPK_OK && ppk_config().rank_planes.load() != 0 && ppk_self_job_takes_tiles(db)) {
     unsigned *d_max = nullptr;
     unsigned distinct = 0;
-    e = hipMalloc(reinterpret_cast<void **>(&d_max), sizeof(unsigned));
+    const size_t n_blocks = nk * sketchsize64;
+    std::vector<unsigned> counts(1 + n_blocks, 0u);
+    e = hipMalloc(reinterpret_cast<void **>(&d_max), counts.size() * sizeof(unsigned));
     if (e == hipSuccess) {
       rc = ppk_launch_rank_count(db->d_skT, n, db->npad, nk, sketchsize64, d_max, s);
       if (rc == PPK_OK) {
-        e = hipMemcpyAsync(&distinct, d_max, sizeof(unsigned), hipMemcpyDeviceToHost, s);
+        e = hipMemcpyAsync(counts.data(), d_max, counts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
+        distinct = counts[0];
         if (e != hipSuccess) rc = ppk_fail(PPK_ERR_HIP, std::string("rank codes: ") + hipGetErrorString(e));
       }
       (void)hipFree(d_max);
@@ -452,6 +459,11 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
         } else {
           rc = ppk_launch_rank_codes(db->d_skT, db->d_skR, n, db->npad, nk, sketchsize64, planes, s);
           db->rank_planes = planes;
+          if (nk < PPK_RANK_SHORT_WORDS && sketchsize64 <= 32) {
+            for (size_t k = 0; k < nk; ++k)
+              for (size_t b = 0; b < sketchsize64; ++b)
+                if (counts[1 + k * sketchsize64 + b] <= (1u << (planes - 1))) db->rank_short[k] |= 1u << b;
+          }
         }
       }
     } else {
@@ -488,6 +500,18 @@ extern "C" int ppk_db_rank_read(const ppk_db *db, uint64_t *out, size_t words) {
   if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(db->device));
   PPK_HIP(hipDeviceSynchronize());
   PPK_HIP(hipMemcpy(out, db->d_skR, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return PPK_OK;
+}
+
+extern "C" int ppk_db_rank_block_planes(const ppk_db *db, uint8_t *out, size_t cap) {
+  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_rank_block_planes: NULL argument");
+  if (!db->rank_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_rank_block_planes: the database has no rank-coded copy");
+  if (cap < db->nk * db->s64) return ppk_fail(PPK_ERR_ARG, "ppk_db_rank_block_planes: `cap` is below nk * sketchsize64");
+  for (size_t k = 0; k < db->nk; ++k)
+    for (size_t b = 0; b < db->s64; ++b) {
+      const bool is_short = k < PPK_RANK_SHORT_WORDS && b < 32 && ((db->rank_short[k] >> b) & 1u);
+      out[k * db->s64 + b] = (uint8_t)(db->rank_planes - (is_short ? 1 : 0));
+    }
   return PPK_OK;
 }
 

@@ -185,6 +185,11 @@ struct DistParams {
   int ext_skip;           // [EXT] a6: skip instead of truncate at J < 5/s (PpkConfig::ext_fit_skip)
 
   int kmers[PPK_MAX_NK];
+  // dist_kernel_v2_rank only (appended: every field above keeps its offset).  Bit b of rank_short[k]: block b of k holds
+  // at most 2^(P-1) distinct values per position, so plane P-1 of its codes is zero and the kernel compares P-1 planes
+  // there (ppk_db::rank_short; all zero with option "rank_short" 0).  The kernel reads word k at the end of k - 1, and
+  // word nk after the last k: PPK_RANK_SHORT_WORDS > nk.
+  unsigned rank_short[PPK_RANK_SHORT_WORDS];
 };
 
 // With every k usable the least-squares fit is LINEAR in the log J_k with launch-constant weights:
@@ -241,7 +246,8 @@ transpose_kernel(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, si
 // Rank codes of a bbits = 14 database (ppk_db::d_skR).  One workgroup per (k, 64-bin block, byte g of the block's
 // words) = 8 bin positions.  Per position a 16 384-bit presence bitmap of the values samples [0, n) hold there goes into
 // LDS; its prefix popcount turns a value into its rank among the position's distinct values.
-//   WRITE = false: only the largest number of distinct values of any position, into *max_distinct.
+//   WRITE = false: only the largest number of distinct values of any position, into max_distinct[0], and of any
+//                  position of each (k, 64-bin block), into max_distinct[1 + k * s64 + block].
 //   WRITE = true:  byte g of the PL code planes of every sample, out = [k][block * PL + plane][npad] (padding samples
 //                  get code 0).  The caller has checked that every rank is below 2^PL.
 constexpr int RANK_BB = 14;                      // the one bbits with a coded copy (the tile kernels' V2_BB)
@@ -287,7 +293,10 @@ rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, un
       if (t >= d) incl += up;
     }
     if (!WRITE) {
-      if (t == 31) atomicMax(max_distinct, incl);
+      if (t == 31) {
+        atomicMax(max_distinct, incl);
+        atomicMax(max_distinct + 1 + kb, incl);
+      }
       return;
     }
     uint32_t run = incl - sum;
@@ -1360,6 +1369,9 @@ int launch_v2(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const f
       const dim3 grid((unsigned)n_blocks), block(NW * 64);
       ppk_set_kernel_name(pl == 12 ? "dist_kernel_v2<256x32,lds-dma,rank 12>" : pl == 10 ? "dist_kernel_v2<256x32,lds-dma,rank 10>"
                                                                                          : "dist_kernel_v2<256x32,lds-dma,rank 8>");
+      // the blocks that compare one plane fewer (option "rank_short", read here: one database runs either way)
+      const bool use_short = ppk_config().rank_short.load() != 0;
+      for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.rank_short[k] = use_short ? ref->rank_short[k] : 0u;
       ppk_prof_begin(s);
       if (pl == 12)
         hipLaunchKernelGGL((dist_kernel_v2_rank<12, MODE>), grid, block, 0, s, sk, sk, d_lut, clu, clu, d_rtab, d_out, d_n_failed, d_mask, p);
@@ -1455,7 +1467,7 @@ int ppk_launch_transpose(const uint64_t *d_in, uint64_t *d_out, size_t n, size_t
 // The rank codes of a transposed bbits = 14 database (rank_code_kernel): the count pass, then -- with `d_out` -- the
 // code planes.  Both only enqueue.
 int ppk_launch_rank_count(const uint64_t *d_skT, size_t n, size_t npad, size_t nk, size_t s64, unsigned *d_max, hipStream_t s) {
-  PPK_HIP(hipMemsetAsync(d_max, 0, sizeof(unsigned), s));
+  PPK_HIP(hipMemsetAsync(d_max, 0, (1 + nk * s64) * sizeof(unsigned), s));
   hipLaunchKernelGGL(rank_code_kernel<false>, dim3((unsigned)(nk * s64 * 8)), dim3(256), 0, s, d_skT, nullptr, d_max, n,
                      npad, (int)s64, 0);
   PPK_HIP(hipGetLastError());

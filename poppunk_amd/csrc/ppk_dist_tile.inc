@@ -6,7 +6,8 @@
 //   PL: the bit-planes a 64-bin block is copied and compared in.  14 = the sketch's own bbits; 8, 10 or 12 on a
 //       rank-coded database (ppk_db::d_skR: every bin value replaced by its rank among the distinct values of its
 //       (k, bin) position, which keeps "equal / not equal" and so every count).  The collision adjustment and the fit
-//       table still see the real width (V2_BB).
+//       table still see the real width (V2_BB).  A block whose flag in DistParams::rank_short is set ("short": every
+//       code of the block is below 2^(PL-1), plane PL-1 is zero) is copied whole and compared in PL - 1 planes.
   static_assert(NW == 8, "the product tile is 256 refs x 32 queries (8 wavefronts)");
   static_assert(PL == V2_BB || (PL >= 8 && PL < V2_BB && PL % 2 == 0 && W == 2 && !KSPLIT && !WIDE && !EXP &&
                                 (MODE == MODE_DIST || ppk_is_mask(MODE))),
@@ -234,6 +235,17 @@
     }
   };
 
+  // PL < 14: the "short" flags of the blocks of k `kk`, one bit per block (DistParams::rank_short).  Fetched through the
+  // kernarg segment pointer, opaquely, once per k -- where the loop does its end-of-k work -- so that the loop carries
+  // one scalar for them and no load or wait stands in front of a block.
+  auto rank_short_word = [&](int kk) __attribute__((always_inline)) -> uint32_t {
+    const char __attribute__((address_space(4))) *ka =
+        (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    LateParams &pl = *reinterpret_cast<LateParams *>(ka + V2_PARAMS_KERNARG_OFFSET);
+    return pl.rank_short[kk];
+  };
+
   issue_dma(0, half);
   if (!(ablate & 16)) {   // (bit 16, measurement only: what hiding the tile's first copy could win)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -245,6 +257,11 @@
   auto compare_loop = [&](auto half_tag) {
   constexpr bool HALF = decltype(half_tag)::value;
   int k = k_first, blk = 0;
+  // the full block of a rank-coded database leaves the top plane out where the block's flag says it is zero (the half
+  // block of the diagonal tiles compares every plane: a zero plane changes no count, and those tiles are few)
+  constexpr bool SHORT_BLOCKS = PL < V2_BB && !HALF;
+  uint32_t short_w = 0;
+  if constexpr (SHORT_BLOCKS) short_w = rank_short_word(k);
   for (int g = 0; g < total; ++g) {
     const int buf = g & 1;
     // the other buffer was last read in iteration g-1, which every wave left through the barrier
@@ -299,27 +316,28 @@
           const uint32_t xblo = __builtin_amdgcn_readfirstlane((uint32_t)xb),
                          xbhi = __builtin_amdgcn_readfirstlane((uint32_t)(xb >> 32));
           const uint32_t vob = dkind[LT] == 0 ? voff_ref : voff_qry;
-          if constexpr (PW == 4) {
-#define PPK_DMA_STMT(SUF)                                                                                         \
-  asm volatile(PPK_BLOCK_DMA_ASM_Q32##SUF                                                                         \
+          // PL < 14: the statement holds the full and the short stream and picks one on bit blk of short_w (a scalar
+          // bit test and a branch inside the asm: the compiler sees one statement, as in the raw kernel)
+#define PPK_DMA_SEL_STMT(SUF, SB2)                                                                                \
+  asm volatile(PPK_BLOCK_DMA_SEL_ASM_Q32##SUF                                                                     \
                : PPK_BLOCK_OPERANDS                                                                               \
                : [rp] "v"(rp), [qp] "v"(qp), [m00] "s"(m00), [m03] "s"(m03), [sb0] "s"(dbase[0]),                 \
-                 [sb1] "s"(dbase[1]), [sb2] "s"(dbase[2]), [sb3] "s"(dbase[3]), [voa] "v"(voff_ref),              \
-                 [vob] "v"(vob), [xblo] "s"(xblo), [xbhi] "s"(xbhi)                                               \
+                 [sb1] "s"(dbase[1]), [sb2] "s"(dbase[SB2]), [sb3] "s"(dbase[LT]), [voa] "v"(voff_ref),           \
+                 [vob] "v"(vob), [xblo] "s"(xblo), [xbhi] "s"(xbhi), [sh] "s"(short_w), [bk] "s"(blk)             \
                : "memory", "scc", PPK_BLOCK_CLOBBERS);
-            if constexpr (PL == 14) { PPK_DMA_STMT() } else { PPK_DMA_STMT(_P12) }
-#undef PPK_DMA_STMT
+          if constexpr (PL < V2_BB) {
+            if constexpr (PL == 12) { PPK_DMA_SEL_STMT(_P12, 2) }
+            else if constexpr (PL == 10) { PPK_DMA_SEL_STMT(_P10, LT) }
+            else { PPK_DMA_SEL_STMT(_P8, LT) }
           } else {
-#define PPK_DMA_STMT(SUF)                                                                                         \
-  asm volatile(PPK_BLOCK_DMA_ASM_Q32##SUF                                                                         \
-               : PPK_BLOCK_OPERANDS                                                                               \
-               : [rp] "v"(rp), [qp] "v"(qp), [m00] "s"(m00), [m03] "s"(m03), [sb0] "s"(dbase[0]),                 \
-                 [sb1] "s"(dbase[1]), [sb2] "s"(dbase[LT]), [voa] "v"(voff_ref),                                  \
-                 [vob] "v"(vob), [xblo] "s"(xblo), [xbhi] "s"(xbhi)                                               \
-               : "memory", "scc", PPK_BLOCK_CLOBBERS);
-            if constexpr (PL == 10) { PPK_DMA_STMT(_P10) } else { PPK_DMA_STMT(_P8) }
-#undef PPK_DMA_STMT
+            asm volatile(PPK_BLOCK_DMA_ASM_Q32
+                         : PPK_BLOCK_OPERANDS
+                         : [rp] "v"(rp), [qp] "v"(qp), [m00] "s"(m00), [m03] "s"(m03), [sb0] "s"(dbase[0]),
+                           [sb1] "s"(dbase[1]), [sb2] "s"(dbase[2]), [sb3] "s"(dbase[3]), [voa] "v"(voff_ref),
+                           [vob] "v"(vob), [xblo] "s"(xblo), [xbhi] "s"(xbhi)
+                         : "memory", "scc", PPK_BLOCK_CLOBBERS);
           }
+#undef PPK_DMA_SEL_STMT
           // (after the last block the pieces harmlessly re-load it into the idle buffer)
           if (g + 2 < total) {
 #pragma unroll
@@ -407,6 +425,7 @@
       if (++blk == ublocks) {
         blk = 0;
         ++k;
+        if constexpr (SHORT_BLOCKS) short_w = rank_short_word(k);      // (word nk after the last k: in the array, unused)
       }
     }
     // my DMA pieces have landed; after the barrier everyone's have, and everyone has

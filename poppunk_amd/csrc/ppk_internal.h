@@ -23,6 +23,7 @@
 #define PPK_MAX_NK 128         // k-mer lengths per query (the reference accepts k = 3 .. 101: PopPUNK/__main__.py)
 #define PPK_LANES 64           // wavefront width on CDNA
 #define PPK_NPAD 256           // sample axis padded to a multiple of this
+#define PPK_RANK_SHORT_WORDS 16   // words of per-block "short" flags a launch carries (ppk_db::rank_short): one per k, and one to spare
 
 #include "ppk_device.h"
 
@@ -37,6 +38,11 @@ struct ppk_db {
   // matches from fewer planes (launch_v2 in ppk_dist.hip).
   uint64_t *d_skR;
   int rank_planes;
+  // rank_planes != 0: per k the 64-bin blocks that are "short".  Bit blk of rank_short[k] is set when no position of
+  // block (k, blk) holds more than 2^(rank_planes - 1) distinct values, so that the top code plane of the block is zero
+  // in every sample and the tile kernel leaves it out (option "rank_short").  Flags are kept for
+  // nk < PPK_RANK_SHORT_WORDS and s64 <= 32 (a word per k); other shapes have none.
+  unsigned rank_short[PPK_RANK_SHORT_WORDS];
 };
 
 // A database whose per-pair counts the tile kernels cannot hold: more k-mer lengths than the fit tables are laid
@@ -65,6 +71,7 @@ struct PpkConfig {
 #endif
   // -- product options
   std::atomic<long long> rank_planes{1};        // PPK_RANK_PLANES: a bbits = 14 database whose self job runs whole tiles keeps a rank-coded copy (ppk_db::d_skR) and self jobs compare it (0: no copy is built, none is read; same bits)
+  std::atomic<long long> rank_short{1};         // PPK_RANK_SHORT: a self job on a rank-coded database compares one plane fewer in the 64-bin blocks whose positions hold at most half the values the planes can code (0: every block compares all planes; same bits).  Read at launch.
   std::atomic<long long> lds_table{1};          // PPK_LDS_TABLE: interior tiles of the default sketch shape fit from the (E, F) table in LDS (0: the general statement everywhere; same bits)
   std::atomic<long long> ksplit{1200};           // PPK_KSPLIT: tile-count threshold (at 5 k) of the small-job path
   std::atomic<long long> ksplit_wide{215};      // PPK_KSPLIT_WIDE: the same threshold for sketches whose tiles are not fitted from the LDS table (never above ksplit)
@@ -165,6 +172,7 @@ struct PpkRouteChoice {
 PpkRouteChoice ppk_choose_route_impl(const PpkRouteShape &sh, const PpkGeometry &g, const PpkRouteKnobs &k);
 // rank-coded copy of a bbits = 14 database (ppk_dist.hip)
 bool ppk_self_job_takes_tiles(const ppk_db *db);
+// (d_max: 1 + nk * s64 words -- the maximum over all positions, then the maximum of each (k, 64-bin block))
 int ppk_launch_rank_count(const uint64_t *d_skT, size_t n, size_t npad, size_t nk, size_t s64, unsigned *d_max, hipStream_t s);
 int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, size_t n, size_t npad, size_t nk, size_t s64, int planes,
                           hipStream_t s);

@@ -132,6 +132,15 @@ class SketchDB:
         """Bit-planes of the database's rank-coded copy (8, 10 or 12), 0 without one (ppk_db_rank_planes)."""
         return int(_lib.lib().ppk_db_rank_planes(self._h))
 
+    def rank_block_planes(self):
+        """Planes a self job compares per 64-bin block of the rank-coded copy (ppk_db_rank_block_planes): uint8
+        [nk, sketchsize64], rank_planes or -- where no position of the block holds more than 2^(rank_planes - 1)
+        distinct values -- rank_planes - 1.  The database's own flags: option "rank_short" 0 does not change them."""
+        out = np.empty((self.nk, self.sketchsize64), dtype=np.uint8)
+        _lib.check(_lib.lib().ppk_db_rank_block_planes(self._h, C.c_void_p(out.ctypes.data), out.size),
+                   "ppk_db_rank_block_planes")
+        return out
+
     def rank_codes(self):
         """The rank-coded copy un-bitsliced (tests): uint16 [n, nk, 64 * sketchsize64] codes."""
         planes, npad = self.rank_planes, (self.n + 255) // 256 * 256

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Generates poppunk_amd/csrc/ppk_block_asm.inc: the hand-scheduled gfx950 instruction
 stream for ONE 64-bin block (14 bit-planes) of the 4-ref x 4-query register tile, and the same
-stream for the 12, 10 and 8 planes of a rank-coded database (RANK_PLANES below).
+stream for the 12, 10 and 8 planes of a rank-coded database (RANK_PLANES below), each with a "short" variant that
+leaves the top plane out (short_dma_planes).
 
 Why assembly: on MI355X a v_bitop3_b32 whose src0 and src1 sit in the same VGPR bank
 (register number mod 4) issues ~1.5x slower (tools/ubench_bank.hip: 4.7 vs 3.1 clk).  hipcc
@@ -32,6 +33,15 @@ BB = 14
 # of a wavefront is the one that may be a query piece or nothing at all (its exec mask is then 0): with P planes
 # there are 2 P ref pieces and ceil(P / 4) query pieces for 8 wavefronts.
 RANK_PLANES = {12: (4, (1, 3, 6, 9)), 10: (3, (1, 4, 7)), 8: (3, (1, 3, 5))}
+
+
+def short_dma_planes(pl):
+    """The "short" full-block stream of a P-plane database: for a 64-bin block whose positions hold at most 2^(P-1)
+    distinct values, so that plane P-1 is zero in every sample.  It copies the same pieces of the next block (all P
+    planes: the LDS chunk does not change) and reads and compares planes 0 .. P-2 only.  Its pieces sit where the
+    P-plane stream has them, rescaled to P-1 planes (rounded half up): 12 -> (1, 3, 6, 8), 10 -> (1, 4, 6),
+    8 -> (1, 3, 4)."""
+    return tuple((2 * p * (pl - 1) + pl) // (2 * pl) for p in RANK_PLANES[pl][1])
 
 
 def prio_levels(bb, v):
@@ -278,9 +288,19 @@ def main():
         # the packed two-dword kernel on a rank-coded database: the in-stream-DMA and the half block per plane count
         # (GEN_DMA_PLANES applies to the 14-plane block only)
         for pl, (_, dplanes) in sorted(RANK_PLANES.items(), reverse=True):
-            f.write("// %d planes (rank-coded database)\n" % pl)
-            write_macro(f, "PPK_BLOCK_DMA_ASM_Q32_P%d" % pl, gen(256, 4, dma_planes=list(dplanes), bb=pl))
+            f.write("// %d planes (rank-coded database): the half block\n" % pl)
             write_macro(f, "PPK_BLOCK_HALF_ASM_Q32_P%d" % pl, gen(256, 4, half=True, bb=pl))
+            # The kernel's ONE asm statement per block: the choice between the two streams is made inside it, on bit
+            # %[bk] (the block's index in its k, taken mod 32) of %[sh] (the k's short flags).  Two asm statements
+            # under a C++ branch cost more than the short stream saves: the counters are tied to fixed registers in
+            # both, and the compiler joins the two paths through 16 register copies in front of every block.
+            full = gen(256, 4, dma_planes=list(dplanes), bb=pl)
+            short = gen(256, 4, dma_planes=list(short_dma_planes(pl)), bb=pl - 1)
+            f.write("// %d planes, the full block or -- flag set -- the short one: plane %d is zero there and is neither\n"
+                    "// read nor compared (the pieces of the next block are copied whole either way)\n" % (pl, pl - 1))
+            write_macro(f, "PPK_BLOCK_DMA_SEL_ASM_Q32_P%d" % pl,
+                        ["s_bitcmp1_b32 %[sh], %[bk]", "s_cbranch_scc1 .Lppk_short_%="] + full +
+                        ["s_branch .Lppk_done_%=", ".Lppk_short_%=:"] + short + [".Lppk_done_%=:"])
     if "--experiments" not in sys.argv[1:]:
         return
     # measured-and-rejected shapes: generated on demand, not tracked (tools/ubench_pipe.hip needs them)
