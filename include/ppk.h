@@ -177,6 +177,22 @@ size_t ppk_db_size(const ppk_db *db);
 int ppk_db_rank_planes(const ppk_db *db);
 int ppk_db_rank_read(const ppk_db *db, uint64_t *out, size_t words);
 int ppk_db_rank_block_planes(const ppk_db *db, uint8_t *out, size_t cap);
+/* The folded pair.  A bin value that exactly one sample holds at its (k, bin) position can match nothing in a self job,
+ * yet takes a code of its own in the copy above.  Where that lets a self job compare fewer planes over all blocks, the
+ * database keeps two coded copies instead of the one: a value with at least two holders gets the code 2 + its rank among
+ * such values of its position in both, and every single-holder value gets 0 in the ref-side copy and 1 in the query-side
+ * one.  A position then spans E = S + 2 codes (S: its values with at least two holders); the planes and the short blocks
+ * follow from E as they follow from the distinct values above.  A triangular self job compares two different samples, one
+ * from each copy, so every count and every bit is that of the raw planes; a job of a handle against itself as the query
+ * does not read the pair.  Costs 2 x planes/14 of the database's memory.  Option "rank_fold" (PPK_RANK_FOLD, default 1),
+ * read at creation: 0 never builds the pair, 2 builds it whenever the codes fit 12 planes (tests); 0 at launch leaves a
+ * built pair unread (raw planes).  ppk_db_rank_planes and ppk_db_rank_block_planes report what the distinct values give
+ * either way, and ppk_db_rank_read builds the injective copy on demand where only the pair was built.
+ * ppk_db_fold_planes: the planes of the pair, 0 without one.  ppk_db_fold_block_planes, ppk_db_fold_read (which: 0 the
+ * ref side, 1 the query side): as their rank_ namesakes, an error without a pair. */
+int ppk_db_fold_planes(const ppk_db *db);
+int ppk_db_fold_block_planes(const ppk_db *db, uint8_t *out, size_t cap);
+int ppk_db_fold_read(const ppk_db *db, int which, uint64_t *out, size_t words);
 
 /* Number of distance rows for rows q in [q_begin, q_end) (self: n_qry == 0). */
 size_t ppk_rows_in_band(size_t n_ref, size_t n_qry, size_t q_begin, size_t q_end);

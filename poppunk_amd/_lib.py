@@ -126,6 +126,9 @@ SIGNATURES = {
     "ppk_db_rank_planes": (C.c_int, [_vp]),
     "ppk_db_rank_read": (C.c_int, [_vp, _vp, _sz]),
     "ppk_db_rank_block_planes": (C.c_int, [_vp, _vp, _sz]),
+    "ppk_db_fold_planes": (C.c_int, [_vp]),
+    "ppk_db_fold_block_planes": (C.c_int, [_vp, _vp, _sz]),
+    "ppk_db_fold_read": (C.c_int, [_vp, C.c_int, _vp, _sz]),
     "ppk_rows_in_band": (_sz, [_sz, _sz, _sz, _sz]),
     "ppk_band_split": (C.c_int, [_sz, _sz, C.c_int, _szp]),
     "ppk_dist_dev": (C.c_int, [_vp, _vp, _i32p, _f32p, _sz, C.c_int, _sz, _sz, _vp, _vp, _vp]),

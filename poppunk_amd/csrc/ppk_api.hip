@@ -58,6 +58,7 @@ const OptionEntry kOptions[] = {
 #endif
     {"rank_planes", "PPK_RANK_PLANES", &PpkConfig::rank_planes},
     {"rank_short", "PPK_RANK_SHORT", &PpkConfig::rank_short},
+    {"rank_fold", "PPK_RANK_FOLD", &PpkConfig::rank_fold},
     {"lds_table", "PPK_LDS_TABLE", &PpkConfig::lds_table},
     {"ksplit", "PPK_KSPLIT", &PpkConfig::ksplit},
     {"ksplit_slices", "PPK_KSPLIT_SLICES", &PpkConfig::ksplit_slices},
@@ -392,6 +393,9 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   db->d_skR = nullptr;
   db->rank_planes = 0;
   for (unsigned &w : db->rank_short) w = 0;
+  db->d_foldR = db->d_foldQ = nullptr;
+  db->fold_planes = 0;
+  for (unsigned &w : db->fold_short) w = 0;
   const size_t cols = nk * db->words;
   const size_t in_bytes = n * cols * sizeof(uint64_t);
   const size_t out_bytes = db->npad * cols * sizeof(uint64_t);
@@ -399,6 +403,8 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   auto bail = [&](int code, const std::string &msg) {
     if (db->d_skT) (void)hipFree(db->d_skT);
     if (db->d_skR) (void)hipFree(db->d_skR);
+    if (db->d_foldR) (void)hipFree(db->d_foldR);
+    if (db->d_foldQ) (void)hipFree(db->d_foldQ);
     if (db->d_clu) (void)hipFree(db->d_clu);
     delete db;
     return ppk_fail(code, msg);
@@ -434,38 +440,70 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   // synchronisation of `s` per database.  The same pass leaves the maximum of each (k, 64-bin block), read back with
   // it: a block that holds at most 2^(planes - 1) values per position has a zero top plane, and the tile kernel leaves
   // that plane out there (ppk_db::rank_short).
+  // The pass counts a second figure per position: S, the values at least two samples hold there.  A value with a single
+  // holder matches nothing in a self job, so the folded pair (ppk_db::d_foldR / d_foldQ) gives all of them two reserved
+  // codes and spans E = S + 2 codes where the injective copy spans D.  The pair is built instead of the injective copy
+  // where it compares fewer planes over the blocks (option "rank_fold"); rank_planes and rank_short stay functions of D.
   if (rc == PPK_OK && ppk_config().rank_planes.load() != 0 && ppk_self_job_takes_tiles(db)) {
     unsigned *d_max = nullptr;
-    unsigned distinct = 0;
     const size_t n_blocks = nk * sketchsize64;
-    std::vector<unsigned> counts(1 + n_blocks, 0u);
+    std::vector<unsigned> counts(2 * (1 + n_blocks), 0u);
     e = hipMalloc(reinterpret_cast<void **>(&d_max), counts.size() * sizeof(unsigned));
     if (e == hipSuccess) {
       rc = ppk_launch_rank_count(db->d_skT, n, db->npad, nk, sketchsize64, d_max, s);
       if (rc == PPK_OK) {
         e = hipMemcpyAsync(counts.data(), d_max, counts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        distinct = counts[0];
         if (e != hipSuccess) rc = ppk_fail(PPK_ERR_HIP, std::string("rank codes: ") + hipGetErrorString(e));
       }
       (void)hipFree(d_max);
-      const int planes = distinct <= 256 ? 8 : distinct <= 1024 ? 10 : distinct <= 4096 ? 12 : 0;
-      if (rc == PPK_OK && planes) {
+      auto planes_for = [](unsigned codes) { return codes <= 256 ? 8 : codes <= 1024 ? 10 : codes <= 4096 ? 12 : 0; };
+      const unsigned *count_d = counts.data(), *count_e = counts.data() + 1 + n_blocks;
+      const int planes = planes_for(count_d[0]), planes_fold = planes_for(count_e[0]);
+      // the short flags of either coding, and the planes a self job compares over all blocks with it (no coding: 14)
+      const bool flags_fit = nk < PPK_RANK_SHORT_WORDS && sketchsize64 <= 32;
+      auto block_flags = [&](const unsigned *cnt, int pl, unsigned *flags) {
+        size_t sum = 0;
+        for (size_t k = 0; k < nk; ++k)
+          for (size_t b = 0; b < sketchsize64; ++b) {
+            const bool is_short = pl && flags_fit && cnt[1 + k * sketchsize64 + b] <= (1u << (pl - 1));
+            if (is_short) flags[k] |= 1u << b;
+            sum += pl ? (size_t)(pl - (is_short ? 1 : 0)) : (size_t)bbits;
+          }
+        return sum;
+      };
+      unsigned short_d[PPK_RANK_SHORT_WORDS] = {}, short_e[PPK_RANK_SHORT_WORDS] = {};
+      const size_t sum_d = block_flags(count_d, planes, short_d), sum_e = block_flags(count_e, planes_fold, short_e);
+      const long long fold_opt = ppk_config().rank_fold.load();
+      const size_t copy_words = db->npad * nk * sketchsize64;
+      if (rc == PPK_OK && planes_fold && fold_opt != 0 && (fold_opt == 2 || sum_e < sum_d)) {
+        // (a device too full for the pair falls back to the injective copy, and from there to the raw planes)
+        e = hipMalloc(reinterpret_cast<void **>(&db->d_foldR), copy_words * (size_t)planes_fold * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_foldQ), copy_words * (size_t)planes_fold * sizeof(uint64_t));
+        if (e != hipSuccess) {
+          (void)hipGetLastError();
+          if (db->d_foldR) (void)hipFree(db->d_foldR);
+          db->d_foldR = db->d_foldQ = nullptr;
+        } else {
+          rc = ppk_launch_rank_codes(db->d_skT, db->d_foldR, db->d_foldQ, n, db->npad, nk, sketchsize64, planes_fold, s);
+          db->fold_planes = planes_fold;
+          for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) db->fold_short[k] = short_e[k];
+          db->rank_planes = planes;
+        }
+      }
+      if (rc == PPK_OK && planes && !db->fold_planes) {
         // (a device too full for the copy keeps the raw planes alone: the copy only buys speed)
-        e = hipMalloc(reinterpret_cast<void **>(&db->d_skR), db->npad * nk * sketchsize64 * (size_t)planes * sizeof(uint64_t));
+        e = hipMalloc(reinterpret_cast<void **>(&db->d_skR), copy_words * (size_t)planes * sizeof(uint64_t));
         if (e != hipSuccess) {
           (void)hipGetLastError();
           db->d_skR = nullptr;
         } else {
-          rc = ppk_launch_rank_codes(db->d_skT, db->d_skR, n, db->npad, nk, sketchsize64, planes, s);
+          rc = ppk_launch_rank_codes(db->d_skT, db->d_skR, nullptr, n, db->npad, nk, sketchsize64, planes, s);
           db->rank_planes = planes;
-          if (nk < PPK_RANK_SHORT_WORDS && sketchsize64 <= 32) {
-            for (size_t k = 0; k < nk; ++k)
-              for (size_t b = 0; b < sketchsize64; ++b)
-                if (counts[1 + k * sketchsize64 + b] <= (1u << (planes - 1))) db->rank_short[k] |= 1u << b;
-          }
         }
       }
+      if (db->rank_planes)
+        for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) db->rank_short[k] = short_d[k];
     } else {
       (void)hipGetLastError();
     }
@@ -485,12 +523,30 @@ extern "C" void ppk_db_destroy(ppk_db *db) {
   DeviceGuard guard(db->device);
   if (db->d_skT) (void)hipFree(db->d_skT);
   if (db->d_skR) (void)hipFree(db->d_skR);
+  if (db->d_foldR) (void)hipFree(db->d_foldR);
+  if (db->d_foldQ) (void)hipFree(db->d_foldQ);
   if (db->d_clu) (void)hipFree(db->d_clu);
   delete db;
 }
 
 extern "C" size_t ppk_db_size(const ppk_db *db) { return db ? db->n : 0; }
 extern "C" int ppk_db_rank_planes(const ppk_db *db) { return db ? db->rank_planes : 0; }
+// The injective copy of a database that was built with the folded pair alone: made when somebody asks for it
+// (ppk_db_rank_read; a rectangular job of the handle against itself reads the raw planes until then).
+static int ppk_db_build_injective(ppk_db *db) {
+  if (db->d_skR) return PPK_OK;
+  const size_t bytes = db->npad * db->nk * db->s64 * (size_t)db->rank_planes * sizeof(uint64_t);
+  PPK_HIP(hipMalloc(reinterpret_cast<void **>(&db->d_skR), bytes));
+  int rc = ppk_launch_rank_codes(db->d_skT, db->d_skR, nullptr, db->n, db->npad, db->nk, db->s64, db->rank_planes, nullptr);
+  hipError_t e = rc == PPK_OK ? hipDeviceSynchronize() : hipSuccess;
+  if (rc == PPK_OK && e != hipSuccess) rc = ppk_fail(PPK_ERR_HIP, std::string("rank codes: ") + hipGetErrorString(e));
+  if (rc != PPK_OK) {
+    (void)hipFree(db->d_skR);
+    db->d_skR = nullptr;
+  }
+  return rc;
+}
+
 extern "C" int ppk_db_rank_read(const ppk_db *db, uint64_t *out, size_t words) {
   if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_rank_read: NULL argument");
   if (!db->rank_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_rank_read: the database has no rank-coded copy");
@@ -499,7 +555,34 @@ extern "C" int ppk_db_rank_read(const ppk_db *db, uint64_t *out, size_t words) {
   DeviceGuard guard(db->device);
   if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(db->device));
   PPK_HIP(hipDeviceSynchronize());
+  if (int rc = ppk_db_build_injective(const_cast<ppk_db *>(db))) return rc;
   PPK_HIP(hipMemcpy(out, db->d_skR, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return PPK_OK;
+}
+
+extern "C" int ppk_db_fold_planes(const ppk_db *db) { return db ? db->fold_planes : 0; }
+extern "C" int ppk_db_fold_read(const ppk_db *db, int which, uint64_t *out, size_t words) {
+  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold_read: NULL argument");
+  if (which != 0 && which != 1) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold_read: `which` is 0 (ref side) or 1 (query side)");
+  if (!db->fold_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold_read: the database has no folded pair");
+  if (words != db->nk * db->s64 * (size_t)db->fold_planes * db->npad)
+    return ppk_fail(PPK_ERR_ARG, "ppk_db_fold_read: `words` is not nk * sketchsize64 * planes * padded samples");
+  DeviceGuard guard(db->device);
+  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(db->device));
+  PPK_HIP(hipDeviceSynchronize());
+  PPK_HIP(hipMemcpy(out, which ? db->d_foldQ : db->d_foldR, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return PPK_OK;
+}
+
+extern "C" int ppk_db_fold_block_planes(const ppk_db *db, uint8_t *out, size_t cap) {
+  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold_block_planes: NULL argument");
+  if (!db->fold_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold_block_planes: the database has no folded pair");
+  if (cap < db->nk * db->s64) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold_block_planes: `cap` is below nk * sketchsize64");
+  for (size_t k = 0; k < db->nk; ++k)
+    for (size_t b = 0; b < db->s64; ++b) {
+      const bool is_short = k < PPK_RANK_SHORT_WORDS && b < 32 && ((db->fold_short[k] >> b) & 1u);
+      out[k * db->s64 + b] = (uint8_t)(db->fold_planes - (is_short ? 1 : 0));
+    }
   return PPK_OK;
 }
 

@@ -243,25 +243,38 @@ transpose_kernel(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, si
   }
 }
 
-// Rank codes of a bbits = 14 database (ppk_db::d_skR).  One workgroup per (k, 64-bin block, byte g of the block's
-// words) = 8 bin positions.  Per position a 16 384-bit presence bitmap of the values samples [0, n) hold there goes into
-// LDS; its prefix popcount turns a value into its rank among the position's distinct values.
-//   WRITE = false: only the largest number of distinct values of any position, into max_distinct[0], and of any
-//                  position of each (k, 64-bin block), into max_distinct[1 + k * s64 + block].
+// Rank codes of a bbits = 14 database (ppk_db::d_skR, d_foldR / d_foldQ).  One workgroup per (k, 64-bin block, byte g of
+// the block's words) = 8 bin positions.  Per position a 16 384-bit presence bitmap of the values samples [0, n) hold
+// there goes into LDS, and next to it (count pass, folded codes) the bitmap of the values seen at least twice: the
+// presence atomicOr returns the old word, and a bit that was already set is a second holder.  A prefix popcount turns a
+// value into its rank among the position's distinct (or shared) values.
+//   WRITE = false: D, the largest number of distinct values of any position, into max_distinct[0], and of any position
+//                  of each (k, 64-bin block) into max_distinct[1 + k * s64 + block].  Behind them, at
+//                  max_distinct[1 + nk * s64 ...], the same two for E = S + 2, the codes a folded position spans (S: its
+//                  shared values, those with at least two holders).
 //   WRITE = true:  byte g of the PL code planes of every sample, out = [k][block * PL + plane][npad] (padding samples
-//                  get code 0).  The caller has checked that every rank is below 2^PL.
+//                  get code 0).  The caller has checked that every code is below 2^PL.
+//     FOLD = false: code = rank among the position's distinct values (injective).
+//     FOLD = true:  two copies.  A shared value gets 2 + its rank among the position's shared values in both; a value
+//                   with a single holder gets 0 in `out` (the ref side) and 1 in `out_q` (the query side): it can match
+//                   nothing in a job that compares two different samples, and 0 != 1 != every shared code says so.
 constexpr int RANK_BB = 14;                      // the one bbits with a coded copy (the tile kernels' V2_BB)
 constexpr int RANK_BMW = (1 << RANK_BB) / 32;      // bitmap dwords per position
-template <bool WRITE>
+template <bool WRITE, bool FOLD = false>
 __global__ void __launch_bounds__(256)
-rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, unsigned *__restrict__ max_distinct,
-                 size_t n, size_t npad, int s64, int pl) {
+rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, uint8_t *__restrict__ out_q,
+                 unsigned *__restrict__ max_distinct, size_t n, size_t npad, int s64, int pl) {
+  constexpr bool TWICE = !WRITE || FOLD;
   __shared__ uint32_t bitmap[8][RANK_BMW];
-  __shared__ uint16_t before[8][RANK_BMW];      // distinct values below the dword's first one
+  __shared__ uint32_t twice[TWICE ? 8 : 1][RANK_BMW];      // values with at least two holders
+  __shared__ uint16_t before[WRITE ? 8 : 1][RANK_BMW];     // coded values (distinct; FOLD: shared) below the dword's first one
   const int g = blockIdx.x & 7;
   const size_t kb = blockIdx.x >> 3;            // k * s64 + block
   const uint64_t *src = skT + kb * RANK_BB * npad;
-  for (int i = threadIdx.x; i < 8 * RANK_BMW; i += 256) (&bitmap[0][0])[i] = 0;
+  for (int i = threadIdx.x; i < 8 * RANK_BMW; i += 256) {
+    (&bitmap[0][0])[i] = 0;
+    if (TWICE) (&twice[0][0])[i] = 0;
+  }
   __syncthreads();
   auto values = [&](size_t smp, uint32_t (&v)[8]) {
     uint32_t byte[RANK_BB];
@@ -278,49 +291,76 @@ rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, un
     uint32_t v[8];
     values(smp, v);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) atomicOr(&bitmap[j][v[j] >> 5], 1u << (v[j] & 31u));
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t bit = 1u << (v[j] & 31u);
+      const uint32_t old = atomicOr(&bitmap[j][v[j] >> 5], bit);
+      if (TWICE && (old & bit)) atomicOr(&twice[j][v[j] >> 5], bit);
+    }
   }
   __syncthreads();
   // 32 threads per position, 16 consecutive dwords each: an exclusive prefix sum of their popcounts
   {
     const int j = threadIdx.x >> 5, t = threadIdx.x & 31;
-    uint32_t sum = 0;
-    for (int w = 0; w < RANK_BMW / 32; ++w) sum += __popc(bitmap[j][t * (RANK_BMW / 32) + w]);
-    uint32_t incl = sum;
+    auto prefix = [&](const uint32_t *bm, uint32_t &sum) {
+      sum = 0;
+      for (int w = 0; w < RANK_BMW / 32; ++w) sum += __popc(bm[t * (RANK_BMW / 32) + w]);
+      uint32_t incl = sum;
 #pragma unroll
-    for (int d = 1; d < 32; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, 32);
-      if (t >= d) incl += up;
-    }
-    if (!WRITE) {
+      for (int d = 1; d < 32; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 32);
+        if (t >= d) incl += up;
+      }
+      return incl;
+    };
+    if constexpr (!WRITE) {
+      uint32_t sum;
+      const uint32_t d_incl = prefix(bitmap[j], sum), s_incl = prefix(twice[j], sum);
       if (t == 31) {
-        atomicMax(max_distinct, incl);
-        atomicMax(max_distinct + 1 + kb, incl);
+        unsigned *max_fold = max_distinct + 1 + gridDim.x / 8;
+        atomicMax(max_distinct, d_incl);
+        atomicMax(max_distinct + 1 + kb, d_incl);
+        atomicMax(max_fold, s_incl + 2u);
+        atomicMax(max_fold + 1 + kb, s_incl + 2u);
       }
       return;
-    }
-    uint32_t run = incl - sum;
-    for (int w = 0; w < RANK_BMW / 32; ++w) {
-      before[j][t * (RANK_BMW / 32) + w] = (uint16_t)run;
-      run += __popc(bitmap[j][t * (RANK_BMW / 32) + w]);
+    } else {
+      const uint32_t *bm = FOLD ? twice[j] : bitmap[j];
+      uint32_t sum;
+      const uint32_t incl = prefix(bm, sum);
+      uint32_t run = incl - sum;
+      for (int w = 0; w < RANK_BMW / 32; ++w) {
+        before[j][t * (RANK_BMW / 32) + w] = (uint16_t)run;
+        run += __popc(bm[t * (RANK_BMW / 32) + w]);
+      }
     }
   }
   __syncthreads();
   uint8_t *dst = out + kb * (size_t)pl * npad * 8 + g;
+  uint8_t *dst_q = FOLD ? out_q + kb * (size_t)pl * npad * 8 + g : nullptr;
   for (size_t smp = threadIdx.x; smp < npad; smp += 256) {
     uint32_t code[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t single = 0;      // FOLD: bit j set where the sample's value at position j has no other holder
     if (smp < n) {
       uint32_t v[8];
       values(smp, v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
-        code[j] = before[j][v[j] >> 5] + __popc(bitmap[j][v[j] >> 5] & ((1u << (v[j] & 31u)) - 1u));
+      for (int j = 0; j < 8; ++j) {
+        const uint32_t w = v[j] >> 5, bit = 1u << (v[j] & 31u);
+        if constexpr (FOLD) {
+          if (twice[j][w] & bit) code[j] = 2u + before[j][w] + __popc(twice[j][w] & (bit - 1u));
+          else single |= 1u << j;
+        } else {
+          code[j] = before[j][w] + __popc(bitmap[j][w] & (bit - 1u));
+        }
+      }
     }
     for (int b = 0; b < pl; ++b) {
       uint32_t byte = 0;
 #pragma unroll
       for (int j = 0; j < 8; ++j) byte |= ((code[j] >> b) & 1u) << j;
       dst[((size_t)b * npad + smp) * 8] = (uint8_t)byte;
+      // (a shared code is the same on both sides; a single holder's differs in bit 0 alone)
+      if constexpr (FOLD) dst_q[((size_t)b * npad + smp) * 8] = (uint8_t)(b == 0 ? byte | single : byte);
     }
   }
 }
@@ -1362,23 +1402,33 @@ int launch_v2(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const f
   if constexpr (NW == 8 && W == 2 && !WIDE && (MODE == MODE_DIST || ppk_is_mask(MODE))) {
     // A self job on a rank-coded database (ppk_db_create) compares the codes: 8, 10 or 12 planes per block instead of
     // 14, the same counts.  (ref x query jobs would need one code for two databases; the k-split units returned above.)
-    const int pl = (p.self || qry == ref) && !p.k_split && ppk_config().rank_planes.load() != 0 ? ref->rank_planes : 0;
+    // The folded pair (d_foldR / d_foldQ) serves the triangular job alone: every pair it compares is two different
+    // samples, one from each copy.  A rectangular job of a handle against itself has the pairs (r, r), where a value
+    // with a single holder must match itself: it reads the injective copy if there is one, else the raw planes.
+    const bool coded = (p.self || qry == ref) && !p.k_split && ppk_config().rank_planes.load() != 0;
+    const bool fold = coded && p.self && ref->fold_planes != 0 && ppk_config().rank_fold.load() != 0;
+    const int pl = fold ? ref->fold_planes : coded && ref->d_skR ? ref->rank_planes : 0;
     if (pl) {
-      const uint64_t *sk = ref->d_skR;
+      const uint64_t *sk_r = fold ? ref->d_foldR : ref->d_skR, *sk_q = fold ? ref->d_foldQ : ref->d_skR;
+      const unsigned *flags = fold ? ref->fold_short : ref->rank_short;
       const uint16_t *clu = use_clu ? ref->d_clu : nullptr;
       const dim3 grid((unsigned)n_blocks), block(NW * 64);
-      ppk_set_kernel_name(pl == 12 ? "dist_kernel_v2<256x32,lds-dma,rank 12>" : pl == 10 ? "dist_kernel_v2<256x32,lds-dma,rank 10>"
-                                                                                         : "dist_kernel_v2<256x32,lds-dma,rank 8>");
+      if (fold)
+        ppk_set_kernel_name(pl == 12 ? "dist_kernel_v2<256x32,lds-dma,rank 12,fold>" : pl == 10 ? "dist_kernel_v2<256x32,lds-dma,rank 10,fold>"
+                                                                                                : "dist_kernel_v2<256x32,lds-dma,rank 8,fold>");
+      else
+        ppk_set_kernel_name(pl == 12 ? "dist_kernel_v2<256x32,lds-dma,rank 12>" : pl == 10 ? "dist_kernel_v2<256x32,lds-dma,rank 10>"
+                                                                                           : "dist_kernel_v2<256x32,lds-dma,rank 8>");
       // the blocks that compare one plane fewer (option "rank_short", read here: one database runs either way)
       const bool use_short = ppk_config().rank_short.load() != 0;
-      for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.rank_short[k] = use_short ? ref->rank_short[k] : 0u;
+      for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.rank_short[k] = use_short ? flags[k] : 0u;
       ppk_prof_begin(s);
       if (pl == 12)
-        hipLaunchKernelGGL((dist_kernel_v2_rank<12, MODE>), grid, block, 0, s, sk, sk, d_lut, clu, clu, d_rtab, d_out, d_n_failed, d_mask, p);
+        hipLaunchKernelGGL((dist_kernel_v2_rank<12, MODE>), grid, block, 0, s, sk_r, sk_q, d_lut, clu, clu, d_rtab, d_out, d_n_failed, d_mask, p);
       else if (pl == 10)
-        hipLaunchKernelGGL((dist_kernel_v2_rank<10, MODE>), grid, block, 0, s, sk, sk, d_lut, clu, clu, d_rtab, d_out, d_n_failed, d_mask, p);
+        hipLaunchKernelGGL((dist_kernel_v2_rank<10, MODE>), grid, block, 0, s, sk_r, sk_q, d_lut, clu, clu, d_rtab, d_out, d_n_failed, d_mask, p);
       else
-        hipLaunchKernelGGL((dist_kernel_v2_rank<8, MODE>), grid, block, 0, s, sk, sk, d_lut, clu, clu, d_rtab, d_out, d_n_failed, d_mask, p);
+        hipLaunchKernelGGL((dist_kernel_v2_rank<8, MODE>), grid, block, 0, s, sk_r, sk_q, d_lut, clu, clu, d_rtab, d_out, d_n_failed, d_mask, p);
       ppk_prof_end(s);
       PPK_HIP(hipGetLastError());
       return PPK_OK;
@@ -1464,19 +1514,25 @@ int ppk_launch_transpose(const uint64_t *d_in, uint64_t *d_out, size_t n, size_t
   return PPK_OK;
 }
 
-// The rank codes of a transposed bbits = 14 database (rank_code_kernel): the count pass, then -- with `d_out` -- the
-// code planes.  Both only enqueue.
+// The rank codes of a transposed bbits = 14 database (rank_code_kernel): the count pass (d_max: 2 * (1 + nk * s64)
+// words, the D maxima and behind them the E maxima), then -- with `d_out` -- the code planes: injective, or with
+// `d_out_q` the folded pair (d_out the ref side).  Both only enqueue.
 int ppk_launch_rank_count(const uint64_t *d_skT, size_t n, size_t npad, size_t nk, size_t s64, unsigned *d_max, hipStream_t s) {
-  PPK_HIP(hipMemsetAsync(d_max, 0, (1 + nk * s64) * sizeof(unsigned), s));
-  hipLaunchKernelGGL(rank_code_kernel<false>, dim3((unsigned)(nk * s64 * 8)), dim3(256), 0, s, d_skT, nullptr, d_max, n,
-                     npad, (int)s64, 0);
+  PPK_HIP(hipMemsetAsync(d_max, 0, 2 * (1 + nk * s64) * sizeof(unsigned), s));
+  hipLaunchKernelGGL((rank_code_kernel<false>), dim3((unsigned)(nk * s64 * 8)), dim3(256), 0, s, d_skT, nullptr, nullptr, d_max,
+                     n, npad, (int)s64, 0);
   PPK_HIP(hipGetLastError());
   return PPK_OK;
 }
-int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, size_t n, size_t npad, size_t nk, size_t s64, int planes,
-                          hipStream_t s) {
-  hipLaunchKernelGGL(rank_code_kernel<true>, dim3((unsigned)(nk * s64 * 8)), dim3(256), 0, s, d_skT,
-                     reinterpret_cast<uint8_t *>(d_out), nullptr, n, npad, (int)s64, planes);
+int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, uint64_t *d_out_q, size_t n, size_t npad, size_t nk,
+                          size_t s64, int planes, hipStream_t s) {
+  const dim3 grid((unsigned)(nk * s64 * 8)), block(256);
+  if (d_out_q)
+    hipLaunchKernelGGL((rank_code_kernel<true, true>), grid, block, 0, s, d_skT, reinterpret_cast<uint8_t *>(d_out),
+                       reinterpret_cast<uint8_t *>(d_out_q), nullptr, n, npad, (int)s64, planes);
+  else
+    hipLaunchKernelGGL((rank_code_kernel<true, false>), grid, block, 0, s, d_skT, reinterpret_cast<uint8_t *>(d_out), nullptr,
+                       nullptr, n, npad, (int)s64, planes);
   PPK_HIP(hipGetLastError());
   return PPK_OK;
 }

@@ -43,6 +43,15 @@ struct ppk_db {
   // in every sample and the tile kernel leaves it out (option "rank_short").  Flags are kept for
   // nk < PPK_RANK_SHORT_WORDS and s64 <= 32 (a word per k); other shapes have none.
   unsigned rank_short[PPK_RANK_SHORT_WORDS];
+  // The folded pair, built INSTEAD of d_skR where it compares fewer planes (ppk_db_create, option "rank_fold"): two
+  // coded copies in fold_planes planes (0 = none), laid out like d_skR.  A value that at least two samples hold at its
+  // (k, bin) position has the same code >= 2 in both; a value with a single holder is 0 in d_foldR and 1 in d_foldQ.
+  // Only a triangular self job reads them, d_foldR on the ref side and d_foldQ on the query side: it compares two
+  // different samples, which a single-holder value can never match.  rank_planes and rank_short stay what the distinct
+  // values give; d_skR is then built on demand (ppk_db_rank_read).  fold_short: the short flags of the pair.
+  uint64_t *d_foldR, *d_foldQ;
+  int fold_planes;
+  unsigned fold_short[PPK_RANK_SHORT_WORDS];
 };
 
 // A database whose per-pair counts the tile kernels cannot hold: more k-mer lengths than the fit tables are laid
@@ -71,6 +80,7 @@ struct PpkConfig {
 #endif
   // -- product options
   std::atomic<long long> rank_planes{1};        // PPK_RANK_PLANES: a bbits = 14 database whose self job runs whole tiles keeps a rank-coded copy (ppk_db::d_skR) and self jobs compare it (0: no copy is built, none is read; same bits)
+  std::atomic<long long> rank_fold{1};          // PPK_RANK_FOLD: where folding every single-holder bin value into two reserved codes lets a self job compare fewer planes, the database keeps the folded pair (ppk_db::d_foldR / d_foldQ) instead of the injective copy (0: never; 2: whenever the folded codes fit 12 planes, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
   std::atomic<long long> rank_short{1};         // PPK_RANK_SHORT: a self job on a rank-coded database compares one plane fewer in the 64-bin blocks whose positions hold at most half the values the planes can code (0: every block compares all planes; same bits).  Read at launch.
   std::atomic<long long> lds_table{1};          // PPK_LDS_TABLE: interior tiles of the default sketch shape fit from the (E, F) table in LDS (0: the general statement everywhere; same bits)
   std::atomic<long long> ksplit{1200};           // PPK_KSPLIT: tile-count threshold (at 5 k) of the small-job path
@@ -174,7 +184,7 @@ PpkRouteChoice ppk_choose_route_impl(const PpkRouteShape &sh, const PpkGeometry 
 bool ppk_self_job_takes_tiles(const ppk_db *db);
 // (d_max: 1 + nk * s64 words -- the maximum over all positions, then the maximum of each (k, 64-bin block))
 int ppk_launch_rank_count(const uint64_t *d_skT, size_t n, size_t npad, size_t nk, size_t s64, unsigned *d_max, hipStream_t s);
-int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, size_t n, size_t npad, size_t nk, size_t s64, int planes,
+int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, uint64_t *d_out_q, size_t n, size_t npad, size_t nk, size_t s64, int planes,
                           hipStream_t s);
 
 // Profiling hooks (ppk_prof_*) -------------------------------------------------

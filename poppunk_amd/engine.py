@@ -141,17 +141,44 @@ class SketchDB:
                    "ppk_db_rank_block_planes")
         return out
 
-    def rank_codes(self):
-        """The rank-coded copy un-bitsliced (tests): uint16 [n, nk, 64 * sketchsize64] codes."""
-        planes, npad = self.rank_planes, (self.n + 255) // 256 * 256
-        raw = np.empty((self.nk, self.sketchsize64, planes, npad), dtype=np.uint64)
-        _lib.check(_lib.lib().ppk_db_rank_read(self._h, C.c_void_p(raw.ctypes.data), raw.size), "ppk_db_rank_read")
+    def _unslice_codes(self, raw, planes):
+        """coded planes [nk, sketchsize64, planes, npad] uint64 -> uint16 [n, nk, 64 * sketchsize64] codes"""
         bits = np.unpackbits(raw[..., :self.n].view(np.uint8).reshape(self.nk, self.sketchsize64, planes, self.n, 8),
                              axis=-1, bitorder="little")      # [k, blk, plane, sample, 64 bins]
         codes = np.zeros((self.nk, self.sketchsize64, self.n, 64), dtype=np.uint16)
         for b in range(planes):
             codes |= bits[:, :, b].astype(np.uint16) << b
         return np.ascontiguousarray(codes.transpose(2, 0, 1, 3)).reshape(self.n, self.nk, 64 * self.sketchsize64)
+
+    def rank_codes(self):
+        """The rank-coded copy un-bitsliced (tests): uint16 [n, nk, 64 * sketchsize64] codes."""
+        planes, npad = self.rank_planes, (self.n + 255) // 256 * 256
+        raw = np.empty((self.nk, self.sketchsize64, planes, npad), dtype=np.uint64)
+        _lib.check(_lib.lib().ppk_db_rank_read(self._h, C.c_void_p(raw.ctypes.data), raw.size), "ppk_db_rank_read")
+        return self._unslice_codes(raw, planes)
+
+    @property
+    def fold_planes(self):
+        """Bit-planes of the database's folded pair of coded copies (8, 10 or 12), 0 without one (ppk_db_fold_planes)."""
+        return int(_lib.lib().ppk_db_fold_planes(self._h))
+
+    def fold_block_planes(self):
+        """Planes a self job compares per 64-bin block of the folded pair (ppk_db_fold_block_planes): uint8
+        [nk, sketchsize64], fold_planes or -- where no position of the block spans more than 2^(fold_planes - 1)
+        codes -- fold_planes - 1."""
+        out = np.empty((self.nk, self.sketchsize64), dtype=np.uint8)
+        _lib.check(_lib.lib().ppk_db_fold_block_planes(self._h, C.c_void_p(out.ctypes.data), out.size),
+                   "ppk_db_fold_block_planes")
+        return out
+
+    def fold_codes(self, which):
+        """One copy of the folded pair un-bitsliced (tests), 0 the ref side, 1 the query side: uint16
+        [n, nk, 64 * sketchsize64] codes."""
+        planes, npad = self.fold_planes, (self.n + 255) // 256 * 256
+        raw = np.empty((self.nk, self.sketchsize64, max(planes, 1), npad), dtype=np.uint64)
+        _lib.check(_lib.lib().ppk_db_fold_read(self._h, int(which), C.c_void_p(raw.ctypes.data),
+                                               self.nk * self.sketchsize64 * planes * npad), "ppk_db_fold_read")
+        return self._unslice_codes(raw, planes)
 
 
 def _prep_tables(kmers, random_tbl, nk):
