@@ -18,7 +18,7 @@ import tempfile
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from poppunk_amd import distfile, engine, models, synth  # noqa: E402
+from poppunk_amd import distfile, engine, models, network, synth  # noqa: E402
 
 
 def main():
@@ -46,6 +46,9 @@ def main():
     edges = engine.bgmm_edges_dev(dist_t, loaded.model).cpu().numpy()
     assert len(edges) == counts[model.within_label]
     n_clusters, labels = distfile.clusters_from_edges(n, edges)
+    numbers = network.cluster_numbers((np.asarray(edges, dtype=np.int64).reshape(-1, 2), n))
+    print("PopPUNK's cluster numbers (printClusters: by size, largest first): %d clusters, the largest %d genomes"
+          % (int(numbers.max()), int((numbers == 1).sum())))
     print("%s -> %d within-strain pairs -> %d clusters (%d synthetic strains)"
           % (path, len(edges), n_clusters, len(set(member.tolist()))))
 

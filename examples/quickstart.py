@@ -19,7 +19,7 @@ import tempfile
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from poppunk_amd import distfile, engine, models, sketchdb, sketchlib, synth  # noqa: E402
+from poppunk_amd import distfile, engine, models, network, sketchdb, sketchlib, synth  # noqa: E402
 
 
 def main():
@@ -52,6 +52,9 @@ def main():
     y = boundary.assign(X)                                  # -1 within, 0 on the line, +1 outside
     edges = np.asarray(boundary.edges(X), dtype=np.int64).reshape(-1, 2)
     n_clusters, labels = distfile.clusters_from_edges(n, edges)
+    numbers = network.cluster_numbers((np.asarray(edges, dtype=np.int64).reshape(-1, 2), n))
+    print("PopPUNK's cluster numbers (printClusters: by size, largest first): %d clusters, the largest %d genomes"
+          % (int(numbers.max()), int((numbers == 1).sum())))
     print("boundary (%.4f, %.4f): %d within-strain pairs -> %d clusters (%d synthetic lineages)"
           % (x_max, y_max, len(edges), n_clusters, len(set(member.tolist()))))
     assert (y == -1).sum() == len(edges)

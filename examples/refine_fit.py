@@ -19,7 +19,7 @@ import tempfile
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from poppunk_amd import distfile, engine, models, refine, synth  # noqa: E402
+from poppunk_amd import distfile, engine, models, network, refine, synth  # noqa: E402
 
 
 def main():
@@ -52,6 +52,9 @@ def main():
     edges = engine.edge_threshold_dev(scaled, 2, loaded.optimal_x, loaded.optimal_y, inclusive=False).cpu().numpy()
     assert len(edges) == int((y == -1).sum().item())
     n_clusters, labels = distfile.clusters_from_edges(n, edges)
+    numbers = network.cluster_numbers((np.asarray(edges, dtype=np.int64).reshape(-1, 2), n))
+    print("PopPUNK's cluster numbers (printClusters: by size, largest first): %d clusters, the largest %d genomes"
+          % (int(numbers.max()), int((numbers == 1).sum())))
     print("%s -> %d within-strain pairs -> %d clusters (%d synthetic strains)"
           % (path, len(edges), n_clusters, len(set(member.tolist()))))
 

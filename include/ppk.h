@@ -713,6 +713,48 @@ int ppk_network_summary(const long long *i, const long long *j, const long long 
                         double *bt, long long *scored, double *values);
 
 /* ------------------------------------------------------------------------
+ * Cluster numbers: ppk_network_sweep_dev's edge stream, validation, limits and error messages (the
+ * entry point's own name in front), and for every G_t:
+ *  - d_clusters int32 [n_off][n_vertices]: d_clusters[t][v] = printClusters' number, 1-based, of vertex v in G_t.
+ *    Components are taken in the order of their smallest vertex and ranked by len - rankdata(sizes, 'ordinal')
+ *    (PopPUNK/network.py:1538-1545, graph-tool branch): by size descending, and among equal sizes by component index
+ *    DESCENDING -- among singletons the highest vertex id gets the smallest number.  That graph-tool's
+ *    label_components numbers components by their lowest vertex is UNVERIFIED (graph-tool is not installed here).
+ *  - d_n_clusters int32 [n_off]: the number of clusters of G_t.
+ * An offset without edges of its own repeats the row before it; no edges at all: every row is n_vertices - v.
+ * n_off == 1 (d_off NULL) is the one-graph form.  Integer arithmetic only: the same input, in any edge order, gives the
+ * same bits on every call.  Synchronises the stream once (the per-offset edge counts size the batches).
+ * (Replaces the label_components / rankdata block of printClusters, network.py:1538-1545, for one graph, and for every
+ * graph growNetwork(write_clusters=...) prints, PopPUNK/refine.py:458-470, under multi_refine, refine.py:247-330.) */
+int ppk_cluster_sweep_dev(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off,
+                          size_t n_edges, size_t n_vertices, size_t n_off, int32_t *d_clusters, int32_t *d_n_clusters,
+                          void *stream);
+/* Host arrays: i, j, off int64 [n_edges] (off nullable) -> clusters int32 [n_off][n_vertices], n_clusters int32
+ * [n_off], on device_id; blocking.  (The same replacement, for callers holding numpy arrays.) */
+int ppk_cluster_sweep(const long long *i, const long long *j, const long long *off, size_t n_edges, size_t n_vertices,
+                      size_t n_off, int device_id, int32_t *clusters, int32_t *n_clusters);
+
+/* Pair sums of a nested family of clusterings, one pass over a resident self/condensed float32
+ * [n_rows][2] matrix, n_rows = n(n-1)/2.  d_levels int32 [n_levels][n]: cluster numbers in [1, n]; NESTED (the caller's
+ * precondition): two vertices together at level t are together at every later level -- rows of ppk_cluster_sweep_dev's
+ * d_clusters are.  For every row (i, j): t* = the first level with d_levels[t][i] == d_levels[t][j] (none: the row adds
+ * nothing), c = d_levels[t*][i]; d_sum[t*][c] += llrint((double)d_dist[row][col] * 2^shift), d_cnt[t*][c] += 1.
+ * d_sum, d_cnt int64 [n_levels][n + 1] (column 0 unused), zeroed by the call.  The total over the pairs of a cluster at
+ * level t is the sum of the buckets of its sub-clusters at levels <= t (poppunk_amd.iterate does that on the host).
+ * Integer accumulation: the same bits on every call.  With shift = min(40, 62 - ceil_log2(n_rows)) no sum passes 2^62
+ * and a cluster's mean differs from the float64 mean of the same float32 values by at most 2^-(shift + 1).
+ * PPK_ERR_ARG, ppk_last_error() naming the first offender: a value that is NaN, infinite or outside [0, 1]; a cluster
+ * number outside [1, n].  Also PPK_ERR_ARG: col not 0 or 1, n_rows not n(n-1)/2, shift outside [0, 40] or above
+ * 62 - ceil_log2(n_rows), n_levels 0 or > 1023.  Synchronises the stream once (the read-back of the first offender).
+ * (Replaces the per-cluster pp_sketchlib.queryDatabase + np.mean of scripts/poppunk_iterate.py:184-197.) */
+int ppk_cluster_pair_sums_dev(const float *d_dist, size_t n_rows, int col, const int32_t *d_levels, size_t n_levels,
+                              int shift, long long *d_sum, long long *d_cnt, void *stream);
+/* Host arrays: dist float32 [n_rows][2], levels int32 [n_levels][n] -> sum, cnt int64 [n_levels][n + 1], on device_id;
+ * blocking. */
+int ppk_cluster_pair_sums(const float *dist, size_t n_rows, int col, const int32_t *levels, size_t n_levels, int shift,
+                          int device_id, long long *sum, long long *cnt);
+
+/* ------------------------------------------------------------------------
  * Minimum spanning forests.  Edges d_i[k * stride], d_j[k * stride] (stride 1: separate arrays; 2:
  * an int64 [m][2] edge list, d_j = d_i + 1), weights d_w[k], over vertices 0 .. n_vertices-1; i > j, parallel edges and
  * both orientations of a pair allowed.  Edges are totally ordered by (w, min(i, j), max(i, j), k), -0.0 read as +0.0;

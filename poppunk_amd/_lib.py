@@ -88,6 +88,10 @@ SIGNATURES = {
     "ppk_network_sweep": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, C.c_longlong, _llp, _i32p]),
     "ppk_network_summary_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, C.c_longlong, _vp, _vp, _vp, _vp, _vp]),
     "ppk_network_summary": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, C.c_longlong, _llp, _f64p, _llp, _f64p]),
+    "ppk_cluster_sweep_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp, _vp]),
+    "ppk_cluster_sweep": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, _i32p, _i32p]),
+    "ppk_cluster_pair_sums_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _sz, C.c_int, _vp, _vp, _vp]),
+    "ppk_cluster_pair_sums": (C.c_int, [_f32p, _sz, C.c_int, _i32p, _sz, C.c_int, C.c_int, _llp, _llp]),
     "ppk_mst_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "ppk_mst": (C.c_int, [_llp, _llp, _f32p, _sz, _sz, C.c_int, _llp, _ullp, _i32p]),
     "ppk_edge_weights_dev": (C.c_int, [_vp, _sz, _vp, _vp, _sz, _sz, _sz, C.c_longlong, C.c_int, _vp, _vp]),

@@ -268,7 +268,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_BGMM_FIT = 18,                     // the BGMM fit's per-workgroup partial sums, its sums, counters and k-means labels
        SLOT_SPARSE = 19,                       // extend's and lowerRank's row starts, sort pairs, counts, offsets and temp storage
        SLOT_REFINE = 20,                       // the refine fit's bit matrix, union-find parents and counters (one boundary at a time)
-       SLOT_COUNT = 21 };
+       SLOT_CLUSTERS = 21,                     // the cluster pair sums' first-bad-row / first-bad-number words
+       SLOT_COUNT = 22 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

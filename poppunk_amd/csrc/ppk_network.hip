@@ -21,6 +21,8 @@
 //    then one small kernel prefix-sums the per-offset increments into the [n_off][4] result.
 //  - ppk_network_summary_dev : the same counts plus networkSummary's betweenness (network.py:1286-1307) for every
 //    G_t: the stages above, then the betweenness stage below.
+//  - ppk_cluster_sweep_dev : printClusters' cluster numbers (PopPUNK/network.py:1538-1545) of every vertex in every
+//    G_t, from the same validation, buckets and union launches (the section before the entry points).
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -89,7 +91,7 @@ __global__ void __launch_bounds__(kThreads) net_validate_kernel(const long long 
 // ---- csr: bucket by offset, both directions of every edge as (key, neighbour) ---------------------------------
 // Each workgroup takes a chunk of kThreads * kScatterItems edges, ranks them per offset in LDS, reserves its range of
 // every bucket with one atomic per non-empty bin, and writes.  Positions inside a bucket are in no particular order
-// (the union-find does not care).  key = row << 11 | (neighbour > row) << 10 | offset.
+// (the union-find does not care).  key = row << 11 | (neighbour > row) << 10 | offset; keys == nullptr: buckets only.
 __global__ void __launch_bounds__(kThreads) net_scatter_kernel(const long long *ei, const long long *ej, size_t stride,
                                                                const long long *eo, size_t m, int n_off,
                                                                unsigned *cursor, int *bu, int *bv,
@@ -123,6 +125,7 @@ __global__ void __launch_bounds__(kThreads) net_scatter_kernel(const long long *
         const unsigned pos = base[o] + rank[q];
         bu[pos] = i;
         bv[pos] = j;
+        if (!keys) continue;             // (the cluster sweep wants the buckets alone)
         keys[2 * k] = ((unsigned long long)i << 11) | ((unsigned long long)(j > i) << 10) | (unsigned)o;
         vals[2 * k] = j;
         keys[2 * k + 1] = ((unsigned long long)j << 11) | ((unsigned long long)(i > j) << 10) | (unsigned)o;
@@ -1022,6 +1025,141 @@ int net_sweep(const std::string &who, const long long *d_i, const long long *d_j
   return PPK_OK;
 }
 
+// ---- cluster numbers of every G_t ---------------------------------------------------------------
+// The validate stage and the buckets are the sweep's; after every union launch that changed the forest:
+//   clu_sizes    bt_sizes_kernel: every vertex's root, every root's size (integer atomics)
+//   clu_rank     one key per root, (n - size, n - 1 - root): ascending order = size descending, then root descending,
+//                which is len - rankdata(sizes, 'ordinal') over components taken in the order of their smallest
+//                vertex (a root IS the smallest vertex of its set); rocPRIM radix sort; position + 1 is the number
+//   clu_scatter  row t: every vertex reads its root's number
+// An offset without edges of its own copies the row before it; offset 0 is always computed (no edges: all singletons,
+// n - v).  n_clusters[t] = n - the links so far.
+__global__ void __launch_bounds__(kThreads) clu_root_keys_kernel(const int *root, const int *size, size_t n,
+                                                                 unsigned long long *keys) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x)
+    keys[v] = root[v] == (int)v ? ((unsigned long long)(n - size[v]) << 32 | (unsigned long long)(n - 1 - v)) : kNone;
+}
+__global__ void __launch_bounds__(kThreads) clu_numbers_kernel(const unsigned long long *sorted, size_t n, int *number) {
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
+    const unsigned long long key = sorted[p];
+    if (key != kNone) number[n - 1 - (size_t)(key & 0xffffffffu)] = (int)(p + 1);
+  }
+}
+__global__ void __launch_bounds__(kThreads) clu_scatter_kernel(const int *root, const int *number, size_t n,
+                                                               int32_t *row) {
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x)
+    row[v] = number[root[v]];
+}
+__global__ void clu_counts_kernel(const unsigned *links, long long n, int n_off, int32_t *n_clusters) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  long long l = 0;
+  for (int o = 0; o < n_off; ++o) {
+    l += links[o];
+    n_clusters[o] = (int32_t)(n - l);
+  }
+}
+
+int cluster_sweep(const std::string &who, const long long *d_i, const long long *d_j, size_t stride,
+                  const long long *d_off, size_t n_edges, size_t n_vertices, size_t n_off, int32_t *d_clusters,
+                  int32_t *d_n_clusters, void *stream) {
+  if (n_off == 0 || n_off > (size_t)kMaxOff) return ppk_fail(PPK_ERR_ARG, who + ": n_off must be 1 .. 1023");
+  if (!d_off && n_off != 1 && n_edges) return ppk_fail(PPK_ERR_ARG, who + ": no offset array needs n_off == 1");
+  if (n_vertices >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, who + ": n_vertices must be < 2^31");
+  if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, who + ": n_edges must be < 2^31");
+  if (stride != 1 && stride != 2) return ppk_fail(PPK_ERR_ARG, who + ": stride must be 1 or 2");
+  if (!d_n_clusters || (!d_clusters && n_vertices) || (n_edges && (!d_i || !d_j)))
+    return ppk_fail(PPK_ERR_ARG, who + ": NULL array");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int dev = 0;
+  PPK_HIP(hipGetDevice(&dev));
+  PpkCall call(dev, s);
+  const size_t m = n_edges, n = n_vertices, no = n_off;
+
+  unsigned bits = 1;
+  while (bits < 32 && ((size_t)1 << bits) < n) ++bits;
+  const unsigned end_bit = 32 + bits + 1;      // n - size < 2^bits: kNone sorts after every root's key
+  size_t sort_tmp = 0, scan_tmp = 0;
+  if (n) PPK_HIP(rocprim::radix_sort_keys(nullptr, sort_tmp, (unsigned long long *)nullptr, (unsigned long long *)nullptr, n, 0u, end_bit, s));
+  PPK_HIP(rocprim::exclusive_scan(nullptr, scan_tmp, (unsigned *)nullptr, (unsigned *)nullptr, 0u, no,
+                                  rocprim::plus<unsigned>(), s));
+  const size_t tmp = sort_tmp > scan_tmp ? sort_tmp : scan_tmp;
+  unsigned long long *bad, *ka, *kb;
+  unsigned *cnt, *cursor, *links;
+  int *parent, *root, *size, *number, *bu, *bv;
+  char *d_tmp;
+  size_t zero_begin = 0, zero_end = 0;
+  int rc = ppk_scratch_carve(dev, SLOT_NET, [&](Carve &c) {
+    c.take(bad, 1);
+    zero_begin = c.at;
+    c.take(cnt, 1024).take(cursor, 1024).take(links, 1024);
+    zero_end = c.at;
+    c.take(parent, n).take(root, n).take(size, n).take(number, n).take(bu, m).take(bv, m);
+    c.take(ka, n).take(kb, n).take(d_tmp, tmp + 16);
+  });
+  if (rc != PPK_OK) return rc;
+
+  // -- validate: the one synchronisation
+  ppk_prof_stage("validate", s);
+  PPK_HIP(hipMemsetAsync(cnt, 0, zero_end - zero_begin, s));
+  PPK_HIP(hipMemsetAsync(bad, 0xff, 8, s));
+  if (m)
+    hipLaunchKernelGGL(net_validate_kernel, dim3(grid_for(m, kThreads * 8, 2048)), dim3(kThreads), 0, s, d_i, d_j,
+                       stride, d_off, m, (long long)n, (int)no, cnt, bad);
+  PPK_HIP(hipGetLastError());
+  const unsigned long long *h = nullptr;
+  if ((rc = ppk_read_back(dev, s, {{bad, 8}, {cnt, no * 4}}, &h)) != PPK_OK) return rc;
+  if (h[0] != ~0ull) {
+    ppk_prof_stage(nullptr, s);
+    return bad_edge_message(who, d_i, d_j, stride, d_off, (size_t)h[0], n, no);
+  }
+  std::vector<unsigned> counts(no), starts(no);
+  memcpy(counts.data(), h + 1, no * 4);
+  for (size_t o = 0, acc = 0; o < no; ++o) {
+    starts[o] = (unsigned)acc;
+    acc += counts[o];
+  }
+
+  // -- buckets
+  ppk_prof_stage("csr", s);
+  if (m) {
+    size_t tb = tmp;
+    PPK_HIP(rocprim::exclusive_scan(d_tmp, tb, cnt, cursor, 0u, no, rocprim::plus<unsigned>(), s));
+    hipLaunchKernelGGL(net_scatter_kernel, dim3(grid_for(m, (size_t)kThreads * kScatterItems, 4096)), dim3(kThreads), 0,
+                       s, d_i, d_j, stride, d_off, m, (int)no, cursor, bu, bv, (unsigned long long *)nullptr,
+                       (int *)nullptr);
+    PPK_HIP(hipGetLastError());
+  }
+
+  // -- components and numbers, batch by batch
+  ppk_prof_stage("clusters", s);
+  if (n) {
+    const dim3 gn(grid_for(n, kThreads, 4096));
+    hipLaunchKernelGGL(net_parent_init_kernel, gn, dim3(kThreads), 0, s, parent, n);
+    for (size_t o = 0; o < no; ++o) {
+      int32_t *row = d_clusters + o * n;
+      if (!counts[o] && o) {
+        PPK_HIP(hipMemcpyAsync(row, row - n, n * 4, hipMemcpyDeviceToDevice, s));
+        continue;
+      }
+      if (counts[o])
+        hipLaunchKernelGGL(net_union_kernel, dim3(grid_for(counts[o], kThreads * 4, 2048)), dim3(kThreads), 0, s,
+                           bu + starts[o], bv + starts[o], counts[o], parent, links + o);
+      PPK_HIP(hipMemsetAsync(size, 0, n * 4, s));
+      hipLaunchKernelGGL(bt_sizes_kernel, gn, dim3(kThreads), 0, s, parent, n, root, size);
+      hipLaunchKernelGGL(clu_root_keys_kernel, gn, dim3(kThreads), 0, s, root, size, n, ka);
+      size_t tb = tmp;
+      PPK_HIP(rocprim::radix_sort_keys(d_tmp, tb, ka, kb, n, 0u, end_bit, s));
+      hipLaunchKernelGGL(clu_numbers_kernel, gn, dim3(kThreads), 0, s, kb, n, number);
+      hipLaunchKernelGGL(clu_scatter_kernel, gn, dim3(kThreads), 0, s, root, number, n, row);
+      PPK_HIP(hipGetLastError());
+    }
+  }
+  hipLaunchKernelGGL(clu_counts_kernel, dim3(1), dim3(64), 0, s, links, (long long)n, (int)no, d_n_clusters);
+  ppk_prof_stage(nullptr, s);
+  PPK_HIP(hipGetLastError());
+  return PPK_OK;
+}
+
 }  // namespace
 
 extern "C" int ppk_network_sweep_dev(const long long *d_i, const long long *d_j, size_t stride,
@@ -1096,6 +1234,40 @@ extern "C" int ppk_network_summary(const long long *i, const long long *j, const
     PPK_HIP(hipMemcpy(bt, d_bt, n_off * 16, hipMemcpyDeviceToHost));
     if (scored) PPK_HIP(hipMemcpy(scored, d_scored, n_off * 8, hipMemcpyDeviceToHost));
     if (values_at >= 0 && n_vertices) PPK_HIP(hipMemcpy(values, d_values, n_vertices * 8, hipMemcpyDeviceToHost));
+    return PPK_OK;
+  });
+}
+
+extern "C" int ppk_cluster_sweep_dev(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off,
+                                     size_t n_edges, size_t n_vertices, size_t n_off, int32_t *d_clusters,
+                                     int32_t *d_n_clusters, void *stream) {
+  return cluster_sweep("ppk_cluster_sweep", d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, d_clusters,
+                       d_n_clusters, stream);
+}
+
+extern "C" int ppk_cluster_sweep(const long long *i, const long long *j, const long long *off, size_t n_edges,
+                                 size_t n_vertices, size_t n_off, int device_id, int32_t *clusters,
+                                 int32_t *n_clusters) {
+  if (!n_clusters || (!clusters && n_vertices) || (n_edges && (!i || !j)))
+    return ppk_fail(PPK_ERR_ARG, "ppk_cluster_sweep: NULL array");
+  const int rc = net_check("ppk_cluster_sweep", n_edges, n_vertices, n_off);
+  if (rc != PPK_OK) return rc;
+  long long *d_i, *d_j, *d_o;
+  int32_t *d_clusters, *d_nc;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_i, n_edges).take(d_j, n_edges).take(d_o, n_edges).take(d_clusters, n_off * n_vertices).take(d_nc, n_off);
+    c.at += 256;     // (spare)
+  }, [&]() -> int {
+    if (n_edges) {
+      PPK_HIP(hipMemcpy(d_i, i, n_edges * 8, hipMemcpyHostToDevice));
+      PPK_HIP(hipMemcpy(d_j, j, n_edges * 8, hipMemcpyHostToDevice));
+      if (off) PPK_HIP(hipMemcpy(d_o, off, n_edges * 8, hipMemcpyHostToDevice));
+    }
+    const int rc = ppk_cluster_sweep_dev(d_i, d_j, 1, off ? d_o : nullptr, n_edges, n_vertices, n_off, d_clusters,
+                                         d_nc, nullptr);
+    if (rc != PPK_OK) return rc;
+    if (n_vertices) PPK_HIP(hipMemcpy(clusters, d_clusters, n_off * n_vertices * 4, hipMemcpyDeviceToHost));
+    PPK_HIP(hipMemcpy(n_clusters, d_nc, n_off * 4, hipMemcpyDeviceToHost));
     return PPK_OK;
   });
 }

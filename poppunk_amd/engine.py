@@ -756,6 +756,73 @@ def network_stats_dev(edges_t, n, labels=False):
     return stats[0], lab
 
 
+def cluster_sweep_dev(i_t, j_t, off_t, n, n_off):
+    """printClusters' cluster numbers of every vertex in every graph of a sweep (ppk_cluster_sweep_dev, DESIGN.md
+    3.15): the edge stream of network_sweep_dev.  Returns (clusters int32 [n_off, n] CUDA: 1-based, by size descending,
+    equal sizes by component index descending; n_clusters int32 [n_off] CUDA).  n_off == 1 with off_t None is the
+    one-graph form."""
+    torch = _torch()
+    m, stride = _edge_stream(i_t, j_t, off_t)
+    dev = i_t.device
+    n, n_off = int(n), int(n_off)
+    with torch.cuda.device(dev):
+        clusters = torch.empty((max(n_off, 1), max(n, 1)), dtype=torch.int32, device=dev)
+        counts = torch.empty(max(n_off, 1), dtype=torch.int32, device=dev)
+        if n != max(n, 1):                  # n == 0: a [n_off, 0] result over storage of its own
+            clusters = clusters[:, :0]
+        rc = _lib.lib().ppk_cluster_sweep_dev(
+            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride,
+            C.c_void_p(off_t.data_ptr()) if off_t is not None else None, m, n, n_off,
+            C.c_void_p(clusters.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_cluster_sweep_dev")
+    return clusters, counts
+
+
+def cluster_numbers_dev(edges_t, n):
+    """cluster_sweep_dev of one int64 [m, 2] CUDA edge list, read in place -> (numbers int32 [n] CUDA, the count)."""
+    torch = _torch()
+    if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
+            and edges_t.is_contiguous()):
+        raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
+    clusters, counts = cluster_sweep_dev(edges_t[:, 0], edges_t[:, 1], None, n, 1)
+    return clusters[0], int(counts[0].item())
+
+
+def pair_sum_shift(n_rows):
+    """The fixed-point shift of cluster_pair_sums: min(40, 62 - ceil_log2(n_rows)), so that no sum passes 2^62
+    (ceil_log2 as ppk_device.h states it)."""
+    r = 0
+    while r < 62 and (1 << r) < int(n_rows):
+        r += 1
+    return min(40, 62 - r)
+
+
+def cluster_pair_sums_dev(dist_t, levels_t, col=0, shift=None):
+    """One pass over a resident float32 [n(n-1)/2, 2] CUDA matrix (ppk_cluster_pair_sums_dev):
+    levels_t int32 [n_levels, n] CUDA, nested cluster numbers in [1, n].  Every row (i, j) adds
+    llrint(dist[row, col] * 2^shift) to bucket (t*, c): the first level at which i and j share a cluster, and that
+    cluster.  Returns (sum, cnt) int64 [n_levels, n + 1] CUDA and the shift.  Nesting is the caller's precondition
+    (iterate.check_nested)."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    n_rows = int(dist_t.shape[0])
+    n = _samples_of(n_rows)
+    if not (levels_t.is_cuda and levels_t.dtype == torch.int32 and levels_t.dim() == 2 and levels_t.is_contiguous()
+            and levels_t.shape[1] == n and levels_t.device == dist_t.device):
+        raise TypeError("levels must be a contiguous int32 [n_levels, %d] CUDA tensor on the matrix's device" % n)
+    if shift is None:
+        shift = pair_sum_shift(n_rows)
+    n_levels = int(levels_t.shape[0])
+    dev = dist_t.device
+    with torch.cuda.device(dev):
+        out = torch.empty((2, max(n_levels, 1), n + 1), dtype=torch.int64, device=dev)
+        rc = _lib.lib().ppk_cluster_pair_sums_dev(
+            C.c_void_p(dist_t.data_ptr()), n_rows, int(col), C.c_void_p(levels_t.data_ptr()), n_levels, int(shift),
+            C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_cluster_pair_sums_dev")
+    return out[0], out[1], int(shift)
+
+
 def network_summary_dev(i_t, j_t, off_t, n, n_off, values_at=None):
     """network_sweep_dev plus networkSummary's betweenness for every G_t (ppk_network_summary_dev).
     The same edge stream and checks.  Returns (stats int64 [n_off, 4], bit for bit network_sweep_dev's; bt float64

@@ -115,11 +115,13 @@ class RefineBoundary:
 
     def fit_dev(self, dist_t, sample_names, model, max_move, min_move, startFile=None, indiv_refine=None,
                 unconstrained=False, score_idx=0, no_local=False, betweenness_sample=100, sample_size=None,
-                use_gpu=False):
+                use_gpu=False, multi_boundary=0, outPrefix=None):
         """RefineFit.fit on a resident float32 [n(n-1)/2, 2] CUDA matrix: the 2-D refinement from the start points of
         `model` (a BGMMModel, a DBSCANModel, or `startFile`), then, for indiv_refine 'core' / 'accessory' / 'both',
         the slope-0 and slope-1 refinements, with the reference's fall-back when one of them fails.  Returns the
-        assignment (assign_dev).  multi_boundary is not mirrored (it needs printClusters)."""
+        assignment (assign_dev).  multi_boundary > 1: after the 2-D fit, refine.multi_refine writes the clusters at that
+        many boundaries between the axis and the optimum under `outPrefix` (models.py:905-918); what it returns is kept
+        in self.multi_boundary_clusters.  The fit itself is the same with or without it."""
         import sys
         import torch
         from . import refine
@@ -141,6 +143,15 @@ class RefineBoundary:
         self.fitted = True
         self.threshold = False
         self.indiv_fitted = False
+
+        if multi_boundary > 1:
+            if outPrefix is None:
+                raise ValueError("multi_boundary needs outPrefix")
+            sys.stderr.write("Creating multiple boundary fits\n")
+            self.multi_boundary_clusters = refine.multi_refine(
+                scaled, sample_names, self.mean0, self.mean1, self.scale, self.optimal_s, multi_boundary, outPrefix,
+                num_processes=self.threads, betweenness_sample=betweenness_sample, sample_size=sample_size,
+                use_gpu=use_gpu)
 
         self.core_boundary = self.optimal_x
         self.accessory_boundary = self.optimal_y
@@ -164,7 +175,8 @@ class RefineBoundary:
         return self.assign_dev(dist_t)
 
     def fit(self, X, sample_names, model, max_move, min_move, startFile=None, indiv_refine=None, unconstrained=False,
-            score_idx=0, no_local=False, betweenness_sample=100, sample_size=None, use_gpu=False, device_id=0):
+            score_idx=0, no_local=False, betweenness_sample=100, sample_size=None, use_gpu=False, device_id=0,
+            multi_boundary=0, outPrefix=None):
         """fit_dev on a host float32 [n(n-1)/2, 2] array, uploaded once: the same model to the bit.  Returns the
         assignment as a numpy array."""
         import torch
@@ -174,7 +186,7 @@ class RefineBoundary:
         y = self.fit_dev(torch.from_numpy(X).to("cuda:%d" % device_id), sample_names, model, max_move, min_move,
                          startFile=startFile, indiv_refine=indiv_refine, unconstrained=unconstrained,
                          score_idx=score_idx, no_local=no_local, betweenness_sample=betweenness_sample,
-                         sample_size=sample_size, use_gpu=use_gpu)
+                         sample_size=sample_size, use_gpu=use_gpu, multi_boundary=multi_boundary, outPrefix=outPrefix)
         return y.cpu().numpy()
 
     def save(self, prefix):

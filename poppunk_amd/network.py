@@ -16,6 +16,11 @@ the vertex count; a binding passes (G.get_edges(), G.num_vertices()).  A CUDA te
 `betweenness_sample` and `use_gpu` only steer the reference's cugraph branch: accepted and ignored.  `subsample`
 (random vertex subsampling) raises NotImplementedError before the device is touched.
 
+Cluster numbers: printClusters and printExternalClusters (PopPUNK/network.py:1478-1719).  The
+number of every vertex comes from ppk_cluster_sweep / ppk_cluster_sweep_dev (cluster_numbers); the naming rules, the
+CSV and the external-cluster table are host code on that number array (name_clusters, print_cluster_numbers), so that
+refine.multi_refine hands in the rows of one sweep.
+
 Minimum spanning trees: generate_minimum_spanning_tree and generate_network_from_distances
 (PopPUNK/network.py:1721-1831, 2075-2151) take and return G as (edges, n_vertices, weights); the forest comes from
 ppk_mst / ppk_mst_dev and the seed linking (seed_links) runs on the host.
@@ -70,6 +75,177 @@ def print_network_summary(G, sample_size=None, betweenness_sample=betweenness_sa
                                                        "\tScore (w/ betweenness)\t\t\t" + "{:.4f}".format(scores[1]),
                                                        "\tScore (w/ weighted-betweenness)\t\t" + "{:.4f}".format(scores[2])])
                      + "\n")
+
+
+# ---- cluster numbers and names (PopPUNK/network.py:1478-1719) -------------------------------------
+
+def cluster_sweep(i_vec, j_vec, idx_vec, n, n_off=None, device=0):
+    """ppk_cluster_sweep on host arrays -> (clusters int32 [n_off, n], n_clusters int32 [n_off]); idx_vec None puts
+    every edge at offset 0."""
+    i = np.ascontiguousarray(i_vec, dtype=np.int64).ravel()
+    j = np.ascontiguousarray(j_vec, dtype=np.int64).ravel()
+    o = None if idx_vec is None else np.ascontiguousarray(idx_vec, dtype=np.int64).ravel()
+    if i.size != j.size or (o is not None and o.size != i.size):
+        raise ValueError("i_vec, j_vec and idx_vec differ in length")
+    if n_off is None:
+        n_off = int(o.max()) + 1 if o is not None and o.size else 1
+    n, n_off = int(n), int(n_off)
+    clusters = np.zeros((max(n_off, 1), max(n, 1)), dtype=np.int32)
+    counts = np.zeros(max(n_off, 1), dtype=np.int32)
+    llp, ip = C.POINTER(C.c_longlong), C.POINTER(C.c_int32)
+    rc = _lib.lib().ppk_cluster_sweep(i.ctypes.data_as(llp), j.ctypes.data_as(llp),
+                                      o.ctypes.data_as(llp) if o is not None else None, i.size, n, n_off, int(device),
+                                      clusters.ctypes.data_as(ip), counts.ctypes.data_as(ip))
+    _lib.check(rc, "ppk_cluster_sweep")
+    return (clusters if n else clusters[:, :0]), counts
+
+
+def cluster_numbers(G):
+    """printClusters' number (1-based) of every vertex of G = (edges, n_vertices), as an int32 numpy array: components
+    in the order of their smallest vertex, ranked by len - rankdata(sizes, 'ordinal') (network.py:1538-1545): by size
+    descending, equal sizes by component index descending.  A CUDA edge tensor is read in place."""
+    edges, n = G[0], int(G[1])
+    if hasattr(edges, "is_cuda"):
+        from . import engine
+        return engine.cluster_numbers_dev(edges, n)[0].cpu().numpy()
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    return cluster_sweep(e[:, 0], e[:, 1], None, n, 1)[0][0]
+
+
+def clusters_of_numbers(numbers, rlist):
+    """newClusters of printClusters from the number array: entry k lists the names of cluster k + 1, in rlist order
+    (the reference holds each as a set)."""
+    numbers = np.asarray(numbers, dtype=np.int64).ravel()
+    if numbers.size != len(rlist):
+        raise ValueError("one cluster number per name")
+    newClusters = [[] for _ in range(int(numbers.max()) if numbers.size else 0)]
+    for name, c in zip(rlist, numbers.tolist()):
+        newClusters[c - 1].append(name)
+    return newClusters
+
+
+def name_clusters(newClusters, oldClusters=None):
+    """The naming rules of printClusters (network.py:1547-1633) on newClusters (lists of names, in cluster-number
+    order) and the old clusters {name: set of samples} in their file order (None: no old file) ->
+    (clustering dict, merged_queries list, the set of names the old file knows).
+
+    Without old clusters a cluster's id is its number, an int.  With them ids are str.  A cluster none of whose names
+    is known takes the next fresh id, counted on from one above the largest integer that occurs in an old name (the
+    parts of a merged name `a_b` included).  Otherwise the old clusters are gone through in file order: one that
+    holds ALL of the cluster's known names gives its name and ends the search; each one that holds only some of them
+    adds its name to a merged id `a_b...`, and the cluster's unknown names go into merged_queries once per such old
+    cluster (as upstream's extend does).  An old cluster met for a second time is reported as split, a merged id as
+    merged, both on stderr in the reference's words."""
+    if oldClusters is None:
+        return ({name: number for number, members in enumerate(newClusters, 1) for name in members}, [], set())
+    known = set().union(*oldClusters.values()) if oldClusters else set()
+    fresh = 1 + max(int(part) for old_name in oldClusters for part in old_name.split("_"))
+    clustering, merged_queries, met = {}, [], set()
+    for members in newClusters:
+        mine = [name for name in members if name in known]
+        unknown = [name for name in members if name not in known]
+        if not mine:
+            label = str(fresh)
+            fresh += 1
+        else:
+            partial, label = [], None
+            for old_name, old_members in oldClusters.items():
+                shared = sum(1 for name in mine if name in old_members)
+                if shared == 0:
+                    continue
+                if old_name in met:
+                    sys.stderr.write("WARNING: Old cluster %s split across multiple new clusters\n" % old_name)
+                met.add(old_name)
+                if shared == len(mine):
+                    assert not partial, "a cluster matched exactly after a partial match"    # (upstream asserts too)
+                    label = old_name
+                    break
+                partial.append(old_name)
+                merged_queries.extend(unknown)
+            if label is None:
+                label = "_".join(partial)
+                sys.stderr.write("Clusters %s have merged into %s\n" % (",".join(label.split("_")), label))
+        clustering.update((name, label) for name in members)
+    return clustering, merged_queries, known
+
+
+def write_cluster_csv(clustering, outFileName, oldNames=(), printRef=True):
+    """`Taxon,Cluster` rows in blocks of one cluster name each: frequency descending, ties in the order the names were
+    first assigned (network.py:1636-1653); inside a block, the order of `clustering` (rlist order within a cluster)."""
+    from collections import Counter
+    freq_order = sorted(Counter(clustering.values()).items(), key=lambda kv: kv[1], reverse=True)
+    position = {name: k for k, (name, _) in enumerate(freq_order)}
+    with open(outFileName, 'w') as cluster_file:
+        cluster_file.write("Taxon,Cluster\n")
+        for cluster_member, cluster_name in sorted(clustering.items(), key=lambda kv: position[kv[1]]):
+            if printRef or cluster_member not in oldNames:
+                cluster_file.write(",".join((cluster_member, str(cluster_name))) + "\n")
+
+
+def print_cluster_numbers(numbers, rlist, outPrefix=None, oldClusterFile=None, externalClusterCSV=None, printRef=True,
+                          printCSV=True, clustering_type='combined', write_unwords=True):
+    """printClusters from the number array of cluster_numbers (or one row of a cluster sweep): everything after the
+    component ranking.  See printClusters."""
+    from .utils import readIsolateTypeFromCsv
+    if oldClusterFile is None and printRef is False:
+        raise RuntimeError("Trying to print query clusters with no query sequences")
+    if write_unwords and not printCSV:
+        write_unwords = False
+    newClusters = clusters_of_numbers(numbers, rlist)
+    oldClusters = None
+    if oldClusterFile is not None:
+        oldAllClusters = readIsolateTypeFromCsv(oldClusterFile, mode='external', return_dict=False)
+        oldClusters = oldAllClusters[list(oldAllClusters.keys())[0]]
+    clustering, merged_queries, oldNames = name_clusters(newClusters, oldClusters)
+    if printCSV:
+        if write_unwords:
+            sys.stderr.write("Pronounceable cluster names are not generated: no _unword_clusters.csv is written\n")
+        write_cluster_csv(clustering, outPrefix + "_clusters.csv", oldNames, printRef)
+        if externalClusterCSV is not None:
+            printExternalClusters(newClusters, externalClusterCSV, outPrefix, oldNames, printRef)
+    return clustering, merged_queries
+
+
+def printClusters(G, rlist, outPrefix=None, oldClusterFile=None, externalClusterCSV=None, printRef=True,
+                  printCSV=True, clustering_type='combined', write_unwords=True, use_gpu=False):
+    """PopPUNK/network.py:1478-1663, graph-tool branch -> (clustering dict, merged_queries list).
+
+    G = (edges, n_vertices), edges a numpy array or a CUDA tensor read in place; the cluster numbers come from the
+    device (cluster_numbers), the rest is print_cluster_numbers.  `<outPrefix>_clusters.csv` holds `Taxon,Cluster`
+    and one block per cluster name in the reference's block order; inside a block the reference iterates a Python set,
+    so its row order depends on the hash seed -- here the rows of a cluster follow rlist.  Ids are int without an old cluster file and
+    str with one.  Unword names need a word list that is not shipped and an unseeded random: `write_unwords` is
+    accepted, no `_unword_clusters.csv` is written and one stderr line says so.  `clustering_type` is unused upstream
+    too; `use_gpu` selects cugraph upstream (whose value_counts breaks ties differently) and is ignored.
+    That graph-tool's label_components numbers components by their lowest vertex is UNVERIFIED."""
+    if oldClusterFile is None and printRef is False:
+        raise RuntimeError("Trying to print query clusters with no query sequences")
+    return print_cluster_numbers(cluster_numbers(G), rlist, outPrefix, oldClusterFile, externalClusterCSV, printRef,
+                                 printCSV, clustering_type, write_unwords)
+
+
+def printExternalClusters(newClusters, extClusterFile, outPrefix, oldNames, printRef=True):
+    """PopPUNK/network.py:1665-1719: `<outPrefix>_external_clusters.csv`.  One row per sample (with printRef False only
+    those not in oldNames), in cluster order; per external column the labels that any sample of its cluster carries
+    there, ';'-joined in sorted order (the reference joins a set), 'NA' when none does.  No row at all: nothing is
+    written and the reference's warning goes to stderr."""
+    import csv
+    from .utils import readIsolateTypeFromCsv
+    external = readIsolateTypeFromCsv(extClusterFile, mode='external', return_dict=True)
+    table = []
+    for members in newClusters:
+        cells = []
+        for labels_of in external.values():
+            seen = sorted({labels_of[sample] for sample in members if sample in labels_of})
+            cells.append(";".join(seen) if seen else "NA")
+        table.extend([sample] + cells for sample in members if printRef or sample not in oldNames)
+    if not table:
+        sys.stderr.write("WARNING: No new samples found, cannot write external clusters\n")
+        return
+    with open(outPrefix + "_external_clusters.csv", 'w', newline='') as f:
+        out = csv.writer(f, lineterminator="\n")
+        out.writerow(["sample"] + list(external))
+        out.writerows(table)
 
 
 # ---- minimum spanning trees (PopPUNK/network.py:1721-1831, 2075-2151; DESIGN.md 3.9) ----------------------------

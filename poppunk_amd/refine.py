@@ -30,9 +30,17 @@ edge_threshold_dev + network_summary_graph_dev.  `num_processes` and `use_gpu` a
 raises NotImplementedError before the device is touched.  `last_fit` describes the latest refineFit call: the global
 scores, the bounds, every evaluation of the local search (s, counts, score) and which path scored it.
 
+Clusters at several boundaries mirrors PopPUNK/refine.py:249-312:
+
+    multi_refine(distMat, sample_names, mean0, mean1, scale, s_max, n_boundary_points, output_prefix, ...)
+        -> (numbers int32 [n_files, n], file indices)
+
+one thresholdIterate1D sweep, one ppk_cluster_sweep_dev for the cluster numbers of every graph, and the files
+growNetwork(write_clusters=...) would write (boundary_files states its index rule).  It makes its own device calls.
+
 Not mirrored by growNetwork (NotImplementedError, raised before the device is touched): betweenness scores
 (score_idx > 0; the device path for those is engine.refine_sweep_scores_dev(..., score_idx=...)),
-random vertex subsampling (sample_size), and writing each step's clusters (write_clusters: printClusters).
+random vertex subsampling (sample_size), and writing each step's clusters (write_clusters: multi_refine writes them).
 `use_gpu` selects cugraph upstream; it is accepted and ignored (this is the device path either way).
 """
 import ctypes as C
@@ -400,6 +408,69 @@ def refineFit(distMat, sample_names, mean0, mean1, scale, max_move, min_move, sl
                 raise RuntimeError("Optimisation failed: produced a boundary outside of allowed range\n")
 
     return optimal_x, optimal_y, optimised_s
+
+
+def boundary_files(edge_counts, n_clusters, n):
+    """Which `_boundary<k>_clusters.csv` files growNetwork(write_clusters=...) writes, and from which graph
+    (PopPUNK/refine.py:435-472), from the per-offset edge counts and cluster counts of one sweep -> a list of
+    (file index k, offset index of the graph).  The loop runs over the offset indices that add edges; the graph after
+    index idx is written as boundary prev_idx + 1 .. idx (prev_idx starts at -1), so an index without edges of its own
+    gets the NEXT graph that has some, not the one before it; only a graph with fewer clusters than samples is
+    written; nothing is written after the last index with edges."""
+    out = []
+    prev_idx = -1
+    for idx in np.flatnonzero(np.asarray(edge_counts).ravel() > 0).tolist():
+        if int(n_clusters[idx]) < int(n):
+            out.extend((k, idx) for k in range(prev_idx + 1, idx + 1))
+        prev_idx = idx
+    return out
+
+
+def multi_refine(distMat, sample_names, mean0, mean1, scale, s_max, n_boundary_points, output_prefix,
+                 num_processes=1, betweenness_sample=betweenness_sample_default, sample_size=None, use_gpu=False):
+    """PopPUNK/refine.py:249-312: the boundary moved in n_boundary_points steps from where the line mean0 -> mean1
+    meets an axis to the optimum s_max, and the clusters at each step written to
+    `<output_prefix>/<basename>_boundary<k>_clusters.csv` (printClusters without unword names).
+
+    distMat: the scaled float32 [n(n-1)/2, 2] matrix, a numpy array (uploaded once) or a resident CUDA tensor.  One
+    threshold_iterate_1d_dev, one cluster_sweep_dev; only the rows that are written leave the device.  The reference
+    returns None; this returns (numbers int32 [n_files, n]: row r is the number array of the r-th file; the file
+    indices k).  `num_processes`, `betweenness_sample` and `use_gpu` are accepted and ignored; `sample_size` raises
+    NotImplementedError before the device is touched."""
+    if sample_size is not None:
+        raise NotImplementedError("multi_refine: random vertex subsampling (sample_size) is not mirrored")
+    import os
+    import torch
+    from . import engine, network
+
+    # the range (refine.py:283-295): from where the line through mean0 and mean1, followed backwards from mean0, first
+    # meets an axis -- x = 0 when mean0 lies on or above the line of the same slope through the origin, else y = 0 --
+    # to the optimum; per unit of x the line is sqrt(1 + m^2) long, per unit of y sqrt(1 + 1 / m^2)
+    m = (mean1[1] - mean0[1]) / (mean1[0] - mean0[0])
+    meets_y_axis = mean0[1] >= m * mean0[0]
+    s_start = -mean0[0] * np.sqrt(1 + m * m) if meets_y_axis else -mean0[1] * np.sqrt(1 + 1 / (m * m))
+    s_range = np.linspace(s_start, s_max, num=n_boundary_points)
+    x_ends, y_ends = check_search_range(scale, mean0, mean1, s_range[0], s_range[-1])
+    if x_ends[0] < 0 or y_ends[0] < 0:
+        sys.stderr.write("Boundary range below zero")
+
+    dist_t = distMat if isinstance(distMat, torch.Tensor) else DeviceScorer(distMat).dist_t
+    n = len(sample_names)
+    n_off = len(s_range)
+    i_t, j_t, idx_t = engine.threshold_iterate_1d_dev(dist_t, s_range, 2, mean0[0], mean0[1], mean1[0], mean1[1])
+    clusters, counts = engine.cluster_sweep_dev(i_t.contiguous(), j_t.contiguous(), idx_t.contiguous(), n, n_off)
+    edge_counts = torch.bincount(idx_t, minlength=n_off).cpu().numpy()
+    files = boundary_files(edge_counts, counts.cpu().numpy(), n)
+    rows = sorted(set(idx for _, idx in files))
+    fetched = dict(zip(rows, clusters[torch.as_tensor(rows, dtype=torch.int64, device=clusters.device)].cpu().numpy())) \
+        if rows else {}
+    if files:
+        os.makedirs(output_prefix, exist_ok=True)
+    for k, idx in files:
+        o_prefix = f"{output_prefix}/{os.path.basename(output_prefix)}_boundary{k}"
+        network.print_cluster_numbers(fetched[idx], sample_names, outPrefix=o_prefix, write_unwords=False)
+    kept = np.stack([fetched[idx] for _, idx in files]) if files else np.zeros((0, n), dtype=np.int32)
+    return kept, [k for k, _ in files]
 
 
 def readManualStart(startFile):

@@ -52,6 +52,37 @@ def stderr_redirected(to=os.devnull):
             os.close(old)
 
 
+def readIsolateTypeFromCsv(clustCSV, mode='clusters', return_dict=False):
+    """Cluster definitions from a CSV file (PopPUNK/utils.py:264-319), read with the csv module (pandas is not a
+    dependency of this package).  The first column names the samples; the other columns are selected by `mode`:
+    'clusters' (columns with 'Cluster' in their name), 'lineages' ('Rank_' or 'overall'), 'external' (the only column,
+    or every column but the last).  Returns {column: {cluster: set of samples}}, or with return_dict
+    {column: {sample: cluster}}; '__autocolour' is dropped from column names.  Every value is the cell's text: the
+    reference's pandas reads an all-numeric column as numbers first, so '07' becomes '7' there and stays '07' here,
+    and numeric sample names are ints in its sets."""
+    import csv
+    with open(clustCSV, newline='') as f:
+        table = [row for row in csv.reader(f, quotechar='"') if row]
+    header = [col.replace('__autocolour', '') for col in table[0][1:]] if table else []
+    wanted = {'clusters': lambda k, col: 'Cluster' in col,
+              'lineages': lambda k, col: 'Rank_' in col or 'overall' in col,
+              'external': lambda k, col: k == 0 if len(header) == 1 else k < len(header) - 1}
+    if mode not in wanted:
+        sys.stderr.write('Unknown CSV reading mode: ' + mode + '\n')
+        sys.exit(1)
+    # the column test sees the name as the file has it ('__autocolour' and all), the result carries it stripped
+    picked = [k for k, col in enumerate(table[0][1:] if table else []) if wanted[mode](k, col)]
+    out = {}
+    for sample, *cells in table[1:]:
+        for k in picked:
+            column = out.setdefault(header[k], {})
+            if return_dict:
+                column[sample] = cells[k]
+            else:
+                column.setdefault(cells[k], set()).add(sample)
+    return out
+
+
 def iterDistRows(refSeqs, querySeqs, self=True):
     """Row -> (ref, query) names of the distance matrix (PopPUNK/utils.py:199-226)."""
     if self:
