@@ -755,6 +755,57 @@ int ppk_cluster_pair_sums(const float *dist, size_t n_rows, int col, const int32
                           int device_id, long long *sum, long long *cnt);
 
 /* ------------------------------------------------------------------------
+ * Queries against an existing clustering.  Vertices 0 .. n_ref-1 are references, n_ref .. n_ref+n_qry-1
+ * queries: the ids ppk_dist_edges_dev, ppk_*_edges_dev and ppk_generate_tuples_dev emit for a query-vs-reference job.
+ * The edge stream is d_i[k * stride], d_j[k * stride] (stride 1 or 2), either orientation, any order.  d_ref_label int32
+ * [n_ref]: two references with equal labels are in one component of the loaded network; any values in [0, n_ref), not
+ * necessarily dense or ordered.  For assignment the reference network matters only through these labels, so neither
+ * call reads its edges.  Integer arithmetic only: the same input, in any edge order, gives the same bits on every call.
+ * PPK_ERR_ARG, ppk_last_error() naming the first offender, nothing further launched: a label outside [0, n_ref), a
+ * vertex id outside [0, n_ref + n_qry), a self-loop.  Also PPK_ERR_ARG: max_links outside 1 .. 64, n_ref + n_qry >=
+ * 2^31, n_edges >= 2^31, stride not 1 or 2, a NULL array.
+ *
+ * ppk_query_links_dev: per query q (vertex n_ref + q), over its query-reference edges (edges with both ends on one
+ * side are skipped, so the stream ppk_cluster_extend_dev takes can be passed as it is):
+ *  - d_degree int32 [n_qry]: the number of those edges (a repeated edge counts every time);
+ *  - d_n_links int32 [n_qry]: the exact number of distinct labels among the references it is linked to;
+ *  - d_links int32 [n_qry][max_links]: the max_links smallest of those labels, ascending, padded with -1.
+ * A stream whose query-reference edges are non-decreasing in the query (every producer's row order; skipped edges
+ * after them, or none) is not sorted: one wave per query keeps the distinct labels of its segment in an LDS set of
+ * PPK_ASSIGN_SET_CAP entries.  A query with more distinct labels than that goes onto an overflow list, whose (query,
+ * label) keys are radix-sorted and made unique; any other stream takes that sort route for every query.
+ * Synchronises the stream once (the first offender and whether the stream is ordered), and once more on the ordered
+ * route for the length of the overflow list.
+ * (Replaces the per-query set walk of qcQueryAssignments, PopPUNK/qc.py:372-417, and, with `serial`, the per-query
+ * graph copy + label_components of assign_query_hdf5, PopPUNK/assign.py:696-722.) */
+#define PPK_ASSIGN_SET_CAP 128
+int ppk_query_links_dev(const long long *d_i, const long long *d_j, size_t stride, size_t n_edges,
+                        const int32_t *d_ref_label, size_t n_ref, size_t n_qry, int max_links, int32_t *d_degree,
+                        int32_t *d_n_links, int32_t *d_links, void *stream);
+/* Host arrays: i, j int64 [n_edges], ref_label int32 [n_ref] -> degree, n_links int32 [n_qry], links int32
+ * [n_qry][max_links], on device_id; blocking. */
+int ppk_query_links(const long long *i, const long long *j, size_t n_edges, const int32_t *ref_label, size_t n_ref,
+                    size_t n_qry, int max_links, int device_id, int32_t *degree, int32_t *n_links, int32_t *links);
+
+/* ppk_cluster_extend_dev: printClusters' number (ppk_cluster_sweep_dev's d_clusters, one graph) of each of the n_ref +
+ * n_qry vertices of (the loaded network + these edges): bit for bit what ppk_cluster_sweep_dev gives on the explicit
+ * union of the reference network's edges and the stream, provided d_ref_label holds that network's components.
+ * d_numbers int32 [n_ref + n_qry], d_n_clusters int32 [1].  The union-find is seeded from the labels (every reference
+ * under the smallest reference of its label, every query its own root), one union launch runs over the stream
+ * (query-query and reference-reference edges included), and the ranking is the cluster sweep's: O(n + n_edges) work
+ * whatever the reference network's edge count.  Synchronises the stream once.
+ * (Replaces addQueryToNetwork's edge insertion into the loaded graph, PopPUNK/network.py:1315-1442, followed by
+ * printClusters' label_components / rankdata block, network.py:1538-1545, in assign_query_hdf5, PopPUNK/assign.py:
+ * 628-660.) */
+int ppk_cluster_extend_dev(const long long *d_i, const long long *d_j, size_t stride, size_t n_edges,
+                           const int32_t *d_ref_label, size_t n_ref, size_t n_qry, int32_t *d_numbers,
+                           int32_t *d_n_clusters, void *stream);
+/* Host arrays: i, j int64 [n_edges], ref_label int32 [n_ref] -> numbers int32 [n_ref + n_qry], n_clusters int32 [1],
+ * on device_id; blocking. */
+int ppk_cluster_extend(const long long *i, const long long *j, size_t n_edges, const int32_t *ref_label, size_t n_ref,
+                       size_t n_qry, int device_id, int32_t *numbers, int32_t *n_clusters);
+
+/* ------------------------------------------------------------------------
  * Minimum spanning forests.  Edges d_i[k * stride], d_j[k * stride] (stride 1: separate arrays; 2:
  * an int64 [m][2] edge list, d_j = d_i + 1), weights d_w[k], over vertices 0 .. n_vertices-1; i > j, parallel edges and
  * both orientations of a pair allowed.  Edges are totally ordered by (w, min(i, j), max(i, j), k), -0.0 read as +0.0;

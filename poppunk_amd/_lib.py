@@ -92,6 +92,10 @@ SIGNATURES = {
     "ppk_cluster_sweep": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, _i32p, _i32p]),
     "ppk_cluster_pair_sums_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _sz, C.c_int, _vp, _vp, _vp]),
     "ppk_cluster_pair_sums": (C.c_int, [_f32p, _sz, C.c_int, _i32p, _sz, C.c_int, C.c_int, _llp, _llp]),
+    "ppk_query_links_dev": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, C.c_int, _vp, _vp, _vp, _vp]),
+    "ppk_query_links": (C.c_int, [_llp, _llp, _sz, _i32p, _sz, _sz, C.c_int, C.c_int, _i32p, _i32p, _i32p]),
+    "ppk_cluster_extend_dev": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "ppk_cluster_extend": (C.c_int, [_llp, _llp, _sz, _i32p, _sz, _sz, C.c_int, _i32p, _i32p]),
     "ppk_mst_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "ppk_mst": (C.c_int, [_llp, _llp, _f32p, _sz, _sz, C.c_int, _llp, _ullp, _i32p]),
     "ppk_edge_weights_dev": (C.c_int, [_vp, _sz, _vp, _vp, _sz, _sz, _sz, C.c_longlong, C.c_int, _vp, _vp]),

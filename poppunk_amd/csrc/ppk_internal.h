@@ -269,7 +269,9 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_SPARSE = 19,                       // extend's and lowerRank's row starts, sort pairs, counts, offsets and temp storage
        SLOT_REFINE = 20,                       // the refine fit's bit matrix, union-find parents and counters (one boundary at a time)
        SLOT_CLUSTERS = 21,                     // the cluster pair sums' first-bad-row / first-bad-number words
-       SLOT_COUNT = 22 };
+       SLOT_ASSIGN = 22,                       // the query links' counters, segment starts, overflow list and first ranks
+       SLOT_ASSIGN_SORT = 23,                  // ... and, on the sort route only, its (query, label) keys, flags and temp storage
+       SLOT_COUNT = 24 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

@@ -23,6 +23,8 @@
 //    G_t: the stages above, then the betweenness stage below.
 //  - ppk_cluster_sweep_dev : printClusters' cluster numbers (PopPUNK/network.py:1538-1545) of every vertex in every
 //    G_t, from the same validation, buckets and union launches (the section before the entry points).
+//  - ppk_cluster_extend_dev : the same numbers for (a loaded network + new edges), the loaded network given by its
+//    component labels alone: the cluster sweep with a seeded forest.
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -1034,6 +1036,35 @@ int net_sweep(const std::string &who, const long long *d_i, const long long *d_j
 //   clu_scatter  row t: every vertex reads its root's number
 // An offset without edges of its own copies the row before it; offset 0 is always computed (no edges: all singletons,
 // n - v).  n_clusters[t] = n - the links so far.
+// Seeded (ppk_cluster_extend_dev): vertices 0 .. n_ref-1 arrive as components, label[r] in [0, n_ref).
+//   clu_seed_first  first[l] = the smallest r with label[r] == l (atomicMin); a label out of range is the bad reference
+//   clu_seed        parent[r] = first[label[r]], parent[v >= n_ref] = v: parent[x] <= x and a root is its set's smallest
+//                   vertex, which is all uf_union and the ranking ask; every non-root counts as a link at offset 0
+// and the rest is the unseeded call's, over the new edges alone.
+__global__ void __launch_bounds__(kThreads) clu_seed_first_kernel(const int32_t *label, size_t n_ref, unsigned *first,
+                                                                  unsigned long long *bad) {
+  for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_ref; r += (size_t)gridDim.x * blockDim.x) {
+    const long long l = label[r];
+    if (l < 0 || l >= (long long)n_ref) atomicMin(bad, (unsigned long long)r);
+    else atomicMin(&first[l], (unsigned)r);
+  }
+}
+__global__ void __launch_bounds__(kThreads) clu_seed_kernel(const int32_t *label, const unsigned *first, size_t n_ref,
+                                                            size_t n, int *parent, unsigned *links0) {
+  unsigned mine = 0;
+  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) {
+    const int p = v < n_ref ? (int)first[label[v]] : (int)v;
+    parent[v] = p;
+    mine += p != (int)v;
+  }
+  __shared__ unsigned acc;
+  if (threadIdx.x == 0) acc = 0;
+  __syncthreads();
+  if (mine) atomicAdd(&acc, mine);
+  __syncthreads();
+  const unsigned tot = acc;
+  if (threadIdx.x == 0 && tot) atomicAdd(links0, tot);
+}
 __global__ void __launch_bounds__(kThreads) clu_root_keys_kernel(const int *root, const int *size, size_t n,
                                                                  unsigned long long *keys) {
   for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x)
@@ -1061,10 +1092,11 @@ __global__ void clu_counts_kernel(const unsigned *links, long long n, int n_off,
 
 int cluster_sweep(const std::string &who, const long long *d_i, const long long *d_j, size_t stride,
                   const long long *d_off, size_t n_edges, size_t n_vertices, size_t n_off, int32_t *d_clusters,
-                  int32_t *d_n_clusters, void *stream) {
+                  int32_t *d_n_clusters, void *stream, const int32_t *d_ref_label = nullptr, size_t n_ref = 0) {
   if (n_off == 0 || n_off > (size_t)kMaxOff) return ppk_fail(PPK_ERR_ARG, who + ": n_off must be 1 .. 1023");
   if (!d_off && n_off != 1 && n_edges) return ppk_fail(PPK_ERR_ARG, who + ": no offset array needs n_off == 1");
-  if (n_vertices >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, who + ": n_vertices must be < 2^31");
+  if (n_vertices >= ((size_t)1 << 31))
+    return ppk_fail(PPK_ERR_ARG, who + (d_ref_label ? ": n_ref + n_qry must be < 2^31" : ": n_vertices must be < 2^31"));
   if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, who + ": n_edges must be < 2^31");
   if (stride != 1 && stride != 2) return ppk_fail(PPK_ERR_ARG, who + ": stride must be 1 or 2");
   if (!d_n_clusters || (!d_clusters && n_vertices) || (n_edges && (!d_i || !d_j)))
@@ -1084,36 +1116,48 @@ int cluster_sweep(const std::string &who, const long long *d_i, const long long 
                                   rocprim::plus<unsigned>(), s));
   const size_t tmp = sort_tmp > scan_tmp ? sort_tmp : scan_tmp;
   unsigned long long *bad, *ka, *kb;
-  unsigned *cnt, *cursor, *links;
+  unsigned *cnt, *cursor, *links, *first;
   int *parent, *root, *size, *number, *bu, *bv;
   char *d_tmp;
   size_t zero_begin = 0, zero_end = 0;
   int rc = ppk_scratch_carve(dev, SLOT_NET, [&](Carve &c) {
-    c.take(bad, 1);
+    c.take(bad, 2);                      // the first bad edge, the first bad reference label
     zero_begin = c.at;
     c.take(cnt, 1024).take(cursor, 1024).take(links, 1024);
     zero_end = c.at;
     c.take(parent, n).take(root, n).take(size, n).take(number, n).take(bu, m).take(bv, m);
-    c.take(ka, n).take(kb, n).take(d_tmp, tmp + 16);
+    c.take(ka, n).take(kb, n).take(first, n_ref).take(d_tmp, tmp + 16);
   });
   if (rc != PPK_OK) return rc;
 
   // -- validate: the one synchronisation
   ppk_prof_stage("validate", s);
   PPK_HIP(hipMemsetAsync(cnt, 0, zero_end - zero_begin, s));
-  PPK_HIP(hipMemsetAsync(bad, 0xff, 8, s));
+  PPK_HIP(hipMemsetAsync(bad, 0xff, 16, s));
+  if (n_ref) {
+    PPK_HIP(hipMemsetAsync(first, 0xff, n_ref * 4, s));
+    hipLaunchKernelGGL(clu_seed_first_kernel, dim3(grid_for(n_ref, kThreads * 4, 2048)), dim3(kThreads), 0, s,
+                       d_ref_label, n_ref, first, bad + 1);
+  }
   if (m)
     hipLaunchKernelGGL(net_validate_kernel, dim3(grid_for(m, kThreads * 8, 2048)), dim3(kThreads), 0, s, d_i, d_j,
                        stride, d_off, m, (long long)n, (int)no, cnt, bad);
   PPK_HIP(hipGetLastError());
   const unsigned long long *h = nullptr;
-  if ((rc = ppk_read_back(dev, s, {{bad, 8}, {cnt, no * 4}}, &h)) != PPK_OK) return rc;
+  if ((rc = ppk_read_back(dev, s, {{bad, 16}, {cnt, no * 4}}, &h)) != PPK_OK) return rc;
+  if (h[1] != ~0ull) {
+    ppk_prof_stage(nullptr, s);
+    int32_t l = 0;
+    PPK_HIP(hipMemcpy(&l, d_ref_label + h[1], 4, hipMemcpyDeviceToHost));
+    return ppk_fail(PPK_ERR_ARG, who + ": reference " + std::to_string(h[1]) + ": label " + std::to_string(l) +
+                                     " outside [0, " + std::to_string(n_ref) + ")");
+  }
   if (h[0] != ~0ull) {
     ppk_prof_stage(nullptr, s);
     return bad_edge_message(who, d_i, d_j, stride, d_off, (size_t)h[0], n, no);
   }
   std::vector<unsigned> counts(no), starts(no);
-  memcpy(counts.data(), h + 1, no * 4);
+  memcpy(counts.data(), h + 2, no * 4);
   for (size_t o = 0, acc = 0; o < no; ++o) {
     starts[o] = (unsigned)acc;
     acc += counts[o];
@@ -1134,7 +1178,8 @@ int cluster_sweep(const std::string &who, const long long *d_i, const long long 
   ppk_prof_stage("clusters", s);
   if (n) {
     const dim3 gn(grid_for(n, kThreads, 4096));
-    hipLaunchKernelGGL(net_parent_init_kernel, gn, dim3(kThreads), 0, s, parent, n);
+    if (n_ref) hipLaunchKernelGGL(clu_seed_kernel, gn, dim3(kThreads), 0, s, d_ref_label, first, n_ref, n, parent, links);
+    else hipLaunchKernelGGL(net_parent_init_kernel, gn, dim3(kThreads), 0, s, parent, n);
     for (size_t o = 0; o < no; ++o) {
       int32_t *row = d_clusters + o * n;
       if (!counts[o] && o) {
@@ -1243,6 +1288,42 @@ extern "C" int ppk_cluster_sweep_dev(const long long *d_i, const long long *d_j,
                                      int32_t *d_n_clusters, void *stream) {
   return cluster_sweep("ppk_cluster_sweep", d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, d_clusters,
                        d_n_clusters, stream);
+}
+
+extern "C" int ppk_cluster_extend_dev(const long long *d_i, const long long *d_j, size_t stride, size_t n_edges,
+                                      const int32_t *d_ref_label, size_t n_ref, size_t n_qry, int32_t *d_numbers,
+                                      int32_t *d_n_clusters, void *stream) {
+  if (n_ref >= ((size_t)1 << 31) || n_qry >= ((size_t)1 << 31) || n_ref + n_qry >= ((size_t)1 << 31))
+    return ppk_fail(PPK_ERR_ARG, "ppk_cluster_extend: n_ref + n_qry must be < 2^31");
+  if (n_ref && !d_ref_label) return ppk_fail(PPK_ERR_ARG, "ppk_cluster_extend: NULL array");
+  return cluster_sweep("ppk_cluster_extend", d_i, d_j, stride, nullptr, n_edges, n_ref + n_qry, 1, d_numbers,
+                       d_n_clusters, stream, d_ref_label, n_ref);
+}
+
+extern "C" int ppk_cluster_extend(const long long *i, const long long *j, size_t n_edges, const int32_t *ref_label,
+                                  size_t n_ref, size_t n_qry, int device_id, int32_t *numbers, int32_t *n_clusters) {
+  if (n_ref >= ((size_t)1 << 31) || n_qry >= ((size_t)1 << 31) || n_ref + n_qry >= ((size_t)1 << 31))
+    return ppk_fail(PPK_ERR_ARG, "ppk_cluster_extend: n_ref + n_qry must be < 2^31");
+  if (n_edges >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_cluster_extend: n_edges must be < 2^31");
+  if (!n_clusters || (!numbers && n_ref + n_qry) || (n_edges && (!i || !j)) || (n_ref && !ref_label))
+    return ppk_fail(PPK_ERR_ARG, "ppk_cluster_extend: NULL array");
+  const size_t n = n_ref + n_qry;
+  long long *d_i, *d_j;
+  int32_t *d_label, *d_numbers, *d_nc;
+  return ppk_host_frame(device_id, [&](Carve &c) {
+    c.take(d_i, n_edges).take(d_j, n_edges).take(d_label, n_ref).take(d_numbers, n).take(d_nc, 1);
+  }, [&]() -> int {
+    if (n_edges) {
+      PPK_HIP(hipMemcpy(d_i, i, n_edges * 8, hipMemcpyHostToDevice));
+      PPK_HIP(hipMemcpy(d_j, j, n_edges * 8, hipMemcpyHostToDevice));
+    }
+    if (n_ref) PPK_HIP(hipMemcpy(d_label, ref_label, n_ref * 4, hipMemcpyHostToDevice));
+    const int rc = ppk_cluster_extend_dev(d_i, d_j, 1, n_edges, d_label, n_ref, n_qry, d_numbers, d_nc, nullptr);
+    if (rc != PPK_OK) return rc;
+    if (n) PPK_HIP(hipMemcpy(numbers, d_numbers, n * 4, hipMemcpyDeviceToHost));
+    PPK_HIP(hipMemcpy(n_clusters, d_nc, 4, hipMemcpyDeviceToHost));
+    return PPK_OK;
+  });
 }
 
 extern "C" int ppk_cluster_sweep(const long long *i, const long long *j, const long long *off, size_t n_edges,

@@ -788,6 +788,101 @@ def cluster_numbers_dev(edges_t, n):
     return clusters[0], int(counts[0].item())
 
 
+def _assign_args(edges_t, ref_label_t):
+    """(i_t, j_t, m, stride) of the query-vs-reference edge stream after checking it and the int32 label tensor.
+    edges_t: a contiguous int64 [m, 2] CUDA tensor, or an (i_t, j_t) pair as network_sweep_dev takes it."""
+    torch = _torch()
+    if isinstance(edges_t, (tuple, list)):
+        i_t, j_t = edges_t
+    else:
+        if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
+                and edges_t.is_contiguous()):
+            raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
+        i_t, j_t = edges_t[:, 0], edges_t[:, 1]
+    m, stride = _edge_stream(i_t, j_t, None)
+    if not (ref_label_t.is_cuda and ref_label_t.dtype == torch.int32 and ref_label_t.dim() == 1
+            and ref_label_t.is_contiguous() and ref_label_t.device == i_t.device):
+        raise TypeError("ref_label must be a contiguous int32 CUDA tensor on the edges' device")
+    return i_t, j_t, m, stride
+
+
+def check_assign_sizes(who, n_ref, n_qry, max_links=None):
+    """The size limits of ppk_query_links* / ppk_cluster_extend*, in the library's words, before any output is
+    allocated (an n_qry of 2^31 would otherwise cost gigabytes just to be refused)."""
+    if max_links is not None and not 1 <= max_links <= 64:
+        raise RuntimeError("%s: max_links must be 1 .. 64" % who)
+    if n_ref < 0 or n_qry < 0 or n_ref + n_qry >= 1 << 31:
+        raise RuntimeError("%s: n_ref + n_qry must be < 2^31" % who)
+
+
+def query_links_dev(edges_t, ref_label_t, n_qry, max_links=8):
+    """Per query of a query-vs-reference edge stream (ppk_query_links_dev): vertices 0 .. n_ref-1 are
+    references (n_ref = len(ref_label_t)), n_ref .. n_ref+n_qry-1 queries; ref_label_t int32 [n_ref] holds the component
+    of every reference in the loaded network, any values in [0, n_ref).  Edges with both ends on one side are skipped.
+    Returns CUDA tensors (degree int32 [n_qry]: query-reference edges; n_links int32 [n_qry]: distinct labels linked
+    to, exact; links int32 [n_qry, max_links]: the smallest max_links of them, ascending, padded with -1)."""
+    torch = _torch()
+    i_t, j_t, m, stride = _assign_args(edges_t, ref_label_t)
+    dev = i_t.device
+    n_ref, n_qry, max_links = int(ref_label_t.shape[0]), int(n_qry), int(max_links)
+    check_assign_sizes("ppk_query_links", n_ref, n_qry, max_links)
+    with torch.cuda.device(dev):
+        degree = torch.empty(max(n_qry, 1), dtype=torch.int32, device=dev)
+        n_links = torch.empty(max(n_qry, 1), dtype=torch.int32, device=dev)
+        links = torch.empty((max(n_qry, 1), max_links), dtype=torch.int32, device=dev)
+        rc = _lib.lib().ppk_query_links_dev(
+            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride, m, C.c_void_p(ref_label_t.data_ptr()),
+            n_ref, n_qry, max_links, C.c_void_p(degree.data_ptr()), C.c_void_p(n_links.data_ptr()),
+            C.c_void_p(links.data_ptr()), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_query_links_dev")
+    return degree[:n_qry], n_links[:n_qry], links[:n_qry]
+
+
+def cluster_extend_dev(edges_t, ref_label_t, n_qry):
+    """printClusters' number of every vertex of (the loaded network + these edges), the loaded network given by its
+    component labels alone (ppk_cluster_extend_dev): what cluster_numbers_dev gives on the union of
+    the reference network's edges and edges_t, without reading the former.  The stream and labels of
+    query_links_dev; query-query and reference-reference edges take part.  Returns (numbers int32 [n_ref + n_qry]
+    CUDA, the cluster count)."""
+    torch = _torch()
+    i_t, j_t, m, stride = _assign_args(edges_t, ref_label_t)
+    dev = i_t.device
+    n_ref, n_qry = int(ref_label_t.shape[0]), int(n_qry)
+    check_assign_sizes("ppk_cluster_extend", n_ref, n_qry)
+    with torch.cuda.device(dev):
+        numbers = torch.empty(max(n_ref + n_qry, 1), dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        rc = _lib.lib().ppk_cluster_extend_dev(
+            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride, m, C.c_void_p(ref_label_t.data_ptr()),
+            n_ref, n_qry, C.c_void_p(numbers.data_ptr()), C.c_void_p(count.data_ptr()), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_cluster_extend_dev")
+    return numbers[:n_ref + n_qry], int(count.item())
+
+
+def nearest_reference_dev(dist_t, n_qry, n_ref, dist_col=0):
+    """get_kNN_distances(qrDistMat[:, dist_col].reshape(n_qry, n_ref), kNN=1) as assign_query_hdf5's `stable` branch
+    calls it (PopPUNK/assign.py:678-684), on the resident float32 [n_qry * n_ref, 2] matrix, read in place
+    (ppk_knn_rect_dev): for every query the reference of the smallest distance, ties by the lower index -- and, as
+    upstream, never the reference whose INDEX equals the query's (src/extend.cpp:271 skips column i of row i, also in
+    a rectangle).  Returns int64 [n_qry] CUDA."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    n_qry, n_ref = int(n_qry), int(n_ref)
+    if dist_t.shape[0] != n_qry * n_ref:
+        raise ValueError("the matrix must have n_qry * n_ref rows")
+    dev = dist_t.device
+    with torch.cuda.device(dev):
+        oi = torch.empty(max(n_qry, 1), dtype=torch.int64, device=dev)
+        oj = torch.zeros(max(n_qry, 1), dtype=torch.int64, device=dev)
+        od = torch.empty(max(n_qry, 1), dtype=torch.float32, device=dev)
+        if n_qry and n_ref:
+            rc = _lib.lib().ppk_knn_rect_dev(C.c_void_p(dist_t.data_ptr()), 2, int(dist_col), n_qry, n_ref, 0, 1,
+                                             C.c_void_p(oi.data_ptr()), C.c_void_p(oj.data_ptr()),
+                                             C.c_void_p(od.data_ptr()), _stream_ptr(dev.index))
+            _lib.check(rc, "ppk_knn_rect_dev")
+    return oj[:n_qry]
+
+
 def pair_sum_shift(n_rows):
     """The fixed-point shift of cluster_pair_sums: min(40, 62 - ceil_log2(n_rows)), so that no sum passes 2^62
     (ceil_log2 as ppk_device.h states it)."""

@@ -21,6 +21,11 @@ number of every vertex comes from ppk_cluster_sweep / ppk_cluster_sweep_dev (clu
 CSV and the external-cluster table are host code on that number array (name_clusters, print_cluster_numbers), so that
 refine.multi_refine hands in the rows of one sweep.
 
+Queries against a loaded network: construct_network_from_assignments and addQueryToNetwork
+(PopPUNK/network.py:1115-1203, 1315-1442) on G = (edges, n_vertices[, weights]); query_links and cluster_extend are the
+host-array forms of ppk_query_links / ppk_cluster_extend (the CUDA forms are engine.query_links_dev /
+engine.cluster_extend_dev), which answer per query what the loaded network matters for: its components.
+
 Minimum spanning trees: generate_minimum_spanning_tree and generate_network_from_distances
 (PopPUNK/network.py:1721-1831, 2075-2151) take and return G as (edges, n_vertices, weights); the forest comes from
 ppk_mst / ppk_mst_dev and the seed linking (seed_links) runs on the host.
@@ -246,6 +251,232 @@ def printExternalClusters(newClusters, extClusterFile, outPrefix, oldNames, prin
         out = csv.writer(f, lineterminator="\n")
         out.writerow(["sample"] + list(external))
         out.writerows(table)
+
+
+# ---- queries against a loaded network (PopPUNK/network.py:1115-1203, 1315-1442) -----------------
+
+def _assign_arrays(i_vec, j_vec, ref_label):
+    i = np.ascontiguousarray(i_vec, dtype=np.int64).ravel()
+    j = np.ascontiguousarray(j_vec, dtype=np.int64).ravel()
+    if i.size != j.size:
+        raise ValueError("i_vec and j_vec differ in length")
+    return i, j, np.ascontiguousarray(ref_label, dtype=np.int32).ravel()
+
+
+def query_links(i_vec, j_vec, ref_label, n_qry, max_links=8, device=0):
+    """ppk_query_links on host arrays: vertices 0 .. len(ref_label)-1 are references, the next n_qry the queries;
+    ref_label[r] in [0, n_ref) is the component of reference r in the loaded network.  Returns (degree int32 [n_qry]:
+    query-reference edges; n_links int32 [n_qry]: distinct labels linked to, exact; links int32 [n_qry, max_links]: the
+    smallest max_links of them, ascending, padded with -1).  Edges with both ends on one side are skipped."""
+    i, j, lab = _assign_arrays(i_vec, j_vec, ref_label)
+    n_qry, max_links = int(n_qry), int(max_links)
+    from .engine import check_assign_sizes
+    check_assign_sizes("ppk_query_links", lab.size, n_qry, max_links)          # before the outputs are allocated
+    degree = np.zeros(max(n_qry, 1), dtype=np.int32)
+    n_links = np.zeros(max(n_qry, 1), dtype=np.int32)
+    links = np.full((max(n_qry, 1), max_links), -1, dtype=np.int32)
+    llp, ip = C.POINTER(C.c_longlong), C.POINTER(C.c_int32)
+    rc = _lib.lib().ppk_query_links(i.ctypes.data_as(llp), j.ctypes.data_as(llp), i.size, lab.ctypes.data_as(ip),
+                                    lab.size, n_qry, max_links, int(device), degree.ctypes.data_as(ip),
+                                    n_links.ctypes.data_as(ip), links.ctypes.data_as(ip))
+    _lib.check(rc, "ppk_query_links")
+    return degree[:n_qry], n_links[:n_qry], links[:n_qry]
+
+
+def cluster_extend(i_vec, j_vec, ref_label, n_qry, device=0):
+    """ppk_cluster_extend on host arrays -> (numbers int32 [n_ref + n_qry], the cluster count): printClusters' number
+    of every vertex of (the loaded network + these edges), the loaded network given by its component labels."""
+    i, j, lab = _assign_arrays(i_vec, j_vec, ref_label)
+    from .engine import check_assign_sizes
+    check_assign_sizes("ppk_cluster_extend", lab.size, int(n_qry))
+    n = lab.size + int(n_qry)
+    numbers = np.zeros(max(n, 1), dtype=np.int32)
+    count = np.zeros(1, dtype=np.int32)
+    llp, ip = C.POINTER(C.c_longlong), C.POINTER(C.c_int32)
+    rc = _lib.lib().ppk_cluster_extend(i.ctypes.data_as(llp), j.ctypes.data_as(llp), i.size, lab.ctypes.data_as(ip),
+                                       lab.size, int(n_qry), int(device), numbers.ctypes.data_as(ip),
+                                       count.ctypes.data_as(ip))
+    _lib.check(rc, "ppk_cluster_extend")
+    return numbers[:n], int(count[0])
+
+
+def _is_cuda(x):
+    return bool(getattr(x, "is_cuda", False))        # (a CPU torch tensor goes the host-array way)
+
+
+def _cat(parts):
+    """the parts one after another, on the device if any of them is there"""
+    dev = next((p.device for p in parts if _is_cuda(p)), None)
+    if dev is None:
+        return np.concatenate([np.asarray(p) for p in parts])
+    import torch
+    return torch.cat([p if _is_cuda(p) else torch.as_tensor(np.asarray(p), device=dev) for p in parts])
+
+
+def assignment_edges(assignments, within_label, self_comparison, num_ref, int_offset=0, distMat=None,
+                     weights_type=None, weights=None):
+    """The new edges of construct_network_from_assignments and their weights (network.py:1170-1184): generateTuples of
+    the rows with assignments == within_label, and `weights` filtered to those rows, or process_weights of distMat's.
+    A CUDA assignment tensor stays on the device (generate_tuples_dev, edge_weights_dev); numpy arrays go through the
+    host-array calls.  Returns (edges int64 [m, 2], weights float32 [m] or None)."""
+    from . import poppunk_refine
+    if _is_cuda(assignments):
+        import torch
+        from . import engine
+        a = assignments if assignments.dtype == torch.int32 else assignments.to(torch.int32)
+        edges = engine.generate_tuples_dev(a.contiguous(), within_label, self_comparison, num_ref, int_offset)
+    else:
+        assignments = np.asarray(assignments)
+        edges = poppunk_refine.generateTuples_array(assignments, within_label, self_comparison, num_ref, int_offset)
+    w = None
+    if weights is not None:
+        w = weights[assignments == within_label]
+    elif distMat is not None and weights_type is not None:
+        if _is_cuda(distMat):
+            import torch
+            from . import engine
+            e_t = edges if _is_cuda(edges) else torch.as_tensor(edges, device=distMat.device)
+            w = engine.edge_weights_dev(distMat, e_t, weights_type, 0 if self_comparison else num_ref, int_offset)
+        else:
+            a = assignments.cpu().numpy() if _is_cuda(assignments) else assignments
+            rows = np.asarray(distMat)[a == within_label, :]
+            w = {'euclidean': lambda d: np.linalg.norm(d, axis=1), 'core': lambda d: d[:, 0],
+                 'accessory': lambda d: d[:, 1]}[weights_type](rows)
+    return edges, w
+
+
+def _previous_edges(previous_network, vertex_labels, adding_qq_dists, old_ids, previous_pkl, weights):
+    """process_previous_network / network_to_edges (network.py:676-732, 519-614) on G = (edges, n[, weights]): the old
+    edges under the new numbering, and their weights when `weights`."""
+    if previous_pkl is not None:
+        raise NotImplementedError("construct_network_from_assignments: previous_pkl (a names pickle) is not "
+                                  "mirrored; pass old_ids")
+    if old_ids is None:
+        sys.stderr.write('Missing .pkl file containing names of sequences in previous network\n')
+        sys.exit(1)
+    old_edges = previous_network[0]
+    old_w = None
+    if weights:
+        if len(previous_network) < 3 or previous_network[2] is None:
+            sys.stderr.write('Loaded network does not have edge weights; try a different '
+                             'network or turn off graph weights\n')
+            sys.exit(1)
+        old_w = previous_network[2]
+    if not adding_qq_dists:
+        try:
+            index = {name: k for k, name in reversed(list(enumerate(vertex_labels)))}      # list.index: the first
+            old_id_indices = [index[x] for x in old_ids]
+        except KeyError:
+            sys.stderr.write("Network size mismatch: a vertex of the previous network is not in the new one\n")
+            sys.exit(1)
+        if old_id_indices != list(range(len(old_id_indices))):
+            remap = np.asarray(old_id_indices, dtype=np.int64)
+            if _is_cuda(old_edges):
+                import torch
+                old_edges = torch.as_tensor(remap, device=old_edges.device)[old_edges]
+            else:
+                old_edges = remap[np.asarray(old_edges, dtype=np.int64).reshape(-1, 2)]
+    return old_edges, old_w
+
+
+def construct_network_from_assignments(rlist, qlist, assignments, within_label=1, int_offset=0, weights=None,
+                                       distMat=None, weights_type=None, previous_network=None, old_ids=None,
+                                       adding_qq_dists=False, previous_pkl=None,
+                                       betweenness_sample=betweenness_sample_default, summarise=True, sample_size=None,
+                                       use_gpu=False):
+    """PopPUNK/network.py:1115-1203 with the reference's signature, on G = (edges, n_vertices), or (edges, n_vertices,
+    weights) when weights are asked for (`weights`, or distMat with weights_type).  The new edges come first, in
+    generateTuples' order, then the previous network's (construct_network_from_edge_list, network.py:822-834).
+    `assignments` (and distMat) may be numpy arrays or CUDA tensors; a CUDA assignment gives CUDA edges.
+    previous_network is such a G, its vertices named by old_ids; the reference's messages and exits are kept for a
+    previous network without weights when weights are asked for and for old names missing from the new list.
+    previous_pkl raises NotImplementedError (file loading is not mirrored); `use_gpu` is accepted and ignored."""
+    rlist, qlist = list(rlist), list(qlist)
+    self_comparison = rlist == qlist
+    vertex_labels = rlist if self_comparison else rlist + qlist
+    edges, w = assignment_edges(assignments, within_label, self_comparison, len(rlist), int_offset, distMat,
+                                weights_type, weights)
+    if previous_network is not None:
+        old_edges, old_w = _previous_edges(previous_network, vertex_labels, adding_qq_dists, old_ids, previous_pkl,
+                                           w is not None)
+        old_edges = old_edges if _is_cuda(old_edges) else np.asarray(old_edges, dtype=np.int64).reshape(-1, 2)
+        edges = _cat([edges, old_edges])
+        if w is not None:
+            w = _cat([w if _is_cuda(w) else np.asarray(w, dtype=np.float32),
+                      old_w if _is_cuda(old_w) else np.asarray(old_w, dtype=np.float32)])
+    G = (edges, len(vertex_labels)) if w is None else (edges, len(vertex_labels), w)
+    if summarise:
+        print_network_summary(G[:2], sample_size=sample_size, betweenness_sample=betweenness_sample, use_gpu=use_gpu)
+    return G
+
+
+def model_assign(model, X, slope=None):
+    """model.assign(X[, slope=slope]) as upstream calls it; a CUDA matrix goes to the model's assign_dev"""
+    fn = model.assign_dev if _is_cuda(X) else model.assign
+    return fn(X) if slope is None else fn(X, slope=slope)
+
+
+def query_degrees(edges, n_ref, n_qry):
+    """G.get_total_degrees of the query vertices (network.py:1395) from the query-reference edges alone (the previous
+    network has no edge at a query): the degree array of query_links under labels that do not matter (all zero)."""
+    if _is_cuda(edges):
+        import torch
+        from . import engine
+        lab = torch.zeros(n_ref, dtype=torch.int32, device=edges.device)
+        return engine.query_links_dev(edges.contiguous(), lab, n_qry, 1)[0].cpu().numpy()
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    return query_links(e[:, 0], e[:, 1], np.zeros(n_ref, dtype=np.int32), n_qry, 1)[0]
+
+
+def addQueryToNetwork(dbFuncs, rList, qList, G, assignments, model, queryDB, kmers=None, distance_type='euclidean',
+                      queryQuery=False, strand_preserved=False, weights=None, threads=1, use_gpu=False):
+    """PopPUNK/network.py:1315-1442 with the reference's signature -> (G, qqDistMat), G = (edges, n[, weights]).
+
+    The query-reference edges of `assignments` are put in front of G's; a query left without an edge switches on the
+    query-query distances, as upstream ("Found novel query clusters..."), which come from dbFuncs['queryDatabase']
+    (called with the reference's keywords; a CUDA tensor it returns stays on the device), are assigned by `model` under distance_type's slope and added in front
+    again.  One query never needs them (an empty [0, 2] matrix is returned); more than one without `kmers` is the
+    reference's RuntimeError.  `weights` is the query-reference distance matrix, as upstream passes it; G must then
+    carry weights too (the reference's message and exit otherwise).  addRandom (network.py:1408) is NOT called:
+    sketching and the random-match table of the query database are out of scope, queryDatabase is expected to find
+    them.  `use_gpu` is accepted and ignored."""
+    queryDatabase = dbFuncs['queryDatabase']
+    if len(qList) > 1 and kmers is None:
+        raise RuntimeError("Must provide db querying info (kmers) if adding "
+                           "more than one sample, as q-q dists may be needed")
+    weights_type = None if weights is None else distance_type
+    qqDistMat = None
+    ref_count = len(rList)
+    n_old = int(G[0].shape[0]) if hasattr(G[0], "shape") else len(G[0])
+    G = construct_network_from_assignments(rList, qList, assignments, within_label=model.within_label,
+                                           previous_network=G, old_ids=rList, distMat=weights,
+                                           weights_type=weights_type, summarise=False, use_gpu=use_gpu)
+    if not queryQuery:
+        # the new edges are in front of the previous network's, which has none at a query and is not read again
+        edge_count = query_degrees(G[0][:G[0].shape[0] - n_old], ref_count, len(qList))
+        if np.any(edge_count == 0):
+            sys.stderr.write("Found novel query clusters. Calculating distances between them.\n")
+            queryQuery = True
+    if queryQuery:
+        if len(qList) == 1:
+            qqDistMat = np.zeros((0, 2), dtype=np.float32)
+        else:
+            sys.stderr.write("Calculating all query-query distances\n")
+            qqDistMat = queryDatabase(rNames=qList, qNames=qList, dbPrefix=queryDB, queryPrefix=queryDB, klist=kmers,
+                                      self=True, number_plot_fits=0, threads=threads)
+            if distance_type == 'core':
+                queryAssignation = model_assign(model, qqDistMat, 0)
+            elif distance_type == 'accessory':
+                queryAssignation = model_assign(model, qqDistMat, 1)
+            else:
+                queryAssignation = model_assign(model, qqDistMat)
+            vertex_labels = list(rList) + list(qList)
+            G = construct_network_from_assignments(vertex_labels, vertex_labels, queryAssignation,
+                                                   int_offset=ref_count, within_label=model.within_label,
+                                                   previous_network=G, old_ids=vertex_labels, adding_qq_dists=True,
+                                                   distMat=qqDistMat, weights_type=weights_type, summarise=False,
+                                                   use_gpu=use_gpu)
+    return G, qqDistMat
 
 
 # ---- minimum spanning trees (PopPUNK/network.py:1721-1831, 2075-2151; DESIGN.md 3.9) ----------------------------

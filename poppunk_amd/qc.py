@@ -83,6 +83,48 @@ def prune_query_distance_matrix(refList, queryList, remove_seqs, qrDistMat, quer
     return passing_queries, newqr, queryAssign
 
 
+# ---- graph QC of query assignments (PopPUNK/qc.py:372-417) -----------------------------------
+
+def cluster_labels_of_names(rList, clusters_of):
+    """int32 [len(rList)] labels in [0, n_ref) from {name: cluster name}: every cluster name becomes the index of the
+    first reference that carries it.  A reference missing from the dict raises KeyError, as upstream's lookup does."""
+    first = {}
+    return np.array([first.setdefault(clusters_of[name], k) for k, name in enumerate(rList)], dtype=np.int32)
+
+
+def failed_by_links(qList, n_links, max_clusters):
+    """qcQueryAssignments' verdict from the distinct-cluster count of every query -> (retained list, failed dict)."""
+    message = ["Failed graph QC (too many links)"]
+    retained_samples, failed_samples = [], {}
+    for query, count in zip(qList, np.asarray(n_links).tolist()):
+        if count > max_clusters:
+            failed_samples[query] = message
+        else:
+            retained_samples.append(query)
+    return retained_samples, failed_samples
+
+
+def qcQueryAssignments(rList, qList, query_assignments, max_clusters, original_cluster_file):
+    """PopPUNK/qc.py:372-417: queries linked (assignment == -1, as upstream has it) to references of more than
+    max_clusters clusters of the old cluster file fail.  The reference walks a Python set per query over the
+    [n_qry * n_ref] assignment; here the links become an edge list (generateTuples) and one ppk_query_links call counts
+    every query's distinct clusters.  query_assignments: a numpy array, or a CUDA tensor read on its device.
+    Returns (retained names, {failed name: message})."""
+    from . import network
+    from .utils import readIsolateTypeFromCsv
+    clusters = readIsolateTypeFromCsv(original_cluster_file, return_dict=True)
+    labels = cluster_labels_of_names(rList, clusters['Cluster'])
+    edges, _ = network.assignment_edges(query_assignments, -1, False, len(rList))
+    if network._is_cuda(edges):
+        import torch
+        from . import engine
+        n_links = engine.query_links_dev(edges, torch.as_tensor(labels, device=edges.device), len(qList), 1)[1]
+        n_links = n_links.cpu().numpy()
+    else:
+        n_links = network.query_links(edges[:, 0], edges[:, 1], labels, len(qList), 1)[1]
+    return failed_by_links(qList, n_links, max_clusters)
+
+
 # ---- distance QC (PopPUNK/qc.py:238-369,:419-468) -----------------------------------------------------
 
 def qc_edge_lists(distMat, n_ref, max_pi_dist, max_a_dist, zeros=True, device_id=0):
