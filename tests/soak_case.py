@@ -3,7 +3,10 @@ tests/test_gpu_soak.py (the driver's GPU suite runs 600 + a few large ones) and 
 builder's longer campaigns): random n / split / bands, nk 2..11 (12..33: the wide-k tile kernel), sketchsize64 1..156, bbits in {14 (tile
 kernel), 8, 16 (generic kernel)}, multi-cluster random tables in random or contiguous runs, related /
 unrelated data, counts / jaccard / distance / fused-edge modes, neighbours from the tiles, both
-settings of the two [EXT] switches (kernel and oracle flipped together).
+settings of the two [EXT] switches (kernel and oracle flipped together), the three options of the coded copies
+("rank_planes", "rank_short", "rank_fold") and, in half of the bbits 14 self cases, one to three positions planted with a
+count of distinct or of shared values at a threshold of the coded copies' planes (128 | 129 ... 2 048 | 2 049).  A self job
+that fits the coded route runs it once more at the end under every setting of "rank_fold" and "rank_short".
 """
 import os
 
@@ -25,14 +28,56 @@ def reset_options():
     _lib.set_option("chunk_rows", 8 << 20)
     for name, default in (("wide_kpg", 0), ("lds_table", 1), ("ksplit_wide", 215), ("knn_warm", 32), ("knn_cut", 4),
                           ("ksplit_long", 1), ("host_parts", 2), ("host_parts_rows", 16 << 20), ("prefault_threads", 8), ("db_cache", 1),
-                          ("progress", 1), ("host_trace", 0)):
+                          ("progress", 1), ("host_trace", 0), ("rank_planes", 1), ("rank_short", 1), ("rank_fold", 1),
+                          ("sweep_window", 1), ("knn_lane_lists", 0), ("ksplit_scratch_mb", 2048)):
         _lib.set_option(name, default)
     oracle.set_ext(0, 0)
+
+
+RANK_THRESHOLDS = (128, 129, 256, 257, 512, 513, 1024, 1025, 2048, 2049)      # either side of what decides a plane
+
+
+def plant_position(sk, rng, s64, top=False):
+    """One (k, bin) position of bbits = 14 sketches gets a count at a threshold of the coded copies, drawn from those n
+    allows: either d distinct values spread over the samples (D = d), or d - 2 values with exactly two holders and single
+    holders for the rest (E = S + 2 = d, D = n - d + 2).  Values and holders are drawn.  `top`: D one past the largest
+    threshold n allows, i.e. the most planes a population of this size can take."""
+    n, nk = sk.shape[0], sk.shape[1]
+    fit = [d for d in RANK_THRESHOLDS if d <= n]
+    if not fit:
+        return None
+    d = int(rng.choice(fit))
+    shared = bool(rng.integers(0, 2)) and n - 2 * (d - 2) >= 1
+    if top:
+        d, shared = max(x for x in fit if x % 2), False
+    idx = np.arange(n)
+    if shared:
+        idx[:2 * (d - 2)] %= d - 2
+        idx[2 * (d - 2):] -= d - 2
+    else:
+        idx %= d
+    vals = rng.permutation(1 << 14)[idx][rng.permutation(n)].astype(np.uint64)
+    k, blk, bit = int(rng.integers(0, nk)), int(rng.integers(0, s64)), np.uint64(rng.integers(0, 64))
+    for b in range(14):
+        w = sk[:, k, blk * 14 + b]
+        sk[:, k, blk * 14 + b] = (w & ~(np.uint64(1) << bit)) | (((vals >> np.uint64(b)) & np.uint64(1)) << bit)
+    return "%s%d" % ("E" if shared else "D", d)
+
+
+def route_label(kernel):
+    """ppk_last_kernel_name() in short: the k-split forms, the wide-k tile kernel, the coded tile kernel with its planes
+    ("rank 8", "rank 10 fold"), the raw tile kernel, the generic-bbits kernel"""
+    if "rank " in kernel:
+        return "rank %s%s" % (kernel.split("rank ")[1].split(",")[0].rstrip(">"), " fold" if kernel.endswith("fold>") else "")
+    return ("ksplit1" if "k-split fused" in kernel else "ksplit2" if "k-split counts" in kernel else
+            "wide" if kernel.endswith("wide>") else "tile" if "256x32" in kernel else "generic")
 
 
 def soak_case(rng, big=False):
     """Runs one case drawn from `rng`; returns (description, list of mismatch messages)."""
     import torch
+    # draws added after the campaign was committed come from a child stream: `rng` gives every earlier draw as before
+    extra = np.random.Generator(np.random.PCG64(rng.bit_generator.seed_seq.spawn(1)[0]))
     bbits = int(rng.choice([14, 14, 14, 8, 16]))
     s64 = int(rng.choice([1, 2, 3, 16, 16, 16, 5, 40, 64, 156]))      # (32 and up: the long-sketch rule, k-split at any size)
     if os.environ.get("SOAK_KSPLIT"):      # the hand-over campaign: only shapes the one-launch k-split path takes
@@ -79,6 +124,10 @@ def soak_case(rng, big=False):
     _lib.set_option("prefault_threads", int(rng.choice([8, 8, 0, 3])))
     _lib.set_option("db_cache", int(rng.integers(0, 4) != 0))
     _lib.set_option("progress", int(rng.integers(0, 4) != 0))
+    # the coded copies of a bbits = 14 database whose self job runs whole tiles (same bits either way)
+    _lib.set_option("rank_planes", int(extra.choice([1, 1, 1, 0])))
+    _lib.set_option("rank_short", int(extra.choice([1, 1, 0])))
+    _lib.set_option("rank_fold", int(extra.choice([1, 1, 0, 2])))
     # a quarter of the cases run as a very large job would: a few tiles per launch, a short neighbour-candidate
     # list, small pieces in the fused host call
     tiny = rng.integers(0, 4) == 0
@@ -99,6 +148,9 @@ def soak_case(rng, big=False):
         clu = np.sort(clu)          # contiguous runs: whole tiles with one cluster pair (the LDS-table epilogue)
     use_tbl = bool(rng.integers(0, 4))
     nr = int(rng.integers(1, n)) if n > 2 and rng.integers(0, 2) else n
+    planted = []
+    if bbits == 14 and nr == n and extra.integers(0, 2):
+        planted = [plant_position(sk, extra, s64, top=i == 0) for i in range(int(extra.integers(1, 4)))]
     ref, qry = sk[:nr], (sk[nr:] if nr < n else None)
     rclu, qclu = clu[:nr], (clu[nr:] if nr < n else None)
     kw = dict(random_table=tbl if use_tbl else None, ref_clusters=rclu if use_tbl else None,
@@ -119,9 +171,7 @@ def soak_case(rng, big=False):
         if not np.array_equal(c, oracle.match_counts(ref, qry, s64, bbits, threads=8)):
             msgs.append("counts differ")
         got, gf = pp_sketchlib.query_arrays(ref, qry, kmers, s64, bbits, **kw)
-        route = _lib.lib().ppk_last_kernel_name().decode()
-        route = ("ksplit1" if "k-split fused" in route else "ksplit2" if "k-split counts" in route else
-                 "wide" if route.endswith("wide>") else "tile" if "256x32" in route else "generic")
+        route = route_label(_lib.lib().ppk_last_kernel_name().decode())
         trace("dist done")
         want, wf = oracle.query(ref, qry, kmers, s64, bbits, **okw)
         err = float(np.abs(got - want).max(initial=0))
@@ -202,12 +252,35 @@ def soak_case(rng, big=False):
             if not (np.array_equal(gi, np.repeat(np.arange(nr + nq), knn)) and np.array_equal(gj, wj.ravel())
                     and np.array_equal(gd, wd.ravel())):
                 msgs.append("ref x query kNN from tiles differs (k=%d col=%d)" % (knn, col))
+        # the coded copies, whatever route the case's own options gave its jobs: a self job whose counts fit 64 bits runs
+        # whole tiles with the k-split path off, on a database created under each "rank_fold" and launched under both
+        # "rank_short" (the three large cases run s64 = 16 alone, where the directed tests sit)
+        coded = set()
+        if qry is None and not big and bbits == 14 and nr > 1 and nk * cnt_bits_k <= 64 and _lib.get_option("rank_planes"):
+            saved = {name: _lib.get_option(name) for name in ("ksplit", "ksplit_long", "wide_kpg", "rank_fold", "rank_short")}
+            for name in ("ksplit", "ksplit_long", "wide_kpg"):
+                _lib.set_option(name, 0)
+            for fold in (0, 1, 2):
+                _lib.set_option("rank_fold", fold)
+                dbc = engine.SketchDB(ref, s64, bbits, clusters=rclu if use_tbl else None)
+                for short in (1, 0):
+                    _lib.set_option("rank_short", short)
+                    cd = engine.dist(dbc, None, kmers, t_tbl, random_correct=use_tbl)[0].cpu().numpy()
+                    coded.add(route_label(_lib.lib().ppk_last_kernel_name().decode()))
+                    if not np.abs(cd - want).max(initial=0) <= 1e-6:
+                        msgs.append("coded self job differs (rank_fold %d rank_short %d)" % (fold, short))
+                dbc.close()
+            for name, value in saved.items():
+                _lib.set_option(name, value)
+            route += " +" + "/".join(sorted(coded))
         db.close()
         if dbq is not None:
             dbq.close()
     except Exception as e:  # noqa: BLE001
         msgs.append("EXCEPTION %r" % (e,))
     desc = ("bbits=%2d s64=%2d nk=%d n=%4d nr=%4d clu=%d tbl=%d related=%d ext=%d%d tiny=%d pad=%d %s"
+            " rank_planes=%d rank_short=%d rank_fold=%d planted=%s"
             % (bbits, s64, nk, n, nr, n_clu, use_tbl, related, ext[0], ext[1], int(tiny), _lib.get_option("ks_grid_pad"),
-               route))
+               route, _lib.get_option("rank_planes"), _lib.get_option("rank_short"), _lib.get_option("rank_fold"),
+               ",".join(x for x in planted if x) or "-"))
     return desc, msgs

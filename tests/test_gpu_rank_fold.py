@@ -18,6 +18,7 @@ import torch
 
 from oracle import oracle
 from poppunk_amd import engine, synth
+from rank_model import fold_planes_of, n_distinct, n_shared, shared_mask, unslice
 
 pytestmark = pytest.mark.gpu
 
@@ -26,59 +27,8 @@ TOL = 1e-6          # tests/test_gpu_dist.py: distances against the CPU oracle
 K, BLK, BIT = 2, 5, 37      # the position the small cases overwrite
 
 
-def unslice(sk, bbits=14):
-    """bit-sliced words [n, nk, s64 * bbits] -> bin values [n, nk, 64 * s64]"""
-    n, nk, words = sk.shape
-    s64 = words // bbits
-    bits = np.unpackbits(np.ascontiguousarray(sk).view(np.uint8).reshape(n, nk, s64, bbits, 8), axis=-1, bitorder="little")
-    vals = np.zeros((n, nk, s64, 64), dtype=np.uint16)
-    for b in range(bbits):
-        vals |= bits[:, :, :, b].astype(np.uint16) << b
-    return vals.reshape(n, nk, 64 * s64)
-
-
 def random_bins(n, seed):
     return np.random.Generator(np.random.PCG64(seed)).integers(0, 1 << 14, size=(n, 5, 1024), dtype=np.uint16)
-
-
-def n_distinct(a):
-    s = np.sort(a, axis=0)
-    return 1 + (s[1:] != s[:-1]).sum(axis=0)
-
-
-def n_shared(bins):
-    """S per position: the values at least two samples hold there (runs of equal values in the sorted column)"""
-    s = np.sort(bins, axis=0)
-    eq = s[1:] == s[:-1]
-    starts = eq.copy()
-    starts[1:] &= ~eq[:-1]
-    return starts.sum(axis=0)
-
-
-def shared_mask(bins):
-    """per sample and position: does another sample hold the same value there"""
-    order = np.argsort(bins, axis=0, kind="stable")
-    s = np.take_along_axis(bins, order, axis=0)
-    eq = s[1:] == s[:-1]
-    m = np.zeros(s.shape, dtype=bool)
-    m[1:] |= eq
-    m[:-1] |= eq
-    out = np.empty_like(m)
-    np.put_along_axis(out, order, m, axis=0)
-    return out
-
-
-def planes_for(codes):
-    return 8 if codes <= 256 else 10 if codes <= 1024 else 12 if codes <= 4096 else 0
-
-
-def fold_planes_of(bins):
-    """what fold_planes and fold_block_planes() must say: E = S + 2 per position, its maximum per 64-bin block and over
-    all; P from the largest, P - 1 in the blocks whose E <= 2^(P-1)"""
-    e = n_shared(bins) + 2
-    e = e.reshape(e.shape[0], -1, 64).max(axis=2)
-    p = planes_for(int(e.max()))
-    return p, np.where(e <= (1 << (p - 1)), p - 1, p).astype(np.uint8)
 
 
 def set_position(sk, vals, k=K, blk=BLK, bit=BIT):

@@ -17,32 +17,12 @@ import torch
 
 from oracle import oracle
 from poppunk_amd import engine, synth
+from rank_model import distinct_max, planes_for, unslice
 
 pytestmark = pytest.mark.gpu
 
 KMERS = np.asarray(synth.DEFAULT_KMERS, dtype=np.int32)
 TOL = 1e-6          # tests/test_gpu_dist.py: distances against the CPU oracle
-
-
-def unslice(sk, bbits=14):
-    """bit-sliced words [n, nk, s64 * bbits] -> bin values [n, nk, 64 * s64] (inverse of synth.bitslice)"""
-    n, nk, words = sk.shape
-    s64 = words // bbits
-    bits = np.unpackbits(np.ascontiguousarray(sk).view(np.uint8).reshape(n, nk, s64, bbits, 8), axis=-1, bitorder="little")
-    vals = np.zeros((n, nk, s64, 64), dtype=np.uint16)
-    for b in range(bbits):
-        vals |= bits[:, :, :, b].astype(np.uint16) << b
-    return vals.reshape(n, nk, 64 * s64)
-
-
-def distinct_max(bins):
-    """D: the most distinct values any (k, bin) position holds over the samples"""
-    s = np.sort(bins, axis=0)
-    return int((1 + (s[1:] != s[:-1]).sum(axis=0)).max())
-
-
-def planes_for(d):
-    return 8 if d <= 256 else 10 if d <= 1024 else 12 if d <= 4096 else 0
 
 
 def random_bins(n, seed):

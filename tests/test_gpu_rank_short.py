@@ -19,56 +19,13 @@ import torch
 
 from oracle import oracle
 from poppunk_amd import engine, synth
+from rank_model import block_d, d_after, overwrite, planes_of, unslice
 
 pytestmark = pytest.mark.gpu
 
 KMERS = np.asarray(synth.DEFAULT_KMERS, dtype=np.int32)
 TOL = 1e-6          # tests/test_gpu_dist.py: distances against the CPU oracle
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bgmm_assign.npz")
-
-
-def unslice(sk, bbits=14):
-    """bit-sliced words [n, nk, s64 * bbits] -> bin values [n, nk, 64 * s64]"""
-    n, nk, words = sk.shape
-    s64 = words // bbits
-    bits = np.unpackbits(np.ascontiguousarray(sk).view(np.uint8).reshape(n, nk, s64, bbits, 8), axis=-1, bitorder="little")
-    vals = np.zeros((n, nk, s64, 64), dtype=np.uint16)
-    for b in range(bbits):
-        vals |= bits[:, :, :, b].astype(np.uint16) << b
-    return vals.reshape(n, nk, 64 * s64)
-
-
-def block_d(bins):
-    """bin values [n, nk, 64 * s64] -> the most distinct values any position of each (k, 64-bin block) holds"""
-    s = np.sort(bins, axis=0)
-    d = 1 + (s[1:] != s[:-1]).sum(axis=0)
-    return d.reshape(d.shape[0], -1, 64).max(axis=2)
-
-
-def planes_of(d):
-    """what rank_block_planes() must say: per-block D -> P from the largest, P - 1 where D <= 2^(P-1)"""
-    top = int(d.max())
-    p = 8 if top <= 256 else 10 if top <= 1024 else 12
-    return p, np.where(d <= (1 << (p - 1)), p - 1, p).astype(np.uint8)
-
-
-def overwrite(sk, k, blk, bit, d):
-    """position (k, 64 * blk + bit) gets exactly d distinct 14-bit values (as test_thresholds_of_d does)"""
-    vals = (np.arange(len(sk)) % d).astype(np.uint64) * np.uint64(3) + np.uint64(1)
-    assert vals.max() < (1 << 14) and len(np.unique(vals)) == d
-    bit = np.uint64(bit)
-    for b in range(14):
-        w = sk[:, k, blk * 14 + b]
-        sk[:, k, blk * 14 + b] = (w & ~(np.uint64(1) << bit)) | (((vals >> np.uint64(b)) & np.uint64(1)) << bit)
-
-
-def d_after(sk, base_d, blocks):
-    """per-block D of a population whose D was base_d before the blocks in `blocks` were overwritten: those blocks are
-    recomputed from the sketches' unsliced bins, the others have not changed"""
-    d = base_d.copy()
-    for k, blk in blocks:
-        d[k, blk] = block_d(unslice(sk[:, k:k + 1, blk * 14:(blk + 1) * 14]))[0, 0]
-    return d
 
 
 @pytest.fixture(scope="module")
