@@ -17,15 +17,9 @@
 
 #include "ppk_internal.h"
 
-// launchers defined in ppk_dist.hip
+// launcher defined in ppk_dist.hip
 int ppk_launch_transpose(const uint64_t *d_in, uint64_t *d_out, size_t n, size_t cols, size_t npad,
                          hipStream_t s);
-int ppk_launch_dist(const ppk_db *ref, const ppk_db *qry_or_null, const int32_t *kmers,
-                    const float *d_rtab, size_t n_clu, int flags, size_t q_begin, size_t q_end,
-                    void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, int slope,
-                    float x_max, float y_max, float scale_x, float scale_y, int inclusive,
-                    double *d_lut, hipStream_t s, const int *knn_args = nullptr, bool lut_ready = false,
-                    const ppk_bgmm *d_bgmm = nullptr);
 
 // ---- errors ---------------------------------------------------------------
 static thread_local std::string g_err;
@@ -923,8 +917,11 @@ extern "C" int ppk_dist_dev(const ppk_db *ref, const ppk_db *qry, const int32_t 
   bool lut_ready = false;
   rc = stage_tables(ref, kmers, random_tbl, n_clu, flags, s, &d_lut, &d_rtab, &lut_ready);
   if (rc != PPK_OK) return rc;
-  return ppk_launch_dist(ref, qry, kmers, d_rtab, d_rtab ? n_clu : 1, flags, q_begin, q_end, d_out,
-                         d_n_failed, nullptr, 2, 0.f, 0.f, 1.f, 1.f, 1, d_lut, s, nullptr, lut_ready);
+  DistJob job;
+  job.ref = ref, job.qry = qry, job.kmers = kmers, job.d_rtab = d_rtab, job.n_clu = d_rtab ? n_clu : 1, job.flags = flags;
+  job.q_begin = q_begin, job.q_end = q_end, job.d_out = d_out, job.d_n_failed = d_n_failed;
+  job.d_lut = d_lut, job.lut_ready = lut_ready, job.s = s;
+  return ppk_launch_dist(job);
 }
 
 // The fused edge list of a band: the line boundary (model == NULL) or the label test of a BGMM model
@@ -950,6 +947,10 @@ static int dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *k
   bool lut_ready = false;
   rc = stage_tables(ref, kmers, random_tbl, n_clu, flags, s, &d_lut, &d_rtab, &lut_ready);
   if (rc != PPK_OK) return rc;
+  DistJob job;
+  job.ref = ref, job.qry = qry, job.kmers = kmers, job.d_rtab = d_rtab, job.n_clu = d_rtab ? n_clu : 1, job.flags = flags;
+  job.d_n_failed = d_n_failed, job.d_lut = d_lut, job.s = s;
+  job.slope = slope, job.x_max = x_max, job.y_max = y_max, job.scale_x = scale_x, job.scale_y = scale_y, job.inclusive = inclusive;
   {
     // sketches the tile kernels cannot fit (ppk_unfused: bbits other than 14 with more than 128 count bits --
     // nothing PopPUNK writes): distances (pre-divided by scale) go to scratch and the row-linear edge kernel
@@ -962,8 +963,8 @@ static int dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *k
       void *d_dist = nullptr;
       rc = scratch_get(ref->device, SLOT_ITER_B, rows * 8 + 8, &d_dist);
       if (rc != PPK_OK) return rc;
-      rc = ppk_launch_dist(ref, qry, kmers, d_rtab, d_rtab ? n_clu : 1, flags, 0, nq, d_dist, d_n_failed,
-                           nullptr, slope, x_max, y_max, scale_x, scale_y, inclusive, d_lut, s);
+      job.q_begin = 0, job.q_end = nq, job.d_out = d_dist;
+      rc = ppk_launch_dist(job);
       if (rc != PPK_OK) return rc;
       RowTest t = {};
       t.kind = model ? RowTest::BGMM : RowTest::LINE;
@@ -982,9 +983,9 @@ static int dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *k
   const ppk_bgmm *d_model = nullptr;
   if (model && (rc = ppk_bgmm_to_device(ref->device, *model, &d_model, s)) != PPK_OK) return rc;
   PPK_HIP(hipMemsetAsync(d_mask, 0, n_words * sizeof(uint64_t), s));
-  rc = ppk_launch_dist(ref, qry, kmers, d_rtab, d_rtab ? n_clu : 1, flags, q_begin, q_end, nullptr,
-                       d_n_failed, static_cast<uint64_t *>(d_mask), slope, x_max, y_max, scale_x,
-                       scale_y, inclusive, d_lut, s, nullptr, lut_ready, d_model);
+  job.q_begin = q_begin, job.q_end = q_end, job.d_mask = static_cast<uint64_t *>(d_mask);
+  job.lut_ready = lut_ready, job.d_bgmm = d_model;
+  rc = ppk_launch_dist(job);
   if (rc != PPK_OK) return rc;
   EdgeGeom g = {};
   g.layout = qry ? EDGE_TILED_NONSELF : EDGE_TILED_SELF;
@@ -1181,15 +1182,18 @@ int ppk_knn_band_dev(const ppk_db *db, const ppk_db *qry, const int32_t *kmers, 
   if (warm && warm < cur) cur = warm;
   if (big && rows_that_fit(0) < cur && q_end - q_begin > rows_that_fit(0)) cur = rows_that_fit(0);
   const bool staged = cur < q_end - q_begin && cur < piece;      // the job opens with a short piece and a cut
-  bool tables_built = lut_ready;
+  DistJob job;
+  job.ref = db, job.qry = qry, job.kmers = kmers, job.d_rtab = d_rtab, job.n_clu = d_rtab ? n_clu : 1, job.flags = flags;
+  job.d_mask = static_cast<uint64_t *>(d_state), job.knn_args = knn_args;
+  job.d_lut = d_lut, job.lut_ready = lut_ready, job.s = s;
   for (size_t lo = q_begin; lo < q_end && n > 1;) {
     const size_t this_piece = cur;
     const size_t hi = lo + this_piece < q_end ? lo + this_piece : q_end;
     const unsigned long long before = count;
-    rc = ppk_launch_dist(db, qry, kmers, d_rtab, d_rtab ? n_clu : 1, flags, lo, hi, d_cand, nullptr,
-                         static_cast<uint64_t *>(d_state), 2, 0.f, 0.f, 1.f, 1.f, 1, d_lut, s, knn_args, tables_built);
+    job.q_begin = lo, job.q_end = hi, job.d_out = d_cand;      // (`room` may have moved the list)
+    rc = ppk_launch_dist(job);
     if (rc != PPK_OK) return rc;
-    tables_built = true;
+    job.lut_ready = true;
     rc = read_count(&count);
     if (rc != PPK_OK) return rc;
     if (ppk_config().host_trace.load())
@@ -1319,8 +1323,11 @@ extern "C" int ppk_knn_candidates_dev(const ppk_db *db, const int32_t *kmers, co
   rc = ppk_launch_knn_state_init(d_state, n, cap, vals_off, 1, s);
   if (rc != PPK_OK) return rc;
   const int knn_args[2] = {knn, dist_col};
-  rc = ppk_launch_dist(db, nullptr, kmers, d_rtab, d_rtab ? n_clu : 1, flags, q_begin, q_end, d_keys, nullptr,
-                       static_cast<uint64_t *>(d_state), 2, 0.f, 0.f, 1.f, 1.f, 1, d_lut, s, knn_args, lut_ready);
+  DistJob job;
+  job.ref = db, job.kmers = kmers, job.d_rtab = d_rtab, job.n_clu = d_rtab ? n_clu : 1, job.flags = flags;
+  job.q_begin = q_begin, job.q_end = q_end, job.d_out = d_keys, job.d_mask = static_cast<uint64_t *>(d_state);
+  job.knn_args = knn_args, job.d_lut = d_lut, job.lut_ready = lut_ready, job.s = s;
+  rc = ppk_launch_dist(job);
   if (rc != PPK_OK) return rc;
   unsigned long long count = 0;
   rc = read_device_word(db->device, static_cast<const unsigned long long *>(d_state), &count, s);

@@ -1228,39 +1228,70 @@ regress_packed_kernel(const uint32_t *__restrict__ counts, size_t n_rows, const 
 
 // ---- host-side launch ------------------------------------------------------
 
+// bits of one packed count: the fewest that hold 0 .. 64 * s64
+static int count_bits(size_t s64) {
+  int bits = 1;
+  while (((size_t)1 << bits) <= s64 * 64) ++bits;
+  return bits;
+}
+// the options the route choice reads
+static PpkRouteKnobs route_knobs() {
+  const PpkConfig &c = ppk_config();
+  return {c.ksplit.load(), c.ksplit_wide.load(), c.ksplit_long.load(), c.ksplit_fused.load(), c.ksplit_slices.load(),
+          c.wide_kpg.load(), (size_t)c.ksplit_scratch_mb.load() << 20};
+}
+// distance rows of the band [p.q_begin, p.q_end) (p.row_base: the rows before it)
+static size_t band_rows(const DistParams &p) {
+  return p.self ? (p.q_end * p.n_ref - (p.q_end * (p.q_end + 1)) / 2) - p.row_base : (p.q_end - p.q_begin) * p.n_ref;
+}
+
 namespace {
 
-template <int TQ, int NW, int MODE, typename PackT>
-int launch_variant(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const float *d_rtab,
-                   void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, DistParams &p,
-                   hipStream_t s, const char *name) {
-  constexpr int QT = TQ * NW;
-  p.q_tile0 = p.q_begin / QT;
-  const size_t q_tiles = (p.q_end + QT - 1) / QT - p.q_tile0;
-  if (q_tiles == 0 || p.n_rtiles == 0) return PPK_OK;
-  if (q_tiles > 65535) return ppk_fail(PPK_ERR_ARG, "query band too tall for one launch");
-  dim3 grid((unsigned)p.n_rtiles, (unsigned)q_tiles);
-  // cluster ids only matter when a multi-cluster random-match table is in use
-  const bool use_clu = p.random_correct && p.n_clu > 1;
-  const uint16_t *rclu = use_clu ? ref->d_clu : nullptr;
-  const uint16_t *qclu = use_clu ? qry->d_clu : nullptr;
+// The pointer arguments of the pair-tile kernels, in their order (DistParams follows them)
+struct DistArgs {
+  const uint64_t *sk_r, *sk_q;
+  const double *lut;
+  const uint16_t *rclu, *qclu;      // cluster ids: only where a multi-cluster random-match table is in use
+  const float *rtab;
+  void *out;
+  unsigned long long *n_failed;
+  uint64_t *mask;
+};
+
+// One launch of a pair-tile kernel, timed under `name` while the profiler is on.  (Q: dist_kernel reads its query words
+// as dwords.)
+template <typename Q, typename... Tail>
+int launch_kernel(void (*kernel)(const uint64_t *, const Q *, Tail...), dim3 grid, dim3 block, const char *name,
+                  const DistArgs &a, const DistParams &p, hipStream_t s) {
   ppk_set_kernel_name(name);
   ppk_prof_begin(s);
-  hipLaunchKernelGGL((dist_kernel<TQ, NW, MODE, PackT>), grid, dim3(NW * 64), 0, s,
-                     ref->d_skT, reinterpret_cast<const uint32_t *>(qry->d_skT), d_lut, rclu, qclu,
-                     d_rtab, d_out, d_n_failed, d_mask, p);
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, a.sk_r, reinterpret_cast<const Q *>(a.sk_q), a.lut, a.rclu, a.qclu,
+                     a.rtab, a.out, a.n_failed, a.mask, p);
   ppk_prof_end(s);
   PPK_HIP(hipGetLastError());
   return PPK_OK;
 }
 
-template <int NW, int MODE, int W, bool WIDE = false>
-int launch_v2(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const float *d_rtab,
-              void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, DistParams &p,
-              hipStream_t s) {
-  constexpr int V2_QT = NW * V2_TQ;
-  p.q_tile0 = p.q_begin / V2_QT;
-  const size_t q_tiles = (p.q_end + V2_QT - 1) / V2_QT - p.q_tile0;
+template <int TQ, int NW, int MODE, typename PackT>
+int launch_variant(const DistArgs &a, DistParams &p, hipStream_t s, const char *name) {
+  constexpr int QT = TQ * NW;
+  p.q_tile0 = p.q_begin / QT;
+  const size_t q_tiles = (p.q_end + QT - 1) / QT - p.q_tile0;
+  if (q_tiles == 0 || p.n_rtiles == 0) return PPK_OK;
+  if (q_tiles > 65535) return ppk_fail(PPK_ERR_ARG, "query band too tall for one launch");
+  return launch_kernel(&dist_kernel<TQ, NW, MODE, PackT>, dim3((unsigned)p.n_rtiles, (unsigned)q_tiles), dim3(NW * 64),
+                       name, a, p, s);
+}
+
+// The grid of the 256 x 32 tile kernels over the band: fills p's grid fields (q_tile0, r_limit, the strip, r_tiles /
+// q_tiles, xcd_*, n_strip_pad, tri_*, n_tiles, tiles_per_xcd) and gives the workgroups along x in *n_blocks_out (0: the
+// band holds no tile).  nw: wavefronts per workgroup; strips: the mode has strip tiles; one_order: an instantiation
+// without the A/B tile orders.
+int plan_grid(DistParams &p, int nw, bool strips, bool one_order, const PpkGeometry &geo, size_t *n_blocks_out) {
+  *n_blocks_out = 0;
+  const int qt = nw * V2_TQ;
+  p.q_tile0 = p.q_begin / qt;
+  const size_t q_tiles = (p.q_end + qt - 1) / qt - p.q_tile0;
   size_t r_tiles = (p.n_ref + V2_RT - 1) / V2_RT;
   p.r_limit = p.n_ref;
   p.n_strip = 0;
@@ -1274,7 +1305,7 @@ int launch_v2(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const f
   // sit on the query axis against all smaller samples on the lane axis, writing the same
   // condensed rows; the strip tiles lead the same grid.
   const size_t rem = p.n_ref % V2_RT;
-  if constexpr (MODE == MODE_DIST || ppk_is_mask(MODE)) {
+  if (strips) {
     bool split = p.self && rem != 0 && rem <= 224 && p.n_ref > V2_RT;
 #ifdef PPK_EXPERIMENTS
     if (ppk_config().strip.load() == 0) split = false;
@@ -1286,23 +1317,21 @@ int launch_v2(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const f
       p.strip_rt0 = (unsigned)(p.q_begin / V2_RT);          // lane tiles intersecting the band's rows
       const size_t rt_hi = ((p.q_end < p.n_ref ? p.q_end : p.n_ref) + V2_RT - 1) / V2_RT;
       p.strip_r_tiles = (unsigned)(rt_hi - p.strip_rt0);
-      p.n_strip = p.strip_r_tiles * (unsigned)((rem + V2_QT - 1) / V2_QT);
+      p.n_strip = p.strip_r_tiles * (unsigned)((rem + qt - 1) / qt);
     }
   }
   if (q_tiles == 0 || (r_tiles == 0 && p.n_strip == 0)) return PPK_OK;
-  const bool use_clu = p.random_correct && p.n_clu > 1;
   p.r_tiles = (unsigned)(r_tiles ? r_tiles : 1);
   p.q_tiles = (unsigned)(r_tiles ? q_tiles : 0);
   p.xcd_map = 0;      // XCD-contiguous runs
 #ifdef PPK_EXPERIMENTS
   p.xcd_map = (int)ppk_config().map.load();  // A/B of tile orders
 #endif
-  if (p.k_split || WIDE) p.xcd_map = 0;      // (the alternatives exist in the EXP instantiation only)
-  const PpkGeometry &geo = ppk_geometry(ref->device);
+  if (p.k_split || one_order) p.xcd_map = 0;      // (the alternatives exist in the EXP instantiation only)
   const unsigned xcds = 1u << geo.xcd_shift;
   p.xcd_shift = geo.xcd_shift;
   p.n_strip_pad = (p.n_strip + xcds - 1u) & ~(xcds - 1u);
-  p.tri_m = V2_RT / V2_QT;
+  p.tri_m = V2_RT / qt;
   p.tri_c0 = p.tri_m - (int)p.q_tile0;
   const unsigned long long n_tiles64 = r_tiles ? tiles_before64(p.r_tiles, p.self, p.q_tiles, p.tri_m, p.tri_c0) : 0;
   if (n_tiles64 > 0x7ffffff0ull) return ppk_fail(PPK_ERR_ARG, "tile grid too large for one launch: split the query band");
@@ -1314,177 +1343,145 @@ int launch_v2(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const f
   const size_t n_tri = !r_tiles ? 0 : p.xcd_map == 0 ? (size_t)p.tiles_per_xcd * xcds
                                   : p.xcd_map == 1 ? per_xcd * 8 : r_tiles * q_tiles;
   const size_t n_blocks = n_tri + p.n_strip_pad;
-  if (n_blocks * (size_t)(NW * 64) >= ((size_t)1 << 32))
+  if (n_blocks * (size_t)(nw * 64) >= ((size_t)1 << 32))
     return ppk_fail(PPK_ERR_ARG, "internal: tile grid too large for one launch (ppk_launch_dist splits bands before this)");
-  if ((MODE == MODE_DIST || ppk_is_mask(MODE)) && NW == 8 && p.k_split) {
-    // k-split job in one launch: ks_units workgroups per tile, the last one to finish fits it (KS_FUSED in the
-    // kernel).  Scratch: one zero-initialised counter per tile; 32 bytes per (tile, unit, thread) of partial counts.
-    if constexpr (NW == 8 && W == 2 && (MODE == MODE_DIST || ppk_is_mask(MODE))) {
-      void *d_tickets = nullptr, *d_part = nullptr;
-      const size_t ticket_bytes = (n_blocks * 4 + 255) / 256 * 256;
-      int rc = ppk_scratch_get(ref->device, SLOT_TICKETS, ticket_bytes, &d_tickets);
-      if (rc != PPK_OK) return kNoKsplitScratch;
-      rc = ppk_scratch_get(ref->device, SLOT_ITER_A, n_blocks * (size_t)p.ks_units * (NW * 64) * 32 + 256, &d_part);
-      if (rc != PPK_OK) return kNoKsplitScratch;
-      p.ks_part_off = (size_t)(static_cast<char *>(d_part) - static_cast<char *>(d_tickets));
-      p.ks_tickets = static_cast<unsigned *>(d_tickets);
-      ppk_set_kernel_name(WIDE ? "dist_kernel_v2<256x32,lds-dma,k-split fused,fit from parts>" : "dist_kernel_v2<256x32,lds-dma,k-split fused>");
-      ppk_prof_begin(s);
+  *n_blocks_out = n_blocks;
+  return PPK_OK;
+}
+
+// k-split job in one launch: ks_units workgroups per tile, the last one to finish fits it (KS_FUSED in the
+// kernel).  Scratch: one zero-initialised counter per tile; 32 bytes per (tile, unit, thread) of partial counts.
+template <int NW, int MODE, bool WIDE>
+int launch_ksplit_fused(int dev, const DistArgs &a, DistParams &p, size_t n_blocks, hipStream_t s) {
+  void *d_tickets = nullptr, *d_part = nullptr;
+  const size_t ticket_bytes = (n_blocks * 4 + 255) / 256 * 256;
+  int rc = ppk_scratch_get(dev, SLOT_TICKETS, ticket_bytes, &d_tickets);
+  if (rc != PPK_OK) return kNoKsplitScratch;
+  rc = ppk_scratch_get(dev, SLOT_ITER_A, n_blocks * (size_t)p.ks_units * (NW * 64) * 32 + 256, &d_part);
+  if (rc != PPK_OK) return kNoKsplitScratch;
+  p.ks_part_off = (size_t)(static_cast<char *>(d_part) - static_cast<char *>(d_tickets));
+  p.ks_tickets = static_cast<unsigned *>(d_tickets);
+  const char *name = WIDE ? "dist_kernel_v2<256x32,lds-dma,k-split fused,fit from parts>" : "dist_kernel_v2<256x32,lds-dma,k-split fused>";
 #ifdef PPK_EXPERIMENTS
-      if constexpr (!WIDE && MODE == MODE_DIST) {
-        if (p.ablate) {
-          hipLaunchKernelGGL((dist_kernel_v2<NW, MODE, W, true, false, true>), dim3((unsigned)n_blocks, p.ks_units),
-                             dim3(NW * 64), 0, s, ref->d_skT, qry->d_skT, d_lut, use_clu ? ref->d_clu : nullptr,
-                             use_clu ? qry->d_clu : nullptr, d_rtab, d_out, d_n_failed, d_mask, p);
-          ppk_prof_end(s);
-          PPK_HIP(hipGetLastError());
-          return PPK_OK;
-        }
-      }
+  if constexpr (!WIDE && MODE == MODE_DIST)
+    if (p.ablate)
+      return launch_kernel(&dist_kernel_v2<NW, MODE, 2, true, false, true>, dim3((unsigned)n_blocks, p.ks_units),
+                           dim3(NW * 64), name, a, p, s);
 #endif
-      // Option "ks_grid_pad": one more (empty) column of workgroups.  gridDim.x is otherwise a multiple of 8 and
-      // workgroups go to XCD (linear id mod 8), so the ks_units workgroups of a tile all run on ONE XCD and the
-      // hand-over below never crosses an L2; with an odd width unit y of tile x runs on XCD (x + y) mod 8
-      // (tools/ubench_grid_xcd.hip).  The extra workgroups return at once (their j is past tiles_per_xcd).
-      const unsigned grid_x = (unsigned)n_blocks + (ppk_config().ks_grid_pad.load() != 0 ? 1u : 0u);
-      hipLaunchKernelGGL((dist_kernel_v2<NW, MODE, W, true, WIDE>), dim3(grid_x, p.ks_units),
-                         dim3(NW * 64), 0, s, ref->d_skT, qry->d_skT, d_lut,
-                         use_clu ? ref->d_clu : nullptr, use_clu ? qry->d_clu : nullptr, d_rtab, d_out,
-                         d_n_failed, d_mask, p);
-      ppk_prof_end(s);
-      PPK_HIP(hipGetLastError());
-      return PPK_OK;
-    }
+  // Option "ks_grid_pad": one more (empty) column of workgroups.  gridDim.x is otherwise a multiple of 8 and
+  // workgroups go to XCD (linear id mod 8), so the ks_units workgroups of a tile all run on ONE XCD and the
+  // hand-over below never crosses an L2; with an odd width unit y of tile x runs on XCD (x + y) mod 8
+  // (tools/ubench_grid_xcd.hip).  The extra workgroups return at once (their j is past tiles_per_xcd).
+  const unsigned grid_x = (unsigned)n_blocks + (ppk_config().ks_grid_pad.load() != 0 ? 1u : 0u);
+  return launch_kernel(&dist_kernel_v2<NW, MODE, 2, true, WIDE>, dim3(grid_x, p.ks_units), dim3(NW * 64), name, a, p, s);
+}
+
+// More than 128 count bits per pair: the four-dword register windowed over the k list, full windows parked in
+// the spill-slot pool (PackWide): a bitmap page + nslots x groups x 128 KB, kept per device
+template <int NW, int MODE>
+int launch_wide(int dev, const PpkGeometry &geo, const DistArgs &a, DistParams &p, size_t n_blocks, hipStream_t s) {
+  p.wide_kpg = 128 / p.cnt_bits;
+  if (const long long force = ppk_config().wide_kpg.load(); force > 0 && force < p.wide_kpg) p.wide_kpg = (int)force;
+  p.wide_groups = (p.nk + p.wide_kpg - 1) / p.wide_kpg;
+  // spill slots: a power of two, at least twice the workgroups the device holds at once
+  p.wide_nslots = 64;
+  while (p.wide_nslots < 2u * (unsigned)geo.tile_slots) p.wide_nslots *= 2;
+  void *pool = nullptr;
+  const size_t pool_bytes = 4096 + (size_t)p.wide_nslots * (size_t)p.wide_groups * WIDE_GROUP_U64 * 8;
+  int rc = ppk_scratch_get(dev, SLOT_WIDE, pool_bytes, &pool);
+  if (rc != PPK_OK) return rc;
+  p.wide_bitmap = static_cast<unsigned *>(pool);
+  p.wide_slots = reinterpret_cast<unsigned long long *>(static_cast<char *>(pool) + 4096);
+  // every launch leaves the bitmap at zero -- unless one was aborted in a process that lives on: a bit left set
+  // would make a later workgroup wait for a slot nobody returns.  The pool is idle here (a scratch slot last used
+  // on another stream has been waited for), so the page is simply cleared again.
+  PPK_HIP(hipMemsetAsync(pool, 0, 4096, s));
+  return launch_kernel(&dist_kernel_v2<NW, MODE, 4, false, true>, dim3((unsigned)n_blocks), dim3(NW * 64),
+                       "dist_kernel_v2<256x32,lds-dma,wide>", a, p, s);
+}
+
+// A self job on a rank-coded database (ppk_db_create) compares the codes: 8, 10 or 12 planes per block instead of
+// 14, the same counts.  (ref x query jobs would need one code for two databases; k-split jobs have their own kernels.)
+// The folded pair (d_foldR / d_foldQ) serves the triangular job alone: every pair it compares is two different
+// samples, one from each copy.  A rectangular job of a handle against itself has the pairs (r, r), where a value
+// with a single holder must match itself: it reads the injective copy if there is one, else the raw planes.
+// Returns the planes of the copy this band reads (0: the raw planes) and whether that is the folded pair.
+int coded_planes(const ppk_db *ref, const ppk_db *qry, const DistParams &p, bool *fold) {
+  const bool coded = (p.self || qry == ref) && !p.k_split && ppk_config().rank_planes.load() != 0;
+  *fold = coded && p.self && ref->fold_planes != 0 && ppk_config().rank_fold.load() != 0;
+  return *fold ? ref->fold_planes : coded && ref->d_skR ? ref->rank_planes : 0;
+}
+template <int MODE>
+int launch_rank(const ppk_db *ref, int planes, bool fold, DistArgs a, DistParams &p, size_t n_blocks, hipStream_t s) {
+  a.sk_r = fold ? ref->d_foldR : ref->d_skR;
+  a.sk_q = fold ? ref->d_foldQ : ref->d_skR;
+  // the blocks that compare one plane fewer (option "rank_short", read here: one database runs either way)
+  const unsigned *flags = fold ? ref->fold_short : ref->rank_short;
+  const bool use_short = ppk_config().rank_short.load() != 0;
+  for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.rank_short[k] = use_short ? flags[k] : 0u;
+  const auto kernel = planes == 12   ? &dist_kernel_v2_rank<12, MODE>
+                      : planes == 10 ? &dist_kernel_v2_rank<10, MODE>
+                                     : &dist_kernel_v2_rank<8, MODE>;
+  const std::string name = "dist_kernel_v2<256x32,lds-dma,rank " + std::to_string(planes) + (fold ? ",fold>" : ">");
+  return launch_kernel(kernel, dim3((unsigned)n_blocks), dim3(8 * 64), name.c_str(), a, p, s);
+}
+
+// One band through the 256 x 32 tile kernels: the grid, then the variant that p and the instantiation select
+template <int NW, int MODE, int W, bool WIDE = false>
+int launch_v2(const ppk_db *ref, const ppk_db *qry, const DistArgs &a, DistParams &p, hipStream_t s) {
+  constexpr bool kFits = MODE == MODE_DIST || ppk_is_mask(MODE);      // the modes that fit a pair in the tile's epilogue
+  const PpkGeometry &geo = ppk_geometry(ref->device);
+  size_t n_blocks = 0;
+  const int rc = plan_grid(p, NW, kFits, WIDE, geo, &n_blocks);
+  if (rc != PPK_OK || n_blocks == 0) return rc;
+  if (kFits && NW == 8 && p.k_split) {
+    if constexpr (NW == 8 && W == 2 && kFits) return launch_ksplit_fused<NW, MODE, WIDE>(ref->device, a, p, n_blocks, s);
     return ppk_fail(PPK_ERR_STATE, "internal: no k-split instantiation for this mode");
   }
   if constexpr (WIDE && W != 4) {
     return ppk_fail(PPK_ERR_STATE, "internal: the fit-from-parts instantiation is a k-split kernel");
   } else if constexpr (WIDE) {
-    // the spill-slot pool (PackWide): a bitmap page + nslots x groups x 128 KB, kept per device
-    p.wide_kpg = 128 / p.cnt_bits;
-    if (const long long force = ppk_config().wide_kpg.load(); force > 0 && force < p.wide_kpg) p.wide_kpg = (int)force;
-    p.wide_groups = (p.nk + p.wide_kpg - 1) / p.wide_kpg;
-    // spill slots: a power of two, at least twice the workgroups the device holds at once
-    p.wide_nslots = 64;
-    while (p.wide_nslots < 2u * (unsigned)geo.tile_slots) p.wide_nslots *= 2;
-    void *pool = nullptr;
-    const size_t pool_bytes = 4096 + (size_t)p.wide_nslots * (size_t)p.wide_groups * WIDE_GROUP_U64 * 8;
-    int rc = ppk_scratch_get(ref->device, SLOT_WIDE, pool_bytes, &pool);
-    if (rc != PPK_OK) return rc;
-    p.wide_bitmap = static_cast<unsigned *>(pool);
-    p.wide_slots = reinterpret_cast<unsigned long long *>(static_cast<char *>(pool) + 4096);
-    // every launch leaves the bitmap at zero -- unless one was aborted in a process that lives on: a bit left set
-    // would make a later workgroup wait for a slot nobody returns.  The pool is idle here (a scratch slot last used
-    // on another stream has been waited for), so the page is simply cleared again.
-    PPK_HIP(hipMemsetAsync(pool, 0, 4096, s));
-    ppk_set_kernel_name("dist_kernel_v2<256x32,lds-dma,wide>");
-    ppk_prof_begin(s);
-    hipLaunchKernelGGL((dist_kernel_v2<NW, MODE, W, false, true>), dim3((unsigned)n_blocks), dim3(NW * 64), 0, s,
-                       ref->d_skT, qry->d_skT, d_lut, use_clu ? ref->d_clu : nullptr, use_clu ? qry->d_clu : nullptr,
-                       d_rtab, d_out, d_n_failed, d_mask, p);
-    ppk_prof_end(s);
-    PPK_HIP(hipGetLastError());
-    return PPK_OK;
+    return launch_wide<NW, MODE>(ref->device, geo, a, p, n_blocks, s);
   }
+  const dim3 grid((unsigned)n_blocks), block(NW * 64);
 #ifdef PPK_EXPERIMENTS
   // the experiments build (make experiments): `ablate` and the rejected tile orders run their own instantiation
-  if ((p.ablate || p.xcd_map) && !p.k_split) {
-    ppk_set_kernel_name("dist_kernel_v2<256x32,lds-dma,exp>");
-    ppk_prof_begin(s);
-    hipLaunchKernelGGL((dist_kernel_v2<NW, MODE, W, false, false, true>), dim3((unsigned)n_blocks), dim3(NW * 64), 0, s,
-                       ref->d_skT, qry->d_skT, d_lut, use_clu ? ref->d_clu : nullptr, use_clu ? qry->d_clu : nullptr,
-                       d_rtab, d_out, d_n_failed, d_mask, p);
-    ppk_prof_end(s);
-    PPK_HIP(hipGetLastError());
-    return PPK_OK;
-  }
+  if ((p.ablate || p.xcd_map) && !p.k_split)
+    return launch_kernel(&dist_kernel_v2<NW, MODE, W, false, false, true>, grid, block, "dist_kernel_v2<256x32,lds-dma,exp>", a, p, s);
 #endif
-  if constexpr (NW == 8 && W == 2 && !WIDE && (MODE == MODE_DIST || ppk_is_mask(MODE))) {
-    // A self job on a rank-coded database (ppk_db_create) compares the codes: 8, 10 or 12 planes per block instead of
-    // 14, the same counts.  (ref x query jobs would need one code for two databases; the k-split units returned above.)
-    // The folded pair (d_foldR / d_foldQ) serves the triangular job alone: every pair it compares is two different
-    // samples, one from each copy.  A rectangular job of a handle against itself has the pairs (r, r), where a value
-    // with a single holder must match itself: it reads the injective copy if there is one, else the raw planes.
-    const bool coded = (p.self || qry == ref) && !p.k_split && ppk_config().rank_planes.load() != 0;
-    const bool fold = coded && p.self && ref->fold_planes != 0 && ppk_config().rank_fold.load() != 0;
-    const int pl = fold ? ref->fold_planes : coded && ref->d_skR ? ref->rank_planes : 0;
-    if (pl) {
-      const uint64_t *sk_r = fold ? ref->d_foldR : ref->d_skR, *sk_q = fold ? ref->d_foldQ : ref->d_skR;
-      const unsigned *flags = fold ? ref->fold_short : ref->rank_short;
-      const uint16_t *clu = use_clu ? ref->d_clu : nullptr;
-      const dim3 grid((unsigned)n_blocks), block(NW * 64);
-      if (fold)
-        ppk_set_kernel_name(pl == 12 ? "dist_kernel_v2<256x32,lds-dma,rank 12,fold>" : pl == 10 ? "dist_kernel_v2<256x32,lds-dma,rank 10,fold>"
-                                                                                                : "dist_kernel_v2<256x32,lds-dma,rank 8,fold>");
-      else
-        ppk_set_kernel_name(pl == 12 ? "dist_kernel_v2<256x32,lds-dma,rank 12>" : pl == 10 ? "dist_kernel_v2<256x32,lds-dma,rank 10>"
-                                                                                           : "dist_kernel_v2<256x32,lds-dma,rank 8>");
-      // the blocks that compare one plane fewer (option "rank_short", read here: one database runs either way)
-      const bool use_short = ppk_config().rank_short.load() != 0;
-      for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.rank_short[k] = use_short ? flags[k] : 0u;
-      ppk_prof_begin(s);
-      if (pl == 12)
-        hipLaunchKernelGGL((dist_kernel_v2_rank<12, MODE>), grid, block, 0, s, sk_r, sk_q, d_lut, clu, clu, d_rtab, d_out, d_n_failed, d_mask, p);
-      else if (pl == 10)
-        hipLaunchKernelGGL((dist_kernel_v2_rank<10, MODE>), grid, block, 0, s, sk_r, sk_q, d_lut, clu, clu, d_rtab, d_out, d_n_failed, d_mask, p);
-      else
-        hipLaunchKernelGGL((dist_kernel_v2_rank<8, MODE>), grid, block, 0, s, sk_r, sk_q, d_lut, clu, clu, d_rtab, d_out, d_n_failed, d_mask, p);
-      ppk_prof_end(s);
-      PPK_HIP(hipGetLastError());
-      return PPK_OK;
-    }
+  if constexpr (NW == 8 && W == 2 && !WIDE && kFits) {
+    bool fold = false;
+    if (const int planes = coded_planes(ref, qry, p, &fold)) return launch_rank<MODE>(ref, planes, fold, a, p, n_blocks, s);
   }
-  ppk_set_kernel_name("dist_kernel_v2<256x32,lds-dma>");
-  ppk_prof_begin(s);
-  if (MODE == MODE_COUNTS && NW == 8 && p.k_split) {
-    if constexpr (MODE == MODE_COUNTS && NW == 8)
-      hipLaunchKernelGGL((dist_kernel_v2<NW, MODE, W, true>), dim3((unsigned)n_blocks, (unsigned)p.nk),
-                         dim3(NW * 64), 0, s, ref->d_skT, qry->d_skT, d_lut,
-                         use_clu ? ref->d_clu : nullptr, use_clu ? qry->d_clu : nullptr, d_rtab, d_out,
-                         d_n_failed, d_mask, p);
-  } else {
-    hipLaunchKernelGGL((dist_kernel_v2<NW, MODE, W>), dim3((unsigned)n_blocks),
-                       dim3(NW * 64), 0, s, ref->d_skT, qry->d_skT, d_lut,
-                       use_clu ? ref->d_clu : nullptr, use_clu ? qry->d_clu : nullptr, d_rtab, d_out,
-                       d_n_failed, d_mask, p);
-  }
-  ppk_prof_end(s);
-  PPK_HIP(hipGetLastError());
-  return PPK_OK;
+  // (the counts pass of a two-pass k-split job: one workgroup per (tile, k))
+  if constexpr (MODE == MODE_COUNTS && NW == 8)
+    if (p.k_split)
+      return launch_kernel(&dist_kernel_v2<NW, MODE, W, true>, dim3((unsigned)n_blocks, (unsigned)p.nk), block,
+                           "dist_kernel_v2<256x32,lds-dma>", a, p, s);
+  return launch_kernel(&dist_kernel_v2<NW, MODE, W>, grid, block, "dist_kernel_v2<256x32,lds-dma>", a, p, s);
 }
 
 // COUNTS / JACCARD modes: each k's counts are consumed at once, nothing is packed
 template <int MODE>
-int launch_tiles_unpacked(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const float *d_rtab,
-                          void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, DistParams &p,
-                          hipStream_t s) {
+int launch_tiles_unpacked(const ppk_db *ref, const ppk_db *qry, const DistArgs &a, DistParams &p, hipStream_t s) {
   static_assert(MODE == MODE_COUNTS || MODE == MODE_JACCARD, "unpacked modes");
-  if (p.bbits != 14)
-    return launch_variant<8, 4, MODE, uint64_t>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask,
-                                                p, s, "dist_kernel<8,4,generic>");
-  return launch_v2<8, MODE, 1>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
+  if (p.bbits != 14) return launch_variant<8, 4, MODE, uint64_t>(a, p, s, "dist_kernel<8,4,generic>");
+  return launch_v2<8, MODE, 1>(ref, qry, a, p, s);
 }
 
 // DIST / MASK modes: the per-pair count register is sized by nk * cnt_bits (<= 128, checked by
 // the caller)
 template <int MODE>
-int launch_tiles_packed(const ppk_db *ref, const ppk_db *qry, const double *d_lut, const float *d_rtab,
-                        void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, DistParams &p,
-                        hipStream_t s) {
+int launch_tiles_packed(const ppk_db *ref, const ppk_db *qry, const DistArgs &a, DistParams &p, hipStream_t s) {
   static_assert(MODE == MODE_DIST || ppk_is_mask(MODE) || MODE == MODE_KNN, "packed modes");
   const int total_bits = p.nk * p.cnt_bits;
   if constexpr (MODE == MODE_KNN) {
     if (p.bbits != 14) return ppk_fail(PPK_ERR_ARG, "neighbours from tiles need bbits = 14 (use the square-matrix path)");
   } else if (p.bbits != 14) {
     // the generic-bbits kernel has registers to spare and packs into plain integers
-    if (total_bits <= 64)
-      return launch_variant<8, 4, MODE, uint64_t>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask,
-                                                  p, s, "dist_kernel<8,4,generic>");
-    if (p.nk <= 6 && p.cnt_bits <= 16)
-      return launch_variant<8, 4, MODE, Pack96>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask,
-                                                p, s, "dist_kernel<8,4,generic>");
-    return launch_variant<8, 4, MODE, u128>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask,
-                                            p, s, "dist_kernel<8,4,generic>");
+    if (total_bits <= 64) return launch_variant<8, 4, MODE, uint64_t>(a, p, s, "dist_kernel<8,4,generic>");
+    if (p.nk <= 6 && p.cnt_bits <= 16) return launch_variant<8, 4, MODE, Pack96>(a, p, s, "dist_kernel<8,4,generic>");
+    return launch_variant<8, 4, MODE, u128>(a, p, s, "dist_kernel<8,4,generic>");
   }
   // (option "wide_kpg": a narrower window, i.e. the wide path on a k list the register would hold -- tests)
   const long long force_kpg = ppk_config().wide_kpg.load();
@@ -1493,15 +1490,13 @@ int launch_tiles_packed(const ppk_db *ref, const ppk_db *qry, const double *d_lu
     // (every k list of more than 64 count bits: rebuilding three- and four-dword registers in the last unit measured
     // the same -- profiles/r05/ksplit_fit_from_parts.txt -- and cost two more instantiations, both with spills; the
     // two-dword register path stays for the shapes whose tiles are fitted from the LDS table)
-    if (p.k_split && (total_bits > 64 || (force_kpg > 0 && force_kpg < p.nk)))
-      return launch_v2<8, MODE, 2, true>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
-    if (p.k_split) return launch_v2<8, MODE, 2>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
+    if (p.k_split && (total_bits > 64 || (force_kpg > 0 && force_kpg < p.nk))) return launch_v2<8, MODE, 2, true>(ref, qry, a, p, s);
+    if (p.k_split) return launch_v2<8, MODE, 2>(ref, qry, a, p, s);
   }
-  if (total_bits > 128 || (force_kpg > 0 && force_kpg < p.nk && !p.k_split))
-    return launch_v2<8, MODE, 4, true>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
-  if (total_bits <= 64) return launch_v2<8, MODE, 2>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
-  if (total_bits <= 96) return launch_v2<8, MODE, 3>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
-  return launch_v2<8, MODE, 4>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
+  if (total_bits > 128 || (force_kpg > 0 && force_kpg < p.nk && !p.k_split)) return launch_v2<8, MODE, 4, true>(ref, qry, a, p, s);
+  if (total_bits <= 64) return launch_v2<8, MODE, 2>(ref, qry, a, p, s);
+  if (total_bits <= 96) return launch_v2<8, MODE, 3>(ref, qry, a, p, s);
+  return launch_v2<8, MODE, 4>(ref, qry, a, p, s);
 }
 
 }  // namespace
@@ -1540,18 +1535,12 @@ int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, uint64_t *d_ou
 // options in force: the one shape that reads a rank-coded copy (launch_v2)
 bool ppk_self_job_takes_tiles(const ppk_db *db) {
   if (db->bbits != V2_BB || db->n < 2) return false;
-  int bits = 1;
-  while (((size_t)1 << bits) <= db->s64 * 64) ++bits;
+  const int bits = count_bits(db->s64);
   if (db->nk * (size_t)bits > 64) return false;
   PpkRouteShape shape = {db->n, db->n, db->n * (db->n - 1) / 2, 1, (int)db->nk, (int)db->s64, bits, (int)db->bbits, 0, 0};
-  PpkRouteKnobs knobs = {ppk_config().ksplit.load(), ppk_config().ksplit_wide.load(), ppk_config().ksplit_long.load(),
-                         ppk_config().ksplit_fused.load(), ppk_config().ksplit_slices.load(), ppk_config().wide_kpg.load(),
-                         (size_t)ppk_config().ksplit_scratch_mb.load() << 20};
-  return ppk_choose_route_impl(shape, ppk_geometry(db->device), knobs).route == PPK_ROUTE_TILE;
+  return ppk_choose_route_impl(shape, ppk_geometry(db->device), route_knobs()).route == PPK_ROUTE_TILE;
 }
 
-// Enqueue kernel 1 for one band.  d_scratch must hold lut_bytes (+ table).
-// mode_mask: d_mask non-null selects the fused boundary/bitmask output.
 // ---- device geometry -----------------------------------------------------------------------------------------------
 // Nothing below assumes a part: the compute units, the XCD count and the number of pair-tile workgroups the device
 // holds at once are read here, once per device.  (MI355X in SPX mode: 256 CUs, 8 XCDs, 2 workgroups of the tile
@@ -1689,8 +1678,7 @@ extern "C" int ppk_choose_route(size_t n_ref, size_t q_rows, int self, int nk, i
   sh.nk = nk;
   sh.s64 = sketchsize64;
   sh.bbits = bbits;
-  sh.cnt_bits = 1;
-  while ((1u << sh.cnt_bits) <= 64u * (unsigned)sketchsize64) ++sh.cnt_bits;
+  sh.cnt_bits = count_bits((size_t)sketchsize64);
   sh.mask = mask;
   sh.knn = knn;
   PpkGeometry g = {cus, 0, tile_slots};
@@ -1704,13 +1692,6 @@ extern "C" int ppk_choose_route(size_t n_ref, size_t q_rows, int self, int nk, i
   return PPK_OK;
 }
 
-static int launch_dist_band(const ppk_db *ref, const ppk_db *qry_or_null, const int32_t *kmers,
-                            const float *d_rtab, size_t n_clu, int flags, size_t q_begin, size_t q_end,
-                            void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, int slope,
-                            float x_max, float y_max, float scale_x, float scale_y, int inclusive,
-                            double *d_lut, hipStream_t s, const int *knn_args, bool lut_ready,
-                            const ppk_bgmm *d_bgmm);
-
 size_t ppk_rows_per_dispatch(const ppk_db *ref) {
   const size_t r_tiles = (ref->n + V2_RT - 1) / V2_RT;
   long long per_launch = ppk_config().launch_tiles.load();
@@ -1720,55 +1701,19 @@ size_t ppk_rows_per_dispatch(const ppk_db *ref) {
   return q_sub < 64 ? 64 : q_sub;
 }
 
-// A dispatch holds fewer than 2^32 work-items: with 512-thread workgroups that is 8.4 M pair tiles, which
-// 370 000 genomes against themselves exceed (a million: 61 M).  Larger bands go out as several launches over
-// consecutive query rows, each writing to its own part of the output (the kernels address rows and mask
-// words relative to the band they are launched on; kNN candidates are appended through a shared counter).
-int ppk_launch_dist(const ppk_db *ref, const ppk_db *qry_or_null, const int32_t *kmers,
-                    const float *d_rtab, size_t n_clu, int flags, size_t q_begin, size_t q_end,
-                    void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, int slope,
-                    float x_max, float y_max, float scale_x, float scale_y, int inclusive,
-                    double *d_lut, hipStream_t s, const int *knn_args, bool lut_ready,
-                    const ppk_bgmm *d_bgmm) {
-  const size_t q_sub = ppk_rows_per_dispatch(ref);
-  if (q_end - q_begin <= q_sub)
-    return launch_dist_band(ref, qry_or_null, kmers, d_rtab, n_clu, flags, q_begin, q_end, d_out, d_n_failed, d_mask,
-                            slope, x_max, y_max, scale_x, scale_y, inclusive, d_lut, s, knn_args, lut_ready, d_bgmm);
-  const size_t n_qry = qry_or_null ? qry_or_null->n : 0;
-  const size_t row_bytes = (flags & (PPK_FLAG_COUNTS | PPK_FLAG_JACCARD)) ? ref->nk * 4 : 8;
-  const size_t n_rtiles = (ref->n + 63) / 64;
-  for (size_t lo = q_begin; lo < q_end; lo += q_sub) {
-    const size_t hi = lo + q_sub < q_end ? lo + q_sub : q_end;
-    if (ppk_rows_in_band(ref->n, n_qry, lo, hi) == 0) continue;      // (the last sample of a self job pairs with nobody)
-    void *out = d_out;
-    uint64_t *mask = d_mask;
-    if (!knn_args) {
-      if (d_out) out = static_cast<char *>(d_out) + ppk_rows_in_band(ref->n, n_qry, q_begin, lo) * row_bytes;
-      if (d_mask) mask = d_mask + (lo - q_begin) * n_rtiles;
-    }
-    int rc = launch_dist_band(ref, qry_or_null, kmers, d_rtab, n_clu, flags, lo, hi, out, d_n_failed, mask, slope,
-                              x_max, y_max, scale_x, scale_y, inclusive, d_lut, s, knn_args, lut_ready || lo > q_begin,
-                              d_bgmm);
-    if (rc != PPK_OK) return rc;
-  }
-  return PPK_OK;
-}
-
-static int launch_dist_band(const ppk_db *ref, const ppk_db *qry_or_null, const int32_t *kmers,
-                            const float *d_rtab, size_t n_clu, int flags, size_t q_begin, size_t q_end,
-                            void *d_out, unsigned long long *d_n_failed, uint64_t *d_mask, int slope,
-                            float x_max, float y_max, float scale_x, float scale_y, int inclusive,
-                            double *d_lut, hipStream_t s, const int *knn_args, bool lut_ready,
-                            const ppk_bgmm *d_bgmm) {
-  const ppk_db *qry = qry_or_null ? qry_or_null : ref;
+// Kernel 1 for one band that a single dispatch holds
+static int launch_dist_band(const DistJob &job) {
+  const ppk_db *ref = job.ref, *qry = job.qry ? job.qry : ref;
+  const int32_t *kmers = job.kmers;
+  hipStream_t s = job.s;
   DistParams p = {};
-  p.self = qry_or_null ? 0 : 1;
+  p.self = job.qry ? 0 : 1;
   p.npad_r = ref->npad;
   p.npad_q = qry->npad;
   p.n_ref = ref->n;
-  p.q_begin = q_begin;
-  p.q_end = q_end;
-  p.row_base = p.self ? q_begin * ref->n - (q_begin * (q_begin + 1)) / 2 : q_begin * ref->n;
+  p.q_begin = job.q_begin;
+  p.q_end = job.q_end;
+  p.row_base = p.self ? p.q_begin * ref->n - (p.q_begin * (p.q_begin + 1)) / 2 : p.q_begin * ref->n;
   p.nk = (int)ref->nk;
   p.s64 = (int)ref->s64;
   p.bbits = (int)ref->bbits;
@@ -1776,17 +1721,15 @@ static int launch_dist_band(const ppk_db *ref, const ppk_db *qry_or_null, const 
   p.lut_kstride = nbins + 1;
   p.lut_cpstride = (size_t)p.nk * (nbins + 1);
   p.n_rtiles = (ref->n + 63) / 64;
-  p.n_clu = (int)(n_clu ? n_clu : 1);
-  p.random_correct = (flags & PPK_FLAG_RANDOM_CORRECT) && d_rtab ? 1 : 0;
-  p.slope = slope;
-  p.inclusive = inclusive;
-  p.x_max = x_max;
-  p.y_max = y_max;
-  p.scale_x = scale_x;
-  p.scale_y = scale_y;
-  int bits = 1;
-  while (((size_t)1 << bits) <= nbins) ++bits;
-  p.cnt_bits = bits;
+  p.n_clu = (int)(job.n_clu ? job.n_clu : 1);
+  p.random_correct = (job.flags & PPK_FLAG_RANDOM_CORRECT) && job.d_rtab ? 1 : 0;
+  p.slope = job.slope;
+  p.inclusive = job.inclusive;
+  p.x_max = job.x_max;
+  p.y_max = job.y_max;
+  p.scale_x = job.scale_x;
+  p.scale_y = job.scale_y;
+  p.cnt_bits = count_bits(ref->s64);
   for (int k = 0; k < p.nk && k < PPK_MAX_NK; ++k) p.kmers[k] = kmers[k];
   FitCoef coef = {};
   {
@@ -1803,8 +1746,8 @@ static int launch_dist_band(const ppk_db *ref, const ppk_db *qry_or_null, const 
   }
   p.lut_total = (size_t)p.n_clu * p.n_clu * p.lut_cpstride;
   p.lut32 = (p.lut_total * 16 < ((size_t)1 << 32)) ? 1 : 0;
-  p.knn = knn_args ? knn_args[0] : 0;
-  p.knn_col = knn_args ? knn_args[1] : 0;
+  p.knn = job.knn_args ? job.knn_args[0] : 0;
+  p.knn_col = job.knn_args ? job.knn_args[1] : 0;
   p.ablate = 0;
 #ifdef PPK_EXPERIMENTS
   p.ablate = (int)ppk_config().ablate.load();
@@ -1813,113 +1756,128 @@ static int launch_dist_band(const ppk_db *ref, const ppk_db *qry_or_null, const 
   p.ext_adjust = ppk_config().ext_collision_adjust.load() ? 1 : 0;
   p.ext_skip = ppk_config().ext_fit_skip.load() ? 1 : 0;
 
-  // MODE_BGMM reads the model through the kernel's `out` pointer (MODE_MASK leaves it unused)
-  if (d_bgmm && !d_mask) return ppk_fail(PPK_ERR_STATE, "internal: a BGMM launch needs an edge bitmask");
-  void *bgmm_out = const_cast<ppk_bgmm *>(d_bgmm);
-  const bool want_counts = flags & PPK_FLAG_COUNTS;
-  const bool want_jac = flags & PPK_FLAG_JACCARD;
-  if (want_counts)
-    return launch_tiles_unpacked<MODE_COUNTS>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
-  if (want_jac)
-    return launch_tiles_unpacked<MODE_JACCARD>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
+  if (job.d_bgmm && !job.d_mask) return ppk_fail(PPK_ERR_STATE, "internal: a BGMM launch needs an edge bitmask");
+  // cluster ids only matter when a multi-cluster random-match table is in use
+  const bool use_clu = p.random_correct && p.n_clu > 1;
+  DistArgs a = {ref->d_skT, qry->d_skT, job.d_lut, use_clu ? ref->d_clu : nullptr, use_clu ? qry->d_clu : nullptr,
+                job.d_rtab, job.d_out, job.d_n_failed, job.d_mask};
+  // a counts pass: its rows go to scratch, it counts no failures and fills no mask
+  auto counts_to = [&a](void *d_cnt) {
+    DistArgs c = a;
+    c.out = d_cnt, c.n_failed = nullptr, c.mask = nullptr;
+    return c;
+  };
+  if (job.flags & PPK_FLAG_COUNTS) return launch_tiles_unpacked<MODE_COUNTS>(ref, qry, a, p, s);
+  if (job.flags & PPK_FLAG_JACCARD) return launch_tiles_unpacked<MODE_JACCARD>(ref, qry, a, p, s);
 
   // which kernel shape this band runs through: a pure function of shape, geometry and options (ppk_choose_route_impl)
-  const size_t band_rows = p.self ? (q_end * ref->n - (q_end * (q_end + 1)) / 2) - p.row_base : (q_end - q_begin) * ref->n;
-  PpkRouteShape shape = {ref->n, q_end - q_begin, band_rows, p.self, p.nk, p.s64, p.cnt_bits, p.bbits, d_mask ? 1 : 0,
-                         knn_args ? 1 : 0};
-  PpkRouteKnobs knobs = {ppk_config().ksplit.load(), ppk_config().ksplit_wide.load(), ppk_config().ksplit_long.load(),
-                         ppk_config().ksplit_fused.load(), ppk_config().ksplit_slices.load(), ppk_config().wide_kpg.load(),
-                         (size_t)ppk_config().ksplit_scratch_mb.load() << 20};
-  PpkRouteChoice choice = ppk_choose_route_impl(shape, ppk_geometry(ref->device), knobs);
-  const bool too_wide = choice.route == PPK_ROUTE_COUNTS_UNFUSED;
-  bool small = choice.route == PPK_ROUTE_KSPLIT_ONE_LAUNCH || choice.route == PPK_ROUTE_KSPLIT_TWO_PASS;
-  if (too_wide && knn_args) return ppk_fail(PPK_ERR_ARG, "neighbours from tiles need bbits = 14");
-  if (too_wide) {
+  const size_t rows = band_rows(p);
+  PpkRouteShape shape = {ref->n, p.q_end - p.q_begin, rows, p.self, p.nk, p.s64, p.cnt_bits, p.bbits, job.d_mask ? 1 : 0,
+                         job.knn_args ? 1 : 0};
+  PpkRouteChoice choice = ppk_choose_route_impl(shape, ppk_geometry(ref->device), route_knobs());
+  if (choice.route == PPK_ROUTE_COUNTS_UNFUSED) {
     // the packed per-pair state does not fit: raw counts to scratch, then a generic regression pass
-    int dev = ref->device;
-    const size_t rows = p.self ? (q_end * ref->n - (q_end * (q_end + 1)) / 2) - p.row_base
-                               : (q_end - q_begin) * ref->n;
-    if (d_mask) return ppk_fail(PPK_ERR_STATE, "internal: counts fallback is resolved by the caller");
+    if (job.knn_args) return ppk_fail(PPK_ERR_ARG, "neighbours from tiles need bbits = 14");
+    if (job.d_mask) return ppk_fail(PPK_ERR_STATE, "internal: counts fallback is resolved by the caller");
     void *p_cnt = nullptr;
-    int rc = ppk_scratch_get(dev, SLOT_ITER_A, rows * (size_t)p.nk * 4 + (size_t)p.nk * 4 + 256, &p_cnt);
+    int rc = ppk_scratch_get(ref->device, SLOT_ITER_A, rows * (size_t)p.nk * 4 + (size_t)p.nk * 4 + 256, &p_cnt);
     if (rc != PPK_OK) return rc;
     uint32_t *d_cnt = static_cast<uint32_t *>(p_cnt);
     int *d_kmers = reinterpret_cast<int *>(d_cnt + rows * (size_t)p.nk);
     PPK_HIP(hipMemcpyAsync(d_kmers, kmers, (size_t)p.nk * 4, hipMemcpyHostToDevice, s));
-    rc = launch_tiles_unpacked<MODE_COUNTS>(ref, qry, d_lut, d_rtab, d_cnt, nullptr, nullptr, p, s);
+    rc = launch_tiles_unpacked<MODE_COUNTS>(ref, qry, counts_to(d_cnt), p, s);
     if (rc != PPK_OK) return rc;
-    const bool use_clu = p.random_correct && p.n_clu > 1;
     hipLaunchKernelGGL(regress_counts_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_cnt,
                        rows, p.row_base, p.self, p.n_ref, p.nk, d_kmers, ref->s64, ref->bbits,
-                       p.random_correct ? d_rtab : nullptr, p.n_clu, use_clu ? ref->d_clu : nullptr,
-                       use_clu ? qry->d_clu : nullptr, scale_x, scale_y, p.ext_adjust, p.ext_skip,
-                       static_cast<float2 *>(d_out), d_n_failed);
+                       p.random_correct ? job.d_rtab : nullptr, p.n_clu, a.rclu, a.qclu, job.scale_x, job.scale_y,
+                       p.ext_adjust, p.ext_skip, static_cast<float2 *>(job.d_out), job.d_n_failed);
     PPK_HIP(hipGetLastError());
     return PPK_OK;
   }
   // log-J table, built on the device for this (random table, k list) -- unless an identical earlier call
   // left it there (stage_tables)
-  if (!lut_ready) {
+  if (!job.lut_ready) {
     const size_t total = (size_t)p.n_clu * p.n_clu * p.lut_cpstride;
-    hipLaunchKernelGGL(lut_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_lut,
-                       d_rtab, p.nk, p.n_clu, nbins, ref->s64, ref->bbits, p.random_correct, p.ext_adjust, total,
+    hipLaunchKernelGGL(lut_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, job.d_lut,
+                       job.d_rtab, p.nk, p.n_clu, nbins, ref->s64, ref->bbits, p.random_correct, p.ext_adjust, total,
                        coef);
     PPK_HIP(hipGetLastError());
-    ppk_lut_commit(ref->device, d_lut);
+    ppk_lut_commit(ref->device, job.d_lut);
   }
-  const size_t rows = band_rows;
-  const int slices = choice.slices;      // pieces each k is cut into (ppk_choose_route_impl)
-  if (small) {
-    // one workgroup per (tile, k) -> raw counts; then the same per-pair fit as the tile epilogue
-    p.k_split = slices;
-    p.ks_rows = rows;
-    p.ks_blocks = p.s64 / slices;
-    p.ks_units = (unsigned)(p.nk * slices);
-    // ONE launch: every tile's last unit fits it (a unit's counts travel as 16-bit numbers)
+  // The band's mode.  MODE_KNN -- d_out: candidate arrays, d_mask: KnnState + bounds over n_ref (+ n_qry: a ref x
+  // query job) samples.  MODE_BGMM reads the model through the kernel's `out` pointer (MODE_MASK leaves it unused).
+  if (job.d_bgmm) a.out = const_cast<ppk_bgmm *>(job.d_bgmm);
+  auto launch_packed = [&]() {
+    if (job.knn_args) return launch_tiles_packed<MODE_KNN>(ref, qry, a, p, s);
+    if (job.d_bgmm) return launch_tiles_packed<MODE_BGMM>(ref, qry, a, p, s);
+    if (job.d_mask) return launch_tiles_packed<MODE_MASK>(ref, qry, a, p, s);
+    return launch_tiles_packed<MODE_DIST>(ref, qry, a, p, s);
+  };
+  if (choice.route != PPK_ROUTE_KSPLIT_ONE_LAUNCH && choice.route != PPK_ROUTE_KSPLIT_TWO_PASS) return launch_packed();
+
+  // a small job: one workgroup per (tile, k), or per piece of a k (ppk_choose_route_impl)
+  const int slices = choice.slices;
+  p.k_split = slices;
+  p.ks_rows = rows;
+  p.ks_blocks = p.s64 / slices;
+  p.ks_units = (unsigned)(p.nk * slices);
+  if (choice.route == PPK_ROUTE_KSPLIT_ONE_LAUNCH) {
+    // ONE launch: every tile's last unit fits it
     // (a unit's counts travel as 16-bit numbers; fitted from the parts as they lie, a k's pieces are added in place)
-    if (choice.route == PPK_ROUTE_KSPLIT_ONE_LAUNCH) {
-      const int rc1 = d_bgmm ? launch_tiles_packed<MODE_BGMM>(ref, qry, d_lut, d_rtab, bgmm_out, d_n_failed, d_mask, p, s)
-                      : d_mask ? launch_tiles_packed<MODE_MASK>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s)
-                             : launch_tiles_packed<MODE_DIST>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, nullptr, p, s);
-      if (rc1 != kNoKsplitScratch) return rc1;
-      // the device could not give the partial counts their scratch: the band runs through the tile kernel, which
-      // needs none (a job that fits a nearly full GPU must not fail on a buffer that only buys speed)
-      (void)hipGetLastError();
-      p.k_split = 0;
-      small = false;
-    }
+    const int rc1 = launch_packed();
+    if (rc1 != kNoKsplitScratch) return rc1;
+    // the device could not give the partial counts their scratch: the band runs through the tile kernel, which
+    // needs none (a job that fits a nearly full GPU must not fail on a buffer that only buys speed)
+    (void)hipGetLastError();
+    p.k_split = 0;
+    return launch_packed();
   }
-  if (small) {
-    if (d_mask) {      // (cannot happen: edge_ks admits one-launch shapes only; stay on the tile kernel)
-      p.k_split = 0;
-      if (d_bgmm) return launch_tiles_packed<MODE_BGMM>(ref, qry, d_lut, d_rtab, bgmm_out, d_n_failed, d_mask, p, s);
-      return launch_tiles_packed<MODE_MASK>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
+  // two passes: raw counts, k-major, then the same per-pair fit as the tile epilogue
+  if (job.d_mask) return ppk_fail(PPK_ERR_STATE, "internal: the two-pass k-split route serves plain distances only");
+  void *p_cnt = nullptr;
+  int rc = ppk_scratch_get(ref->device, SLOT_ITER_A, rows * (size_t)p.nk * slices * 4 + 256, &p_cnt);
+  if (rc != PPK_OK) return rc;
+  {
+    DistParams pc = p;
+    pc.nk = p.nk * slices;
+    pc.s64 = p.s64 / slices;
+    rc = launch_tiles_unpacked<MODE_COUNTS>(ref, qry, counts_to(p_cnt), pc, s);
+  }
+  if (rc != PPK_OK) return rc;
+  ppk_set_kernel_name("dist_kernel_v2<256x32,lds-dma,k-split counts> + regress_packed_kernel");
+  ppk_prof_begin(s);
+  hipLaunchKernelGGL(regress_packed_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s,
+                     static_cast<const uint32_t *>(p_cnt), rows, job.d_lut, a.rclu, a.qclu,
+                     static_cast<float2 *>(job.d_out), job.d_n_failed, p);
+  ppk_prof_end(s);
+  PPK_HIP(hipGetLastError());
+  return PPK_OK;
+}
+
+// A dispatch holds fewer than 2^32 work-items: with 512-thread workgroups that is 8.4 M pair tiles, which
+// 370 000 genomes against themselves exceed (a million: 61 M).  Larger bands go out as several launches over
+// consecutive query rows, each writing to its own part of the output (the kernels address rows and mask
+// words relative to the band they are launched on; kNN candidates are appended through a shared counter).
+int ppk_launch_dist(const DistJob &job) {
+  const ppk_db *ref = job.ref;
+  const size_t q_sub = ppk_rows_per_dispatch(ref);
+  if (job.q_end - job.q_begin <= q_sub) return launch_dist_band(job);
+  const size_t n_qry = job.qry ? job.qry->n : 0;
+  const size_t row_bytes = (job.flags & (PPK_FLAG_COUNTS | PPK_FLAG_JACCARD)) ? ref->nk * 4 : 8;
+  const size_t n_rtiles = (ref->n + 63) / 64;
+  for (size_t lo = job.q_begin; lo < job.q_end; lo += q_sub) {
+    const size_t hi = lo + q_sub < job.q_end ? lo + q_sub : job.q_end;
+    if (ppk_rows_in_band(ref->n, n_qry, lo, hi) == 0) continue;      // (the last sample of a self job pairs with nobody)
+    DistJob band = job;
+    band.q_begin = lo;
+    band.q_end = hi;
+    if (!job.knn_args) {
+      if (job.d_out) band.d_out = static_cast<char *>(job.d_out) + ppk_rows_in_band(ref->n, n_qry, job.q_begin, lo) * row_bytes;
+      if (job.d_mask) band.d_mask = job.d_mask + (lo - job.q_begin) * n_rtiles;
     }
-    void *p_cnt = nullptr;
-    int rc = ppk_scratch_get(ref->device, SLOT_ITER_A, rows * (size_t)p.nk * slices * 4 + 256, &p_cnt);
+    band.lut_ready = job.lut_ready || lo > job.q_begin;
+    const int rc = launch_dist_band(band);
     if (rc != PPK_OK) return rc;
-    {
-      DistParams pc = p;
-      pc.nk = p.nk * slices;
-      pc.s64 = p.s64 / slices;
-      rc = launch_tiles_unpacked<MODE_COUNTS>(ref, qry, d_lut, d_rtab, p_cnt, nullptr, nullptr, pc, s);
-    }
-    if (rc != PPK_OK) return rc;
-    const bool use_clu = p.random_correct && p.n_clu > 1;
-    ppk_set_kernel_name("dist_kernel_v2<256x32,lds-dma,k-split counts> + regress_packed_kernel");
-    ppk_prof_begin(s);
-    hipLaunchKernelGGL(regress_packed_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s,
-                       static_cast<const uint32_t *>(p_cnt), rows, d_lut, use_clu ? ref->d_clu : nullptr,
-                       use_clu ? qry->d_clu : nullptr, static_cast<float2 *>(d_out), d_n_failed, p);
-    ppk_prof_end(s);
-    PPK_HIP(hipGetLastError());
-    return PPK_OK;
   }
-  if (knn_args) {
-    // d_out: candidate arrays, d_mask: KnnState + bounds over n_ref (+ n_qry: a ref x query job) samples (MODE_KNN)
-    return launch_tiles_packed<MODE_KNN>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
-  }
-  if (d_bgmm) return launch_tiles_packed<MODE_BGMM>(ref, qry, d_lut, d_rtab, bgmm_out, d_n_failed, d_mask, p, s);
-  if (d_mask) return launch_tiles_packed<MODE_MASK>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
-  return launch_tiles_packed<MODE_DIST>(ref, qry, d_lut, d_rtab, d_out, d_n_failed, d_mask, p, s);
+  return PPK_OK;
 }

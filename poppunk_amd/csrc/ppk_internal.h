@@ -372,6 +372,30 @@ int ppk_knn_band_dev(const ppk_db *db, const ppk_db *qry, const int32_t *kmers, 
                      long long *d_j, float *d_dist, unsigned long long *n_candidates, void *stream);
 size_t ppk_rows_per_dispatch(const ppk_db *ref);     // query rows one kernel launch may cover (ppk_launch_dist)
 
+// One call of kernel 1 (ppk_dist.hip): a band of query rows of `qry` (null: a self job of `ref`) against `ref`.  A
+// caller sets the fields it means; the boundary's defaults are those of a call without one.
+struct DistJob {
+  const ppk_db *ref = nullptr, *qry = nullptr;
+  const int32_t *kmers = nullptr;
+  const float *d_rtab = nullptr;      // random-match table (null: none, n_clu = 1)
+  size_t n_clu = 1;
+  int flags = 0;
+  size_t q_begin = 0, q_end = 0;
+  void *d_out = nullptr;              // rows of the band; neighbour mode: the candidate arrays
+  unsigned long long *d_n_failed = nullptr;
+  uint64_t *d_mask = nullptr;         // edge bitmask of the fused boundary modes; neighbour mode: KnnState + bounds
+  int slope = 2;                      // the boundary (src/boundary.cpp:42-58); plain distances are divided by the scales
+  float x_max = 0.f, y_max = 0.f, scale_x = 1.f, scale_y = 1.f;
+  int inclusive = 1;
+  double *d_lut = nullptr;            // the log-J table's place, built by the call unless lut_ready
+  bool lut_ready = false;
+  const int *knn_args = nullptr;      // neighbour mode: {knn, distance column}
+  const ppk_bgmm *d_bgmm = nullptr;   // device copy of the model whose label test fills d_mask instead of the line
+  hipStream_t s = nullptr;
+};
+// enqueues only; a band of more rows than one dispatch holds goes out as several launches
+int ppk_launch_dist(const DistJob &job);
+
 // ---- helper threads ----------------------------------------------------------------
 // A host call uses a dozen short-lived helpers (page touchers, per-device workers, hash lanes); starting
 // a thread costs 30-100 us and jitters to several hundred, which is the scale of the call's whole start-up.
