@@ -108,6 +108,12 @@ int ppk_device_count(int *n);
  *   refine fit
  *     "refine_local" (1)   refineFit's local search scores its evaluations through the bracket handle
  *                          (ppk_refine_local_*); 0 = every evaluation through ppk_refine_score_dev (same fit)
+ *   density grids
+ *     "density_hot_table" (1)  ppk_density_counts_dev adds through a per-workgroup LDS table of hot pixels in front of
+ *                          the global atomics; 0 = one global atomic per row (same counts)
+ *     "density_kde_presum" (0)  ppk_density_kde_dev sums the terms of lanes of a wave whose rows share a window of
+ *                          nodes before the LDS add, for groups of at least this many lanes (at most 64); 0 = every
+ *                          lane adds its own terms (same sums)
  *   host calls
  *     "chunk_rows" (8 Mi)  rows per sub-band of a host query (about an eighth of the job, at least 1 Mi, below 16 Mi
  *                          rows); also scales the pieces of the fused host edge call
@@ -753,6 +759,59 @@ int ppk_cluster_pair_sums_dev(const float *d_dist, size_t n_rows, int col, const
  * blocking. */
 int ppk_cluster_pair_sums(const float *dist, size_t n_rows, int col, const int32_t *levels, size_t n_levels, int shift,
                           int device_id, long long *sum, long long *cnt);
+
+/* ------------------------------------------------------------------------
+ * Density grids of a resident float32 [n_rows][2] matrix: the two layers of the fit plots, each one
+ * streaming pass with integer accumulation -- the same bits on every call and for any row order.  The matrix need not
+ * be condensed (a ref x query matrix works).
+ *
+ * ppk_density_kde_dev: the Epanechnikov sums on the nodes (gx[a], gy[b]).  Rows read: d_idx[0 .. n_idx) (int64, any
+ * order, repeats allowed) or, d_idx NULL, every row.  gx [nx], gy [ny]: HOST doubles, strictly ascending (the call
+ * places them in its scratch); scale: two HOST floats, or NULL for the column maxima of the rows read, taken on the
+ * device as float32 (np.amax(X, axis = 0)); scale_used (nullable): the two floats the call divided by.  For every row
+ * read (x, y):  xs = x / scale[0], ys = y / scale[1] (IEEE float32 divisions: the reference's `X /= scale` on a float32
+ * array), px = (double)xs, py = (double)ys, and for every cell (a, b)
+ *     dx = px - gx[a], dy = py - gy[b], d2 = dx*dx + dy*dy (two products, one add, un-fused),
+ *     t = 1.0 - d2 * inv_h2 with inv_h2 = 1.0 / (h*h) computed once on the host,
+ *     t > 0:  d_sum[a][b] += llrint(t * 2^shift).
+ * d_sum int64 [nx][ny], zeroed by the call.  sklearn's density is d_sum * 2^-shift * 2 / (pi h^2 N).  A row visits
+ * only the cells inside [px - hw, px + hw] x [py - hw, py + hw], hw = h (1 + 2^-20): a superset of the cells with
+ * t > 0 for any h and any spacing.  nx * ny + nx + ny <= PPK_DENSITY_KDE_MAX_CELLS: a workgroup keeps the grid and its
+ * coordinates in LDS, 8 bytes each, two workgroups to a CU (100 x 100 takes 10 200); the error message states the limit.
+ * PPK_ERR_ARG, ppk_last_error() naming the first offender in the order the rows are read (the position in d_idx, or
+ * the row), whichever kind it is: an index outside [0, n_rows); a non-finite value in a row read.  Also PPK_ERR_ARG: scale or h not finite or not positive (h*h and 1/(h*h) must be finite and positive too), a
+ * grid not finite or not strictly ascending, nx * ny zero or the grid above the limit, shift outside [0, 40] or above
+ * 62 - ceil_log2(rows read), a NULL array.  Synchronises the stream once (the offenders and the scale).
+ * (Replaces KernelDensity(bandwidth, kernel='epanechnikov').fit(X) and score_samples(xy) of plot_scatter,
+ * PopPUNK/plot.py:62-66, and with d_idx the sklearn.utils.shuffle copy of :50-51.) */
+#define PPK_DENSITY_KDE_MAX_CELLS 10240
+int ppk_density_kde_dev(const float *d_dist, size_t n_rows, const long long *d_idx, size_t n_idx, const float *scale,
+                        const double *gx, size_t nx, const double *gy, size_t ny, double h, int shift,
+                        long long *d_sum, float *scale_used, void *stream);
+/* Host arrays: dist float32 [n_rows][2], idx int64 [n_idx] (nullable) -> sum int64 [nx][ny], on device_id; blocking. */
+int ppk_density_kde(const float *dist, size_t n_rows, const long long *idx, size_t n_idx, const float *scale,
+                    const double *gx, size_t nx, const double *gy, size_t ny, double h, int shift, int device_id,
+                    long long *sum, float *scale_used);
+
+/* ppk_density_counts_dev: which pixels of a uniform raster hold a row, per label -- the scatter layer.  For every row
+ * (x, y): ix = floor(((double)x - x0) * inv_dx), iy = floor(((double)y - y0) * inv_dy); ix outside [0, nx) or iy
+ * outside [0, ny): *d_outside += 1 and nothing else; otherwise d_counts[slot][iy][ix] += 1 with slot = d_label[row] -
+ * label_lo (d_label NULL: slot 0, and n_slots must be 1).  d_label int32 [n_rows]: what ppk_bgmm_assign_dev and
+ * ppk_dbscan_assign_dev write.  d_counts uint32 [n_slots][ny][nx] and d_outside int64 [1], zeroed by the call.
+ * Limits: n_rows < 2^32, 1 <= n_slots <= 32, 1 <= nx, ny <= 4096, n_slots * nx * ny <= 2^26.
+ * PPK_ERR_ARG, ppk_last_error() naming the first row at fault: a non-finite value; a label outside [label_lo,
+ * label_lo + n_slots).  Also PPK_ERR_ARG: x0 / y0 not finite, inv_dx / inv_dy not finite or not positive, a limit
+ * passed, a NULL array.  Synchronises the stream once.
+ * (Replaces the one-marker-per-row plt.scatter / plt.plot calls of plot_results, plot_dbscan_results and
+ * plot_refined_results, PopPUNK/plot.py:221, :275, :330-331, for matrices too large to draw row by row.) */
+int ppk_density_counts_dev(const float *d_dist, size_t n_rows, const int32_t *d_label, int label_lo, int n_slots,
+                           double x0, double inv_dx, size_t nx, double y0, double inv_dy, size_t ny,
+                           uint32_t *d_counts, long long *d_outside, void *stream);
+/* Host arrays: dist float32 [n_rows][2], label int32 [n_rows] (nullable) -> counts uint32 [n_slots][ny][nx], outside
+ * int64 [1], on device_id; blocking. */
+int ppk_density_counts(const float *dist, size_t n_rows, const int32_t *label, int label_lo, int n_slots, double x0,
+                       double inv_dx, size_t nx, double y0, double inv_dy, size_t ny, int device_id,
+                       uint32_t *counts, long long *outside);
 
 /* ------------------------------------------------------------------------
  * Queries against an existing clustering.  Vertices 0 .. n_ref-1 are references, n_ref .. n_ref+n_qry-1

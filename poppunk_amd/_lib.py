@@ -92,6 +92,14 @@ SIGNATURES = {
     "ppk_cluster_sweep": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, _i32p, _i32p]),
     "ppk_cluster_pair_sums_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _sz, C.c_int, _vp, _vp, _vp]),
     "ppk_cluster_pair_sums": (C.c_int, [_f32p, _sz, C.c_int, _i32p, _sz, C.c_int, C.c_int, _llp, _llp]),
+    "ppk_density_kde_dev": (C.c_int, [_vp, _sz, _vp, _sz, _f32p, _f64p, _sz, _f64p, _sz, C.c_double, C.c_int, _vp, _f32p,
+                                      _vp]),
+    "ppk_density_kde": (C.c_int, [_f32p, _sz, _llp, _sz, _f32p, _f64p, _sz, _f64p, _sz, C.c_double, C.c_int, C.c_int,
+                                  _llp, _f32p]),
+    "ppk_density_counts_dev": (C.c_int, [_vp, _sz, _vp, C.c_int, C.c_int, C.c_double, C.c_double, _sz, C.c_double,
+                                         C.c_double, _sz, _vp, _vp, _vp]),
+    "ppk_density_counts": (C.c_int, [_f32p, _sz, _i32p, C.c_int, C.c_int, C.c_double, C.c_double, _sz, C.c_double,
+                                     C.c_double, _sz, C.c_int, C.POINTER(C.c_uint32), _llp]),
     "ppk_query_links_dev": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, C.c_int, _vp, _vp, _vp, _vp]),
     "ppk_query_links": (C.c_int, [_llp, _llp, _sz, _i32p, _sz, _sz, C.c_int, C.c_int, _i32p, _i32p, _i32p]),
     "ppk_cluster_extend_dev": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _vp]),

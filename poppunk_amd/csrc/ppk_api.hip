@@ -77,6 +77,8 @@ const OptionEntry kOptions[] = {
     {"bt_small_max", "PPK_BT_SMALL_MAX", &PpkConfig::bt_small_max},
     {"dbscan_search", "PPK_DBSCAN_SEARCH", &PpkConfig::dbscan_search},
     {"refine_local", "PPK_REFINE_LOCAL", &PpkConfig::refine_local},
+    {"density_hot_table", "PPK_DENSITY_HOT_TABLE", &PpkConfig::density_hot_table},
+    {"density_kde_presum", "PPK_DENSITY_KDE_PRESUM", &PpkConfig::density_kde_presum},
     {"host_parts", "PPK_HOST_PARTS", &PpkConfig::host_parts},
     {"host_parts_rows", "PPK_HOST_PARTS_ROWS", &PpkConfig::host_parts_rows},
     {"host_trace", "PPK_HOST_TRACE", &PpkConfig::host_trace},

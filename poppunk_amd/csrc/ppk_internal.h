@@ -106,6 +106,8 @@ struct PpkConfig {
   std::atomic<long long> bt_small_max{64};      // PPK_BT_SMALL_MAX: largest component Brandes gives one wave for all its sources (0 = none; at most 256; results within rounding)
   std::atomic<long long> dbscan_search{0};      // PPK_DBSCAN_SEARCH: the DBSCAN assignment's search: 0 = the grid from 1 024 training points up, 1 = the scan of every training point, 2 = the grid at any size (same labels)
   std::atomic<long long> refine_local{1};       // PPK_REFINE_LOCAL: refineFit's local search scores through the bracket handle (ppk_refine_local_*); 0 = every evaluation through ppk_refine_score_dev (same fit)
+  std::atomic<long long> density_hot_table{1};  // PPK_DENSITY_HOT_TABLE: ppk_density_counts_dev adds through a per-workgroup LDS table of hot pixels in front of the global atomics (0: every row one global atomic; same counts)
+  std::atomic<long long> density_kde_presum{0}; // PPK_DENSITY_KDE_PRESUM: ppk_density_kde_dev sums the terms of lanes of a wave that share a window of nodes before the LDS add, for groups of at least this many lanes (0: every lane adds its own terms; same sums)
   std::atomic<long long> knn_list{0};           // PPK_KNN_LIST: entries of the neighbour-candidate list (0 = sized from n and knn)
   std::atomic<long long> host_parts_rows{16 << 20};   // PPK_HOST_PARTS_ROWS: ... from this many rows up
   std::atomic<long long> host_parts{2};         // PPK_HOST_PARTS: worker threads of a one-device host query (>= 16 Mi rows)
@@ -271,7 +273,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_CLUSTERS = 21,                     // the cluster pair sums' first-bad-row / first-bad-number words
        SLOT_ASSIGN = 22,                       // the query links' counters, segment starts, overflow list and first ranks
        SLOT_ASSIGN_SORT = 23,                  // ... and, on the sort route only, its (query, label) keys, flags and temp storage
-       SLOT_COUNT = 24 };
+       SLOT_DENSITY = 24,                      // the density grids' coordinates, scale keys and first-offender words
+       SLOT_COUNT = 25 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

@@ -918,6 +918,126 @@ def cluster_pair_sums_dev(dist_t, levels_t, col=0, shift=None):
     return out[0], out[1], int(shift)
 
 
+def _kde_args(gx, gy, scale):
+    gx = np.ascontiguousarray(gx, dtype=np.float64)
+    gy = np.ascontiguousarray(gy, dtype=np.float64)
+    if gx.ndim != 1 or gy.ndim != 1:
+        raise ValueError("gx and gy must be one-dimensional")
+    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32).reshape(2)
+    return gx, gy, sc
+
+
+def density_kde_dev(dist_t, gx, gy, h, scale=None, idx_t=None, shift=None, return_scale=False):
+    """The Epanechnikov sums of a resident float32 [n, 2] CUDA matrix on the nodes (gx[a], gy[b])
+    (ppk_density_kde_dev; tests/density_model.py restates the rule).  gx, gy: ascending float64 host
+    arrays; h: the bandwidth; scale: two float32, or None for the column maxima of the rows read, taken on the device
+    (np.amax(X, axis=0)); idx_t: an int64 CUDA index list (any order, repeats allowed), or None for every row; shift:
+    None = pair_sum_shift(rows read).  Returns (sum int64 [nx, ny] CUDA, shift, rows_read), and with return_scale the
+    float32 [2] the call divided by as a fourth item.  sklearn's density is sum * 2^-shift * 2 / (pi h^2 N)."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    gx, gy, sc = _kde_args(gx, gy, scale)
+    n_rows = int(dist_t.shape[0])
+    if idx_t is not None and not (idx_t.is_cuda and idx_t.dtype == torch.int64 and idx_t.dim() == 1
+                                  and idx_t.is_contiguous() and idx_t.device == dist_t.device):
+        raise TypeError("idx must be a contiguous int64 CUDA vector on the matrix's device")
+    rows_read = n_rows if idx_t is None else int(idx_t.shape[0])
+    if shift is None:
+        shift = pair_sum_shift(rows_read)
+    used = np.zeros(2, dtype=np.float32)
+    dev = dist_t.device
+    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+    # NULL means every row, and an empty tensor has no address: an empty list passes the matrix's (never read)
+    idx_p = None if idx_t is None else C.c_void_p(idx_t.data_ptr() or dist_t.data_ptr())
+    with torch.cuda.device(dev):
+        out = torch.empty((len(gx), len(gy)), dtype=torch.int64, device=dev)
+        rc = _lib.lib().ppk_density_kde_dev(
+            C.c_void_p(dist_t.data_ptr()), n_rows, idx_p, rows_read if idx_t is not None else 0, sc.ctypes.data_as(fp) if sc is not None else None,
+            gx.ctypes.data_as(dp), len(gx), gy.ctypes.data_as(dp), len(gy), float(h), int(shift),
+            C.c_void_p(out.data_ptr()), used.ctypes.data_as(fp), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_density_kde_dev")
+    return (out, int(shift), rows_read, used) if return_scale else (out, int(shift), rows_read)
+
+
+def density_kde(dist, gx, gy, h, scale=None, idx=None, shift=None, device=0):
+    """density_kde_dev for host arrays (ppk_density_kde): dist float32 [n, 2], idx int64 or None.  Returns (sum int64
+    [nx, ny] numpy, shift, rows_read, scale float32 [2])."""
+    dist = np.ascontiguousarray(dist, dtype=np.float32)
+    if dist.ndim != 2 or dist.shape[1] != 2:
+        raise ValueError("dist must be [n, 2]")
+    gx, gy, sc = _kde_args(gx, gy, scale)
+    ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64).ravel()
+    rows_read = dist.shape[0] if ix is None else len(ix)
+    if shift is None:
+        shift = pair_sum_shift(rows_read)
+    out = np.empty((len(gx), len(gy)), dtype=np.int64)
+    used = np.zeros(2, dtype=np.float32)
+    fp, dp, lp = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_longlong)
+    rc = _lib.lib().ppk_density_kde(
+        dist.ctypes.data_as(fp), dist.shape[0], ix.ctypes.data_as(lp) if ix is not None else None,
+        rows_read if ix is not None else 0, sc.ctypes.data_as(fp) if sc is not None else None, gx.ctypes.data_as(dp),
+        len(gx), gy.ctypes.data_as(dp), len(gy), float(h), int(shift), int(device), out.ctypes.data_as(lp),
+        used.ctypes.data_as(fp))
+    _lib.check(rc, "ppk_density_kde")
+    return out, int(shift), rows_read, used
+
+
+def _raster_args(raster):
+    x0, inv_dx, nx, y0, inv_dy, ny = raster
+    return float(x0), float(inv_dx), int(nx), float(y0), float(inv_dy), int(ny)
+
+
+def density_counts_dev(dist_t, raster, labels_t=None, label_lo=0, n_slots=1):
+    """Which pixels of a uniform raster hold a row, per label (ppk_density_counts_dev).  raster =
+    (x0, inv_dx, nx, y0, inv_dy, ny); a row (x, y) falls in pixel (floor((x - x0) * inv_dx), floor((y - y0) * inv_dy))
+    of slot labels[row] - label_lo (no labels: slot 0).  labels_t: the int32 [n] CUDA tensor bgmm_assign_dev or
+    dbscan_assign_dev returns.  Returns (counts uint32 [n_slots, ny, nx] CUDA, outside int64 [1] CUDA: the rows off
+    the raster)."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    x0, inv_dx, nx, y0, inv_dy, ny = _raster_args(raster)
+    n_rows = int(dist_t.shape[0])
+    if labels_t is not None and not (labels_t.is_cuda and labels_t.dtype == torch.int32 and labels_t.dim() == 1
+                                     and labels_t.is_contiguous() and labels_t.shape[0] == n_rows
+                                     and labels_t.device == dist_t.device):
+        raise TypeError("labels must be a contiguous int32 [n] CUDA tensor on the matrix's device")
+    if not (1 <= int(n_slots) <= 32 and 1 <= nx <= 4096 and 1 <= ny <= 4096):
+        raise ValueError("n_slots must be 1 .. 32 and nx, ny 1 .. 4096")
+    dev = dist_t.device
+    with torch.cuda.device(dev):
+        counts = torch.empty((int(n_slots), ny, nx), dtype=torch.uint32, device=dev)
+        outside = torch.empty(1, dtype=torch.int64, device=dev)
+        rc = _lib.lib().ppk_density_counts_dev(
+            C.c_void_p(dist_t.data_ptr()), n_rows, C.c_void_p(labels_t.data_ptr()) if labels_t is not None else None,
+            int(label_lo), int(n_slots), x0, inv_dx, nx, y0, inv_dy, ny, C.c_void_p(counts.data_ptr()),
+            C.c_void_p(outside.data_ptr()), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_density_counts_dev")
+    return counts, outside
+
+
+def density_counts(dist, raster, labels=None, label_lo=0, n_slots=1, device=0):
+    """density_counts_dev for host arrays (ppk_density_counts).  Returns (counts uint32 [n_slots, ny, nx] numpy, the
+    number of rows off the raster)."""
+    dist = np.ascontiguousarray(dist, dtype=np.float32)
+    if dist.ndim != 2 or dist.shape[1] != 2:
+        raise ValueError("dist must be [n, 2]")
+    x0, inv_dx, nx, y0, inv_dy, ny = _raster_args(raster)
+    lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    if lab is not None and len(lab) != dist.shape[0]:
+        raise ValueError("one label per row")
+    if not (1 <= int(n_slots) <= 32 and 1 <= nx <= 4096 and 1 <= ny <= 4096):
+        raise ValueError("n_slots must be 1 .. 32 and nx, ny 1 .. 4096")
+    counts = np.empty((int(n_slots), ny, nx), dtype=np.uint32)
+    outside = np.zeros(1, dtype=np.int64)
+    rc = _lib.lib().ppk_density_counts(
+        dist.ctypes.data_as(C.POINTER(C.c_float)), dist.shape[0],
+        lab.ctypes.data_as(C.POINTER(C.c_int32)) if lab is not None else None, int(label_lo), int(n_slots), x0, inv_dx,
+        nx, y0, inv_dy, ny, int(device), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+        outside.ctypes.data_as(C.POINTER(C.c_longlong)))
+    _lib.check(rc, "ppk_density_counts")
+    return counts, int(outside[0])
+
+
 def network_summary_dev(i_t, j_t, off_t, n, n_off, values_at=None):
     """network_sweep_dev plus networkSummary's betweenness for every G_t (ppk_network_summary_dev).
     The same edge stream and checks.  Returns (stats int64 [n_off, 4], bit for bit network_sweep_dev's; bt float64

@@ -28,6 +28,7 @@ distances, the mutual-reachability spanning tree and the per-row assignment on t
 them on the host (poppunk_amd/dbscan.py).
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -188,6 +189,23 @@ class RefineBoundary:
                          score_idx=score_idx, no_local=no_local, betweenness_sample=betweenness_sample,
                          sample_size=sample_size, use_gpu=use_gpu, multi_boundary=multi_boundary, outPrefix=outPrefix)
         return y.cpu().numpy()
+
+    def plot(self, X, y=None, outPrefix=None, raster_above=1000000):
+        """RefineFit.plot (models.py:1038-1062): plot.plot_refined_results into <outPrefix>/<basename>_refined_fit.png.
+        X: a numpy array or a resident CUDA tensor; y: its assignments (None: assigned here, as the reference does).
+        The reference draws a sample of 12 500 000 rows of a larger matrix; here every row is drawn (above
+        raster_above rows as an occupancy raster made on the device).  outPrefix is required (ValueError without it):
+        the model keeps no output directory of its own."""
+        from . import plot as _plot
+        if outPrefix is None:
+            raise ValueError("plot needs outPrefix: the directory the picture is written into")
+        prefix = outPrefix
+        if y is None:
+            y = self.assign_dev(X) if hasattr(X, "is_cuda") else self.assign(X)
+        _plot.plot_refined_results(X, y, self.optimal_x, self.optimal_y, self.core_boundary, self.accessory_boundary,
+                                   self.mean0, self.mean1, self.min_move, self.max_move, self.scale, self.threshold,
+                                   self.indiv_fitted, self.unconstrained, "Refined fit boundary",
+                                   prefix + "/" + os.path.basename(prefix) + "_refined_fit", raster_above=raster_above)
 
     def save(self, prefix):
         """`<prefix>/<basename>_fit.npz` with RefineFit.save's keys (models.py:996-1005: intercept,
@@ -385,6 +403,21 @@ class BGMMModel:
             return y, torch.bincount(y, minlength=params.K).cpu().numpy()
         return cls._fitted(res, scale, seed, "labels" if init_labels is not None else "kmeans++", assign_points,
                            labels_of)
+
+    def plot(self, X, y, outPrefix=None, raster_above=1000000):
+        """The two pictures of BGMMFit.plot (models.py:404-408): plot.plot_results into <outPrefix>/<basename>_DPGMM_fit
+        .png and plot.plot_contours into ..._DPGMM_fit_contours.pdf.  X, y: numpy arrays or resident CUDA tensors (y as
+        `assign` / `assign_dev` return it).  The "Fit summary" entropy line of the reference is not written.  outPrefix is
+        required (ValueError without it): the model keeps no output directory of its own."""
+        from . import plot as _plot
+        if outPrefix is None:
+            raise ValueError("plot needs outPrefix: the directory the picture is written into")
+        prefix = outPrefix
+        used = int((_plot._label_counts(y, 0, self.n_components) > 0).sum())
+        title = "DPGMM – estimated number of spatial clusters: " + str(used)
+        outfile = prefix + "/" + os.path.basename(prefix) + "_DPGMM_fit"
+        _plot.plot_results(X, y, self.means, self.covariances, self.scale, title, outfile, raster_above=raster_above)
+        _plot.plot_contours(self, y, title + " assignment boundary", outfile + "_contours")
 
     def save(self, prefix):
         """`<prefix>/<basename>_fit.npz` with exactly `BGMMFit.save`'s keys (models.py:341-352: weights, means,
@@ -683,6 +716,20 @@ class DBSCANModel:
         self._check()
         return engine.dbscan_edges_dev(dist_t, self.handle(dist_t.device.index), n_ref=n_ref, int_offset=int_offset,
                                        cap=cap)
+
+    def plot(self, X, y=None, outPrefix=None, raster_above=1000000):
+        """DBSCANFit.plot's picture (models.py:695-704): plot.plot_dbscan_results into <outPrefix>/<basename>_dbscan.png.
+        X: the un-scaled distances, a numpy array or a resident CUDA tensor; y: their assignments (None: assigned
+        here).  The reference draws its fit's subsample; any matrix may be passed here.  outPrefix is required
+        (ValueError without it): the model keeps no output directory of its own."""
+        from . import plot as _plot
+        if outPrefix is None:
+            raise ValueError("plot needs outPrefix: the directory the picture is written into")
+        prefix = outPrefix
+        if y is None:
+            y = self.assign_dev(X) if hasattr(X, "is_cuda") else self.assign(X)
+        _plot.plot_dbscan_results(X, y, self.n_clusters, prefix + "/" + os.path.basename(prefix) + "_dbscan",
+                                  raster_above=raster_above)
 
     # -- persistence ---------------------------------------------------------------------------------------------
     def save(self, prefix):
