@@ -96,6 +96,11 @@ int ppk_device_count(int *n);
  *                          a smaller value sends narrower k lists through that kernel)
  *     "launch_tiles" (8 000 000)  pair tiles per kernel launch: a dispatch holds fewer than 2^32 work-items, so bands
  *                          of more tiles -- 370 000 genomes against themselves and up -- go out as several launches
+ *   pair lists (ppk_dist_pairs_dev)
+ *     "pairs_scratch_mb" (1 024)  what the scratch of one chunk of the list (its row image and counts) may take as
+ *                          allocated: a chunk holds as many pairs as keep 2 x pairs x (bytes of one sample's sketch)
+ *                          within four fifths of it (a scratch slot is allocated with a quarter to spare); at least one
+ *     "pairs_chunk" (0)    pairs per chunk, whatever the cap says (0 = from the cap; tests)
  *   neighbours from tiles
  *     "knn_list" (0 = sized from n and knn), "knn_warm" (32), "knn_cut" (4)  the candidate list, its staged
  *                          opening and where it is cut back to the best knn per sample
@@ -250,6 +255,31 @@ int ppk_dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmer
                        long long *d_edges, size_t cap,
                        unsigned long long *d_n_edges,
                        unsigned long long *d_n_failed, void *stream);
+
+/* Kernel 1 for a LIST of pairs: the rows ppk_dist_dev would write for them, without the matrix.  What the reference
+ * looks up in its dense matrix -- scripts/poppunk_add_weights.py, process_weights (PopPUNK/network.py:646-674), the
+ * subsample a model is fitted on (PopPUNK/models.py:246-254,:520-534) -- is computed here from the resident sketches.
+ *   pair p             : (d_i[p*stride], d_j[p*stride]), device int64, stride 1 or 2 (an int64 [m][2] edge list goes
+ *                        in unchanged).  Ids are edge ids as in ppk_edge_weights_dev: with a = min - int_offset and
+ *                        b = max - int_offset, qry == NULL: samples a < b of `ref`; otherwise ref sample a < n_ref and
+ *                        query b - n_ref.  Either orientation, duplicates allowed.
+ *   d_out              : row p belongs to pair p: float [n_pairs][2], or float [n_pairs][nk] with PPK_FLAG_JACCARD,
+ *                        or uint32 [n_pairs][nk] with PPK_FLAG_COUNTS; the bits ppk_dist_dev writes into that pair's
+ *                        row of the dense result (same databases, k list, random table, flags and ext_* options).
+ *   d_n_failed         : device uint64 (nullable), incremented once per listed occurrence of a pair with < 2 usable k.
+ * The ids are checked on the device before a sketch is read through them: PPK_ERR_ARG, naming the first offending
+ * pair, for an id out of range, a == b in a self job, or both ids on one side of a ref x query job; d_out is then
+ * untouched.  That check's read-back is the call's one synchronisation; the list is then worked through in chunks
+ * (options "pairs_scratch_mb", "pairs_chunk") whose scratch does not grow with the list.  n_pairs == 0 is a no-op. */
+int ppk_dist_pairs_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, const float *random_tbl,
+                       size_t n_clu, int flags, const long long *d_i, const long long *d_j, size_t stride,
+                       size_t n_pairs, long long int_offset, void *d_out, unsigned long long *d_n_failed,
+                       void *stream);
+/* Host arrays (i, j int64 [n_pairs]; out as d_out; n_failed nullable, set, not incremented), on the databases'
+ * device; blocking. */
+int ppk_dist_pairs(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, const float *random_tbl, size_t n_clu,
+                   int flags, const long long *i, const long long *j, size_t n_pairs, long long int_offset, void *out,
+                   unsigned long long *n_failed);
 
 /* ------------------------------------------------------------------------
  * N processes, N GPUs of one node, ONE result matrix ("peers write directly at final
@@ -896,6 +926,9 @@ int ppk_mst(const long long *i, const long long *j, const float *w, size_t n_edg
  * network.py:2108-2117.) */
 int ppk_edge_weights_dev(const float *d_dist, size_t n_rows, const long long *d_i, const long long *d_j, size_t stride,
                          size_t n_edges, size_t n_ref, long long int_offset, int weights_type, float *d_w, void *stream);
+/* The "euclidean" weights of rows that are the edges' own already (ppk_dist_pairs_dev of the edge list): d_w[k] = the
+ * same un-fused float32 statement on row k of d_rows float32 [n_rows][2].  Enqueues only. */
+int ppk_row_norms_dev(const float *d_rows, size_t n_rows, float *d_w, void *stream);
 
 /* ------------------------------------------------------------------------
  * Neighbour-joining trees.  Exact neighbour joining of n samples' core distances, with the join and

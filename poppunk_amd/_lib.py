@@ -107,6 +107,7 @@ SIGNATURES = {
     "ppk_mst_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "ppk_mst": (C.c_int, [_llp, _llp, _f32p, _sz, _sz, C.c_int, _llp, _ullp, _i32p]),
     "ppk_edge_weights_dev": (C.c_int, [_vp, _sz, _vp, _vp, _sz, _sz, _sz, C.c_longlong, C.c_int, _vp, _vp]),
+    "ppk_row_norms_dev": (C.c_int, [_vp, _sz, _vp, _vp]),
     "ppk_nj_dev": (C.c_int, [_vp, C.c_int, _sz, _sz, _sz, _vp, _vp, _vp]),
     "ppk_nj": (C.c_int, [_f32p, _sz, C.c_int, _llp, _f64p]),
     "ppk_embed_weights_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz, C.c_double, _vp, _vp, _vp]),
@@ -148,6 +149,9 @@ SIGNATURES = {
     "ppk_rows_in_band": (_sz, [_sz, _sz, _sz, _sz]),
     "ppk_band_split": (C.c_int, [_sz, _sz, C.c_int, _szp]),
     "ppk_dist_dev": (C.c_int, [_vp, _vp, _i32p, _f32p, _sz, C.c_int, _sz, _sz, _vp, _vp, _vp]),
+    "ppk_dist_pairs_dev": (C.c_int, [_vp, _vp, _i32p, _f32p, _sz, C.c_int, _vp, _vp, _sz, _sz, C.c_longlong, _vp, _vp,
+                                     _vp]),
+    "ppk_dist_pairs": (C.c_int, [_vp, _vp, _i32p, _f32p, _sz, C.c_int, _llp, _llp, _sz, C.c_longlong, _vp, _ullp]),
     "ppk_dist_edges_dev": (C.c_int, [_vp, _vp, _i32p, _f32p, _sz, C.c_int, _sz, _sz, C.c_int,
                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _vp,
                                      _sz, _vp, _vp, _vp]),

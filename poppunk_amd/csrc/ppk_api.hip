@@ -68,6 +68,8 @@ const OptionEntry kOptions[] = {
     {"knn_lane_lists", "PPK_KNN_LANE_LISTS", &PpkConfig::knn_lane_lists},
     {"ks_grid_pad", "PPK_KS_GRID_PAD", &PpkConfig::ks_grid_pad},
     {"ksplit_scratch_mb", "PPK_KSPLIT_SCRATCH_MB", &PpkConfig::ksplit_scratch_mb},
+    {"pairs_scratch_mb", "PPK_PAIRS_SCRATCH_MB", &PpkConfig::pairs_scratch_mb},
+    {"pairs_chunk", "PPK_PAIRS_CHUNK", &PpkConfig::pairs_chunk},
     {"knn_list", "PPK_KNN_LIST", &PpkConfig::knn_list},
     {"knn_warm", "PPK_KNN_WARM", &PpkConfig::knn_warm},
     {"knn_cut", "PPK_KNN_CUT", &PpkConfig::knn_cut},
@@ -924,6 +926,58 @@ extern "C" int ppk_dist_dev(const ppk_db *ref, const ppk_db *qry, const int32_t 
   job.q_begin = q_begin, job.q_end = q_end, job.d_out = d_out, job.d_n_failed = d_n_failed;
   job.d_lut = d_lut, job.lut_ready = lut_ready, job.s = s;
   return ppk_launch_dist(job);
+}
+
+extern "C" int ppk_dist_pairs_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, const float *random_tbl,
+                                  size_t n_clu, int flags, const long long *d_i, const long long *d_j, size_t stride,
+                                  size_t n_pairs, long long int_offset, void *d_out, unsigned long long *d_n_failed,
+                                  void *stream) {
+  int rc = ppk_check_pair(ref, qry, kmers, 0, 0);
+  if (rc != PPK_OK) return rc;
+  if (stride != 1 && stride != 2) return ppk_fail(PPK_ERR_ARG, "ppk_dist_pairs: stride must be 1 or 2");
+  if (n_pairs == 0) return PPK_OK;
+  if (!d_i || !d_j || !d_out) return ppk_fail(PPK_ERR_ARG, "ppk_dist_pairs: NULL array");
+  if (n_pairs >= ((size_t)1 << 40)) return ppk_fail(PPK_ERR_ARG, "ppk_dist_pairs: n_pairs must be < 2^40");
+  DeviceGuard guard(ref->device);
+  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(ref->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  PpkCall call(ref->device, s);
+  PairsJob job;
+  float *d_rtab = nullptr;
+  rc = stage_tables(ref, kmers, random_tbl, n_clu, flags, s, &job.d_lut, &d_rtab, &job.lut_ready);
+  if (rc != PPK_OK) return rc;
+  job.d_rtab = d_rtab;
+  job.ref = ref, job.qry = qry, job.kmers = kmers, job.n_clu = job.d_rtab ? n_clu : 1, job.flags = flags;
+  job.d_i = d_i, job.d_j = d_j, job.stride = stride, job.n_pairs = n_pairs, job.int_offset = int_offset;
+  job.d_out = d_out, job.d_n_failed = d_n_failed, job.s = s;
+  return ppk_launch_pairs(job);
+}
+
+extern "C" int ppk_dist_pairs(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, const float *random_tbl,
+                              size_t n_clu, int flags, const long long *i, const long long *j, size_t n_pairs,
+                              long long int_offset, void *out, unsigned long long *n_failed) {
+  if (!ref) return ppk_fail(PPK_ERR_ARG, "ref database / kmers missing");
+  if (n_failed) *n_failed = 0;
+  if (n_pairs && (!i || !j || !out)) return ppk_fail(PPK_ERR_ARG, "ppk_dist_pairs: NULL array");
+  const size_t row_words = (flags & (PPK_FLAG_COUNTS | PPK_FLAG_JACCARD)) ? ref->nk : 2;
+  long long *d_i, *d_j;
+  uint32_t *d_out;
+  unsigned long long *d_nf;
+  return ppk_host_frame(ref->device, [&](Carve &c) {
+    c.take(d_i, n_pairs).take(d_j, n_pairs).take(d_out, n_pairs * row_words).take(d_nf, 1);
+  }, [&]() -> int {
+    if (n_pairs) {
+      PPK_HIP(hipMemcpy(d_i, i, n_pairs * 8, hipMemcpyHostToDevice));
+      PPK_HIP(hipMemcpy(d_j, j, n_pairs * 8, hipMemcpyHostToDevice));
+    }
+    PPK_HIP(hipMemset(d_nf, 0, 8));
+    const int rc = ppk_dist_pairs_dev(ref, qry, kmers, random_tbl, n_clu, flags, d_i, d_j, 1, n_pairs, int_offset, d_out,
+                                      d_nf, nullptr);
+    if (rc != PPK_OK) return rc;
+    if (n_pairs) PPK_HIP(hipMemcpy(out, d_out, n_pairs * row_words * 4, hipMemcpyDeviceToHost));
+    if (n_failed) PPK_HIP(hipMemcpy(n_failed, d_nf, 8, hipMemcpyDeviceToHost));
+    return PPK_OK;
+  });
 }
 
 // The fused edge list of a band: the line boundary (model == NULL) or the label test of a BGMM model

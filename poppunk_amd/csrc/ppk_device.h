@@ -168,6 +168,26 @@ __device__ __forceinline__ float ppk_line_dist(float x0, float y0, float x_max, 
   return side;
 }
 
+// The correctly rounded float32 square root of s >= 0, as numpy's: the device sqrt (measured 1 ulp off) corrected
+// against the midpoints to its neighbours, whose squares (25-bit by 25-bit) are exact in double.
+__device__ __forceinline__ float sqrt_rn(float s) {
+  float r = __fsqrt_rn(s);
+  if (!(s > 0.0f) || isinf(s)) return r;
+  const double ds = (double)s;
+  for (int it = 0; it < 2; ++it) {
+    const float up = nextafterf(r, INFINITY), dn = nextafterf(r, 0.0f);
+    const double hi = ((double)r + (double)up) * 0.5, lo = ((double)r + (double)dn) * 0.5;
+    if (hi * hi < ds) r = up;
+    else if (lo * lo > ds) r = dn;
+    else break;
+  }
+  return r;
+}
+// process_weights' "euclidean" (PopPUNK/network.py:646-674): float32, nothing fused, the root as numpy's
+__device__ __forceinline__ float ppk_euclid(float x0, float x1) {
+  return sqrt_rn(__fadd_rn(__fmul_rn(x0, x0), __fmul_rn(x1, x1)));
+}
+
 // ---- the x / scale rule and the 2-D Gaussian form ----
 // BGMMFit assignment of one row (PopPUNK/bgmm.py:100-176, PopPUNK/models.py:181-187), the ONE statement every
 // path uses (kernel 2, the fused tile epilogues, the DBSCAN assignment's scaling and the BGMM fit's E-step), so that

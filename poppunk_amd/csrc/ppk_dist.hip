@@ -1052,6 +1052,69 @@ dist_kernel_v2_rank(const uint64_t *__restrict__ refT, const uint64_t *__restric
 // ---- generic fallback: counts -> distances when nk * count-bits does not fit 128 bits ---------
 // (e.g. 17 k-mer lengths at s = 10 000).  dist_kernel* write the raw counts, this kernel does
 // a4-a6 per row with the expression order of the CPU statement.
+// (q, r) of distance row `row` of a job: the "query" and the "ref" sample (ppk.h: self: row <-> (q < r), condensed)
+__device__ __forceinline__ void row_samples(size_t row, int self, size_t n_ref, size_t &q, size_t &r) {
+  if (self) {
+    // condensed row -> (q, r): largest q with q*n - q(q+1)/2 <= row
+    const double d = sqrt((double)(4 * n_ref * (n_ref - 1)) - 8.0 * (double)row - 7.0);
+    long long qi = (long long)n_ref - 2 - (long long)floor(d / 2.0 - 0.5);
+    if (qi < 0) qi = 0;
+    while (qi > 0 && (size_t)qi * n_ref - ((size_t)qi * ((size_t)qi + 1)) / 2 > row) --qi;
+    while ((size_t)(qi + 1) * n_ref - ((size_t)(qi + 1) * ((size_t)qi + 2)) / 2 <= row) ++qi;
+    q = (size_t)qi;
+    r = row - (q * n_ref - (q * (q + 1)) / 2) + q + 1;
+  } else {
+    q = row / n_ref;
+    r = row % n_ref;
+  }
+}
+
+// One row of the generic regression: `cnt` its nk counts (cnt[k * k_stride]), (q, r) its samples (read only with a
+// multi-cluster table).  The dense route names the row by its index, the pair-list route by its samples.
+__device__ __forceinline__ bool regress_counts_row(const uint32_t *__restrict__ cnt, size_t k_stride, size_t q, size_t r,
+                                                   int nk, const int *__restrict__ kmers, size_t s64, size_t bbits,
+                                                   const float *__restrict__ rtab, int n_clu,
+                                                   const uint16_t *__restrict__ ref_clu,
+                                                   const uint16_t *__restrict__ qry_clu, float scale_x, float scale_y,
+                                                   int ext_adjust, int ext_skip, float2 &v) {
+  bool failed = false;
+  const double tol = 5.0 / (double)(s64 * 64);
+  double sx = 0.0, sxx = 0.0, sy = 0.0, sxy = 0.0;
+  int n = 0;
+  bool open = true;
+  for (int k = 0; k < nk; ++k) {
+    double jr = 0.0;
+    if (rtab) {
+      const int cr = (n_clu > 1 && ref_clu) ? ref_clu[r] : 0;
+      const int cq = (n_clu > 1 && qry_clu) ? qry_clu[q] : 0;
+      jr = (double)rtab[((size_t)k * n_clu + cr) * n_clu + cq];
+    }
+    const double j = observed_excess(jaccard_obs(cnt[(size_t)k * k_stride], s64, bbits, ext_adjust), jr);
+    open = (ext_skip || open) && !(j < tol);
+    if (open) {
+      const double x = (double)kmers[k], y = log(j);
+      sx += x;
+      sxx += x * x;
+      sy += y;
+      sxy += x * y;
+      ++n;
+    }
+  }
+  float core = 0.0f, acc = 0.0f;
+  if (n < 2) {
+    failed = true;
+  } else {
+    const double dn = (double)n;
+    const double slope = (dn * sxy - sx * sy) / (dn * sxx - sx * sx);
+    const double icpt = (sy - slope * sx) / dn;
+    core = slope < 0.0 ? (float)(1.0 - exp(slope)) : 0.0f;
+    acc = icpt < 0.0 ? (float)(1.0 - exp(icpt)) : 0.0f;
+  }
+  v.x = __fdiv_rn(core, scale_x);
+  v.y = __fdiv_rn(acc, scale_y);
+  return failed;
+}
+
 __global__ void __launch_bounds__(256)
 regress_counts_kernel(const uint32_t *__restrict__ counts, size_t n_rows, size_t row_base, int self,
                       size_t n_ref, int nk, const int *__restrict__ kmers, size_t s64, size_t bbits,
@@ -1063,57 +1126,10 @@ regress_counts_kernel(const uint32_t *__restrict__ counts, size_t n_rows, size_t
   bool failed = false;
   if (i < n_rows) {
     size_t q = 0, r = 0;
-    if (rtab && n_clu > 1) {
-      const size_t row = row_base + i;
-      if (self) {
-        // condensed row -> (q, r): largest q with q*n - q(q+1)/2 <= row
-        const double d = sqrt((double)(4 * n_ref * (n_ref - 1)) - 8.0 * (double)row - 7.0);
-        long long qi = (long long)n_ref - 2 - (long long)floor(d / 2.0 - 0.5);
-        if (qi < 0) qi = 0;
-        while (qi > 0 && (size_t)qi * n_ref - ((size_t)qi * ((size_t)qi + 1)) / 2 > row) --qi;
-        while ((size_t)(qi + 1) * n_ref - ((size_t)(qi + 1) * ((size_t)qi + 2)) / 2 <= row) ++qi;
-        q = (size_t)qi;
-        r = row - (q * n_ref - (q * (q + 1)) / 2) + q + 1;
-      } else {
-        q = row / n_ref;
-        r = row % n_ref;
-      }
-    }
-    const double tol = 5.0 / (double)(s64 * 64);
-    double sx = 0.0, sxx = 0.0, sy = 0.0, sxy = 0.0;
-    int n = 0;
-    bool open = true;
-    for (int k = 0; k < nk; ++k) {
-      double jr = 0.0;
-      if (rtab) {
-        const int cr = (n_clu > 1 && ref_clu) ? ref_clu[r] : 0;
-        const int cq = (n_clu > 1 && qry_clu) ? qry_clu[q] : 0;
-        jr = (double)rtab[((size_t)k * n_clu + cr) * n_clu + cq];
-      }
-      const double j = observed_excess(jaccard_obs(counts[i * nk + k], s64, bbits, ext_adjust), jr);
-      open = (ext_skip || open) && !(j < tol);
-      if (open) {
-        const double x = (double)kmers[k], y = log(j);
-        sx += x;
-        sxx += x * x;
-        sy += y;
-        sxy += x * y;
-        ++n;
-      }
-    }
-    float core = 0.0f, acc = 0.0f;
-    if (n < 2) {
-      failed = true;
-    } else {
-      const double dn = (double)n;
-      const double slope = (dn * sxy - sx * sy) / (dn * sxx - sx * sx);
-      const double icpt = (sy - slope * sx) / dn;
-      core = slope < 0.0 ? (float)(1.0 - exp(slope)) : 0.0f;
-      acc = icpt < 0.0 ? (float)(1.0 - exp(icpt)) : 0.0f;
-    }
+    if (rtab && n_clu > 1) row_samples(row_base + i, self, n_ref, q, r);
     float2 v;
-    v.x = __fdiv_rn(core, scale_x);
-    v.y = __fdiv_rn(acc, scale_y);
+    failed = regress_counts_row(counts + i * nk, 1, q, r, nk, kmers, s64, bbits, rtab, n_clu, ref_clu, qry_clu, scale_x,
+                                scale_y, ext_adjust, ext_skip, v);
     out[i] = v;
   }
   if (n_failed) {
@@ -1185,6 +1201,26 @@ __device__ __forceinline__ void fit_packed(const PackRows &pk, const double *__r
   fit_general(pk, lut + cp_off, p, core, acc, failed);
 }
 
+// One row of the k-split regression: its counts at counts[k * n_rows] (one piece per k unless p.k_split says more),
+// (q, r) its samples, read only with a multi-cluster table (ref_clu non-null).
+__device__ __forceinline__ bool regress_packed_row(const uint32_t *__restrict__ counts, size_t n_rows, int slices,
+                                                   size_t q, size_t r, const double *__restrict__ lut,
+                                                   const uint16_t *__restrict__ ref_clu,
+                                                   const uint16_t *__restrict__ qry_clu, const DistParams &p,
+                                                   float2 &v) {
+  bool failed = false;
+  size_t cp = 0;
+  if (p.n_clu > 1 && ref_clu) cp = (size_t)ref_clu[r] * p.n_clu + (qry_clu ? qry_clu[q] : 0);
+  PackRows pk;      // a k's blocks were counted in `k_split` pieces: [k * slices + piece][row]
+  pk.counts = counts;
+  pk.n_rows = n_rows;
+  pk.slices = slices;
+  float core, acc;
+  fit_packed(pk, lut, cp * p.lut_cpstride, p, core, acc, failed);
+  v = make_float2(core, acc);
+  return failed;
+}
+
 __global__ void __launch_bounds__(256)
 regress_packed_kernel(const uint32_t *__restrict__ counts, size_t n_rows, const double *__restrict__ lut,
                       const uint16_t *__restrict__ ref_clu, const uint16_t *__restrict__ qry_clu,
@@ -1193,34 +1229,177 @@ regress_packed_kernel(const uint32_t *__restrict__ counts, size_t n_rows, const 
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   bool failed = false;
   if (i < n_rows) {
-    size_t cp = 0;
-    if (p.n_clu > 1 && ref_clu) {
-      const size_t row = p.row_base + i, n_ref = p.n_ref;
-      size_t q, r;
-      if (p.self) {
-        // condensed row -> (q, r): largest q with q*n - q(q+1)/2 <= row
-        const double d = sqrt((double)(4 * n_ref * (n_ref - 1)) - 8.0 * (double)row - 7.0);
-        long long qi = (long long)n_ref - 2 - (long long)floor(d / 2.0 - 0.5);
-        if (qi < 0) qi = 0;
-        while (qi > 0 && (size_t)qi * n_ref - ((size_t)qi * ((size_t)qi + 1)) / 2 > row) --qi;
-        while ((size_t)(qi + 1) * n_ref - ((size_t)(qi + 1) * ((size_t)qi + 2)) / 2 <= row) ++qi;
-        q = (size_t)qi;
-        r = row - (q * n_ref - (q * (q + 1)) / 2) + q + 1;
-      } else {
-        q = row / n_ref;
-        r = row % n_ref;
-      }
-      cp = (size_t)ref_clu[r] * p.n_clu + (qry_clu ? qry_clu[q] : 0);
-    }
-    PackRows pk;      // a k's blocks were counted in `k_split` pieces: [k * slices + piece][row]
-    pk.counts = counts + i;
-    pk.n_rows = n_rows;
-    pk.slices = p.k_split;
-    float core, acc;
-    fit_packed(pk, lut, cp * p.lut_cpstride, p, core, acc, failed);
-    out[i] = make_float2(core, acc);
+    size_t q = 0, r = 0;
+    if (p.n_clu > 1 && ref_clu) row_samples(p.row_base + i, p.self, p.n_ref, q, r);
+    float2 v;
+    failed = regress_packed_row(counts + i, n_rows, p.k_split, q, r, lut, ref_clu, qry_clu, p, v);
+    out[i] = v;
   }
   if (n_failed) {
+    const uint64_t fm = __ballot(failed);
+    if (fm && (threadIdx.x & 63) == 0) atomicAdd(n_failed, (unsigned long long)__popcll(fm));
+  }
+}
+
+// ---- pair lists: the rows of listed pairs, without the matrix (ppk_dist_pairs_dev) -----------------
+// Per chunk of the list: the samples it names get a slot each (mark), their sketches are gathered out of
+// [k][word][sample] into a row image R[slot][(k * bbits + plane) * s64 + block] by an LDS tile transpose (the
+// inverse of transpose_kernel, planes outermost within a k so that the lanes of a pair read consecutive words), a
+// group of lanes counts each pair's matches per k from two rows, and the row is fitted by the statements of the dense
+// route (regress_packed_row, regress_counts_row, the tiles' Jaccard statement).  The counts are integers, so a pair's
+// bits do not depend on the chunk, the slot or the lanes that counted it.
+struct PairsGeom {
+  long long n_ref, n_qry, off;      // n_qry 0: a self job
+  const long long *i, *j;
+  size_t stride;
+};
+constexpr uint32_t kNoSlot = 0xffffffffu, kSlotPending = 0xfffffffeu;
+
+// Edge ids -> a = min - off, b = max - off, as ppk_edge_weights_dev reads them: samples a < b of a self job, ref a and
+// query b - n_ref otherwise.  False for a pair that names no row of the dense result.
+__device__ __forceinline__ bool pair_ends(const PairsGeom &g, size_t p, long long &a, long long &b) {
+  const long long i = g.i[p * g.stride], j = g.j[p * g.stride];
+  a = (i < j ? i : j) - g.off;
+  b = (i < j ? j : i) - g.off;
+  if (g.n_qry == 0) return a >= 0 && b < g.n_ref && a != b;
+  return a >= 0 && a < g.n_ref && b >= g.n_ref && b - g.n_ref < g.n_qry;
+}
+// the "query" and the "ref" sample of a checked pair, in the dense route's meaning (row_samples)
+__device__ __forceinline__ void pair_samples(const PairsGeom &g, long long a, long long b, size_t &q, size_t &r) {
+  q = g.n_qry == 0 ? (size_t)a : (size_t)(b - g.n_ref);
+  r = g.n_qry == 0 ? (size_t)b : (size_t)a;
+}
+
+// the smallest p whose pair names no row (nothing is read through an id here)
+__global__ void __launch_bounds__(256) pairs_validate_kernel(const PairsGeom g, size_t n_pairs, unsigned long long *bad) {
+  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < n_pairs; p += (size_t)gridDim.x * 256) {
+    long long a, b;
+    if (!pair_ends(g, p, a, b)) atomicMin(bad, (unsigned long long)p);
+  }
+}
+
+// slot[u] of every sample u the chunk [p0, p0 + n) names (a self job: u = sample; otherwise refs first, query q at
+// n_ref + q, which is b itself): the order of arrival, counted in slot[n_tot].  The array comes in as all-ones, so the
+// counter's first value is 0 after the increment wraps.  Which slot a sample gets changes no result.
+__global__ void __launch_bounds__(256)
+pairs_mark_kernel(const PairsGeom g, size_t p0, size_t n, uint32_t *slot, size_t n_tot) {
+  for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < 2 * n; t += (size_t)gridDim.x * 256) {
+    long long a, b;
+    pair_ends(g, p0 + (t >> 1), a, b);
+    const size_t u = (size_t)((t & 1) ? b : a);
+    if (atomicCAS(slot + u, kNoSlot, kSlotPending) == kNoSlot) slot[u] = atomicAdd(slot + n_tot, 1u) + 1u;
+  }
+}
+
+// R[slot[s]][c'] = skT[c * npad + s] for the named samples s of one database; c' = (k * bbits + plane) * s64 + block
+// is word c = k * words + block * bbits + plane.  A workgroup moves 32 words x 32 samples: 256-byte runs along the
+// sample axis in, 256-byte runs along the row out; a tile of 32 samples none of which is named is skipped.
+__global__ void __launch_bounds__(256)
+pairs_gather_kernel(const uint64_t *__restrict__ skT, size_t n, size_t npad, const uint32_t *__restrict__ slot,
+                    uint64_t *__restrict__ R, size_t cols, int s64, int bbits) {
+  __shared__ uint64_t tile[32][33];
+  __shared__ uint32_t sl[32];
+  const size_t c0 = (size_t)blockIdx.x * 32, s0 = (size_t)blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  uint32_t mine = kNoSlot;
+  if (threadIdx.x < 32) {
+    if (s0 + threadIdx.x < n) mine = slot[s0 + threadIdx.x];
+    sl[threadIdx.x] = mine;
+  }
+  if (!__syncthreads_or(mine != kNoSlot)) return;
+  const size_t words = (size_t)s64 * bbits;
+  for (int i = ty; i < 32; i += 8) {
+    const size_t cp = c0 + i;
+    if (cp < cols) {
+      const size_t k = cp / words, rem = cp % words, b = rem / s64, blk = rem % s64;
+      tile[i][tx] = skT[(k * words + blk * bbits + b) * npad + s0 + tx];      // (s0 + tx < npad: a multiple of 256)
+    }
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const uint32_t row = sl[i];
+    if (row != kNoSlot && c0 + tx < cols) R[(size_t)row * cols + c0 + tx] = tile[tx][i];
+  }
+}
+
+// Match counts of the chunk's pairs: cnt[k * k_stride + pair * p_stride].  G lanes (a power of two, at most 64) take
+// one pair, lane l the 64-bin blocks l, l + G, ...: per plane bits &= ~(a ^ b) on both halves, as kernel 1, then the
+// popcounts; a k's sum over the G lanes is an integer sum.  A wave works through a contiguous span of the list, 64 / G
+// pairs at a time, so the rows a row-ordered list repeats stay in the cache next to it.
+__global__ void __launch_bounds__(256)
+pairs_counts_kernel(const uint64_t *__restrict__ R, size_t cols, const uint32_t *__restrict__ slot, const PairsGeom g,
+                    size_t p0, size_t n, size_t span, int G, int nk, int s64, int bbits, uint32_t *__restrict__ cnt,
+                    size_t k_stride, size_t p_stride) {
+  const int lane = threadIdx.x & 63, sub = lane / G, l = lane % G;
+  const size_t wave = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+  const size_t lo = wave * span < n ? wave * span : n, hi = lo + span < n ? lo + span : n;
+  for (size_t base = lo; base < hi; base += (size_t)(64 / G)) {      // (wave-uniform)
+    const size_t pl = base + sub;
+    const bool active = pl < hi;
+    const uint64_t *ra = R, *rb = R;
+    if (active) {
+      long long a, b;
+      pair_ends(g, p0 + pl, a, b);
+      ra = R + (size_t)slot[a] * cols;
+      rb = R + (size_t)slot[b] * cols;
+    }
+    for (int k = 0; k < nk; ++k) {
+      uint32_t c = 0;
+      if (active)
+        for (int blk = l; blk < s64; blk += G) {
+          uint32_t x = 0xffffffffu, y = 0xffffffffu;
+          for (int b = 0; b < bbits; ++b) {
+            const size_t w = ((size_t)k * bbits + b) * s64 + blk;
+            const uint64_t va = ra[w], vb = rb[w];
+            x = __builtin_amdgcn_bitop3_b32(x, (uint32_t)va, (uint32_t)vb, 0x90);
+            y = __builtin_amdgcn_bitop3_b32(y, (uint32_t)(va >> 32), (uint32_t)(vb >> 32), 0x90);
+          }
+          c += __popc(x) + __popc(y);
+        }
+      for (int o = G >> 1; o > 0; o >>= 1) c += __shfl_xor(c, o);
+      if (active && l == 0) cnt[(size_t)k * k_stride + pl * p_stride] = c;
+    }
+  }
+}
+
+// The chunk's rows from its counts, one thread per pair.  FIT 0: regress_packed_row on counts [k][pair] (the databases
+// the tile kernels take); 1: regress_counts_row on counts [pair][k] (ppk_unfused); 2: the tiles' Jaccard statement on
+// counts [pair][k].  `out` is the chunk's first row.
+template <int FIT>
+__global__ void __launch_bounds__(256)
+pairs_fit_kernel(const uint32_t *__restrict__ cnt, size_t n, const PairsGeom g, size_t p0,
+                 const double *__restrict__ lut, const uint16_t *__restrict__ ref_clu,
+                 const uint16_t *__restrict__ qry_clu, const float *__restrict__ rtab, const int *__restrict__ kmers,
+                 void *__restrict__ out, unsigned long long *__restrict__ n_failed, const DistParams p) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  bool failed = false;
+  if (i < n) {
+    long long a, b;
+    pair_ends(g, p0 + i, a, b);
+    size_t q, r;
+    pair_samples(g, a, b, q, r);
+    if constexpr (FIT == 2) {
+      for (int k = 0; k < p.nk; ++k) {
+        double jr = 0.0;
+        if (p.random_correct) {
+          const int cr = ref_clu ? ref_clu[r] : 0;
+          const int cq = qry_clu ? qry_clu[q] : 0;
+          jr = (double)rtab[((size_t)k * p.n_clu + cr) * p.n_clu + cq];
+        }
+        static_cast<float *>(out)[i * p.nk + k] =
+            (float)observed_excess(jaccard_obs(cnt[i * p.nk + k], p.s64, p.bbits, p.ext_adjust), jr);
+      }
+    } else {
+      float2 v;
+      if constexpr (FIT == 0)
+        failed = regress_packed_row(cnt + i, n, 1, q, r, lut, ref_clu, qry_clu, p, v);
+      else
+        failed = regress_counts_row(cnt + i * p.nk, 1, q, r, p.nk, kmers, p.s64, p.bbits, rtab, p.n_clu, ref_clu, qry_clu,
+                                    p.scale_x, p.scale_y, p.ext_adjust, p.ext_skip, v);
+      static_cast<float2 *>(out)[i] = v;
+    }
+  }
+  if (FIT != 2 && n_failed) {
     const uint64_t fm = __ballot(failed);
     if (fm && (threadIdx.x & 63) == 0) atomicAdd(n_failed, (unsigned long long)__popcll(fm));
   }
@@ -1701,37 +1880,20 @@ size_t ppk_rows_per_dispatch(const ppk_db *ref) {
   return q_sub < 64 ? 64 : q_sub;
 }
 
-// Kernel 1 for one band that a single dispatch holds
-static int launch_dist_band(const DistJob &job) {
-  const ppk_db *ref = job.ref, *qry = job.qry ? job.qry : ref;
-  const int32_t *kmers = job.kmers;
-  hipStream_t s = job.s;
-  DistParams p = {};
-  p.self = job.qry ? 0 : 1;
-  p.npad_r = ref->npad;
-  p.npad_q = qry->npad;
-  p.n_ref = ref->n;
-  p.q_begin = job.q_begin;
-  p.q_end = job.q_end;
-  p.row_base = p.self ? p.q_begin * ref->n - (p.q_begin * (p.q_begin + 1)) / 2 : p.q_begin * ref->n;
+// What the fit of every route reads of a (database, k list, random table) job: the shape, the table strides, the
+// k-mer lengths, the [EXT] switches, and the weights of the all-k-usable fast path (FitCoef)
+static void fit_params(const ppk_db *ref, const int32_t *kmers, size_t n_clu, int flags, const float *d_rtab,
+                       DistParams &p, FitCoef &coef) {
   p.nk = (int)ref->nk;
   p.s64 = (int)ref->s64;
   p.bbits = (int)ref->bbits;
   const size_t nbins = ref->s64 * 64;
   p.lut_kstride = nbins + 1;
   p.lut_cpstride = (size_t)p.nk * (nbins + 1);
-  p.n_rtiles = (ref->n + 63) / 64;
-  p.n_clu = (int)(job.n_clu ? job.n_clu : 1);
-  p.random_correct = (job.flags & PPK_FLAG_RANDOM_CORRECT) && job.d_rtab ? 1 : 0;
-  p.slope = job.slope;
-  p.inclusive = job.inclusive;
-  p.x_max = job.x_max;
-  p.y_max = job.y_max;
-  p.scale_x = job.scale_x;
-  p.scale_y = job.scale_y;
+  p.n_clu = (int)(n_clu ? n_clu : 1);
+  p.random_correct = (flags & PPK_FLAG_RANDOM_CORRECT) && d_rtab ? 1 : 0;
   p.cnt_bits = count_bits(ref->s64);
   for (int k = 0; k < p.nk && k < PPK_MAX_NK; ++k) p.kmers[k] = kmers[k];
-  FitCoef coef = {};
   {
     double sx = 0.0, sxx = 0.0;
     for (int k = 0; k < p.nk && k < PPK_MAX_NK; ++k) {
@@ -1746,6 +1908,42 @@ static int launch_dist_band(const DistJob &job) {
   }
   p.lut_total = (size_t)p.n_clu * p.n_clu * p.lut_cpstride;
   p.lut32 = (p.lut_total * 16 < ((size_t)1 << 32)) ? 1 : 0;
+  p.ext_adjust = ppk_config().ext_collision_adjust.load() ? 1 : 0;
+  p.ext_skip = ppk_config().ext_fit_skip.load() ? 1 : 0;
+}
+// the log-J and (E, F) tables of such a job into d_lut (stage_tables found no identical earlier call's there)
+static int enqueue_lut(const ppk_db *ref, double *d_lut, const float *d_rtab, const DistParams &p, const FitCoef &coef,
+                       hipStream_t s) {
+  const size_t total = (size_t)p.n_clu * p.n_clu * p.lut_cpstride;
+  hipLaunchKernelGGL(lut_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_lut, d_rtab, p.nk, p.n_clu,
+                     ref->s64 * 64, ref->s64, ref->bbits, p.random_correct, p.ext_adjust, total, coef);
+  PPK_HIP(hipGetLastError());
+  ppk_lut_commit(ref->device, d_lut);
+  return PPK_OK;
+}
+
+// Kernel 1 for one band that a single dispatch holds
+static int launch_dist_band(const DistJob &job) {
+  const ppk_db *ref = job.ref, *qry = job.qry ? job.qry : ref;
+  const int32_t *kmers = job.kmers;
+  hipStream_t s = job.s;
+  DistParams p = {};
+  p.self = job.qry ? 0 : 1;
+  p.npad_r = ref->npad;
+  p.npad_q = qry->npad;
+  p.n_ref = ref->n;
+  p.q_begin = job.q_begin;
+  p.q_end = job.q_end;
+  p.row_base = p.self ? p.q_begin * ref->n - (p.q_begin * (p.q_begin + 1)) / 2 : p.q_begin * ref->n;
+  FitCoef coef = {};
+  fit_params(ref, kmers, job.n_clu, job.flags, job.d_rtab, p, coef);
+  p.n_rtiles = (ref->n + 63) / 64;
+  p.slope = job.slope;
+  p.inclusive = job.inclusive;
+  p.x_max = job.x_max;
+  p.y_max = job.y_max;
+  p.scale_x = job.scale_x;
+  p.scale_y = job.scale_y;
   p.knn = job.knn_args ? job.knn_args[0] : 0;
   p.knn_col = job.knn_args ? job.knn_args[1] : 0;
   p.ablate = 0;
@@ -1753,8 +1951,6 @@ static int launch_dist_band(const DistJob &job) {
   p.ablate = (int)ppk_config().ablate.load();
 #endif
   p.lds_table = ppk_config().lds_table.load() != 0 && !(p.ablate & 32) ? 1 : 0;
-  p.ext_adjust = ppk_config().ext_collision_adjust.load() ? 1 : 0;
-  p.ext_skip = ppk_config().ext_fit_skip.load() ? 1 : 0;
 
   if (job.d_bgmm && !job.d_mask) return ppk_fail(PPK_ERR_STATE, "internal: a BGMM launch needs an edge bitmask");
   // cluster ids only matter when a multi-cluster random-match table is in use
@@ -1796,14 +1992,8 @@ static int launch_dist_band(const DistJob &job) {
   }
   // log-J table, built on the device for this (random table, k list) -- unless an identical earlier call
   // left it there (stage_tables)
-  if (!job.lut_ready) {
-    const size_t total = (size_t)p.n_clu * p.n_clu * p.lut_cpstride;
-    hipLaunchKernelGGL(lut_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, job.d_lut,
-                       job.d_rtab, p.nk, p.n_clu, nbins, ref->s64, ref->bbits, p.random_correct, p.ext_adjust, total,
-                       coef);
-    PPK_HIP(hipGetLastError());
-    ppk_lut_commit(ref->device, job.d_lut);
-  }
+  if (!job.lut_ready)
+    if (const int rc = enqueue_lut(ref, job.d_lut, job.d_rtab, p, coef, s)) return rc;
   // The band's mode.  MODE_KNN -- d_out: candidate arrays, d_mask: KnnState + bounds over n_ref (+ n_qry: a ref x
   // query job) samples.  MODE_BGMM reads the model through the kernel's `out` pointer (MODE_MASK leaves it unused).
   if (job.d_bgmm) a.out = const_cast<ppk_bgmm *>(job.d_bgmm);
@@ -1879,5 +2069,128 @@ int ppk_launch_dist(const DistJob &job) {
     const int rc = launch_dist_band(band);
     if (rc != PPK_OK) return rc;
   }
+  return PPK_OK;
+}
+
+// ---- kernel 1 for a list of pairs -----------------------------------------------------------------------------------
+// Check (the call's one synchronisation), then chunk by chunk: mark, gather, count, fit.  Scratch (SLOT_PAIRS): a slot
+// word per sample, and per chunk the row image (at most 2 x chunk rows, never more than there are samples) and nk
+// counts per pair -- the chunk is sized so that image and counts, as allocated, stay below option "pairs_scratch_mb",
+// whatever the list's length.  Stages (ppk_prof_stages names): pairs_check, pairs_image, pairs_counts, pairs_fit.
+int ppk_launch_pairs(const PairsJob &job) {
+  const ppk_db *ref = job.ref, *qry = job.qry;
+  hipStream_t s = job.s;
+  const int dev = ref->device;
+  const size_t n_ref = ref->n, n_qry = qry ? qry->n : 0, n_tot = n_ref + n_qry, m = job.n_pairs;
+  const size_t nk = ref->nk, cols = nk * ref->words, row_bytes = cols * 8;
+  if ((n_ref + 31) / 32 > 65535 || (n_qry + 31) / 32 > 65535)
+    return ppk_fail(PPK_ERR_ARG, "ppk_dist_pairs: more than 2 097 120 samples in a database");
+  const PairsGeom g = {(long long)n_ref, (long long)n_qry, job.int_offset, job.d_i, job.d_j, job.stride};
+
+  // (four fifths of the cap: a scratch slot is allocated with a quarter to spare, and the cap is on what is allocated)
+  const long long cap_mb = ppk_config().pairs_scratch_mb.load();
+  size_t chunk = ((size_t)(cap_mb > 0 ? cap_mb : 0) << 20) / 5 * 4 / (2 * row_bytes + nk * 4);
+  if (const long long force = ppk_config().pairs_chunk.load(); force > 0) chunk = (size_t)force;
+  if (chunk < 1) chunk = 1;
+  if (chunk > m) chunk = m;
+  if (chunk > ((size_t)1 << 30)) chunk = (size_t)1 << 30;      // (slots are 32-bit)
+  const size_t img_rows = 2 * chunk < n_tot ? 2 * chunk : n_tot;
+
+  unsigned long long *bad;
+  uint32_t *slot, *cnt;
+  int *d_kmers;
+  uint64_t *R;
+  const bool to_out = (job.flags & PPK_FLAG_COUNTS) != 0;
+  int rc = ppk_scratch_carve(dev, SLOT_PAIRS, [&](Carve &c) {
+    c.take(bad, 1).take(slot, n_tot + 1).take(d_kmers, nk).take(cnt, to_out ? 1 : chunk * nk).take(R, img_rows * cols);
+  });
+  if (rc != PPK_OK) return rc;
+
+  // -- the ids, before anything is read through one
+  ppk_prof_stage("pairs_check", s);
+  PPK_HIP(hipMemsetAsync(bad, 0xff, 8, s));
+  hipLaunchKernelGGL(pairs_validate_kernel, dim3(grid_for(m, 256 * 4, 4096)), dim3(256), 0, s, g, m, bad);
+  PPK_HIP(hipGetLastError());
+  const unsigned long long *h = nullptr;
+  rc = ppk_read_back(dev, s, {{bad, 8}}, &h);
+  ppk_prof_stage(nullptr, s);
+  if (rc != PPK_OK) return rc;
+  if (h[0] != ~0ull) {
+    long long i = 0, j = 0;
+    if (!ppk_read_edge(job.d_i, job.d_j, job.stride, nullptr, (size_t)h[0], &i, &j, nullptr))
+      return ppk_fail(PPK_ERR_HIP, "cannot read back the bad pair");
+    const long long a = (i < j ? i : j) - job.int_offset, b = (i < j ? j : i) - job.int_offset;
+    std::string why;
+    if (!qry) why = a == b ? "a sample paired with itself" : "sample id out of range [0, " + std::to_string(n_ref) + ")";
+    else if (a < 0 || (size_t)b >= n_tot) why = "id out of range [0, " + std::to_string(n_tot) + ")";
+    else why = "both ids on one side (refs are [0, " + std::to_string(n_ref) + "), queries follow them)";
+    return ppk_fail(PPK_ERR_ARG, "ppk_dist_pairs: pair " + std::to_string(h[0]) + " (i=" + std::to_string(i) + ", j=" +
+                                     std::to_string(j) + "): " + why);
+  }
+
+  DistParams p = {};
+  FitCoef coef = {};
+  fit_params(ref, job.kmers, job.n_clu, job.flags, job.d_rtab, p, coef);
+  p.self = qry ? 0 : 1;
+  p.n_ref = n_ref;
+  p.scale_x = p.scale_y = 1.0f;
+  const bool use_clu = p.random_correct && p.n_clu > 1;
+  const uint16_t *rclu = use_clu ? ref->d_clu : nullptr, *qclu = use_clu ? (qry ? qry : ref)->d_clu : nullptr;
+  const float *rtab = p.random_correct ? job.d_rtab : nullptr;
+  // the route of the rows: raw counts, Jaccard, the generic regression (what the dense route gives such a database)
+  // or the table fit
+  const bool jaccard = !to_out && (job.flags & PPK_FLAG_JACCARD), unfused = !to_out && !jaccard && ppk_unfused(ref);
+  const bool packed = !to_out && !jaccard && !unfused;
+  if (unfused) PPK_HIP(hipMemcpyAsync(d_kmers, job.kmers, nk * 4, hipMemcpyHostToDevice, s));
+  if (packed && !job.lut_ready)
+    if ((rc = enqueue_lut(ref, job.d_lut, job.d_rtab, p, coef, s)) != PPK_OK) return rc;
+
+  // lanes per pair: the least power of two that holds a k's 64-bin blocks, at most a wave
+  int G = 1;
+  while (G < 64 && (size_t)G < ref->s64) G *= 2;
+  const size_t ppw = 64 / G;
+  const size_t out_row = (job.flags & (PPK_FLAG_COUNTS | PPK_FLAG_JACCARD)) ? nk * 4 : 8;
+  for (size_t p0 = 0; p0 < m; p0 += chunk) {
+    const size_t n = p0 + chunk < m ? chunk : m - p0;
+    ppk_prof_stage("pairs_image", s);
+    PPK_HIP(hipMemsetAsync(slot, 0xff, (n_tot + 1) * 4, s));
+    hipLaunchKernelGGL(pairs_mark_kernel, dim3(grid_for(2 * n, 256 * 2, 4096)), dim3(256), 0, s, g, p0, n, slot, n_tot);
+    hipLaunchKernelGGL(pairs_gather_kernel, dim3((unsigned)((cols + 31) / 32), (unsigned)((n_ref + 31) / 32)), dim3(256),
+                       0, s, ref->d_skT, n_ref, ref->npad, slot, R, cols, (int)ref->s64, (int)ref->bbits);
+    if (qry)
+      hipLaunchKernelGGL(pairs_gather_kernel, dim3((unsigned)((cols + 31) / 32), (unsigned)((n_qry + 31) / 32)),
+                         dim3(256), 0, s, qry->d_skT, n_qry, qry->npad, slot + n_ref, R, cols, (int)ref->s64,
+                         (int)ref->bbits);
+    PPK_HIP(hipGetLastError());
+
+    ppk_prof_stage("pairs_counts", s);
+    // a wave's span of the list: whole groups of pairs, about 16 of them while that leaves the device enough waves
+    size_t waves = (n + ppw * 16 - 1) / (ppw * 16);
+    const size_t min_waves = (size_t)ppk_geometry(dev).cus * 16;
+    if (waves < min_waves) waves = (n + ppw - 1) / ppw < min_waves ? (n + ppw - 1) / ppw : min_waves;
+    const size_t span = ((n + waves - 1) / waves + ppw - 1) / ppw * ppw;
+    const size_t blocks = ((n + span - 1) / span + 3) / 4;
+    uint32_t *c_out = to_out ? static_cast<uint32_t *>(job.d_out) + p0 * nk : cnt;
+    hipLaunchKernelGGL(pairs_counts_kernel, dim3((unsigned)blocks), dim3(256), 0, s, R, cols, slot, g, p0, n, span, G,
+                       (int)nk, (int)ref->s64, (int)ref->bbits, c_out, packed ? n : (size_t)1, packed ? (size_t)1 : nk);
+    PPK_HIP(hipGetLastError());
+
+    if (!to_out) {
+      ppk_prof_stage("pairs_fit", s);
+      void *o = static_cast<char *>(job.d_out) + p0 * out_row;
+      const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+      if (packed)
+        hipLaunchKernelGGL(pairs_fit_kernel<0>, grid, block, 0, s, cnt, n, g, p0, job.d_lut, rclu, qclu, rtab, d_kmers, o,
+                           job.d_n_failed, p);
+      else if (unfused)
+        hipLaunchKernelGGL(pairs_fit_kernel<1>, grid, block, 0, s, cnt, n, g, p0, job.d_lut, rclu, qclu, rtab, d_kmers, o,
+                           job.d_n_failed, p);
+      else
+        hipLaunchKernelGGL(pairs_fit_kernel<2>, grid, block, 0, s, cnt, n, g, p0, job.d_lut, rclu, qclu, rtab, d_kmers, o,
+                           job.d_n_failed, p);
+      PPK_HIP(hipGetLastError());
+    }
+  }
+  ppk_prof_stage(nullptr, s);
   return PPK_OK;
 }

@@ -108,6 +108,8 @@ struct PpkConfig {
   std::atomic<long long> refine_local{1};       // PPK_REFINE_LOCAL: refineFit's local search scores through the bracket handle (ppk_refine_local_*); 0 = every evaluation through ppk_refine_score_dev (same fit)
   std::atomic<long long> density_hot_table{1};  // PPK_DENSITY_HOT_TABLE: ppk_density_counts_dev adds through a per-workgroup LDS table of hot pixels in front of the global atomics (0: every row one global atomic; same counts)
   std::atomic<long long> density_kde_presum{0}; // PPK_DENSITY_KDE_PRESUM: ppk_density_kde_dev sums the terms of lanes of a wave that share a window of nodes before the LDS add, for groups of at least this many lanes (0: every lane adds its own terms; same sums)
+  std::atomic<long long> pairs_scratch_mb{1024}; // PPK_PAIRS_SCRATCH_MB: what the scratch of one chunk of a pair list may take as allocated (ppk_dist_pairs_dev: 2 x pairs x the bytes of one sample's sketch, plus the counts, stays within four fifths of it; same results)
+  std::atomic<long long> pairs_chunk{0};        // PPK_PAIRS_CHUNK: pairs per chunk of a pair list whatever the cap says (0 = from the cap; tests; same results)
   std::atomic<long long> knn_list{0};           // PPK_KNN_LIST: entries of the neighbour-candidate list (0 = sized from n and knn)
   std::atomic<long long> host_parts_rows{16 << 20};   // PPK_HOST_PARTS_ROWS: ... from this many rows up
   std::atomic<long long> host_parts{2};         // PPK_HOST_PARTS: worker threads of a one-device host query (>= 16 Mi rows)
@@ -274,7 +276,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_ASSIGN = 22,                       // the query links' counters, segment starts, overflow list and first ranks
        SLOT_ASSIGN_SORT = 23,                  // ... and, on the sort route only, its (query, label) keys, flags and temp storage
        SLOT_DENSITY = 24,                      // the density grids' coordinates, scale keys and first-offender words
-       SLOT_COUNT = 25 };
+       SLOT_PAIRS = 25,                        // a pair list's first-bad-pair word, sample flags and slots, the chunk's row image, ids and counts
+       SLOT_COUNT = 26 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and
@@ -398,6 +401,25 @@ struct DistJob {
 };
 // enqueues only; a band of more rows than one dispatch holds goes out as several launches
 int ppk_launch_dist(const DistJob &job);
+
+// Kernel 1 for a list of pairs (ppk_dist.hip, ppk_dist_pairs_dev): validated ids in, rows of d_out out.  The caller
+// holds the PpkCall and has staged the tables; synchronises `s` once (the check of the ids).
+struct PairsJob {
+  const ppk_db *ref = nullptr, *qry = nullptr;
+  const int32_t *kmers = nullptr;
+  const float *d_rtab = nullptr;
+  size_t n_clu = 1;
+  int flags = 0;
+  const long long *d_i = nullptr, *d_j = nullptr;
+  size_t stride = 1, n_pairs = 0;
+  long long int_offset = 0;
+  void *d_out = nullptr;
+  unsigned long long *d_n_failed = nullptr;
+  double *d_lut = nullptr;
+  bool lut_ready = false;
+  hipStream_t s = nullptr;
+};
+int ppk_launch_pairs(const PairsJob &job);
 
 // ---- helper threads ----------------------------------------------------------------
 // A host call uses a dozen short-lived helpers (page touchers, per-device workers, hash lanes); starting

@@ -178,22 +178,6 @@ __global__ void __launch_bounds__(kThreads) mst_unrank_kernel(const unsigned cha
 }
 
 // ---- edge weights ------------------------------------------------------------------------------------------------
-// The correctly rounded float32 square root of s >= 0, as numpy's: the device sqrt (measured 1 ulp off) corrected
-// against the midpoints to its neighbours, whose squares (25-bit by 25-bit) are exact in double.
-__device__ __forceinline__ float sqrt_rn(float s) {
-  float r = __fsqrt_rn(s);
-  if (!(s > 0.0f) || isinf(s)) return r;
-  const double ds = (double)s;
-  for (int it = 0; it < 2; ++it) {
-    const float up = nextafterf(r, INFINITY), dn = nextafterf(r, 0.0f);
-    const double hi = ((double)r + (double)up) * 0.5, lo = ((double)r + (double)dn) * 0.5;
-    if (hi * hi < ds) r = up;
-    else if (lo * lo > ds) r = dn;
-    else break;
-  }
-  return r;
-}
-
 __global__ void __launch_bounds__(kThreads) mst_weights_kernel(const float2 *dist, long long n_samples, long long n_ref,
                                                                long long n_qry, long long off, const long long *ei,
                                                                const long long *ej, size_t stride, size_t m, int type,
@@ -216,7 +200,15 @@ __global__ void __launch_bounds__(kThreads) mst_weights_kernel(const float2 *dis
       continue;
     }
     const float2 d = dist[row];
-    w[k] = type == 0 ? d.x : type == 1 ? d.y : sqrt_rn(__fadd_rn(__fmul_rn(d.x, d.x), __fmul_rn(d.y, d.y)));
+    w[k] = type == 0 ? d.x : type == 1 ? d.y : ppk_euclid(d.x, d.y);
+  }
+}
+
+// process_weights' "euclidean" of rows that are already the edges' own (ppk_dist_pairs_dev's output)
+__global__ void __launch_bounds__(kThreads) row_norms_kernel(const float2 *rows, size_t m, float *w) {
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += (size_t)gridDim.x * blockDim.x) {
+    const float2 d = rows[k];
+    w[k] = ppk_euclid(d.x, d.y);
   }
 }
 
@@ -439,5 +431,15 @@ extern "C" int ppk_edge_weights_dev(const float *d_dist, size_t n_rows, const lo
     return ppk_fail(PPK_ERR_ARG, "ppk_edge_weights: edge " + std::to_string(h[0]) + " (i=" + std::to_string(i) +
                                      ", j=" + std::to_string(j) + ") has no row in the distance matrix");
   }
+  return PPK_OK;
+}
+
+extern "C" int ppk_row_norms_dev(const float *d_rows, size_t n_rows, float *d_w, void *stream) {
+  if (n_rows && (!d_rows || !d_w)) return ppk_fail(PPK_ERR_ARG, "ppk_row_norms: NULL array");
+  if (!n_rows) return PPK_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(row_norms_kernel, dim3(grid_for(n_rows, kThreads * 4, 4096)), dim3(kThreads), 0, s,
+                     reinterpret_cast<const float2 *>(d_rows), n_rows, d_w);
+  PPK_HIP(hipGetLastError());
   return PPK_OK;
 }

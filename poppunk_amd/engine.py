@@ -1137,6 +1137,94 @@ def edge_weights_dev(dist_t, edges_t, weights_type="core", n_ref=0, int_offset=0
     return w[:m]
 
 
+def dist_pairs(ref, qry=None, kmers=None, random_tbl=None, pairs=None, random_correct=True, jaccard=False,
+               counts=False, int_offset=0):
+    """Kernel 1 for a LIST of pairs (ppk_dist_pairs_dev): the rows `dist` would write for them, bit
+    for bit, without the matrix.  pairs: an int64 [m, 2] CUDA tensor or an (i_t, j_t) pair, edge ids as
+    edge_weights_dev reads them (self: two samples of `ref`; otherwise a ref r and n_ref + q; either order, duplicates
+    allowed, `int_offset` subtracted).  Returns (out, n_failed): float32 [m, 2], float32 [m, nk] (jaccard) or int32
+    [m, nk] (counts), row p for pair p, and a 1-element int64 CUDA tensor counting the listed pairs with fewer than 2
+    usable k-mer lengths.  Raises, naming the first offending pair, before anything is written."""
+    torch = _torch()
+    _check_pair(ref, qry)
+    if pairs is None:
+        raise ValueError("dist_pairs needs a pair list")
+    i_t, j_t = _mst_stream(pairs)
+    m, stride = _edge_stream(i_t, j_t, None)
+    if i_t.device.index != ref.device:
+        raise ValueError("the pair list is not on the databases' device")
+    kmers, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
+    flags = (FLAG_RANDOM_CORRECT if random_correct else 0) | (FLAG_JACCARD if jaccard else 0) \
+        | (FLAG_COUNTS if counts else 0)
+    cols = ref.nk if (jaccard or counts) else 2
+    dev = "cuda:%d" % ref.device
+    with torch.cuda.device(ref.device):
+        out = torch.empty((m, cols), dtype=torch.int32 if counts else torch.float32, device=dev)
+        n_failed = torch.zeros(1, dtype=torch.int64, device=dev)
+        rc = _lib.lib().ppk_dist_pairs_dev(ref._h, qry._h if qry is not None else None,
+                                           kmers.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr, n_clu, flags,
+                                           C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride, m,
+                                           int(int_offset), C.c_void_p(out.data_ptr()),
+                                           C.c_void_p(n_failed.data_ptr()), _stream_ptr(ref.device))
+        _lib.check(rc, "ppk_dist_pairs_dev")
+    return out, n_failed
+
+
+def _isqrt(x):
+    """floor(sqrt(x)) of a non-negative int64 array, exactly: the double root, then an integer fix-up (above 2^52 the
+    double rounds, and a row index of a few million samples is)."""
+    x = np.asarray(x, dtype=np.int64)
+    r = np.sqrt(x.astype(np.float64)).astype(np.int64)
+    for _ in range(2):
+        r = np.where(r * r > x, r - 1, r)
+    for _ in range(2):
+        r = np.where((r + 1) * (r + 1) <= x, r + 1, r)
+    return r
+
+
+def rows_to_pairs(rows, n_ref, n_qry=0):
+    """Distance rows -> edge ids, the inverse of the row order (PopPUNK/utils.py:199-226 iterDistRows,
+    src/boundary.cpp:22-37) in exact integer arithmetic.  n_qry 0: condensed rows of n_ref samples -> (i, j), i < j;
+    otherwise row = q * n_ref + r -> (r, n_ref + q).  numpy int64 [m] in, int64 [m, 2] out."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+    n = int(n_ref)
+    n_rows = n * int(n_qry) if n_qry else n * (n - 1) // 2
+    if rows.size and (rows.min() < 0 or rows.max() >= n_rows):
+        raise ValueError("row index outside [0, %d)" % n_rows)
+    out = np.empty((rows.size, 2), dtype=np.int64)
+    if n_qry:
+        out[:, 0] = rows % n
+        out[:, 1] = n + rows // n
+        return out
+    # rows from the END of the triangle, t = n_rows - 1 - row, lie in reversed row c with c (c + 1) / 2 <= t:
+    # c = floor((sqrt(8 t + 1) - 1) / 2), and i = n - 2 - c
+    t = (n_rows - 1) - rows
+    c = (_isqrt(8 * t + 1) - 1) // 2
+    i = n - 2 - c
+    out[:, 0] = i
+    out[:, 1] = i + 1 + (rows - (i * n - i * (i + 1) // 2))
+    return out
+
+
+def edge_weights_from_sketches(ref, qry, kmers, random_tbl, edges_t, weights_type="core", int_offset=0,
+                               random_correct=True):
+    """process_weights (PopPUNK/network.py:646-674; scripts/poppunk_add_weights.py) of an edge list with no matrix:
+    the edges' distances come from the resident sketches (dist_pairs).  Returns float32 [m], bit for bit
+    edge_weights_dev(dist(...), edges_t, ...)."""
+    torch = _torch()
+    if weights_type not in WEIGHTS_TYPES:
+        raise ValueError("weights_type must be one of %s" % sorted(WEIGHTS_TYPES))
+    d, _ = dist_pairs(ref, qry, kmers, random_tbl, edges_t, random_correct=random_correct, int_offset=int_offset)
+    if weights_type != "euclidean":
+        return d[:, WEIGHTS_TYPES[weights_type]].contiguous()
+    with torch.cuda.device(d.device):
+        w = torch.empty(max(d.shape[0], 1), dtype=torch.float32, device=d.device)
+        rc = _lib.lib().ppk_row_norms_dev(C.c_void_p(d.data_ptr()), d.shape[0], C.c_void_p(w.data_ptr()),
+                                          _stream_ptr(d.device.index))
+        _lib.check(rc, "ppk_row_norms_dev")
+    return w[:d.shape[0]]
+
+
 NJ_SQUARE, NJ_LONG = 0, 1
 
 

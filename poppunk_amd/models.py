@@ -265,6 +265,35 @@ class RefineBoundary:
 
 
 # ---- BGMM assignment (PopPUNK's default --fit-model bgmm) -----------------------------------------------
+SAMPLE_ROWS_PERMUTE_MAX = 1 << 27
+
+
+def sample_rows(n_rows, max_samples, seed):
+    """The rows a fit trains on when there are more than `max_samples`; None when every row is used.  Up to 2^27 rows
+    this is `DBSCANModel.subsample_index`, the draw the matrix routes make (a permutation's head).  Above that a
+    permutation is the matrix problem again -- 5e9 rows are 40 GB of host memory -- and the rows are
+    `default_rng(seed).choice(n_rows, max_samples, replace=False)`, whose memory is O(max_samples)."""
+    n_rows, max_samples = int(n_rows), int(max_samples)
+    if n_rows <= SAMPLE_ROWS_PERMUTE_MAX:
+        return DBSCANModel.subsample_index(n_rows, max_samples, seed)
+    if n_rows <= max_samples:
+        return None
+    return np.random.default_rng(seed).choice(n_rows, max_samples, replace=False).astype(np.int64, copy=False)
+
+
+def _training_rows(db, kmers, random_tbl, max_samples, seed, rows, random_correct):
+    """float32 [m, 2] CUDA tensor: the distances of the training rows of `db`'s self job, from its sketches."""
+    import torch
+    n_rows = db.n * (db.n - 1) // 2
+    if rows is None:
+        rows = sample_rows(n_rows, max_samples, seed)
+    if rows is None:
+        rows = np.arange(n_rows, dtype=np.int64)
+    pairs_t = torch.as_tensor(engine.rows_to_pairs(rows, db.n), device="cuda:%d" % db.device)
+    dist_t, _ = engine.dist_pairs(db, None, kmers, random_tbl, pairs_t, random_correct=random_correct)
+    return dist_t
+
+
 class BGMMModel:
     """PopPUNK's default model, a Bayesian Gaussian mixture: `BGMMFit.fit` / `.assign` / `.save` / `.load`
     (PopPUNK/models.py:296-465).  The constructor takes fitted arrays (the state `BGMMFit.assign` reads).
@@ -403,6 +432,18 @@ class BGMMModel:
             return y, torch.bincount(y, minlength=params.K).cpu().numpy()
         return cls._fitted(res, scale, seed, "labels" if init_labels is not None else "kmeans++", assign_points,
                            labels_of)
+
+    @classmethod
+    def fit_from_sketches(cls, db, kmers, random_tbl, max_components, max_samples=100000, seed=42, init_labels=None,
+                          n_init=5, rows=None, random_correct=True):
+        """The fit without a distance matrix: the training rows -- `rows`, or `sample_rows` of the
+        self job's n (n - 1) / 2 -- are computed from the resident database `db` as a pair list (engine.dist_pairs),
+        and fitted by `fit_dev` on that [m, 2] tensor as it stands (max_samples=None, assign_points=False): `labels`
+        are the subsample's, `within_label` comes from their counts.  The model equals fit_dev's on the same rows of
+        the dense matrix bit for bit."""
+        dist_t = _training_rows(db, kmers, random_tbl, max_samples, seed, rows, random_correct)
+        return cls.fit_dev(dist_t, max_components, max_samples=None, seed=seed, assign_points=False,
+                           init_labels=init_labels, n_init=n_init)
 
     def plot(self, X, y, outPrefix=None, raster_above=1000000):
         """The two pictures of BGMMFit.plot (models.py:404-408): plot.plot_results into <outPrefix>/<basename>_DPGMM_fit
@@ -590,7 +631,7 @@ class DBSCANModel:
     @staticmethod
     def subsample_index(n_rows, max_samples, seed):
         """Rows of the subsample, in the order they are fitted in; None when every row is used."""
-        if n_rows <= max_samples:
+        if max_samples is None or n_rows <= max_samples:
             return None
         return np.random.default_rng(seed).permutation(n_rows)[:max_samples]
 
@@ -686,6 +727,14 @@ class DBSCANModel:
         if self.assign_points:
             return self.assign_dev(dist_t)
         return torch.as_tensor(self.subsample_labels.astype(np.int32), device=dist_t.device)
+
+    def fit_from_sketches(self, db, kmers, random_tbl, max_num_clusters, min_cluster_prop, max_samples=100000, seed=42,
+                          rows=None, random_correct=True):
+        """`fit_dev` without a distance matrix, as BGMMModel.fit_from_sketches: the training rows come from the
+        resident database as a pair list; returns the subsample's labels (int32 CUDA tensor)."""
+        dist_t = _training_rows(db, kmers, random_tbl, max_samples, seed, rows, random_correct)
+        return self.fit_dev(dist_t, max_num_clusters, min_cluster_prop, max_samples=None, seed=seed,
+                            assign_points=False)
 
     # -- assignment ----------------------------------------------------------------------------------------------
     def assign(self, X, device_id=0):

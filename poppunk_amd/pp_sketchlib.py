@@ -282,6 +282,56 @@ def query_arrays(ref_sk, qry_sk, klist, sketchsize64, bbits, random_table=None, 
     return out, int(n_failed.value)
 
 
+def query_pairs_arrays(ref_sk, qry_sk, klist, sketchsize64, bbits, pairs, random_table=None, ref_clusters=None,
+                       qry_clusters=None, random_correct=True, jaccard=False, counts=False, device=0):
+    """ppk_dist_pairs on in-memory sketch arrays [n, nk, words] (qry_sk=None => self): the rows query_arrays would
+    return for the listed pairs, and only those.  pairs: int64 [m, 2] edge ids (self: two samples; otherwise a ref r
+    and n_ref + q; either order).  Returns (out [m, 2] / [m, nk], n_failed)."""
+    lib = _lib.lib()
+    ref_sk = np.ascontiguousarray(ref_sk, dtype=np.uint64)
+    n_ref, nk, words = ref_sk.shape
+    if words != sketchsize64 * bbits:
+        raise RuntimeError("sketch word count does not match sketchsize64*bbits")
+    kmers = np.ascontiguousarray(klist, dtype=np.int32).ravel()
+    if kmers.size != nk:
+        raise RuntimeError("klist does not match the sketches")
+    if qry_sk is not None:
+        qry_sk = np.ascontiguousarray(qry_sk, dtype=np.uint64)
+        if qry_sk.shape[1:] != ref_sk.shape[1:]:
+            raise RuntimeError("query and reference sketches have different shapes")
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    pi, pj = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+    m = pairs.shape[0]
+    cols = nk if (jaccard or counts) else 2
+    out = np.zeros((m, cols), dtype=np.uint32 if counts else np.float32)
+    tptr, n_clu, rclu, qclu, keep = _table_args(random_table, random_correct, ref_clusters, qry_clusters,
+                                                qry_sk is not None)
+    n_failed = C.c_ulonglong(0)
+    if m == 0:
+        return out, 0
+    u16, u64, ll = C.POINTER(C.c_uint16), C.POINTER(C.c_uint64), C.POINTER(C.c_longlong)
+    handles = []
+    try:
+        for sk, clu in ((ref_sk, rclu), (qry_sk, qclu)):
+            if sk is None:
+                continue
+            h = C.c_void_p()
+            rc = lib.ppk_db_create(int(device), sk.ctypes.data_as(u64), sk.shape[0], nk, sketchsize64, bbits,
+                                   None if clu is None else clu.ctypes.data_as(u16), 0, None, C.byref(h))
+            _lib.check(rc, "ppk_db_create")
+            handles.append(h)
+        rc = lib.ppk_dist_pairs(handles[0], handles[1] if len(handles) > 1 else None,
+                                kmers.ctypes.data_as(C.POINTER(C.c_int32)), tptr, n_clu,
+                                _flags(random_correct, jaccard, counts), pi.ctypes.data_as(ll), pj.ctypes.data_as(ll),
+                                m, 0, C.c_void_p(out.ctypes.data), C.byref(n_failed))
+        _lib.check(rc, "ppk_dist_pairs")
+    finally:
+        for h in handles:
+            lib.ppk_db_destroy(h)
+    del keep
+    return out, int(n_failed.value)
+
+
 def _open_query(ref_db_name, query_db_name, rList, qList, klist, random_correct):
     """The loaded databases and random-match arguments of one queryDatabase-shaped call:
     (ref entry, query entry or None, table, ref clusters, query clusters).  Transient entries are the
