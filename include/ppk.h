@@ -204,6 +204,30 @@ int ppk_db_rank_block_planes(const ppk_db *db, uint8_t *out, size_t cap);
 int ppk_db_fold_planes(const ppk_db *db);
 int ppk_db_fold_block_planes(const ppk_db *db, uint8_t *out, size_t cap);
 int ppk_db_fold_read(const ppk_db *db, int which, uint64_t *out, size_t words);
+/* The two-holder pair.  Almost every value the folded pair still codes has exactly two holders: a chance collision, which
+ * can match in exactly one pair of the triangular job (its higher holder as ref, its lower as query).  Where that lets a
+ * large self job compare fewer planes than both codings above, the database keeps this pair instead: a value with at
+ * least three holders gets 2 + its rank among such values, every other value 0 in the ref-side copy and 1 in the
+ * query-side one, so a position spans E2 = S3 + 2 codes.  The compare then counts every two-holder value's one match
+ * short; the database lists them as events (hi, lo, k), bucketed by (lo / 32, hi / 256), and the tile kernel adds a
+ * tile's events to its counts before the fit: every count and every bit is that of the raw planes.  Built only at 8
+ * planes, at most five k, at most 256 two-holder values per position and 63 events per (pair, k); a database past a cap
+ * keeps the copies above.  Option "rank_fold2" (PPK_RANK_FOLD2, default 1), read at creation: 1 builds the pair where
+ * its plane sum over the blocks is the lowest of the three codings, "rank_fold" is not 0 and the self job runs at least
+ * four rounds of tiles; 0 never; 2 whenever the caps allow (tests).  0 at launch leaves a built pair unread.
+ * ppk_db_fold2_planes / _block_planes / _read: as their fold_ namesakes.  ppk_db_fold2_events: the number of events
+ * (and of buckets: (padded samples / 32) x (padded samples / 256)); ppk_db_fold2_events_read: the buckets + 1 offsets,
+ * bucket (lo / 32) * (padded samples / 256) + hi / 256, and the events, hi % 256 | (lo % 32) << 8 | k << 13, in no
+ * order within a bucket.  ppk_db_rank_counts: what the count pass found, 3 x (1 + nk * sketchsize64) words -- for the
+ * distinct values D, E = S + 2 and E2 = S3 + 2 the maximum over all positions, then per (k, block) -- and three more:
+ * the most two-holder values of a position, their number over all positions, 1 if the per-pair cap was hit; returns the
+ * words there are (0: no count pass ran) and fills `out` if `cap` holds them. */
+int ppk_db_fold2_planes(const ppk_db *db);
+int ppk_db_fold2_block_planes(const ppk_db *db, uint8_t *out, size_t cap);
+int ppk_db_fold2_read(const ppk_db *db, int which, uint64_t *out, size_t words);
+size_t ppk_db_fold2_events(const ppk_db *db, size_t *n_buckets);
+int ppk_db_fold2_events_read(const ppk_db *db, uint32_t *off, size_t n_off, uint16_t *ev, size_t n_ev);
+size_t ppk_db_rank_counts(const ppk_db *db, uint32_t *out, size_t cap);
 
 /* Number of distance rows for rows q in [q_begin, q_end) (self: n_qry == 0). */
 size_t ppk_rows_in_band(size_t n_ref, size_t n_qry, size_t q_begin, size_t q_end);

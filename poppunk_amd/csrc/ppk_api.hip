@@ -53,6 +53,7 @@ const OptionEntry kOptions[] = {
     {"rank_planes", "PPK_RANK_PLANES", &PpkConfig::rank_planes},
     {"rank_short", "PPK_RANK_SHORT", &PpkConfig::rank_short},
     {"rank_fold", "PPK_RANK_FOLD", &PpkConfig::rank_fold},
+    {"rank_fold2", "PPK_RANK_FOLD2", &PpkConfig::rank_fold2},
     {"lds_table", "PPK_LDS_TABLE", &PpkConfig::lds_table},
     {"ksplit", "PPK_KSPLIT", &PpkConfig::ksplit},
     {"ksplit_slices", "PPK_KSPLIT_SLICES", &PpkConfig::ksplit_slices},
@@ -394,6 +395,13 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   db->d_foldR = db->d_foldQ = nullptr;
   db->fold_planes = 0;
   for (unsigned &w : db->fold_short) w = 0;
+  db->d_fold2R = db->d_fold2Q = nullptr;
+  db->d_fold2_ev = nullptr;
+  db->d_fold2_off = nullptr;
+  db->fold2_planes = 0;
+  db->fold2_qt = db->fold2_rt = 0;
+  db->fold2_events = 0;
+  for (unsigned &w : db->fold2_short) w = 0;
   const size_t cols = nk * db->words;
   const size_t in_bytes = n * cols * sizeof(uint64_t);
   const size_t out_bytes = db->npad * cols * sizeof(uint64_t);
@@ -403,6 +411,8 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
     if (db->d_skR) (void)hipFree(db->d_skR);
     if (db->d_foldR) (void)hipFree(db->d_foldR);
     if (db->d_foldQ) (void)hipFree(db->d_foldQ);
+    for (void *ptr : {(void *)db->d_fold2R, (void *)db->d_fold2Q, (void *)db->d_fold2_ev, (void *)db->d_fold2_off})
+      if (ptr) (void)hipFree(ptr);
     if (db->d_clu) (void)hipFree(db->d_clu);
     delete db;
     return ppk_fail(code, msg);
@@ -442,10 +452,18 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   // holder matches nothing in a self job, so the folded pair (ppk_db::d_foldR / d_foldQ) gives all of them two reserved
   // codes and spans E = S + 2 codes where the injective copy spans D.  The pair is built instead of the injective copy
   // where it compares fewer planes over the blocks (option "rank_fold"); rank_planes and rank_short stay functions of D.
+  // A third figure, S3, counts the values at least three samples hold.  The two-holder pair (ppk_db::d_fold2R /
+  // d_fold2Q) codes the values with exactly two holders like single-holder ones and spans E2 = S3 + 2 codes; what the
+  // compare then misses -- one match per such value, in one known pair -- the tile kernel adds back from an event list
+  // built here.  That costs three more small kernels, a second synchronisation and a fixed step per tile, so the
+  // default (option "rank_fold2" 1) takes it only where its plane sum is the lowest of the three AND the self job runs
+  // at least four rounds of tiles (a smaller job's time is its latency, not its compare stream).  Caps: at most five k,
+  // 8 planes, PPK_FOLD2_SLOTS two-holder values per position, PPK_FOLD2_MAX_PER_PAIR events per (pair, k); a database
+  // past any of them keeps the copies it would have had.
   if (rc == PPK_OK && ppk_config().rank_planes.load() != 0 && ppk_self_job_takes_tiles(db)) {
     unsigned *d_max = nullptr;
     const size_t n_blocks = nk * sketchsize64;
-    std::vector<unsigned> counts(2 * (1 + n_blocks), 0u);
+    std::vector<unsigned> counts(3 * (1 + n_blocks) + PPK_RANK_EXTRA, 0u);
     e = hipMalloc(reinterpret_cast<void **>(&d_max), counts.size() * sizeof(unsigned));
     if (e == hipSuccess) {
       rc = ppk_launch_rank_count(db->d_skT, n, db->npad, nk, sketchsize64, d_max, s);
@@ -456,8 +474,9 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
       }
       (void)hipFree(d_max);
       auto planes_for = [](unsigned codes) { return codes <= 256 ? 8 : codes <= 1024 ? 10 : codes <= 4096 ? 12 : 0; };
-      const unsigned *count_d = counts.data(), *count_e = counts.data() + 1 + n_blocks;
-      const int planes = planes_for(count_d[0]), planes_fold = planes_for(count_e[0]);
+      const unsigned *count_d = counts.data(), *count_e = counts.data() + 1 + n_blocks, *count_e2 = counts.data() + 2 * (1 + n_blocks);
+      unsigned *extra = counts.data() + 3 * (1 + n_blocks);      // most two-holder values of a position, all of them, cap hit
+      const int planes = planes_for(count_d[0]), planes_fold = planes_for(count_e[0]), planes_fold2 = planes_for(count_e2[0]);
       // the short flags of either coding, and the planes a self job compares over all blocks with it (no coding: 14)
       const bool flags_fit = nk < PPK_RANK_SHORT_WORDS && sketchsize64 <= 32;
       auto block_flags = [&](const unsigned *cnt, int pl, unsigned *flags) {
@@ -470,11 +489,26 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
           }
         return sum;
       };
-      unsigned short_d[PPK_RANK_SHORT_WORDS] = {}, short_e[PPK_RANK_SHORT_WORDS] = {};
+      unsigned short_d[PPK_RANK_SHORT_WORDS] = {}, short_e[PPK_RANK_SHORT_WORDS] = {}, short_e2[PPK_RANK_SHORT_WORDS] = {};
       const size_t sum_d = block_flags(count_d, planes, short_d), sum_e = block_flags(count_e, planes_fold, short_e);
-      const long long fold_opt = ppk_config().rank_fold.load();
+      const size_t sum_e2 = block_flags(count_e2, planes_fold2, short_e2);
+      const long long fold_opt = ppk_config().rank_fold.load(), fold2_opt = ppk_config().rank_fold2.load();
       const size_t copy_words = db->npad * nk * sketchsize64;
-      if (rc == PPK_OK && planes_fold && fold_opt != 0 && (fold_opt == 2 || sum_e < sum_d)) {
+      // the two-holder pair first: where it is built nothing else is
+      const bool fold2_fits = planes_fold2 == 8 && nk <= PPK_FOLD2_MAX_NK && extra[0] <= PPK_FOLD2_SLOTS && n < ((size_t)1 << 28);
+      const size_t self_tiles = (db->npad / 256) * (db->npad / 32) / 2;
+      const bool fold2_pays = fold_opt != 0 && sum_e2 < sum_d && sum_e2 < (planes_fold ? sum_e : (size_t)-1) &&
+                              self_tiles >= 4 * (size_t)ppk_geometry(device_id).tile_slots;
+      if (rc == PPK_OK && fold2_fits && fold2_opt != 0 && (fold2_opt == 2 || fold2_pays)) {
+        bool overflow = false;
+        rc = ppk_build_fold2(db, planes_fold2, extra[1], &overflow, s);
+        extra[2] = overflow ? 1u : 0u;
+        if (rc == PPK_OK && db->fold2_planes) {
+          for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) db->fold2_short[k] = short_e2[k];
+          db->rank_planes = planes;
+        }
+      }
+      if (rc == PPK_OK && !db->fold2_planes && planes_fold && fold_opt != 0 && (fold_opt == 2 || sum_e < sum_d)) {
         // (a device too full for the pair falls back to the injective copy, and from there to the raw planes)
         e = hipMalloc(reinterpret_cast<void **>(&db->d_foldR), copy_words * (size_t)planes_fold * sizeof(uint64_t));
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_foldQ), copy_words * (size_t)planes_fold * sizeof(uint64_t));
@@ -489,7 +523,7 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
           db->rank_planes = planes;
         }
       }
-      if (rc == PPK_OK && planes && !db->fold_planes) {
+      if (rc == PPK_OK && planes && !db->fold_planes && !db->fold2_planes) {
         // (a device too full for the copy keeps the raw planes alone: the copy only buys speed)
         e = hipMalloc(reinterpret_cast<void **>(&db->d_skR), copy_words * (size_t)planes * sizeof(uint64_t));
         if (e != hipSuccess) {
@@ -502,6 +536,7 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
       }
       if (db->rank_planes)
         for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) db->rank_short[k] = short_d[k];
+      if (rc == PPK_OK) db->rank_counts = counts;
     } else {
       (void)hipGetLastError();
     }
@@ -523,6 +558,8 @@ extern "C" void ppk_db_destroy(ppk_db *db) {
   if (db->d_skR) (void)hipFree(db->d_skR);
   if (db->d_foldR) (void)hipFree(db->d_foldR);
   if (db->d_foldQ) (void)hipFree(db->d_foldQ);
+  for (void *ptr : {(void *)db->d_fold2R, (void *)db->d_fold2Q, (void *)db->d_fold2_ev, (void *)db->d_fold2_off})
+    if (ptr) (void)hipFree(ptr);
   if (db->d_clu) (void)hipFree(db->d_clu);
   delete db;
 }
@@ -582,6 +619,56 @@ extern "C" int ppk_db_fold_block_planes(const ppk_db *db, uint8_t *out, size_t c
       out[k * db->s64 + b] = (uint8_t)(db->fold_planes - (is_short ? 1 : 0));
     }
   return PPK_OK;
+}
+
+extern "C" int ppk_db_fold2_planes(const ppk_db *db) { return db ? db->fold2_planes : 0; }
+extern "C" int ppk_db_fold2_read(const ppk_db *db, int which, uint64_t *out, size_t words) {
+  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_read: NULL argument");
+  if (which != 0 && which != 1) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_read: `which` is 0 (ref side) or 1 (query side)");
+  if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_read: the database has no two-holder pair");
+  if (words != db->nk * db->s64 * (size_t)db->fold2_planes * db->npad)
+    return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_read: `words` is not nk * sketchsize64 * planes * padded samples");
+  DeviceGuard guard(db->device);
+  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(db->device));
+  PPK_HIP(hipDeviceSynchronize());
+  PPK_HIP(hipMemcpy(out, which ? db->d_fold2Q : db->d_fold2R, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return PPK_OK;
+}
+
+extern "C" int ppk_db_fold2_block_planes(const ppk_db *db, uint8_t *out, size_t cap) {
+  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_block_planes: NULL argument");
+  if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_block_planes: the database has no two-holder pair");
+  if (cap < db->nk * db->s64) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_block_planes: `cap` is below nk * sketchsize64");
+  for (size_t k = 0; k < db->nk; ++k)
+    for (size_t b = 0; b < db->s64; ++b) {
+      const bool is_short = k < PPK_RANK_SHORT_WORDS && b < 32 && ((db->fold2_short[k] >> b) & 1u);
+      out[k * db->s64 + b] = (uint8_t)(db->fold2_planes - (is_short ? 1 : 0));
+    }
+  return PPK_OK;
+}
+
+extern "C" size_t ppk_db_fold2_events(const ppk_db *db, size_t *n_buckets) {
+  if (n_buckets) *n_buckets = db && db->fold2_planes ? (size_t)db->fold2_qt * db->fold2_rt : 0;
+  return db && db->fold2_planes ? db->fold2_events : 0;
+}
+extern "C" int ppk_db_fold2_events_read(const ppk_db *db, uint32_t *off, size_t n_off, uint16_t *ev, size_t n_ev) {
+  if (!db || !off) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_events_read: NULL argument");
+  if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_events_read: the database has no two-holder pair");
+  if (n_off != (size_t)db->fold2_qt * db->fold2_rt + 1 || n_ev != db->fold2_events || (n_ev && !ev))
+    return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_events_read: sizes are buckets + 1 and events (ppk_db_fold2_events)");
+  DeviceGuard guard(db->device);
+  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(db->device));
+  PPK_HIP(hipDeviceSynchronize());
+  PPK_HIP(hipMemcpy(off, db->d_fold2_off, n_off * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (n_ev) PPK_HIP(hipMemcpy(ev, db->d_fold2_ev, n_ev * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  return PPK_OK;
+}
+
+extern "C" size_t ppk_db_rank_counts(const ppk_db *db, uint32_t *out, size_t cap) {
+  if (!db) return 0;
+  if (out && cap >= db->rank_counts.size())
+    for (size_t i = 0; i < db->rank_counts.size(); ++i) out[i] = db->rank_counts[i];
+  return db->rank_counts.size();
 }
 
 extern "C" int ppk_db_rank_block_planes(const ppk_db *db, uint8_t *out, size_t cap) {

@@ -190,6 +190,10 @@ struct DistParams {
   // there (ppk_db::rank_short; all zero with option "rank_short" 0).  The kernel reads word k at the end of k - 1, and
   // word nk after the last k: PPK_RANK_SHORT_WORDS > nk.
   unsigned rank_short[PPK_RANK_SHORT_WORDS];
+  // the FOLD2 instantiations only: the event list of the two-holder pair (ppk_db::d_fold2_ev / d_fold2_off / fold2_rt)
+  const uint16_t *fold2_ev;
+  const unsigned *fold2_off;
+  unsigned fold2_rt;
 };
 
 // With every k usable the least-squares fit is LINEAR in the log J_k with launch-constant weights:
@@ -260,20 +264,48 @@ transpose_kernel(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, si
 //                   nothing in a job that compares two different samples, and 0 != 1 != every shared code says so.
 constexpr int RANK_BB = 14;                      // the one bbits with a coded copy (the tile kernels' V2_BB)
 constexpr int RANK_BMW = (1 << RANK_BB) / 32;      // bitmap dwords per position
-template <bool WRITE, bool FOLD = false>
+//     FOLD2 (with FOLD): the two-holder pair.  A third bitmap, fed by what the atomicOr into "seen twice" returns, holds
+//                   the values with at least three holders; they alone keep codes 2 + rank (among themselves), and a
+//                   value with one or two holders is 0 in `out` and 1 in `out_q`.  Every two-holder value is an event:
+//                   its rank among the position's two-holder values names a pair of LDS slots, the samples that hold it
+//                   atomicMin / atomicMax themselves into them, and the workgroup appends (hi, lo, k) to ev.raw and
+//                   counts the event's bucket (ppk_db::d_fold2_ev).
+//   The count pass leaves E2 = S3 + 2 behind E in the same form, and behind that the most two-holder values of any
+//   position and their number over all positions.
+struct Fold2Emit {
+  unsigned long long *raw;      // hi | lo << 28 | k << 56
+  unsigned *count;              // events appended so far
+  unsigned *bucket;             // events per bucket (lo / 32) * rt + hi / 256
+  unsigned cap, rt;
+};
+template <bool WRITE, bool FOLD = false, bool FOLD2 = false>
 __global__ void __launch_bounds__(256)
 rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, uint8_t *__restrict__ out_q,
-                 unsigned *__restrict__ max_distinct, size_t n, size_t npad, int s64, int pl) {
+                 unsigned *__restrict__ max_distinct, size_t n, size_t npad, int s64, int pl, const Fold2Emit ev) {
+  static_assert(!FOLD2 || (WRITE && FOLD), "the two-holder pair is a folded pair");
   constexpr bool TWICE = !WRITE || FOLD;
-  __shared__ uint32_t bitmap[8][RANK_BMW];
+  constexpr bool THRICE = !WRITE || FOLD2;
+  constexpr int SLOTS = PPK_FOLD2_SLOTS;
+  __shared__ uint32_t bitmap[8][RANK_BMW];                 // (FOLD2, after the feed: the values with exactly two holders)
   __shared__ uint32_t twice[TWICE ? 8 : 1][RANK_BMW];      // values with at least two holders
-  __shared__ uint16_t before[WRITE ? 8 : 1][RANK_BMW];     // coded values (distinct; FOLD: shared) below the dword's first one
+  __shared__ uint32_t thrice[THRICE ? 8 : 1][RANK_BMW];    // values with at least three holders
+  __shared__ uint16_t before[WRITE ? 8 : 1][RANK_BMW];     // coded values (distinct; FOLD: shared; FOLD2: thrice held) below the dword's first one
+  __shared__ uint16_t before2[FOLD2 ? 8 : 1][RANK_BMW];    // two-holder values below the dword's first one
+  __shared__ uint32_t ev_lo[FOLD2 ? 8 : 1][FOLD2 ? SLOTS : 1], ev_hi[FOLD2 ? 8 : 1][FOLD2 ? SLOTS : 1];
+  __shared__ uint32_t ev_n[8], ev_base[8];
   const int g = blockIdx.x & 7;
   const size_t kb = blockIdx.x >> 3;            // k * s64 + block
   const uint64_t *src = skT + kb * RANK_BB * npad;
   for (int i = threadIdx.x; i < 8 * RANK_BMW; i += 256) {
     (&bitmap[0][0])[i] = 0;
     if (TWICE) (&twice[0][0])[i] = 0;
+    if (THRICE) (&thrice[0][0])[i] = 0;
+  }
+  if constexpr (FOLD2) {
+    for (int i = threadIdx.x; i < 8 * SLOTS; i += 256) {
+      (&ev_lo[0][0])[i] = 0xffffffffu;
+      (&ev_hi[0][0])[i] = 0;
+    }
   }
   __syncthreads();
   auto values = [&](size_t smp, uint32_t (&v)[8]) {
@@ -294,7 +326,10 @@ rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, ui
     for (int j = 0; j < 8; ++j) {
       const uint32_t bit = 1u << (v[j] & 31u);
       const uint32_t old = atomicOr(&bitmap[j][v[j] >> 5], bit);
-      if (TWICE && (old & bit)) atomicOr(&twice[j][v[j] >> 5], bit);
+      if (TWICE && (old & bit)) {
+        const uint32_t old2 = atomicOr(&twice[j][v[j] >> 5], bit);
+        if (THRICE && (old2 & bit)) atomicOr(&thrice[j][v[j] >> 5], bit);
+      }
     }
   }
   __syncthreads();
@@ -314,23 +349,41 @@ rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, ui
     };
     if constexpr (!WRITE) {
       uint32_t sum;
-      const uint32_t d_incl = prefix(bitmap[j], sum), s_incl = prefix(twice[j], sum);
+      const uint32_t d_incl = prefix(bitmap[j], sum), s_incl = prefix(twice[j], sum), s3_incl = prefix(thrice[j], sum);
       if (t == 31) {
-        unsigned *max_fold = max_distinct + 1 + gridDim.x / 8;
+        const unsigned seg = 1 + gridDim.x / 8;
+        unsigned *max_fold = max_distinct + seg, *max_fold2 = max_distinct + 2 * seg, *extra = max_distinct + 3 * seg;
         atomicMax(max_distinct, d_incl);
         atomicMax(max_distinct + 1 + kb, d_incl);
         atomicMax(max_fold, s_incl + 2u);
         atomicMax(max_fold + 1 + kb, s_incl + 2u);
+        atomicMax(max_fold2, s3_incl + 2u);
+        atomicMax(max_fold2 + 1 + kb, s3_incl + 2u);
+        atomicMax(extra, s_incl - s3_incl);
+        atomicAdd(extra + 1, s_incl - s3_incl);
       }
       return;
     } else {
-      const uint32_t *bm = FOLD ? twice[j] : bitmap[j];
-      uint32_t sum;
-      const uint32_t incl = prefix(bm, sum);
-      uint32_t run = incl - sum;
-      for (int w = 0; w < RANK_BMW / 32; ++w) {
-        before[j][t * (RANK_BMW / 32) + w] = (uint16_t)run;
-        run += __popc(bm[t * (RANK_BMW / 32) + w]);
+      if constexpr (FOLD2) {
+        for (int w = 0; w < RANK_BMW / 32; ++w) {
+          const int i = t * (RANK_BMW / 32) + w;
+          bitmap[j][i] = twice[j][i] & ~thrice[j][i];      // (this thread's own 16 dwords, read back below)
+        }
+      }
+      auto ranks = [&](const uint32_t *bm, uint16_t *bef) {
+        uint32_t sum;
+        const uint32_t incl = prefix(bm, sum);
+        uint32_t run = incl - sum;
+        for (int w = 0; w < RANK_BMW / 32; ++w) {
+          bef[t * (RANK_BMW / 32) + w] = (uint16_t)run;
+          run += __popc(bm[t * (RANK_BMW / 32) + w]);
+        }
+        return incl;
+      };
+      ranks(FOLD2 ? thrice[j] : FOLD ? twice[j] : bitmap[j], before[j]);
+      if constexpr (FOLD2) {
+        const uint32_t two_incl = ranks(bitmap[j], before2[j]);
+        if (t == 31) ev_n[j] = two_incl < (uint32_t)SLOTS ? two_incl : (uint32_t)SLOTS;      // (the caller has checked: never above)
       }
     }
   }
@@ -339,14 +392,27 @@ rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, ui
   uint8_t *dst_q = FOLD ? out_q + kb * (size_t)pl * npad * 8 + g : nullptr;
   for (size_t smp = threadIdx.x; smp < npad; smp += 256) {
     uint32_t code[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t single = 0;      // FOLD: bit j set where the sample's value at position j has no other holder
+    uint32_t single = 0;      // FOLD: bit j set where the sample's value at position j has no other holder (FOLD2: at most one)
     if (smp < n) {
       uint32_t v[8];
       values(smp, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const uint32_t w = v[j] >> 5, bit = 1u << (v[j] & 31u);
-        if constexpr (FOLD) {
+        if constexpr (FOLD2) {
+          if (thrice[j][w] & bit) {
+            code[j] = 2u + before[j][w] + __popc(thrice[j][w] & (bit - 1u));
+          } else {
+            single |= 1u << j;
+            if (bitmap[j][w] & bit) {
+              const uint32_t slot = before2[j][w] + __popc(bitmap[j][w] & (bit - 1u));
+              if (slot < (uint32_t)SLOTS) {
+                atomicMin(&ev_lo[j][slot], (uint32_t)smp);
+                atomicMax(&ev_hi[j][slot], (uint32_t)smp);
+              }
+            }
+          }
+        } else if constexpr (FOLD) {
           if (twice[j][w] & bit) code[j] = 2u + before[j][w] + __popc(twice[j][w] & (bit - 1u));
           else single |= 1u << j;
         } else {
@@ -362,6 +428,88 @@ rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, ui
       // (a shared code is the same on both sides; a single holder's differs in bit 0 alone)
       if constexpr (FOLD) dst_q[((size_t)b * npad + smp) * 8] = (uint8_t)(b == 0 ? byte | single : byte);
     }
+  }
+  if constexpr (FOLD2) {
+    // one event per two-holder value: one reservation per workgroup, then 32 threads per position
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t total = 0;
+      for (int j = 0; j < 8; ++j) {
+        ev_base[j] = total;
+        total += ev_n[j];
+      }
+      const uint32_t at = total ? atomicAdd(ev.count, total) : 0u;
+      for (int j = 0; j < 8; ++j) ev_base[j] += at;
+    }
+    __syncthreads();
+    const int j = threadIdx.x >> 5;
+    const unsigned long long k = kb / (size_t)s64;
+    for (uint32_t slot = threadIdx.x & 31; slot < ev_n[j]; slot += 32) {
+      const uint32_t hi = ev_hi[j][slot], lo = ev_lo[j][slot], at = ev_base[j] + slot;
+      if (at >= ev.cap) continue;
+      if (hi < n && lo < hi) {
+        ev.raw[at] = (unsigned long long)hi | ((unsigned long long)lo << 28) | (k << 56);
+        atomicAdd(ev.bucket + (size_t)(lo >> 5) * ev.rt + (hi >> 8), 1u);
+      } else {
+        ev.raw[at] = ~0ull;      // (not two holders after all: never -- the scatter reports it, the pair is dropped)
+      }
+    }
+  }
+}
+
+constexpr int FOLD2_TILE_PAIRS = 256 * 32;      // pairs of one (256 refs x 32 queries) tile: 13 bits of an event
+// The counting sort of the events into their buckets (ppk_db::d_fold2_ev) and the check of the per-pair cap.
+// fold2_scan_kernel: one workgroup; off = exclusive prefix sum of cnt (nb entries, off[nb] = the total), cnt back to
+// zero for the scatter's cursors.
+__global__ void __launch_bounds__(1024)
+fold2_scan_kernel(unsigned *__restrict__ cnt, unsigned *__restrict__ off, size_t nb) {
+  __shared__ unsigned part[1024];
+  const size_t per = (nb + 1023) / 1024, b0 = threadIdx.x * per, b1 = b0 + per < nb ? b0 + per : nb;
+  unsigned sum = 0;
+  for (size_t b = b0; b < b1; ++b) sum += cnt[b];
+  part[threadIdx.x] = sum;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {
+    const unsigned up = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0u;
+    __syncthreads();
+    part[threadIdx.x] += up;
+    __syncthreads();
+  }
+  unsigned run = part[threadIdx.x] - sum;
+  for (size_t b = b0; b < b1; ++b) {
+    off[b] = run;
+    run += cnt[b];
+    cnt[b] = 0;
+  }
+  if (threadIdx.x == 1023) off[nb] = part[1023];
+}
+__global__ void __launch_bounds__(256)
+fold2_scatter_kernel(const unsigned long long *__restrict__ raw, unsigned *n_raw, unsigned cap,
+                     const unsigned *__restrict__ off, unsigned *__restrict__ cursor, uint16_t *__restrict__ ev, unsigned rt) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x, total = *n_raw < cap ? *n_raw : cap;
+  if (i >= total) return;
+  const unsigned long long e = raw[i];
+  if (e == ~0ull) {
+    n_raw[1] = 1u;      // the overflow flag sits behind the counter
+    return;
+  }
+  const uint32_t hi = (uint32_t)e & 0xfffffffu, lo = (uint32_t)(e >> 28) & 0xfffffffu, k = (uint32_t)(e >> 56);
+  const size_t b = (size_t)(lo >> 5) * rt + (hi >> 8);
+  const unsigned at = off[b] + atomicAdd(cursor + b, 1u);
+  if (at < off[b + 1]) ev[at] = (uint16_t)((hi & 255u) | ((lo & 31u) << 8) | (k << 13));
+}
+// one workgroup per bucket, the tile kernel's own correction words: a field that is asked to count past 63 sets *overflow
+__global__ void __launch_bounds__(256)
+fold2_check_kernel(const uint16_t *__restrict__ ev, const unsigned *__restrict__ off, unsigned *__restrict__ overflow) {
+  __shared__ uint32_t corr[FOLD2_TILE_PAIRS];
+  const unsigned e0 = off[blockIdx.x], e1 = off[blockIdx.x + 1];
+  if (e0 == e1) return;      // (workgroup-uniform)
+  for (int i = threadIdx.x; i < FOLD2_TILE_PAIRS; i += 256) corr[i] = 0;
+  __syncthreads();
+  for (unsigned e = e0 + threadIdx.x; e < e1; e += 256) {
+    const uint32_t v = ev[e], k = v >> 13;
+    const uint32_t old = atomicAdd(&corr[v & 0x1fffu], 1u << (6u * k));
+    if (((old >> (6u * k)) & 63u) == (uint32_t)PPK_FOLD2_MAX_PER_PAIR) *overflow = 1u;
   }
 }
 
@@ -1031,6 +1179,7 @@ dist_kernel_v2(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ q
                void *__restrict__ out, unsigned long long *__restrict__ n_failed,
                uint64_t *__restrict__ mask_out, const DistParams p) {
   constexpr int PL = V2_BB;      // raw planes
+  constexpr bool FOLD2 = false;
 #include "ppk_dist_tile.inc"
 }
 
@@ -1044,7 +1193,22 @@ dist_kernel_v2_rank(const uint64_t *__restrict__ refT, const uint64_t *__restric
                     void *__restrict__ out, unsigned long long *__restrict__ n_failed,
                     uint64_t *__restrict__ mask_out, const DistParams p) {
   constexpr int NW = 8, W = 2;
-  constexpr bool KSPLIT = false, WIDE = false, EXP = false;
+  constexpr bool KSPLIT = false, WIDE = false, EXP = false, FOLD2 = false;
+#include "ppk_dist_tile.inc"
+}
+
+// The same kernel at 8 planes on the two-holder pair (ppk_db::d_fold2R / d_fold2Q): FOLD2 compiles one more block into
+// the body, at the top of the epilogue, which adds the tile's events (DistParams::fold2_ev) to the counts.  A kernel of
+// its own name: dist_kernel_v2_rank<PL, MODE> stays the code (and the symbols) it was.
+template <int MODE>
+__global__ void __launch_bounds__(8 * 64, 4)
+dist_kernel_v2_fold2(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ qryT,
+                     const double *__restrict__ lut, const uint16_t *__restrict__ ref_clu,
+                     const uint16_t *__restrict__ qry_clu, const float *__restrict__ rtab,
+                     void *__restrict__ out, unsigned long long *__restrict__ n_failed,
+                     uint64_t *__restrict__ mask_out, const DistParams p) {
+  constexpr int NW = 8, W = 2, PL = 8;
+  constexpr bool KSPLIT = false, WIDE = false, EXP = false, FOLD2 = true;
 #include "ppk_dist_tile.inc"
 }
 
@@ -1584,24 +1748,33 @@ int launch_wide(int dev, const PpkGeometry &geo, const DistArgs &a, DistParams &
 // The folded pair (d_foldR / d_foldQ) serves the triangular job alone: every pair it compares is two different
 // samples, one from each copy.  A rectangular job of a handle against itself has the pairs (r, r), where a value
 // with a single holder must match itself: it reads the injective copy if there is one, else the raw planes.
-// Returns the planes of the copy this band reads (0: the raw planes) and whether that is the folded pair.
-int coded_planes(const ppk_db *ref, const ppk_db *qry, const DistParams &p, bool *fold) {
+// The two-holder pair (d_fold2R / d_fold2Q, always 8 planes) serves the same job with the event list beside it.
+// Returns the planes of the copy this band reads (0: the raw planes) and which copy that is: 0 the injective one, 1 the
+// folded pair, 2 the two-holder pair.
+int coded_planes(const ppk_db *ref, const ppk_db *qry, const DistParams &p, int *fold) {
   const bool coded = (p.self || qry == ref) && !p.k_split && ppk_config().rank_planes.load() != 0;
-  *fold = coded && p.self && ref->fold_planes != 0 && ppk_config().rank_fold.load() != 0;
-  return *fold ? ref->fold_planes : coded && ref->d_skR ? ref->rank_planes : 0;
+  *fold = !(coded && p.self)                                                    ? 0
+          : ref->fold2_planes != 0 && ppk_config().rank_fold2.load() != 0       ? 2
+          : ref->fold_planes != 0 && ppk_config().rank_fold.load() != 0         ? 1
+                                                                                : 0;
+  return *fold == 2 ? ref->fold2_planes : *fold == 1 ? ref->fold_planes : coded && ref->d_skR ? ref->rank_planes : 0;
 }
 template <int MODE>
-int launch_rank(const ppk_db *ref, int planes, bool fold, DistArgs a, DistParams &p, size_t n_blocks, hipStream_t s) {
-  a.sk_r = fold ? ref->d_foldR : ref->d_skR;
-  a.sk_q = fold ? ref->d_foldQ : ref->d_skR;
+int launch_rank(const ppk_db *ref, int planes, int fold, DistArgs a, DistParams &p, size_t n_blocks, hipStream_t s) {
+  a.sk_r = fold == 2 ? ref->d_fold2R : fold ? ref->d_foldR : ref->d_skR;
+  a.sk_q = fold == 2 ? ref->d_fold2Q : fold ? ref->d_foldQ : ref->d_skR;
   // the blocks that compare one plane fewer (option "rank_short", read here: one database runs either way)
-  const unsigned *flags = fold ? ref->fold_short : ref->rank_short;
+  const unsigned *flags = fold == 2 ? ref->fold2_short : fold ? ref->fold_short : ref->rank_short;
   const bool use_short = ppk_config().rank_short.load() != 0;
   for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.rank_short[k] = use_short ? flags[k] : 0u;
-  const auto kernel = planes == 12   ? &dist_kernel_v2_rank<12, MODE>
+  p.fold2_ev = fold == 2 ? ref->d_fold2_ev : nullptr;
+  p.fold2_off = fold == 2 ? ref->d_fold2_off : nullptr;
+  p.fold2_rt = fold == 2 ? ref->fold2_rt : 0u;
+  const auto kernel = fold == 2      ? &dist_kernel_v2_fold2<MODE>
+                      : planes == 12 ? &dist_kernel_v2_rank<12, MODE>
                       : planes == 10 ? &dist_kernel_v2_rank<10, MODE>
                                      : &dist_kernel_v2_rank<8, MODE>;
-  const std::string name = "dist_kernel_v2<256x32,lds-dma,rank " + std::to_string(planes) + (fold ? ",fold>" : ">");
+  const std::string name = "dist_kernel_v2<256x32,lds-dma,rank " + std::to_string(planes) + (fold == 2 ? ",fold2>" : fold ? ",fold>" : ">");
   return launch_kernel(kernel, dim3((unsigned)n_blocks), dim3(8 * 64), name.c_str(), a, p, s);
 }
 
@@ -1629,7 +1802,7 @@ int launch_v2(const ppk_db *ref, const ppk_db *qry, const DistArgs &a, DistParam
     return launch_kernel(&dist_kernel_v2<NW, MODE, W, false, false, true>, grid, block, "dist_kernel_v2<256x32,lds-dma,exp>", a, p, s);
 #endif
   if constexpr (NW == 8 && W == 2 && !WIDE && kFits) {
-    bool fold = false;
+    int fold = 0;
     if (const int planes = coded_planes(ref, qry, p, &fold)) return launch_rank<MODE>(ref, planes, fold, a, p, n_blocks, s);
   }
   // (the counts pass of a two-pass k-split job: one workgroup per (tile, k))
@@ -1688,13 +1861,13 @@ int ppk_launch_transpose(const uint64_t *d_in, uint64_t *d_out, size_t n, size_t
   return PPK_OK;
 }
 
-// The rank codes of a transposed bbits = 14 database (rank_code_kernel): the count pass (d_max: 2 * (1 + nk * s64)
-// words, the D maxima and behind them the E maxima), then -- with `d_out` -- the code planes: injective, or with
-// `d_out_q` the folded pair (d_out the ref side).  Both only enqueue.
+// The rank codes of a transposed bbits = 14 database (rank_code_kernel): the count pass (d_max: 3 * (1 + nk * s64) +
+// PPK_RANK_EXTRA words, the D maxima, behind them the E and the E2 maxima, then the two-holder figures), then -- with
+// `d_out` -- the code planes: injective, or with `d_out_q` the folded pair (d_out the ref side).  Both only enqueue.
 int ppk_launch_rank_count(const uint64_t *d_skT, size_t n, size_t npad, size_t nk, size_t s64, unsigned *d_max, hipStream_t s) {
-  PPK_HIP(hipMemsetAsync(d_max, 0, 2 * (1 + nk * s64) * sizeof(unsigned), s));
+  PPK_HIP(hipMemsetAsync(d_max, 0, (3 * (1 + nk * s64) + PPK_RANK_EXTRA) * sizeof(unsigned), s));
   hipLaunchKernelGGL((rank_code_kernel<false>), dim3((unsigned)(nk * s64 * 8)), dim3(256), 0, s, d_skT, nullptr, nullptr, d_max,
-                     n, npad, (int)s64, 0);
+                     n, npad, (int)s64, 0, Fold2Emit{});
   PPK_HIP(hipGetLastError());
   return PPK_OK;
 }
@@ -1703,12 +1876,73 @@ int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, uint64_t *d_ou
   const dim3 grid((unsigned)(nk * s64 * 8)), block(256);
   if (d_out_q)
     hipLaunchKernelGGL((rank_code_kernel<true, true>), grid, block, 0, s, d_skT, reinterpret_cast<uint8_t *>(d_out),
-                       reinterpret_cast<uint8_t *>(d_out_q), nullptr, n, npad, (int)s64, planes);
+                       reinterpret_cast<uint8_t *>(d_out_q), nullptr, n, npad, (int)s64, planes, Fold2Emit{});
   else
     hipLaunchKernelGGL((rank_code_kernel<true, false>), grid, block, 0, s, d_skT, reinterpret_cast<uint8_t *>(d_out), nullptr,
-                       nullptr, n, npad, (int)s64, planes);
+                       nullptr, n, npad, (int)s64, planes, Fold2Emit{});
   PPK_HIP(hipGetLastError());
   return PPK_OK;
+}
+// The two-holder pair of `db` and its event list.  Everything is allocated here; a device too full for it, or a
+// (pair, k) with more events than its field holds (*overflow), leaves the database without the pair.
+int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, bool *overflow, hipStream_t s) {
+  *overflow = false;
+  const size_t copy_bytes = db->npad * db->nk * db->s64 * (size_t)planes * sizeof(uint64_t);
+  const unsigned qt = (unsigned)(db->npad / 32), rt = (unsigned)(db->npad / V2_RT);
+  const size_t nb = (size_t)qt * rt, cap = n_two ? n_two : 1;
+  unsigned long long *d_raw = nullptr;
+  unsigned *d_cnt = nullptr;      // [nb] bucket counts / cursors, then the event counter and the overflow flag
+  auto drop = [&]() {
+    (void)hipGetLastError();
+    for (void *ptr : {(void *)db->d_fold2R, (void *)db->d_fold2Q, (void *)db->d_fold2_ev, (void *)db->d_fold2_off})
+      if (ptr) (void)hipFree(ptr);
+    db->d_fold2R = db->d_fold2Q = nullptr;
+    db->d_fold2_ev = nullptr;
+    db->d_fold2_off = nullptr;
+    db->fold2_planes = 0;
+  };
+  auto done = [&](int rc) {
+    if (d_raw) (void)hipFree(d_raw);
+    if (d_cnt) (void)hipFree(d_cnt);
+    return rc;
+  };
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&db->d_fold2R), copy_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_fold2Q), copy_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_fold2_ev), cap * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_fold2_off), (nb + 1) * sizeof(unsigned));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_raw), cap * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), (nb + 2) * sizeof(unsigned));
+  if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (nb + 2) * sizeof(unsigned), s);
+  if (e != hipSuccess) {
+    drop();
+    return done(PPK_OK);
+  }
+  const Fold2Emit ev = {d_raw, d_cnt + nb, d_cnt, (unsigned)cap, rt};
+  hipLaunchKernelGGL((rank_code_kernel<true, true, true>), dim3((unsigned)(db->nk * db->s64 * 8)), dim3(256), 0, s, db->d_skT,
+                     reinterpret_cast<uint8_t *>(db->d_fold2R), reinterpret_cast<uint8_t *>(db->d_fold2Q), nullptr, db->n,
+                     db->npad, (int)db->s64, planes, ev);
+  hipLaunchKernelGGL(fold2_scan_kernel, dim3(1), dim3(1024), 0, s, d_cnt, db->d_fold2_off, nb);
+  hipLaunchKernelGGL(fold2_scatter_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, d_raw, d_cnt + nb, (unsigned)cap,
+                     db->d_fold2_off, d_cnt, db->d_fold2_ev, rt);
+  hipLaunchKernelGGL(fold2_check_kernel, dim3((unsigned)nb), dim3(256), 0, s, db->d_fold2_ev, db->d_fold2_off, d_cnt + nb + 1);
+  unsigned tail[2] = {0, 0};      // events, overflow
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(tail, d_cnt + nb, sizeof(tail), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    drop();
+    return done(ppk_fail(PPK_ERR_HIP, std::string("two-holder pair: ") + hipGetErrorString(e)));
+  }
+  if (tail[1] || tail[0] != n_two) {      // (a count that differs from the count pass's: never -- the list would be incomplete)
+    *overflow = true;
+    drop();
+    return done(PPK_OK);
+  }
+  db->fold2_planes = planes;
+  db->fold2_qt = qt;
+  db->fold2_rt = rt;
+  db->fold2_events = n_two;
+  return done(PPK_OK);
 }
 // whether a self job over the whole of `db` runs whole 256 x 32 tiles of the two-dword count register under the
 // options in force: the one shape that reads a rank-coded copy (launch_v2)

@@ -1,8 +1,9 @@
-// The body of the pair-tile kernels (ppk_dist.hip): dist_kernel_v2 and dist_kernel_v2_rank include it between
-// their braces.  It is text, not a function, on purpose: the kernels sit at the register limit, and the same body
+// The body of the pair-tile kernels (ppk_dist.hip): dist_kernel_v2, dist_kernel_v2_rank and dist_kernel_v2_fold2 include
+// it between their braces.  It is text, not a function, on purpose: the kernels sit at the register limit, and the same body
 // inlined from a __device__ function compiles to other code (the by-value DistParams is then read differently).
 // In scope at the point of inclusion: the kernel's arguments (refT, qryT, lut, ref_clu, qry_clu, rtab, out, n_failed,
-// mask_out, p) and the compile-time constants NW, MODE, W, KSPLIT, WIDE, EXP and
+// mask_out, p) and the compile-time constants NW, MODE, W, KSPLIT, WIDE, EXP, FOLD2 (the two-holder pair: one block at the
+// top of the epilogue) and
 //   PL: the bit-planes a 64-bin block is copied and compared in.  14 = the sketch's own bbits; 8, 10 or 12 on a
 //       rank-coded database (ppk_db::d_skR: every bin value replaced by its rank among the distinct values of its
 //       (k, bin) position, which keeps "equal / not equal" and so every count).  The collision adjustment and the fit
@@ -444,7 +445,7 @@
   // ---- epilogue: regression (+ boundary) per pair ---------------------------
   if constexpr (MODE == MODE_DIST || ppk_is_mask(MODE) || MODE == MODE_KNN) {
     if (ablate & 1) return;
-    if (!KS_FUSED && !WIDE_TILE && MODE != MODE_KNN && !wave_active) return;      // (KNN, k-split, wide: every wave takes part in an exchange)
+    if (!FOLD2 && !KS_FUSED && !WIDE_TILE && MODE != MODE_KNN && !wave_active) return;      // (KNN, k-split, wide, FOLD2: every wave takes part in an exchange)
     // the compare stream leaves the wave at priority 0 (it falls through each block, see
     // tools/gen_block_asm.py); the epilogue is the last thing between this workgroup's slot and the next
     // tile, so it runs at the top priority (measured: another -0.5..-1 %)
@@ -480,6 +481,74 @@
         (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(ka));
     LateParams &p_late = *reinterpret_cast<LateParams *>(ka + V2_PARAMS_KERNARG_OFFSET);
+    if constexpr (FOLD2) {
+      // ---- the two-holder pair: the matches the codes cannot see ------------------------------------
+      // A value with exactly two holders is coded 0 / 1 like a single-holder one, so the pair (its higher holder as
+      // ref, its lower as query) was counted one short at that k.  The database lists these events by (lo / 32,
+      // hi / 256) (ppk_db::d_fold2_ev): a tile's bucket is the list of what its pairs are owed.  The compare buffers
+      // are dead: their first 32 KB take one dword per pair of the tile, five 6-bit fields (one per k), laid out so
+      // that lane l of wavefront w reads its sixteen pairs as four conflict-free 16-byte reads --
+      // [q][w * 64 + l][r] -- and the events are added in with LDS atomics.  The barriers are workgroup-wide, so the
+      // wavefronts with nothing to compare leave only below.  A strip tile holds the LOWER holders on its lane axis
+      // (256 of them: eight buckets) and 32 of the last ref tile's samples on its query axis.
+      static_assert(PL == 8 && W == 2 && !KSPLIT && !WIDE, "the two-holder pair is an 8-plane whole-tile kernel");
+      const uint32_t tid = (uint32_t)wave * 64u + (uint32_t)lane_late;
+      uint32_t *corr = reinterpret_cast<uint32_t *>(lds);
+      u32x4 zero4;
+      zero4.x = zero4.y = zero4.z = zero4.w = 0;
+#pragma unroll
+      for (int i = 0; i < TQ; ++i) lds[tid + 512u * i] = zero4;
+      __syncthreads();
+      {
+        const unsigned *off = p_late.fold2_off;
+        const uint16_t *evs = p_late.fold2_ev;
+        const uint32_t frt = p_late.fold2_rt;
+        const uint32_t q_sub = (uint32_t)(q0 >> 5) & 7u;      // strip: which 32 of its ref tile's samples the tile holds
+        const int n_buckets = strip ? 8 : 1;
+        for (int i = 0; i < n_buckets; ++i) {
+          const uint32_t b = strip ? ((uint32_t)(r0 >> 5) + (uint32_t)i) * frt + (uint32_t)(q0 >> 8)
+                                   : (uint32_t)(q0 >> 5) * frt + (uint32_t)rt;
+          const uint32_t e1 = off[b + 1];
+          for (uint32_t e = off[b] + tid; e < e1; e += 512u) {
+            const uint32_t ev = evs[e], kk = ev >> 13;
+            uint32_t ref_l = ev & 255u, qry_l = (ev >> 8) & 31u;      // hi % 256, lo % 32
+            if (strip) {
+              if ((ref_l >> 5) != q_sub) continue;
+              const uint32_t hi_l = ref_l;
+              ref_l = 32u * (uint32_t)i + qry_l;
+              qry_l = hi_l & 31u;
+            }
+            // pair (ref_l, qry_l): wavefront qry_l / 4, q = qry_l % 4, lane (ref_l % 128) / 2, r = ref_l % 2 + 2 * (ref_l / 128)
+            const uint32_t slot = (((qry_l & 3u) * 512u + (qry_l >> 2) * 64u + ((ref_l & 127u) >> 1)) << 2) + (ref_l & 1u) + ((ref_l >> 7) << 1);
+            if (kk < 5u) __hip_atomic_fetch_add(corr + slot, 1u << (6u * kk), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
+        }
+      }
+      __syncthreads();
+      {
+        const int cb = p_late.cnt_bits, top = p_late.nk - 1;
+#pragma unroll
+        for (int q = 0; q < TQ; ++q) {
+          const u32x4 c4 = lds[tid + 512u * q];
+          const uint32_t c[R] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+          for (int r = 0; r < R; ++r) {
+            if (c[r] != 0) {
+              // field k lands where the end-of-k shifts left k's count: bit cnt_bits * (nk - 1 - k)
+              uint64_t add = 0;
+#pragma unroll
+              for (int k = 0; k < 5; ++k)
+                if (k <= top) add += (uint64_t)((c[r] >> (6 * k)) & 63u) << (cb * (top - k));
+              const uint64_t v = (((uint64_t)pw[1][r][q] << 32) | pw[0][r][q]) + add;
+              pw[0][r][q] = (uint32_t)v;
+              pw[1][r][q] = (uint32_t)(v >> 32);
+            }
+          }
+        }
+      }
+      __syncthreads();      // (the table copy below lands on the words just read)
+      if (!wave_active) return;
+    }
     uint32_t ks_tile = 0;
     // WIDE: the last group joins the others in the slot; from here on the counts are read from there
     uint32_t wide_slot = 0;

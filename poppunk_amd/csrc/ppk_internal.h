@@ -52,7 +52,31 @@ struct ppk_db {
   uint64_t *d_foldR, *d_foldQ;
   int fold_planes;
   unsigned fold_short[PPK_RANK_SHORT_WORDS];
+  // The two-holder pair, built INSTEAD of the folded pair where it compares fewer planes still (option "rank_fold2"):
+  // the same two copies, but a value with exactly two holders is coded like a single-holder one (0 / 1) and only the
+  // values with at least three holders keep codes >= 2, so a position spans E2 = S3 + 2 codes.  A two-holder value can
+  // match in exactly one pair of the triangular job (its higher holder as ref, its lower as query), which the compare
+  // then under-counts by one: every such value is one EVENT (hi, lo, k), and the tile kernel adds the events of its
+  // tile back at the top of its epilogue (FOLD2 in ppk_dist_tile.inc).  Events are bucketed by (lo / 32, hi / 256):
+  // bucket b = (lo / 32) * fold2_rt + hi / 256 holds d_fold2_ev[fold2_off[b] .. fold2_off[b + 1]), 16 bits each:
+  // hi % 256 | (lo % 32) << 8 | k << 13.  At most PPK_FOLD2_MAX_PER_PAIR events per (pair, k) (a 6-bit field).
+  uint64_t *d_fold2R, *d_fold2Q;
+  int fold2_planes;
+  unsigned fold2_short[PPK_RANK_SHORT_WORDS];
+  uint16_t *d_fold2_ev;
+  unsigned *d_fold2_off;        // fold2_qt * fold2_rt + 1 offsets
+  unsigned fold2_qt, fold2_rt;  // npad / 32, npad / 256
+  size_t fold2_events;
+  // what the count pass found (ppk_db_rank_counts): the maxima of D, E = S + 2 and E2 = S3 + 2 over all positions and
+  // per (k, 64-bin block) -- 3 x (1 + nk * s64) words -- then PPK_RANK_EXTRA words: the most two-holder values of any
+  // position, their number over all positions, and (after an attempt at the two-holder pair) whether a (pair, k) had
+  // more events than its field holds.  Empty where no count pass ran.
+  std::vector<unsigned> rank_counts;
 };
+#define PPK_RANK_EXTRA 3
+#define PPK_FOLD2_SLOTS 256          // two-holder values per position the code pass has LDS slots for
+#define PPK_FOLD2_MAX_PER_PAIR 63    // events per (pair, k): a 6-bit field of the tile kernel's correction word
+#define PPK_FOLD2_MAX_NK 5           // five 6-bit fields per correction word; k in 3 bits of an event
 
 // A database whose per-pair counts the tile kernels cannot hold: more k-mer lengths than the fit tables are laid
 // out for, or more than 128 count bits at a bbits other than PopPUNK's 14 (the wide-k tile kernel is built for
@@ -81,6 +105,7 @@ struct PpkConfig {
   // -- product options
   std::atomic<long long> rank_planes{1};        // PPK_RANK_PLANES: a bbits = 14 database whose self job runs whole tiles keeps a rank-coded copy (ppk_db::d_skR) and self jobs compare it (0: no copy is built, none is read; same bits)
   std::atomic<long long> rank_fold{1};          // PPK_RANK_FOLD: where folding every single-holder bin value into two reserved codes lets a self job compare fewer planes, the database keeps the folded pair (ppk_db::d_foldR / d_foldQ) instead of the injective copy (0: never; 2: whenever the folded codes fit 12 planes, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
+  std::atomic<long long> rank_fold2{1};         // PPK_RANK_FOLD2: where coding the two-holder bin values like single-holder ones (their one match per value added back in the tile kernel's epilogue from an event list) lets a large self job compare fewer planes than both other codings, the database keeps the two-holder pair (ppk_db::d_fold2R / d_fold2Q) instead (0: never; 2: whenever the caps allow, any size, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
   std::atomic<long long> rank_short{1};         // PPK_RANK_SHORT: a self job on a rank-coded database compares one plane fewer in the 64-bin blocks whose positions hold at most half the values the planes can code (0: every block compares all planes; same bits).  Read at launch.
   std::atomic<long long> lds_table{1};          // PPK_LDS_TABLE: interior tiles of the default sketch shape fit from the (E, F) table in LDS (0: the general statement everywhere; same bits)
   std::atomic<long long> ksplit{1200};           // PPK_KSPLIT: tile-count threshold (at 5 k) of the small-job path
@@ -186,10 +211,15 @@ struct PpkRouteChoice {
 PpkRouteChoice ppk_choose_route_impl(const PpkRouteShape &sh, const PpkGeometry &g, const PpkRouteKnobs &k);
 // rank-coded copy of a bbits = 14 database (ppk_dist.hip)
 bool ppk_self_job_takes_tiles(const ppk_db *db);
-// (d_max: 1 + nk * s64 words -- the maximum over all positions, then the maximum of each (k, 64-bin block))
+// (d_max: 3 x (1 + nk * s64) words -- per figure the maximum over all positions, then the maximum of each (k, 64-bin
+// block) -- and PPK_RANK_EXTRA more, see ppk_db::rank_counts)
 int ppk_launch_rank_count(const uint64_t *d_skT, size_t n, size_t npad, size_t nk, size_t s64, unsigned *d_max, hipStream_t s);
 int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, uint64_t *d_out_q, size_t n, size_t npad, size_t nk, size_t s64, int planes,
                           hipStream_t s);
+// The two-holder pair and its event list (ppk_db::d_fold2R ...): allocates the list, enqueues the code pass, the
+// counting sort and the cap check, and synchronises `s` once.  *overflow: a (pair, k) has more events than its field
+// holds (the caller drops the pair).  `n_two`: the two-holder values the count pass found.
+int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, bool *overflow, hipStream_t s);
 
 // Profiling hooks (ppk_prof_*) -------------------------------------------------
 void ppk_prof_begin(hipStream_t s);

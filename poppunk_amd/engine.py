@@ -180,6 +180,58 @@ class SketchDB:
                                                self.nk * self.sketchsize64 * planes * npad), "ppk_db_fold_read")
         return self._unslice_codes(raw, planes)
 
+    @property
+    def fold2_planes(self):
+        """Bit-planes of the database's two-holder pair of coded copies (8), 0 without one (ppk_db_fold2_planes)."""
+        return int(_lib.lib().ppk_db_fold2_planes(self._h))
+
+    def fold2_block_planes(self):
+        """Planes a self job compares per 64-bin block of the two-holder pair (ppk_db_fold2_block_planes): uint8
+        [nk, sketchsize64]."""
+        out = np.empty((self.nk, self.sketchsize64), dtype=np.uint8)
+        _lib.check(_lib.lib().ppk_db_fold2_block_planes(self._h, C.c_void_p(out.ctypes.data), out.size),
+                   "ppk_db_fold2_block_planes")
+        return out
+
+    def fold2_codes(self, which):
+        """One copy of the two-holder pair un-bitsliced (tests), 0 the ref side, 1 the query side: uint16
+        [n, nk, 64 * sketchsize64] codes."""
+        planes, npad = self.fold2_planes, (self.n + 255) // 256 * 256
+        raw = np.empty((self.nk, self.sketchsize64, max(planes, 1), npad), dtype=np.uint64)
+        _lib.check(_lib.lib().ppk_db_fold2_read(self._h, int(which), C.c_void_p(raw.ctypes.data),
+                                                self.nk * self.sketchsize64 * planes * npad), "ppk_db_fold2_read")
+        return self._unslice_codes(raw, planes)
+
+    def fold2_events(self):
+        """The event list of the two-holder pair (ppk_db_fold2_events_read): (offsets uint32 [npad / 32, npad / 256]
+        flattened + 1, events uint16).  Bucket (lo // 32) * (npad // 256) + hi // 256 holds
+        events[offsets[b]:offsets[b + 1]], each hi % 256 | (lo % 32) << 8 | k << 13, in no order within a bucket."""
+        nb = C.c_size_t(0)
+        n_ev = int(_lib.lib().ppk_db_fold2_events(self._h, C.byref(nb)))
+        off = np.zeros(nb.value + 1, dtype=np.uint32)
+        ev = np.zeros(n_ev, dtype=np.uint16)
+        _lib.check(_lib.lib().ppk_db_fold2_events_read(self._h, C.c_void_p(off.ctypes.data), off.size,
+                                                       C.c_void_p(ev.ctypes.data) if n_ev else None, n_ev),
+                   "ppk_db_fold2_events_read")
+        return off, ev
+
+    def rank_counts(self):
+        """What the count pass of the coded copies found (ppk_db_rank_counts), None where none ran: a dict of the
+        maxima over all positions "D", "E", "E2", per (k, block) "block_D", "block_E", "block_E2" [nk, sketchsize64],
+        "two_max" (most two-holder values of a position), "two_total" and "pair_cap_hit"."""
+        words = int(_lib.lib().ppk_db_rank_counts(self._h, None, 0))
+        if not words:
+            return None
+        raw = np.zeros(words, dtype=np.uint32)
+        _lib.lib().ppk_db_rank_counts(self._h, C.c_void_p(raw.ctypes.data), raw.size)
+        seg = 1 + self.nk * self.sketchsize64
+        out = {}
+        for i, name in enumerate(("D", "E", "E2")):
+            out[name] = int(raw[i * seg])
+            out["block_" + name] = raw[i * seg + 1:(i + 1) * seg].reshape(self.nk, self.sketchsize64).copy()
+        out["two_max"], out["two_total"], out["pair_cap_hit"] = (int(x) for x in raw[3 * seg:3 * seg + 3])
+        return out
+
 
 def _prep_tables(kmers, random_tbl, nk):
     kmers = np.ascontiguousarray(kmers, dtype=np.int32)
