@@ -3,8 +3,8 @@ tests/test_gpu_soak.py (the driver's GPU suite runs 600 + a few large ones) and 
 builder's longer campaigns): random n / split / bands, nk 2..11 (12..33: the wide-k tile kernel), sketchsize64 1..156, bbits in {14 (tile
 kernel), 8, 16 (generic kernel)}, multi-cluster random tables in random or contiguous runs, related /
 unrelated data, counts / jaccard / distance / fused-edge modes, neighbours from the tiles, both
-settings of the two [EXT] switches (kernel and oracle flipped together), the three options of the coded copies
-("rank_planes", "rank_short", "rank_fold") and, in half of the bbits 14 self cases, one to three positions planted with a
+settings of the two [EXT] switches (kernel and oracle flipped together), the four options of the coded copies
+("rank_planes", "rank_short", "rank_fold", "rank_fold2") and, in half of the bbits 14 self cases, one to three positions planted with a
 count of distinct or of shared values at a threshold of the coded copies' planes (128 | 129 ... 2 048 | 2 049).  A self job
 that fits the coded route runs it once more at the end under every setting of "rank_fold" and "rank_short".
 """
@@ -29,7 +29,8 @@ def reset_options():
     for name, default in (("wide_kpg", 0), ("lds_table", 1), ("ksplit_wide", 215), ("knn_warm", 32), ("knn_cut", 4),
                           ("ksplit_long", 1), ("host_parts", 2), ("host_parts_rows", 16 << 20), ("prefault_threads", 8), ("db_cache", 1),
                           ("progress", 1), ("host_trace", 0), ("rank_planes", 1), ("rank_short", 1), ("rank_fold", 1),
-                          ("sweep_window", 1), ("knn_lane_lists", 0), ("ksplit_scratch_mb", 2048)):
+                          ("sweep_window", 1), ("knn_lane_lists", 0), ("ksplit_scratch_mb", 2048), ("rank_fold2", 1),
+                          ("pairs_chunk", 0), ("pairs_scratch_mb", 1024)):
         _lib.set_option(name, default)
     oracle.set_ext(0, 0)
 
@@ -68,7 +69,8 @@ def route_label(kernel):
     """ppk_last_kernel_name() in short: the k-split forms, the wide-k tile kernel, the coded tile kernel with its planes
     ("rank 8", "rank 10 fold"), the raw tile kernel, the generic-bbits kernel"""
     if "rank " in kernel:
-        return "rank %s%s" % (kernel.split("rank ")[1].split(",")[0].rstrip(">"), " fold" if kernel.endswith("fold>") else "")
+        return "rank %s%s" % (kernel.split("rank ")[1].split(",")[0].rstrip(">"),
+                              " fold" if kernel.endswith("fold>") else " fold2" if kernel.endswith("fold2>") else "")
     return ("ksplit1" if "k-split fused" in kernel else "ksplit2" if "k-split counts" in kernel else
             "wide" if kernel.endswith("wide>") else "tile" if "256x32" in kernel else "generic")
 
@@ -78,6 +80,8 @@ def soak_case(rng, big=False):
     import torch
     # draws added after the campaign was committed come from a child stream: `rng` gives every earlier draw as before
     extra = np.random.Generator(np.random.PCG64(rng.bit_generator.seed_seq.spawn(1)[0]))
+    # ... and draws added after those from a child of that child: `extra` gives its draws as before, too
+    later = np.random.Generator(np.random.PCG64(extra.bit_generator.seed_seq.spawn(1)[0]))
     bbits = int(rng.choice([14, 14, 14, 8, 16]))
     s64 = int(rng.choice([1, 2, 3, 16, 16, 16, 5, 40, 64, 156]))      # (32 and up: the long-sketch rule, k-split at any size)
     if os.environ.get("SOAK_KSPLIT"):      # the hand-over campaign: only shapes the one-launch k-split path takes
@@ -128,6 +132,7 @@ def soak_case(rng, big=False):
     _lib.set_option("rank_planes", int(extra.choice([1, 1, 1, 0])))
     _lib.set_option("rank_short", int(extra.choice([1, 1, 0])))
     _lib.set_option("rank_fold", int(extra.choice([1, 1, 0, 2])))
+    _lib.set_option("rank_fold2", int(later.choice([1, 1, 0, 2])))      # (2: the two-holder pair at any size the caps allow)
     # a quarter of the cases run as a very large job would: a few tiles per launch, a short neighbour-candidate
     # list, small pieces in the fused host call
     tiny = rng.integers(0, 4) == 0
@@ -279,8 +284,8 @@ def soak_case(rng, big=False):
     except Exception as e:  # noqa: BLE001
         msgs.append("EXCEPTION %r" % (e,))
     desc = ("bbits=%2d s64=%2d nk=%d n=%4d nr=%4d clu=%d tbl=%d related=%d ext=%d%d tiny=%d pad=%d %s"
-            " rank_planes=%d rank_short=%d rank_fold=%d planted=%s"
+            " rank_planes=%d rank_short=%d rank_fold=%d rank_fold2=%d planted=%s"
             % (bbits, s64, nk, n, nr, n_clu, use_tbl, related, ext[0], ext[1], int(tiny), _lib.get_option("ks_grid_pad"),
                route, _lib.get_option("rank_planes"), _lib.get_option("rank_short"), _lib.get_option("rank_fold"),
-               ",".join(x for x in planted if x) or "-"))
+               _lib.get_option("rank_fold2"), ",".join(x for x in planted if x) or "-"))
     return desc, msgs

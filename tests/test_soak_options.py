@@ -6,14 +6,15 @@ import re
 import soak_case
 from poppunk_amd import _lib
 
-# the options of the coded copies and three more that reset_options() once left as a case set them, with PpkConfig's defaults
-LATE = {"rank_planes": 1, "rank_short": 1, "rank_fold": 1, "sweep_window": 1, "knn_lane_lists": 0,
-        "ksplit_scratch_mb": 2048}
+# the options of the coded copies and five more that reset_options() once left as a case (or another suite's) set them,
+# with PpkConfig's defaults
+LATE = {"rank_planes": 1, "rank_short": 1, "rank_fold": 1, "rank_fold2": 1, "sweep_window": 1, "knn_lane_lists": 0,
+        "ksplit_scratch_mb": 2048, "pairs_chunk": 0, "pairs_scratch_mb": 1024}
 
 
 def test_reset_options_restores_every_option_a_case_sets():
     names = set(re.findall(r'set_option\("(\w+)"', inspect.getsource(soak_case.soak_case))) | set(LATE)
-    assert {"rank_planes", "rank_short", "rank_fold", "ksplit", "db_cache"} <= names
+    assert {"rank_planes", "rank_short", "rank_fold", "rank_fold2", "ksplit", "db_cache"} <= names
     defaults = {name: _lib.get_option(name) for name in names}
     assert {name: defaults[name] for name in LATE} == LATE
     try:
