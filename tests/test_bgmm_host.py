@@ -1,5 +1,5 @@
 """CPU tests of BGMM assignment: ppk_bgmm_prepare (no device), the model loader, and a numpy restatement of the
-reference's assignment against tests/golden/bgmm_assign.npz (tests/golden/make_golden_bgmm.py)."""
+reference's assignment against tests/golden/bgmm_assign.npz and bgmm_assign_k.npz (tests/golden/make_golden_bgmm.py)."""
 import os
 
 import numpy as np
@@ -9,10 +9,16 @@ from poppunk_amd import _lib
 from poppunk_amd.models import BGMMModel
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bgmm_assign.npz")
+GOLDEN_K = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bgmm_assign_k.npz")
 
 
 def golden():
     return np.load(GOLDEN, allow_pickle=False)
+
+
+def golden_k():
+    """K = 1, 3, 5, 16 with odd row counts (make_golden_bgmm.py --k)"""
+    return np.load(GOLDEN_K, allow_pickle=False)
 
 
 def case_model(g, case):
@@ -22,8 +28,7 @@ def case_model(g, case):
 
 def test_prepare_matches_scipy_cholesky():
     from scipy import linalg
-    g = golden()
-    for case in list(g["cases"]):
+    for g, case in [(g, case) for g in (golden(), golden_k()) for case in list(g["cases"])]:
         m = case_model(g, case).model
         for c, cv in enumerate(g[case + "_covariances"]):
             try:
@@ -126,10 +131,33 @@ def restated(X, weights, means, covariances, scale):
 
 
 def test_numpy_restatement_matches_golden():
-    g = golden()
-    for case in list(g["cases"]):
+    for g, case in [(g, case) for g in (golden(), golden_k()) for case in list(g["cases"])]:
         X = g[case + "_X"]
         labels, resp = restated(X, g[case + "_weights"], g[case + "_means"], g[case + "_covariances"],
                                 g[case + "_scale"])
         assert np.array_equal(labels, g[case + "_labels"]), case
         np.testing.assert_allclose(resp, g[case + "_resp"], rtol=1e-6, atol=1e-30)
+
+
+def test_golden_k_has_no_undecided_row_and_every_component_matters():
+    """What tests/test_gpu_bgmm_shapes.py relies on: every row of bgmm_assign_k.npz is decided by the rule of
+    test_gpu_bgmm.py (so labels compare exactly on all of them), a kernel that skipped a component would mislabel a
+    row (every component of k3 and k5, at least 12 of k16's 16, is some row's label), every row count is odd (the
+    one-row tail of a kernel that takes two rows per lane), and the file is no larger than bgmm_assign.npz."""
+    g = golden_k()
+    assert list(g["cases"]) == ["k1", "k3", "k3_f64", "k5", "k16"]
+    for case, K in (("k1", 1), ("k3", 3), ("k3_f64", 3), ("k5", 5), ("k16", 16)):
+        gap, top, labels = g[case + "_gap"], g[case + "_top"], g[case + "_labels"]
+        assert g[case + "_weights"].shape == (K,) and g[case + "_resp"].shape == (labels.shape[0], K)
+        assert labels.shape[0] % 2 == 1, case
+        assert (gap <= 1e-9 * np.maximum(1.0, np.abs(top))).sum() == 0, case
+        assert np.unique(labels).size >= (12 if K == 16 else K), case
+        assert 0 <= g[case + "_within"].item() < K
+    assert (g["k1_labels"] == 0).all() and (g["k1_resp"] == 1.0).all()
+    assert g["k5_within"].item() == 4 and g["k5_weights"].min() == 1e-4 and g["k16_weights"].min() == 1e-4
+    assert g["k3_scale"].dtype == np.float32 and g["k3_f64_scale"].dtype == np.float64
+    for case in ("k5", "k16"):      # correlated covariances, up to +-0.9
+        cv = g[case + "_covariances"]
+        rho = cv[:, 0, 1] / np.sqrt(cv[:, 0, 0] * cv[:, 1, 1])
+        assert abs(rho.min() + 0.9) < 1e-12 and abs(rho.max() - 0.9) < 1e-12
+    assert os.path.getsize(GOLDEN_K) <= os.path.getsize(GOLDEN)

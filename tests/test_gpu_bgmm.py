@@ -67,14 +67,19 @@ def test_labels_and_responsibilities_match_golden():
 
 def test_host_assign_across_a_chunk_boundary_equals_the_device_path():
     """ppk_bgmm_assign works through its rows in chunks of 8 Mi from one buffer: three rows more than a chunk take the
-    loop's second pass, and labels and responsibilities asked for together equal the device-array path's."""
+    loop's second pass, and labels and responsibilities asked for together equal the device-array path's.  The rows
+    are the k2 case's, repeated, so both also equal the reference's recorded answers for those rows (an indexing
+    error the two paths shared would pass the first comparison alone)."""
     import ctypes as C
     import torch
     from poppunk_amd import _lib, engine
-    m = case_model(golden(), "k2")
+    g = golden()
+    m = case_model(g, "k2")
     assert m.n_components == 2
+    assert (g["k2_gap"] > 1e-9 * np.maximum(1.0, np.abs(g["k2_top"]))).all()
     n = (8 << 20) + 3
-    X = np.random.Generator(np.random.PCG64(8)).random((n, 2), dtype=np.float32)
+    idx = np.arange(n) % g["k2_X"].shape[0]
+    X = np.ascontiguousarray(g["k2_X"][idx])
     lab = np.empty(n, dtype=np.int32)
     resp = np.empty((n, 2), dtype=np.float32)
     rc = _lib.lib().ppk_bgmm_assign(X.ctypes.data_as(C.POINTER(C.c_float)), n, m.model, 0,
@@ -83,6 +88,8 @@ def test_host_assign_across_a_chunk_boundary_equals_the_device_path():
     want_lab, want_resp = engine.bgmm_assign_dev(torch.from_numpy(X).cuda(), m.model, True, True)
     assert np.array_equal(lab, want_lab.cpu().numpy())
     assert np.array_equal(resp, want_resp.cpu().numpy())
+    assert np.array_equal(lab, g["k2_labels"][idx])
+    assert ulp_diff(resp, g["k2_resp"][idx]).max() <= 2
 
 
 def test_empty_input():
