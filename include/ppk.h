@@ -119,6 +119,12 @@ int ppk_device_count(int *n);
  *     "density_kde_presum" (0)  ppk_density_kde_dev sums the terms of lanes of a wave whose rows share a window of
  *                          nodes before the LDS add, for groups of at least this many lanes (at most 64); 0 = every
  *                          lane adds its own terms (same sums)
+ *   silhouette (ppk_silhouette_dev; exercised by its own GPU tests, not by the campaign)
+ *     "silhouette_scratch_mb" (1 024)  what the band of square rows may take as allocated: a band holds as many samples
+ *                          as keep float32 [band][n] within four fifths of it; at least one
+ *     "silhouette_band" (0)    samples per band, whatever the cap says (0 = from the cap; tests)
+ *     "silhouette_window" (0)  labels per LDS table window of the sums stage (0 = as many as the table holds, 4 096;
+ *                          small values force the windowed path: tests)
  *   host calls
  *     "chunk_rows" (8 Mi)  rows per sub-band of a host query (about an eighth of the job, at least 1 Mi, below 16 Mi
  *                          rows); also scales the pieces of the fused host edge call
@@ -813,6 +819,44 @@ int ppk_cluster_pair_sums_dev(const float *d_dist, size_t n_rows, int col, const
  * blocking. */
 int ppk_cluster_pair_sums(const float *dist, size_t n_rows, int col, const int32_t *levels, size_t n_levels, int shift,
                           int device_id, long long *sum, long long *cnt);
+
+/* ------------------------------------------------------------------------
+ * Silhouette: the silhouette of every sample under every level of a family of clusterings, from a
+ * resident self/condensed float32 [n_rows][2] matrix, n_rows = n(n-1)/2, n >= 3.  d_labels int32 [n_levels][n]: cluster
+ * numbers in [1, n]; rows of ppk_cluster_sweep_dev's d_clusters qualify.  The numbers may have gaps and the levels need
+ * not be nested.
+ * Distance of a pair, d(i, j), from its row (x0, x1), by `metric`:
+ *     0  core, x0                        1  accessory, x1
+ *     2  "euclidean": the float32 sqrtf(x0*x0 + x1*x1), un-fused, the root correctly rounded -- the statement
+ *        ppk_edge_weights_dev / ppk_row_norms_dev make for process_weights
+ *     3  "difference": the float32 fabsf(x0 - x1).  [EXT], unpinned: what the script's euclidean(distRow[0],
+ *        distRow[1]) gave under scipy releases whose euclidean accepted scalars; not recorded.
+ * Accumulation: q(i, j) = llrint((double)d(i, j) * 2^shift); T[i][c] = the sum of q(i, j) over j != i with label c;
+ * cnt[c] = the samples with label c.  shift = min(40, 61 - ceil_log2(n)) keeps every sum below 2^62 (a distance is at
+ * most sqrt 2).  The sums are integers: the same bits on every call and in any order.
+ * Per sample i (label ci) and level, in float64, un-fused, exactly these operations:
+ *     a = ((double)T[i][ci] * 2^-shift) / (double)(cnt[ci] - 1)
+ *     b = the minimum over c != ci with cnt[c] > 0 of ((double)T[i][c] * 2^-shift) / (double)cnt[c]
+ *     s = (b - a) / max(a, b);  s = 0 when max(a, b) == 0;  a = b = s = 0 when cnt[ci] == 1
+ * (sklearn.metrics.silhouette_samples' rules, its nan_to_num included).  a and b differ from the float64 means of the
+ * same float32 distances by at most 2^-(shift + 1) + n * 2^-53 * max d each.
+ * Per level t: d_n_labels[t] = its distinct labels; the level is valid iff 2 <= n_labels <= n - 1 (sklearn's
+ * check_number_of_labels); an invalid level gets d_valid[t] = 0 and its rows of a, b, s filled with NaN -- not an error,
+ * and the other levels are unaffected.  d_a, d_b, d_s double [n_levels][n]; d_a and d_b may be NULL.
+ * PPK_ERR_ARG, ppk_last_error() naming the first offender: a distance (either column, whatever the metric) that is NaN,
+ * infinite or outside [0, 1]; a label outside [1, n].  Also PPK_ERR_ARG, before any device is touched: metric outside
+ * 0 .. 3, shift outside [0, 40] or above 61 - ceil_log2(n), n_levels 0 or > 1023, n_rows not n(n-1)/2, n < 3, a NULL
+ * array.  Synchronises the stream once (the read-back of the first offender, before the sums).  The square matrix is
+ * never built: samples are taken in bands whose float32 [band][n] rows stay below option "silhouette_scratch_mb".
+ * (Replaces the X_mat loop + sklearn.metrics.silhouette_score of scripts/poppunk_calculate_silhouette.py:57-84, for
+ * every level of a sweep in one call.) */
+int ppk_silhouette_dev(const float *d_dist, size_t n_rows, int metric, const int32_t *d_labels, size_t n_levels,
+                       int shift, double *d_a, double *d_b, double *d_s, int32_t *d_n_labels, int32_t *d_valid,
+                       void *stream);
+/* Host arrays: dist float32 [n_rows][2], labels int32 [n_levels][n] -> a, b (nullable), s double [n_levels][n],
+ * n_labels, valid int32 [n_levels], on device_id; blocking. */
+int ppk_silhouette(const float *dist, size_t n_rows, int metric, const int32_t *labels, size_t n_levels, int shift,
+                   int device_id, double *a, double *b, double *s, int32_t *n_labels, int32_t *valid);
 
 /* ------------------------------------------------------------------------
  * Density grids of a resident float32 [n_rows][2] matrix: the two layers of the fit plots, each one

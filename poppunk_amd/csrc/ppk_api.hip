@@ -71,6 +71,9 @@ const OptionEntry kOptions[] = {
     {"ksplit_scratch_mb", "PPK_KSPLIT_SCRATCH_MB", &PpkConfig::ksplit_scratch_mb},
     {"pairs_scratch_mb", "PPK_PAIRS_SCRATCH_MB", &PpkConfig::pairs_scratch_mb},
     {"pairs_chunk", "PPK_PAIRS_CHUNK", &PpkConfig::pairs_chunk},
+    {"silhouette_scratch_mb", "PPK_SILHOUETTE_SCRATCH_MB", &PpkConfig::silhouette_scratch_mb},
+    {"silhouette_band", "PPK_SILHOUETTE_BAND", &PpkConfig::silhouette_band},
+    {"silhouette_window", "PPK_SILHOUETTE_WINDOW", &PpkConfig::silhouette_window},
     {"knn_list", "PPK_KNN_LIST", &PpkConfig::knn_list},
     {"knn_warm", "PPK_KNN_WARM", &PpkConfig::knn_warm},
     {"knn_cut", "PPK_KNN_CUT", &PpkConfig::knn_cut},

@@ -135,6 +135,9 @@ struct PpkConfig {
   std::atomic<long long> density_kde_presum{0}; // PPK_DENSITY_KDE_PRESUM: ppk_density_kde_dev sums the terms of lanes of a wave that share a window of nodes before the LDS add, for groups of at least this many lanes (0: every lane adds its own terms; same sums)
   std::atomic<long long> pairs_scratch_mb{1024}; // PPK_PAIRS_SCRATCH_MB: what the scratch of one chunk of a pair list may take as allocated (ppk_dist_pairs_dev: 2 x pairs x the bytes of one sample's sketch, plus the counts, stays within four fifths of it; same results)
   std::atomic<long long> pairs_chunk{0};        // PPK_PAIRS_CHUNK: pairs per chunk of a pair list whatever the cap says (0 = from the cap; tests; same results)
+  std::atomic<long long> silhouette_scratch_mb{1024}; // PPK_SILHOUETTE_SCRATCH_MB: what the band of square rows of ppk_silhouette_dev may take as allocated (float32 [band][n] stays within four fifths of it; at least one row; same results)
+  std::atomic<long long> silhouette_band{0};    // PPK_SILHOUETTE_BAND: samples per band whatever the cap says (0 = from the cap; tests; same results)
+  std::atomic<long long> silhouette_window{0};  // PPK_SILHOUETTE_WINDOW: labels per LDS table window of the silhouette's sums stage (0 = as many as the table holds, 4 096; small values force the windowed path: tests; same results)
   std::atomic<long long> knn_list{0};           // PPK_KNN_LIST: entries of the neighbour-candidate list (0 = sized from n and knn)
   std::atomic<long long> host_parts_rows{16 << 20};   // PPK_HOST_PARTS_ROWS: ... from this many rows up
   std::atomic<long long> host_parts{2};         // PPK_HOST_PARTS: worker threads of a one-device host query (>= 16 Mi rows)
@@ -307,7 +310,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_ASSIGN_SORT = 23,                  // ... and, on the sort route only, its (query, label) keys, flags and temp storage
        SLOT_DENSITY = 24,                      // the density grids' coordinates, scale keys and first-offender words
        SLOT_PAIRS = 25,                        // a pair list's first-bad-pair word, sample flags and slots, the chunk's row image, ids and counts
-       SLOT_COUNT = 26 };
+       SLOT_SILHOUETTE = 26,                   // the silhouette's first-offender words, label histogram and band of square rows
+       SLOT_COUNT = 27 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

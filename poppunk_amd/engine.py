@@ -970,6 +970,47 @@ def cluster_pair_sums_dev(dist_t, levels_t, col=0, shift=None):
     return out[0], out[1], int(shift)
 
 
+def silhouette_shift(n):
+    """The fixed-point shift of the silhouette's sums: min(40, 61 - ceil_log2(n)), so that no sum of n distances of at
+    most sqrt 2 passes 2^62 (ceil_log2 as ppk_device.h states it)."""
+    r = 0
+    while r < 62 and (1 << r) < int(n):
+        r += 1
+    return min(40, 61 - r)
+
+
+def silhouette_dev(dist_t, levels_t, metric=2, shift=None, want_ab=False):
+    """The silhouette of every sample under every level (ppk_silhouette_dev, DESIGN.md 3.19;
+    tests/silhouette_model.py restates the rule): dist_t a resident float32 [n(n-1)/2, 2] CUDA matrix, levels_t int32
+    [n_levels, n] CUDA, cluster numbers in [1, n] (gaps allowed, levels need not be nested).  metric: 0 core,
+    1 accessory, 2 euclidean, 3 difference.  Returns (s float64 [n_levels, n], n_labels int32 [n_levels], valid int32
+    [n_levels]) as CUDA tensors -- the rows of an invalid level (fewer than 2 or more than n - 1 labels) are NaN -- and
+    with want_ab the mean distances (a, b) float64 [n_levels, n] as a fourth and fifth item."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    n_rows = int(dist_t.shape[0])
+    n = _samples_of(n_rows)
+    if not (levels_t.is_cuda and levels_t.dtype == torch.int32 and levels_t.dim() == 2 and levels_t.is_contiguous()
+            and levels_t.shape[1] == n and levels_t.device == dist_t.device):
+        raise TypeError("levels must be a contiguous int32 [n_levels, %d] CUDA tensor on the matrix's device" % n)
+    if shift is None:
+        shift = silhouette_shift(n)
+    n_levels = int(levels_t.shape[0])
+    dev = dist_t.device
+    with torch.cuda.device(dev):
+        out = torch.empty((3 if want_ab else 1, max(n_levels, 1), n), dtype=torch.float64, device=dev)
+        counts = torch.empty((2, max(n_levels, 1)), dtype=torch.int32, device=dev)
+        rc = _lib.lib().ppk_silhouette_dev(
+            C.c_void_p(dist_t.data_ptr()), n_rows, int(metric), C.c_void_p(levels_t.data_ptr()), n_levels, int(shift),
+            C.c_void_p(out[1].data_ptr()) if want_ab else None, C.c_void_p(out[2].data_ptr()) if want_ab else None,
+            C.c_void_p(out[0].data_ptr()), C.c_void_p(counts[0].data_ptr()), C.c_void_p(counts[1].data_ptr()),
+            _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_silhouette_dev")
+    if want_ab:
+        return out[0], counts[0], counts[1], out[1], out[2]
+    return out[0], counts[0], counts[1]
+
+
 def _kde_args(gx, gy, scale):
     gx = np.ascontiguousarray(gx, dtype=np.float64)
     gy = np.ascontiguousarray(gy, dtype=np.float64)
