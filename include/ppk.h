@@ -125,6 +125,16 @@ int ppk_device_count(int *n);
  *     "silhouette_band" (0)    samples per band, whatever the cap says (0 = from the cap; tests)
  *     "silhouette_window" (0)  labels per LDS table window of the sums stage (0 = as many as the table holds, 4 096;
  *                          small values force the windowed path: tests)
+ *   contingency sums (ppk_contingency_sums_dev; exercised by its own GPU tests, not by the campaign)
+ *     "rand_scratch_mb" (1 024)  what the per-level state and one batch of pairs' partial sums may take as allocated: a
+ *                          batch holds as many pairs as keep both within four fifths of it; at least one
+ *     "rand_batch" (0)     pairs per batch, whatever the cap says (0 = from the cap; tests)
+ *     "rand_wave_max" (64) classes of up to this many samples take the wave route of the pair stage, longer ones the
+ *                          LDS table; 0 forbids the wave route, a value of at least n forces it for every class (tests)
+ *     "rand_window" (0)    ranks per LDS table window of the pair stage (0 = as many as the table holds, 8 192; small
+ *                          values force the windowed path: tests); -1 forbids the windowed path: the classes of a pair
+ *                          that would need more than one window take the wave route.  A single table cannot be forced
+ *                          beyond the 8 192 ranks it holds.
  *   host calls
  *     "chunk_rows" (8 Mi)  rows per sub-band of a host query (about an eighth of the job, at least 1 Mi, below 16 Mi
  *                          rows); also scales the pieces of the fused host edge call
@@ -857,6 +867,33 @@ int ppk_silhouette_dev(const float *d_dist, size_t n_rows, int metric, const int
  * n_labels, valid int32 [n_levels], on device_id; blocking. */
 int ppk_silhouette(const float *dist, size_t n_rows, int metric, const int32_t *labels, size_t n_levels, int shift,
                    int device_id, double *a, double *b, double *s, int32_t *n_labels, int32_t *valid);
+
+/* ------------------------------------------------------------------------
+ * Contingency sums: what the Rand and adjusted Rand indices between two clusterings of the same n
+ * samples are made of, for every level of a family A against every level of a family B in one call.  d_a int32
+ * [n_a][n], d_b int32 [n_b][n]: cluster numbers in [1, n]; rows of ppk_cluster_sweep_dev's d_clusters qualify.  The
+ * numbers may have gaps and the levels need not be nested.  d_b == NULL means B = A (n_b is then taken as n_a, and
+ * d_sq_b / d_labels_b may be NULL): every level against every level, each pair computed once.
+ *     d_sq_a[x]        long long [n_a]: the sum over the labels of level x of (class size)^2
+ *     d_labels_a[x]    int32 [n_a]: the distinct labels of level x          (d_sq_b, d_labels_b: the same of B, [n_b])
+ *     d_sq_cells[x][y] long long [n_a][n_b]: the sum over the non-empty cells of the contingency table of n_ij^2
+ *     d_n_cells[x][y]  long long [n_a][n_b]: the non-empty cells; level x refines level y iff it equals d_labels_a[x]
+ * All of them are integers, exact (every sum is at most n^2 < 2^62), the same bits on every call and for every value
+ * of the routing options; nothing on the device is floating point.  poppunk_amd.scores turns them into sklearn's
+ * pair_confusion_matrix, rand_score and adjusted_rand_score and the reference script's rand_index_score.
+ * PPK_ERR_ARG, before any device is touched: a NULL required array, n == 0, n >= 2^31 - 1, n_a == 0, more than 1 023
+ * levels on a side.  PPK_ERR_ARG, ppk_last_error() naming the first offender ("side a, level 2, sample 17: label 0
+ * outside [1, 100]"; A's levels come before B's): a label outside [1, n].  Synchronises the stream once (the read-back
+ * of the first offender and of every level's label count, before the pair stage).  Scratch: 12 bytes per (level,
+ * sample) of state, and the pairs' partial sums in batches, under option "rand_scratch_mb".
+ * (Replaces the per-pair sklearn calls of scripts/poppunk_calculate_rand_indices.py:138-141.) */
+int ppk_contingency_sums_dev(const int32_t *d_a, size_t n_a, const int32_t *d_b, size_t n_b, size_t n,
+                             long long *d_sq_a, long long *d_sq_b, int32_t *d_labels_a, int32_t *d_labels_b,
+                             long long *d_sq_cells, long long *d_n_cells, void *stream);
+/* Host arrays of the same shapes (b == NULL: B = A; sq_b and labels_b may then be NULL), on device_id; blocking. */
+int ppk_contingency_sums(const int32_t *a, size_t n_a, const int32_t *b, size_t n_b, size_t n, int device_id,
+                         long long *sq_a, long long *sq_b, int32_t *labels_a, int32_t *labels_b, long long *sq_cells,
+                         long long *n_cells);
 
 /* ------------------------------------------------------------------------
  * Density grids of a resident float32 [n_rows][2] matrix: the two layers of the fit plots, each one

@@ -74,6 +74,10 @@ const OptionEntry kOptions[] = {
     {"silhouette_scratch_mb", "PPK_SILHOUETTE_SCRATCH_MB", &PpkConfig::silhouette_scratch_mb},
     {"silhouette_band", "PPK_SILHOUETTE_BAND", &PpkConfig::silhouette_band},
     {"silhouette_window", "PPK_SILHOUETTE_WINDOW", &PpkConfig::silhouette_window},
+    {"rand_scratch_mb", "PPK_RAND_SCRATCH_MB", &PpkConfig::rand_scratch_mb},
+    {"rand_batch", "PPK_RAND_BATCH", &PpkConfig::rand_batch},
+    {"rand_wave_max", "PPK_RAND_WAVE_MAX", &PpkConfig::rand_wave_max},
+    {"rand_window", "PPK_RAND_WINDOW", &PpkConfig::rand_window},
     {"knn_list", "PPK_KNN_LIST", &PpkConfig::knn_list},
     {"knn_warm", "PPK_KNN_WARM", &PpkConfig::knn_warm},
     {"knn_cut", "PPK_KNN_CUT", &PpkConfig::knn_cut},

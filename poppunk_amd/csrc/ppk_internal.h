@@ -138,6 +138,10 @@ struct PpkConfig {
   std::atomic<long long> silhouette_scratch_mb{1024}; // PPK_SILHOUETTE_SCRATCH_MB: what the band of square rows of ppk_silhouette_dev may take as allocated (float32 [band][n] stays within four fifths of it; at least one row; same results)
   std::atomic<long long> silhouette_band{0};    // PPK_SILHOUETTE_BAND: samples per band whatever the cap says (0 = from the cap; tests; same results)
   std::atomic<long long> silhouette_window{0};  // PPK_SILHOUETTE_WINDOW: labels per LDS table window of the silhouette's sums stage (0 = as many as the table holds, 4 096; small values force the windowed path: tests; same results)
+  std::atomic<long long> rand_scratch_mb{1024}; // PPK_RAND_SCRATCH_MB: what ppk_contingency_sums_dev's per-level state and the partial sums of one batch of pairs may take as allocated (a batch holds as many pairs as keep both within four fifths of it; at least one; same results)
+  std::atomic<long long> rand_batch{0};         // PPK_RAND_BATCH: pairs per batch whatever the cap says (0 = from the cap; tests; same results)
+  std::atomic<long long> rand_wave_max{64};     // PPK_RAND_WAVE_MAX: classes of up to this many samples take the wave route of the pair stage, longer ones the LDS table (0 forbids the wave route; a value of at least n forces it for every class: tests; same results)
+  std::atomic<long long> rand_window{0};        // PPK_RAND_WINDOW: ranks per LDS table window of the pair stage (0 = as many as the table holds, 8 192; small values force the windowed path: tests; -1 forbids it: the classes of a pair that would need more than one window take the wave route; same results)
   std::atomic<long long> knn_list{0};           // PPK_KNN_LIST: entries of the neighbour-candidate list (0 = sized from n and knn)
   std::atomic<long long> host_parts_rows{16 << 20};   // PPK_HOST_PARTS_ROWS: ... from this many rows up
   std::atomic<long long> host_parts{2};         // PPK_HOST_PARTS: worker threads of a one-device host query (>= 16 Mi rows)
@@ -311,7 +315,9 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_DENSITY = 24,                      // the density grids' coordinates, scale keys and first-offender words
        SLOT_PAIRS = 25,                        // a pair list's first-bad-pair word, sample flags and slots, the chunk's row image, ids and counts
        SLOT_SILHOUETTE = 26,                   // the silhouette's first-offender words, label histogram and band of square rows
-       SLOT_COUNT = 27 };
+       SLOT_RAND = 27,                         // the contingency sums' first-offender word and per-level state: segment ends, grouped sample indices, dense ranks, long classes
+       SLOT_RAND_SUMS = 28,                    // ... and one batch of pairs' partial sums (sized after the levels have been read: growing a slot moves it)
+       SLOT_COUNT = 29 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and

@@ -1011,6 +1011,41 @@ def silhouette_dev(dist_t, levels_t, metric=2, shift=None, want_ab=False):
     return out[0], counts[0], counts[1]
 
 
+def contingency_sums_dev(levels_a, levels_b=None):
+    """The integer sums the Rand and adjusted Rand indices are made of (ppk_contingency_sums_dev, DESIGN.md 3.20;
+    tests/contingency_model.py restates them): levels_a int32 [n_a, n] CUDA, levels_b int32 [n_b, n] CUDA or None for
+    B = A, cluster numbers in [1, n] (gaps allowed, levels need not be nested; engine.cluster_sweep_dev's rows
+    qualify).  Returns (sq_a int64 [n_a], sq_b int64 [n_b], labels_a int32 [n_a], labels_b int32 [n_b], sq_cells int64
+    [n_a, n_b], n_cells int64 [n_a, n_b]) as CUDA tensors: the squared class sizes and the label count of every level,
+    the squared cell sizes and the non-empty cells of every pair's contingency table."""
+    torch = _torch()
+
+    def check(t, what):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.is_contiguous()):
+            raise TypeError("%s must be a contiguous int32 [n_levels, n] CUDA tensor" % what)
+
+    check(levels_a, "levels_a")
+    n_a, n = int(levels_a.shape[0]), int(levels_a.shape[1])
+    n_b = n_a
+    if levels_b is not None:
+        check(levels_b, "levels_b")
+        if int(levels_b.shape[1]) != n or levels_b.device != levels_a.device:
+            raise TypeError("levels_b must have levels_a's %d samples and live on its device" % n)
+        n_b = int(levels_b.shape[0])
+    dev = levels_a.device
+    with torch.cuda.device(dev):
+        sq = [torch.empty(max(k, 1), dtype=torch.int64, device=dev) for k in (n_a, n_b)]
+        labels = [torch.empty(max(k, 1), dtype=torch.int32, device=dev) for k in (n_a, n_b)]
+        cells = torch.empty((2, max(n_a, 1), max(n_b, 1)), dtype=torch.int64, device=dev)
+        rc = _lib.lib().ppk_contingency_sums_dev(
+            C.c_void_p(levels_a.data_ptr()), n_a, None if levels_b is None else C.c_void_p(levels_b.data_ptr()), n_b, n,
+            C.c_void_p(sq[0].data_ptr()), C.c_void_p(sq[1].data_ptr()), C.c_void_p(labels[0].data_ptr()),
+            C.c_void_p(labels[1].data_ptr()), C.c_void_p(cells[0].data_ptr()), C.c_void_p(cells[1].data_ptr()),
+            _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_contingency_sums_dev")
+    return sq[0][:n_a], sq[1][:n_b], labels[0][:n_a], labels[1][:n_b], cells[0][:n_a, :n_b], cells[1][:n_a, :n_b]
+
+
 def _kde_args(gx, gy, scale):
     gx = np.ascontiguousarray(gx, dtype=np.float64)
     gy = np.ascontiguousarray(gy, dtype=np.float64)
