@@ -135,6 +135,13 @@ int ppk_device_count(int *n);
  *                          values force the windowed path: tests); -1 forbids the windowed path: the classes of a pair
  *                          that would need more than one window take the wave route.  A single table cannot be forced
  *                          beyond the 8 192 ranks it holds.
+ *   strain lineages (ppk_strain_knn_dev; exercised by its own GPU tests, not by the campaign)
+ *     "lineage_scratch_mb" (1 024)  what the two key buffers of one band of rows of the long route may take as
+ *                          allocated: a band holds as many rows of a strain as keep both within four fifths of it; at
+ *                          least one
+ *     "lineage_lds_keys" (0)   the longest row (members of the strain but one) sorted in LDS (0 = as many keys as the
+ *                          table holds, 4 096; smaller values send shorter strains through the long route: tests; rows
+ *                          of up to 64 keys keep the wave route)
  *   host calls
  *     "chunk_rows" (8 Mi)  rows per sub-band of a host query (about an eighth of the job, at least 1 Mi, below 16 Mi
  *                          rows); also scales the pieces of the fused host edge call
@@ -894,6 +901,61 @@ int ppk_contingency_sums_dev(const int32_t *d_a, size_t n_a, const int32_t *d_b,
 int ppk_contingency_sums(const int32_t *a, size_t n_a, const int32_t *b, size_t n_b, size_t n, int device_id,
                          long long *sq_a, long long *sq_b, int32_t *labels_a, int32_t *labels_b, long long *sq_cells,
                          long long *n_cells);
+
+/* ------------------------------------------------------------------------
+ * Lineages within every strain: the neighbour lists and rank prefixes LineageFit builds inside each
+ * strain (poppunk_lineages --create-db, PopPUNK/lineages.py:156-326), for all strains in one call each, from the
+ * resident self/condensed float32 [n(n-1)/2][2] matrix.
+ * Strains: d_members int64 [m] (device), the strains' member lists back to back -- global sample ids, each list in the
+ * strain's LOCAL order, which is the caller's (it need not ascend, and strains may interleave in id space); seg_off
+ * int64 [n_strains + 1], a HOST array: strain s is d_members[seg_off[s] .. seg_off[s + 1]), n_s members.  A sample in
+ * no strain does not appear.  PPK_ERR_ARG before any device is touched: a NULL array, seg_off[0] != 0, a strain of
+ * fewer than 2 members ("strain 3 has 1 members: a strain needs at least 2").  PPK_ERR_ARG, ppk_last_error() naming the
+ * first offender by position: an id outside [0, n) ("strain 1, member 4: sample 700 outside [0, 700)"), an id that an
+ * earlier position holds ("strain 2, member 0: sample 17 is already member 5 of strain 0").
+ *
+ * ppk_strain_knn_dev: for every member, its d_s = min(depth, n_s - 1) nearest members of its own strain in
+ * get_kNN_distances' order (src/extend.cpp:248-289): ascending distance (column dist_col), ties by local column, the
+ * member itself skipped; -0.0 ties with and is returned as 0.0.  d_i, d_j int64, d_out float32 [nnz], nnz = the sum of
+ * n_s * d_s: strain by strain, local row by local row, (local row, local column, distance).  Row r of strain s is bit
+ * for bit what ppk_knn_dev gives on the square of that strain's pruned matrix.  No limit on depth or n_s but memory
+ * (and fewer than 2^31 members per strain).  Synchronises the stream once: the check of the member lists, before
+ * anything is indexed by them (nnz itself is known to the caller beforehand).  Routes: the header of ppk_lineage.hip.
+ * [get_kNN_distances is C++ that cannot be compiled in this tree (Eigen is missing): parity with it is unpinned, as
+ * for ppk_knn_dev, with which this call agrees bit for bit -- OUTSIDE SURVEY 8 stays as marked below.]
+ *
+ * ppk_strain_ranks_dev: lowerRank's rule (src/extend.cpp:128-246, as ppk_lower_rank states it: kNN + 1 entries without
+ * count_unique_distances, `prev` starting at 0.0, steps of at least epsilon in float32) applied to the sorted lists
+ * d_j / d_dist of ppk_strain_knn_dev (same seg_off and depth; distances unfloored), for every rank of `ranks` (HOST
+ * int32 [n_ranks], at least 1, ascending, n_ranks <= 1 023) at once.  On a sorted row the rule keeps a prefix:
+ *     d_prefix int32 [n_ranks][m]: d_prefix[q][g] = the entries of the row of position g that rank q keeps
+ * and the family is nested in the rank.  The level stream, *n_out entries in the order (position, place in the row):
+ * (d_pos_i, d_pos_j, d_level) int64, positions into d_members, level = a rank index; d_level_dist (nullable) float32,
+ * the entry's distance.  Every unordered pair appears at most once:
+ *     reciprocal_only == 0: a pair kept in either direction, at the lowest rank index at which either is kept; from the
+ *         lower row (i < j) where both directions are kept under the last rank, else as the one direction has it
+ *     reciprocal_only != 0: i < j, both directions kept, at the later of the two levels -- the entries of level <= q,
+ *         in stream order, are lowerRank's reciprocal output for rank q
+ * so (d_pos_i, d_pos_j, d_level) is an edge stream for ppk_cluster_sweep_dev with n_vertices = m, n_off = n_ranks.
+ * Positions keep local order inside a segment, so a strain's printClusters number of a member is the dense rank of its
+ * number among the numbers of its segment.  PPK_ERR_CAPACITY with *n_out set when the stream exceeds cap (worst case
+ * nnz).  PPK_ERR_ARG naming the first row with a column outside its strain or equal to the row.  Compare and integer arithmetic only: the
+ * same bits on every call.  Synchronises the stream once (the stream's length, before it is written). */
+int ppk_strain_knn_dev(const float *d_dist, size_t n, int dist_col, const long long *d_members,
+                       const long long *seg_off, size_t n_strains, size_t depth, long long *d_i, long long *d_j,
+                       float *d_out, void *stream);
+int ppk_strain_ranks_dev(const long long *d_j, const float *d_dist, const long long *seg_off, size_t n_strains,
+                         size_t depth, const int32_t *ranks, size_t n_ranks, int reciprocal_only,
+                         int count_unique_distances, float epsilon, int32_t *d_prefix, long long *d_pos_i,
+                         long long *d_pos_j, long long *d_level, float *d_level_dist, size_t cap, size_t *n_out,
+                         void *stream);
+/* Host arrays of the same shapes (dist float32 [n(n-1)/2][2], members int64 [m]), on device_id; blocking. */
+int ppk_strain_knn(const float *dist, size_t n, int dist_col, const long long *members, const long long *seg_off,
+                   size_t n_strains, size_t depth, int device_id, long long *i_out, long long *j_out, float *d_out);
+int ppk_strain_ranks(const long long *j, const float *dist, const long long *seg_off, size_t n_strains, size_t depth,
+                     const int32_t *ranks, size_t n_ranks, int reciprocal_only, int count_unique_distances,
+                     float epsilon, int device_id, int32_t *prefix, long long *pos_i, long long *pos_j,
+                     long long *level, float *level_dist, size_t cap, size_t *n_out);
 
 /* ------------------------------------------------------------------------
  * Density grids of a resident float32 [n_rows][2] matrix: the two layers of the fit plots, each one

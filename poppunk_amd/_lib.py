@@ -97,6 +97,12 @@ SIGNATURES = {
                                  _i32p]),
     "ppk_contingency_sums_dev": (C.c_int, [_vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ppk_contingency_sums": (C.c_int, [_i32p, _sz, _i32p, _sz, _sz, C.c_int, _llp, _llp, _i32p, _i32p, _llp, _llp]),
+    "ppk_strain_knn_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _llp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "ppk_strain_ranks_dev": (C.c_int, [_vp, _vp, _llp, _sz, _sz, _i32p, _sz, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp,
+                                       _vp, _vp, _sz, _szp, _vp]),
+    "ppk_strain_knn": (C.c_int, [_f32p, _sz, C.c_int, _llp, _llp, _sz, _sz, C.c_int, _llp, _llp, _f32p]),
+    "ppk_strain_ranks": (C.c_int, [_llp, _f32p, _llp, _sz, _sz, _i32p, _sz, C.c_int, C.c_int, C.c_float, C.c_int, _i32p,
+                                   _llp, _llp, _llp, _f32p, _sz, _szp]),
     "ppk_density_kde_dev": (C.c_int, [_vp, _sz, _vp, _sz, _f32p, _f64p, _sz, _f64p, _sz, C.c_double, C.c_int, _vp, _f32p,
                                       _vp]),
     "ppk_density_kde": (C.c_int, [_f32p, _sz, _llp, _sz, _f32p, _f64p, _sz, _f64p, _sz, C.c_double, C.c_int, C.c_int,

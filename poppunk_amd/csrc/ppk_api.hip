@@ -78,6 +78,8 @@ const OptionEntry kOptions[] = {
     {"rand_batch", "PPK_RAND_BATCH", &PpkConfig::rand_batch},
     {"rand_wave_max", "PPK_RAND_WAVE_MAX", &PpkConfig::rand_wave_max},
     {"rand_window", "PPK_RAND_WINDOW", &PpkConfig::rand_window},
+    {"lineage_scratch_mb", "PPK_LINEAGE_SCRATCH_MB", &PpkConfig::lineage_scratch_mb},
+    {"lineage_lds_keys", "PPK_LINEAGE_LDS_KEYS", &PpkConfig::lineage_lds_keys},
     {"knn_list", "PPK_KNN_LIST", &PpkConfig::knn_list},
     {"knn_warm", "PPK_KNN_WARM", &PpkConfig::knn_warm},
     {"knn_cut", "PPK_KNN_CUT", &PpkConfig::knn_cut},

@@ -1046,6 +1046,111 @@ def contingency_sums_dev(levels_a, levels_b=None):
     return sq[0][:n_a], sq[1][:n_b], labels[0][:n_a], labels[1][:n_b], cells[0][:n_a, :n_b], cells[1][:n_a, :n_b]
 
 
+def _strain_segments(seg_off):
+    seg = np.ascontiguousarray(seg_off, dtype=np.int64)
+    if seg.ndim != 1 or seg.shape[0] < 2:
+        raise ValueError("seg_off must be a one-dimensional array of n_strains + 1 offsets")
+    return seg
+
+
+def strain_nnz(seg_off, depth):
+    """The entries of strain_knn_dev's lists: the sum over the strains of n_s * min(depth, n_s - 1)."""
+    sizes = np.diff(_strain_segments(seg_off))
+    return int((sizes * np.minimum(int(depth), sizes - 1)).sum())
+
+
+def strain_knn_dev(dist_t, members_t, seg_off, depth, dist_col=0):
+    """Every member's min(depth, n_s - 1) nearest members of its own strain, for all strains in one call
+    (ppk_strain_knn_dev; tests/lineage_model.py restates it): dist_t the resident float32
+    [n(n-1)/2, 2] CUDA matrix, members_t int64 [m] CUDA (the strains' member lists back to back, global ids, each in
+    the strain's local order), seg_off the n_strains + 1 offsets (host).  Returns CUDA tensors (i, j, dist) with LOCAL
+    indices, strain by strain and row by row: per strain what ppk_knn_dev gives on its pruned square."""
+    torch = _torch()
+    _check_dist_tensor(dist_t)
+    n_rows = int(dist_t.shape[0])
+    n = _samples_of(n_rows)
+    if n * (n - 1) // 2 != n_rows:
+        raise ValueError("the matrix must hold n(n-1)/2 rows")
+    if not (members_t.is_cuda and members_t.dtype == torch.int64 and members_t.dim() == 1
+            and members_t.is_contiguous() and members_t.device == dist_t.device):
+        raise TypeError("members must be a contiguous int64 [m] CUDA tensor on the matrix's device")
+    seg = _strain_segments(seg_off)
+    if int(seg[-1]) != int(members_t.shape[0]):
+        raise ValueError("seg_off must end at the number of members")
+    sizes = np.diff(seg)
+    nnz = strain_nnz(seg, depth) if len(sizes) and sizes.min() >= 2 and int(depth) >= 1 else 0
+    dev = dist_t.device
+    with torch.cuda.device(dev):
+        oi = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
+        oj = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
+        od = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
+        rc = _lib.lib().ppk_strain_knn_dev(
+            C.c_void_p(dist_t.data_ptr()), n, int(dist_col), C.c_void_p(members_t.data_ptr()),
+            seg.ctypes.data_as(C.POINTER(C.c_longlong)), len(seg) - 1, int(depth), C.c_void_p(oi.data_ptr()),
+            C.c_void_p(oj.data_ptr()), C.c_void_p(od.data_ptr()), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_strain_knn_dev")
+    return oi[:nnz], oj[:nnz], od[:nnz]
+
+
+def strain_ranks_dev(j_t, d_t, seg_off, depth, ranks, reciprocal_only=False, count_unique_distances=False,
+                     epsilon=1e-10):
+    """lowerRank's rule for every rank on strain_knn_dev's sorted lists (ppk_strain_ranks_dev): j_t,
+    d_t the lists, same seg_off and depth, ranks ascending.  Returns (prefix int32 [n_ranks, m]: the entries of each
+    row each rank keeps; pos_i, pos_j, level int64 and dist float32: the level stream, positions into the member
+    array, every unordered pair once -- an edge stream for cluster_sweep_dev with n = m, n_off = n_ranks)."""
+    torch = _torch()
+    if not (j_t.is_cuda and j_t.dtype == torch.int64 and j_t.dim() == 1 and j_t.is_contiguous() and d_t.is_cuda
+            and d_t.dtype == torch.float32 and d_t.shape == j_t.shape and d_t.is_contiguous()
+            and d_t.device == j_t.device):
+        raise TypeError("the lists must be contiguous CUDA tensors of one length, int64 columns and float32 distances")
+    seg = _strain_segments(seg_off)
+    rk = np.ascontiguousarray(ranks, dtype=np.int32)
+    if rk.ndim != 1 or rk.shape[0] < 1:
+        raise ValueError("ranks must be a non-empty one-dimensional array")
+    m, n_ranks = int(seg[-1]), int(rk.shape[0])
+    sizes = np.diff(seg)
+    ok = len(sizes) and sizes.min() >= 2 and int(depth) >= 1
+    nnz = strain_nnz(seg, depth) if ok else 0
+    if ok and nnz != int(j_t.shape[0]):
+        raise ValueError("the lists must hold the %d entries of strain_knn_dev at this depth" % nnz)
+    # the stream holds no more than the last rank's prefixes: known exactly without count_unique_distances
+    cap = nnz if count_unique_distances or not ok else int((sizes * np.minimum(
+        np.minimum(int(depth), sizes - 1), int(rk.max()) + 1)).sum())
+    dev = j_t.device
+    with torch.cuda.device(dev):
+        prefix = torch.empty((n_ranks, max(m, 1)), dtype=torch.int32, device=dev)
+        pos = torch.empty((3, max(cap, 1)), dtype=torch.int64, device=dev)
+        sd = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
+        n_out = C.c_size_t(0)
+        rc = _lib.lib().ppk_strain_ranks_dev(
+            C.c_void_p(j_t.data_ptr()), C.c_void_p(d_t.data_ptr()), seg.ctypes.data_as(C.POINTER(C.c_longlong)),
+            len(seg) - 1, int(depth), rk.ctypes.data_as(C.POINTER(C.c_int32)), n_ranks, int(bool(reciprocal_only)),
+            int(bool(count_unique_distances)), float(np.float32(epsilon)), C.c_void_p(prefix.data_ptr()),
+            C.c_void_p(pos[0].data_ptr()), C.c_void_p(pos[1].data_ptr()), C.c_void_p(pos[2].data_ptr()),
+            C.c_void_p(sd.data_ptr()), cap, C.byref(n_out), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_strain_ranks_dev")
+    k = int(n_out.value)
+    return prefix[:, :m], pos[0, :k], pos[1, :k], pos[2, :k], sd[:k]
+
+
+def strain_cluster_numbers(clusters_t, seg_off):
+    """cluster_sweep_dev's rows over the m positions of all strains -> every strain's own printClusters numbers: a
+    member's number is the dense rank of its number among the numbers of its segment (positions keep local order
+    inside a segment, and components are ranked by size, then by their first vertex)."""
+    torch = _torch()
+    seg = _strain_segments(seg_off)
+    m = int(seg[-1])
+    seg_id = torch.as_tensor(np.repeat(np.arange(len(seg) - 1, dtype=np.int64), np.diff(seg)), device=clusters_t.device)
+    out = torch.empty_like(clusters_t)
+    for t in range(int(clusters_t.shape[0])):
+        key = seg_id * (m + 1) + clusters_t[t].to(torch.int64)
+        _, inverse = torch.unique(key, sorted=True, return_inverse=True)
+        first = torch.full((len(seg) - 1,), m, dtype=torch.int64, device=clusters_t.device)
+        first.scatter_reduce_(0, seg_id, inverse, reduce="amin")
+        out[t] = (inverse - first[seg_id] + 1).to(torch.int32)
+    return out
+
+
 def _kde_args(gx, gy, scale):
     gx = np.ascontiguousarray(gx, dtype=np.float64)
     gy = np.ascontiguousarray(gy, dtype=np.float64)

@@ -845,6 +845,11 @@ class DBSCANModel:
 EPSILON = 1e-10            # PopPUNK/models.py:75: sparse matrices hold no explicit zeros
 
 
+def rankFile(rank):
+    """PopPUNK/models.py:78-79: the file suffix of one rank's fit."""
+    return '_rank_' + str(rank) + '_fit.npz'
+
+
 class LineageRanks:
     """The state `LineageFit` builds and reads -- `nn_dists` (the neighbours at the search depth) and
     `lower_rank_dists[rank]`, scipy COO matrices -- with the same steps behind the same method names:
@@ -954,6 +959,43 @@ class LineageRanks:
         self.nn_dists = self._coo(higher[2], higher[0], higher[1], n)
         self._ranks_from((higher[0], higher[1], self.nn_dists.data), n)
         return self.assign(self.ranks[0])
+
+    def save(self, prefix):
+        """LineageFit.save (models.py:1240-1262) with `prefix` for its outPrefix: `<prefix>/<basename>_sparse_dists.npz`,
+        one `<basename>_rank_<r>_fit.npz` per rank (rankFile, models.py:78-79) and `<basename>_fit.pkl` holding
+        [[ranks, max_search_depth, reciprocal_only, count_unique_distances, dist_col, resolution], 'lineage']."""
+        import pickle
+
+        import scipy.sparse
+        if not self.fitted:
+            raise RuntimeError("Trying to save unfitted model")
+        stem = os.path.join(prefix, os.path.basename(prefix))
+        scipy.sparse.save_npz(stem + "_sparse_dists.npz", self.nn_dists)
+        for rank in self.ranks:
+            scipy.sparse.save_npz(stem + rankFile(rank), self.lower_rank_dists[rank])
+        with open(stem + "_fit.pkl", "wb") as pickle_file:
+            pickle.dump([[self.ranks, self.max_search_depth, self.reciprocal_only, self.count_unique_distances,
+                          self.dist_col, self.resolution], "lineage"], pickle_file)
+
+    @classmethod
+    def load(cls, prefix):
+        """The model `save(prefix)` wrote (loadClusterFit's lineage branch, models.py:127-140, and LineageFit.load,
+        :1264-1276; the rank matrices too, as assign.py reads them back)."""
+        import pickle
+
+        import scipy.sparse
+        stem = os.path.join(prefix, os.path.basename(prefix))
+        with open(stem + "_fit.pkl", "rb") as pickle_file:
+            fit_obj, fit_type = pickle.load(pickle_file)
+        if fit_type != "lineage":
+            raise RuntimeError("not a lineage model: " + str(fit_type))
+        ranks, depth, reciprocal_only, count_unique_distances, dist_col, resolution = fit_obj
+        m = cls(ranks, depth, reciprocal_only, count_unique_distances, resolution, dist_col)
+        m.max_search_depth = depth
+        m.nn_dists = scipy.sparse.load_npz(stem + "_sparse_dists.npz")
+        m.lower_rank_dists = {rank: scipy.sparse.load_npz(stem + rankFile(rank)) for rank in m.ranks}
+        m.fitted = True
+        return m
 
     def assign(self, rank):
         if not self.fitted:
