@@ -3,8 +3,12 @@ sklearn's recorded fits (tests/golden/bgmm_fit.npz), the host-only M-step and di
 restatement and scipy, the within / between label rules, save -> load, and the argument errors of the ABI.
 
 The restatement (ref_*) is what the GPU suite (tests/test_gpu_bgmm_fit.py) compares the device with, and what
-tests/golden/make_golden_bgmm_fit.py checks against sklearn before it writes a case."""
+tests/golden/make_golden_bgmm_fit.py checks against sklearn before it writes a case.  ref_sums_exact (the sums of one
+pass with math.fsum, and the scale each is compared on) and the seeded inputs of tests/test_gpu_bgmm_fit_shapes.py
+live here too, with the CPU tests of both."""
 import ctypes as C
+import functools
+import math
 import os
 
 import numpy as np
@@ -51,8 +55,8 @@ def ref_chol(S):
     return np.stack([np.linalg.cholesky(c) for c in S["cov"]])
 
 
-def ref_log_resp(X, S):
-    """The E-step: log responsibilities [n, K]."""
+def ref_weighted_log_prob(X, S):
+    """The E-step's weighted log-probabilities w [n, K]."""
     K = S["a"].size
     ds = digamma(S["a"] + S["b"])
     log_w = digamma(S["a"]) - ds + np.hstack((0, np.cumsum(digamma(S["b"]) - ds)[:-1]))
@@ -63,10 +67,19 @@ def ref_log_resp(X, S):
         lp[:, k] = -0.5 * (2 * np.log(2 * np.pi) + (y * y).sum(axis=1)) + np.log(np.diag(Pc)).sum()
     lp -= 0.5 * 2 * np.log(S["dof"])
     log_lambda = 2 * np.log(2.0) + digamma(0.5 * S["dof"]) + digamma(0.5 * (S["dof"] - 1))
-    w = lp + 0.5 * (log_lambda - 2 / S["beta"]) + log_w
+    return lp + 0.5 * (log_lambda - 2 / S["beta"]) + log_w
+
+
+def ref_logsumexp(w):
+    """scipy's logsumexp over the components: max + log sum exp(w - max)."""
     m = w.max(axis=1, keepdims=True)
-    lse = m[:, 0] + np.log(np.exp(w - m).sum(axis=1))
-    return w - lse[:, None]
+    return m[:, 0] + np.log(np.exp(w - m).sum(axis=1))
+
+
+def ref_log_resp(X, S):
+    """The E-step: log responsibilities [n, K]."""
+    w = ref_weighted_log_prob(X, S)
+    return w - ref_logsumexp(w)[:, None]
 
 
 def ref_bound(log_resp, S):
@@ -128,6 +141,43 @@ def ref_sums(X, resp, log_resp, pivot):
                   (r * d[:, 0] * d[:, 1]).sum(), (r * d[:, 1] * d[:, 1]).sum(),
                   0.0 if log_resp is None else (r * log_resp[:, k]).sum()]
     return out
+
+
+def ref_sums_exact(X64, S, pivot, counts=None):
+    """One device pass with no summation error of its own: (sums [K, 7], scales [K, 7]).
+
+    X64: the scaled rows xs = float32(x / scale) widened to float64.  S: a variational state (the E-step's
+    responsibilities) or an integer label per row (the one-hot passes: w = lse = 0).  counts[i]: how often row i occurs
+    (its term is multiplied by it), so n rows that repeat a block cyclically cost the block's terms only.  The terms
+    are float64 numpy, as ref_log_resp and ref_sums compute them; each sum is math.fsum's, exactly rounded.
+
+    scales[k, s] = S_i |term_iks| (1 + |w_ik| + |lse_i|), the seventh sum's term being r (1 + |log r|): log r = w - lse
+    carries an absolute error of a few eps (|w| + |lse|) (ppk_bgmm_lpr's multiply-add chain, device exp / log an ulp
+    or two from libm), r = exp(log r) carries that as a relative error, and the device's sum of the terms (at most 9
+    serial additions per lane below the grid's cap, then fixed trees) adds about 30 eps S |term|."""
+    pivot = np.asarray(pivot, dtype=np.float64)
+    K = pivot.shape[0]
+    if isinstance(S, dict):
+        w = ref_weighted_log_prob(X64, S)
+        lse = ref_logsumexp(w)
+        lr = w - lse[:, None]
+        r = np.exp(lr)
+        amp = 1.0 + np.abs(w) + np.abs(lse)[:, None]
+    else:
+        r = one_hot(np.asarray(S), K)
+        lr = np.zeros_like(r)
+        amp = np.ones_like(r)
+    c = np.ones(X64.shape[0]) if counts is None else np.asarray(counts, dtype=np.float64)
+    sums, scales = np.zeros((K, 7)), np.zeros((K, 7))
+    for k in range(K):
+        d, rk = X64 - pivot[k], r[:, k]
+        terms = [rk, rk * d[:, 0], rk * d[:, 1], rk * d[:, 0] * d[:, 0], rk * d[:, 0] * d[:, 1], rk * d[:, 1] * d[:, 1],
+                 rk * lr[:, k]]
+        sizes = [np.abs(t) for t in terms[:6]] + [rk * (1.0 + np.abs(lr[:, k]))]
+        for s in range(7):
+            sums[k, s] = math.fsum((c * terms[s]).tolist())
+            scales[k, s] = math.fsum((c * sizes[s] * amp[:, k]).tolist())
+    return sums, scales
 
 
 def ref_nearest(X, centres):
@@ -229,6 +279,101 @@ def state_from_ref(S, K):
         st.log_const[k] = ((-0.5 * 2 * np.log(2 * np.pi) + np.log(i0) + np.log(i1)) - 0.5 * 2 * np.log(S["dof"][k])
                            + 0.5 * (log_lambda - 2 / S["beta"][k]) + log_w[k])
     return st
+
+
+# ---- inputs of the shape tests (tests/test_gpu_bgmm_fit_shapes.py): one generator, its conditions asserted below ---------
+SHAPE_BLOCK = 4099                                          # rows of the block; larger n repeats it cyclically
+SHAPE_SCALE = np.array([0.037, 0.41], dtype=np.float32)
+SHAPE_KS = tuple(range(1, _lib.BGMM_MAX_K + 1))
+SHAPE_OUTLIERS, SHAPE_DUPLICATES = 41, 82                   # 1 % and 2 % of the block
+PLANTED = (1000.0, -1000.0)                                 # a centre no row is nearest to
+
+
+def _frozen(a):
+    a.setflags(write=False)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def shape_block():
+    """(raw float32 [4099, 2], xs = float32(raw / scale) as float64, positions of the outliers, of the duplicates and of
+    the rows they copy).  The rows lie around 16 centres on a 4 x 4 grid in [0, 1]^2 (sigma 0.02, a tenth of the
+    spacing) in scaled units; the outliers 40 to 60 units from (0.5, 0.5), where the components that hold no outlier
+    underflow to a responsibility of 0."""
+    rng = np.random.default_rng(20261020)
+    n = SHAPE_BLOCK
+    g = (np.arange(4) + 0.5) / 4
+    centres = np.array([(a, b) for a in g for b in g])
+    X = centres[rng.integers(0, 16, n)] + rng.normal(0.0, 0.02, (n, 2))
+    pos = rng.permutation(n)
+    out, dup = pos[:SHAPE_OUTLIERS], pos[SHAPE_OUTLIERS:SHAPE_OUTLIERS + SHAPE_DUPLICATES]
+    src = pos[SHAPE_OUTLIERS + SHAPE_DUPLICATES:SHAPE_OUTLIERS + 2 * SHAPE_DUPLICATES]
+    angle = rng.uniform(0.0, 2 * np.pi, out.size)
+    X[out] = 0.5 + 40.0 * rng.uniform(1.0, 1.5, (out.size, 1)) * np.stack([np.cos(angle), np.sin(angle)], axis=1)
+    X[dup] = X[src]
+    raw = (X * SHAPE_SCALE).astype(np.float32)
+    xs = (raw / SHAPE_SCALE).astype(np.float64)
+    return tuple(_frozen(a) for a in (raw, xs, out, dup, src))
+
+
+def shape_rows(n):
+    """Positions in the block of the n rows of a case: the block repeated cyclically."""
+    return np.arange(n) % SHAPE_BLOCK
+
+
+def shape_counts(n):
+    """How often each row of the block occurs among shape_rows(n)."""
+    return n // SHAPE_BLOCK + (np.arange(SHAPE_BLOCK) < n % SHAPE_BLOCK)
+
+
+def shape_labels(n, K):
+    return (np.arange(n) * 7 % K).astype(np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def shape_state(K):
+    """The K-component state every row count uses: the restatement's first iteration on the block from arbitrary labels
+    (only parameters; K = 7 and 14 leave components with next to no responsibility, which the scale carries)."""
+    return ref_fit(shape_block()[1], shape_labels(SHAPE_BLOCK, K), K, max_iter=1)["first"]
+
+
+@functools.lru_cache(maxsize=None)
+def shape_centres(K, n):
+    """Two sets of K centres for the first n rows of the block: k-means++ centres of its inliers with PLANTED inserted
+    at K // 2 (K = 1: the one drawn centre), and what one Lloyd step makes of them (an emptied centre keeps its
+    place)."""
+    X = shape_block()[1][:n]
+    inliers = X[np.abs(X - 0.5).max(axis=1) < 0.5]              # (drawn from every row, most centres would be outliers)
+    rng = np.random.default_rng(1000 * K + n)
+    if K == 1:
+        first = bgmm.kmeanspp_centres(inliers, 1, rng)
+    else:
+        first = np.insert(bgmm.kmeanspp_centres(inliers, K - 1, rng), K // 2, PLANTED, axis=0)
+    second = first.copy()
+    labels = ref_nearest(X, first)
+    for k in range(K):
+        if np.any(labels == k):
+            second[k] = first[k] + (X[labels == k] - first[k]).sum(axis=0) / np.count_nonzero(labels == k)
+    return _frozen(first), _frozen(second)
+
+
+@functools.lru_cache(maxsize=None)
+def tied_set():
+    """(rows float32 [n, 2] at scale (1, 1), centres [9, 2], a second set of 5 centres): every coordinate a multiple of
+    2^-6 below 4 in size, so every d2 and every sum of the pass is exact in double, in any order.  The rows are the
+    1/16 grid over [-0.5, 2.5]^2 (2 401 rows, two workgroups) and one more.  Centres 0 to 3 are the unit square's corners
+    (its centre ties four, its edges' midpoints two); (1.375, 0.5) ties centres 1, 3 and 4 and (1.5, 0.75) centres 3
+    and 4, across the edge between the first four components and the next; centres 5 and 6 are the same point.  The
+    second set repeats centre 1 as 2 and centre 3 as 4."""
+    t = np.arange(-8, 41) / 16.0
+    rows = np.array([(x, y) for x in t for y in t] + [(1.375, 0.5)], dtype=np.float32)
+    nine = np.array([(0, 0), (1, 0), (0, 1), (1, 1), (2, 0.5), (2, 2), (2, 2), (0, 2), (1, 2)], dtype=np.float64)
+    five = nine[[0, 1, 1, 3, 3]]
+    return _frozen(rows), _frozen(nine), _frozen(five)
+
+
+def nearest_d2(X, centres):
+    return np.stack([(X[:, 0] - c[0]) * (X[:, 0] - c[0]) + (X[:, 1] - c[1]) * (X[:, 1] - c[1]) for c in centres], axis=1)
 
 
 # ---- tests ---------------------------------------------------------------------------------------------------------
@@ -465,3 +610,108 @@ def test_kmeanspp_draw_is_seeded_and_bounded():
     assert all((scaled == ck).all(axis=1).any() for ck in c)
     same = np.full((10, 2), 0.25, dtype=np.float32)
     assert np.array_equal(bgmm.initial_centres(lambda pos: same, 10, (1.0, 1.0), 3, 1, 1)[0], np.full((3, 2), 0.25))
+
+
+# ---- the exact reference and the inputs of the shape tests ---------------------------------------------------------------
+def exact_close(got, want, scale, bar=1e-11):
+    """(largest |got - want| / scale, whether it is within bar); where the scale is 0 the two must be equal."""
+    err = np.abs(np.asarray(got, dtype=np.float64) - want)
+    if np.any(err[scale == 0] != 0) or not np.all(np.isfinite(err)):
+        return np.inf, False
+    d = float((err[scale > 0] / scale[scale > 0]).max()) if np.any(scale > 0) else 0.0
+    return d, d <= bar
+
+
+@pytest.mark.parametrize("case", cases())
+def test_exact_sums_equal_the_plain_ones(case):
+    g = case_of(golden(), case)
+    K = int(g["K"])
+    X = g["X"].astype(np.float64)
+    S = ref_fit(X, g["labels0"], K, max_iter=1)["init"]
+    lr = ref_log_resp(X, S)
+    want, scale = ref_sums_exact(X, S, S["means"])
+    assert np.all(scale[:, :1] > 0)
+    d, ok = exact_close(ref_sums(X, np.exp(lr), lr, S["means"]), want, scale)
+    assert ok, d
+    _, xk, _ = ref_stats(X, one_hot(g["labels0"], K))
+    want, scale = ref_sums_exact(X, g["labels0"], xk)
+    d, ok = exact_close(ref_sums(X, one_hot(g["labels0"], K), None, xk), want, scale)
+    assert ok, d
+    assert np.array_equal(want[:, 0], np.bincount(g["labels0"], minlength=K)) and np.all(want[:, 6] == 0)
+    assert np.array_equal(scale[:, 0], want[:, 0]) and np.array_equal(scale[:, 6], want[:, 0])
+
+
+def test_counts_equal_explicit_repetition():
+    _, xs, _, _, _ = shape_block()
+    X = xs[:37]
+    counts = np.array([(3 * i) % 5 for i in range(37)])             # zeros included
+    rep = np.repeat(X, counts, axis=0)
+    for K in (1, 5):
+        S = shape_state(K)
+        a, sa = ref_sums_exact(X, S, S["means"], counts)
+        b, sb = ref_sums_exact(rep, S, S["means"])
+        # (count * term rounds once where the repetition adds the term count times exactly: half an ulp per term)
+        assert np.all(np.abs(a - b) <= 2 * EPS * sb) and np.all(np.abs(sa - sb) <= 4 * EPS * sb)
+        lab = shape_labels(37, K)
+        a, sa = ref_sums_exact(X, lab, S["means"], counts)
+        b, sb = ref_sums_exact(rep, np.repeat(lab, counts), S["means"])
+        assert np.all(np.abs(a - b) <= 2 * EPS * sb) and np.array_equal(a[:, 0], b[:, 0])
+    for n in (1, 300, 4099, 4100, 524_289):
+        assert np.array_equal(shape_counts(n), np.bincount(shape_rows(n), minlength=SHAPE_BLOCK))
+
+
+def test_shape_inputs_meet_their_conditions():
+    raw, xs, out, dup, src = shape_block()
+    assert raw.dtype == np.float32 and raw.shape == (SHAPE_BLOCK, 2) and np.isfinite(raw).all() and np.isfinite(xs).all()
+    assert tuple(SHAPE_SCALE) != (1.0, 1.0)
+    assert out.size == SHAPE_OUTLIERS and dup.size == SHAPE_DUPLICATES
+    assert np.array_equal(raw[dup], raw[src]) and not set(dup) & set(src) and not set(out) & (set(dup) | set(src))
+    inl = np.setdiff1d(np.arange(SHAPE_BLOCK), out)
+    assert xs[inl].min() > 0.0 and xs[inl].max() < 1.0
+    assert np.hypot(*(xs[out] - 0.5).T).min() > 39.0
+    for K in SHAPE_KS:
+        S = shape_state(K)
+        assert all(np.isfinite(S[k]).all() for k in ("a", "b", "beta", "means", "dof", "cov"))
+        assert min(np.linalg.eigvalsh(c).min() for c in S["cov"]) > 0
+        r = np.exp(ref_log_resp(xs, S))
+        assert np.all(r.sum(axis=0) > 0)
+        sums, scale = ref_sums_exact(xs[:300], S, S["means"])
+        assert np.all(scale[:, 0] > 0) and np.isfinite(sums).all() and np.isfinite(scale).all()
+    # the outliers: with two components every one of them leaves a single responsibility above 0
+    r = np.exp(ref_log_resp(xs, shape_state(2)))
+    assert np.all((r[out] == 0).sum(axis=1) == 1) and np.all(r[inl] > 0)
+    assert sum(int((np.exp(ref_log_resp(xs, shape_state(K))) == 0).any()) for K in SHAPE_KS) >= 12
+
+
+@pytest.mark.parametrize("n", [300, 4097])
+def test_shape_centres_leave_no_label_to_a_rounding(n):
+    X = shape_block()[1][:n]
+    for K in SHAPE_KS:
+        for centres in shape_centres(K, n):
+            assert centres.shape == (K, 2) and np.isfinite(centres).all()
+            d2 = np.sort(nearest_d2(X, centres), axis=1)
+            if K > 1:
+                assert np.all(d2[:, 1] - d2[:, 0] > 1e-9 * d2[:, 1])
+                k = K // 2
+                assert tuple(centres[k]) == PLANTED and not np.any(ref_nearest(X, centres) == k)
+                assert nearest_d2(X, centres[k:k + 1]).min() > np.delete(nearest_d2(X, centres), k, axis=1).max()
+        a, b = shape_centres(K, n)
+        assert K <= 2 or np.any(ref_nearest(X, a) != ref_nearest(X, b))         # the second pass changes labels
+
+
+def test_tied_set_is_exact_and_holds_every_tie():
+    rows, nine, five = tied_set()
+    X = rows.astype(np.float64)
+    for a in (X, nine, five):
+        assert np.array_equal(a * 64, np.round(a * 64)) and np.abs(a).max() < 4
+    assert rows.shape[0] > 2048
+    d2 = nearest_d2(X, nine[:5])
+    ties = (d2 == d2.min(axis=1, keepdims=True)).sum(axis=1)
+    assert {2, 3, 4} <= set(ties.tolist())
+    first = ref_nearest(X, nine[:5])
+    across = (d2[:, 3] == d2.min(axis=1)) & (d2[:, 4] == d2.min(axis=1))
+    assert np.any(across & (ties == 2)) and np.any(across & (ties == 3)) and np.all(first[across] <= 3)
+    lab9 = ref_nearest(X, nine)
+    assert not np.any(lab9 == 6) and all(np.any(lab9 == k) for k in (0, 1, 2, 3, 4, 5, 7, 8))
+    lab5 = ref_nearest(X, five)
+    assert set(lab5.tolist()) == {0, 1, 3}
