@@ -1135,10 +1135,14 @@ int ppk_nj(const float *square, size_t n, int device_id, long long *join, double
  *  - per row, x_j = d_j^2 - min_j d_j^2 and beta by float64 bisection from beta = 1 (doubling while no upper bound is
  *    known) on H(beta) = ln Z + beta sum_j p_j x_j / Z, p_j = exp(-beta x_j), Z = sum_j p_j, toward H = ln(perplexity):
  *    H > target raises beta.  It stops once hi - lo <= hi * 2^-48, or after 256 steps: a row that cannot reach the
- *    target (K < perplexity, equal distances, zero distances of duplicates) ends at beta = 2^-256 or 2^256, finite;
+ *    target (equal distances, zero distances of duplicates) ends at beta = 2^-256 or 2^256, finite.  K <= perplexity
+ *    takes beta = 2^-256 without the bisection (at K == perplexity H is within rounding of the target up to
+ *    beta ~ 1e-8, and the comparison would follow the last bit of log);
  *  - P[e] = (p_j / Z) / n (sum P = 1), c[e] = rint(P[e] * 2^52), the integer sampling weight of edge e.
  *
- * ppk_embed_dev: P (as above, or any P in [0, 1]) + lists + seed -> d_Y float64 [n][2].  With W = min(workers, n)
+ * ppk_embed_dev: P (as above, or any P in [0, 1] whose weights c = rint(P * 2^52) can be summed in 64 bits: PPK_ERR_ARG
+ * naming the sum once sum(c >> 20) >= 2^43, that is for every sum of c from 2^63 + n k 2^20 and for none below 2^63,
+ * a sum of P of 2048; and PPK_ERR_ARG when every c is 0) + lists + seed -> d_Y float64 [n][2].  With W = min(workers, n)
  * workers per iteration (the cap that keeps small n stable) and T = max(1, rint(max_iter / W))
  * iterations (ties to even), every draw from the counter-based generator of ppk_embed.hip
  * (splitmix64 finaliser over seed, iteration, worker and draw):

@@ -32,6 +32,8 @@ constexpr int kCalSteps = 256;           // bisection steps of the calibration a
 constexpr double kCalTol = 0x1p-48;      // ... which stops once hi - lo <= hi * kCalTol
 constexpr long long kPoll = 256;         // iterations between two interrupt checks
 constexpr double kGainClip = 0.1;        // |gain| of one pair update per coordinate at most
+constexpr int kHighShift = 20;           // the weights' sum is refused once sum(c >> 20) >= 2^43: the sum of c is
+constexpr unsigned long long kHighMax = 1ull << 43;   // then >= 2^63 (a sum of P of 2048), and below it < 2^63 + m 2^20
 constexpr unsigned long long kGolden = 0x9E3779B97F4A7C15ull;
 constexpr unsigned long long kInitKey = 0xD1B54A32D192ED03ull;
 
@@ -110,9 +112,12 @@ __global__ void __launch_bounds__(kThreads) embed_rms_kernel(const double *part,
 // One thread per row r: x_j = (dist[r, j] / rms)^2 - min_j of the same, then beta by bisection (doubling while no
 // upper bound is known) until H(beta) = ln(perplexity) is bracketed within hi * kCalTol, at most kCalSteps steps.
 // P[r, j] = (p_j / Z) / n with p_j = exp(-beta x_j), Z = sum p_j; c[r, j] = rint(P * 2^52).
+// steps = 0 (k <= perplexity: no beta reaches the target) takes beta = 2^-256, where 256 halvings from 1 end, without
+// asking H: at k == perplexity H(beta) = ln k - beta^2 Var(x) / 2 is within rounding of the target up to beta ~ 1e-8,
+// and which way H > target then falls depends on the last bit of log.
 __global__ void __launch_bounds__(kThreads) embed_calibrate_kernel(const float *__restrict__ dist, size_t n, size_t k,
-                                                                   const double *rms_p, double target, double *P,
-                                                                   unsigned long long *c) {
+                                                                   const double *rms_p, double target, int steps,
+                                                                   double *P, unsigned long long *c) {
   const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
   const float *row = dist + r * k;
@@ -122,8 +127,8 @@ __global__ void __launch_bounds__(kThreads) embed_calibrate_kernel(const float *
     const double x = (double)row[j] / rms;
     xmin = fmin(xmin, x * x);
   }
-  double beta = 1.0, lo = 0.0, hi = INFINITY;
-  for (int step = 0; step < kCalSteps; ++step) {
+  double beta = steps ? 1.0 : 0x1p-256, lo = 0.0, hi = INFINITY;
+  for (int step = 0; step < steps; ++step) {
     double Z = 0.0, S = 0.0;
     for (size_t j = 0; j < k; ++j) {
       const double x = (double)row[j] / rms;
@@ -156,10 +161,19 @@ __global__ void __launch_bounds__(kThreads) embed_calibrate_kernel(const float *
 }
 
 // ---- weights / init ------------------------------------------------------------------------------------------------
+// c = rint(P * 2^52); high[0] += sum of c >> kHighShift, one integer atomic per wave (order-free).  Every term is at
+// most 2^32 (P <= 1 past the check; anything else is refused before the sum is looked at), so the high sum itself
+// cannot wrap below 2^32 entries.
 __global__ void __launch_bounds__(kThreads) embed_quantise_kernel(const double *__restrict__ P, size_t m,
-                                                                  unsigned long long *c) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += (size_t)gridDim.x * blockDim.x)
-    c[e] = (unsigned long long)rint(P[e] * 0x1p52);
+                                                                  unsigned long long *c, unsigned long long *high) {
+  unsigned long long hs = 0;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += (size_t)gridDim.x * blockDim.x) {
+    const unsigned long long v = (unsigned long long)rint(P[e] * 0x1p52);
+    c[e] = v;
+    hs += v >> kHighShift;
+  }
+  for (int o = PPK_LANES / 2; o > 0; o >>= 1) hs += __shfl_xor(hs, o);
+  if ((threadIdx.x & (PPK_LANES - 1)) == 0 && hs) atomicAdd(high, hs);
 }
 
 // Y[v][c] = ((u53 * 2^-53) * 2 - 1) * 1e-4 from draw 2v + c of the init key; Eq = 1; the deltas and q sums zero
@@ -339,7 +353,7 @@ extern "C" int ppk_embed_weights_dev(const long long *d_i, const long long *d_j,
   hipLaunchKernelGGL(embed_sumsq_kernel, dim3(kSumParts), dim3(kThreads), 0, s, d_dist, m, part);
   hipLaunchKernelGGL(embed_rms_kernel, dim3(1), dim3(kThreads), 0, s, part, m, rms);
   hipLaunchKernelGGL(embed_calibrate_kernel, dim3(grid_for(n, kThreads, 1u << 30)), dim3(kThreads), 0, s, d_dist, n,
-                     k, rms, std::log(perplexity), d_P, d_c);
+                     k, rms, std::log(perplexity), perplexity < (double)k ? kCalSteps : 0, d_P, d_c);
   PPK_HIP(hipGetLastError());
   ppk_prof_stage(nullptr, s);
   return PPK_OK;
@@ -362,7 +376,7 @@ extern "C" int ppk_embed_dev(const long long *d_i, const long long *d_j, const d
   PpkCall call(dev, s);
   const size_t m = n * k;
 
-  // scratch: bad | q sums | Eq | c | prefix | deltas | rocprim temp
+  // scratch: bad, high sum | q sums | Eq | c | prefix | deltas | rocprim temp
   size_t tmp_bytes = 0;
   PPK_HIP(rocprim::inclusive_scan(nullptr, tmp_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, m,
                                   rocprim::plus<unsigned long long>(), s));
@@ -371,27 +385,36 @@ extern "C" int ppk_embed_dev(const long long *d_i, const long long *d_j, const d
   double *Eq;
   char *tmp;
   if ((rc = ppk_scratch_carve(dev, SLOT_EMBED, [&](Carve &cv) {
-         cv.take(bad, 1).take(qacc, 2).take(Eq, 1).take(c, m).take(prefix, m).take(delta, 2 * n).take(tmp, tmp_bytes);
+         cv.take(bad, 2).take(qacc, 2).take(Eq, 1).take(c, m).take(prefix, m).take(delta, 2 * n).take(tmp, tmp_bytes);
        })) != PPK_OK)
     return rc;
 
   ppk_prof_stage("check", s);
+  unsigned long long *high = bad + 1;
   PPK_HIP(hipMemsetAsync(bad, 0xff, 8, s));
+  PPK_HIP(hipMemsetAsync(high, 0, 8, s));
   const unsigned gm = grid_for(m, kThreads, 4096);
   hipLaunchKernelGGL(embed_check_kernel, dim3(gm), dim3(kThreads), 0, s, d_i, d_j, (const float *)nullptr, d_P, n, k,
                      bad);
   PPK_HIP(hipGetLastError());
   ppk_prof_stage("weights", s);
-  hipLaunchKernelGGL(embed_quantise_kernel, dim3(gm), dim3(kThreads), 0, s, d_P, m, c);
+  hipLaunchKernelGGL(embed_quantise_kernel, dim3(gm), dim3(kThreads), 0, s, d_P, m, c, high);
   PPK_HIP(hipGetLastError());
   PPK_HIP(rocprim::inclusive_scan(tmp, tmp_bytes, c, prefix, m, rocprim::plus<unsigned long long>(), s));
   const unsigned long long *h = nullptr;
-  if ((rc = ppk_read_back(dev, s, {{bad, 8}, {prefix + (m - 1), 8}}, &h)) != PPK_OK) return rc;
+  if ((rc = ppk_read_back(dev, s, {{bad, 16}, {prefix + (m - 1), 8}}, &h)) != PPK_OK) return rc;
   if (h[0] != ~0ull) {
     ppk_prof_stage(nullptr, s);
     return bad_entry(who, d_i, d_j, nullptr, d_P, n, k, (size_t)h[0]);
   }
-  if (h[1] == 0) {
+  if (h[1] >= kHighMax) {
+    ppk_prof_stage(nullptr, s);
+    return ppk_fail(PPK_ERR_ARG, "ppk_embed: the sum of the weights rint(P * 2^52) is " +
+                                     std::to_string((double)h[1] * 0x1p20) + " or more (a sum of P of about " +
+                                     std::to_string((double)h[1] * 0x1p-32) +
+                                     "): it must stay below 2^63, a sum of P of 2048, to be summed in 64 bits");
+  }
+  if (h[2] == 0) {
     ppk_prof_stage(nullptr, s);
     return ppk_fail(PPK_ERR_ARG, "ppk_embed: every weight rint(P * 2^52) is 0");
   }
