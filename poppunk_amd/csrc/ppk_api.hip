@@ -1,14 +1,9 @@
-// C-ABI entry points of libppk_hip.so (declared in include/ppk.h): errors, options, resident databases, per-device
-// scratch and the DEVICE entry points of kernels 1 and 2.  The host-buffer entry points (what PopPUNK itself calls:
-// worker threads, uploads, downloads, what is kept between calls) are in ppk_host.hip.
+// C-ABI entry points of libppk_hip.so (declared in include/ppk.h): errors, options, resident databases and the DEVICE
+// entry points of kernels 1 and 2 (what is kept per device: ppk_devstate.hip).  The host-buffer entry points (what
+// PopPUNK itself calls: worker threads, uploads, downloads, what is kept between calls) are in ppk_host.hip.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstring>
-#include <deque>
-#include <pthread.h>
-#include <unistd.h>
 #include <functional>
 #include <memory>
 #include <map>
@@ -128,35 +123,6 @@ extern "C" int ppk_get_option(const char *name, long long *value) {
       return PPK_OK;
     }
   return ppk_fail(PPK_ERR_ARG, std::string("unknown option: ") + name);
-}
-
-// ---- the only supported target: gfx950 (MI355X), wave64 ---------------------------------------
-// Every kernel in this library is compiled for gfx950 alone and the tile kernels are fixed-register
-// wave64 instruction streams; on anything else the launches would fail with "no kernel image" (or
-// worse).  Checked once per device, loudly.
-int ppk_check_arch(int device_id) {
-  static std::mutex mu;
-  static int verdict[64] = {0};   // 0 unknown, 1 ok, -1 refused
-  static std::string why[64];
-  if (device_id < 0 || device_id >= 64) return ppk_fail(PPK_ERR_ARG, "device id out of range");
-  std::lock_guard<std::mutex> lk(mu);
-  if (verdict[device_id] == 0) {
-    hipDeviceProp_t prop;
-    hipError_t e = hipGetDeviceProperties(&prop, device_id);
-    if (e != hipSuccess) {
-      why[device_id] = std::string("hipGetDeviceProperties: ") + hipGetErrorString(e);
-      verdict[device_id] = -1;
-    } else if (strncmp(prop.gcnArchName, "gfx950", 6) != 0 || prop.warpSize != 64) {
-      why[device_id] = std::string("device ") + std::to_string(device_id) + " is " + prop.gcnArchName +
-                       " (wavefront " + std::to_string(prop.warpSize) +
-                       "): libppk_hip.so is built for gfx950 / wave64 (MI355X) only";
-      verdict[device_id] = -1;
-    } else {
-      verdict[device_id] = 1;
-    }
-  }
-  if (verdict[device_id] < 0) return ppk_fail(PPK_ERR_HIP, why[device_id]);
-  return PPK_OK;
 }
 
 extern "C" int ppk_device_count(int *n) {
@@ -383,8 +349,7 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   if (sketchsize64 * 64 >= ((size_t)1 << 31))
     return ppk_fail(PPK_ERR_ARG, "ppk_db_create: sketch too large");
   if (n >= ((size_t)1 << 31)) return ppk_fail(PPK_ERR_ARG, "ppk_db_create: too many samples (sample indices are 32-bit)");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
+  PPK_ENTER_DEVICE(guard, device_id);
   if (int rc_arch = ppk_check_arch(device_id)) return rc_arch;
   hipStream_t s = static_cast<hipStream_t>(stream);
 
@@ -416,14 +381,7 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   const size_t out_bytes = db->npad * cols * sizeof(uint64_t);
 
   auto bail = [&](int code, const std::string &msg) {
-    if (db->d_skT) (void)hipFree(db->d_skT);
-    if (db->d_skR) (void)hipFree(db->d_skR);
-    if (db->d_foldR) (void)hipFree(db->d_foldR);
-    if (db->d_foldQ) (void)hipFree(db->d_foldQ);
-    for (void *ptr : {(void *)db->d_fold2R, (void *)db->d_fold2Q, (void *)db->d_fold2_ev, (void *)db->d_fold2_off})
-      if (ptr) (void)hipFree(ptr);
-    if (db->d_clu) (void)hipFree(db->d_clu);
-    delete db;
+    ppk_db_destroy(db);
     return ppk_fail(code, msg);
   };
   hipError_t e = hipMalloc(reinterpret_cast<void **>(&db->d_skT), out_bytes);
@@ -596,8 +554,7 @@ extern "C" int ppk_db_rank_read(const ppk_db *db, uint64_t *out, size_t words) {
   if (!db->rank_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_rank_read: the database has no rank-coded copy");
   if (words != db->nk * db->s64 * (size_t)db->rank_planes * db->npad)
     return ppk_fail(PPK_ERR_ARG, "ppk_db_rank_read: `words` is not nk * sketchsize64 * planes * padded samples");
-  DeviceGuard guard(db->device);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(db->device));
+  PPK_ENTER_DEVICE(guard, db->device);
   PPK_HIP(hipDeviceSynchronize());
   if (int rc = ppk_db_build_injective(const_cast<ppk_db *>(db))) return rc;
   PPK_HIP(hipMemcpy(out, db->d_skR, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -611,8 +568,7 @@ extern "C" int ppk_db_fold_read(const ppk_db *db, int which, uint64_t *out, size
   if (!db->fold_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold_read: the database has no folded pair");
   if (words != db->nk * db->s64 * (size_t)db->fold_planes * db->npad)
     return ppk_fail(PPK_ERR_ARG, "ppk_db_fold_read: `words` is not nk * sketchsize64 * planes * padded samples");
-  DeviceGuard guard(db->device);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(db->device));
+  PPK_ENTER_DEVICE(guard, db->device);
   PPK_HIP(hipDeviceSynchronize());
   PPK_HIP(hipMemcpy(out, which ? db->d_foldQ : db->d_foldR, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return PPK_OK;
@@ -637,8 +593,7 @@ extern "C" int ppk_db_fold2_read(const ppk_db *db, int which, uint64_t *out, siz
   if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_read: the database has no two-holder pair");
   if (words != db->nk * db->s64 * (size_t)db->fold2_planes * db->npad)
     return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_read: `words` is not nk * sketchsize64 * planes * padded samples");
-  DeviceGuard guard(db->device);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(db->device));
+  PPK_ENTER_DEVICE(guard, db->device);
   PPK_HIP(hipDeviceSynchronize());
   PPK_HIP(hipMemcpy(out, which ? db->d_fold2Q : db->d_fold2R, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return PPK_OK;
@@ -665,8 +620,7 @@ extern "C" int ppk_db_fold2_events_read(const ppk_db *db, uint32_t *off, size_t 
   if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_events_read: the database has no two-holder pair");
   if (n_off != (size_t)db->fold2_qt * db->fold2_rt + 1 || n_ev != db->fold2_events || (n_ev && !ev))
     return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_events_read: sizes are buckets + 1 and events (ppk_db_fold2_events)");
-  DeviceGuard guard(db->device);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(db->device));
+  PPK_ENTER_DEVICE(guard, db->device);
   PPK_HIP(hipDeviceSynchronize());
   PPK_HIP(hipMemcpy(off, db->d_fold2_off, n_off * sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (n_ev) PPK_HIP(hipMemcpy(ev, db->d_fold2_ev, n_ev * sizeof(uint16_t), hipMemcpyDeviceToHost));
@@ -696,6 +650,7 @@ extern "C" int ppk_db_rank_block_planes(const ppk_db *db, uint8_t *out, size_t c
 int ppk_check_pair(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, size_t q_begin,
                    size_t q_end) {
   if (!ref || !kmers) return ppk_fail(PPK_ERR_ARG, "ref database / kmers missing");
+  if (int rc = ppk_check_device(ref->device)) return rc;
   if (qry) {
     if (qry->device != ref->device) return ppk_fail(PPK_ERR_ARG, "ref and query databases on different devices");
     if (qry->nk != ref->nk || qry->s64 != ref->s64 || qry->bbits != ref->bbits)
@@ -707,79 +662,6 @@ int ppk_check_pair(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, s
 }
 
 namespace {
-// Per-device scratch (log-J table, edge bitmask, sort buffers ...): grow-only blocks shared by all
-// calls on a device.  Two rules make that safe for any caller:
-//  * every entry point that touches scratch holds the device's (recursive) mutex for the length of
-//    the call -- it only enqueues, so that is microseconds -- through a PpkCall scope, which also
-//    names the stream the call enqueues on;
-//  * a slot remembers, as an event recorded when the call that used it returns, the last work
-//    enqueued on it; a later call on a DIFFERENT stream makes its stream wait for that event
-//    before it re-uses (or re-allocates) the block.  Calls on one stream are ordered anyway.
-struct Scratch {
-  void *p = nullptr;
-  size_t bytes = 0;
-  hipEvent_t ev = nullptr;      // recorded after the last call that used the slot
-  hipStream_t last = nullptr;   // ... on this stream
-  bool recorded = false;
-};
-struct DevState {
-  std::recursive_mutex mu;
-  Scratch slot[SLOT_COUNT];
-  // the fit tables sitting in SLOT_LUT: key of what they were built from (0 = nothing valid) and the
-  // block they sit in -- a call with the same k list, random table and options skips the rebuild
-  uint64_t lut_key = 0;
-  const void *lut_ptr = nullptr;
-  // the pinned block of ppk_read_back (grow-only, never freed) and the kernels' dynamic-LDS opt-ins (ppk_lds_opt_in)
-  unsigned long long *pinned = nullptr;
-  size_t pinned_bytes = 0;
-  std::map<const void *, bool> lds_opt_in;
-};
-DevState g_dev[64];
-
-struct CallCtx {
-  int dev = -1;
-  hipStream_t s = nullptr;
-  unsigned touched = 0;
-};
-thread_local CallCtx tl_call;
-thread_local uint64_t tl_lut_pending_key = 0;
-thread_local const void *tl_lut_pending_ptr = nullptr;
-
-int scratch_get(int dev, int slot, size_t bytes, void **out) {
-  if (dev < 0 || dev >= 64 || slot < 0 || slot >= SLOT_COUNT)
-    return ppk_fail(PPK_ERR_ARG, "device id out of range");
-  if (tl_call.dev != dev) return ppk_fail(PPK_ERR_STATE, "internal: scratch requested outside a PpkCall scope");
-  Scratch &s = g_dev[dev].slot[slot];
-  if (s.recorded && s.last != tl_call.s) {
-    // the previous user ran on another stream: order this call's work after it
-    hipError_t e = hipStreamWaitEvent(tl_call.s, s.ev, 0);
-    if (e != hipSuccess) (void)hipDeviceSynchronize();
-  }
-  if (s.bytes < bytes) {
-    if (slot == SLOT_LUT) {          // the tables a later call might re-use go with the block
-      g_dev[dev].lut_key = 0;
-      g_dev[dev].lut_ptr = nullptr;
-    }
-    if (s.p) {
-      (void)hipDeviceSynchronize();  // earlier launches may still read the old block
-      (void)hipFree(s.p);
-      s.p = nullptr;
-      s.bytes = 0;
-    }
-    const size_t want = bytes + bytes / 4 + 4096;
-    hipError_t e = hipMalloc(&s.p, want);
-    if (e != hipSuccess) return ppk_fail(PPK_ERR_HIP, std::string("hipMalloc(scratch): ") + hipGetErrorString(e));
-    s.bytes = want;
-    // the per-tile counters of the k-split kernel start at zero and every launch leaves them there
-    if (slot == SLOT_TICKETS && hipMemset(s.p, 0, want) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipMemset(scratch) failed");
-    // the slot bitmap of the wide-k kernel likewise
-    if (slot == SLOT_WIDE && hipMemset(s.p, 0, 4096) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipMemset(scratch) failed");
-  }
-  tl_call.touched |= 1u << slot;
-  *out = s.p;
-  return PPK_OK;
-}
-
 // random table (host) -> device copy placed after the LUT in the LUT scratch.  *lut_ready: the
 // tables of an identical earlier call (same k list, random table, sketch size, options) are still
 // there -- the launcher then skips lut_kernel (one launch and one H2D copy less per call: what a
@@ -793,7 +675,7 @@ int stage_tables(const ppk_db *ref, const int32_t *kmers, const float *random_tb
   const size_t tab_bytes = C * C * ref->nk * sizeof(float);
   const bool use_tbl = (flags & PPK_FLAG_RANDOM_CORRECT) && random_tbl;
   void *base = nullptr;
-  int rc = scratch_get(ref->device, SLOT_LUT, lut_bytes + tab_bytes + 256, &base);
+  int rc = ppk_scratch_get(ref->device, SLOT_LUT, lut_bytes + tab_bytes + 256, &base);
   if (rc != PPK_OK) return rc;
   *d_lut = static_cast<double *>(base);
   float *t = reinterpret_cast<float *>(static_cast<char *>(base) + ((lut_bytes + 255) / 256) * 256);
@@ -803,46 +685,12 @@ int stage_tables(const ppk_db *ref, const int32_t *kmers, const float *random_tb
   uint64_t key = ppk_token(dims, sizeof(dims), 21);
   key = ppk_token(kmers, ref->nk * sizeof(int32_t), key);
   if (use_tbl) key = ppk_token(random_tbl, tab_bytes, key);
-  DevState &ds = g_dev[ref->device];
-  *lut_ready = ds.lut_key == key && ds.lut_ptr == base;
-  if (!*lut_ready) {
-    ds.lut_key = 0;        // nothing valid until the launcher has really built the tables (ppk_lut_commit)
-    tl_lut_pending_key = key;
-    tl_lut_pending_ptr = base;
-    if (use_tbl) PPK_HIP(hipMemcpyAsync(t, random_tbl, tab_bytes, hipMemcpyHostToDevice, s));
-  }
+  *lut_ready = ppk_lut_ready(ref->device, key, base);
+  if (!*lut_ready && use_tbl) PPK_HIP(hipMemcpyAsync(t, random_tbl, tab_bytes, hipMemcpyHostToDevice, s));
   return PPK_OK;
 }
 
 }  // namespace
-
-int ppk_scratch_get(int dev, int slot, size_t bytes, void **out) { return scratch_get(dev, slot, bytes, out); }
-
-int ppk_read_back(int dev, hipStream_t s, std::initializer_list<PpkCopy> copies, const unsigned long long **words) {
-  if (dev < 0 || dev >= 64) return ppk_fail(PPK_ERR_ARG, "device id " + std::to_string(dev) + " out of range [0, 64)");
-  if (tl_call.dev != dev) return ppk_fail(PPK_ERR_STATE, "internal: read-back requested outside a PpkCall scope");
-  size_t bytes = 0;
-  for (const PpkCopy &c : copies) bytes += (c.bytes + 7) & ~(size_t)7;
-  DevState &ds = g_dev[dev];
-  if (ds.pinned_bytes < align256(bytes)) {
-    if (ds.pinned) (void)hipHostFree(ds.pinned);
-    const size_t want = align256(bytes) + align256(bytes) / 4 + 4096;   // as the scratch slots grow
-    hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&ds.pinned), want, hipHostMallocDefault);
-    ds.pinned_bytes = e == hipSuccess ? want : 0;
-    if (e != hipSuccess) {
-      ds.pinned = nullptr;
-      return ppk_fail(PPK_ERR_HIP, std::string("hipHostMalloc(read-back): ") + hipGetErrorString(e));
-    }
-  }
-  char *at = reinterpret_cast<char *>(ds.pinned);
-  for (const PpkCopy &c : copies) {
-    PPK_HIP(hipMemcpyAsync(at, c.src, c.bytes, hipMemcpyDeviceToHost, s));
-    at += (c.bytes + 7) & ~(size_t)7;
-  }
-  PPK_HIP(hipStreamSynchronize(s));
-  *words = ds.pinned;
-  return PPK_OK;
-}
 
 bool ppk_read_edge(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off, size_t k,
                    long long *i, long long *j, long long *o) {
@@ -852,85 +700,12 @@ bool ppk_read_edge(const long long *d_i, const long long *d_j, size_t stride, co
          (!d_off || hipMemcpy(o, d_off + k, 8, hipMemcpyDeviceToHost) == hipSuccess);
 }
 
-bool ppk_lds_opt_in(const void *kernel, int dev, int bytes) {
-  if (dev < 0 || dev >= 64) return false;
-  std::lock_guard<std::recursive_mutex> lk(g_dev[dev].mu);
-  auto it = g_dev[dev].lds_opt_in.find(kernel);
-  if (it != g_dev[dev].lds_opt_in.end()) return it->second;
-  const bool ok = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
-  (void)hipGetLastError();
-  g_dev[dev].lds_opt_in[kernel] = ok;
-  return ok;
-}
-
-// lut_kernel has been enqueued for the tables stage_tables announced: they may be re-used
-void ppk_lut_commit(int dev, const void *d_lut) {
-  if (dev < 0 || dev >= 64 || tl_lut_pending_ptr != d_lut) return;
-  g_dev[dev].lut_key = tl_lut_pending_key;
-  g_dev[dev].lut_ptr = d_lut;
-}
-
-PpkCall::PpkCall(int dev, hipStream_t s) : dev_(dev), prev_dev_(tl_call.dev), prev_s_(tl_call.s), prev_touched_(tl_call.touched) {
-  if (dev_ < 0 || dev_ >= 64) {
-    dev_ = -1;
-    return;
-  }
-  g_dev[dev_].mu.lock();
-  tl_call.dev = dev_;
-  tl_call.s = s;
-  tl_call.touched = 0;
-}
-
-PpkCall::~PpkCall() {
-  if (dev_ < 0) return;
-  for (int k = 0; k < SLOT_COUNT; ++k) {
-    if (!(tl_call.touched & (1u << k))) continue;
-    Scratch &sc = g_dev[dev_].slot[k];
-    if (!sc.ev && hipEventCreateWithFlags(&sc.ev, hipEventDisableTiming) != hipSuccess) sc.ev = nullptr;
-    sc.recorded = sc.ev && hipEventRecord(sc.ev, tl_call.s) == hipSuccess;
-    sc.last = tl_call.s;
-  }
-  // an enclosing scope on the same device (a host wrapper calling a device entry point) has
-  // touched what its callee touched
-  const unsigned mine = tl_call.touched;
-  tl_call.dev = prev_dev_;
-  tl_call.s = prev_s_;
-  tl_call.touched = prev_touched_ | (prev_dev_ == dev_ ? mine : 0u);
-  g_dev[dev_].mu.unlock();
-}
-
-extern "C" int ppk_release_scratch(void) {
-  ppk_query_cache_clear();
-  ppk_parked_clear();
-  ppk_assign_bufs_release_all();
-  ppk_upload_rings_release();
-  for (int d = 0; d < 64; ++d) {
-    std::lock_guard<std::recursive_mutex> lk(g_dev[d].mu);
-    bool any = false;
-    for (int k = 0; k < SLOT_COUNT; ++k) any = any || g_dev[d].slot[k].p || g_dev[d].slot[k].ev;
-    if (!any) continue;
-    DeviceGuard guard(d);
-    (void)hipDeviceSynchronize();
-    for (int k = 0; k < SLOT_COUNT; ++k) {
-      if (g_dev[d].slot[k].p) (void)hipFree(g_dev[d].slot[k].p);
-      if (g_dev[d].slot[k].ev) (void)hipEventDestroy(g_dev[d].slot[k].ev);
-      g_dev[d].slot[k] = Scratch();
-    }
-    // a re-allocated block commonly comes back at the same address: without this the next call with the
-    // same k list and table would take the freed tables for valid (stage_tables) and skip lut_kernel
-    g_dev[d].lut_key = 0;
-    g_dev[d].lut_ptr = nullptr;
-  }
-  return PPK_OK;
-}
-
 // ---- one result matrix, N processes (ppk.h) -----------------------------------------------------------
 static_assert(sizeof(hipIpcMemHandle_t) == PPK_WINDOW_HANDLE_BYTES, "hipIpcMemHandle_t is not 64 bytes");
 
 extern "C" int ppk_window_alloc(int device, size_t bytes, void **d_window) {
   if (!d_window || bytes == 0) return ppk_fail(PPK_ERR_ARG, "window: no size / no output pointer");
-  DeviceGuard g(device);
-  if (!g.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device));
+  PPK_ENTER_DEVICE(g, device);
   // FINE-GRAINED device memory: peers store into it over xGMI while the owner's kernels read it later.  Those stores
   // arrive at the owner's memory side, not through its L2s; with a plain (coarse-grained) allocation a line of the
   // window that an earlier kernel of the owner left in one of its eight L2s could be served stale afterwards -- only
@@ -950,8 +725,7 @@ extern "C" int ppk_window_alloc(int device, size_t bytes, void **d_window) {
 
 extern "C" int ppk_window_free(int device, void *d_window) {
   if (!d_window) return PPK_OK;
-  DeviceGuard g(device);
-  if (!g.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device));
+  PPK_ENTER_DEVICE(g, device);
   (void)hipDeviceSynchronize();
   PPK_HIP(hipFree(d_window));
   return PPK_OK;
@@ -959,8 +733,7 @@ extern "C" int ppk_window_free(int device, void *d_window) {
 
 extern "C" int ppk_window_export(int device, const void *d_window, unsigned char handle[PPK_WINDOW_HANDLE_BYTES]) {
   if (!d_window || !handle) return ppk_fail(PPK_ERR_ARG, "window: null argument");
-  DeviceGuard g(device);
-  if (!g.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device));
+  PPK_ENTER_DEVICE(g, device);
   hipIpcMemHandle_t h;
   hipError_t e = hipIpcGetMemHandle(&h, const_cast<void *>(d_window));
   if (e != hipSuccess) {
@@ -973,8 +746,7 @@ extern "C" int ppk_window_export(int device, const void *d_window, unsigned char
 
 extern "C" int ppk_window_open(int device, const unsigned char handle[PPK_WINDOW_HANDLE_BYTES], void **d_window) {
   if (!d_window || !handle) return ppk_fail(PPK_ERR_ARG, "window: null argument");
-  DeviceGuard g(device);
-  if (!g.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device));
+  PPK_ENTER_DEVICE(g, device);
   hipIpcMemHandle_t h;
   memcpy(&h, handle, sizeof(h));
   void *p = nullptr;
@@ -989,8 +761,7 @@ extern "C" int ppk_window_open(int device, const unsigned char handle[PPK_WINDOW
 
 extern "C" int ppk_window_close(int device, void *d_window) {
   if (!d_window) return PPK_OK;
-  DeviceGuard g(device);
-  if (!g.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device));
+  PPK_ENTER_DEVICE(g, device);
   (void)hipDeviceSynchronize();
   hipError_t e = hipIpcCloseMemHandle(d_window);
   if (e != hipSuccess) {
@@ -1034,8 +805,7 @@ extern "C" int ppk_dist_pairs_dev(const ppk_db *ref, const ppk_db *qry, const in
   if (n_pairs == 0) return PPK_OK;
   if (!d_i || !d_j || !d_out) return ppk_fail(PPK_ERR_ARG, "ppk_dist_pairs: NULL array");
   if (n_pairs >= ((size_t)1 << 40)) return ppk_fail(PPK_ERR_ARG, "ppk_dist_pairs: n_pairs must be < 2^40");
-  DeviceGuard guard(ref->device);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(ref->device));
+  PPK_ENTER_DEVICE(guard, ref->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   PpkCall call(ref->device, s);
   PairsJob job;
@@ -1113,7 +883,7 @@ static int dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *k
         return ppk_fail(PPK_ERR_ARG, "edge lists of a band need bbits = 14 or nk * count bits <= 128");
       const size_t rows = ppk_rows_in_band(ref->n, qry ? qry->n : 0, 0, nq);
       void *d_dist = nullptr;
-      rc = scratch_get(ref->device, SLOT_ITER_B, rows * 8 + 8, &d_dist);
+      rc = ppk_scratch_get(ref->device, SLOT_ITER_B, rows * 8 + 8, &d_dist);
       if (rc != PPK_OK) return rc;
       job.q_begin = 0, job.q_end = nq, job.d_out = d_dist;
       rc = ppk_launch_dist(job);
@@ -1128,9 +898,9 @@ static int dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *k
   const size_t n_rtiles = (ref->n + 63) / 64;
   const size_t n_words = (q_end - q_begin) * n_rtiles;
   void *d_mask = nullptr, *d_ws = nullptr;
-  rc = scratch_get(ref->device, SLOT_MASK, n_words * sizeof(uint64_t), &d_mask);
+  rc = ppk_scratch_get(ref->device, SLOT_MASK, n_words * sizeof(uint64_t), &d_mask);
   if (rc != PPK_OK) return rc;
-  rc = scratch_get(ref->device, SLOT_WS, ppk_compact_ws_bytes(n_words), &d_ws);
+  rc = ppk_scratch_get(ref->device, SLOT_WS, ppk_compact_ws_bytes(n_words), &d_ws);
   if (rc != PPK_OK) return rc;
   const ppk_bgmm *d_model = nullptr;
   if (model && (rc = ppk_bgmm_to_device(ref->device, *model, &d_model, s)) != PPK_OK) return rc;
@@ -1202,34 +972,12 @@ __global__ void publish_word_kernel(const unsigned long long *__restrict__ src, 
   __hip_atomic_store(&dst->ticket, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 int read_device_word(int dev, const unsigned long long *d_word, unsigned long long *out, hipStream_t s) {
-  static PinnedWord *blocks[64] = {};
-  static unsigned long long tickets[64] = {};
-  PinnedWord *&b = blocks[dev & 63];      // (the caller holds the device's PpkCall)
-  if (!b) {
-    if (hipHostMalloc(reinterpret_cast<void **>(&b), 256, hipHostMallocCoherent) != hipSuccess) {
-      b = nullptr;
-      return ppk_fail(PPK_ERR_HIP, "hipHostMalloc failed");
-    }
-    memset(b, 0, 256);
-  }
-  const unsigned long long ticket = ++tickets[dev & 63];
+  PinnedWord *b = static_cast<PinnedWord *>(ppk_ticket_block(dev, PPK_TICKET_KNN_COUNT));
+  if (!b) return ppk_fail(PPK_ERR_HIP, "hipHostMalloc failed");
+  const unsigned long long ticket = ppk_next_ticket(dev);
   hipLaunchKernelGGL(publish_word_kernel, dim3(1), dim3(1), 0, s, d_word, b, ticket);
   PPK_HIP(hipGetLastError());
-  const volatile unsigned long long *word = &b->ticket;
-  const auto t0 = std::chrono::steady_clock::now();
-  for (unsigned spin = 0;; ++spin) {
-    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == ticket) {
-      *out = b->value;
-      return PPK_OK;
-    }
-    if ((spin & 1023u) == 1023u) {
-      if (hipStreamQuery(s) != hipErrorNotReady) break;      // done, or failed: let the drain say which
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
-    }
-    __builtin_ia32_pause();
-  }
-  PPK_HIP(hipStreamSynchronize(s));
-  if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != ticket) return ppk_fail(PPK_ERR_HIP, "the count did not arrive");
+  if (int rc = ppk_wait_ticket(s, &b->ticket, ticket, 5000, "the count did not arrive")) return rc;
   *out = b->value;
   return PPK_OK;
 }
@@ -1256,7 +1004,7 @@ int ppk_knn_band_dev(const ppk_db *db, const ppk_db *qry, const int32_t *kmers, 
   rc = stage_tables(db, kmers, random_tbl, n_clu, flags, s, &d_lut, &d_rtab, &lut_ready);
   if (rc != PPK_OK) return rc;
   void *d_state = nullptr;
-  rc = scratch_get(db->device, SLOT_ITER_A, 3 * sizeof(unsigned long long) + n * 4 + 256, &d_state);
+  rc = ppk_scratch_get(db->device, SLOT_ITER_A, 3 * sizeof(unsigned long long) + n * 4 + 256, &d_state);
   if (rc != PPK_OK) return rc;
   const size_t all = qry ? 2 * db->n * qry->n : n * (n - 1);       // two candidates per pair at most
   // Measured (k = 5): ~200 / 530 / 1 000 candidates per sample at 10k / 50k / 100k samples.  A bound is the
@@ -1290,7 +1038,7 @@ int ppk_knn_band_dev(const ppk_db *db, const ppk_db *qry, const int32_t *kmers, 
   size_t vals_off = 0;
   auto room = [&](size_t entries) {        // (re)allocates the list for `entries`; only while it is empty
     vals_off = (entries * 4 + 255) & ~(size_t)255;
-    return scratch_get(db->device, SLOT_ITER_B, vals_off + entries * 8 + 256, &d_cand);
+    return ppk_scratch_get(db->device, SLOT_ITER_B, vals_off + entries * 8 + 256, &d_cand);
   };
   rc = room(cap);
   if (rc != PPK_OK) return rc;
@@ -1468,7 +1216,7 @@ extern "C" int ppk_knn_candidates_dev(const ppk_db *db, const int32_t *kmers, co
   rc = stage_tables(db, kmers, random_tbl, n_clu, flags, s, &d_lut, &d_rtab, &lut_ready);
   if (rc != PPK_OK) return rc;
   void *d_state = nullptr;
-  rc = scratch_get(db->device, SLOT_ITER_A, 3 * sizeof(unsigned long long) + n * 4 + 256, &d_state);
+  rc = ppk_scratch_get(db->device, SLOT_ITER_A, 3 * sizeof(unsigned long long) + n * 4 + 256, &d_state);
   if (rc != PPK_OK) return rc;
   // the kernel addresses the value array relative to the key array (modulo 2^64)
   const unsigned long long vals_off = (unsigned long long)(reinterpret_cast<char *>(d_vals) - reinterpret_cast<char *>(d_keys));

@@ -188,12 +188,12 @@ extern "C" int ppk_bgmm_prepare(int K, const double *weights, const double *mean
 // in) at a time, each chunk uploaded, assigned and fetched in turn on the device's default stream.
 extern "C" int ppk_bgmm_assign(const float *dist, size_t n_rows, const ppk_bgmm *model, int device_id, int32_t *labels,
                                float *resp) {
+  if (int rc = ppk_check_device(device_id)) return rc;
   if (!model) return ppk_fail(PPK_ERR_ARG, "ppk_bgmm_assign: model is NULL");
   if (model->K < 1 || model->K > PPK_BGMM_MAX_K || model->within_label < 0 || model->within_label >= model->K)
     return ppk_fail(PPK_ERR_ARG, "ppk_bgmm_assign: the model is not prepared (ppk_bgmm_prepare)");
   if (n_rows == 0) return PPK_OK;
   if (!dist || (!labels && !resp)) return ppk_fail(PPK_ERR_ARG, "ppk_bgmm_assign: NULL input / no output");
-  if (device_id < 0 || device_id >= 64) return ppk_fail(PPK_ERR_ARG, "device id out of range");
   if (int rc = ppk_check_arch(device_id)) return rc;
   const size_t chunk = (size_t)8 << 20;
   const size_t buf_rows = n_rows < chunk ? n_rows : chunk;

@@ -632,6 +632,7 @@ extern "C" int ppk_bgmm_fit_dev(const float *d_rows, size_t n_rows, const long l
 extern "C" int ppk_bgmm_fit(const float *rows, size_t n_rows, const long long *index, size_t n_index, const float *scale,
                             const int32_t *init_labels, const double *init_centres, const ppk_bgmm_fit_params *params,
                             int device_id, ppk_bgmm_fit_result *result) {
+  if (int rc = ppk_check_device(device_id)) return rc;
   if (int rc = check_params(params, "ppk_bgmm_fit")) return rc;
   if (!rows || !scale || !result) return ppk_fail(PPK_ERR_ARG, "ppk_bgmm_fit: NULL rows / scale / result");
   const size_t n = index ? n_index : n_rows;
@@ -657,7 +658,6 @@ extern "C" int ppk_bgmm_fit(const float *rows, size_t n_rows, const long long *i
       return ppk_fail(PPK_ERR_ARG, "ppk_bgmm_fit: the label of training row " + std::to_string(i) + " is outside [0, " +
                                        std::to_string(params->K) + ")");
   }
-  if (device_id < 0 || device_id >= 64) return ppk_fail(PPK_ERR_ARG, "device id out of range");
   if (int rc = ppk_check_arch(device_id)) return rc;
   // the training rows go up gathered, in the order of the index list: the device then sees what ppk_bgmm_fit_dev
   // sees through the list, and the sums are the same bits

@@ -680,7 +680,6 @@ extern "C" int ppk_dbscan_fit(const float *pts, size_t n, int min_samples, int d
                               int32_t *b, double *mr2) {
   if (!pts || !core2 || (n > 1 && (!a || !b || !mr2))) return ppk_fail(PPK_ERR_ARG, "ppk_dbscan_fit: NULL array");
   if (n > (size_t)0x7fffffff) return ppk_fail(PPK_ERR_ARG, "ppk_dbscan_fit: n must be < 2^31");
-  if (device_id < 0 || device_id >= 64) return ppk_fail(PPK_ERR_ARG, "device id out of range");
   if (int rc = ppk_check_arch(device_id)) return rc;
   float *d_pts;
   double *d_core2, *d_mr2;
@@ -705,6 +704,7 @@ extern "C" int ppk_dbscan_create(const float *pts, const double *core2, size_t n
                                  const int32_t *pt_cluster, const double *pt_lambda, const int32_t *cl_parent,
                                  const double *cl_birth, const int32_t *cl_label, size_t n_cl, const double *scale,
                                  int scale_is_f64, int within_label, int device_id, ppk_dbscan **out) {
+  if (int rc = ppk_check_device(device_id)) return rc;
   if (!pts || !core2 || !pt_cluster || !pt_lambda || !cl_parent || !cl_birth || !cl_label || !scale || !out)
     return ppk_fail(PPK_ERR_ARG, "ppk_dbscan_create: NULL argument");
   if (n < 1 || n > (size_t)0x7fffffff) return ppk_fail(PPK_ERR_ARG, "ppk_dbscan_create: n must be in [1, 2^31)");
@@ -720,10 +720,8 @@ extern "C" int ppk_dbscan_create(const float *pts, const double *core2, size_t n
   for (size_t p = 0; p < n; ++p)
     if (pt_cluster[p] < 0 || (size_t)pt_cluster[p] >= n_cl)
       return ppk_fail(PPK_ERR_ARG, "ppk_dbscan_create: point " + std::to_string(p) + " is in no cluster");
-  if (device_id < 0 || device_id >= 64) return ppk_fail(PPK_ERR_ARG, "device id out of range");
   if (int rc = ppk_check_arch(device_id)) return rc;
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
+  PPK_ENTER_DEVICE(guard, device_id);
   ppk_dbscan *m = new ppk_dbscan();
   m->device = device_id;
   m->n = n;
@@ -838,8 +836,7 @@ extern "C" void ppk_dbscan_destroy(ppk_dbscan *m) {
 extern "C" int ppk_dbscan_stats(const ppk_dbscan *model, unsigned long long *rows_scanned) {
   if (int rc = check_model(model, "ppk_dbscan_stats")) return rc;
   if (!rows_scanned) return ppk_fail(PPK_ERR_ARG, "ppk_dbscan_stats: NULL argument");
-  DeviceGuard guard(model->device);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(model->device));
+  PPK_ENTER_DEVICE(guard, model->device);
   PPK_HIP(hipDeviceSynchronize());
   PPK_HIP(hipMemcpy(rows_scanned, model->d_full, 8, hipMemcpyDeviceToHost));
   return PPK_OK;

@@ -406,6 +406,7 @@ extern "C" int ppk_density_kde_dev(const float *d_dist, size_t n_rows, const lon
 extern "C" int ppk_density_kde(const float *dist, size_t n_rows, const long long *idx, size_t n_idx, const float *scale,
                                const double *gx, size_t nx, const double *gy, size_t ny, double h, int shift,
                                int device_id, long long *sum, float *scale_used) {
+  if (int rc = ppk_check_device(device_id)) return rc;
   const std::string who = kWhoKde;
   const size_t n_read = idx ? n_idx : n_rows;
   // the grid before SLOT_HOST_IN is sized from it (the device call checks again, against the LDS it really gets)

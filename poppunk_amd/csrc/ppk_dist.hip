@@ -1956,18 +1956,10 @@ bool ppk_self_job_takes_tiles(const ppk_db *db) {
 
 // ---- device geometry -----------------------------------------------------------------------------------------------
 // Nothing below assumes a part: the compute units, the XCD count and the number of pair-tile workgroups the device
-// holds at once are read here, once per device.  (MI355X in SPX mode: 256 CUs, 8 XCDs, 2 workgroups of the tile
-// kernel per CU = 512 slots; in CPX mode one partition shows 32 CUs, 1 XCD, 64 slots.)
-const PpkGeometry &ppk_geometry(int dev) {
-  static PpkGeometry cache[64];
-  static std::atomic<int> ready[64];
-  static std::mutex mu;
-  static const PpkGeometry fallback = {256, 3, 512};
-  if (dev < 0 || dev >= 64) return fallback;
-  if (ready[dev].load(std::memory_order_acquire)) return cache[dev];
-  std::lock_guard<std::mutex> lk(mu);
-  if (ready[dev].load(std::memory_order_relaxed)) return cache[dev];
-  PpkGeometry g = fallback;
+// holds at once are read here, once per device (ppk_geometry keeps the answer).  (MI355X in SPX mode: 256 CUs, 8 XCDs,
+// 2 workgroups of the tile kernel per CU = 512 slots; in CPX mode one partition shows 32 CUs, 1 XCD, 64 slots.)
+PpkGeometry ppk_measure_geometry(int dev) {
+  PpkGeometry g = {256, 3, 512};      // (what a whole MI355X shows, for whatever cannot be read)
   int v = 0;
   if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) g.cus = v;
   unsigned shift = 0;
@@ -1985,9 +1977,7 @@ const PpkGeometry &ppk_geometry(int dev) {
     g.tile_slots = per_cu * g.cus;
   else
     g.tile_slots = 2 * g.cus;
-  cache[dev] = g;
-  ready[dev].store(1, std::memory_order_release);
-  return cache[dev];
+  return g;
 }
 
 // ---- the route of one band --------------------------------------------------------------------------------------------

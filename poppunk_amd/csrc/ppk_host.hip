@@ -3,6 +3,7 @@
 // thread per listed device, sub-band pipeline, resident-database cache), the host forms of kernel 2 and the
 // hand-over of results of data-dependent size.  Device entry points and per-device scratch: ppk_api.hip.
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -88,32 +89,29 @@ void ppk_pool_wait(const PpkTicket &t) {
 namespace {
 struct UploadRing {
   std::mutex mu;                       // one upload at a time per device
-  void *slot[2] = {nullptr, nullptr};
+  PpkPinnedBuf slot[2];
   hipEvent_t freed[2] = {nullptr, nullptr};
   bool used[2] = {false, false};
 };
-UploadRing g_ring[64];
+PpkPerDevice<UploadRing> g_ring;
 constexpr size_t kUploadPiece = (size_t)32 << 20;
-}  // namespace
 
-void ppk_upload_rings_release() {
-  for (int d = 0; d < 64; ++d) {
-    UploadRing &r = g_ring[d];
-    std::lock_guard<std::mutex> lk(r.mu);
-    for (int i = 0; i < 2; ++i) {
-      if (r.used[i] && r.freed[i]) (void)hipEventSynchronize(r.freed[i]);
-      if (r.slot[i]) (void)hipHostFree(r.slot[i]);
-      if (r.freed[i]) (void)hipEventDestroy(r.freed[i]);
-      r.slot[i] = nullptr;
-      r.freed[i] = nullptr;
-      r.used[i] = false;
-    }
+void upload_ring_release(PpkDeviceVisit &visit) {
+  UploadRing &r = g_ring.at(visit.dev);
+  std::lock_guard<std::mutex> lk(r.mu);
+  for (int i = 0; i < 2; ++i) {
+    if (!r.slot[i].p && !r.freed[i]) continue;
+    visit.enter();
+    r.slot[i].release();
+    ppk_event_release(&r.freed[i]);
+    r.used[i] = false;
   }
 }
+}  // namespace
 
 int ppk_upload(int device, void *d_dst, const void *h_src, size_t bytes, hipStream_t s) {
   if (bytes == 0) return PPK_OK;
-  if (device < 0 || device >= 64) return ppk_fail(PPK_ERR_ARG, "device id out of range");
+  if (int rc = ppk_check_device(device)) return rc;
   int nt = (int)ppk_config().prefault_threads.load();
   if (bytes < ((size_t)256 << 10) || nt < 1) {      // small: the runtime's own (staged) path
     PPK_HIP(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, s));
@@ -124,15 +122,14 @@ int ppk_upload(int device, void *d_dst, const void *h_src, size_t bytes, hipStre
   // it and restores them off a timer -- the next kernel starts 10 - 25 ms late: DESIGN.md 3.6, tools/ab_pinning.py)
   if (bytes < ((size_t)4 << 20)) nt = 1;
   if (nt > 16) nt = 16;
-  UploadRing &r = g_ring[device];
+  UploadRing &r = g_ring.at(device);
   std::lock_guard<std::mutex> lk(r.mu);
   for (int i = 0; i < 2; ++i) {
-    if (!r.slot[i] && hipHostMalloc(&r.slot[i], kUploadPiece, hipHostMallocDefault) != hipSuccess) {
-      r.slot[i] = nullptr;
+    if (r.slot[i].grow(kUploadPiece) != hipSuccess) {
       PPK_HIP(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, s));      // no pinned memory: the plain path
       return PPK_OK;
     }
-    if (!r.freed[i]) PPK_HIP(hipEventCreateWithFlags(&r.freed[i], hipEventDisableTiming));
+    PPK_HIP(ppk_event_get(&r.freed[i]));
   }
   const char *src = static_cast<const char *>(h_src);
   char *dst = static_cast<char *>(d_dst);
@@ -140,7 +137,7 @@ int ppk_upload(int device, void *d_dst, const void *h_src, size_t bytes, hipStre
   for (size_t off = 0; off < bytes; off += kUploadPiece, i ^= 1) {
     const size_t len = bytes - off < kUploadPiece ? bytes - off : kUploadPiece;
     if (r.used[i]) PPK_HIP(hipEventSynchronize(r.freed[i]));      // the DMA that last read this slot is done
-    char *stage = static_cast<char *>(r.slot[i]);
+    char *stage = static_cast<char *>(r.slot[i].p);
     const size_t per = (len + (size_t)nt - 1) / (size_t)nt;
     std::vector<PpkTicket> th;
     auto copy = [&](int t) {
@@ -177,26 +174,39 @@ static void progress_line(double frac, bool last) {
 
 
 // ---- per-device worker streams of the host-buffer entry points -------------------------
-// hipStreamCreate + hipStreamDestroy cost ~0.4 ms each on this stack: three quarters of a
+// Creating and destroying a stream cost ~0.4 ms each on this stack: three quarters of a
 // 1 000-genome ppk_query call.  The host-buffer entry points therefore take their (up to three)
-// streams from a per-device cache that lives as long as the process.  Calls from several host
-// threads share them: their work is ordered on the streams, which is correct (each call
-// synchronises its streams before it returns) if not concurrent.
+// streams from a cache that lives as long as the process, keyed by device and set: sets 0 .. kMaxDup - 1 are
+// the occurrences of the device in a query's device list, kAssignSet is ppk_assign_threshold's (a query and
+// an assign may run side by side: they must not share streams).
 namespace {
-int worker_streams(int device, hipStream_t *out, int n) {
-  static std::mutex mu;
-  static std::vector<std::vector<hipStream_t>> cache;
-  std::lock_guard<std::mutex> lk(mu);
-  if (device < 0 || n < 1 || n > 3) return ppk_fail(PPK_ERR_ARG, "bad worker stream request");
-  if ((size_t)device >= cache.size()) cache.resize((size_t)device + 1);
-  std::vector<hipStream_t> &v = cache[(size_t)device];
-  while ((int)v.size() < n) {
-    hipStream_t s = nullptr;
-    if (hipStreamCreate(&s) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipStreamCreate failed");
-    v.push_back(s);
+constexpr int kMaxDup = 4;       // a device may be listed up to kMaxDup times in one ppk_query call
+constexpr int kMaxParts = 64;    // entries of one device list
+constexpr int kAssignSet = kMaxDup, kStreamSets = kMaxDup + 1, kSetStreams = 3;
+struct StreamSets {
+  hipStream_t s[kStreamSets][kSetStreams] = {};
+};
+PpkPerDevice<StreamSets> g_streams;
+
+// The first n streams of a set, on the current device.  No lock: each set has one owner at a time -- a part's set is
+// asked for by that part's one worker (under g_query_mu), the assign set under AssignBufs::mu --, so that the
+// entries of a first call create their streams side by side (4 ms each on this stack).
+int worker_streams(int device, int set, hipStream_t *out, int n) {
+  if (set < 0 || set >= kStreamSets || n < 1 || n > kSetStreams) return ppk_fail(PPK_ERR_ARG, "bad worker stream request");
+  hipStream_t *cache = g_streams.at(device).s[set];
+  for (int i = 0; i < n; ++i) {
+    if (!cache[i] && hipStreamCreate(&cache[i]) != hipSuccess) {
+      cache[i] = nullptr;
+      return ppk_fail(PPK_ERR_HIP, "hipStreamCreate failed");
+    }
+    out[i] = cache[i];
   }
-  for (int i = 0; i < n; ++i) out[i] = v[(size_t)i];
   return PPK_OK;
+}
+// a part's worker has selected its device: the two streams of its (device, occurrence) set
+int part_streams(const DeviceGuard &g, int device, int dup, hipStream_t *out) {
+  if (!g.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device));
+  return worker_streams(device, dup, out, 2);
 }
 }  // namespace
 
@@ -211,46 +221,27 @@ namespace {
 std::mutex g_query_mu;           // one host-buffer query at a time (PopPUNK calls blocking, from one thread)
 
 struct QueryBufs {
-  void *buf[2] = {nullptr, nullptr};
-  size_t bytes[2] = {0, 0};
-  unsigned long long *d_failed = nullptr;
-  unsigned long long *d_cnt2 = nullptr;      // {edges, failed fits} of the fused edge-list calls
+  PpkDeviceBuf buf[2], failed, cnt2;      // the failed-fit counter; {edges, failed fits} of the fused edge-list calls
   hipEvent_t done[2] = {nullptr, nullptr};
 };
-constexpr int kMaxDup = 4;       // a device may be listed up to kMaxDup times in one ppk_query call
-QueryBufs g_qbufs[64][kMaxDup];  // [device][occurrence in the device list]; one worker owns each
+// [device][occurrence in the device list]; one worker owns each (under g_query_mu)
+PpkPerDevice<std::array<QueryBufs, kMaxDup>> g_qbufs;
 
-int query_buf(int dev, int dup, int i, size_t bytes, void **out) {
-  QueryBufs &q = g_qbufs[dev][dup];
-  if (q.bytes[i] < bytes) {
-    if (q.buf[i]) {
-      (void)hipDeviceSynchronize();
-      (void)hipFree(q.buf[i]);
-      q.buf[i] = nullptr;
-      q.bytes[i] = 0;
-    }
-    hipError_t e = hipMalloc(&q.buf[i], bytes);
-    if (e != hipSuccess) return ppk_fail(PPK_ERR_HIP, std::string("hipMalloc(output): ") + hipGetErrorString(e));
-    q.bytes[i] = bytes;
-  }
-  *out = q.buf[i];
+int query_buf(QueryBufs &q, int i, size_t bytes, void **out) {
+  hipError_t e = q.buf[i].grow(bytes);
+  if (e != hipSuccess) return ppk_fail(PPK_ERR_HIP, std::string("hipMalloc(output): ") + hipGetErrorString(e));
+  *out = q.buf[i].p;
   return PPK_OK;
 }
 
-// worker streams per (device, occurrence): two entries naming one device run on their own streams
-int part_streams(int device, int dup, hipStream_t *out) {
-  // (each (device, occurrence) pair is only ever asked for by one thread at a time: no lock around the creation,
-  // so that the entries of a first call create their streams side by side -- 4 ms each on this stack)
-  static hipStream_t cache[64][kMaxDup][2];
-  if (device < 0 || device >= 64 || dup < 0 || dup >= kMaxDup) return ppk_fail(PPK_ERR_ARG, "bad worker stream request");
-  for (int i = 0; i < 2; ++i) {
-    if (!cache[device][dup][i] && hipStreamCreate(&cache[device][dup][i]) != hipSuccess) {
-      cache[device][dup][i] = nullptr;
-      return ppk_fail(PPK_ERR_HIP, "hipStreamCreate failed");
-    }
-    out[i] = cache[device][dup][i];
+void query_bufs_release(PpkDeviceVisit &visit) {
+  std::lock_guard<std::mutex> lk(g_query_mu);
+  for (QueryBufs &q : g_qbufs.at(visit.dev)) {
+    if (!q.buf[0].p && !q.buf[1].p && !q.failed.p && !q.cnt2.p && !q.done[0] && !q.done[1]) continue;
+    visit.enter();
+    for (PpkDeviceBuf *b : {&q.buf[0], &q.buf[1], &q.failed, &q.cnt2}) b->release();
+    for (hipEvent_t &e : q.done) ppk_event_release(&e);
   }
-  return PPK_OK;
 }
 
 // ---- resident databases of earlier ppk_query calls ------------------------------------------------
@@ -528,21 +519,14 @@ void run_part(QueryJob &job, std::vector<QueryPart> &parts, int d, bool poll, bo
     job.stop.store(1);
   };
   DeviceGuard g(p.device);
-  if (!g.ok) {
-    ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(p.device));
+  hipStream_t ws[2] = {nullptr, nullptr};
+  int rc = part_streams(g, p.device, p.dup, ws);
+  if (rc != PPK_OK) {
     p.db_ready.store(-1);
-    return fail(PPK_ERR_HIP);
+    return fail(rc);
   }
-  int rc = PPK_OK;
-  {
-    hipStream_t ws[2] = {nullptr, nullptr};
-    if ((rc = part_streams(p.device, p.dup, ws)) != PPK_OK) {
-      p.db_ready.store(-1);
-      return fail(rc);
-    }
-    p.s = ws[0];
-    p.sc = ws[1];
-  }
+  p.s = ws[0];
+  p.sc = ws[1];
   g_trace.mark(d, "device_set");
   // 1. resident databases
   if (job.ref_sk) {
@@ -582,18 +566,16 @@ void run_part(QueryJob &job, std::vector<QueryPart> &parts, int d, bool poll, bo
   QueryJob::DevWork &w = job.work[(size_t)p.work];
   if (w.c_end == w.c_begin) return;                                 // no work for this device
   // 2. buffers
-  QueryBufs &qb = g_qbufs[p.device][p.dup];
+  QueryBufs &qb = g_qbufs.at(p.device)[p.dup];
   const size_t buf_bytes = job.max_rows * job.cols * 4;
-  rc = query_buf(p.device, p.dup, 0, buf_bytes, &p.buf[0]);
-  if (rc == PPK_OK && w.c_end - w.c_begin > 1) rc = query_buf(p.device, p.dup, 1, buf_bytes, &p.buf[1]);
-  if (rc == PPK_OK && !qb.d_failed &&
-      hipMalloc(reinterpret_cast<void **>(&qb.d_failed), sizeof(unsigned long long)) != hipSuccess)
+  rc = query_buf(qb, 0, buf_bytes, &p.buf[0]);
+  if (rc == PPK_OK && w.c_end - w.c_begin > 1) rc = query_buf(qb, 1, buf_bytes, &p.buf[1]);
+  if (rc == PPK_OK && qb.failed.grow(sizeof(unsigned long long)) != hipSuccess)
     rc = ppk_fail(PPK_ERR_HIP, "hipMalloc(output) failed");
   for (int i = 0; i < 2 && rc == PPK_OK; ++i)
-    if (!qb.done[i] && hipEventCreateWithFlags(&qb.done[i], hipEventDisableTiming) != hipSuccess)
-      rc = ppk_fail(PPK_ERR_HIP, "hipEventCreate failed");
+    if (ppk_event_get(&qb.done[i]) != hipSuccess) rc = ppk_fail(PPK_ERR_HIP, "hipEventCreate failed");
   if (rc != PPK_OK) return fail(rc);
-  p.d_failed = qb.d_failed;
+  p.d_failed = static_cast<unsigned long long *>(qb.failed.p);
   p.done[0] = qb.done[0];
   p.done[1] = qb.done[1];
   (void)hipMemsetAsync(p.d_failed, 0, sizeof(unsigned long long), p.s);
@@ -862,7 +844,7 @@ int prepare_parts(std::vector<QueryPart> &parts, const int *devices) {
   for (size_t d = 0; d < parts.size(); ++d) {
     QueryPart &p = parts[d];
     p.device = devices[d];
-    if (p.device < 0 || p.device >= 64) return ppk_fail(PPK_ERR_ARG, "device id out of range");
+    if (int rc = ppk_check_device(p.device)) return rc;
     for (size_t e = 0; e < d; ++e)
       if (devices[e] == p.device) {
         ++p.dup;
@@ -878,27 +860,19 @@ int prepare_parts(std::vector<QueryPart> &parts, const int *devices) {
 }
 }  // namespace
 
-void ppk_query_cache_clear() {
+void ppk_db_cache_clear() {
   std::lock_guard<std::mutex> lk(g_query_mu);
-  {
-    std::lock_guard<std::mutex> lc(g_cache_mu);
-    for (CachedDb &c : g_db_cache) ppk_db_destroy(c.db);
-    g_db_cache.clear();
-  }
-  for (int d = 0; d < 64; ++d)
-    for (int u = 0; u < kMaxDup; ++u) {
-      QueryBufs &q = g_qbufs[d][u];
-      if (!q.buf[0] && !q.buf[1] && !q.d_failed && !q.d_cnt2 && !q.done[0] && !q.done[1]) continue;
-      DeviceGuard guard(d);
-      (void)hipDeviceSynchronize();
-      for (int i = 0; i < 2; ++i) {
-        if (q.buf[i]) (void)hipFree(q.buf[i]);
-        if (q.done[i]) (void)hipEventDestroy(q.done[i]);
-      }
-      if (q.d_failed) (void)hipFree(q.d_failed);
-      if (q.d_cnt2) (void)hipFree(q.d_cnt2);
-      q = QueryBufs();
-    }
+  std::lock_guard<std::mutex> lc(g_cache_mu);
+  for (CachedDb &c : g_db_cache) ppk_db_destroy(c.db);
+  g_db_cache.clear();
+}
+
+void ppk_query_cache_clear() {
+  ppk_db_cache_clear();
+  g_qbufs.each([](int d, std::array<QueryBufs, kMaxDup> &) {
+    PpkDeviceVisit visit(d);
+    query_bufs_release(visit);
+  });
 }
 
 extern "C" int ppk_query(const uint64_t *ref_sk, size_t n_ref, const uint64_t *qry_sk, size_t n_qry,
@@ -1009,7 +983,7 @@ extern "C" int ppk_query_dbs(const ppk_db *const *refs, const ppk_db *const *qry
                              const int32_t *kmers, const float *random_tbl, size_t n_clu, int flags,
                              void *out, unsigned long long *n_failed) {
   if (n_failed) *n_failed = 0;
-  if (!refs || n_dev < 1 || n_dev > 64) return ppk_fail(PPK_ERR_ARG, "ppk_query_dbs: no databases");
+  if (!refs || n_dev < 1 || n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, "ppk_query_dbs: no databases");
   if (!out) return ppk_fail(PPK_ERR_ARG, "ppk_query_dbs: out is NULL");
   std::vector<int> devices((size_t)n_dev);
   for (int d = 0; d < n_dev; ++d) {
@@ -1082,40 +1056,36 @@ extern "C" int ppk_query_last_stats(double *vals, int n) {
 namespace {
 struct AssignBufs {
   std::mutex mu;                 // one host assign at a time per device
-  float *d_in[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
-  size_t rows = 0;
+  PpkDeviceBuf d_in[2], d_out[2];
   hipEvent_t up[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}, freed_in[2] = {nullptr, nullptr};
-};
-AssignBufs g_assign[64];
-void assign_bufs_release(int d) {
-  AssignBufs &a = g_assign[d];
-  std::lock_guard<std::mutex> lk(a.mu);
-  if (!a.d_in[0] && !a.up[0]) return;
-  DeviceGuard guard(d);
-  (void)hipDeviceSynchronize();
-  for (int i = 0; i < 2; ++i) {
-    if (a.d_in[i]) (void)hipFree(a.d_in[i]);
-    if (a.d_out[i]) (void)hipFree(a.d_out[i]);
-    if (a.up[i]) (void)hipEventDestroy(a.up[i]);
-    if (a.done[i]) (void)hipEventDestroy(a.done[i]);
-    if (a.freed_in[i]) (void)hipEventDestroy(a.freed_in[i]);
-    a.d_in[i] = a.d_out[i] = nullptr;
-    a.up[i] = a.done[i] = a.freed_in[i] = nullptr;
+  void release() {
+    for (int i = 0; i < 2; ++i) {
+      d_in[i].release();
+      d_out[i].release();
+      ppk_event_release(&up[i]);
+      ppk_event_release(&done[i]);
+      ppk_event_release(&freed_in[i]);
+    }
   }
-  a.rows = 0;
-}
+};
+PpkPerDevice<AssignBufs> g_assign;
 }  // namespace
-void ppk_assign_bufs_release_all() {
-  for (int d = 0; d < 64; ++d) assign_bufs_release(d);
+
+void ppk_host_bufs_release(PpkDeviceVisit &visit) {
+  query_bufs_release(visit);
+  upload_ring_release(visit);
+  AssignBufs &a = g_assign.at(visit.dev);
+  std::lock_guard<std::mutex> lk(a.mu);
+  if (!a.d_in[0].p && !a.up[0]) return;
+  visit.enter();
+  a.release();
 }
 
 extern "C" int ppk_assign_threshold(const float *dist, size_t n_rows, int slope, float x_max,
                                     float y_max, int device_id, float *out) {
   if (n_rows == 0) return PPK_OK;
   if (!dist || !out) return ppk_fail(PPK_ERR_ARG, "NULL distance/output buffer");
-  if (device_id < 0 || device_id >= 64) return ppk_fail(PPK_ERR_ARG, "device id out of range");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
+  PPK_ENTER_DEVICE(guard, device_id);
   // 12 bytes per row over PCIe against 0.002 ns of kernel: the rows go through in chunks of 64 MB in / 32 MB out.
   // Step c stages and uploads chunk c (ppk_upload: helper threads copy it into a pinned ring, the DMA runs on
   // behind), launches its kernel, and only then fetches chunk c-1 -- that copy into pageable memory blocks the
@@ -1124,7 +1094,7 @@ extern "C" int ppk_assign_threshold(const float *dist, size_t n_rows, int slope,
   const size_t chunk = (size_t)8 << 20;
   const size_t n_chunks = (n_rows + chunk - 1) / chunk;
   const size_t buf_rows = n_rows < chunk ? n_rows : chunk;
-  AssignBufs &ab = g_assign[device_id];
+  AssignBufs &ab = g_assign.at(device_id);
   std::lock_guard<std::mutex> lk(ab.mu);
   int rc = PPK_OK;
   auto ok = [&](hipError_t e, const char *what) {
@@ -1133,32 +1103,15 @@ extern "C" int ppk_assign_threshold(const float *dist, size_t n_rows, int slope,
   };
   g_trace.t0 = now_ms();
   HostToucher toucher(out, n_rows * 4);
-  hipStream_t s_up = nullptr, s_k = nullptr, s_dn = nullptr;
-  {
-    hipStream_t ws[3] = {nullptr, nullptr, nullptr};
-    if (worker_streams(device_id, ws, 3) != PPK_OK) return PPK_ERR_HIP;
-    s_up = ws[0];
-    s_k = ws[1];
-    s_dn = ws[2];
-  }
-  if (ab.rows < buf_rows) {
-    (void)hipDeviceSynchronize();
-    for (int i = 0; i < 2; ++i) {
-      if (ab.d_in[i]) (void)hipFree(ab.d_in[i]);
-      if (ab.d_out[i]) (void)hipFree(ab.d_out[i]);
-      ab.d_in[i] = ab.d_out[i] = nullptr;
-    }
-    ab.rows = 0;
-    for (int i = 0; i < 2 && rc == PPK_OK; ++i) {
-      ok(hipMalloc(reinterpret_cast<void **>(&ab.d_in[i]), buf_rows * 8), "hipMalloc");
-      ok(hipMalloc(reinterpret_cast<void **>(&ab.d_out[i]), buf_rows * 4), "hipMalloc");
-    }
-    if (rc == PPK_OK) ab.rows = buf_rows;
-  }
+  hipStream_t ws[3] = {nullptr, nullptr, nullptr};
+  if (worker_streams(device_id, kAssignSet, ws, 3) != PPK_OK) return PPK_ERR_HIP;
+  const hipStream_t s_up = ws[0], s_k = ws[1], s_dn = ws[2];
   for (int i = 0; i < 2 && rc == PPK_OK; ++i) {
-    if (!ab.up[i]) ok(hipEventCreateWithFlags(&ab.up[i], hipEventDisableTiming), "hipEventCreate");
-    if (!ab.done[i]) ok(hipEventCreateWithFlags(&ab.done[i], hipEventDisableTiming), "hipEventCreate");
-    if (!ab.freed_in[i]) ok(hipEventCreateWithFlags(&ab.freed_in[i], hipEventDisableTiming), "hipEventCreate");
+    ok(ab.d_in[i].grow(buf_rows * 8), "hipMalloc");
+    ok(ab.d_out[i].grow(buf_rows * 4), "hipMalloc");
+    ok(ppk_event_get(&ab.up[i]), "hipEventCreate");
+    ok(ppk_event_get(&ab.done[i]), "hipEventCreate");
+    ok(ppk_event_get(&ab.freed_in[i]), "hipEventCreate");
   }
   for (size_t c = 0; c <= n_chunks && rc == PPK_OK; ++c) {
     if (c < n_chunks) {
@@ -1166,12 +1119,12 @@ extern "C" int ppk_assign_threshold(const float *dist, size_t n_rows, int slope,
       const size_t r0 = c * chunk, nr = r0 + chunk < n_rows ? chunk : n_rows - r0;
       if (c >= 2) ok(hipStreamWaitEvent(s_up, ab.freed_in[b], 0), "hipStreamWaitEvent");      // kernel c-2 has read d_in[b]
       g_trace.mark(0, "a_up_begin", (long long)c);
-      if (rc == PPK_OK) rc = ppk_upload(device_id, ab.d_in[b], dist + r0 * 2, nr * 8, s_up);
+      if (rc == PPK_OK) rc = ppk_upload(device_id, ab.d_in[b].p, dist + r0 * 2, nr * 8, s_up);
       g_trace.mark(0, "a_up_end", (long long)c);
       ok(hipEventRecord(ab.up[b], s_up), "hipEventRecord");
       ok(hipStreamWaitEvent(s_k, ab.up[b], 0), "hipStreamWaitEvent");
       // (d_out[b] is free: chunk c-2 was fetched, synchronously, in step c-1)
-      if (rc == PPK_OK) rc = ppk_assign_threshold_dev(ab.d_in[b], nr, slope, x_max, y_max, ab.d_out[b], s_k);
+      if (rc == PPK_OK) rc = ppk_assign_threshold_dev(static_cast<float *>(ab.d_in[b].p), nr, slope, x_max, y_max, static_cast<float *>(ab.d_out[b].p), s_k);
       ok(hipEventRecord(ab.done[b], s_k), "hipEventRecord");
       ok(hipEventRecord(ab.freed_in[b], s_k), "hipEventRecord");
     }
@@ -1182,16 +1135,16 @@ extern "C" int ppk_assign_threshold(const float *dist, size_t n_rows, int slope,
       ok(hipStreamWaitEvent(s_dn, ab.done[b], 0), "hipStreamWaitEvent");
       toucher.wait((r0 + nr) * 4);
       g_trace.mark(0, "a_dn_begin", (long long)p);
-      ok(hipMemcpyAsync(out + r0, ab.d_out[b], nr * 4, hipMemcpyDeviceToHost, s_dn), "hipMemcpy D2H");
+      ok(hipMemcpyAsync(out + r0, ab.d_out[b].p, nr * 4, hipMemcpyDeviceToHost, s_dn), "hipMemcpy D2H");
       ok(hipStreamSynchronize(s_dn), "hipMemcpy D2H");
       g_trace.mark(0, "a_dn_end", (long long)p);
     }
   }
   g_trace.mark(0, "a_loop_done");
   const std::string keep = ppk_error();
-  if (s_up) (void)hipStreamSynchronize(s_up);
-  if (s_k) ok(hipStreamSynchronize(s_k), "assign kernel");
-  if (s_dn) ok(hipStreamSynchronize(s_dn), "hipMemcpy D2H");
+  (void)hipStreamSynchronize(s_up);
+  ok(hipStreamSynchronize(s_k), "assign kernel");
+  ok(hipStreamSynchronize(s_dn), "hipMemcpy D2H");
   g_trace.mark(0, "a_synced");
   toucher.join();
   if (rc != PPK_OK && !keep.empty()) ppk_set_error(keep);
@@ -1380,8 +1333,7 @@ extern "C" int ppk_edge_threshold(const float *dist, size_t n_rows, size_t n_ref
   if (n_rows == 0) return PPK_OK;
   if (!dist) return ppk_fail(PPK_ERR_ARG, "dist is NULL");
   if (!n_edges) return ppk_fail(PPK_ERR_ARG, "n_edges is NULL");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
+  PPK_ENTER_DEVICE(guard, device_id);
   size_t guess = n_rows / 8 > ((size_t)1 << 20) ? n_rows / 8 : ((size_t)1 << 20);
   if (guess > n_rows) guess = n_rows;
   return host_edge_list(device_id, dist, n_rows * 8, guess, ij_out, cap, n_edges,
@@ -1403,8 +1355,7 @@ extern "C" int ppk_generate_all_tuples(size_t num_ref, size_t num_queries, int s
   if (n == 0) return PPK_OK;
   if (n > cap) return ppk_fail(PPK_ERR_CAPACITY, "output too small: need " + std::to_string(n));
   if (!ij_out) return ppk_fail(PPK_ERR_ARG, "ij_out is NULL");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
+  PPK_ENTER_DEVICE(guard, device_id);
   if (int rc = ppk_check_arch(device_id)) return rc;
   PpkCall call(device_id, nullptr);
   void *d = nullptr;
@@ -1429,8 +1380,7 @@ extern "C" int ppk_qc_edges(const float *dist, size_t n_rows, size_t n_ref, int 
   if (!dist) return ppk_fail(PPK_ERR_ARG, "dist is NULL");
   if (!n_edges || !n_first) return ppk_fail(PPK_ERR_ARG, "n_edges / n_first is NULL");
   if ((modes & 3) == 0 || (modes & ~3)) return ppk_fail(PPK_ERR_ARG, "modes: bit 0 long distances, bit 1 zero distances");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
+  PPK_ENTER_DEVICE(guard, device_id);
   size_t guess = n_rows / 16 > ((size_t)1 << 20) ? n_rows / 16 : ((size_t)1 << 20);   // QC failures are the exception
   if (guess > 2 * n_rows) guess = 2 * n_rows;
   return host_edge_list(device_id, dist, n_rows * 8, guess, ij_out, cap, n_edges,
@@ -1462,8 +1412,7 @@ extern "C" int ppk_generate_tuples(const int32_t *assignments, size_t n_rows, in
   if (n_rows == 0) return PPK_OK;
   if (!assignments) return ppk_fail(PPK_ERR_ARG, "assignments is NULL");
   if (!n_edges) return ppk_fail(PPK_ERR_ARG, "n_edges is NULL");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
+  PPK_ENTER_DEVICE(guard, device_id);
   size_t guess = n_rows / 8 > ((size_t)1 << 20) ? n_rows / 8 : ((size_t)1 << 20);
   if (guess > n_rows) guess = n_rows;
   return host_edge_list(device_id, assignments, n_rows * 4, guess, ij_out, cap, n_edges,
@@ -1510,12 +1459,8 @@ void run_edge_part(EdgePart &p, const int32_t *kmers, const float *random_tbl, s
     p.err = ppk_error();
   };
   DeviceGuard g(p.device);
-  if (!g.ok) {
-    ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(p.device));
-    return fail(PPK_ERR_HIP);
-  }
   hipStream_t ws[2] = {nullptr, nullptr};
-  int rc = part_streams(p.device, p.dup, ws);
+  int rc = part_streams(g, p.device, p.dup, ws);
   if (rc != PPK_OK) return fail(rc);
   hipStream_t s = ws[0];
   p.s = s;
@@ -1538,12 +1483,11 @@ void run_edge_part(EdgePart &p, const int32_t *kmers, const float *random_tbl, s
   // hipFree pair of that size costs anything between a few and several hundred milliseconds on a fresh box.  A
   // piece is first offered the room that is left (at least one edge per 64 pairs, 1 Mi entries); a piece that does
   // not fit runs once more with the exact size in a buffer that then stays that large.
-  QueryBufs &qb = g_qbufs[p.device][p.dup];
-  if (!qb.d_cnt2 && hipMalloc(reinterpret_cast<void **>(&qb.d_cnt2), 16) != hipSuccess)
-    return fail(ppk_fail(PPK_ERR_HIP, "hipMalloc failed"));
-  unsigned long long *d_cnt = qb.d_cnt2;      // [0] edges, [1] failed fits
-  long long *d_edges = static_cast<long long *>(qb.buf[0]);
-  size_t cap = qb.bytes[0] / 16, acc = 0;      // entries the buffer holds / entries of this band already in it
+  QueryBufs &qb = g_qbufs.at(p.device)[p.dup];
+  if (qb.cnt2.grow(16) != hipSuccess) return fail(ppk_fail(PPK_ERR_HIP, "hipMalloc failed"));
+  unsigned long long *d_cnt = static_cast<unsigned long long *>(qb.cnt2.p);      // [0] edges, [1] failed fits
+  long long *d_edges = static_cast<long long *>(qb.buf[0].p);
+  size_t cap = qb.buf[0].bytes / 16, acc = 0;      // entries the buffer holds / entries of this band already in it
   for (size_t lo = p.q_begin; lo < p.q_end;) {
     const size_t hi = lo + step < p.q_end ? lo + step : p.q_end;
     const size_t rows = ppk_rows_in_band(p.ref->n, n_qry, lo, hi);
@@ -1565,7 +1509,7 @@ void run_edge_part(EdgePart &p, const int32_t *kmers, const float *random_tbl, s
         if (want > cap) {
           g_trace.mark(p.dup, "e_alloc", (long long)want);
           void *b = nullptr;
-          if ((rc = query_buf(p.device, p.dup, 0, want * 16, &b)) != PPK_OK) return fail(rc);
+          if ((rc = query_buf(qb, 0, want * 16, &b)) != PPK_OK) return fail(rc);
           d_edges = static_cast<long long *>(b);
           cap = want;
           g_trace.mark(p.dup, "e_alloc_done", (long long)want);
@@ -1620,7 +1564,7 @@ int query_edges_dbs_locked(const ppk_db *const *refs, const ppk_db *const *qrys,
                            unsigned long long *n_failed) {
   if (n_edges) *n_edges = 0;
   if (n_failed) *n_failed = 0;
-  if (!refs || n_dev < 1 || n_dev > 64) return ppk_fail(PPK_ERR_ARG, "ppk_query_edges_dbs: no databases");
+  if (!refs || n_dev < 1 || n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, "ppk_query_edges_dbs: no databases");
   if (!n_edges) return ppk_fail(PPK_ERR_ARG, "n_edges is NULL");
   if (slope < 0 || slope > 2) return ppk_fail(PPK_ERR_ARG, "slope must be 0, 1 or 2");
   if (flags & (PPK_FLAG_JACCARD | PPK_FLAG_COUNTS)) return ppk_fail(PPK_ERR_ARG, "edge output excludes the jaccard/counts flags");
@@ -1739,6 +1683,36 @@ extern "C" int ppk_query_bgmm_edges_dbs(const ppk_db *const *refs, const ppk_db 
   return rc;
 }
 
+namespace {
+// the resident copies of a host sketch array on the listed devices: from (and into) ppk_query's cache.  `pinned`
+// (nullable): per entry a database the call already uses on that device (never evicted).
+int acquire_on_devices(const uint64_t *sk, size_t n, size_t nk, size_t s64, size_t bbits, const uint16_t *clu,
+                       const int *devices, int n_dev, const std::vector<const ppk_db *> *pinned,
+                       std::vector<const ppk_db *> &dbs, std::vector<ppk_db *> &owned) {
+  const bool use_cache = ppk_config().db_cache.load() != 0;
+  const uint64_t fp = use_cache ? fingerprint(sk, n * nk * s64 * bbits, clu, n) : 0;
+  dbs.assign((size_t)n_dev, nullptr);
+  for (int d = 0; d < n_dev; ++d) {
+    int first = -1;
+    for (int e = 0; e < d && first < 0; ++e)
+      if (devices[e] == devices[d]) first = e;
+    if (first >= 0) {                       // the same device again: the same copy
+      dbs[(size_t)d] = dbs[(size_t)first];
+      continue;
+    }
+    if (int rc = ppk_check_device(devices[d])) return rc;
+    ppk_db *db = nullptr;
+    bool own = false;
+    int rc = db_acquire(devices[d], sk, n, nk, s64, bbits, clu, fp, use_cache, pinned ? (*pinned)[(size_t)d] : nullptr,
+                        nullptr, &db, &own);
+    if (rc != PPK_OK) return rc;
+    dbs[(size_t)d] = db;
+    if (own) owned.push_back(db);
+  }
+  return PPK_OK;
+}
+}  // namespace
+
 extern "C" int ppk_query_edges(const uint64_t *ref_sk, size_t n_ref, const uint64_t *qry_sk, size_t n_qry,
                                const int32_t *kmers, size_t nk, size_t sketchsize64, size_t bbits,
                                const float *random_tbl, const uint16_t *ref_clu, const uint16_t *qry_clu,
@@ -1754,44 +1728,14 @@ extern "C" int ppk_query_edges(const uint64_t *ref_sk, size_t n_ref, const uint6
     devices = &default_dev;
     n_dev = 1;
   }
-  if (n_dev > 64) return ppk_fail(PPK_ERR_ARG, "too many devices");
+  if (n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, "too many devices");
   std::lock_guard<std::mutex> lk(g_query_mu);
   // the resident copies: from ppk_query's cache (hash of every word, checked here before anything runs) or uploaded
-  const bool use_cache = ppk_config().db_cache.load() != 0;
-  const uint64_t ref_fp = use_cache ? fingerprint(ref_sk, n_ref * nk * sketchsize64 * bbits, ref_clu, n_ref) : 0;
-  const uint64_t qry_fp = use_cache && n_qry ? fingerprint(qry_sk, n_qry * nk * sketchsize64 * bbits, qry_clu, n_qry) : 0;
-  std::vector<const ppk_db *> refs((size_t)n_dev, nullptr), qrys((size_t)n_dev, nullptr);
+  std::vector<const ppk_db *> refs, qrys;
   std::vector<ppk_db *> owned;
-  int rc = PPK_OK;
-  for (int d = 0; d < n_dev && rc == PPK_OK; ++d) {
-    int first = -1;
-    for (int e = 0; e < d && first < 0; ++e)
-      if (devices[e] == devices[d]) first = e;
-    if (first >= 0) {                       // the same device again: the same copies
-      refs[(size_t)d] = refs[(size_t)first];
-      qrys[(size_t)d] = qrys[(size_t)first];
-      continue;
-    }
-    if (devices[d] < 0 || devices[d] >= 64) {
-      rc = ppk_fail(PPK_ERR_ARG, "device id out of range");
-      break;
-    }
-    ppk_db *db = nullptr;
-    bool own = false;
-    rc = db_acquire(devices[d], ref_sk, n_ref, nk, sketchsize64, bbits, ref_clu, ref_fp, use_cache, nullptr, nullptr,
-                    &db, &own);
-    if (rc != PPK_OK) break;
-    refs[(size_t)d] = db;
-    if (own) owned.push_back(db);
-    if (n_qry) {
-      db = nullptr;
-      rc = db_acquire(devices[d], qry_sk, n_qry, nk, sketchsize64, bbits, qry_clu, qry_fp, use_cache, refs[(size_t)d],
-                      nullptr, &db, &own);
-      if (rc != PPK_OK) break;
-      qrys[(size_t)d] = db;
-      if (own) owned.push_back(db);
-    }
-  }
+  int rc = acquire_on_devices(ref_sk, n_ref, nk, sketchsize64, bbits, ref_clu, devices, n_dev, nullptr, refs, owned);
+  if (rc == PPK_OK && n_qry)
+    rc = acquire_on_devices(qry_sk, n_qry, nk, sketchsize64, bbits, qry_clu, devices, n_dev, &refs, qrys, owned);
   if (rc == PPK_OK)
     rc = query_edges_dbs_locked(refs.data(), n_qry ? qrys.data() : nullptr, n_dev, kmers, random_tbl, n_clu, flags, slope,
                                 x_max, y_max, scale_x, scale_y, inclusive, nullptr, ij_out, cap, n_edges, n_failed);
@@ -1826,12 +1770,8 @@ void run_knn_part(KnnPart &p, const int32_t *kmers, const float *random_tbl, siz
     p.err = ppk_error();
   };
   DeviceGuard g(p.device);
-  if (!g.ok) {
-    ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(p.device));
-    return fail(PPK_ERR_HIP);
-  }
   hipStream_t ws[2] = {nullptr, nullptr};
-  int rc = part_streams(p.device, p.dup, ws);
+  int rc = part_streams(g, p.device, p.dup, ws);
   if (rc != PPK_OK) return fail(rc);
   const size_t m = (p.db->n + (p.qry ? p.qry->n : 0)) * (size_t)knn;
   long long *d_i = nullptr, *d_j = nullptr;
@@ -1862,7 +1802,7 @@ void run_knn_part(KnnPart &p, const int32_t *kmers, const float *random_tbl, siz
 int knn_lists_locked(const ppk_db *const *dbs, const ppk_db *const *qrys, int n_dev, const int32_t *kmers,
                      const float *random_tbl, size_t n_clu, int flags, int knn, int dist_col,
                      std::vector<long long> &j_out, std::vector<float> &d_out) {
-  if (!dbs || n_dev < 1 || n_dev > 64) return ppk_fail(PPK_ERR_ARG, "neighbour lists: no databases");
+  if (!dbs || n_dev < 1 || n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, "neighbour lists: no databases");
   if (knn < 1 || knn > 32) return ppk_fail(PPK_ERR_ARG, "knn must be in [1, 32]");
   std::vector<KnnPart> parts((size_t)n_dev);
   for (int d = 0; d < n_dev; ++d) {
@@ -1935,30 +1875,6 @@ int knn_lists_locked(const ppk_db *const *dbs, const ppk_db *const *qrys, int n_
   return PPK_OK;
 }
 
-// the resident copies of a host sketch array on the listed devices: from (and into) ppk_query's cache
-int acquire_on_devices(const uint64_t *sk, size_t n, size_t nk, size_t s64, size_t bbits, const uint16_t *clu,
-                       const int *devices, int n_dev, std::vector<const ppk_db *> &dbs, std::vector<ppk_db *> &owned) {
-  const bool use_cache = ppk_config().db_cache.load() != 0;
-  const uint64_t fp = use_cache ? fingerprint(sk, n * nk * s64 * bbits, clu, n) : 0;
-  dbs.assign((size_t)n_dev, nullptr);
-  for (int d = 0; d < n_dev; ++d) {
-    int first = -1;
-    for (int e = 0; e < d && first < 0; ++e)
-      if (devices[e] == devices[d]) first = e;
-    if (first >= 0) {
-      dbs[(size_t)d] = dbs[(size_t)first];
-      continue;
-    }
-    if (devices[d] < 0 || devices[d] >= 64) return ppk_fail(PPK_ERR_ARG, "device id out of range");
-    ppk_db *db = nullptr;
-    bool own = false;
-    int rc = db_acquire(devices[d], sk, n, nk, s64, bbits, clu, fp, use_cache, nullptr, nullptr, &db, &own);
-    if (rc != PPK_OK) return rc;
-    dbs[(size_t)d] = db;
-    if (own) owned.push_back(db);
-  }
-  return PPK_OK;
-}
 }  // namespace
 
 extern "C" int ppk_query_knn_dbs(const ppk_db *const *dbs, int n_dev, const int32_t *kmers, const float *random_tbl,
@@ -1991,13 +1907,13 @@ extern "C" int ppk_query_knn(const uint64_t *sk, size_t n, const int32_t *kmers,
     devices = &default_dev;
     n_dev = 1;
   }
-  if (n_dev > 64) return ppk_fail(PPK_ERR_ARG, "too many devices");
+  if (n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, "too many devices");
   std::lock_guard<std::mutex> lk(g_query_mu);
   std::vector<const ppk_db *> dbs;
   std::vector<ppk_db *> owned;
   std::vector<long long> j;
   std::vector<float> d;
-  int rc = acquire_on_devices(sk, n, nk, sketchsize64, bbits, clu, devices, n_dev, dbs, owned);
+  int rc = acquire_on_devices(sk, n, nk, sketchsize64, bbits, clu, devices, n_dev, nullptr, dbs, owned);
   if (rc == PPK_OK) rc = knn_lists_locked(dbs.data(), nullptr, n_dev, kmers, random_tbl, n_clu, flags, knn, dist_col, j, d);
   const std::string keep = ppk_error();
   for (ppk_db *db : owned) ppk_db_destroy(db);

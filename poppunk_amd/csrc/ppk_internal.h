@@ -24,6 +24,7 @@
 #define PPK_LANES 64           // wavefront width on CDNA
 #define PPK_NPAD 256           // sample axis padded to a multiple of this
 #define PPK_RANK_SHORT_WORDS 16   // words of per-block "short" flags a launch carries (ppk_db::rank_short): one per k, and one to spare
+constexpr int PPK_MAX_DEVICES = 64;   // device ids the per-device tables hold: [0, PPK_MAX_DEVICES)
 
 #include "ppk_device.h"
 
@@ -160,11 +161,11 @@ void ppk_set_error(const std::string &msg);
 const std::string &ppk_error();          // the calling thread's message
 int ppk_fail(int code, const std::string &msg);
 
-// shared between ppk_api.hip (device entry points) and ppk_host.hip (host-buffer entry points)
-int ppk_check_arch(int device_id);       // gfx950 / wave64 or an error, cached per device
+// PPK_ERR_ARG for an id outside [0, PPK_MAX_DEVICES): what every entry point that is given a device id, a device list
+// or a handle carrying one asks before its first HIP call and before it touches any per-device state
+int ppk_check_device(int dev);
+int ppk_check_arch(int device_id);       // ... and gfx950 / wave64 or an error, cached per device (ppk_devstate.hip)
 int ppk_check_pair(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, size_t q_begin, size_t q_end);
-void ppk_upload_rings_release();
-void ppk_assign_bufs_release_all();
 bool ppk_interrupted();                  // the ppk_set_interrupt_check check asks to stop (ppk_host.hip)
 
 #define PPK_HIP(call)                                                              \
@@ -187,6 +188,25 @@ struct DeviceGuard {
   }
 };
 
+// An entry point's device: the id checked, then the device selected for the scope
+#define PPK_ENTER_DEVICE(guard, dev)                             \
+  if (int rc_dev_ = ppk_check_device(dev)) return rc_dev_;       \
+  DeviceGuard guard(dev);                                        \
+  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(dev))
+
+// One device's turn in a release loop: the first holder that has something to free there calls enter(), which selects
+// the device and drains it -- once, however many holders follow.
+struct PpkDeviceVisit {
+  explicit PpkDeviceVisit(int d) : dev(d) {}
+  void enter();
+  const int dev;
+  std::unique_ptr<DeviceGuard> guard;
+};
+// what ppk_host.hip keeps on visit.dev (upload ring, assign and query buffers), each under its own lock; the resident
+// databases of the host queries on every device
+void ppk_host_bufs_release(PpkDeviceVisit &visit);
+void ppk_db_cache_clear();
+
 // Device geometry (ppk_dist.hip): read once per device, never assumed ----------
 struct PpkGeometry {
   int cus;              // compute units (hipDeviceProp_t::multiProcessorCount)
@@ -194,7 +214,8 @@ struct PpkGeometry {
   int tile_slots;       // 512-thread workgroups of the pair-tile kernel resident at once (occupancy x cus: 512 on
                         // MI355X in SPX mode -- the "round" every tile-count rule of the route choice is stated in)
 };
-const PpkGeometry &ppk_geometry(int dev);
+const PpkGeometry &ppk_geometry(int dev);      // cached in the device's state (ppk_devstate.hip)
+PpkGeometry ppk_measure_geometry(int dev);     // ... from this, once per device (ppk_dist.hip: it names the tile kernel)
 
 // Route of one band of pair tiles (ppk_dist.hip: ppk_choose_route) -------------
 enum PpkRoute {
@@ -295,7 +316,56 @@ int ppk_row_edges(const void *d_rows, size_t n_rows, size_t n_ref, long long int
 // the model into scratch slot SLOT_BGMM of `dev`, enqueued on `s` (the caller holds a PpkCall)
 int ppk_bgmm_to_device(int dev, const ppk_bgmm &m, const ppk_bgmm **d_model, hipStream_t s);
 
-// grow-only per-device scratch (ppk_api.hip)
+// ---- per-device state ------------------------------------------------------------------------------------------
+// A per-device table.  The entry points have asked ppk_check_device: an id that still arrives out of range is a bug
+// in this library, and the process stops there instead of reading another device's state.
+template <typename T>
+class PpkPerDevice {
+  T v_[PPK_MAX_DEVICES];
+
+ public:
+  T &at(int dev) {
+    if (dev < 0 || dev >= PPK_MAX_DEVICES) abort();
+    return v_[dev];
+  }
+  template <typename F>
+  void each(F &&f) {
+    for (int d = 0; d < PPK_MAX_DEVICES; ++d) f(d, v_[d]);
+  }
+};
+
+// Grow-only blocks of device / pinned host memory, on the current device.  grow(): nothing when the block holds
+// `bytes` already; otherwise the device is synchronised (earlier work may still use the old block), the block freed and
+// bytes + slack allocated.  A failed allocation leaves the block released and its size 0.
+struct PpkDeviceBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  hipError_t grow(size_t want, size_t slack = 0);
+  void release();      // (the caller has synchronised)
+};
+struct PpkPinnedBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  hipError_t grow(size_t want, size_t slack = 0, unsigned flags = hipHostMallocDefault);
+  void release();
+};
+// an untimed event, created where *e is still null; release destroys and clears it
+hipError_t ppk_event_get(hipEvent_t *e);
+void ppk_event_release(hipEvent_t *e);
+
+// A ticket a kernel publishes into coherent pinned memory, polled by the host.  ONE counter per device for every user
+// (with a counter each, one could hand out a number the pinned word still holds from another's last call, and the wait
+// would return before the kernel had run); a zeroed 256-byte block per (device, user): their layouts differ.  The
+// caller holds the device's PpkCall: one call at a time.
+enum PpkTicketUser { PPK_TICKET_KNN_COUNT = 0, PPK_TICKET_SWEEP_CTRL = 1, PPK_TICKET_USERS = 2 };
+void *ppk_ticket_block(int dev, PpkTicketUser user);      // null: no pinned memory
+unsigned long long ppk_next_ticket(int dev);
+// Polls `word` for `ticket` for at most budget_us, asking the stream every 1024 spins whether it has ended or failed;
+// then drains the stream and looks once more.  `what`: the error message of a ticket that never came.
+int ppk_wait_ticket(hipStream_t s, const volatile unsigned long long *word, unsigned long long ticket, long long budget_us,
+                    const char *what);
+
+// grow-only per-device scratch (ppk_devstate.hip)
 enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 4, SLOT_ITER_C = 5,
        SLOT_BOUNDS = 6, SLOT_HOST_IN = 7,      // HOST_IN: the uploaded input of a host-array call
        SLOT_TICKETS = 8,                       // one counter per tile of a k-split job: zero when allocated, left zero by every launch
@@ -322,10 +392,14 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_LINEAGE = 29,                      // the strain lineages' first-offender words, id owners, segment and route tables, one band's key buffers and temp storage; the ranks' counts and offsets
        SLOT_COUNT = 30 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
+// The fit tables in SLOT_LUT.  ppk_lut_ready: whether the tables of `key` (k list, random table, sketch size, options)
+// already stand at `d_lut`; if not, none count as valid until the calling thread's launcher has enqueued lut_kernel
+// for them and said so with ppk_lut_commit.  Inside a PpkCall scope of `dev`.
+bool ppk_lut_ready(int dev, uint64_t key, const void *d_lut);
 void ppk_lut_commit(int dev, const void *d_lut);
 // Scope of one entry point that uses the scratch of `dev`: holds that device's (recursive) mutex and
 // names the stream the call enqueues on, so that a slot last used on another stream is waited for
-// (see ppk_api.hip).  ppk_scratch_get fails outside such a scope.
+// (see ppk_devstate.hip).  ppk_scratch_get fails outside such a scope.
 class PpkCall {
  public:
   PpkCall(int dev, hipStream_t s);
@@ -392,8 +466,7 @@ bool ppk_lds_opt_in(const void *kernel, int dev, int bytes);
 // SLOT_HOST_IN carved by `layout` and `body` (the uploads, the device call and the downloads).
 template <typename Layout, typename Body>
 int ppk_host_frame(int device, Layout &&layout, Body &&body) {
-  DeviceGuard guard(device);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device));
+  PPK_ENTER_DEVICE(guard, device);
   PpkCall call(device, nullptr);
   const int rc = ppk_scratch_carve(device, SLOT_HOST_IN, layout);
   return rc != PPK_OK ? rc : body();

@@ -30,7 +30,7 @@
 //    builds a ballot bitmask per offset (within boundary o and not within o-1), then the shared
 //    stable compaction emits (i, j, o) like the reference's loops.
 //  The call's one synchronisation (the candidate count sizes the sort) is a ticket the scan kernel leaves in a pinned
-//  block and the host polls (wait_for_ticket).
+//  block and the host polls (ppk_wait_ticket).
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -862,42 +862,6 @@ unsigned resident_workgroups(int dev, const void *kernel, int threads, size_t dy
   return (unsigned)per_cu * (unsigned)cus;
 }
 
-// one pinned control block per device (the caller holds that device's PpkCall: one call at a time); kept for the
-// life of the process
-Ctrl *pinned_ctrl(int dev) {
-  static Ctrl *blocks[64] = {};
-  if (dev < 0 || dev >= 64) return nullptr;
-  // coherent host memory: the host reads it while the stream is still running
-  if (!blocks[dev]) {
-    if (hipHostMalloc(reinterpret_cast<void **>(&blocks[dev]), 256, hipHostMallocCoherent) != hipSuccess) blocks[dev] = nullptr;
-    else memset(blocks[dev], 0, 256);
-  }
-  return blocks[dev];
-}
-
-// The tickets of a device's calls: ONE counter per device for every instantiation of ti_classify (a counter of its own
-// per instantiation could hand out a number the pinned word still holds from the other one's last call, and the wait
-// below would return before the scan kernel had run).  The caller holds the device's PpkCall: one call at a time.
-unsigned long long next_ticket(int dev) {
-  static unsigned long long tickets[64] = {};
-  return ++tickets[dev & 63];
-}
-
-// Waits for the scan kernel's ticket in the pinned block (the word behind the control block), polling for up to about
-// 2 ms -- the classify pass of a 10 000-genome matrix takes 0.25 ms --, then, or when the stream reports an error,
-// by draining the stream.
-int wait_for_ticket(hipStream_t s, const Ctrl *h_ctrl, unsigned long long ticket) {
-  const volatile unsigned long long *word = reinterpret_cast<const volatile unsigned long long *>(h_ctrl + 1);
-  for (int spin = 0; spin < 40000; ++spin) {
-    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == ticket) return PPK_OK;
-    if ((spin & 1023) == 1023 && hipStreamQuery(s) != hipErrorNotReady) break;      // done, or failed: let the drain say which
-    __builtin_ia32_pause();
-  }
-  PPK_HIP(hipStreamSynchronize(s));
-  if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != ticket) return ppk_fail(PPK_ERR_HIP, "the sweep's scan kernel did not report");
-  return PPK_OK;
-}
-
 // what the classify pass leaves on the device, and the control block as the host read it after its one sync
 template <typename F>
 struct Classified {
@@ -1019,7 +983,8 @@ int ti_classify(int dev, hipStream_t s, const float2 *dist, size_t n_rows, const
   unsigned *cand_key = reinterpret_cast<unsigned *>(A + a_keys);
   uint64_t *mask = static_cast<uint64_t *>(p_mask);
   unsigned long long *block_sums = static_cast<unsigned long long *>(p_ws);
-  Ctrl *h_ctrl = pinned_ctrl(dev);
+  // the sweeps' pinned block: the control block, the scan kernel's ticket in the word behind it
+  Ctrl *h_ctrl = static_cast<Ctrl *>(ppk_ticket_block(dev, PPK_TICKET_SWEEP_CTRL));
   if (!h_ctrl) return ppk_fail(PPK_ERR_HIP, "hipHostMalloc failed");
 
   std::vector<char> up(256 + padded.size() * sizeof(Bnd), 0);
@@ -1045,11 +1010,14 @@ int ti_classify(int dev, hipStream_t s, const float2 *dist, size_t n_rows, const
   else PPK_TI1_CLASSIFY(2, false);
 #undef PPK_TI1_CLASSIFY
   ppk_prof_stage("scan", s);
-  const unsigned long long ticket = next_ticket(dev);
+  const unsigned long long ticket = ppk_next_ticket(dev);
   hipLaunchKernelGGL(ti1_scan_kernel, dim3(1), dim3(1024), 0, s, block_sums, n_cblocks, stops, n_stops, ctrl, h_ctrl, ticket);
   ppk_prof_stage(nullptr, s);
   PPK_HIP(hipGetLastError());
-  rc = wait_for_ticket(s, h_ctrl, ticket);      // (the scan kernel has left the control block in the pinned host block)
+  // up to 2 ms of polling (the classify pass of a 10 000-genome matrix takes 0.25 ms); the scan kernel has then left
+  // the control block in the pinned host block
+  rc = ppk_wait_ticket(s, reinterpret_cast<const volatile unsigned long long *>(h_ctrl + 1), ticket, 2000,
+                       "the sweep's scan kernel did not report");
   if (rc != PPK_OK) return rc;
   out.got = *h_ctrl;
   out.d_bnd = d_bnd;
@@ -1373,8 +1341,7 @@ int host_coo(const float *dist, size_t n_rows, size_t n_off, int device_id, long
   *n_out = 0;
   if (n_rows == 0) return PPK_OK;
   if (!dist) return ppk_fail(PPK_ERR_ARG, "dist is NULL");
-  DeviceGuard guard(device_id);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(device_id));
+  PPK_ENTER_DEVICE(guard, device_id);
   size_t guess = n_rows / 4 > ((size_t)1 << 20) ? n_rows / 4 : ((size_t)1 << 20);
   if (guess > n_rows * (n_off ? n_off : 1)) guess = n_rows * (n_off ? n_off : 1);
   auto compute = [&](size_t c, void **d_res, unsigned long long *want) {

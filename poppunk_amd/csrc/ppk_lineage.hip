@@ -606,6 +606,7 @@ extern "C" int ppk_strain_ranks_dev(const long long *d_j, const float *d_dist, c
 extern "C" int ppk_strain_knn(const float *dist, size_t n, int dist_col, const long long *members,
                               const long long *seg_off, size_t n_strains, size_t depth, int device_id,
                               long long *i_out, long long *j_out, float *d_out) {
+  if (int rc = ppk_check_device(device_id)) return rc;
   const std::string who = "ppk_strain_knn";
   if (!dist || !members || !i_out || !j_out || !d_out) return ppk_fail(PPK_ERR_ARG, who + ": NULL array");
   if (n < 2 || n >= (size_t)0x7fffffff) return ppk_fail(PPK_ERR_ARG, who + ": n must be 2 .. 2^31 - 2");
@@ -637,6 +638,7 @@ extern "C" int ppk_strain_ranks(const long long *j, const float *dist, const lon
                                 int count_unique_distances, float epsilon, int device_id, int32_t *prefix,
                                 long long *pos_i, long long *pos_j, long long *level, float *level_dist, size_t cap,
                                 size_t *n_out) {
+  if (int rc = ppk_check_device(device_id)) return rc;
   const std::string who = "ppk_strain_ranks";
   if (!n_out) return ppk_fail(PPK_ERR_ARG, who + ": n_out is NULL");
   *n_out = 0;

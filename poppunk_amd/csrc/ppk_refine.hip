@@ -515,8 +515,7 @@ extern "C" int ppk_refine_local_eval_dev(const ppk_refine_local *h, float x_max,
   const bool x_in = x_max >= h->lo[0] && x_max <= h->hi[0], y_in = y_max >= h->lo[1] && y_max <= h->hi[1];
   if ((h->slope != 1 && !x_in) || (h->slope != 0 && !y_in)) return ppk_fail(PPK_ERR_ARG, who + ": the line is outside the bracket");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DeviceGuard guard(h->device);
-  if (!guard.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(h->device));
+  PPK_ENTER_DEVICE(guard, h->device);
   const int dev = h->device;
   PpkCall call(dev, s);
   const size_t n = h->n, words = h->words, m = (size_t)h->n_cand;

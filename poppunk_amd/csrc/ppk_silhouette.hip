@@ -328,6 +328,7 @@ extern "C" int ppk_silhouette_dev(const float *d_dist, size_t n_rows, int metric
 extern "C" int ppk_silhouette(const float *dist, size_t n_rows, int metric, const int32_t *labels, size_t n_levels,
                               int shift, int device_id, double *a, double *b, double *s, int32_t *n_labels,
                               int32_t *valid) {
+  if (int rc = ppk_check_device(device_id)) return rc;
   const std::string who = kWho;
   size_t n = 0;
   const int rc0 = sil_check_args(n_rows, metric, n_levels, shift, &n);

@@ -204,3 +204,62 @@ def test_hot_kernels_have_no_scratch_in_the_compare_loop(tmp_path):
         bc = re.findall(r"v_bcnt_u32_b32 v(\d+), v(\d+), v(\d+)", m.group(2))
         assert len(bc) >= 48
         assert not [t for t in bc if int(t[1]) % 4 == int(t[2]) % 4], prefix + ": v_bcnt bank conflict"
+
+
+def device_entry_points():
+    """(name, [(type, name), ...]) of every function of include/ppk.h that takes a device id or a device list."""
+    src = open(os.path.join(ROOT, "include", "ppk.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    out = []
+    for name, params in re.findall(r"\bint\s+(ppk_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src, flags=re.S):
+        ps = []
+        for p in params.split(","):
+            m = re.match(r"\s*(.*?)(\w+)\s*(\[\w*\])?\s*$", p, flags=re.S)
+            if not m:      # (a function pointer: no such entry point takes a device)
+                ps = []
+                break
+            ps.append(((m.group(1) + ("*" if m.group(3) else "")).replace(" ", ""), m.group(2)))
+        if any(n in ("device", "device_id", "devices") for _, n in ps):
+            out.append((name, ps))
+    return out
+
+
+def test_device_ids_outside_the_table_are_argument_errors():
+    """Every entry point that takes a device id or a device list answers an id outside [0, 64) with ERR_ARG in one
+    wording, before it selects a device or touches per-device state.  The other arguments are minimal valid host
+    arguments: non-null zeroed arrays, one row, the smallest legal counts."""
+    lib = _lib.lib()
+    entries = device_entry_points()
+    assert len(entries) >= 44, [n for n, _ in entries]      # (the header has 44 today)
+    ints = {"slope": 2, "modes": 1, "knn": 1, "dist_col": 0, "flags": 0, "self": 1, "max_links": 1, "min_samples": 2,
+            "n_dev": 1, "inclusive": 1, "n_repu": 1}
+    sizes = {"bbits": 14, "n": 4, "n_vertices": 4, "n_ref": 4, "num_ref": 4, "cap": 1 << 16, "nk": 2, "max_iter": 1, "n_keep": 2}
+    wrong = []
+    for bad in (-1, 64):
+        for name, params in entries:
+            argtypes = _lib.SIGNATURES[name][1]
+            assert len(argtypes) == len(params), name
+            args, keep = [], []
+            for (ctype, pname), at in zip(params, argtypes):
+                if pname == "devices":
+                    keep.append((C.c_int * 1)(bad))
+                    args.append(C.cast(keep[-1], at))
+                elif pname in ("device", "device_id"):
+                    args.append(bad)
+                elif "*" in ctype:
+                    keep.append((C.c_char * 65536)())
+                    if pname == "kmers":
+                        keep[-1][0:8] = np.array([13, 17], dtype=np.int32).tobytes()
+                    if pname == "keep":      # ppk_prune_long: two samples kept (fewer is an empty result)
+                        keep[-1][0:16] = np.array([0, 1], dtype=np.int64).tobytes()
+                    args.append(C.cast(keep[-1], at))
+                elif ctype in ("float", "double"):
+                    args.append(0.5)
+                elif ctype == "size_t":
+                    args.append(sizes.get(pname, 1))
+                else:
+                    args.append(ints.get(pname, sizes.get(pname, 1)))
+            rc = getattr(lib, name)(*args)
+            if rc != _lib.ERR_ARG or b"out of range [0, 64)" not in lib.ppk_last_error():
+                wrong.append((name, bad, rc, lib.ppk_last_error()))
+    assert not wrong, "\n".join(map(repr, wrong))

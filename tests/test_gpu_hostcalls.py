@@ -3,6 +3,7 @@ calls (fit tables, resident databases, parked results) must never answer for inp
 computed from, and a device list runs its entries side by side (one worker thread each).
 """
 import ctypes as C
+import functools
 import os
 import threading
 
@@ -456,12 +457,11 @@ def test_queryDatabaseKNN_mirror(tmp_path, monkeypatch):
     pp_sketchlib.clear_cache()
 
 
-def test_repeated_host_calls_do_not_leak_device_memory():
-    """Every host entry point of the round, 25 times over: after ppk_release_scratch the device has as much free
-    memory as after the first pass (what stays is scratch, caches and resident databases -- all released)."""
-    import torch
+@functools.lru_cache(maxsize=None)
+def _every_host_call(n=600):
+    """The distances of n genomes, and every host entry point of the round on them as a list of calls."""
     from poppunk_amd import qc
-    sk, _ = synth.make_sketches(600, KMERS, cluster_size=30, seed=2)
+    sk, _ = synth.make_sketches(n, KMERS, cluster_size=30, seed=2)
     tbl = synth.random_match_table(KMERS)
     dist, _ = pp_sketchlib.query_arrays(sk, None, KMERS, 16, 14, tbl)
     x_max, y_max = synth.boundary_for_quantile(dist, 0.1)
@@ -469,32 +469,99 @@ def test_repeated_host_calls_do_not_leak_device_memory():
     qq, _ = pp_sketchlib.query_arrays(sk[500:], None, KMERS, 16, 14, tbl)
     qr, _ = pp_sketchlib.query_arrays(sk[:500], sk[500:], KMERS, 16, 14, tbl)
 
-    def one_pass():
-        pp_sketchlib.query_arrays(sk, None, KMERS, 16, 14, tbl, devices=(0, 0))
-        pp_sketchlib.query_edges_arrays(sk, None, KMERS, 16, 14, 2, x_max, y_max, random_table=tbl, devices=(0, 0), cap=5)
-        pp_sketchlib.query_knn_arrays(sk, KMERS, 16, 14, 4, 0, tbl, devices=(0, 0))
-        poppunk_refine.assignThreshold(dist, 2, x_max, y_max)
-        poppunk_refine.edgeThreshold_array(dist, 2, x_max, y_max)
-        poppunk_refine.thresholdIterate1D_arrays(dist, np.linspace(0, 0.2, 7), 2, 0.0, 0.0, x_max, y_max)
-        poppunk_refine.generateAllTuples_array(300)
-        qc.qc_edge_lists(dist, 0, 0.02, 0.3)
+    def neighbours():
         nn = poppunk_refine.get_kNN_distances(sq, 6)
-        poppunk_refine.lowerRank_arrays(nn, 600, 2, True, True, 1e-4)
-        sub = poppunk_refine.get_kNN_distances(np.ascontiguousarray(sq[:500, :500]), 6)
-        poppunk_refine.extend_arrays(sub, oracle.long_to_square(qq[:, 0]), np.ascontiguousarray(qr[:, 0].reshape(100, 500).T), 6)
+        return nn, poppunk_refine.lowerRank_arrays(nn, 600, 2, True, True, 1e-4)
 
-    def free_bytes():
-        pp_sketchlib.clear_cache()               # resident databases, query buffers, scratch
-        _lib.lib().ppk_release_scratch()
-        torch.cuda.synchronize()
-        return torch.cuda.mem_get_info(0)[0]
+    def extend():
+        sub = poppunk_refine.get_kNN_distances(np.ascontiguousarray(sq[:500, :500]), 6)
+        return poppunk_refine.extend_arrays(sub, oracle.long_to_square(qq[:, 0]), np.ascontiguousarray(qr[:, 0].reshape(100, 500).T), 6)
+
+    calls = [
+        lambda: pp_sketchlib.query_arrays(sk, None, KMERS, 16, 14, tbl, devices=(0, 0)),
+        lambda: pp_sketchlib.query_edges_arrays(sk, None, KMERS, 16, 14, 2, x_max, y_max, random_table=tbl, devices=(0, 0), cap=5),
+        lambda: pp_sketchlib.query_knn_arrays(sk, KMERS, 16, 14, 4, 0, tbl, devices=(0, 0)),
+        lambda: poppunk_refine.assignThreshold(dist, 2, x_max, y_max),
+        lambda: poppunk_refine.edgeThreshold_array(dist, 2, x_max, y_max),
+        lambda: poppunk_refine.thresholdIterate1D_arrays(dist, np.linspace(0, 0.2, 7), 2, 0.0, 0.0, x_max, y_max),
+        lambda: poppunk_refine.generateAllTuples_array(300),
+        lambda: qc.qc_edge_lists(dist, 0, 0.02, 0.3),
+        neighbours,
+        extend,
+    ]
+    sweep_2d = lambda: poppunk_refine.thresholdIterate2D_arrays(dist, np.linspace(0.01, x_max, 6), y_max)      # noqa: E731
+    return calls, sweep_2d
+
+
+def _released_free_bytes():
+    import torch
+    pp_sketchlib.clear_cache()               # resident databases, query buffers, scratch
+    _lib.lib().ppk_release_scratch()
+    torch.cuda.synchronize()
+    return torch.cuda.mem_get_info(0)[0]
+
+
+def _flat(result):
+    """The arrays and numbers of a call's result, in order."""
+    if isinstance(result, (tuple, list)):
+        return [a for r in result for a in _flat(r)]
+    return [np.asarray(result)]
+
+
+def test_repeated_host_calls_do_not_leak_device_memory():
+    """Every host entry point of the round, 25 times over: after ppk_release_scratch the device has as much free
+    memory as after the first pass (what stays is scratch, caches and resident databases -- all released)."""
+    calls, _ = _every_host_call()
+
+    def one_pass():
+        for call in calls:
+            call()
 
     one_pass()
-    base = free_bytes()
+    base = _released_free_bytes()
     for _ in range(25):
         one_pass()
-    after = free_bytes()
+    after = _released_free_bytes()
     assert base - after < (64 << 20), "device memory shrank by %d MB over 25 passes" % ((base - after) >> 20)
+
+
+def test_every_kept_buffer_is_rebuilt_after_release():
+    """Everything the host calls keep per device -- scratch slots, the query buffers and streams of both occurrence
+    entries of devices=(0, 0), the assign buffers, the upload ring, the fit tables -- is given back by clear_cache +
+    ppk_release_scratch and built again by the next call: the same calls return the same arrays after a release, and
+    a second release leaves the free device memory where the first did."""
+    calls, sweep_2d = _every_host_call()
+    calls = calls + [sweep_2d]
+    start = _released_free_bytes()
+    first = [_flat(call()) for call in calls]
+    _released_free_bytes()
+    for k, call in enumerate(calls):
+        again = _flat(call())
+        assert len(again) == len(first[k]), k
+        for a, b in zip(first[k], again):
+            assert np.array_equal(a, b), "call %d differs after a release" % k
+    assert abs(start - _released_free_bytes()) < (64 << 20)
+
+
+def test_sweep_and_neighbour_tickets_share_one_counter():
+    """The 1-D sweep, the 2-D sweep and the neighbour lists each wait for a kernel's ticket in pinned host memory, and
+    all three take their tickets from the device's one counter: alternated on device 0, none of them ever takes a
+    number left by another for its own (it would read a result before the kernel had run)."""
+    sk, _ = synth.make_sketches(500, KMERS, cluster_size=25, seed=12)
+    tbl = synth.random_match_table(KMERS)
+    dist, _ = pp_sketchlib.query_arrays(sk, None, KMERS, 16, 14, tbl)
+    x_max, y_max = synth.boundary_for_quantile(dist, 0.1)
+    jobs = [
+        lambda: poppunk_refine.thresholdIterate1D_arrays(dist, np.linspace(0, 0.2, 7), 2, 0.0, 0.0, x_max, y_max),
+        lambda: poppunk_refine.thresholdIterate2D_arrays(dist, np.linspace(0.01, x_max, 6), y_max),
+        lambda: pp_sketchlib.query_knn_arrays(sk, KMERS, 16, 14, 5, 1, tbl),
+    ]
+    want = [_flat(job()) for job in jobs]
+    for rnd in range(1, 10):
+        for k, job in enumerate(jobs):
+            got = _flat(job())
+            assert len(got) == len(want[k]) and all(np.array_equal(a, b) for a, b in zip(got, want[k])), (rnd, k)
+    pp_sketchlib.clear_cache()
 
 
 def _two_component_model(dist):
