@@ -694,7 +694,9 @@ __global__ void __launch_bounds__(64) bt_small_kernel(const unsigned *rstart, co
   for (int v = threadIdx.x; v < nc; v += blockDim.x) out[v] = bc[v];
 }
 
-// per scored vertex: the sum of its component's partials in item order, times 1 / ((nc - 1)(nc - 2))
+// per scored vertex: the sum of its component's partials in item order, over (nc - 1)(nc - 2).  A division, not a
+// product with the rounded reciprocal: a sum that is exact (a star's centre, (nc - 1)(nc - 2) itself) gives the
+// correctly rounded value, 1.0, where x * (1 / x) falls one ulp short for 50 of the sizes below 400 (nc = 301 is one).
 __global__ void __launch_bounds__(kThreads) bt_reduce_kernel(const double *partial, const int *csize,
                                                              const int *cstart, const int *ibase,
                                                              const long long *pbase, const long long *hdr, double *val) {
@@ -704,7 +706,7 @@ __global__ void __launch_bounds__(kThreads) bt_reduce_kernel(const double *parti
     const double *x = partial + pbase[c] + (p - cstart[c]);
     double acc = 0.0;
     for (int k = 0; k < items; ++k) acc += x[(long long)k * nc];
-    val[p] = acc * (1.0 / ((double)(nc - 1) * (double)(nc - 2)));
+    val[p] = acc / ((double)(nc - 1) * (double)(nc - 2));
   }
 }
 
