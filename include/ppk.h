@@ -957,6 +957,40 @@ int ppk_strain_ranks(const long long *j, const float *dist, const long long *seg
                      float epsilon, int device_id, int32_t *prefix, long long *pos_i, long long *pos_j,
                      long long *level, float *level_dist, size_t cap, size_t *n_out);
 
+/* ppk_strain_extend_dev: poppunk_refine.extend (src/extend.cpp:52-126, as ppk_extend states it) inside
+ * every strain at once -- a query batch added to the stored neighbour lists of the strains it was assigned to
+ * (poppunk_lineages --query-db, PopPUNK/lineages.py:329-466; LineageFit.extend, PopPUNK/models.py:1337-1389).
+ * References: d_members / seg_off as above, ids in [0, n_ref).  Queries: d_queries int64 [mq] (device) with qry_off
+ * int64 [n_strains + 1] (HOST): ids in [0, n_qry), strain by strain in the caller's order; a strain may have none; ids
+ * need not ascend.  Stored lists d_nn_j int64 / d_nn_d float32: the layout ppk_strain_knn_dev writes for (seg_off,
+ * depth), local columns, every row non-decreasing in distance.  d_qr float32 [n_qry * n_ref][2], row q * n_ref + r
+ * (query-major); d_qq float32 [n_qry(n_qry-1)/2][2], the long form over all queries (NULL allowed when no strain has two
+ * queries; d_queries and d_qr NULL allowed when there is no query at all).  Values read from d_qr and d_qq below
+ * `floor` become `floor`; stored values are taken as they are.
+ * Output: strain s has n'_s = n_s + q_s local rows, the members in member order then its queries in list order, each
+ * with min(depth, n'_s - 1) entries (local row, local column, distance): the layout of ppk_strain_knn_dev for the
+ * segment sizes n'_s, so what ppk_strain_ranks_dev takes with those segments.  A row is the merge of the query side
+ * (the strain's queries in list order, stably sorted by distance) and the stored side (a member's stored row as stored;
+ * for a query the members in member order, stably sorted), the query side first on a tie, the sample itself skipped by
+ * index, the first `depth` kept; -0.0 ties with and is returned as 0.0.  Row for row it is bit for bit what ppk_extend
+ * returns for that strain alone with knn = depth.  A strain without queries comes back as its stored lists.
+ * PPK_ERR_ARG before any device is touched for the segment errors above, qry_off[0] != 0 or descending, a strain of two
+ * queries with d_qq NULL.  PPK_ERR_ARG naming the first offender -- the members first, then the queries, then the
+ * stored lists: "strain 1, member 4: sample 700 outside [0, 700)", "strain 2, query 0: query 17 is already query 1 of
+ * strain 0", "strain 3, row 2, entry 5: column 9 outside [0, 9)" / "column 2 is the row itself" / "the distance is below
+ * the entry before it".  Synchronises the stream once, for these checks, before anything is indexed through the lists.
+ * Routes and options as ppk_strain_knn_dev, by the n'_s - 1 candidates of a row.  [parity with src/extend.cpp unpinned,
+ * as for ppk_extend: OUTSIDE SURVEY 8 stays as marked below.] */
+int ppk_strain_extend_dev(const long long *d_members, const long long *seg_off, const long long *d_queries,
+                          const long long *qry_off, size_t n_strains, const long long *d_nn_j, const float *d_nn_d,
+                          const float *d_qr, const float *d_qq, size_t n_ref, size_t n_qry, int dist_col, float floor,
+                          size_t depth, long long *d_i, long long *d_j, float *d_out, void *stream);
+/* Host arrays of the same shapes, on device_id; blocking. */
+int ppk_strain_extend(const long long *members, const long long *seg_off, const long long *queries,
+                      const long long *qry_off, size_t n_strains, const long long *nn_j, const float *nn_d,
+                      const float *qr, const float *qq, size_t n_ref, size_t n_qry, int dist_col, float floor,
+                      size_t depth, int device_id, long long *i_out, long long *j_out, float *d_out);
+
 /* ------------------------------------------------------------------------
  * Density grids of a resident float32 [n_rows][2] matrix: the two layers of the fit plots, each one
  * streaming pass with integer accumulation -- the same bits on every call and for any row order.  The matrix need not

@@ -103,6 +103,10 @@ SIGNATURES = {
     "ppk_strain_knn": (C.c_int, [_f32p, _sz, C.c_int, _llp, _llp, _sz, _sz, C.c_int, _llp, _llp, _f32p]),
     "ppk_strain_ranks": (C.c_int, [_llp, _f32p, _llp, _sz, _sz, _i32p, _sz, C.c_int, C.c_int, C.c_float, C.c_int, _i32p,
                                    _llp, _llp, _llp, _f32p, _sz, _szp]),
+    "ppk_strain_extend_dev": (C.c_int, [_vp, _llp, _vp, _llp, _sz, _vp, _vp, _vp, _vp, _sz, _sz, C.c_int, C.c_float,
+                                        _sz, _vp, _vp, _vp, _vp]),
+    "ppk_strain_extend": (C.c_int, [_llp, _llp, _llp, _llp, _sz, _llp, _f32p, _f32p, _f32p, _sz, _sz, C.c_int,
+                                    C.c_float, _sz, C.c_int, _llp, _llp, _f32p]),
     "ppk_density_kde_dev": (C.c_int, [_vp, _sz, _vp, _sz, _f32p, _f64p, _sz, _f64p, _sz, C.c_double, C.c_int, _vp, _f32p,
                                       _vp]),
     "ppk_density_kde": (C.c_int, [_f32p, _sz, _llp, _sz, _f32p, _f64p, _sz, _f64p, _sz, C.c_double, C.c_int, C.c_int,

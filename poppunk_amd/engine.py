@@ -1092,6 +1092,65 @@ def strain_knn_dev(dist_t, members_t, seg_off, depth, dist_col=0):
     return oi[:nnz], oj[:nnz], od[:nnz]
 
 
+def qr_row_index(q, r, n_ref):
+    """The row of pair (query q, reference r) in the query-major [n_qry * n_ref, 2] matrix, as the kernels of
+    strain_extend_dev compute it: 64-bit, q * n_ref + r passes 2^31 on large databases."""
+    return int(np.int64(q) * np.int64(n_ref) + np.int64(r))
+
+
+def strain_extend_dev(members_t, seg_off, queries_t, qry_off, nn_j_t, nn_d_t, qr_t, qq_t, n_ref, n_qry, depth,
+                      dist_col=0, floor=1e-10):
+    """poppunk_refine.extend inside every strain in one call (ppk_strain_extend_dev, DESIGN.md 3.22;
+    tests/strain_extend_model.py restates it): members_t / seg_off as strain_knn_dev takes them; queries_t int64 [mq]
+    CUDA with qry_off (host), the query ids of every strain back to back (a strain may have none); nn_j_t / nn_d_t the
+    stored lists in strain_knn_dev's layout for (seg_off, depth); qr_t the resident float32 [n_qry * n_ref, 2]
+    query-major matrix; qq_t the float32 [n_qry(n_qry-1)/2, 2] long form of the queries, or None when no strain has
+    two.  Returns CUDA tensors (i, j, dist) with LOCAL indices over the n_s + q_s rows of every strain (members, then
+    queries), min(depth, n_s + q_s - 1) entries a row: strain_knn_dev's layout for seg_off + qry_off, which is what
+    strain_ranks_dev takes."""
+    torch = _torch()
+    dev = members_t.device
+
+    def ok(t, dtype, shape_ok=lambda t: t.dim() == 1):
+        return t.is_cuda and t.dtype == dtype and shape_ok(t) and t.is_contiguous() and t.device == dev
+    if not (ok(members_t, torch.int64) and ok(nn_j_t, torch.int64) and ok(nn_d_t, torch.float32)):
+        raise TypeError("members, and the stored lists, must be contiguous CUDA tensors on one device: int64 [m], "
+                        "int64 and float32 [nnz]")
+    seg, qoff = _strain_segments(seg_off), _strain_segments(qry_off)
+    if seg.shape != qoff.shape:
+        raise ValueError("seg_off and qry_off must have one entry per strain and one more")
+    if int(seg[-1]) != int(members_t.shape[0]):
+        raise ValueError("seg_off must end at the number of members")
+    mq = int(qoff[-1])
+    two = lambda t: t.dim() == 2 and t.shape[1] == 2
+    if mq:
+        if not (ok(queries_t, torch.int64) and int(queries_t.shape[0]) == mq):
+            raise TypeError("queries must be a contiguous int64 [mq] CUDA tensor on the members' device, qry_off ending "
+                            "at mq")
+        if not (ok(qr_t, torch.float32, two) and int(qr_t.shape[0]) == int(n_qry) * int(n_ref)):
+            raise TypeError("qr must be a contiguous float32 [n_qry * n_ref, 2] CUDA tensor on the members' device")
+    if qq_t is not None and not (ok(qq_t, torch.float32, two)
+                                 and int(qq_t.shape[0]) == int(n_qry) * (int(n_qry) - 1) // 2):
+        raise TypeError("qq must be a contiguous float32 [n_qry(n_qry-1)/2, 2] CUDA tensor on the members' device")
+    sizes = np.diff(seg)
+    valid = len(sizes) and sizes.min() >= 2 and int(depth) >= 1 and np.diff(qoff).min() >= 0
+    if valid and strain_nnz(seg, depth) != int(nn_j_t.shape[0]) or nn_j_t.shape != nn_d_t.shape:
+        raise ValueError("the stored lists must hold the entries of strain_knn_dev at this depth")
+    nnz = strain_nnz(seg + qoff, depth) if valid else 0
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    llp = C.POINTER(C.c_longlong)
+    with torch.cuda.device(dev):
+        oi = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
+        oj = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
+        od = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
+        rc = _lib.lib().ppk_strain_extend_dev(
+            ptr(members_t), seg.ctypes.data_as(llp), ptr(queries_t if mq else None), qoff.ctypes.data_as(llp),
+            len(seg) - 1, ptr(nn_j_t), ptr(nn_d_t), ptr(qr_t if mq else None), ptr(qq_t), int(n_ref), int(n_qry),
+            int(dist_col), float(np.float32(floor)), int(depth), ptr(oi), ptr(oj), ptr(od), _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_strain_extend_dev")
+    return oi[:nnz], oj[:nnz], od[:nnz]
+
+
 def strain_ranks_dev(j_t, d_t, seg_off, depth, ranks, reciprocal_only=False, count_unique_distances=False,
                      epsilon=1e-10):
     """lowerRank's rule for every rank on strain_knn_dev's sorted lists (ppk_strain_ranks_dev): j_t,
