@@ -142,6 +142,11 @@ int ppk_device_count(int *n);
  *     "lineage_lds_keys" (0)   the longest row (members of the strain but one) sorted in LDS (0 = as many keys as the
  *                          table holds, 4 096; smaller values send shorter strains through the long route: tests; rows
  *                          of up to 64 keys keep the wave route)
+ *   sketching (ppk_sketch_dev, ppk_sketch; exercised by their own GPU tests, not by the campaign)
+ *     "sketch_lds_bins" (0)    the most bins whose minima the hash kernel keeps in LDS (0 = as many as LDS holds,
+ *                          20 352; smaller values send smaller sketches through the global-atomics route: tests)
+ *     "sketch_batch_mb" (1 024)  the codes of one batch of whole samples of the host call (at least one sample)
+ *     "sketch_batch" (0)   samples per batch, whatever the cap says (0 = from the cap; tests)
  *   host calls
  *     "chunk_rows" (8 Mi)  rows per sub-band of a host query (about an eighth of the job, at least 1 Mi, below 16 Mi
  *                          rows); also scales the pieces of the fused host edge call
@@ -1543,6 +1548,38 @@ int ppk_h5_all_params(ppk_h5 *h, size_t count_cap, int64_t *sketchsize64, int64_
                       size_t kmers_cap, size_t *n_kmers);
 int ppk_h5_read(ppk_h5 *h, const char *names, size_t n, const int32_t *kmers, size_t nk, size_t words,
                 uint64_t *out, int64_t *lengths, int64_t *missing, double *base_freq, int threads);
+
+/* ------------------------------------------------------------------------
+ * Sketching: the codes of n assemblies -> their bin sketches, in the layout every other entry point
+ * reads.  [EXT] The rule -- 64-bit ntHash with seeds recalled from memory, bin = floor(h * nbins / 2^64), the bin's
+ * minimum cut to its low bbits bits, an empty bin filled from the nearest non-empty bin above it, cyclically -- is this
+ * project's own ("poppunk_amd:sketch1"): pp-sketchlib is not in the tree, and sketches made here are NOT bit-compatible
+ * with databases it wrote.  The whole rule is three device functions of poppunk_amd/csrc/ppk_device.h.
+ *     d_codes    uint8: 0-3 = A, C, G, T; 4 = any other residue; 5 = contig break.  A k-mer is hashed when its k
+ *                codes are all below 4.
+ *     d_seq_off  long long [n + 1]: sample i is d_codes[d_seq_off[i] .. d_seq_off[i + 1]); ascending, from 0 or above
+ *     kmers      int32 [nk] (host): 3 .. 101 each, nk <= 128
+ *     flags      PPK_SKETCH_STRAND_PRESERVED: the forward hash alone, not min(forward, reverse complement)
+ *     d_sketches uint64 [n][nk][sketchsize64 * bbits], word [blk * bbits + b] = bit b of bins 64 blk .. 64 blk + 63
+ *     d_stats    long long [n][6]: length (codes below 5), missing bases (codes 4), then the counts of A, C, G, T
+ *     d_filled   int32 [n][nk]: the non-empty bins before empty ones were filled; 0 = the sample has no k-mer of that
+ *                length, and its words are all zero
+ * The same bits on every call, for every cut of the sequences and for every value of the routing options.
+ * PPK_ERR_ARG, before any device is touched: a NULL array, nk outside 1 .. 128, a k-mer length outside 3 .. 101, bbits
+ * other than 14, sketchsize64 below 1 or above 4 096, an unknown flag.  PPK_ERR_ARG, ppk_last_error() naming the first
+ * offender: offsets that do not ascend ("offsets do not ascend at sample 3"), a code above 5 ("sample 2, position 17
+ * (code 1234): code 9 above 5").  The kernels are enqueued on `stream`, which is then synchronised once for that check.
+ * Scratch: 8 bytes per (sample, k, bin) for groups of samples of up to 512 MiB.
+ * (Replaces the sketching half of pp_sketchlib.constructDatabase [EXT], call site PopPUNK/sketchlib.py:410-422.) */
+#define PPK_SKETCH_STRAND_PRESERVED 1
+int ppk_sketch_dev(const uint8_t *d_codes, const long long *d_seq_off, size_t n, const int32_t *kmers, size_t nk,
+                   size_t sketchsize64, size_t bbits, int flags, uint64_t *d_sketches, long long *d_stats,
+                   int32_t *d_filled, void *stream);
+/* Host arrays of the same shapes, on device_id; blocking.  The codes go up through pinned staging in batches of whole
+ * samples of at most option "sketch_batch_mb" MiB (at least one sample; "sketch_batch" forces the count). */
+int ppk_sketch(const uint8_t *codes, const long long *seq_off, size_t n, const int32_t *kmers, size_t nk,
+               size_t sketchsize64, size_t bbits, int flags, int device_id, uint64_t *sketches, long long *stats,
+               int32_t *filled);
 
 /* ------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, the dominant kernel of each

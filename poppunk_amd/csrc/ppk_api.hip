@@ -75,6 +75,9 @@ const OptionEntry kOptions[] = {
     {"rand_window", "PPK_RAND_WINDOW", &PpkConfig::rand_window},
     {"lineage_scratch_mb", "PPK_LINEAGE_SCRATCH_MB", &PpkConfig::lineage_scratch_mb},
     {"lineage_lds_keys", "PPK_LINEAGE_LDS_KEYS", &PpkConfig::lineage_lds_keys},
+    {"sketch_lds_bins", "PPK_SKETCH_LDS_BINS", &PpkConfig::sketch_lds_bins},
+    {"sketch_batch_mb", "PPK_SKETCH_BATCH_MB", &PpkConfig::sketch_batch_mb},
+    {"sketch_batch", "PPK_SKETCH_BATCH", &PpkConfig::sketch_batch},
     {"knn_list", "PPK_KNN_LIST", &PpkConfig::knn_list},
     {"knn_warm", "PPK_KNN_WARM", &PpkConfig::knn_warm},
     {"knn_cut", "PPK_KNN_CUT", &PpkConfig::knn_cut},

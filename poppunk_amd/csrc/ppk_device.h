@@ -251,6 +251,71 @@ __device__ __forceinline__ int ppk_bgmm_label(float core, float acc, const ppk_b
   return ppk_bgmm_label_k<KT>(xs, ys, m);
 }
 
+// ---- the sketch rule "poppunk_amd:sketch1" (ppk_sketch.hip, tests/sketch_device_host.hip) ----
+// [EXT] The hash, the bin and the densify rule below are this project's own definition of a bin sketch: pp-sketchlib
+// is not in the tree, so none of the three is pinned to it.  A later pin changes these functions and nothing else.
+// Codes: 0-3 = A, C, G, T; 4 = any other residue; 5 = contig break.  The seed of a code above 3 is 0: a window that
+// holds one is never hashed, and the rolling form may carry such a term in and out.
+__host__ __device__ __forceinline__ uint64_t ppk_sketch_seed(unsigned code) {      // ntHash's seeds [EXT: recalled]
+  return code == 0 ? 0x3c8bfbb395c60474ull : code == 1 ? 0x3193c18562a02b4cull : code == 2 ? 0x20323ed082572324ull
+       : code == 3 ? 0x295549f54be24456ull : 0ull;
+}
+__host__ __device__ __forceinline__ uint64_t ppk_sketch_seed_rc(unsigned code) {   // the complement's seed
+  return code < 4 ? ppk_sketch_seed(3u - code) : 0ull;
+}
+__host__ __device__ __forceinline__ uint64_t ppk_rol64(uint64_t x, unsigned r) {   // rotation amounts are taken mod 64
+  r &= 63u;
+  return r ? (x << r) | (x >> (64u - r)) : x;
+}
+// min(forward, reverse), or forward alone when strand-preserved
+__host__ __device__ __forceinline__ uint64_t ppk_sketch_pick(uint64_t f, uint64_t r, int strand_preserved) {
+  return strand_preserved || f < r ? f : r;
+}
+// HASH, as defined: f = XOR_i rol(seed[s_i], k-1-i), r = XOR_i rol(seed[3-s_i], i) over the k codes at s (all < 4)
+__host__ __device__ __forceinline__ uint64_t ppk_sketch_hash(const uint8_t *s, int k, int strand_preserved) {
+  uint64_t f = 0, r = 0;
+  for (int i = 0; i < k; ++i) {
+    f ^= ppk_rol64(ppk_sketch_seed(s[i]), (unsigned)(k - 1 - i));
+    r ^= ppk_rol64(ppk_sketch_seed_rc(s[i]), (unsigned)i);
+  }
+  return ppk_sketch_pick(f, r, strand_preserved);
+}
+// ... and its rolling form.  The four terms a code contributes at length k: {entering f, entering r, leaving f,
+// leaving r} (the kernel keeps them in a table per code); all zero for a code above 3.
+__host__ __device__ __forceinline__ void ppk_sketch_terms(unsigned code, int k, uint64_t t[4]) {
+  t[0] = ppk_sketch_seed(code);
+  t[1] = ppk_rol64(ppk_sketch_seed_rc(code), (unsigned)(k - 1));
+  t[2] = ppk_rol64(ppk_sketch_seed(code), (unsigned)k);
+  t[3] = ppk_sketch_seed_rc(code);
+}
+// One step: a code with terms in_f, in_r enters the window, the code k places back (out_f, out_r) leaves it.  Started
+// from f = r = 0 with zero leaving terms for the first k steps, (f, r) after a step are the window's two hashes.
+__host__ __device__ __forceinline__ void ppk_sketch_roll(uint64_t &f, uint64_t &r, uint64_t in_f, uint64_t in_r,
+                                                         uint64_t out_f, uint64_t out_r) {
+  f = ppk_rol64(f, 1) ^ out_f ^ in_f;
+  r = ppk_rol64(r ^ out_r, 63) ^ in_r;
+}
+// BIN: floor(h * nbins / 2^64), one 64-bit multiply-high (nbins < 2^32)
+__host__ __device__ __forceinline__ uint32_t ppk_sketch_bin(uint64_t h, uint32_t nbins) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return (uint32_t)__umul64hi(h, (uint64_t)nbins);
+#else
+  return (uint32_t)(((unsigned __int128)h * nbins) >> 64);
+#endif
+}
+#define PPK_SKETCH_EMPTY (~0ull)      // a bin no k-mer fell into (no hash is stored as this: see ppk_sketch_keep)
+// what a bin keeps of a hash: the hash itself, except that the one value the empty mark takes is stored one lower
+// (both fall into the last bin; the low bbits of the result are the bin's value)
+__host__ __device__ __forceinline__ uint64_t ppk_sketch_keep(uint64_t h) { return h == PPK_SKETCH_EMPTY ? h - 1 : h; }
+// DENSIFY: the bin an empty bin takes its value from -- the nearest non-empty bin above it, cyclically, in the state
+// before densification.  For bin 64 * blk + lane: `mask` = the non-empty bins of its 64-bin block, `next` = the first
+// non-empty bin of the blocks after it, cyclically (this block last).  Bounded and order-free: no loop.
+__host__ __device__ __forceinline__ uint32_t ppk_sketch_densify_src(uint64_t mask, unsigned lane, uint32_t blk,
+                                                                    uint32_t next) {
+  const uint64_t above = mask >> lane;
+  return above ? blk * 64u + lane + (uint32_t)__builtin_ctzll(above) : next;
+}
+
 // ---- host only ----
 // Lower Cholesky factor {L00, L10, L11} of [[a, b], [b, d]], as LAPACK's dpotrf (scipy.linalg.cholesky, bgmm.py:131-
 // 176): false when a pivot is <= 0 or NaN

@@ -145,6 +145,9 @@ struct PpkConfig {
   std::atomic<long long> rand_window{0};        // PPK_RAND_WINDOW: ranks per LDS table window of the pair stage (0 = as many as the table holds, 8 192; small values force the windowed path: tests; -1 forbids it: the classes of a pair that would need more than one window take the wave route; same results)
   std::atomic<long long> lineage_scratch_mb{1024}; // PPK_LINEAGE_SCRATCH_MB: what the two key buffers of one band of rows of ppk_strain_knn_dev's long route may take as allocated (a band holds as many rows of a strain as keep both within four fifths of it; at least one; same results)
   std::atomic<long long> lineage_lds_keys{0};   // PPK_LINEAGE_LDS_KEYS: the longest row (members of the strain but one) ppk_strain_knn_dev sorts in LDS (0 = as many keys as its table holds, 4 096; smaller values send shorter strains through the long route: tests; rows of up to 64 keep the wave route; same results)
+  std::atomic<long long> sketch_lds_bins{0};    // PPK_SKETCH_LDS_BINS: the most bins whose minima ppk_sketch_dev's hash kernel keeps in LDS (0 = as many as LDS holds, 20 352; smaller values send smaller sketches through the global-atomics route: tests; same bits)
+  std::atomic<long long> sketch_batch_mb{1024}; // PPK_SKETCH_BATCH_MB: the codes of one batch of samples of the host call ppk_sketch (whole samples, at least one; same bits)
+  std::atomic<long long> sketch_batch{0};       // PPK_SKETCH_BATCH: samples per batch whatever the cap says (0 = from the cap; tests; same bits)
   std::atomic<long long> knn_list{0};           // PPK_KNN_LIST: entries of the neighbour-candidate list (0 = sized from n and knn)
   std::atomic<long long> host_parts_rows{16 << 20};   // PPK_HOST_PARTS_ROWS: ... from this many rows up
   std::atomic<long long> host_parts{2};         // PPK_HOST_PARTS: worker threads of a one-device host query (>= 16 Mi rows)
@@ -390,7 +393,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_RAND = 27,                         // the contingency sums' first-offender word and per-level state: segment ends, grouped sample indices, dense ranks, long classes
        SLOT_RAND_SUMS = 28,                    // ... and one batch of pairs' partial sums (sized after the levels have been read: growing a slot moves it)
        SLOT_LINEAGE = 29,                      // the strain lineages' first-offender words, id owners, segment and route tables, one band's key buffers and temp storage; the ranks' counts and offsets
-       SLOT_COUNT = 30 };
+       SLOT_SKETCH = 30,                       // the sketcher's control words, piece table and one group of samples' per-bin minima
+       SLOT_COUNT = 31 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 // The fit tables in SLOT_LUT.  ppk_lut_ready: whether the tables of `key` (k list, random table, sketch size, options)
 // already stand at `d_lut`; if not, none count as valid until the calling thread's launcher has enqueued lut_kernel

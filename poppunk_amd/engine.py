@@ -1046,6 +1046,42 @@ def contingency_sums_dev(levels_a, levels_b=None):
     return sq[0][:n_a], sq[1][:n_b], labels[0][:n_a], labels[1][:n_b], cells[0][:n_a, :n_b], cells[1][:n_a, :n_b]
 
 
+def sketch_dev(codes_t, seq_off, kmers, sketchsize64, bbits=14, strand_preserved=False):
+    """Bin sketches of the samples in codes_t (ppk_sketch_dev; tests/sketch_model.py restates the
+    rule): codes_t uint8 CUDA (0-3 = A, C, G, T; 4 = any other residue; 5 = contig break), seq_off the n + 1 offsets
+    of the samples in it (host array or int64 CUDA tensor), kmers the k-mer lengths (host).  Returns CUDA tensors
+    (sketches int64 [n, nk, sketchsize64 * bbits] ready for SketchDB, stats int64 [n, 6] = length, missing bases,
+    A, C, G, T counts, filled int32 [n, nk] = non-empty bins before empty ones were filled).  [EXT] The rule is this
+    project's own: sketches made here do not match those of pp-sketchlib."""
+    torch = _torch()
+    if not (codes_t.is_cuda and codes_t.dtype == torch.uint8 and codes_t.dim() == 1 and codes_t.is_contiguous()):
+        raise TypeError("codes_t must be a contiguous one-dimensional uint8 CUDA tensor")
+    dev = codes_t.device
+    if hasattr(seq_off, "is_cuda"):
+        off_t = seq_off.to(device=dev, dtype=torch.int64).contiguous()
+    else:
+        off_t = torch.as_tensor(np.ascontiguousarray(seq_off, dtype=np.int64), device=dev)
+    if off_t.dim() != 1 or off_t.numel() < 1:
+        raise ValueError("seq_off must be a one-dimensional array of n + 1 offsets")
+    n = int(off_t.numel()) - 1
+    if n > 0 and not hasattr(seq_off, "is_cuda") and int(np.asarray(seq_off).ravel()[-1]) > int(codes_t.numel()):
+        raise ValueError("seq_off ends beyond codes_t")
+    k = np.ascontiguousarray(kmers, dtype=np.int32).ravel()
+    nk, words = int(k.size), int(sketchsize64) * int(bbits)
+    with torch.cuda.device(dev):
+        sketches = torch.zeros((n, nk, max(words, 0)), dtype=torch.int64, device=dev)
+        stats = torch.zeros((n, 6), dtype=torch.int64, device=dev)
+        filled = torch.zeros((n, nk), dtype=torch.int32, device=dev)
+        rc = _lib.lib().ppk_sketch_dev(
+            C.c_void_p(codes_t.data_ptr() if codes_t.numel() else off_t.data_ptr()), C.c_void_p(off_t.data_ptr()), n,
+            k.ctypes.data_as(C.POINTER(C.c_int32)), nk, int(sketchsize64), int(bbits),
+            _lib.SKETCH_STRAND_PRESERVED if strand_preserved else 0, C.c_void_p(sketches.data_ptr() or off_t.data_ptr()),
+            C.c_void_p(stats.data_ptr() or off_t.data_ptr()), C.c_void_p(filled.data_ptr() or off_t.data_ptr()),
+            _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_sketch_dev")
+    return sketches, stats, filled
+
+
 def _strain_segments(seg_off):
     seg = np.ascontiguousarray(seg_off, dtype=np.int64)
     if seg.ndim != 1 or seg.shape[0] < 2:

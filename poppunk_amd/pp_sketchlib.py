@@ -648,6 +648,115 @@ def extendFromDatabases(rr_mat, ref_db_name, query_db_name, rList, qList, klist,
     return oi[:n.value], oj[:n.value], od[:n.value]
 
 
+# ---- making a database (PopPUNK/sketchlib.py:410-422,:469-473) -------------------------------------------------
+
+def _db_path(db_name):
+    """(path, ".h5" | ".npz") of an existing database file, the form sketchdb.load prefers first."""
+    for ext in (".npz", ".h5"):
+        if os.path.exists(db_name + ext):
+            return db_name + ext, ext
+    raise RuntimeError("sketch database %s(.npz|.h5) not found" % db_name)
+
+
+def _write_db(db_name, ext, **content):
+    if ext == ".h5":
+        sketchdb.save_h5(db_name, **content)
+    else:
+        content.pop("sketch_version", None)
+        sketchdb.save_npz(db_name, **content)
+
+
+def constructDatabase(db_name, samples, files, klist, sketch_size, codon_phased=False, calc_random=False,
+                      use_rc=True, min_count=0, exact=False, num_threads=1, use_gpu=False, device_id=0):
+    """Sketch the assemblies `files` (per sample a path or a list of paths, FASTA, plain or gzip) on the MI355X and
+    write `<db_name>.h5` in the reference's layout, with every sample's real `length`, `missing_bases` and `base_freq`:
+    the keywords the reference passes at PopPUNK/sketchlib.py:410-422.  `use_gpu` and `num_threads` do not choose where
+    the sketching runs (there is no CPU path); `num_threads` host threads read the files (at most 16).
+
+    [EXT] The sketch rule is this project's own (poppunk_amd.sketching): the database carries
+    sketch_version "poppunk_amd:sketch1" and is not bit-compatible with one pp-sketchlib wrote.  Not built, each a
+    one-line error: codon_phased=True, read input (FASTQ), min_count and exact other than their defaults.  Without
+    h5py and libhdf5 the same content is written as `<db_name>.npz`, and a line on stderr says so."""
+    from . import sketching
+    if codon_phased:
+        raise RuntimeError("constructDatabase: codon_phased sketches are not built")
+    if min_count not in (0, None) or exact:
+        raise RuntimeError("constructDatabase: min_count and exact count k-mers in reads; sketching reads is not built")
+    samples = [str(s) for s in samples]
+    klist = [int(k) for k in np.asarray(klist).ravel()]
+    if len(samples) != len(files):
+        raise RuntimeError("constructDatabase: samples and files differ in length")
+    for ext in (".h5", ".npz"):
+        # [EXT] pp-sketchlib adds to a file that is there; here a database is written whole or not at all
+        if os.path.exists(db_name + ext):
+            raise RuntimeError("constructDatabase: %s%s exists; remove it (--overwrite) to sketch again" % (db_name, ext))
+    sketches, stats, _ = sketching.sketch_files(samples, files, klist, sketch_size, strand_preserved=not use_rc,
+                                                device_id=device_id, threads=num_threads)
+    content = dict(names=samples, kmers=klist, sketches=sketches, sketchsize64=sketching.sketchsize64_of(sketch_size),
+                   bbits=sketching.BBITS, lengths=stats[:, 0], base_freq=sketching.base_freq_of(stats),
+                   missing_bases=stats[:, 1], sketch_version=sketching.SKETCH_VERSION)
+    try:
+        sketchdb._h5_backend()
+        ext = ".h5"
+    except ImportError:
+        sys.stderr.write("poppunk_amd: neither h5py nor libhdf5 is available; writing %s.npz instead of .h5\n" % db_name)
+        ext = ".npz"
+    _write_db(db_name, ext, **content)
+    if calc_random:
+        addRandom(db_name, samples, klist, use_rc=use_rc, num_threads=num_threads)
+    return samples
+
+
+def addRandom(db_name, samples, klist, use_rc=True, num_threads=1):
+    """[EXT] A /random table for a database made here, so that queryDatabase(random_correct=True) runs on it.  NOT
+    pp-sketchlib's estimate (it simulates random sequences at the samples' base frequencies and clusters them): one
+    cluster for all samples and the documented closed form J_r(k) of docs/sketching.rst:107-114 at the mean sketched
+    length (synth.random_match_table), with its factor 2 (either strand) only when `use_rc`.  The database file is
+    rewritten with the table; `samples` and `klist` are accepted as the reference passes them and the table covers
+    every sample and k-mer length of the file."""
+    path, ext = _db_path(db_name)
+    names = sketchdb.getSeqsInDb(path)
+    version = "poppunk_amd"
+    if ext == ".npz":
+        with np.load(path, allow_pickle=False) as z:
+            kmers = [int(k) for k in z["kmers"]]
+    else:
+        f = sketchdb._h5_backend()[1](path, "r")
+        try:
+            top = f["sketches"]
+            kmers = sorted(int(k) for k in np.asarray(top[names[0]].attrs["kmers"]).ravel())
+            if "sketch_version" in list(top.attrs.keys()):
+                version = top.attrs["sketch_version"]
+                version = version.decode() if isinstance(version, bytes) else str(version)
+        finally:
+            f.close()
+    loaded = sketchdb.load(db_name, names, kmers)
+    mean_length = float(np.mean(loaded.lengths)) if loaded.lengths is not None and len(loaded.lengths) else 0.0
+    table = random_table_for(kmers, mean_length, use_rc)
+    _write_db(db_name, ext, names=loaded.names, kmers=kmers, sketches=loaded.sketches, sketchsize64=loaded.sketchsize64,
+              bbits=loaded.bbits, random_table=table, clusters=np.zeros(len(names), dtype=np.uint16),
+              lengths=loaded.lengths, base_freq=loaded.base_freq, missing_bases=loaded.missing_bases,
+              sketch_version=version)
+    clear_cache_of(path)
+
+
+def random_table_for(kmers, mean_length, use_rc=True):
+    """float32 [nk, 1, 1]: synth.random_match_table at `mean_length`; strand-preserved sketches see one strand, so the
+    chance r of a given k-mer in a random sequence loses its factor 2 (r = 1 - (1 - 4^-k)^l)."""
+    from . import synth
+    if use_rc:
+        return synth.random_match_table(kmers, genome_length=mean_length)
+    k = np.asarray(kmers, dtype=np.float64)
+    r = -np.expm1(float(mean_length) * np.log1p(-(4.0 ** (-k))))
+    return np.ascontiguousarray((r / (2.0 - r))[:, None, None], dtype=np.float32)
+
+
+def clear_cache_of(path):
+    """Forget the loaded copies of one database file (it has been rewritten)."""
+    for key in [k for k in _DB_CACHE if k[0] == os.path.abspath(path)]:
+        _DB_CACHE.pop(key).close()
+
+
 def _f32(a, what):
     a = np.asarray(a)
     if a.dtype != np.float32:

@@ -83,6 +83,70 @@ def prune_query_distance_matrix(refList, queryList, remove_seqs, qrDistMat, quer
     return passing_queries, newqr, queryAssign
 
 
+# ---- QC of the sketched assemblies (PopPUNK/qc.py:137-236) -------------------------------------------------------
+
+def sketchlibAssemblyQC(prefix, names, qc_dict):
+    """PopPUNK/qc.py:137-236: length outliers and samples with too many ambiguous bases, from the `length`,
+    `missing_bases` and `reads` attributes of `<prefix>/<basename>.h5`.  Host work (two attributes per sample): same
+    messages, failure strings and return -- (retained names in the order of `names`, {failed name: [reasons]})."""
+    import os
+    from .sketchdb import _h5_backend
+
+    sys.stderr.write("Running QC on sketches\n")
+    if qc_dict['upper_n'] is not None:
+        sys.stderr.write("Using count cutoff for ambiguous bases: " + str(qc_dict['upper_n']) + "\n")
+    else:
+        sys.stderr.write("Using proportion cutoff for ambiguous bases: " + str(qc_dict['prop_n']) + "\n")
+    if qc_dict['length_range'][0] is None:
+        sys.stderr.write("Using standard deviation for length cutoff: " + str(qc_dict['length_sigma']) + "\n")
+    else:
+        sys.stderr.write("Using range for length cutoffs: " + str(qc_dict['length_range'][0]) + " - " +
+                         str(qc_dict['length_range'][1]) + "\n")
+
+    _, h5open = _h5_backend()
+    hdf_in = h5open(prefix + '/' + os.path.basename(prefix) + '.h5', 'r')
+    wanted = frozenset(names)
+    seq_length, seq_ambiguous = {}, {}
+    try:
+        sketches = hdf_in['sketches']
+        for dataset in sketches.keys():
+            if dataset in wanted:
+                attrs = sketches[dataset].attrs
+                seq_length[dataset] = int(np.asarray(attrs['length']).ravel()[0])
+                # reads are not judged by their Ns; databases of older versions have no such attribute
+                is_reads = 'reads' in list(attrs.keys()) and bool(np.asarray(attrs['reads']).ravel()[0])
+                seq_ambiguous[dataset] = 0 if is_reads else int(np.asarray(attrs['missing_bases']).ravel()[0])
+    except BaseException:
+        hdf_in.close()
+        sys.stderr.write('Problem processing h5 databases during QC - aborting\n')
+        print("Unexpected error:", sys.exc_info()[0], file=sys.stderr)
+        raise
+    hdf_in.close()
+    return assembly_qc_verdict(names, seq_length, seq_ambiguous, qc_dict)
+
+
+def assembly_qc_verdict(names, seq_length, seq_ambiguous, qc_dict):
+    """sketchlibAssemblyQC's verdict from {name: length} and {name: ambiguous bases} (both in database order)."""
+    genome_lengths = np.fromiter(seq_length.values(), dtype=int)
+    mean_genome_length = np.mean(genome_lengths)
+    if qc_dict['length_range'][0] is None:
+        lower_length = mean_genome_length - qc_dict['length_sigma'] * np.std(genome_lengths)
+        upper_length = mean_genome_length + qc_dict['length_sigma'] * np.std(genome_lengths)
+    else:
+        lower_length, upper_length = qc_dict['length_range']
+    failed_samples = {}
+    for dataset, length in seq_length.items():
+        if length < lower_length:
+            failed_samples[dataset] = ['Below lower length threshold']
+        elif length > upper_length:
+            failed_samples[dataset] = ['Above upper length threshold']
+        if (qc_dict['upper_n'] is not None and seq_ambiguous[dataset] > qc_dict['upper_n']) or \
+                (seq_ambiguous[dataset] > qc_dict['prop_n'] * length):
+            failed_samples.setdefault(dataset, []).append("Ambiguous sequence too high")
+    dropped = frozenset(failed_samples)
+    return [x for x in names if x not in dropped], failed_samples
+
+
 # ---- graph QC of query assignments (PopPUNK/qc.py:372-417; DESIGN.md 3.16) -----------------------------------
 
 def cluster_labels_of_names(rList, clusters_of):

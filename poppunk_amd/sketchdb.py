@@ -6,7 +6,8 @@ per (sample, k) under /sketches/<name>/<k> and the attributes `sketchsize64`,
 `sketch_version`, `codon_phased` on /sketches (PopPUNK/web.py:14-61; readers
 PopPUNK/sketchlib.py:109-214), plus the /random group that pp_sketchlib.addRandom
 leaves there (PopPUNK/sketchlib.py:437-473; its presence is what PopPUNK checks,
-:455-466).  Sketching itself (pp_sketchlib.constructDatabase) is out of scope.
+:455-466).  Sketching itself is poppunk_amd/sketching.py (pp_sketchlib.constructDatabase); what it
+writes through save_h5 carries sketch_version "poppunk_amd:sketch1" [EXT: not pp-sketchlib's rule].
 
 Two on-disk forms are read and written here:
 
@@ -61,7 +62,7 @@ def db_file(prefix, ext):
 
 class LoadedSketches:
     def __init__(self, names, kmers, sketches, sketchsize64, bbits, random_table, clusters,
-                 random_raw=None, lengths=None, base_freq=None, random_status="absent"):
+                 random_raw=None, lengths=None, base_freq=None, random_status="absent", missing_bases=None):
         self.names = names
         self.kmers = kmers
         self.sketches = sketches
@@ -74,6 +75,7 @@ class LoadedSketches:
         self.base_freq = base_freq
         # "absent" | "mapped" ([EXT] layout recognised) | "unrecognised" (present, carried raw only)
         self.random_status = random_status
+        self.missing_bases = missing_bases    # int64 [n] ambiguous-base counts, None where the file has none
 
 
 def _select_kmers(db_kmers, klist):
@@ -175,7 +177,7 @@ def random_to_raw(random_table, clusters, names, kmers):
 # ---- .npz ---------------------------------------------------------------------------------------
 
 def save_npz(db_name, names, kmers, sketches, sketchsize64, bbits, random_table=None,
-             clusters=None, random_raw=None, lengths=None, base_freq=None):
+             clusters=None, random_raw=None, lengths=None, base_freq=None, missing_bases=None):
     """db_name is the reference's `<prefix>/<basename>` (no extension)."""
     os.makedirs(os.path.dirname(db_name) or ".", exist_ok=True)
     payload = dict(names=np.asarray(names, dtype=str), kmers=np.asarray(kmers, dtype=np.int32),
@@ -189,6 +191,8 @@ def save_npz(db_name, names, kmers, sketches, sketchsize64, bbits, random_table=
         payload["lengths"] = np.asarray(lengths, dtype=np.int64)
     if base_freq is not None:
         payload["base_freq"] = np.asarray(base_freq, dtype=np.float64)
+    if missing_bases is not None:
+        payload["missing_bases"] = np.asarray(missing_bases, dtype=np.int64)
     for key, val in (random_raw or {}).items():
         val = np.asarray(val)
         if val.dtype == object:
@@ -216,6 +220,7 @@ def _load_npz(path, names, klist):
                 raw["@" + key[len("random@"):]] = z[key]
         lengths = z["lengths"][rows] if "lengths" in z.files else None
         base_freq = z["base_freq"][rows] if "base_freq" in z.files else None
+        missing = z["missing_bases"][rows] if "missing_bases" in z.files else None
         tbl = z["random_table"][kidx] if "random_table" in z.files else None
         clu = z["clusters"][rows] if "clusters" in z.files else None
         status = "mapped" if tbl is not None else "absent"
@@ -228,7 +233,7 @@ def _load_npz(path, names, klist):
                 status = "unrecognised"
         return LoadedSketches(list(names), np.asarray(klist, dtype=np.int32),
                               np.ascontiguousarray(sk), int(z["sketchsize64"]), int(z["bbits"]),
-                              tbl, clu, raw or None, lengths, base_freq, status)
+                              tbl, clu, raw or None, lengths, base_freq, status, missing)
 
 
 # ---- .h5 ------------------------------------------------------------------------------------------
@@ -243,7 +248,7 @@ def _random_of_file(path):
         f.close()
 
 
-def _finish_h5(names, klist, sk, s64, bbits, lengths, base_freq, raw):
+def _finish_h5(names, klist, sk, s64, bbits, lengths, base_freq, raw, missing=None):
     have_freq = base_freq is not None and not np.isnan(base_freq).any()
     tbl, clu, status = None, None, "absent"
     if raw is not None:
@@ -254,7 +259,8 @@ def _finish_h5(names, klist, sk, s64, bbits, lengths, base_freq, raw):
         else:
             status = "unrecognised"
     return LoadedSketches(list(names), np.asarray(klist, dtype=np.int32), sk, s64, bbits, tbl, clu, raw,
-                          lengths, base_freq if have_freq else None, status)
+                          lengths, base_freq if have_freq else None, status,
+                          None if missing is None else np.asarray(missing))
 
 
 def _pick(path, file_names, file_kmers, names, klist):
@@ -302,7 +308,8 @@ def _load_h5(path, names, klist):
             raw = {}
         last_load.update(source="sidecar", backend=0, packed=False, declined="")
         return _finish_h5(names, klist, _take(side.sketches, rows, kidx), side.sketchsize64, side.bbits,
-                          np.asarray(_take(side.lengths, rows)), _take(side.base_freq, rows), raw)
+                          np.asarray(_take(side.lengths, rows)), _take(side.base_freq, rows), raw,
+                          _take(np.asarray(side.missing), rows))
     stamp = h5bulk.h5_stamp(path)
     with h5bulk.H5Bulk(path) as f:
         s64, bbits, _ = f.params()
@@ -319,17 +326,19 @@ def _load_h5(path, names, klist):
         raw = _random_of_file(path) if f.has_random else None
         last_load.update(source="h5", backend=f.backend, packed=False, declined=f.declined)
     if not pack:
-        return _finish_h5(names, klist, sk, s64, bbits, lengths, freq, raw)
+        return _finish_h5(names, klist, sk, s64, bbits, lengths, freq, raw, missing)
     # (base_freq rows of samples without the attribute are NaN in the image too: whether a request has the
     # frequencies is decided over the rows it selects, _finish_h5, exactly as on the direct read)
     last_load["packed"] = h5bulk.sidecar_write(path, stamp, want, klist, sk, s64, bbits, lengths, missing,
                                                freq, raw is not None, raw)
     rows, _ = _pick(path, want, klist, names, klist)
-    return _finish_h5(names, klist, _take(sk, rows), s64, bbits, _take(lengths, rows), _take(freq, rows), raw)
+    return _finish_h5(names, klist, _take(sk, rows), s64, bbits, _take(lengths, rows), _take(freq, rows), raw,
+                      _take(np.asarray(missing), rows))
 
 
 def save_h5(db_name, names, kmers, sketches, sketchsize64, bbits, random_table=None, clusters=None,
-            random_raw=None, lengths=None, base_freq=None, sketch_version="poppunk_amd", codon_phased=False):
+            random_raw=None, lengths=None, base_freq=None, sketch_version="poppunk_amd", codon_phased=False,
+            missing_bases=None):
     """Write `<db_name>.h5` in the reference's layout (PopPUNK/web.py:14-61 for /sketches; attribute
     names as its readers use them, PopPUNK/sketchlib.py:124-133,155-158).  /random: `random_raw`
     verbatim when given (a round trip of what a conversion carried), else (random_table, clusters)
@@ -349,7 +358,7 @@ def save_h5(db_name, names, kmers, sketches, sketchsize64, bbits, random_table=N
             g.attrs["bbits"] = np.int64(bbits)
             g.attrs["kmers"] = np.asarray(kmers, dtype=np.int64)
             g.attrs["length"] = np.int64(lengths[i] if lengths is not None else 0)
-            g.attrs["missing_bases"] = np.int64(0)
+            g.attrs["missing_bases"] = np.int64(missing_bases[i] if missing_bases is not None else 0)
             bf = np.asarray(base_freq[i] if base_freq is not None else [0.25] * 4, dtype=np.float64)
             if not np.isnan(bf).any():        # a NaN row = a sample that had no base_freq attribute: it gets none
                 g.attrs["base_freq"] = bf

@@ -11,8 +11,10 @@ itself too when matplotlib is importable (drawing it is PopPUNK.plot's job, out 
 (:216-346) the file operations --update-db, QC and reference picking run either side of the distance
 call (poppunk_amd/sketchdb.py).
 
-Out of scope here (sketching: SURVEY.md section 8(d) "no genomes are sketched"):
-constructDatabase, addRandom.
+`constructDatabase` (:348-434) and `addRandom` (:437-473) make a database from a list of assemblies: the sketching
+runs on the device (poppunk_amd/sketching.py).  [EXT] Its hash, bin and densify rule is this
+project's own, so a database made here is not bit-compatible with one pp-sketchlib wrote, and addRandom writes the
+documented closed form J_r(k), not pp-sketchlib's simulation.
 """
 import os
 import sys
@@ -21,7 +23,7 @@ from random import sample
 import numpy as np
 
 from . import pp_sketchlib
-from .utils import iterDistRows, stderr_redirected  # noqa: F401  (PopPUNK/utils.py:61-83,:199-226)
+from .utils import iterDistRows, readRfile, stderr_redirected  # noqa: F401  (PopPUNK/utils.py:61-83,:199-226,:410-471)
 from .sketchdb import (getSeqsInDb, readDBParams, getSketchSize, getKmersFromReferenceDatabase,  # noqa: F401
                        get_database_statistics, joinDBs, removeFromDB)  # (PopPUNK/sketchlib.py:109-346,:672-690)
 
@@ -83,6 +85,52 @@ def _write_fit_example(klist, raw, raw_fit, corrected, corrected_fit, out_prefix
     ax.legend()
     fig.savefig(out_prefix + ".png")
     plt.close(fig)
+
+
+def constructDatabase(assemblyList, klist, sketch_size, oPrefix, threads, overwrite, strand_preserved, min_count,
+                      use_exact, calc_random=True, codon_phased=False, use_gpu=False, deviceid=0):
+    """Sketch the assemblies listed in `assemblyList` (readRfile: name and file(s) per line) at the k-mer lengths
+    `klist` into `<oPrefix>/<basename>.h5` and return the sample names, sorted (PopPUNK/sketchlib.py:348-434: same
+    signature, messages and return value).  With `overwrite` an existing database file is removed first; with
+    `calc_random` the random match chances are added (addRandom).  The sketching runs on the MI355X
+    (pp_sketchlib.constructDatabase; [EXT] this project's own sketch rule)."""
+    names, sequences = readRfile(assemblyList)
+    dbname = oPrefix + "/" + os.path.basename(oPrefix)
+    dbfilename = dbname + ".h5"
+    if os.path.isfile(dbfilename) and overwrite == True:      # noqa: E712  (the reference's test)
+        sys.stderr.write("Overwriting db: " + dbfilename + "\n")
+        os.remove(dbfilename)
+    if os.path.isfile(dbname + ".npz") and overwrite == True:      # noqa: E712  (this package's flat form of it)
+        os.remove(dbname + ".npz")
+    pp_sketchlib.constructDatabase(db_name=dbname, samples=names, files=sequences, klist=klist,
+                                   sketch_size=sketch_size, codon_phased=codon_phased, calc_random=False,
+                                   use_rc=not strand_preserved, min_count=min_count, exact=use_exact,
+                                   num_threads=threads, use_gpu=use_gpu, device_id=deviceid)
+    if calc_random:
+        addRandom(oPrefix, names, klist, strand_preserved, overwrite=True, threads=threads)
+    return names
+
+
+def addRandom(oPrefix, sequence_names, klist, strand_preserved=False, overwrite=False, threads=1):
+    """Random match chances for `<oPrefix>/<basename>` (PopPUNK/sketchlib.py:437-473: same signature and messages).
+    [EXT] The table is pp_sketchlib.addRandom's closed form, NOT pp-sketchlib's simulation (see there)."""
+    if len(sequence_names) <= 2:
+        sys.stderr.write("Cannot add random match chances with this few genomes\n")
+        return
+    dbname = oPrefix + "/" + os.path.basename(oPrefix)
+    if not overwrite:
+        from . import sketchdb
+        have = False
+        if os.path.exists(dbname + ".npz"):
+            with np.load(dbname + ".npz", allow_pickle=False) as z:
+                have = "random_table" in z.files or any(k.startswith("random/") for k in z.files)
+        elif os.path.exists(dbname + ".h5"):
+            have = sketchdb._random_of_file(dbname + ".h5") is not None
+        if have:
+            sys.stderr.write("Using existing random match chances in DB\n")
+            return
+    pp_sketchlib.addRandom(db_name=dbname, samples=sequence_names, klist=klist, use_rc=(not strand_preserved),
+                           num_threads=threads)
 
 
 def queryDatabase(rNames, qNames, dbPrefix, queryPrefix, klist, self=True, number_plot_fits=0,

@@ -1,8 +1,8 @@
 """Synthetic bin-sketch generator.
 
-Sketching genomes is out of scope (pp_sketchlib.constructDatabase,
-PopPUNK/sketchlib.py:348-434), so benchmark and test inputs are synthesised
-directly as sketches with the on-disk shape of PopPUNK/web.py:14-61:
+Benchmark and test inputs of the distance engine are synthesised directly as
+sketches, not sketched from genomes (that is poppunk_amd/sketching.py, whose
+rule is this project's own), with the on-disk shape of PopPUNK/web.py:14-61:
 per (sample, k) one uint64 vector of length sketchsize64*bbits, bit-sliced so
 that word [blk*bbits + b] holds bit b of bins 64*blk .. 64*blk+63.
 

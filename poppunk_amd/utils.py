@@ -83,6 +83,49 @@ def readIsolateTypeFromCsv(clustCSV, mode='clusters', return_dict=False):
     return out
 
 
+def isolateNameToLabel(names):
+    """Sample names as labels (PopPUNK/utils.py:473-488): what follows the last '/', '.' '(' ')' as '_', ':' dropped."""
+    drop = str.maketrans({'.': '_', ':': None, '(': '_', ')': '_'})
+    return [name.split('/')[-1].translate(drop) for name in names]
+
+
+def readRfile(rFile, oneSeq=False):
+    """The list of assemblies to sketch (PopPUNK/utils.py:410-471): one sample per line, its name and its sequence
+    file(s) separated by tabs.  Returns (names, sequences) sorted by name, `sequences[i]` the list of files of sample i
+    (with oneSeq its first file alone, with the reference's note when there are more).  A line with fewer than two
+    fields, a '/' in a name and duplicate names (after isolateNameToLabel) each write the reference's message to stderr
+    and exit(1)."""
+    names, sequences = [], []
+    with open(rFile, 'r') as listing:
+        for line in listing:
+            fields = line.rstrip().split("\t")
+            if len(fields) < 2:
+                sys.stderr.write("Input reference list is misformatted\n"
+                                 "Must contain sample name and file, tab separated\n")
+                sys.exit(1)
+            if "/" in fields[0]:
+                sys.stderr.write("Sample names may not contain slashes\n")
+                sys.exit(1)
+            names.append(fields[0])
+            if oneSeq:
+                if len(fields) > 2:
+                    sys.stderr.write("Multiple sequence found for " + fields[0] + ". Only using first\n")
+                sequences.append(fields[1])
+            else:
+                sequences.append(fields[1:])
+    names = isolateNameToLabel(names)
+    if len(set(names)) != len(names):
+        seen, dupes = set(), set()
+        for name in names:
+            (dupes if name in seen else seen).add(name)
+        sys.stderr.write("Input contains duplicate names! All names must be unique\n")
+        sys.stderr.write("Non-unique names are " + ",".join(dupes) + "\n")
+        sys.exit(1)
+    # sorted by name on return, as the reference does (an empty list stays two empty lists)
+    order = sorted(range(len(names)), key=lambda i: (names[i], sequences[i]))
+    return [names[i] for i in order], [sequences[i] for i in order]
+
+
 def iterDistRows(refSeqs, querySeqs, self=True):
     """Row -> (ref, query) names of the distance matrix (PopPUNK/utils.py:199-226)."""
     if self:
