@@ -249,9 +249,19 @@ int ppk_db_fold_read(const ppk_db *db, int which, uint64_t *out, size_t words);
  * order within a bucket.  ppk_db_rank_counts: what the count pass found, 3 x (1 + nk * sketchsize64) words -- for the
  * distinct values D, E = S + 2 and E2 = S3 + 2 the maximum over all positions, then per (k, block) -- and three more:
  * the most two-holder values of a position, their number over all positions, 1 if the per-pair cap was hit; returns the
- * words there are (0: no count pass ran) and fills `out` if `cap` holds them. */
+ * words there are (0: no count pass ran) and fills `out` if `cap` holds them.
+ * Neither a count nor an event depends on the order of a k's positions, so the pair stores them sorted by E2, descending,
+ * ties by stored position ascending (option "fold2_sort", PPK_FOLD2_SORT, default 1, read at creation; 0 keeps the
+ * stored order): the few wide positions share the first blocks of a k and the rest span at most 64 codes, which the
+ * tile kernel compares in 6 planes (option "fold2_min_planes", PPK_FOLD2_MIN_PLANES, default 6, read at launch; 7 stops
+ * at 7 planes).  ppk_db_fold2_position_order: out[k * 64 * sketchsize64 + i] = the stored position slot i of k holds.
+ * ppk_db_fold2_stream_planes: the planes a self job compares per block of SLOTS under the options in force, 8 where the
+ * block's largest E2 is above 128, 7 above 64, else 6.  ppk_db_fold2_block_planes stays the 8 / 7 rule on the STORED
+ * blocks, and ppk_db_fold2_read returns the planes as they lie, in slot order. */
 int ppk_db_fold2_planes(const ppk_db *db);
 int ppk_db_fold2_block_planes(const ppk_db *db, uint8_t *out, size_t cap);
+int ppk_db_fold2_stream_planes(const ppk_db *db, uint8_t *out, size_t cap);
+int ppk_db_fold2_position_order(const ppk_db *db, uint32_t *out, size_t cap);
 int ppk_db_fold2_read(const ppk_db *db, int which, uint64_t *out, size_t words);
 size_t ppk_db_fold2_events(const ppk_db *db, size_t *n_buckets);
 int ppk_db_fold2_events_read(const ppk_db *db, uint32_t *off, size_t n_off, uint16_t *ev, size_t n_ev);

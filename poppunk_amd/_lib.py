@@ -166,6 +166,8 @@ SIGNATURES = {
     "ppk_db_fold_read": (C.c_int, [_vp, C.c_int, _vp, _sz]),
     "ppk_db_fold2_planes": (C.c_int, [_vp]),
     "ppk_db_fold2_block_planes": (C.c_int, [_vp, _vp, _sz]),
+    "ppk_db_fold2_stream_planes": (C.c_int, [_vp, _vp, _sz]),
+    "ppk_db_fold2_position_order": (C.c_int, [_vp, _vp, _sz]),
     "ppk_db_fold2_read": (C.c_int, [_vp, C.c_int, _vp, _sz]),
     "ppk_db_fold2_events": (_sz, [_vp, C.POINTER(C.c_size_t)]),
     "ppk_db_fold2_events_read": (C.c_int, [_vp, _vp, _sz, _vp, _sz]),

@@ -49,6 +49,8 @@ const OptionEntry kOptions[] = {
     {"rank_short", "PPK_RANK_SHORT", &PpkConfig::rank_short},
     {"rank_fold", "PPK_RANK_FOLD", &PpkConfig::rank_fold},
     {"rank_fold2", "PPK_RANK_FOLD2", &PpkConfig::rank_fold2},
+    {"fold2_sort", "PPK_FOLD2_SORT", &PpkConfig::fold2_sort},
+    {"fold2_min_planes", "PPK_FOLD2_MIN_PLANES", &PpkConfig::fold2_min_planes},
     {"lds_table", "PPK_LDS_TABLE", &PpkConfig::lds_table},
     {"ksplit", "PPK_KSPLIT", &PpkConfig::ksplit},
     {"ksplit_slices", "PPK_KSPLIT_SLICES", &PpkConfig::ksplit_slices},
@@ -379,6 +381,8 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   db->fold2_qt = db->fold2_rt = 0;
   db->fold2_events = 0;
   for (unsigned &w : db->fold2_short) w = 0;
+  for (unsigned &w : db->fold2_seven) w = 0;
+  for (unsigned &w : db->fold2_six) w = 0;
   const size_t cols = nk * db->words;
   const size_t in_bytes = n * cols * sizeof(uint64_t);
   const size_t out_bytes = db->npad * cols * sizeof(uint64_t);
@@ -430,10 +434,14 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   // at least four rounds of tiles (a smaller job's time is its latency, not its compare stream).  Caps: at most five k,
   // 8 planes, PPK_FOLD2_SLOTS two-holder values per position, PPK_FOLD2_MAX_PER_PAIR events per (pair, k); a database
   // past any of them keeps the copies it would have had.
+  // The pass also leaves E2 of every position.  Counts and events do not depend on the order of a k's positions, so
+  // the two-holder pair stores them sorted by E2 (option "fold2_sort"): the wide positions share a few blocks and the
+  // rest compare 6 planes (ppk_db::fold2_order / fold2_seven / fold2_six).  The choice among the codings does not look
+  // at the order: it keeps the sums over the stored blocks.
   if (rc == PPK_OK && ppk_config().rank_planes.load() != 0 && ppk_self_job_takes_tiles(db)) {
     unsigned *d_max = nullptr;
     const size_t n_blocks = nk * sketchsize64;
-    std::vector<unsigned> counts(3 * (1 + n_blocks) + PPK_RANK_EXTRA, 0u);
+    std::vector<unsigned> counts(3 * (1 + n_blocks) + PPK_RANK_EXTRA + n_blocks * 64, 0u);      // (behind the figures: E2 per position)
     e = hipMalloc(reinterpret_cast<void **>(&d_max), counts.size() * sizeof(unsigned));
     if (e == hipSuccess) {
       rc = ppk_launch_rank_count(db->d_skT, n, db->npad, nk, sketchsize64, d_max, s);
@@ -471,10 +479,28 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
                               self_tiles >= 4 * (size_t)ppk_geometry(device_id).tile_slots;
       if (rc == PPK_OK && fold2_fits && fold2_opt != 0 && (fold2_opt == 2 || fold2_pays)) {
         bool overflow = false;
-        rc = ppk_build_fold2(db, planes_fold2, extra[1], &overflow, s);
+        // per k a stable sort of the positions by E2, descending: ties keep their stored order
+        const unsigned *pos_e2 = extra + PPK_RANK_EXTRA;
+        const size_t nbins = sketchsize64 * 64;
+        const bool sorted = ppk_config().fold2_sort.load() != 0;
+        db->fold2_order.resize(nk * nbins);
+        for (size_t k = 0; k < nk; ++k) {
+          unsigned *ord = db->fold2_order.data() + k * nbins;
+          for (size_t i = 0; i < nbins; ++i) ord[i] = (unsigned)i;
+          if (sorted)
+            std::stable_sort(ord, ord + nbins, [&](unsigned a, unsigned b) { return pos_e2[k * nbins + a] > pos_e2[k * nbins + b]; });
+        }
+        rc = ppk_build_fold2(db, planes_fold2, extra[1], sorted ? &db->fold2_order : nullptr, &overflow, s);
         extra[2] = overflow ? 1u : 0u;
         if (rc == PPK_OK && db->fold2_planes) {
           for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) db->fold2_short[k] = short_e2[k];
+          for (size_t k = 0; k < nk && flags_fit; ++k)
+            for (size_t b = 0; b < sketchsize64; ++b) {
+              unsigned widest = 0;
+              for (size_t i = 0; i < 64; ++i) widest = std::max(widest, pos_e2[k * nbins + db->fold2_order[k * nbins + b * 64 + i]]);
+              if (widest <= 128u) db->fold2_seven[k] |= 1u << b;
+              if (widest <= 64u) db->fold2_six[k] |= 1u << b;
+            }
           db->rank_planes = planes;
         }
       }
@@ -506,7 +532,8 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
       }
       if (db->rank_planes)
         for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) db->rank_short[k] = short_d[k];
-      if (rc == PPK_OK) db->rank_counts = counts;
+      if (!db->fold2_planes) db->fold2_order.clear();
+      if (rc == PPK_OK) db->rank_counts.assign(counts.begin(), counts.begin() + 3 * (1 + n_blocks) + PPK_RANK_EXTRA);
     } else {
       (void)hipGetLastError();
     }
@@ -611,6 +638,28 @@ extern "C" int ppk_db_fold2_block_planes(const ppk_db *db, uint8_t *out, size_t 
       const bool is_short = k < PPK_RANK_SHORT_WORDS && b < 32 && ((db->fold2_short[k] >> b) & 1u);
       out[k * db->s64 + b] = (uint8_t)(db->fold2_planes - (is_short ? 1 : 0));
     }
+  return PPK_OK;
+}
+
+extern "C" int ppk_db_fold2_stream_planes(const ppk_db *db, uint8_t *out, size_t cap) {
+  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_stream_planes: NULL argument");
+  if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_stream_planes: the database has no two-holder pair");
+  if (cap < db->nk * db->s64) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_stream_planes: `cap` is below nk * sketchsize64");
+  const bool use_short = ppk_config().rank_short.load() != 0, use_six = use_short && ppk_config().fold2_min_planes.load() <= 6;
+  for (size_t k = 0; k < db->nk; ++k)
+    for (size_t b = 0; b < db->s64; ++b) {
+      const bool fits = k < PPK_RANK_SHORT_WORDS && b < 32;
+      const bool seven = fits && use_short && ((db->fold2_seven[k] >> b) & 1u), six = fits && use_six && ((db->fold2_six[k] >> b) & 1u);
+      out[k * db->s64 + b] = (uint8_t)(db->fold2_planes - (six ? 2 : seven ? 1 : 0));
+    }
+  return PPK_OK;
+}
+
+extern "C" int ppk_db_fold2_position_order(const ppk_db *db, uint32_t *out, size_t cap) {
+  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_position_order: NULL argument");
+  if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_position_order: the database has no two-holder pair");
+  if (cap < db->fold2_order.size()) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_position_order: `cap` is below nk * 64 * sketchsize64");
+  for (size_t i = 0; i < db->fold2_order.size(); ++i) out[i] = db->fold2_order[i];
   return PPK_OK;
 }
 

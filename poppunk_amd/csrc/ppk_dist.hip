@@ -194,6 +194,10 @@ struct DistParams {
   const uint16_t *fold2_ev;
   const unsigned *fold2_off;
   unsigned fold2_rt;
+  // Bit b of fold2_six[k]: block b of k spans at most 2^6 codes, planes 6 and 7 are zero there and the kernel compares
+  // 6 planes (ppk_db::fold2_six; every such bit is set in rank_short[k] too; all zero with "fold2_min_planes" 7).
+  // Fetched where rank_short is.
+  unsigned fold2_six[PPK_RANK_SHORT_WORDS];
 };
 
 // With every k usable the least-squares fit is LINEAR in the log J_k with launch-constant weights:
@@ -270,8 +274,11 @@ constexpr int RANK_BMW = (1 << RANK_BB) / 32;      // bitmap dwords per position
 //                   its rank among the position's two-holder values names a pair of LDS slots, the samples that hold it
 //                   atomicMin / atomicMax themselves into them, and the workgroup appends (hi, lo, k) to ev.raw and
 //                   counts the event's bucket (ppk_db::d_fold2_ev).
-//   The count pass leaves E2 = S3 + 2 behind E in the same form, and behind that the most two-holder values of any
-//   position and their number over all positions.
+//   The count pass leaves E2 = S3 + 2 behind E in the same form, behind that the most two-holder values of any
+//   position and their number over all positions (PPK_RANK_EXTRA words), and behind those E2 of every position,
+//   [k][64 * s64]: what ppk_db_create sorts the positions of the two-holder pair by.
+//     FOLD2 with `bytes`: no planes are written; the ref-side code of stored position i of k goes to
+//                   bytes[(k * 64 * s64 + i) * npad + sample] (padding samples 0), for fold2_slice_kernel.
 struct Fold2Emit {
   unsigned long long *raw;      // hi | lo << 28 | k << 56
   unsigned *count;              // events appended so far
@@ -281,7 +288,8 @@ struct Fold2Emit {
 template <bool WRITE, bool FOLD = false, bool FOLD2 = false>
 __global__ void __launch_bounds__(256)
 rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, uint8_t *__restrict__ out_q,
-                 unsigned *__restrict__ max_distinct, size_t n, size_t npad, int s64, int pl, const Fold2Emit ev) {
+                 unsigned *__restrict__ max_distinct, size_t n, size_t npad, int s64, int pl, const Fold2Emit ev,
+                 uint8_t *__restrict__ bytes = nullptr) {
   static_assert(!FOLD2 || (WRITE && FOLD), "the two-holder pair is a folded pair");
   constexpr bool TWICE = !WRITE || FOLD;
   constexpr bool THRICE = !WRITE || FOLD2;
@@ -361,6 +369,7 @@ rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, ui
         atomicMax(max_fold2 + 1 + kb, s3_incl + 2u);
         atomicMax(extra, s_incl - s3_incl);
         atomicAdd(extra + 1, s_incl - s3_incl);
+        extra[PPK_RANK_EXTRA + kb * 64 + (size_t)(g * 8 + j)] = s3_incl + 2u;
       }
       return;
     } else {
@@ -420,6 +429,13 @@ rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, ui
         }
       }
     }
+    if constexpr (FOLD2) {
+      if (bytes) {      // (workgroup-uniform)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) bytes[(kb * 64 + (size_t)(g * 8 + j)) * npad + smp] = (uint8_t)code[j];
+        continue;
+      }
+    }
     for (int b = 0; b < pl; ++b) {
       uint32_t byte = 0;
 #pragma unroll
@@ -454,6 +470,35 @@ rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, ui
         ev.raw[at] = ~0ull;      // (not two holders after all: never -- the scatter reports it, the pair is dropped)
       }
     }
+  }
+}
+
+// The planes of the two-holder pair with its positions in sorted order (ppk_db::fold2_order): slot i of k holds stored
+// position order[k * 64 * s64 + i].  One workgroup per (k, destination block, byte g of its words) and 256 samples; a
+// thread gathers its sample's 8 byte codes (rank_code_kernel with `bytes`) and writes byte g of the `pl` planes of both
+// copies, laid out as rank_code_kernel writes them.  A code is 0 or at least 2: 0 is 1 on the query side (samples below n).
+__global__ void __launch_bounds__(256)
+fold2_slice_kernel(const uint8_t *__restrict__ bytes, const unsigned *__restrict__ order, uint8_t *__restrict__ out,
+                   uint8_t *__restrict__ out_q, size_t n, size_t npad, int s64, int pl) {
+  const int g = blockIdx.x & 7;
+  const size_t kb = blockIdx.x >> 3, k = kb / (size_t)s64, nbins = 64 * (size_t)s64;
+  const size_t smp = (size_t)blockIdx.y * 256 + threadIdx.x;
+  if (smp >= npad) return;
+  const unsigned *ord = order + k * nbins + (kb % (size_t)s64) * 64 + (size_t)g * 8;
+  uint32_t code[8], single = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const size_t pos = ord[j] < nbins ? ord[j] : 0;      // (a permutation of [0, nbins): always below)
+    code[j] = bytes[(k * nbins + pos) * npad + smp];
+    if (smp < n && code[j] == 0) single |= 1u << j;
+  }
+  uint8_t *dst = out + kb * (size_t)pl * npad * 8 + g, *dst_q = out_q + kb * (size_t)pl * npad * 8 + g;
+  for (int b = 0; b < pl; ++b) {
+    uint32_t byte = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) byte |= ((code[j] >> b) & 1u) << j;
+    dst[((size_t)b * npad + smp) * 8] = (uint8_t)byte;
+    dst_q[((size_t)b * npad + smp) * 8] = (uint8_t)(b == 0 ? byte | single : byte);
   }
 }
 
@@ -1764,12 +1809,15 @@ int launch_rank(const ppk_db *ref, int planes, int fold, DistArgs a, DistParams 
   a.sk_r = fold == 2 ? ref->d_fold2R : fold ? ref->d_foldR : ref->d_skR;
   a.sk_q = fold == 2 ? ref->d_fold2Q : fold ? ref->d_foldQ : ref->d_skR;
   // the blocks that compare one plane fewer (option "rank_short", read here: one database runs either way)
-  const unsigned *flags = fold == 2 ? ref->fold2_short : fold ? ref->fold_short : ref->rank_short;
+  const unsigned *flags = fold == 2 ? ref->fold2_seven : fold ? ref->fold_short : ref->rank_short;
   const bool use_short = ppk_config().rank_short.load() != 0;
   for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.rank_short[k] = use_short ? flags[k] : 0u;
   p.fold2_ev = fold == 2 ? ref->d_fold2_ev : nullptr;
   p.fold2_off = fold == 2 ? ref->d_fold2_off : nullptr;
   p.fold2_rt = fold == 2 ? ref->fold2_rt : 0u;
+  // the two-holder pair: the blocks that compare 6 planes (option "fold2_min_planes", read here; 7 keeps them at 7)
+  const bool use_six = fold == 2 && use_short && ppk_config().fold2_min_planes.load() <= 6;
+  for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.fold2_six[k] = use_six ? ref->fold2_six[k] : 0u;
   const auto kernel = fold == 2      ? &dist_kernel_v2_fold2<MODE>
                       : planes == 12 ? &dist_kernel_v2_rank<12, MODE>
                       : planes == 10 ? &dist_kernel_v2_rank<10, MODE>
@@ -1862,10 +1910,11 @@ int ppk_launch_transpose(const uint64_t *d_in, uint64_t *d_out, size_t n, size_t
 }
 
 // The rank codes of a transposed bbits = 14 database (rank_code_kernel): the count pass (d_max: 3 * (1 + nk * s64) +
-// PPK_RANK_EXTRA words, the D maxima, behind them the E and the E2 maxima, then the two-holder figures), then -- with
+// PPK_RANK_EXTRA + nk * s64 * 64 words, the D maxima, behind them the E and the E2 maxima, then the two-holder figures
+// and E2 of every position), then -- with
 // `d_out` -- the code planes: injective, or with `d_out_q` the folded pair (d_out the ref side).  Both only enqueue.
 int ppk_launch_rank_count(const uint64_t *d_skT, size_t n, size_t npad, size_t nk, size_t s64, unsigned *d_max, hipStream_t s) {
-  PPK_HIP(hipMemsetAsync(d_max, 0, (3 * (1 + nk * s64) + PPK_RANK_EXTRA) * sizeof(unsigned), s));
+  PPK_HIP(hipMemsetAsync(d_max, 0, (3 * (1 + nk * s64) + PPK_RANK_EXTRA + nk * s64 * 64) * sizeof(unsigned), s));
   hipLaunchKernelGGL((rank_code_kernel<false>), dim3((unsigned)(nk * s64 * 8)), dim3(256), 0, s, d_skT, nullptr, nullptr, d_max,
                      n, npad, (int)s64, 0, Fold2Emit{});
   PPK_HIP(hipGetLastError());
@@ -1884,14 +1933,21 @@ int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, uint64_t *d_ou
   return PPK_OK;
 }
 // The two-holder pair of `db` and its event list.  Everything is allocated here; a device too full for it, or a
-// (pair, k) with more events than its field holds (*overflow), leaves the database without the pair.
-int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, bool *overflow, hipStream_t s) {
+// (pair, k) with more events than its field holds (*overflow), leaves the database without the pair.  With `order`
+// (nk * 64 * s64 stored positions, a permutation per k) slot i of k holds stored position order[k * 64 * s64 + i]: the
+// code pass then leaves byte codes per stored position and fold2_slice_kernel gathers them into the planes (one byte
+// per (position, sample) of scratch, freed here).  Gathering inside the code pass would read every source word eight
+// times, once per position of the workgroup's byte.
+int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, const std::vector<unsigned> *order, bool *overflow, hipStream_t s) {
   *overflow = false;
   const size_t copy_bytes = db->npad * db->nk * db->s64 * (size_t)planes * sizeof(uint64_t);
   const unsigned qt = (unsigned)(db->npad / 32), rt = (unsigned)(db->npad / V2_RT);
   const size_t nb = (size_t)qt * rt, cap = n_two ? n_two : 1;
   unsigned long long *d_raw = nullptr;
   unsigned *d_cnt = nullptr;      // [nb] bucket counts / cursors, then the event counter and the overflow flag
+  uint8_t *d_bytes = nullptr;     // `order`: the byte codes per stored position
+  unsigned *d_order = nullptr;
+  const size_t n_pos = db->nk * db->s64 * 64;
   auto drop = [&]() {
     (void)hipGetLastError();
     for (void *ptr : {(void *)db->d_fold2R, (void *)db->d_fold2Q, (void *)db->d_fold2_ev, (void *)db->d_fold2_off})
@@ -1904,6 +1960,8 @@ int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, bool *overflow, hipStr
   auto done = [&](int rc) {
     if (d_raw) (void)hipFree(d_raw);
     if (d_cnt) (void)hipFree(d_cnt);
+    if (d_bytes) (void)hipFree(d_bytes);
+    if (d_order) (void)hipFree(d_order);
     return rc;
   };
   hipError_t e = hipMalloc(reinterpret_cast<void **>(&db->d_fold2R), copy_bytes);
@@ -1913,6 +1971,10 @@ int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, bool *overflow, hipStr
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_raw), cap * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), (nb + 2) * sizeof(unsigned));
   if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (nb + 2) * sizeof(unsigned), s);
+  if (order && order->size() != n_pos) order = nullptr;
+  if (e == hipSuccess && order) e = hipMalloc(reinterpret_cast<void **>(&d_bytes), n_pos * db->npad);
+  if (e == hipSuccess && order) e = hipMalloc(reinterpret_cast<void **>(&d_order), n_pos * sizeof(unsigned));
+  if (e == hipSuccess && order) e = hipMemcpyAsync(d_order, order->data(), n_pos * sizeof(unsigned), hipMemcpyHostToDevice, s);
   if (e != hipSuccess) {
     drop();
     return done(PPK_OK);
@@ -1920,7 +1982,11 @@ int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, bool *overflow, hipStr
   const Fold2Emit ev = {d_raw, d_cnt + nb, d_cnt, (unsigned)cap, rt};
   hipLaunchKernelGGL((rank_code_kernel<true, true, true>), dim3((unsigned)(db->nk * db->s64 * 8)), dim3(256), 0, s, db->d_skT,
                      reinterpret_cast<uint8_t *>(db->d_fold2R), reinterpret_cast<uint8_t *>(db->d_fold2Q), nullptr, db->n,
-                     db->npad, (int)db->s64, planes, ev);
+                     db->npad, (int)db->s64, planes, ev, d_bytes);
+  if (order)
+    hipLaunchKernelGGL(fold2_slice_kernel, dim3((unsigned)(db->nk * db->s64 * 8), (unsigned)(db->npad / 256)), dim3(256), 0, s,
+                       d_bytes, d_order, reinterpret_cast<uint8_t *>(db->d_fold2R), reinterpret_cast<uint8_t *>(db->d_fold2Q),
+                       db->n, db->npad, (int)db->s64, planes);
   hipLaunchKernelGGL(fold2_scan_kernel, dim3(1), dim3(1024), 0, s, d_cnt, db->d_fold2_off, nb);
   hipLaunchKernelGGL(fold2_scatter_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, d_raw, d_cnt + nb, (unsigned)cap,
                      db->d_fold2_off, d_cnt, db->d_fold2_ev, rt);

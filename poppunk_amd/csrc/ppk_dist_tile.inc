@@ -246,6 +246,14 @@
     LateParams &pl = *reinterpret_cast<LateParams *>(ka + V2_PARAMS_KERNARG_OFFSET);
     return pl.rank_short[kk];
   };
+  // FOLD2: the second flag word of k `kk` (DistParams::fold2_six: the blocks that compare 6 planes), fetched the same way
+  auto fold2_six_word = [&](int kk) __attribute__((always_inline)) -> uint32_t {
+    const char __attribute__((address_space(4))) *ka =
+        (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    LateParams &pl = *reinterpret_cast<LateParams *>(ka + V2_PARAMS_KERNARG_OFFSET);
+    return pl.fold2_six[kk];
+  };
 
   issue_dma(0, half);
   if (!(ablate & 16)) {   // (bit 16, measurement only: what hiding the tile's first copy could win)
@@ -263,6 +271,8 @@
   constexpr bool SHORT_BLOCKS = PL < V2_BB && !HALF;
   uint32_t short_w = 0;
   if constexpr (SHORT_BLOCKS) short_w = rank_short_word(k);
+  uint32_t six_w = 0;
+  if constexpr (SHORT_BLOCKS && FOLD2) six_w = fold2_six_word(k);
   for (int g = 0; g < total; ++g) {
     const int buf = g & 1;
     // the other buffer was last read in iteration g-1, which every wave left through the barrier
@@ -326,9 +336,19 @@
                  [sb1] "s"(dbase[1]), [sb2] "s"(dbase[SB2]), [sb3] "s"(dbase[LT]), [voa] "v"(voff_ref),           \
                  [vob] "v"(vob), [xblo] "s"(xblo), [xbhi] "s"(xbhi), [sh] "s"(short_w), [bk] "s"(blk)             \
                : "memory", "scc", PPK_BLOCK_CLOBBERS);
+          // FOLD2: three streams, 8 / 7 / 6 planes, on bit blk of short_w and of six_w
+#define PPK_DMA_SEL3_STMT(SUF, SB2)                                                                               \
+  asm volatile(PPK_BLOCK_DMA_SEL3_ASM_Q32##SUF                                                                    \
+               : PPK_BLOCK_OPERANDS                                                                               \
+               : [rp] "v"(rp), [qp] "v"(qp), [m00] "s"(m00), [m03] "s"(m03), [sb0] "s"(dbase[0]),                 \
+                 [sb1] "s"(dbase[1]), [sb2] "s"(dbase[SB2]), [sb3] "s"(dbase[LT]), [voa] "v"(voff_ref),           \
+                 [vob] "v"(vob), [xblo] "s"(xblo), [xbhi] "s"(xbhi), [sh] "s"(short_w), [sh2] "s"(six_w),         \
+                 [bk] "s"(blk)                                                                                    \
+               : "memory", "scc", PPK_BLOCK_CLOBBERS);
           if constexpr (PL < V2_BB) {
             if constexpr (PL == 12) { PPK_DMA_SEL_STMT(_P12, 2) }
             else if constexpr (PL == 10) { PPK_DMA_SEL_STMT(_P10, LT) }
+            else if constexpr (FOLD2) { PPK_DMA_SEL3_STMT(_P8, LT) }
             else { PPK_DMA_SEL_STMT(_P8, LT) }
           } else {
             asm volatile(PPK_BLOCK_DMA_ASM_Q32
@@ -339,6 +359,7 @@
                          : "memory", "scc", PPK_BLOCK_CLOBBERS);
           }
 #undef PPK_DMA_SEL_STMT
+#undef PPK_DMA_SEL3_STMT
           // (after the last block the pieces harmlessly re-load it into the idle buffer)
           if (g + 2 < total) {
 #pragma unroll
@@ -427,6 +448,7 @@
         blk = 0;
         ++k;
         if constexpr (SHORT_BLOCKS) short_w = rank_short_word(k);      // (word nk after the last k: in the array, unused)
+        if constexpr (SHORT_BLOCKS && FOLD2) six_w = fold2_six_word(k);
       }
     }
     // my DMA pieces have landed; after the barrier everyone's have, and everyone has

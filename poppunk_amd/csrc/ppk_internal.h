@@ -64,6 +64,14 @@ struct ppk_db {
   uint64_t *d_fold2R, *d_fold2Q;
   int fold2_planes;
   unsigned fold2_short[PPK_RANK_SHORT_WORDS];
+  // Neither a match count nor an event depends on the order of a k's positions, so the pair stores them sorted by
+  // code span (option "fold2_sort", ppk_db_create): slot i of k holds stored position fold2_order[k * 64 * s64 + i],
+  // E2 descending, ties by stored position ascending (the identity with "fold2_sort" 0).  A block of SLOTS whose
+  // largest E2 is at most 128 compares 7 planes (bit in fold2_seven[k]), at most 64 compares 6 (bit in fold2_six[k]
+  // as well); along a sorted k the planes never increase.  fold2_short stays the 7-plane rule on the STORED blocks
+  // (ppk_db_fold2_block_planes and the choice among the codings); the launch reads fold2_seven / fold2_six.
+  std::vector<unsigned> fold2_order;
+  unsigned fold2_seven[PPK_RANK_SHORT_WORDS], fold2_six[PPK_RANK_SHORT_WORDS];
   uint16_t *d_fold2_ev;
   unsigned *d_fold2_off;        // fold2_qt * fold2_rt + 1 offsets
   unsigned fold2_qt, fold2_rt;  // npad / 32, npad / 256
@@ -107,6 +115,8 @@ struct PpkConfig {
   std::atomic<long long> rank_planes{1};        // PPK_RANK_PLANES: a bbits = 14 database whose self job runs whole tiles keeps a rank-coded copy (ppk_db::d_skR) and self jobs compare it (0: no copy is built, none is read; same bits)
   std::atomic<long long> rank_fold{1};          // PPK_RANK_FOLD: where folding every single-holder bin value into two reserved codes lets a self job compare fewer planes, the database keeps the folded pair (ppk_db::d_foldR / d_foldQ) instead of the injective copy (0: never; 2: whenever the folded codes fit 12 planes, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
   std::atomic<long long> rank_fold2{1};         // PPK_RANK_FOLD2: where coding the two-holder bin values like single-holder ones (their one match per value added back in the tile kernel's epilogue from an event list) lets a large self job compare fewer planes than both other codings, the database keeps the two-holder pair (ppk_db::d_fold2R / d_fold2Q) instead (0: never; 2: whenever the caps allow, any size, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
+  std::atomic<long long> fold2_sort{1};         // PPK_FOLD2_SORT: the two-holder pair stores the positions of each k sorted by the codes they span, so that most 64-bin blocks span at most 64 codes (0: positions as stored; same bits).  Read at creation.
+  std::atomic<long long> fold2_min_planes{6};   // PPK_FOLD2_MIN_PLANES: a self job on the two-holder pair compares 6 planes in the blocks that span at most 64 codes (7: such blocks compare 7, as every block spanning at most 128 does; same bits).  Read at launch.
   std::atomic<long long> rank_short{1};         // PPK_RANK_SHORT: a self job on a rank-coded database compares one plane fewer in the 64-bin blocks whose positions hold at most half the values the planes can code (0: every block compares all planes; same bits).  Read at launch.
   std::atomic<long long> lds_table{1};          // PPK_LDS_TABLE: interior tiles of the default sketch shape fit from the (E, F) table in LDS (0: the general statement everywhere; same bits)
   std::atomic<long long> ksplit{1200};           // PPK_KSPLIT: tile-count threshold (at 5 k) of the small-job path
@@ -252,7 +262,7 @@ int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, uint64_t *d_ou
 // The two-holder pair and its event list (ppk_db::d_fold2R ...): allocates the list, enqueues the code pass, the
 // counting sort and the cap check, and synchronises `s` once.  *overflow: a (pair, k) has more events than its field
 // holds (the caller drops the pair).  `n_two`: the two-holder values the count pass found.
-int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, bool *overflow, hipStream_t s);
+int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, const std::vector<unsigned> *order, bool *overflow, hipStream_t s);
 
 // Profiling hooks (ppk_prof_*) -------------------------------------------------
 void ppk_prof_begin(hipStream_t s);

@@ -186,21 +186,41 @@ class SketchDB:
         return int(_lib.lib().ppk_db_fold2_planes(self._h))
 
     def fold2_block_planes(self):
-        """Planes a self job compares per 64-bin block of the two-holder pair (ppk_db_fold2_block_planes): uint8
-        [nk, sketchsize64]."""
+        """The 8 / 7 plane rule on the 64-bin blocks of the two-holder pair as the sketches store them
+        (ppk_db_fold2_block_planes): uint8 [nk, sketchsize64].  What a self job compares: fold2_stream_planes()."""
         out = np.empty((self.nk, self.sketchsize64), dtype=np.uint8)
         _lib.check(_lib.lib().ppk_db_fold2_block_planes(self._h, C.c_void_p(out.ctypes.data), out.size),
                    "ppk_db_fold2_block_planes")
         return out
 
+    def fold2_stream_planes(self):
+        """Planes a self job compares per block of the two-holder pair's sorted positions, under the options in force
+        (ppk_db_fold2_stream_planes): uint8 [nk, sketchsize64] of 8, 7 or 6."""
+        out = np.empty((self.nk, self.sketchsize64), dtype=np.uint8)
+        _lib.check(_lib.lib().ppk_db_fold2_stream_planes(self._h, C.c_void_p(out.ctypes.data), out.size),
+                   "ppk_db_fold2_stream_planes")
+        return out
+
+    def fold2_position_order(self):
+        """The stored position each slot of the two-holder pair holds (ppk_db_fold2_position_order): uint32
+        [nk, 64 * sketchsize64], per k a permutation (the identity under option "fold2_sort" 0)."""
+        out = np.empty((self.nk, 64 * self.sketchsize64), dtype=np.uint32)
+        _lib.check(_lib.lib().ppk_db_fold2_position_order(self._h, C.c_void_p(out.ctypes.data), out.size),
+                   "ppk_db_fold2_position_order")
+        return out
+
     def fold2_codes(self, which):
         """One copy of the two-holder pair un-bitsliced (tests), 0 the ref side, 1 the query side: uint16
-        [n, nk, 64 * sketchsize64] codes."""
+        [n, nk, 64 * sketchsize64] codes, in stored position order (the sort of fold2_position_order() undone)."""
         planes, npad = self.fold2_planes, (self.n + 255) // 256 * 256
         raw = np.empty((self.nk, self.sketchsize64, max(planes, 1), npad), dtype=np.uint64)
         _lib.check(_lib.lib().ppk_db_fold2_read(self._h, int(which), C.c_void_p(raw.ctypes.data),
                                                 self.nk * self.sketchsize64 * planes * npad), "ppk_db_fold2_read")
-        return self._unslice_codes(raw, planes)
+        slots, order = self._unslice_codes(raw, planes), self.fold2_position_order()
+        codes = np.empty_like(slots)
+        for k in range(self.nk):
+            codes[:, k, order[k]] = slots[:, k]
+        return codes
 
     def fold2_events(self):
         """The event list of the two-holder pair (ppk_db_fold2_events_read): (offsets uint32 [npad / 32, npad / 256]

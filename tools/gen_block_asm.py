@@ -2,7 +2,7 @@
 """Generates poppunk_amd/csrc/ppk_block_asm.inc: the hand-scheduled gfx950 instruction
 stream for ONE 64-bin block (14 bit-planes) of the 4-ref x 4-query register tile, and the same
 stream for the 12, 10 and 8 planes of a rank-coded database (RANK_PLANES below), each with a "short" variant that
-leaves the top plane out (short_dma_planes).
+leaves the top plane out (short_dma_planes), and for the two-holder pair at 8 planes one that leaves two out.
 
 Why assembly: on MI355X a v_bitop3_b32 whose src0 and src1 sit in the same VGPR bank
 (register number mod 4) issues ~1.5x slower (tools/ubench_bank.hip: 4.7 vs 3.1 clk).  hipcc
@@ -42,6 +42,12 @@ def short_dma_planes(pl):
     P-plane stream has them, rescaled to P-1 planes (rounded half up): 12 -> (1, 3, 6, 8), 10 -> (1, 4, 6),
     8 -> (1, 3, 4)."""
     return tuple((2 * p * (pl - 1) + pl) // (2 * pl) for p in RANK_PLANES[pl][1])
+
+
+def shorter_dma_planes(pl, fewer):
+    """The same rule for a stream that leaves `fewer` top planes out (the two-holder pair's 6-plane stream, fewer = 2:
+    8 -> (1, 2, 4)); fewer = 1 is short_dma_planes."""
+    return tuple((2 * p * (pl - fewer) + pl) // (2 * pl) for p in RANK_PLANES[pl][1])
 
 
 def prio_levels(bb, v):
@@ -301,6 +307,22 @@ def main():
             write_macro(f, "PPK_BLOCK_DMA_SEL_ASM_Q32_P%d" % pl,
                         ["s_bitcmp1_b32 %[sh], %[bk]", "s_cbranch_scc1 .Lppk_short_%="] + full +
                         ["s_branch .Lppk_done_%=", ".Lppk_short_%=:"] + short + [".Lppk_done_%=:"])
+        # The two-holder pair (dist_kernel_v2_fold2): its positions are sorted by code span at creation, so most blocks
+        # span at most 2^6 codes and planes 6 and 7 are zero there.  Three streams in the one statement: bit %[bk] of
+        # %[sh2] picks the 6-plane stream, else bit %[bk] of %[sh] the 7-plane one, else all 8 (every set bit of %[sh2]
+        # is set in %[sh]; the commonest case is tested first).
+        pl = 8
+        assert shorter_dma_planes(pl, 1) == short_dma_planes(pl)
+        full = gen(256, 4, dma_planes=list(RANK_PLANES[pl][1]), bb=pl)
+        short = gen(256, 4, dma_planes=list(short_dma_planes(pl)), bb=pl - 1)
+        six = gen(256, 4, dma_planes=list(shorter_dma_planes(pl, 2)), bb=pl - 2)
+        f.write("// %d planes, the two-holder pair: the full block, the 7-plane one (flag in sh) or the 6-plane one (flag in\n"
+                "// sh2): the planes left out are zero there and are neither read nor compared\n" % pl)
+        write_macro(f, "PPK_BLOCK_DMA_SEL3_ASM_Q32_P%d" % pl,
+                    ["s_bitcmp1_b32 %[sh2], %[bk]", "s_cbranch_scc1 .Lppk_six_%=",
+                     "s_bitcmp1_b32 %[sh], %[bk]", "s_cbranch_scc1 .Lppk_short_%="] + full +
+                    ["s_branch .Lppk_done_%=", ".Lppk_short_%=:"] + short +
+                    ["s_branch .Lppk_done_%=", ".Lppk_six_%=:"] + six + [".Lppk_done_%=:"])
     if "--experiments" not in sys.argv[1:]:
         return
     # measured-and-rejected shapes: generated on demand, not tracked (tools/ubench_pipe.hip needs them)
