@@ -266,6 +266,30 @@ int ppk_db_fold2_read(const ppk_db *db, int which, uint64_t *out, size_t words);
 size_t ppk_db_fold2_events(const ppk_db *db, size_t *n_buckets);
 int ppk_db_fold2_events_read(const ppk_db *db, uint32_t *off, size_t n_off, uint16_t *ev, size_t n_ev);
 size_t ppk_db_rank_counts(const ppk_db *db, uint32_t *out, size_t cap);
+/* The holder pair, built BESIDE the two-holder pair (option "rank_foldh", PPK_RANK_FOLDH, default 1, read at creation; 0
+ * never, 2 whenever the caps allow -- tests; 0 at launch leaves a built pair unread): every value with at most H holders
+ * at its (k, bin) position is coded 0 on the ref side and 1 on the query side, and only the values with more than H
+ * holders keep codes 2 + rank.  The positions of each k are sorted by E_H = (values with more than H holders) + 2,
+ * descending, ties by stored position; a block of 64 slots then spans at most 16 codes and the tile kernel compares 4, 3
+ * (at most 8 codes) or 2 (at most 4) of the chunk's 8 planes (option "foldh_min_planes", PPK_FOLDH_MIN_PLANES, default 2,
+ * read at launch: 3 or 4 keep every block at that many or more).  What a (pair, k) is owed -- its matches on values with
+ * 2 .. H holders -- is found once, at creation, by comparing a temporary pair that codes those values alone, and kept as
+ * 32-bit entries hi % 256 | (lo % 32) << 8 | k << 13 | count << 16 in the buckets of the two-holder pair's events; the
+ * tile kernel adds its tile's entries to the counts before the fit, so every count and every bit is that of the raw
+ * planes.  H is the smallest of 4, 8, ... 256 (option "foldh_holders", PPK_FOLDH_HOLDERS, default 0; another value
+ * forces that H) whose sorted blocks fit 16 codes and, under the default rule, whose stream plane sum is at most 0.6 of
+ * the two-holder pair's on a self job of at least four rounds of tiles; more entries than a sixteenth of the self job's
+ * (pair, k) leave the database without the pair ("rank_foldh" 2: more than all of them).  Caps: those of the two-holder
+ * pair, fewer than 2^24 samples, at most 1 024 shared values per position.
+ * ppk_db_foldh_holders: H, 0 without the pair.  ppk_db_foldh_stream_planes / _position_order / _read: as their fold2_
+ * namesakes (planes 4 .. 7 of the 8 read back are zero).  ppk_db_foldh_entries / _entries_read: as ppk_db_fold2_events /
+ * _events_read, 32 bits per entry. */
+unsigned ppk_db_foldh_holders(const ppk_db *db);
+int ppk_db_foldh_stream_planes(const ppk_db *db, uint8_t *out, size_t cap);
+int ppk_db_foldh_position_order(const ppk_db *db, uint32_t *out, size_t cap);
+int ppk_db_foldh_read(const ppk_db *db, int which, uint64_t *out, size_t words);
+size_t ppk_db_foldh_entries(const ppk_db *db, size_t *n_buckets);
+int ppk_db_foldh_entries_read(const ppk_db *db, uint32_t *off, size_t n_off, uint32_t *ent, size_t n_ent);
 
 /* Number of distance rows for rows q in [q_begin, q_end) (self: n_qry == 0). */
 size_t ppk_rows_in_band(size_t n_ref, size_t n_qry, size_t q_begin, size_t q_end);

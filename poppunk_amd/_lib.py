@@ -172,6 +172,12 @@ SIGNATURES = {
     "ppk_db_fold2_events": (_sz, [_vp, C.POINTER(C.c_size_t)]),
     "ppk_db_fold2_events_read": (C.c_int, [_vp, _vp, _sz, _vp, _sz]),
     "ppk_db_rank_counts": (_sz, [_vp, _vp, _sz]),
+    "ppk_db_foldh_holders": (C.c_uint, [_vp]),
+    "ppk_db_foldh_stream_planes": (C.c_int, [_vp, _vp, _sz]),
+    "ppk_db_foldh_position_order": (C.c_int, [_vp, _vp, _sz]),
+    "ppk_db_foldh_read": (C.c_int, [_vp, C.c_int, _vp, _sz]),
+    "ppk_db_foldh_entries": (_sz, [_vp, C.POINTER(C.c_size_t)]),
+    "ppk_db_foldh_entries_read": (C.c_int, [_vp, _vp, _sz, _vp, _sz]),
     "ppk_rows_in_band": (_sz, [_sz, _sz, _sz, _sz]),
     "ppk_band_split": (C.c_int, [_sz, _sz, C.c_int, _szp]),
     "ppk_dist_dev": (C.c_int, [_vp, _vp, _i32p, _f32p, _sz, C.c_int, _sz, _sz, _vp, _vp, _vp]),

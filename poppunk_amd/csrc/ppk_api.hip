@@ -51,6 +51,9 @@ const OptionEntry kOptions[] = {
     {"rank_fold2", "PPK_RANK_FOLD2", &PpkConfig::rank_fold2},
     {"fold2_sort", "PPK_FOLD2_SORT", &PpkConfig::fold2_sort},
     {"fold2_min_planes", "PPK_FOLD2_MIN_PLANES", &PpkConfig::fold2_min_planes},
+    {"rank_foldh", "PPK_RANK_FOLDH", &PpkConfig::rank_foldh},
+    {"foldh_holders", "PPK_FOLDH_HOLDERS", &PpkConfig::foldh_holders},
+    {"foldh_min_planes", "PPK_FOLDH_MIN_PLANES", &PpkConfig::foldh_min_planes},
     {"lds_table", "PPK_LDS_TABLE", &PpkConfig::lds_table},
     {"ksplit", "PPK_KSPLIT", &PpkConfig::ksplit},
     {"ksplit_slices", "PPK_KSPLIT_SLICES", &PpkConfig::ksplit_slices},
@@ -344,6 +347,83 @@ extern "C" int ppk_band_split(size_t n_ref, size_t n_qry, int n_parts, size_t *b
 }
 
 // ---- resident sketch database --------------------------------------------------
+// The holder pair (ppk_db::d_foldhR ...), tried where the two-holder pair has been (whether or not its event cap held).  The choice is a pure function
+// of the count pass's figures and the options: the smallest H of the ladder 4, 8, ... 256 (option "foldh_holders": that
+// H alone) for which, with each k's positions sorted by E_H (descending, ties by stored position), every block of 64
+// slots spans at most 16 codes -- and, under the default rule, the stream plane sum (2, 3 or 4 per block) is at most 0.6
+// of the two-holder pair's and the self job runs at least four rounds of tiles (`four_rounds`): a smaller saving does
+// not pay for the creation pass.  Option "rank_foldh" 2 takes the first H whose blocks fit, and lifts the cap on the
+// entries from a sixteenth of the (pair, k) to all of them.  No H: the database keeps what it has.
+struct FoldhChoice {
+  int rung;                                // index into the ladder, -1: none
+  std::vector<unsigned> order;             // [k][slot]
+  std::vector<uint8_t> block_planes;       // [k][block]
+};
+static FoldhChoice ppk_choose_foldh(const std::vector<unsigned> &pos_e, size_t nk, size_t s64, int rungs, size_t fold2_sum,
+                                    bool take_any, bool four_rounds) {
+  FoldhChoice c;
+  c.rung = -1;
+  const size_t nbins = s64 * 64;
+  c.order.resize(nk * nbins);
+  c.block_planes.resize(nk * s64);
+  for (int i = 0; i < rungs; ++i) {
+    bool fits = true;
+    size_t sum = 0;
+    for (size_t k = 0; k < nk && fits; ++k) {
+      unsigned *ord = c.order.data() + k * nbins;
+      for (size_t j = 0; j < nbins; ++j) ord[j] = (unsigned)j;
+      std::stable_sort(ord, ord + nbins, [&](unsigned a, unsigned b) {
+        return pos_e[(k * nbins + a) * PPK_FOLDH_LADDER + i] > pos_e[(k * nbins + b) * PPK_FOLDH_LADDER + i];
+      });
+      for (size_t b = 0; b < s64; ++b) {
+        const unsigned widest = pos_e[(k * nbins + ord[b * 64]) * PPK_FOLDH_LADDER + i];      // (sorted: the block's first slot)
+        if (widest > PPK_FOLDH_MAX_CODES) fits = false;
+        const uint8_t planes = widest <= 4u ? 2 : widest <= 8u ? 3 : 4;
+        c.block_planes[k * s64 + b] = planes;
+        sum += planes;
+      }
+    }
+    if (fits && (take_any || (four_rounds && sum * 10 <= fold2_sum * 6))) {
+      c.rung = i;
+      return c;
+    }
+  }
+  return c;
+}
+static int ppk_try_foldh(ppk_db *db, long long opt, size_t most_shared, size_t fold2_sum, bool four_rounds, hipStream_t s) {
+  const size_t nk = db->nk, s64 = db->s64, n = db->n;
+  if (nk > PPK_FOLD2_MAX_NK || s64 > 32 || nk >= PPK_RANK_SHORT_WORDS || n >= ((size_t)1 << 24) || most_shared > PPK_FOLDH_SLOTS) return PPK_OK;
+  unsigned ladder[PPK_FOLDH_LADDER];
+  for (int i = 0; i < PPK_FOLDH_LADDER; ++i) ladder[i] = 4u << i;
+  const long long forced = ppk_config().foldh_holders.load();
+  if (forced > 0) ladder[0] = (unsigned)(forced < 65534 ? forced : 65534);
+  unsigned *d_twice = nullptr;
+  uint16_t *d_holders = nullptr;
+  std::vector<unsigned> pos_e;
+  int rc = ppk_foldh_count(db, ladder, &d_twice, &d_holders, &pos_e, s);
+  if (rc != PPK_OK || pos_e.empty()) return rc;
+  FoldhChoice c = ppk_choose_foldh(pos_e, nk, s64, forced > 0 ? 1 : PPK_FOLDH_LADDER, fold2_sum, opt == 2, four_rounds);
+  if (c.rung >= 0) {
+    db->foldh_order.swap(c.order);
+    db->foldh_block_planes.swap(c.block_planes);
+    const size_t pair_k = n * (n - 1) / 2 * nk;
+    rc = ppk_build_foldh(db, ladder[c.rung], d_twice, d_holders, opt == 2 ? pair_k : pair_k / 16, s);
+    if (rc == PPK_OK && db->foldh_planes)
+      for (size_t k = 0; k < nk; ++k)
+        for (size_t b = 0; b < s64; ++b) {
+          if (db->foldh_block_planes[k * s64 + b] <= 3) db->foldh_three[k] |= 1u << b;
+          if (db->foldh_block_planes[k * s64 + b] <= 2) db->foldh_two[k] |= 1u << b;
+        }
+  }
+  if (!db->foldh_planes) {
+    db->foldh_order.clear();
+    db->foldh_block_planes.clear();
+  }
+  (void)hipFree(d_twice);
+  (void)hipFree(d_holders);
+  return rc;
+}
+
 extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t nk,
                              size_t sketchsize64, size_t bbits, const uint16_t *clu,
                              int src_on_device, void *stream, ppk_db **out) {
@@ -383,6 +463,15 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   for (unsigned &w : db->fold2_short) w = 0;
   for (unsigned &w : db->fold2_seven) w = 0;
   for (unsigned &w : db->fold2_six) w = 0;
+  db->d_foldhR = db->d_foldhQ = nullptr;
+  db->d_foldh_ent = nullptr;
+  db->d_foldh_off = nullptr;
+  db->foldh_planes = 0;
+  db->foldh_holders = 0;
+  db->foldh_qt = db->foldh_rt = 0;
+  db->foldh_entries = 0;
+  for (unsigned &w : db->foldh_three) w = 0;
+  for (unsigned &w : db->foldh_two) w = 0;
   const size_t cols = nk * db->words;
   const size_t in_bytes = n * cols * sizeof(uint64_t);
   const size_t out_bytes = db->npad * cols * sizeof(uint64_t);
@@ -503,6 +592,20 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
             }
           db->rank_planes = planes;
         }
+        // The holder pair beside it (option "rank_foldh"), also where a (pair, k) had more events than the two-holder
+        // pair's field holds: its counts have no such cap.  (count_e[0] - 2: the most shared values of any position;
+        // fold2_sum: what the two-holder pair streams over its sorted blocks, 8 / 7 / 6 planes each.)
+        if (const long long foldh_opt = ppk_config().rank_foldh.load(); rc == PPK_OK && foldh_opt != 0 && flags_fit) {
+          size_t fold2_sum = 0;
+          for (size_t k = 0; k < nk; ++k)
+            for (size_t b = 0; b < sketchsize64; ++b) {
+              unsigned widest = 0;
+              for (size_t i = 0; i < 64; ++i) widest = std::max(widest, pos_e2[k * nbins + db->fold2_order[k * nbins + b * 64 + i]]);
+              fold2_sum += widest <= 64u ? 6 : widest <= 128u ? 7 : 8;
+            }
+          rc = ppk_try_foldh(db, foldh_opt, count_e[0] - 2u, fold2_sum, self_tiles >= 4 * (size_t)ppk_geometry(device_id).tile_slots, s);
+          if (rc == PPK_OK && db->foldh_planes) db->rank_planes = planes;
+        }
       }
       if (rc == PPK_OK && !db->fold2_planes && planes_fold && fold_opt != 0 && (fold_opt == 2 || sum_e < sum_d)) {
         // (a device too full for the pair falls back to the injective copy, and from there to the raw planes)
@@ -557,6 +660,7 @@ extern "C" void ppk_db_destroy(ppk_db *db) {
   if (db->d_foldQ) (void)hipFree(db->d_foldQ);
   for (void *ptr : {(void *)db->d_fold2R, (void *)db->d_fold2Q, (void *)db->d_fold2_ev, (void *)db->d_fold2_off})
     if (ptr) (void)hipFree(ptr);
+  ppk_drop_foldh(db);
   if (db->d_clu) (void)hipFree(db->d_clu);
   delete db;
 }
@@ -663,6 +767,51 @@ extern "C" int ppk_db_fold2_position_order(const ppk_db *db, uint32_t *out, size
   return PPK_OK;
 }
 
+extern "C" unsigned ppk_db_foldh_holders(const ppk_db *db) { return db && db->foldh_planes ? db->foldh_holders : 0u; }
+extern "C" int ppk_db_foldh_stream_planes(const ppk_db *db, uint8_t *out, size_t cap) {
+  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_stream_planes: NULL argument");
+  if (!db->foldh_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_foldh_stream_planes: the database has no holder pair");
+  if (cap < db->nk * db->s64) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_stream_planes: `cap` is below nk * sketchsize64");
+  const long long min_planes = ppk_config().rank_short.load() != 0 ? ppk_config().foldh_min_planes.load() : 4;
+  for (size_t i = 0; i < db->nk * db->s64; ++i) {
+    const uint8_t planes = db->foldh_block_planes[i];
+    out[i] = min_planes >= 4 ? (uint8_t)4 : planes < min_planes ? (uint8_t)min_planes : planes;
+  }
+  return PPK_OK;
+}
+extern "C" int ppk_db_foldh_position_order(const ppk_db *db, uint32_t *out, size_t cap) {
+  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_position_order: NULL argument");
+  if (!db->foldh_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_foldh_position_order: the database has no holder pair");
+  if (cap < db->foldh_order.size()) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_position_order: `cap` is below nk * 64 * sketchsize64");
+  for (size_t i = 0; i < db->foldh_order.size(); ++i) out[i] = db->foldh_order[i];
+  return PPK_OK;
+}
+extern "C" int ppk_db_foldh_read(const ppk_db *db, int which, uint64_t *out, size_t words) {
+  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_read: NULL argument");
+  if (which != 0 && which != 1) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_read: `which` is 0 (ref side) or 1 (query side)");
+  if (!db->foldh_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_foldh_read: the database has no holder pair");
+  if (words != db->nk * db->s64 * (size_t)db->foldh_planes * db->npad)
+    return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_read: `words` is not nk * sketchsize64 * 8 * padded samples");
+  DeviceGuard guard(db->device);
+  PPK_HIP(hipDeviceSynchronize());
+  PPK_HIP(hipMemcpy(out, which ? db->d_foldhQ : db->d_foldhR, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return PPK_OK;
+}
+extern "C" size_t ppk_db_foldh_entries(const ppk_db *db, size_t *n_buckets) {
+  if (n_buckets) *n_buckets = db && db->foldh_planes ? (size_t)db->foldh_qt * db->foldh_rt : 0;
+  return db && db->foldh_planes ? db->foldh_entries : 0;
+}
+extern "C" int ppk_db_foldh_entries_read(const ppk_db *db, uint32_t *off, size_t n_off, uint32_t *ent, size_t n_ent) {
+  if (!db || !off) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_entries_read: NULL argument");
+  if (!db->foldh_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_foldh_entries_read: the database has no holder pair");
+  if (n_off != (size_t)db->foldh_qt * db->foldh_rt + 1 || n_ent != db->foldh_entries || (n_ent && !ent))
+    return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_entries_read: sizes are buckets + 1 and entries (ppk_db_foldh_entries)");
+  DeviceGuard guard(db->device);
+  PPK_HIP(hipDeviceSynchronize());
+  PPK_HIP(hipMemcpy(off, db->d_foldh_off, n_off * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (n_ent) PPK_HIP(hipMemcpy(ent, db->d_foldh_ent, n_ent * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return PPK_OK;
+}
 extern "C" size_t ppk_db_fold2_events(const ppk_db *db, size_t *n_buckets) {
   if (n_buckets) *n_buckets = db && db->fold2_planes ? (size_t)db->fold2_qt * db->fold2_rt : 0;
   return db && db->fold2_planes ? db->fold2_events : 0;

@@ -558,6 +558,267 @@ fold2_check_kernel(const uint16_t *__restrict__ ev, const unsigned *__restrict__
   }
 }
 
+// ---- the holder pair (ppk_db::d_foldhR ...) ---------------------------------------------------------------------------
+// Holder counts.  One workgroup per (k, 64-bin block, byte g) = 8 positions, as rank_code_kernel: a first pass over the
+// samples leaves the bitmap of the values at least two samples hold (the position's SHARED values), a prefix popcount
+// ranks them, and a second pass counts every shared value's holders in an LDS counter named by its rank (the caller
+// has checked that no position has more than PPK_FOLDH_SLOTS shared values).  Out: the bitmap, twice[position][512];
+// the counts in rank order, saturated at 65 535, holders[position][PPK_FOLDH_SLOTS]; and per position and bound H of
+// `ladder` E_H = (values with more than H holders) + 2, pos_e[position][PPK_FOLDH_LADDER].
+struct FoldhLadder {
+  unsigned h[PPK_FOLDH_LADDER];
+};
+__device__ __forceinline__ void foldh_values(const uint64_t *src, size_t npad, size_t smp, int g, uint32_t (&v)[8]) {
+  uint32_t byte[RANK_BB];
+#pragma unroll
+  for (int b = 0; b < RANK_BB; ++b) byte[b] = (uint32_t)(src[(size_t)b * npad + smp] >> (8 * g)) & 0xffu;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    v[j] = 0;
+#pragma unroll
+    for (int b = 0; b < RANK_BB; ++b) v[j] |= ((byte[b] >> j) & 1u) << b;
+  }
+}
+// 32 threads per position (t = their index), 16 consecutive dwords each: before[i] = set bits below dword i
+__device__ __forceinline__ void foldh_rank_bitmap(const uint32_t *bm, uint16_t *bef, int t) {
+  uint32_t sum = 0;
+  for (int w = 0; w < RANK_BMW / 32; ++w) sum += __popc(bm[t * (RANK_BMW / 32) + w]);
+  uint32_t incl = sum;
+#pragma unroll
+  for (int d = 1; d < 32; d <<= 1) {
+    const uint32_t up = __shfl_up(incl, d, 32);
+    if (t >= d) incl += up;
+  }
+  uint32_t run = incl - sum;
+  for (int w = 0; w < RANK_BMW / 32; ++w) {
+    bef[t * (RANK_BMW / 32) + w] = (uint16_t)run;
+    run += __popc(bm[t * (RANK_BMW / 32) + w]);
+  }
+}
+__global__ void __launch_bounds__(256)
+foldh_count_kernel(const uint64_t *__restrict__ skT, unsigned *__restrict__ twice_out, uint16_t *__restrict__ holders,
+                   unsigned *__restrict__ pos_e, size_t n, size_t npad, const FoldhLadder ladder) {
+  constexpr int SLOTS = PPK_FOLDH_SLOTS;
+  __shared__ uint32_t bitmap[8][RANK_BMW];
+  __shared__ uint32_t twice[8][RANK_BMW];
+  __shared__ uint16_t before[8][RANK_BMW];
+  __shared__ uint32_t cnt[8][SLOTS];
+  const int g = blockIdx.x & 7;
+  const size_t kb = blockIdx.x >> 3;            // k * s64 + block
+  const uint64_t *src = skT + kb * RANK_BB * npad;
+  for (int i = threadIdx.x; i < 8 * RANK_BMW; i += 256) {
+    (&bitmap[0][0])[i] = 0;
+    (&twice[0][0])[i] = 0;
+  }
+  for (int i = threadIdx.x; i < 8 * SLOTS; i += 256) (&cnt[0][0])[i] = 0;
+  __syncthreads();
+  for (size_t smp = threadIdx.x; smp < n; smp += 256) {
+    uint32_t v[8];
+    foldh_values(src, npad, smp, g, v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t bit = 1u << (v[j] & 31u);
+      const uint32_t old = atomicOr(&bitmap[j][v[j] >> 5], bit);
+      if (old & bit) atomicOr(&twice[j][v[j] >> 5], bit);
+    }
+  }
+  __syncthreads();
+  const int pj = threadIdx.x >> 5, t = threadIdx.x & 31;
+  foldh_rank_bitmap(twice[pj], before[pj], t);
+  __syncthreads();
+  for (size_t smp = threadIdx.x; smp < n; smp += 256) {
+    uint32_t v[8];
+    foldh_values(src, npad, smp, g, v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t w = v[j] >> 5, bit = 1u << (v[j] & 31u);
+      if (twice[j][w] & bit) {
+        const uint32_t slot = before[j][w] + __popc(twice[j][w] & (bit - 1u));
+        if (slot < (uint32_t)SLOTS) atomicAdd(&cnt[j][slot], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  const size_t pos = kb * 64 + (size_t)(g * 8 + pj);
+  unsigned above[PPK_FOLDH_LADDER];
+#pragma unroll
+  for (int i = 0; i < PPK_FOLDH_LADDER; ++i) above[i] = 0;
+  for (int sl = t; sl < SLOTS; sl += 32) {
+    const uint32_t c = cnt[pj][sl];
+    holders[pos * SLOTS + sl] = (uint16_t)(c < 65535u ? c : 65535u);
+#pragma unroll
+    for (int i = 0; i < PPK_FOLDH_LADDER; ++i) above[i] += c > ladder.h[i] ? 1u : 0u;
+  }
+  for (int w = t; w < RANK_BMW; w += 32) twice_out[pos * RANK_BMW + w] = twice[pj][w];
+#pragma unroll
+  for (int i = 0; i < PPK_FOLDH_LADDER; ++i) {
+#pragma unroll
+    for (int d = 16; d > 0; d >>= 1) above[i] += __shfl_down(above[i], d, 32);
+    if (t == 0) pos_e[pos * PPK_FOLDH_LADDER + i] = above[i] + 2u;
+  }
+}
+
+// Codes.  Same grid; reads the count pass's bitmap and holder counts back.  Per position the shared values split in two
+// classes, each ranked in value order: KEPT (more than H holders) and FOLDED (2 .. H).  Two codes per (position, sample):
+//   kept_out  (one byte, for fold2_slice_kernel): 2 + rank of a kept value, 0 for every other -- the holder pair;
+//   owed_out  (16 bits, for foldh_slice14_kernel): 2 + rank of a folded value, 0 for every other -- the temporary pair,
+//             whose compare counts exactly the matches the holder pair cannot see.
+// Padding samples get 0 in both.
+__global__ void __launch_bounds__(256)
+foldh_code_kernel(const uint64_t *__restrict__ skT, const unsigned *__restrict__ twice_in, const uint16_t *__restrict__ holders,
+                  uint8_t *__restrict__ kept_out, uint16_t *__restrict__ owed_out, size_t n, size_t npad, unsigned H) {
+  constexpr int SLOTS = PPK_FOLDH_SLOTS;
+  __shared__ uint32_t twice[8][RANK_BMW];
+  __shared__ uint16_t before[8][RANK_BMW];
+  __shared__ uint16_t code[8][SLOTS];      // bit 15: kept; below it the rank within the class
+  const int g = blockIdx.x & 7;
+  const size_t kb = blockIdx.x >> 3;
+  const uint64_t *src = skT + kb * RANK_BB * npad;
+  const int pj = threadIdx.x >> 5, t = threadIdx.x & 31;
+  const size_t pos = kb * 64 + (size_t)(g * 8 + pj);
+  for (int w = t; w < RANK_BMW; w += 32) twice[pj][w] = twice_in[pos * RANK_BMW + w];
+  __syncthreads();
+  foldh_rank_bitmap(twice[pj], before[pj], t);
+  {
+    // thread t ranks slots [t * 32, t * 32 + 32) (slots past the position's shared values hold 0 holders: never read)
+    constexpr int PER = SLOTS / 32;
+    uint32_t kept = 0, folded = 0;
+    for (int i = 0; i < PER; ++i) {
+      const uint32_t c = holders[pos * SLOTS + t * PER + i];
+      kept += c > H ? 1u : 0u;
+      folded += c >= 2u && c <= H ? 1u : 0u;
+    }
+    uint32_t packed = kept | (folded << 16), incl = packed;
+#pragma unroll
+    for (int d = 1; d < 32; d <<= 1) {
+      const uint32_t up = __shfl_up(incl, d, 32);
+      if (t >= d) incl += up;
+    }
+    uint32_t run_k = (incl - packed) & 0xffffu, run_f = (incl - packed) >> 16;
+    for (int i = 0; i < PER; ++i) {
+      const uint32_t c = holders[pos * SLOTS + t * PER + i];
+      if (c > H) code[pj][t * PER + i] = (uint16_t)(0x8000u | run_k++);
+      else code[pj][t * PER + i] = (uint16_t)(c >= 2u ? run_f++ : 0x7fffu);
+    }
+  }
+  __syncthreads();
+  for (size_t smp = threadIdx.x; smp < npad; smp += 256) {
+    uint32_t ck[8] = {0, 0, 0, 0, 0, 0, 0, 0}, co[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (smp < n) {
+      uint32_t v[8];
+      foldh_values(src, npad, smp, g, v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const uint32_t w = v[j] >> 5, bit = 1u << (v[j] & 31u);
+        if (twice[j][w] & bit) {
+          const uint32_t slot = before[j][w] + __popc(twice[j][w] & (bit - 1u));
+          const uint32_t c = slot < (uint32_t)SLOTS ? code[j][slot] : 0x7fffu;
+          if (c & 0x8000u) ck[j] = 2u + (c & 0x7fffu);
+          else if (c != 0x7fffu) co[j] = 2u + c;
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const size_t at = (kb * 64 + (size_t)(g * 8 + j)) * npad + smp;
+      kept_out[at] = (uint8_t)ck[j];
+      owed_out[at] = (uint16_t)co[j];
+    }
+  }
+}
+
+// The temporary pair in the raw 14-plane layout, positions in stored order: [k][block * 14 + plane][npad], byte g of
+// both copies per workgroup and 256 samples (fold2_slice_kernel for 16-bit codes).  0 is 1 on the query side.
+__global__ void __launch_bounds__(256)
+foldh_slice14_kernel(const uint16_t *__restrict__ codes, uint8_t *__restrict__ out, uint8_t *__restrict__ out_q, size_t n,
+                     size_t npad) {
+  const int g = blockIdx.x & 7;
+  const size_t kb = blockIdx.x >> 3;
+  const size_t smp = (size_t)blockIdx.y * 256 + threadIdx.x;
+  if (smp >= npad) return;
+  uint32_t code[8], single = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    code[j] = codes[(kb * 64 + (size_t)(g * 8 + j)) * npad + smp];
+    if (smp < n && code[j] == 0) single |= 1u << j;
+  }
+  uint8_t *dst = out + kb * (size_t)RANK_BB * npad * 8 + g, *dst_q = out_q + kb * (size_t)RANK_BB * npad * 8 + g;
+#pragma unroll
+  for (int b = 0; b < RANK_BB; ++b) {
+    uint32_t byte = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) byte |= ((code[j] >> b) & 1u) << j;
+    dst[((size_t)b * npad + smp) * 8] = (uint8_t)byte;
+    dst_q[((size_t)b * npad + smp) * 8] = (uint8_t)(b == 0 ? byte | single : byte);
+  }
+}
+
+// One band of the temporary pair's counts (the tile kernel's MODE_COUNTS rows: row * nk + k) into raw entries
+// hi | lo << 24 | k << 48 | count << 52.  One workgroup per bucket -- 32 queries from q_begin + 32 * blockIdx.y, the 256
+// refs of ref block blockIdx.x, thread t its ref -- so a bucket's count is its workgroup's total, written without an
+// atomic, and the list is appended to through ONE reservation per workgroup (a reservation per wavefront, 780 000 adds
+// to one address at the bench shape, took 8 ms).  Two passes over the bucket's 160 KB of counts: count, then write.
+struct FoldhEmit {
+  unsigned long long *raw;
+  unsigned long long *count;    // entries appended so far (may pass cap: the caller then drops the pair)
+  unsigned *bucket;             // entries per bucket (lo / 32) * rt + hi / 256
+  unsigned long long cap;
+  unsigned rt;
+};
+__global__ void __launch_bounds__(256)
+foldh_emit_kernel(const uint32_t *__restrict__ counts, size_t n, size_t q_begin, size_t q_end, size_t row_base, int nk,
+                  const FoldhEmit ev) {
+  __shared__ uint32_t part[256];
+  __shared__ unsigned long long base_s;
+  const size_t q0 = q_begin + (size_t)blockIdx.y * 32, rf = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if ((size_t)blockIdx.x * 256 + 255 <= q0) return;      // (workgroup-uniform: no ref above the bucket's first query)
+  const size_t q1 = q0 + 32 < q_end ? q0 + 32 : q_end;
+  uint32_t mine = 0;
+  if (rf < n)
+    for (size_t qq = q0; qq < q1 && qq < rf; ++qq) {
+      const uint32_t *c = counts + (qq * n - (qq * (qq + 1)) / 2 + (rf - qq - 1) - row_base) * (size_t)nk;
+      for (int k = 0; k < nk; ++k) mine += c[k] != 0 ? 1u : 0u;
+    }
+  part[threadIdx.x] = mine;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const uint32_t up = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0u;
+    __syncthreads();
+    part[threadIdx.x] += up;
+    __syncthreads();
+  }
+  const uint32_t total = part[255];
+  if (total == 0) return;      // (workgroup-uniform)
+  if (threadIdx.x == 0) {
+    base_s = atomicAdd(ev.count, (unsigned long long)total);
+    ev.bucket[(size_t)(q0 >> 5) * ev.rt + blockIdx.x] = total;
+  }
+  __syncthreads();
+  unsigned long long at = base_s + (part[threadIdx.x] - mine);
+  if (rf < n && mine)
+    for (size_t qq = q0; qq < q1 && qq < rf; ++qq) {
+      const uint32_t *c = counts + (qq * n - (qq * (qq + 1)) / 2 + (rf - qq - 1) - row_base) * (size_t)nk;
+      for (int k = 0; k < nk; ++k)
+        if (c[k] != 0) {
+          if (at < ev.cap)
+            ev.raw[at] = (unsigned long long)rf | ((unsigned long long)qq << 24) | ((unsigned long long)k << 48) |
+                         ((unsigned long long)(c[k] & 4095u) << 52);
+          ++at;
+        }
+    }
+}
+__global__ void __launch_bounds__(256)
+foldh_scatter_kernel(const unsigned long long *__restrict__ raw, size_t total, const unsigned *__restrict__ off,
+                     unsigned *__restrict__ cursor, uint32_t *__restrict__ ent, unsigned rt) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const unsigned long long e = raw[i];
+  const uint32_t hi = (uint32_t)e & 0xffffffu, lo = (uint32_t)(e >> 24) & 0xffffffu, k = (uint32_t)(e >> 48) & 7u, c = (uint32_t)(e >> 52);
+  const size_t b = (size_t)(lo >> 5) * rt + (hi >> 8);
+  const unsigned at = off[b] + atomicAdd(cursor + b, 1u);
+  if (at < off[b + 1]) ent[at] = (hi & 255u) | ((lo & 31u) << 8) | (k << 13) | (c << 16);
+}
+
 // LUT[(cr*C + cq)][k][count] = log J, or +1.0 when J < 5/nbins (the point and
 // every later k are dropped from the fit; docs/sketching.rst:161-165).  Behind it, per entry, the
 // pair (E, F) = (J^a_k, J^b_k) of the all-k-usable fast path (FitCoef), NaN where the log-J entry is
@@ -1224,7 +1485,7 @@ dist_kernel_v2(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ q
                void *__restrict__ out, unsigned long long *__restrict__ n_failed,
                uint64_t *__restrict__ mask_out, const DistParams p) {
   constexpr int PL = V2_BB;      // raw planes
-  constexpr bool FOLD2 = false;
+  constexpr bool FOLD2 = false, FOLDH = false;
 #include "ppk_dist_tile.inc"
 }
 
@@ -1238,7 +1499,7 @@ dist_kernel_v2_rank(const uint64_t *__restrict__ refT, const uint64_t *__restric
                     void *__restrict__ out, unsigned long long *__restrict__ n_failed,
                     uint64_t *__restrict__ mask_out, const DistParams p) {
   constexpr int NW = 8, W = 2;
-  constexpr bool KSPLIT = false, WIDE = false, EXP = false, FOLD2 = false;
+  constexpr bool KSPLIT = false, WIDE = false, EXP = false, FOLD2 = false, FOLDH = false;
 #include "ppk_dist_tile.inc"
 }
 
@@ -1253,7 +1514,23 @@ dist_kernel_v2_fold2(const uint64_t *__restrict__ refT, const uint64_t *__restri
                      void *__restrict__ out, unsigned long long *__restrict__ n_failed,
                      uint64_t *__restrict__ mask_out, const DistParams p) {
   constexpr int NW = 8, W = 2, PL = 8;
-  constexpr bool KSPLIT = false, WIDE = false, EXP = false, FOLD2 = true;
+  constexpr bool KSPLIT = false, WIDE = false, EXP = false, FOLD2 = true, FOLDH = false;
+#include "ppk_dist_tile.inc"
+}
+
+// The same kernel on the holder pair (ppk_db::d_foldhR / d_foldhQ, an 8-plane chunk whose planes 4 .. 7 are zero):
+// FOLDH swaps the three streams for the 4- / 3- / 2-plane ones and the correction block for the one that adds the
+// database's 12-bit entries (DistParams::fold2_ev / fold2_off carry d_foldh_ent / d_foldh_off; rank_short / fold2_six
+// the 3- and the 2-plane flags).  A kernel of its own name again: every other symbol stays the code it was.
+template <int MODE>
+__global__ void __launch_bounds__(8 * 64, 4)
+dist_kernel_v2_foldh(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ qryT,
+                     const double *__restrict__ lut, const uint16_t *__restrict__ ref_clu,
+                     const uint16_t *__restrict__ qry_clu, const float *__restrict__ rtab,
+                     void *__restrict__ out, unsigned long long *__restrict__ n_failed,
+                     uint64_t *__restrict__ mask_out, const DistParams p) {
+  constexpr int NW = 8, W = 2, PL = 8;
+  constexpr bool KSPLIT = false, WIDE = false, EXP = false, FOLD2 = true, FOLDH = true;
 #include "ppk_dist_tile.inc"
 }
 
@@ -1794,35 +2071,42 @@ int launch_wide(int dev, const PpkGeometry &geo, const DistArgs &a, DistParams &
 // samples, one from each copy.  A rectangular job of a handle against itself has the pairs (r, r), where a value
 // with a single holder must match itself: it reads the injective copy if there is one, else the raw planes.
 // The two-holder pair (d_fold2R / d_fold2Q, always 8 planes) serves the same job with the event list beside it.
+// The holder pair (d_foldhR / d_foldhQ, an 8-plane chunk of which at most 4 planes are compared) serves it before both.
 // Returns the planes of the copy this band reads (0: the raw planes) and which copy that is: 0 the injective one, 1 the
-// folded pair, 2 the two-holder pair.
+// folded pair, 2 the two-holder pair, 3 the holder pair.
 int coded_planes(const ppk_db *ref, const ppk_db *qry, const DistParams &p, int *fold) {
   const bool coded = (p.self || qry == ref) && !p.k_split && ppk_config().rank_planes.load() != 0;
   *fold = !(coded && p.self)                                                    ? 0
+          : ref->foldh_planes != 0 && ppk_config().rank_foldh.load() != 0       ? 3
           : ref->fold2_planes != 0 && ppk_config().rank_fold2.load() != 0       ? 2
           : ref->fold_planes != 0 && ppk_config().rank_fold.load() != 0         ? 1
                                                                                 : 0;
-  return *fold == 2 ? ref->fold2_planes : *fold == 1 ? ref->fold_planes : coded && ref->d_skR ? ref->rank_planes : 0;
+  return *fold == 3 ? ref->foldh_planes : *fold == 2 ? ref->fold2_planes : *fold == 1 ? ref->fold_planes : coded && ref->d_skR ? ref->rank_planes : 0;
 }
 template <int MODE>
 int launch_rank(const ppk_db *ref, int planes, int fold, DistArgs a, DistParams &p, size_t n_blocks, hipStream_t s) {
-  a.sk_r = fold == 2 ? ref->d_fold2R : fold ? ref->d_foldR : ref->d_skR;
-  a.sk_q = fold == 2 ? ref->d_fold2Q : fold ? ref->d_foldQ : ref->d_skR;
+  a.sk_r = fold == 3 ? ref->d_foldhR : fold == 2 ? ref->d_fold2R : fold ? ref->d_foldR : ref->d_skR;
+  a.sk_q = fold == 3 ? ref->d_foldhQ : fold == 2 ? ref->d_fold2Q : fold ? ref->d_foldQ : ref->d_skR;
   // the blocks that compare one plane fewer (option "rank_short", read here: one database runs either way)
-  const unsigned *flags = fold == 2 ? ref->fold2_seven : fold ? ref->fold_short : ref->rank_short;
-  const bool use_short = ppk_config().rank_short.load() != 0;
+  const unsigned *flags = fold == 3 ? ref->foldh_three : fold == 2 ? ref->fold2_seven : fold ? ref->fold_short : ref->rank_short;
+  // (the holder pair: option "foldh_min_planes" 4 keeps every block at 4 planes, 3 the 2-plane blocks at 3)
+  const long long foldh_min = ppk_config().foldh_min_planes.load();
+  const bool use_short = ppk_config().rank_short.load() != 0 && !(fold == 3 && foldh_min > 3);
   for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.rank_short[k] = use_short ? flags[k] : 0u;
-  p.fold2_ev = fold == 2 ? ref->d_fold2_ev : nullptr;
-  p.fold2_off = fold == 2 ? ref->d_fold2_off : nullptr;
-  p.fold2_rt = fold == 2 ? ref->fold2_rt : 0u;
+  // (the holder pair's 32-bit entries travel in the event list's fields: dist_kernel_v2_foldh reads them as such)
+  p.fold2_ev = fold == 3 ? reinterpret_cast<const uint16_t *>(ref->d_foldh_ent) : fold == 2 ? ref->d_fold2_ev : nullptr;
+  p.fold2_off = fold == 3 ? ref->d_foldh_off : fold == 2 ? ref->d_fold2_off : nullptr;
+  p.fold2_rt = fold == 3 ? ref->foldh_rt : fold == 2 ? ref->fold2_rt : 0u;
   // the two-holder pair: the blocks that compare 6 planes (option "fold2_min_planes", read here; 7 keeps them at 7)
   const bool use_six = fold == 2 && use_short && ppk_config().fold2_min_planes.load() <= 6;
-  for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.fold2_six[k] = use_six ? ref->fold2_six[k] : 0u;
-  const auto kernel = fold == 2      ? &dist_kernel_v2_fold2<MODE>
+  const bool use_two = fold == 3 && use_short && foldh_min <= 2;
+  for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.fold2_six[k] = use_six ? ref->fold2_six[k] : use_two ? ref->foldh_two[k] : 0u;
+  const auto kernel = fold == 3      ? &dist_kernel_v2_foldh<MODE>
+                      : fold == 2    ? &dist_kernel_v2_fold2<MODE>
                       : planes == 12 ? &dist_kernel_v2_rank<12, MODE>
                       : planes == 10 ? &dist_kernel_v2_rank<10, MODE>
                                      : &dist_kernel_v2_rank<8, MODE>;
-  const std::string name = "dist_kernel_v2<256x32,lds-dma,rank " + std::to_string(planes) + (fold == 2 ? ",fold2>" : fold ? ",fold>" : ">");
+  const std::string name = "dist_kernel_v2<256x32,lds-dma,rank " + std::to_string(planes) + (fold == 3 ? ",foldh>" : fold == 2 ? ",fold2>" : fold ? ",fold>" : ">");
   return launch_kernel(kernel, dim3((unsigned)n_blocks), dim3(8 * 64), name.c_str(), a, p, s);
 }
 
@@ -2332,6 +2616,143 @@ static int launch_dist_band(const DistJob &job) {
   ppk_prof_end(s);
   PPK_HIP(hipGetLastError());
   return PPK_OK;
+}
+
+// ---- the holder pair: creation -------------------------------------------------------------------------------------------
+void ppk_drop_foldh(ppk_db *db) {
+  for (void *ptr : {(void *)db->d_foldhR, (void *)db->d_foldhQ, (void *)db->d_foldh_ent, (void *)db->d_foldh_off})
+    if (ptr) (void)hipFree(ptr);
+  db->d_foldhR = db->d_foldhQ = nullptr;
+  db->d_foldh_ent = nullptr;
+  db->d_foldh_off = nullptr;
+  db->foldh_planes = 0;
+  db->foldh_entries = 0;
+}
+int ppk_foldh_count(const ppk_db *db, const unsigned *ladder, unsigned **d_twice, uint16_t **d_holders, std::vector<unsigned> *pos_e,
+                    hipStream_t s) {
+  const size_t n_pos = db->nk * db->s64 * 64;
+  unsigned *d_e = nullptr;
+  *d_twice = nullptr;
+  *d_holders = nullptr;
+  pos_e->assign(n_pos * PPK_FOLDH_LADDER, 0u);
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(d_twice), n_pos * RANK_BMW * sizeof(unsigned));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(d_holders), n_pos * PPK_FOLDH_SLOTS * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_e), pos_e->size() * sizeof(unsigned));
+  if (e == hipSuccess) {
+    FoldhLadder l;
+    for (int i = 0; i < PPK_FOLDH_LADDER; ++i) l.h[i] = ladder[i];
+    hipLaunchKernelGGL(foldh_count_kernel, dim3((unsigned)(db->nk * db->s64 * 8)), dim3(256), 0, s, db->d_skT, *d_twice, *d_holders,
+                       d_e, db->n, db->npad, l);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(pos_e->data(), d_e, pos_e->size() * sizeof(unsigned), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (d_e) (void)hipFree(d_e);
+  if (e != hipSuccess) {      // (a device too full for the pass: no holder pair, nothing else changes)
+    (void)hipGetLastError();
+    if (*d_twice) (void)hipFree(*d_twice);
+    if (*d_holders) (void)hipFree(*d_holders);
+    *d_twice = nullptr;
+    *d_holders = nullptr;
+    pos_e->clear();
+  }
+  return PPK_OK;
+}
+// one band of the temporary pair's counts: the raw-plane tile kernel in MODE_COUNTS, ref side d_r, query side d_q
+static int foldh_counts_band(const ppk_db *db, const uint64_t *d_r, const uint64_t *d_q, size_t q_begin, size_t q_end, void *d_cnt,
+                             hipStream_t s) {
+  DistParams p = {};
+  p.self = 1;
+  p.npad_r = p.npad_q = db->npad;
+  p.n_ref = db->n;
+  p.q_begin = q_begin;
+  p.q_end = q_end;
+  p.row_base = q_begin * db->n - (q_begin * (q_begin + 1)) / 2;
+  FitCoef coef = {};
+  int32_t kmers[PPK_MAX_NK] = {};
+  fit_params(db, kmers, 0, 0, nullptr, p, coef);
+  p.n_rtiles = (db->n + 63) / 64;
+  const DistArgs a = {d_r, d_q, nullptr, nullptr, nullptr, nullptr, d_cnt, nullptr, nullptr};
+  return launch_tiles_unpacked<MODE_COUNTS>(db, db, a, p, s);
+}
+int ppk_build_foldh(ppk_db *db, unsigned H, const unsigned *d_twice, const uint16_t *d_holders, size_t max_entries, hipStream_t s) {
+  const size_t n = db->n, npad = db->npad, n_pos = db->nk * db->s64 * 64, n_kb = db->nk * db->s64;
+  const size_t copy_bytes = npad * n_kb * 8 * sizeof(uint64_t), tmp_bytes = npad * n_kb * (size_t)RANK_BB * sizeof(uint64_t);
+  const unsigned qt = (unsigned)(npad / 32), rt = (unsigned)(npad / V2_RT);
+  const size_t nb = (size_t)qt * rt, cap = max_entries ? max_entries : 1;
+  // the counts of one band: at most 512 MB, whole blocks of 256 query rows, no more than a dispatch holds
+  size_t band_q = ((size_t)512 << 20) / (n * db->nk * 4) / 256 * 256;
+  if (band_q < 256) band_q = 256;
+  if (band_q > ppk_rows_per_dispatch(db)) band_q = ppk_rows_per_dispatch(db);
+  const size_t band_rows = ppk_rows_in_band(n, 0, 0, band_q < n ? band_q : n);      // (the first band is the longest)
+  uint8_t *d_kept = nullptr;
+  uint16_t *d_owed = nullptr;
+  unsigned *d_order = nullptr, *d_cnt = nullptr;      // d_cnt: [nb] bucket counts / cursors, then the 64-bit entry counter
+  uint64_t *d_tr = nullptr, *d_tq = nullptr;
+  unsigned long long *d_raw = nullptr;
+  void *d_band = nullptr;
+  auto done = [&](int rc, bool keep) {
+    for (void *ptr : {(void *)d_kept, (void *)d_owed, (void *)d_order, (void *)d_cnt, (void *)d_tr, (void *)d_tq, (void *)d_raw, d_band})
+      if (ptr) (void)hipFree(ptr);
+    if (!keep) {
+      (void)hipGetLastError();
+      ppk_drop_foldh(db);
+    }
+    return rc;
+  };
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&db->d_foldhR), copy_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_foldhQ), copy_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_foldh_off), (nb + 1) * sizeof(unsigned));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_kept), n_pos * npad);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_owed), n_pos * npad * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_order), n_pos * sizeof(unsigned));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), (nb + 2) * sizeof(unsigned) + 8);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_tr), tmp_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_tq), tmp_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_raw), cap * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc(&d_band, band_rows * db->nk * 4 + 256);
+  if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (nb + 2) * sizeof(unsigned) + 8, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_order, db->foldh_order.data(), n_pos * sizeof(unsigned), hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return done(PPK_OK, false);      // (a device too full: the pair only buys speed)
+  const dim3 grid_pos((unsigned)(n_kb * 8)), grid_slice((unsigned)(n_kb * 8), (unsigned)(npad / 256));
+  hipLaunchKernelGGL(foldh_code_kernel, grid_pos, dim3(256), 0, s, db->d_skT, d_twice, d_holders, d_kept, d_owed, n, npad, H);
+  hipLaunchKernelGGL(fold2_slice_kernel, grid_slice, dim3(256), 0, s, d_kept, d_order, reinterpret_cast<uint8_t *>(db->d_foldhR),
+                     reinterpret_cast<uint8_t *>(db->d_foldhQ), n, npad, (int)db->s64, 8);
+  hipLaunchKernelGGL(foldh_slice14_kernel, grid_slice, dim3(256), 0, s, d_owed, reinterpret_cast<uint8_t *>(d_tr),
+                     reinterpret_cast<uint8_t *>(d_tq), n, npad);
+  e = hipGetLastError();
+  // (the entry counter sits behind the cursors, 8-byte aligned)
+  unsigned long long *d_total = reinterpret_cast<unsigned long long *>(d_cnt + ((nb + 2) & ~(size_t)1));
+  const FoldhEmit ev = {d_raw, d_total, d_cnt, (unsigned long long)cap, rt};
+  for (size_t lo = 0; e == hipSuccess && lo + 1 < n; lo += band_q) {
+    const size_t hi = lo + band_q < n ? lo + band_q : n;
+    if (ppk_rows_in_band(n, 0, lo, hi) == 0) continue;
+    const int rc = foldh_counts_band(db, d_tr, d_tq, lo, hi, d_band, s);
+    if (rc != PPK_OK) return done(rc, false);
+    hipLaunchKernelGGL(foldh_emit_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)((hi - lo + 31) / 32)), dim3(256), 0, s,
+                       static_cast<const uint32_t *>(d_band), n, lo, hi, lo * n - (lo * (lo + 1)) / 2, (int)db->nk, ev);
+    e = hipGetLastError();
+  }
+  unsigned long long total = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return done(ppk_fail(PPK_ERR_HIP, std::string("holder pair: ") + hipGetErrorString(e)), false);
+  if (total > max_entries || total >= ((unsigned long long)1 << 32)) return done(PPK_OK, false);      // too dense to pay
+  e = hipMalloc(reinterpret_cast<void **>(&db->d_foldh_ent), (total ? total : 1) * sizeof(uint32_t));
+  if (e != hipSuccess) return done(PPK_OK, false);
+  hipLaunchKernelGGL(fold2_scan_kernel, dim3(1), dim3(1024), 0, s, d_cnt, db->d_foldh_off, nb);
+  if (total)
+    hipLaunchKernelGGL(foldh_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_raw, (size_t)total,
+                       db->d_foldh_off, d_cnt, db->d_foldh_ent, rt);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return done(ppk_fail(PPK_ERR_HIP, std::string("holder pair: ") + hipGetErrorString(e)), false);
+  db->foldh_planes = 8;
+  db->foldh_holders = H;
+  db->foldh_qt = qt;
+  db->foldh_rt = rt;
+  db->foldh_entries = (size_t)total;
+  return done(PPK_OK, true);
 }
 
 // A dispatch holds fewer than 2^32 work-items: with 512-thread workgroups that is 8.4 M pair tiles, which

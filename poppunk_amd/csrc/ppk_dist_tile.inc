@@ -3,7 +3,7 @@
 // inlined from a __device__ function compiles to other code (the by-value DistParams is then read differently).
 // In scope at the point of inclusion: the kernel's arguments (refT, qryT, lut, ref_clu, qry_clu, rtab, out, n_failed,
 // mask_out, p) and the compile-time constants NW, MODE, W, KSPLIT, WIDE, EXP, FOLD2 (the two-holder pair: one block at the
-// top of the epilogue) and
+// top of the epilogue), FOLDH (with FOLD2: the holder pair -- 4 / 3 / 2-plane streams and 12-bit corrections) and
 //   PL: the bit-planes a 64-bin block is copied and compared in.  14 = the sketch's own bbits; 8, 10 or 12 on a
 //       rank-coded database (ppk_db::d_skR: every bin value replaced by its rank among the distinct values of its
 //       (k, bin) position, which keeps "equal / not equal" and so every count).  The collision adjustment and the fit
@@ -308,7 +308,12 @@
 #define PPK_HALF_STMT(SUF)                                                                                  \
   asm volatile(PPK_BLOCK_HALF_ASM_Q32##SUF : PPK_BLOCK_OPERANDS : [rp] "v"(rp), [qp] "v"(qp) \
                : "memory", PPK_BLOCK_CLOBBERS);
-          PPK_BLOCK_BY_PLANES(PPK_HALF_STMT)
+          if constexpr (FOLDH) {      // (planes 4 .. 7 of the holder pair are zero everywhere)
+            asm volatile(PPK_BLOCK_HALF_H4_ASM_Q32_P8 : PPK_BLOCK_OPERANDS : [rp] "v"(rp), [qp] "v"(qp)
+                         : "memory", PPK_BLOCK_CLOBBERS);
+          } else {
+            PPK_BLOCK_BY_PLANES(PPK_HALF_STMT)
+          }
 #undef PPK_HALF_STMT
         } else if constexpr (DMA_IN_STREAM) {
           // the in-stream variant issues the wavefront's PW pieces: PW - 1 ref pieces 8 KB apart and a LAST one that is a
@@ -336,9 +341,11 @@
                  [sb1] "s"(dbase[1]), [sb2] "s"(dbase[SB2]), [sb3] "s"(dbase[LT]), [voa] "v"(voff_ref),           \
                  [vob] "v"(vob), [xblo] "s"(xblo), [xbhi] "s"(xbhi), [sh] "s"(short_w), [bk] "s"(blk)             \
                : "memory", "scc", PPK_BLOCK_CLOBBERS);
-          // FOLD2: three streams, 8 / 7 / 6 planes, on bit blk of short_w and of six_w
-#define PPK_DMA_SEL3_STMT(SUF, SB2)                                                                               \
-  asm volatile(PPK_BLOCK_DMA_SEL3_ASM_Q32##SUF                                                                    \
+          // FOLD2: three streams, 8 / 7 / 6 planes, on bit blk of short_w and of six_w (FOLDH: 4 / 3 / 2 planes, the
+          // words then hold DistParams' flags of the holder pair)
+#define PPK_DMA_SEL3_STMT(SUF, SB2) PPK_DMA_SEL3_STMT_OF(PPK_BLOCK_DMA_SEL3_ASM_Q32##SUF, SB2)
+#define PPK_DMA_SEL3_STMT_OF(STREAM, SB2)                                                                         \
+  asm volatile(STREAM                                                                                             \
                : PPK_BLOCK_OPERANDS                                                                               \
                : [rp] "v"(rp), [qp] "v"(qp), [m00] "s"(m00), [m03] "s"(m03), [sb0] "s"(dbase[0]),                 \
                  [sb1] "s"(dbase[1]), [sb2] "s"(dbase[SB2]), [sb3] "s"(dbase[LT]), [voa] "v"(voff_ref),           \
@@ -348,6 +355,7 @@
           if constexpr (PL < V2_BB) {
             if constexpr (PL == 12) { PPK_DMA_SEL_STMT(_P12, 2) }
             else if constexpr (PL == 10) { PPK_DMA_SEL_STMT(_P10, LT) }
+            else if constexpr (FOLDH) { PPK_DMA_SEL3_STMT_OF(PPK_BLOCK_DMA_SELH_ASM_Q32_P8, LT) }
             else if constexpr (FOLD2) { PPK_DMA_SEL3_STMT(_P8, LT) }
             else { PPK_DMA_SEL_STMT(_P8, LT) }
           } else {
@@ -360,6 +368,7 @@
           }
 #undef PPK_DMA_SEL_STMT
 #undef PPK_DMA_SEL3_STMT
+#undef PPK_DMA_SEL3_STMT_OF
           // (after the last block the pieces harmlessly re-load it into the idle buffer)
           if (g + 2 < total) {
 #pragma unroll
@@ -503,7 +512,79 @@
         (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(ka));
     LateParams &p_late = *reinterpret_cast<LateParams *>(ka + V2_PARAMS_KERNARG_OFFSET);
-    if constexpr (FOLD2) {
+    if constexpr (FOLDH) {
+      // ---- the holder pair: the matches the codes cannot see ---------------------------------------------
+      // Every value with at most H holders is coded 0 / 1, so a pair that shares such values was counted short by
+      // their number at that k.  The database lists what each (pair, k) is owed as 32-bit entries -- hi % 256 |
+      // (lo % 32) << 8 | k << 13 | count << 16 -- bucketed like the two-holder pair's events (ppk_db::d_foldh_ent).
+      // The dead compare buffers take one 64-bit word per pair of the tile, five 12-bit fields (one per k; a count
+      // is at most 64 * sketchsize64 <= 2 048), 64 KB laid out so that lane l of wavefront w reads its sixteen pairs
+      // as eight conflict-free 16-byte reads -- [q][r / 2][w * 64 + l][r % 2] -- and the entries are added in with
+      // 64-bit LDS atomics.  Barriers, buckets of a strip tile and the wavefronts' exit: as for the two-holder pair.
+      static_assert(FOLD2 && PL == 8 && W == 2 && !KSPLIT && !WIDE, "the holder pair is an 8-plane whole-tile kernel");
+      static_assert(sizeof(lds) >= 8 * 512 * sizeof(u32x4), "one 64-bit word per pair of the tile");
+      const uint32_t tid = (uint32_t)wave * 64u + (uint32_t)lane_late;
+      unsigned long long *corr = reinterpret_cast<unsigned long long *>(lds);
+      u32x4 zero4;
+      zero4.x = zero4.y = zero4.z = zero4.w = 0;
+#pragma unroll
+      for (int i = 0; i < 2 * TQ; ++i) lds[tid + 512u * i] = zero4;
+      __syncthreads();
+      {
+        const unsigned *off = p_late.fold2_off;
+        const uint32_t *ents = reinterpret_cast<const uint32_t *>(p_late.fold2_ev);
+        const uint32_t frt = p_late.fold2_rt;
+        const uint32_t q_sub = (uint32_t)(q0 >> 5) & 7u;      // strip: which 32 of its ref tile's samples the tile holds
+        const int n_buckets = strip ? 8 : 1;
+        for (int i = 0; i < n_buckets; ++i) {
+          const uint32_t b = strip ? ((uint32_t)(r0 >> 5) + (uint32_t)i) * frt + (uint32_t)(q0 >> 8)
+                                   : (uint32_t)(q0 >> 5) * frt + (uint32_t)rt;
+          const uint32_t e1 = off[b + 1];
+          for (uint32_t e = off[b] + tid; e < e1; e += 512u) {
+            const uint32_t ev = ents[e], kk = (ev >> 13) & 7u;
+            uint32_t ref_l = ev & 255u, qry_l = (ev >> 8) & 31u;      // hi % 256, lo % 32
+            if (strip) {
+              if ((ref_l >> 5) != q_sub) continue;
+              const uint32_t hi_l = ref_l;
+              ref_l = 32u * (uint32_t)i + qry_l;
+              qry_l = hi_l & 31u;
+            }
+            // pair (ref_l, qry_l): wavefront qry_l / 4, q = qry_l % 4, lane (ref_l % 128) / 2, r = ref_l % 2 + 2 * (ref_l / 128)
+            const uint32_t slot = ((((qry_l & 3u) * 2u + (ref_l >> 7)) * 512u + (qry_l >> 2) * 64u + ((ref_l & 127u) >> 1)) << 1) + (ref_l & 1u);
+            if (kk < 5u)
+              __hip_atomic_fetch_add(corr + slot, (unsigned long long)(ev >> 16) << (12u * kk), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
+        }
+      }
+      __syncthreads();
+      {
+        const int cb = p_late.cnt_bits, top = p_late.nk - 1;
+#pragma unroll
+        for (int q = 0; q < TQ; ++q) {
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const u32x4 c4 = lds[tid + 512u * (2 * q + h)];
+            const uint64_t c[2] = {((uint64_t)c4.y << 32) | c4.x, ((uint64_t)c4.w << 32) | c4.z};
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              const int r = 2 * h + j;
+              if (c[j] != 0) {
+                // field k lands where the end-of-k shifts left k's count: bit cnt_bits * (nk - 1 - k)
+                uint64_t add = 0;
+#pragma unroll
+                for (int k = 0; k < 5; ++k)
+                  if (k <= top) add += ((c[j] >> (12 * k)) & 4095u) << (cb * (top - k));
+                const uint64_t v = (((uint64_t)pw[1][r][q] << 32) | pw[0][r][q]) + add;
+                pw[0][r][q] = (uint32_t)v;
+                pw[1][r][q] = (uint32_t)(v >> 32);
+              }
+            }
+          }
+        }
+      }
+      __syncthreads();      // (the table copy below lands on the words just read)
+      if (!wave_active) return;
+    } else if constexpr (FOLD2) {
       // ---- the two-holder pair: the matches the codes cannot see ------------------------------------
       // A value with exactly two holders is coded 0 / 1 like a single-holder one, so the pair (its higher holder as
       // ref, its lower as query) was counted one short at that k.  The database lists these events by (lo / 32,

@@ -76,6 +76,25 @@ struct ppk_db {
   unsigned *d_fold2_off;        // fold2_qt * fold2_rt + 1 offsets
   unsigned fold2_qt, fold2_rt;  // npad / 32, npad / 256
   size_t fold2_events;
+  // The holder pair, built BESIDE the two-holder pair where it compares far fewer planes (ppk_db_create, option
+  // "rank_foldh"): the same two copies in the same 8-plane layout, but EVERY value with at most foldh_holders (H)
+  // holders is coded 0 / 1 and only the values with more than H holders keep codes 2 + rank, so that a sorted block
+  // of 64 slots spans at most 16 codes and streams 4, 3 (bit in foldh_three[k]) or 2 (bit in foldh_two[k] as well)
+  // planes; planes 4 .. 7 are zero.  Slot i of k holds stored position foldh_order[k * 64 * s64 + i] (E_H descending,
+  // ties by stored position).  What the compare then misses is a COUNT per (pair, k): the matches on values with
+  // 2 .. H holders, found once at creation by comparing a temporary pair that codes those values alone.  Non-zero
+  // counts are 32-bit entries hi % 256 | (lo % 32) << 8 | k << 13 | count << 16, bucketed like the events:
+  // bucket b = (lo / 32) * foldh_rt + hi / 256 holds d_foldh_ent[foldh_off[b] .. foldh_off[b + 1]).
+  uint64_t *d_foldhR, *d_foldhQ;
+  int foldh_planes;               // 8 (the chunk's layout), 0 = no such pair
+  unsigned foldh_holders;         // H
+  std::vector<unsigned> foldh_order;
+  std::vector<uint8_t> foldh_block_planes;      // [k * s64 + block]: 2, 3 or 4, what the sorted block's widest position needs
+  unsigned foldh_three[PPK_RANK_SHORT_WORDS], foldh_two[PPK_RANK_SHORT_WORDS];
+  uint32_t *d_foldh_ent;
+  unsigned *d_foldh_off;          // foldh_qt * foldh_rt + 1 offsets
+  unsigned foldh_qt, foldh_rt;    // npad / 32, npad / 256
+  size_t foldh_entries;
   // what the count pass found (ppk_db_rank_counts): the maxima of D, E = S + 2 and E2 = S3 + 2 over all positions and
   // per (k, 64-bin block) -- 3 x (1 + nk * s64) words -- then PPK_RANK_EXTRA words: the most two-holder values of any
   // position, their number over all positions, and (after an attempt at the two-holder pair) whether a (pair, k) had
@@ -85,6 +104,9 @@ struct ppk_db {
 #define PPK_RANK_EXTRA 3
 #define PPK_FOLD2_SLOTS 256          // two-holder values per position the code pass has LDS slots for
 #define PPK_FOLD2_MAX_PER_PAIR 63    // events per (pair, k): a 6-bit field of the tile kernel's correction word
+#define PPK_FOLDH_SLOTS 1024         // shared values per position the holder count pass has LDS counters for
+#define PPK_FOLDH_LADDER 7           // the holder bounds the choice tries: 4, 8, ... 256
+#define PPK_FOLDH_MAX_CODES 16       // codes a sorted block of the holder pair may span (4 planes)
 #define PPK_FOLD2_MAX_NK 5           // five 6-bit fields per correction word; k in 3 bits of an event
 
 // A database whose per-pair counts the tile kernels cannot hold: more k-mer lengths than the fit tables are laid
@@ -117,6 +139,9 @@ struct PpkConfig {
   std::atomic<long long> rank_fold2{1};         // PPK_RANK_FOLD2: where coding the two-holder bin values like single-holder ones (their one match per value added back in the tile kernel's epilogue from an event list) lets a large self job compare fewer planes than both other codings, the database keeps the two-holder pair (ppk_db::d_fold2R / d_fold2Q) instead (0: never; 2: whenever the caps allow, any size, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
   std::atomic<long long> fold2_sort{1};         // PPK_FOLD2_SORT: the two-holder pair stores the positions of each k sorted by the codes they span, so that most 64-bin blocks span at most 64 codes (0: positions as stored; same bits).  Read at creation.
   std::atomic<long long> fold2_min_planes{6};   // PPK_FOLD2_MIN_PLANES: a self job on the two-holder pair compares 6 planes in the blocks that span at most 64 codes (7: such blocks compare 7, as every block spanning at most 128 does; same bits).  Read at launch.
+  std::atomic<long long> rank_foldh{1};         // PPK_RANK_FOLDH: where folding every bin value with at most H holders (their matches added back in the tile kernel's epilogue from a list of per-pair counts) cuts the two-holder pair's compare stream to 0.6 of its planes or less, the database keeps the holder pair (ppk_db::d_foldhR / d_foldhQ) beside it and self jobs read that (0: never; 2: whenever the caps allow, any size, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
+  std::atomic<long long> foldh_holders{0};      // PPK_FOLDH_HOLDERS: the holder bound H of the holder pair (0: the smallest of 4, 8, ... 256 that qualifies; any other value forces that H).  Read at creation.
+  std::atomic<long long> foldh_min_planes{2};   // PPK_FOLDH_MIN_PLANES: a self job on the holder pair compares 2 planes in the blocks that span at most 4 codes and 3 in those that span at most 8 (3, 4: no block compares fewer; same bits).  Read at launch.
   std::atomic<long long> rank_short{1};         // PPK_RANK_SHORT: a self job on a rank-coded database compares one plane fewer in the 64-bin blocks whose positions hold at most half the values the planes can code (0: every block compares all planes; same bits).  Read at launch.
   std::atomic<long long> lds_table{1};          // PPK_LDS_TABLE: interior tiles of the default sketch shape fit from the (E, F) table in LDS (0: the general statement everywhere; same bits)
   std::atomic<long long> ksplit{1200};           // PPK_KSPLIT: tile-count threshold (at 5 k) of the small-job path
@@ -263,6 +288,15 @@ int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, uint64_t *d_ou
 // counting sort and the cap check, and synchronises `s` once.  *overflow: a (pair, k) has more events than its field
 // holds (the caller drops the pair).  `n_two`: the two-holder values the count pass found.
 int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, const std::vector<unsigned> *order, bool *overflow, hipStream_t s);
+// The holder pair (ppk_db::d_foldhR ...).  ppk_foldh_count: the holder count of every shared value of every position
+// (left on the device in *d_twice / *d_holders, which the caller frees) and, per position and bound of `ladder`, E_H =
+// (values with more than H holders) + 2 into pos_e[(k * 64 * s64 + position) * PPK_FOLDH_LADDER + i]; synchronises.
+// ppk_build_foldh: the pair for bound H in the slot order db->foldh_order, the temporary pair, its counts band by
+// band and the entries; a device too full, or more entries than `max_entries`, leaves the database without the pair
+// (db->foldh_planes 0).  Synchronises.
+int ppk_foldh_count(const ppk_db *db, const unsigned *ladder, unsigned **d_twice, uint16_t **d_holders, std::vector<unsigned> *pos_e, hipStream_t s);
+int ppk_build_foldh(ppk_db *db, unsigned H, const unsigned *d_twice, const uint16_t *d_holders, size_t max_entries, hipStream_t s);
+void ppk_drop_foldh(ppk_db *db);
 
 // Profiling hooks (ppk_prof_*) -------------------------------------------------
 void ppk_prof_begin(hipStream_t s);

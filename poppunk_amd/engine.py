@@ -235,6 +235,54 @@ class SketchDB:
                    "ppk_db_fold2_events_read")
         return off, ev
 
+    def foldh_holders(self):
+        """The holder bound H of the database's holder pair, 0 without one (ppk_db_foldh_holders): every bin value
+        with at most H holders is coded 0 / 1 there and what its pairs are owed is kept in foldh_entries()."""
+        return int(_lib.lib().ppk_db_foldh_holders(self._h))
+
+    def foldh_stream_planes(self):
+        """Planes a self job compares per block of the holder pair's sorted positions, under the options in force
+        (ppk_db_foldh_stream_planes): uint8 [nk, sketchsize64] of 4, 3 or 2."""
+        out = np.empty((self.nk, self.sketchsize64), dtype=np.uint8)
+        _lib.check(_lib.lib().ppk_db_foldh_stream_planes(self._h, C.c_void_p(out.ctypes.data), out.size),
+                   "ppk_db_foldh_stream_planes")
+        return out
+
+    def foldh_position_order(self):
+        """The stored position each slot of the holder pair holds (ppk_db_foldh_position_order): uint32
+        [nk, 64 * sketchsize64], per k a permutation."""
+        out = np.empty((self.nk, 64 * self.sketchsize64), dtype=np.uint32)
+        _lib.check(_lib.lib().ppk_db_foldh_position_order(self._h, C.c_void_p(out.ctypes.data), out.size),
+                   "ppk_db_foldh_position_order")
+        return out
+
+    def foldh_codes(self, which):
+        """One copy of the holder pair un-bitsliced (tests), 0 the ref side, 1 the query side: uint16
+        [n, nk, 64 * sketchsize64] codes, in stored position order (the sort of foldh_position_order() undone)."""
+        planes, npad = 8, (self.n + 255) // 256 * 256
+        raw = np.empty((self.nk, self.sketchsize64, planes, npad), dtype=np.uint64)
+        _lib.check(_lib.lib().ppk_db_foldh_read(self._h, int(which), C.c_void_p(raw.ctypes.data),
+                                                self.nk * self.sketchsize64 * planes * npad), "ppk_db_foldh_read")
+        slots, order = self._unslice_codes(raw, planes), self.foldh_position_order()
+        codes = np.empty_like(slots)
+        for k in range(self.nk):
+            codes[:, k, order[k]] = slots[:, k]
+        return codes
+
+    def foldh_entries(self):
+        """What the holder pair's compare owes (ppk_db_foldh_entries_read): (offsets uint32 [npad / 32, npad / 256]
+        flattened + 1, entries uint32).  Bucket (lo // 32) * (npad // 256) + hi // 256 holds
+        entries[offsets[b]:offsets[b + 1]], each hi % 256 | (lo % 32) << 8 | k << 13 | count << 16, one per (pair, k)
+        with a non-zero count, in no order within a bucket."""
+        nb = C.c_size_t(0)
+        n_ent = int(_lib.lib().ppk_db_foldh_entries(self._h, C.byref(nb)))
+        off = np.zeros(nb.value + 1, dtype=np.uint32)
+        ent = np.zeros(n_ent, dtype=np.uint32)
+        _lib.check(_lib.lib().ppk_db_foldh_entries_read(self._h, C.c_void_p(off.ctypes.data), off.size,
+                                                        C.c_void_p(ent.ctypes.data) if n_ent else None, n_ent),
+                   "ppk_db_foldh_entries_read")
+        return off, ent
+
     def rank_counts(self):
         """What the count pass of the coded copies found (ppk_db_rank_counts), None where none ran: a dict of the
         maxima over all positions "D", "E", "E2", per (k, block) "block_D", "block_E", "block_E2" [nk, sketchsize64],

@@ -2,7 +2,8 @@
 """Generates poppunk_amd/csrc/ppk_block_asm.inc: the hand-scheduled gfx950 instruction
 stream for ONE 64-bin block (14 bit-planes) of the 4-ref x 4-query register tile, and the same
 stream for the 12, 10 and 8 planes of a rank-coded database (RANK_PLANES below), each with a "short" variant that
-leaves the top plane out (short_dma_planes), and for the two-holder pair at 8 planes one that leaves two out.
+leaves the top plane out (short_dma_planes), for the two-holder pair at 8 planes one that leaves two out, and for the
+holder pair (dist_kernel_v2_foldh) the 4-, 3- and 2-plane streams of the same 8-plane chunk.
 
 Why assembly: on MI355X a v_bitop3_b32 whose src0 and src1 sit in the same VGPR bank
 (register number mod 4) issues ~1.5x slower (tools/ubench_bank.hip: 4.7 vs 3.1 clk).  hipcc
@@ -142,8 +143,15 @@ def gen(QRY_PLANE_BYTES, TQ=4, dma_planes=None, half=False, a2=False, bb=BB):
 
     def ops(plane, rs):
         for r in rs:
-            if dma_planes and r == 3 and plane in dma_planes:
-                dma(dma_planes.index(plane))
+            # one piece per plane, in front of ref 3's compares; a stream shorter than its pieces (the holder pair's
+            # 2-plane stream: pieces at planes 0, 1, 1) issues a plane's FIRST piece in front of ref 1's instead
+            if dma_planes and plane in dma_planes:
+                ts = [t for t, pp in enumerate(dma_planes) if pp == plane]
+                assert len(ts) <= 2
+                if r == 3:
+                    dma(ts[-1])
+                elif r == 1 and len(ts) == 2:
+                    dma(ts[0])
             for q in range(TQ):
                 for hi in (0, 1):
                     acc = hi_acc(r, q) if hi else lo_acc(r, q)
@@ -323,6 +331,23 @@ def main():
                      "s_bitcmp1_b32 %[sh], %[bk]", "s_cbranch_scc1 .Lppk_short_%="] + full +
                     ["s_branch .Lppk_done_%=", ".Lppk_short_%=:"] + short +
                     ["s_branch .Lppk_done_%=", ".Lppk_six_%=:"] + six + [".Lppk_done_%=:"])
+        # The holder pair (dist_kernel_v2_foldh): every value with at most H holders is folded, a sorted block spans at
+        # most 16 codes and planes 4 .. 7 of its 8-plane chunk are zero.  Three streams in the one statement, picked like
+        # the two-holder pair's: bit %[bk] of %[sh2] the 2-plane stream (at most 4 codes), else bit %[bk] of %[sh] the
+        # 3-plane one (at most 8), else 4 planes.  The chunk and its DMA pieces are the 8-plane ones, issued at the
+        # planes of the 8-plane stream rescaled to each length (4: 1, 2, 3; 3: 0, 1, 2; 2: 0, 1, 1).
+        four = gen(256, 4, dma_planes=list(shorter_dma_planes(pl, 4)), bb=4)
+        three = gen(256, 4, dma_planes=list(shorter_dma_planes(pl, 5)), bb=3)
+        two = gen(256, 4, dma_planes=list(shorter_dma_planes(pl, 6)), bb=2)
+        f.write("// %d-plane chunk, the holder pair: the 4-plane stream, the 3-plane one (flag in sh) or the 2-plane one (flag\n"
+                "// in sh2): planes 4 .. 7 are zero in every block and are neither read nor compared\n" % pl)
+        write_macro(f, "PPK_BLOCK_DMA_SELH_ASM_Q32_P%d" % pl,
+                    ["s_bitcmp1_b32 %[sh2], %[bk]", "s_cbranch_scc1 .Lppk_two_%=",
+                     "s_bitcmp1_b32 %[sh], %[bk]", "s_cbranch_scc1 .Lppk_three_%="] + four +
+                    ["s_branch .Lppk_done_%=", ".Lppk_three_%=:"] + three +
+                    ["s_branch .Lppk_done_%=", ".Lppk_two_%=:"] + two + [".Lppk_done_%=:"])
+        f.write("// ... and its half block (diagonal tiles): 4 planes\n")
+        write_macro(f, "PPK_BLOCK_HALF_H4_ASM_Q32_P%d" % pl, gen(256, 4, half=True, bb=4))
     if "--experiments" not in sys.argv[1:]:
         return
     # measured-and-rejected shapes: generated on demand, not tracked (tools/ubench_pipe.hip needs them)
