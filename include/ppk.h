@@ -1634,6 +1634,27 @@ const char *ppk_last_kernel_name(void);
 int ppk_choose_route(size_t n_ref, size_t q_rows, int self, int nk, int sketchsize64, int bbits, int mask, int knn,
                      int cus, int xcds, int tile_slots, const long long *knobs, int *route, int *slices, size_t *tiles,
                      size_t *limit);
+/* Which coded copies ppk_db_create builds, as a pure function of what its count pass reads back (counts: n_counts =
+ * 3 x (1 + nk * sketchsize64) + 3 + nk * sketchsize64 * 64 words -- the ppk_db_rank_counts layout, then E2 of every
+ * position [k][64 * sketchsize64]), the shape, the device's resident tile workgroups and four options in this order:
+ * rank_fold, rank_fold2, fold2_sort, rank_foldh.  No device is touched.  first: the coding tried first, fallback: the
+ * one tried if that is dropped (device full, or a (pair, k) past the event field) -- 0 the injective copy, 1 the folded
+ * pair, 2 the two-holder pair, -1 the raw planes.  plane_sums[3]: the planes a self job compares over the stored blocks
+ * with the codings of D, E and E2.  With first == 2, and each where not NULL: order[nk * 64 * sketchsize64] the
+ * two-holder pair's slot order, flags[2 * 16] the per-k words of its 7-plane and then its 6-plane blocks,
+ * stream_planes[nk * sketchsize64] and their sum, and whether the holder pair is to be tried beside it. */
+int ppk_choose_coding(const uint32_t *counts, size_t n_counts, size_t n, size_t nk, size_t sketchsize64, size_t bbits,
+                      int tile_slots, const long long *options, int *first, int *fallback, size_t *plane_sums,
+                      uint32_t *order, uint32_t *flags, uint8_t *stream_planes, size_t *stream_sum, int *try_holder);
+/* The holder bound H of the holder pair (holders: 0 = no pair), as a pure function of E_H per position and ladder rung
+ * (pos_e[(k * 64 * sketchsize64 + position) * 7 + rung], rungs H = 4, 8, ... 256; with foldh_holders > 0 rung 0 is that
+ * H and the only one read), the shape, the resident tile workgroups, the most shared values of any position, the
+ * two-holder pair's stream plane sum and the options rank_foldh and foldh_holders.  No device is touched.  With a pair:
+ * order[nk * 64 * sketchsize64] its slot order, block_planes[nk * sketchsize64] of 2, 3 or 4, max_entries the cap on
+ * its entries. */
+int ppk_choose_holder(const uint32_t *pos_e, size_t n_pos_e, size_t n, size_t nk, size_t sketchsize64, int tile_slots,
+                      size_t most_shared, size_t fold2_sum, long long rank_foldh, long long foldh_holders,
+                      unsigned *holders, uint32_t *order, uint8_t *block_planes, size_t *max_entries);
 /* Named stages of the multi-kernel entry points (the sweeps of src/boundary.cpp:154-237, neighbours of
  * src/extend.cpp:248-289, the QC lists of PopPUNK/qc.py:330-354, long <-> square): when enabled, one hipEvent between
  * stages on the call's stream.  ppk_prof_stages_read writes "name<TAB>total ms<TAB>count" lines in first-seen order

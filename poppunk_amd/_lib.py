@@ -239,6 +239,11 @@ SIGNATURES = {
     "ppk_choose_route": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "ppk_choose_coding": (C.c_int, [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int), C.POINTER(C.c_size_t), _vp, _vp, _vp, C.POINTER(C.c_size_t),
+                                    C.POINTER(C.c_int)]),
+    "ppk_choose_holder": (C.c_int, [_vp, _sz, _sz, _sz, _sz, C.c_int, _sz, _sz, C.c_longlong, C.c_longlong,
+                                    C.POINTER(C.c_uint), _vp, _vp, C.POINTER(C.c_size_t)]),
     "ppk_sweep_plan": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "ppk_prof_stages_enable": (C.c_int, [C.c_int]),
     "ppk_prof_stages_read": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int]),

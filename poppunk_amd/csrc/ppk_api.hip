@@ -347,83 +347,6 @@ extern "C" int ppk_band_split(size_t n_ref, size_t n_qry, int n_parts, size_t *b
 }
 
 // ---- resident sketch database --------------------------------------------------
-// The holder pair (ppk_db::d_foldhR ...), tried where the two-holder pair has been (whether or not its event cap held).  The choice is a pure function
-// of the count pass's figures and the options: the smallest H of the ladder 4, 8, ... 256 (option "foldh_holders": that
-// H alone) for which, with each k's positions sorted by E_H (descending, ties by stored position), every block of 64
-// slots spans at most 16 codes -- and, under the default rule, the stream plane sum (2, 3 or 4 per block) is at most 0.6
-// of the two-holder pair's and the self job runs at least four rounds of tiles (`four_rounds`): a smaller saving does
-// not pay for the creation pass.  Option "rank_foldh" 2 takes the first H whose blocks fit, and lifts the cap on the
-// entries from a sixteenth of the (pair, k) to all of them.  No H: the database keeps what it has.
-struct FoldhChoice {
-  int rung;                                // index into the ladder, -1: none
-  std::vector<unsigned> order;             // [k][slot]
-  std::vector<uint8_t> block_planes;       // [k][block]
-};
-static FoldhChoice ppk_choose_foldh(const std::vector<unsigned> &pos_e, size_t nk, size_t s64, int rungs, size_t fold2_sum,
-                                    bool take_any, bool four_rounds) {
-  FoldhChoice c;
-  c.rung = -1;
-  const size_t nbins = s64 * 64;
-  c.order.resize(nk * nbins);
-  c.block_planes.resize(nk * s64);
-  for (int i = 0; i < rungs; ++i) {
-    bool fits = true;
-    size_t sum = 0;
-    for (size_t k = 0; k < nk && fits; ++k) {
-      unsigned *ord = c.order.data() + k * nbins;
-      for (size_t j = 0; j < nbins; ++j) ord[j] = (unsigned)j;
-      std::stable_sort(ord, ord + nbins, [&](unsigned a, unsigned b) {
-        return pos_e[(k * nbins + a) * PPK_FOLDH_LADDER + i] > pos_e[(k * nbins + b) * PPK_FOLDH_LADDER + i];
-      });
-      for (size_t b = 0; b < s64; ++b) {
-        const unsigned widest = pos_e[(k * nbins + ord[b * 64]) * PPK_FOLDH_LADDER + i];      // (sorted: the block's first slot)
-        if (widest > PPK_FOLDH_MAX_CODES) fits = false;
-        const uint8_t planes = widest <= 4u ? 2 : widest <= 8u ? 3 : 4;
-        c.block_planes[k * s64 + b] = planes;
-        sum += planes;
-      }
-    }
-    if (fits && (take_any || (four_rounds && sum * 10 <= fold2_sum * 6))) {
-      c.rung = i;
-      return c;
-    }
-  }
-  return c;
-}
-static int ppk_try_foldh(ppk_db *db, long long opt, size_t most_shared, size_t fold2_sum, bool four_rounds, hipStream_t s) {
-  const size_t nk = db->nk, s64 = db->s64, n = db->n;
-  if (nk > PPK_FOLD2_MAX_NK || s64 > 32 || nk >= PPK_RANK_SHORT_WORDS || n >= ((size_t)1 << 24) || most_shared > PPK_FOLDH_SLOTS) return PPK_OK;
-  unsigned ladder[PPK_FOLDH_LADDER];
-  for (int i = 0; i < PPK_FOLDH_LADDER; ++i) ladder[i] = 4u << i;
-  const long long forced = ppk_config().foldh_holders.load();
-  if (forced > 0) ladder[0] = (unsigned)(forced < 65534 ? forced : 65534);
-  unsigned *d_twice = nullptr;
-  uint16_t *d_holders = nullptr;
-  std::vector<unsigned> pos_e;
-  int rc = ppk_foldh_count(db, ladder, &d_twice, &d_holders, &pos_e, s);
-  if (rc != PPK_OK || pos_e.empty()) return rc;
-  FoldhChoice c = ppk_choose_foldh(pos_e, nk, s64, forced > 0 ? 1 : PPK_FOLDH_LADDER, fold2_sum, opt == 2, four_rounds);
-  if (c.rung >= 0) {
-    db->foldh_order.swap(c.order);
-    db->foldh_block_planes.swap(c.block_planes);
-    const size_t pair_k = n * (n - 1) / 2 * nk;
-    rc = ppk_build_foldh(db, ladder[c.rung], d_twice, d_holders, opt == 2 ? pair_k : pair_k / 16, s);
-    if (rc == PPK_OK && db->foldh_planes)
-      for (size_t k = 0; k < nk; ++k)
-        for (size_t b = 0; b < s64; ++b) {
-          if (db->foldh_block_planes[k * s64 + b] <= 3) db->foldh_three[k] |= 1u << b;
-          if (db->foldh_block_planes[k * s64 + b] <= 2) db->foldh_two[k] |= 1u << b;
-        }
-  }
-  if (!db->foldh_planes) {
-    db->foldh_order.clear();
-    db->foldh_block_planes.clear();
-  }
-  (void)hipFree(d_twice);
-  (void)hipFree(d_holders);
-  return rc;
-}
-
 extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t nk,
                              size_t sketchsize64, size_t bbits, const uint16_t *clu,
                              int src_on_device, void *stream, ppk_db **out) {
@@ -446,32 +369,6 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
   db->s64 = sketchsize64;
   db->bbits = bbits;
   db->words = sketchsize64 * bbits;
-  db->d_skT = nullptr;
-  db->d_clu = nullptr;
-  db->d_skR = nullptr;
-  db->rank_planes = 0;
-  for (unsigned &w : db->rank_short) w = 0;
-  db->d_foldR = db->d_foldQ = nullptr;
-  db->fold_planes = 0;
-  for (unsigned &w : db->fold_short) w = 0;
-  db->d_fold2R = db->d_fold2Q = nullptr;
-  db->d_fold2_ev = nullptr;
-  db->d_fold2_off = nullptr;
-  db->fold2_planes = 0;
-  db->fold2_qt = db->fold2_rt = 0;
-  db->fold2_events = 0;
-  for (unsigned &w : db->fold2_short) w = 0;
-  for (unsigned &w : db->fold2_seven) w = 0;
-  for (unsigned &w : db->fold2_six) w = 0;
-  db->d_foldhR = db->d_foldhQ = nullptr;
-  db->d_foldh_ent = nullptr;
-  db->d_foldh_off = nullptr;
-  db->foldh_planes = 0;
-  db->foldh_holders = 0;
-  db->foldh_qt = db->foldh_rt = 0;
-  db->foldh_entries = 0;
-  for (unsigned &w : db->foldh_three) w = 0;
-  for (unsigned &w : db->foldh_two) w = 0;
   const size_t cols = nk * db->words;
   const size_t in_bytes = n * cols * sizeof(uint64_t);
   const size_t out_bytes = db->npad * cols * sizeof(uint64_t);
@@ -505,142 +402,8 @@ extern "C" int ppk_db_create(int device_id, const uint64_t *sk, size_t n, size_t
       e = hipErrorUnknown;
     if (e != hipSuccess) rc = PPK_ERR_HIP;
   }
-  // Rank-coded copy (ppk_db::d_skR), once per database: D = the most distinct values any (k, bin) position holds over
-  // the samples decides the planes (8, 10 or 12; more than 4 096 values: no copy).  Only a database whose self job runs
-  // whole tiles reads one (launch_v2), so only such a database pays for one.  The count is read back: one
-  // synchronisation of `s` per database.  The same pass leaves the maximum of each (k, 64-bin block), read back with
-  // it: a block that holds at most 2^(planes - 1) values per position has a zero top plane, and the tile kernel leaves
-  // that plane out there (ppk_db::rank_short).
-  // The pass counts a second figure per position: S, the values at least two samples hold there.  A value with a single
-  // holder matches nothing in a self job, so the folded pair (ppk_db::d_foldR / d_foldQ) gives all of them two reserved
-  // codes and spans E = S + 2 codes where the injective copy spans D.  The pair is built instead of the injective copy
-  // where it compares fewer planes over the blocks (option "rank_fold"); rank_planes and rank_short stay functions of D.
-  // A third figure, S3, counts the values at least three samples hold.  The two-holder pair (ppk_db::d_fold2R /
-  // d_fold2Q) codes the values with exactly two holders like single-holder ones and spans E2 = S3 + 2 codes; what the
-  // compare then misses -- one match per such value, in one known pair -- the tile kernel adds back from an event list
-  // built here.  That costs three more small kernels, a second synchronisation and a fixed step per tile, so the
-  // default (option "rank_fold2" 1) takes it only where its plane sum is the lowest of the three AND the self job runs
-  // at least four rounds of tiles (a smaller job's time is its latency, not its compare stream).  Caps: at most five k,
-  // 8 planes, PPK_FOLD2_SLOTS two-holder values per position, PPK_FOLD2_MAX_PER_PAIR events per (pair, k); a database
-  // past any of them keeps the copies it would have had.
-  // The pass also leaves E2 of every position.  Counts and events do not depend on the order of a k's positions, so
-  // the two-holder pair stores them sorted by E2 (option "fold2_sort"): the wide positions share a few blocks and the
-  // rest compare 6 planes (ppk_db::fold2_order / fold2_seven / fold2_six).  The choice among the codings does not look
-  // at the order: it keeps the sums over the stored blocks.
-  if (rc == PPK_OK && ppk_config().rank_planes.load() != 0 && ppk_self_job_takes_tiles(db)) {
-    unsigned *d_max = nullptr;
-    const size_t n_blocks = nk * sketchsize64;
-    std::vector<unsigned> counts(3 * (1 + n_blocks) + PPK_RANK_EXTRA + n_blocks * 64, 0u);      // (behind the figures: E2 per position)
-    e = hipMalloc(reinterpret_cast<void **>(&d_max), counts.size() * sizeof(unsigned));
-    if (e == hipSuccess) {
-      rc = ppk_launch_rank_count(db->d_skT, n, db->npad, nk, sketchsize64, d_max, s);
-      if (rc == PPK_OK) {
-        e = hipMemcpyAsync(counts.data(), d_max, counts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) rc = ppk_fail(PPK_ERR_HIP, std::string("rank codes: ") + hipGetErrorString(e));
-      }
-      (void)hipFree(d_max);
-      auto planes_for = [](unsigned codes) { return codes <= 256 ? 8 : codes <= 1024 ? 10 : codes <= 4096 ? 12 : 0; };
-      const unsigned *count_d = counts.data(), *count_e = counts.data() + 1 + n_blocks, *count_e2 = counts.data() + 2 * (1 + n_blocks);
-      unsigned *extra = counts.data() + 3 * (1 + n_blocks);      // most two-holder values of a position, all of them, cap hit
-      const int planes = planes_for(count_d[0]), planes_fold = planes_for(count_e[0]), planes_fold2 = planes_for(count_e2[0]);
-      // the short flags of either coding, and the planes a self job compares over all blocks with it (no coding: 14)
-      const bool flags_fit = nk < PPK_RANK_SHORT_WORDS && sketchsize64 <= 32;
-      auto block_flags = [&](const unsigned *cnt, int pl, unsigned *flags) {
-        size_t sum = 0;
-        for (size_t k = 0; k < nk; ++k)
-          for (size_t b = 0; b < sketchsize64; ++b) {
-            const bool is_short = pl && flags_fit && cnt[1 + k * sketchsize64 + b] <= (1u << (pl - 1));
-            if (is_short) flags[k] |= 1u << b;
-            sum += pl ? (size_t)(pl - (is_short ? 1 : 0)) : (size_t)bbits;
-          }
-        return sum;
-      };
-      unsigned short_d[PPK_RANK_SHORT_WORDS] = {}, short_e[PPK_RANK_SHORT_WORDS] = {}, short_e2[PPK_RANK_SHORT_WORDS] = {};
-      const size_t sum_d = block_flags(count_d, planes, short_d), sum_e = block_flags(count_e, planes_fold, short_e);
-      const size_t sum_e2 = block_flags(count_e2, planes_fold2, short_e2);
-      const long long fold_opt = ppk_config().rank_fold.load(), fold2_opt = ppk_config().rank_fold2.load();
-      const size_t copy_words = db->npad * nk * sketchsize64;
-      // the two-holder pair first: where it is built nothing else is
-      const bool fold2_fits = planes_fold2 == 8 && nk <= PPK_FOLD2_MAX_NK && extra[0] <= PPK_FOLD2_SLOTS && n < ((size_t)1 << 28);
-      const size_t self_tiles = (db->npad / 256) * (db->npad / 32) / 2;
-      const bool fold2_pays = fold_opt != 0 && sum_e2 < sum_d && sum_e2 < (planes_fold ? sum_e : (size_t)-1) &&
-                              self_tiles >= 4 * (size_t)ppk_geometry(device_id).tile_slots;
-      if (rc == PPK_OK && fold2_fits && fold2_opt != 0 && (fold2_opt == 2 || fold2_pays)) {
-        bool overflow = false;
-        // per k a stable sort of the positions by E2, descending: ties keep their stored order
-        const unsigned *pos_e2 = extra + PPK_RANK_EXTRA;
-        const size_t nbins = sketchsize64 * 64;
-        const bool sorted = ppk_config().fold2_sort.load() != 0;
-        db->fold2_order.resize(nk * nbins);
-        for (size_t k = 0; k < nk; ++k) {
-          unsigned *ord = db->fold2_order.data() + k * nbins;
-          for (size_t i = 0; i < nbins; ++i) ord[i] = (unsigned)i;
-          if (sorted)
-            std::stable_sort(ord, ord + nbins, [&](unsigned a, unsigned b) { return pos_e2[k * nbins + a] > pos_e2[k * nbins + b]; });
-        }
-        rc = ppk_build_fold2(db, planes_fold2, extra[1], sorted ? &db->fold2_order : nullptr, &overflow, s);
-        extra[2] = overflow ? 1u : 0u;
-        if (rc == PPK_OK && db->fold2_planes) {
-          for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) db->fold2_short[k] = short_e2[k];
-          for (size_t k = 0; k < nk && flags_fit; ++k)
-            for (size_t b = 0; b < sketchsize64; ++b) {
-              unsigned widest = 0;
-              for (size_t i = 0; i < 64; ++i) widest = std::max(widest, pos_e2[k * nbins + db->fold2_order[k * nbins + b * 64 + i]]);
-              if (widest <= 128u) db->fold2_seven[k] |= 1u << b;
-              if (widest <= 64u) db->fold2_six[k] |= 1u << b;
-            }
-          db->rank_planes = planes;
-        }
-        // The holder pair beside it (option "rank_foldh"), also where a (pair, k) had more events than the two-holder
-        // pair's field holds: its counts have no such cap.  (count_e[0] - 2: the most shared values of any position;
-        // fold2_sum: what the two-holder pair streams over its sorted blocks, 8 / 7 / 6 planes each.)
-        if (const long long foldh_opt = ppk_config().rank_foldh.load(); rc == PPK_OK && foldh_opt != 0 && flags_fit) {
-          size_t fold2_sum = 0;
-          for (size_t k = 0; k < nk; ++k)
-            for (size_t b = 0; b < sketchsize64; ++b) {
-              unsigned widest = 0;
-              for (size_t i = 0; i < 64; ++i) widest = std::max(widest, pos_e2[k * nbins + db->fold2_order[k * nbins + b * 64 + i]]);
-              fold2_sum += widest <= 64u ? 6 : widest <= 128u ? 7 : 8;
-            }
-          rc = ppk_try_foldh(db, foldh_opt, count_e[0] - 2u, fold2_sum, self_tiles >= 4 * (size_t)ppk_geometry(device_id).tile_slots, s);
-          if (rc == PPK_OK && db->foldh_planes) db->rank_planes = planes;
-        }
-      }
-      if (rc == PPK_OK && !db->fold2_planes && planes_fold && fold_opt != 0 && (fold_opt == 2 || sum_e < sum_d)) {
-        // (a device too full for the pair falls back to the injective copy, and from there to the raw planes)
-        e = hipMalloc(reinterpret_cast<void **>(&db->d_foldR), copy_words * (size_t)planes_fold * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_foldQ), copy_words * (size_t)planes_fold * sizeof(uint64_t));
-        if (e != hipSuccess) {
-          (void)hipGetLastError();
-          if (db->d_foldR) (void)hipFree(db->d_foldR);
-          db->d_foldR = db->d_foldQ = nullptr;
-        } else {
-          rc = ppk_launch_rank_codes(db->d_skT, db->d_foldR, db->d_foldQ, n, db->npad, nk, sketchsize64, planes_fold, s);
-          db->fold_planes = planes_fold;
-          for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) db->fold_short[k] = short_e[k];
-          db->rank_planes = planes;
-        }
-      }
-      if (rc == PPK_OK && planes && !db->fold_planes && !db->fold2_planes) {
-        // (a device too full for the copy keeps the raw planes alone: the copy only buys speed)
-        e = hipMalloc(reinterpret_cast<void **>(&db->d_skR), copy_words * (size_t)planes * sizeof(uint64_t));
-        if (e != hipSuccess) {
-          (void)hipGetLastError();
-          db->d_skR = nullptr;
-        } else {
-          rc = ppk_launch_rank_codes(db->d_skT, db->d_skR, nullptr, n, db->npad, nk, sketchsize64, planes, s);
-          db->rank_planes = planes;
-        }
-      }
-      if (db->rank_planes)
-        for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) db->rank_short[k] = short_d[k];
-      if (!db->fold2_planes) db->fold2_order.clear();
-      if (rc == PPK_OK) db->rank_counts.assign(counts.begin(), counts.begin() + 3 * (1 + n_blocks) + PPK_RANK_EXTRA);
-    } else {
-      (void)hipGetLastError();
-    }
-  }
+  // the coded copies of a self job that runs whole tiles (ppk_coding.hip): the count pass, the choice, the copies
+  if (rc == PPK_OK) rc = ppk_db_build_codings(db, s);
   // the staging copy must outlive the transpose; the host-source path blocks here
   if (d_stage) {
     (void)hipStreamSynchronize(s);
@@ -655,197 +418,12 @@ extern "C" void ppk_db_destroy(ppk_db *db) {
   if (!db) return;
   DeviceGuard guard(db->device);
   if (db->d_skT) (void)hipFree(db->d_skT);
-  if (db->d_skR) (void)hipFree(db->d_skR);
-  if (db->d_foldR) (void)hipFree(db->d_foldR);
-  if (db->d_foldQ) (void)hipFree(db->d_foldQ);
-  for (void *ptr : {(void *)db->d_fold2R, (void *)db->d_fold2Q, (void *)db->d_fold2_ev, (void *)db->d_fold2_off})
-    if (ptr) (void)hipFree(ptr);
-  ppk_drop_foldh(db);
+  for (PpkCoding &c : db->coding) ppk_coding_free(c);
   if (db->d_clu) (void)hipFree(db->d_clu);
   delete db;
 }
 
 extern "C" size_t ppk_db_size(const ppk_db *db) { return db ? db->n : 0; }
-extern "C" int ppk_db_rank_planes(const ppk_db *db) { return db ? db->rank_planes : 0; }
-// The injective copy of a database that was built with the folded pair alone: made when somebody asks for it
-// (ppk_db_rank_read; a rectangular job of the handle against itself reads the raw planes until then).
-static int ppk_db_build_injective(ppk_db *db) {
-  if (db->d_skR) return PPK_OK;
-  const size_t bytes = db->npad * db->nk * db->s64 * (size_t)db->rank_planes * sizeof(uint64_t);
-  PPK_HIP(hipMalloc(reinterpret_cast<void **>(&db->d_skR), bytes));
-  int rc = ppk_launch_rank_codes(db->d_skT, db->d_skR, nullptr, db->n, db->npad, db->nk, db->s64, db->rank_planes, nullptr);
-  hipError_t e = rc == PPK_OK ? hipDeviceSynchronize() : hipSuccess;
-  if (rc == PPK_OK && e != hipSuccess) rc = ppk_fail(PPK_ERR_HIP, std::string("rank codes: ") + hipGetErrorString(e));
-  if (rc != PPK_OK) {
-    (void)hipFree(db->d_skR);
-    db->d_skR = nullptr;
-  }
-  return rc;
-}
-
-extern "C" int ppk_db_rank_read(const ppk_db *db, uint64_t *out, size_t words) {
-  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_rank_read: NULL argument");
-  if (!db->rank_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_rank_read: the database has no rank-coded copy");
-  if (words != db->nk * db->s64 * (size_t)db->rank_planes * db->npad)
-    return ppk_fail(PPK_ERR_ARG, "ppk_db_rank_read: `words` is not nk * sketchsize64 * planes * padded samples");
-  PPK_ENTER_DEVICE(guard, db->device);
-  PPK_HIP(hipDeviceSynchronize());
-  if (int rc = ppk_db_build_injective(const_cast<ppk_db *>(db))) return rc;
-  PPK_HIP(hipMemcpy(out, db->d_skR, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return PPK_OK;
-}
-
-extern "C" int ppk_db_fold_planes(const ppk_db *db) { return db ? db->fold_planes : 0; }
-extern "C" int ppk_db_fold_read(const ppk_db *db, int which, uint64_t *out, size_t words) {
-  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold_read: NULL argument");
-  if (which != 0 && which != 1) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold_read: `which` is 0 (ref side) or 1 (query side)");
-  if (!db->fold_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold_read: the database has no folded pair");
-  if (words != db->nk * db->s64 * (size_t)db->fold_planes * db->npad)
-    return ppk_fail(PPK_ERR_ARG, "ppk_db_fold_read: `words` is not nk * sketchsize64 * planes * padded samples");
-  PPK_ENTER_DEVICE(guard, db->device);
-  PPK_HIP(hipDeviceSynchronize());
-  PPK_HIP(hipMemcpy(out, which ? db->d_foldQ : db->d_foldR, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return PPK_OK;
-}
-
-extern "C" int ppk_db_fold_block_planes(const ppk_db *db, uint8_t *out, size_t cap) {
-  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold_block_planes: NULL argument");
-  if (!db->fold_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold_block_planes: the database has no folded pair");
-  if (cap < db->nk * db->s64) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold_block_planes: `cap` is below nk * sketchsize64");
-  for (size_t k = 0; k < db->nk; ++k)
-    for (size_t b = 0; b < db->s64; ++b) {
-      const bool is_short = k < PPK_RANK_SHORT_WORDS && b < 32 && ((db->fold_short[k] >> b) & 1u);
-      out[k * db->s64 + b] = (uint8_t)(db->fold_planes - (is_short ? 1 : 0));
-    }
-  return PPK_OK;
-}
-
-extern "C" int ppk_db_fold2_planes(const ppk_db *db) { return db ? db->fold2_planes : 0; }
-extern "C" int ppk_db_fold2_read(const ppk_db *db, int which, uint64_t *out, size_t words) {
-  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_read: NULL argument");
-  if (which != 0 && which != 1) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_read: `which` is 0 (ref side) or 1 (query side)");
-  if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_read: the database has no two-holder pair");
-  if (words != db->nk * db->s64 * (size_t)db->fold2_planes * db->npad)
-    return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_read: `words` is not nk * sketchsize64 * planes * padded samples");
-  PPK_ENTER_DEVICE(guard, db->device);
-  PPK_HIP(hipDeviceSynchronize());
-  PPK_HIP(hipMemcpy(out, which ? db->d_fold2Q : db->d_fold2R, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return PPK_OK;
-}
-
-extern "C" int ppk_db_fold2_block_planes(const ppk_db *db, uint8_t *out, size_t cap) {
-  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_block_planes: NULL argument");
-  if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_block_planes: the database has no two-holder pair");
-  if (cap < db->nk * db->s64) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_block_planes: `cap` is below nk * sketchsize64");
-  for (size_t k = 0; k < db->nk; ++k)
-    for (size_t b = 0; b < db->s64; ++b) {
-      const bool is_short = k < PPK_RANK_SHORT_WORDS && b < 32 && ((db->fold2_short[k] >> b) & 1u);
-      out[k * db->s64 + b] = (uint8_t)(db->fold2_planes - (is_short ? 1 : 0));
-    }
-  return PPK_OK;
-}
-
-extern "C" int ppk_db_fold2_stream_planes(const ppk_db *db, uint8_t *out, size_t cap) {
-  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_stream_planes: NULL argument");
-  if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_stream_planes: the database has no two-holder pair");
-  if (cap < db->nk * db->s64) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_stream_planes: `cap` is below nk * sketchsize64");
-  const bool use_short = ppk_config().rank_short.load() != 0, use_six = use_short && ppk_config().fold2_min_planes.load() <= 6;
-  for (size_t k = 0; k < db->nk; ++k)
-    for (size_t b = 0; b < db->s64; ++b) {
-      const bool fits = k < PPK_RANK_SHORT_WORDS && b < 32;
-      const bool seven = fits && use_short && ((db->fold2_seven[k] >> b) & 1u), six = fits && use_six && ((db->fold2_six[k] >> b) & 1u);
-      out[k * db->s64 + b] = (uint8_t)(db->fold2_planes - (six ? 2 : seven ? 1 : 0));
-    }
-  return PPK_OK;
-}
-
-extern "C" int ppk_db_fold2_position_order(const ppk_db *db, uint32_t *out, size_t cap) {
-  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_position_order: NULL argument");
-  if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_position_order: the database has no two-holder pair");
-  if (cap < db->fold2_order.size()) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_position_order: `cap` is below nk * 64 * sketchsize64");
-  for (size_t i = 0; i < db->fold2_order.size(); ++i) out[i] = db->fold2_order[i];
-  return PPK_OK;
-}
-
-extern "C" unsigned ppk_db_foldh_holders(const ppk_db *db) { return db && db->foldh_planes ? db->foldh_holders : 0u; }
-extern "C" int ppk_db_foldh_stream_planes(const ppk_db *db, uint8_t *out, size_t cap) {
-  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_stream_planes: NULL argument");
-  if (!db->foldh_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_foldh_stream_planes: the database has no holder pair");
-  if (cap < db->nk * db->s64) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_stream_planes: `cap` is below nk * sketchsize64");
-  const long long min_planes = ppk_config().rank_short.load() != 0 ? ppk_config().foldh_min_planes.load() : 4;
-  for (size_t i = 0; i < db->nk * db->s64; ++i) {
-    const uint8_t planes = db->foldh_block_planes[i];
-    out[i] = min_planes >= 4 ? (uint8_t)4 : planes < min_planes ? (uint8_t)min_planes : planes;
-  }
-  return PPK_OK;
-}
-extern "C" int ppk_db_foldh_position_order(const ppk_db *db, uint32_t *out, size_t cap) {
-  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_position_order: NULL argument");
-  if (!db->foldh_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_foldh_position_order: the database has no holder pair");
-  if (cap < db->foldh_order.size()) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_position_order: `cap` is below nk * 64 * sketchsize64");
-  for (size_t i = 0; i < db->foldh_order.size(); ++i) out[i] = db->foldh_order[i];
-  return PPK_OK;
-}
-extern "C" int ppk_db_foldh_read(const ppk_db *db, int which, uint64_t *out, size_t words) {
-  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_read: NULL argument");
-  if (which != 0 && which != 1) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_read: `which` is 0 (ref side) or 1 (query side)");
-  if (!db->foldh_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_foldh_read: the database has no holder pair");
-  if (words != db->nk * db->s64 * (size_t)db->foldh_planes * db->npad)
-    return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_read: `words` is not nk * sketchsize64 * 8 * padded samples");
-  DeviceGuard guard(db->device);
-  PPK_HIP(hipDeviceSynchronize());
-  PPK_HIP(hipMemcpy(out, which ? db->d_foldhQ : db->d_foldhR, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return PPK_OK;
-}
-extern "C" size_t ppk_db_foldh_entries(const ppk_db *db, size_t *n_buckets) {
-  if (n_buckets) *n_buckets = db && db->foldh_planes ? (size_t)db->foldh_qt * db->foldh_rt : 0;
-  return db && db->foldh_planes ? db->foldh_entries : 0;
-}
-extern "C" int ppk_db_foldh_entries_read(const ppk_db *db, uint32_t *off, size_t n_off, uint32_t *ent, size_t n_ent) {
-  if (!db || !off) return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_entries_read: NULL argument");
-  if (!db->foldh_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_foldh_entries_read: the database has no holder pair");
-  if (n_off != (size_t)db->foldh_qt * db->foldh_rt + 1 || n_ent != db->foldh_entries || (n_ent && !ent))
-    return ppk_fail(PPK_ERR_ARG, "ppk_db_foldh_entries_read: sizes are buckets + 1 and entries (ppk_db_foldh_entries)");
-  DeviceGuard guard(db->device);
-  PPK_HIP(hipDeviceSynchronize());
-  PPK_HIP(hipMemcpy(off, db->d_foldh_off, n_off * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (n_ent) PPK_HIP(hipMemcpy(ent, db->d_foldh_ent, n_ent * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return PPK_OK;
-}
-extern "C" size_t ppk_db_fold2_events(const ppk_db *db, size_t *n_buckets) {
-  if (n_buckets) *n_buckets = db && db->fold2_planes ? (size_t)db->fold2_qt * db->fold2_rt : 0;
-  return db && db->fold2_planes ? db->fold2_events : 0;
-}
-extern "C" int ppk_db_fold2_events_read(const ppk_db *db, uint32_t *off, size_t n_off, uint16_t *ev, size_t n_ev) {
-  if (!db || !off) return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_events_read: NULL argument");
-  if (!db->fold2_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_fold2_events_read: the database has no two-holder pair");
-  if (n_off != (size_t)db->fold2_qt * db->fold2_rt + 1 || n_ev != db->fold2_events || (n_ev && !ev))
-    return ppk_fail(PPK_ERR_ARG, "ppk_db_fold2_events_read: sizes are buckets + 1 and events (ppk_db_fold2_events)");
-  PPK_ENTER_DEVICE(guard, db->device);
-  PPK_HIP(hipDeviceSynchronize());
-  PPK_HIP(hipMemcpy(off, db->d_fold2_off, n_off * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (n_ev) PPK_HIP(hipMemcpy(ev, db->d_fold2_ev, n_ev * sizeof(uint16_t), hipMemcpyDeviceToHost));
-  return PPK_OK;
-}
-
-extern "C" size_t ppk_db_rank_counts(const ppk_db *db, uint32_t *out, size_t cap) {
-  if (!db) return 0;
-  if (out && cap >= db->rank_counts.size())
-    for (size_t i = 0; i < db->rank_counts.size(); ++i) out[i] = db->rank_counts[i];
-  return db->rank_counts.size();
-}
-
-extern "C" int ppk_db_rank_block_planes(const ppk_db *db, uint8_t *out, size_t cap) {
-  if (!db || !out) return ppk_fail(PPK_ERR_ARG, "ppk_db_rank_block_planes: NULL argument");
-  if (!db->rank_planes) return ppk_fail(PPK_ERR_STATE, "ppk_db_rank_block_planes: the database has no rank-coded copy");
-  if (cap < db->nk * db->s64) return ppk_fail(PPK_ERR_ARG, "ppk_db_rank_block_planes: `cap` is below nk * sketchsize64");
-  for (size_t k = 0; k < db->nk; ++k)
-    for (size_t b = 0; b < db->s64; ++b) {
-      const bool is_short = k < PPK_RANK_SHORT_WORDS && b < 32 && ((db->rank_short[k] >> b) & 1u);
-      out[k * db->s64 + b] = (uint8_t)(db->rank_planes - (is_short ? 1 : 0));
-    }
-  return PPK_OK;
-}
 
 // ---- kernel 1, device entry points -------------------------------------------------
 int ppk_check_pair(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, size_t q_begin,

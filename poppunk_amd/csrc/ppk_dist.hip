@@ -187,15 +187,15 @@ struct DistParams {
   int kmers[PPK_MAX_NK];
   // dist_kernel_v2_rank only (appended: every field above keeps its offset).  Bit b of rank_short[k]: block b of k holds
   // at most 2^(P-1) distinct values per position, so plane P-1 of its codes is zero and the kernel compares P-1 planes
-  // there (ppk_db::rank_short; all zero with option "rank_short" 0).  The kernel reads word k at the end of k - 1, and
+  // there (PpkCoding::less1; all zero with option "rank_short" 0).  The kernel reads word k at the end of k - 1, and
   // word nk after the last k: PPK_RANK_SHORT_WORDS > nk.
   unsigned rank_short[PPK_RANK_SHORT_WORDS];
-  // the FOLD2 instantiations only: the event list of the two-holder pair (ppk_db::d_fold2_ev / d_fold2_off / fold2_rt)
+  // the FOLD2 instantiations only: the event list of the two-holder pair (PpkCoding::d_list / d_off / rt)
   const uint16_t *fold2_ev;
   const unsigned *fold2_off;
   unsigned fold2_rt;
   // Bit b of fold2_six[k]: block b of k spans at most 2^6 codes, planes 6 and 7 are zero there and the kernel compares
-  // 6 planes (ppk_db::fold2_six; every such bit is set in rank_short[k] too; all zero with "fold2_min_planes" 7).
+  // 6 planes (PpkCoding::less2; every such bit is set in rank_short[k] too; all zero with "fold2_min_planes" 7).
   // Fetched where rank_short is.
   unsigned fold2_six[PPK_RANK_SHORT_WORDS];
 };
@@ -249,574 +249,6 @@ transpose_kernel(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, si
     const size_t c = c0 + i, s = s0 + tx;
     if (c < cols && s < npad) out[c * npad + s] = tile[tx][i];
   }
-}
-
-// Rank codes of a bbits = 14 database (ppk_db::d_skR, d_foldR / d_foldQ).  One workgroup per (k, 64-bin block, byte g of
-// the block's words) = 8 bin positions.  Per position a 16 384-bit presence bitmap of the values samples [0, n) hold
-// there goes into LDS, and next to it (count pass, folded codes) the bitmap of the values seen at least twice: the
-// presence atomicOr returns the old word, and a bit that was already set is a second holder.  A prefix popcount turns a
-// value into its rank among the position's distinct (or shared) values.
-//   WRITE = false: D, the largest number of distinct values of any position, into max_distinct[0], and of any position
-//                  of each (k, 64-bin block) into max_distinct[1 + k * s64 + block].  Behind them, at
-//                  max_distinct[1 + nk * s64 ...], the same two for E = S + 2, the codes a folded position spans (S: its
-//                  shared values, those with at least two holders).
-//   WRITE = true:  byte g of the PL code planes of every sample, out = [k][block * PL + plane][npad] (padding samples
-//                  get code 0).  The caller has checked that every code is below 2^PL.
-//     FOLD = false: code = rank among the position's distinct values (injective).
-//     FOLD = true:  two copies.  A shared value gets 2 + its rank among the position's shared values in both; a value
-//                   with a single holder gets 0 in `out` (the ref side) and 1 in `out_q` (the query side): it can match
-//                   nothing in a job that compares two different samples, and 0 != 1 != every shared code says so.
-constexpr int RANK_BB = 14;                      // the one bbits with a coded copy (the tile kernels' V2_BB)
-constexpr int RANK_BMW = (1 << RANK_BB) / 32;      // bitmap dwords per position
-//     FOLD2 (with FOLD): the two-holder pair.  A third bitmap, fed by what the atomicOr into "seen twice" returns, holds
-//                   the values with at least three holders; they alone keep codes 2 + rank (among themselves), and a
-//                   value with one or two holders is 0 in `out` and 1 in `out_q`.  Every two-holder value is an event:
-//                   its rank among the position's two-holder values names a pair of LDS slots, the samples that hold it
-//                   atomicMin / atomicMax themselves into them, and the workgroup appends (hi, lo, k) to ev.raw and
-//                   counts the event's bucket (ppk_db::d_fold2_ev).
-//   The count pass leaves E2 = S3 + 2 behind E in the same form, behind that the most two-holder values of any
-//   position and their number over all positions (PPK_RANK_EXTRA words), and behind those E2 of every position,
-//   [k][64 * s64]: what ppk_db_create sorts the positions of the two-holder pair by.
-//     FOLD2 with `bytes`: no planes are written; the ref-side code of stored position i of k goes to
-//                   bytes[(k * 64 * s64 + i) * npad + sample] (padding samples 0), for fold2_slice_kernel.
-struct Fold2Emit {
-  unsigned long long *raw;      // hi | lo << 28 | k << 56
-  unsigned *count;              // events appended so far
-  unsigned *bucket;             // events per bucket (lo / 32) * rt + hi / 256
-  unsigned cap, rt;
-};
-template <bool WRITE, bool FOLD = false, bool FOLD2 = false>
-__global__ void __launch_bounds__(256)
-rank_code_kernel(const uint64_t *__restrict__ skT, uint8_t *__restrict__ out, uint8_t *__restrict__ out_q,
-                 unsigned *__restrict__ max_distinct, size_t n, size_t npad, int s64, int pl, const Fold2Emit ev,
-                 uint8_t *__restrict__ bytes = nullptr) {
-  static_assert(!FOLD2 || (WRITE && FOLD), "the two-holder pair is a folded pair");
-  constexpr bool TWICE = !WRITE || FOLD;
-  constexpr bool THRICE = !WRITE || FOLD2;
-  constexpr int SLOTS = PPK_FOLD2_SLOTS;
-  __shared__ uint32_t bitmap[8][RANK_BMW];                 // (FOLD2, after the feed: the values with exactly two holders)
-  __shared__ uint32_t twice[TWICE ? 8 : 1][RANK_BMW];      // values with at least two holders
-  __shared__ uint32_t thrice[THRICE ? 8 : 1][RANK_BMW];    // values with at least three holders
-  __shared__ uint16_t before[WRITE ? 8 : 1][RANK_BMW];     // coded values (distinct; FOLD: shared; FOLD2: thrice held) below the dword's first one
-  __shared__ uint16_t before2[FOLD2 ? 8 : 1][RANK_BMW];    // two-holder values below the dword's first one
-  __shared__ uint32_t ev_lo[FOLD2 ? 8 : 1][FOLD2 ? SLOTS : 1], ev_hi[FOLD2 ? 8 : 1][FOLD2 ? SLOTS : 1];
-  __shared__ uint32_t ev_n[8], ev_base[8];
-  const int g = blockIdx.x & 7;
-  const size_t kb = blockIdx.x >> 3;            // k * s64 + block
-  const uint64_t *src = skT + kb * RANK_BB * npad;
-  for (int i = threadIdx.x; i < 8 * RANK_BMW; i += 256) {
-    (&bitmap[0][0])[i] = 0;
-    if (TWICE) (&twice[0][0])[i] = 0;
-    if (THRICE) (&thrice[0][0])[i] = 0;
-  }
-  if constexpr (FOLD2) {
-    for (int i = threadIdx.x; i < 8 * SLOTS; i += 256) {
-      (&ev_lo[0][0])[i] = 0xffffffffu;
-      (&ev_hi[0][0])[i] = 0;
-    }
-  }
-  __syncthreads();
-  auto values = [&](size_t smp, uint32_t (&v)[8]) {
-    uint32_t byte[RANK_BB];
-#pragma unroll
-    for (int b = 0; b < RANK_BB; ++b) byte[b] = (uint32_t)(src[(size_t)b * npad + smp] >> (8 * g)) & 0xffu;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      v[j] = 0;
-#pragma unroll
-      for (int b = 0; b < RANK_BB; ++b) v[j] |= ((byte[b] >> j) & 1u) << b;
-    }
-  };
-  for (size_t smp = threadIdx.x; smp < n; smp += 256) {
-    uint32_t v[8];
-    values(smp, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t bit = 1u << (v[j] & 31u);
-      const uint32_t old = atomicOr(&bitmap[j][v[j] >> 5], bit);
-      if (TWICE && (old & bit)) {
-        const uint32_t old2 = atomicOr(&twice[j][v[j] >> 5], bit);
-        if (THRICE && (old2 & bit)) atomicOr(&thrice[j][v[j] >> 5], bit);
-      }
-    }
-  }
-  __syncthreads();
-  // 32 threads per position, 16 consecutive dwords each: an exclusive prefix sum of their popcounts
-  {
-    const int j = threadIdx.x >> 5, t = threadIdx.x & 31;
-    auto prefix = [&](const uint32_t *bm, uint32_t &sum) {
-      sum = 0;
-      for (int w = 0; w < RANK_BMW / 32; ++w) sum += __popc(bm[t * (RANK_BMW / 32) + w]);
-      uint32_t incl = sum;
-#pragma unroll
-      for (int d = 1; d < 32; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 32);
-        if (t >= d) incl += up;
-      }
-      return incl;
-    };
-    if constexpr (!WRITE) {
-      uint32_t sum;
-      const uint32_t d_incl = prefix(bitmap[j], sum), s_incl = prefix(twice[j], sum), s3_incl = prefix(thrice[j], sum);
-      if (t == 31) {
-        const unsigned seg = 1 + gridDim.x / 8;
-        unsigned *max_fold = max_distinct + seg, *max_fold2 = max_distinct + 2 * seg, *extra = max_distinct + 3 * seg;
-        atomicMax(max_distinct, d_incl);
-        atomicMax(max_distinct + 1 + kb, d_incl);
-        atomicMax(max_fold, s_incl + 2u);
-        atomicMax(max_fold + 1 + kb, s_incl + 2u);
-        atomicMax(max_fold2, s3_incl + 2u);
-        atomicMax(max_fold2 + 1 + kb, s3_incl + 2u);
-        atomicMax(extra, s_incl - s3_incl);
-        atomicAdd(extra + 1, s_incl - s3_incl);
-        extra[PPK_RANK_EXTRA + kb * 64 + (size_t)(g * 8 + j)] = s3_incl + 2u;
-      }
-      return;
-    } else {
-      if constexpr (FOLD2) {
-        for (int w = 0; w < RANK_BMW / 32; ++w) {
-          const int i = t * (RANK_BMW / 32) + w;
-          bitmap[j][i] = twice[j][i] & ~thrice[j][i];      // (this thread's own 16 dwords, read back below)
-        }
-      }
-      auto ranks = [&](const uint32_t *bm, uint16_t *bef) {
-        uint32_t sum;
-        const uint32_t incl = prefix(bm, sum);
-        uint32_t run = incl - sum;
-        for (int w = 0; w < RANK_BMW / 32; ++w) {
-          bef[t * (RANK_BMW / 32) + w] = (uint16_t)run;
-          run += __popc(bm[t * (RANK_BMW / 32) + w]);
-        }
-        return incl;
-      };
-      ranks(FOLD2 ? thrice[j] : FOLD ? twice[j] : bitmap[j], before[j]);
-      if constexpr (FOLD2) {
-        const uint32_t two_incl = ranks(bitmap[j], before2[j]);
-        if (t == 31) ev_n[j] = two_incl < (uint32_t)SLOTS ? two_incl : (uint32_t)SLOTS;      // (the caller has checked: never above)
-      }
-    }
-  }
-  __syncthreads();
-  uint8_t *dst = out + kb * (size_t)pl * npad * 8 + g;
-  uint8_t *dst_q = FOLD ? out_q + kb * (size_t)pl * npad * 8 + g : nullptr;
-  for (size_t smp = threadIdx.x; smp < npad; smp += 256) {
-    uint32_t code[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t single = 0;      // FOLD: bit j set where the sample's value at position j has no other holder (FOLD2: at most one)
-    if (smp < n) {
-      uint32_t v[8];
-      values(smp, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const uint32_t w = v[j] >> 5, bit = 1u << (v[j] & 31u);
-        if constexpr (FOLD2) {
-          if (thrice[j][w] & bit) {
-            code[j] = 2u + before[j][w] + __popc(thrice[j][w] & (bit - 1u));
-          } else {
-            single |= 1u << j;
-            if (bitmap[j][w] & bit) {
-              const uint32_t slot = before2[j][w] + __popc(bitmap[j][w] & (bit - 1u));
-              if (slot < (uint32_t)SLOTS) {
-                atomicMin(&ev_lo[j][slot], (uint32_t)smp);
-                atomicMax(&ev_hi[j][slot], (uint32_t)smp);
-              }
-            }
-          }
-        } else if constexpr (FOLD) {
-          if (twice[j][w] & bit) code[j] = 2u + before[j][w] + __popc(twice[j][w] & (bit - 1u));
-          else single |= 1u << j;
-        } else {
-          code[j] = before[j][w] + __popc(bitmap[j][w] & (bit - 1u));
-        }
-      }
-    }
-    if constexpr (FOLD2) {
-      if (bytes) {      // (workgroup-uniform)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) bytes[(kb * 64 + (size_t)(g * 8 + j)) * npad + smp] = (uint8_t)code[j];
-        continue;
-      }
-    }
-    for (int b = 0; b < pl; ++b) {
-      uint32_t byte = 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) byte |= ((code[j] >> b) & 1u) << j;
-      dst[((size_t)b * npad + smp) * 8] = (uint8_t)byte;
-      // (a shared code is the same on both sides; a single holder's differs in bit 0 alone)
-      if constexpr (FOLD) dst_q[((size_t)b * npad + smp) * 8] = (uint8_t)(b == 0 ? byte | single : byte);
-    }
-  }
-  if constexpr (FOLD2) {
-    // one event per two-holder value: one reservation per workgroup, then 32 threads per position
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t total = 0;
-      for (int j = 0; j < 8; ++j) {
-        ev_base[j] = total;
-        total += ev_n[j];
-      }
-      const uint32_t at = total ? atomicAdd(ev.count, total) : 0u;
-      for (int j = 0; j < 8; ++j) ev_base[j] += at;
-    }
-    __syncthreads();
-    const int j = threadIdx.x >> 5;
-    const unsigned long long k = kb / (size_t)s64;
-    for (uint32_t slot = threadIdx.x & 31; slot < ev_n[j]; slot += 32) {
-      const uint32_t hi = ev_hi[j][slot], lo = ev_lo[j][slot], at = ev_base[j] + slot;
-      if (at >= ev.cap) continue;
-      if (hi < n && lo < hi) {
-        ev.raw[at] = (unsigned long long)hi | ((unsigned long long)lo << 28) | (k << 56);
-        atomicAdd(ev.bucket + (size_t)(lo >> 5) * ev.rt + (hi >> 8), 1u);
-      } else {
-        ev.raw[at] = ~0ull;      // (not two holders after all: never -- the scatter reports it, the pair is dropped)
-      }
-    }
-  }
-}
-
-// The planes of the two-holder pair with its positions in sorted order (ppk_db::fold2_order): slot i of k holds stored
-// position order[k * 64 * s64 + i].  One workgroup per (k, destination block, byte g of its words) and 256 samples; a
-// thread gathers its sample's 8 byte codes (rank_code_kernel with `bytes`) and writes byte g of the `pl` planes of both
-// copies, laid out as rank_code_kernel writes them.  A code is 0 or at least 2: 0 is 1 on the query side (samples below n).
-__global__ void __launch_bounds__(256)
-fold2_slice_kernel(const uint8_t *__restrict__ bytes, const unsigned *__restrict__ order, uint8_t *__restrict__ out,
-                   uint8_t *__restrict__ out_q, size_t n, size_t npad, int s64, int pl) {
-  const int g = blockIdx.x & 7;
-  const size_t kb = blockIdx.x >> 3, k = kb / (size_t)s64, nbins = 64 * (size_t)s64;
-  const size_t smp = (size_t)blockIdx.y * 256 + threadIdx.x;
-  if (smp >= npad) return;
-  const unsigned *ord = order + k * nbins + (kb % (size_t)s64) * 64 + (size_t)g * 8;
-  uint32_t code[8], single = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const size_t pos = ord[j] < nbins ? ord[j] : 0;      // (a permutation of [0, nbins): always below)
-    code[j] = bytes[(k * nbins + pos) * npad + smp];
-    if (smp < n && code[j] == 0) single |= 1u << j;
-  }
-  uint8_t *dst = out + kb * (size_t)pl * npad * 8 + g, *dst_q = out_q + kb * (size_t)pl * npad * 8 + g;
-  for (int b = 0; b < pl; ++b) {
-    uint32_t byte = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) byte |= ((code[j] >> b) & 1u) << j;
-    dst[((size_t)b * npad + smp) * 8] = (uint8_t)byte;
-    dst_q[((size_t)b * npad + smp) * 8] = (uint8_t)(b == 0 ? byte | single : byte);
-  }
-}
-
-constexpr int FOLD2_TILE_PAIRS = 256 * 32;      // pairs of one (256 refs x 32 queries) tile: 13 bits of an event
-// The counting sort of the events into their buckets (ppk_db::d_fold2_ev) and the check of the per-pair cap.
-// fold2_scan_kernel: one workgroup; off = exclusive prefix sum of cnt (nb entries, off[nb] = the total), cnt back to
-// zero for the scatter's cursors.
-__global__ void __launch_bounds__(1024)
-fold2_scan_kernel(unsigned *__restrict__ cnt, unsigned *__restrict__ off, size_t nb) {
-  __shared__ unsigned part[1024];
-  const size_t per = (nb + 1023) / 1024, b0 = threadIdx.x * per, b1 = b0 + per < nb ? b0 + per : nb;
-  unsigned sum = 0;
-  for (size_t b = b0; b < b1; ++b) sum += cnt[b];
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const unsigned up = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0u;
-    __syncthreads();
-    part[threadIdx.x] += up;
-    __syncthreads();
-  }
-  unsigned run = part[threadIdx.x] - sum;
-  for (size_t b = b0; b < b1; ++b) {
-    off[b] = run;
-    run += cnt[b];
-    cnt[b] = 0;
-  }
-  if (threadIdx.x == 1023) off[nb] = part[1023];
-}
-__global__ void __launch_bounds__(256)
-fold2_scatter_kernel(const unsigned long long *__restrict__ raw, unsigned *n_raw, unsigned cap,
-                     const unsigned *__restrict__ off, unsigned *__restrict__ cursor, uint16_t *__restrict__ ev, unsigned rt) {
-  const unsigned i = blockIdx.x * 256u + threadIdx.x, total = *n_raw < cap ? *n_raw : cap;
-  if (i >= total) return;
-  const unsigned long long e = raw[i];
-  if (e == ~0ull) {
-    n_raw[1] = 1u;      // the overflow flag sits behind the counter
-    return;
-  }
-  const uint32_t hi = (uint32_t)e & 0xfffffffu, lo = (uint32_t)(e >> 28) & 0xfffffffu, k = (uint32_t)(e >> 56);
-  const size_t b = (size_t)(lo >> 5) * rt + (hi >> 8);
-  const unsigned at = off[b] + atomicAdd(cursor + b, 1u);
-  if (at < off[b + 1]) ev[at] = (uint16_t)((hi & 255u) | ((lo & 31u) << 8) | (k << 13));
-}
-// one workgroup per bucket, the tile kernel's own correction words: a field that is asked to count past 63 sets *overflow
-__global__ void __launch_bounds__(256)
-fold2_check_kernel(const uint16_t *__restrict__ ev, const unsigned *__restrict__ off, unsigned *__restrict__ overflow) {
-  __shared__ uint32_t corr[FOLD2_TILE_PAIRS];
-  const unsigned e0 = off[blockIdx.x], e1 = off[blockIdx.x + 1];
-  if (e0 == e1) return;      // (workgroup-uniform)
-  for (int i = threadIdx.x; i < FOLD2_TILE_PAIRS; i += 256) corr[i] = 0;
-  __syncthreads();
-  for (unsigned e = e0 + threadIdx.x; e < e1; e += 256) {
-    const uint32_t v = ev[e], k = v >> 13;
-    const uint32_t old = atomicAdd(&corr[v & 0x1fffu], 1u << (6u * k));
-    if (((old >> (6u * k)) & 63u) == (uint32_t)PPK_FOLD2_MAX_PER_PAIR) *overflow = 1u;
-  }
-}
-
-// ---- the holder pair (ppk_db::d_foldhR ...) ---------------------------------------------------------------------------
-// Holder counts.  One workgroup per (k, 64-bin block, byte g) = 8 positions, as rank_code_kernel: a first pass over the
-// samples leaves the bitmap of the values at least two samples hold (the position's SHARED values), a prefix popcount
-// ranks them, and a second pass counts every shared value's holders in an LDS counter named by its rank (the caller
-// has checked that no position has more than PPK_FOLDH_SLOTS shared values).  Out: the bitmap, twice[position][512];
-// the counts in rank order, saturated at 65 535, holders[position][PPK_FOLDH_SLOTS]; and per position and bound H of
-// `ladder` E_H = (values with more than H holders) + 2, pos_e[position][PPK_FOLDH_LADDER].
-struct FoldhLadder {
-  unsigned h[PPK_FOLDH_LADDER];
-};
-__device__ __forceinline__ void foldh_values(const uint64_t *src, size_t npad, size_t smp, int g, uint32_t (&v)[8]) {
-  uint32_t byte[RANK_BB];
-#pragma unroll
-  for (int b = 0; b < RANK_BB; ++b) byte[b] = (uint32_t)(src[(size_t)b * npad + smp] >> (8 * g)) & 0xffu;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    v[j] = 0;
-#pragma unroll
-    for (int b = 0; b < RANK_BB; ++b) v[j] |= ((byte[b] >> j) & 1u) << b;
-  }
-}
-// 32 threads per position (t = their index), 16 consecutive dwords each: before[i] = set bits below dword i
-__device__ __forceinline__ void foldh_rank_bitmap(const uint32_t *bm, uint16_t *bef, int t) {
-  uint32_t sum = 0;
-  for (int w = 0; w < RANK_BMW / 32; ++w) sum += __popc(bm[t * (RANK_BMW / 32) + w]);
-  uint32_t incl = sum;
-#pragma unroll
-  for (int d = 1; d < 32; d <<= 1) {
-    const uint32_t up = __shfl_up(incl, d, 32);
-    if (t >= d) incl += up;
-  }
-  uint32_t run = incl - sum;
-  for (int w = 0; w < RANK_BMW / 32; ++w) {
-    bef[t * (RANK_BMW / 32) + w] = (uint16_t)run;
-    run += __popc(bm[t * (RANK_BMW / 32) + w]);
-  }
-}
-__global__ void __launch_bounds__(256)
-foldh_count_kernel(const uint64_t *__restrict__ skT, unsigned *__restrict__ twice_out, uint16_t *__restrict__ holders,
-                   unsigned *__restrict__ pos_e, size_t n, size_t npad, const FoldhLadder ladder) {
-  constexpr int SLOTS = PPK_FOLDH_SLOTS;
-  __shared__ uint32_t bitmap[8][RANK_BMW];
-  __shared__ uint32_t twice[8][RANK_BMW];
-  __shared__ uint16_t before[8][RANK_BMW];
-  __shared__ uint32_t cnt[8][SLOTS];
-  const int g = blockIdx.x & 7;
-  const size_t kb = blockIdx.x >> 3;            // k * s64 + block
-  const uint64_t *src = skT + kb * RANK_BB * npad;
-  for (int i = threadIdx.x; i < 8 * RANK_BMW; i += 256) {
-    (&bitmap[0][0])[i] = 0;
-    (&twice[0][0])[i] = 0;
-  }
-  for (int i = threadIdx.x; i < 8 * SLOTS; i += 256) (&cnt[0][0])[i] = 0;
-  __syncthreads();
-  for (size_t smp = threadIdx.x; smp < n; smp += 256) {
-    uint32_t v[8];
-    foldh_values(src, npad, smp, g, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t bit = 1u << (v[j] & 31u);
-      const uint32_t old = atomicOr(&bitmap[j][v[j] >> 5], bit);
-      if (old & bit) atomicOr(&twice[j][v[j] >> 5], bit);
-    }
-  }
-  __syncthreads();
-  const int pj = threadIdx.x >> 5, t = threadIdx.x & 31;
-  foldh_rank_bitmap(twice[pj], before[pj], t);
-  __syncthreads();
-  for (size_t smp = threadIdx.x; smp < n; smp += 256) {
-    uint32_t v[8];
-    foldh_values(src, npad, smp, g, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t w = v[j] >> 5, bit = 1u << (v[j] & 31u);
-      if (twice[j][w] & bit) {
-        const uint32_t slot = before[j][w] + __popc(twice[j][w] & (bit - 1u));
-        if (slot < (uint32_t)SLOTS) atomicAdd(&cnt[j][slot], 1u);
-      }
-    }
-  }
-  __syncthreads();
-  const size_t pos = kb * 64 + (size_t)(g * 8 + pj);
-  unsigned above[PPK_FOLDH_LADDER];
-#pragma unroll
-  for (int i = 0; i < PPK_FOLDH_LADDER; ++i) above[i] = 0;
-  for (int sl = t; sl < SLOTS; sl += 32) {
-    const uint32_t c = cnt[pj][sl];
-    holders[pos * SLOTS + sl] = (uint16_t)(c < 65535u ? c : 65535u);
-#pragma unroll
-    for (int i = 0; i < PPK_FOLDH_LADDER; ++i) above[i] += c > ladder.h[i] ? 1u : 0u;
-  }
-  for (int w = t; w < RANK_BMW; w += 32) twice_out[pos * RANK_BMW + w] = twice[pj][w];
-#pragma unroll
-  for (int i = 0; i < PPK_FOLDH_LADDER; ++i) {
-#pragma unroll
-    for (int d = 16; d > 0; d >>= 1) above[i] += __shfl_down(above[i], d, 32);
-    if (t == 0) pos_e[pos * PPK_FOLDH_LADDER + i] = above[i] + 2u;
-  }
-}
-
-// Codes.  Same grid; reads the count pass's bitmap and holder counts back.  Per position the shared values split in two
-// classes, each ranked in value order: KEPT (more than H holders) and FOLDED (2 .. H).  Two codes per (position, sample):
-//   kept_out  (one byte, for fold2_slice_kernel): 2 + rank of a kept value, 0 for every other -- the holder pair;
-//   owed_out  (16 bits, for foldh_slice14_kernel): 2 + rank of a folded value, 0 for every other -- the temporary pair,
-//             whose compare counts exactly the matches the holder pair cannot see.
-// Padding samples get 0 in both.
-__global__ void __launch_bounds__(256)
-foldh_code_kernel(const uint64_t *__restrict__ skT, const unsigned *__restrict__ twice_in, const uint16_t *__restrict__ holders,
-                  uint8_t *__restrict__ kept_out, uint16_t *__restrict__ owed_out, size_t n, size_t npad, unsigned H) {
-  constexpr int SLOTS = PPK_FOLDH_SLOTS;
-  __shared__ uint32_t twice[8][RANK_BMW];
-  __shared__ uint16_t before[8][RANK_BMW];
-  __shared__ uint16_t code[8][SLOTS];      // bit 15: kept; below it the rank within the class
-  const int g = blockIdx.x & 7;
-  const size_t kb = blockIdx.x >> 3;
-  const uint64_t *src = skT + kb * RANK_BB * npad;
-  const int pj = threadIdx.x >> 5, t = threadIdx.x & 31;
-  const size_t pos = kb * 64 + (size_t)(g * 8 + pj);
-  for (int w = t; w < RANK_BMW; w += 32) twice[pj][w] = twice_in[pos * RANK_BMW + w];
-  __syncthreads();
-  foldh_rank_bitmap(twice[pj], before[pj], t);
-  {
-    // thread t ranks slots [t * 32, t * 32 + 32) (slots past the position's shared values hold 0 holders: never read)
-    constexpr int PER = SLOTS / 32;
-    uint32_t kept = 0, folded = 0;
-    for (int i = 0; i < PER; ++i) {
-      const uint32_t c = holders[pos * SLOTS + t * PER + i];
-      kept += c > H ? 1u : 0u;
-      folded += c >= 2u && c <= H ? 1u : 0u;
-    }
-    uint32_t packed = kept | (folded << 16), incl = packed;
-#pragma unroll
-    for (int d = 1; d < 32; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, 32);
-      if (t >= d) incl += up;
-    }
-    uint32_t run_k = (incl - packed) & 0xffffu, run_f = (incl - packed) >> 16;
-    for (int i = 0; i < PER; ++i) {
-      const uint32_t c = holders[pos * SLOTS + t * PER + i];
-      if (c > H) code[pj][t * PER + i] = (uint16_t)(0x8000u | run_k++);
-      else code[pj][t * PER + i] = (uint16_t)(c >= 2u ? run_f++ : 0x7fffu);
-    }
-  }
-  __syncthreads();
-  for (size_t smp = threadIdx.x; smp < npad; smp += 256) {
-    uint32_t ck[8] = {0, 0, 0, 0, 0, 0, 0, 0}, co[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (smp < n) {
-      uint32_t v[8];
-      foldh_values(src, npad, smp, g, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const uint32_t w = v[j] >> 5, bit = 1u << (v[j] & 31u);
-        if (twice[j][w] & bit) {
-          const uint32_t slot = before[j][w] + __popc(twice[j][w] & (bit - 1u));
-          const uint32_t c = slot < (uint32_t)SLOTS ? code[j][slot] : 0x7fffu;
-          if (c & 0x8000u) ck[j] = 2u + (c & 0x7fffu);
-          else if (c != 0x7fffu) co[j] = 2u + c;
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const size_t at = (kb * 64 + (size_t)(g * 8 + j)) * npad + smp;
-      kept_out[at] = (uint8_t)ck[j];
-      owed_out[at] = (uint16_t)co[j];
-    }
-  }
-}
-
-// The temporary pair in the raw 14-plane layout, positions in stored order: [k][block * 14 + plane][npad], byte g of
-// both copies per workgroup and 256 samples (fold2_slice_kernel for 16-bit codes).  0 is 1 on the query side.
-__global__ void __launch_bounds__(256)
-foldh_slice14_kernel(const uint16_t *__restrict__ codes, uint8_t *__restrict__ out, uint8_t *__restrict__ out_q, size_t n,
-                     size_t npad) {
-  const int g = blockIdx.x & 7;
-  const size_t kb = blockIdx.x >> 3;
-  const size_t smp = (size_t)blockIdx.y * 256 + threadIdx.x;
-  if (smp >= npad) return;
-  uint32_t code[8], single = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    code[j] = codes[(kb * 64 + (size_t)(g * 8 + j)) * npad + smp];
-    if (smp < n && code[j] == 0) single |= 1u << j;
-  }
-  uint8_t *dst = out + kb * (size_t)RANK_BB * npad * 8 + g, *dst_q = out_q + kb * (size_t)RANK_BB * npad * 8 + g;
-#pragma unroll
-  for (int b = 0; b < RANK_BB; ++b) {
-    uint32_t byte = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) byte |= ((code[j] >> b) & 1u) << j;
-    dst[((size_t)b * npad + smp) * 8] = (uint8_t)byte;
-    dst_q[((size_t)b * npad + smp) * 8] = (uint8_t)(b == 0 ? byte | single : byte);
-  }
-}
-
-// One band of the temporary pair's counts (the tile kernel's MODE_COUNTS rows: row * nk + k) into raw entries
-// hi | lo << 24 | k << 48 | count << 52.  One workgroup per bucket -- 32 queries from q_begin + 32 * blockIdx.y, the 256
-// refs of ref block blockIdx.x, thread t its ref -- so a bucket's count is its workgroup's total, written without an
-// atomic, and the list is appended to through ONE reservation per workgroup (a reservation per wavefront, 780 000 adds
-// to one address at the bench shape, took 8 ms).  Two passes over the bucket's 160 KB of counts: count, then write.
-struct FoldhEmit {
-  unsigned long long *raw;
-  unsigned long long *count;    // entries appended so far (may pass cap: the caller then drops the pair)
-  unsigned *bucket;             // entries per bucket (lo / 32) * rt + hi / 256
-  unsigned long long cap;
-  unsigned rt;
-};
-__global__ void __launch_bounds__(256)
-foldh_emit_kernel(const uint32_t *__restrict__ counts, size_t n, size_t q_begin, size_t q_end, size_t row_base, int nk,
-                  const FoldhEmit ev) {
-  __shared__ uint32_t part[256];
-  __shared__ unsigned long long base_s;
-  const size_t q0 = q_begin + (size_t)blockIdx.y * 32, rf = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if ((size_t)blockIdx.x * 256 + 255 <= q0) return;      // (workgroup-uniform: no ref above the bucket's first query)
-  const size_t q1 = q0 + 32 < q_end ? q0 + 32 : q_end;
-  uint32_t mine = 0;
-  if (rf < n)
-    for (size_t qq = q0; qq < q1 && qq < rf; ++qq) {
-      const uint32_t *c = counts + (qq * n - (qq * (qq + 1)) / 2 + (rf - qq - 1) - row_base) * (size_t)nk;
-      for (int k = 0; k < nk; ++k) mine += c[k] != 0 ? 1u : 0u;
-    }
-  part[threadIdx.x] = mine;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const uint32_t up = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0u;
-    __syncthreads();
-    part[threadIdx.x] += up;
-    __syncthreads();
-  }
-  const uint32_t total = part[255];
-  if (total == 0) return;      // (workgroup-uniform)
-  if (threadIdx.x == 0) {
-    base_s = atomicAdd(ev.count, (unsigned long long)total);
-    ev.bucket[(size_t)(q0 >> 5) * ev.rt + blockIdx.x] = total;
-  }
-  __syncthreads();
-  unsigned long long at = base_s + (part[threadIdx.x] - mine);
-  if (rf < n && mine)
-    for (size_t qq = q0; qq < q1 && qq < rf; ++qq) {
-      const uint32_t *c = counts + (qq * n - (qq * (qq + 1)) / 2 + (rf - qq - 1) - row_base) * (size_t)nk;
-      for (int k = 0; k < nk; ++k)
-        if (c[k] != 0) {
-          if (at < ev.cap)
-            ev.raw[at] = (unsigned long long)rf | ((unsigned long long)qq << 24) | ((unsigned long long)k << 48) |
-                         ((unsigned long long)(c[k] & 4095u) << 52);
-          ++at;
-        }
-    }
-}
-__global__ void __launch_bounds__(256)
-foldh_scatter_kernel(const unsigned long long *__restrict__ raw, size_t total, const unsigned *__restrict__ off,
-                     unsigned *__restrict__ cursor, uint32_t *__restrict__ ent, unsigned rt) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const unsigned long long e = raw[i];
-  const uint32_t hi = (uint32_t)e & 0xffffffu, lo = (uint32_t)(e >> 24) & 0xffffffu, k = (uint32_t)(e >> 48) & 7u, c = (uint32_t)(e >> 52);
-  const size_t b = (size_t)(lo >> 5) * rt + (hi >> 8);
-  const unsigned at = off[b] + atomicAdd(cursor + b, 1u);
-  if (at < off[b + 1]) ent[at] = (hi & 255u) | ((lo & 31u) << 8) | (k << 13) | (c << 16);
 }
 
 // LUT[(cr*C + cq)][k][count] = log J, or +1.0 when J < 5/nbins (the point and
@@ -1489,7 +921,7 @@ dist_kernel_v2(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ q
 #include "ppk_dist_tile.inc"
 }
 
-// The whole-tile kernel of the two-dword count register on a rank-coded database: refT / qryT are ppk_db::d_skR,
+// The whole-tile kernel of the two-dword count register on a rank-coded database: refT / qryT are the injective copy (PpkCoding),
 // [k][block * PL + plane][npad].  Same arguments at the same kernarg offsets (the epilogue reads DistParams there).
 template <int PL, int MODE>
 __global__ void __launch_bounds__(8 * 64, 4)
@@ -1503,7 +935,7 @@ dist_kernel_v2_rank(const uint64_t *__restrict__ refT, const uint64_t *__restric
 #include "ppk_dist_tile.inc"
 }
 
-// The same kernel at 8 planes on the two-holder pair (ppk_db::d_fold2R / d_fold2Q): FOLD2 compiles one more block into
+// The same kernel at 8 planes on the two-holder pair (PPK_CODING_FOLD2): FOLD2 compiles one more block into
 // the body, at the top of the epilogue, which adds the tile's events (DistParams::fold2_ev) to the counts.  A kernel of
 // its own name: dist_kernel_v2_rank<PL, MODE> stays the code (and the symbols) it was.
 template <int MODE>
@@ -1518,9 +950,9 @@ dist_kernel_v2_fold2(const uint64_t *__restrict__ refT, const uint64_t *__restri
 #include "ppk_dist_tile.inc"
 }
 
-// The same kernel on the holder pair (ppk_db::d_foldhR / d_foldhQ, an 8-plane chunk whose planes 4 .. 7 are zero):
+// The same kernel on the holder pair (PPK_CODING_FOLDH, an 8-plane chunk whose planes 4 .. 7 are zero):
 // FOLDH swaps the three streams for the 4- / 3- / 2-plane ones and the correction block for the one that adds the
-// database's 12-bit entries (DistParams::fold2_ev / fold2_off carry d_foldh_ent / d_foldh_off; rank_short / fold2_six
+// database's 12-bit entries (DistParams::fold2_ev / fold2_off carry its d_list / d_off; rank_short / fold2_six
 // the 3- and the 2-plane flags).  A kernel of its own name again: every other symbol stays the code it was.
 template <int MODE>
 __global__ void __launch_bounds__(8 * 64, 4)
@@ -2067,46 +1499,33 @@ int launch_wide(int dev, const PpkGeometry &geo, const DistArgs &a, DistParams &
 
 // A self job on a rank-coded database (ppk_db_create) compares the codes: 8, 10 or 12 planes per block instead of
 // 14, the same counts.  (ref x query jobs would need one code for two databases; k-split jobs have their own kernels.)
-// The folded pair (d_foldR / d_foldQ) serves the triangular job alone: every pair it compares is two different
-// samples, one from each copy.  A rectangular job of a handle against itself has the pairs (r, r), where a value
-// with a single holder must match itself: it reads the injective copy if there is one, else the raw planes.
-// The two-holder pair (d_fold2R / d_fold2Q, always 8 planes) serves the same job with the event list beside it.
-// The holder pair (d_foldhR / d_foldhQ, an 8-plane chunk of which at most 4 planes are compared) serves it before both.
-// Returns the planes of the copy this band reads (0: the raw planes) and which copy that is: 0 the injective one, 1 the
-// folded pair, 2 the two-holder pair, 3 the holder pair.
-int coded_planes(const ppk_db *ref, const ppk_db *qry, const DistParams &p, int *fold) {
-  const bool coded = (p.self || qry == ref) && !p.k_split && ppk_config().rank_planes.load() != 0;
-  *fold = !(coded && p.self)                                                    ? 0
-          : ref->foldh_planes != 0 && ppk_config().rank_foldh.load() != 0       ? 3
-          : ref->fold2_planes != 0 && ppk_config().rank_fold2.load() != 0       ? 2
-          : ref->fold_planes != 0 && ppk_config().rank_fold.load() != 0         ? 1
-                                                                                : 0;
-  return *fold == 3 ? ref->foldh_planes : *fold == 2 ? ref->fold2_planes : *fold == 1 ? ref->fold_planes : coded && ref->d_skR ? ref->rank_planes : 0;
+// The pairs (PpkCodingKind) serve the triangular job alone: every pair it compares is two different samples, one from
+// each copy; the latest kind the database holds and the options allow is read.  A rectangular job of a handle against
+// itself has the pairs (r, r), where a value with a single holder must match itself: it reads the injective copy if
+// there is one, else the raw planes.  Returns the coding this band reads (null: the raw planes).
+const PpkCoding *coded_planes(const ppk_db *ref, const ppk_db *qry, const DistParams &p) {
+  if (!(p.self || qry == ref) || p.k_split || !ppk_coding_enabled(PPK_CODING_RANK)) return nullptr;
+  for (int kind = PPK_CODING_FOLDH; p.self && kind > PPK_CODING_RANK; --kind)
+    if (ref->coding[kind].planes != 0 && ppk_coding_enabled(kind)) return &ref->coding[kind];
+  const PpkCoding &injective = ref->coding[PPK_CODING_RANK];
+  return injective.d_ref ? &injective : nullptr;
 }
 template <int MODE>
-int launch_rank(const ppk_db *ref, int planes, int fold, DistArgs a, DistParams &p, size_t n_blocks, hipStream_t s) {
-  a.sk_r = fold == 3 ? ref->d_foldhR : fold == 2 ? ref->d_fold2R : fold ? ref->d_foldR : ref->d_skR;
-  a.sk_q = fold == 3 ? ref->d_foldhQ : fold == 2 ? ref->d_fold2Q : fold ? ref->d_foldQ : ref->d_skR;
-  // the blocks that compare one plane fewer (option "rank_short", read here: one database runs either way)
-  const unsigned *flags = fold == 3 ? ref->foldh_three : fold == 2 ? ref->fold2_seven : fold ? ref->fold_short : ref->rank_short;
-  // (the holder pair: option "foldh_min_planes" 4 keeps every block at 4 planes, 3 the 2-plane blocks at 3)
-  const long long foldh_min = ppk_config().foldh_min_planes.load();
-  const bool use_short = ppk_config().rank_short.load() != 0 && !(fold == 3 && foldh_min > 3);
-  for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.rank_short[k] = use_short ? flags[k] : 0u;
+int launch_rank(const PpkCoding &c, DistArgs a, DistParams &p, size_t n_blocks, hipStream_t s) {
+  a.sk_r = c.d_ref;
+  a.sk_q = c.d_qry;
+  ppk_coding_launch_flags(c, p.rank_short, p.fold2_six);
   // (the holder pair's 32-bit entries travel in the event list's fields: dist_kernel_v2_foldh reads them as such)
-  p.fold2_ev = fold == 3 ? reinterpret_cast<const uint16_t *>(ref->d_foldh_ent) : fold == 2 ? ref->d_fold2_ev : nullptr;
-  p.fold2_off = fold == 3 ? ref->d_foldh_off : fold == 2 ? ref->d_fold2_off : nullptr;
-  p.fold2_rt = fold == 3 ? ref->foldh_rt : fold == 2 ? ref->fold2_rt : 0u;
-  // the two-holder pair: the blocks that compare 6 planes (option "fold2_min_planes", read here; 7 keeps them at 7)
-  const bool use_six = fold == 2 && use_short && ppk_config().fold2_min_planes.load() <= 6;
-  const bool use_two = fold == 3 && use_short && foldh_min <= 2;
-  for (int k = 0; k < PPK_RANK_SHORT_WORDS; ++k) p.fold2_six[k] = use_six ? ref->fold2_six[k] : use_two ? ref->foldh_two[k] : 0u;
-  const auto kernel = fold == 3      ? &dist_kernel_v2_foldh<MODE>
-                      : fold == 2    ? &dist_kernel_v2_fold2<MODE>
-                      : planes == 12 ? &dist_kernel_v2_rank<12, MODE>
-                      : planes == 10 ? &dist_kernel_v2_rank<10, MODE>
-                                     : &dist_kernel_v2_rank<8, MODE>;
-  const std::string name = "dist_kernel_v2<256x32,lds-dma,rank " + std::to_string(planes) + (fold == 3 ? ",foldh>" : fold == 2 ? ",fold2>" : fold ? ",fold>" : ">");
+  p.fold2_ev = static_cast<const uint16_t *>(c.d_list);
+  p.fold2_off = c.d_off;
+  p.fold2_rt = c.rt;
+  static const char *const suffix[PPK_CODINGS] = {">", ",fold>", ",fold2>", ",foldh>"};
+  const auto kernel = c.kind == PPK_CODING_FOLDH   ? &dist_kernel_v2_foldh<MODE>
+                      : c.kind == PPK_CODING_FOLD2 ? &dist_kernel_v2_fold2<MODE>
+                      : c.planes == 12             ? &dist_kernel_v2_rank<12, MODE>
+                      : c.planes == 10             ? &dist_kernel_v2_rank<10, MODE>
+                                                   : &dist_kernel_v2_rank<8, MODE>;
+  const std::string name = "dist_kernel_v2<256x32,lds-dma,rank " + std::to_string(c.planes) + suffix[c.kind];
   return launch_kernel(kernel, dim3((unsigned)n_blocks), dim3(8 * 64), name.c_str(), a, p, s);
 }
 
@@ -2134,8 +1553,7 @@ int launch_v2(const ppk_db *ref, const ppk_db *qry, const DistArgs &a, DistParam
     return launch_kernel(&dist_kernel_v2<NW, MODE, W, false, false, true>, grid, block, "dist_kernel_v2<256x32,lds-dma,exp>", a, p, s);
 #endif
   if constexpr (NW == 8 && W == 2 && !WIDE && kFits) {
-    int fold = 0;
-    if (const int planes = coded_planes(ref, qry, p, &fold)) return launch_rank<MODE>(ref, planes, fold, a, p, n_blocks, s);
+    if (const PpkCoding *c = coded_planes(ref, qry, p)) return launch_rank<MODE>(*c, a, p, n_blocks, s);
   }
   // (the counts pass of a two-pass k-split job: one workgroup per (tile, k))
   if constexpr (MODE == MODE_COUNTS && NW == 8)
@@ -2193,107 +1611,6 @@ int ppk_launch_transpose(const uint64_t *d_in, uint64_t *d_out, size_t n, size_t
   return PPK_OK;
 }
 
-// The rank codes of a transposed bbits = 14 database (rank_code_kernel): the count pass (d_max: 3 * (1 + nk * s64) +
-// PPK_RANK_EXTRA + nk * s64 * 64 words, the D maxima, behind them the E and the E2 maxima, then the two-holder figures
-// and E2 of every position), then -- with
-// `d_out` -- the code planes: injective, or with `d_out_q` the folded pair (d_out the ref side).  Both only enqueue.
-int ppk_launch_rank_count(const uint64_t *d_skT, size_t n, size_t npad, size_t nk, size_t s64, unsigned *d_max, hipStream_t s) {
-  PPK_HIP(hipMemsetAsync(d_max, 0, (3 * (1 + nk * s64) + PPK_RANK_EXTRA + nk * s64 * 64) * sizeof(unsigned), s));
-  hipLaunchKernelGGL((rank_code_kernel<false>), dim3((unsigned)(nk * s64 * 8)), dim3(256), 0, s, d_skT, nullptr, nullptr, d_max,
-                     n, npad, (int)s64, 0, Fold2Emit{});
-  PPK_HIP(hipGetLastError());
-  return PPK_OK;
-}
-int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, uint64_t *d_out_q, size_t n, size_t npad, size_t nk,
-                          size_t s64, int planes, hipStream_t s) {
-  const dim3 grid((unsigned)(nk * s64 * 8)), block(256);
-  if (d_out_q)
-    hipLaunchKernelGGL((rank_code_kernel<true, true>), grid, block, 0, s, d_skT, reinterpret_cast<uint8_t *>(d_out),
-                       reinterpret_cast<uint8_t *>(d_out_q), nullptr, n, npad, (int)s64, planes, Fold2Emit{});
-  else
-    hipLaunchKernelGGL((rank_code_kernel<true, false>), grid, block, 0, s, d_skT, reinterpret_cast<uint8_t *>(d_out), nullptr,
-                       nullptr, n, npad, (int)s64, planes, Fold2Emit{});
-  PPK_HIP(hipGetLastError());
-  return PPK_OK;
-}
-// The two-holder pair of `db` and its event list.  Everything is allocated here; a device too full for it, or a
-// (pair, k) with more events than its field holds (*overflow), leaves the database without the pair.  With `order`
-// (nk * 64 * s64 stored positions, a permutation per k) slot i of k holds stored position order[k * 64 * s64 + i]: the
-// code pass then leaves byte codes per stored position and fold2_slice_kernel gathers them into the planes (one byte
-// per (position, sample) of scratch, freed here).  Gathering inside the code pass would read every source word eight
-// times, once per position of the workgroup's byte.
-int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, const std::vector<unsigned> *order, bool *overflow, hipStream_t s) {
-  *overflow = false;
-  const size_t copy_bytes = db->npad * db->nk * db->s64 * (size_t)planes * sizeof(uint64_t);
-  const unsigned qt = (unsigned)(db->npad / 32), rt = (unsigned)(db->npad / V2_RT);
-  const size_t nb = (size_t)qt * rt, cap = n_two ? n_two : 1;
-  unsigned long long *d_raw = nullptr;
-  unsigned *d_cnt = nullptr;      // [nb] bucket counts / cursors, then the event counter and the overflow flag
-  uint8_t *d_bytes = nullptr;     // `order`: the byte codes per stored position
-  unsigned *d_order = nullptr;
-  const size_t n_pos = db->nk * db->s64 * 64;
-  auto drop = [&]() {
-    (void)hipGetLastError();
-    for (void *ptr : {(void *)db->d_fold2R, (void *)db->d_fold2Q, (void *)db->d_fold2_ev, (void *)db->d_fold2_off})
-      if (ptr) (void)hipFree(ptr);
-    db->d_fold2R = db->d_fold2Q = nullptr;
-    db->d_fold2_ev = nullptr;
-    db->d_fold2_off = nullptr;
-    db->fold2_planes = 0;
-  };
-  auto done = [&](int rc) {
-    if (d_raw) (void)hipFree(d_raw);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (d_bytes) (void)hipFree(d_bytes);
-    if (d_order) (void)hipFree(d_order);
-    return rc;
-  };
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&db->d_fold2R), copy_bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_fold2Q), copy_bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_fold2_ev), cap * sizeof(uint16_t));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_fold2_off), (nb + 1) * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_raw), cap * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), (nb + 2) * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (nb + 2) * sizeof(unsigned), s);
-  if (order && order->size() != n_pos) order = nullptr;
-  if (e == hipSuccess && order) e = hipMalloc(reinterpret_cast<void **>(&d_bytes), n_pos * db->npad);
-  if (e == hipSuccess && order) e = hipMalloc(reinterpret_cast<void **>(&d_order), n_pos * sizeof(unsigned));
-  if (e == hipSuccess && order) e = hipMemcpyAsync(d_order, order->data(), n_pos * sizeof(unsigned), hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    drop();
-    return done(PPK_OK);
-  }
-  const Fold2Emit ev = {d_raw, d_cnt + nb, d_cnt, (unsigned)cap, rt};
-  hipLaunchKernelGGL((rank_code_kernel<true, true, true>), dim3((unsigned)(db->nk * db->s64 * 8)), dim3(256), 0, s, db->d_skT,
-                     reinterpret_cast<uint8_t *>(db->d_fold2R), reinterpret_cast<uint8_t *>(db->d_fold2Q), nullptr, db->n,
-                     db->npad, (int)db->s64, planes, ev, d_bytes);
-  if (order)
-    hipLaunchKernelGGL(fold2_slice_kernel, dim3((unsigned)(db->nk * db->s64 * 8), (unsigned)(db->npad / 256)), dim3(256), 0, s,
-                       d_bytes, d_order, reinterpret_cast<uint8_t *>(db->d_fold2R), reinterpret_cast<uint8_t *>(db->d_fold2Q),
-                       db->n, db->npad, (int)db->s64, planes);
-  hipLaunchKernelGGL(fold2_scan_kernel, dim3(1), dim3(1024), 0, s, d_cnt, db->d_fold2_off, nb);
-  hipLaunchKernelGGL(fold2_scatter_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, d_raw, d_cnt + nb, (unsigned)cap,
-                     db->d_fold2_off, d_cnt, db->d_fold2_ev, rt);
-  hipLaunchKernelGGL(fold2_check_kernel, dim3((unsigned)nb), dim3(256), 0, s, db->d_fold2_ev, db->d_fold2_off, d_cnt + nb + 1);
-  unsigned tail[2] = {0, 0};      // events, overflow
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(tail, d_cnt + nb, sizeof(tail), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    drop();
-    return done(ppk_fail(PPK_ERR_HIP, std::string("two-holder pair: ") + hipGetErrorString(e)));
-  }
-  if (tail[1] || tail[0] != n_two) {      // (a count that differs from the count pass's: never -- the list would be incomplete)
-    *overflow = true;
-    drop();
-    return done(PPK_OK);
-  }
-  db->fold2_planes = planes;
-  db->fold2_qt = qt;
-  db->fold2_rt = rt;
-  db->fold2_events = n_two;
-  return done(PPK_OK);
-}
 // whether a self job over the whole of `db` runs whole 256 x 32 tiles of the two-dword count register under the
 // options in force: the one shape that reads a rank-coded copy (launch_v2)
 bool ppk_self_job_takes_tiles(const ppk_db *db) {
@@ -2618,49 +1935,9 @@ static int launch_dist_band(const DistJob &job) {
   return PPK_OK;
 }
 
-// ---- the holder pair: creation -------------------------------------------------------------------------------------------
-void ppk_drop_foldh(ppk_db *db) {
-  for (void *ptr : {(void *)db->d_foldhR, (void *)db->d_foldhQ, (void *)db->d_foldh_ent, (void *)db->d_foldh_off})
-    if (ptr) (void)hipFree(ptr);
-  db->d_foldhR = db->d_foldhQ = nullptr;
-  db->d_foldh_ent = nullptr;
-  db->d_foldh_off = nullptr;
-  db->foldh_planes = 0;
-  db->foldh_entries = 0;
-}
-int ppk_foldh_count(const ppk_db *db, const unsigned *ladder, unsigned **d_twice, uint16_t **d_holders, std::vector<unsigned> *pos_e,
-                    hipStream_t s) {
-  const size_t n_pos = db->nk * db->s64 * 64;
-  unsigned *d_e = nullptr;
-  *d_twice = nullptr;
-  *d_holders = nullptr;
-  pos_e->assign(n_pos * PPK_FOLDH_LADDER, 0u);
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(d_twice), n_pos * RANK_BMW * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(d_holders), n_pos * PPK_FOLDH_SLOTS * sizeof(uint16_t));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_e), pos_e->size() * sizeof(unsigned));
-  if (e == hipSuccess) {
-    FoldhLadder l;
-    for (int i = 0; i < PPK_FOLDH_LADDER; ++i) l.h[i] = ladder[i];
-    hipLaunchKernelGGL(foldh_count_kernel, dim3((unsigned)(db->nk * db->s64 * 8)), dim3(256), 0, s, db->d_skT, *d_twice, *d_holders,
-                       d_e, db->n, db->npad, l);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(pos_e->data(), d_e, pos_e->size() * sizeof(unsigned), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (d_e) (void)hipFree(d_e);
-  if (e != hipSuccess) {      // (a device too full for the pass: no holder pair, nothing else changes)
-    (void)hipGetLastError();
-    if (*d_twice) (void)hipFree(*d_twice);
-    if (*d_holders) (void)hipFree(*d_holders);
-    *d_twice = nullptr;
-    *d_holders = nullptr;
-    pos_e->clear();
-  }
-  return PPK_OK;
-}
-// one band of the temporary pair's counts: the raw-plane tile kernel in MODE_COUNTS, ref side d_r, query side d_q
-static int foldh_counts_band(const ppk_db *db, const uint64_t *d_r, const uint64_t *d_q, size_t q_begin, size_t q_end, void *d_cnt,
-                             hipStream_t s) {
+// one band of raw-plane counts of two given copies (the holder pair's temporary pair): the tile kernel in MODE_COUNTS
+int ppk_counts_band_raw(const ppk_db *db, const uint64_t *d_r, const uint64_t *d_q, size_t q_begin, size_t q_end, void *d_cnt,
+                        hipStream_t s) {
   DistParams p = {};
   p.self = 1;
   p.npad_r = p.npad_q = db->npad;
@@ -2675,86 +1952,6 @@ static int foldh_counts_band(const ppk_db *db, const uint64_t *d_r, const uint64
   const DistArgs a = {d_r, d_q, nullptr, nullptr, nullptr, nullptr, d_cnt, nullptr, nullptr};
   return launch_tiles_unpacked<MODE_COUNTS>(db, db, a, p, s);
 }
-int ppk_build_foldh(ppk_db *db, unsigned H, const unsigned *d_twice, const uint16_t *d_holders, size_t max_entries, hipStream_t s) {
-  const size_t n = db->n, npad = db->npad, n_pos = db->nk * db->s64 * 64, n_kb = db->nk * db->s64;
-  const size_t copy_bytes = npad * n_kb * 8 * sizeof(uint64_t), tmp_bytes = npad * n_kb * (size_t)RANK_BB * sizeof(uint64_t);
-  const unsigned qt = (unsigned)(npad / 32), rt = (unsigned)(npad / V2_RT);
-  const size_t nb = (size_t)qt * rt, cap = max_entries ? max_entries : 1;
-  // the counts of one band: at most 512 MB, whole blocks of 256 query rows, no more than a dispatch holds
-  size_t band_q = ((size_t)512 << 20) / (n * db->nk * 4) / 256 * 256;
-  if (band_q < 256) band_q = 256;
-  if (band_q > ppk_rows_per_dispatch(db)) band_q = ppk_rows_per_dispatch(db);
-  const size_t band_rows = ppk_rows_in_band(n, 0, 0, band_q < n ? band_q : n);      // (the first band is the longest)
-  uint8_t *d_kept = nullptr;
-  uint16_t *d_owed = nullptr;
-  unsigned *d_order = nullptr, *d_cnt = nullptr;      // d_cnt: [nb] bucket counts / cursors, then the 64-bit entry counter
-  uint64_t *d_tr = nullptr, *d_tq = nullptr;
-  unsigned long long *d_raw = nullptr;
-  void *d_band = nullptr;
-  auto done = [&](int rc, bool keep) {
-    for (void *ptr : {(void *)d_kept, (void *)d_owed, (void *)d_order, (void *)d_cnt, (void *)d_tr, (void *)d_tq, (void *)d_raw, d_band})
-      if (ptr) (void)hipFree(ptr);
-    if (!keep) {
-      (void)hipGetLastError();
-      ppk_drop_foldh(db);
-    }
-    return rc;
-  };
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&db->d_foldhR), copy_bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_foldhQ), copy_bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db->d_foldh_off), (nb + 1) * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_kept), n_pos * npad);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_owed), n_pos * npad * sizeof(uint16_t));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_order), n_pos * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), (nb + 2) * sizeof(unsigned) + 8);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_tr), tmp_bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_tq), tmp_bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_raw), cap * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc(&d_band, band_rows * db->nk * 4 + 256);
-  if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (nb + 2) * sizeof(unsigned) + 8, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_order, db->foldh_order.data(), n_pos * sizeof(unsigned), hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return done(PPK_OK, false);      // (a device too full: the pair only buys speed)
-  const dim3 grid_pos((unsigned)(n_kb * 8)), grid_slice((unsigned)(n_kb * 8), (unsigned)(npad / 256));
-  hipLaunchKernelGGL(foldh_code_kernel, grid_pos, dim3(256), 0, s, db->d_skT, d_twice, d_holders, d_kept, d_owed, n, npad, H);
-  hipLaunchKernelGGL(fold2_slice_kernel, grid_slice, dim3(256), 0, s, d_kept, d_order, reinterpret_cast<uint8_t *>(db->d_foldhR),
-                     reinterpret_cast<uint8_t *>(db->d_foldhQ), n, npad, (int)db->s64, 8);
-  hipLaunchKernelGGL(foldh_slice14_kernel, grid_slice, dim3(256), 0, s, d_owed, reinterpret_cast<uint8_t *>(d_tr),
-                     reinterpret_cast<uint8_t *>(d_tq), n, npad);
-  e = hipGetLastError();
-  // (the entry counter sits behind the cursors, 8-byte aligned)
-  unsigned long long *d_total = reinterpret_cast<unsigned long long *>(d_cnt + ((nb + 2) & ~(size_t)1));
-  const FoldhEmit ev = {d_raw, d_total, d_cnt, (unsigned long long)cap, rt};
-  for (size_t lo = 0; e == hipSuccess && lo + 1 < n; lo += band_q) {
-    const size_t hi = lo + band_q < n ? lo + band_q : n;
-    if (ppk_rows_in_band(n, 0, lo, hi) == 0) continue;
-    const int rc = foldh_counts_band(db, d_tr, d_tq, lo, hi, d_band, s);
-    if (rc != PPK_OK) return done(rc, false);
-    hipLaunchKernelGGL(foldh_emit_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)((hi - lo + 31) / 32)), dim3(256), 0, s,
-                       static_cast<const uint32_t *>(d_band), n, lo, hi, lo * n - (lo * (lo + 1)) / 2, (int)db->nk, ev);
-    e = hipGetLastError();
-  }
-  unsigned long long total = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return done(ppk_fail(PPK_ERR_HIP, std::string("holder pair: ") + hipGetErrorString(e)), false);
-  if (total > max_entries || total >= ((unsigned long long)1 << 32)) return done(PPK_OK, false);      // too dense to pay
-  e = hipMalloc(reinterpret_cast<void **>(&db->d_foldh_ent), (total ? total : 1) * sizeof(uint32_t));
-  if (e != hipSuccess) return done(PPK_OK, false);
-  hipLaunchKernelGGL(fold2_scan_kernel, dim3(1), dim3(1024), 0, s, d_cnt, db->d_foldh_off, nb);
-  if (total)
-    hipLaunchKernelGGL(foldh_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_raw, (size_t)total,
-                       db->d_foldh_off, d_cnt, db->d_foldh_ent, rt);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return done(ppk_fail(PPK_ERR_HIP, std::string("holder pair: ") + hipGetErrorString(e)), false);
-  db->foldh_planes = 8;
-  db->foldh_holders = H;
-  db->foldh_qt = qt;
-  db->foldh_rt = rt;
-  db->foldh_entries = (size_t)total;
-  return done(PPK_OK, true);
-}
-
 // A dispatch holds fewer than 2^32 work-items: with 512-thread workgroups that is 8.4 M pair tiles, which
 // 370 000 genomes against themselves exceed (a million: 61 M).  Larger bands go out as several launches over
 // consecutive query rows, each writing to its own part of the output (the kernels address rows and mask

@@ -23,84 +23,88 @@
 #define PPK_MAX_NK 128         // k-mer lengths per query (the reference accepts k = 3 .. 101: PopPUNK/__main__.py)
 #define PPK_LANES 64           // wavefront width on CDNA
 #define PPK_NPAD 256           // sample axis padded to a multiple of this
-#define PPK_RANK_SHORT_WORDS 16   // words of per-block "short" flags a launch carries (ppk_db::rank_short): one per k, and one to spare
+#define PPK_RANK_SHORT_WORDS 16   // words of per-block "short" flags a launch carries (PpkCoding::less1): one per k, and one to spare
 constexpr int PPK_MAX_DEVICES = 64;   // device ids the per-device tables hold: [0, PPK_MAX_DEVICES)
 
 #include "ppk_device.h"
 
-struct ppk_db {
-  int device;
-  size_t n, npad, nk, s64, bbits, words;   // words = s64*bbits per (sample,k)
-  uint64_t *d_skT;                         // [(k*words + w)*npad + sample]
-  uint16_t *d_clu;                         // [npad] or nullptr
-  // bbits = 14 only: the same sketches with every bin value replaced by its rank among the distinct values of its
-  // (k, bin) position, bit-sliced in rank_planes (8, 10 or 12; 0 = no such copy) planes: [(k*s64 + blk)*rank_planes +
-  // plane][npad].  Equal values have equal codes and different values different ones, so a self job counts the same
-  // matches from fewer planes (launch_v2 in ppk_dist.hip).
-  uint64_t *d_skR;
-  int rank_planes;
-  // rank_planes != 0: per k the 64-bin blocks that are "short".  Bit blk of rank_short[k] is set when no position of
-  // block (k, blk) holds more than 2^(rank_planes - 1) distinct values, so that the top code plane of the block is zero
-  // in every sample and the tile kernel leaves it out (option "rank_short").  Flags are kept for
-  // nk < PPK_RANK_SHORT_WORDS and s64 <= 32 (a word per k); other shapes have none.
-  unsigned rank_short[PPK_RANK_SHORT_WORDS];
-  // The folded pair, built INSTEAD of d_skR where it compares fewer planes (ppk_db_create, option "rank_fold"): two
-  // coded copies in fold_planes planes (0 = none), laid out like d_skR.  A value that at least two samples hold at its
-  // (k, bin) position has the same code >= 2 in both; a value with a single holder is 0 in d_foldR and 1 in d_foldQ.
-  // Only a triangular self job reads them, d_foldR on the ref side and d_foldQ on the query side: it compares two
-  // different samples, which a single-holder value can never match.  rank_planes and rank_short stay what the distinct
-  // values give; d_skR is then built on demand (ppk_db_rank_read).  fold_short: the short flags of the pair.
-  uint64_t *d_foldR, *d_foldQ;
-  int fold_planes;
-  unsigned fold_short[PPK_RANK_SHORT_WORDS];
+// The coded copies of a bbits = 14 database (ppk_coding.hip): the same sketches with every bin value replaced by a code
+// among the values of its (k, bin) position, bit-sliced in `planes` planes: [(k*s64 + blk)*planes + plane][npad].  A
+// self job counts the same matches from fewer planes (launch_v2 in ppk_dist.hip).  The kinds, in the order a launch
+// prefers them from the last to the first (coded_planes):
+enum PpkCodingKind {
+  // Every value is its rank among the distinct values of its position, in 8, 10 or 12 planes: equal values have equal
+  // codes and different values different ones.  One allocation serves both sides (d_ref == d_qry).  `planes` is what
+  // the distinct values give whenever ANY coding was built; the copy itself (d_ref) is built at creation only where no
+  // pair is, and otherwise on demand (ppk_db_rank_read; a rectangular job of the handle against itself reads the raw
+  // planes until then): a launch asks for the pointer.  less1: bit blk of word k is set when no position of block
+  // (k, blk) holds more than 2^(planes - 1) distinct values, so that the top code plane of the block is zero in every
+  // sample and the tile kernel leaves it out (option "rank_short").  Flags are kept for nk < PPK_RANK_SHORT_WORDS and
+  // s64 <= 32 (a word per k); other shapes have none.
+  PPK_CODING_RANK = 0,
+  // The folded pair, built INSTEAD of the injective copy where it compares fewer planes (option "rank_fold"): two
+  // copies in `planes` planes.  A value that at least two samples hold at its position has the same code >= 2 in both;
+  // a value with a single holder is 0 in d_ref and 1 in d_qry.  Only a triangular self job reads them, d_ref on the ref
+  // side and d_qry on the query side: it compares two different samples, which a single-holder value can never match.
+  // less1: the short flags of the pair.
+  PPK_CODING_FOLD = 1,
   // The two-holder pair, built INSTEAD of the folded pair where it compares fewer planes still (option "rank_fold2"):
   // the same two copies, but a value with exactly two holders is coded like a single-holder one (0 / 1) and only the
   // values with at least three holders keep codes >= 2, so a position spans E2 = S3 + 2 codes.  A two-holder value can
   // match in exactly one pair of the triangular job (its higher holder as ref, its lower as query), which the compare
   // then under-counts by one: every such value is one EVENT (hi, lo, k), and the tile kernel adds the events of its
-  // tile back at the top of its epilogue (FOLD2 in ppk_dist_tile.inc).  Events are bucketed by (lo / 32, hi / 256):
-  // bucket b = (lo / 32) * fold2_rt + hi / 256 holds d_fold2_ev[fold2_off[b] .. fold2_off[b + 1]), 16 bits each:
+  // tile back at the top of its epilogue (FOLD2 in ppk_dist_tile.inc).  The list holds them, 16 bits each:
   // hi % 256 | (lo % 32) << 8 | k << 13.  At most PPK_FOLD2_MAX_PER_PAIR events per (pair, k) (a 6-bit field).
-  uint64_t *d_fold2R, *d_fold2Q;
-  int fold2_planes;
-  unsigned fold2_short[PPK_RANK_SHORT_WORDS];
   // Neither a match count nor an event depends on the order of a k's positions, so the pair stores them sorted by
-  // code span (option "fold2_sort", ppk_db_create): slot i of k holds stored position fold2_order[k * 64 * s64 + i],
-  // E2 descending, ties by stored position ascending (the identity with "fold2_sort" 0).  A block of SLOTS whose
-  // largest E2 is at most 128 compares 7 planes (bit in fold2_seven[k]), at most 64 compares 6 (bit in fold2_six[k]
-  // as well); along a sorted k the planes never increase.  fold2_short stays the 7-plane rule on the STORED blocks
-  // (ppk_db_fold2_block_planes and the choice among the codings); the launch reads fold2_seven / fold2_six.
-  std::vector<unsigned> fold2_order;
-  unsigned fold2_seven[PPK_RANK_SHORT_WORDS], fold2_six[PPK_RANK_SHORT_WORDS];
-  uint16_t *d_fold2_ev;
-  unsigned *d_fold2_off;        // fold2_qt * fold2_rt + 1 offsets
-  unsigned fold2_qt, fold2_rt;  // npad / 32, npad / 256
-  size_t fold2_events;
-  // The holder pair, built BESIDE the two-holder pair where it compares far fewer planes (ppk_db_create, option
-  // "rank_foldh"): the same two copies in the same 8-plane layout, but EVERY value with at most foldh_holders (H)
-  // holders is coded 0 / 1 and only the values with more than H holders keep codes 2 + rank, so that a sorted block
-  // of 64 slots spans at most 16 codes and streams 4, 3 (bit in foldh_three[k]) or 2 (bit in foldh_two[k] as well)
-  // planes; planes 4 .. 7 are zero.  Slot i of k holds stored position foldh_order[k * 64 * s64 + i] (E_H descending,
-  // ties by stored position).  What the compare then misses is a COUNT per (pair, k): the matches on values with
-  // 2 .. H holders, found once at creation by comparing a temporary pair that codes those values alone.  Non-zero
-  // counts are 32-bit entries hi % 256 | (lo % 32) << 8 | k << 13 | count << 16, bucketed like the events:
-  // bucket b = (lo / 32) * foldh_rt + hi / 256 holds d_foldh_ent[foldh_off[b] .. foldh_off[b + 1]).
-  uint64_t *d_foldhR, *d_foldhQ;
-  int foldh_planes;               // 8 (the chunk's layout), 0 = no such pair
-  unsigned foldh_holders;         // H
-  std::vector<unsigned> foldh_order;
-  std::vector<uint8_t> foldh_block_planes;      // [k * s64 + block]: 2, 3 or 4, what the sorted block's widest position needs
-  unsigned foldh_three[PPK_RANK_SHORT_WORDS], foldh_two[PPK_RANK_SHORT_WORDS];
-  uint32_t *d_foldh_ent;
-  unsigned *d_foldh_off;          // foldh_qt * foldh_rt + 1 offsets
-  unsigned foldh_qt, foldh_rt;    // npad / 32, npad / 256
-  size_t foldh_entries;
+  // code span (option "fold2_sort"): slot i of k holds stored position order[k * 64 * s64 + i], E2 descending, ties by
+  // stored position ascending (the identity with "fold2_sort" 0).  A block of SLOTS whose largest E2 is at most 128
+  // compares 7 planes (less1), at most 64 compares 6 (less2 as well); along a sorted k the planes never increase.  The
+  // 7-plane rule on the STORED blocks (ppk_db_fold2_block_planes and the choice among the codings) is a function of
+  // rank_counts and is derived from them where it is asked for.
+  PPK_CODING_FOLD2 = 2,
+  // The holder pair, built BESIDE the two-holder pair where it compares far fewer planes (option "rank_foldh"): the
+  // same two copies in the same 8-plane layout, but EVERY value with at most `holders` (H) holders is coded 0 / 1 and
+  // only the values with more than H holders keep codes 2 + rank, so that a sorted block of 64 slots spans at most 16
+  // codes and streams 4 (`stream_planes`), 3 (less1) or 2 (less2 as well) planes; planes 4 .. 7 are zero.  Slot i of k
+  // holds stored position order[k * 64 * s64 + i] (E_H descending, ties by stored position).  What the compare then
+  // misses is a COUNT per (pair, k): the matches on values with 2 .. H holders, found once at creation by comparing a
+  // temporary pair that codes those values alone.  Non-zero counts are the 32-bit entries of the list:
+  // hi % 256 | (lo % 32) << 8 | k << 13 | count << 16.
+  PPK_CODING_FOLDH = 3,
+  PPK_CODINGS = 4
+};
+struct PpkCoding {
+  PpkCodingKind kind = PPK_CODING_RANK;
+  uint64_t *d_ref = nullptr, *d_qry = nullptr;      // the copies a launch reads on either side
+  int planes = 0;                                   // of the layout; 0 = no such coding
+  int stream_planes = 0;                            // the most a block compares: `planes`, 4 for the holder pair
+  unsigned holders = 0;                             // H (holder pair)
+  // per k the 64-bin blocks that compare one plane fewer than stream_planes, and two fewer
+  unsigned less1[PPK_RANK_SHORT_WORDS] = {}, less2[PPK_RANK_SHORT_WORDS] = {};
+  std::vector<unsigned> order;                      // slot order of the sorted pairs, empty elsewhere
+  // the corrections of the tile kernel's epilogue, bucketed by (lo / 32, hi / 256): bucket b = (lo / 32) * rt +
+  // hi / 256 holds elements d_off[b] .. d_off[b + 1] of d_list, list_elem (2 or 4) bytes each
+  void *d_list = nullptr;
+  unsigned *d_off = nullptr;                        // qt * rt + 1 offsets
+  unsigned list_elem = 0, qt = 0, rt = 0;           // npad / 32, npad / 256
+  size_t list_count = 0;
+};
+// releases what `c` holds on the current device and leaves it empty (its kind kept)
+void ppk_coding_free(PpkCoding &c);
+
+struct ppk_db {
+  int device = 0;
+  size_t n = 0, npad = 0, nk = 0, s64 = 0, bbits = 0, words = 0;   // words = s64*bbits per (sample,k)
+  uint64_t *d_skT = nullptr;               // [(k*words + w)*npad + sample]
+  uint16_t *d_clu = nullptr;               // [npad] or nullptr
+  PpkCoding coding[PPK_CODINGS] = {{PPK_CODING_RANK}, {PPK_CODING_FOLD}, {PPK_CODING_FOLD2}, {PPK_CODING_FOLDH}};
   // what the count pass found (ppk_db_rank_counts): the maxima of D, E = S + 2 and E2 = S3 + 2 over all positions and
   // per (k, 64-bin block) -- 3 x (1 + nk * s64) words -- then PPK_RANK_EXTRA words: the most two-holder values of any
   // position, their number over all positions, and (after an attempt at the two-holder pair) whether a (pair, k) had
   // more events than its field holds.  Empty where no count pass ran.
   std::vector<unsigned> rank_counts;
 };
+constexpr int RANK_BB = 14;          // the one bbits with a coded copy (the tile kernels' V2_BB)
 #define PPK_RANK_EXTRA 3
 #define PPK_FOLD2_SLOTS 256          // two-holder values per position the code pass has LDS slots for
 #define PPK_FOLD2_MAX_PER_PAIR 63    // events per (pair, k): a 6-bit field of the tile kernel's correction word
@@ -134,12 +138,12 @@ struct PpkConfig {
   std::atomic<long long> edge_list_keep{1};     // PPK_EDGE_LIST_KEEP: the fused host edge call keeps its device list buffer between calls (0: allocate + free per call, measurement)
 #endif
   // -- product options
-  std::atomic<long long> rank_planes{1};        // PPK_RANK_PLANES: a bbits = 14 database whose self job runs whole tiles keeps a rank-coded copy (ppk_db::d_skR) and self jobs compare it (0: no copy is built, none is read; same bits)
-  std::atomic<long long> rank_fold{1};          // PPK_RANK_FOLD: where folding every single-holder bin value into two reserved codes lets a self job compare fewer planes, the database keeps the folded pair (ppk_db::d_foldR / d_foldQ) instead of the injective copy (0: never; 2: whenever the folded codes fit 12 planes, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
-  std::atomic<long long> rank_fold2{1};         // PPK_RANK_FOLD2: where coding the two-holder bin values like single-holder ones (their one match per value added back in the tile kernel's epilogue from an event list) lets a large self job compare fewer planes than both other codings, the database keeps the two-holder pair (ppk_db::d_fold2R / d_fold2Q) instead (0: never; 2: whenever the caps allow, any size, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
+  std::atomic<long long> rank_planes{1};        // PPK_RANK_PLANES: a bbits = 14 database whose self job runs whole tiles keeps a rank-coded copy (PPK_CODING_RANK) and self jobs compare it (0: no copy is built, none is read; same bits)
+  std::atomic<long long> rank_fold{1};          // PPK_RANK_FOLD: where folding every single-holder bin value into two reserved codes lets a self job compare fewer planes, the database keeps the folded pair (PPK_CODING_FOLD) instead of the injective copy (0: never; 2: whenever the folded codes fit 12 planes, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
+  std::atomic<long long> rank_fold2{1};         // PPK_RANK_FOLD2: where coding the two-holder bin values like single-holder ones (their one match per value added back in the tile kernel's epilogue from an event list) lets a large self job compare fewer planes than both other codings, the database keeps the two-holder pair (PPK_CODING_FOLD2) instead (0: never; 2: whenever the caps allow, any size, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
   std::atomic<long long> fold2_sort{1};         // PPK_FOLD2_SORT: the two-holder pair stores the positions of each k sorted by the codes they span, so that most 64-bin blocks span at most 64 codes (0: positions as stored; same bits).  Read at creation.
   std::atomic<long long> fold2_min_planes{6};   // PPK_FOLD2_MIN_PLANES: a self job on the two-holder pair compares 6 planes in the blocks that span at most 64 codes (7: such blocks compare 7, as every block spanning at most 128 does; same bits).  Read at launch.
-  std::atomic<long long> rank_foldh{1};         // PPK_RANK_FOLDH: where folding every bin value with at most H holders (their matches added back in the tile kernel's epilogue from a list of per-pair counts) cuts the two-holder pair's compare stream to 0.6 of its planes or less, the database keeps the holder pair (ppk_db::d_foldhR / d_foldhQ) beside it and self jobs read that (0: never; 2: whenever the caps allow, any size, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
+  std::atomic<long long> rank_foldh{1};         // PPK_RANK_FOLDH: where folding every bin value with at most H holders (their matches added back in the tile kernel's epilogue from a list of per-pair counts) cuts the two-holder pair's compare stream to 0.6 of its planes or less, the database keeps the holder pair (PPK_CODING_FOLDH) beside it and self jobs read that (0: never; 2: whenever the caps allow, any size, gain or none -- tests; same bits).  Read at creation; 0 at launch leaves a built pair unread.
   std::atomic<long long> foldh_holders{0};      // PPK_FOLDH_HOLDERS: the holder bound H of the holder pair (0: the smallest of 4, 8, ... 256 that qualifies; any other value forces that H).  Read at creation.
   std::atomic<long long> foldh_min_planes{2};   // PPK_FOLDH_MIN_PLANES: a self job on the holder pair compares 2 planes in the blocks that span at most 4 codes and 3 in those that span at most 8 (3, 4: no block compares fewer; same bits).  Read at launch.
   std::atomic<long long> rank_short{1};         // PPK_RANK_SHORT: a self job on a rank-coded database compares one plane fewer in the 64-bin blocks whose positions hold at most half the values the planes can code (0: every block compares all planes; same bits).  Read at launch.
@@ -277,26 +281,58 @@ struct PpkRouteChoice {
   size_t tiles, limit, scratch_bytes;
 };
 PpkRouteChoice ppk_choose_route_impl(const PpkRouteShape &sh, const PpkGeometry &g, const PpkRouteKnobs &k);
-// rank-coded copy of a bbits = 14 database (ppk_dist.hip)
-bool ppk_self_job_takes_tiles(const ppk_db *db);
-// (d_max: 3 x (1 + nk * s64) words -- per figure the maximum over all positions, then the maximum of each (k, 64-bin
-// block) -- and PPK_RANK_EXTRA more, see ppk_db::rank_counts)
-int ppk_launch_rank_count(const uint64_t *d_skT, size_t n, size_t npad, size_t nk, size_t s64, unsigned *d_max, hipStream_t s);
-int ppk_launch_rank_codes(const uint64_t *d_skT, uint64_t *d_out, uint64_t *d_out_q, size_t n, size_t npad, size_t nk, size_t s64, int planes,
-                          hipStream_t s);
-// The two-holder pair and its event list (ppk_db::d_fold2R ...): allocates the list, enqueues the code pass, the
-// counting sort and the cap check, and synchronises `s` once.  *overflow: a (pair, k) has more events than its field
-// holds (the caller drops the pair).  `n_two`: the two-holder values the count pass found.
-int ppk_build_fold2(ppk_db *db, int planes, size_t n_two, const std::vector<unsigned> *order, bool *overflow, hipStream_t s);
-// The holder pair (ppk_db::d_foldhR ...).  ppk_foldh_count: the holder count of every shared value of every position
-// (left on the device in *d_twice / *d_holders, which the caller frees) and, per position and bound of `ladder`, E_H =
-// (values with more than H holders) + 2 into pos_e[(k * 64 * s64 + position) * PPK_FOLDH_LADDER + i]; synchronises.
-// ppk_build_foldh: the pair for bound H in the slot order db->foldh_order, the temporary pair, its counts band by
-// band and the entries; a device too full, or more entries than `max_entries`, leaves the database without the pair
-// (db->foldh_planes 0).  Synchronises.
-int ppk_foldh_count(const ppk_db *db, const unsigned *ladder, unsigned **d_twice, uint16_t **d_holders, std::vector<unsigned> *pos_e, hipStream_t s);
-int ppk_build_foldh(ppk_db *db, unsigned H, const unsigned *d_twice, const uint16_t *d_holders, size_t max_entries, hipStream_t s);
-void ppk_drop_foldh(ppk_db *db);
+bool ppk_self_job_takes_tiles(const ppk_db *db);      // (ppk_dist.hip) the one job shape that reads a coded copy
+// one band of raw-plane match counts (MODE_COUNTS of the tile kernel) of a self job of `db`'s shape, ref side d_r, query
+// side d_q: what ppk_coding.hip needs of the distance file; enqueues only
+int ppk_counts_band_raw(const ppk_db *db, const uint64_t *d_r, const uint64_t *d_q, size_t q_begin, size_t q_end, void *d_cnt,
+                        hipStream_t s);
+
+// ---- the coded copies (ppk_coding.hip) ----
+// What ppk_db_create builds, as a pure function of the count pass's read-back (`counts`: the layout
+// ppk_launch_rank_count leaves -- 3 x (1 + nk * s64) maxima of D, E, E2, PPK_RANK_EXTRA words, E2 of every position),
+// the shape, the device's tile_slots and the options rank_fold, rank_fold2, fold2_sort, rank_foldh.  No device touched.
+struct PpkCodingPlan {
+  int planes[3];                                   // of the codings of D, E and E2 (8, 10, 12; 0: past 4 096 codes)
+  unsigned less1[3][PPK_RANK_SHORT_WORDS];         // their short flags on the stored blocks
+  size_t sum[3];                                   // the planes a self job compares over all blocks with each (none: bbits)
+  // the codings to try, in this order, until one is built; ends with -1 (the raw planes).  A coding is dropped where
+  // the device is too full for it, the two-holder pair also where a (pair, k) overflows its event field.
+  int chain[PPK_CODINGS];
+  // chain[0] == PPK_CODING_FOLD2 only: the pair's slot order ("fold2_sort" 0: the identity), the flags and planes of
+  // its sorted blocks (8, 7, 6), their sum, and whether the holder pair is to be tried beside it
+  bool sorted;
+  std::vector<unsigned> order;
+  unsigned seven[PPK_RANK_SHORT_WORDS], six[PPK_RANK_SHORT_WORDS];
+  std::vector<uint8_t> stream;
+  size_t stream_sum;
+  bool try_holder;
+};
+PpkCodingPlan ppk_plan_codings(const unsigned *counts, size_t n, size_t nk, size_t s64, size_t bbits, int tile_slots,
+                               long long rank_fold, long long rank_fold2, long long fold2_sort, long long rank_foldh);
+// The holder pair's bound.  ppk_holder_ladder: the bounds the count pass is to try (option "foldh_holders": that one
+// alone), 0 where a cap refuses the pair outright -- more than five k, sketchsize64 > 32, nk >= PPK_RANK_SHORT_WORDS,
+// n >= 2^24, more than PPK_FOLDH_SLOTS shared values at a position.  ppk_choose_holder_impl: the smallest of them for which,
+// with each k's positions sorted by E_H (descending, ties by stored position), every block of 64 slots spans at most
+// 16 codes -- and, under the default rule, the stream plane sum (2, 3 or 4 per block) is at most 0.6 of the two-holder
+// pair's and the self job runs at least four rounds of tiles: a smaller saving does not pay for the creation pass.
+// Option "rank_foldh" 2 takes the first H whose blocks fit, and lifts the cap on the entries from a sixteenth of the
+// (pair, k) to all of them.  pos_e: E_H at [(k * 64 * s64 + position) * PPK_FOLDH_LADDER + rung].  H 0: no pair.
+struct PpkHolderChoice {
+  unsigned H = 0;
+  std::vector<unsigned> order;             // [k][slot]
+  std::vector<uint8_t> block_planes;       // [k][block]: 2, 3 or 4
+  size_t max_entries = 0;
+};
+int ppk_holder_ladder(size_t n, size_t nk, size_t s64, size_t most_shared, long long foldh_holders, unsigned *ladder);
+PpkHolderChoice ppk_choose_holder_impl(const unsigned *pos_e, const unsigned *ladder, int rungs, size_t n, size_t nk, size_t s64,
+                                  int tile_slots, size_t fold2_sum, long long rank_foldh);
+// the execution: the count pass, the plan, and the codings it names with their fallbacks; synchronises `s`
+int ppk_db_build_codings(ppk_db *db, hipStream_t s);
+// whether the options in force let a launch read coding `kind` ("rank_planes", "rank_fold", "rank_fold2", "rank_foldh")
+bool ppk_coding_enabled(int kind);
+// the flag words a launch on `c` carries under the options in force ("rank_short", "fold2_min_planes",
+// "foldh_min_planes"; read at launch: one database runs either way)
+void ppk_coding_launch_flags(const PpkCoding &c, unsigned *less1, unsigned *less2);
 
 // Profiling hooks (ppk_prof_*) -------------------------------------------------
 void ppk_prof_begin(hipStream_t s);

@@ -136,10 +136,38 @@ class SketchDB:
         """Planes a self job compares per 64-bin block of the rank-coded copy (ppk_db_rank_block_planes): uint8
         [nk, sketchsize64], rank_planes or -- where no position of the block holds more than 2^(rank_planes - 1)
         distinct values -- rank_planes - 1.  The database's own flags: option "rank_short" 0 does not change them."""
-        out = np.empty((self.nk, self.sketchsize64), dtype=np.uint8)
-        _lib.check(_lib.lib().ppk_db_rank_block_planes(self._h, C.c_void_p(out.ctypes.data), out.size),
-                   "ppk_db_rank_block_planes")
+        return self._per_block("ppk_db_rank_block_planes")
+
+    def _per_block(self, fn, per_block=1, dtype=np.uint8):
+        """[nk, per_block * sketchsize64] from one of the ppk_db_*_block_planes / _stream_planes / _position_order
+        accessors"""
+        out = np.empty((self.nk, per_block * self.sketchsize64), dtype=dtype)
+        _lib.check(getattr(_lib.lib(), fn)(self._h, C.c_void_p(out.ctypes.data), out.size), fn)
         return out
+
+    def _codes(self, fn, planes, which=None, order=None):
+        """One coded copy (ppk_db_*_read) un-bitsliced; with `order`, the sort of its slots undone."""
+        npad = (self.n + 255) // 256 * 256
+        raw = np.empty((self.nk, self.sketchsize64, max(planes, 1), npad), dtype=np.uint64)
+        args = (C.c_void_p(raw.ctypes.data), self.nk * self.sketchsize64 * planes * npad)
+        _lib.check(getattr(_lib.lib(), fn)(self._h, *(args if which is None else (int(which),) + args)), fn)
+        slots = self._unslice_codes(raw, planes)
+        if order is None:
+            return slots
+        codes = np.empty_like(slots)
+        for k in range(self.nk):
+            codes[:, k, order[k]] = slots[:, k]
+        return codes
+
+    def _bucketed(self, size_fn, read_fn, dtype):
+        """(offsets uint32, list) of a coding's bucketed corrections (ppk_db_*_events / _entries and their _read)"""
+        nb = C.c_size_t(0)
+        count = int(getattr(_lib.lib(), size_fn)(self._h, C.byref(nb)))
+        off = np.zeros(nb.value + 1, dtype=np.uint32)
+        items = np.zeros(count, dtype=dtype)
+        _lib.check(getattr(_lib.lib(), read_fn)(self._h, C.c_void_p(off.ctypes.data), off.size,
+                                                C.c_void_p(items.ctypes.data) if count else None, count), read_fn)
+        return off, items
 
     def _unslice_codes(self, raw, planes):
         """coded planes [nk, sketchsize64, planes, npad] uint64 -> uint16 [n, nk, 64 * sketchsize64] codes"""
@@ -152,10 +180,7 @@ class SketchDB:
 
     def rank_codes(self):
         """The rank-coded copy un-bitsliced (tests): uint16 [n, nk, 64 * sketchsize64] codes."""
-        planes, npad = self.rank_planes, (self.n + 255) // 256 * 256
-        raw = np.empty((self.nk, self.sketchsize64, planes, npad), dtype=np.uint64)
-        _lib.check(_lib.lib().ppk_db_rank_read(self._h, C.c_void_p(raw.ctypes.data), raw.size), "ppk_db_rank_read")
-        return self._unslice_codes(raw, planes)
+        return self._codes("ppk_db_rank_read", self.rank_planes)
 
     @property
     def fold_planes(self):
@@ -166,19 +191,12 @@ class SketchDB:
         """Planes a self job compares per 64-bin block of the folded pair (ppk_db_fold_block_planes): uint8
         [nk, sketchsize64], fold_planes or -- where no position of the block spans more than 2^(fold_planes - 1)
         codes -- fold_planes - 1."""
-        out = np.empty((self.nk, self.sketchsize64), dtype=np.uint8)
-        _lib.check(_lib.lib().ppk_db_fold_block_planes(self._h, C.c_void_p(out.ctypes.data), out.size),
-                   "ppk_db_fold_block_planes")
-        return out
+        return self._per_block("ppk_db_fold_block_planes")
 
     def fold_codes(self, which):
         """One copy of the folded pair un-bitsliced (tests), 0 the ref side, 1 the query side: uint16
         [n, nk, 64 * sketchsize64] codes."""
-        planes, npad = self.fold_planes, (self.n + 255) // 256 * 256
-        raw = np.empty((self.nk, self.sketchsize64, max(planes, 1), npad), dtype=np.uint64)
-        _lib.check(_lib.lib().ppk_db_fold_read(self._h, int(which), C.c_void_p(raw.ctypes.data),
-                                               self.nk * self.sketchsize64 * planes * npad), "ppk_db_fold_read")
-        return self._unslice_codes(raw, planes)
+        return self._codes("ppk_db_fold_read", self.fold_planes, which)
 
     @property
     def fold2_planes(self):
@@ -188,52 +206,28 @@ class SketchDB:
     def fold2_block_planes(self):
         """The 8 / 7 plane rule on the 64-bin blocks of the two-holder pair as the sketches store them
         (ppk_db_fold2_block_planes): uint8 [nk, sketchsize64].  What a self job compares: fold2_stream_planes()."""
-        out = np.empty((self.nk, self.sketchsize64), dtype=np.uint8)
-        _lib.check(_lib.lib().ppk_db_fold2_block_planes(self._h, C.c_void_p(out.ctypes.data), out.size),
-                   "ppk_db_fold2_block_planes")
-        return out
+        return self._per_block("ppk_db_fold2_block_planes")
 
     def fold2_stream_planes(self):
         """Planes a self job compares per block of the two-holder pair's sorted positions, under the options in force
         (ppk_db_fold2_stream_planes): uint8 [nk, sketchsize64] of 8, 7 or 6."""
-        out = np.empty((self.nk, self.sketchsize64), dtype=np.uint8)
-        _lib.check(_lib.lib().ppk_db_fold2_stream_planes(self._h, C.c_void_p(out.ctypes.data), out.size),
-                   "ppk_db_fold2_stream_planes")
-        return out
+        return self._per_block("ppk_db_fold2_stream_planes")
 
     def fold2_position_order(self):
         """The stored position each slot of the two-holder pair holds (ppk_db_fold2_position_order): uint32
         [nk, 64 * sketchsize64], per k a permutation (the identity under option "fold2_sort" 0)."""
-        out = np.empty((self.nk, 64 * self.sketchsize64), dtype=np.uint32)
-        _lib.check(_lib.lib().ppk_db_fold2_position_order(self._h, C.c_void_p(out.ctypes.data), out.size),
-                   "ppk_db_fold2_position_order")
-        return out
+        return self._per_block("ppk_db_fold2_position_order", 64, np.uint32)
 
     def fold2_codes(self, which):
         """One copy of the two-holder pair un-bitsliced (tests), 0 the ref side, 1 the query side: uint16
         [n, nk, 64 * sketchsize64] codes, in stored position order (the sort of fold2_position_order() undone)."""
-        planes, npad = self.fold2_planes, (self.n + 255) // 256 * 256
-        raw = np.empty((self.nk, self.sketchsize64, max(planes, 1), npad), dtype=np.uint64)
-        _lib.check(_lib.lib().ppk_db_fold2_read(self._h, int(which), C.c_void_p(raw.ctypes.data),
-                                                self.nk * self.sketchsize64 * planes * npad), "ppk_db_fold2_read")
-        slots, order = self._unslice_codes(raw, planes), self.fold2_position_order()
-        codes = np.empty_like(slots)
-        for k in range(self.nk):
-            codes[:, k, order[k]] = slots[:, k]
-        return codes
+        return self._codes("ppk_db_fold2_read", self.fold2_planes, which, self.fold2_position_order())
 
     def fold2_events(self):
         """The event list of the two-holder pair (ppk_db_fold2_events_read): (offsets uint32 [npad / 32, npad / 256]
         flattened + 1, events uint16).  Bucket (lo // 32) * (npad // 256) + hi // 256 holds
         events[offsets[b]:offsets[b + 1]], each hi % 256 | (lo % 32) << 8 | k << 13, in no order within a bucket."""
-        nb = C.c_size_t(0)
-        n_ev = int(_lib.lib().ppk_db_fold2_events(self._h, C.byref(nb)))
-        off = np.zeros(nb.value + 1, dtype=np.uint32)
-        ev = np.zeros(n_ev, dtype=np.uint16)
-        _lib.check(_lib.lib().ppk_db_fold2_events_read(self._h, C.c_void_p(off.ctypes.data), off.size,
-                                                       C.c_void_p(ev.ctypes.data) if n_ev else None, n_ev),
-                   "ppk_db_fold2_events_read")
-        return off, ev
+        return self._bucketed("ppk_db_fold2_events", "ppk_db_fold2_events_read", np.uint16)
 
     def foldh_holders(self):
         """The holder bound H of the database's holder pair, 0 without one (ppk_db_foldh_holders): every bin value
@@ -243,45 +237,24 @@ class SketchDB:
     def foldh_stream_planes(self):
         """Planes a self job compares per block of the holder pair's sorted positions, under the options in force
         (ppk_db_foldh_stream_planes): uint8 [nk, sketchsize64] of 4, 3 or 2."""
-        out = np.empty((self.nk, self.sketchsize64), dtype=np.uint8)
-        _lib.check(_lib.lib().ppk_db_foldh_stream_planes(self._h, C.c_void_p(out.ctypes.data), out.size),
-                   "ppk_db_foldh_stream_planes")
-        return out
+        return self._per_block("ppk_db_foldh_stream_planes")
 
     def foldh_position_order(self):
         """The stored position each slot of the holder pair holds (ppk_db_foldh_position_order): uint32
         [nk, 64 * sketchsize64], per k a permutation."""
-        out = np.empty((self.nk, 64 * self.sketchsize64), dtype=np.uint32)
-        _lib.check(_lib.lib().ppk_db_foldh_position_order(self._h, C.c_void_p(out.ctypes.data), out.size),
-                   "ppk_db_foldh_position_order")
-        return out
+        return self._per_block("ppk_db_foldh_position_order", 64, np.uint32)
 
     def foldh_codes(self, which):
         """One copy of the holder pair un-bitsliced (tests), 0 the ref side, 1 the query side: uint16
         [n, nk, 64 * sketchsize64] codes, in stored position order (the sort of foldh_position_order() undone)."""
-        planes, npad = 8, (self.n + 255) // 256 * 256
-        raw = np.empty((self.nk, self.sketchsize64, planes, npad), dtype=np.uint64)
-        _lib.check(_lib.lib().ppk_db_foldh_read(self._h, int(which), C.c_void_p(raw.ctypes.data),
-                                                self.nk * self.sketchsize64 * planes * npad), "ppk_db_foldh_read")
-        slots, order = self._unslice_codes(raw, planes), self.foldh_position_order()
-        codes = np.empty_like(slots)
-        for k in range(self.nk):
-            codes[:, k, order[k]] = slots[:, k]
-        return codes
+        return self._codes("ppk_db_foldh_read", 8, which, self.foldh_position_order())
 
     def foldh_entries(self):
         """What the holder pair's compare owes (ppk_db_foldh_entries_read): (offsets uint32 [npad / 32, npad / 256]
         flattened + 1, entries uint32).  Bucket (lo // 32) * (npad // 256) + hi // 256 holds
         entries[offsets[b]:offsets[b + 1]], each hi % 256 | (lo % 32) << 8 | k << 13 | count << 16, one per (pair, k)
         with a non-zero count, in no order within a bucket."""
-        nb = C.c_size_t(0)
-        n_ent = int(_lib.lib().ppk_db_foldh_entries(self._h, C.byref(nb)))
-        off = np.zeros(nb.value + 1, dtype=np.uint32)
-        ent = np.zeros(n_ent, dtype=np.uint32)
-        _lib.check(_lib.lib().ppk_db_foldh_entries_read(self._h, C.c_void_p(off.ctypes.data), off.size,
-                                                        C.c_void_p(ent.ctypes.data) if n_ent else None, n_ent),
-                   "ppk_db_foldh_entries_read")
-        return off, ent
+        return self._bucketed("ppk_db_foldh_entries", "ppk_db_foldh_entries_read", np.uint32)
 
     def rank_counts(self):
         """What the count pass of the coded copies found (ppk_db_rank_counts), None where none ran: a dict of the

@@ -1,4 +1,4 @@
-"""Numpy model of the holder pair of a bbits = 14 database (ppk_db::d_foldhR / d_foldhQ, options "rank_foldh",
+"""Numpy model of the holder pair of a bbits = 14 database (PPK_CODING_FOLDH, options "rank_foldh",
 "foldh_holders", "foldh_min_planes"), for tests/test_rank_foldh_host.py and tests/test_gpu_rank_foldh.py: every value
 with at most H holders at its position is coded 0 / 1, the values with more keep codes 2 + rank; the positions of a k
 are sorted by E_H = (values with more than H holders) + 2; what a (pair, k) is owed is one entry (hi, lo, k, count); and

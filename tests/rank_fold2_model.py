@@ -1,4 +1,4 @@
-"""Numpy model of the two-holder pair of a bbits = 14 database (ppk_db::d_fold2R / d_fold2Q, option "rank_fold2"), for
+"""Numpy model of the two-holder pair of a bbits = 14 database (PPK_CODING_FOLD2, option "rank_fold2"), for
 tests/test_rank_fold2_host.py and tests/test_gpu_rank_fold2.py: per position the holders of every value, D / S / S3 and
 E2 = S3 + 2, the codes of the two copies, the events (hi, lo, k) the tile kernel adds back, their buckets, the caps and
 ppk_db_create's choice among the three codings."""

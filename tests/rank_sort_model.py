@@ -1,4 +1,4 @@
-"""Numpy model of the sorted positions of the two-holder pair (ppk_db::fold2_order, options "fold2_sort" and
+"""Numpy model of the sorted positions of the two-holder pair (the order of PPK_CODING_FOLD2, options "fold2_sort" and
 "fold2_min_planes"), for tests/test_rank_sort_host.py and tests/test_gpu_rank_sort.py: E2 per position, the order of a
 k's positions, the planes the tile kernel compares per block of slots, the copies in slot order, and populations
 planted to a chosen E2 per position."""

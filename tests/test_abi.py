@@ -263,3 +263,34 @@ def test_device_ids_outside_the_table_are_argument_errors():
             if rc != _lib.ERR_ARG or b"out of range [0, 64)" not in lib.ppk_last_error():
                 wrong.append((name, bad, rc, lib.ppk_last_error()))
     assert not wrong, "\n".join(map(repr, wrong))
+
+
+def test_the_coding_choice_exports_refuse_null_and_misshapen_arguments():
+    """ppk_choose_coding / ppk_choose_holder: pure functions of plain arrays, callable without a device; a NULL array
+    or a length that does not fit the shape is ERR_ARG with the export's name, and nothing is written"""
+    lib = _lib.lib()
+    nk, s64 = 2, 1
+    counts = np.full(3 * (1 + nk * s64) + 3 + nk * s64 * 64, 2, dtype=np.uint32)
+    opts = (C.c_longlong * 4)(1, 1, 1, 1)
+    first, fallback, sums = C.c_int(7), C.c_int(7), (C.c_size_t * 3)()
+    good = [C.c_void_p(counts.ctypes.data), counts.size, 100, nk, s64, 14, 512, opts, C.byref(first), C.byref(fallback),
+            sums, None, None, None, None, None]
+    assert lib.ppk_choose_coding(*good) == 0 and (first.value, fallback.value, list(sums)) == (0, -1, [14, 14, 14])
+    for i in (0, 7, 8, 9, 10):
+        bad = list(good)
+        bad[i] = None
+        assert lib.ppk_choose_coding(*bad) == _lib.ERR_ARG and b"ppk_choose_coding: NULL argument" in lib.ppk_last_error()
+    bad = list(good)
+    bad[1] = counts.size - 1
+    assert lib.ppk_choose_coding(*bad) == _lib.ERR_ARG and b"ppk_choose_coding: bad shape" in lib.ppk_last_error()
+    pos_e = np.full(nk * s64 * 64 * 7, 2, dtype=np.uint32)
+    h = C.c_uint(9)
+    good = [C.c_void_p(pos_e.ctypes.data), pos_e.size, 100, nk, s64, 512, 0, 16, 2, 0, C.byref(h), None, None, None]
+    assert lib.ppk_choose_holder(*good) == 0 and h.value == 4
+    for i in (0, 10):
+        bad = list(good)
+        bad[i] = None
+        assert lib.ppk_choose_holder(*bad) == _lib.ERR_ARG and b"ppk_choose_holder: NULL argument" in lib.ppk_last_error()
+    bad = list(good)
+    bad[1] = pos_e.size + 7
+    assert lib.ppk_choose_holder(*bad) == _lib.ERR_ARG and b"ppk_choose_holder: bad shape" in lib.ppk_last_error()

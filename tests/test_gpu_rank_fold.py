@@ -1,4 +1,4 @@
-"""The folded pair of coded copies (ppk_db::d_foldR / d_foldQ, option "rank_fold"): every bin value that exactly one
+"""The folded pair of coded copies (PPK_CODING_FOLD, option "rank_fold"): every bin value that exactly one
 sample holds at its (k, bin) position is folded into two reserved codes, 0 on the ref side and 1 on the query side, and
 the values with at least two holders get the codes 2 + rank in both.  A triangular self job compares two different
 samples, so the bits must be those of the 14 raw planes, from as few as 8 planes.

@@ -1,4 +1,4 @@
-"""The two-holder pair of coded copies (ppk_db::d_fold2R / d_fold2Q and the event list, option "rank_fold2"): every bin
+"""The two-holder pair of coded copies (PPK_CODING_FOLD2: the pair and its event list, option "rank_fold2"): every bin
 value with exactly two holders is coded like a single-holder one, and the tile kernel adds the one match each is owed
 back at the top of its epilogue.  n = 257 and n = 300: one full ref tile with its diagonal and half tiles and a strip.
 

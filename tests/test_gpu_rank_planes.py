@@ -1,4 +1,4 @@
-"""Rank-coded resident databases (ppk_db::d_skR): a self job that compares 8, 10 or 12 code planes per 64-bin block
+"""Rank-coded resident databases (PPK_CODING_RANK): a self job that compares 8, 10 or 12 code planes per 64-bin block
 must return the bits the 14 raw planes return.
 
 Every case runs engine.dist twice on the same sketches -- option "rank_planes" 1 and 0 at database creation -- with

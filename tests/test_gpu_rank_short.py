@@ -1,5 +1,5 @@
 """Short blocks of a rank-coded database: a 64-bin block none of whose positions holds more than 2^(P-1) distinct values
-has a zero top code plane, and a self job compares P - 1 planes there (option "rank_short", ppk_db::rank_short).  The
+has a zero top code plane, and a self job compares P - 1 planes there (option "rank_short", PpkCoding::less1).  The
 bits must be those of the 14 raw planes.
 
 Settings as in tests/test_gpu_rank_planes.py: s = 1024, five k, option "ksplit" 0 (whole tiles), the random-match

@@ -2,12 +2,16 @@
 force.  What the device must reproduce is stated here once: with the values of exactly two holders coded like
 single-holder ones, the compare of (ref copy of r, query copy of q), r > q, plus the events of (r, q, k) is the true
 match count -- for every pair and k; the codes of a position span E2 = S3 + 2 values; the buckets hold every event once;
-the caps and the plane-sum rule decide what ppk_db_create builds."""
+the caps and the plane-sum rule decide what ppk_db_create builds.  `choice` asks the numpy model AND the library
+(ppk_choose_coding, no device touched) and returns what both say (tests/coding_choice.py)."""
 import numpy as np
 
-from rank_fold2_model import (MAX_PER_PAIR, SLOTS, block_counts, buckets_of, choice, counts_of, events_of, fold2_codes_of,
+from coding_choice import counts_layout, plan
+from coding_choice import fold2_choice as choice
+from rank_fold2_model import (MAX_PER_PAIR, SLOTS, block_counts, buckets_of, counts_of, events_of, fold2_codes_of,
                               match_counts, per_pair_max)
 from rank_model import fold_codes_of, n_distinct, n_shared
+from rank_sort_model import order_of, planted_e2, position_e2, spread_targets, stream_planes
 
 
 def population(n=90, nk=3, nbins=128, values=700, seed=5):
@@ -106,3 +110,31 @@ def test_caps_are_what_the_model_counts():
     assert per_pair_max(events_of(bins)) == 63
     bd, be, be2, two_max, _ = block_counts(bins)
     assert choice(bd, be, be2, two_max, 63, len(bins), rank_fold2=2) == "fold2"
+
+
+def flag_bits(words, nk, s64):
+    """per-k flag words -> bool [nk, s64]"""
+    return (words[:nk, None] >> np.arange(s64)[None, :] & 1).astype(bool)
+
+
+def test_the_library_plans_the_sorted_pair_like_the_model():
+    """what the models of the choice cannot say: the slot order, the 7- and 6-plane flags, the stream planes and their
+    sum of ppk_choose_coding are rank_sort_model's, sorted and as stored, on a population whose blocks take 8, 7 and 6"""
+    targets = spread_targets(2, 192, 140, seed=11, wide=[[(140, 3), (100, 70)], [(90, 5)]])
+    for bins in (population(), planted_e2(430, targets, seed=12)):
+        bd, be, be2, two_max, two_total = block_counts(bins)
+        e2 = position_e2(bins)
+        nk, s64 = bd.shape
+        for sort in (1, 0):
+            p = plan(counts_layout(bd, be, be2, two_max, two_total, e2), len(bins), nk, s64, rank_fold2=2, fold2_sort=sort)
+            order = order_of(e2, bool(sort))
+            want = stream_planes(e2, order)
+            assert p["first"] == "fold2" and p["try_holder"]
+            assert np.array_equal(p["order"], order) and np.array_equal(p["stream"], want) and p["stream_sum"] == want.sum()
+            assert np.array_equal(flag_bits(p["seven"], nk, s64), want <= 7) and np.array_equal(flag_bits(p["six"], nk, s64), want <= 6)
+            assert not p["seven"][nk:].any() and not p["six"][nk:].any()
+            seen = set(want.ravel().tolist()) if sort else seen
+    assert seen == {6, 7, 8}      # (the planted population, sorted)
+    # nothing but the first coding has an order: the folded pair first leaves every output empty
+    p = plan(counts_layout(bd, be, be2, two_max, two_total, e2), len(bins), nk, s64, rank_fold2=0)
+    assert p["first"] in ("fold", "rank") and p["stream_sum"] == 0 and not p["order"].any() and not p["try_holder"]

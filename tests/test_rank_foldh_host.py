@@ -1,10 +1,13 @@
 """The holder pair (options "rank_foldh", "foldh_holders", "foldh_min_planes") on the CPU: tests/foldh_model.py against
 brute force on planted populations and against the rule as the issue states it, and the figures of the benchmark's
-database (synth.make_sketches(10000)): H = 64, 163 stream planes, 2 693 184 entries."""
+database (synth.make_sketches(10000)): H = 64, 163 stream planes, 2 693 184 entries.  `choice` asks the numpy model
+AND the library (ppk_choose_holder, no device touched) and returns what both say (tests/coding_choice.py)."""
 import numpy as np
 import pytest
 
-from foldh_model import (LADDER, block_planes, buckets_of, choice, entries_of, foldh_codes_of, held_of, match_counts,
+from coding_choice import counts_layout, holder, plan
+from coding_choice import holder_choice as choice
+from foldh_model import (LADDER, block_planes, buckets_of, entries_of, foldh_codes_of, held_of, match_counts,
                          max_entries, owed_brute, planted_holders, position_eh, stream_planes)
 from rank_sort_model import in_slots, order_of
 
@@ -124,14 +127,20 @@ def test_the_benchmark_database():
     """synth.make_sketches(10000): the rule lands on H = 64 with 163 stream planes -- 2 in 77 blocks, 3 in 3 -- against
     the two-holder pair's 490, and 2 693 184 entries of which 1 463 328 carry count 1 and 1 223 377 more than 63"""
     from poppunk_amd import synth
-    from rank_model import unslice
-    from rank_sort_model import position_e2
+    from rank_fold2_model import counts_of
+    from rank_model import block_max, unslice
     from rank_sort_model import stream_planes as fold2_stream_planes
     n = 10000
     bins = unslice(synth.make_sketches(n)[0])
-    e2 = position_e2(bins)
+    d, s, s3, two = counts_of(bins)
+    e2 = s3 + 2                                          # (rank_sort_model.position_e2)
     fold2_sum = int(fold2_stream_planes(e2, order_of(e2)).sum())
     assert fold2_sum == 490
+    # the library's plan from the same figures: the two-holder pair first, its order and its 490 planes, the holder
+    # pair to be tried beside it
+    p = plan(counts_layout(block_max(d), block_max(s + 2), block_max(e2), int(two.max()), int(two.sum()), e2), n, 5, 16)
+    assert (p["first"], p["fallback"], p["stream_sum"], p["try_holder"]) == ("fold2", "fold", 490, True)
+    assert np.array_equal(p["order"], order_of(e2)) and np.array_equal(p["stream"], fold2_stream_planes(e2, order_of(e2)))
     cache = {}
 
     def eh_of(h):
@@ -142,6 +151,9 @@ def test_the_benchmark_database():
     assert eh_of(32).max() == 77 and eh_of(64).max() == 5
     planes = block_planes(eh_of(64), order_of(eh_of(64)))
     assert int(planes.sum()) == 163
+    got_h, got_order, got_planes, got_cap = holder(eh_of, p["stream_sum"], n, 5, 16, most_shared=int(s.max()))
+    assert got_h == 64 and int(got_planes.sum()) == 163 and np.array_equal(got_planes, planes)
+    assert np.array_equal(got_order, order_of(eh_of(64))) and got_cap == max_entries(n, 5)
     assert [np.bincount(row, minlength=5)[2:].tolist() for row in planes] == [[16, 0, 0], [16, 0, 0], [15, 1, 0], [15, 1, 0], [15, 1, 0]]
     ent = entries_of(bins, 64)
     assert len(ent) == 2693184 <= max_entries(n, 5)
