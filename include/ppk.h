@@ -147,6 +147,10 @@ int ppk_device_count(int *n);
  *                          20 352; smaller values send smaller sketches through the global-atomics route: tests)
  *     "sketch_batch_mb" (1 024)  the codes of one batch of whole samples of the host call (at least one sample)
  *     "sketch_batch" (0)   samples per batch, whatever the cap says (0 = from the cap; tests)
+ *     "sketch_count_bits" (0)  read samples: the bits B of a row of the count table, 4 .. 26 (0 = from the sample's own
+ *                          code count; PART OF THE RULE -- another B admits other k-mers on the table route; tests)
+ *     "sketch_exact_rounds" (64)  read samples: the most select passes of the exact route over one group before the
+ *                          call gives up with PPK_ERR_CAPACITY
  *   host calls
  *     "chunk_rows" (8 Mi)  rows per sub-band of a host query (about an eighth of the job, at least 1 Mi, below 16 Mi
  *                          rows); also scales the pieces of the fused host edge call
@@ -1614,6 +1618,48 @@ int ppk_sketch_dev(const uint8_t *d_codes, const long long *d_seq_off, size_t n,
 int ppk_sketch(const uint8_t *codes, const long long *seq_off, size_t n, const int32_t *kmers, size_t nk,
                size_t sketchsize64, size_t bbits, int flags, int device_id, uint64_t *sketches, long long *stats,
                int32_t *filled);
+
+/* ------------------------------------------------------------------------
+ * Sketching read sets: as above -- the same hash, bin, bin value, densify and layout, so that a sketch
+ * of reads and a sketch of an assembly are comparable -- but a k-mer may enter a bin only when it was seen at least
+ * min_count times in the sample.  All n samples are reads: every read is a contig (a code 5 between reads).
+ * A k-mer's count is the number of valid start positions of the sample whose kept hash equals its own (both strands
+ * together unless strand-preserved; counts are of 64-bit hash values).
+ *   table route (default)  [EXT: rows, remix and default B are this project's own; upstream's count-min table is
+ *                recalled, not pinned]  2 rows of 2^B 32-bit counters; a counter holds the sum of the counts of the
+ *                hashes that index it (ppk_sketch_count_index of ppk_device.h); a k-mer is admitted when both its
+ *                counters reach min_count.  A superset of the exact route's k-mers: no true k-mer is dropped.
+ *                B = ppk_sketch_count_bits(the sample's code count): 12 .. 26; option "sketch_count_bits" forces it.
+ *   exact route (PPK_SKETCH_EXACT)  a k-mer is admitted when its count reaches min_count.  The table is the first
+ *                filter; every bin's winner is then counted exactly, a bin whose winner falls short takes the next
+ *                admitted value above it, and so on until no bin fails: at most option "sketch_exact_rounds" select
+ *                passes per group of samples, else PPK_ERR_CAPACITY naming the first failing sample and k ("sample 0,
+ *                k 13: bins still hold a k-mer below the minimum count after 4 exact rounds").
+ *   min_count 1  admits everything and builds no table: words and filled are bit for bit those of ppk_sketch.
+ * A bin's value is the least admitted kept hash that falls in it; d_filled counts the bins with one.
+ *     min_count  1 .. 65 535
+ *     d_kstats   long long [n][nk][4]: occ (valid start positions), adm_occ (those whose k-mer passes the count table;
+ *                all of them at min_count 1; on BOTH routes the table's verdict -- exact counts exist for winners
+ *                only), filled, win_occ (the sum of the exact counts of the bins' winning k-mers)
+ *     d_stats    as above, except length: the winners are a uniform sample of the admitted distinct k-mers, so
+ *                adm_occ * filled / win_occ estimates their number; length is that estimate at the largest k, rounded
+ *                half up (ppk_sketch_reads_length), 0 when nothing was admitted.  The other five count all read bases.
+ * The same bits on every call, for every cut of the codes, every batch and every routing option: a counter only grows
+ * and is only asked "at least min_count?", so skipping the atomic once it shows min_count changes no answer.
+ * PPK_ERR_ARG before any device is touched: everything ppk_sketch checks, min_count outside 1 .. 65 535, an unknown flag,
+ * option "sketch_count_bits" outside 0, 4 .. 26; later: a sample of more than 2^32 - 1 codes (32-bit counters).
+ * Scratch: per (sample, k) of a group 24 bytes per bin (minimum, floor, winner count; groups of up to 512 MiB) and
+ * 2 x 2^B x 4 bytes of counters (groups of up to 512 MiB; a sample whose tables alone exceed that goes a few k at a time).
+ * ppk_sketch_reads_dev copies the n + 1 offsets to the host first (the groups are planned there), then enqueues on
+ * `stream`; the exact route synchronises it once per round. */
+#define PPK_SKETCH_EXACT 2
+int ppk_sketch_reads_dev(const uint8_t *d_codes, const long long *d_seq_off, size_t n, const int32_t *kmers, size_t nk,
+                         size_t sketchsize64, size_t bbits, int flags, int min_count, uint64_t *d_sketches,
+                         long long *d_stats, long long *d_kstats, int32_t *d_filled, void *stream);
+/* Host arrays of the same shapes, on device_id; blocking; batches as ppk_sketch ("sketch_batch_mb", "sketch_batch"). */
+int ppk_sketch_reads(const uint8_t *codes, const long long *seq_off, size_t n, const int32_t *kmers, size_t nk,
+                     size_t sketchsize64, size_t bbits, int flags, int min_count, int device_id, uint64_t *sketches,
+                     long long *stats, long long *kstats, int32_t *filled);
 
 /* ------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, the dominant kernel of each

@@ -13,7 +13,8 @@ SO_PATH = os.environ.get("PPK_LIBRARY") or os.path.join(_HERE, "csrc", "libppk_h
 OK, ERR_ARG, ERR_HIP, ERR_CAPACITY, ERR_STATE, ERR_INTERRUPTED = 0, 1, 2, 3, 4, 5
 REFINE_NOT_NESTED = 6      # ppk_refine_local_create_dev: the two lines do not form a bracket
 FLAG_RANDOM_CORRECT, FLAG_JACCARD, FLAG_COUNTS = 1, 2, 4
-SKETCH_STRAND_PRESERVED = 1      # flag of ppk_sketch / ppk_sketch_dev
+SKETCH_STRAND_PRESERVED = 1      # flag of ppk_sketch / ppk_sketch_dev / ppk_sketch_reads / ppk_sketch_reads_dev
+SKETCH_EXACT = 2                 # flag of ppk_sketch_reads / ppk_sketch_reads_dev: the exact route
 
 # every symbol include/ppk.h declares: name -> (restype, argtypes)
 _u64p, _f32p, _i32p, _u16p = (C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_int32),
@@ -110,6 +111,9 @@ SIGNATURES = {
                                     C.c_float, _sz, C.c_int, _llp, _llp, _f32p]),
     "ppk_sketch_dev": (C.c_int, [_vp, _vp, _sz, _i32p, _sz, _sz, _sz, C.c_int, _vp, _vp, _vp, _vp]),
     "ppk_sketch": (C.c_int, [C.POINTER(C.c_uint8), _llp, _sz, _i32p, _sz, _sz, _sz, C.c_int, C.c_int, _u64p, _llp, _i32p]),
+    "ppk_sketch_reads_dev": (C.c_int, [_vp, _vp, _sz, _i32p, _sz, _sz, _sz, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "ppk_sketch_reads": (C.c_int, [C.POINTER(C.c_uint8), _llp, _sz, _i32p, _sz, _sz, _sz, C.c_int, C.c_int, C.c_int, _u64p,
+                                   _llp, _llp, _i32p]),
     "ppk_density_kde_dev": (C.c_int, [_vp, _sz, _vp, _sz, _f32p, _f64p, _sz, _f64p, _sz, C.c_double, C.c_int, _vp, _f32p,
                                       _vp]),
     "ppk_density_kde": (C.c_int, [_f32p, _sz, _llp, _sz, _f32p, _f64p, _sz, _f64p, _sz, C.c_double, C.c_int, C.c_int,

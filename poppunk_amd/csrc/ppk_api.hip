@@ -83,6 +83,8 @@ const OptionEntry kOptions[] = {
     {"sketch_lds_bins", "PPK_SKETCH_LDS_BINS", &PpkConfig::sketch_lds_bins},
     {"sketch_batch_mb", "PPK_SKETCH_BATCH_MB", &PpkConfig::sketch_batch_mb},
     {"sketch_batch", "PPK_SKETCH_BATCH", &PpkConfig::sketch_batch},
+    {"sketch_count_bits", "PPK_SKETCH_COUNT_BITS", &PpkConfig::sketch_count_bits},
+    {"sketch_exact_rounds", "PPK_SKETCH_EXACT_ROUNDS", &PpkConfig::sketch_exact_rounds},
     {"knn_list", "PPK_KNN_LIST", &PpkConfig::knn_list},
     {"knn_warm", "PPK_KNN_WARM", &PpkConfig::knn_warm},
     {"knn_cut", "PPK_KNN_CUT", &PpkConfig::knn_cut},

@@ -316,6 +316,38 @@ __host__ __device__ __forceinline__ uint32_t ppk_sketch_densify_src(uint64_t mas
   return above ? blk * 64u + lane + (uint32_t)__builtin_ctzll(above) : next;
 }
 
+// ---- the count filter of read samples (ppk_sketch.hip, tests/sketch_reads_device_host.hip) ----
+// Which k-mers of a read sample may enter a bin: those whose PPK_SKETCH_COUNT_ROWS counters, one per row of 2^bits,
+// all reach the minimum count.  [EXT] The number of rows, the remix and the default number of bits are this project's
+// own: upstream's count-min table is recalled, not pinned.
+#define PPK_SKETCH_COUNT_ROWS 2
+#define PPK_SKETCH_COUNT_BITS_MIN 4       // what option "sketch_count_bits" may force: 4 .. 26
+#define PPK_SKETCH_COUNT_BITS_MAX 26      // (two rows of 2^26 32-bit counters: 512 MiB)
+// ROW INDEX [EXT]: the kept hash folded once, times an odd constant per row, cut to its top `bits` bits
+__host__ __device__ __forceinline__ uint64_t ppk_sketch_count_mult(int row) {
+  return row == 0 ? 0x9e3779b97f4a7c15ull : 0xc2b2ae3d27d4eb4full;
+}
+__host__ __device__ __forceinline__ uint32_t ppk_sketch_count_index(uint64_t h, int row, int bits) {
+  return (uint32_t)(((h ^ (h >> 29)) * ppk_sketch_count_mult(row)) >> (64 - bits));
+}
+// DEFAULT BITS [EXT]: a function of the sample's own code count alone -- four counters per code and row, rounded up to
+// a power of two, between 2^12 and 2^26 -- so that a sample is sketched the same in any company
+__host__ __device__ __forceinline__ int ppk_sketch_count_bits(long long codes) {
+  int b = 0;
+  while (b < PPK_SKETCH_COUNT_BITS_MAX && ((long long)1 << b) < codes) ++b;
+  b += 2;
+  return b < 12 ? 12 : b > PPK_SKETCH_COUNT_BITS_MAX ? PPK_SKETCH_COUNT_BITS_MAX : b;
+}
+// LENGTH of a read sample from the four integers of its largest k: adm_occ * filled / win_occ rounded half up (0 when
+// nothing was admitted).  Exact in 64 bits below 2^43 admitted occurrences; in double beyond.
+__host__ __device__ __forceinline__ long long ppk_sketch_reads_length(unsigned long long adm_occ, unsigned long long filled,
+                                                                      unsigned long long win_occ) {
+  if (win_occ == 0 || filled == 0) return 0;
+  if (adm_occ < ((unsigned long long)1 << 43) && filled < ((unsigned long long)1 << 19))
+    return (long long)((2 * adm_occ * filled + win_occ) / (2 * win_occ));
+  return (long long)((double)adm_occ * (double)filled / (double)win_occ + 0.5);
+}
+
 // ---- host only ----
 // Lower Cholesky factor {L00, L10, L11} of [[a, b], [b, d]], as LAPACK's dpotrf (scipy.linalg.cholesky, bgmm.py:131-
 // 176): false when a pivot is <= 0 or NaN

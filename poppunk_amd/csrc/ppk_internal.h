@@ -187,6 +187,8 @@ struct PpkConfig {
   std::atomic<long long> sketch_lds_bins{0};    // PPK_SKETCH_LDS_BINS: the most bins whose minima ppk_sketch_dev's hash kernel keeps in LDS (0 = as many as LDS holds, 20 352; smaller values send smaller sketches through the global-atomics route: tests; same bits)
   std::atomic<long long> sketch_batch_mb{1024}; // PPK_SKETCH_BATCH_MB: the codes of one batch of samples of the host call ppk_sketch (whole samples, at least one; same bits)
   std::atomic<long long> sketch_batch{0};       // PPK_SKETCH_BATCH: samples per batch whatever the cap says (0 = from the cap; tests; same bits)
+  std::atomic<long long> sketch_count_bits{0};  // PPK_SKETCH_COUNT_BITS: the bits B of a row of ppk_sketch_reads' count table, 4 .. 26 (0 = ppk_sketch_count_bits of the sample's code count; part of the rule: another B admits other k-mers on the table route; tests)
+  std::atomic<long long> sketch_exact_rounds{64}; // PPK_SKETCH_EXACT_ROUNDS: the most select passes of ppk_sketch_reads' exact route over one group of samples before it gives up with an error (same bits)
   std::atomic<long long> knn_list{0};           // PPK_KNN_LIST: entries of the neighbour-candidate list (0 = sized from n and knn)
   std::atomic<long long> host_parts_rows{16 << 20};   // PPK_HOST_PARTS_ROWS: ... from this many rows up
   std::atomic<long long> host_parts{2};         // PPK_HOST_PARTS: worker threads of a one-device host query (>= 16 Mi rows)
@@ -473,7 +475,7 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_RAND = 27,                         // the contingency sums' first-offender word and per-level state: segment ends, grouped sample indices, dense ranks, long classes
        SLOT_RAND_SUMS = 28,                    // ... and one batch of pairs' partial sums (sized after the levels have been read: growing a slot moves it)
        SLOT_LINEAGE = 29,                      // the strain lineages' first-offender words, id owners, segment and route tables, one band's key buffers and temp storage; the ranks' counts and offsets
-       SLOT_SKETCH = 30,                       // the sketcher's control words, piece table and one group of samples' per-bin minima
+       SLOT_SKETCH = 30,                       // the sketcher's control words, piece table and one group of samples' per-bin minima (read samples: floors, winner counts and count tables too)
        SLOT_COUNT = 31 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 // The fit tables in SLOT_LUT.  ppk_lut_ready: whether the tables of `key` (k list, random table, sketch size, options)

@@ -1123,6 +1123,43 @@ def sketch_dev(codes_t, seq_off, kmers, sketchsize64, bbits=14, strand_preserved
     return sketches, stats, filled
 
 
+def sketch_reads_dev(codes_t, seq_off, kmers, sketchsize64, min_count, exact=False, bbits=14, strand_preserved=False):
+    """Bin sketches of the read samples in codes_t (ppk_sketch_reads_dev; tests/sketch_reads_model.py
+    restates the rule): as sketch_dev, every read a contig (a code 5 between reads), with a k-mer entering a bin only
+    when the sample holds it at least min_count times (exact: the exact route; otherwise the count table [EXT]).
+    Returns CUDA tensors (sketches, stats, filled, kstats int64 [n, nk, 4] = occ, adm_occ, filled, win_occ);
+    stats[:, 0] is the estimate of the distinct admitted k-mers at the largest k."""
+    torch = _torch()
+    if not (codes_t.is_cuda and codes_t.dtype == torch.uint8 and codes_t.dim() == 1 and codes_t.is_contiguous()):
+        raise TypeError("codes_t must be a contiguous one-dimensional uint8 CUDA tensor")
+    dev = codes_t.device
+    if hasattr(seq_off, "is_cuda"):
+        off_t = seq_off.to(device=dev, dtype=torch.int64).contiguous()
+    else:
+        off_t = torch.as_tensor(np.ascontiguousarray(seq_off, dtype=np.int64), device=dev)
+    if off_t.dim() != 1 or off_t.numel() < 1:
+        raise ValueError("seq_off must be a one-dimensional array of n + 1 offsets")
+    n = int(off_t.numel()) - 1
+    if n > 0 and not hasattr(seq_off, "is_cuda") and int(np.asarray(seq_off).ravel()[-1]) > int(codes_t.numel()):
+        raise ValueError("seq_off ends beyond codes_t")
+    k = np.ascontiguousarray(kmers, dtype=np.int32).ravel()
+    nk, words = int(k.size), int(sketchsize64) * int(bbits)
+    flags = (_lib.SKETCH_STRAND_PRESERVED if strand_preserved else 0) | (_lib.SKETCH_EXACT if exact else 0)
+    with torch.cuda.device(dev):
+        sketches = torch.zeros((n, nk, max(words, 0)), dtype=torch.int64, device=dev)
+        stats = torch.zeros((n, 6), dtype=torch.int64, device=dev)
+        kstats = torch.zeros((n, nk, 4), dtype=torch.int64, device=dev)
+        filled = torch.zeros((n, nk), dtype=torch.int32, device=dev)
+        rc = _lib.lib().ppk_sketch_reads_dev(
+            C.c_void_p(codes_t.data_ptr() if codes_t.numel() else off_t.data_ptr()), C.c_void_p(off_t.data_ptr()), n,
+            k.ctypes.data_as(C.POINTER(C.c_int32)), nk, int(sketchsize64), int(bbits), flags, int(min_count),
+            C.c_void_p(sketches.data_ptr() or off_t.data_ptr()), C.c_void_p(stats.data_ptr() or off_t.data_ptr()),
+            C.c_void_p(kstats.data_ptr() or off_t.data_ptr()), C.c_void_p(filled.data_ptr() or off_t.data_ptr()),
+            _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_sketch_reads_dev")
+    return sketches, stats, filled, kstats
+
+
 def _strain_segments(seg_off):
     seg = np.ascontiguousarray(seg_off, dtype=np.int64)
     if seg.ndim != 1 or seg.shape[0] < 2:

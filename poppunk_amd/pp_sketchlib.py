@@ -668,20 +668,27 @@ def _write_db(db_name, ext, **content):
 
 def constructDatabase(db_name, samples, files, klist, sketch_size, codon_phased=False, calc_random=False,
                       use_rc=True, min_count=0, exact=False, num_threads=1, use_gpu=False, device_id=0):
-    """Sketch the assemblies `files` (per sample a path or a list of paths, FASTA, plain or gzip) on the MI355X and
-    write `<db_name>.h5` in the reference's layout, with every sample's real `length`, `missing_bases` and `base_freq`:
-    the keywords the reference passes at PopPUNK/sketchlib.py:410-422.  `use_gpu` and `num_threads` do not choose where
-    the sketching runs (there is no CPU path); `num_threads` host threads read the files (at most 16).
+    """Sketch the samples `files` (per sample a path or a list of paths, plain or gzip; FASTA = an assembly, FASTQ =
+    reads) on the MI355X and write `<db_name>.h5` in the reference's layout, with every sample's `length`,
+    `missing_bases` and `base_freq`: the keywords the reference passes at PopPUNK/sketchlib.py:410-422.  `use_gpu` and
+    `num_threads` do not choose where the sketching runs (there is no CPU path); `num_threads` host threads read the
+    files (at most 16).
 
-    [EXT] The sketch rule is this project's own (poppunk_amd.sketching, DESIGN.md 3.23): the database carries
-    sketch_version "poppunk_amd:sketch1" and is not bit-compatible with one pp-sketchlib wrote.  Not built, each a
-    one-line error: codon_phased=True, read input (FASTQ), min_count and exact other than their defaults.  Without
-    h5py and libhdf5 the same content is written as `<db_name>.npz`, and a line on stderr says so."""
+    Reads: with `min_count` >= 1 the FASTQ samples go through the count filter -- a k-mer enters a
+    bin only when the sample holds it at least min_count times; `exact` counts the winners exactly instead of
+    trusting the count table -- and the assemblies are sketched as before, into one database whose samples carry a
+    `reads` attribute (written only when there is a read sample).  A read sample's `length` is the estimate of its
+    distinct admitted k-mers at the largest k.  A FASTQ sample with min_count 0 or None is a ValueError ("looks like
+    FASTQ") and nothing is written; min_count >= 1 or exact without a FASTQ sample is a RuntimeError.
+
+    [EXT] The sketch rule is this project's own (poppunk_amd.sketching, DESIGN.md 3.23, 3.24): the database carries
+    sketch_version "poppunk_amd:sketch1" and is not bit-compatible with one pp-sketchlib wrote; the count table's
+    rows, remix and size are recalled from upstream's count-min filter, not pinned.  Not built, a one-line error:
+    codon_phased=True.  Without h5py and libhdf5 the same content is written as `<db_name>.npz`, and a line on stderr
+    says so."""
     from . import sketching
     if codon_phased:
         raise RuntimeError("constructDatabase: codon_phased sketches are not built")
-    if min_count not in (0, None) or exact:
-        raise RuntimeError("constructDatabase: min_count and exact count k-mers in reads; sketching reads is not built")
     samples = [str(s) for s in samples]
     klist = [int(k) for k in np.asarray(klist).ravel()]
     if len(samples) != len(files):
@@ -690,11 +697,20 @@ def constructDatabase(db_name, samples, files, klist, sketch_size, codon_phased=
         # [EXT] pp-sketchlib adds to a file that is there; here a database is written whole or not at all
         if os.path.exists(db_name + ext):
             raise RuntimeError("constructDatabase: %s%s exists; remove it (--overwrite) to sketch again" % (db_name, ext))
-    sketches, stats, _ = sketching.sketch_files(samples, files, klist, sketch_size, strand_preserved=not use_rc,
-                                                device_id=device_id, threads=num_threads)
+    try:
+        sketches, stats, _ = sketching.sketch_files(samples, files, klist, sketch_size, strand_preserved=not use_rc,
+                                                    device_id=device_id, threads=num_threads, min_count=min_count,
+                                                    exact=bool(exact))
+    except RuntimeError as e:
+        if "apply to read samples" in str(e):
+            raise RuntimeError("constructDatabase: min_count and exact count k-mers in reads; they apply to read "
+                               "samples (FASTQ) and none was given") from None
+        raise
     content = dict(names=samples, kmers=klist, sketches=sketches, sketchsize64=sketching.sketchsize64_of(sketch_size),
                    bbits=sketching.BBITS, lengths=stats[:, 0], base_freq=sketching.base_freq_of(stats),
                    missing_bases=stats[:, 1], sketch_version=sketching.SKETCH_VERSION)
+    if sketching.last_reads.any():
+        content["reads"] = [bool(x) for x in sketching.last_reads]
     try:
         sketchdb._h5_backend()
         ext = ".h5"
@@ -731,12 +747,13 @@ def addRandom(db_name, samples, klist, use_rc=True, num_threads=1):
         finally:
             f.close()
     loaded = sketchdb.load(db_name, names, kmers)
+    reads = sketchdb.reads_flags(path, names)
     mean_length = float(np.mean(loaded.lengths)) if loaded.lengths is not None and len(loaded.lengths) else 0.0
     table = random_table_for(kmers, mean_length, use_rc)
     _write_db(db_name, ext, names=loaded.names, kmers=kmers, sketches=loaded.sketches, sketchsize64=loaded.sketchsize64,
               bbits=loaded.bbits, random_table=table, clusters=np.zeros(len(names), dtype=np.uint16),
               lengths=loaded.lengths, base_freq=loaded.base_freq, missing_bases=loaded.missing_bases,
-              sketch_version=version)
+              sketch_version=version, **({} if reads is None else {"reads": reads}))
     clear_cache_of(path)
 
 

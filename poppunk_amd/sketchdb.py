@@ -174,11 +174,33 @@ def random_to_raw(random_table, clusters, names, kmers):
             "@k_min": np.uint32(min(kmers)), "@k_max": np.uint32(max(kmers)), "@use_rc": np.uint8(1)}
 
 
+def reads_flags(path, names):
+    """The per-sample `reads` flags of the database file `path` (.npz or .h5) in the order of `names`, or None when
+    the file stores none."""
+    if path.endswith(".npz"):
+        with np.load(path, allow_pickle=False) as z:
+            if "reads" not in z.files:
+                return None
+            pos = {str(nm): i for i, nm in enumerate(z["names"])}
+            return [bool(z["reads"][pos[str(nm)]]) for nm in names]
+    f = _h5_backend()[1](path, "r")
+    try:
+        top = f["sketches"]
+        flags = []
+        for nm in names:
+            attrs = top[str(nm)].attrs
+            flags.append(bool(np.asarray(attrs["reads"]).ravel()[0]) if "reads" in list(attrs.keys()) else None)
+        return None if all(x is None for x in flags) else [bool(x) for x in flags]
+    finally:
+        f.close()
+
+
 # ---- .npz ---------------------------------------------------------------------------------------
 
 def save_npz(db_name, names, kmers, sketches, sketchsize64, bbits, random_table=None,
-             clusters=None, random_raw=None, lengths=None, base_freq=None, missing_bases=None):
-    """db_name is the reference's `<prefix>/<basename>` (no extension)."""
+             clusters=None, random_raw=None, lengths=None, base_freq=None, missing_bases=None, reads=None):
+    """db_name is the reference's `<prefix>/<basename>` (no extension).  reads: per sample, whether it was sketched
+    from reads (stored only when given)."""
     os.makedirs(os.path.dirname(db_name) or ".", exist_ok=True)
     payload = dict(names=np.asarray(names, dtype=str), kmers=np.asarray(kmers, dtype=np.int32),
                    sketches=np.ascontiguousarray(sketches, dtype=np.uint64),
@@ -193,6 +215,8 @@ def save_npz(db_name, names, kmers, sketches, sketchsize64, bbits, random_table=
         payload["base_freq"] = np.asarray(base_freq, dtype=np.float64)
     if missing_bases is not None:
         payload["missing_bases"] = np.asarray(missing_bases, dtype=np.int64)
+    if reads is not None:
+        payload["reads"] = np.asarray(reads, dtype=np.uint8)
     for key, val in (random_raw or {}).items():
         val = np.asarray(val)
         if val.dtype == object:
@@ -338,11 +362,12 @@ def _load_h5(path, names, klist):
 
 def save_h5(db_name, names, kmers, sketches, sketchsize64, bbits, random_table=None, clusters=None,
             random_raw=None, lengths=None, base_freq=None, sketch_version="poppunk_amd", codon_phased=False,
-            missing_bases=None):
+            missing_bases=None, reads=None):
     """Write `<db_name>.h5` in the reference's layout (PopPUNK/web.py:14-61 for /sketches; attribute
     names as its readers use them, PopPUNK/sketchlib.py:124-133,155-158).  /random: `random_raw`
     verbatim when given (a round trip of what a conversion carried), else (random_table, clusters)
-    in the recalled pp-sketchlib layout [EXT]."""
+    in the recalled pp-sketchlib layout [EXT].  reads: per sample, whether it was sketched from reads -- the `reads`
+    attribute qc.sketchlibAssemblyQC looks for, written only when given."""
     _, h5open = _h5_backend()
     os.makedirs(os.path.dirname(db_name) or ".", exist_ok=True)
     sketches = np.ascontiguousarray(sketches, dtype=np.uint64)
@@ -359,6 +384,8 @@ def save_h5(db_name, names, kmers, sketches, sketchsize64, bbits, random_table=N
             g.attrs["kmers"] = np.asarray(kmers, dtype=np.int64)
             g.attrs["length"] = np.int64(lengths[i] if lengths is not None else 0)
             g.attrs["missing_bases"] = np.int64(missing_bases[i] if missing_bases is not None else 0)
+            if reads is not None:
+                g.attrs["reads"] = bool(reads[i])
             bf = np.asarray(base_freq[i] if base_freq is not None else [0.25] * 4, dtype=np.float64)
             if not np.isnan(bf).any():        # a NaN row = a sample that had no base_freq attribute: it gets none
                 g.attrs["base_freq"] = bf

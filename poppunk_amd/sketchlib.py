@@ -89,7 +89,8 @@ def _write_fit_example(klist, raw, raw_fit, corrected, corrected_fit, out_prefix
 
 def constructDatabase(assemblyList, klist, sketch_size, oPrefix, threads, overwrite, strand_preserved, min_count,
                       use_exact, calc_random=True, codon_phased=False, use_gpu=False, deviceid=0):
-    """Sketch the assemblies listed in `assemblyList` (readRfile: name and file(s) per line) at the k-mer lengths
+    """Sketch the assemblies and read sets listed in `assemblyList` (readRfile: name and file(s) per line; FASTQ files
+    are reads and need `min_count` >= 1, `use_exact` counts their winning k-mers exactly: DESIGN.md 3.24) at the k-mer lengths
     `klist` into `<oPrefix>/<basename>.h5` and return the sample names, sorted (PopPUNK/sketchlib.py:348-434: same
     signature, messages and return value).  With `overwrite` an existing database file is removed first; with
     `calc_random` the random match chances are added (addRandom).  The sketching runs on the MI355X
