@@ -503,6 +503,118 @@ def test_scale_rows_dtype_rule():
     assert scale_rows(X, s64).dtype == np.float64 and not np.array_equal(scale_rows(X, s64), scale_rows(X, s32))
 
 
+# ---- 4b. the inputs of tests/test_gpu_dbscan_shapes.py reach what they were built for ---------------------------------------
+@pytest.mark.parametrize("n", [16, 34, 514, 4096])
+def test_two_chains_hook_into_two_deep_trees(n):
+    import dbscan_shapes as S
+    P = S.two_chains(n)                                       # (asserts the float32 round trip itself)
+    assert P.dtype == np.float32 and P.shape == (n, 2)
+    h = n // 2
+    assert np.all(P[:h, 1] == 0.0) and np.all(P[h:, 1] == 64.0)
+    for chain in (P[:h, 0].astype(np.float64), P[h:, 0].astype(np.float64)):
+        gaps = np.diff(chain)
+        assert np.all(gaps > 0) and np.all(np.diff(gaps) < 0)
+    partner = S.least_partner(P, ref_core2(P, 1))
+    assert np.array_equal(partner, S.chain_successors(n))
+    # followed from any point, the least edges reach the chain's last pair: one tree per chain, about n / 2 deep
+    assert partner[h - 2] == h - 1 and partner[h - 1] == h - 2 and partner[n - 2] == n - 1 and partner[n - 1] == n - 2
+
+
+def test_lattice_ties():
+    import dbscan_shapes as S
+    P = S.lattice(33)
+    assert P.shape == (1089, 2) and np.array_equal(P[34], np.float32([1 / 32, 1 / 32]))
+    core2 = ref_core2(P, 4)
+    assert len(np.unique(core2)) == 3                         # corner, side and inner points
+    assert len(np.unique(ref_mst(P, core2)[2])) == 3
+    # many rows tie exactly at the rank: an inner point has four neighbours at each of its 4th and 8th distances
+    d2 = np.sort(ref_d2(P)[33 * 16 + 16])
+    assert d2[1] == d2[4] < d2[5] == d2[8] < d2[9]
+    P = S.lattice(22)
+    core2 = ref_core2(P, 4)
+    for x, y in zip(ref_mst(P, core2), ref_mst_kruskal(P, core2)):
+        assert np.array_equal(x.view(np.uint64) if x.dtype == np.float64 else x,
+                              y.view(np.uint64) if y.dtype == np.float64 else y)
+
+
+def test_wide_range_spans_the_exponent_passes():
+    import dbscan_shapes as S
+    P = S.wide_range(2049, 0)
+    assert P.dtype == np.float32 and np.all(np.isfinite(P)) and np.all(P != 0)
+    core2 = ref_core2(P, 7)
+    assert np.all(np.isfinite(core2)) and np.all(core2 > 0)
+    e = np.frexp(core2)[1]
+    assert e.min() <= -100 and e.max() >= 100
+    # the six two-bit passes over the exponent field each branch more than one way across the rows
+    key = core2.view(np.uint64)
+    for shift in range(62, 50, -2):
+        assert len(np.unique((key >> np.uint64(shift)) & np.uint64(3))) >= 2, shift
+
+
+def test_grid_restatement_and_the_row_sets_of_the_tall_grid():
+    import dbscan_shapes as S
+    P, rows = S.tall_grid_points()
+    assert P.shape == (20000, 2) and rows.shape == (4000, 2)
+    G = S.grid_of(P)
+    assert G.g == 70 and G.count.sum() == 20000 and G.count.shape == (70, 70)
+    assert np.array_equal(G.count, np.histogram2d(G.cy, G.cx, bins=[np.arange(71), np.arange(71)])[0])
+    A, tall, whole = S.tall_grid_row_sets(G, rows, S.TALL_M)
+    assert len(tall) == 761 and len(A) > 0 and len(whole) > 0
+    assert set(A.tolist()) <= set(tall.tolist()) and not set(whole.tolist()) & set(tall.tolist())
+    print("first 1500 rows at m = %d: %d first squares of more than 64 grid rows, set A %d, whole grid at once %d"
+          % (S.TALL_M, len(tall), len(A), len(whole)))
+    # a row of set A by hand: its square holds the target, the square one step smaller did not
+    gr, gc, is_all, dk2, safe = S.first_square(G, rows[A[0]].astype(np.float64), S.TALL_M)
+    assert 64 < gr <= 70 and not is_all and dk2 < 0.9 * safe * safe
+    # at a small m no square grows that tall: the largest min_samples is what reaches the branch
+    assert len(S.tall_grid_row_sets(G, rows, 25)[1]) == 0
+    # with the float64 scale of the GPU test the sets are not empty either
+    assert len(S.tall_grid_row_sets(G, rows, S.TALL_M, scale=np.array([1.1, 0.9]))[0]) > 0
+    # far rows: three fail their first square and regrow into the whole grid; (0.5, 1e6) certifies in a square that
+    # spans every column (only the side below it has cells beyond)
+    got = []
+    for q in S.FAR_ROWS.astype(np.float64):
+        gr, gc, is_all, dk2, safe = S.first_square(G, q, S.TALL_M)
+        got.append((bool(safe > 0.0 and dk2 < safe * safe), gc == G.g, S.regrown_square_is_all(G, dk2)))
+    assert got == [(False, False, True), (False, False, True), (True, True, True), (False, False, True)]
+    assert S.scanned_far_rows(G, S.TALL_M) == [0, 1, 3]
+    # the blob of this input lies in the first grid rows of every tall square: the count's first run holds the target
+    assert not any(S.rows_past_the_64th_decide(G, rows[i].astype(np.float64), S.TALL_M) for i in A)
+    # with the blob against the upper edge every row of set A needs the grid rows past its square's 64th
+    P2, rows2 = S.tall_grid_points("top")
+    G2 = S.grid_of(P2)
+    A2, tall2, whole2 = S.tall_grid_row_sets(G2, rows2, S.TALL_M)
+    assert G2.g == 70 and len(A2) > 0 and len(whole2) > 0
+    assert all(S.rows_past_the_64th_decide(G2, rows2[i].astype(np.float64), S.TALL_M) for i in A2)
+    assert S.scanned_far_rows(G2, S.TALL_M) == [0, 2, 3]
+    assert len(S.tall_grid_row_sets(G2, rows2, S.TALL_M, scale=np.array([1.1, 0.9]))[0]) > 0
+    print("blob against the upper edge: %d tall first squares, set A %d, whole grid at once %d" % (len(tall2), len(A2), len(whole2)))
+    # the whole grid at once when the training set is smaller than the target
+    Ps = blobs(100, 0)
+    assert S.first_square(S.grid_of(Ps), np.array([0.5, 0.5]), 40)[2]
+    # a box without width or height has cells of width 1.0 there
+    line = np.stack([np.full(400, 0.5, dtype=np.float32), np.linspace(0, 1, 400, dtype=np.float32)], axis=1)
+    Gl = S.grid_of(line)
+    assert (Gl.g, Gl.wx) == (10, 1.0) and Gl.wy == pytest.approx(0.1) and np.all(Gl.cx == 0)
+
+
+@pytest.mark.parametrize("n,n_cl", [(300, 200), (2300, 500)])
+def test_assignment_block_form_equals_row_form_on_a_deep_chain(n, n_cl):
+    import dbscan_shapes as S
+    m = 10
+    M = S.synthetic_model(n, n_cl, np.random.default_rng(n))
+    assert M.cl_parent[0] == -1 and np.all(M.cl_parent[1:] < np.arange(1, n_cl)) and np.all(M.cl_parent[1:] >= 0)
+    assert np.array_equal(M.cl_parent[1:n_cl // 2 + 1], np.arange(n_cl // 2))
+    assert np.all(M.core2 > 0) and np.all(M.cl_birth[1:] > 0) and np.all(M.pt_lambda > 0)
+    assert set(np.unique(M.cl_label).tolist()) == {-1, 0, 1, 2, 3, 4} and M.n_clusters == 5
+    Q = np.vstack([M.points[::5], planted_rows(M.points, np.random.default_rng(1)),
+                   np.random.default_rng(2).uniform(-3, 4, (200, 2)).astype(np.float32)]).astype(np.float64)
+    rows = np.array([ref_assign_row(q, M.points, M.core2, m, M) for q in Q])
+    assert np.array_equal(rows, ref_assign(Q, M.points, M.core2, m, M, block=64))
+    assert len(np.unique(rows)) == 6
+    assert max(S.walk_depth(q, M, m) for q in Q) >= n_cl // 4
+
+
 # ---- 5. persistence ----------------------------------------------------------------------------------------------------------
 def host_model(P, m, c, within=0, between=1):
     """A DBSCANModel filled from the restatement (no device)."""
