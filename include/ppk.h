@@ -275,7 +275,7 @@ size_t ppk_db_rank_counts(const ppk_db *db, uint32_t *out, size_t cap);
  * at its (k, bin) position is coded 0 on the ref side and 1 on the query side, and only the values with more than H
  * holders keep codes 2 + rank.  The positions of each k are sorted by E_H = (values with more than H holders) + 2,
  * descending, ties by stored position; a block of 64 slots then spans at most 16 codes and the tile kernel compares 4, 3
- * (at most 8 codes) or 2 (at most 4) of the chunk's 8 planes (option "foldh_min_planes", PPK_FOLDH_MIN_PLANES, default 2,
+ * (at most 8 codes) or 2 (at most 4) planes of the 4 the pair stores per block (option "foldh_min_planes", PPK_FOLDH_MIN_PLANES, default 2,
  * read at launch: 3 or 4 keep every block at that many or more).  What a (pair, k) is owed -- its matches on values with
  * 2 .. H holders -- is found once, at creation, by comparing a temporary pair that codes those values alone, and kept as
  * 32-bit entries hi % 256 | (lo % 32) << 8 | k << 13 | count << 16 in the buckets of the two-holder pair's events; the
@@ -286,9 +286,12 @@ size_t ppk_db_rank_counts(const ppk_db *db, uint32_t *out, size_t cap);
  * (pair, k) leave the database without the pair ("rank_foldh" 2: more than all of them).  Caps: those of the two-holder
  * pair, fewer than 2^24 samples, at most 1 024 shared values per position.
  * ppk_db_foldh_holders: H, 0 without the pair.  ppk_db_foldh_stream_planes / _position_order / _read: as their fold2_
- * namesakes (planes 4 .. 7 of the 8 read back are zero).  ppk_db_foldh_entries / _entries_read: as ppk_db_fold2_events /
+ * namesakes; ppk_db_foldh_chunk_planes: the planes a stored block holds and _read returns, 4 (the codes are those of an
+ * 8-plane coding whose planes 4 .. 7 are zero everywhere and are not kept), 0 without the pair: `words` of _read is
+ * nk * sketchsize64 * chunk planes * padded samples.  ppk_db_foldh_entries / _entries_read: as ppk_db_fold2_events /
  * _events_read, 32 bits per entry. */
 unsigned ppk_db_foldh_holders(const ppk_db *db);
+int ppk_db_foldh_chunk_planes(const ppk_db *db);
 int ppk_db_foldh_stream_planes(const ppk_db *db, uint8_t *out, size_t cap);
 int ppk_db_foldh_position_order(const ppk_db *db, uint32_t *out, size_t cap);
 int ppk_db_foldh_read(const ppk_db *db, int which, uint64_t *out, size_t words);

@@ -177,6 +177,7 @@ SIGNATURES = {
     "ppk_db_fold2_events_read": (C.c_int, [_vp, _vp, _sz, _vp, _sz]),
     "ppk_db_rank_counts": (_sz, [_vp, _vp, _sz]),
     "ppk_db_foldh_holders": (C.c_uint, [_vp]),
+    "ppk_db_foldh_chunk_planes": (C.c_int, [_vp]),
     "ppk_db_foldh_stream_planes": (C.c_int, [_vp, _vp, _sz]),
     "ppk_db_foldh_position_order": (C.c_int, [_vp, _vp, _sz]),
     "ppk_db_foldh_read": (C.c_int, [_vp, C.c_int, _vp, _sz]),

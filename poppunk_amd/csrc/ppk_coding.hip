@@ -706,7 +706,8 @@ int ppk_foldh_count(const ppk_db *db, const unsigned *ladder, unsigned **d_twice
 }
 int ppk_build_foldh(ppk_db *db, unsigned H, const unsigned *d_twice, const uint16_t *d_holders, size_t max_entries, hipStream_t s) {
   const size_t n = db->n, npad = db->npad, n_pos = db->nk * db->s64 * 64, n_kb = db->nk * db->s64;
-  const size_t copy_bytes = npad * n_kb * 8 * sizeof(uint64_t), tmp_bytes = npad * n_kb * (size_t)RANK_BB * sizeof(uint64_t);
+  // (the copies keep PPK_FOLDH_CHUNK_PLANES planes of a block: no kept code reaches 2^4, PPK_FOLDH_MAX_CODES)
+  const size_t copy_bytes = npad * n_kb * PPK_FOLDH_CHUNK_PLANES * sizeof(uint64_t), tmp_bytes = npad * n_kb * (size_t)RANK_BB * sizeof(uint64_t);
   const unsigned qt = (unsigned)(npad / 32), rt = (unsigned)(npad / 256);
   const size_t nb = (size_t)qt * rt, cap = max_entries ? max_entries : 1;
   // the counts of one band: at most 512 MB, whole blocks of 256 query rows, no more than a dispatch holds
@@ -747,7 +748,7 @@ int ppk_build_foldh(ppk_db *db, unsigned H, const unsigned *d_twice, const uint1
   const dim3 grid_pos((unsigned)(n_kb * 8)), grid_slice((unsigned)(n_kb * 8), (unsigned)(npad / 256));
   hipLaunchKernelGGL(foldh_code_kernel, grid_pos, dim3(256), 0, s, db->d_skT, d_twice, d_holders, d_kept, d_owed, n, npad, H);
   hipLaunchKernelGGL(fold2_slice_kernel, grid_slice, dim3(256), 0, s, d_kept, d_order, reinterpret_cast<uint8_t *>(c.d_ref),
-                     reinterpret_cast<uint8_t *>(c.d_qry), n, npad, (int)db->s64, 8);
+                     reinterpret_cast<uint8_t *>(c.d_qry), n, npad, (int)db->s64, PPK_FOLDH_CHUNK_PLANES);
   hipLaunchKernelGGL(foldh_slice14_kernel, grid_slice, dim3(256), 0, s, d_owed, reinterpret_cast<uint8_t *>(d_tr),
                      reinterpret_cast<uint8_t *>(d_tq), n, npad);
   e = hipGetLastError();
@@ -1111,8 +1112,8 @@ static int coding_check(const char *fn, const ppk_db *db, const void *out, int k
 static int coding_read(const char *fn, const ppk_db *db, int kind, int which, uint64_t *out, size_t words) {
   if (int rc = coding_check(fn, db, out, kind, which)) return rc;
   const PpkCoding &c = db->coding[kind];
-  if (words != db->nk * db->s64 * (size_t)c.planes * db->npad)
-    return fail_in(fn, PPK_ERR_ARG, std::string("`words` is not nk * sketchsize64 * ") + (kind == PPK_CODING_FOLDH ? "8" : "planes") + " * padded samples");
+  if (words != db->nk * db->s64 * (size_t)c.chunk_planes() * db->npad)
+    return fail_in(fn, PPK_ERR_ARG, std::string("`words` is not nk * sketchsize64 * ") + (kind == PPK_CODING_FOLDH ? "chunk planes" : "planes") + " * padded samples");
   PPK_ENTER_DEVICE(guard, db->device);
   PPK_HIP(hipDeviceSynchronize());
   if (kind == PPK_CODING_RANK)
@@ -1195,6 +1196,7 @@ extern "C" int ppk_db_fold2_events_read(const ppk_db *db, uint32_t *off, size_t 
   return coding_list_read(__func__, db, PPK_CODING_FOLD2, off, n_off, ev, n_ev);
 }
 extern "C" unsigned ppk_db_foldh_holders(const ppk_db *db) { return db ? db->coding[PPK_CODING_FOLDH].holders : 0u; }
+extern "C" int ppk_db_foldh_chunk_planes(const ppk_db *db) { return db ? db->coding[PPK_CODING_FOLDH].chunk_planes() : 0; }
 extern "C" int ppk_db_foldh_read(const ppk_db *db, int which, uint64_t *out, size_t words) { return coding_read(__func__, db, PPK_CODING_FOLDH, which, out, words); }
 extern "C" int ppk_db_foldh_stream_planes(const ppk_db *db, uint8_t *out, size_t cap) { return coding_stream_planes(__func__, db, PPK_CODING_FOLDH, out, cap); }
 extern "C" int ppk_db_foldh_position_order(const ppk_db *db, uint32_t *out, size_t cap) { return coding_position_order(__func__, db, PPK_CODING_FOLDH, out, cap); }

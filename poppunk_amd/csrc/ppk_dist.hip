@@ -950,7 +950,9 @@ dist_kernel_v2_fold2(const uint64_t *__restrict__ refT, const uint64_t *__restri
 #include "ppk_dist_tile.inc"
 }
 
-// The same kernel on the holder pair (PPK_CODING_FOLDH, an 8-plane chunk whose planes 4 .. 7 are zero):
+// The same kernel on the holder pair (PPK_CODING_FOLDH: the 8-plane coding, stored and copied as a 4-plane chunk,
+// PPK_FOLDH_CHUNK_PLANES -- planes 4 .. 7 are zero in every block, so a block is 8 ref pieces and one query piece, 9 KB
+// through L2 into LDS instead of 18, two DMA pieces per wavefront instead of three).
 // FOLDH swaps the three streams for the 4- / 3- / 2-plane ones and the correction block for the one that adds the
 // database's 12-bit entries (DistParams::fold2_ev / fold2_off carry its d_list / d_off; rank_short / fold2_six
 // the 3- and the 2-plane flags).  A kernel of its own name again: every other symbol stays the code it was.

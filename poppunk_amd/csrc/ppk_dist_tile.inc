@@ -23,13 +23,17 @@
   const int ablate = EXP ? p.ablate : 0;
   constexpr int R = V2_R, TQ = V2_TQ, BB = V2_BB;
   constexpr int V2_QT = NW * TQ;              // queries per workgroup tile (32)
-  constexpr int REF_U4 = PL * 128;            // 14 rows x 256 samples x 8 B = 28 KB
-  constexpr int QRY_U4 = PL * (V2_QT / 2);    // 14 rows x QT samples x 8 B = 3.5 / 7 KB
+  // CPL: the planes of a STORED chunk, which is what is copied.  PL everywhere but on the holder pair, whose blocks
+  // never span more than 16 codes: its copies keep planes 0 .. 3 only (PPK_FOLDH_CHUNK_PLANES), 8 ref pieces and one
+  // query piece per block, two DMA pieces per wavefront
+  constexpr int CPL = FOLDH ? PPK_FOLDH_CHUNK_PLANES : PL;
+  constexpr int REF_U4 = CPL * 128;           // 14 rows x 256 samples x 8 B = 28 KB
+  constexpr int QRY_U4 = CPL * (V2_QT / 2);   // 14 rows x QT samples x 8 B = 3.5 / 7 KB
   constexpr int CHUNK_U4 = REF_U4 + QRY_U4;   // one 64-bin block of the tile
   constexpr int LPP = V2_QT / 2;              // lanes (16 B each) per query row
   constexpr int PPP = 64 / LPP;               // query rows per one-KB DMA piece
-  constexpr int NQP = (PL + PPP - 1) / PPP;   // query pieces per chunk
-  constexpr int NPIECE = 2 * PL + NQP;        // 28 ref pieces + query pieces
+  constexpr int NQP = (CPL + PPP - 1) / PPP;  // query pieces per chunk
+  constexpr int NPIECE = 2 * CPL + NQP;       // 28 ref pieces + query pieces
   constexpr int PW = (NPIECE + NW - 1) / NW;  // DMA pieces per wavefront per chunk
   // double buffer: 63 KB.  The modes with a per-pair fit take 80 KB -- two workgroups then own all
   // 160 KB of a CU -- so that the epilogue of an interior tile can hold the whole (E, F) table
@@ -165,16 +169,16 @@
     dbase[t] = nullptr;
     dstep[t] = 0;
     doff[t] = 0;
-    if (i < 2 * PL) {
+    if (i < 2 * CPL) {
       dkind[t] = 0;
-      dbase[t] = reinterpret_cast<const char *>(refT + ((size_t)k_first * ublocks * PL + (size_t)(i >> 1)) * p.npad_r + r0 + (i & 1) * 128);
-      dstep[t] = (size_t)PL * p.npad_r * 8;
+      dbase[t] = reinterpret_cast<const char *>(refT + ((size_t)k_first * ublocks * CPL + (size_t)(i >> 1)) * p.npad_r + r0 + (i & 1) * 128);
+      dstep[t] = (size_t)CPL * p.npad_r * 8;
       doff[t] = i * 64;
     } else if (i < NPIECE) {
-      const int j = i - 2 * PL;
+      const int j = i - 2 * CPL;
       dkind[t] = 1;
-      dbase[t] = reinterpret_cast<const char *>(qryT + ((size_t)k_first * ublocks * PL + (size_t)(PPP * j)) * p.npad_q + q0);
-      dstep[t] = (size_t)PL * p.npad_q * 8;
+      dbase[t] = reinterpret_cast<const char *>(qryT + ((size_t)k_first * ublocks * CPL + (size_t)(PPP * j)) * p.npad_q + q0);
+      dstep[t] = (size_t)CPL * p.npad_q * 8;
       doff[t] = REF_U4 + j * 64;
     } else {
       dkind[t] = 2;
@@ -183,7 +187,7 @@
   const uint32_t voff_ref = lane * 16;
   const uint32_t voff_qry = (uint32_t)((lane / LPP) * p.npad_q * 8) + (lane % LPP) * 16;
   // the last query piece may hold fewer than PPP rows (14 and 10 are no multiples of 4)
-  const bool qlane_ok = (PPP * (NQP - 1) + lane / LPP) < PL;
+  const bool qlane_ok = (PPP * (NQP - 1) + lane / LPP) < CPL;
   // skip_first_half: a half tile does not copy the even ref pieces (samples 0..127 of each row);
   // with 8 waves piece parity is wave parity
   auto issue_dma = [&](int buf, bool skip_first_half) {
@@ -308,8 +312,8 @@
 #define PPK_HALF_STMT(SUF)                                                                                  \
   asm volatile(PPK_BLOCK_HALF_ASM_Q32##SUF : PPK_BLOCK_OPERANDS : [rp] "v"(rp), [qp] "v"(qp) \
                : "memory", PPK_BLOCK_CLOBBERS);
-          if constexpr (FOLDH) {      // (planes 4 .. 7 of the holder pair are zero everywhere)
-            asm volatile(PPK_BLOCK_HALF_H4_ASM_Q32_P8 : PPK_BLOCK_OPERANDS : [rp] "v"(rp), [qp] "v"(qp)
+          if constexpr (FOLDH) {      // (every plane of the holder pair's 4-plane chunk)
+            asm volatile(PPK_BLOCK_HALF_H4_ASM_Q32_P4 : PPK_BLOCK_OPERANDS : [rp] "v"(rp), [qp] "v"(qp)
                          : "memory", PPK_BLOCK_CLOBBERS);
           } else {
             PPK_BLOCK_BY_PLANES(PPK_HALF_STMT)
@@ -318,8 +322,8 @@
         } else if constexpr (DMA_IN_STREAM) {
           // the in-stream variant issues the wavefront's PW pieces: PW - 1 ref pieces 8 KB apart and a LAST one that is a
           // ref piece, a query piece or (fewer than 8 PW pieces in a block) nothing, by wavefront
-          static_assert(NW != 8 || PW == (PL >= 12 ? 4 : 3), "DMA pieces per wavefront of the generated stream");
-          static_assert(2 * PL >= NW * (PW - 1), "every piece but a wavefront's last is a ref piece");
+          static_assert(NW != 8 || PW == (FOLDH ? 2 : PL >= 12 ? 4 : 3), "DMA pieces per wavefront of the generated stream");
+          static_assert(2 * CPL >= NW * (PW - 1), "every piece but a wavefront's last is a ref piece");
           constexpr int LT = PW - 1;
           const uint32_t lbase =
               (uint32_t)(size_t)(__attribute__((address_space(3))) void *)(lds + (buf ^ 1) * CHUNK_U4);
@@ -355,7 +359,7 @@
           if constexpr (PL < V2_BB) {
             if constexpr (PL == 12) { PPK_DMA_SEL_STMT(_P12, 2) }
             else if constexpr (PL == 10) { PPK_DMA_SEL_STMT(_P10, LT) }
-            else if constexpr (FOLDH) { PPK_DMA_SEL3_STMT_OF(PPK_BLOCK_DMA_SELH_ASM_Q32_P8, LT) }
+            else if constexpr (FOLDH) { PPK_DMA_SEL3_STMT_OF(PPK_BLOCK_DMA_SELH_ASM_Q32_P4, LT) }
             else if constexpr (FOLD2) { PPK_DMA_SEL3_STMT(_P8, LT) }
             else { PPK_DMA_SEL_STMT(_P8, LT) }
           } else {

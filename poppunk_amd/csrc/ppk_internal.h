@@ -63,9 +63,11 @@ enum PpkCodingKind {
   // rank_counts and is derived from them where it is asked for.
   PPK_CODING_FOLD2 = 2,
   // The holder pair, built BESIDE the two-holder pair where it compares far fewer planes (option "rank_foldh"): the
-  // same two copies in the same 8-plane layout, but EVERY value with at most `holders` (H) holders is coded 0 / 1 and
-  // only the values with more than H holders keep codes 2 + rank, so that a sorted block of 64 slots spans at most 16
-  // codes and streams 4 (`stream_planes`), 3 (less1) or 2 (less2 as well) planes; planes 4 .. 7 are zero.  Slot i of k
+  // same two copies, but EVERY value with at most `holders` (H) holders is coded 0 / 1 and only the values with more
+  // than H holders keep codes 2 + rank, so that a sorted block of 64 slots spans at most 16 codes and streams 4
+  // (`stream_planes`), 3 (less1) or 2 (less2 as well) planes.  `planes` stays 8 -- the coding is the two-holder pair's
+  // 8-plane one -- but planes 4 .. 7 are zero in every block and are not stored: the copies are laid out
+  // [(k * s64 + blk) * 4 + plane][npad] (chunk_planes(): what a launch copies per block, half the bytes).  Slot i of k
   // holds stored position order[k * 64 * s64 + i] (E_H descending, ties by stored position).  What the compare then
   // misses is a COUNT per (pair, k): the matches on values with 2 .. H holders, found once at creation by comparing a
   // temporary pair that codes those values alone.  Non-zero counts are the 32-bit entries of the list:
@@ -73,11 +75,14 @@ enum PpkCodingKind {
   PPK_CODING_FOLDH = 3,
   PPK_CODINGS = 4
 };
+#define PPK_FOLDH_CHUNK_PLANES 4     // planes the holder pair stores per chunk (PPK_FOLDH_MAX_CODES = 2^4 codes)
 struct PpkCoding {
   PpkCodingKind kind = PPK_CODING_RANK;
   uint64_t *d_ref = nullptr, *d_qry = nullptr;      // the copies a launch reads on either side
   int planes = 0;                                   // of the layout; 0 = no such coding
   int stream_planes = 0;                            // the most a block compares: `planes`, 4 for the holder pair
+  // the planes of a stored 64-bin chunk, [(k * s64 + blk) * chunk_planes() + plane][npad]: `planes` but for the holder pair
+  int chunk_planes() const { return kind == PPK_CODING_FOLDH && planes ? PPK_FOLDH_CHUNK_PLANES : planes; }
   unsigned holders = 0;                             // H (holder pair)
   // per k the 64-bin blocks that compare one plane fewer than stream_planes, and two fewer
   unsigned less1[PPK_RANK_SHORT_WORDS] = {}, less2[PPK_RANK_SHORT_WORDS] = {};

@@ -247,7 +247,8 @@ class SketchDB:
     def foldh_codes(self, which):
         """One copy of the holder pair un-bitsliced (tests), 0 the ref side, 1 the query side: uint16
         [n, nk, 64 * sketchsize64] codes, in stored position order (the sort of foldh_position_order() undone)."""
-        return self._codes("ppk_db_foldh_read", 8, which, self.foldh_position_order())
+        planes = int(_lib.lib().ppk_db_foldh_chunk_planes(self._h))      # (the planes a block stores: 4)
+        return self._codes("ppk_db_foldh_read", planes, which, self.foldh_position_order())
 
     def foldh_entries(self):
         """What the holder pair's compare owes (ppk_db_foldh_entries_read): (offsets uint32 [npad / 32, npad / 256]

@@ -3,7 +3,7 @@
 stream for ONE 64-bin block (14 bit-planes) of the 4-ref x 4-query register tile, and the same
 stream for the 12, 10 and 8 planes of a rank-coded database (RANK_PLANES below), each with a "short" variant that
 leaves the top plane out (short_dma_planes), for the two-holder pair at 8 planes one that leaves two out, and for the
-holder pair (dist_kernel_v2_foldh) the 4-, 3- and 2-plane streams of the same 8-plane chunk.
+holder pair (dist_kernel_v2_foldh) the 4-, 3- and 2-plane streams of its 4-plane chunk.
 
 Why assembly: on MI355X a v_bitop3_b32 whose src0 and src1 sit in the same VGPR bank
 (register number mod 4) issues ~1.5x slower (tools/ubench_bank.hip: 4.7 vs 3.1 clk).  hipcc
@@ -51,6 +51,21 @@ def shorter_dma_planes(pl, fewer):
     return tuple((2 * p * (pl - fewer) + pl) // (2 * pl) for p in RANK_PLANES[pl][1])
 
 
+# The holder pair's stored chunk: 4 planes, 8 ref pieces + 1 query piece = 2 pieces per wavefront, at planes 1 and 2 of
+# the 4-plane stream (the middle of the block, as the 8-plane chunk's 1, 3, 5).
+HOLDER_CHUNK = (4, (1, 2))
+
+
+def holder_dma_planes(bb):
+    """The planes that carry the two pieces in a stream of bb of the chunk's 4 planes.  The rule of shorter_dma_planes
+    gives 3 -> (1, 2) and 2 -> (1, 1); measured on MI355X (profiles/NOTES_r15.md, same box, four alternating rounds of
+    the 10 000-genome self job, 77 of whose 80 blocks stream 2 planes) the 2-plane stream is 1.3 % faster with its
+    pieces at planes (0, 1) and 5 % faster with both at plane 0, and the 3-plane stream 1.4 % faster at plane 0 too:
+    a short block ends before a copy issued in its second half has landed.  The 4-plane stream keeps (1, 2): at
+    plane 0 it measured 0.5 % slower."""
+    return HOLDER_CHUNK[1] if bb == HOLDER_CHUNK[0] else (0, 0)
+
+
 def prio_levels(bb, v):
     """the four falling priorities of the 14-plane block, rescaled to a block of bb planes"""
     return [v[min(3, (b * BB // bb) // 4)] for b in range(bb)]
@@ -90,7 +105,7 @@ REF_PLANE_BYTES = 2048      # 256 samples x 8 B
 REF_HALF_BYTES = 1024
 
 
-def gen(QRY_PLANE_BYTES, TQ=4, dma_planes=None, half=False, a2=False, bb=BB):
+def gen(QRY_PLANE_BYTES, TQ=4, dma_planes=None, half=False, a2=False, bb=BB, pair_refs=(1, 3)):
     """TQ = 4: counters %[c0]..%[c15], one per pair (p = 4r + q).
     TQ = 8: counters %[c0]..%[c15], two pairs per counter (pair p = 8r + q -> counter p >> 1,
     16-bit half p & 1; a block adds at most 64 and a k at most 16 * 64 per pair ... callers
@@ -148,10 +163,11 @@ def gen(QRY_PLANE_BYTES, TQ=4, dma_planes=None, half=False, a2=False, bb=BB):
             if dma_planes and plane in dma_planes:
                 ts = [t for t, pp in enumerate(dma_planes) if pp == plane]
                 assert len(ts) <= 2
-                if r == 3:
+                if len(ts) == 2:      # (pair_refs: the refs whose compares the two pieces of one plane precede)
+                    if r in pair_refs:
+                        dma(ts[pair_refs.index(r)])
+                elif r == 3:
                     dma(ts[-1])
-                elif r == 1 and len(ts) == 2:
-                    dma(ts[0])
             for q in range(TQ):
                 for hi in (0, 1):
                     acc = hi_acc(r, q) if hi else lo_acc(r, q)
@@ -332,15 +348,25 @@ def main():
                     ["s_branch .Lppk_done_%=", ".Lppk_short_%=:"] + short +
                     ["s_branch .Lppk_done_%=", ".Lppk_six_%=:"] + six + [".Lppk_done_%=:"])
         # The holder pair (dist_kernel_v2_foldh): every value with at most H holders is folded, a sorted block spans at
-        # most 16 codes and planes 4 .. 7 of its 8-plane chunk are zero.  Three streams in the one statement, picked like
-        # the two-holder pair's: bit %[bk] of %[sh2] the 2-plane stream (at most 4 codes), else bit %[bk] of %[sh] the
-        # 3-plane one (at most 8), else 4 planes.  The chunk and its DMA pieces are the 8-plane ones, issued at the
-        # planes of the 8-plane stream rescaled to each length (4: 1, 2, 3; 3: 0, 1, 2; 2: 0, 1, 1).
-        four = gen(256, 4, dma_planes=list(shorter_dma_planes(pl, 4)), bb=4)
-        three = gen(256, 4, dma_planes=list(shorter_dma_planes(pl, 5)), bb=3)
-        two = gen(256, 4, dma_planes=list(shorter_dma_planes(pl, 6)), bb=2)
+        # most 16 codes and the copies store a 4-plane chunk (HOLDER_CHUNK).  Three streams in the one statement, picked
+        # like the two-holder pair's: bit %[bk] of %[sh2] the 2-plane stream (at most 4 codes), else bit %[bk] of %[sh]
+        # the 3-plane one (at most 8), else 4 planes.  A chunk is 8 ref pieces and one query piece: every wavefront
+        # issues one ref piece and a LAST piece that is the query piece for wavefront 0 and nothing for the others.  They
+        # sit at planes 1 and 2 of the 4-plane stream and both at plane 0 of the shorter ones (holder_dma_planes: the
+        # ref piece in front of ref 1's compares of plane 0, the last one in front of ref 3's).
+        # (Experiments: GEN_HOLDER2_DMA=a,b the planes of the 2-plane stream's pieces, GEN_HOLDER_DMA=a,b of all three
+        # streams', GEN_HOLDER_REFS=r,s the refs whose compares two pieces of one plane precede.)
+        pl, dplanes = HOLDER_CHUNK
+        two_planes = os.environ.get("GEN_HOLDER2_DMA")
+        two_planes = [int(x) for x in two_planes.split(",")] if two_planes else list(holder_dma_planes(2))
+        all_planes = os.environ.get("GEN_HOLDER_DMA")
+        all_planes = [int(x) for x in all_planes.split(",")] if all_planes else None
+        refs = tuple(int(x) for x in os.environ.get("GEN_HOLDER_REFS", "1,3").split(","))
+        four = gen(256, 4, dma_planes=all_planes or list(dplanes), bb=4, pair_refs=refs)
+        three = gen(256, 4, dma_planes=all_planes or list(holder_dma_planes(3)), bb=3, pair_refs=refs)
+        two = gen(256, 4, dma_planes=all_planes or two_planes, bb=2, pair_refs=refs)
         f.write("// %d-plane chunk, the holder pair: the 4-plane stream, the 3-plane one (flag in sh) or the 2-plane one (flag\n"
-                "// in sh2): planes 4 .. 7 are zero in every block and are neither read nor compared\n" % pl)
+                "// in sh2); one ref piece per wavefront and wavefront 0's query piece\n" % pl)
         write_macro(f, "PPK_BLOCK_DMA_SELH_ASM_Q32_P%d" % pl,
                     ["s_bitcmp1_b32 %[sh2], %[bk]", "s_cbranch_scc1 .Lppk_two_%=",
                      "s_bitcmp1_b32 %[sh], %[bk]", "s_cbranch_scc1 .Lppk_three_%="] + four +
