@@ -11,58 +11,10 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from poppunk_amd import _lib, engine, network, sparse_mst, synth  # noqa: E402
+from mst_shapes import kruskal, multigraph, scipy_labels  # noqa: E402,F401
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mst.npz")
 DEV = "cuda:0"
-
-
-def kruskal(edges, n, w):
-    """Kruskal with a stable sort on (w, min, max, index), -0.0 == +0.0: indices ascending, and scipy-style labels."""
-    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
-    w = np.asarray(w, dtype=np.float32).astype(np.float64) + 0.0
-    order = np.lexsort((np.arange(len(e)), e.max(axis=1), e.min(axis=1), w))
-    parent = np.arange(n)
-
-    def find(x):
-        r = x
-        while parent[r] != r:
-            r = parent[r]
-        while parent[x] != r:
-            parent[x], x = r, parent[x]
-        return r
-    keep = []
-    for k in order.tolist():
-        a, b = find(e[k, 0]), find(e[k, 1])
-        if a != b:
-            parent[max(a, b)] = min(a, b)
-            keep.append(k)
-    return np.array(sorted(keep), dtype=np.int64)
-
-
-def scipy_labels(edges, n):
-    from scipy.sparse import coo_matrix
-    from scipy.sparse.csgraph import connected_components
-    e = np.asarray(edges).reshape(-1, 2)
-    return connected_components(coo_matrix((np.ones(len(e)), (e[:, 0], e[:, 1])), shape=(n, n)), directed=False)
-
-
-def multigraph(rng, n, n_comp, n_edges, levels):
-    """Random multigraph: vertices split into n_comp groups plus isolated ones, edges inside groups in both
-    orientations with parallel copies, weights from a few levels (many ties, 0.0 and -0.0 among them)."""
-    groups = rng.integers(0, n_comp + 1, n)                  # group n_comp: isolated
-    members = [np.flatnonzero(groups == g) for g in range(n_comp)]
-    members = [m for m in members if m.size > 1]
-    e = []
-    for _ in range(n_edges):
-        m = members[int(rng.integers(0, len(members)))]
-        a, b = rng.choice(m, 2, replace=False)
-        e.append((a, b))
-    e = np.array(e, dtype=np.int64)
-    dup = rng.random(len(e)) < 0.2
-    e = np.concatenate([e, e[dup][:, ::-1], e[rng.random(len(e)) < 0.1]])
-    vals = np.concatenate([[0.0, -0.0], rng.random(levels - 2)]).astype(np.float32)
-    w = vals[rng.integers(0, levels, len(e))]
-    return e, w
 
 
 def run(e, w, n, labels=True):
