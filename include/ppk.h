@@ -125,6 +125,12 @@ int ppk_device_count(int *n);
  *     "silhouette_band" (0)    samples per band, whatever the cap says (0 = from the cap; tests)
  *     "silhouette_window" (0)  labels per LDS table window of the sums stage (0 = as many as the table holds, 4 096;
  *                          small values force the windowed path: tests)
+ *   reference picking (ppk_pick_refs_dev; exercised by its own GPU tests, not by the campaign)
+ *     "refs_scratch_mb" (4 096)  the most MiB the component-local bit matrices may take (the sum of |V|^2 / 8 bytes over
+ *                          the components of 3 or more vertices); over it the call fails with PPK_ERR_CAPACITY and names
+ *                          the largest component (a row-compressed adjacency is not built)
+ *     "refs_lds_bits" (65 536)  a component's bitsets live in LDS up to this many vertices, 64 .. 65 536, and in global
+ *                          scratch beyond (the same bits; small values force the global route: tests)
  *   contingency sums (ppk_contingency_sums_dev; exercised by its own GPU tests, not by the campaign)
  *     "rand_scratch_mb" (1 024)  what the per-level state and one batch of pairs' partial sums may take as allocated: a
  *                          batch holds as many pairs as keep both within four fifths of it; at least one
@@ -1140,6 +1146,38 @@ int ppk_cluster_extend_dev(const long long *d_i, const long long *d_j, size_t st
  * on device_id; blocking. */
 int ppk_cluster_extend(const long long *i, const long long *j, size_t n_edges, const int32_t *ref_label, size_t n_ref,
                        size_t n_qry, int device_id, int32_t *numbers, int32_t *n_clusters);
+
+/* ------------------------------------------------------------------------
+ * Reference genomes of a cluster network ([EXT]): extractReferences, PopPUNK/network.py:283-487, as a
+ * deterministic rule (graph-tool's clique order and list(frozenset)[0] are implementation-defined).  Edges
+ * d_i[k * stride], d_j[k * stride] (stride 1 or 2 as above) over vertices 0 .. n_vertices-1: every unordered pair once
+ * or several times, either orientation, no self-loop.  d_existing, d_merged uint8 [n_vertices] flags (non-zero = set),
+ * either may be NULL.
+ *  1. components of G;
+ *  2. fast == 0, per component V: |V| <= 2, its lowest vertex becomes a reference unconditionally; else R = V and,
+ *     while R is non-empty: s = min R, K = {s}, C = N(s) & R; while C is non-empty: v = min C, K += v, C &= N(v); if K
+ *     holds no reference (existing or picked), s becomes one; R -= K;
+ *  3. fast == 1 instead: a component without an existing reference gets its |V| / 10 + 1 lowest vertices, and a
+ *     component with m > 0 merged queries the m / 3 + 1 lowest of them;
+ *  4. repair: in a component whose references fall into more than one component of G[references], a breadth-first
+ *     search of G from r0, its lowest reference (a vertex's parent: its lowest neighbour in the level before); every
+ *     vertex on the parent path of every reference outside r0's component of G[references] becomes a reference.
+ * Outputs: d_is_ref uint8 [n_vertices] (0 / 1); d_ref_edges int64 [n_edges][2] (NULL to skip): the edges with both ends
+ * references, in stream order and orientation, renumbered by rank among the references (the first counts[1] rows are
+ * written); d_counts int64 [8]: references, reference edges, components, cliques removed, references from cliques
+ * (fast: from rule 3's first half), references from components of one or two vertices (fast: from merged queries),
+ * references added by the repair, components repaired -- counts 4 .. 6 count vertices NEWLY flagged, so
+ * counts[0] = existing + counts[4] + counts[5] + counts[6].  Integer arithmetic; the same edges in any order give the
+ * same bits.  PPK_ERR_ARG names the first offending edge; PPK_ERR_CAPACITY: option "refs_scratch_mb".  Synchronises
+ * the stream once. */
+int ppk_pick_refs_dev(const long long *d_i, const long long *d_j, size_t stride, size_t n_edges, size_t n_vertices,
+                      const uint8_t *d_existing, const uint8_t *d_merged, int fast, uint8_t *d_is_ref,
+                      long long *d_ref_edges, long long *d_counts, void *stream);
+/* Host arrays: i, j int64 [n_edges], existing / merged uint8 [n_vertices] or NULL -> is_ref uint8 [n_vertices],
+ * ref_edges int64 [n_edges][2] (nullable; counts[1] rows written), counts int64 [8], on device_id; blocking. */
+int ppk_pick_refs(const long long *i, const long long *j, size_t n_edges, size_t n_vertices, const uint8_t *existing,
+                  const uint8_t *merged, int fast, int device_id, uint8_t *is_ref, long long *ref_edges,
+                  long long *counts);
 
 /* ------------------------------------------------------------------------
  * Minimum spanning forests.  Edges d_i[k * stride], d_j[k * stride] (stride 1: separate arrays; 2:

@@ -126,6 +126,9 @@ SIGNATURES = {
     "ppk_query_links": (C.c_int, [_llp, _llp, _sz, _i32p, _sz, _sz, C.c_int, C.c_int, _i32p, _i32p, _i32p]),
     "ppk_cluster_extend_dev": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _vp]),
     "ppk_cluster_extend": (C.c_int, [_llp, _llp, _sz, _i32p, _sz, _sz, C.c_int, _i32p, _i32p]),
+    "ppk_pick_refs_dev": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "ppk_pick_refs": (C.c_int, [_llp, _llp, _sz, _sz, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int, C.c_int,
+                                C.POINTER(C.c_uint8), _llp, _llp]),
     "ppk_mst_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "ppk_mst": (C.c_int, [_llp, _llp, _f32p, _sz, _sz, C.c_int, _llp, _ullp, _i32p]),
     "ppk_edge_weights_dev": (C.c_int, [_vp, _sz, _vp, _vp, _sz, _sz, _sz, C.c_longlong, C.c_int, _vp, _vp]),

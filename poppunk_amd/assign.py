@@ -18,7 +18,8 @@ has those components.
 Device results and host naming are kept apart, as cluster_numbers / print_cluster_numbers are: the device gives number
 and link arrays (query_links, cluster_extend), the names come from network.name_clusters on lists.
 
-Not mirrored: --update-db, extractReferences and database joining; the lineage branch here (it
+Not mirrored: --update-db and database joining (extractReferences itself is
+network.extractReferences); the lineage branch here (it
 is lineages.extend_strain_lineages, DESIGN.md 3.22: every strain's LineageFit.extend in one pass); fetchNetwork's file loading (G arrives loaded); the betweenness QC table (qc_dict['betweenness'] raises
 NotImplementedError); `stable` without a distance matrix; printExternalClusters under `serial` / `stable` (upstream
 hands it a dict where it expects lists of names).  No _unword_clusters.csv is written (network.printClusters).

@@ -85,6 +85,8 @@ const OptionEntry kOptions[] = {
     {"sketch_batch", "PPK_SKETCH_BATCH", &PpkConfig::sketch_batch},
     {"sketch_count_bits", "PPK_SKETCH_COUNT_BITS", &PpkConfig::sketch_count_bits},
     {"sketch_exact_rounds", "PPK_SKETCH_EXACT_ROUNDS", &PpkConfig::sketch_exact_rounds},
+    {"refs_scratch_mb", "PPK_REFS_SCRATCH_MB", &PpkConfig::refs_scratch_mb},
+    {"refs_lds_bits", "PPK_REFS_LDS_BITS", &PpkConfig::refs_lds_bits},
     {"knn_list", "PPK_KNN_LIST", &PpkConfig::knn_list},
     {"knn_warm", "PPK_KNN_WARM", &PpkConfig::knn_warm},
     {"knn_cut", "PPK_KNN_CUT", &PpkConfig::knn_cut},

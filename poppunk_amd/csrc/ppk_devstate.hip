@@ -100,7 +100,7 @@ PpkPerDevice<DevState> g_dev;
 struct CallCtx {
   int dev = -1;
   hipStream_t s = nullptr;
-  unsigned touched = 0;
+  unsigned long long touched = 0;     // one bit per scratch slot
 };
 thread_local CallCtx tl_call;
 thread_local uint64_t tl_lut_pending_key = 0;
@@ -130,7 +130,7 @@ int ppk_scratch_get(int dev, int slot, size_t bytes, void **out) {
     // the slot bitmap of the wide-k kernel likewise
     if (slot == SLOT_WIDE && hipMemset(s.buf.p, 0, 4096) != hipSuccess) return ppk_fail(PPK_ERR_HIP, "hipMemset(scratch) failed");
   }
-  tl_call.touched |= 1u << slot;
+  tl_call.touched |= 1ull << slot;
   *out = s.buf.p;
   return PPK_OK;
 }
@@ -190,7 +190,7 @@ PpkCall::PpkCall(int dev, hipStream_t s) : dev_(dev), prev_dev_(tl_call.dev), pr
 
 PpkCall::~PpkCall() {
   for (int k = 0; k < SLOT_COUNT; ++k) {
-    if (!(tl_call.touched & (1u << k))) continue;
+    if (!(tl_call.touched & (1ull << k))) continue;
     Scratch &sc = g_dev.at(dev_).slot[k];
     if (ppk_event_get(&sc.ev) != hipSuccess) sc.ev = nullptr;
     sc.recorded = sc.ev && hipEventRecord(sc.ev, tl_call.s) == hipSuccess;
@@ -198,10 +198,10 @@ PpkCall::~PpkCall() {
   }
   // an enclosing scope on the same device (a host wrapper calling a device entry point) has
   // touched what its callee touched
-  const unsigned mine = tl_call.touched;
+  const unsigned long long mine = tl_call.touched;
   tl_call.dev = prev_dev_;
   tl_call.s = prev_s_;
-  tl_call.touched = prev_touched_ | (prev_dev_ == dev_ ? mine : 0u);
+  tl_call.touched = prev_touched_ | (prev_dev_ == dev_ ? mine : 0ull);
   g_dev.at(dev_).mu.unlock();
 }
 

@@ -194,6 +194,8 @@ struct PpkConfig {
   std::atomic<long long> sketch_batch{0};       // PPK_SKETCH_BATCH: samples per batch whatever the cap says (0 = from the cap; tests; same bits)
   std::atomic<long long> sketch_count_bits{0};  // PPK_SKETCH_COUNT_BITS: the bits B of a row of ppk_sketch_reads' count table, 4 .. 26 (0 = ppk_sketch_count_bits of the sample's code count; part of the rule: another B admits other k-mers on the table route; tests)
   std::atomic<long long> sketch_exact_rounds{64}; // PPK_SKETCH_EXACT_ROUNDS: the most select passes of ppk_sketch_reads' exact route over one group of samples before it gives up with an error (same bits)
+  std::atomic<long long> refs_scratch_mb{4096}; // PPK_REFS_SCRATCH_MB: the most MiB ppk_pick_refs' component-local bit matrices may take (sum of |V|^2 / 8 bytes); over it the call fails and names the largest component
+  std::atomic<long long> refs_lds_bits{65536};  // PPK_REFS_LDS_BITS: ppk_pick_refs keeps a component's bitsets in LDS up to this many vertices, 64 .. 65536; beyond it in global scratch (same bits; tests)
   std::atomic<long long> knn_list{0};           // PPK_KNN_LIST: entries of the neighbour-candidate list (0 = sized from n and knn)
   std::atomic<long long> host_parts_rows{16 << 20};   // PPK_HOST_PARTS_ROWS: ... from this many rows up
   std::atomic<long long> host_parts{2};         // PPK_HOST_PARTS: worker threads of a one-device host query (>= 16 Mi rows)
@@ -481,7 +483,9 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_RAND_SUMS = 28,                    // ... and one batch of pairs' partial sums (sized after the levels have been read: growing a slot moves it)
        SLOT_LINEAGE = 29,                      // the strain lineages' first-offender words, id owners, segment and route tables, one band's key buffers and temp storage; the ranks' counts and offsets
        SLOT_SKETCH = 30,                       // the sketcher's control words, piece table and one group of samples' per-bin minima (read samples: floors, winner counts and count tables too)
-       SLOT_COUNT = 31 };
+       SLOT_REFS = 31,                         // the reference pick's control words, union-find parents, component layout, BFS parents, ranks and temp storage
+       SLOT_REFS_BITS = 32,                    // ... and the component-local bit matrices with the large components' bitsets (sized after the layout has been read: growing a slot moves it)
+       SLOT_COUNT = 33 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 // The fit tables in SLOT_LUT.  ppk_lut_ready: whether the tables of `key` (k list, random table, sketch size, options)
 // already stand at `d_lut`; if not, none count as valid until the calling thread's launcher has enqueued lut_kernel
@@ -501,7 +505,7 @@ class PpkCall {
  private:
   int dev_, prev_dev_;
   hipStream_t prev_s_;
-  unsigned prev_touched_;
+  unsigned long long prev_touched_;
 };
 
 // ---- host-side frame of every module but the distance queries and sweeps (ppk_host.hip, ppk_iterate.hip: their

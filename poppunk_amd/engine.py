@@ -953,6 +953,81 @@ def cluster_extend_dev(edges_t, ref_label_t, n_qry):
     return numbers[:n_ref + n_qry], int(count.item())
 
 
+REFS_COUNT_NAMES = ("references", "reference_edges", "components", "cliques_removed", "from_cliques", "from_small",
+                    "added_by_repair", "components_repaired")
+
+
+def pick_references_dev(edges_t, n, existing=None, merged=None, fast=False):
+    """extractReferences' choice of reference genomes as the deterministic rule of DESIGN.md 3.25
+    (ppk_pick_refs_dev): clique pruning per component (fast: fastPrune's rank test), then the repair that joins the
+    references of a component.  edges_t: a contiguous int64 [m, 2] CUDA tensor or an (i_t, j_t) pair, read in place;
+    existing, merged: uint8 / bool CUDA tensors of n flags, or None.  Returns (is_ref uint8 [n] CUDA, ref_edges int64
+    [k, 2] CUDA: the edges among references in stream order, renumbered by rank, counts: a dict of REFS_COUNT_NAMES)."""
+    torch = _torch()
+    if isinstance(edges_t, (tuple, list)):
+        i_t, j_t = edges_t
+    else:
+        if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
+                and edges_t.is_contiguous()):
+            raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
+        i_t, j_t = edges_t[:, 0], edges_t[:, 1]
+    m, stride = _edge_stream(i_t, j_t, None)
+    dev = i_t.device
+    n = int(n)
+    if n < 0 or n >= 1 << 31:
+        raise RuntimeError("ppk_pick_refs: n_vertices must be < 2^31")
+    flags = []
+    for name, f in (("existing", existing), ("merged", merged)):
+        if f is not None:
+            if not (f.is_cuda and f.device == dev and f.dim() == 1 and f.shape[0] == n
+                    and f.dtype in (torch.uint8, torch.bool)):
+                raise TypeError("%s must be a uint8 or bool CUDA tensor of n flags on the edges' device" % name)
+            f = f.contiguous().view(torch.uint8)
+        flags.append(f)
+    with torch.cuda.device(dev):
+        is_ref = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        ref_edges = torch.empty((max(m, 1), 2), dtype=torch.int64, device=dev)
+        counts = torch.empty(8, dtype=torch.int64, device=dev)
+        rc = _lib.lib().ppk_pick_refs_dev(
+            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride, m, n,
+            C.c_void_p(flags[0].data_ptr()) if flags[0] is not None else None,
+            C.c_void_p(flags[1].data_ptr()) if flags[1] is not None else None, 1 if fast else 0,
+            C.c_void_p(is_ref.data_ptr()), C.c_void_p(ref_edges.data_ptr()), C.c_void_p(counts.data_ptr()),
+            _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_pick_refs_dev")
+    c = dict(zip(REFS_COUNT_NAMES, counts.cpu().tolist()))
+    return is_ref[:n], ref_edges[:c["reference_edges"]], c
+
+
+def pick_references(edges, n, existing=None, merged=None, fast=False, device=0):
+    """pick_references_dev on host arrays (ppk_pick_refs): edges int64 [m, 2], existing / merged n flags or None ->
+    (is_ref uint8 [n], ref_edges int64 [k, 2], counts dict)."""
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.int64).reshape(-1, 2))
+    i, j = np.ascontiguousarray(e[:, 0]), np.ascontiguousarray(e[:, 1])
+    n, m = int(n), e.shape[0]
+    if n < 0 or n >= 1 << 31:
+        raise RuntimeError("ppk_pick_refs: n_vertices must be < 2^31")
+    flags = []
+    for name, f in (("existing", existing), ("merged", merged)):
+        if f is not None:
+            f = np.ascontiguousarray(np.asarray(f) != 0, dtype=np.uint8).ravel()
+            if f.size != n:
+                raise ValueError("%s must hold n flags" % name)
+        flags.append(f)
+    is_ref = np.zeros(max(n, 1), dtype=np.uint8)
+    ref_edges = np.zeros((max(m, 1), 2), dtype=np.int64)
+    counts = np.zeros(8, dtype=np.int64)
+    llp, bp = C.POINTER(C.c_longlong), C.POINTER(C.c_uint8)
+    rc = _lib.lib().ppk_pick_refs(i.ctypes.data_as(llp), j.ctypes.data_as(llp), m, n,
+                                  flags[0].ctypes.data_as(bp) if flags[0] is not None else None,
+                                  flags[1].ctypes.data_as(bp) if flags[1] is not None else None, 1 if fast else 0,
+                                  int(device), is_ref.ctypes.data_as(bp), ref_edges.ctypes.data_as(llp),
+                                  counts.ctypes.data_as(llp))
+    _lib.check(rc, "ppk_pick_refs")
+    c = dict(zip(REFS_COUNT_NAMES, counts.tolist()))
+    return is_ref[:n], ref_edges[:c["reference_edges"]], c
+
+
 def nearest_reference_dev(dist_t, n_qry, n_ref, dist_col=0):
     """get_kNN_distances(qrDistMat[:, dist_col].reshape(n_qry, n_ref), kNN=1) as assign_query_hdf5's `stable` branch
     calls it (PopPUNK/assign.py:678-684), on the resident float32 [n_qry * n_ref, 2] matrix, read in place

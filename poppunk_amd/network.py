@@ -29,8 +29,12 @@ engine.cluster_extend_dev), which answer per query what the loaded network matte
 Minimum spanning trees: generate_minimum_spanning_tree and generate_network_from_distances
 (PopPUNK/network.py:1721-1831, 2075-2151) take and return G as (edges, n_vertices, weights); the forest comes from
 ppk_mst / ppk_mst_dev and the seed linking (seed_links) runs on the host.
+
+Reference genomes: extractReferences and writeReferences (PopPUNK/network.py:283-509) on G = (edges,
+n_vertices); the pick is the deterministic rule of ppk_pick_refs / ppk_pick_refs_dev, not graph-tool's clique order.
 """
 import ctypes as C
+import os
 import sys
 
 import numpy as np
@@ -679,3 +683,61 @@ def generate_network_from_distances(mode, model, core_distMat=None, acc_distMat=
     w = engine.edge_weights_dev(dist_t, edges, distance_type)
     n = len(combined_seq) if combined_seq is not None else engine._samples_of(dist_t.shape[0])
     return edges, n, w
+
+
+# ---- reference genomes (PopPUNK/network.py:283-509) ------------------------------------------------
+
+def _pick_references(edges, n, existing, merged, fast):
+    """the engine call of extractReferences: (is_ref, ref_edges, counts), on the device of a CUDA edge tensor"""
+    from . import engine
+    if _is_cuda(edges):
+        import torch
+        up = [None if f is None else torch.as_tensor(f, device=edges.device) for f in (existing, merged)]
+        return engine.pick_references_dev(edges, n, up[0], up[1], fast)
+    return engine.pick_references(edges, n, existing, merged, fast)
+
+
+def _name_flags(names, dbOrder, what):
+    """uint8 [len(dbOrder)]: 1 where the name is listed; an unknown name is a KeyError, as upstream's index_lookup"""
+    index_lookup = {v: k for k, v in enumerate(dbOrder)}
+    flags = np.zeros(len(dbOrder), dtype=np.uint8)
+    for r in frozenset(names):
+        if r not in index_lookup:
+            raise KeyError("%s %r is not in dbOrder" % (what, r))
+        flags[index_lookup[r]] = 1
+    return flags
+
+
+def extractReferences(G, dbOrder, outPrefix, merged_queries=list(), outSuffix='', existingRefs=None, threads=1,
+                      use_gpu=False, fast_mode=False):
+    """PopPUNK/network.py:283-487 with the reference's argument order, stderr lines and return order
+    (reference_indices, reference_names, refFileName, G_ref), by the deterministic rule of DESIGN.md 3.25
+    (ppk_pick_refs / ppk_pick_refs_dev) in place of graph-tool's clique enumeration: which genomes are picked differs
+    from upstream, what the pick guarantees does not.
+
+    G is the (edges, n_vertices) pair of this module (a CUDA edge tensor is read in place) and G_ref such a pair over
+    the references, vertex k being the k-th reference in dbOrder.  reference_indices is a SORTED int64 array where the
+    reference returns a set.  `threads` and `use_gpu` are accepted and ignored; the cugraph Leiden branch is not
+    mirrored."""
+    edges, n = G[0], int(G[1])
+    if n != len(dbOrder):
+        raise ValueError("one name in dbOrder per vertex of G")
+    existing = None if existingRefs is None else _name_flags(existingRefs, dbOrder, "existing reference")
+    merged = _name_flags(merged_queries, dbOrder, "merged query") if len(merged_queries) > 0 else None
+    sys.stderr.write("Running quick reference picking\n" if fast_mode else "Running clique finding\n")
+    is_ref, ref_edges, counts = _pick_references(edges, n, existing, merged, bool(fast_mode))
+    sys.stderr.write("Reconstructing clusters with shortest paths\n")
+    flags = is_ref.cpu().numpy() if hasattr(is_ref, "cpu") else np.asarray(is_ref)
+    reference_indices = np.flatnonzero(flags).astype(np.int64)
+    reference_names = [dbOrder[int(x)] for x in reference_indices]
+    refFileName = writeReferences(reference_names, outPrefix, outSuffix=outSuffix)
+    return reference_indices, reference_names, refFileName, (ref_edges, len(reference_names))
+
+
+def writeReferences(refList, outPrefix, outSuffix=""):
+    """PopPUNK/network.py:489-509: the names, one a line, to <outPrefix>/<basename(outPrefix)><outSuffix>.refs; returns
+    the file's name."""
+    name = "%s/%s%s.refs" % (outPrefix, os.path.basename(outPrefix), outSuffix)
+    with open(name, "w") as f:
+        f.write("".join(ref + "\n" for ref in refList))
+    return name
