@@ -9,6 +9,8 @@
                                                         PopPUNK/assign.py:592-660, network.py:1315-1442, 1478-1663
     -> engine.query_links_dev on the same edges: how many old clusters every query touches (the graph QC of
        qc.qcQueryAssignments, and what `--serial` names a query from)
+    -> network.vertex_betweenness on the network after assignment: `poppunk_assign --betweenness`'s table
+                                                        PopPUNK/assign.py:646-651
 
     python examples/assign_queries.py [n_references] [n_queries] [workdir]          # needs an MI355X
 """
@@ -60,6 +62,12 @@ def main():
     degree, n_links, links = engine.query_links_dev(edges, refnet.labels_on(edges.device), n_qry, 4)
     print("links: %d queries without a reference within the boundary, %d touching more than one old cluster (at most %d)"
           % (int((degree == 0).sum()), int((n_links > 1).sum()), int(n_links.max())))
+
+    # poppunk_assign --betweenness: every query's betweenness in the network after assignment (the references' edges
+    # plus the query-reference edges), highest first; the first lines of the table
+    whole = (network._cat([edges, ref_edges]), n_ref + n_qry)
+    values = network.vertex_betweenness(whole)[n_ref:]
+    print("".join(line + "\n" for line in assign.query_betweenness_table(qNames, values).split("\n")[:6]), end="")
     ref_db.close()
     qry_db.close()
 

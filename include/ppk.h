@@ -848,6 +848,38 @@ int ppk_network_summary(const long long *i, const long long *j, const long long 
                         double *bt, long long *scored, double *values);
 
 /* ------------------------------------------------------------------------
+ * Network summary with betweenness from sampled sources: ppk_network_summary_dev's edge stream,
+ * arguments, validation, limits and error messages (with this call's name in front), its d_stats bit for bit, and its
+ * d_bt / d_scored / d_values computed from at most bt_sources (k >= 1) sources per component.  Per scored component
+ * of n_c vertices:
+ *  - n_c <= k: every vertex is a source; the values are ppk_network_summary_dev's bit for bit.
+ *  - n_c > k: [EXT] the k vertices of smallest (h, v), v the global vertex id and h the high 32 bits of
+ *    fmix64(seed + (v + 1) * 0x9E3779B97F4A7C15), fmix64 = splitmix64's finaliser.  The rule is this project's own
+ *    (cugraph draws from its own generator); it depends on (seed, ids, component membership) alone: any edge order
+ *    and any call give the same sample, and a merged component's sample is a subset of the union of its parts'.
+ *    BC(v) = (sum over the sampled s of delta_s(v)) * n_c / (k * ((n_c - 1)(n_c - 2))), evaluated in double as
+ *    (S * n_c) / (k * ((n_c - 1) * (n_c - 2))): networkx 3.4.2's _rescale for betweenness_centrality(G, k=k).
+ * flags: 0, or PPK_BT_WHOLE_GRAPH: d_values becomes every vertex's betweenness in the whole graph G_{values_at},
+ * networkx's betweenness_centrality(G, normalized=True) on a disconnected graph: every component of at least 3
+ * vertices is scored and the divisor is (n - 1)(n - 2), n = n_vertices (sampled: S * n_c / (k * ((n - 1)(n - 2))));
+ * all 0 when n <= 2.  d_bt and d_scored stay the per-component summary.  That graph-tool normalises the same way is
+ * UNVERIFIED.  No float atomics: the same input, in any edge order, gives the same bits on every call.
+ * PPK_ERR_ARG for bt_sources == 0 and for unknown flag bits.
+ * (Replaces the device branch of networkSummary, betweenness_centrality(k=betweenness_sample, normalized=True) for
+ * components of at least betweenness_sample vertices, PopPUNK/network.py:1272-1287; with PPK_BT_WHOLE_GRAPH,
+ * vertex_betweenness(G, norm=True), network.py:1310-1313, as poppunk_assign --betweenness calls it, assign.py:646-651.) */
+#define PPK_BT_WHOLE_GRAPH 1
+int ppk_network_summary_sampled_dev(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off,
+                                    size_t n_edges, size_t n_vertices, size_t n_off, long long values_at,
+                                    long long *d_stats, double *d_bt, long long *d_scored, double *d_values,
+                                    size_t bt_sources, unsigned long long seed, int flags, void *stream);
+/* Host arrays, as ppk_network_summary; blocking. */
+int ppk_network_summary_sampled(const long long *i, const long long *j, const long long *off, size_t n_edges,
+                                size_t n_vertices, size_t n_off, int device_id, long long values_at, long long *stats,
+                                double *bt, long long *scored, double *values, size_t bt_sources,
+                                unsigned long long seed, int flags);
+
+/* ------------------------------------------------------------------------
  * Cluster numbers: ppk_network_sweep_dev's edge stream, validation, limits and error messages (the
  * entry point's own name in front), and for every G_t:
  *  - d_clusters int32 [n_off][n_vertices]: d_clusters[t][v] = printClusters' number, 1-based, of vertex v in G_t.

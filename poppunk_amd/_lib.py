@@ -15,6 +15,7 @@ REFINE_NOT_NESTED = 6      # ppk_refine_local_create_dev: the two lines do not f
 FLAG_RANDOM_CORRECT, FLAG_JACCARD, FLAG_COUNTS = 1, 2, 4
 SKETCH_STRAND_PRESERVED = 1      # flag of ppk_sketch / ppk_sketch_dev / ppk_sketch_reads / ppk_sketch_reads_dev
 SKETCH_EXACT = 2                 # flag of ppk_sketch_reads / ppk_sketch_reads_dev: the exact route
+BT_WHOLE_GRAPH = 1               # flag of ppk_network_summary_sampled / _dev: values normalised by the whole graph
 
 # every symbol include/ppk.h declares: name -> (restype, argtypes)
 _u64p, _f32p, _i32p, _u16p = (C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_int32),
@@ -90,6 +91,10 @@ SIGNATURES = {
     "ppk_network_sweep": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, C.c_longlong, _llp, _i32p]),
     "ppk_network_summary_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, C.c_longlong, _vp, _vp, _vp, _vp, _vp]),
     "ppk_network_summary": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, C.c_longlong, _llp, _f64p, _llp, _f64p]),
+    "ppk_network_summary_sampled_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, C.c_longlong, _vp, _vp, _vp, _vp,
+                                                  _sz, C.c_ulonglong, C.c_int, _vp]),
+    "ppk_network_summary_sampled": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, C.c_longlong, _llp, _f64p, _llp,
+                                              _f64p, _sz, C.c_ulonglong, C.c_int]),
     "ppk_cluster_sweep_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp, _vp]),
     "ppk_cluster_sweep": (C.c_int, [_llp, _llp, _llp, _sz, _sz, _sz, C.c_int, _i32p, _i32p]),
     "ppk_cluster_pair_sums_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _sz, C.c_int, _vp, _vp, _vp]),

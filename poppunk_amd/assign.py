@@ -20,12 +20,13 @@ and link arrays (query_links, cluster_extend), the names come from network.name_
 
 Not mirrored: --update-db and database joining (extractReferences itself is
 network.extractReferences); the lineage branch here (it
-is lineages.extend_strain_lineages, DESIGN.md 3.22: every strain's LineageFit.extend in one pass); fetchNetwork's file loading (G arrives loaded); the betweenness QC table (qc_dict['betweenness'] raises
-NotImplementedError); `stable` without a distance matrix; printExternalClusters under `serial` / `stable` (upstream
+is lineages.extend_strain_lineages, DESIGN.md 3.22: every strain's LineageFit.extend in one pass); fetchNetwork's file
+loading (G arrives loaded); `stable` without a distance matrix; printExternalClusters under `serial` / `stable` (upstream
 hands it a dict where it expects lists of names).  No _unword_clusters.csv is written (network.printClusters).
 """
 import os
 import sys
+from operator import itemgetter
 
 import numpy as np
 
@@ -191,6 +192,16 @@ def _prune(rNames, qNames, failed, qrDistMat, queryAssignments):
     return [qNames[q] for q in keep], rows(qrDistMat), rows(queryAssignments)
 
 
+def query_betweenness_table(qNames, betweenness):
+    """The text of poppunk_assign --betweenness (PopPUNK/assign.py:648-651): the header, then one line per query, by
+    descending betweenness, equal values in the queries' order (Python's stable sort, as the reference's)."""
+    query_betweenness = {query: b for query, b in zip(qNames, betweenness)}
+    lines = ["query\tbetweenness"]
+    for query, q_betweenness in sorted(query_betweenness.items(), key=itemgetter(1), reverse=True):
+        lines.append(f"{query}\t{q_betweenness}")
+    return "\n".join(lines) + "\n"
+
+
 def assign_query_clusters(dbFuncs, refnet, qNames, qrDistMat, model, output, kmers=None, fit_type='default',
                           qc_dict=None, graph_weights=False, serial=False, stable=None, update_db=False,
                           write_references=False, external_clustering=None, strand_preserved=False, threads=1,
@@ -209,7 +220,10 @@ def assign_query_clusters(dbFuncs, refnet, qNames, qrDistMat, model, output, kme
                          gather of the assignment (stable_names); matrix route only
 
     qc_dict {'run_qc', 'max_merge', 'betweenness'}: with run_qc and max_merge > 1, qcQueryAssignments and the
-    reference's report, exit when every query fails, and pruning; 'betweenness' raises NotImplementedError.
+    reference's report, exit when every query fails, and pruning; with run_qc and 'betweenness' (joint mode), the
+    table of every query's betweenness in the whole network after assignment goes to stdout (assign.py:646-651,
+    network.vertex_betweenness; this is the one step that reads the loaded network's edges); 'betweenness_sample'
+    (absent: every source) and 'betweenness_seed' are this project's additions.
     graph_weights needs a loaded network with weights (the reference's message and exit otherwise).
     update_db only widens printRef, as upstream's `write_references or update_db`; nothing is updated."""
     rNames, qNames = refnet.rNames, list(qNames)
@@ -247,8 +261,6 @@ def assign_query_clusters(dbFuncs, refnet, qNames, qrDistMat, model, output, kme
               "genomeNetwork": None}
     n_ref, n_qry = len(rNames), len(qNames)
     if not serial:
-        if qc_dict['run_qc'] and qc_dict.get('betweenness'):
-            raise NotImplementedError("assign_query_clusters: the betweenness QC table is not mirrored")
         # the new edges alone: addQueryToNetwork on a network of the loaded one's vertices and no edges
         loaded = refnet.G
         none = (np.zeros((0, 2), dtype=np.int64), n_ref) + \
@@ -258,6 +270,12 @@ def assign_query_clusters(dbFuncs, refnet, qNames, qrDistMat, model, output, kme
                                                    queryQuery=update_db and fit_type == 'default',
                                                    strand_preserved=strand_preserved, weights=weights,
                                                    threads=threads, use_gpu=gpu_graph)
+        if qc_dict['run_qc'] and qc_dict.get('betweenness'):
+            # assign.py:646-651: every query's betweenness in the whole network after assignment
+            whole = (network._cat([new[0], loaded[0]]), n_ref + n_qry)
+            values = network.vertex_betweenness(whole, betweenness_sample=qc_dict.get('betweenness_sample'),
+                                                seed=qc_dict.get('betweenness_seed', 0))
+            sys.stdout.write(query_betweenness_table(qNames, values[n_ref:n_ref + n_qry]))
         numbers = extend_numbers(new[0], refnet, n_qry)
         isolateClustering, merged_queries = network.print_cluster_numbers(
             numbers, rNames + qNames, output_fn, old_cluster_file, external_clustering,

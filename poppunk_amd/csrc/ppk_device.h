@@ -101,6 +101,18 @@ __device__ __forceinline__ int uf_find_ro(const int *parent, int x) {
   return x;
 }
 
+// ---- splitmix64's finaliser (ppk_embed.hip's generator, ppk_network.hip's source sample) ----
+__host__ __device__ __forceinline__ unsigned long long ppk_fmix64(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// [EXT] The sampled betweenness's key of global vertex v under `seed`: a component's sample is its k
+// vertices of smallest (key, v).  The rule is this project's own: cugraph's draw is its generator's and is not pinned.
+__host__ __device__ __forceinline__ unsigned ppk_bt_sample_key(unsigned long long seed, unsigned long long v) {
+  return (unsigned)(ppk_fmix64(seed + (v + 1) * 0x9E3779B97F4A7C15ull) >> 32);
+}
+
 // ---- order-preserving float -> uint32 keys (unsigned compare == operator< on non-NaN floats) ----
 // The raw transform of the bit pattern: -0.0 sorts strictly BEFORE +0.0 (ppk_iterate.hip's sort key).
 __host__ __device__ __forceinline__ unsigned ord_raw(float f) {

@@ -38,13 +38,10 @@ constexpr unsigned long long kGolden = 0x9E3779B97F4A7C15ull;
 constexpr unsigned long long kInitKey = 0xD1B54A32D192ED03ull;
 
 // ---- the generator (restated in tests/test_embed_host.py) ---------------------------------------------------------
-// splitmix64's finaliser.  Iteration t's key is fmix(seed + (t + 1) * G); draw d of worker w in that iteration is
-// fmix(key + ((w << 8 | d) + 1) * G).  Initial positions use the key fmix(seed ^ kInitKey) and the counter 2v + c.
-__host__ __device__ __forceinline__ unsigned long long fmix(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// fmix = splitmix64's finaliser (ppk_device.h).  Iteration t's key is fmix(seed + (t + 1) * G); draw d of worker w in
+// that iteration is fmix(key + ((w << 8 | d) + 1) * G).  Initial positions use the key fmix(seed ^ kInitKey) and the
+// counter 2v + c.
+__host__ __device__ __forceinline__ unsigned long long fmix(unsigned long long z) { return ppk_fmix64(z); }
 __host__ __device__ __forceinline__ unsigned long long draw(unsigned long long key, unsigned long long ctr) {
   return fmix(key + (ctr + 1) * kGolden);
 }

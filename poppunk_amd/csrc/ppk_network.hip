@@ -21,10 +21,14 @@
 //    then one small kernel prefix-sums the per-offset increments into the [n_off][4] result.
 //  - ppk_network_summary_dev : the same counts plus networkSummary's betweenness (network.py:1286-1307) for every
 //    G_t: the stages above, then the betweenness stage below.
+//  - ppk_network_summary_sampled_dev : the same with at most bt_sources sources per component (the reference's
+//    betweenness_sample, network.py:1272-1287), and optionally every vertex's value in the whole graph
+//    (vertex_betweenness, network.py:1310-1313): the same stages plus bt_sources.
 //  - ppk_cluster_sweep_dev : printClusters' cluster numbers (PopPUNK/network.py:1538-1545) of every vertex in every
 //    G_t, from the same validation, buckets and union launches (the section before the entry points).
 //  - ppk_cluster_extend_dev : the same numbers for (a loaded network + new edges), the loaded network given by its
 //    component labels alone: the cluster sweep with a seeded forest.
+#include <climits>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -340,16 +344,24 @@ int bad_edge_message(const std::string &who, const long long *d_i, const long lo
 // and union-find, and its components of more than 3 vertices are scored with exact Brandes:
 //   bt_relabel  roots and sizes from the union-find at t; those components ordered by (size desc, root), their
 //               vertices given local ids ordered by (component, id); a local CSR of G_t with rows sorted by neighbour
+//   bt_sources  (sampled calls only) [EXT] every component of more than k vertices keeps k sources: its vertices of
+//               smallest (ppk_bt_sample_key(seed, global id), global id), found by one stable sort of (component, key)
+//               over the local ids; a scan of the picked flags gives each such component its list of sources in
+//               ascending local id.  Components of at most k vertices take no list: every vertex, the id range.
 //   bt_plan     one workgroup splits every component into work items of a fixed number of sources, sized from the
-//               component's work (sources x adjacency); the graph's ONE synchronisation reads the plan's header
+//               component's work (sources x (adjacency + n_c)); the graph's ONE synchronisation reads the plan's header
 //   bt_brandes  level-synchronous Brandes per source; a work item writes its partial sums, never adds into a shared one
 //   bt_reduce   per vertex the partials in item order, normalised; per component the maximum; the two means
+// Normalisation, S = the sum of the partials in item order, every factor converted to double first:
+//   all n_c sources               S / ((n_c - 1) * (n_c - 2))
+//   k < n_c sources               (S * n_c) / (k * ((n_c - 1) * (n_c - 2)))        (networkx 3.4.2's _rescale)
+//   whole graph (d_values only)   the same with (n - 1) * (n - 2), n = n_vertices, in place of the component's product
 constexpr int kBtItems = 1024;         // work items per graph the plan aims at (fixed: results do not depend on the GPU)
 constexpr int kBtSmallCap = 256;       // the small-component path's LDS holds components up to this size
 constexpr size_t kBtLdsBytes = 160 * 1024 - 64;   // dynamic LDS of the LDS-state path (static: a few scalars)
 constexpr unsigned long long kNone = ~0ull;
 enum { H_K, H_KBIG, H_KGLOB, H_ITEMS, H_ITEMS_GLOB, H_PARTIAL, H_SCORED, H_NC_GLOB, H_NC_LDS, H_WORK, H_ADJ,
-       H_LEN = 16 };
+       H_K4, H_LEN = 16 };
 
 size_t bt_state_bytes(size_t nc) { return 36 * nc + 8; }
 
@@ -361,11 +373,12 @@ __global__ void __launch_bounds__(kThreads) bt_sizes_kernel(const int *parent, s
   }
 }
 
-// one key per root of a component of more than 3 vertices: (n - size, root); every other vertex kNone
-__global__ void __launch_bounds__(kThreads) bt_root_keys_kernel(const int *root, const int *size, size_t n,
+// one key per root of a component of at least min_nc vertices (4; 3 for whole-graph values): (n - size, root); every
+// other vertex kNone
+__global__ void __launch_bounds__(kThreads) bt_root_keys_kernel(const int *root, const int *size, size_t n, int min_nc,
                                                                 unsigned long long *keys) {
   for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x)
-    keys[v] = (root[v] == (int)v && size[v] > 3) ? ((unsigned long long)(n - size[v]) << 32 | v) : kNone;
+    keys[v] = (root[v] == (int)v && size[v] >= min_nc) ? ((unsigned long long)(n - size[v]) << 32 | v) : kNone;
 }
 
 // component c (sorted position): its rank at its root, its size (0 past the last component)
@@ -384,10 +397,11 @@ __global__ void __launch_bounds__(kThreads) bt_comps_kernel(const unsigned long 
 }
 
 __global__ void __launch_bounds__(kThreads) bt_vertex_keys_kernel(const int *root, const int *size, const int *crank,
-                                                                  size_t n, unsigned long long *keys, int *local) {
+                                                                  size_t n, int min_nc, unsigned long long *keys,
+                                                                  int *local) {
   for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) {
     const int r = root[v];
-    keys[v] = size[r] > 3 ? ((unsigned long long)crank[r] << 32 | v) : kNone;
+    keys[v] = size[r] >= min_nc ? ((unsigned long long)crank[r] << 32 | v) : kNone;
     local[v] = -1;
   }
 }
@@ -458,45 +472,92 @@ __global__ void __launch_bounds__(kThreads) bt_starts_kernel(const int *csize, s
   if (threadIdx.x == kThreads - 1) cstart[n + 1] = (int)acc;
 }
 
+// ---- bt_sources ----
+// vkeys: the sorted (component, vertex) keys of bt_relabel, position = local id.  Sort key of local id p: (component,
+// sample key of its vertex) in a component of more than k vertices, (component, 0) in the others, so that every
+// component's segment stays at cstart[c]; the sort is stable and p ascends with the vertex id within a component, so
+// equal keys stay in id order.
+__global__ void __launch_bounds__(kThreads) bt_src_keys_kernel(const unsigned long long *vkeys, const int *csize,
+                                                               const long long *hdr, size_t n, int k,
+                                                               unsigned long long seed, unsigned long long *keys,
+                                                               int *ids, int *flag) {
+  const size_t ns = (size_t)hdr[H_SCORED];
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
+    unsigned long long key = kNone;
+    if (p < ns) {
+      const unsigned long long c = vkeys[p] >> 32, v = vkeys[p] & 0xffffffffu;
+      key = c << 32 | (csize[c] > k ? ppk_bt_sample_key(seed, v) : 0u);
+    }
+    keys[p] = key;
+    ids[p] = (int)p;
+    flag[p] = 0;
+  }
+}
+// position r of the sorted order has rank r - cstart[c] in its component: the first k of a sampled component are picked
+__global__ void __launch_bounds__(kThreads) bt_src_pick_kernel(const unsigned long long *sorted, const int *ids,
+                                                               const int *csize, const int *cstart,
+                                                               const long long *hdr, int k, int *flag) {
+  const size_t ns = (size_t)hdr[H_SCORED];
+  for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < ns; r += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(sorted[r] >> 32);
+    if (csize[c] > k && (long long)r - cstart[c] < k) flag[ids[r]] = 1;
+  }
+}
+// pos = the exclusive scan of flag: the picked vertices of component c are src[sbase[c] .. + k), component-relative,
+// in ascending local id
+__global__ void __launch_bounds__(kThreads) bt_src_list_kernel(const unsigned long long *vkeys, const int *flag,
+                                                               const int *pos, const int *cstart, const long long *hdr,
+                                                               int *src, int *sbase) {
+  const size_t ns = (size_t)hdr[H_SCORED];
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < ns; p += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(vkeys[p] >> 32), first = cstart[c];
+    if ((int)p == first) sbase[c] = pos[p];
+    if (flag[p]) src[pos[p]] = (int)p - first;
+  }
+}
+
 // the plan: components [0, K) sorted by size; [0, K_glob) global-state, [K_glob, K_big) LDS-state (both 256-thread
 // items of spi[c] sources), [K_big, K) one wave each.  ibase / pbase: each component's first item and first partial.
 __global__ void __launch_bounds__(kThreads) bt_plan_kernel(const int *csize, const int *cstart, const unsigned *rstart,
-                                                           size_t n, int small_max, int lds_max, int *spi, int *ibase,
-                                                           long long *pbase, long long *hdr) {
+                                                           size_t n, int small_max, int lds_max, int k_src, int *spi,
+                                                           int *ibase, long long *pbase, long long *hdr) {
   __shared__ long long s_part[kThreads], s_items[kThreads];
   __shared__ double s_work[kThreads];
-  __shared__ int s_k[kThreads], s_big[kThreads], s_glob[kThreads];
+  __shared__ int s_k[kThreads], s_big[kThreads], s_glob[kThreads], s_k4[kThreads];
   __shared__ long long s_adj[kThreads];
   const int tid = threadIdx.x;
-  int k = 0, kb = 0, kg = 0;
+  int k = 0, kb = 0, kg = 0, k4 = 0;
   long long adj_sum = 0;
   double work = 0;
   for (size_t c = tid; c < n; c += kThreads) {
     const int nc = csize[c];
     if (nc == 0) continue;
     ++k;
+    if (nc > 3) ++k4;
     const long long adj = (long long)rstart[cstart[c + 1]] - rstart[cstart[c]];
     adj_sum += adj;
     if (nc > small_max) {
       ++kb;
-      work += (double)nc * (double)(adj + nc);
+      work += (double)(nc < k_src ? nc : k_src) * (double)(adj + nc);
       if (nc > lds_max) ++kg;
     }
   }
   s_k[tid] = k;
   s_big[tid] = kb;
   s_glob[tid] = kg;
+  s_k4[tid] = k4;
   s_work[tid] = work;
   s_adj[tid] = adj_sum;
   __syncthreads();
   if (tid == 0) {
-    int K = 0, KB = 0, KG = 0;
+    int K = 0, KB = 0, KG = 0, K4 = 0;
     double W = 0;
     long long A = 0;
     for (int q = 0; q < kThreads; ++q) {
       K += s_k[q];
       KB += s_big[q];
       KG += s_glob[q];
+      K4 += s_k4[q];
       W += s_work[q];
       A += s_adj[q];
     }
@@ -507,7 +568,8 @@ __global__ void __launch_bounds__(kThreads) bt_plan_kernel(const int *csize, con
     hdr[H_K] = K;
     hdr[H_KBIG] = KB;
     hdr[H_KGLOB] = KG;
-    hdr[H_WORK] = (long long)W;    // sum of nc (adjacency + nc) over the 256-thread components (measurement)
+    hdr[H_K4] = K4;                // the components of more than 3 vertices: the summary's (a prefix: sorted by size)
+    hdr[H_WORK] = (long long)W;    // sum of sources (adjacency + nc) over the 256-thread components (measurement)
     hdr[H_ADJ] = A;
   }
   __syncthreads();
@@ -517,16 +579,16 @@ __global__ void __launch_bounds__(kThreads) bt_plan_kernel(const int *csize, con
   const int per = (K + kThreads - 1) / kThreads, c0 = tid * per, c1 = c0 + per < K ? c0 + per : K;
   long long items = 0, part = 0;
   for (int c = c0; c < c1; ++c) {
-    const int nc = csize[c];
-    int s = nc;
+    const int nc = csize[c], nsrc = nc < k_src ? nc : k_src;
+    int s = nsrc;
     if (c < KB) {
       const double cost = (double)((long long)rstart[cstart[c + 1]] - rstart[cstart[c]] + nc);
       const double want = ceil(target / cost);
-      s = want < (double)nc ? (int)want : nc;
+      s = want < (double)nsrc ? (int)want : nsrc;
       if (s < 1) s = 1;
     }
     spi[c] = s;
-    const int it = (nc + s - 1) / s;
+    const int it = (nsrc + s - 1) / s;
     items += it;
     part += (long long)it * nc;
   }
@@ -550,7 +612,7 @@ __global__ void __launch_bounds__(kThreads) bt_plan_kernel(const int *csize, con
   items = s_items[tid];
   part = s_part[tid];
   for (int c = c0; c < c1; ++c) {
-    const int nc = csize[c], it = (nc + spi[c] - 1) / spi[c];
+    const int nc = csize[c], it = ((nc < k_src ? nc : k_src) + spi[c] - 1) / spi[c];
     ibase[c] = (int)items;
     pbase[c] = part;
     items += it;
@@ -565,7 +627,8 @@ __global__ void __launch_bounds__(kThreads) bt_plan_kernel(const int *csize, con
   }
 }
 
-// Brandes for sources [s0, s1) of one component of nc vertices (comp-relative ids; the local CSR row of v is
+// Brandes for sources [s0, s1) of one component of nc vertices -- the ids themselves, or with a source list (a sampled
+// component) src[s0 .. s1) -- (comp-relative ids; the local CSR row of v is
 // rstart[base + v] ..., its neighbours nb[] - base).  SUB lanes share a vertex (64: a wave walks the row; 1: a lane).
 // State: lev / q (BFS order) / ls (level starts, nc + 2) int, sig (path counts), cof = (1 + delta) / sig and bc (this
 // item's sum over its sources) double.  Levels are pushed (discover), sigma and delta pulled in CSR order, so every
@@ -580,12 +643,13 @@ __device__ __forceinline__ double bt_sum(double x) {
 
 template <int SUB>
 __device__ __forceinline__ void bt_brandes(const unsigned *__restrict__ rstart, const int *__restrict__ nb, int base,
-                                           int nc, int s0, int s1, int *lev, int *q, int *ls, double *sig, double *cof,
-                                           double *bc, int *tail) {
+                                           int nc, int s0, int s1, const int *__restrict__ src, int *lev, int *q, int *ls,
+                                           double *sig, double *cof, double *bc, int *tail) {
   const int tid = threadIdx.x, nthr = blockDim.x, g = tid / SUB, l = tid % SUB, ng = nthr / SUB;
   const unsigned *rs = rstart + base;
   for (int v = tid; v < nc; v += nthr) bc[v] = 0.0;
-  for (int s = s0; s < s1; ++s) {
+  for (int si = s0; si < s1; ++si) {
+    const int s = src ? src[si] : si;
     for (int v = tid; v < nc; v += nthr) lev[v] = -1;
     __syncthreads();
     if (tid == 0) {
@@ -657,9 +721,9 @@ __device__ __forceinline__ int bt_comp_of(const int *first, int count, int x) { 
 template <bool IN_LDS>
 __global__ void __launch_bounds__(kThreads) bt_items_kernel(const unsigned *rstart, const int *nb, const int *csize,
                                                             const int *cstart, const int *spi, const int *ibase,
-                                                            const long long *pbase, int kbig, int i0, int i1,
-                                                            unsigned *next, char *slab, size_t slab_stride,
-                                                            double *partial) {
+                                                            const long long *pbase, const int *src, const int *sbase,
+                                                            int k_src, int kbig, int i0, int i1, unsigned *next,
+                                                            char *slab, size_t slab_stride, double *partial) {
   extern __shared__ double lds_state[];
   __shared__ int item, tail;
   char *mine = IN_LDS ? reinterpret_cast<char *>(lds_state) : slab + (size_t)blockIdx.x * slab_stride;
@@ -670,25 +734,27 @@ __global__ void __launch_bounds__(kThreads) bt_items_kernel(const unsigned *rsta
     const int k = item;
     if (k >= i1) break;
     const int c = bt_comp_of(ibase, kbig, k), nc = csize[c], base = cstart[c];
-    const int s0 = (k - ibase[c]) * spi[c], s1 = s0 + spi[c] < nc ? s0 + spi[c] : nc;
+    const int nsrc = nc < k_src ? nc : k_src;
+    const int s0 = (k - ibase[c]) * spi[c], s1 = s0 + spi[c] < nsrc ? s0 + spi[c] : nsrc;
     double *sig = reinterpret_cast<double *>(mine), *cof = sig + nc, *bc = cof + nc;
     int *lev = reinterpret_cast<int *>(bc + nc), *q = lev + nc, *ls = q + nc;
-    bt_brandes<64>(rstart, nb, base, nc, s0, s1, lev, q, ls, sig, cof, bc, &tail);
+    bt_brandes<64>(rstart, nb, base, nc, s0, s1, nc > k_src ? src + sbase[c] : nullptr, lev, q, ls, sig, cof, bc, &tail);
     __syncthreads();
     double *out = partial + pbase[c] + (long long)(k - ibase[c]) * nc;
     for (int v = threadIdx.x; v < nc; v += blockDim.x) out[v] = bc[v];
   }
 }
 
-// one wave per component of at most kBtSmallCap vertices, every source
+// one wave per component of at most kBtSmallCap vertices, every source (or the k_src of its list)
 __global__ void __launch_bounds__(64) bt_small_kernel(const unsigned *rstart, const int *nb, const int *csize,
-                                                      const int *cstart, const long long *pbase, int k0,
-                                                      double *partial) {
+                                                      const int *cstart, const long long *pbase, const int *src,
+                                                      const int *sbase, int k_src, int k0, double *partial) {
   __shared__ double sig[kBtSmallCap], cof[kBtSmallCap], bc[kBtSmallCap];
   __shared__ int lev[kBtSmallCap], q[kBtSmallCap], ls[kBtSmallCap + 2], tail;
   const int c = k0 + blockIdx.x, nc = csize[c];
   if (nc > kBtSmallCap) return;        // (the plan never sends one)
-  bt_brandes<1>(rstart, nb, cstart[c], nc, 0, nc, lev, q, ls, sig, cof, bc, &tail);
+  bt_brandes<1>(rstart, nb, cstart[c], nc, 0, nc < k_src ? nc : k_src, nc > k_src ? src + sbase[c] : nullptr, lev, q, ls,
+                sig, cof, bc, &tail);
   __syncthreads();
   double *out = partial + pbase[c];
   for (int v = threadIdx.x; v < nc; v += blockDim.x) out[v] = bc[v];
@@ -697,16 +763,27 @@ __global__ void __launch_bounds__(64) bt_small_kernel(const unsigned *rstart, co
 // per scored vertex: the sum of its component's partials in item order, over (nc - 1)(nc - 2).  A division, not a
 // product with the rounded reciprocal: a sum that is exact (a star's centre, (nc - 1)(nc - 2) itself) gives the
 // correctly rounded value, 1.0, where x * (1 / x) falls one ulp short for 50 of the sizes below 400 (nc = 301 is one).
+// A sampled component (nc > k_src): (sum * nc) / (k_src * ((nc - 1)(nc - 2))).  wval (whole-graph calls): the same two
+// forms with (n_all - 1)(n_all - 2) as the product, n_all = the graph's vertex count.
 __global__ void __launch_bounds__(kThreads) bt_reduce_kernel(const double *partial, const int *csize,
                                                              const int *cstart, const int *ibase,
-                                                             const long long *pbase, const long long *hdr, double *val) {
+                                                             const long long *pbase, const long long *hdr, int k_src,
+                                                             long long n_all, double *val, double *wval) {
   const int K = (int)hdr[H_K], ns = (int)hdr[H_SCORED];
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < ns; p += gridDim.x * blockDim.x) {
     const int c = bt_comp_of(cstart, K, p), nc = csize[c], items = ibase[c + 1] - ibase[c];
     const double *x = partial + pbase[c] + (p - cstart[c]);
     double acc = 0.0;
     for (int k = 0; k < items; ++k) acc += x[(long long)k * nc];
-    val[p] = acc / ((double)(nc - 1) * (double)(nc - 2));
+    const double own = (double)(nc - 1) * (double)(nc - 2), all = (double)(n_all - 1) * (double)(n_all - 2);
+    if (nc > k_src) {
+      const double num = acc * (double)nc;
+      val[p] = num / ((double)k_src * own);
+      if (wval) wval[p] = num / ((double)k_src * all);
+    } else {
+      val[p] = acc / own;
+      if (wval) wval[p] = acc / all;
+    }
   }
 }
 
@@ -714,7 +791,7 @@ __global__ void __launch_bounds__(kThreads) bt_reduce_kernel(const double *parti
 __global__ void __launch_bounds__(kThreads) bt_summary_kernel(const double *val, const int *csize, const int *cstart,
                                                               const long long *hdr, double *cmax, int t, double *bt,
                                                               long long *scored) {
-  const int K = (int)hdr[H_K];
+  const int K = (int)hdr[H_K4];
   for (int c = threadIdx.x; c < K; c += blockDim.x) {
     double m = 0.0;
     for (int p = cstart[c]; p < cstart[c + 1]; ++p) m = val[p] > m ? val[p] : m;
@@ -763,6 +840,9 @@ struct BtJob {
   long long *scored;           // [n_off] or nullptr
   double *values;              // [n] or nullptr
   long long values_at;         // -1: no values
+  int k_src;                   // sources per component at most (INT_MAX: every vertex, ppk_network_summary)
+  unsigned long long seed;     // ... of the sample
+  bool whole;                  // values: every component of >= 3 vertices, normalised by the whole graph's size
 };
 
 int bt_run(const BtJob &job, hipStream_t s, int dev, size_t n, size_t m, size_t no, const std::vector<unsigned> &counts,
@@ -775,20 +855,36 @@ int bt_run(const BtJob &job, hipStream_t s, int dev, size_t n, size_t m, size_t 
   size_t sort_tmp = 0, sort_tmp2 = 0;
   if (n) PPK_HIP(rocprim::radix_sort_keys(nullptr, sort_tmp, (unsigned long long *)nullptr, (unsigned long long *)nullptr, n, 0u, end_bit, s));
   if (e) PPK_HIP(rocprim::radix_sort_keys(nullptr, sort_tmp2, (unsigned long long *)nullptr, (unsigned long long *)nullptr, e, 0u, end_bit, s));
-  const size_t tmp = sort_tmp > sort_tmp2 ? sort_tmp : sort_tmp2;
+  size_t tmp = sort_tmp > sort_tmp2 ? sort_tmp : sort_tmp2;
+  // a sampled call's source lists (bt_sources) and a whole-graph call's second normalisation: no bytes otherwise
+  const bool sampled = job.k_src != INT_MAX;
+  const int min_nc = job.whole ? 3 : 4;
+  const size_t n_s = sampled ? n : 0, n_w = job.whole ? n : 0;
+  if (n_s) {
+    size_t pair_tmp = 0, scan_tmp = 0;
+    PPK_HIP(rocprim::radix_sort_pairs(nullptr, pair_tmp, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                      (int *)nullptr, (int *)nullptr, n, 0u, end_bit, s));
+    PPK_HIP(rocprim::exclusive_scan(nullptr, scan_tmp, (int *)nullptr, (int *)nullptr, 0, n, rocprim::plus<int>(), s));
+    tmp = tmp > pair_tmp ? tmp : pair_tmp;
+    tmp = tmp > scan_tmp ? tmp : scan_tmp;
+  }
   long long *hdr, *pbase;
   unsigned *fill, *rstart;
   int *root, *size, *crank, *csize, *cstart, *spi, *ibase, *local, *order, *lnbr;
-  unsigned long long *ka, *kb, *ea, *eb;
-  double *val, *cmax;
+  int *sid_a, *sid_b, *sflag, *spos, *src, *sbase;
+  unsigned long long *ka, *kb, *ea, *eb, *ska, *skb;
+  double *val, *cmax, *wval;
   char *d_tmp;
   int rc = ppk_scratch_carve(dev, SLOT_NET_BT, [&](Carve &c) {
     c.take(hdr, H_LEN).take(fill, 1).take(root, n).take(size, n).take(crank, n);
     c.take(csize, n + 2).take(cstart, n + 2).take(spi, n + 2).take(ibase, n + 2).take(pbase, n + 2);
     c.take(local, n).take(order, n).take(ka, n).take(kb, n).take(rstart, n + 1).take(val, n).take(cmax, n);
     c.take(ea, e).take(eb, e).take(lnbr, e).take(d_tmp, tmp + 16);
+    c.take(ska, n_s).take(skb, n_s).take(sid_a, n_s).take(sid_b, n_s).take(sflag, n_s).take(spos, n_s);
+    c.take(src, n_s).take(sbase, n_s ? n + 2 : 0).take(wval, n_w);
   });
   if (rc != PPK_OK) return rc;
+  if (!job.whole) wval = nullptr;
 
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
@@ -822,13 +918,14 @@ int bt_run(const BtJob &job, hipStream_t s, int dev, size_t n, size_t m, size_t 
     PPK_HIP(hipMemsetAsync(fill, 0, 4, s));
     const dim3 gn(grid_for(n, kThreads, 4096));
     hipLaunchKernelGGL(bt_sizes_kernel, gn, dim3(kThreads), 0, s, parent, n, root, size);
-    hipLaunchKernelGGL(bt_root_keys_kernel, gn, dim3(kThreads), 0, s, root, size, n, ka);
+    hipLaunchKernelGGL(bt_root_keys_kernel, gn, dim3(kThreads), 0, s, root, size, n, min_nc, ka);
     size_t tb = tmp;
     PPK_HIP(rocprim::radix_sort_keys(d_tmp, tb, ka, kb, n, 0u, end_bit, s));
     hipLaunchKernelGGL(bt_comps_kernel, dim3(grid_for(n + 1, kThreads, 4096)), dim3(kThreads), 0, s, kb, size, n,
                        crank, csize);
     hipLaunchKernelGGL(bt_starts_kernel, dim3(1), dim3(kThreads), 0, s, csize, n, cstart, hdr);
-    hipLaunchKernelGGL(bt_vertex_keys_kernel, gn, dim3(kThreads), 0, s, root, size, crank, n, ka, local);
+    hipLaunchKernelGGL(bt_vertex_keys_kernel, gn, dim3(kThreads), 0, s, root, size, crank, n, min_nc, ka,
+                       local);
     tb = tmp;
     PPK_HIP(rocprim::radix_sort_keys(d_tmp, tb, ka, kb, n, 0u, end_bit, s));
     hipLaunchKernelGGL(bt_local_kernel, gn, dim3(kThreads), 0, s, kb, n, local, order);
@@ -841,10 +938,23 @@ int bt_run(const BtJob &job, hipStream_t s, int dev, size_t n, size_t m, size_t 
     hipLaunchKernelGGL(bt_rows_kernel, dim3(grid_for(len, kThreads, 8192)), dim3(kThreads), 0, s, eb, len, hdr,
                        rstart, lnbr);
     PPK_HIP(hipGetLastError());
+    if (sampled) {
+      // -- sources: (component, sample key) sorted over the local ids; the first k of each larger component, listed
+      ppk_prof_stage("bt_sources", s);
+      hipLaunchKernelGGL(bt_src_keys_kernel, gn, dim3(kThreads), 0, s, kb, csize, hdr, n, job.k_src, job.seed, ska,
+                         sid_a, sflag);
+      tb = tmp;
+      PPK_HIP(rocprim::radix_sort_pairs(d_tmp, tb, ska, skb, sid_a, sid_b, n, 0u, end_bit, s));
+      hipLaunchKernelGGL(bt_src_pick_kernel, gn, dim3(kThreads), 0, s, skb, sid_b, csize, cstart, hdr, job.k_src, sflag);
+      tb = tmp;
+      PPK_HIP(rocprim::exclusive_scan(d_tmp, tb, sflag, spos, 0, n, rocprim::plus<int>(), s));
+      hipLaunchKernelGGL(bt_src_list_kernel, gn, dim3(kThreads), 0, s, kb, sflag, spos, cstart, hdr, src, sbase);
+      PPK_HIP(hipGetLastError());
+    }
     // -- plan: the graph's one synchronisation
     ppk_prof_stage("bt_plan", s);
     hipLaunchKernelGGL(bt_plan_kernel, dim3(1), dim3(kThreads), 0, s, csize, cstart, rstart, n, (int)small_max,
-                       (int)lds_max, spi, ibase, pbase, hdr);
+                       (int)lds_max, job.k_src, spi, ibase, pbase, hdr);
     PPK_HIP(hipGetLastError());
     const unsigned long long *h = nullptr;
     if ((rc = ppk_read_back(dev, s, {{hdr, H_LEN * 8}}, &h)) != PPK_OK) return rc;
@@ -865,27 +975,28 @@ int bt_run(const BtJob &job, hipStream_t s, int dev, size_t n, size_t m, size_t 
       PPK_HIP(hipMemsetAsync(next, 0, 8, s));
       if (items_glob > 0)
         hipLaunchKernelGGL(bt_items_kernel<false>, dim3(g_glob), dim3(kThreads), 0, s, rstart, lnbr, csize, cstart,
-                           spi, ibase, pbase, kbig, 0, items_glob, next, slab, slab_stride, partial);
+                           spi, ibase, pbase, src, sbase, job.k_src, kbig, 0, items_glob, next, slab, slab_stride,
+                           partial);
       if (n_items > items_glob) {
         const int li = n_items - items_glob;
         hipLaunchKernelGGL(bt_items_kernel<true>, dim3((unsigned)(li < 8 * cus ? li : 8 * cus)), dim3(kThreads),
-                           bt_state_bytes(nc_lds), s, rstart, lnbr, csize, cstart, spi, ibase, pbase, kbig, items_glob,
-                           n_items, next + 1, (char *)nullptr, (size_t)0, partial);
+                           bt_state_bytes(nc_lds), s, rstart, lnbr, csize, cstart, spi, ibase, pbase, src, sbase,
+                           job.k_src, kbig, items_glob, n_items, next + 1, (char *)nullptr, (size_t)0, partial);
       }
       if (K > kbig)
         hipLaunchKernelGGL(bt_small_kernel, dim3((unsigned)(K - kbig)), dim3(64), 0, s, rstart, lnbr, csize, cstart,
-                           pbase, kbig, partial);
+                           pbase, src, sbase, job.k_src, kbig, partial);
       PPK_HIP(hipGetLastError());
       ppk_prof_stage("bt_reduce", s);
       hipLaunchKernelGGL(bt_reduce_kernel, dim3(grid_for((size_t)h[H_SCORED], kThreads, 4096)), dim3(kThreads), 0, s,
-                         partial, csize, cstart, ibase, pbase, hdr, val);
+                         partial, csize, cstart, ibase, pbase, hdr, job.k_src, (long long)n, val, wval);
     }
     if (K == 0) ppk_prof_stage("bt_reduce", s);
     hipLaunchKernelGGL(bt_summary_kernel, dim3(1), dim3(kThreads), 0, s, val, csize, cstart, hdr, cmax, (int)o, job.bt,
                        job.scored);
     if ((long long)o == values_graph && K > 0)
       hipLaunchKernelGGL(bt_values_kernel, dim3(grid_for((size_t)h[H_SCORED], kThreads, 4096)), dim3(kThreads), 0, s,
-                         val, order, hdr, job.values);
+                         job.whole ? wval : val, order, hdr, job.values);
     PPK_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(bt_fill_kernel, dim3(1), dim3(64), 0, s, cnt, (int)no, job.bt, job.scored);
@@ -1243,24 +1354,35 @@ extern "C" int ppk_network_sweep(const long long *i, const long long *j, const l
   });
 }
 
-extern "C" int ppk_network_summary_dev(const long long *d_i, const long long *d_j, size_t stride,
-                                       const long long *d_off, size_t n_edges, size_t n_vertices, size_t n_off,
-                                       long long values_at, long long *d_stats, double *d_bt, long long *d_scored,
-                                       double *d_values, void *stream) {
+namespace {
+
+// ppk_network_summary_dev and its sampled form: k_src = INT_MAX is every source
+int summary_dev(const std::string &who, const long long *d_i, const long long *d_j, size_t stride, const long long *d_off,
+                size_t n_edges, size_t n_vertices, size_t n_off, long long values_at, long long *d_stats, double *d_bt,
+                long long *d_scored, double *d_values, int k_src, unsigned long long seed, bool whole, void *stream) {
   if (n_off >= 1 && n_off <= (size_t)kMaxOff && (values_at < -1 || values_at >= (long long)n_off))
-    return ppk_fail(PPK_ERR_ARG, "ppk_network_summary: values_at must be -1 or an offset index");
-  if (!d_bt || (values_at >= 0 && !d_values && n_vertices)) return ppk_fail(PPK_ERR_ARG, "ppk_network_summary: NULL array");
-  const BtJob job{d_bt, d_scored, values_at >= 0 && n_vertices ? d_values : nullptr, values_at};
-  return net_sweep("ppk_network_summary", d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, -1, d_stats, nullptr,
-                   stream, &job);
+    return ppk_fail(PPK_ERR_ARG, who + ": values_at must be -1 or an offset index");
+  if (!d_bt || (values_at >= 0 && !d_values && n_vertices)) return ppk_fail(PPK_ERR_ARG, who + ": NULL array");
+  const BtJob job{d_bt, d_scored, values_at >= 0 && n_vertices ? d_values : nullptr, values_at, k_src, seed, whole};
+  return net_sweep(who, d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, -1, d_stats, nullptr, stream, &job);
 }
 
-extern "C" int ppk_network_summary(const long long *i, const long long *j, const long long *off, size_t n_edges,
-                                   size_t n_vertices, size_t n_off, int device_id, long long values_at, long long *stats,
-                                   double *bt, long long *scored, double *values) {
+// the sampled calls' own arguments, checked: *k_src = min(bt_sources, INT_MAX)
+int sampled_check(const std::string &who, size_t bt_sources, int flags, int *k_src) {
+  if (bt_sources == 0) return ppk_fail(PPK_ERR_ARG, who + ": bt_sources must be >= 1");
+  if (flags & ~PPK_BT_WHOLE_GRAPH) return ppk_fail(PPK_ERR_ARG, who + ": unknown flag bits");
+  *k_src = bt_sources < (size_t)INT_MAX ? (int)bt_sources : INT_MAX;
+  return PPK_OK;
+}
+
+// the host-array forms: copy in, call `dev_call(d_i, d_j, d_off, d_stats, d_bt, d_scored, d_values)`, copy out
+template <typename Call>
+int summary_host(const std::string &who, const long long *i, const long long *j, const long long *off, size_t n_edges,
+                 size_t n_vertices, size_t n_off, int device_id, long long values_at, long long *stats, double *bt,
+                 long long *scored, double *values, Call dev_call) {
   if (!stats || !bt || (n_edges && (!i || !j)) || (values_at >= 0 && !values && n_vertices))
-    return ppk_fail(PPK_ERR_ARG, "ppk_network_summary: NULL array");
-  const int rc = net_check("ppk_network_summary", n_edges, n_vertices, n_off);
+    return ppk_fail(PPK_ERR_ARG, who + ": NULL array");
+  const int rc = net_check(who, n_edges, n_vertices, n_off);
   if (rc != PPK_OK) return rc;
   long long *d_i, *d_j, *d_o, *d_stats, *d_scored;
   double *d_bt, *d_values;
@@ -1274,8 +1396,7 @@ extern "C" int ppk_network_summary(const long long *i, const long long *j, const
       PPK_HIP(hipMemcpy(d_j, j, n_edges * 8, hipMemcpyHostToDevice));
       if (off) PPK_HIP(hipMemcpy(d_o, off, n_edges * 8, hipMemcpyHostToDevice));
     }
-    const int rc = ppk_network_summary_dev(d_i, d_j, 1, off ? d_o : nullptr, n_edges, n_vertices, n_off, values_at,
-                                           d_stats, d_bt, d_scored, values_at >= 0 ? d_values : nullptr, nullptr);
+    const int rc = dev_call(d_i, d_j, off ? d_o : nullptr, d_stats, d_bt, d_scored, values_at >= 0 ? d_values : nullptr);
     if (rc != PPK_OK) return rc;
     PPK_HIP(hipMemcpy(stats, d_stats, n_off * 32, hipMemcpyDeviceToHost));
     PPK_HIP(hipMemcpy(bt, d_bt, n_off * 16, hipMemcpyDeviceToHost));
@@ -1283,6 +1404,57 @@ extern "C" int ppk_network_summary(const long long *i, const long long *j, const
     if (values_at >= 0 && n_vertices) PPK_HIP(hipMemcpy(values, d_values, n_vertices * 8, hipMemcpyDeviceToHost));
     return PPK_OK;
   });
+}
+
+}  // namespace
+
+extern "C" int ppk_network_summary_dev(const long long *d_i, const long long *d_j, size_t stride,
+                                       const long long *d_off, size_t n_edges, size_t n_vertices, size_t n_off,
+                                       long long values_at, long long *d_stats, double *d_bt, long long *d_scored,
+                                       double *d_values, void *stream) {
+  return summary_dev("ppk_network_summary", d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, values_at, d_stats, d_bt,
+                     d_scored, d_values, INT_MAX, 0, false, stream);
+}
+
+extern "C" int ppk_network_summary(const long long *i, const long long *j, const long long *off, size_t n_edges,
+                                   size_t n_vertices, size_t n_off, int device_id, long long values_at, long long *stats,
+                                   double *bt, long long *scored, double *values) {
+  return summary_host("ppk_network_summary", i, j, off, n_edges, n_vertices, n_off, device_id, values_at, stats, bt,
+                      scored, values,
+                      [&](const long long *d_i, const long long *d_j, const long long *d_o, long long *d_stats,
+                          double *d_bt, long long *d_scored, double *d_values) {
+                        return ppk_network_summary_dev(d_i, d_j, 1, d_o, n_edges, n_vertices, n_off, values_at, d_stats,
+                                                       d_bt, d_scored, d_values, nullptr);
+                      });
+}
+
+extern "C" int ppk_network_summary_sampled_dev(const long long *d_i, const long long *d_j, size_t stride,
+                                               const long long *d_off, size_t n_edges, size_t n_vertices, size_t n_off,
+                                               long long values_at, long long *d_stats, double *d_bt,
+                                               long long *d_scored, double *d_values, size_t bt_sources,
+                                               unsigned long long seed, int flags, void *stream) {
+  int k_src = 0;
+  const int rc = sampled_check("ppk_network_summary_sampled", bt_sources, flags, &k_src);
+  if (rc != PPK_OK) return rc;
+  return summary_dev("ppk_network_summary_sampled", d_i, d_j, stride, d_off, n_edges, n_vertices, n_off, values_at,
+                     d_stats, d_bt, d_scored, d_values, k_src, seed, (flags & PPK_BT_WHOLE_GRAPH) != 0, stream);
+}
+
+extern "C" int ppk_network_summary_sampled(const long long *i, const long long *j, const long long *off,
+                                           size_t n_edges, size_t n_vertices, size_t n_off, int device_id,
+                                           long long values_at, long long *stats, double *bt, long long *scored,
+                                           double *values, size_t bt_sources, unsigned long long seed, int flags) {
+  int k_src = 0;
+  const int rc = sampled_check("ppk_network_summary_sampled", bt_sources, flags, &k_src);
+  if (rc != PPK_OK) return rc;
+  return summary_host("ppk_network_summary_sampled", i, j, off, n_edges, n_vertices, n_off, device_id, values_at, stats,
+                      bt, scored, values,
+                      [&](const long long *d_i, const long long *d_j, const long long *d_o, long long *d_stats,
+                          double *d_bt, long long *d_scored, double *d_values) {
+                        return ppk_network_summary_sampled_dev(d_i, d_j, 1, d_o, n_edges, n_vertices, n_off, values_at,
+                                                               d_stats, d_bt, d_scored, d_values, bt_sources, seed,
+                                                               flags, nullptr);
+                      });
 }
 
 extern "C" int ppk_cluster_sweep_dev(const long long *d_i, const long long *d_j, size_t stride, const long long *d_off,

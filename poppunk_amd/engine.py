@@ -1556,6 +1556,46 @@ def network_summary_graph_dev(edges_t, n, values=False):
     return stats[0], bt[0], scored[0], val
 
 
+def network_summary_sampled_dev(i_t, j_t, off_t, n, n_off, values_at=None, sources=100, seed=0, whole_graph=False):
+    """network_summary_dev from at most `sources` Brandes sources per component, the sample fixed by `seed`
+    (ppk_network_summary_sampled_dev): components of at most `sources` vertices give
+    network_summary_dev's bits.  whole_graph: `values` are vertex_betweenness(G, norm=True) of the whole graph
+    (components of 3 vertices included, divisor (n - 1)(n - 2)); bt and scored do not change.  Same returns."""
+    torch = _torch()
+    sources = int(sources)
+    if sources < 1:
+        raise ValueError("network_summary_sampled_dev: sources must be >= 1")
+    m, stride = _edge_stream(i_t, j_t, off_t)
+    va = -1 if values_at is None else int(values_at)
+    dev = i_t.device
+    no = max(int(n_off), 1)
+    with torch.cuda.device(dev):
+        stats = torch.empty((no, 4), dtype=torch.int64, device=dev)
+        bt = torch.empty((no, 2), dtype=torch.float64, device=dev)
+        scored = torch.empty(no, dtype=torch.int64, device=dev)
+        values = torch.empty(max(int(n), 1), dtype=torch.float64, device=dev) if va >= 0 else None
+        rc = _lib.lib().ppk_network_summary_sampled_dev(
+            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride,
+            C.c_void_p(off_t.data_ptr()) if off_t is not None else None, m, int(n), int(n_off), va,
+            C.c_void_p(stats.data_ptr()), C.c_void_p(bt.data_ptr()), C.c_void_p(scored.data_ptr()),
+            C.c_void_p(values.data_ptr()) if values is not None else None, sources, int(seed) & ((1 << 64) - 1),
+            _lib.BT_WHOLE_GRAPH if whole_graph else 0, _stream_ptr(dev.index))
+        _lib.check(rc, "ppk_network_summary_sampled_dev")
+    return stats, bt, scored, (values[:int(n)] if values is not None else None)
+
+
+def network_summary_sampled_graph_dev(edges_t, n, values=False, sources=100, seed=0, whole_graph=False):
+    """network_summary_sampled_dev of one int64 [m, 2] CUDA edge list, read in place; network_summary_graph_dev's
+    returns."""
+    torch = _torch()
+    if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
+            and edges_t.is_contiguous()):
+        raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
+    stats, bt, scored, val = network_summary_sampled_dev(edges_t[:, 0], edges_t[:, 1], None, n, 1,
+                                                         0 if values else None, sources, seed, whole_graph)
+    return stats[0], bt[0], scored[0], val
+
+
 def _mst_stream(edges_t):
     """(i_t, j_t) of an int64 [m, 2] CUDA edge list, or the pair itself."""
     torch = _torch()
@@ -1844,7 +1884,7 @@ def _samples_of(n_rows):
     return n
 
 
-def _sweep_scores(dist_t, sweep, n_off, score_idx=0):
+def _sweep_scores(dist_t, sweep, n_off, score_idx=0, betweenness_sample=None, seed=0):
     from . import refine
     n = _samples_of(dist_t.shape[0])
     i, j, o = sweep
@@ -1852,7 +1892,10 @@ def _sweep_scores(dist_t, sweep, n_off, score_idx=0):
         stats, _ = network_sweep_dev(i, j, o, n, n_off)
         st = stats.cpu().numpy()
         return stats, refine.grow_scores(st, n)
-    stats, bt, _, _ = network_summary_dev(i, j, o, n, n_off)
+    if betweenness_sample is None:
+        stats, bt, _, _ = network_summary_dev(i, j, o, n, n_off)
+    else:
+        stats, bt, _, _ = network_summary_sampled_dev(i, j, o, n, n_off, sources=betweenness_sample, seed=seed)
     return stats, refine.grow_scores(stats.cpu().numpy(), n, score_idx, bt=bt.cpu().numpy())
 
 
@@ -1862,21 +1905,24 @@ def _check_score_idx(score_idx):
     return int(score_idx)
 
 
-def refine_sweep_scores_dev(dist_t, offsets, slope, x0, y0, x1, y1, score_idx=0):
+def refine_sweep_scores_dev(dist_t, offsets, slope, x0, y0, x1, y1, score_idx=0, betweenness_sample=None, seed=0):
     """thresholdIterate1D + growNetwork on a resident float32 [n,2] CUDA matrix, without the edge list leaving the
     device (PopPUNK/refine.py:190-202).  Returns (stats int64 [len(offsets), 4] CUDA, growNetwork's score list).
-    score_idx 1 / 2 (refine's --score-idx) scores with the mean / size-weighted mean betweenness (network_summary_dev);
+    score_idx 1 / 2 (refine's --score-idx) scores with the mean / size-weighted mean betweenness (network_summary_dev;
+    with betweenness_sample = k, network_summary_sampled_dev from at most k sources per component under `seed`);
     0 leaves betweenness out, as growNetwork does."""
     score_idx = _check_score_idx(score_idx)
     off = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
-    return _sweep_scores(dist_t, threshold_iterate_1d_dev(dist_t, off, slope, x0, y0, x1, y1), off.size, score_idx)
+    return _sweep_scores(dist_t, threshold_iterate_1d_dev(dist_t, off, slope, x0, y0, x1, y1), off.size, score_idx,
+                         betweenness_sample, seed)
 
 
-def refine_sweep_scores_2d_dev(dist_t, x_max, y_max, score_idx=0):
+def refine_sweep_scores_2d_dev(dist_t, x_max, y_max, score_idx=0, betweenness_sample=None, seed=0):
     """thresholdIterate2D + growNetwork for one y (PopPUNK/refine.py:587-595), as refine_sweep_scores_dev."""
     score_idx = _check_score_idx(score_idx)
     xm = np.ascontiguousarray(x_max, dtype=np.float32).ravel()
-    return _sweep_scores(dist_t, threshold_iterate_2d_dev(dist_t, xm, y_max), xm.size, score_idx)
+    return _sweep_scores(dist_t, threshold_iterate_2d_dev(dist_t, xm, y_max), xm.size, score_idx, betweenness_sample,
+                         seed)
 
 
 def refine_score_dev(dist_t, slope, x_max, y_max):

@@ -116,13 +116,14 @@ class RefineBoundary:
 
     def fit_dev(self, dist_t, sample_names, model, max_move, min_move, startFile=None, indiv_refine=None,
                 unconstrained=False, score_idx=0, no_local=False, betweenness_sample=100, sample_size=None,
-                use_gpu=False, multi_boundary=0, outPrefix=None):
+                use_gpu=False, multi_boundary=0, outPrefix=None, sampled_betweenness=False, seed=0):
         """RefineFit.fit on a resident float32 [n(n-1)/2, 2] CUDA matrix: the 2-D refinement from the start points of
         `model` (a BGMMModel, a DBSCANModel, or `startFile`), then, for indiv_refine 'core' / 'accessory' / 'both',
         the slope-0 and slope-1 refinements, with the reference's fall-back when one of them fails.  Returns the
         assignment (assign_dev).  multi_boundary > 1: after the 2-D fit, refine.multi_refine writes the clusters at that
         many boundaries between the axis and the optimum under `outPrefix` (models.py:905-918); what it returns is kept
-        in self.multi_boundary_clusters.  The fit itself is the same with or without it."""
+        in self.multi_boundary_clusters.  The fit itself is the same with or without it.  sampled_betweenness / seed:
+        refine.refineFit's (score_idx 1 | 2 from at most betweenness_sample sources per component)."""
         import sys
         import torch
         from . import refine
@@ -136,7 +137,8 @@ class RefineBoundary:
         scaled = dist_t / torch.as_tensor(self.scale, device=dist_t.device)      # (the rule of assign_dev)
         scorer = refine.DeviceScorer(scaled)
         common = dict(score_idx=score_idx, no_local=no_local, num_processes=self.threads,
-                      betweenness_sample=betweenness_sample, sample_size=sample_size, use_gpu=use_gpu)
+                      betweenness_sample=betweenness_sample, sample_size=sample_size, use_gpu=use_gpu,
+                      sampled_betweenness=sampled_betweenness, seed=seed)
         self.optimal_x, self.optimal_y, self.optimal_s = refine.refineFit(
             scorer, sample_names, self.mean0, self.mean1, self.scale, max_move, min_move, slope=2,
             unconstrained=unconstrained, **common)
@@ -177,7 +179,7 @@ class RefineBoundary:
 
     def fit(self, X, sample_names, model, max_move, min_move, startFile=None, indiv_refine=None, unconstrained=False,
             score_idx=0, no_local=False, betweenness_sample=100, sample_size=None, use_gpu=False, device_id=0,
-            multi_boundary=0, outPrefix=None):
+            multi_boundary=0, outPrefix=None, sampled_betweenness=False, seed=0):
         """fit_dev on a host float32 [n(n-1)/2, 2] array, uploaded once: the same model to the bit.  Returns the
         assignment as a numpy array."""
         import torch
@@ -187,7 +189,8 @@ class RefineBoundary:
         y = self.fit_dev(torch.from_numpy(X).to("cuda:%d" % device_id), sample_names, model, max_move, min_move,
                          startFile=startFile, indiv_refine=indiv_refine, unconstrained=unconstrained,
                          score_idx=score_idx, no_local=no_local, betweenness_sample=betweenness_sample,
-                         sample_size=sample_size, use_gpu=use_gpu, multi_boundary=multi_boundary, outPrefix=outPrefix)
+                         sample_size=sample_size, use_gpu=use_gpu, multi_boundary=multi_boundary, outPrefix=outPrefix,
+                         sampled_betweenness=sampled_betweenness, seed=seed)
         return y.cpu().numpy()
 
     def plot(self, X, y=None, outPrefix=None, raster_above=1000000):

@@ -13,8 +13,11 @@ betweenness(norm=True) gives the same values is UNVERIFIED.
 
 G is an (edges, n_vertices) pair: edges an int64 [m, 2] numpy array or CUDA tensor (each unordered pair once), and
 the vertex count; a binding passes (G.get_edges(), G.num_vertices()).  A CUDA tensor is read in place on its device.
-`betweenness_sample` and `use_gpu` only steer the reference's cugraph branch: accepted and ignored.  `subsample`
-(random vertex subsampling) raises NotImplementedError before the device is touched.
+`betweenness_sample` and `use_gpu` only steer the reference's cugraph branch: accepted and ignored, unless
+`sampled_betweenness=True` asks for that branch's sampled sources (at most betweenness_sample per component, the sample
+fixed by `seed`: ppk_network_summary_sampled, this project's sampling rule).  `subsample` (random vertex subsampling)
+raises NotImplementedError before the device is touched.  vertex_betweenness(G, norm=True, betweenness_sample=None,
+seed=0) is PopPUNK/network.py:1310-1313 on the whole graph.
 
 Cluster numbers: printClusters and printExternalClusters (PopPUNK/network.py:1478-1719).  The
 number of every vertex comes from ppk_cluster_sweep / ppk_cluster_sweep_dev (cluster_numbers); the naming rules, the
@@ -44,17 +47,24 @@ from . import _lib, refine
 betweenness_sample_default = refine.betweenness_sample_default
 
 
-def _counts(G, calc_betweenness):
-    edges, n = G
+def _counts(G, calc_betweenness, sources=None, seed=0):
+    """sources: None = every source (ppk_network_summary); k = at most k per component (ppk_network_summary_sampled)"""
+    edges, n = G[:2]
     n = int(n)
     if hasattr(edges, "is_cuda"):
         from . import engine
+        if calc_betweenness and sources is not None:
+            stats, bt, _, _ = engine.network_summary_sampled_graph_dev(edges, n, sources=sources, seed=seed)
+            return stats.cpu().numpy(), bt.cpu().numpy(), n
         if calc_betweenness:
             stats, bt, _, _ = engine.network_summary_graph_dev(edges, n)
             return stats.cpu().numpy(), bt.cpu().numpy(), n
         stats, _ = engine.network_stats_dev(edges, n)
         return stats.cpu().numpy(), None, n
     e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    if calc_betweenness and sources is not None:
+        stats, bt, _, _ = refine.network_summary_sampled(e[:, 0], e[:, 1], None, n, 1, sources=sources, seed=seed)
+        return stats[0], bt[0], n
     if calc_betweenness:
         stats, bt, _, _ = refine.network_summary(e[:, 0], e[:, 1], None, n, 1)
         return stats[0], bt[0], n
@@ -63,18 +73,51 @@ def _counts(G, calc_betweenness):
 
 
 def networkSummary(G, calc_betweenness=True, betweenness_sample=betweenness_sample_default, subsample=None,
-                   use_gpu=False):
-    """PopPUNK/network.py:1204-1307, graph-tool branch (see the module docstring)."""
+                   use_gpu=False, sampled_betweenness=False, seed=0):
+    """PopPUNK/network.py:1204-1307, graph-tool branch (see the module docstring).  sampled_betweenness=True: the
+    device branch's betweenness_centrality(k=betweenness_sample) instead (network.py:1272-1287): at most
+    betweenness_sample sources per component, the sample fixed by `seed` (this project's rule)."""
     if subsample is not None:
         raise NotImplementedError("networkSummary: random vertex subsampling (subsample) is not mirrored")
-    stats, bt, n = _counts(G, calc_betweenness)
+    if sampled_betweenness and calc_betweenness:
+        if int(betweenness_sample) < 1:
+            raise ValueError("networkSummary: betweenness_sample must be >= 1")
+        stats, bt, n = _counts(G, True, int(betweenness_sample), seed)
+    else:
+        stats, bt, n = _counts(G, calc_betweenness)
     return refine.summary_from_stats(stats, n, bt)
 
 
-def print_network_summary(G, sample_size=None, betweenness_sample=betweenness_sample_default, use_gpu=False):
+def vertex_betweenness(G, norm=True, betweenness_sample=None, seed=0):
+    """PopPUNK/network.py:1310-1313 on G = (edges, n): float64 numpy [n], every vertex's betweenness in the whole graph,
+    networkx's betweenness_centrality(G, normalized=norm): the sum over sources of delta_s(v) over (n - 1)(n - 2) (0
+    for every vertex when n <= 2); norm=False gives the pair counts, each unordered pair once.  That graph-tool's
+    betweenness(norm=True) normalises the same way is UNVERIFIED.  betweenness_sample = k (this project's addition;
+    the reference takes (graph, norm) alone): at most k sources per component under `seed`, scaled by n_c / k
+    (ppk_network_summary_sampled).  A CUDA edge tensor is read in place."""
+    edges, n = G[:2]
+    n = int(n)
+    sources = (1 << 31) - 1 if betweenness_sample is None else int(betweenness_sample)
+    if sources < 1:
+        raise ValueError("vertex_betweenness: betweenness_sample must be >= 1")
+    if hasattr(edges, "is_cuda"):
+        from . import engine
+        values = engine.network_summary_sampled_graph_dev(edges, n, values=True, sources=sources, seed=seed,
+                                                          whole_graph=True)[3].cpu().numpy()
+    else:
+        e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+        values = refine.network_summary_sampled(e[:, 0], e[:, 1], None, n, 1, values_at=0, sources=sources, seed=seed,
+                                                whole_graph=True)[3]
+    if not norm:
+        values = values * (0.5 * float(n - 1) * float(n - 2))
+    return values
+
+
+def print_network_summary(G, sample_size=None, betweenness_sample=betweenness_sample_default, use_gpu=False,
+                          sampled_betweenness=False, seed=0):
     """PopPUNK/network.py:616-643: networkSummary's metrics and scores to stderr, in the reference's words."""
     (metrics, scores) = networkSummary(G, subsample=sample_size, betweenness_sample=betweenness_sample,
-                                       use_gpu=use_gpu)
+                                       use_gpu=use_gpu, sampled_betweenness=sampled_betweenness, seed=seed)
     sys.stderr.write("Network summary:\n" + "\n".join(["\tComponents\t\t\t\t" + str(metrics[0]),
                                                        "\tDensity\t\t\t\t\t" + "{:.4f}".format(metrics[1]),
                                                        "\tTransitivity\t\t\t\t" + "{:.4f}".format(metrics[2]),

@@ -26,9 +26,12 @@ evaluation of the local search and the 2-D grid run on that one tensor and no ed
 search is scipy's bounded minimiser, as upstream; its objective takes the four integer counts of one boundary from
 ppk_refine_score_dev, or, between the two lines of the search's bounds, from the bracket handle ppk_refine_local_*
 (option refine_local, 1 by default; both give the same counts, hence the same fit).  score_idx 1 and 2 evaluate through
-edge_threshold_dev + network_summary_graph_dev.  `num_processes` and `use_gpu` are accepted and ignored; `sample_size`
+edge_threshold_dev + network_summary_graph_dev; with sampled_betweenness=True (and seed=s) the sweep and the local search
+score from at most betweenness_sample Brandes sources per component instead (ppk_network_summary_sampled, DESIGN.md
+3.8).  `num_processes` and `use_gpu` are accepted and ignored; `sample_size`
 raises NotImplementedError before the device is touched.  `last_fit` describes the latest refineFit call: the global
-scores, the bounds, every evaluation of the local search (s, counts, score) and which path scored it.
+scores, the bounds, every evaluation of the local search (s, counts, score), which path scored it, and the betweenness
+mode ("exact" / "sampled") with its sample size and seed.
 
 Clusters at several boundaries mirrors PopPUNK/refine.py:249-312:
 
@@ -142,6 +145,37 @@ def network_summary(i_vec, j_vec, idx_vec, n, n_off=None, values_at=None, device
     return stats, bt, scored, (values[:int(n)] if values is not None else None)
 
 
+def network_summary_sampled(i_vec, j_vec, idx_vec, n, n_off=None, values_at=None, device=0, sources=100, seed=0,
+                            whole_graph=False):
+    """ppk_network_summary_sampled on host arrays: network_summary with at most `sources` Brandes sources per
+    component, the sample fixed by `seed`.  whole_graph: `values` are vertex_betweenness(G, norm=True)
+    of the whole graph (components of 3 vertices included, divisor (n - 1)(n - 2)); bt and scored do not change."""
+    sources = int(sources)
+    if sources < 1:
+        raise ValueError("network_summary_sampled: sources must be >= 1")
+    i = np.ascontiguousarray(i_vec, dtype=np.int64).ravel()
+    j = np.ascontiguousarray(j_vec, dtype=np.int64).ravel()
+    o = None if idx_vec is None else np.ascontiguousarray(idx_vec, dtype=np.int64).ravel()
+    if i.size != j.size or (o is not None and o.size != i.size):
+        raise ValueError("i_vec, j_vec and idx_vec differ in length")
+    if n_off is None:
+        n_off = int(o.max()) + 1 if o is not None and o.size else 1
+    va = -1 if values_at is None else int(values_at)
+    no = max(int(n_off), 1)
+    stats = np.zeros((no, 4), dtype=np.int64)
+    bt = np.zeros((no, 2), dtype=np.float64)
+    scored = np.zeros(no, dtype=np.int64)
+    values = np.zeros(max(int(n), 1), dtype=np.float64) if va >= 0 else None
+    llp, dp = C.POINTER(C.c_longlong), C.POINTER(C.c_double)
+    rc = _lib.lib().ppk_network_summary_sampled(
+        i.ctypes.data_as(llp), j.ctypes.data_as(llp), o.ctypes.data_as(llp) if o is not None else None, i.size, int(n),
+        int(n_off), int(device), va, stats.ctypes.data_as(llp), bt.ctypes.data_as(dp), scored.ctypes.data_as(llp),
+        values.ctypes.data_as(dp) if values is not None else None, sources, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        _lib.BT_WHOLE_GRAPH if whole_graph else 0)
+    _lib.check(rc, "ppk_network_summary_sampled")
+    return stats, bt, scored, (values[:int(n)] if values is not None else None)
+
+
 def growNetwork(sample_names, i_vec, j_vec, idx_vec, s_range, score_idx=0, thread_idx=0,
                 betweenness_sample=betweenness_sample_default, write_clusters=None, sample_size=None,
                 use_gpu=False):
@@ -217,15 +251,23 @@ class DeviceScorer:
                 raise ValueError("distMat must be a float32 [n, 2] array")
             self.dist_t = torch.from_numpy(X).to("cuda:%d" % device_id)
         self.n_rows = int(self.dist_t.shape[0])
+        self.bt_sources, self.bt_seed = None, 0
+
+    def set_betweenness_sample(self, sources, seed=0):
+        """score_idx 1 / 2 from at most `sources` Brandes sources per component (None: every source, the default)"""
+        if sources is not None and int(sources) < 1:
+            raise ValueError("betweenness_sample must be >= 1")
+        self.bt_sources, self.bt_seed = (None if sources is None else int(sources)), int(seed)
 
     def sweep_1d(self, s_range, slope, mean0, mean1, score_idx):
         """-> (rows the sweep lists, growNetwork's list)"""
         stats, scores = self.engine.refine_sweep_scores_dev(self.dist_t, s_range, slope, mean0[0], mean0[1], mean1[0],
-                                                            mean1[1], score_idx)
+                                                            mean1[1], score_idx, self.bt_sources, self.bt_seed)
         return int(stats[-1, 0].item()), scores
 
     def sweep_2d(self, x_range, y_max, score_idx):
-        stats, scores = self.engine.refine_sweep_scores_2d_dev(self.dist_t, x_range, y_max, score_idx)
+        stats, scores = self.engine.refine_sweep_scores_2d_dev(self.dist_t, x_range, y_max, score_idx,
+                                                               self.bt_sources, self.bt_seed)
         return int(stats[-1, 0].item()), scores
 
     def score(self, slope, x_max, y_max, score_idx):
@@ -233,7 +275,12 @@ class DeviceScorer:
         if score_idx == 0:
             return self.engine.refine_score_dev(self.dist_t, slope, x_max, y_max), None
         edges = self.engine.edge_threshold_dev(self.dist_t, slope, x_max, y_max)
-        stats, bt, _, _ = self.engine.network_summary_graph_dev(edges, self.engine._samples_of(self.n_rows))
+        n = self.engine._samples_of(self.n_rows)
+        if self.bt_sources is None:
+            stats, bt, _, _ = self.engine.network_summary_graph_dev(edges, n)
+        else:
+            stats, bt, _, _ = self.engine.network_summary_sampled_graph_dev(edges, n, sources=self.bt_sources,
+                                                                            seed=self.bt_seed)
         return stats.cpu().numpy(), bt.cpu().numpy()
 
     def bracket(self, slope, lo, hi):
@@ -241,8 +288,13 @@ class DeviceScorer:
         return self.engine.RefineLocal.create(self.dist_t, slope, lo[0], lo[1], hi[0], hi[1])
 
 
-def _scorer_of(distMat):
-    return distMat if hasattr(distMat, "sweep_1d") else DeviceScorer(distMat)
+def _scorer_of(distMat, bt_sources=None, seed=0):
+    scorer = distMat if hasattr(distMat, "sweep_1d") else DeviceScorer(distMat)
+    if hasattr(scorer, "set_betweenness_sample"):
+        scorer.set_betweenness_sample(bt_sources, seed)
+    elif bt_sources is not None:
+        raise TypeError("sampled_betweenness needs a scorer with set_betweenness_sample (DeviceScorer)")
+    return scorer
 
 
 def _check_fit_args(score_idx, sample_size, who):
@@ -307,14 +359,21 @@ def _local_objective(scorer, n, mean0, mean1, gradient, slope, score_idx, bounds
 
 def refineFit(distMat, sample_names, mean0, mean1, scale, max_move, min_move, slope=2, score_idx=0,
               unconstrained=False, no_local=False, num_processes=1, betweenness_sample=betweenness_sample_default,
-              sample_size=None, use_gpu=False):
+              sample_size=None, use_gpu=False, sampled_betweenness=False, seed=0):
     """PopPUNK/refine.py:51-247: the global sweep (40 offsets along mean0 -> mean1, or the 20 x 20 grid of the
     unconstrained search), then scipy's bounded minimiser between the global minimum's neighbours
-    -> (optimal_x, optimal_y, optimised_s)."""
+    -> (optimal_x, optimal_y, optimised_s).  sampled_betweenness=True (score_idx 1 | 2): the sweep and the local
+    search score from at most betweenness_sample Brandes sources per component, the sample fixed by `seed` (DESIGN.md
+    3.8); False, the default, ignores betweenness_sample as before."""
     global last_fit
     _check_fit_args(score_idx, sample_size, "refineFit")
     import scipy.optimize
-    info = {"global_s": None, "bounds": None, "evals": [], "local_path": None, "split": None}
+    sampled = bool(sampled_betweenness) and score_idx > 0
+    if sampled and int(betweenness_sample) < 1:
+        raise ValueError("refineFit: betweenness_sample must be >= 1")
+    info = {"global_s": None, "bounds": None, "evals": [], "local_path": None, "split": None,
+            "betweenness": "sampled" if sampled else "exact", "betweenness_sample": int(betweenness_sample) if sampled
+            else None, "seed": int(seed) if sampled else None}
     last_fit = info
     n = len(sample_names)
     sys.stderr.write("Trying to optimise score globally\n")
@@ -339,7 +398,7 @@ def refineFit(distMat, sample_names, mean0, mean1, scale, max_move, min_move, sl
         sys.stderr.write("Searching accessory intercept from " + "{:.3f}".format(y_max_start * scale[1]) + " to " +
                          "{:.3f}".format(y_max_end * scale[1]) + "\n")
 
-        scorer = _scorer_of(distMat)
+        scorer = _scorer_of(distMat, int(betweenness_sample) if sampled else None, seed)
         global_s = [newNetwork2D(y_idx, sample_names, scorer, x_max, y_max, score_idx, betweenness_sample,
                                  sample_size, use_gpu) for y_idx in range(global_grid_resolution)]
         global_s = np.array(list(chain.from_iterable(global_s)))
@@ -367,7 +426,7 @@ def refineFit(distMat, sample_names, mean0, mean1, scale, max_move, min_move, sl
         if min_x < 0 or min_y < 0:
             raise RuntimeError("Boundary range below zero")
 
-        scorer = _scorer_of(distMat)
+        scorer = _scorer_of(distMat, int(betweenness_sample) if sampled else None, seed)
         listed, scores = scorer.sweep_1d(s_range, slope, mean0, mean1, score_idx)
         if listed == scorer.n_rows:
             raise RuntimeError("Boundary range includes all points")

@@ -3,6 +3,7 @@ its 40-offset thresholdIterate1D sweep (built as tools/bench_network.py builds i
 
     timeout -k 10 900 python tools/bench_betweenness.py [--out profiles/betweenness/bench_betweenness.json]
                                                         [--final-only] [--steps K] [--no-cpu]
+                                                        [--sampled K] [--seed S]
 
 Records: HIP-event ms and wall ms per call (median of --steps after one warm-up) for the final graph alone (every
 edge at one offset: what each fit's networkSummary pays) and, unless --final-only, for the whole sweep; the library's
@@ -10,6 +11,9 @@ stage split of each; the work model W = sum over components c of more than 3 ver
 c) per graph, and the probe rate 2 W / time it implies (each source reads every row of its component twice: discover
 with sigma, then delta); the final graph's component sizes and betweenness means.  CPU: networkx cannot finish the
 final graph in reasonable time, so a networkx Brandes of one subgraph is timed and EXTRAPOLATED by the work model.
+--sampled K (default 100; 0 leaves the leg out): the sampled call (ppk_network_summary_sampled_dev, at most K sources
+per component) timed next to the exact call in the same run, with its stage split, |sampled - exact| of the two
+betweenness means per level, and whether grow_scores(score_idx = 1 and 2) puts its optimum at the same level.
 --pmc-only: only final-graph calls (five), the program a counter pass (rocprofv3 --pmc) runs."""
 import argparse
 import json
@@ -94,6 +98,8 @@ def main():
     ap.add_argument("--final-only", action="store_true")
     ap.add_argument("--pmc-only", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--sampled", type=int, default=100)
+    ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     import torch
     from poppunk_amd import _lib, engine
@@ -135,6 +141,43 @@ def main():
                         "work_model_per_graph": w_sweep, "work_model": int(sum(w_sweep)),
                         "probes_per_s": round(2 * sum(w_sweep) / (ev * 1e-3), -6)}
         print(json.dumps({k: v for k, v in res["sweep"].items() if k != "work_model_per_graph"}), flush=True)
+    if a.sampled > 0:
+        from poppunk_amd import refine
+
+        def final_s():
+            return engine.network_summary_sampled_dev(i, j, None, n, 1, sources=a.sampled, seed=a.seed)
+
+        def sweep_s():
+            return engine.network_summary_sampled_dev(i, j, o, n, 40, sources=a.sampled, seed=a.seed)
+
+        ev, wall = timed(final_s, a.steps)
+        stats_s, bt_f, _, _ = final_s()
+        assert torch.equal(stats_s, stats), "the sampled call's counts differ"
+        leg = {"sources": a.sampled, "seed": a.seed,
+               "final": {"event_ms": ev, "wall_ms": wall, "stages_ms_per_call": staged(lib, final_s, a.steps),
+                         "exact_event_ms": res["final"]["event_ms"],
+                         "speedup": round(res["final"]["event_ms"] / ev, 2), "bt": [float(x) for x in bt_f[0].tolist()],
+                         "abs_diff_bt": [abs(float(x) - float(y)) for x, y in zip(bt_f[0].tolist(), bt[0].tolist())]}}
+        if not a.final_only:
+            ev, wall = timed(sweep_s, a.steps)
+            st_s, bt_ss, _, _ = sweep_s()
+            diff = (bt_ss - bt_s).abs().cpu().numpy()
+            st_h = st_s.cpu().numpy()
+            optimum = {}
+            for idx in (1, 2):
+                ex = refine.grow_scores(st_h, n, idx, bt=bt_s.cpu().numpy())
+                sa = refine.grow_scores(st_h, n, idx, bt=bt_ss.cpu().numpy())
+                optimum["score_idx_%d" % idx] = {"exact_level": int(np.argmin(ex)), "sampled_level": int(np.argmin(sa)),
+                                                 "same": bool(np.argmin(ex) == np.argmin(sa)),
+                                                 "max_abs_score_diff": float(np.abs(np.array(ex) - np.array(sa)).max())}
+            leg["sweep"] = {"event_ms": ev, "wall_ms": wall, "stages_ms_per_call": staged(lib, sweep_s, a.steps),
+                            "exact_event_ms": res["sweep"]["event_ms"],
+                            "speedup": round(res["sweep"]["event_ms"] / ev, 2),
+                            "abs_diff_mean_per_level": [float(x) for x in diff[:, 0]],
+                            "abs_diff_weighted_mean_per_level": [float(x) for x in diff[:, 1]],
+                            "max_abs_diff": [float(diff[:, 0].max()), float(diff[:, 1].max())], "optimum": optimum}
+        res["sampled"] = leg
+        print(json.dumps(leg), flush=True)
     if not a.no_cpu:
         # networkx Brandes of the subgraph on the first k vertices of the largest component, extrapolated by W
         import networkx as nx
