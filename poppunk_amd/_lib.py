@@ -6,6 +6,8 @@ import of this module's `lib()` raises, and every product entry point fails.
 import ctypes as C
 import os
 
+from numpy import ndarray as _ndarray
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PPK_LIBRARY: another build of the same library (the measurement tools load csrc/libppk_hip_exp.so, tools/_exp.py)
 SO_PATH = os.environ.get("PPK_LIBRARY") or os.path.join(_HERE, "csrc", "libppk_hip.so")
@@ -440,3 +442,23 @@ def check(rc, what="ppk call"):
     (src/python_bindings.cpp:54-56)."""
     if rc != OK:
         raise RuntimeError("%s failed (%d): %s" % (what, rc, last_error()))
+
+
+def call(name, *args, arg_error=None, accept=(), what=None):
+    """Call the status-returning function `name` and deal with its status.  A numpy array (a plain ndarray, as
+    np.ascontiguousarray and np.empty make them: the caller made it contiguous and of the right dtype) goes in as the
+    pointer type SIGNATURES declares for its position; everything else --
+    None, ints, floats, ctypes objects, byref -- is passed as it is.  A status in `accept` is returned (the
+    ERR_CAPACITY retries); with `arg_error`, ERR_ARG raises arg_error(last_error()); every other failure is `check`'s
+    RuntimeError, under `what` where the error has always been reported under another name than the symbol's."""
+    fn = getattr(lib(), name)
+    if _ndarray in map(type, args):         # (most device calls carry no host array: one C-level scan finds that out)
+        types = fn.argtypes
+        args = [a.ctypes.data_as(types[i]) if type(a) is _ndarray else a for i, a in enumerate(args)]
+    rc = fn(*args)
+    if rc in accept:
+        return rc
+    if arg_error is not None and rc == ERR_ARG:
+        raise arg_error(last_error())
+    check(rc, what or name)
+    return rc

@@ -25,6 +25,50 @@ def _stream_ptr(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+# ---- the frame every device call below goes through ------------------------------------------------
+def _dev_call(name, dev, *args, then=(), arg_error=None, accept=()):
+    """`name(*args, stream, *then)` on device `dev`: inside torch.cuda.device(dev), with every tensor (anything that
+    has a data_ptr) as its address and the device's current stream -- read now, never kept: callers switch streams --
+    after the arguments (`then`: what the two create calls declare behind the stream).  Host arrays, scalars, None
+    and the status (`arg_error`, `accept`) are `_lib.call`'s.  Addresses go in as plain integers, which ctypes turns
+    into the `void *` SIGNATURES declares exactly as it does a c_void_p, without an object per argument and call."""
+    cuda = _torch().cuda
+    scope = cuda.device(dev)        # (resolves `dev` -- an index, a torch.device, "cuda:0" -- once: .idx)
+    with scope:
+        return _lib.call(name, *[a.data_ptr() if hasattr(a, "data_ptr") else a for a in args],
+                         cuda.current_stream(scope.idx).cuda_stream, *then, arg_error=arg_error, accept=accept)
+
+
+def _check_tensor(t, message, dtype, shape=None, dim=None, numel=None, like=None, contiguous=True):
+    """TypeError(message) unless t is a CUDA tensor of `dtype` (one, or a tuple to choose from), contiguous, with
+    `dim` dimensions (one, or a tuple), the sizes of `shape` (None: any size) or `numel` elements, on the device of
+    `like`."""
+    ok = (t.is_cuda and (t.dtype == dtype or (type(dtype) is tuple and t.dtype in dtype))
+          and (not contiguous or t.is_contiguous())
+          and (dim is None or (t.dim() in dim if type(dim) is tuple else t.dim() == dim))
+          and (numel is None or int(t.numel()) == numel)
+          and (like is None or t.device == like.device))
+    if ok and shape is not None:
+        have = t.shape
+        ok = len(have) == len(shape)
+        for want, size in zip(shape, have):
+            ok = ok and (want is None or want == size)
+    if not ok:
+        raise TypeError(message)
+
+
+def _cap_guess(n):
+    """The first capacity of a data-dependent list out of n rows (a short guess costs one exact re-run)."""
+    return min(n, max(1 << 20, n // 8))
+
+
+def _neighbour_outputs(n, dev):
+    """(i int64, j int64, dist float32) of n entries each: the neighbour lists as get_kNN_distances returns them."""
+    torch = _torch()
+    return (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
+            torch.empty(n, dtype=torch.float32, device=dev))
+
+
 def rows_in_band(n_ref, n_qry, q_begin, q_end):
     return int(_lib.lib().ppk_rows_in_band(n_ref, n_qry, q_begin, q_end))
 
@@ -32,7 +76,7 @@ def rows_in_band(n_ref, n_qry, q_begin, q_end):
 def band_split(n_ref, n_qry, n_parts):
     """Query-axis band edges giving n_parts (nearly) equal pair counts (multiples of 64)."""
     bounds = (C.c_size_t * (n_parts + 1))()
-    _lib.check(_lib.lib().ppk_band_split(n_ref, n_qry, n_parts, bounds), "ppk_band_split")
+    _lib.call("ppk_band_split", n_ref, n_qry, n_parts, bounds)
     return [int(b) for b in bounds]
 
 
@@ -70,7 +114,6 @@ class SketchDB:
     """
 
     def __init__(self, sketches, sketchsize64, bbits, clusters=None, device=0):
-        lib = _lib.lib()
         torch = _torch()
         self.device = int(device)
         self.sketchsize64 = int(sketchsize64)
@@ -83,35 +126,28 @@ class SketchDB:
             if sketches.device.index != self.device:
                 raise ValueError("sketch tensor is on a different device")
             n, nk, words = sketches.shape
-            src = C.c_void_p(sketches.data_ptr())
         else:
             sketches = np.ascontiguousarray(sketches, dtype=np.uint64)
             if sketches.ndim != 3:
                 raise ValueError("sketches must be [n, nk, sketchsize64*bbits]")
             n, nk, words = sketches.shape
-            src = C.c_void_p(sketches.ctypes.data)
         if words != self.sketchsize64 * self.bbits:
             raise ValueError("sketch word count %d != sketchsize64*bbits = %d"
                              % (words, self.sketchsize64 * self.bbits))
         self.n, self.nk = int(n), int(nk)
-        clu_ptr = None
         self._clu_keep = None
         if clusters is not None:
             if on_dev:
                 c = clusters.to(device="cuda:%d" % self.device, dtype=torch.int16).contiguous()
-                clu_ptr = C.c_void_p(c.data_ptr())
             else:
                 c = np.ascontiguousarray(clusters, dtype=np.uint16)
                 if c.shape != (n,):
                     raise ValueError("clusters must be [n]")
-                clu_ptr = C.c_void_p(c.ctypes.data)
             self._clu_keep = c
-        with torch.cuda.device(self.device):
-            rc = lib.ppk_db_create(self.device, src, n, nk, self.sketchsize64, self.bbits, clu_ptr,
-                                   1 if on_dev else 0, _stream_ptr(self.device), C.byref(self._h))
-            _lib.check(rc, "ppk_db_create")
-            if on_dev:
-                torch.cuda.current_stream(self.device).synchronize()   # source tensor may be freed
+        _dev_call("ppk_db_create", self.device, self.device, sketches, n, nk, self.sketchsize64, self.bbits,
+                  self._clu_keep, 1 if on_dev else 0, then=(C.byref(self._h),))
+        if on_dev:
+            torch.cuda.current_stream(self.device).synchronize()   # source tensor may be freed
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -142,15 +178,15 @@ class SketchDB:
         """[nk, per_block * sketchsize64] from one of the ppk_db_*_block_planes / _stream_planes / _position_order
         accessors"""
         out = np.empty((self.nk, per_block * self.sketchsize64), dtype=dtype)
-        _lib.check(getattr(_lib.lib(), fn)(self._h, C.c_void_p(out.ctypes.data), out.size), fn)
+        _lib.call(fn, self._h, out, out.size)
         return out
 
     def _codes(self, fn, planes, which=None, order=None):
         """One coded copy (ppk_db_*_read) un-bitsliced; with `order`, the sort of its slots undone."""
         npad = (self.n + 255) // 256 * 256
         raw = np.empty((self.nk, self.sketchsize64, max(planes, 1), npad), dtype=np.uint64)
-        args = (C.c_void_p(raw.ctypes.data), self.nk * self.sketchsize64 * planes * npad)
-        _lib.check(getattr(_lib.lib(), fn)(self._h, *(args if which is None else (int(which),) + args)), fn)
+        _lib.call(fn, self._h, *(() if which is None else (int(which),)), raw,
+                  self.nk * self.sketchsize64 * planes * npad)
         slots = self._unslice_codes(raw, planes)
         if order is None:
             return slots
@@ -165,8 +201,7 @@ class SketchDB:
         count = int(getattr(_lib.lib(), size_fn)(self._h, C.byref(nb)))
         off = np.zeros(nb.value + 1, dtype=np.uint32)
         items = np.zeros(count, dtype=dtype)
-        _lib.check(getattr(_lib.lib(), read_fn)(self._h, C.c_void_p(off.ctypes.data), off.size,
-                                                C.c_void_p(items.ctypes.data) if count else None, count), read_fn)
+        _lib.call(read_fn, self._h, off, off.size, items if count else None, count)
         return off, items
 
     def _unslice_codes(self, raw, planes):
@@ -265,7 +300,7 @@ class SketchDB:
         if not words:
             return None
         raw = np.zeros(words, dtype=np.uint32)
-        _lib.lib().ppk_db_rank_counts(self._h, C.c_void_p(raw.ctypes.data), raw.size)
+        _lib.lib().ppk_db_rank_counts(self._h, raw.ctypes.data, raw.size)      # (returns the word count, no status)
         seg = 1 + self.nk * self.sketchsize64
         out = {}
         for i, name in enumerate(("D", "E", "E2")):
@@ -276,19 +311,18 @@ class SketchDB:
 
 
 def _prep_tables(kmers, random_tbl, nk):
+    """(kmers int32 [nk], random table float32 [nk, n_clu, n_clu] or None, n_clu) as the kernel-1 calls take them."""
     kmers = np.ascontiguousarray(kmers, dtype=np.int32)
     if kmers.shape != (nk,):
         raise ValueError("klist length %d does not match the sketches' %d k-mer lengths"
                          % (kmers.size, nk))
     n_clu = 0
-    tbl_ptr = None
     if random_tbl is not None:
         random_tbl = np.ascontiguousarray(random_tbl, dtype=np.float32)
         if random_tbl.ndim != 3 or random_tbl.shape[0] != nk or random_tbl.shape[1] != random_tbl.shape[2]:
             raise ValueError("random table must be [nk, n_clu, n_clu]")
         n_clu = random_tbl.shape[1]
-        tbl_ptr = random_tbl.ctypes.data_as(C.POINTER(C.c_float))
-    return kmers, random_tbl, tbl_ptr, n_clu
+    return kmers, random_tbl, n_clu
 
 
 def _check_pair(ref, qry):
@@ -308,53 +342,46 @@ def dist(ref, qry=None, kmers=None, random_tbl=None, random_correct=True, jaccar
     fill kernel per launch).
     """
     torch = _torch()
-    lib = _lib.lib()
     _check_pair(ref, qry)
     nq = qry.n if qry is not None else ref.n
     q_end = nq if q_end is None else int(q_end)
-    kmers, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
+    kmers, random_tbl, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
     rows = rows_in_band(ref.n, qry.n if qry is not None else 0, q_begin, q_end)
     flags = (FLAG_RANDOM_CORRECT if random_correct else 0) | (FLAG_JACCARD if jaccard else 0) \
         | (FLAG_COUNTS if counts else 0)
     cols = ref.nk if (jaccard or counts) else 2
     dev = "cuda:%d" % ref.device
-    with torch.cuda.device(ref.device):
-        if out is None:
-            out = torch.empty((rows, cols), dtype=torch.int32 if counts else torch.float32,
-                              device=dev)
-        elif out.numel() != rows * cols or not out.is_contiguous() or out.element_size() != 4:
-            raise ValueError("out has the wrong size")
-        if n_failed is None:
-            n_failed = torch.zeros(1, dtype=torch.int64, device=dev)
-        rc = lib.ppk_dist_dev(ref._h, qry._h if qry is not None else None,
-                              kmers.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr, n_clu, flags,
-                              q_begin, q_end, C.c_void_p(out.data_ptr()),
-                              C.c_void_p(n_failed.data_ptr()), _stream_ptr(ref.device))
-        _lib.check(rc, "ppk_dist_dev")
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.int32 if counts else torch.float32, device=dev)
+    elif out.numel() != rows * cols or not out.is_contiguous() or out.element_size() != 4:
+        raise ValueError("out has the wrong size")
+    if n_failed is None:
+        n_failed = torch.zeros(1, dtype=torch.int64, device=dev)
+    _dev_call("ppk_dist_dev", ref.device, ref._h, qry._h if qry is not None else None, kmers, random_tbl, n_clu,
+              flags, q_begin, q_end, out, n_failed)
     return out, n_failed
 
 
-def _fused_edges(ref, qry, kmers, random_tbl, random_correct, q_begin, q_end, cap, what, launch):
+def _fused_edges(name, ref, qry, kmers, random_tbl, random_correct, q_begin, q_end, cap, *test):
     """The fused kernel-1 edge calls (line boundary / BGMM): capacity guess, exact re-run when it was short.
-    `launch(ref_h, qry_h, kmers_p, tbl_p, n_clu, flags, q_begin, q_end, d_edges, cap, d_n_edges, d_n_failed, stream)`."""
+    `name(ref_h, qry_h, kmers, tbl, n_clu, flags, q_begin, q_end, *test, d_edges, cap, d_n_edges, d_n_failed, stream)`."""
     torch = _torch()
     _check_pair(ref, qry)
     nq = qry.n if qry is not None else ref.n
     q_end = nq if q_end is None else int(q_end)
-    kmers, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
+    kmers, random_tbl, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
     rows = rows_in_band(ref.n, qry.n if qry is not None else 0, q_begin, q_end)
     flags = FLAG_RANDOM_CORRECT if random_correct else 0
     dev = torch.device("cuda:%d" % ref.device)
     if cap is None:
-        cap = min(rows, max(1 << 20, rows // 8))
+        cap = _cap_guess(rows)
     n_failed = torch.zeros(1, dtype=torch.int64, device=dev)
 
-    def call(edges, c, n_edges):
+    def launch(edges, c, n_edges):
         n_failed.zero_()
-        return launch(ref._h, qry._h if qry is not None else None, kmers.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr,
-                      n_clu, flags, q_begin, q_end, C.c_void_p(edges.data_ptr()), c, C.c_void_p(n_edges.data_ptr()),
-                      C.c_void_p(n_failed.data_ptr()), _stream_ptr(ref.device))
-    return _edges_dev(call, what, dev, cap), n_failed
+        _dev_call(name, dev, ref._h, qry._h if qry is not None else None, kmers, random_tbl, n_clu, flags, q_begin,
+                  q_end, *test, edges, c, n_edges, n_failed)
+    return _edges_dev(launch, dev, cap), n_failed
 
 
 def dist_edges(ref, qry=None, kmers=None, random_tbl=None, random_correct=True, slope=2,
@@ -364,18 +391,15 @@ def dist_edges(ref, qry=None, kmers=None, random_tbl=None, random_correct=True, 
 
     The edge count is data dependent: the call runs with a capacity guess and is
     re-run with the exact size only if the guess was too small."""
-    lib = _lib.lib()
-    return _fused_edges(ref, qry, kmers, random_tbl, random_correct, q_begin, q_end, cap, "ppk_dist_edges_dev",
-                        lambda r, q, k, t, nc, fl, qb, qe, e, c, ne, nf, st: lib.ppk_dist_edges_dev(
-                            r, q, k, t, nc, fl, qb, qe, int(slope), float(x_max), float(y_max), float(scale[0]),
-                            float(scale[1]), 1 if inclusive else 0, e, c, ne, nf, st))
+    return _fused_edges("ppk_dist_edges_dev", ref, qry, kmers, random_tbl, random_correct, q_begin, q_end, cap,
+                        int(slope), float(x_max), float(y_max), float(scale[0]), float(scale[1]),
+                        1 if inclusive else 0)
 
 
-def _host_edges(refs, qrys, kmers, random_tbl, random_correct, cap, what, launch):
+def _host_edges(name, refs, qrys, kmers, random_tbl, random_correct, cap, *test):
     """The multi-device host edge calls (line boundary / BGMM): one SketchDB per device (or a single one), a host int64
     [m, 2] array, the parked list fetched when `cap` was too small.
-    `launch(refs_h, qrys_h, n_dev, kmers_p, tbl_p, n_clu, flags, out_p, cap, byref(n_edges), byref(n_failed))`."""
-    lib = _lib.lib()
+    `name(refs_h, qrys_h, n_dev, kmers, tbl, n_clu, flags, *test, out, cap, byref(n_edges), byref(n_failed))`."""
     refs = [refs] if isinstance(refs, SketchDB) else list(refs)
     if qrys is not None:
         qrys = [qrys] if isinstance(qrys, SketchDB) else list(qrys)
@@ -384,24 +408,21 @@ def _host_edges(refs, qrys, kmers, random_tbl, random_correct, cap, what, launch
         for r, q in zip(refs, qrys):
             _check_pair(r, q)
     ref = refs[0]
-    kmers, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
+    kmers, random_tbl, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
     n_qry = qrys[0].n if qrys is not None else 0
     rows = rows_in_band(ref.n, n_qry, 0, n_qry if qrys is not None else ref.n)
     if cap is None:
-        cap = min(rows, max(1 << 20, rows // 8))
+        cap = _cap_guess(rows)
     rh = (C.c_void_p * len(refs))(*[r._h.value for r in refs])
     qh = (C.c_void_p * len(refs))(*[q._h.value for q in qrys]) if qrys is not None else None
-    llp = C.POINTER(C.c_longlong)
     out = np.empty((max(int(cap), 1), 2), dtype=np.int64)
     n_edges = C.c_size_t(0)
     n_failed = C.c_ulonglong(0)
-    rc = launch(rh, qh, len(refs), kmers.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr, n_clu,
-                FLAG_RANDOM_CORRECT if random_correct else 0, out.ctypes.data_as(llp), int(cap), C.byref(n_edges),
-                C.byref(n_failed))
+    rc = _lib.call(name, rh, qh, len(refs), kmers, random_tbl, n_clu, FLAG_RANDOM_CORRECT if random_correct else 0,
+                   *test, out, int(cap), C.byref(n_edges), C.byref(n_failed), accept=(_lib.ERR_CAPACITY,))
     if rc == _lib.ERR_CAPACITY:
         out = np.empty((n_edges.value, 2), dtype=np.int64)
-        rc = lib.ppk_parked_fetch(out.ctypes.data_as(llp), None, None, n_edges.value, None)
-    _lib.check(rc, what)
+        _lib.call("ppk_parked_fetch", out, None, None, n_edges.value, None, what=name)
     return out[:n_edges.value], int(n_failed.value)
 
 
@@ -411,18 +432,12 @@ def edges_host(refs, qrys=None, kmers=None, random_tbl=None, random_correct=True
     every device that holds a copy of the database (`refs` / `qrys`: one SketchDB per device, or a single
     SketchDB), each on its band of rows, one worker thread per device inside the library.
     Returns (edges, n_failed)."""
-    lib = _lib.lib()
-    return _host_edges(refs, qrys, kmers, random_tbl, random_correct, cap, "ppk_query_edges_dbs",
-                       lambda rh, qh, nd, k, t, nc, fl, o, c, ne, nf: lib.ppk_query_edges_dbs(
-                           rh, qh, nd, k, t, nc, fl, int(slope), float(x_max), float(y_max), float(scale[0]),
-                           float(scale[1]), 1 if inclusive else 0, o, c, ne, nf))
+    return _host_edges("ppk_query_edges_dbs", refs, qrys, kmers, random_tbl, random_correct, cap, int(slope),
+                       float(x_max), float(y_max), float(scale[0]), float(scale[1]), 1 if inclusive else 0)
 
 
 def _check_dist_tensor(dist_t):
-    torch = _torch()
-    if not (dist_t.is_cuda and dist_t.dtype == torch.float32 and dist_t.is_contiguous()
-            and dist_t.dim() == 2 and dist_t.shape[1] == 2):
-        raise TypeError("distMat must be a C-contiguous float32 [n,2] CUDA tensor")
+    _check_tensor(dist_t, "distMat must be a C-contiguous float32 [n,2] CUDA tensor", _torch().float32, (None, 2))
 
 
 def bgmm_assign_dev(dist_t, model, labels=True, values=False):
@@ -433,40 +448,38 @@ def bgmm_assign_dev(dist_t, model, labels=True, values=False):
     if not (labels or values):
         raise ValueError("ask for labels, responsibilities or both")
     n = dist_t.shape[0]
-    with torch.cuda.device(dist_t.device):
-        lab = torch.empty(n, dtype=torch.int32, device=dist_t.device) if labels else None
-        resp = torch.empty((n, model.K), dtype=torch.float32, device=dist_t.device) if values else None
-        rc = _lib.lib().ppk_bgmm_assign_dev(C.c_void_p(dist_t.data_ptr()), n, C.byref(model),
-                                            C.c_void_p(lab.data_ptr()) if lab is not None else None,
-                                            C.c_void_p(resp.data_ptr()) if resp is not None else None,
-                                            _stream_ptr(dist_t.device.index))
-        _lib.check(rc, "ppk_bgmm_assign_dev")
+    lab = torch.empty(n, dtype=torch.int32, device=dist_t.device) if labels else None
+    resp = torch.empty((n, model.K), dtype=torch.float32, device=dist_t.device) if values else None
+    _dev_call("ppk_bgmm_assign_dev", dist_t.device, dist_t, n, C.byref(model), lab, resp)
     return lab, resp
 
 
-def _edges_dev(call, what, device, cap):
-    """Run an edge-list call with a capacity guess, once more with the exact size if the guess was short."""
+def _edges_dev(launch, device, cap):
+    """Run an edge-list call, `launch(edges, cap, n_edges)`, with a capacity guess, once more with the exact size if
+    the guess was short."""
     torch = _torch()
-    with torch.cuda.device(device):
-        while True:
-            edges = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=device)
-            n_edges = torch.zeros(1, dtype=torch.int64, device=device)
-            _lib.check(call(edges, cap, n_edges), what)
-            m = int(n_edges.item())
-            if m <= cap:
-                return edges[:m]
-            cap = m
+    while True:
+        edges = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=device)
+        n_edges = torch.zeros(1, dtype=torch.int64, device=device)
+        launch(edges, cap, n_edges)
+        m = int(n_edges.item())
+        if m <= cap:
+            return edges[:m]
+        cap = m
+
+
+def _row_edges_dev(name, dist_t, cap, *test):
+    """The edge list of the rows of a resident [n, 2] matrix that pass a test:
+    `name(dist, n, *test, d_edges, cap, d_n_edges, stream)` through _edges_dev."""
+    _check_dist_tensor(dist_t)
+    n = dist_t.shape[0]
+    return _edges_dev(lambda e, c, ne: _dev_call(name, dist_t.device, dist_t, n, *test, e, c, ne), dist_t.device,
+                      _cap_guess(n) if cap is None else cap)
 
 
 def bgmm_edges_dev(dist_t, model, n_ref=0, int_offset=0, cap=None):
     """Rows labelled model.within_label -> int64 [m,2] edges in generateTuples order (n_ref 0: self)."""
-    _check_dist_tensor(dist_t)
-    n = dist_t.shape[0]
-    if cap is None:
-        cap = min(n, max(1 << 20, n // 8))
-    return _edges_dev(lambda e, c, ne: _lib.lib().ppk_bgmm_edges_dev(
-        C.c_void_p(dist_t.data_ptr()), n, int(n_ref), C.byref(model), int(int_offset), C.c_void_p(e.data_ptr()), c,
-        C.c_void_p(ne.data_ptr()), _stream_ptr(dist_t.device.index)), "ppk_bgmm_edges_dev", dist_t.device, cap)
+    return _row_edges_dev("ppk_bgmm_edges_dev", dist_t, cap, int(n_ref), C.byref(model), int(int_offset))
 
 
 # ---- BGMM fit (include/ppk.h "BGMM fit", DESIGN.md 3.13) --------------------------------------------------------
@@ -474,10 +487,7 @@ def bgmm_fit_params(K, **overrides):
     """`_lib.BgmmFitParams` with fit2dMultiGaussian's values (PopPUNK/bgmm.py:38-43); keyword arguments replace
     fields (`mean_prior` a pair).  ValueError for values outside their ranges (K outside [1, 16], ...)."""
     p = _lib.BgmmFitParams()
-    rc = _lib.lib().ppk_bgmm_fit_params_default(int(K), C.byref(p))
-    if rc == _lib.ERR_ARG:
-        raise ValueError(_lib.last_error())
-    _lib.check(rc, "ppk_bgmm_fit_params_default")
+    _lib.call("ppk_bgmm_fit_params_default", int(K), C.byref(p), arg_error=ValueError)
     for k, v in overrides.items():
         if k == "mean_prior":
             p.mean_prior[0], p.mean_prior[1] = float(v[0]), float(v[1])
@@ -491,24 +501,19 @@ def bgmm_fit_params(K, **overrides):
 
 
 def _fit_scale(scale):
+    """(the two float32 scales, a pointer to them): the array goes to the frame, the pointer to raw library calls
+    (tests make some)."""
     s = np.ascontiguousarray(np.asarray(scale, dtype=np.float32).reshape(2))
     return s, s.ctypes.data_as(C.POINTER(C.c_float))
 
 
 def _check_index_tensor(index_t, dist_t):
-    torch = _torch()
+    """The length of the optional list of training rows (0 without one), after checking it."""
     if index_t is None:
-        return None, 0
-    if not (index_t.is_cuda and index_t.dtype == torch.int64 and index_t.is_contiguous() and index_t.dim() == 1
-            and index_t.device == dist_t.device):
-        raise TypeError("index must be a contiguous int64 [m] CUDA tensor on the matrix's device")
-    return C.c_void_p(index_t.data_ptr()), index_t.shape[0]
-
-
-def _fit_check(rc, what):
-    if rc == _lib.ERR_ARG:
-        raise ValueError(_lib.last_error())
-    _lib.check(rc, what)
+        return 0
+    _check_tensor(index_t, "index must be a contiguous int64 [m] CUDA tensor on the matrix's device", _torch().int64,
+                  dim=1, like=dist_t)
+    return index_t.shape[0]
 
 
 def bgmm_stats_dev(dist_t, state, scale, index_t=None):
@@ -516,13 +521,10 @@ def bgmm_stats_dev(dist_t, state, scale, index_t=None):
     S r, S r dx, S r dy, S r dx dx, S r dx dy, S r dy dy, S r log r about the state's means."""
     torch = _torch()
     _check_dist_tensor(dist_t)
-    ip, ni = _check_index_tensor(index_t, dist_t)
-    s, sp = _fit_scale(scale)
-    with torch.cuda.device(dist_t.device):
-        out = torch.empty((state.K, _lib.BGMM_FIT_STATS), dtype=torch.float64, device=dist_t.device)
-        _fit_check(_lib.lib().ppk_bgmm_stats_dev(C.c_void_p(dist_t.data_ptr()), dist_t.shape[0], ip, ni, sp,
-                                                 C.byref(state), C.c_void_p(out.data_ptr()),
-                                                 _stream_ptr(dist_t.device.index)), "ppk_bgmm_stats_dev")
+    ni = _check_index_tensor(index_t, dist_t)
+    out = torch.empty((state.K, _lib.BGMM_FIT_STATS), dtype=torch.float64, device=dist_t.device)
+    _dev_call("ppk_bgmm_stats_dev", dist_t.device, dist_t, dist_t.shape[0], index_t, ni, _fit_scale(scale)[0],
+              C.byref(state), out, arg_error=ValueError)
     return out
 
 
@@ -532,32 +534,27 @@ def bgmm_kmeans_dev(dist_t, centres, scale, labels_t, index_t=None):
     labels that changed as an int32 CUDA tensor [1])."""
     torch = _torch()
     _check_dist_tensor(dist_t)
-    ip, ni = _check_index_tensor(index_t, dist_t)
+    ni = _check_index_tensor(index_t, dist_t)
     n = ni if index_t is not None else dist_t.shape[0]
-    if not (labels_t.is_cuda and labels_t.dtype == torch.int32 and labels_t.is_contiguous() and labels_t.shape == (n,)):
-        raise TypeError("labels must be a contiguous int32 CUDA tensor with one entry per training row")
+    _check_tensor(labels_t, "labels must be a contiguous int32 CUDA tensor with one entry per training row",
+                  torch.int32, (n,))
     c = np.ascontiguousarray(centres, dtype=np.float64)
     if c.ndim != 2 or c.shape[1] != 2:
         raise ValueError("centres must be [K, 2]")
-    s, sp = _fit_scale(scale)
-    with torch.cuda.device(dist_t.device):
-        out = torch.empty((c.shape[0], _lib.BGMM_FIT_STATS), dtype=torch.float64, device=dist_t.device)
-        changed = torch.zeros(1, dtype=torch.int32, device=dist_t.device)
-        _fit_check(_lib.lib().ppk_bgmm_kmeans_dev(C.c_void_p(dist_t.data_ptr()), dist_t.shape[0], ip, ni, sp, c.shape[0],
-                                                  c.ctypes.data_as(C.POINTER(C.c_double)),
-                                                  C.c_void_p(labels_t.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                  C.c_void_p(changed.data_ptr()), _stream_ptr(dist_t.device.index)),
-                   "ppk_bgmm_kmeans_dev")
+    out = torch.empty((c.shape[0], _lib.BGMM_FIT_STATS), dtype=torch.float64, device=dist_t.device)
+    changed = torch.zeros(1, dtype=torch.int32, device=dist_t.device)
+    _dev_call("ppk_bgmm_kmeans_dev", dist_t.device, dist_t, dist_t.shape[0], index_t, ni, _fit_scale(scale)[0],
+              c.shape[0], c, labels_t, out, changed, arg_error=ValueError)
     return out, changed
 
 
 def _fit_centres(init_centres, params):
     if init_centres is None:
-        return None, None
+        return None
     c = np.ascontiguousarray(init_centres, dtype=np.float64)
     if c.shape != (params.n_init, params.K, 2):
         raise ValueError("init_centres must be [n_init, K, 2]")
-    return c, c.ctypes.data_as(C.POINTER(C.c_double))
+    return c
 
 
 def bgmm_fit_dev(dist_t, scale, params, index_t=None, init_labels_t=None, init_centres=None):
@@ -567,19 +564,15 @@ def bgmm_fit_dev(dist_t, scale, params, index_t=None, init_labels_t=None, init_c
     from . import bgmm
     torch = _torch()
     _check_dist_tensor(dist_t)
-    ip, ni = _check_index_tensor(index_t, dist_t)
+    ni = _check_index_tensor(index_t, dist_t)
     n = ni if index_t is not None else dist_t.shape[0]
-    if init_labels_t is not None and not (init_labels_t.is_cuda and init_labels_t.dtype == torch.int32
-                                          and init_labels_t.is_contiguous() and init_labels_t.shape == (n,)):
-        raise TypeError("init_labels must be a contiguous int32 CUDA tensor with one entry per training row")
-    c, cp = _fit_centres(init_centres, params)
-    s, sp = _fit_scale(scale)
+    if init_labels_t is not None:
+        _check_tensor(init_labels_t, "init_labels must be a contiguous int32 CUDA tensor with one entry per training "
+                      "row", torch.int32, (n,))
+    c = _fit_centres(init_centres, params)
     res = _lib.BgmmFitResult()
-    with torch.cuda.device(dist_t.device):
-        _fit_check(_lib.lib().ppk_bgmm_fit_dev(C.c_void_p(dist_t.data_ptr()), dist_t.shape[0], ip, ni, sp,
-                                               C.c_void_p(init_labels_t.data_ptr()) if init_labels_t is not None else None,
-                                               cp, C.byref(params), C.byref(res), _stream_ptr(dist_t.device.index)),
-                   "ppk_bgmm_fit_dev")
+    _dev_call("ppk_bgmm_fit_dev", dist_t.device, dist_t, dist_t.shape[0], index_t, ni, _fit_scale(scale)[0],
+              init_labels_t, c, C.byref(params), C.byref(res), arg_error=ValueError)
     return bgmm.FitResult(res)
 
 
@@ -594,36 +587,24 @@ def bgmm_fit(X, scale, params, index=None, init_labels=None, init_centres=None, 
     n = X.shape[0] if idx is None else idx.shape[0]
     if lab is not None and lab.shape != (n,):
         raise ValueError("init_labels must have one entry per training row")
-    c, cp = _fit_centres(init_centres, params)
-    s, sp = _fit_scale(scale)
+    c = _fit_centres(init_centres, params)
     res = _lib.BgmmFitResult()
-    _fit_check(_lib.lib().ppk_bgmm_fit(X.ctypes.data_as(C.POINTER(C.c_float)), X.shape[0],
-                                       idx.ctypes.data_as(C.POINTER(C.c_longlong)) if idx is not None else None,
-                                       0 if idx is None else idx.shape[0], sp,
-                                       lab.ctypes.data_as(C.POINTER(C.c_int32)) if lab is not None else None, cp,
-                                       C.byref(params), int(device_id), C.byref(res)), "ppk_bgmm_fit")
+    _lib.call("ppk_bgmm_fit", X, X.shape[0], idx, 0 if idx is None else idx.shape[0], _fit_scale(scale)[0], lab, c,
+              C.byref(params), int(device_id), C.byref(res), arg_error=ValueError)
     return bgmm.FitResult(res)
 
 
 def generate_tuples_dev(assign_t, within_label, self_comparison=True, num_ref=0, int_offset=0, cap=None):
     """poppunk_refine.generateTuples on a resident int32 [n] CUDA tensor -> int64 [m,2]."""
-    torch = _torch()
-    if not (assign_t.is_cuda and assign_t.dtype == torch.int32 and assign_t.is_contiguous()):
-        raise TypeError("assignments must be a contiguous int32 CUDA tensor")
+    _check_tensor(assign_t, "assignments must be a contiguous int32 CUDA tensor", _torch().int32)
     n = assign_t.shape[0]
-    if cap is None:
-        cap = min(n, max(1 << 20, n // 8))
-    return _edges_dev(lambda e, c, ne: _lib.lib().ppk_generate_tuples_dev(
-        C.c_void_p(assign_t.data_ptr()), n, int(within_label), 1 if self_comparison else 0, int(num_ref),
-        int(int_offset), C.c_void_p(e.data_ptr()), c, C.c_void_p(ne.data_ptr()), _stream_ptr(assign_t.device.index)),
-        "ppk_generate_tuples_dev", assign_t.device, cap)
+    return _edges_dev(lambda e, c, ne: _dev_call(
+        "ppk_generate_tuples_dev", assign_t.device, assign_t, n, int(within_label), 1 if self_comparison else 0,
+        int(num_ref), int(int_offset), e, c, ne), assign_t.device, _cap_guess(n) if cap is None else cap)
 
 
 def _check_points_tensor(pts_t):
-    torch = _torch()
-    if not (pts_t.is_cuda and pts_t.dtype == torch.float32 and pts_t.is_contiguous() and pts_t.dim() == 2
-            and pts_t.shape[1] == 2):
-        raise TypeError("points must be a C-contiguous float32 [n,2] CUDA tensor")
+    _check_tensor(pts_t, "points must be a C-contiguous float32 [n,2] CUDA tensor", _torch().float32, (None, 2))
 
 
 def dbscan_core_dev(pts_t, min_samples):
@@ -632,13 +613,8 @@ def dbscan_core_dev(pts_t, min_samples):
     torch = _torch()
     _check_points_tensor(pts_t)
     n = pts_t.shape[0]
-    with torch.cuda.device(pts_t.device):
-        core2 = torch.empty(n, dtype=torch.float64, device=pts_t.device)
-        rc = _lib.lib().ppk_dbscan_core_dev(C.c_void_p(pts_t.data_ptr()), n, int(min_samples),
-                                            C.c_void_p(core2.data_ptr()), _stream_ptr(pts_t.device.index))
-        if rc == _lib.ERR_ARG:
-            raise ValueError(_lib.last_error())
-        _lib.check(rc, "ppk_dbscan_core_dev")
+    core2 = torch.empty(n, dtype=torch.float64, device=pts_t.device)
+    _dev_call("ppk_dbscan_core_dev", pts_t.device, pts_t, n, int(min_samples), core2, arg_error=ValueError)
     return core2
 
 
@@ -648,43 +624,27 @@ def dbscan_mst_dev(pts_t, core2_t):
     torch = _torch()
     _check_points_tensor(pts_t)
     n = pts_t.shape[0]
-    if not (core2_t.is_cuda and core2_t.dtype == torch.float64 and core2_t.is_contiguous() and core2_t.dim() == 1
-            and core2_t.shape[0] == n):
-        raise TypeError("core2 must be a contiguous float64 [n] CUDA tensor")
+    _check_tensor(core2_t, "core2 must be a contiguous float64 [n] CUDA tensor", torch.float64, (n,))
     dev = pts_t.device
-    with torch.cuda.device(dev):
-        a = torch.empty(max(n - 1, 1), dtype=torch.int32, device=dev)
-        b = torch.empty(max(n - 1, 1), dtype=torch.int32, device=dev)
-        w = torch.empty(max(n - 1, 1), dtype=torch.float64, device=dev)
-        rc = _lib.lib().ppk_dbscan_mst_dev(C.c_void_p(pts_t.data_ptr()), C.c_void_p(core2_t.data_ptr()), n,
-                                           C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
-                                           C.c_void_p(w.data_ptr()), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_dbscan_mst_dev")
+    a = torch.empty(max(n - 1, 1), dtype=torch.int32, device=dev)
+    b = torch.empty(max(n - 1, 1), dtype=torch.int32, device=dev)
+    w = torch.empty(max(n - 1, 1), dtype=torch.float64, device=dev)
+    _dev_call("ppk_dbscan_mst_dev", dev, pts_t, core2_t, n, a, b, w)
     return a[:n - 1], b[:n - 1], w[:n - 1]
 
 
 def dbscan_assign_dev(dist_t, handle):
     """DBSCANFit.assign on a resident float32 [n,2] CUDA tensor with a model handle (ppk_dbscan_create): int32 [n]."""
-    torch = _torch()
     _check_dist_tensor(dist_t)
     n = dist_t.shape[0]
-    with torch.cuda.device(dist_t.device):
-        lab = torch.empty(n, dtype=torch.int32, device=dist_t.device)
-        rc = _lib.lib().ppk_dbscan_assign_dev(C.c_void_p(dist_t.data_ptr()), n, handle, C.c_void_p(lab.data_ptr()),
-                                              _stream_ptr(dist_t.device.index))
-        _lib.check(rc, "ppk_dbscan_assign_dev")
+    lab = _torch().empty(n, dtype=_torch().int32, device=dist_t.device)
+    _dev_call("ppk_dbscan_assign_dev", dist_t.device, dist_t, n, handle, lab)
     return lab
 
 
 def dbscan_edges_dev(dist_t, handle, n_ref=0, int_offset=0, cap=None):
     """Rows assigned the model's within-strain label -> int64 [m,2] edges in generateTuples order (n_ref 0: self)."""
-    _check_dist_tensor(dist_t)
-    n = dist_t.shape[0]
-    if cap is None:
-        cap = min(n, max(1 << 20, n // 8))
-    return _edges_dev(lambda e, c, ne: _lib.lib().ppk_dbscan_edges_dev(
-        C.c_void_p(dist_t.data_ptr()), n, int(n_ref), handle, int(int_offset), C.c_void_p(e.data_ptr()), c,
-        C.c_void_p(ne.data_ptr()), _stream_ptr(dist_t.device.index)), "ppk_dbscan_edges_dev", dist_t.device, cap)
+    return _row_edges_dev("ppk_dbscan_edges_dev", dist_t, cap, int(n_ref), handle, int(int_offset))
 
 
 def dist_bgmm_edges(ref, qry=None, kmers=None, random_tbl=None, model=None, random_correct=True, q_begin=0,
@@ -693,85 +653,63 @@ def dist_bgmm_edges(ref, qry=None, kmers=None, random_tbl=None, model=None, rand
     CUDA, n_failed); capacity guess, exact re-run when it was short (as dist_edges)."""
     if model is None:
         raise ValueError("a prepared BGMM model is needed")
-    lib = _lib.lib()
-    return _fused_edges(ref, qry, kmers, random_tbl, random_correct, q_begin, q_end, cap, "ppk_dist_bgmm_edges_dev",
-                        lambda r, q, k, t, nc, fl, qb, qe, e, c, ne, nf, st: lib.ppk_dist_bgmm_edges_dev(
-                            r, q, k, t, nc, fl, qb, qe, C.byref(model), e, c, ne, nf, st))
+    return _fused_edges("ppk_dist_bgmm_edges_dev", ref, qry, kmers, random_tbl, random_correct, q_begin, q_end, cap,
+                        C.byref(model))
 
 
 def bgmm_edges_host(refs, qrys=None, kmers=None, random_tbl=None, model=None, random_correct=True, cap=None):
     """ppk_query_bgmm_edges_dbs: edges_host with the BGMM label test.  Returns (edges int64 [m,2] host, n_failed)."""
     if model is None:
         raise ValueError("a prepared BGMM model is needed")
-    lib = _lib.lib()
-    return _host_edges(refs, qrys, kmers, random_tbl, random_correct, cap, "ppk_query_bgmm_edges_dbs",
-                       lambda rh, qh, nd, k, t, nc, fl, o, c, ne, nf: lib.ppk_query_bgmm_edges_dbs(
-                           rh, qh, nd, k, t, nc, fl, C.byref(model), o, c, ne, nf))
+    return _host_edges("ppk_query_bgmm_edges_dbs", refs, qrys, kmers, random_tbl, random_correct, cap,
+                       C.byref(model))
 
 
 def assign_threshold_dev(dist_t, slope, x_max, y_max, out=None):
     """poppunk_refine.assignThreshold on a resident float32 [n,2] CUDA tensor."""
-    torch = _torch()
     _check_dist_tensor(dist_t)
     n = dist_t.shape[0]
-    with torch.cuda.device(dist_t.device):
-        if out is None:
-            out = torch.empty(n, dtype=torch.float32, device=dist_t.device)
-        rc = _lib.lib().ppk_assign_threshold_dev(C.c_void_p(dist_t.data_ptr()), n, int(slope),
-                                                 float(x_max), float(y_max),
-                                                 C.c_void_p(out.data_ptr()),
-                                                 _stream_ptr(dist_t.device.index))
-        _lib.check(rc, "ppk_assign_threshold_dev")
+    if out is None:
+        out = _torch().empty(n, dtype=_torch().float32, device=dist_t.device)
+    _dev_call("ppk_assign_threshold_dev", dist_t.device, dist_t, n, int(slope), float(x_max), float(y_max), out)
     return out
 
 
 def edge_threshold_dev(dist_t, slope, x_max, y_max, n_ref=0, inclusive=True, cap=None):
     """poppunk_refine.edgeThreshold on a resident float32 [n,2] CUDA tensor -> int64 [m,2]."""
-    _check_dist_tensor(dist_t)
-    n = dist_t.shape[0]
-    if cap is None:
-        cap = min(n, max(1 << 20, n // 8))
-    return _edges_dev(lambda e, c, ne: _lib.lib().ppk_edge_threshold_dev(
-        C.c_void_p(dist_t.data_ptr()), n, int(n_ref), int(slope), float(x_max), float(y_max), 1 if inclusive else 0,
-        C.c_void_p(e.data_ptr()), c, C.c_void_p(ne.data_ptr()), _stream_ptr(dist_t.device.index)),
-        "ppk_edge_threshold_dev", dist_t.device, cap)
+    return _row_edges_dev("ppk_edge_threshold_dev", dist_t, cap, int(n_ref), int(slope), float(x_max), float(y_max),
+                          1 if inclusive else 0)
 
 
 def qc_edges_dev(dist_t, max_pi_dist, max_a_dist, n_ref=0, zero=False, cap=None):
     """qcDistMat's outlier edge lists on a resident float32 [n,2] CUDA tensor
     (PopPUNK/qc.py:332-337 long distances; :349-354 zero distances) -> int64 [m,2]."""
-    _check_dist_tensor(dist_t)
-    n = dist_t.shape[0]
-    if cap is None:
-        cap = min(n, max(1 << 20, n // 8))
-    return _edges_dev(lambda e, c, ne: _lib.lib().ppk_qc_edges_dev(
-        C.c_void_p(dist_t.data_ptr()), n, int(n_ref), 1 if zero else 0, float(max_pi_dist), float(max_a_dist),
-        C.c_void_p(e.data_ptr()), c, C.c_void_p(ne.data_ptr()), _stream_ptr(dist_t.device.index)),
-        "ppk_qc_edges_dev", dist_t.device, cap)
+    return _row_edges_dev("ppk_qc_edges_dev", dist_t, cap, int(n_ref), 1 if zero else 0, float(max_pi_dist),
+                          float(max_a_dist))
+
+
+def _sweep_dev(launch, device, cap):
+    """Run a boundary-sweep call, `launch(d_i, d_j, d_offset_idx, cap, d_n_out)`, with a capacity guess, once more
+    with the exact size if the guess was short.  Returns the (i, j, offset_idx) int64 CUDA tensors."""
+    torch = _torch()
+    while True:
+        buf = torch.empty((3, max(cap, 1)), dtype=torch.int64, device=device)
+        n_out = torch.zeros(1, dtype=torch.int64, device=device)
+        launch(buf[0], buf[1], buf[2], cap, n_out)
+        m = int(n_out.item())
+        if m <= cap:
+            return buf[0, :m], buf[1, :m], buf[2, :m]
+        cap = m
 
 
 def threshold_iterate_1d_dev(dist_t, offsets, slope, x0, y0, x1, y1, cap=None):
     """poppunk_refine.thresholdIterate1D on a resident float32 [n,2] CUDA tensor ->
     (i, j, offset_idx) int64 CUDA tensors (src/boundary.cpp:154-210)."""
-    torch = _torch()
     off = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
     n = dist_t.shape[0]
-    if cap is None:
-        cap = min(n, max(1 << 20, n // 8))
-    with torch.cuda.device(dist_t.device):
-        while True:
-            buf = torch.empty((3, max(cap, 1)), dtype=torch.int64, device=dist_t.device)
-            n_out = torch.zeros(1, dtype=torch.int64, device=dist_t.device)
-            rc = _lib.lib().ppk_threshold_iterate_1d_dev(
-                C.c_void_p(dist_t.data_ptr()), n, off.ctypes.data_as(C.POINTER(C.c_double)), off.size,
-                int(slope), float(x0), float(y0), float(x1), float(y1), C.c_void_p(buf[0].data_ptr()),
-                C.c_void_p(buf[1].data_ptr()), C.c_void_p(buf[2].data_ptr()), cap,
-                C.c_void_p(n_out.data_ptr()), _stream_ptr(dist_t.device.index))
-            _lib.check(rc, "ppk_threshold_iterate_1d_dev")
-            m = int(n_out.item())
-            if m <= cap:
-                return buf[0, :m], buf[1, :m], buf[2, :m]
-            cap = m
+    return _sweep_dev(lambda i, j, o, c, n_out: _dev_call(
+        "ppk_threshold_iterate_1d_dev", dist_t.device, dist_t, n, off, off.size, int(slope), float(x0), float(y0),
+        float(x1), float(y1), i, j, o, c, n_out), dist_t.device, _cap_guess(n) if cap is None else cap)
 
 
 def threshold_iterate_2d_dev(dist_t, x_max, y_max, cap=None):
@@ -779,27 +717,13 @@ def threshold_iterate_2d_dev(dist_t, x_max, y_max, cap=None):
     (i, j, offset_idx) int64 CUDA tensors (src/boundary.cpp:212-237).  refine's 2-D mode calls it
     once per y value on the same matrix (PopPUNK/refine.py:587-593): resident, the 400 MB matrix is
     not re-sent for every y."""
-    torch = _torch()
     xm = np.ascontiguousarray(x_max, dtype=np.float32).ravel()
     if xm.size > 1 and np.any(np.diff(xm) < 0):
         raise RuntimeError("x_max range to thresholdIterate2D must be sorted")
     n = dist_t.shape[0]
-    if cap is None:
-        cap = min(n, max(1 << 20, n // 8))
-    with torch.cuda.device(dist_t.device):
-        while True:
-            buf = torch.empty((3, max(cap, 1)), dtype=torch.int64, device=dist_t.device)
-            n_out = torch.zeros(1, dtype=torch.int64, device=dist_t.device)
-            rc = _lib.lib().ppk_threshold_iterate_2d_dev(
-                C.c_void_p(dist_t.data_ptr()), n, xm.ctypes.data_as(C.POINTER(C.c_float)), xm.size,
-                float(y_max), C.c_void_p(buf[0].data_ptr()), C.c_void_p(buf[1].data_ptr()),
-                C.c_void_p(buf[2].data_ptr()), cap, C.c_void_p(n_out.data_ptr()),
-                _stream_ptr(dist_t.device.index))
-            _lib.check(rc, "ppk_threshold_iterate_2d_dev")
-            m = int(n_out.item())
-            if m <= cap:
-                return buf[0, :m], buf[1, :m], buf[2, :m]
-            cap = m
+    return _sweep_dev(lambda i, j, o, c, n_out: _dev_call(
+        "ppk_threshold_iterate_2d_dev", dist_t.device, dist_t, n, xm, xm.size, float(y_max), i, j, o, c, n_out),
+        dist_t.device, _cap_guess(n) if cap is None else cap)
 
 
 def _edge_stream(i_t, j_t, off_t):
@@ -807,8 +731,7 @@ def _edge_stream(i_t, j_t, off_t):
     torch = _torch()
     m = int(i_t.shape[0])
     for t in (i_t, j_t) + ((off_t,) if off_t is not None else ()):
-        if not (t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.shape[0] == m):
-            raise TypeError("edge arrays must be int64 CUDA tensors of one length")
+        _check_tensor(t, "edge arrays must be int64 CUDA tensors of one length", torch.int64, (m,), contiguous=False)
     stride = i_t.stride(0) if m > 1 else 1
     if (m > 1 and j_t.stride(0) != stride) or stride not in (1, 2):
         raise TypeError("edge arrays must be contiguous, or the two columns of a contiguous [m, 2] tensor")
@@ -827,26 +750,29 @@ def network_sweep_dev(i_t, j_t, off_t, n, n_off, labels_at=None):
     m, stride = _edge_stream(i_t, j_t, off_t)
     la = -1 if labels_at is None else int(labels_at)
     dev = i_t.device
-    with torch.cuda.device(dev):
-        stats = torch.empty((max(int(n_off), 1), 4), dtype=torch.int64, device=dev)
-        labels = torch.empty(max(int(n), 1), dtype=torch.int32, device=dev) if la >= 0 else None
-        rc = _lib.lib().ppk_network_sweep_dev(
-            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride,
-            C.c_void_p(off_t.data_ptr()) if off_t is not None else None, m, int(n), int(n_off), la,
-            C.c_void_p(stats.data_ptr()), C.c_void_p(labels.data_ptr()) if labels is not None else None,
-            _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_network_sweep_dev")
+    stats = torch.empty((max(int(n_off), 1), 4), dtype=torch.int64, device=dev)
+    labels = torch.empty(max(int(n), 1), dtype=torch.int32, device=dev) if la >= 0 else None
+    _dev_call("ppk_network_sweep_dev", dev, i_t, j_t, stride, off_t, m, int(n), int(n_off), la, stats, labels)
     return stats, (labels[:int(n)] if labels is not None else None)
+
+
+_EDGES = "edges must be a contiguous int64 [m, 2] CUDA tensor"
+_EDGES_OR_PAIR = _EDGES + ", or an (i, j) pair of int64 tensors"      # (what mst_dev and its kin have always said)
+
+
+def _edge_cols(edges_t, message=_EDGES, pair=False):
+    """(i_t, j_t): the two columns of a contiguous int64 [m, 2] CUDA edge list, read in place -- or, where the
+    wrapper takes one (`pair`), the (i_t, j_t) pair itself, as network_sweep_dev takes it.  _edge_stream checks them."""
+    if pair and isinstance(edges_t, (tuple, list)):
+        return edges_t[0], edges_t[1]
+    _check_tensor(edges_t, message, _torch().int64, (None, 2))
+    return edges_t[:, 0], edges_t[:, 1]
 
 
 def network_stats_dev(edges_t, n, labels=False):
     """network_sweep_dev of one int64 [m, 2] CUDA edge list (edge_threshold_dev, dist_edges, ...), read in place.
     Returns (stats int64 [4], labels int32 [n] or None)."""
-    torch = _torch()
-    if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
-            and edges_t.is_contiguous()):
-        raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
-    stats, lab = network_sweep_dev(edges_t[:, 0], edges_t[:, 1], None, n, 1, 0 if labels else None)
+    stats, lab = network_sweep_dev(*_edge_cols(edges_t), None, n, 1, 0 if labels else None)
     return stats[0], lab
 
 
@@ -859,44 +785,27 @@ def cluster_sweep_dev(i_t, j_t, off_t, n, n_off):
     m, stride = _edge_stream(i_t, j_t, off_t)
     dev = i_t.device
     n, n_off = int(n), int(n_off)
-    with torch.cuda.device(dev):
-        clusters = torch.empty((max(n_off, 1), max(n, 1)), dtype=torch.int32, device=dev)
-        counts = torch.empty(max(n_off, 1), dtype=torch.int32, device=dev)
-        if n != max(n, 1):                  # n == 0: a [n_off, 0] result over storage of its own
-            clusters = clusters[:, :0]
-        rc = _lib.lib().ppk_cluster_sweep_dev(
-            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride,
-            C.c_void_p(off_t.data_ptr()) if off_t is not None else None, m, n, n_off,
-            C.c_void_p(clusters.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_cluster_sweep_dev")
+    clusters = torch.empty((max(n_off, 1), max(n, 1)), dtype=torch.int32, device=dev)
+    counts = torch.empty(max(n_off, 1), dtype=torch.int32, device=dev)
+    if n != max(n, 1):                  # n == 0: a [n_off, 0] result over storage of its own
+        clusters = clusters[:, :0]
+    _dev_call("ppk_cluster_sweep_dev", dev, i_t, j_t, stride, off_t, m, n, n_off, clusters, counts)
     return clusters, counts
 
 
 def cluster_numbers_dev(edges_t, n):
     """cluster_sweep_dev of one int64 [m, 2] CUDA edge list, read in place -> (numbers int32 [n] CUDA, the count)."""
-    torch = _torch()
-    if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
-            and edges_t.is_contiguous()):
-        raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
-    clusters, counts = cluster_sweep_dev(edges_t[:, 0], edges_t[:, 1], None, n, 1)
+    clusters, counts = cluster_sweep_dev(*_edge_cols(edges_t), None, n, 1)
     return clusters[0], int(counts[0].item())
 
 
 def _assign_args(edges_t, ref_label_t):
     """(i_t, j_t, m, stride) of the query-vs-reference edge stream after checking it and the int32 label tensor.
     edges_t: a contiguous int64 [m, 2] CUDA tensor, or an (i_t, j_t) pair as network_sweep_dev takes it."""
-    torch = _torch()
-    if isinstance(edges_t, (tuple, list)):
-        i_t, j_t = edges_t
-    else:
-        if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
-                and edges_t.is_contiguous()):
-            raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
-        i_t, j_t = edges_t[:, 0], edges_t[:, 1]
+    i_t, j_t = _edge_cols(edges_t, pair=True)
     m, stride = _edge_stream(i_t, j_t, None)
-    if not (ref_label_t.is_cuda and ref_label_t.dtype == torch.int32 and ref_label_t.dim() == 1
-            and ref_label_t.is_contiguous() and ref_label_t.device == i_t.device):
-        raise TypeError("ref_label must be a contiguous int32 CUDA tensor on the edges' device")
+    _check_tensor(ref_label_t, "ref_label must be a contiguous int32 CUDA tensor on the edges' device",
+                  _torch().int32, dim=1, like=i_t)
     return i_t, j_t, m, stride
 
 
@@ -920,15 +829,11 @@ def query_links_dev(edges_t, ref_label_t, n_qry, max_links=8):
     dev = i_t.device
     n_ref, n_qry, max_links = int(ref_label_t.shape[0]), int(n_qry), int(max_links)
     check_assign_sizes("ppk_query_links", n_ref, n_qry, max_links)
-    with torch.cuda.device(dev):
-        degree = torch.empty(max(n_qry, 1), dtype=torch.int32, device=dev)
-        n_links = torch.empty(max(n_qry, 1), dtype=torch.int32, device=dev)
-        links = torch.empty((max(n_qry, 1), max_links), dtype=torch.int32, device=dev)
-        rc = _lib.lib().ppk_query_links_dev(
-            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride, m, C.c_void_p(ref_label_t.data_ptr()),
-            n_ref, n_qry, max_links, C.c_void_p(degree.data_ptr()), C.c_void_p(n_links.data_ptr()),
-            C.c_void_p(links.data_ptr()), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_query_links_dev")
+    degree = torch.empty(max(n_qry, 1), dtype=torch.int32, device=dev)
+    n_links = torch.empty(max(n_qry, 1), dtype=torch.int32, device=dev)
+    links = torch.empty((max(n_qry, 1), max_links), dtype=torch.int32, device=dev)
+    _dev_call("ppk_query_links_dev", dev, i_t, j_t, stride, m, ref_label_t, n_ref, n_qry, max_links, degree, n_links,
+              links)
     return degree[:n_qry], n_links[:n_qry], links[:n_qry]
 
 
@@ -943,13 +848,9 @@ def cluster_extend_dev(edges_t, ref_label_t, n_qry):
     dev = i_t.device
     n_ref, n_qry = int(ref_label_t.shape[0]), int(n_qry)
     check_assign_sizes("ppk_cluster_extend", n_ref, n_qry)
-    with torch.cuda.device(dev):
-        numbers = torch.empty(max(n_ref + n_qry, 1), dtype=torch.int32, device=dev)
-        count = torch.empty(1, dtype=torch.int32, device=dev)
-        rc = _lib.lib().ppk_cluster_extend_dev(
-            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride, m, C.c_void_p(ref_label_t.data_ptr()),
-            n_ref, n_qry, C.c_void_p(numbers.data_ptr()), C.c_void_p(count.data_ptr()), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_cluster_extend_dev")
+    numbers = torch.empty(max(n_ref + n_qry, 1), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    _dev_call("ppk_cluster_extend_dev", dev, i_t, j_t, stride, m, ref_label_t, n_ref, n_qry, numbers, count)
     return numbers[:n_ref + n_qry], int(count.item())
 
 
@@ -964,13 +865,7 @@ def pick_references_dev(edges_t, n, existing=None, merged=None, fast=False):
     existing, merged: uint8 / bool CUDA tensors of n flags, or None.  Returns (is_ref uint8 [n] CUDA, ref_edges int64
     [k, 2] CUDA: the edges among references in stream order, renumbered by rank, counts: a dict of REFS_COUNT_NAMES)."""
     torch = _torch()
-    if isinstance(edges_t, (tuple, list)):
-        i_t, j_t = edges_t
-    else:
-        if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
-                and edges_t.is_contiguous()):
-            raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
-        i_t, j_t = edges_t[:, 0], edges_t[:, 1]
+    i_t, j_t = _edge_cols(edges_t, pair=True)
     m, stride = _edge_stream(i_t, j_t, None)
     dev = i_t.device
     n = int(n)
@@ -979,22 +874,15 @@ def pick_references_dev(edges_t, n, existing=None, merged=None, fast=False):
     flags = []
     for name, f in (("existing", existing), ("merged", merged)):
         if f is not None:
-            if not (f.is_cuda and f.device == dev and f.dim() == 1 and f.shape[0] == n
-                    and f.dtype in (torch.uint8, torch.bool)):
-                raise TypeError("%s must be a uint8 or bool CUDA tensor of n flags on the edges' device" % name)
+            _check_tensor(f, "%s must be a uint8 or bool CUDA tensor of n flags on the edges' device" % name,
+                          (torch.uint8, torch.bool), (n,), like=i_t, contiguous=False)
             f = f.contiguous().view(torch.uint8)
         flags.append(f)
-    with torch.cuda.device(dev):
-        is_ref = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        ref_edges = torch.empty((max(m, 1), 2), dtype=torch.int64, device=dev)
-        counts = torch.empty(8, dtype=torch.int64, device=dev)
-        rc = _lib.lib().ppk_pick_refs_dev(
-            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride, m, n,
-            C.c_void_p(flags[0].data_ptr()) if flags[0] is not None else None,
-            C.c_void_p(flags[1].data_ptr()) if flags[1] is not None else None, 1 if fast else 0,
-            C.c_void_p(is_ref.data_ptr()), C.c_void_p(ref_edges.data_ptr()), C.c_void_p(counts.data_ptr()),
-            _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_pick_refs_dev")
+    is_ref = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    ref_edges = torch.empty((max(m, 1), 2), dtype=torch.int64, device=dev)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    _dev_call("ppk_pick_refs_dev", dev, i_t, j_t, stride, m, n, flags[0], flags[1], 1 if fast else 0, is_ref,
+              ref_edges, counts)
     c = dict(zip(REFS_COUNT_NAMES, counts.cpu().tolist()))
     return is_ref[:n], ref_edges[:c["reference_edges"]], c
 
@@ -1017,13 +905,8 @@ def pick_references(edges, n, existing=None, merged=None, fast=False, device=0):
     is_ref = np.zeros(max(n, 1), dtype=np.uint8)
     ref_edges = np.zeros((max(m, 1), 2), dtype=np.int64)
     counts = np.zeros(8, dtype=np.int64)
-    llp, bp = C.POINTER(C.c_longlong), C.POINTER(C.c_uint8)
-    rc = _lib.lib().ppk_pick_refs(i.ctypes.data_as(llp), j.ctypes.data_as(llp), m, n,
-                                  flags[0].ctypes.data_as(bp) if flags[0] is not None else None,
-                                  flags[1].ctypes.data_as(bp) if flags[1] is not None else None, 1 if fast else 0,
-                                  int(device), is_ref.ctypes.data_as(bp), ref_edges.ctypes.data_as(llp),
-                                  counts.ctypes.data_as(llp))
-    _lib.check(rc, "ppk_pick_refs")
+    _lib.call("ppk_pick_refs", i, j, m, n, flags[0], flags[1], 1 if fast else 0, int(device), is_ref, ref_edges,
+              counts)
     c = dict(zip(REFS_COUNT_NAMES, counts.tolist()))
     return is_ref[:n], ref_edges[:c["reference_edges"]], c
 
@@ -1040,15 +923,11 @@ def nearest_reference_dev(dist_t, n_qry, n_ref, dist_col=0):
     if dist_t.shape[0] != n_qry * n_ref:
         raise ValueError("the matrix must have n_qry * n_ref rows")
     dev = dist_t.device
-    with torch.cuda.device(dev):
-        oi = torch.empty(max(n_qry, 1), dtype=torch.int64, device=dev)
-        oj = torch.zeros(max(n_qry, 1), dtype=torch.int64, device=dev)
-        od = torch.empty(max(n_qry, 1), dtype=torch.float32, device=dev)
-        if n_qry and n_ref:
-            rc = _lib.lib().ppk_knn_rect_dev(C.c_void_p(dist_t.data_ptr()), 2, int(dist_col), n_qry, n_ref, 0, 1,
-                                             C.c_void_p(oi.data_ptr()), C.c_void_p(oj.data_ptr()),
-                                             C.c_void_p(od.data_ptr()), _stream_ptr(dev.index))
-            _lib.check(rc, "ppk_knn_rect_dev")
+    oi = torch.empty(max(n_qry, 1), dtype=torch.int64, device=dev)
+    oj = torch.zeros(max(n_qry, 1), dtype=torch.int64, device=dev)
+    od = torch.empty(max(n_qry, 1), dtype=torch.float32, device=dev)
+    if n_qry and n_ref:
+        _dev_call("ppk_knn_rect_dev", dev, dist_t, 2, int(dist_col), n_qry, n_ref, 0, 1, oi, oj, od)
     return oj[:n_qry]
 
 
@@ -1068,23 +947,24 @@ def cluster_pair_sums_dev(dist_t, levels_t, col=0, shift=None):
     cluster.  Returns (sum, cnt) int64 [n_levels, n + 1] CUDA and the shift.  Nesting is the caller's precondition
     (iterate.check_nested)."""
     torch = _torch()
+    n_rows, n, n_levels = _condensed_and_levels(dist_t, levels_t)
+    if shift is None:
+        shift = pair_sum_shift(n_rows)
+    out = torch.empty((2, max(n_levels, 1), n + 1), dtype=torch.int64, device=dist_t.device)
+    _dev_call("ppk_cluster_pair_sums_dev", dist_t.device, dist_t, n_rows, int(col), levels_t, n_levels, int(shift),
+              out[0], out[1])
+    return out[0], out[1], int(shift)
+
+
+def _condensed_and_levels(dist_t, levels_t):
+    """(rows, samples, levels) of a resident condensed [n(n-1)/2, 2] matrix and the int32 [n_levels, n] cluster
+    numbers that go with it, after checking both."""
     _check_dist_tensor(dist_t)
     n_rows = int(dist_t.shape[0])
     n = _samples_of(n_rows)
-    if not (levels_t.is_cuda and levels_t.dtype == torch.int32 and levels_t.dim() == 2 and levels_t.is_contiguous()
-            and levels_t.shape[1] == n and levels_t.device == dist_t.device):
-        raise TypeError("levels must be a contiguous int32 [n_levels, %d] CUDA tensor on the matrix's device" % n)
-    if shift is None:
-        shift = pair_sum_shift(n_rows)
-    n_levels = int(levels_t.shape[0])
-    dev = dist_t.device
-    with torch.cuda.device(dev):
-        out = torch.empty((2, max(n_levels, 1), n + 1), dtype=torch.int64, device=dev)
-        rc = _lib.lib().ppk_cluster_pair_sums_dev(
-            C.c_void_p(dist_t.data_ptr()), n_rows, int(col), C.c_void_p(levels_t.data_ptr()), n_levels, int(shift),
-            C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_cluster_pair_sums_dev")
-    return out[0], out[1], int(shift)
+    _check_tensor(levels_t, "levels must be a contiguous int32 [n_levels, %d] CUDA tensor on the matrix's device" % n,
+                  _torch().int32, (None, n), like=dist_t)
+    return n_rows, n, int(levels_t.shape[0])
 
 
 def silhouette_shift(n):
@@ -1104,25 +984,14 @@ def silhouette_dev(dist_t, levels_t, metric=2, shift=None, want_ab=False):
     [n_levels]) as CUDA tensors -- the rows of an invalid level (fewer than 2 or more than n - 1 labels) are NaN -- and
     with want_ab the mean distances (a, b) float64 [n_levels, n] as a fourth and fifth item."""
     torch = _torch()
-    _check_dist_tensor(dist_t)
-    n_rows = int(dist_t.shape[0])
-    n = _samples_of(n_rows)
-    if not (levels_t.is_cuda and levels_t.dtype == torch.int32 and levels_t.dim() == 2 and levels_t.is_contiguous()
-            and levels_t.shape[1] == n and levels_t.device == dist_t.device):
-        raise TypeError("levels must be a contiguous int32 [n_levels, %d] CUDA tensor on the matrix's device" % n)
+    n_rows, n, n_levels = _condensed_and_levels(dist_t, levels_t)
     if shift is None:
         shift = silhouette_shift(n)
-    n_levels = int(levels_t.shape[0])
     dev = dist_t.device
-    with torch.cuda.device(dev):
-        out = torch.empty((3 if want_ab else 1, max(n_levels, 1), n), dtype=torch.float64, device=dev)
-        counts = torch.empty((2, max(n_levels, 1)), dtype=torch.int32, device=dev)
-        rc = _lib.lib().ppk_silhouette_dev(
-            C.c_void_p(dist_t.data_ptr()), n_rows, int(metric), C.c_void_p(levels_t.data_ptr()), n_levels, int(shift),
-            C.c_void_p(out[1].data_ptr()) if want_ab else None, C.c_void_p(out[2].data_ptr()) if want_ab else None,
-            C.c_void_p(out[0].data_ptr()), C.c_void_p(counts[0].data_ptr()), C.c_void_p(counts[1].data_ptr()),
-            _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_silhouette_dev")
+    out = torch.empty((3 if want_ab else 1, max(n_levels, 1), n), dtype=torch.float64, device=dev)
+    counts = torch.empty((2, max(n_levels, 1)), dtype=torch.int32, device=dev)
+    _dev_call("ppk_silhouette_dev", dev, dist_t, n_rows, int(metric), levels_t, n_levels, int(shift),
+              out[1] if want_ab else None, out[2] if want_ab else None, out[0], counts[0], counts[1])
     if want_ab:
         return out[0], counts[0], counts[1], out[1], out[2]
     return out[0], counts[0], counts[1]
@@ -1138,8 +1007,7 @@ def contingency_sums_dev(levels_a, levels_b=None):
     torch = _torch()
 
     def check(t, what):
-        if not (t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.is_contiguous()):
-            raise TypeError("%s must be a contiguous int32 [n_levels, n] CUDA tensor" % what)
+        _check_tensor(t, "%s must be a contiguous int32 [n_levels, n] CUDA tensor" % what, torch.int32, dim=2)
 
     check(levels_a, "levels_a")
     n_a, n = int(levels_a.shape[0]), int(levels_a.shape[1])
@@ -1150,16 +1018,11 @@ def contingency_sums_dev(levels_a, levels_b=None):
             raise TypeError("levels_b must have levels_a's %d samples and live on its device" % n)
         n_b = int(levels_b.shape[0])
     dev = levels_a.device
-    with torch.cuda.device(dev):
-        sq = [torch.empty(max(k, 1), dtype=torch.int64, device=dev) for k in (n_a, n_b)]
-        labels = [torch.empty(max(k, 1), dtype=torch.int32, device=dev) for k in (n_a, n_b)]
-        cells = torch.empty((2, max(n_a, 1), max(n_b, 1)), dtype=torch.int64, device=dev)
-        rc = _lib.lib().ppk_contingency_sums_dev(
-            C.c_void_p(levels_a.data_ptr()), n_a, None if levels_b is None else C.c_void_p(levels_b.data_ptr()), n_b, n,
-            C.c_void_p(sq[0].data_ptr()), C.c_void_p(sq[1].data_ptr()), C.c_void_p(labels[0].data_ptr()),
-            C.c_void_p(labels[1].data_ptr()), C.c_void_p(cells[0].data_ptr()), C.c_void_p(cells[1].data_ptr()),
-            _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_contingency_sums_dev")
+    sq = [torch.empty(max(k, 1), dtype=torch.int64, device=dev) for k in (n_a, n_b)]
+    labels = [torch.empty(max(k, 1), dtype=torch.int32, device=dev) for k in (n_a, n_b)]
+    cells = torch.empty((2, max(n_a, 1), max(n_b, 1)), dtype=torch.int64, device=dev)
+    _dev_call("ppk_contingency_sums_dev", dev, levels_a, n_a, levels_b, n_b, n, sq[0], sq[1], labels[0], labels[1],
+              cells[0], cells[1])
     return sq[0][:n_a], sq[1][:n_b], labels[0][:n_a], labels[1][:n_b], cells[0][:n_a, :n_b], cells[1][:n_a, :n_b]
 
 
@@ -1171,8 +1034,23 @@ def sketch_dev(codes_t, seq_off, kmers, sketchsize64, bbits=14, strand_preserved
     A, C, G, T counts, filled int32 [n, nk] = non-empty bins before empty ones were filled).  [EXT] The rule is this
     project's own: sketches made here do not match those of pp-sketchlib."""
     torch = _torch()
-    if not (codes_t.is_cuda and codes_t.dtype == torch.uint8 and codes_t.dim() == 1 and codes_t.is_contiguous()):
-        raise TypeError("codes_t must be a contiguous one-dimensional uint8 CUDA tensor")
+    dev, off_t, n, k, nk, words = _sketch_args(codes_t, seq_off, kmers, sketchsize64, bbits)
+    sketches = torch.zeros((n, nk, max(words, 0)), dtype=torch.int64, device=dev)
+    stats = torch.zeros((n, 6), dtype=torch.int64, device=dev)
+    filled = torch.zeros((n, nk), dtype=torch.int32, device=dev)
+    # an empty tensor has address 0 and NULL is an error to the library: it gets the offsets' address (never used)
+    _dev_call("ppk_sketch_dev", dev, C.c_void_p(codes_t.data_ptr() if codes_t.numel() else off_t.data_ptr()), off_t,
+              n, k, nk, int(sketchsize64), int(bbits), _lib.SKETCH_STRAND_PRESERVED if strand_preserved else 0,
+              C.c_void_p(sketches.data_ptr() or off_t.data_ptr()), C.c_void_p(stats.data_ptr() or off_t.data_ptr()),
+              C.c_void_p(filled.data_ptr() or off_t.data_ptr()))
+    return sketches, stats, filled
+
+
+def _sketch_args(codes_t, seq_off, kmers, sketchsize64, bbits):
+    """(device, offsets int64 CUDA [n + 1], n, k-mer lengths int32, nk, words a sketch) of the two sketch calls, after
+    checking the codes and the offsets."""
+    torch = _torch()
+    _check_tensor(codes_t, "codes_t must be a contiguous one-dimensional uint8 CUDA tensor", torch.uint8, dim=1)
     dev = codes_t.device
     if hasattr(seq_off, "is_cuda"):
         off_t = seq_off.to(device=dev, dtype=torch.int64).contiguous()
@@ -1184,19 +1062,7 @@ def sketch_dev(codes_t, seq_off, kmers, sketchsize64, bbits=14, strand_preserved
     if n > 0 and not hasattr(seq_off, "is_cuda") and int(np.asarray(seq_off).ravel()[-1]) > int(codes_t.numel()):
         raise ValueError("seq_off ends beyond codes_t")
     k = np.ascontiguousarray(kmers, dtype=np.int32).ravel()
-    nk, words = int(k.size), int(sketchsize64) * int(bbits)
-    with torch.cuda.device(dev):
-        sketches = torch.zeros((n, nk, max(words, 0)), dtype=torch.int64, device=dev)
-        stats = torch.zeros((n, 6), dtype=torch.int64, device=dev)
-        filled = torch.zeros((n, nk), dtype=torch.int32, device=dev)
-        rc = _lib.lib().ppk_sketch_dev(
-            C.c_void_p(codes_t.data_ptr() if codes_t.numel() else off_t.data_ptr()), C.c_void_p(off_t.data_ptr()), n,
-            k.ctypes.data_as(C.POINTER(C.c_int32)), nk, int(sketchsize64), int(bbits),
-            _lib.SKETCH_STRAND_PRESERVED if strand_preserved else 0, C.c_void_p(sketches.data_ptr() or off_t.data_ptr()),
-            C.c_void_p(stats.data_ptr() or off_t.data_ptr()), C.c_void_p(filled.data_ptr() or off_t.data_ptr()),
-            _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_sketch_dev")
-    return sketches, stats, filled
+    return dev, off_t, n, k, int(k.size), int(sketchsize64) * int(bbits)
 
 
 def sketch_reads_dev(codes_t, seq_off, kmers, sketchsize64, min_count, exact=False, bbits=14, strand_preserved=False):
@@ -1206,33 +1072,17 @@ def sketch_reads_dev(codes_t, seq_off, kmers, sketchsize64, min_count, exact=Fal
     Returns CUDA tensors (sketches, stats, filled, kstats int64 [n, nk, 4] = occ, adm_occ, filled, win_occ);
     stats[:, 0] is the estimate of the distinct admitted k-mers at the largest k."""
     torch = _torch()
-    if not (codes_t.is_cuda and codes_t.dtype == torch.uint8 and codes_t.dim() == 1 and codes_t.is_contiguous()):
-        raise TypeError("codes_t must be a contiguous one-dimensional uint8 CUDA tensor")
-    dev = codes_t.device
-    if hasattr(seq_off, "is_cuda"):
-        off_t = seq_off.to(device=dev, dtype=torch.int64).contiguous()
-    else:
-        off_t = torch.as_tensor(np.ascontiguousarray(seq_off, dtype=np.int64), device=dev)
-    if off_t.dim() != 1 or off_t.numel() < 1:
-        raise ValueError("seq_off must be a one-dimensional array of n + 1 offsets")
-    n = int(off_t.numel()) - 1
-    if n > 0 and not hasattr(seq_off, "is_cuda") and int(np.asarray(seq_off).ravel()[-1]) > int(codes_t.numel()):
-        raise ValueError("seq_off ends beyond codes_t")
-    k = np.ascontiguousarray(kmers, dtype=np.int32).ravel()
-    nk, words = int(k.size), int(sketchsize64) * int(bbits)
+    dev, off_t, n, k, nk, words = _sketch_args(codes_t, seq_off, kmers, sketchsize64, bbits)
     flags = (_lib.SKETCH_STRAND_PRESERVED if strand_preserved else 0) | (_lib.SKETCH_EXACT if exact else 0)
-    with torch.cuda.device(dev):
-        sketches = torch.zeros((n, nk, max(words, 0)), dtype=torch.int64, device=dev)
-        stats = torch.zeros((n, 6), dtype=torch.int64, device=dev)
-        kstats = torch.zeros((n, nk, 4), dtype=torch.int64, device=dev)
-        filled = torch.zeros((n, nk), dtype=torch.int32, device=dev)
-        rc = _lib.lib().ppk_sketch_reads_dev(
-            C.c_void_p(codes_t.data_ptr() if codes_t.numel() else off_t.data_ptr()), C.c_void_p(off_t.data_ptr()), n,
-            k.ctypes.data_as(C.POINTER(C.c_int32)), nk, int(sketchsize64), int(bbits), flags, int(min_count),
-            C.c_void_p(sketches.data_ptr() or off_t.data_ptr()), C.c_void_p(stats.data_ptr() or off_t.data_ptr()),
-            C.c_void_p(kstats.data_ptr() or off_t.data_ptr()), C.c_void_p(filled.data_ptr() or off_t.data_ptr()),
-            _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_sketch_reads_dev")
+    sketches = torch.zeros((n, nk, max(words, 0)), dtype=torch.int64, device=dev)
+    stats = torch.zeros((n, 6), dtype=torch.int64, device=dev)
+    kstats = torch.zeros((n, nk, 4), dtype=torch.int64, device=dev)
+    filled = torch.zeros((n, nk), dtype=torch.int32, device=dev)
+    # (empty tensors: the offsets' address, as sketch_dev)
+    _dev_call("ppk_sketch_reads_dev", dev, C.c_void_p(codes_t.data_ptr() if codes_t.numel() else off_t.data_ptr()),
+              off_t, n, k, nk, int(sketchsize64), int(bbits), flags, int(min_count),
+              C.c_void_p(sketches.data_ptr() or off_t.data_ptr()), C.c_void_p(stats.data_ptr() or off_t.data_ptr()),
+              C.c_void_p(kstats.data_ptr() or off_t.data_ptr()), C.c_void_p(filled.data_ptr() or off_t.data_ptr()))
     return sketches, stats, filled, kstats
 
 
@@ -1261,24 +1111,16 @@ def strain_knn_dev(dist_t, members_t, seg_off, depth, dist_col=0):
     n = _samples_of(n_rows)
     if n * (n - 1) // 2 != n_rows:
         raise ValueError("the matrix must hold n(n-1)/2 rows")
-    if not (members_t.is_cuda and members_t.dtype == torch.int64 and members_t.dim() == 1
-            and members_t.is_contiguous() and members_t.device == dist_t.device):
-        raise TypeError("members must be a contiguous int64 [m] CUDA tensor on the matrix's device")
+    _check_tensor(members_t, "members must be a contiguous int64 [m] CUDA tensor on the matrix's device", torch.int64,
+                  dim=1, like=dist_t)
     seg = _strain_segments(seg_off)
     if int(seg[-1]) != int(members_t.shape[0]):
         raise ValueError("seg_off must end at the number of members")
     sizes = np.diff(seg)
     nnz = strain_nnz(seg, depth) if len(sizes) and sizes.min() >= 2 and int(depth) >= 1 else 0
-    dev = dist_t.device
-    with torch.cuda.device(dev):
-        oi = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
-        oj = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
-        od = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
-        rc = _lib.lib().ppk_strain_knn_dev(
-            C.c_void_p(dist_t.data_ptr()), n, int(dist_col), C.c_void_p(members_t.data_ptr()),
-            seg.ctypes.data_as(C.POINTER(C.c_longlong)), len(seg) - 1, int(depth), C.c_void_p(oi.data_ptr()),
-            C.c_void_p(oj.data_ptr()), C.c_void_p(od.data_ptr()), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_strain_knn_dev")
+    oi, oj, od = _neighbour_outputs(max(nnz, 1), dist_t.device)
+    _dev_call("ppk_strain_knn_dev", dist_t.device, dist_t, n, int(dist_col), members_t, seg, len(seg) - 1, int(depth),
+              oi, oj, od)
     return oi[:nnz], oj[:nnz], od[:nnz]
 
 
@@ -1301,43 +1143,32 @@ def strain_extend_dev(members_t, seg_off, queries_t, qry_off, nn_j_t, nn_d_t, qr
     torch = _torch()
     dev = members_t.device
 
-    def ok(t, dtype, shape_ok=lambda t: t.dim() == 1):
-        return t.is_cuda and t.dtype == dtype and shape_ok(t) and t.is_contiguous() and t.device == dev
-    if not (ok(members_t, torch.int64) and ok(nn_j_t, torch.int64) and ok(nn_d_t, torch.float32)):
-        raise TypeError("members, and the stored lists, must be contiguous CUDA tensors on one device: int64 [m], "
-                        "int64 and float32 [nnz]")
+    for t, dtype in ((members_t, torch.int64), (nn_j_t, torch.int64), (nn_d_t, torch.float32)):
+        _check_tensor(t, "members, and the stored lists, must be contiguous CUDA tensors on one device: int64 [m], "
+                      "int64 and float32 [nnz]", dtype, dim=1, like=members_t)
     seg, qoff = _strain_segments(seg_off), _strain_segments(qry_off)
     if seg.shape != qoff.shape:
         raise ValueError("seg_off and qry_off must have one entry per strain and one more")
     if int(seg[-1]) != int(members_t.shape[0]):
         raise ValueError("seg_off must end at the number of members")
     mq = int(qoff[-1])
-    two = lambda t: t.dim() == 2 and t.shape[1] == 2
     if mq:
-        if not (ok(queries_t, torch.int64) and int(queries_t.shape[0]) == mq):
-            raise TypeError("queries must be a contiguous int64 [mq] CUDA tensor on the members' device, qry_off ending "
-                            "at mq")
-        if not (ok(qr_t, torch.float32, two) and int(qr_t.shape[0]) == int(n_qry) * int(n_ref)):
-            raise TypeError("qr must be a contiguous float32 [n_qry * n_ref, 2] CUDA tensor on the members' device")
-    if qq_t is not None and not (ok(qq_t, torch.float32, two)
-                                 and int(qq_t.shape[0]) == int(n_qry) * (int(n_qry) - 1) // 2):
-        raise TypeError("qq must be a contiguous float32 [n_qry(n_qry-1)/2, 2] CUDA tensor on the members' device")
+        _check_tensor(queries_t, "queries must be a contiguous int64 [mq] CUDA tensor on the members' device, qry_off "
+                      "ending at mq", torch.int64, (mq,), like=members_t)
+        _check_tensor(qr_t, "qr must be a contiguous float32 [n_qry * n_ref, 2] CUDA tensor on the members' device",
+                      torch.float32, (int(n_qry) * int(n_ref), 2), like=members_t)
+    if qq_t is not None:
+        _check_tensor(qq_t, "qq must be a contiguous float32 [n_qry(n_qry-1)/2, 2] CUDA tensor on the members' device",
+                      torch.float32, (int(n_qry) * (int(n_qry) - 1) // 2, 2), like=members_t)
     sizes = np.diff(seg)
     valid = len(sizes) and sizes.min() >= 2 and int(depth) >= 1 and np.diff(qoff).min() >= 0
     if valid and strain_nnz(seg, depth) != int(nn_j_t.shape[0]) or nn_j_t.shape != nn_d_t.shape:
         raise ValueError("the stored lists must hold the entries of strain_knn_dev at this depth")
     nnz = strain_nnz(seg + qoff, depth) if valid else 0
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    llp = C.POINTER(C.c_longlong)
-    with torch.cuda.device(dev):
-        oi = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
-        oj = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
-        od = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
-        rc = _lib.lib().ppk_strain_extend_dev(
-            ptr(members_t), seg.ctypes.data_as(llp), ptr(queries_t if mq else None), qoff.ctypes.data_as(llp),
-            len(seg) - 1, ptr(nn_j_t), ptr(nn_d_t), ptr(qr_t if mq else None), ptr(qq_t), int(n_ref), int(n_qry),
-            int(dist_col), float(np.float32(floor)), int(depth), ptr(oi), ptr(oj), ptr(od), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_strain_extend_dev")
+    oi, oj, od = _neighbour_outputs(max(nnz, 1), dev)
+    _dev_call("ppk_strain_extend_dev", dev, members_t, seg, queries_t if mq else None, qoff, len(seg) - 1, nn_j_t,
+              nn_d_t, qr_t if mq else None, qq_t, int(n_ref), int(n_qry), int(dist_col), float(np.float32(floor)),
+              int(depth), oi, oj, od)
     return oi[:nnz], oj[:nnz], od[:nnz]
 
 
@@ -1348,10 +1179,9 @@ def strain_ranks_dev(j_t, d_t, seg_off, depth, ranks, reciprocal_only=False, cou
     row each rank keeps; pos_i, pos_j, level int64 and dist float32: the level stream, positions into the member
     array, every unordered pair once -- an edge stream for cluster_sweep_dev with n = m, n_off = n_ranks)."""
     torch = _torch()
-    if not (j_t.is_cuda and j_t.dtype == torch.int64 and j_t.dim() == 1 and j_t.is_contiguous() and d_t.is_cuda
-            and d_t.dtype == torch.float32 and d_t.shape == j_t.shape and d_t.is_contiguous()
-            and d_t.device == j_t.device):
-        raise TypeError("the lists must be contiguous CUDA tensors of one length, int64 columns and float32 distances")
+    for t, dtype, shape in ((j_t, torch.int64, (None,)), (d_t, torch.float32, tuple(j_t.shape))):
+        _check_tensor(t, "the lists must be contiguous CUDA tensors of one length, int64 columns and float32 "
+                      "distances", dtype, shape, like=j_t)
     seg = _strain_segments(seg_off)
     rk = np.ascontiguousarray(ranks, dtype=np.int32)
     if rk.ndim != 1 or rk.shape[0] < 1:
@@ -1366,18 +1196,13 @@ def strain_ranks_dev(j_t, d_t, seg_off, depth, ranks, reciprocal_only=False, cou
     cap = nnz if count_unique_distances or not ok else int((sizes * np.minimum(
         np.minimum(int(depth), sizes - 1), int(rk.max()) + 1)).sum())
     dev = j_t.device
-    with torch.cuda.device(dev):
-        prefix = torch.empty((n_ranks, max(m, 1)), dtype=torch.int32, device=dev)
-        pos = torch.empty((3, max(cap, 1)), dtype=torch.int64, device=dev)
-        sd = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
-        n_out = C.c_size_t(0)
-        rc = _lib.lib().ppk_strain_ranks_dev(
-            C.c_void_p(j_t.data_ptr()), C.c_void_p(d_t.data_ptr()), seg.ctypes.data_as(C.POINTER(C.c_longlong)),
-            len(seg) - 1, int(depth), rk.ctypes.data_as(C.POINTER(C.c_int32)), n_ranks, int(bool(reciprocal_only)),
-            int(bool(count_unique_distances)), float(np.float32(epsilon)), C.c_void_p(prefix.data_ptr()),
-            C.c_void_p(pos[0].data_ptr()), C.c_void_p(pos[1].data_ptr()), C.c_void_p(pos[2].data_ptr()),
-            C.c_void_p(sd.data_ptr()), cap, C.byref(n_out), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_strain_ranks_dev")
+    prefix = torch.empty((n_ranks, max(m, 1)), dtype=torch.int32, device=dev)
+    pos = torch.empty((3, max(cap, 1)), dtype=torch.int64, device=dev)
+    sd = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
+    n_out = C.c_size_t(0)
+    _dev_call("ppk_strain_ranks_dev", dev, j_t, d_t, seg, len(seg) - 1, int(depth), rk, n_ranks,
+              int(bool(reciprocal_only)), int(bool(count_unique_distances)), float(np.float32(epsilon)), prefix,
+              pos[0], pos[1], pos[2], sd, cap, C.byref(n_out))
     k = int(n_out.value)
     return prefix[:, :m], pos[0, :k], pos[1, :k], pos[2, :k], sd[:k]
 
@@ -1420,24 +1245,18 @@ def density_kde_dev(dist_t, gx, gy, h, scale=None, idx_t=None, shift=None, retur
     _check_dist_tensor(dist_t)
     gx, gy, sc = _kde_args(gx, gy, scale)
     n_rows = int(dist_t.shape[0])
-    if idx_t is not None and not (idx_t.is_cuda and idx_t.dtype == torch.int64 and idx_t.dim() == 1
-                                  and idx_t.is_contiguous() and idx_t.device == dist_t.device):
-        raise TypeError("idx must be a contiguous int64 CUDA vector on the matrix's device")
+    if idx_t is not None:
+        _check_tensor(idx_t, "idx must be a contiguous int64 CUDA vector on the matrix's device", torch.int64, dim=1,
+                      like=dist_t)
     rows_read = n_rows if idx_t is None else int(idx_t.shape[0])
     if shift is None:
         shift = pair_sum_shift(rows_read)
     used = np.zeros(2, dtype=np.float32)
-    dev = dist_t.device
-    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
     # NULL means every row, and an empty tensor has no address: an empty list passes the matrix's (never read)
     idx_p = None if idx_t is None else C.c_void_p(idx_t.data_ptr() or dist_t.data_ptr())
-    with torch.cuda.device(dev):
-        out = torch.empty((len(gx), len(gy)), dtype=torch.int64, device=dev)
-        rc = _lib.lib().ppk_density_kde_dev(
-            C.c_void_p(dist_t.data_ptr()), n_rows, idx_p, rows_read if idx_t is not None else 0, sc.ctypes.data_as(fp) if sc is not None else None,
-            gx.ctypes.data_as(dp), len(gx), gy.ctypes.data_as(dp), len(gy), float(h), int(shift),
-            C.c_void_p(out.data_ptr()), used.ctypes.data_as(fp), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_density_kde_dev")
+    out = torch.empty((len(gx), len(gy)), dtype=torch.int64, device=dist_t.device)
+    _dev_call("ppk_density_kde_dev", dist_t.device, dist_t, n_rows, idx_p, rows_read if idx_t is not None else 0, sc,
+              gx, len(gx), gy, len(gy), float(h), int(shift), out, used)
     return (out, int(shift), rows_read, used) if return_scale else (out, int(shift), rows_read)
 
 
@@ -1454,13 +1273,8 @@ def density_kde(dist, gx, gy, h, scale=None, idx=None, shift=None, device=0):
         shift = pair_sum_shift(rows_read)
     out = np.empty((len(gx), len(gy)), dtype=np.int64)
     used = np.zeros(2, dtype=np.float32)
-    fp, dp, lp = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_longlong)
-    rc = _lib.lib().ppk_density_kde(
-        dist.ctypes.data_as(fp), dist.shape[0], ix.ctypes.data_as(lp) if ix is not None else None,
-        rows_read if ix is not None else 0, sc.ctypes.data_as(fp) if sc is not None else None, gx.ctypes.data_as(dp),
-        len(gx), gy.ctypes.data_as(dp), len(gy), float(h), int(shift), int(device), out.ctypes.data_as(lp),
-        used.ctypes.data_as(fp))
-    _lib.check(rc, "ppk_density_kde")
+    _lib.call("ppk_density_kde", dist, dist.shape[0], ix, rows_read if ix is not None else 0, sc, gx, len(gx), gy,
+              len(gy), float(h), int(shift), int(device), out, used)
     return out, int(shift), rows_read, used
 
 
@@ -1479,21 +1293,16 @@ def density_counts_dev(dist_t, raster, labels_t=None, label_lo=0, n_slots=1):
     _check_dist_tensor(dist_t)
     x0, inv_dx, nx, y0, inv_dy, ny = _raster_args(raster)
     n_rows = int(dist_t.shape[0])
-    if labels_t is not None and not (labels_t.is_cuda and labels_t.dtype == torch.int32 and labels_t.dim() == 1
-                                     and labels_t.is_contiguous() and labels_t.shape[0] == n_rows
-                                     and labels_t.device == dist_t.device):
-        raise TypeError("labels must be a contiguous int32 [n] CUDA tensor on the matrix's device")
+    if labels_t is not None:
+        _check_tensor(labels_t, "labels must be a contiguous int32 [n] CUDA tensor on the matrix's device",
+                      torch.int32, (n_rows,), like=dist_t)
     if not (1 <= int(n_slots) <= 32 and 1 <= nx <= 4096 and 1 <= ny <= 4096):
         raise ValueError("n_slots must be 1 .. 32 and nx, ny 1 .. 4096")
     dev = dist_t.device
-    with torch.cuda.device(dev):
-        counts = torch.empty((int(n_slots), ny, nx), dtype=torch.uint32, device=dev)
-        outside = torch.empty(1, dtype=torch.int64, device=dev)
-        rc = _lib.lib().ppk_density_counts_dev(
-            C.c_void_p(dist_t.data_ptr()), n_rows, C.c_void_p(labels_t.data_ptr()) if labels_t is not None else None,
-            int(label_lo), int(n_slots), x0, inv_dx, nx, y0, inv_dy, ny, C.c_void_p(counts.data_ptr()),
-            C.c_void_p(outside.data_ptr()), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_density_counts_dev")
+    counts = torch.empty((int(n_slots), ny, nx), dtype=torch.uint32, device=dev)
+    outside = torch.empty(1, dtype=torch.int64, device=dev)
+    _dev_call("ppk_density_counts_dev", dev, dist_t, n_rows, labels_t, int(label_lo), int(n_slots), x0, inv_dx, nx, y0,
+              inv_dy, ny, counts, outside)
     return counts, outside
 
 
@@ -1511,12 +1320,8 @@ def density_counts(dist, raster, labels=None, label_lo=0, n_slots=1, device=0):
         raise ValueError("n_slots must be 1 .. 32 and nx, ny 1 .. 4096")
     counts = np.empty((int(n_slots), ny, nx), dtype=np.uint32)
     outside = np.zeros(1, dtype=np.int64)
-    rc = _lib.lib().ppk_density_counts(
-        dist.ctypes.data_as(C.POINTER(C.c_float)), dist.shape[0],
-        lab.ctypes.data_as(C.POINTER(C.c_int32)) if lab is not None else None, int(label_lo), int(n_slots), x0, inv_dx,
-        nx, y0, inv_dy, ny, int(device), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
-        outside.ctypes.data_as(C.POINTER(C.c_longlong)))
-    _lib.check(rc, "ppk_density_counts")
+    _lib.call("ppk_density_counts", dist, dist.shape[0], lab, int(label_lo), int(n_slots), x0, inv_dx, nx, y0, inv_dy,
+              ny, int(device), counts, outside)
     return counts, int(outside[0])
 
 
@@ -1526,33 +1331,28 @@ def network_summary_dev(i_t, j_t, off_t, n, n_off, values_at=None):
     [n_off, 2] = mean and size-weighted mean over the components of more than 3 vertices of their maximum normalised
     vertex betweenness; scored int64 [n_off] = how many such components; values float64 [n] = every vertex's
     normalised betweenness in G_{values_at} within its component, or None), CUDA tensors."""
+    return _network_summary("ppk_network_summary_dev", i_t, j_t, off_t, n, n_off, values_at)
+
+
+def _network_summary(name, i_t, j_t, off_t, n, n_off, values_at, *sampling):
+    """The body of network_summary_dev and network_summary_sampled_dev: the latter's call ends in `sampling`."""
     torch = _torch()
     m, stride = _edge_stream(i_t, j_t, off_t)
     va = -1 if values_at is None else int(values_at)
     dev = i_t.device
     no = max(int(n_off), 1)
-    with torch.cuda.device(dev):
-        stats = torch.empty((no, 4), dtype=torch.int64, device=dev)
-        bt = torch.empty((no, 2), dtype=torch.float64, device=dev)
-        scored = torch.empty(no, dtype=torch.int64, device=dev)
-        values = torch.empty(max(int(n), 1), dtype=torch.float64, device=dev) if va >= 0 else None
-        rc = _lib.lib().ppk_network_summary_dev(
-            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride,
-            C.c_void_p(off_t.data_ptr()) if off_t is not None else None, m, int(n), int(n_off), va,
-            C.c_void_p(stats.data_ptr()), C.c_void_p(bt.data_ptr()), C.c_void_p(scored.data_ptr()),
-            C.c_void_p(values.data_ptr()) if values is not None else None, _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_network_summary_dev")
+    stats = torch.empty((no, 4), dtype=torch.int64, device=dev)
+    bt = torch.empty((no, 2), dtype=torch.float64, device=dev)
+    scored = torch.empty(no, dtype=torch.int64, device=dev)
+    values = torch.empty(max(int(n), 1), dtype=torch.float64, device=dev) if va >= 0 else None
+    _dev_call(name, dev, i_t, j_t, stride, off_t, m, int(n), int(n_off), va, stats, bt, scored, values, *sampling)
     return stats, bt, scored, (values[:int(n)] if values is not None else None)
 
 
 def network_summary_graph_dev(edges_t, n, values=False):
     """network_summary_dev of one int64 [m, 2] CUDA edge list, read in place.  Returns (stats int64 [4], bt float64
     [2], scored int64 [] and values float64 [n] or None)."""
-    torch = _torch()
-    if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
-            and edges_t.is_contiguous()):
-        raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
-    stats, bt, scored, val = network_summary_dev(edges_t[:, 0], edges_t[:, 1], None, n, 1, 0 if values else None)
+    stats, bt, scored, val = network_summary_dev(*_edge_cols(edges_t), None, n, 1, 0 if values else None)
     return stats[0], bt[0], scored[0], val
 
 
@@ -1561,50 +1361,19 @@ def network_summary_sampled_dev(i_t, j_t, off_t, n, n_off, values_at=None, sourc
     (ppk_network_summary_sampled_dev): components of at most `sources` vertices give
     network_summary_dev's bits.  whole_graph: `values` are vertex_betweenness(G, norm=True) of the whole graph
     (components of 3 vertices included, divisor (n - 1)(n - 2)); bt and scored do not change.  Same returns."""
-    torch = _torch()
     sources = int(sources)
     if sources < 1:
         raise ValueError("network_summary_sampled_dev: sources must be >= 1")
-    m, stride = _edge_stream(i_t, j_t, off_t)
-    va = -1 if values_at is None else int(values_at)
-    dev = i_t.device
-    no = max(int(n_off), 1)
-    with torch.cuda.device(dev):
-        stats = torch.empty((no, 4), dtype=torch.int64, device=dev)
-        bt = torch.empty((no, 2), dtype=torch.float64, device=dev)
-        scored = torch.empty(no, dtype=torch.int64, device=dev)
-        values = torch.empty(max(int(n), 1), dtype=torch.float64, device=dev) if va >= 0 else None
-        rc = _lib.lib().ppk_network_summary_sampled_dev(
-            C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride,
-            C.c_void_p(off_t.data_ptr()) if off_t is not None else None, m, int(n), int(n_off), va,
-            C.c_void_p(stats.data_ptr()), C.c_void_p(bt.data_ptr()), C.c_void_p(scored.data_ptr()),
-            C.c_void_p(values.data_ptr()) if values is not None else None, sources, int(seed) & ((1 << 64) - 1),
-            _lib.BT_WHOLE_GRAPH if whole_graph else 0, _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_network_summary_sampled_dev")
-    return stats, bt, scored, (values[:int(n)] if values is not None else None)
+    return _network_summary("ppk_network_summary_sampled_dev", i_t, j_t, off_t, n, n_off, values_at, sources,
+                            int(seed) & ((1 << 64) - 1), _lib.BT_WHOLE_GRAPH if whole_graph else 0)
 
 
 def network_summary_sampled_graph_dev(edges_t, n, values=False, sources=100, seed=0, whole_graph=False):
     """network_summary_sampled_dev of one int64 [m, 2] CUDA edge list, read in place; network_summary_graph_dev's
     returns."""
-    torch = _torch()
-    if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
-            and edges_t.is_contiguous()):
-        raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor")
-    stats, bt, scored, val = network_summary_sampled_dev(edges_t[:, 0], edges_t[:, 1], None, n, 1,
-                                                         0 if values else None, sources, seed, whole_graph)
+    stats, bt, scored, val = network_summary_sampled_dev(*_edge_cols(edges_t), None, n, 1, 0 if values else None,
+                                                         sources, seed, whole_graph)
     return stats[0], bt[0], scored[0], val
-
-
-def _mst_stream(edges_t):
-    """(i_t, j_t) of an int64 [m, 2] CUDA edge list, or the pair itself."""
-    torch = _torch()
-    if isinstance(edges_t, (tuple, list)):
-        return edges_t[0], edges_t[1]
-    if not (edges_t.is_cuda and edges_t.dtype == torch.int64 and edges_t.dim() == 2 and edges_t.shape[1] == 2
-            and edges_t.is_contiguous()):
-        raise TypeError("edges must be a contiguous int64 [m, 2] CUDA tensor, or an (i, j) pair of int64 tensors")
-    return edges_t[:, 0], edges_t[:, 1]
 
 
 def mst_dev(edges_t, w_t, n, labels=False):
@@ -1614,23 +1383,16 @@ def mst_dev(edges_t, w_t, n, labels=False):
     indices of the forest's edges, ascending; the number of components; labels int32 [n] numbered as scipy's
     connected_components numbers them, or None), CUDA tensors and an int."""
     torch = _torch()
-    i_t, j_t = _mst_stream(edges_t)
+    i_t, j_t = _edge_cols(edges_t, _EDGES_OR_PAIR, pair=True)
     m, stride = _edge_stream(i_t, j_t, None)
-    if not (w_t.is_cuda and w_t.dtype == torch.float32 and w_t.dim() == 1 and w_t.shape[0] == m
-            and w_t.is_contiguous()):
-        raise TypeError("weights must be a contiguous float32 CUDA tensor, one per edge")
+    _check_tensor(w_t, "weights must be a contiguous float32 CUDA tensor, one per edge", torch.float32, (m,))
     n = int(n)
     dev = i_t.device
-    with torch.cuda.device(dev):
-        tree = torch.empty(max(min(m, n - 1), 1), dtype=torch.int64, device=dev)
-        n_tree = torch.zeros(1, dtype=torch.int64, device=dev)
-        lab = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if labels else None
-        rc = _lib.lib().ppk_mst_dev(C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride,
-                                    C.c_void_p(w_t.data_ptr()), m, n, C.c_void_p(tree.data_ptr()),
-                                    C.c_void_p(n_tree.data_ptr()), C.c_void_p(lab.data_ptr()) if labels else None,
-                                    _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_mst_dev")
-        k = int(n_tree.item())
+    tree = torch.empty(max(min(m, n - 1), 1), dtype=torch.int64, device=dev)
+    n_tree = torch.zeros(1, dtype=torch.int64, device=dev)
+    lab = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if labels else None
+    _dev_call("ppk_mst_dev", dev, i_t, j_t, stride, w_t, m, n, tree, n_tree, lab)
+    k = int(n_tree.item())
     return tree[:k], n - k, (lab[:n] if labels else None)
 
 
@@ -1646,16 +1408,11 @@ def edge_weights_dev(dist_t, edges_t, weights_type="core", n_ref=0, int_offset=0
     _check_dist_tensor(dist_t)
     if weights_type not in WEIGHTS_TYPES:
         raise ValueError("weights_type must be one of %s" % sorted(WEIGHTS_TYPES))
-    i_t, j_t = _mst_stream(edges_t)
+    i_t, j_t = _edge_cols(edges_t, _EDGES_OR_PAIR, pair=True)
     m, stride = _edge_stream(i_t, j_t, None)
-    dev = dist_t.device
-    with torch.cuda.device(dev):
-        w = torch.empty(max(m, 1), dtype=torch.float32, device=dev)
-        rc = _lib.lib().ppk_edge_weights_dev(C.c_void_p(dist_t.data_ptr()), dist_t.shape[0],
-                                             C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride, m,
-                                             int(n_ref), int(int_offset), WEIGHTS_TYPES[weights_type],
-                                             C.c_void_p(w.data_ptr()), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_edge_weights_dev")
+    w = torch.empty(max(m, 1), dtype=torch.float32, device=dist_t.device)
+    _dev_call("ppk_edge_weights_dev", dist_t.device, dist_t, dist_t.shape[0], i_t, j_t, stride, m, int(n_ref),
+              int(int_offset), WEIGHTS_TYPES[weights_type], w)
     return w[:m]
 
 
@@ -1671,24 +1428,19 @@ def dist_pairs(ref, qry=None, kmers=None, random_tbl=None, pairs=None, random_co
     _check_pair(ref, qry)
     if pairs is None:
         raise ValueError("dist_pairs needs a pair list")
-    i_t, j_t = _mst_stream(pairs)
+    i_t, j_t = _edge_cols(pairs, _EDGES_OR_PAIR, pair=True)
     m, stride = _edge_stream(i_t, j_t, None)
     if i_t.device.index != ref.device:
         raise ValueError("the pair list is not on the databases' device")
-    kmers, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
+    kmers, random_tbl, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
     flags = (FLAG_RANDOM_CORRECT if random_correct else 0) | (FLAG_JACCARD if jaccard else 0) \
         | (FLAG_COUNTS if counts else 0)
     cols = ref.nk if (jaccard or counts) else 2
     dev = "cuda:%d" % ref.device
-    with torch.cuda.device(ref.device):
-        out = torch.empty((m, cols), dtype=torch.int32 if counts else torch.float32, device=dev)
-        n_failed = torch.zeros(1, dtype=torch.int64, device=dev)
-        rc = _lib.lib().ppk_dist_pairs_dev(ref._h, qry._h if qry is not None else None,
-                                           kmers.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr, n_clu, flags,
-                                           C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()), stride, m,
-                                           int(int_offset), C.c_void_p(out.data_ptr()),
-                                           C.c_void_p(n_failed.data_ptr()), _stream_ptr(ref.device))
-        _lib.check(rc, "ppk_dist_pairs_dev")
+    out = torch.empty((m, cols), dtype=torch.int32 if counts else torch.float32, device=dev)
+    n_failed = torch.zeros(1, dtype=torch.int64, device=dev)
+    _dev_call("ppk_dist_pairs_dev", ref.device, ref._h, qry._h if qry is not None else None, kmers, random_tbl, n_clu,
+              flags, i_t, j_t, stride, m, int(int_offset), out, n_failed)
     return out, n_failed
 
 
@@ -1739,11 +1491,8 @@ def edge_weights_from_sketches(ref, qry, kmers, random_tbl, edges_t, weights_typ
     d, _ = dist_pairs(ref, qry, kmers, random_tbl, edges_t, random_correct=random_correct, int_offset=int_offset)
     if weights_type != "euclidean":
         return d[:, WEIGHTS_TYPES[weights_type]].contiguous()
-    with torch.cuda.device(d.device):
-        w = torch.empty(max(d.shape[0], 1), dtype=torch.float32, device=d.device)
-        rc = _lib.lib().ppk_row_norms_dev(C.c_void_p(d.data_ptr()), d.shape[0], C.c_void_p(w.data_ptr()),
-                                          _stream_ptr(d.device.index))
-        _lib.check(rc, "ppk_row_norms_dev")
+    w = torch.empty(max(d.shape[0], 1), dtype=torch.float32, device=d.device)
+    _dev_call("ppk_row_norms_dev", d.device, d, d.shape[0], w)
     return w[:d.shape[0]]
 
 
@@ -1757,8 +1506,8 @@ def nj_dev(src, n=None, col=0):
     t's node ids (a, b) -- samples 0 .. n-1, node n + t' made by join t' -- and (len_a, len_b); row n-2 is the final
     edge (the two nodes left, its length twice).  n = 1 gives empty tensors."""
     torch = _torch()
-    if not (src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and src.dim() in (1, 2)):
-        raise TypeError("the matrix must be a contiguous float32 CUDA tensor: [n, n] square or [n_pairs(, k)] long")
+    _check_tensor(src, "the matrix must be a contiguous float32 CUDA tensor: [n, n] square or [n_pairs(, k)] long",
+                  torch.float32, dim=(1, 2))
     if src.dim() == 2 and src.shape[0] == src.shape[1]:
         kind, stride, col, nn = NJ_SQUARE, 1, 0, int(src.shape[0])
     else:
@@ -1770,13 +1519,9 @@ def nj_dev(src, n=None, col=0):
             raise ValueError("col must index a column of the long form")
     if n is not None and int(n) != nn:
         raise ValueError("n = %d does not match the matrix (%d samples)" % (int(n), nn))
-    dev = src.device
-    with torch.cuda.device(dev):
-        join = torch.empty((max(nn - 1, 0), 2), dtype=torch.int64, device=dev)
-        ln = torch.empty((max(nn - 1, 0), 2), dtype=torch.float64, device=dev)
-        rc = _lib.lib().ppk_nj_dev(C.c_void_p(src.data_ptr()), kind, stride, col, nn,
-                                   C.c_void_p(join.data_ptr()), C.c_void_p(ln.data_ptr()), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_nj_dev")
+    join = torch.empty((max(nn - 1, 0), 2), dtype=torch.int64, device=src.device)
+    ln = torch.empty((max(nn - 1, 0), 2), dtype=torch.float64, device=src.device)
+    _dev_call("ppk_nj_dev", src.device, src, kind, stride, col, nn, join, ln)
     return join, ln
 
 
@@ -1789,9 +1534,7 @@ def nj(square, device_id=0):
     nn = int(sq.shape[0])
     join = np.empty((max(nn - 1, 0), 2), dtype=np.int64)
     ln = np.empty((max(nn - 1, 0), 2), dtype=np.float64)
-    _lib.check(_lib.lib().ppk_nj(sq.ctypes.data_as(C.POINTER(C.c_float)), nn, int(device_id),
-                                 join.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                 ln.ctypes.data_as(C.POINTER(C.c_double))), "ppk_nj")
+    _lib.call("ppk_nj", sq, nn, int(device_id), join, ln)
     return join, ln
 
 
@@ -1802,8 +1545,7 @@ def _embed_lists(i_t, j_t, n, what):
     torch = _torch()
     n = int(n)
     for t in (i_t, j_t):
-        if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 1):
-            raise TypeError("%s: i and j must be contiguous int64 CUDA vectors" % what)
+        _check_tensor(t, "%s: i and j must be contiguous int64 CUDA vectors" % what, torch.int64, dim=1)
     m = int(i_t.numel())
     if int(j_t.numel()) != m or n < 2 or m % n or not 1 <= m // n <= n - 1:
         raise ValueError("%s: lists of n*k entries with n >= 2 and 1 <= k <= n - 1 expected (n = %d, %d entries)"
@@ -1817,18 +1559,12 @@ def embed_weights_dev(i_t, j_t, dist_t, n, perplexity=20.0, weights=False):
     sum 1, and with weights=True also the integer sampling weights rint(P * 2^52) as int64 (uint64 bits)."""
     torch = _torch()
     k = _embed_lists(i_t, j_t, n, "embed_weights_dev")
-    if not (dist_t.is_cuda and dist_t.dtype == torch.float32 and dist_t.is_contiguous()
-            and int(dist_t.numel()) == int(i_t.numel())):
-        raise TypeError("embed_weights_dev: dist must be a contiguous float32 CUDA vector as long as i")
+    _check_tensor(dist_t, "embed_weights_dev: dist must be a contiguous float32 CUDA vector as long as i",
+                  torch.float32, numel=int(i_t.numel()))
     dev = i_t.device
-    with torch.cuda.device(dev):
-        P = torch.empty(int(i_t.numel()), dtype=torch.float64, device=dev)
-        c = torch.empty(int(i_t.numel()), dtype=torch.int64, device=dev) if weights else None
-        rc = _lib.lib().ppk_embed_weights_dev(C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()),
-                                              C.c_void_p(dist_t.data_ptr()), int(n), k, float(perplexity),
-                                              C.c_void_p(P.data_ptr()), C.c_void_p(c.data_ptr() if weights else None),
-                                              _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_embed_weights_dev")
+    P = torch.empty(int(i_t.numel()), dtype=torch.float64, device=dev)
+    c = torch.empty(int(i_t.numel()), dtype=torch.int64, device=dev) if weights else None
+    _dev_call("ppk_embed_weights_dev", dev, i_t, j_t, dist_t, int(n), k, float(perplexity), P, c)
     return (P, c) if weights else P
 
 
@@ -1837,17 +1573,11 @@ def embed_dev(i_t, j_t, P_t, n, seed, max_iter=10000000, n_repu=5, eta0=1.0, wor
     a float64 [n, 2] CUDA tensor.  min(workers, n) workers per iteration, round(max_iter / that) iterations."""
     torch = _torch()
     k = _embed_lists(i_t, j_t, n, "embed_dev")
-    if not (P_t.is_cuda and P_t.dtype == torch.float64 and P_t.is_contiguous()
-            and int(P_t.numel()) == int(i_t.numel())):
-        raise TypeError("embed_dev: P must be a contiguous float64 CUDA vector as long as i")
-    dev = i_t.device
-    with torch.cuda.device(dev):
-        Y = torch.empty((int(n), 2), dtype=torch.float64, device=dev)
-        rc = _lib.lib().ppk_embed_dev(C.c_void_p(i_t.data_ptr()), C.c_void_p(j_t.data_ptr()),
-                                      C.c_void_p(P_t.data_ptr()), int(n), k, int(seed) & ((1 << 64) - 1),
-                                      int(max_iter), int(n_repu), float(eta0), int(workers), C.c_void_p(Y.data_ptr()),
-                                      _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_embed_dev")
+    _check_tensor(P_t, "embed_dev: P must be a contiguous float64 CUDA vector as long as i", torch.float64,
+                  numel=int(i_t.numel()))
+    Y = torch.empty((int(n), 2), dtype=torch.float64, device=i_t.device)
+    _dev_call("ppk_embed_dev", i_t.device, i_t, j_t, P_t, int(n), k, int(seed) & ((1 << 64) - 1), int(max_iter),
+              int(n_repu), float(eta0), int(workers), Y)
     return Y
 
 
@@ -1864,12 +1594,8 @@ def embed(i, j, dist, n, seed, perplexity=20.0, max_iter=10000000, n_repu=5, eta
                          % (n, m))
     P = np.empty(m, dtype=np.float64)
     Y = np.empty((n, 2), dtype=np.float64)
-    ll, f64 = C.POINTER(C.c_longlong), C.POINTER(C.c_double)
-    _lib.check(_lib.lib().ppk_embed(ii.ctypes.data_as(ll), jj.ctypes.data_as(ll),
-                                    dd.ctypes.data_as(C.POINTER(C.c_float)), n, m // n, float(perplexity),
-                                    int(seed) & ((1 << 64) - 1), int(max_iter), int(n_repu), float(eta0),
-                                    int(workers), int(device_id), P.ctypes.data_as(f64), Y.ctypes.data_as(f64)),
-               "ppk_embed")
+    _lib.call("ppk_embed", ii, jj, dd, n, m // n, float(perplexity), int(seed) & ((1 << 64) - 1), int(max_iter),
+              int(n_repu), float(eta0), int(workers), int(device_id), P, Y)
     return P, Y
 
 
@@ -1931,12 +1657,9 @@ def refine_score_dev(dist_t, slope, x_max, y_max):
     line_dist <= 0 -- edge_threshold_dev + network_stats_dev in one call, without the edge list."""
     torch = _torch()
     _check_dist_tensor(dist_t)
-    with torch.cuda.device(dist_t.device):
-        stats = torch.empty(4, dtype=torch.int64, device=dist_t.device)
-        rc = _lib.lib().ppk_refine_score_dev(C.c_void_p(dist_t.data_ptr()), dist_t.shape[0], int(slope), float(x_max),
-                                             float(y_max), C.c_void_p(stats.data_ptr()),
-                                             _stream_ptr(dist_t.device.index))
-        _lib.check(rc, "ppk_refine_score_dev")
+    stats = torch.empty(4, dtype=torch.int64, device=dist_t.device)
+    _dev_call("ppk_refine_score_dev", dist_t.device, dist_t, dist_t.shape[0], int(slope), float(x_max), float(y_max),
+              stats)
     return stats.cpu().numpy()
 
 
@@ -1946,9 +1669,7 @@ def refine_score(X, slope, x_max, y_max, device_id=0):
     if X.ndim != 2 or X.shape[1] != 2:
         raise ValueError("distances must be a float32 [n, 2] array")
     stats = np.zeros(4, dtype=np.int64)
-    rc = _lib.lib().ppk_refine_score(X.ctypes.data_as(C.POINTER(C.c_float)), X.shape[0], int(slope), float(x_max),
-                                     float(y_max), int(device_id), stats.ctypes.data_as(C.POINTER(C.c_longlong)))
-    _lib.check(rc, "ppk_refine_score")
+    _lib.call("ppk_refine_score", X, X.shape[0], int(slope), float(x_max), float(y_max), int(device_id), stats)
     return stats
 
 
@@ -1961,32 +1682,23 @@ class RefineLocal:
     def __init__(self, handle, device):
         self._h, self.device = handle, device
         split = (C.c_ulonglong * 3)()
-        _lib.check(_lib.lib().ppk_refine_local_stats(self._h, split), "ppk_refine_local_stats")
+        _lib.call("ppk_refine_local_stats", self._h, split)
         self.split = tuple(int(v) for v in split)
 
     @classmethod
     def create(cls, dist_t, slope, x_lo, y_lo, x_hi, y_hi):
-        torch = _torch()
         _check_dist_tensor(dist_t)
         h = C.c_void_p()
-        with torch.cuda.device(dist_t.device):
-            rc = _lib.lib().ppk_refine_local_create_dev(
-                C.c_void_p(dist_t.data_ptr()), dist_t.shape[0], int(slope), float(x_lo), float(y_lo), float(x_hi),
-                float(y_hi), _stream_ptr(dist_t.device.index), C.byref(h))
-        if rc == _lib.REFINE_NOT_NESTED:
-            return None
-        _lib.check(rc, "ppk_refine_local_create_dev")
-        return cls(h, dist_t.device)
+        rc = _dev_call("ppk_refine_local_create_dev", dist_t.device, dist_t, dist_t.shape[0], int(slope), float(x_lo),
+                       float(y_lo), float(x_hi), float(y_hi), then=(C.byref(h),), accept=(_lib.REFINE_NOT_NESTED,))
+        return None if rc == _lib.REFINE_NOT_NESTED else cls(h, dist_t.device)
 
     def eval(self, x_max, y_max):
         torch = _torch()
         if self._h is None:
             raise RuntimeError("the bracket handle is closed")
-        with torch.cuda.device(self.device):
-            stats = torch.empty(4, dtype=torch.int64, device=self.device)
-            rc = _lib.lib().ppk_refine_local_eval_dev(self._h, float(x_max), float(y_max), C.c_void_p(stats.data_ptr()),
-                                                      _stream_ptr(self.device.index))
-            _lib.check(rc, "ppk_refine_local_eval_dev")
+        stats = torch.empty(4, dtype=torch.int64, device=self.device)
+        _dev_call("ppk_refine_local_eval_dev", self.device, self._h, float(x_max), float(y_max), stats)
         return stats.cpu().numpy()
 
     def close(self):
@@ -2012,10 +1724,7 @@ def long_to_square_dev(dist_t, col, n):
     """pp_sketchlib.longToSquare of one column of the resident [n_pairs,2] matrix -> [n,n] CUDA."""
     torch = _torch()
     out = torch.empty((n, n), dtype=torch.float32, device=dist_t.device)
-    with torch.cuda.device(dist_t.device):
-        rc = _lib.lib().ppk_long_to_square_dev(C.c_void_p(dist_t.data_ptr()), dist_t.shape[1], int(col), n,
-                                               C.c_void_p(out.data_ptr()), _stream_ptr(dist_t.device.index))
-        _lib.check(rc, "ppk_long_to_square_dev")
+    _dev_call("ppk_long_to_square_dev", dist_t.device, dist_t, dist_t.shape[1], int(col), n, out)
     return out
 
 
@@ -2031,11 +1740,7 @@ def prune_long_dev(dist_t, n, keep):
     cols = 1 if dist_t.dim() == 1 else int(dist_t.shape[1])
     shape = (m * (m - 1) // 2,) if dist_t.dim() == 1 else (m * (m - 1) // 2, cols)
     out = torch.empty(shape, dtype=torch.float32, device=dist_t.device)
-    with torch.cuda.device(dist_t.device):
-        rc = _lib.lib().ppk_prune_long_dev(C.c_void_p(dist_t.data_ptr()), n, cols,
-                                           C.c_void_p(keep_t.data_ptr()), m,
-                                           C.c_void_p(out.data_ptr()), _stream_ptr(dist_t.device.index))
-        _lib.check(rc, "ppk_prune_long_dev")
+    _dev_call("ppk_prune_long_dev", dist_t.device, dist_t, n, cols, keep_t, m, out)
     return out
 
 
@@ -2050,13 +1755,10 @@ def prune_query_rows_dev(qr_t, n_ref, keep_q):
         raise RuntimeError("kept query index outside the matrix")
     shape = (m * n_ref,) if qr_t.dim() == 1 else (m * n_ref, cols)
     out = torch.empty(shape, dtype=torch.float32, device=qr_t.device)
-    with torch.cuda.device(qr_t.device):
-        for lo in range(0, m, 65535):
-            hi = min(m, lo + 65535)
-            rc = _lib.lib().ppk_prune_query_rows_dev(
-                C.c_void_p(qr_t.data_ptr()), n_ref, cols, C.c_void_p(keep_t[lo:].data_ptr()), hi - lo,
-                C.c_void_p(out[lo * n_ref:].data_ptr()), _stream_ptr(qr_t.device.index))
-            _lib.check(rc, "ppk_prune_query_rows_dev")
+    for lo in range(0, m, 65535):
+        hi = min(m, lo + 65535)
+        _dev_call("ppk_prune_query_rows_dev", qr_t.device, qr_t, n_ref, cols, keep_t[lo:], hi - lo,
+                  out[lo * n_ref:])
     return out
 
 
@@ -2064,21 +1766,12 @@ def knn_ref_query(ref, qry, kmers, random_tbl, knn, dist_col=0, random_correct=T
     """ppk_knn_sketches_rq_dev: for every reference its knn nearest queries (numbered n_ref + q) and for every
     query its knn nearest references, one pass over the rectangle's tiles.  CUDA tensors (i, j, dist) of length
     (n_ref + n_qry) * knn, references first."""
-    torch = _torch()
     _check_pair(ref, qry)
-    n = ref.n + qry.n
-    dev = "cuda:%d" % ref.device
-    oi = torch.empty(n * knn, dtype=torch.int64, device=dev)
-    oj = torch.empty(n * knn, dtype=torch.int64, device=dev)
-    od = torch.empty(n * knn, dtype=torch.float32, device=dev)
-    kmers_a, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
+    oi, oj, od = _neighbour_outputs((ref.n + qry.n) * knn, "cuda:%d" % ref.device)
+    kmers_a, random_tbl, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
     n_cand = C.c_ulonglong(0)
-    with torch.cuda.device(ref.device):
-        rc = _lib.lib().ppk_knn_sketches_rq_dev(ref._h, qry._h, kmers_a.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr,
-                                                n_clu, FLAG_RANDOM_CORRECT if random_correct else 0, int(knn),
-                                                int(dist_col), C.c_void_p(oi.data_ptr()), C.c_void_p(oj.data_ptr()),
-                                                C.c_void_p(od.data_ptr()), C.byref(n_cand), _stream_ptr(ref.device))
-        _lib.check(rc, "ppk_knn_sketches_rq_dev")
+    _dev_call("ppk_knn_sketches_rq_dev", ref.device, ref._h, qry._h, kmers_a, random_tbl, n_clu,
+              FLAG_RANDOM_CORRECT if random_correct else 0, int(knn), int(dist_col), oi, oj, od, C.byref(n_cand))
     if info is not None:
         info["candidates"] = int(n_cand.value)
     return oi, oj, od
@@ -2099,51 +1792,36 @@ def knn_from_sketches(db, kmers, random_tbl, knn, dist_col=0, random_correct=Tru
         compare work, one band of the matrix at a time).
     "auto" falls back to "square" while n*n <= band_items, else "bands", where "tiles" does not apply."""
     torch = _torch()
-    lib = _lib.lib()
     n = db.n
     dev = "cuda:%d" % db.device
-    oi = torch.empty(n * knn, dtype=torch.int64, device=dev)
-    oj = torch.empty(n * knn, dtype=torch.int64, device=dev)
-    od = torch.empty(n * knn, dtype=torch.float32, device=dev)
+    oi, oj, od = _neighbour_outputs(n * knn, dev)
     if method == "auto":
         # (any k list the tile kernel takes: lists of more than 128 count bits run its windowed instantiation)
         tiles_ok = db.bbits == 14 and 1 <= knn <= 32 and db.nk <= 128 and n > 1
         method = "tiles" if tiles_ok else ("square" if n * n <= band_items else "bands")
     if method == "tiles":
-        kmers_a, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, db.nk)
+        kmers_a, random_tbl, n_clu = _prep_tables(kmers, random_tbl, db.nk)
         n_cand = C.c_ulonglong(0)
-        with torch.cuda.device(db.device):
-            rc = lib.ppk_knn_sketches_dev(db._h, kmers_a.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr, n_clu,
-                                          FLAG_RANDOM_CORRECT if random_correct else 0, int(knn), int(dist_col),
-                                          C.c_void_p(oi.data_ptr()), C.c_void_p(oj.data_ptr()),
-                                          C.c_void_p(od.data_ptr()), C.byref(n_cand), _stream_ptr(db.device))
-            _lib.check(rc, "ppk_knn_sketches_dev")
+        _dev_call("ppk_knn_sketches_dev", db.device, db._h, kmers_a, random_tbl, n_clu,
+                  FLAG_RANDOM_CORRECT if random_correct else 0, int(knn), int(dist_col), oi, oj, od, C.byref(n_cand))
         if info is not None:
             info["candidates"] = int(n_cand.value)
         return oi, oj, od
     if method == "square" and n > 1:
-        with torch.cuda.device(db.device):
-            tri, _ = dist(db, None, kmers, random_tbl, random_correct=random_correct)
-            sq = long_to_square_dev(tri, dist_col, n)
-            del tri
-            rc = lib.ppk_knn_dev(C.c_void_p(sq.data_ptr()), n, int(knn), C.c_void_p(oi.data_ptr()),
-                                 C.c_void_p(oj.data_ptr()), C.c_void_p(od.data_ptr()),
-                                 _stream_ptr(db.device))
-            _lib.check(rc, "ppk_knn_dev")
+        tri, _ = dist(db, None, kmers, random_tbl, random_correct=random_correct)
+        sq = long_to_square_dev(tri, dist_col, n)
+        del tri
+        _dev_call("ppk_knn_dev", db.device, sq, n, int(knn), oi, oj, od)
         return oi, oj, od
     band = max(64, min(n, (band_items // max(n, 1)) // 64 * 64))
     buf = torch.empty((min(band, n) * n, 2), dtype=torch.float32, device=dev)
-    with torch.cuda.device(db.device):
-        for qb in range(0, n, band):
-            qe = min(n, qb + band)
-            block = buf[:(qe - qb) * n]
-            dist(db, db, kmers, random_tbl, random_correct=random_correct, q_begin=qb, q_end=qe,
-                 out=block)
-            rc = lib.ppk_knn_rect_dev(C.c_void_p(block.data_ptr()), 2, int(dist_col), qe - qb, n, qb,
-                                      int(knn), C.c_void_p(oi[qb * knn:].data_ptr()),
-                                      C.c_void_p(oj[qb * knn:].data_ptr()),
-                                      C.c_void_p(od[qb * knn:].data_ptr()), _stream_ptr(db.device))
-            _lib.check(rc, "ppk_knn_rect_dev")
+    for qb in range(0, n, band):
+        qe = min(n, qb + band)
+        block = buf[:(qe - qb) * n]
+        dist(db, db, kmers, random_tbl, random_correct=random_correct, q_begin=qb, q_end=qe,
+             out=block)
+        _dev_call("ppk_knn_rect_dev", db.device, block, 2, int(dist_col), qe - qb, n, qb, int(knn), oi[qb * knn:],
+                  oj[qb * knn:], od[qb * knn:])
     return oi, oj, od
 
 
@@ -2163,19 +1841,15 @@ def extend_from_sketches(rr_mat, ref, qry, kmers, random_tbl, knn, dist_col=0, r
     r = np.ascontiguousarray(np.asarray(r).astype(np.int64, copy=False)).ravel()
     c = np.ascontiguousarray(np.asarray(c).astype(np.int64, copy=False)).ravel()
     d = np.ascontiguousarray(np.asarray(d).astype(np.float32, copy=False)).ravel()
-    kmers, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
+    kmers, random_tbl, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
     cap = max(int(knn) * (ref.n + qry.n), 1)
     oi, oj, od = np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.float32)
     n = C.c_size_t(0)
-    ll, fp = C.POINTER(C.c_longlong), C.POINTER(C.c_float)
     rh = (C.c_void_p * len(refs))(*[x._h.value for x in refs])
     qh = (C.c_void_p * len(refs))(*[x._h.value for x in qrys])
-    rc = _lib.lib().ppk_extend_sketches_dbs(r.ctypes.data_as(ll), c.ctypes.data_as(ll), d.ctypes.data_as(fp), r.size,
-                                        rh, qh, len(refs), kmers.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr, n_clu,
-                                        FLAG_RANDOM_CORRECT if random_correct else 0, int(knn), int(dist_col),
-                                        oi.ctypes.data_as(ll), oj.ctypes.data_as(ll), od.ctypes.data_as(fp), cap,
-                                        C.byref(n))
-    _lib.check(rc, "ppk_extend_sketches")
+    _lib.call("ppk_extend_sketches_dbs", r, c, d, r.size, rh, qh, len(refs), kmers, random_tbl, n_clu,
+              FLAG_RANDOM_CORRECT if random_correct else 0, int(knn), int(dist_col), oi, oj, od, cap, C.byref(n),
+              what="ppk_extend_sketches")
     return oi[:n.value], oj[:n.value], od[:n.value]
 
 
@@ -2184,68 +1858,44 @@ def knn_candidates(db, kmers, random_tbl, knn, dist_col=0, random_correct=True, 
     """Neighbour candidates of one band of query rows (ppk_knn_candidates_dev): CUDA tensors
     (keys int32 [m] = sample, vals int64 [m] = distance bits << 32 | other sample)."""
     torch = _torch()
-    lib = _lib.lib()
     q_end = db.n if q_end is None else int(q_end)
-    kmers_a, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, db.nk)
+    kmers_a, random_tbl, n_clu = _prep_tables(kmers, random_tbl, db.nk)
     dev = "cuda:%d" % db.device
     rows = rows_in_band(db.n, 0, q_begin, q_end)
     if cap is None:
         cap = min(2 * rows, max(1 << 20, (256 + 256 * knn) * max(q_end - q_begin, 1) * 2))
-    with torch.cuda.device(db.device):
-        while True:
-            keys = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-            vals = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
-            n_cand = C.c_ulonglong(0)
-            rc = lib.ppk_knn_candidates_dev(db._h, kmers_a.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr, n_clu,
-                                            FLAG_RANDOM_CORRECT if random_correct else 0, int(knn), int(dist_col),
-                                            int(q_begin), q_end, C.c_void_p(keys.data_ptr()),
-                                            C.c_void_p(vals.data_ptr()), cap, C.byref(n_cand),
-                                            _stream_ptr(db.device))
-            m = int(n_cand.value)
-            if rc == _lib.ERR_CAPACITY:
-                cap = m + m // 4 + 1024
-                continue
-            _lib.check(rc, "ppk_knn_candidates_dev")
+    while True:
+        keys = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        vals = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        n_cand = C.c_ulonglong(0)
+        rc = _dev_call("ppk_knn_candidates_dev", db.device, db._h, kmers_a, random_tbl, n_clu,
+                       FLAG_RANDOM_CORRECT if random_correct else 0, int(knn), int(dist_col), int(q_begin), q_end,
+                       keys, vals, cap, C.byref(n_cand), accept=(_lib.ERR_CAPACITY,))
+        m = int(n_cand.value)
+        if rc == _lib.OK:
             return keys[:m], vals[:m]
+        cap = m + m // 4 + 1024
 
 
 def knn_select(keys, vals, n, knn):
     """Every sample's knn smallest (distance, column) keys out of a candidate list
     (ppk_knn_select_dev) -> (i, j, dist) CUDA tensors of length n*knn."""
-    torch = _torch()
-    dev = keys.device
-    oi = torch.empty(n * knn, dtype=torch.int64, device=dev)
-    oj = torch.empty(n * knn, dtype=torch.int64, device=dev)
-    od = torch.empty(n * knn, dtype=torch.float32, device=dev)
-    keys = keys.contiguous()
-    vals = vals.contiguous()
-    with torch.cuda.device(dev):
-        rc = _lib.lib().ppk_knn_select_dev(C.c_void_p(keys.data_ptr()), C.c_void_p(vals.data_ptr()), int(keys.shape[0]),
-                                           int(n), int(knn), C.c_void_p(oi.data_ptr()), C.c_void_p(oj.data_ptr()),
-                                           C.c_void_p(od.data_ptr()), _stream_ptr(dev.index))
-        _lib.check(rc, "ppk_knn_select_dev")
+    oi, oj, od = _neighbour_outputs(n * knn, keys.device)
+    _dev_call("ppk_knn_select_dev", keys.device, keys.contiguous(), vals.contiguous(), int(keys.shape[0]), int(n),
+              int(knn), oi, oj, od)
     return oi, oj, od
 
 
 def knn_band(db, kmers, random_tbl, knn, dist_col=0, random_correct=True, q_begin=0, q_end=None, info=None):
     """ppk_knn_sketches_band_dev: the best knn per sample among the pairs of one band of the triangle's rows;
     CUDA tensors (j int64, dist float32) of length n * knn, unfilled slots j = -1."""
-    torch = _torch()
-    n = db.n
-    q_end = n if q_end is None else int(q_end)
-    dev = "cuda:%d" % db.device
-    oi = torch.empty(n * knn, dtype=torch.int64, device=dev)
-    oj = torch.empty(n * knn, dtype=torch.int64, device=dev)
-    od = torch.empty(n * knn, dtype=torch.float32, device=dev)
-    kmers_a, random_tbl, tbl_ptr, n_clu = _prep_tables(kmers, random_tbl, db.nk)
+    q_end = db.n if q_end is None else int(q_end)
+    oi, oj, od = _neighbour_outputs(db.n * knn, "cuda:%d" % db.device)
+    kmers_a, random_tbl, n_clu = _prep_tables(kmers, random_tbl, db.nk)
     n_cand = C.c_ulonglong(0)
-    with torch.cuda.device(db.device):
-        rc = _lib.lib().ppk_knn_sketches_band_dev(db._h, kmers_a.ctypes.data_as(C.POINTER(C.c_int32)), tbl_ptr, n_clu,
-                                                  FLAG_RANDOM_CORRECT if random_correct else 0, int(knn), int(dist_col),
-                                                  int(q_begin), q_end, C.c_void_p(oi.data_ptr()),
-                                                  C.c_void_p(oj.data_ptr()), C.c_void_p(od.data_ptr()),
-                                                  C.byref(n_cand), _stream_ptr(db.device))
-        _lib.check(rc, "ppk_knn_sketches_band_dev")
+    _dev_call("ppk_knn_sketches_band_dev", db.device, db._h, kmers_a, random_tbl, n_clu,
+              FLAG_RANDOM_CORRECT if random_correct else 0, int(knn), int(dist_col), int(q_begin), q_end, oi, oj, od,
+              C.byref(n_cand))
     if info is not None:
         info["candidates"] = int(n_cand.value)
     return oj, od
@@ -2623,7 +2273,7 @@ class PeerStoreQuery:
         if self.world > 1:
             handle = C.create_string_buffer(64)
             if self.rank == 0 and ok:
-                if lib.ppk_window_export(self.ref.device, C.c_void_p(self.window), handle) != 0:
+                if lib.ppk_window_export(self.ref.device, self.window, handle) != 0:
                     ok, why = 0, _lib.last_error()
             t = self.flag_tensor(0).new_zeros(64, dtype=torch.uint8)
             if self.rank == 0:
@@ -2756,12 +2406,12 @@ class PeerStoreQuery:
             dist_.barrier(self.group)        # nobody is still storing into a window that is about to go
         self._matrix = None
         if self.window is not None and self.rank != 0:
-            lib.ppk_window_close(self.ref.device, C.c_void_p(self.window))
+            lib.ppk_window_close(self.ref.device, self.window)
             self.window = None
         if collective and self.world > 1:
             dist_.barrier(self.group)        # every mapping is gone before the allocation is
         if self.window is not None:
-            lib.ppk_window_free(self.ref.device, C.c_void_p(self.window))
+            lib.ppk_window_free(self.ref.device, self.window)
             self.window = None
 
 
