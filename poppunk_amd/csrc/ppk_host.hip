@@ -413,22 +413,176 @@ int db_acquire(int device, const uint64_t *sk, size_t n, size_t nk, size_t s64, 
   return PPK_OK;
 }
 
-// ---- one host query = one job, one part per listed device ---------------------------------------
-struct QueryPart {
+// ---- the device-list frame of the multi-device host calls ----------------------------------------
+// Dense distances, fused edge lists and neighbour lists share it: a checked list of per-device databases
+// (check_db_list) or of device ids (device_list) becomes entries (plan_entries: device, occurrence, first entry of
+// the device; plan_db_bands: an entry's databases and its band of query rows), the entries run (run_entries: inline
+// when there is one, else one helper thread each), and a worker begins with an EntryScope (device, streams, where its
+// error goes).
+struct Entry {
   int device = 0;
   int dup = 0;                                  // occurrence index of `device` in the device list
-  int leader = -1;                              // dup > 0: index of the part that acquires this device's databases
+  int leader = -1;                              // dup > 0: index of the first entry of this device
   const ppk_db *ref = nullptr, *qry = nullptr;
+  size_t q_begin = 0, q_end = 0;                // its band of query rows (plan_db_bands)
+  int rc = PPK_OK;
+  std::string err;
+};
+
+// per-device databases of one job: all there, each pair compatible (ppk_check_pair), all of one shape
+int check_db_list(const char *what, const ppk_db *const *refs, const ppk_db *const *qrys, int n_dev,
+                  const int32_t *kmers) {
+  const std::string w(what);
+  if (!refs || n_dev < 1 || n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, w + ": no databases (or more than 64)");
+  for (int d = 0; d < n_dev; ++d)
+    if (!refs[d] || (qrys && !qrys[d])) return ppk_fail(PPK_ERR_ARG, w + ": a database is missing for some device");
+  for (int d = 0; d < n_dev; ++d) {
+    const ppk_db *q = qrys ? qrys[d] : nullptr;
+    if (int rc = ppk_check_pair(refs[d], q, kmers, 0, 0)) return rc;
+    if (refs[d]->n != refs[0]->n || refs[d]->nk != refs[0]->nk || refs[d]->s64 != refs[0]->s64 ||
+        refs[d]->bbits != refs[0]->bbits || (q ? q->n : 0) != (qrys ? qrys[0]->n : 0))
+      return ppk_fail(PPK_ERR_ARG, w + ": the per-device databases differ in shape");
+  }
+  return PPK_OK;
+}
+
+// the device list of a host-array entry point: none given -> device 0
+int device_list(const int *&devices, int &n_dev) {
+  static const int default_dev = 0;
+  if (!devices || n_dev < 1) {
+    devices = &default_dev;
+    n_dev = 1;
+  }
+  if (n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, "too many devices");
+  return PPK_OK;
+}
+
+// a device list -> entries (`parts` has its final size: one per listed device)
+template <class Part>
+int plan_entries(std::vector<Part> &parts, const int *devices) {
+  for (size_t d = 0; d < parts.size(); ++d) {
+    Entry &p = parts[d];
+    p.device = devices[d];
+    if (int rc = ppk_check_device(p.device)) return rc;
+    for (size_t e = 0; e < d; ++e)
+      if (devices[e] == p.device) {
+        if (p.dup == 0) p.leader = (int)e;
+        ++p.dup;
+      }
+    if (p.dup >= kMaxDup) return ppk_fail(PPK_ERR_ARG, "a device may be listed at most 4 times");
+    if (int rc = ppk_check_arch(p.device)) return rc;
+  }
+  return PPK_OK;
+}
+
+// a checked database list -> entries, each with its databases and its band of query rows (consecutive, in list order)
+template <class Part>
+int plan_db_bands(std::vector<Part> &parts, const ppk_db *const *refs, const ppk_db *const *qrys) {
+  std::vector<int> devices(parts.size());
+  for (size_t d = 0; d < parts.size(); ++d) {
+    devices[d] = refs[d]->device;
+    parts[d].ref = refs[d];
+    parts[d].qry = qrys ? qrys[d] : nullptr;
+  }
+  if (int rc = plan_entries(parts, devices.data())) return rc;
+  std::vector<size_t> bounds(parts.size() + 1, 0);
+  if (int rc = ppk_band_split(refs[0]->n, qrys ? qrys[0]->n : 0, (int)parts.size(), bounds.data())) return rc;
+  for (size_t d = 0; d < parts.size(); ++d) {
+    parts[d].q_begin = bounds[d];
+    parts[d].q_end = bounds[d + 1];
+  }
+  return PPK_OK;
+}
+
+// Runs work(entry) for every entry: on the calling thread when there is one, else on one helper thread each while the
+// calling thread calls `waiting` until they are done.  The first failing entry's (rc, err) is the call's error.
+template <class Part, class Work, class Waiting>
+int run_entries(std::vector<Part> &parts, Work work, Waiting waiting) {
+  if (parts.size() == 1) {
+    work(parts[0]);
+  } else {
+    std::vector<PpkTicket> th;
+    for (Part &p : parts) th.push_back(ppk_pool_run([&work, &p]() { work(p); }));
+    for (auto &t : th)
+      while (t->load(std::memory_order_acquire) == 0) waiting();
+  }
+  for (const Part &p : parts)
+    if (p.rc != PPK_OK) return ppk_fail(p.rc, p.err);
+  return PPK_OK;
+}
+template <class Part, class Work>
+int run_entries(std::vector<Part> &parts, Work work) {
+  return run_entries(parts, work, []() { std::this_thread::yield(); });
+}
+
+// A worker's first lines: the entry's device selected for the scope, the two streams of its (device, occurrence)
+// set (compute / copy), and the entry as the place where the worker's error goes.
+struct EntryScope {
+  Entry &p;
+  DeviceGuard g;
+  hipStream_t s[2] = {nullptr, nullptr};
+  bool ok;
+  explicit EntryScope(Entry &part) : p(part), g(part.device) {
+    const int rc = part_streams(g, p.device, p.dup, s);
+    ok = rc == PPK_OK;
+    if (!ok) fail(rc);
+  }
+  void fail(int code) {
+    p.rc = code;
+    p.err = ppk_error();
+  }
+};
+
+// The resident copies of a host-array call's sketches on its device list, for the scope of the call: from (and into)
+// ppk_query's cache (hash of every word, checked before anything runs) or uploaded.  What the cache did not take is
+// destroyed on exit; the call's error message stays.
+struct ResidentCopies {
+  const int *devices;
+  int n_dev;
+  std::vector<const ppk_db *> refs, qrys;
+  std::vector<ppk_db *> owned;
+  ResidentCopies(const int *devs, int n) : devices(devs), n_dev(n) {}
+  ~ResidentCopies() {
+    const std::string keep = ppk_error();
+    for (ppk_db *db : owned) ppk_db_destroy(db);
+    ppk_set_error(keep);
+  }
+  // `pinned` (nullable): per entry a database the call already uses on that device (never evicted)
+  int acquire(const uint64_t *sk, size_t n, size_t nk, size_t s64, size_t bbits, const uint16_t *clu,
+              const std::vector<const ppk_db *> *pinned, std::vector<const ppk_db *> &dbs) {
+    const bool use_cache = ppk_config().db_cache.load() != 0;
+    const uint64_t fp = use_cache ? fingerprint(sk, n * nk * s64 * bbits, clu, n) : 0;
+    dbs.assign((size_t)n_dev, nullptr);
+    for (int d = 0; d < n_dev; ++d) {
+      int first = -1;
+      for (int e = 0; e < d && first < 0; ++e)
+        if (devices[e] == devices[d]) first = e;
+      if (first >= 0) {                       // the same device again: the same copy
+        dbs[(size_t)d] = dbs[(size_t)first];
+        continue;
+      }
+      if (int rc = ppk_check_device(devices[d])) return rc;
+      ppk_db *db = nullptr;
+      bool own = false;
+      int rc = db_acquire(devices[d], sk, n, nk, s64, bbits, clu, fp, use_cache, pinned ? (*pinned)[(size_t)d] : nullptr,
+                          nullptr, &db, &own);
+      if (rc != PPK_OK) return rc;
+      dbs[(size_t)d] = db;
+      if (own) owned.push_back(db);
+    }
+    return PPK_OK;
+  }
+};
+
+// ---- one host query = one job, one part per listed device ---------------------------------------
+struct QueryPart : Entry {
   bool own_ref = false, own_qry = false;
   hipStream_t s = nullptr, sc = nullptr;        // compute / copy
   void *buf[2] = {nullptr, nullptr};
   unsigned long long *d_failed = nullptr;
   hipEvent_t done[2] = {nullptr, nullptr};      // sub-band in buf[i] computed
-  std::atomic<int> db_ready{0};                 // 0 pending, 1 databases resident, -1 failed
-  int prev_same_dev = -1;                       // the entry of the same device before this one, if any
+  std::atomic<int> db_ready{0};                 // 0 pending, 1 databases resident, -1 failed (its `leader` acquires them)
   int work = 0;                                 // index of this entry's device in QueryJob::work
-  int rc = PPK_OK;
-  std::string err;
   unsigned long long failed = 0;
   double upload_ms = 0.0, total_ms = 0.0;
 };
@@ -467,7 +621,6 @@ struct QueryJob {
   HostToucher *toucher = nullptr;
   std::atomic<int> stop{0};                     // interrupt or another part's failure: launch nothing more
   std::atomic<long long> done_chunks{0};
-  std::atomic<int> parts_done{0};
 };
 
 // counters of the last host query (ppk_query_last_stats): what ran side by side
@@ -513,20 +666,19 @@ void run_part(QueryJob &job, std::vector<QueryPart> &parts, int d, bool poll, bo
   QueryPart &p = parts[(size_t)d];
   const double t_begin = now_ms();
   g_trace.mark(d, "thread_start");
+  EntryScope scope(p);
   auto fail = [&](int code) {
-    p.rc = code;
-    p.err = ppk_error();
+    scope.fail(code);
     job.stop.store(1);
   };
-  DeviceGuard g(p.device);
-  hipStream_t ws[2] = {nullptr, nullptr};
-  int rc = part_streams(g, p.device, p.dup, ws);
-  if (rc != PPK_OK) {
+  if (!scope.ok) {
     p.db_ready.store(-1);
-    return fail(rc);
+    job.stop.store(1);
+    return;
   }
-  p.s = ws[0];
-  p.sc = ws[1];
+  p.s = scope.s[0];
+  p.sc = scope.s[1];
+  int rc = PPK_OK;
   g_trace.mark(d, "device_set");
   // 1. resident databases
   if (job.ref_sk) {
@@ -787,37 +939,26 @@ int run_query(QueryJob &job, std::vector<QueryPart> &parts, unsigned long long *
   g_qstats.parts = n_dev;
   g_qstats.upload_ms_max = 0.0;
   g_qstats.part_ms_max = 0.0;
-  if (n_dev == 1) {
-    g_qstats.threads = 0;
-    run_part(job, parts, 0, true, meter);
-  } else {
-    g_qstats.threads = n_dev;
-    std::vector<PpkTicket> th;
-    for (int d = 0; d < n_dev; ++d)
-      th.push_back(ppk_pool_run([&job, &parts, d]() {
-        run_part(job, parts, d, false, false);
-        job.parts_done.fetch_add(1);
-      }));
-    // the calling thread: Ctrl-C and the meter (a Python signal handler only ever runs on this thread)
-    const long long all_chunks = (long long)job.n_chunks;
-    bool was_interrupted = false;
-    while (job.parts_done.load() < n_dev) {
-      if (!was_interrupted && interrupted()) {
-        was_interrupted = true;
-        job.stop.store(1);
-      }
-      if (meter) progress_line((double)job.done_chunks.load() / (double)(all_chunks + 1), false);
-      std::this_thread::sleep_for(std::chrono::microseconds(200));
-    }
-    for (auto &t : th) ppk_pool_wait(t);
-    if (was_interrupted) rc = ppk_fail(PPK_ERR_INTERRUPTED, "interrupted");
-  }
+  g_qstats.threads = n_dev == 1 ? 0 : n_dev;
+  // one entry runs here and polls for itself; while several run, the calling thread has Ctrl-C and the meter (a Python
+  // signal handler only ever runs on this thread)
+  bool was_interrupted = false;
+  rc = run_entries(
+      parts, [&](QueryPart &p) { run_part(job, parts, (int)(&p - parts.data()), n_dev == 1, n_dev == 1 && meter); },
+      [&]() {
+        if (!was_interrupted && interrupted()) {
+          was_interrupted = true;
+          job.stop.store(1);
+        }
+        if (meter) progress_line((double)job.done_chunks.load() / (double)(job.n_chunks + 1), false);
+        std::this_thread::sleep_for(std::chrono::microseconds(200));
+      });
+  if (was_interrupted) rc = ppk_fail(PPK_ERR_INTERRUPTED, "interrupted");
   g_trace.mark(-1, "parts_done");
   toucher.join();
   g_trace.mark(-1, "toucher_joined");
   job.toucher = nullptr;
   for (QueryPart &p : parts) {
-    if (p.rc != PPK_OK && rc == PPK_OK) rc = ppk_fail(p.rc, p.err);
     if (n_failed) *n_failed += p.failed;
     if (p.upload_ms > g_qstats.upload_ms_max) g_qstats.upload_ms_max = p.upload_ms;
     if (p.total_ms > g_qstats.part_ms_max) g_qstats.part_ms_max = p.total_ms;
@@ -838,25 +979,6 @@ int single_device_entries(size_t n_ref, size_t n_qry) {
   const size_t rows = ppk_rows_in_band(n_ref, n_qry, 0, n_qry ? n_qry : n_ref);
   if (hp < 2 || rows < (size_t)ppk_config().host_parts_rows.load()) return 1;
   return hp > kMaxDup ? kMaxDup : (int)hp;
-}
-
-int prepare_parts(std::vector<QueryPart> &parts, const int *devices) {
-  for (size_t d = 0; d < parts.size(); ++d) {
-    QueryPart &p = parts[d];
-    p.device = devices[d];
-    if (int rc = ppk_check_device(p.device)) return rc;
-    for (size_t e = 0; e < d; ++e)
-      if (devices[e] == p.device) {
-        ++p.dup;
-        if (p.leader < 0) p.leader = (int)e;
-        p.prev_same_dev = (int)e;
-      }
-    if (p.dup >= kMaxDup) return ppk_fail(PPK_ERR_ARG, "a device may be listed at most 4 times");
-    DeviceGuard g(p.device);
-    if (!g.ok) return ppk_fail(PPK_ERR_HIP, "cannot select device " + std::to_string(p.device));
-    if (int rc = ppk_check_arch(p.device)) return rc;
-  }
-  return PPK_OK;
 }
 }  // namespace
 
@@ -884,11 +1006,7 @@ extern "C" int ppk_query(const uint64_t *ref_sk, size_t n_ref, const uint64_t *q
   if (!ref_sk || !kmers || !out || n_ref == 0 || nk == 0)
     return ppk_fail(PPK_ERR_ARG, "ppk_query: missing sketches / kmers / output");
   if (n_qry && !qry_sk) return ppk_fail(PPK_ERR_ARG, "ppk_query: n_qry > 0 but no query sketches");
-  const int default_dev = 0;
-  if (!devices || n_dev < 1) {
-    devices = &default_dev;
-    n_dev = 1;
-  }
+  if (int rc = device_list(devices, n_dev)) return rc;
   const bool self = (n_qry == 0);
   if (ppk_rows_in_band(n_ref, n_qry, 0, self ? n_ref : n_qry) == 0) return PPK_OK;  // a single self sample: no pairs
   std::lock_guard<std::mutex> lk(g_query_mu);
@@ -924,7 +1042,7 @@ extern "C" int ppk_query(const uint64_t *ref_sk, size_t n_ref, const uint64_t *q
   int rc = PPK_OK;
   for (int attempt = 0; attempt < 2; ++attempt) {
     std::vector<QueryPart> parts((size_t)n_dev);
-    rc = prepare_parts(parts, devices);
+    rc = plan_entries(parts, devices);
     if (rc != PPK_OK) break;
     QueryJob job;
     job.n_ref = n_ref;
@@ -983,19 +1101,10 @@ extern "C" int ppk_query_dbs(const ppk_db *const *refs, const ppk_db *const *qry
                              const int32_t *kmers, const float *random_tbl, size_t n_clu, int flags,
                              void *out, unsigned long long *n_failed) {
   if (n_failed) *n_failed = 0;
-  if (!refs || n_dev < 1 || n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, "ppk_query_dbs: no databases");
+  if (int rc = check_db_list("ppk_query_dbs", refs, qrys, n_dev, kmers)) return rc;
   if (!out) return ppk_fail(PPK_ERR_ARG, "ppk_query_dbs: out is NULL");
   std::vector<int> devices((size_t)n_dev);
-  for (int d = 0; d < n_dev; ++d) {
-    const ppk_db *q = qrys ? qrys[d] : nullptr;
-    if (!refs[d] || (qrys && !q)) return ppk_fail(PPK_ERR_ARG, "ppk_query_dbs: a database is missing for some device");
-    int rc = ppk_check_pair(refs[d], q, kmers, 0, 0);
-    if (rc != PPK_OK) return rc;
-    if (refs[d]->n != refs[0]->n || refs[d]->nk != refs[0]->nk || refs[d]->s64 != refs[0]->s64 ||
-        refs[d]->bbits != refs[0]->bbits || (q ? q->n : 0) != (qrys && qrys[0] ? qrys[0]->n : 0))
-      return ppk_fail(PPK_ERR_ARG, "ppk_query_dbs: the per-device databases differ in shape");
-    devices[(size_t)d] = refs[d]->device;
-  }
+  for (int d = 0; d < n_dev; ++d) devices[(size_t)d] = refs[d]->device;
   const ppk_db *q0 = qrys ? qrys[0] : nullptr;
   const size_t n_qry = q0 ? q0->n : 0;
   if (ppk_rows_in_band(refs[0]->n, n_qry, 0, q0 ? q0->n : refs[0]->n) == 0) return PPK_OK;
@@ -1008,13 +1117,11 @@ extern "C" int ppk_query_dbs(const ppk_db *const *refs, const ppk_db *const *qry
     devices.assign((size_t)n_dev, refs[0]->device);
   }
   std::vector<QueryPart> parts((size_t)n_dev);
-  int rc = prepare_parts(parts, devices.data());
-  if (rc != PPK_OK) return rc;
+  if (int rc = plan_entries(parts, devices.data())) return rc;
   g_trace.mark(-1, "prepared");
-  for (int d = 0; d < n_dev; ++d) {
+  for (int d = 0; d < n_dev; ++d) {      // (run_part consults `leader` only where it acquires the databases itself)
     parts[(size_t)d].ref = refs[n_given == 1 ? 0 : d];
     parts[(size_t)d].qry = qrys ? qrys[n_given == 1 ? 0 : d] : nullptr;
-    parts[(size_t)d].leader = -1;
   }
   QueryJob job;
   job.n_ref = refs[0]->n;
@@ -1432,10 +1539,7 @@ extern "C" int ppk_generate_tuples(const int32_t *assignments, size_t n_rows, in
 // concatenate to the list of the whole matrix in reference row order.  BASELINE config 5 for a single
 // process: 100 000 genomes on N GPUs, 16 bytes per edge over PCIe instead of 8 bytes per pair.
 namespace {
-struct EdgePart {
-  int device = 0, dup = 0;
-  const ppk_db *ref = nullptr, *qry = nullptr;
-  size_t q_begin = 0, q_end = 0;
+struct EdgePart : Entry {
   // The band's list, in row order: `spill` (host; normally empty) followed by the first n_dev entries of the entry's
   // kept device buffer.  The list STAYS on the device until every entry's count is known: it then goes straight to
   // its place in the caller's array (until round 5 it went piece by piece into a growing host vector -- value-
@@ -1444,26 +1548,19 @@ struct EdgePart {
   std::vector<long long> spill;
   long long *d_list = nullptr;
   size_t n_dev = 0;
-  hipStream_t s = nullptr;
+  size_t at = 0;                 // where the list begins in the whole one (in long longs: two per entry)
   unsigned long long failed = 0;
-  int rc = PPK_OK;
-  std::string err;
   size_t count() const { return spill.size() / 2 + n_dev; }
 };
 
 // model == NULL: the line boundary (slope ... inclusive); else the BGMM label test (ppk_dist_bgmm_edges_dev)
 void run_edge_part(EdgePart &p, const int32_t *kmers, const float *random_tbl, size_t n_clu, int flags, int slope,
                    float x_max, float y_max, float scale_x, float scale_y, int inclusive, const ppk_bgmm *model) {
-  auto fail = [&](int code) {
-    p.rc = code;
-    p.err = ppk_error();
-  };
-  DeviceGuard g(p.device);
-  hipStream_t ws[2] = {nullptr, nullptr};
-  int rc = part_streams(g, p.device, p.dup, ws);
-  if (rc != PPK_OK) return fail(rc);
-  hipStream_t s = ws[0];
-  p.s = s;
+  EntryScope scope(p);
+  if (!scope.ok) return;
+  auto fail = [&](int code) { scope.fail(code); };
+  hipStream_t s = scope.s[0];
+  int rc = PPK_OK;
   const size_t n_qry = p.qry ? p.qry->n : 0;
   if (ppk_rows_in_band(p.ref->n, n_qry, p.q_begin, p.q_end) == 0) return;
   // the band in pieces whose edge bitmask (one bit per pair) stays below 2 GiB: 100 000 genomes are one piece,
@@ -1564,46 +1661,20 @@ int query_edges_dbs_locked(const ppk_db *const *refs, const ppk_db *const *qrys,
                            unsigned long long *n_failed) {
   if (n_edges) *n_edges = 0;
   if (n_failed) *n_failed = 0;
-  if (!refs || n_dev < 1 || n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, "ppk_query_edges_dbs: no databases");
+  if (int rc = check_db_list("ppk_query_edges_dbs", refs, qrys, n_dev, kmers)) return rc;
   if (!n_edges) return ppk_fail(PPK_ERR_ARG, "n_edges is NULL");
   if (slope < 0 || slope > 2) return ppk_fail(PPK_ERR_ARG, "slope must be 0, 1 or 2");
   if (flags & (PPK_FLAG_JACCARD | PPK_FLAG_COUNTS)) return ppk_fail(PPK_ERR_ARG, "edge output excludes the jaccard/counts flags");
   std::vector<EdgePart> parts((size_t)n_dev);
-  for (int d = 0; d < n_dev; ++d) {
-    const ppk_db *q = qrys ? qrys[d] : nullptr;
-    if (!refs[d] || (qrys && !q)) return ppk_fail(PPK_ERR_ARG, "ppk_query_edges_dbs: a database is missing for some device");
-    int rc = ppk_check_pair(refs[d], q, kmers, 0, 0);
-    if (rc != PPK_OK) return rc;
-    if (refs[d]->n != refs[0]->n || refs[d]->nk != refs[0]->nk || refs[d]->s64 != refs[0]->s64 ||
-        refs[d]->bbits != refs[0]->bbits || (q ? q->n : 0) != (qrys && qrys[0] ? qrys[0]->n : 0))
-      return ppk_fail(PPK_ERR_ARG, "ppk_query_edges_dbs: the per-device databases differ in shape");
-    EdgePart &p = parts[(size_t)d];
-    p.device = refs[d]->device;
-    for (int e = 0; e < d; ++e) p.dup += parts[(size_t)e].device == p.device;
-    if (p.dup >= kMaxDup) return ppk_fail(PPK_ERR_ARG, "a device may be listed at most 4 times");
-    if (int rc2 = ppk_check_arch(p.device)) return rc2;
-    p.ref = refs[d];
-    p.qry = q;
-  }
-  const size_t n_ref = refs[0]->n, n_qry = qrys ? qrys[0]->n : 0;
-  std::vector<size_t> bounds((size_t)n_dev + 1, 0);
-  int rc = ppk_band_split(n_ref, n_qry, n_dev, bounds.data());
-  if (rc != PPK_OK) return rc;
-  std::vector<PpkTicket> th;
-  for (int d = 0; d < n_dev; ++d) {
-    EdgePart &p = parts[(size_t)d];
-    p.q_begin = bounds[(size_t)d];
-    p.q_end = bounds[(size_t)d + 1];
-    auto work = [&p, kmers, random_tbl, n_clu, flags, slope, x_max, y_max, scale_x, scale_y, inclusive, model]() {
+  int rc = plan_db_bands(parts, refs, qrys);
+  if (rc == PPK_OK)
+    rc = run_entries(parts, [&](EdgePart &p) {
       run_edge_part(p, kmers, random_tbl, n_clu, flags, slope, x_max, y_max, scale_x, scale_y, inclusive, model);
-    };
-    if (n_dev == 1) work();
-    else th.push_back(ppk_pool_run(work));
-  }
-  for (auto &t : th) ppk_pool_wait(t);
+    });
+  if (rc != PPK_OK) return rc;
   size_t total = 0;
   for (EdgePart &p : parts) {
-    if (p.rc != PPK_OK) return ppk_fail(p.rc, p.err);
+    p.at = total * 2;
     total += p.count();
     if (n_failed) *n_failed += p.failed;
   }
@@ -1615,11 +1686,8 @@ int query_edges_dbs_locked(const ppk_db *const *refs, const ppk_db *const *qrys,
     r.arrays = 1;
     r.n = total;
     r.host.resize(total * 2);
-    size_t off = 0;
-    for (EdgePart &p : parts) {
-      if ((rc = fetch_edge_part(p, r.host.data() + off)) != PPK_OK) return rc;
-      off += p.count() * 2;
-    }
+    for (EdgePart &p : parts)
+      if ((rc = fetch_edge_part(p, r.host.data() + p.at)) != PPK_OK) return rc;
     parked_put(std::move(r));
     return ppk_fail(PPK_ERR_CAPACITY, "output too small: need " + std::to_string(total) + " entries (parked: ppk_parked_fetch)");
   }
@@ -1627,29 +1695,26 @@ int query_edges_dbs_locked(const ppk_db *const *refs, const ppk_db *const *qrys,
   // every band's list goes from its device straight to its place in the caller's array, whose pages (a fresh array:
   // never touched) are faulted in ahead of the copies by the helper threads, 2 MB at a time
   HostToucher toucher(ij_out, total * 16);
-  std::vector<PpkTicket> fetchers;
-  std::vector<int> frc(parts.size(), PPK_OK);
-  std::vector<std::string> ferr(parts.size());
-  size_t off = 0;
-  for (size_t d = 0; d < parts.size(); ++d) {
-    EdgePart &p = parts[d];
-    const size_t at = off;
-    off += p.count() * 2;
-    if (p.count() == 0) continue;
-    auto work = [&p, &toucher, &frc, &ferr, d, at, ij_out]() {
-      toucher.wait((at + p.count() * 2) * sizeof(long long));
-      frc[d] = fetch_edge_part(p, ij_out + at);
-      if (frc[d] != PPK_OK) ferr[d] = ppk_error();
-    };
-    if (parts.size() == 1) work();
-    else fetchers.push_back(ppk_pool_run(work));
-  }
-  for (auto &t : fetchers) ppk_pool_wait(t);
-  for (size_t d = 0; d < parts.size(); ++d)
-    if (frc[d] != PPK_OK) return ppk_fail(frc[d], ferr[d]);
-  return PPK_OK;
+  return run_entries(parts, [&](EdgePart &p) {
+    if (p.count() == 0) return;
+    toucher.wait((p.at + p.count() * 2) * sizeof(long long));
+    if ((p.rc = fetch_edge_part(p, ij_out + p.at)) != PPK_OK) p.err = ppk_error();
+  });
 }
 
+// the resident-handle entry points: the lock, and the call's two marks on the host trace
+int query_edges_dbs_traced(const ppk_db *const *refs, const ppk_db *const *qrys, int n_dev, const int32_t *kmers,
+                           const float *random_tbl, size_t n_clu, int flags, int slope, float x_max, float y_max,
+                           float scale_x, float scale_y, int inclusive, const ppk_bgmm *model, long long *ij_out,
+                           size_t cap, size_t *n_edges, unsigned long long *n_failed) {
+  std::lock_guard<std::mutex> lk(g_query_mu);
+  g_trace.t0 = now_ms();
+  g_trace.mark(-1, "e_enter");
+  const int rc = query_edges_dbs_locked(refs, qrys, n_dev, kmers, random_tbl, n_clu, flags, slope, x_max, y_max, scale_x,
+                                        scale_y, inclusive, model, ij_out, cap, n_edges, n_failed);
+  g_trace.mark(-1, "e_return", n_edges ? (long long)*n_edges : -1);
+  return rc;
+}
 }  // namespace
 
 extern "C" int ppk_query_edges_dbs(const ppk_db *const *refs, const ppk_db *const *qrys, int n_dev,
@@ -1657,13 +1722,8 @@ extern "C" int ppk_query_edges_dbs(const ppk_db *const *refs, const ppk_db *cons
                                    int slope, float x_max, float y_max, float scale_x, float scale_y,
                                    int inclusive, long long *ij_out, size_t cap, size_t *n_edges,
                                    unsigned long long *n_failed) {
-  std::lock_guard<std::mutex> lk(g_query_mu);
-  g_trace.t0 = now_ms();
-  g_trace.mark(-1, "e_enter");
-  const int rc = query_edges_dbs_locked(refs, qrys, n_dev, kmers, random_tbl, n_clu, flags, slope, x_max, y_max, scale_x,
-                                        scale_y, inclusive, nullptr, ij_out, cap, n_edges, n_failed);
-  g_trace.mark(-1, "e_return", n_edges ? (long long)*n_edges : -1);
-  return rc;
+  return query_edges_dbs_traced(refs, qrys, n_dev, kmers, random_tbl, n_clu, flags, slope, x_max, y_max, scale_x, scale_y,
+                                inclusive, nullptr, ij_out, cap, n_edges, n_failed);
 }
 
 // the same with the label test of a fitted BGMM (queryDatabase -> BGMMFit.assign -> generateTuples)
@@ -1674,44 +1734,9 @@ extern "C" int ppk_query_bgmm_edges_dbs(const ppk_db *const *refs, const ppk_db 
   if (n_edges) *n_edges = 0;
   if (n_failed) *n_failed = 0;
   if (!model) return ppk_fail(PPK_ERR_ARG, "model is NULL");
-  std::lock_guard<std::mutex> lk(g_query_mu);
-  g_trace.t0 = now_ms();
-  g_trace.mark(-1, "e_enter");
-  const int rc = query_edges_dbs_locked(refs, qrys, n_dev, kmers, random_tbl, n_clu, flags, 2, 0.f, 0.f, 1.f, 1.f, 0,
-                                        model, ij_out, cap, n_edges, n_failed);
-  g_trace.mark(-1, "e_return", n_edges ? (long long)*n_edges : -1);
-  return rc;
+  return query_edges_dbs_traced(refs, qrys, n_dev, kmers, random_tbl, n_clu, flags, 2, 0.f, 0.f, 1.f, 1.f, 0, model, ij_out,
+                                cap, n_edges, n_failed);
 }
-
-namespace {
-// the resident copies of a host sketch array on the listed devices: from (and into) ppk_query's cache.  `pinned`
-// (nullable): per entry a database the call already uses on that device (never evicted).
-int acquire_on_devices(const uint64_t *sk, size_t n, size_t nk, size_t s64, size_t bbits, const uint16_t *clu,
-                       const int *devices, int n_dev, const std::vector<const ppk_db *> *pinned,
-                       std::vector<const ppk_db *> &dbs, std::vector<ppk_db *> &owned) {
-  const bool use_cache = ppk_config().db_cache.load() != 0;
-  const uint64_t fp = use_cache ? fingerprint(sk, n * nk * s64 * bbits, clu, n) : 0;
-  dbs.assign((size_t)n_dev, nullptr);
-  for (int d = 0; d < n_dev; ++d) {
-    int first = -1;
-    for (int e = 0; e < d && first < 0; ++e)
-      if (devices[e] == devices[d]) first = e;
-    if (first >= 0) {                       // the same device again: the same copy
-      dbs[(size_t)d] = dbs[(size_t)first];
-      continue;
-    }
-    if (int rc = ppk_check_device(devices[d])) return rc;
-    ppk_db *db = nullptr;
-    bool own = false;
-    int rc = db_acquire(devices[d], sk, n, nk, s64, bbits, clu, fp, use_cache, pinned ? (*pinned)[(size_t)d] : nullptr,
-                        nullptr, &db, &own);
-    if (rc != PPK_OK) return rc;
-    dbs[(size_t)d] = db;
-    if (own) owned.push_back(db);
-  }
-  return PPK_OK;
-}
-}  // namespace
 
 extern "C" int ppk_query_edges(const uint64_t *ref_sk, size_t n_ref, const uint64_t *qry_sk, size_t n_qry,
                                const int32_t *kmers, size_t nk, size_t sketchsize64, size_t bbits,
@@ -1723,25 +1748,14 @@ extern "C" int ppk_query_edges(const uint64_t *ref_sk, size_t n_ref, const uint6
   if (n_failed) *n_failed = 0;
   if (!ref_sk || !kmers || n_ref == 0 || nk == 0) return ppk_fail(PPK_ERR_ARG, "ppk_query_edges: missing sketches / kmers");
   if (n_qry && !qry_sk) return ppk_fail(PPK_ERR_ARG, "ppk_query_edges: n_qry > 0 but no query sketches");
-  const int default_dev = 0;
-  if (!devices || n_dev < 1) {
-    devices = &default_dev;
-    n_dev = 1;
-  }
-  if (n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, "too many devices");
+  if (int rc = device_list(devices, n_dev)) return rc;
   std::lock_guard<std::mutex> lk(g_query_mu);
-  // the resident copies: from ppk_query's cache (hash of every word, checked here before anything runs) or uploaded
-  std::vector<const ppk_db *> refs, qrys;
-  std::vector<ppk_db *> owned;
-  int rc = acquire_on_devices(ref_sk, n_ref, nk, sketchsize64, bbits, ref_clu, devices, n_dev, nullptr, refs, owned);
-  if (rc == PPK_OK && n_qry)
-    rc = acquire_on_devices(qry_sk, n_qry, nk, sketchsize64, bbits, qry_clu, devices, n_dev, &refs, qrys, owned);
+  ResidentCopies on(devices, n_dev);
+  int rc = on.acquire(ref_sk, n_ref, nk, sketchsize64, bbits, ref_clu, nullptr, on.refs);
+  if (rc == PPK_OK && n_qry) rc = on.acquire(qry_sk, n_qry, nk, sketchsize64, bbits, qry_clu, &on.refs, on.qrys);
   if (rc == PPK_OK)
-    rc = query_edges_dbs_locked(refs.data(), n_qry ? qrys.data() : nullptr, n_dev, kmers, random_tbl, n_clu, flags, slope,
-                                x_max, y_max, scale_x, scale_y, inclusive, nullptr, ij_out, cap, n_edges, n_failed);
-  const std::string keep = ppk_error();
-  for (ppk_db *db : owned) ppk_db_destroy(db);
-  if (rc != PPK_OK) ppk_set_error(keep);
+    rc = query_edges_dbs_locked(on.refs.data(), n_qry ? on.qrys.data() : nullptr, n_dev, kmers, random_tbl, n_clu, flags,
+                                slope, x_max, y_max, scale_x, scale_y, inclusive, nullptr, ij_out, cap, n_edges, n_failed);
   return rc;
 }
 
@@ -1753,44 +1767,34 @@ extern "C" int ppk_query_edges(const uint64_t *ref_sk, size_t n_ref, const uint6
 // the reference's stable order (src/extend.cpp:266-279).  A pair is a candidate for both of its samples and
 // belongs to exactly one band, so a sample's true neighbours are among the best knn of every band's list.
 namespace {
-struct KnnPart {
-  int device = 0, dup = 0;
-  const ppk_db *db = nullptr, *qry = nullptr;
-  size_t q_begin = 0, q_end = 0;
+struct KnnPart : Entry {
   std::vector<long long> j;
   std::vector<float> d;
-  int rc = PPK_OK;
-  std::string err;
 };
 
 void run_knn_part(KnnPart &p, const int32_t *kmers, const float *random_tbl, size_t n_clu, int flags, int knn,
                   int dist_col) {
-  auto fail = [&](int code) {
-    p.rc = code;
-    p.err = ppk_error();
-  };
-  DeviceGuard g(p.device);
-  hipStream_t ws[2] = {nullptr, nullptr};
-  int rc = part_streams(g, p.device, p.dup, ws);
-  if (rc != PPK_OK) return fail(rc);
-  const size_t m = (p.db->n + (p.qry ? p.qry->n : 0)) * (size_t)knn;
+  EntryScope scope(p);
+  if (!scope.ok) return;
+  const hipStream_t s = scope.s[0];
+  const size_t m = (p.ref->n + (p.qry ? p.qry->n : 0)) * (size_t)knn;
   long long *d_i = nullptr, *d_j = nullptr;
   float *d_d = nullptr;
   auto done = [&](int code) {
     if (d_i) (void)hipFree(d_i);
     if (d_j) (void)hipFree(d_j);
     if (d_d) (void)hipFree(d_d);
-    if (code != PPK_OK) fail(code);
+    if (code != PPK_OK) scope.fail(code);
   };
   if (hipMalloc(reinterpret_cast<void **>(&d_i), m * 8) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&d_j), m * 8) != hipSuccess ||
       hipMalloc(reinterpret_cast<void **>(&d_d), m * 4) != hipSuccess)
     return done(ppk_fail(PPK_ERR_HIP, "hipMalloc(neighbour lists) failed"));
-  rc = ppk_knn_band_dev(p.db, p.qry, kmers, random_tbl, n_clu, flags, knn, dist_col, p.q_begin, p.q_end, -1, d_i, d_j, d_d,
-                        nullptr, ws[0]);
+  const int rc = ppk_knn_band_dev(p.ref, p.qry, kmers, random_tbl, n_clu, flags, knn, dist_col, p.q_begin, p.q_end, -1, d_i,
+                                  d_j, d_d, nullptr, s);
   if (rc != PPK_OK) return done(rc);
   p.j.resize(m);
   p.d.resize(m);
-  if (hipStreamSynchronize(ws[0]) != hipSuccess || hipMemcpy(p.j.data(), d_j, m * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(p.j.data(), d_j, m * 8, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(p.d.data(), d_d, m * 4, hipMemcpyDeviceToHost) != hipSuccess)
     return done(ppk_fail(PPK_ERR_HIP, "neighbour lists: execution or download failed"));
   done(PPK_OK);
@@ -1802,41 +1806,14 @@ void run_knn_part(KnnPart &p, const int32_t *kmers, const float *random_tbl, siz
 int knn_lists_locked(const ppk_db *const *dbs, const ppk_db *const *qrys, int n_dev, const int32_t *kmers,
                      const float *random_tbl, size_t n_clu, int flags, int knn, int dist_col,
                      std::vector<long long> &j_out, std::vector<float> &d_out) {
-  if (!dbs || n_dev < 1 || n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, "neighbour lists: no databases");
+  if (int rc = check_db_list("neighbour lists", dbs, qrys, n_dev, kmers)) return rc;
   if (knn < 1 || knn > 32) return ppk_fail(PPK_ERR_ARG, "knn must be in [1, 32]");
   std::vector<KnnPart> parts((size_t)n_dev);
-  for (int d = 0; d < n_dev; ++d) {
-    const ppk_db *q = qrys ? qrys[d] : nullptr;
-    if (!dbs[d] || (qrys && !q)) return ppk_fail(PPK_ERR_ARG, "neighbour lists: a database is missing for some device");
-    if (dbs[d]->n != dbs[0]->n || dbs[d]->nk != dbs[0]->nk || dbs[d]->s64 != dbs[0]->s64 || dbs[d]->bbits != dbs[0]->bbits ||
-        (q && (q->n != qrys[0]->n || q->device != dbs[d]->device)))
-      return ppk_fail(PPK_ERR_ARG, "neighbour lists: the per-device databases differ in shape or device");
-    KnnPart &p = parts[(size_t)d];
-    p.device = dbs[d]->device;
-    for (int e = 0; e < d; ++e) p.dup += parts[(size_t)e].device == p.device;
-    if (p.dup >= kMaxDup) return ppk_fail(PPK_ERR_ARG, "a device may be listed at most 4 times");
-    if (int rc = ppk_check_arch(p.device)) return rc;
-    p.db = dbs[d];
-    p.qry = q;
-  }
-  const size_t n_ref = dbs[0]->n, n_qry = qrys ? qrys[0]->n : 0, n = n_ref + n_qry, k = (size_t)knn;
-  std::vector<size_t> bounds((size_t)n_dev + 1, 0);
-  int rc = ppk_band_split(n_ref, n_qry, n_dev, bounds.data());
+  int rc = plan_db_bands(parts, dbs, qrys);
+  if (rc == PPK_OK)
+    rc = run_entries(parts, [&](KnnPart &p) { run_knn_part(p, kmers, random_tbl, n_clu, flags, knn, dist_col); });
   if (rc != PPK_OK) return rc;
-  std::vector<PpkTicket> th;
-  for (int d = 0; d < n_dev; ++d) {
-    KnnPart &p = parts[(size_t)d];
-    p.q_begin = bounds[(size_t)d];
-    p.q_end = bounds[(size_t)d + 1];
-    auto work = [&p, kmers, random_tbl, n_clu, flags, knn, dist_col]() {
-      run_knn_part(p, kmers, random_tbl, n_clu, flags, knn, dist_col);
-    };
-    if (n_dev == 1) work();
-    else th.push_back(ppk_pool_run(work));
-  }
-  for (auto &t : th) ppk_pool_wait(t);
-  for (KnnPart &p : parts)
-    if (p.rc != PPK_OK) return ppk_fail(p.rc, p.err);
+  const size_t n = dbs[0]->n + (qrys ? qrys[0]->n : 0), k = (size_t)knn;
   if (n_dev == 1) {
     j_out.swap(parts[0].j);
     d_out.swap(parts[0].d);
@@ -1875,6 +1852,16 @@ int knn_lists_locked(const ppk_db *const *dbs, const ppk_db *const *qrys, int n_
   return PPK_OK;
 }
 
+// merged lists -> the caller's (i, j, dist) arrays of n * k slots; fewer than knn other samples: the reference leaves
+// (i, 0, 0.0) in the slot (src/extend.cpp:266-279)
+void knn_fill(const std::vector<long long> &j, const std::vector<float> &d, size_t n, size_t k, long long *i_out,
+              long long *j_out, float *d_out) {
+  for (size_t e = 0; e < n * k; ++e) {
+    i_out[e] = (long long)(e / k);
+    j_out[e] = j[e] < 0 ? 0 : j[e];
+    d_out[e] = j[e] < 0 ? 0.0f : d[e];
+  }
+}
 }  // namespace
 
 extern "C" int ppk_query_knn_dbs(const ppk_db *const *dbs, int n_dev, const int32_t *kmers, const float *random_tbl,
@@ -1885,15 +1872,8 @@ extern "C" int ppk_query_knn_dbs(const ppk_db *const *dbs, int n_dev, const int3
   std::vector<long long> j;
   std::vector<float> d;
   int rc = knn_lists_locked(dbs, nullptr, n_dev, kmers, random_tbl, n_clu, flags, knn, dist_col, j, d);
-  if (rc != PPK_OK) return rc;
-  const size_t k = (size_t)knn, m = dbs[0]->n * k;
-  for (size_t e = 0; e < m; ++e) {
-    i_out[e] = (long long)(e / k);
-    // fewer than knn other samples: the reference leaves (i, 0, 0.0) in the slot (src/extend.cpp:266-279)
-    j_out[e] = j[e] < 0 ? 0 : j[e];
-    d_out[e] = j[e] < 0 ? 0.0f : d[e];
-  }
-  return PPK_OK;
+  if (rc == PPK_OK) knn_fill(j, d, dbs[0]->n, (size_t)knn, i_out, j_out, d_out);
+  return rc;
 }
 
 extern "C" int ppk_query_knn(const uint64_t *sk, size_t n, const int32_t *kmers, size_t nk, size_t sketchsize64,
@@ -1902,32 +1882,16 @@ extern "C" int ppk_query_knn(const uint64_t *sk, size_t n, const int32_t *kmers,
                              long long *j_out, float *d_out) {
   if (!sk || !kmers || n == 0 || nk == 0) return ppk_fail(PPK_ERR_ARG, "ppk_query_knn: missing sketches / kmers");
   if (!i_out || !j_out || !d_out) return ppk_fail(PPK_ERR_ARG, "NULL output");
-  const int default_dev = 0;
-  if (!devices || n_dev < 1) {
-    devices = &default_dev;
-    n_dev = 1;
-  }
-  if (n_dev > kMaxParts) return ppk_fail(PPK_ERR_ARG, "too many devices");
+  if (int rc = device_list(devices, n_dev)) return rc;
   std::lock_guard<std::mutex> lk(g_query_mu);
-  std::vector<const ppk_db *> dbs;
-  std::vector<ppk_db *> owned;
+  ResidentCopies on(devices, n_dev);
   std::vector<long long> j;
   std::vector<float> d;
-  int rc = acquire_on_devices(sk, n, nk, sketchsize64, bbits, clu, devices, n_dev, nullptr, dbs, owned);
-  if (rc == PPK_OK) rc = knn_lists_locked(dbs.data(), nullptr, n_dev, kmers, random_tbl, n_clu, flags, knn, dist_col, j, d);
-  const std::string keep = ppk_error();
-  for (ppk_db *db : owned) ppk_db_destroy(db);
-  if (rc != PPK_OK) {
-    ppk_set_error(keep);
-    return rc;
-  }
-  const size_t k = (size_t)knn;
-  for (size_t e = 0; e < n * k; ++e) {
-    i_out[e] = (long long)(e / k);
-    j_out[e] = j[e] < 0 ? 0 : j[e];
-    d_out[e] = j[e] < 0 ? 0.0f : d[e];
-  }
-  return PPK_OK;
+  int rc = on.acquire(sk, n, nk, sketchsize64, bbits, clu, nullptr, on.refs);
+  if (rc == PPK_OK)
+    rc = knn_lists_locked(on.refs.data(), nullptr, n_dev, kmers, random_tbl, n_clu, flags, knn, dist_col, j, d);
+  if (rc == PPK_OK) knn_fill(j, d, n, (size_t)knn, i_out, j_out, d_out);
+  return rc;
 }
 
 // ---- poppunk_refine.extend without the dense matrices ------------------------------------------------------
