@@ -101,6 +101,9 @@ int ppk_device_count(int *n);
  *                          allocated: a chunk holds as many pairs as keep 2 x pairs x (bytes of one sample's sketch)
  *                          within four fifths of it (a scratch slot is allocated with a quarter to spare); at least one
  *     "pairs_chunk" (0)    pairs per chunk, whatever the cap says (0 = from the cap; tests)
+ *   edge lists with rows (ppk_dist_edges_rows_dev, ppk_dist_bgmm_edges_rows_dev)
+ *     "edge_rows_fused" (1)  the rows come out of the tile kernel's own epilogue where the band runs whole tiles of the
+ *                          plain packed kernels; 0 = always the edge call followed by the list kernel (same results)
  *   neighbours from tiles
  *     "knn_list" (0 = sized from n and knn), "knn_warm" (32), "knn_cut" (4)  the candidate list, its staged
  *                          opening and where it is cut back to the best knn per sample
@@ -355,6 +358,28 @@ int ppk_dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmer
                        unsigned long long *d_n_edges,
                        unsigned long long *d_n_failed, void *stream);
 
+/* ppk_dist_edges_dev, and with every edge its distances: what process_weights, a minimum spanning tree or a refine fit
+ * read of a fused edge list, without a second pass over the sketches.  d_edges, *d_n_edges, cap and d_n_failed are
+ * exactly what ppk_dist_edges_dev gives (same order: reference row order).
+ *   d_rows             : device float [cap][2]; row e = the UNSCALED (core, accessory) of edge e, the bits ppk_dist_dev
+ *                        writes into that pair's row of the dense result (same databases, k list, random table, flags
+ *                        and ext_* options; (0, 0) for a pair with fewer than two usable k).  The scales only enter
+ *                        the boundary test.  Calls with the same input give the same bytes.
+ *                        When *d_n_edges > cap, d_edges holds the first cap edges and d_rows is UNSPECIFIED: run again
+ *                        with the exact size.  NULL: PPK_ERR_ARG.
+ * A band of whole tiles of the plain packed kernels (two to four count dwords, not k-split, no wide k window -- a
+ * 10 000-genome self job and up) emits the rows from the same pass: 8 bytes of scratch per mask word (one word per
+ * query row and 64 refs) and 8 per edge of cap.  Every other shape runs ppk_dist_edges_dev and then the list kernel of
+ * ppk_dist_pairs_dev on its edges (one more synchronisation): the same bits.  Option "edge_rows_fused" 0 forces that
+ * two-step; ppk_last_kernel_name() tells which ran ("...,rows>" / "... + pairs list"). */
+int ppk_dist_edges_rows_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers,
+                            const float *random_tbl, size_t n_clu, int flags,
+                            size_t q_begin, size_t q_end, int slope, float x_max,
+                            float y_max, float scale_x, float scale_y, int inclusive,
+                            long long *d_edges, float *d_rows, size_t cap,
+                            unsigned long long *d_n_edges,
+                            unsigned long long *d_n_failed, void *stream);
+
 /* Kernel 1 for a LIST of pairs: the rows ppk_dist_dev would write for them, without the matrix.  What the reference
  * looks up in its dense matrix -- scripts/poppunk_add_weights.py, process_weights (PopPUNK/network.py:646-674), the
  * subsample a model is fitted on (PopPUNK/models.py:246-254,:520-534) -- is computed here from the resident sketches.
@@ -511,6 +536,12 @@ int ppk_dist_bgmm_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t 
                             const float *random_tbl, size_t n_clu, int flags, size_t q_begin, size_t q_end,
                             const ppk_bgmm *model, long long *d_edges, size_t cap,
                             unsigned long long *d_n_edges, unsigned long long *d_n_failed, void *stream);
+/* ... and with every edge its unscaled (core, accessory) row: d_rows and everything about it as in
+ * ppk_dist_edges_rows_dev. */
+int ppk_dist_bgmm_edges_rows_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers,
+                                 const float *random_tbl, size_t n_clu, int flags, size_t q_begin, size_t q_end,
+                                 const ppk_bgmm *model, long long *d_edges, float *d_rows, size_t cap,
+                                 unsigned long long *d_n_edges, unsigned long long *d_n_failed, void *stream);
 
 /* Host form, several devices: ppk_query_edges_dbs with the BGMM label test -- the same band split, pieces (option
  * "chunk_rows"), concatenation in row order and PPK_ERR_CAPACITY -> ppk_parked_fetch hand-over; the list does not
@@ -746,6 +777,17 @@ int ppk_dbscan_assign(const float *dist, size_t n_rows, const ppk_dbscan *model,
  * reference's line_dist as it stands), early-exit filter, bisection over nested boundaries, guessed end indices (evenly
  * spaced parallel boundaries, the 1-D sweep only: one_d != 0)}. */
 int ppk_sweep_plan(const float *x_max, const float *y_max, size_t n_off, int slope, int one_d, int out[4]);
+/* The boundaries of a 1-D sweep: (x_max[o], y_max[o]) of offset o along the line (x0, y0) -> (x1, y1), with the
+ * float / double mix of src/boundary.cpp:161-186 -- the one statement of them, which ppk_threshold_iterate_1d_dev
+ * reads too.  Host arrays of n_off entries (offsets sorted ascending, at most 1023); no device is touched. */
+int ppk_sweep_boundaries_1d(const double *offsets, size_t n_off, int slope, float x0, float y0, float x1, float y1,
+                            float *x_max, float *y_max);
+/* The sweep level of LISTED rows: d_level[p] (device int32 [n_rows]) = the offset index the two sweeps below assign to a
+ * row with the coordinates of row p of d_rows (device float [n_rows][2], any list: 4-byte alignment is enough) -- the
+ * first of the boundaries (x_max[o], y_max[o]) (HOST arrays, n_off <= 1023) that holds it -- and n_off for a row that
+ * none of them lists.  The sweeps' own per-row statement, every boundary evaluated; enqueues only. */
+int ppk_sweep_levels_dev(const float *d_rows, size_t n_rows, const float *x_max, const float *y_max, size_t n_off,
+                         int slope, int32_t *d_level, void *stream);
 
 /* replaces poppunk_refine.thresholdIterate1D (src/python_bindings.cpp:49-60;
  * src/boundary.cpp:154-210; caller PopPUNK/refine.py:190-200).  `offsets`

@@ -202,6 +202,14 @@ SIGNATURES = {
     "ppk_dist_edges_dev": (C.c_int, [_vp, _vp, _i32p, _f32p, _sz, C.c_int, _sz, _sz, C.c_int,
                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _vp,
                                      _sz, _vp, _vp, _vp]),
+    "ppk_dist_edges_rows_dev": (C.c_int, [_vp, _vp, _i32p, _f32p, _sz, C.c_int, _sz, _sz, C.c_int,
+                                          C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _vp, _vp,
+                                          _sz, _vp, _vp, _vp]),
+    "ppk_dist_bgmm_edges_rows_dev": (C.c_int, [_vp, _vp, _i32p, _f32p, _sz, C.c_int, _sz, _sz, _bgmmp, _vp, _vp, _sz,
+                                               _vp, _vp, _vp]),
+    "ppk_sweep_boundaries_1d": (C.c_int, [C.POINTER(C.c_double), _sz, C.c_int, C.c_float, C.c_float, C.c_float,
+                                          C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ppk_sweep_levels_dev": (C.c_int, [_vp, _sz, C.POINTER(C.c_float), C.POINTER(C.c_float), _sz, C.c_int, _vp, _vp]),
     "ppk_assign_threshold_dev": (C.c_int, [_vp, _sz, C.c_int, C.c_float, C.c_float, _vp, _vp]),
     "ppk_edge_threshold_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, C.c_float, C.c_float, C.c_int,
                                          _vp, _sz, _vp, _vp]),

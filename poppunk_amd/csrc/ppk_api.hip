@@ -71,6 +71,7 @@ const OptionEntry kOptions[] = {
     {"ksplit_scratch_mb", "PPK_KSPLIT_SCRATCH_MB", &PpkConfig::ksplit_scratch_mb},
     {"pairs_scratch_mb", "PPK_PAIRS_SCRATCH_MB", &PpkConfig::pairs_scratch_mb},
     {"pairs_chunk", "PPK_PAIRS_CHUNK", &PpkConfig::pairs_chunk},
+    {"edge_rows_fused", "PPK_EDGE_ROWS_FUSED", &PpkConfig::edge_rows_fused},
     {"silhouette_scratch_mb", "PPK_SILHOUETTE_SCRATCH_MB", &PpkConfig::silhouette_scratch_mb},
     {"silhouette_band", "PPK_SILHOUETTE_BAND", &PpkConfig::silhouette_band},
     {"silhouette_window", "PPK_SILHOUETTE_WINDOW", &PpkConfig::silhouette_window},
@@ -629,14 +630,43 @@ extern "C" int ppk_dist_pairs(const ppk_db *ref, const ppk_db *qry, const int32_
   });
 }
 
-// The fused edge list of a band: the line boundary (model == NULL) or the label test of a BGMM model
+// The two-step of the edge calls with rows: the unscaled rows of the first min(*d_n_edges, cap) edges of a finished edge
+// call, through the list kernel (one read-back of the count; failures were counted by the edge call)
+static int rows_of_edges(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, const float *random_tbl, size_t n_clu,
+                         int flags, const long long *d_edges, size_t cap, const unsigned long long *d_n_edges, float *d_rows,
+                         hipStream_t s) {
+  const unsigned long long *h = nullptr;
+  int rc = ppk_read_back(ref->device, s, {{d_n_edges, 8}}, &h);
+  if (rc != PPK_OK) return rc;
+  const size_t n = h[0] < cap ? (size_t)h[0] : cap;
+  if (n == 0) return PPK_OK;
+  if (n >= ((size_t)1 << 40)) return ppk_fail(PPK_ERR_ARG, "edge rows: the list kernel takes fewer than 2^40 pairs");
+  PairsJob job;
+  float *d_rtab = nullptr;
+  rc = stage_tables(ref, kmers, random_tbl, n_clu, flags, s, &job.d_lut, &d_rtab, &job.lut_ready);
+  if (rc != PPK_OK) return rc;
+  job.d_rtab = d_rtab;
+  job.ref = ref, job.qry = qry, job.kmers = kmers, job.n_clu = d_rtab ? n_clu : 1, job.flags = flags;
+  job.d_i = d_edges, job.d_j = d_edges + 1, job.stride = 2, job.n_pairs = n, job.int_offset = 0;
+  job.d_out = d_rows, job.d_n_failed = nullptr, job.s = s;
+  rc = ppk_launch_pairs(job);
+  if (rc != PPK_OK) return rc;
+  ppk_set_kernel_name((std::string(ppk_last_kernel_name()) + " + pairs list").c_str());
+  return PPK_OK;
+}
+
+// The fused edge list of a band: the line boundary (model == NULL) or the label test of a BGMM model.  want_rows: the
+// unscaled (core, accessory) row of every edge into d_rows as well -- from the tile kernel's rows modes where
+// ppk_edge_rows_fused says so, else by the two-step (rows_of_edges); the same bits either way.
 static int dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers, const float *random_tbl,
                           size_t n_clu, int flags, size_t q_begin, size_t q_end, int slope, float x_max, float y_max,
                           float scale_x, float scale_y, int inclusive, const ppk_bgmm *model, long long *d_edges,
-                          size_t cap, unsigned long long *d_n_edges, unsigned long long *d_n_failed, void *stream) {
+                          float *d_rows, bool want_rows, size_t cap, unsigned long long *d_n_edges,
+                          unsigned long long *d_n_failed, void *stream) {
   int rc = ppk_check_pair(ref, qry, kmers, q_begin, q_end);
   if (rc != PPK_OK) return rc;
   if (!d_n_edges) return ppk_fail(PPK_ERR_ARG, "d_n_edges is NULL");
+  if (want_rows && !d_rows) return ppk_fail(PPK_ERR_ARG, "d_rows is NULL");
   if (slope < 0 || slope > 2) return ppk_fail(PPK_ERR_ARG, "slope must be 0, 1 or 2");
   if (flags & (PPK_FLAG_JACCARD | PPK_FLAG_COUNTS))
     return ppk_fail(PPK_ERR_ARG, "edge output excludes the jaccard/counts flags");
@@ -675,9 +705,12 @@ static int dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *k
       t.kind = model ? RowTest::BGMM : RowTest::LINE;
       if (model) t.bgmm = *model;
       t.slope = slope, t.inclusive = inclusive, t.x_max = x_max, t.y_max = y_max;
-      return ppk_row_edges(d_dist, rows, qry ? ref->n : 0, 0, t, d_edges, cap, d_n_edges, s);
+      rc = ppk_row_edges(d_dist, rows, qry ? ref->n : 0, 0, t, d_edges, cap, d_n_edges, s);
+      if (rc != PPK_OK || !want_rows) return rc;
+      return rows_of_edges(ref, qry, kmers, random_tbl, n_clu, flags, d_edges, cap, d_n_edges, d_rows, s);
     }
   }
+  const bool fused_rows = want_rows && ppk_edge_rows_fused(ref, qry, q_begin, q_end);
   const size_t n_rtiles = (ref->n + 63) / 64;
   const size_t n_words = (q_end - q_begin) * n_rtiles;
   void *d_mask = nullptr, *d_ws = nullptr;
@@ -690,6 +723,18 @@ static int dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *k
   PPK_HIP(hipMemsetAsync(d_mask, 0, n_words * sizeof(uint64_t), s));
   job.q_begin = q_begin, job.q_end = q_end, job.d_mask = static_cast<uint64_t *>(d_mask);
   job.lut_ready = lut_ready, job.d_bgmm = d_model;
+  // the rows modes' scratch: 8 bytes per mask word (where a word's first row is staged) and 8 bytes per edge of the
+  // caller's cap (the staged rows), behind the reservation counter
+  unsigned long long *d_rows_count = nullptr, *d_word_base = nullptr;
+  float2 *d_stage = nullptr;
+  if (fused_rows) {
+    rc = ppk_scratch_carve(ref->device, SLOT_EDGE_ROWS, [&](Carve &c) {
+      c.take(d_rows_count, 1).take(d_word_base, n_words).take(d_stage, cap ? cap : 1);
+    });
+    if (rc != PPK_OK) return rc;
+    PPK_HIP(hipMemsetAsync(d_rows_count, 0, sizeof(unsigned long long), s));
+    job.d_rows_stage = d_stage, job.d_rows_base = d_word_base, job.d_rows_count = d_rows_count, job.rows_cap = cap;
+  }
   rc = ppk_launch_dist(job);
   if (rc != PPK_OK) return rc;
   EdgeGeom g = {};
@@ -698,8 +743,22 @@ static int dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *k
   g.q_begin = q_begin;
   g.n_rtiles = n_rtiles;
   g.int_offset = 0;
-  return ppk_launch_compact(static_cast<const uint64_t *>(d_mask), n_words, g, d_ws, d_edges, cap,
-                            d_n_edges, s);
+  if (fused_rows)
+    return ppk_launch_compact_rows(static_cast<const uint64_t *>(d_mask), n_words, g, d_ws, d_edges, cap, d_n_edges, d_stage,
+                                   d_word_base, cap, d_rows, s);
+  rc = ppk_launch_compact(static_cast<const uint64_t *>(d_mask), n_words, g, d_ws, d_edges, cap, d_n_edges, s);
+  if (rc != PPK_OK || !want_rows) return rc;
+  return rows_of_edges(ref, qry, kmers, random_tbl, n_clu, flags, d_edges, cap, d_n_edges, d_rows, s);
+}
+
+extern "C" int ppk_dist_edges_rows_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers,
+                                       const float *random_tbl, size_t n_clu, int flags, size_t q_begin,
+                                       size_t q_end, int slope, float x_max, float y_max, float scale_x,
+                                       float scale_y, int inclusive, long long *d_edges, float *d_rows, size_t cap,
+                                       unsigned long long *d_n_edges, unsigned long long *d_n_failed,
+                                       void *stream) {
+  return dist_edges_dev(ref, qry, kmers, random_tbl, n_clu, flags, q_begin, q_end, slope, x_max, y_max, scale_x,
+                        scale_y, inclusive, nullptr, d_edges, d_rows, true, cap, d_n_edges, d_n_failed, stream);
 }
 
 extern "C" int ppk_dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers,
@@ -709,7 +768,7 @@ extern "C" int ppk_dist_edges_dev(const ppk_db *ref, const ppk_db *qry, const in
                                   unsigned long long *d_n_edges, unsigned long long *d_n_failed,
                                   void *stream) {
   return dist_edges_dev(ref, qry, kmers, random_tbl, n_clu, flags, q_begin, q_end, slope, x_max, y_max, scale_x,
-                        scale_y, inclusive, nullptr, d_edges, cap, d_n_edges, d_n_failed, stream);
+                        scale_y, inclusive, nullptr, d_edges, nullptr, false, cap, d_n_edges, d_n_failed, stream);
 }
 
 static int check_bgmm(const ppk_bgmm *model) {
@@ -726,7 +785,17 @@ extern "C" int ppk_dist_bgmm_edges_dev(const ppk_db *ref, const ppk_db *qry, con
                                        void *stream) {
   if (int rc = check_bgmm(model)) return rc;
   return dist_edges_dev(ref, qry, kmers, random_tbl, n_clu, flags, q_begin, q_end, 2, 0.f, 0.f, 1.f, 1.f, 0, model,
-                        d_edges, cap, d_n_edges, d_n_failed, stream);
+                        d_edges, nullptr, false, cap, d_n_edges, d_n_failed, stream);
+}
+
+extern "C" int ppk_dist_bgmm_edges_rows_dev(const ppk_db *ref, const ppk_db *qry, const int32_t *kmers,
+                                            const float *random_tbl, size_t n_clu, int flags, size_t q_begin,
+                                            size_t q_end, const ppk_bgmm *model, long long *d_edges, float *d_rows,
+                                            size_t cap, unsigned long long *d_n_edges, unsigned long long *d_n_failed,
+                                            void *stream) {
+  if (int rc = check_bgmm(model)) return rc;
+  return dist_edges_dev(ref, qry, kmers, random_tbl, n_clu, flags, q_begin, q_end, 2, 0.f, 0.f, 1.f, 1.f, 0, model,
+                        d_edges, d_rows, true, cap, d_n_edges, d_n_failed, stream);
 }
 
 // k nearest neighbours of every sample straight from the resident sketches: kernel 1's tiles emit

@@ -246,11 +246,24 @@ scan_block_sums_kernel(unsigned long long *__restrict__ block_sums, size_t n_blo
 // offset is the total of the segments before this one (g.seg_totals, seg_totals_kernel) plus the self-scan inside the
 // segment -- the sweep's [offset][blocks] mask has 20 x 3 052 blocks, which one workgroup took 105 us to scan.
 constexpr size_t kSelfScanBlocks = 8192;
-template <int SCAN>
+// ROWS (the tiled layouts of the edge calls with rows, ppk_dist_edges_rows_dev): the tile kernel's rows modes have staged
+// the (core, accessory) row of every set bit, word by word -- the t-th set bit of word w at stage[word_base[w] + t]
+// (rows_emit, ppk_dist.hip) -- and this pass, which knows the ordered position of every bit, copies it to rows[pos].
+// A staged position at or past stage_cap was never stored (the list did not fit: rows are then unspecified).
+struct EdgeRowsSrc {
+  const float2 *stage;
+  const unsigned long long *word_base;
+  size_t stage_cap;
+  float2 *rows;
+};
+__device__ __forceinline__ const EdgeRowsSrc &edge_rows_src(const EdgeRowsSrc &rs) { return rs; }
+// (ROWS false: no further argument -- the kernels of the plain lists have the signature, and the code, they had)
+template <int SCAN, bool ROWS = false, typename... Rows>
 __global__ void __launch_bounds__(kBlock)
 mask_expand_kernel(const uint64_t *__restrict__ mask, size_t n_words,
                    const unsigned long long *__restrict__ block_offsets, EdgeGeom g,
-                   longlong2 *__restrict__ edges, size_t cap, unsigned long long *__restrict__ n_edges) {
+                   longlong2 *__restrict__ edges, size_t cap, unsigned long long *__restrict__ n_edges, Rows... rows_src) {
+  static_assert(sizeof...(Rows) == (ROWS ? 1 : 0), "ROWS: one EdgeRowsSrc");
   __shared__ unsigned sh_wave[kBlock / 64];
   __shared__ unsigned long long sh_pre[kBlock / 64];
   unsigned long long block_off = 0;
@@ -378,10 +391,17 @@ mask_expand_kernel(const uint64_t *__restrict__ mask, size_t n_words,
     } else {
       const size_t q = g.q_begin + w / g.n_rtiles;
       const size_t r0 = (w % g.n_rtiles) * 64;
+      [[maybe_unused]] size_t src = 0;
+      if constexpr (ROWS) src = edge_rows_src(rows_src...).word_base[w];
       while (bits) {
         const int t = __builtin_ctzll(bits);
         bits &= bits - 1;
         const size_t r = r0 + t;
+        if constexpr (ROWS) {
+          const EdgeRowsSrc &rs = edge_rows_src(rows_src...);
+          if (pos < cap && src < rs.stage_cap) rs.rows[pos] = rs.stage[src];
+          ++src;
+        }
         if (pos < cap) {
           longlong2 e;
           if (g.layout == EDGE_TILED_SELF) {
@@ -570,6 +590,33 @@ int ppk_row_edges(const void *d_rows, size_t n_rows, size_t n_ref, long long int
   }
   g.pair_interleaved = counted;
   return ppk_launch_compact(d_mask, n_words, g, d_ws, d_edges, cap, d_n_edges, s, counted);
+}
+
+// The same with the staged rows of a tiled mask copied into list order (mask_expand_kernel<SCAN, true>)
+int ppk_launch_compact_rows(const uint64_t *d_mask, size_t n_words, const EdgeGeom &g, void *d_ws, long long *d_edges,
+                            size_t cap, unsigned long long *d_n_edges, const void *d_stage,
+                            const unsigned long long *d_word_base, size_t stage_cap, float *d_rows, hipStream_t s) {
+  if (g.layout != EDGE_TILED_SELF && g.layout != EDGE_TILED_NONSELF)
+    return ppk_fail(PPK_ERR_STATE, "internal: staged rows belong to a tiled mask");
+  if (n_words == 0) {
+    PPK_HIP(hipMemsetAsync(d_n_edges, 0, sizeof(unsigned long long), s));
+    return PPK_OK;
+  }
+  const size_t nb = (n_words + kWordsPerBlock - 1) / kWordsPerBlock;
+  if (nb > 0x7fffffffull) return ppk_fail(PPK_ERR_ARG, "edge mask too large for one launch");
+  unsigned long long *block_sums = static_cast<unsigned long long *>(d_ws);
+  const EdgeRowsSrc rs = {static_cast<const float2 *>(d_stage), d_word_base, stage_cap, reinterpret_cast<float2 *>(d_rows)};
+  hipLaunchKernelGGL(mask_count_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, d_mask, n_words, block_sums);
+  if (nb <= kSelfScanBlocks) {
+    hipLaunchKernelGGL((mask_expand_kernel<1, true, EdgeRowsSrc>), dim3((unsigned)nb), dim3(kBlock), 0, s, d_mask, n_words, block_sums, g,
+                       reinterpret_cast<longlong2 *>(d_edges), cap, d_n_edges, rs);
+  } else {
+    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(1), dim3(1024), 0, s, block_sums, nb, d_n_edges);
+    hipLaunchKernelGGL((mask_expand_kernel<0, true, EdgeRowsSrc>), dim3((unsigned)nb), dim3(kBlock), 0, s, d_mask, n_words, block_sums, g,
+                       reinterpret_cast<longlong2 *>(d_edges), cap, d_n_edges, rs);
+  }
+  PPK_HIP(hipGetLastError());
+  return PPK_OK;
 }
 
 int ppk_launch_compact(const uint64_t *d_mask, size_t n_words, const EdgeGeom &g, void *d_ws,

@@ -98,12 +98,19 @@ __device__ __forceinline__ uint32_t pack_get(const PackW<2> &pk, int k, int bits
   return (uint32_t)(v >> ((nk - 1 - k) * bits)) & mask;
 }
 
-enum { MODE_DIST = 0, MODE_JACCARD = 1, MODE_COUNTS = 2, MODE_MASK = 3, MODE_KNN = 4, MODE_BGMM = 5 };
+enum { MODE_DIST = 0, MODE_JACCARD = 1, MODE_COUNTS = 2, MODE_MASK = 3, MODE_KNN = 4, MODE_BGMM = 5, MODE_MASK_ROWS = 6,
+       MODE_BGMM_ROWS = 7 };
 // The two edge-bitmask modes: MODE_MASK applies the refine/threshold line (ppk_line_dist), MODE_BGMM the label of a
 // fitted BGMM (ppk_bgmm_label; the model is read through the kernel's otherwise unused `out` pointer).  Everything
 // but the per-pair predicate is shared; the predicate is a compile-time choice, so MODE_BGMM adds instantiations
 // and leaves those of MODE_MASK as they were.
-constexpr bool ppk_is_mask(int mode) { return mode == MODE_MASK || mode == MODE_BGMM; }
+// MODE_MASK_ROWS / MODE_BGMM_ROWS: the same two modes, which also hand out the unscaled (core, accessory) row of every
+// pair whose bit they set (rows_emit below; ppk_dist_edges_rows_dev).  Instantiations of their own again: the mask
+// modes' kernels stay as they were.  Whole tiles of the plain packed kernels only (no k-split, no wide window, no strip
+// tiles: the host plans none, ppk_edge_rows_fused).
+constexpr bool ppk_is_rows(int mode) { return mode == MODE_MASK_ROWS || mode == MODE_BGMM_ROWS; }
+constexpr bool ppk_is_mask(int mode) { return mode == MODE_MASK || mode == MODE_BGMM || ppk_is_rows(mode); }
+constexpr bool ppk_is_bgmm(int mode) { return mode == MODE_BGMM || mode == MODE_BGMM_ROWS; }
 
 // MODE_KNN (k nearest neighbours of every sample, straight from the tiles; self job: among the other samples,
 // ref x query job: of every query among the refs AND of every ref among the queries, queries numbered
@@ -198,6 +205,13 @@ struct DistParams {
   // 6 planes (PpkCoding::less2; every such bit is set in rank_short[k] too; all zero with "fold2_min_planes" 7).
   // Fetched where rank_short is.
   unsigned fold2_six[PPK_RANK_SHORT_WORDS];
+  // MODE_MASK_ROWS / MODE_BGMM_ROWS only (appended: every field above keeps its offset).  rows_stage: float2 [rows_cap],
+  // filled in the order the wavefronts reserve it; rows_base: parallel to the mask, the staging position of a word's
+  // first row (written for the words with a bit); rows_count: positions reserved so far (zero before the first launch)
+  float2 *rows_stage;
+  unsigned long long *rows_base;
+  unsigned long long *rows_count;
+  unsigned long long rows_cap;
 };
 
 // With every k usable the least-squares fit is LINEAR in the log J_k with launch-constant weights:
@@ -902,6 +916,47 @@ __device__ __forceinline__ unsigned tiles_before(unsigned r, int self, unsigned 
   return t;
 }
 
+// MODE_MASK_ROWS / MODE_BGMM_ROWS: the rows of one query's four mask words, staged.  ball[0] / ball[1] are the
+// predicate of the even / odd refs of r0 .. r0+127, ball[2] / ball[3] of r0+128 .. r0+255, and lane l holds refs 2l and
+// 2l+1 of each half: lane order, even before odd, is bit order across a half's two consecutive mask words.  One lane
+// reserves the wavefront's rows of this query with ONE atomicAdd (nothing when no bit is set); the position of a word's
+// first row goes to rows_base, parallel to the mask, for the words that exist and have a bit; a lane stores its rows at
+// the reservation + the bits before its own, when that lies inside the staging buffer.  Which reservation a wavefront
+// gets depends on timing; what the expand pass (mask_expand_kernel<SCAN, true>) copies out of it, by rows_base, does not.
+// word0: the first of the four words' index in the band's mask; n_words: how many of the four the mask has.
+template <typename ParamsT>
+__device__ __forceinline__ void rows_emit(const uint64_t (&ball)[4], const float (&core)[4], const float (&acc)[4], int lane,
+                                          size_t word0, size_t n_words, const ParamsT &p) {
+  const unsigned c0 = (unsigned)__popcll(ball[0]) + (unsigned)__popcll(ball[1]);
+  const unsigned c1 = (unsigned)__popcll(ball[2]) + (unsigned)__popcll(ball[3]);
+  if (c0 + c1 == 0) return;      // wave-uniform
+  unsigned long long base = 0;
+  if (lane == 0) base = atomicAdd(p.rows_count, (unsigned long long)(c0 + c1));
+  base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+  if (lane == 0) {
+    // words 2h / 2h+1 hold lanes 0..31 / 32..63 of half h
+    const unsigned lo0 = (unsigned)__popc((uint32_t)ball[0]) + (unsigned)__popc((uint32_t)ball[1]);
+    const unsigned lo1 = (unsigned)__popc((uint32_t)ball[2]) + (unsigned)__popc((uint32_t)ball[3]);
+    unsigned long long *wb = p.rows_base + word0;
+    if (n_words > 0 && lo0) wb[0] = base;
+    if (n_words > 1 && c0 != lo0) wb[1] = base + lo0;
+    if (n_words > 2 && lo1) wb[2] = base + c0;
+    if (n_words > 3 && c1 != lo1) wb[3] = base + c0 + lo1;
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const uint64_t e = ball[2 * h], o = ball[2 * h + 1];
+    const unsigned below =
+        __builtin_amdgcn_mbcnt_hi((uint32_t)(e >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)e, 0u)) +
+        __builtin_amdgcn_mbcnt_hi((uint32_t)(o >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)o, 0u));
+    const bool pe = (e >> lane) & 1, po = (o >> lane) & 1;
+    const unsigned long long pos = base + (h ? c0 : 0u) + below;
+    if (pe && pos < p.rows_cap) p.rows_stage[pos] = make_float2(core[2 * h], acc[2 * h]);
+    if (po && pos + (pe ? 1u : 0u) < p.rows_cap) p.rows_stage[pos + (pe ? 1u : 0u)] = make_float2(core[2 * h + 1], acc[2 * h + 1]);
+  }
+}
+
 // NW = wavefronts per workgroup: 8 (256 x 32 tile, 2 workgroups per CU).  The 16-wavefront shape
 // (256 x 64 tile, one workgroup per CU) was measured and rejected (tools/ubench_pipe.hip).
 // W = dwords of the per-pair count register (1 in the COUNTS / JACCARD modes, which consume each
@@ -965,6 +1020,33 @@ dist_kernel_v2_foldh(const uint64_t *__restrict__ refT, const uint64_t *__restri
                      uint64_t *__restrict__ mask_out, const DistParams p) {
   constexpr int NW = 8, W = 2, PL = 8;
   constexpr bool KSPLIT = false, WIDE = false, EXP = false, FOLD2 = true, FOLDH = true;
+#include "ppk_dist_tile.inc"
+}
+
+// The coded kernels in the rows modes (MODE_MASK_ROWS / MODE_BGMM_ROWS), under names of their own once more: the rank,
+// fold2 and foldh kernels keep exactly the instantiations (and symbols) they had.
+template <int PL, int MODE>
+__global__ void __launch_bounds__(8 * 64, 4)
+dist_kernel_v2_rank_rows(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ qryT,
+                         const double *__restrict__ lut, const uint16_t *__restrict__ ref_clu,
+                         const uint16_t *__restrict__ qry_clu, const float *__restrict__ rtab,
+                         void *__restrict__ out, unsigned long long *__restrict__ n_failed,
+                         uint64_t *__restrict__ mask_out, const DistParams p) {
+  static_assert(ppk_is_rows(MODE), "rows modes");
+  constexpr int NW = 8, W = 2;
+  constexpr bool KSPLIT = false, WIDE = false, EXP = false, FOLD2 = false, FOLDH = false;
+#include "ppk_dist_tile.inc"
+}
+template <int MODE, bool HOLDERS>
+__global__ void __launch_bounds__(8 * 64, 4)
+dist_kernel_v2_fold_rows(const uint64_t *__restrict__ refT, const uint64_t *__restrict__ qryT,
+                         const double *__restrict__ lut, const uint16_t *__restrict__ ref_clu,
+                         const uint16_t *__restrict__ qry_clu, const float *__restrict__ rtab,
+                         void *__restrict__ out, unsigned long long *__restrict__ n_failed,
+                         uint64_t *__restrict__ mask_out, const DistParams p) {
+  static_assert(ppk_is_rows(MODE), "rows modes");
+  constexpr int NW = 8, W = 2, PL = 8;
+  constexpr bool KSPLIT = false, WIDE = false, EXP = false, FOLD2 = true, FOLDH = HOLDERS;
 #include "ppk_dist_tile.inc"
 }
 
@@ -1522,12 +1604,23 @@ int launch_rank(const PpkCoding &c, DistArgs a, DistParams &p, size_t n_blocks, 
   p.fold2_off = c.d_off;
   p.fold2_rt = c.rt;
   static const char *const suffix[PPK_CODINGS] = {">", ",fold>", ",fold2>", ",foldh>"};
-  const auto kernel = c.kind == PPK_CODING_FOLDH   ? &dist_kernel_v2_foldh<MODE>
-                      : c.kind == PPK_CODING_FOLD2 ? &dist_kernel_v2_fold2<MODE>
-                      : c.planes == 12             ? &dist_kernel_v2_rank<12, MODE>
-                      : c.planes == 10             ? &dist_kernel_v2_rank<10, MODE>
-                                                   : &dist_kernel_v2_rank<8, MODE>;
-  const std::string name = "dist_kernel_v2<256x32,lds-dma,rank " + std::to_string(c.planes) + suffix[c.kind];
+  auto pick = [&c]() {
+    if constexpr (ppk_is_rows(MODE))      // (kernels of their own names: the others keep their instantiations)
+      return c.kind == PPK_CODING_FOLDH   ? &dist_kernel_v2_fold_rows<MODE, true>
+             : c.kind == PPK_CODING_FOLD2 ? &dist_kernel_v2_fold_rows<MODE, false>
+             : c.planes == 12             ? &dist_kernel_v2_rank_rows<12, MODE>
+             : c.planes == 10             ? &dist_kernel_v2_rank_rows<10, MODE>
+                                          : &dist_kernel_v2_rank_rows<8, MODE>;
+    else
+      return c.kind == PPK_CODING_FOLDH   ? &dist_kernel_v2_foldh<MODE>
+             : c.kind == PPK_CODING_FOLD2 ? &dist_kernel_v2_fold2<MODE>
+             : c.planes == 12             ? &dist_kernel_v2_rank<12, MODE>
+             : c.planes == 10             ? &dist_kernel_v2_rank<10, MODE>
+                                          : &dist_kernel_v2_rank<8, MODE>;
+  };
+  const auto kernel = pick();
+  std::string name = "dist_kernel_v2<256x32,lds-dma,rank " + std::to_string(c.planes) + suffix[c.kind];
+  if (ppk_is_rows(MODE)) name.insert(name.size() - 1, ",rows");
   return launch_kernel(kernel, dim3((unsigned)n_blocks), dim3(8 * 64), name.c_str(), a, p, s);
 }
 
@@ -1537,15 +1630,21 @@ int launch_v2(const ppk_db *ref, const ppk_db *qry, const DistArgs &a, DistParam
   constexpr bool kFits = MODE == MODE_DIST || ppk_is_mask(MODE);      // the modes that fit a pair in the tile's epilogue
   const PpkGeometry &geo = ppk_geometry(ref->device);
   size_t n_blocks = 0;
-  const int rc = plan_grid(p, NW, kFits, WIDE, geo, &n_blocks);
+  // (the rows modes reserve staging per mask word, and a strip tile sets single bits of other tiles' words: no strips)
+  const int rc = plan_grid(p, NW, kFits && !ppk_is_rows(MODE), WIDE, geo, &n_blocks);
   if (rc != PPK_OK || n_blocks == 0) return rc;
+  if constexpr (ppk_is_rows(MODE)) {
+    // whole tiles of the plain packed kernels only: ppk_edge_rows_fused has sent every other shape through the two-step
+    if (p.k_split || WIDE) return ppk_fail(PPK_ERR_STATE, "internal: the rows modes have whole-tile instantiations only");
+  }
   if (kFits && NW == 8 && p.k_split) {
-    if constexpr (NW == 8 && W == 2 && kFits) return launch_ksplit_fused<NW, MODE, WIDE>(ref->device, a, p, n_blocks, s);
+    if constexpr (NW == 8 && W == 2 && kFits && !ppk_is_rows(MODE))
+      return launch_ksplit_fused<NW, MODE, WIDE>(ref->device, a, p, n_blocks, s);
     return ppk_fail(PPK_ERR_STATE, "internal: no k-split instantiation for this mode");
   }
   if constexpr (WIDE && W != 4) {
     return ppk_fail(PPK_ERR_STATE, "internal: the fit-from-parts instantiation is a k-split kernel");
-  } else if constexpr (WIDE) {
+  } else if constexpr (WIDE && !ppk_is_rows(MODE)) {
     return launch_wide<NW, MODE>(ref->device, geo, a, p, n_blocks, s);
   }
   const dim3 grid((unsigned)n_blocks), block(NW * 64);
@@ -1562,7 +1661,8 @@ int launch_v2(const ppk_db *ref, const ppk_db *qry, const DistArgs &a, DistParam
     if (p.k_split)
       return launch_kernel(&dist_kernel_v2<NW, MODE, W, true>, dim3((unsigned)n_blocks, (unsigned)p.nk), block,
                            "dist_kernel_v2<256x32,lds-dma>", a, p, s);
-  return launch_kernel(&dist_kernel_v2<NW, MODE, W>, grid, block, "dist_kernel_v2<256x32,lds-dma>", a, p, s);
+  return launch_kernel(&dist_kernel_v2<NW, MODE, W>, grid, block,
+                       ppk_is_rows(MODE) ? "dist_kernel_v2<256x32,lds-dma,rows>" : "dist_kernel_v2<256x32,lds-dma>", a, p, s);
 }
 
 // COUNTS / JACCARD modes: each k's counts are consumed at once, nothing is packed
@@ -1603,7 +1703,37 @@ int launch_tiles_packed(const ppk_db *ref, const ppk_db *qry, const DistArgs &a,
   return launch_v2<8, MODE, 4>(ref, qry, a, p, s);
 }
 
+// MASK_ROWS / BGMM_ROWS modes: whole tiles of the three packed count registers, nothing else (the caller has asked
+// ppk_edge_rows_fused, and a band that would go k-split on its own runs whole tiles here -- the same bits)
+template <int MODE>
+int launch_tiles_rows(const ppk_db *ref, const ppk_db *qry, const DistArgs &a, DistParams &p, hipStream_t s) {
+  static_assert(ppk_is_rows(MODE), "rows modes");
+  const int total_bits = p.nk * p.cnt_bits;
+  const long long force_kpg = ppk_config().wide_kpg.load();
+  if (p.bbits != 14 || p.k_split || total_bits > 128 || (force_kpg > 0 && force_kpg < p.nk))
+    return ppk_fail(PPK_ERR_STATE, "internal: this shape takes the two-step (ppk_edge_rows_fused)");
+  if (total_bits <= 64) return launch_v2<8, MODE, 2>(ref, qry, a, p, s);
+  if (total_bits <= 96) return launch_v2<8, MODE, 3>(ref, qry, a, p, s);
+  return launch_v2<8, MODE, 4>(ref, qry, a, p, s);
+}
+
 }  // namespace
+
+// Whether the edge calls with rows (ppk_dist_edges_rows_dev / ppk_dist_bgmm_edges_rows_dev) emit the rows from the tile
+// kernel's own epilogue for this band, or run the two-step (the edge call, then the list kernel on its edges: the same
+// bits).  The one place that decides: fused on the plain packed whole-tile route -- bbits 14, at most 128 count bits, no
+// forced wide window, and a band the route choice sends through whole tiles.  Option "edge_rows_fused" 0 forces the
+// two-step.
+bool ppk_edge_rows_fused(const ppk_db *ref, const ppk_db *qry, size_t q_begin, size_t q_end) {
+  if (ppk_config().edge_rows_fused.load() == 0 || ppk_unfused(ref) || ref->bbits != V2_BB || ref->nk < 1) return false;
+  const int bits = count_bits(ref->s64);
+  const long long force_kpg = ppk_config().wide_kpg.load();
+  if (ref->nk * (size_t)bits > 128 || (force_kpg > 0 && force_kpg < (long long)ref->nk)) return false;
+  const int self = qry ? 0 : 1;
+  const size_t rows = ppk_rows_in_band(ref->n, qry ? qry->n : 0, q_begin, q_end);
+  PpkRouteShape shape = {ref->n, q_end - q_begin, rows, self, (int)ref->nk, (int)ref->s64, bits, (int)ref->bbits, 1, 0};
+  return ppk_choose_route_impl(shape, ppk_geometry(ref->device), route_knobs()).route == PPK_ROUTE_TILE;
+}
 
 int ppk_launch_transpose(const uint64_t *d_in, uint64_t *d_out, size_t n, size_t cols, size_t npad,
                          hipStream_t s) {
@@ -1844,6 +1974,12 @@ static int launch_dist_band(const DistJob &job) {
   p.ablate = (int)ppk_config().ablate.load();
 #endif
   p.lds_table = ppk_config().lds_table.load() != 0 && !(p.ablate & 32) ? 1 : 0;
+  p.rows_stage = static_cast<float2 *>(job.d_rows_stage);
+  p.rows_base = job.d_rows_base;
+  p.rows_count = job.d_rows_count;
+  p.rows_cap = job.rows_cap;
+  if (job.d_rows_stage && !(job.d_mask && job.d_rows_base && job.d_rows_count))
+    return ppk_fail(PPK_ERR_STATE, "internal: a rows launch needs the mask, the word positions and the counter");
 
   if (job.d_bgmm && !job.d_mask) return ppk_fail(PPK_ERR_STATE, "internal: a BGMM launch needs an edge bitmask");
   // cluster ids only matter when a multi-cluster random-match table is in use
@@ -1892,11 +2028,15 @@ static int launch_dist_band(const DistJob &job) {
   if (job.d_bgmm) a.out = const_cast<ppk_bgmm *>(job.d_bgmm);
   auto launch_packed = [&]() {
     if (job.knn_args) return launch_tiles_packed<MODE_KNN>(ref, qry, a, p, s);
+    if (job.d_rows_stage && job.d_bgmm) return launch_tiles_rows<MODE_BGMM_ROWS>(ref, qry, a, p, s);
+    if (job.d_rows_stage) return launch_tiles_rows<MODE_MASK_ROWS>(ref, qry, a, p, s);
     if (job.d_bgmm) return launch_tiles_packed<MODE_BGMM>(ref, qry, a, p, s);
     if (job.d_mask) return launch_tiles_packed<MODE_MASK>(ref, qry, a, p, s);
     return launch_tiles_packed<MODE_DIST>(ref, qry, a, p, s);
   };
   if (choice.route != PPK_ROUTE_KSPLIT_ONE_LAUNCH && choice.route != PPK_ROUTE_KSPLIT_TWO_PASS) return launch_packed();
+  // (a short last piece of a rows job that ppk_edge_rows_fused sent through whole tiles: whole tiles too, the same bits)
+  if (job.d_rows_stage) return launch_packed();
 
   // a small job: one workgroup per (tile, k), or per piece of a k (ppk_choose_route_impl)
   const int slices = choice.slices;
@@ -1974,6 +2114,7 @@ int ppk_launch_dist(const DistJob &job) {
     if (!job.knn_args) {
       if (job.d_out) band.d_out = static_cast<char *>(job.d_out) + ppk_rows_in_band(ref->n, n_qry, job.q_begin, lo) * row_bytes;
       if (job.d_mask) band.d_mask = job.d_mask + (lo - job.q_begin) * n_rtiles;
+      if (job.d_rows_base) band.d_rows_base = job.d_rows_base + (lo - job.q_begin) * n_rtiles;
     }
     band.lut_ready = job.lut_ready || lo > job.q_begin;
     const int rc = launch_dist_band(band);

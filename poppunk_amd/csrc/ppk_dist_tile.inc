@@ -888,6 +888,9 @@
       }
     }
     const bool table_in_lds = interior;      // (a wavefront may still leave the interior path: `interior` is cleared)
+    // MODE_*_ROWS: the queries whose rows the interior path has staged before the wavefront left it (the general
+    // statement then fits every query again and rewrites the same mask words, but must not reserve their rows twice)
+    [[maybe_unused]] int rows_done = 0;      // wave-uniform
     if constexpr (KS_FUSED && !KS_MEM) {
       if (!interior && wave_active) ks_reload();
     }
@@ -966,6 +969,7 @@
           }
           if (!__all(usable) && !(ablate_l & 64)) {
             interior = false;
+            if constexpr (ppk_is_rows(MODE)) rows_done = q;
             break;
           }
           fit_finish(pe, pf, core[r], acc[r]);
@@ -1012,7 +1016,7 @@
 #pragma unroll
           for (int rr = 0; rr < R; ++rr) {
             bool pred;
-            if constexpr (MODE == MODE_BGMM) {
+            if constexpr (ppk_is_bgmm(MODE)) {
               const ppk_bgmm &bg = *static_cast<const ppk_bgmm *>(out);
               pred = ppk_bgmm_label(core[rr], acc[rr], bg) == bg.within_label;
             } else {
@@ -1037,6 +1041,7 @@
               if (rt * 4 + 2 * h + 1 < p.n_rtiles) mrow[2 * h + 1] = w1;
             }
           }
+          if constexpr (ppk_is_rows(MODE)) rows_emit(ball, core, acc, lane_late, (qq - qb) * p.n_rtiles + rt * 4, p.n_rtiles - rt * 4, p);
         } else {
 #pragma unroll
           for (int rr = 0; rr < R; ++rr)
@@ -1198,7 +1203,7 @@
         for (int r = 0; r < R; ++r) {
           bool pred = false;
           if (valid[r]) {
-            if constexpr (MODE == MODE_BGMM) {
+            if constexpr (ppk_is_bgmm(MODE)) {
               const ppk_bgmm &bg = *static_cast<const ppk_bgmm *>(out);
               pred = ppk_bgmm_label(core[r], acc[r], bg) == bg.within_label;
             } else {
@@ -1235,6 +1240,10 @@
             if (rt * 4 + 2 * h < p.n_rtiles) mrow[2 * h] = w0;
             if (rt * 4 + 2 * h + 1 < p.n_rtiles) mrow[2 * h + 1] = w1;
           }
+        }
+        if constexpr (ppk_is_rows(MODE)) {
+          // (the rows modes run without strip tiles: plan_grid)
+          if (q >= rows_done) rows_emit(ball, core, acc, lane_late, (qq - qb) * p.n_rtiles + rt * 4, p.n_rtiles - rt * 4, p);
         }
       }
     }

@@ -179,6 +179,7 @@ struct PpkConfig {
   std::atomic<long long> density_hot_table{1};  // PPK_DENSITY_HOT_TABLE: ppk_density_counts_dev adds through a per-workgroup LDS table of hot pixels in front of the global atomics (0: every row one global atomic; same counts)
   std::atomic<long long> density_kde_presum{0}; // PPK_DENSITY_KDE_PRESUM: ppk_density_kde_dev sums the terms of lanes of a wave that share a window of nodes before the LDS add, for groups of at least this many lanes (0: every lane adds its own terms; same sums)
   std::atomic<long long> pairs_scratch_mb{1024}; // PPK_PAIRS_SCRATCH_MB: what the scratch of one chunk of a pair list may take as allocated (ppk_dist_pairs_dev: 2 x pairs x the bytes of one sample's sketch, plus the counts, stays within four fifths of it; same results)
+  std::atomic<long long> edge_rows_fused{1};    // PPK_EDGE_ROWS_FUSED: the edge calls with rows take them from the tile kernel's epilogue where ppk_edge_rows_fused allows (0: always the edge call followed by the list kernel; same results)
   std::atomic<long long> pairs_chunk{0};        // PPK_PAIRS_CHUNK: pairs per chunk of a pair list whatever the cap says (0 = from the cap; tests; same results)
   std::atomic<long long> silhouette_scratch_mb{1024}; // PPK_SILHOUETTE_SCRATCH_MB: what the band of square rows of ppk_silhouette_dev may take as allocated (float32 [band][n] stays within four fifths of it; at least one row; same results)
   std::atomic<long long> silhouette_band{0};    // PPK_SILHOUETTE_BAND: samples per band whatever the cap says (0 = from the cap; tests; same results)
@@ -383,6 +384,11 @@ int ppk_launch_all_tuples(size_t n_entries, size_t num_ref, size_t num_queries, 
 int ppk_launch_compact(const uint64_t *d_mask, size_t n_words, const EdgeGeom &g, void *d_ws,
                        long long *d_edges, size_t cap, unsigned long long *d_n_edges,
                        hipStream_t s, bool counted = false);
+// a tiled mask whose producer staged the row of every set bit (the tile kernel's rows modes): the edges as above, and
+// row e of d_rows (float [cap][2]) = the staged row of edge e; d_word_base: per mask word, where its first row is staged
+int ppk_launch_compact_rows(const uint64_t *d_mask, size_t n_words, const EdgeGeom &g, void *d_ws, long long *d_edges,
+                            size_t cap, unsigned long long *d_n_edges, const void *d_stage,
+                            const unsigned long long *d_word_base, size_t stage_cap, float *d_rows, hipStream_t s);
 int ppk_launch_assign(const float *d_dist, size_t n_rows, int slope, float x_max, float y_max,
                       float *d_out, hipStream_t s);
 // BGMM assignment: labels and / or responsibilities (ppk_bgmm.hip)
@@ -485,7 +491,8 @@ enum { SLOT_LUT = 0, SLOT_MASK = 1, SLOT_WS = 2, SLOT_ITER_A = 3, SLOT_ITER_B = 
        SLOT_SKETCH = 30,                       // the sketcher's control words, piece table and one group of samples' per-bin minima (read samples: floors, winner counts and count tables too)
        SLOT_REFS = 31,                         // the reference pick's control words, union-find parents, component layout, BFS parents, ranks and temp storage
        SLOT_REFS_BITS = 32,                    // ... and the component-local bit matrices with the large components' bitsets (sized after the layout has been read: growing a slot moves it)
-       SLOT_COUNT = 33 };
+       SLOT_EDGE_ROWS = 33,                    // the edge calls with rows: the reservation counter, a staging position per mask word (8 B) and the staged rows (8 B per edge of the caller's cap)
+       SLOT_COUNT = 34 };
 int ppk_scratch_get(int dev, int slot, size_t bytes, void **out);
 // The fit tables in SLOT_LUT.  ppk_lut_ready: whether the tables of `key` (k list, random table, sketch size, options)
 // already stand at `d_lut`; if not, none count as valid until the calling thread's launcher has enqueued lut_kernel
@@ -608,10 +615,17 @@ struct DistJob {
   bool lut_ready = false;
   const int *knn_args = nullptr;      // neighbour mode: {knn, distance column}
   const ppk_bgmm *d_bgmm = nullptr;   // device copy of the model whose label test fills d_mask instead of the line
+  // with d_mask, the rows modes (ppk_edge_rows_fused said yes): float2 [rows_cap] staging, a staging position per mask
+  // word (parallel to d_mask) and the zeroed reservation counter
+  void *d_rows_stage = nullptr;
+  unsigned long long *d_rows_base = nullptr, *d_rows_count = nullptr;
+  size_t rows_cap = 0;
   hipStream_t s = nullptr;
 };
 // enqueues only; a band of more rows than one dispatch holds goes out as several launches
 int ppk_launch_dist(const DistJob &job);
+// whether an edge call with rows over this band takes the rows from the tile kernel's epilogue (else: the two-step)
+bool ppk_edge_rows_fused(const ppk_db *ref, const ppk_db *qry, size_t q_begin, size_t q_end);
 
 // Kernel 1 for a list of pairs (ppk_dist.hip, ppk_dist_pairs_dev): validated ids in, rows of d_out out.  The caller
 // holds the PpkCall and has staged the tables; synchronises `s` once (the check of the ids).

@@ -125,6 +125,15 @@ __device__ __forceinline__ unsigned eval_rows_slope2(const float (&x)[R], const 
   return holes;
 }
 
+// MODE 0 / 1 / 3: whether boundary B holds the row (the statement the classify pass ballots, and the levels of listed
+// rows, sweep_levels_kernel, read off)
+template <int MODE>
+__device__ __forceinline__ bool row_within(float x, float y, const Bnd &B, int slope) {
+  if constexpr (MODE == 0) return __fsub_rn(x, B.xm) <= 0.0f;
+  else if constexpr (MODE == 1) return __fsub_rn(y, B.ym) <= 0.0f;
+  else return ppk_line_dist(x, y, B.xm, B.ym, slope) <= 0.0f;
+}
+
 constexpr int kDenseRows = 2;      // rows per lane of one dense batch of the filtered form
 
 // WINDOW (slope 2, the boundaries NESTED outwards: x_max and y_max non-decreasing in the offset, all >= 2^-40, finite --
@@ -347,10 +356,7 @@ ti1_classify_kernel(const float2 *__restrict__ dist, size_t n_rows, const Bnd *_
         for (int k = 0; k < 4; ++k) {
 #pragma unroll
           for (int r = 0; r < kUnitWords; ++r) {
-            bool w;
-            if constexpr (MODE == 0) w = __fsub_rn(x[r], B[k].xm) <= 0.0f;
-            else if constexpr (MODE == 1) w = __fsub_rn(y[r], B[k].ym) <= 0.0f;
-            else w = ppk_line_dist(x[r], y[r], B[k].xm, B[k].ym, slope) <= 0.0f;
+            const bool w = row_within<MODE>(x[r], y[r], B[k], slope);
             const uint64_t wm = __ballot(w);
             hole |= prev[r] & ~wm;
             prev[r] = wm;
@@ -416,6 +422,47 @@ ti1_classify_kernel(const float2 *__restrict__ dist, size_t n_rows, const Bnd *_
     stops[wv] = make_ulonglong2((unsigned long long)best_ord,
                                 best_ord == 0xffffffffu && best_rel == 0xffffffffu
                                     ? ~0ull : (unsigned long long)u0 * (kUnitWords * 64) + best_rel);
+}
+
+// The sweep levels of LISTED rows (ppk_sweep_levels_dev): level[p] = the first boundary that holds row p of an arbitrary
+// [n_rows][2] float list, n_off when none does -- what the sweeps above assign to a row with those coordinates (a row
+// with a hole, within a boundary and outside a later one, is listed by them at more than one boundary or not at all: it
+// gets its first).  One thread per row, the boundaries in LDS, the classify pass's own every-boundary statement: MODE 2
+// eval_rows_slope2 (first = n_pad - count where the row has no hole), otherwise row_within boundary by boundary.
+// Rows are read float by float: the list need not be 8-byte aligned.
+template <int MODE>
+__global__ void __launch_bounds__(256)
+sweep_levels_kernel(const float *__restrict__ rows, size_t n_rows, const Bnd *__restrict__ bnd, int n_off, int n_pad,
+                    int slope, int32_t *__restrict__ level) {
+  extern __shared__ float4 lv_lds[];
+  for (int o = threadIdx.x; o < n_pad; o += 256) {
+    const Bnd b = bnd[o];
+    lv_lds[o] = make_float4(b.xm, b.ym, b.c, 0.0f);
+  }
+  __syncthreads();
+  const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n_rows) return;
+  const float x = rows[2 * row], y = rows[2 * row + 1];
+  int lvl = n_off;
+  bool scan = true;
+  if constexpr (MODE == 2) {
+    const float xa[1] = {x}, ya[1] = {y};
+    unsigned cnt[1];
+    const unsigned holes = eval_rows_slope2<1>(xa, ya, lv_lds, n_pad, cnt);
+    scan = holes != 0u;
+    if (!scan && cnt[0]) lvl = n_pad - (int)cnt[0];
+  }
+  if (scan) {
+    for (int o = 0; o < n_off; ++o) {
+      const float4 b = lv_lds[o];
+      constexpr int STMT = MODE == 2 ? 3 : MODE;      // (a row with a hole: ppk_line_dist as it stands, the same verdicts)
+      if (row_within<STMT>(x, y, Bnd{b.x, b.y, b.z, 0.0f}, slope)) {
+        lvl = o;
+        break;
+      }
+    }
+  }
+  level[row] = lvl;
 }
 
 // One workgroup: (a) the stop = lexicographic minimum of the wavefronts' (ord, row); (b) exclusive scan of
@@ -1175,6 +1222,83 @@ extern "C" int ppk_sweep_plan(const float *x_max, const float *y_max, size_t n_o
   return PPK_OK;
 }
 
+// The boundaries of a 1-D sweep, with the arithmetic of boundary.cpp:161-186 (float/double mix kept as is)
+static void sweep_boundaries_1d(const double *offsets, size_t n_off, int slope, float x0, float y0, float x1, float y1,
+                                float *x_max, float *y_max) {
+  const float dx = x1 - x0, dy = y1 - y0;
+  const float ds = std::sqrt(dx * dx + dy * dy);
+  const float gradient = dy / dx;
+  for (size_t o = 0; o < n_off; ++o) {
+    const float x_int = (float)((double)x0 + offsets[o] * (double)(dx / ds));
+    const float y_int = (float)((double)y0 + offsets[o] * (double)(dy / ds));
+    if (slope == 2) {
+      x_max[o] = x_int + y_int * gradient;
+      y_max[o] = y_int + x_int / gradient;
+    } else if (slope == 0) {
+      x_max[o] = x_int;
+      y_max[o] = 0;
+    } else {
+      x_max[o] = 0;
+      y_max[o] = y_int;
+    }
+  }
+}
+
+extern "C" int ppk_sweep_boundaries_1d(const double *offsets, size_t n_off, int slope, float x0, float y0, float x1,
+                                       float y1, float *x_max, float *y_max) {
+  if (slope < 0 || slope > 2) return ppk_fail(PPK_ERR_ARG, "slope must be 0, 1 or 2");
+  if (n_off > (size_t)kMaxOff) return ppk_fail(PPK_ERR_ARG, "too many offsets (max 1023 per call)");
+  if (n_off == 0) return PPK_OK;
+  if (!offsets || !x_max || !y_max) return ppk_fail(PPK_ERR_ARG, "ppk_sweep_boundaries_1d: null argument");
+  for (size_t o = 1; o < n_off; ++o)
+    if (offsets[o] < offsets[o - 1]) return ppk_fail(PPK_ERR_ARG, "Offsets to thresholdIterate1D must be sorted");
+  sweep_boundaries_1d(offsets, n_off, slope, x0, y0, x1, y1, x_max, y_max);
+  return PPK_OK;
+}
+
+extern "C" int ppk_sweep_levels_dev(const float *d_rows, size_t n_rows, const float *x_max, const float *y_max, size_t n_off,
+                                    int slope, int32_t *d_level, void *stream) {
+  if (slope < 0 || slope > 2) return ppk_fail(PPK_ERR_ARG, "slope must be 0, 1 or 2");
+  if (n_off > (size_t)kMaxOff) return ppk_fail(PPK_ERR_ARG, "too many offsets (max 1023 per call)");
+  if (n_rows == 0) return PPK_OK;
+  if (!d_rows || !d_level) return ppk_fail(PPK_ERR_ARG, "ppk_sweep_levels_dev: NULL array");
+  if (n_off && (!x_max || !y_max)) return ppk_fail(PPK_ERR_ARG, "ppk_sweep_levels_dev: NULL boundaries");
+  if ((n_rows + 255) / 256 > 0x7fffffffull) return ppk_fail(PPK_ERR_ARG, "too many rows");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_off == 0) {
+    PPK_HIP(hipMemsetAsync(d_level, 0, n_rows * sizeof(int32_t), s));      // (level n_off = 0: no boundary lists a row)
+    return PPK_OK;
+  }
+  std::vector<Bnd> bnd(n_off);
+  for (size_t o = 0; o < n_off; ++o) {
+    volatile float prod = x_max[o] * y_max[o];      // rounded once, as the sweeps' boundaries are
+    bnd[o] = Bnd{x_max[o], y_max[o], prod, 0.0f};
+  }
+  const int mode = classify_mode(bnd, slope);
+  std::vector<Bnd> padded(bnd);
+  while (padded.size() % 4) padded.push_back(bnd.back());
+  const int n_pad = (int)padded.size();
+  int dev = 0;
+  PPK_HIP(hipGetDevice(&dev));
+  PpkCall call(dev, s);
+  void *p_bnd = nullptr;
+  if (int rc = ppk_scratch_get(dev, SLOT_BOUNDS, 256 + padded.size() * sizeof(Bnd) + 256, &p_bnd)) return rc;
+  const Bnd *d_bnd = reinterpret_cast<const Bnd *>(static_cast<char *>(p_bnd) + 256);
+  PPK_HIP(hipMemcpyAsync(static_cast<char *>(p_bnd) + 256, padded.data(), padded.size() * sizeof(Bnd), hipMemcpyHostToDevice,
+                         s));      // (pageable: staged at the call)
+  const dim3 grid((unsigned)((n_rows + 255) / 256));
+  const size_t lds = (size_t)n_pad * sizeof(float4);
+#define PPK_SWEEP_LEVELS(M) \
+  hipLaunchKernelGGL((sweep_levels_kernel<M>), grid, dim3(256), lds, s, d_rows, n_rows, d_bnd, (int)n_off, n_pad, slope, d_level)
+  if (mode == 0) PPK_SWEEP_LEVELS(0);
+  else if (mode == 1) PPK_SWEEP_LEVELS(1);
+  else if (mode == 2) PPK_SWEEP_LEVELS(2);
+  else PPK_SWEEP_LEVELS(3);
+#undef PPK_SWEEP_LEVELS
+  PPK_HIP(hipGetLastError());
+  return PPK_OK;
+}
+
 extern "C" int ppk_threshold_iterate_1d_dev(const float *d_dist, size_t n_rows,
                                             const double *offsets, size_t n_off, int slope,
                                             float x0, float y0, float x1, float y1,
@@ -1196,29 +1320,20 @@ extern "C" int ppk_threshold_iterate_1d_dev(const float *d_dist, size_t n_rows,
   if (int rc = ppk_condensed_samples(n_rows, &n_samples)) return rc;
   if (n_rows >= (size_t)0x7fffffff * 64) return ppk_fail(PPK_ERR_ARG, "too many rows");
 
-  // boundaries, with the arithmetic of boundary.cpp:161-186 (float/double mix kept as is)
+  // boundaries: the one statement of them (ppk_sweep_boundaries_1d)
   std::vector<Bnd> bnd(n_off);
-  const float dx = x1 - x0, dy = y1 - y0;
-  const float ds = std::sqrt(dx * dx + dy * dy);
-  const float gradient = dy / dx;
-  for (size_t o = 0; o < n_off; ++o) {
-    const float x_int = (float)((double)x0 + offsets[o] * (double)(dx / ds));
-    const float y_int = (float)((double)y0 + offsets[o] * (double)(dy / ds));
-    Bnd &b = bnd[o];
-    if (slope == 2) {
-      b.xm = x_int + y_int * gradient;
-      b.ym = y_int + x_int / gradient;
-    } else if (slope == 0) {
-      b.xm = x_int;
-      b.ym = 0;
-    } else {
-      b.xm = 0;
-      b.ym = y_int;
+  {
+    std::vector<float> xm(n_off), ym(n_off);
+    sweep_boundaries_1d(offsets, n_off, slope, x0, y0, x1, y1, xm.data(), ym.data());
+    for (size_t o = 0; o < n_off; ++o) {
+      Bnd &b = bnd[o];
+      b.xm = xm[o];
+      b.ym = ym[o];
+      // (a float product of two floats, rounded once: what line_dist computes per row, boundary.cpp:49)
+      volatile float prod = b.xm * b.ym;
+      b.c = prod;
+      b.pad = 0;
     }
-    // (a float product of two floats, rounded once: what line_dist computes per row, boundary.cpp:49)
-    volatile float prod = b.xm * b.ym;
-    b.c = prod;
-    b.pad = 0;
   }
 
   int dev = 0;

@@ -396,6 +396,49 @@ def dist_edges(ref, qry=None, kmers=None, random_tbl=None, random_correct=True, 
                         1 if inclusive else 0)
 
 
+def _fused_edges_rows(name, ref, qry, kmers, random_tbl, random_correct, q_begin, q_end, cap, *test):
+    """The fused edge calls that also return every edge's unscaled (core, accessory) row: _fused_edges with a float32
+    [cap, 2] buffer next to the edges; the exact re-run refills both (a short run leaves the rows unspecified).
+    Returns (edges, rows, n_failed)."""
+    torch = _torch()
+    rows_of = {}
+
+    def with_rows(call, edges, c, n_edges, n_failed):
+        rows = torch.empty((max(c, 1), 2), dtype=torch.float32, device=edges.device)
+        rows_of["rows"] = rows
+        call(edges, rows, c, n_edges, n_failed)
+
+    _check_pair(ref, qry)
+    nq = qry.n if qry is not None else ref.n
+    q_end = nq if q_end is None else int(q_end)
+    kmers, random_tbl, n_clu = _prep_tables(kmers, random_tbl, ref.nk)
+    n_rows = rows_in_band(ref.n, qry.n if qry is not None else 0, q_begin, q_end)
+    flags = FLAG_RANDOM_CORRECT if random_correct else 0
+    dev = torch.device("cuda:%d" % ref.device)
+    if cap is None:
+        cap = _cap_guess(n_rows)
+    n_failed = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def launch(edges, c, n_edges):
+        n_failed.zero_()
+        with_rows(lambda e, r, cc, ne, nf: _dev_call(name, dev, ref._h, qry._h if qry is not None else None, kmers,
+                                                     random_tbl, n_clu, flags, q_begin, q_end, *test, e, r, cc, ne, nf),
+                  edges, c, n_edges, n_failed)
+    edges = _edges_dev(launch, dev, cap)
+    return edges, rows_of["rows"][:edges.shape[0]], n_failed
+
+
+def dist_edges_rows(ref, qry=None, kmers=None, random_tbl=None, random_correct=True, slope=2,
+                    x_max=0.0, y_max=0.0, scale=(1.0, 1.0), inclusive=True, q_begin=0, q_end=None,
+                    cap=None):
+    """dist_edges, and with every edge its distances (ppk_dist_edges_rows_dev).  Returns (edges int64
+    [n_edges, 2], rows float32 [n_edges, 2], n_failed): rows[e] is the UNSCALED (core, accessory) of edge e, bit for bit
+    the row `dist` writes for that pair; `scale` only enters the boundary test."""
+    return _fused_edges_rows("ppk_dist_edges_rows_dev", ref, qry, kmers, random_tbl, random_correct, q_begin, q_end,
+                             cap, int(slope), float(x_max), float(y_max), float(scale[0]), float(scale[1]),
+                             1 if inclusive else 0)
+
+
 def _host_edges(name, refs, qrys, kmers, random_tbl, random_correct, cap, *test):
     """The multi-device host edge calls (line boundary / BGMM): one SketchDB per device (or a single one), a host int64
     [m, 2] array, the parked list fetched when `cap` was too small.
@@ -655,6 +698,16 @@ def dist_bgmm_edges(ref, qry=None, kmers=None, random_tbl=None, model=None, rand
         raise ValueError("a prepared BGMM model is needed")
     return _fused_edges("ppk_dist_bgmm_edges_dev", ref, qry, kmers, random_tbl, random_correct, q_begin, q_end, cap,
                         C.byref(model))
+
+
+def dist_bgmm_edges_rows(ref, qry=None, kmers=None, random_tbl=None, model=None, random_correct=True, q_begin=0,
+                         q_end=None, cap=None):
+    """dist_bgmm_edges, and with every edge its (core, accessory) row (ppk_dist_bgmm_edges_rows_dev).  Returns (edges,
+    rows float32 [n_edges, 2], n_failed) as dist_edges_rows."""
+    if model is None:
+        raise ValueError("a prepared BGMM model is needed")
+    return _fused_edges_rows("ppk_dist_bgmm_edges_rows_dev", ref, qry, kmers, random_tbl, random_correct, q_begin,
+                             q_end, cap, C.byref(model))
 
 
 def bgmm_edges_host(refs, qrys=None, kmers=None, random_tbl=None, model=None, random_correct=True, cap=None):
@@ -1489,11 +1542,55 @@ def edge_weights_from_sketches(ref, qry, kmers, random_tbl, edges_t, weights_typ
     if weights_type not in WEIGHTS_TYPES:
         raise ValueError("weights_type must be one of %s" % sorted(WEIGHTS_TYPES))
     d, _ = dist_pairs(ref, qry, kmers, random_tbl, edges_t, random_correct=random_correct, int_offset=int_offset)
+    return edge_weights_of_rows(d, weights_type)
+
+
+def edge_weights_of_rows(rows_t, weights_type="core"):
+    """process_weights of edges whose (core, accessory) rows are at hand -- the rows of dist_edges_rows, or of
+    dist_pairs: float32 [m], the column for "core" / "accessory", the row norms for "euclidean".  What
+    edge_weights_from_sketches returns for those edges, bit for bit, with no further pass over the sketches."""
+    torch = _torch()
+    if weights_type not in WEIGHTS_TYPES:
+        raise ValueError("weights_type must be one of %s" % sorted(WEIGHTS_TYPES))
+    _check_tensor(rows_t, "rows must be a contiguous float32 [m, 2] CUDA tensor", torch.float32, shape=(None, 2))
+    d = rows_t
     if weights_type != "euclidean":
         return d[:, WEIGHTS_TYPES[weights_type]].contiguous()
     w = torch.empty(max(d.shape[0], 1), dtype=torch.float32, device=d.device)
     _dev_call("ppk_row_norms_dev", d.device, d, d.shape[0], w)
     return w[:d.shape[0]]
+
+
+def sweep_boundaries_1d(offsets, slope, x0, y0, x1, y1):
+    """The boundaries of a 1-D sweep (ppk_sweep_boundaries_1d; no device): (x_max, y_max) float32 [n_off] of the sorted
+    offsets along (x0, y0) -> (x1, y1), the values thresholdIterate1D computes (src/boundary.cpp:161-186)."""
+    off = np.ascontiguousarray(offsets, dtype=np.float64)
+    x_max = np.empty(off.size, dtype=np.float32)
+    y_max = np.empty(off.size, dtype=np.float32)
+    _lib.call("ppk_sweep_boundaries_1d", off.ctypes.data_as(C.POINTER(C.c_double)), off.size, int(slope), float(x0),
+              float(y0), float(x1), float(y1), x_max.ctypes.data_as(C.POINTER(C.c_float)),
+              y_max.ctypes.data_as(C.POINTER(C.c_float)))
+    return x_max, y_max
+
+
+def sweep_levels_dev(rows_t, x_max, y_max, slope, out=None):
+    """The sweep level of listed rows (ppk_sweep_levels_dev): int32 [m], for row p of the float32 [m, 2] CUDA tensor
+    the first of the boundaries (x_max[o], y_max[o]) (host arrays) that holds it -- the offset index
+    threshold_iterate_1d_dev / _2d_dev give a row with those coordinates -- and len(x_max) where none does."""
+    torch = _torch()
+    if not (rows_t.is_cuda and rows_t.dtype == torch.float32 and rows_t.dim() == 2 and rows_t.shape[1] == 2
+            and rows_t.is_contiguous()):
+        raise TypeError("rows must be a contiguous float32 [m, 2] CUDA tensor")
+    x_max = np.ascontiguousarray(x_max, dtype=np.float32)
+    y_max = np.ascontiguousarray(y_max, dtype=np.float32)
+    if x_max.ndim != 1 or x_max.shape != y_max.shape:
+        raise ValueError("x_max and y_max must be 1-D arrays of one length")
+    m = int(rows_t.shape[0])
+    if out is None:
+        out = torch.empty(m, dtype=torch.int32, device=rows_t.device)
+    _dev_call("ppk_sweep_levels_dev", rows_t.device, rows_t, m, x_max.ctypes.data_as(C.POINTER(C.c_float)),
+              y_max.ctypes.data_as(C.POINTER(C.c_float)), x_max.size, int(slope), out)
+    return out
 
 
 NJ_SQUARE, NJ_LONG = 0, 1
@@ -1611,8 +1708,12 @@ def _samples_of(n_rows):
 
 
 def _sweep_scores(dist_t, sweep, n_off, score_idx=0, betweenness_sample=None, seed=0):
+    return _sweep_scores_of(_samples_of(dist_t.shape[0]), sweep, n_off, score_idx, betweenness_sample, seed)
+
+
+def _sweep_scores_of(n, sweep, n_off, score_idx=0, betweenness_sample=None, seed=0):
+    """(stats, growNetwork's list) of a sweep's (i, j, offset index) over n samples, the edges in any order."""
     from . import refine
-    n = _samples_of(dist_t.shape[0])
     i, j, o = sweep
     if score_idx == 0:
         stats, _ = network_sweep_dev(i, j, o, n, n_off)

@@ -254,17 +254,75 @@ class RefineBoundary:
         return poppunk_refine.generateTuples(y, self.within_label, self=self_comparison,
                                              num_ref=num_ref, int_offset=int_offset)
 
-    def edges_from_sketches(self, db, qry_db, kmers, random_tbl, slope=None, **kw):
+    def edges_from_sketches(self, db, qry_db, kmers, random_tbl, slope=None, return_rows=False, **kw):
         """CUDA int64 [n_edges, 2]: (i, j) of every pair strictly within the boundary, in the
-        order generateTuples would emit them."""
+        order generateTuples would emit them; and n_failed.  return_rows: (edges, rows, n_failed), rows float32
+        [n_edges, 2] the unscaled (core, accessory) of every edge from the same pass (engine.dist_edges_rows)."""
         if not self.fitted:
             raise RuntimeError("Trying to assign using an unfitted model")
         if slope is None:
             slope = self.slope
         x_max, y_max = self._line(slope)
-        return engine.dist_edges(db, qry_db, kmers, random_tbl, slope=slope, x_max=float(x_max),
-                                 y_max=float(y_max), scale=tuple(float(v) for v in self.scale),
-                                 inclusive=False, **kw)
+        call = engine.dist_edges_rows if return_rows else engine.dist_edges
+        return call(db, qry_db, kmers, random_tbl, slope=slope, x_max=float(x_max),
+                    y_max=float(y_max), scale=tuple(float(v) for v in self.scale),
+                    inclusive=False, **kw)
+
+    def fit_from_sketches(self, db, kmers, random_tbl, sample_names, model, max_move, min_move, startFile=None,
+                          indiv_refine=None, unconstrained=False, score_idx=0, no_local=False, betweenness_sample=100,
+                          sample_size=None, use_gpu=False, outPrefix=None, sampled_betweenness=False, seed=0,
+                          random_correct=True):
+        """fit_dev without the [n_pairs, 2] matrix: refine.refineFit driven by a refine.SketchScorer
+        on the resident sketches of `db` (a self job), the same searches, evaluations and attributes as fit_dev on
+        engine.dist(db, ...).  No assignment vector exists without the matrix: returns
+        self.edges_from_sketches(db, None, kmers, random_tbl) -- (edges, n_failed), the edges fit_dev's assignment gives
+        through generateTuples.  Clusters at several boundaries (multi_boundary) need the matrix route."""
+        import sys
+        from . import refine
+        if sample_size is not None:
+            raise NotImplementedError("RefineBoundary.fit: random vertex subsampling (sample_size) is not mirrored")
+        self.scale = np.asarray(np.copy(model.scale), dtype=np.float32).reshape(2)
+        self.max_move, self.min_move = max_move, min_move
+        self.unconstrained = unconstrained
+        self.mean0, self.mean1 = self._start_points(model, startFile)
+
+        scorer = refine.SketchScorer(db, kmers, random_tbl, self.scale, random_correct=random_correct)
+        if unconstrained:
+            # the far corner of the 20 x 20 grid, as refineFit sets it up: one list for every row of the grid
+            from .utils import decisionBoundary
+            gradient = (self.mean1[1] - self.mean0[1]) / (self.mean1[0] - self.mean0[0])
+            scorer.prime(2, *decisionBoundary(self.mean1, gradient, adj=max_move))
+        common = dict(score_idx=score_idx, no_local=no_local, num_processes=self.threads,
+                      betweenness_sample=betweenness_sample, sample_size=sample_size, use_gpu=use_gpu,
+                      sampled_betweenness=sampled_betweenness, seed=seed)
+        self.optimal_x, self.optimal_y, self.optimal_s = refine.refineFit(
+            scorer, sample_names, self.mean0, self.mean1, self.scale, max_move, min_move, slope=2,
+            unconstrained=unconstrained, **common)
+        self.slope = 2
+        self.fitted = True
+        self.threshold = False
+        self.indiv_fitted = False
+        self.core_boundary = self.optimal_x
+        self.accessory_boundary = self.optimal_y
+        if indiv_refine is not None:
+            try:
+                for dist_type, slope in zip(['core', 'accessory'], [0, 1]):
+                    if indiv_refine == 'both' or indiv_refine == dist_type:
+                        sys.stderr.write("Refining " + dist_type + " distances separately\n")
+                        core_boundary, accessory_boundary, _ = refine.refineFit(
+                            scorer, sample_names, self.mean0, self.mean1, self.scale, max_move, min_move, slope=slope,
+                            **common)
+                        if dist_type == "core":
+                            self.core_boundary = core_boundary
+                        if dist_type == "accessory":
+                            self.accessory_boundary = accessory_boundary
+                self.indiv_fitted = True
+            except RuntimeError as e:
+                print(e)
+                sys.stderr.write("Could not separately refine core and accessory boundaries. "
+                                 "Using joint 2D refinement only.\n")
+        self.fit_passes = scorer.passes
+        return self.edges_from_sketches(db, None, kmers, random_tbl, random_correct=random_correct)
 
 
 # ---- BGMM assignment (PopPUNK's default --fit-model bgmm) -----------------------------------------------
@@ -542,10 +600,13 @@ class BGMMModel:
         return poppunk_refine.generateTuples(y, self.within_label, self=self_comparison, num_ref=num_ref,
                                              int_offset=int_offset)
 
-    def edges_from_sketches(self, db, qry_db, kmers, random_tbl, **kw):
-        """CUDA int64 [n_edges, 2]: the pairs assigned within_label, in generateTuples order; and n_failed."""
+    def edges_from_sketches(self, db, qry_db, kmers, random_tbl, return_rows=False, **kw):
+        """CUDA int64 [n_edges, 2]: the pairs assigned within_label, in generateTuples order; and n_failed.
+        return_rows: (edges, rows, n_failed), rows float32 [n_edges, 2] the (core, accessory) of every edge from the
+        same pass (engine.dist_bgmm_edges_rows)."""
         self._check()
-        return engine.dist_bgmm_edges(db, qry_db, kmers, random_tbl, model=self._model, **kw)
+        call = engine.dist_bgmm_edges_rows if return_rows else engine.dist_bgmm_edges
+        return call(db, qry_db, kmers, random_tbl, model=self._model, **kw)
 
     def edges_host(self, refs, qrys, kmers, random_tbl, **kw):
         """The same as a host int64 [m, 2] array over every device holding a copy of the database; and n_failed."""

@@ -288,6 +288,154 @@ class DeviceScorer:
         return self.engine.RefineLocal.create(self.dist_t, slope, lo[0], lo[1], hi[0], hi[1])
 
 
+class _SketchBracket:
+    """SketchScorer.bracket's handle: the counts of any line between two nested lines, from the candidates of the
+    upper one.  split = (rows within the lower line, further rows within the upper one, the rest), exact counts (the
+    matrix route's handle sorts with a margin; nothing reads the numbers but last_fit)."""
+
+    def __init__(self, scorer, slope, lo, hi):
+        self.scorer, self.slope = scorer, slope
+        self.edges, self.rows = scorer._candidates(slope, [hi[0]], [hi[1]])
+        eng = scorer.engine
+        within_hi = int((eng.assign_threshold_dev(self.rows, slope, hi[0], hi[1]) <= 0).sum().item())
+        within_lo = int((eng.assign_threshold_dev(self.rows, slope, lo[0], lo[1]) <= 0).sum().item())
+        self.split = (within_lo, within_hi - within_lo, scorer.n_rows - within_hi)
+
+    def eval(self, x_max, y_max):
+        return self.scorer._counts(self.edges, self.rows, self.slope, x_max, y_max)[0]
+
+    def close(self):
+        self.edges = self.rows = None
+
+
+class SketchScorer:
+    """DeviceScorer's interface on a resident engine.SketchDB self job: refineFit without the [n_pairs, 2] matrix
+    (DESIGN.md 3.26).  One fused pass (engine.dist_edges_rows) under an OUTER line yields the candidate pairs with their
+    rows; the exact verdict of every boundary then comes from the sweeps' and assign_threshold_dev's own statements on
+    the candidates' scaled rows (rows / scale in float32, the rule fit_dev applies to the matrix).
+
+    The outer line is a superset filter by construction: the largest x_max and the largest y_max of the request, each
+    pushed out by 2^-10 relatively (a row the float test of a boundary accepts lies within ~2^-20 of its exact line).
+    The last candidate list is kept with its un-inflated outer intercepts: a request whose boundaries all lie inside it
+    (same slope, every x_max and y_max no larger) is served from it.  A request with an intercept that is not positive
+    and finite where its slope reads it (a slope-2 line on an axis takes line_dist's sqrt branch) is not cached: one
+    boundary takes a fused pass under that very line, a sweep a pass that lists every pair."""
+
+    MARGIN = 1.0 + 2.0 ** -10
+
+    def __init__(self, db, kmers, random_tbl, scale, random_correct=True):
+        import torch
+        from . import engine
+        self.engine, self.torch = engine, torch
+        self.db, self.kmers, self.random_tbl, self.random_correct = db, kmers, random_tbl, random_correct
+        self.scale = np.asarray(scale, dtype=np.float32).reshape(2)
+        self.n = int(db.n)
+        self.n_rows = self.n * (self.n - 1) // 2
+        self.bt_sources, self.bt_seed = None, 0
+        self._cache = None            # (slope, x_outer, y_outer, edges, scaled rows)
+        self.passes = 0               # fused passes run so far
+
+    def set_betweenness_sample(self, sources, seed=0):
+        if sources is not None and int(sources) < 1:
+            raise ValueError("betweenness_sample must be >= 1")
+        self.bt_sources, self.bt_seed = (None if sources is None else int(sources)), int(seed)
+
+    # ---- candidates -----------------------------------------------------------------------------------------------
+    def _pass(self, slope, x_max, y_max):
+        edges, rows, _ = self.engine.dist_edges_rows(self.db, None, self.kmers, self.random_tbl,
+                                                     random_correct=self.random_correct, slope=slope, x_max=x_max,
+                                                     y_max=y_max, scale=(float(self.scale[0]), float(self.scale[1])),
+                                                     inclusive=True)
+        self.passes += 1
+        return edges, rows / self.torch.as_tensor(self.scale, device=rows.device)
+
+    def _candidates(self, slope, x_maxes, y_maxes):
+        """(edges int64 [m, 2], scaled rows float32 [m, 2]): every pair some boundary of the request may hold."""
+        xs = np.asarray(x_maxes, dtype=np.float32).ravel()
+        ys = np.asarray(y_maxes, dtype=np.float32).ravel()
+        reads_x, reads_y = slope != 1, slope != 0
+        ok = (not reads_x or bool(np.all(np.isfinite(xs) & (xs > 0)))) and \
+             (not reads_y or bool(np.all(np.isfinite(ys) & (ys > 0))))
+        if not ok:
+            if xs.size == 1:
+                return self._pass(slope, float(xs[0]), float(ys[0]))
+            return self._pass(0, float("inf"), 0.0)          # x - inf <= 0: every pair
+        xo = np.float32(xs.max()) if reads_x else np.float32(0)
+        yo = np.float32(ys.max()) if reads_y else np.float32(0)
+        c = self._cache
+        if c is not None and c[0] == slope and xo <= c[1] and yo <= c[2]:
+            return c[3], c[4]
+        edges, rows = self._pass(slope, float(xo) * self.MARGIN, float(yo) * self.MARGIN)
+        self._cache = (slope, xo, yo, edges, rows)
+        return edges, rows
+
+    def prime(self, slope, x_max, y_max):
+        """Make the candidate list of an outer line now, so that every later request inside it is served from it (a
+        search that works outwards, like the 2-D grid's rows of growing y, would otherwise make a list per step)."""
+        self._candidates(slope, [x_max], [y_max])
+
+    def _counts(self, edges, rows, slope, x_max, y_max, score_idx=0):
+        """(counts int64 [4], betweenness means or None) of one boundary over a candidate list"""
+        eng = self.engine
+        sel = edges[eng.assign_threshold_dev(rows, slope, x_max, y_max) <= 0]
+        if score_idx == 0:
+            level = self.torch.zeros(sel.shape[0], dtype=self.torch.int64, device=sel.device)
+            stats, _ = eng.network_sweep_dev(sel[:, 0], sel[:, 1], level, self.n, 1)
+            return stats.cpu().numpy().reshape(-1, 4)[0], None
+        if self.bt_sources is None:
+            stats, bt, _, _ = eng.network_summary_graph_dev(sel, self.n)
+        else:
+            stats, bt, _, _ = eng.network_summary_sampled_graph_dev(sel, self.n, sources=self.bt_sources,
+                                                                    seed=self.bt_seed)
+        return stats.cpu().numpy(), bt.cpu().numpy()
+
+    def _sweep(self, slope, x_max, y_max, score_idx):
+        edges, rows = self._candidates(slope, x_max, y_max)
+        n_off = int(x_max.size)
+        level = self.engine.sweep_levels_dev(rows, x_max, y_max, slope)
+        keep = level < n_off
+        listed = edges[keep]
+        sweep = (listed[:, 0], listed[:, 1], level[keep].to(self.torch.int64))
+        stats, scores = self.engine._sweep_scores_of(self.n, sweep, n_off, score_idx, self.bt_sources, self.bt_seed)
+        return int(stats[-1, 0].item()), scores
+
+    # ---- DeviceScorer's four methods ------------------------------------------------------------------------------
+    def sweep_1d(self, s_range, slope, mean0, mean1, score_idx):
+        """-> (rows the sweep lists, growNetwork's list)"""
+        x_max, y_max = self.engine.sweep_boundaries_1d(s_range, slope, mean0[0], mean0[1], mean1[0], mean1[1])
+        return self._sweep(slope, x_max, y_max, self.engine._check_score_idx(score_idx))
+
+    def sweep_2d(self, x_range, y_max, score_idx):
+        x_max = np.ascontiguousarray(x_range, dtype=np.float32).ravel()
+        if x_max.size > 1 and np.any(np.diff(x_max) < 0):
+            raise RuntimeError("x_max range to thresholdIterate2D must be sorted")
+        return self._sweep(2, x_max, np.full(x_max.size, y_max, dtype=np.float32),
+                           self.engine._check_score_idx(score_idx))
+
+    def score(self, slope, x_max, y_max, score_idx):
+        """-> (counts int64 [4], betweenness means or None) of one boundary"""
+        x_max, y_max = float(np.float32(x_max)), float(np.float32(y_max))
+        edges, rows = self._candidates(slope, [x_max], [y_max])
+        return self._counts(edges, rows, slope, x_max, y_max, score_idx)
+
+    def bracket(self, slope, lo, hi):
+        """-> an object with eval(x_max, y_max) -> counts and split, or None (the lines are not nested: the rule of
+        ppk_refine_local_create_dev)"""
+        lo = [np.float32(v) for v in lo]
+        hi = [np.float32(v) for v in hi]
+        tiny = np.float32(2.0 ** -40)
+        if slope == 0:
+            nested = lo[0] <= hi[0]
+        elif slope == 1:
+            nested = lo[1] <= hi[1]
+        else:
+            nested = (lo[0] <= hi[0] and lo[1] <= hi[1] and lo[0] >= tiny and lo[1] >= tiny
+                      and bool(np.isfinite(hi[0])) and bool(np.isfinite(hi[1])))
+        if not nested:
+            return None
+        return _SketchBracket(self, slope, [float(v) for v in lo], [float(v) for v in hi])
+
+
 def _scorer_of(distMat, bt_sources=None, seed=0):
     scorer = distMat if hasattr(distMat, "sweep_1d") else DeviceScorer(distMat)
     if hasattr(scorer, "set_betweenness_sample"):
